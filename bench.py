@@ -105,6 +105,9 @@ def parse(argv=None):
     ap.add_argument("--no-phases", action="store_true")
     ap.add_argument("--cpu-iters", type=int, default=5)
     ap.add_argument("--pm-steps", type=int, default=1000, help="C4: Perona-Malik steps (T = steps * 0.25)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what they computed (per image: level set, mask, c1/c2, last norm) as "
+                         "DIR/<name>.npy, float32/float64, at most 64 MB in all (a fixed, seeded sample of the pixels of a large plane)")
     ap.add_argument("--prewarm-ms", type=float, default=150.0,
                     help="device clock warm-up before the W warm-up steps: this many ms of the same kernel on a SCRATCH "
                          "context (own buffers; the measured level sets are not touched). 0 = off")
@@ -198,6 +201,35 @@ def verify_result(name, n, gb, ctx, iterations):
     ok = finite and (not settled or (iou >= 0.999 and dev <= tol_c))
     return ok, {"image": gb, "finite": finite, "mask_iou_vs_disk": iou, "inside_is_disk": bool(inside_is_disk),
                 "max_abs_c_minus_level": float(dev)}
+
+
+DUMP_SAMPLE_PIXELS = 1 << 20    # pixels over ALL images of the job, 12 B each (u float64 + mask float32), + 8 B of index: 20 MiB < 64 MB
+
+
+def dump_outputs(dirpath, n, first_image, total_images, ctxs, res):
+    """What a caller of the timed path receives after its last step, per resident image gb: the level set (u_img<gb>), the mask
+    (mask_img<gb>, 0/1), the region means (c1c2_img<gb>: row 0 c1, row 1 c2, one column per channel) and the norm of the last step
+    (norm_img<gb>).  A plane with more pixels than the image's share of DUMP_SAMPLE_PIXELS is sampled at fixed positions (seed 0,
+    the same for every image and every run, sorted; sample_index.npy holds the flat indices) -- the whole plane otherwise."""
+    import numpy as np
+    os.makedirs(dirpath, exist_ok=True)
+    k = max(1, DUMP_SAMPLE_PIXELS // max(total_images, 1))
+    idx = None
+    if n * n > k:
+        idx = np.sort(np.random.default_rng(0).choice(n * n, size=k, replace=False))
+        if first_image == 0:
+            np.save(os.path.join(dirpath, "sample_index.npy"), idx.astype(np.float64))
+    for b, (ctx, r) in enumerate(zip(ctxs, res)):
+        gb = first_image + b
+        u = ctx.get_levelset()
+        m = ctx.get_mask().astype(np.float32)
+        if idx is not None:
+            u, m = u.ravel()[idx], m.ravel()[idx]
+        c1, c2 = ctx.get_means()
+        arrays = {"u": u.astype(np.float64), "mask": m, "c1c2": np.stack([c1, c2]).astype(np.float64),
+                  "norm": np.array([r[1]], dtype=np.float64)}
+        for key, a in arrays.items():
+            np.save(os.path.join(dirpath, f"{key}_img{gb}.npy"), a)
 
 
 def image_planes(name, n, gb):
@@ -355,6 +387,8 @@ def main():
             checked = checked and ok
         if not checked:     # reported after the collectives below (a rank that left early would hang the others)
             print(f"bench.py: result check FAILED on rank {rank}: {check_info}", file=sys.stderr, flush=True)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, n, rank * images, images * world, ctxs, res)
         launch = ctxs[0].launch_info(0)
         pm_launch = ctxs[0].launch_info(1) if pm_info is not None else None
 
