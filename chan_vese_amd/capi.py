@@ -25,7 +25,7 @@ EXPORTS = [
     "cvh_enqueue_steps", "cvh_warm", "cvh_sync", "cvh_reset_run", "cvh_get_means", "cvh_get_trace",
     "cvh_get_stop_condition", "cvh_get_mask", "cvh_get_contour", "cvh_separate", "cvh_perona_malik",
     "cvh_pm_trip_count", "cvh_last_run_ms", "cvh_last_pm_ms", "cvh_ppf_apply",
-    "cvh_ppf_apply_device", "cvh_version", "cvh_launch_info",
+    "cvh_ppf_apply_device", "cvh_version", "cvh_launch_info", "cvh_enqueue_steps_batch", "cvh_run_batch",
 ]
 
 
@@ -90,6 +90,8 @@ def lib():
         "cvh_ppf_apply_device": (C.c_int, [dp, C.c_long, C.c_int, C.c_double, vp]),
         "cvh_version": (C.c_char_p, []),
         "cvh_launch_info": (C.c_int, [vp, C.c_int, C.c_char_p, C.c_int]),
+        "cvh_enqueue_steps_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int]),
+        "cvh_run_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int, ip, dp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -142,6 +144,32 @@ def ppf_apply(data, op, eps=1.0, start=0, end=None, device=0):
     if rc != CVH_OK:
         raise CvhError(rc, lib().cvh_last_error(None).decode())
     return data
+
+
+def _member_array(contexts):
+    hs = [c._h.value for c in contexts]
+    return (C.c_void_p * max(len(hs), 1))(*hs)
+
+
+def enqueue_steps_batch(contexts, n):
+    """Fused batch (cvh_enqueue_steps_batch): enqueues n iterations of every context with one launch per iteration and
+    CSV-step instantiation; follow with sync() on each context, as after Context.enqueue_steps."""
+    contexts = list(contexts)
+    rc = lib().cvh_enqueue_steps_batch(_member_array(contexts), len(contexts), int(n))
+    if rc != CVH_OK:
+        raise CvhError(rc, lib().cvh_last_error(None).decode())
+
+
+def run_batch(contexts, max_steps=-1):
+    """Fused batch (cvh_run_batch): Context.run for every context at once, each with its own stop rule.
+    Returns [(steps_done, last_norm)] per context."""
+    contexts = list(contexts)
+    n = len(contexts)
+    done, nrm = (C.c_int * max(n, 1))(), (C.c_double * max(n, 1))()
+    rc = lib().cvh_run_batch(_member_array(contexts), n, int(max_steps), done, nrm)
+    if rc != CVH_OK:
+        raise CvhError(rc, lib().cvh_last_error(None).decode())
+    return [(done[i], nrm[i]) for i in range(n)]
 
 
 class Context:

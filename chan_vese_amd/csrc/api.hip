@@ -9,12 +9,14 @@
 
 #include <algorithm>
 #include <mutex>
+#include <string>
 #include <vector>
 
 #include "cvh_internal.h"
 
 constexpr int kGraphSteps = 16;   // steps per captured graph (even: the ping-pong parity repeats)
 struct StepGraph { hipGraphExec_t exec = nullptr; CvhStepArgs key[4]; int kind = -1, flavour = -1; };
+struct BatchCache;   // the device tables of a fused batch whose first member this context is (cvh_enqueue_steps_batch)
 
 struct cvh_context {
   int h = 0, w = 0, C = 0, device = 0;
@@ -74,6 +76,12 @@ struct cvh_context {
   int chain_pb = 0;             // sum set that belongs to the level set at run-counter 0
   bool chain_pending = false;   // chain launches enqueued since the last flush
   bool chain_acc_valid = false; // the fixed-point sets hold the sums of the current level set
+  int pending_nparts = 0;       // workgroup rows of sum u_diff^2 the pending iteration left (> 0: a per-launch wave kernel's, which the
+                                // next launch on the same grid or the flush kernel books; 0: a resident launch's, booked inside it)
+  int last_nparts = 0;          // workgroups (without the bookkeeper) of the last per-launch wave launch, own or fused (cvh_debug_read)
+  int geom_cus = 0;             // > 0: the CUs the automatic strip count is sized for (a fused batch: this context's share of the chip)
+  BatchCache *batch = nullptr;  // fused batches led by this context: per-member launch arguments of the four phases, workgroup map
+  hipEvent_t ev_join = nullptr; // fused batch: joins this context's stream with the leader's
   // resident kernel (csv_resident_kernel.hip): cache-resident planes iterate in LDS, one cooperative launch per chunk
   CvhResident *d_resident = nullptr;
   double *d_res_halo = nullptr;
@@ -214,6 +222,8 @@ static double live_footprint(const cvh_context *c)
   return sum;
 }
 
+static void batch_cache_free(cvh_context *c);
+
 extern "C" void cvh_destroy(cvh_context *c)
 {
   if (!c) return;
@@ -246,6 +256,8 @@ extern "C" void cvh_destroy(cvh_context *c)
   if (c->h_status) (void)hipHostFree(c->h_status);
   if (c->d_isums) (void)hipFree(c->d_isums);
   if (c->h_isums) (void)hipHostFree(c->h_isums);
+  batch_cache_free(c);
+  if (c->ev_join) (void)hipEventDestroy(c->ev_join);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
   for (int k = 0; k < 4; ++k) if (c->evp[k]) (void)hipEventDestroy(c->evp[k]);
@@ -705,6 +717,7 @@ static Geometry resolve_geometry(const cvh_context *c)
 {
   Geometry g;
   g.strip = 0;
+  const int cus = c->geom_cus > 0 ? c->geom_cus : c->num_cus;   // what the automatic strip count fills (a fused batch: a share)
   // default: the wave kernel (any width; fastest measured); it addresses the level set through
   // buffer instructions with 32-bit byte offsets and marks dropped lanes with offset 2^31, so
   // images of 2^28 pixels (2 GiB of level set) or more use the tile kernel
@@ -725,14 +738,14 @@ static Geometry resolve_geometry(const cvh_context *c)
     int sr = c->strip_rows, small_exact = 0;
     if (sr <= 0) {
       const int occ = use_fast(c) ? (c->wave_minw == 4 ? 4 : 3) : 2;   // as compiled: cvh_launch_wave2
-      int nstrips = 2 * ((c->num_cus * occ) / nbc);
+      int nstrips = 2 * ((cus * occ) / nbc);
       // small planes (a full round would mean strips of < 13 rows: 3 halo rows and a pipeline fill each): ~1.8 workgroups
       // per CU instead -- measured at 2048^2: 16 rows 23.2, 18 rows 24.1, 20 rows 21.4, 22 rows 22.7, 24 rows 22.8 us
       // (round 3, exact strip counts at 2048^2, one context: 56 strips 22.8 us, 84 21.2, 100 21.1, 104 20.8, 108 21.2, 112 20.7, 114 22.1 --
       // one workgroup more than two per CU --, 128 21.4, 140 21.1, 168 21.6: flat from 84 to 168 except just above a multiple of the CU
       // count; TWO workgroups per CU, never more)
       bool exact = false;
-      if (nstrips > 160) { nstrips = 2 * ((2 * c->num_cus) / nbc); if (nstrips < 2) nstrips = 2; exact = true; }
+      if (nstrips > 160) { nstrips = 2 * ((2 * cus) / nbc); if (nstrips < 2) nstrips = 2; exact = true; }
       if (nstrips < 1) nstrips = 1;
       sr = (c->h + nstrips - 1) / nstrips;
       if (sr < 8) { sr = 8; exact = false; }
@@ -758,7 +771,7 @@ static Geometry resolve_geometry(const cvh_context *c)
     if (sr <= 0) {
       // waves per SIMD the kernel flavour is compiled for (csv_wave_kernel.hip, launch_wave_c)
       const int occ = use_fast(c) ? (c->C == 3 ? 3 : c->wave_minw) : (c->C == 3 ? 2 : 3);
-      int nstrips = (c->num_cus * occ) / ((g.tiles_x + 3) / 4);
+      int nstrips = (cus * occ) / ((g.tiles_x + 3) / 4);
       // Every strip re-reads 3 halo rows and fills its pipeline once: measured on MI355X (512^2 ..
       // 4096^2, tools/size_sweep.sh) a full round of resident waves is best at 4096^2 (75 strips) and
       // 64 strips wherever residency would allow many more (smaller images).
@@ -1128,8 +1141,9 @@ static int launch_one_step(cvh_context *c, int in_buf, int step, bool capturing 
   if (note) return CVH_OK;
   if (c->finalize_mode == 1) HIPCHK(c, cvh_launch_finalize(a, c->C, 0, c->stream));
   if (!capturing) {
-    if (a.chain) c->chain_pending = true;
+    if (a.chain) { c->chain_pending = true; c->pending_nparts = a.nparts; }
     else c->chain_acc_valid = false;   // the means now live in the state block only
+    c->last_nparts = a.nparts;
   }
   return CVH_OK;
 }
@@ -1142,8 +1156,19 @@ static int chain_flush(cvh_context *c)
   CvhStepArgs a;
   fill_args(c, &a, 0, 0);
   if (!a.chain) return fail(c, CVH_ERR_STATE, "chain-mode launches are pending but the context no longer selects chain mode");
+  if (c->pending_nparts > 0) a.nparts = c->pending_nparts;   // the rows the pending launch left (a fused batch's grid may differ)
   HIPCHK(c, cvh_launch_chain_flush(a, c->C, c->stream));
   c->chain_pending = false;
+  return CVH_OK;
+}
+
+// The pending iteration of a per-launch wave kernel is booked by the next launch's bookkeeper only if that launch runs on the same
+// grid (its rows of sum u_diff^2 are read by workgroup count); before anything else -- a resident launch (nparts < 0), which never
+// books it (it used to lose that iteration's norm, trace row and stop test), or a grid of another size (a fused batch's share of the
+// chip, a context's own grid after one) -- the flush kernel books it, exactly as a cvh_sync in between would.
+static int flush_for_grid(cvh_context *c, int nparts)
+{
+  if (c->chain_pending && c->pending_nparts > 0 && c->pending_nparts != nparts) return chain_flush(c);
   return CVH_OK;
 }
 
@@ -1222,6 +1247,7 @@ static int launch_resident(cvh_context *c, const ResidentGeom &rg, int nsteps, C
 {
   const int ntiles = rg.tr * rg.tc;
   if (!note) { const int rc = ensure_resident_buffers(c); if (rc != CVH_OK) return rc; }
+  if (!note) { const int rc = flush_for_grid(c, -1); if (rc != CVH_OK) return rc; }
   constexpr int kMaxPerLaunch = 4096;
   for (int s = 0; s < nsteps || note;) {
     const int n = nsteps - s < kMaxPerLaunch ? nsteps - s : kMaxPerLaunch;
@@ -1243,6 +1269,8 @@ static int launch_resident(cvh_context *c, const ResidentGeom &rg, int nsteps, C
     HIPCHK(c, hipMemsetAsync(c->d_resident, 0, sizeof(CvhResident), c->stream));
     HIPCHK(c, cvh_launch_resident(a, c->stream));
     c->chain_pending = true;       // the flush kernel writes c1 / c2 of the final level set into the state block at the next sync
+    c->pending_nparts = 0;
+    c->last_nparts = 0;
     c->resident_used = true;
     c->enqueued += n;
     s += n;
@@ -1259,6 +1287,8 @@ static int enqueue_impl(cvh_context *c, int nsteps)
     if (resident_geometry(c, &rg)) return launch_resident(c, rg, nsteps, nullptr);
     const Geometry g = resolve_geometry(c);
     if (g.strip >= 2) { const int rc = upload_strip_bounds(c, g); if (rc != CVH_OK) return rc; }
+    const int rc = flush_for_grid(c, g.nblocks);
+    if (rc != CVH_OK) return rc;
   }
   // The odd-sized part goes FIRST as plain launches: from an idle stream they reach the GPU within 3-5 us, while the first
   // hipGraph replay takes 10-16 us; the graphs (runs of kGraphSteps) follow.  warm_impl() builds the graph for that position.
@@ -1275,7 +1305,8 @@ static int enqueue_impl(cvh_context *c, int nsteps)
     if (rc != CVH_OK) return rc;
     const StepGraph &sg = c->graphs[(c->chain_pb + c->enqueued) & 3];
     HIPCHK(c, hipGraphLaunch(sg.exec, c->stream));
-    if (sg.key[0].chain) c->chain_pending = true; else c->chain_acc_valid = false;
+    if (sg.key[0].chain) { c->chain_pending = true; c->pending_nparts = sg.key[0].nparts; } else c->chain_acc_valid = false;
+    c->last_nparts = sg.key[0].nparts;
     c->enqueued += kGraphSteps;
     s += kGraphSteps;
   }
@@ -1403,6 +1434,306 @@ extern "C" int cvh_run(cvh_context *c, int max_steps, int *steps_done, double *l
   c->enqueued = c->steps_done;
   if (steps_done) *steps_done = c->h_state[0].steps_done;
   if (last_norm) *last_norm = c->h_state[0].norm;
+  return CVH_OK;
+}
+
+// ---- fused batch: N contexts advance together, one launch per iteration and CSV-step instantiation ----
+// The grid of a group is the concatenation of its members' own grids (nparts workgroups + the chain-mode bookkeeper), each padded to a
+// multiple of 8 workgroups (CvhBatchArgs, cvh_internal.h).  A member's launch arguments differ between its iterations only with period 4
+// (ping-pong parity x chain-mode sum set, see ensure_step_graph): the four phases of every member are uploaded once, when the batch's
+// composition or a member's arguments change, and an iteration's launch passes two pointers.
+struct BatchGroup {
+  CvhStepArgs rep;          // the first member's arguments: select the instantiation (every member of the group has the same)
+  int kind = 0, C = 1, fast = 0;
+  int n = 0;                // members
+  unsigned grid = 0;        // workgroups, padding included
+  size_t args_off = 0, map_off = 0;   // byte offsets in BatchCache::d: [4][n] CvhStepArgs, grid / 8 CvhBatchEntry
+};
+struct BatchCache {
+  std::vector<cvh_context *> members;
+  std::vector<unsigned char> image;   // what d holds
+  std::vector<BatchGroup> groups;
+  void *d = nullptr;
+  size_t cap = 0;
+  int rot = 0;                        // phase of the tables an enqueue starts at
+};
+
+static void batch_cache_free(cvh_context *c)
+{
+  if (!c->batch) return;
+  if (c->batch->d) (void)hipFree(c->batch->d);
+  delete c->batch;
+  c->batch = nullptr;
+}
+
+// batch errors: the message goes to member 0 (if there is one) and to cvh_last_error(NULL)
+static int batch_fail(cvh_context *const *ctxs, int n, int code, const char *fmt, ...)
+{
+  char msg[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(msg, sizeof(msg), fmt, ap);
+  va_end(ap);
+  snprintf(g_create_err, sizeof(g_create_err), "%s", msg);
+  if (ctxs && n >= 1 && ctxs[0]) snprintf(ctxs[0]->err, sizeof(ctxs[0]->err), "%s", msg);
+  return code;
+}
+
+// What can be refused before anything is enqueued (the members stay as they were).
+static int batch_check(cvh_context *const *ctxs, int n)
+{
+  if (!ctxs || n < 1) return batch_fail(ctxs, 0, CVH_ERR_ARG, "batch: empty member list (ctxs = %p, n = %d)", (const void *)ctxs, n);
+  for (int i = 0; i < n; ++i) {
+    cvh_context *c = ctxs[i];
+    if (!c) return batch_fail(ctxs, i ? n : 0, CVH_ERR_ARG, "batch: member %d is NULL", i);
+    for (int j = 0; j < i; ++j)
+      if (ctxs[j] == c) return batch_fail(ctxs, n, CVH_ERR_ARG, "batch: member %d duplicates member %d", i, j);
+    if (c->device != ctxs[0]->device)
+      return batch_fail(ctxs, n, CVH_ERR_ARG, "batch: member %d is on device %d, member 0 on device %d", i, c->device, ctxs[0]->device);
+    if (!c->have_image) return batch_fail(ctxs, n, CVH_ERR_STATE, "batch: member %d has no image (call cvh_set_image first)", i);
+    if (!c->have_u) return batch_fail(ctxs, n, CVH_ERR_STATE, "batch: member %d has no level set (call cvh_set_levelset or cvh_init_checkerboard first)", i);
+    if (c->finalize_mode != 0) return batch_fail(ctxs, n, CVH_ERR_ARG, "batch: member %d has finalize = 1 (a separate finalise kernel per launch): no fused batch", i);
+    const Geometry g = resolve_geometry(c);
+    if (g.strip < 2) return batch_fail(ctxs, n, CVH_ERR_ARG, "batch: member %d (%d x %d) takes the tile kernel: no fused batch", i, c->h, c->w);
+  }
+  return CVH_OK;
+}
+
+// Automatic geometry of a member: its strips are sized for its share of the chip, num_cus x n_i / sum n (an explicit strip_rows / strips wins)
+// -- where its own full-chip strips are short.  The share exists to lengthen strips that the whole-chip grid makes short (every strip re-reads
+// 3 halo rows and fills its pipeline once): 8 x 1024^2 4.9 against 6.7 us per image-iteration with the full-chip strips of 8 rows.  Where the
+// member's own strips already have kBatchOwnRows rows or more, the share only coarsens its grid into one round of long strips whose
+// workgroup count does not divide the CUs (8 x 4096^2: 680 workgroups of 410-row strips, CUs with 2 and with 3 of them, the 2-workgroup
+// CUs idle for the last third of the launch -- profiles/r05_fused_batch/timeline_*): such a member keeps its own geometry.
+constexpr int kBatchOwnRows = 32;
+static void batch_share(cvh_context *const *ctxs, int n, bool on)
+{
+  double tot = 0.0;
+  for (int i = 0; i < n; ++i) tot += (double)ctxs[i]->n;
+  for (int i = 0; i < n; ++i) {
+    cvh_context *c = ctxs[i];
+    c->geom_cus = 0;
+    if (!on || resolve_geometry(c).strip_rows >= kBatchOwnRows) continue;
+    const int share = (int)((double)c->num_cus * (double)c->n / tot + 0.5);
+    c->geom_cus = share < 1 ? 1 : share;
+  }
+}
+
+// Per enqueue: host work of every member (stop condition, strip table), its pending iteration booked if the batch's grid differs from
+// the one that left it, its initial sums; then the tables (uploaded only when they changed).  geom_cus is set by the caller.
+static int batch_prepare(cvh_context *const *ctxs, int n)
+{
+  for (int i = 0; i < n; ++i) {
+    cvh_context *c = ctxs[i];
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = prepare_host(c);
+    if (rc != CVH_OK) return batch_fail(ctxs, n, rc, "batch: member %d: %s", i, c->err);
+    const Geometry g = resolve_geometry(c);
+    rc = upload_strip_bounds(c, g);
+    if (rc == CVH_OK) rc = flush_for_grid(c, g.nblocks);
+    if (rc == CVH_OK) rc = prepare(c);
+    if (rc != CVH_OK) return batch_fail(ctxs, n, rc, "batch: member %d: %s", i, c->err);
+    if (!c->ev_join) HIPCHK(c, hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
+  }
+  cvh_context *lead = ctxs[0];
+  // group the members by CSV-step instantiation (the name cvh_launch_info reports) and dynamic LDS
+  std::vector<BatchGroup> groups;
+  std::vector<std::string> names;
+  std::vector<int> member_group((size_t)n), local((size_t)n);
+  std::vector<unsigned> blocks((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    cvh_context *c = ctxs[i];
+    CvhLaunchNote note{};
+    const int rc = launch_one_step(c, (c->cur_base + c->enqueued) & 1, c->enqueued, false, &note);
+    if (rc != CVH_OK) return batch_fail(ctxs, n, rc, "batch: member %d: %s", i, c->err);
+    char key[160];
+    snprintf(key, sizeof(key), "%s lds=%u", note.name, note.lds);
+    int gi = 0;
+    while (gi < (int)names.size() && names[gi] != key) ++gi;
+    if (gi == (int)names.size()) {
+      names.push_back(key);
+      BatchGroup bg;
+      fill_args(c, &bg.rep, (c->cur_base + c->enqueued) & 1, c->enqueued);
+      bg.kind = resolve_geometry(c).strip; bg.C = c->C; bg.fast = use_fast(c) ? 1 : 0;
+      groups.push_back(bg);
+    }
+    member_group[i] = gi;
+    local[i] = groups[gi].n++;
+    blocks[i] = note.grid;
+  }
+  // the image: per group [4][n] arguments, then the workgroup map
+  std::vector<unsigned char> img;
+  auto align = [&]() { img.resize((img.size() + 255) & ~(size_t)255); };
+  for (size_t gi = 0; gi < groups.size(); ++gi) {
+    BatchGroup &bg = groups[gi];
+    align();
+    bg.args_off = img.size();
+    img.resize(img.size() + (size_t)4 * bg.n * sizeof(CvhStepArgs));
+    for (int i = 0; i < n; ++i) {
+      if (member_group[i] != (int)gi) continue;
+      cvh_context *c = ctxs[i];
+      for (int q = 0; q < 4; ++q) {
+        CvhStepArgs a;
+        fill_args(c, &a, (c->cur_base + c->enqueued + q) & 1, c->enqueued + q);
+        memcpy(img.data() + bg.args_off + ((size_t)q * bg.n + local[i]) * sizeof(CvhStepArgs), &a, sizeof(a));
+      }
+    }
+    align();
+    bg.map_off = img.size();
+    unsigned first = 0;
+    for (int i = 0; i < n; ++i) {
+      if (member_group[i] != (int)gi) continue;
+      const unsigned len = (blocks[i] + 7) & ~7u;
+      for (unsigned j = 0; j < len; j += 8) {
+        const CvhBatchEntry e = {(unsigned)local[i], first, blocks[i], 0u};
+        img.insert(img.end(), (const unsigned char *)&e, (const unsigned char *)&e + sizeof(e));
+      }
+      first += len;
+    }
+    bg.grid = first;
+  }
+  // the tables of an enqueue that starts r phases later are the cached ones rotated by r (members advance together)
+  BatchCache *bc = lead->batch;
+  bool same_members = bc && bc->members.size() == (size_t)n && !memcmp(bc->members.data(), ctxs, (size_t)n * sizeof(cvh_context *));
+  if (same_members && bc->image.size() == img.size() && bc->groups.size() == groups.size()) {
+    for (int r = 0; r < 4; ++r) {
+      bool eq = true;
+      for (size_t gi = 0; gi < groups.size() && eq; ++gi) {
+        const BatchGroup &bg = groups[gi], &old = bc->groups[gi];
+        eq = bg.args_off == old.args_off && bg.map_off == old.map_off && bg.n == old.n && bg.grid == old.grid;
+        const size_t row = (size_t)bg.n * sizeof(CvhStepArgs);
+        for (int q = 0; q < 4 && eq; ++q)
+          eq = !memcmp(img.data() + bg.args_off + (size_t)q * row, bc->image.data() + old.args_off + (size_t)((q + r) & 3) * row, row);
+        if (eq) eq = !memcmp(img.data() + bg.map_off, bc->image.data() + old.map_off, (size_t)bg.grid / 8 * sizeof(CvhBatchEntry));
+      }
+      if (eq) { bc->rot = r; return CVH_OK; }
+    }
+  }
+  if (!bc) { bc = lead->batch = new (std::nothrow) BatchCache(); if (!bc) return batch_fail(ctxs, n, CVH_ERR_NOMEM, "batch: out of host memory"); }
+  HIPCHK(lead, hipStreamSynchronize(lead->stream));   // launches already enqueued read the old tables
+  if (bc->cap < img.size()) {
+    if (bc->d) (void)hipFree(bc->d);
+    bc->d = nullptr; bc->cap = 0;
+    HIPCHK(lead, hipMalloc(&bc->d, img.size()));
+    bc->cap = img.size();
+  }
+  HIPCHK(lead, hipMemcpy(bc->d, img.data(), img.size(), hipMemcpyHostToDevice));
+  bc->members.assign(ctxs, ctxs + n);
+  bc->image.swap(img);
+  bc->groups = groups;
+  bc->rot = 0;
+  return CVH_OK;
+}
+
+// nsteps fused iterations on the leader's stream (joined with every member's stream before, and they with it after)
+static int batch_launch(cvh_context *const *ctxs, int n, int nsteps)
+{
+  cvh_context *lead = ctxs[0];
+  BatchCache *bc = lead->batch;
+  for (int i = 1; i < n; ++i) {
+    HIPCHK(ctxs[i], hipEventRecord(ctxs[i]->ev_join, ctxs[i]->stream));
+    HIPCHK(lead, hipStreamWaitEvent(lead->stream, ctxs[i]->ev_join, 0));
+  }
+  for (int i = 0; i < n; ++i) {
+    cvh_context *c = ctxs[i];
+    if (!c->timing_open) { HIPCHK(c, hipEventRecord(c->ev0, lead->stream)); c->timing_open = true; }
+  }
+  const unsigned char *d = (const unsigned char *)bc->d;
+  for (int t = 0; t < nsteps; ++t) {
+    const int q = (t + bc->rot) & 3;
+    for (const BatchGroup &bg : bc->groups) {
+      CvhBatchLaunch bl;
+      bl.k.map = (const CvhBatchEntry *)(d + bg.map_off);
+      bl.k.args = (const CvhStepArgs *)(d + bg.args_off) + (size_t)q * bg.n;
+      bl.grid = bg.grid;
+      if (bg.kind == 3) HIPCHK(lead, cvh_launch_wave2(bg.rep, bg.C, bg.fast, lead->stream, &bl));
+      else HIPCHK(lead, cvh_launch_wave(bg.rep, bg.C, bg.fast, lead->stream, &bl));
+    }
+  }
+  bc->rot = (bc->rot + nsteps) & 3;
+  HIPCHK(lead, hipEventRecord(lead->ev_join, lead->stream));
+  for (int i = 0; i < n; ++i) {
+    cvh_context *c = ctxs[i];
+    if (i) HIPCHK(c, hipStreamWaitEvent(c->stream, lead->ev_join, 0));
+    if (nsteps > 0) {
+      const Geometry g = resolve_geometry(c);
+      if (use_chain(c, g)) { c->chain_pending = true; c->pending_nparts = g.nblocks; }
+      else c->chain_acc_valid = false;   // the means now live in the state block only
+      c->last_nparts = g.nblocks;
+      if (c->state_bits == 32) c->mirror_valid = false;
+    }
+    c->enqueued += nsteps;
+  }
+  return CVH_OK;
+}
+
+extern "C" int cvh_enqueue_steps_batch(cvh_context *const *ctxs, int n, int nsteps)
+{
+  int rc = batch_check(ctxs, n);
+  if (rc != CVH_OK) return rc;
+  if (nsteps < 0) return batch_fail(ctxs, n, CVH_ERR_ARG, "batch: nsteps = %d", nsteps);
+  HIPCHK(ctxs[0], hipSetDevice(ctxs[0]->device));
+  batch_share(ctxs, n, true);
+  for (int i = 0; i < n; ++i) if (nsteps > 0) ctxs[i]->run_chunk = nsteps;
+  rc = batch_prepare(ctxs, n);
+  if (rc == CVH_OK) rc = batch_launch(ctxs, n, nsteps);
+  batch_share(ctxs, n, false);
+  return rc;
+}
+
+extern "C" int cvh_run_batch(cvh_context *const *ctxs, int n, int max_steps, int *steps_done, double *last_norm)
+{
+  int rc = batch_check(ctxs, n);
+  if (rc != CVH_OK) return rc;
+  cvh_context *lead = ctxs[0];
+  HIPCHK(lead, hipSetDevice(lead->device));
+  for (int i = 0; i < n; ++i) {   // every member starts a new run (settles whatever it has in flight first)
+    rc = reset_run_impl(ctxs[i]);
+    if (rc != CVH_OK) return batch_fail(ctxs, n, rc, "batch: member %d: %s", i, ctxs[i]->err);
+  }
+  long remaining = max_steps < 0 ? (long)INT_MAX : (long)max_steps;   // src/main.cpp:890, per member
+  int chunk_len = INT_MAX;   // the members' pinned status words are polled every sync_every iterations (the smallest of them)
+  for (int i = 0; i < n; ++i) if (ctxs[i]->sync_every < chunk_len) chunk_len = ctxs[i]->sync_every;
+  if (chunk_len < 1) chunk_len = 1;
+  batch_share(ctxs, n, true);
+  for (int i = 0; i < n; ++i) ctxs[i]->run_chunk = chunk_len;
+  rc = batch_prepare(ctxs, n);
+  if (rc == CVH_OK) rc = batch_launch(ctxs, n, 0);   // opens every member's timed interval on the leader's stream
+  // Chunks as in cvh_run: launches queued behind a member's stop are no-ops for it (sticky flag); the run ends when every member has
+  // stopped or max_steps is reached, never more than kAhead chunks in front of the slowest live member.
+  constexpr int kAhead = 4;
+  long queued = 0;
+  while (rc == CVH_OK && remaining > 0) {
+    bool all_stopped = true;
+    for (;;) {
+      long lag = 0;
+      all_stopped = true;
+      for (int i = 0; i < n; ++i) {
+        volatile int *hs = ctxs[i]->h_status;
+        if (hs[1]) continue;
+        all_stopped = false;
+        if (queued - hs[0] > lag) lag = queued - hs[0];
+      }
+      if (all_stopped || lag <= (long)kAhead * chunk_len) break;
+      if (hipStreamQuery(lead->stream) == hipSuccess) break;   // everything queued has run
+    }
+    if (all_stopped) break;
+    const int chunk = (int)(remaining < chunk_len ? remaining : chunk_len);
+    rc = batch_launch(ctxs, n, chunk);
+    remaining -= chunk;
+    queued += chunk;
+  }
+  batch_share(ctxs, n, false);
+  if (rc != CVH_OK) return rc;
+  for (int i = 0; i < n; ++i) {   // each member's pending iteration is booked (flush) and its run read back
+    cvh_context *c = ctxs[i];
+    c->timing_open = true;   // sync_impl closes the interval opened on the leader's stream before the first fused launch
+    rc = sync_impl(c);
+    if (rc != CVH_OK) return batch_fail(ctxs, n, rc, "batch: member %d: %s", i, c->err);
+    c->enqueued = c->steps_done;
+    if (steps_done) steps_done[i] = c->h_state[0].steps_done;
+    if (last_norm) last_norm[i] = c->h_state[0].norm;
+  }
   return CVH_OK;
 }
 
@@ -1803,7 +2134,7 @@ extern "C" int cvh_debug_read(cvh_context *c, unsigned long long *out, long max_
   HIPCHK(c, hipStreamSynchronize(c->stream));
   long n = (long)c->dbg_words < max_words ? (long)c->dbg_words : max_words;
   *words = n;
-  if (nblocks) *nblocks = resolve_geometry(c).nblocks;
+  if (nblocks) *nblocks = c->last_nparts > 0 ? c->last_nparts : resolve_geometry(c).nblocks;   // the grid the stamps belong to (a fused batch's share)
   if (n > 0 && c->d_dbg) HIPCHK(c, hipMemcpy(out, c->d_dbg, (size_t)n * 8, hipMemcpyDeviceToHost));
   return CVH_OK;
 }

@@ -10,6 +10,19 @@ namespace cvh_dev {
 
 typedef const int __attribute__((address_space(4))) *const_int_p;   // read through the scalar (constant) cache: s_load
 
+// Fused batch (CvhBatchArgs, cvh_internal.h): the member this workgroup works for, and its index inside the member's own grid;
+// null for a padding workgroup.  Both tables are read through the scalar cache (constant address space: s_load).
+__device__ __forceinline__ const CvhStepArgs *batch_member(const CvhBatchArgs &b, unsigned *local)
+{
+  typedef const __attribute__((address_space(4))) CvhBatchEntry *const_entry_p;
+  typedef const __attribute__((address_space(4))) CvhStepArgs *const_args_p;
+  const const_entry_p e = (const_entry_p)b.map + (blockIdx.x >> 3);
+  const unsigned member = e->member, first = e->first, nblk = e->nblk;
+  *local = blockIdx.x - first;
+  if (*local >= nblk) return nullptr;
+  return (const CvhStepArgs *)((const_args_p)b.args + member);
+}
+
 // Sum of a 64-bit integer over each ROW of 16 lanes (DPP, exact).
 __device__ __forceinline__ long long row16_sum_i64(long long v)
 {
@@ -56,20 +69,21 @@ __device__ __forceinline__ void chain_means(const CvhStepArgs &a, long long entr
 }
 
 // A workgroup's contribution: its sums of H - 1/2 and I_k (H - 1/2) as fixed-point integers into the set the next launch
-// reads (shard by workgroup index: no queue on one address), its sum u_diff^2 as a row for the bookkeeper.  `total` is
+// reads (shard by workgroup index: no queue on one address), its sum u_diff^2 as a row for the bookkeeper.  `blk` = the
+// workgroup's index in its context's own grid (blockIdx.x, or its place inside its section of a fused batch).  `total` is
 // block_reduce's result: thread t < NS holds sum t ([0] sum H', [2 + k] sum I_k H', [2 + 2C] sum u_diff^2).
 template <int C>
-__device__ __forceinline__ void chain_publish(const CvhStepArgs &a, double total)
+__device__ __forceinline__ void chain_publish(const CvhStepArgs &a, double total, unsigned blk)
 {
   const int tid = threadIdx.x;
   long long *const set = &a.chain->v[(a.chain_phase + 1) & 3][0];
-  const int shard = (int)blockIdx.x % chain_shards<C>();
+  const int shard = (int)blk % chain_shards<C>();
   if (tid == 0)
     __hip_atomic_fetch_add(&set[shard], __double2ll_rn(total * a.chain_scale[0]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (tid >= 2 && tid < 2 + C)
     __hip_atomic_fetch_add(&set[(tid - 1) * chain_shards<C>() + shard], __double2ll_rn(total * a.chain_scale[tid - 1]), __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_AGENT);
-  if (tid == 2 + 2 * C) a.chain_s4[(size_t)(a.chain_phase & 1) * a.nparts + blockIdx.x] = total;
+  if (tid == 2 + 2 * C) a.chain_s4[(size_t)(a.chain_phase & 1) * a.nparts + blk] = total;
 }
 
 // The extra workgroup of every chain-mode launch (and the whole of the flush kernel): books the iteration of the

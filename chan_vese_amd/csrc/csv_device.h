@@ -243,7 +243,7 @@ template <int C>
 __device__ __forceinline__ void publish_partials_and_maybe_finalize(const CvhStepArgs &a,
                                                                     double total, double *sred,
                                                                     double *sfin, int *s_last,
-                                                                    int nblocks)
+                                                                    int nblocks, unsigned blk)
 {
   constexpr int NS = cvh_nsums(C);
   const int tid = threadIdx.x;
@@ -259,12 +259,12 @@ __device__ __forceinline__ void publish_partials_and_maybe_finalize(const CvhSte
   // The acquire fence below is kept for the plain loads of the state words (c1/c2/steps_done of the previous launch).
   // gfx950-only by design (this library targets nothing else); not a portable C++ memory-model hand-off.
   if (tid < NS)
-    __hip_atomic_store(&a.partials[(size_t)blockIdx.x * NS + tid], total, __ATOMIC_RELAXED,
+    __hip_atomic_store(&a.partials[(size_t)blk * NS + tid], total, __ATOMIC_RELAXED,
                        __HIP_MEMORY_SCOPE_AGENT);
   if (!a.fused_finalize) return;
   if (tid < 64) {  // the storing wave is the signalling wave
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (a.dbg_times && tid == 0) a.dbg_times[(size_t)nblocks * 19 + blockIdx.x] = __builtin_amdgcn_s_memrealtime();
+    if (a.dbg_times && tid == 0) a.dbg_times[(size_t)nblocks * 19 + blk] = __builtin_amdgcn_s_memrealtime();
     if (tid == 0) {
       const unsigned t = __hip_atomic_fetch_add(&a.st->ticket, 1u, __ATOMIC_RELAXED,
                                                 __HIP_MEMORY_SCOPE_AGENT);
@@ -276,7 +276,7 @@ __device__ __forceinline__ void publish_partials_and_maybe_finalize(const CvhSte
     }
   }
   if (a.dbg_times && tid == 0) {  // diagnostic stamps: after the partial row is out, after the ticket
-    a.dbg_times[(size_t)nblocks * 17 + blockIdx.x] = __builtin_amdgcn_s_memrealtime();
+    a.dbg_times[(size_t)nblocks * 17 + blk] = __builtin_amdgcn_s_memrealtime();
   }
   __syncthreads();
   if (*s_last) {

@@ -251,7 +251,7 @@ __global__ __launch_bounds__(CVH_BLOCK) void csv_step_kernel(const CvhStepArgs a
   }
 
   const double total = block_reduce<NS>(acc, sred);
-  publish_partials_and_maybe_finalize<C>(a, total, sred, sfin, s_last, gridDim.x);
+  publish_partials_and_maybe_finalize<C>(a, total, sred, sfin, s_last, gridDim.x, blockIdx.x);
 }
 
 // Sums of H(u), (1-H(u)), I H, I (1-H) for the initial level set (seeds c1/c2 of step 1).

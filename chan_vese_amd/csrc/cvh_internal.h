@@ -132,11 +132,26 @@ struct CvhStepArgs {
   int res_go_shift;              // 2^shift tiles of one XCD share a release line (csv_resident_kernel.hip, go_line)
 };
 
+// Fused batch (cvh_enqueue_steps_batch, api.hip): one grid holds the sections of several contexts, each the context's own grid
+// (nparts workgroups + the chain-mode bookkeeper) padded to a multiple of 8 workgroups, so that blockIdx.x & 7 still names the
+// XCD the member-local numbering assumes.  map[blockIdx.x / 8] names the member and where its section starts; args[member] is
+// that member's launch arguments (read through the scalar cache).  Workgroups past a section's nblk are padding and exit.
+struct CvhBatchEntry { unsigned member, first, nblk, pad; };
+struct CvhBatchArgs { const CvhBatchEntry *map; const CvhStepArgs *args; };
+struct CvhBatchLaunch { CvhBatchArgs k; unsigned grid; };   // host: what the batch entry point of a launcher is given
+
 // The ONE way a step / Perona-Malik kernel is launched: KERNEL may be a parenthesised template-id; the trailing
 // arguments are a printf format + values that spell the instantiation as rocprofv3 prints it.
 #define CVH_LAUNCH(KERNEL, GRID, LDS, S, A, ...)                                                  \
   do {                                                                                             \
     if ((A).note) cvh_fill_note((A).note, (unsigned)(GRID), CVH_BLOCK, (size_t)(LDS), __VA_ARGS__); \
+    else hipLaunchKernelGGL(KERNEL, dim3(GRID), dim3(CVH_BLOCK), (LDS), (S), (A));                 \
+  } while (0)
+// The same, for a kernel that also has a batch entry point BKERNEL: B non-null launches that over B's grid instead
+#define CVH_LAUNCH_B(KERNEL, BKERNEL, GRID, LDS, S, A, B, ...)                                   \
+  do {                                                                                             \
+    if ((A).note) cvh_fill_note((A).note, (unsigned)(GRID), CVH_BLOCK, (size_t)(LDS), __VA_ARGS__); \
+    else if (B) hipLaunchKernelGGL(BKERNEL, dim3((B)->grid), dim3(CVH_BLOCK), (LDS), (S), (B)->k);   \
     else hipLaunchKernelGGL(KERNEL, dim3(GRID), dim3(CVH_BLOCK), (LDS), (S), (A));                 \
   } while (0)
 #define CVH_TF(b) ((b) ? "true" : "false")
@@ -173,7 +188,8 @@ void cvh_step_grid(int h, int w, int tile_rows, int *tiles_x, int *tiles_y);
 int cvh_step_max_blocks(int h, int w);
 hipError_t cvh_launch_step(const CvhStepArgs &a, int channels, int fast, hipStream_t s);
 int cvh_wave2_cols();
-hipError_t cvh_launch_wave2(const CvhStepArgs &a, int channels, int fast, hipStream_t s);
+// batch non-null: the same instantiation's batch entry point over a fused grid (a = any member's arguments: selects the flavour)
+hipError_t cvh_launch_wave2(const CvhStepArgs &a, int channels, int fast, hipStream_t s, const CvhBatchLaunch *batch = nullptr);
 hipError_t cvh_launch_chain_flush(const CvhStepArgs &a, int channels, hipStream_t s);
 size_t cvh_pm_resident_lds_bytes();
 int cvh_pm_resident_halo_doubles();
@@ -185,7 +201,7 @@ int cvh_resident_tile_hmax();
 int cvh_resident_halo_doubles();
 int cvh_resident_blocks_per_cu();
 hipError_t cvh_launch_resident(const CvhStepArgs &a, hipStream_t s);   // cooperative launch, a.res_steps iterations in LDS
-hipError_t cvh_launch_wave(const CvhStepArgs &a, int channels, int fast, hipStream_t s);
+hipError_t cvh_launch_wave(const CvhStepArgs &a, int channels, int fast, hipStream_t s, const CvhBatchLaunch *batch = nullptr);
 int cvh_wave_cols();
 hipError_t cvh_launch_init_sums(const CvhStepArgs &a, int channels, int fast, int *nparts_out,
                                 hipStream_t s);

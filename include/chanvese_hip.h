@@ -180,6 +180,35 @@ int cvh_sync(cvh_context *ctx, int *steps_done_total, double *last_norm, int *st
 /* Clears the iteration counter and the stop flag (cvh_run does this itself). */
 int cvh_reset_run(cvh_context *ctx);
 
+/* Fused batch: n contexts on one device advance together, with ONE kernel launch per iteration for all members that share
+ * a CSV-step instantiation (the kernel= text of cvh_launch_info; a batch of one shape is one launch).  Per member it is
+ * exactly what its own calls do -- src/main.cpp:963-1001, its own stop rule, trace, sums and level set; the members'
+ * bits are those of their own per-launch runs on the same strips.  Everything else stays per context (cvh_set_image,
+ * cvh_get_*, cvh_sync, cvh_perona_malik), and a context may alternate between its own runs and batch runs at any
+ * enqueue boundary.
+ *   cvh_enqueue_steps_batch: enqueues nsteps iterations of every member; then cvh_sync each member, as after
+ *     cvh_enqueue_steps.
+ *   cvh_run_batch: cvh_run per member -- resets every member's run; each stops at its own reference iteration (:1000)
+ *     and the batch's later iterations are no-ops for it; ends when every member has stopped or max_steps iterations
+ *     are done; steps_done[i] / last_norm[i] (arrays of n, or NULL) as cvh_run's.
+ * Members always take the per-launch wave kernels (never the resident flow).  The automatic strip count of a member whose
+ * own strips are short (below 32 rows: planes up to ~2048^2 on MI355X) is sized for its share of the chip, num_cus x (its
+ * pixels) / (all members' pixels); larger members keep their own geometry; an explicit "strip_rows" or "strips" wins.
+ * The fused launches run on member 0's stream, ordered after everything already enqueued on every member's stream and
+ * before anything enqueued on them later; cvh_last_run_ms of every member reports the fused interval.
+ * Throughput: the fused batch pays off for small and mid-size planes (MI355X, us per image-iteration against the same
+ * contexts interleaved: 64 x 256^2 about 2x, 32 x 512^2 1.4-1.7x, 8 x 1024^2 1.1-1.2x).  For large planes it is NOT
+ * faster and can be a few per cent slower (8 x 4096^2): every fused iteration ends with the tail of its last workgroups,
+ * which interleaved streams hide under the next iteration.  For planes of 2048^2 and more, interleave cvh_enqueue_steps.
+ * The enqueue can block the host: it synchronises the leader's stream when the batch's argument tables must be re-uploaded
+ * (first call, a change of members, options or geometry) and a member's stream when its strip table changes -- e.g. on
+ * every switch of a context between its own runs and batch runs of another geometry.
+ * CVH_ERR_ARG: ctxs NULL, n < 1, a NULL or duplicate member, members on different devices, a member with "finalize"
+ * = 1 or one that takes the tile kernel (>= 2^28 pixels); CVH_ERR_STATE: a member without an image or a level set.
+ * The message names the member index; it is cvh_last_error(NULL)'s and member 0's; the members stay usable. */
+int cvh_enqueue_steps_batch(cvh_context *const *ctxs, int n, int nsteps);
+int cvh_run_batch(cvh_context *const *ctxs, int n, int max_steps, int *steps_done, double *last_norm);
+
 /* Region means of the current level set (what the next iteration will use),
  * region_variance src/main.cpp:255-281; c1/c2 have `channels` entries. */
 int cvh_get_means(cvh_context *ctx, double *c1, double *c2);
