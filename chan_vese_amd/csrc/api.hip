@@ -2126,6 +2126,15 @@ extern "C" int cvh_debug_resident_read(cvh_context *c, unsigned *out, int ngo)
   return CVH_OK;
 }
 
+// Diagnostic (not part of include/chanvese_hip.h): the CUs of the context's device, what the automatic geometry and a fused batch's
+// shares are sized for (tests/test_gpu_fused_batch_matrix.py recomputes a member's share geometry from it).
+extern "C" int cvh_debug_num_cus(cvh_context *c, int *out)
+{
+  if (!c || !out) return CVH_ERR_ARG;
+  *out = c->num_cus;
+  return CVH_OK;
+}
+
 // Diagnostic (not part of include/chanvese_hip.h): copies the stamp buffer of "debug_times".
 extern "C" int cvh_debug_read(cvh_context *c, unsigned long long *out, long max_words, long *words, int *nblocks)
 {

@@ -6,10 +6,9 @@ import numpy as np
 import pytest
 
 from chan_vese_amd import synth
+from fused_batch_util import STRICT, assert_same, cone, iou, member, planes, result, tol_for_stop
 
 pytestmark = pytest.mark.gpu
-
-STRICT = 1
 
 
 @pytest.fixture(scope="module")
@@ -18,44 +17,6 @@ def capi():
     m.lib()
     assert m.device_count() >= 1, "no HIP device: the product path has no CPU fallback"
     return m
-
-
-def planes(h, w, ch, seed, noise=16):
-    n = min(h, w)
-    if ch == 1:
-        return [synth.disk(n, 200, 50, noise=noise, seed=seed, h=h, w=w)]
-    return [synth.disk(n, fg, bg, noise=noise, seed=seed + k, h=h, w=w) for k, (fg, bg) in enumerate([(180, 40), (200, 60), (60, 200)])]
-
-
-def cone(h, w):
-    """A smooth initial level set (its norms fall monotonically after the first iterations, unlike the checkerboard's)."""
-    ii = np.arange(h)[:, None] - h / 2 + 37
-    jj = np.arange(w)[None, :] - w / 2 - 21
-    return (min(h, w) / 3 - np.sqrt(ii * ii + jj * jj)) / 4.0
-
-
-def member(capi, h, w, ch=1, opts=None, seed=0, tol=0.0, trace=64, **pk):
-    ctx = capi.Context(h, w, ch, capi.make_params(tol=tol, **pk))
-    for k, v in (opts or {}).items():
-        ctx.set_option(k, v)
-    ctx.set_option("trace", trace)
-    ctx.set_image(planes(h, w, ch, seed))
-    return ctx
-
-
-def result(ctx, steps):
-    done, nrm, stopped = ctx.sync()
-    return ctx.get_levelset().tobytes(), ctx.get_trace(steps), done, stopped
-
-
-def assert_same(a, b, what):
-    assert a[2] == b[2] and a[3] == b[3], (what, a[2:], b[2:])
-    assert a[1].shape == b[1].shape and a[1].tobytes() == b[1].tobytes(), (what, np.abs(a[1] - b[1]).max())
-    assert a[0] == b[0], what
-
-
-def iou(a, b):
-    return (a & b).sum() / max((a | b).sum(), 1)
 
 
 def test_fused_bits_equal_own_runs(capi):
@@ -80,20 +41,6 @@ def test_fused_bits_equal_own_runs(capi):
         assert out[i][1] == own[i][1][steps - 1, -1]
     for c in ctxs:
         c.close()
-
-
-def tol_for_stop(capi, ctx, k, steps, pk):
-    """tol at which the member's stop rule fires at iteration k: from its own tol = 0 run's norm trace."""
-    ctx.set_params(capi.make_params(tol=1.0, **pk))
-    ctx.set_levelset(cone(ctx.h, ctx.w))
-    scale = ctx.get_stop_condition()          # ||mean_k I_k||_2 (tol = 1)
-    ctx.set_params(capi.make_params(tol=0.0, **pk))
-    ctx.set_levelset(cone(ctx.h, ctx.w))
-    ctx.run(steps)
-    norms = ctx.get_trace(steps)[:, -1]
-    tol = norms[k - 1] / scale * (1 + 1e-6)
-    assert norms[:k - 1].min() > norms[k - 1] * (1 + 1e-5), "the norm of iteration k must be the first below the threshold"
-    return tol
 
 
 def test_fused_members_stop_at_their_own_iteration(capi):

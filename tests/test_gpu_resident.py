@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from chan_vese_amd import synth
+from fused_batch_util import cone, first_stop_at_or_after
 
 pytestmark = pytest.mark.gpu
 
@@ -185,13 +186,31 @@ def test_a_batch_of_large_planes_in_long_chunks_takes_the_resident_flow(capi):
     continue each other on one context and agree to 1e-9."""
     n = 1536
     imgs = [synth.disk(n, 200, 50, noise=10, seed=s) for s in (21, 22)]
-    with capi.Context(n, n, 1, capi.make_params(tol=0)) as alone:
-        alone.set_image([imgs[0]]); alone.init_checkerboard()
-        alone.enqueue_steps(120); alone.enqueue_steps(8); alone.sync()
-        assert alone.launch_info()["kernel"].startswith("csv_resident_kernel<")
-        ref = alone.get_levelset()
+    alone_runs = {}
+    for which in (0, 1):
+        with capi.Context(n, n, 1, capi.make_params(tol=0)) as alone:
+            alone.set_option("trace", 128)
+            alone.set_image([imgs[which]]); alone.init_checkerboard()
+            alone.enqueue_steps(120); alone.enqueue_steps(8); alone.sync()
+            assert alone.launch_info()["kernel"].startswith("csv_resident_kernel<")
+            alone_runs[which] = (alone.get_levelset(), alone.get_trace(128))
+    ref = alone_runs[0][0]
+
+    def alone_from_cone(steps):       # b's plane alone from the cone (the checkerboard's FIRST norm is its smallest: no later stop can be placed)
+        with capi.Context(n, n, 1, capi.make_params(tol=0)) as alone:
+            alone.set_option("trace", 128)
+            alone.set_image([imgs[1]]); alone.set_levelset(cone(n, n))
+            alone.enqueue_steps(steps); alone.sync()
+            assert alone.launch_info()["kernel"].startswith("csv_resident_kernel<")
+            return alone.get_levelset(), alone.get_trace(128)
+    tr_cone = alone_from_cone(128)[1]
+    norms = tr_cone[:, -1]
+    k = first_stop_at_or_after(norms, 8)
+    assert k <= 28, (k, norms[:30])      # the enqueue after the per-launch part keeps >= 100 iterations: resident (1536^2 in a batch)
+    u_k = alone_from_cone(k)[0]
     a = capi.Context(n, n, 1, capi.make_params(tol=0)); b = capi.Context(n, n, 1, capi.make_params(tol=0))
     try:
+        b.set_option("trace", 128)
         a.set_image([imgs[0]]); a.init_checkerboard()
         b.set_image([imgs[1]]); b.init_checkerboard()
         assert a.launch_info()["kernel"].startswith("csv_wave")            # a batch, nothing announced yet: the per-launch flow is what would run
@@ -203,6 +222,27 @@ def test_a_batch_of_large_planes_in_long_chunks_takes_the_resident_flow(capi):
         assert a.launch_info()["kernel"].startswith("csv_wave") and b.launch_info()["kernel"].startswith("csv_resident_kernel<")
         assert a.sync()[0] == 128 and b.sync()[0] == 128
         assert rel_err(a.get_levelset(), ref) <= 1e-9                      # 120 resident + 8 per launch against 128 resident
+        # b: 8 per launch then 120 resident without a sync (the pending per-launch iteration is booked before the resident launch)
+        assert rel_err(b.get_levelset(), alone_runs[1][0]) <= 1e-9
+        tr_b = b.get_trace(128)
+        assert tr_b.shape == (128, 3) and np.allclose(tr_b, alone_runs[1][1], rtol=1e-9, atol=0), np.abs(tr_b - alone_runs[1][1]).max()
+        # tol > 0: the stop on the last per-launch iteration, then on the first resident one (iteration k, from the run alone's norms)
+        b.set_params(capi.make_params(tol=1.0))
+        scale = b.get_stop_condition()
+        b.set_params(capi.make_params(tol=norms[k - 1] / scale * (1 + 1e-6)))
+        for m in (k, k - 1):          # per-launch iterations before the resident enqueue
+            a.init_checkerboard(); a.reset_run()
+            b.set_levelset(cone(n, n)); b.reset_run()
+            a.enqueue_steps(120); b.enqueue_steps(m); a.enqueue_steps(8); b.enqueue_steps(128 - m)
+            assert b.launch_info()["kernel"].startswith("csv_resident_kernel<")
+            assert a.sync()[0] == 128
+            done, nrm, stopped = b.sync()
+            assert done == k and stopped, (k, m, done, stopped)
+            assert abs(nrm - norms[k - 1]) <= 1e-9 * norms[k - 1], (k, m, nrm, norms[k - 1])
+            assert rel_err(b.get_levelset(), u_k) <= 1e-9, (k, m)
+            assert np.allclose(b.get_trace(128), tr_cone[:k], rtol=1e-9, atol=0), (k, m)
+        b.set_params(capi.make_params(tol=0))
+        b.init_checkerboard()
         assert b.run(150)[0] == 150                                        # cvh_run: its chunks are long
         assert b.launch_info()["kernel"].startswith("csv_resident_kernel<")
     finally:
