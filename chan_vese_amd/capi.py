@@ -26,6 +26,7 @@ EXPORTS = [
     "cvh_get_stop_condition", "cvh_get_mask", "cvh_get_contour", "cvh_separate", "cvh_perona_malik",
     "cvh_pm_trip_count", "cvh_last_run_ms", "cvh_last_pm_ms", "cvh_ppf_apply",
     "cvh_ppf_apply_device", "cvh_version", "cvh_launch_info", "cvh_enqueue_steps_batch", "cvh_run_batch",
+    "cvh_perona_malik_batch",
 ]
 
 
@@ -92,6 +93,7 @@ def lib():
         "cvh_launch_info": (C.c_int, [vp, C.c_int, C.c_char_p, C.c_int]),
         "cvh_enqueue_steps_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int]),
         "cvh_run_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int, ip, dp]),
+        "cvh_perona_malik_batch": (C.c_int, [C.POINTER(vp), C.c_int, dp, dp, dp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -170,6 +172,24 @@ def run_batch(contexts, max_steps=-1):
     if rc != CVH_OK:
         raise CvhError(rc, lib().cvh_last_error(None).decode())
     return [(done[i], nrm[i]) for i in range(n)]
+
+
+def perona_malik_batch(contexts, K=10.0, L=0.25, T=20.0):
+    """Perona-Malik batch (cvh_perona_malik_batch): Context.perona_malik for every context at once, the planes of several
+    contexts sharing resident launches.  K, L and T are scalars (the same for every member) or sequences of one value per member."""
+    contexts = list(contexts)
+    n = len(contexts)
+
+    def per_member(v, name):
+        vals = [float(x) for x in v] if np.ndim(v) else [float(v)] * n
+        if len(vals) != n:
+            raise ValueError(f"{name}: {len(vals)} values for {n} members")
+        return (C.c_double * max(n, 1))(*vals)
+
+    k, l, t = per_member(K, "K"), per_member(L, "L"), per_member(T, "T")
+    rc = lib().cvh_perona_malik_batch(_member_array(contexts), n, k, l, t)
+    if rc != CVH_OK:
+        raise CvhError(rc, lib().cvh_last_error(None).decode())
 
 
 class Context:

@@ -90,6 +90,8 @@ struct cvh_context {
   int res_straight = 1;          // diagnostic option "res_straight": 0 = the generic march of csv_resident_kernel whatever the tile height
   int pm_resident_cap = -1;      // workgroups of pm_resident_kernel the device holds at once (-1: not asked yet)
   unsigned pm_res_serial = 0;    // launches of pm_resident_kernel so far (tag of the border entries; 0 = the cleared buffer)
+  void *d_pm_batch = nullptr;    // Perona-Malik batches led by this context (cvh_perona_malik_batch): plane tables, workgroup maps
+  size_t pm_batch_cap = 0;
   int resident_opt = -1;         // option "resident": -1 auto (on where it applies, unless a per-launch knob was set), 0 off, 1 on where it applies
   int resident_cap = -1;         // workgroups the device holds at once (-1: not asked yet, 0: unavailable)
   bool resident_used = false;    // a resident launch since the last sync: its error word is checked there
@@ -251,6 +253,7 @@ extern "C" void cvh_destroy(cvh_context *c)
   if (c->d_resident) (void)hipFree(c->d_resident);
   if (c->d_res_halo) (void)hipFree(c->d_res_halo);
   if (c->d_pm_halo) (void)hipFree(c->d_pm_halo);
+  if (c->d_pm_batch) (void)hipFree(c->d_pm_batch);
   if (c->h_resident) (void)hipHostFree(c->h_resident);
   if (c->d_bounds) (void)hipFree(c->d_bounds);
   if (c->h_status) (void)hipHostFree(c->h_status);
@@ -854,18 +857,26 @@ static bool resident_geometry(cvh_context *c, ResidentGeom *rg)
 
 // Perona-Malik on a resident plane (pm_resident_kernel.hip): any channel count (the planes are smoothed one after the other), both
 // arithmetic flavours; the same tiles as the CSV kernel.
-static bool pm_resident_geometry(cvh_context *c, ResidentGeom *rg)
+// workgroups of pm_resident_kernel the device holds at once, at most one per CU and CVH_RESIDENT_MAX_TILES (0: no cooperative launch)
+static int pm_resident_tiles_cap(cvh_context *c)
 {
-  if ((c->w & 1) || c->w < 16 || c->h < 16) return false;
   if (c->pm_resident_cap < 0) {
     int coop = 0;
     c->pm_resident_cap = 0;
     if (hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, c->device) == hipSuccess && coop)
       c->pm_resident_cap = cvh_pm_resident_blocks_per_cu() * c->num_cus;
   }
-  if (c->pm_resident_cap <= 0) return false;
+  if (c->pm_resident_cap <= 0) return 0;
   int cap = c->pm_resident_cap < CVH_RESIDENT_MAX_TILES ? c->pm_resident_cap : CVH_RESIDENT_MAX_TILES;
   if (cap > c->num_cus) cap = c->num_cus;                      // one workgroup per CU
+  return cap;
+}
+
+static bool pm_resident_geometry(cvh_context *c, ResidentGeom *rg)
+{
+  if ((c->w & 1) || c->w < 16 || c->h < 16) return false;
+  const int cap = pm_resident_tiles_cap(c);
+  if (cap <= 0) return false;
   const int tc = (c->w + cvh_resident_tile_w() - 1) / cvh_resident_tile_w();
   // tiles of 8 x band rows x 128 columns, every wave a band of exactly 2, 4, 8 or 16 rows: the shortest bands whose tiles the CUs hold at once
   // (more CUs at work); the last tile row of the image may be shorter, but holds at least the two rows a border piece needs
@@ -1480,7 +1491,7 @@ static int batch_fail(cvh_context *const *ctxs, int n, int code, const char *fmt
 }
 
 // What can be refused before anything is enqueued (the members stay as they were).
-static int batch_check(cvh_context *const *ctxs, int n)
+static int batch_check(cvh_context *const *ctxs, int n, bool csv = true)
 {
   if (!ctxs || n < 1) return batch_fail(ctxs, 0, CVH_ERR_ARG, "batch: empty member list (ctxs = %p, n = %d)", (const void *)ctxs, n);
   for (int i = 0; i < n; ++i) {
@@ -1491,6 +1502,7 @@ static int batch_check(cvh_context *const *ctxs, int n)
     if (c->device != ctxs[0]->device)
       return batch_fail(ctxs, n, CVH_ERR_ARG, "batch: member %d is on device %d, member 0 on device %d", i, c->device, ctxs[0]->device);
     if (!c->have_image) return batch_fail(ctxs, n, CVH_ERR_STATE, "batch: member %d has no image (call cvh_set_image first)", i);
+    if (!csv) continue;   // (a Perona-Malik batch needs no level set and no CSV geometry)
     if (!c->have_u) return batch_fail(ctxs, n, CVH_ERR_STATE, "batch: member %d has no level set (call cvh_set_levelset or cvh_init_checkerboard first)", i);
     if (c->finalize_mode != 0) return batch_fail(ctxs, n, CVH_ERR_ARG, "batch: member %d has finalize = 1 (a separate finalise kernel per launch): no fused batch", i);
     const Geometry g = resolve_geometry(c);
@@ -1837,6 +1849,18 @@ extern "C" int cvh_pm_trip_count(double L, double T)
 // "pm_kernel" = -1: the resident kernel pays ~25 us per cooperative launch that the per-launch flow does not, and gains 0.9 us per step
 // on small planes, 1.6 at 1024^2, 4 at 2048^2 (tools/pm_flows.py): runs shorter than this keep the per-launch flow
 static int pm_resident_min_trips(size_t n) { return n >= ((size_t)3 << 20) ? 8 : (n >= ((size_t)1 << 20) ? 16 : 32); }
+constexpr int kPmMaxPerLaunch = 1 << 16;   // time steps of one launch of the resident kernel
+constexpr int kPmPollCap = 2000000;        // polls before a wait of the resident kernel gives up
+
+// pm_resident_kernel's border buffer: room for CVH_RESIDENT_MAX_TILES tiles per step parity
+static int ensure_pm_halo(cvh_context *c)
+{
+  if (c->d_pm_halo) return CVH_OK;
+  const size_t bytes = (size_t)2 * CVH_RESIDENT_MAX_TILES * cvh_pm_resident_halo_doubles() * sizeof(double);
+  HIPCHK(c, hipMalloc((void **)&c->d_pm_halo, bytes));
+  HIPCHK(c, hipMemset(c->d_pm_halo, 0, bytes));            // tag 0: matches no launch
+  return CVH_OK;
+}
 
 // Perona-Malik with the plane resident in LDS: per channel uint8 -> FP64 plane, ONE cooperative launch per chunk of time steps,
 // FP64 -> uint8 (round-half-even, :551) behind the last step.
@@ -1847,15 +1871,11 @@ static int pm_run_resident(cvh_context *c, const CvhPmArgs &base, const Resident
   a.tiles_x = rg.tc; a.tiles_y = rg.tr; a.res_band_rows = rg.band;
   a.res_prio = c->res_prio;
   a.resident = c->d_resident;
-  if (!c->d_pm_halo) {
-    const size_t bytes = (size_t)2 * CVH_RESIDENT_MAX_TILES * cvh_pm_resident_halo_doubles() * sizeof(double);
-    HIPCHK(c, hipMalloc((void **)&c->d_pm_halo, bytes));
-    HIPCHK(c, hipMemset(c->d_pm_halo, 0, bytes));            // tag 0: matches no launch
-  }
+  { const int rc = ensure_pm_halo(c); if (rc != CVH_OK) return rc; }
   a.res_halo = c->d_pm_halo;
-  a.res_poll_cap = 2000000;
+  a.res_poll_cap = kPmPollCap;
   a.dbg_times = c->d_dbg;
-  constexpr int kMaxPerLaunch = 1 << 16;
+  constexpr int kMaxPerLaunch = kPmMaxPerLaunch;
   {
     CvhLaunchNote nb{};
     CvhPmArgs pa = a; pa.note = &nb; pa.res_steps = trips;
@@ -2018,6 +2038,208 @@ extern "C" int cvh_perona_malik(cvh_context *c, double K, double L, double T)
   HIPCHK(c, hipEventElapsedTime(&c->last_pm_ms, c->ev0, c->ev1));
   c->stop_valid = false;
   c->sums_valid = false;
+  return CVH_OK;
+}
+
+// ---- Perona-Malik batch: the planes of N contexts share cooperative launches of pm_resident_batch_kernel (include/chanvese_hip.h) ----
+// A launch holds planes of one round (channel k of every member that has one) and one arithmetic flavour; each plane is cut into tiles of
+// 8 x nr rows x 128 columns, nr common to the launch (a template parameter), and keeps its own K, L and step count.
+struct PmBatchLaunch { int round = 0, fast = 0, nr = 0, ntiles = 0; std::vector<int> members; };
+
+// tiles of c's plane in tiles of 8 x nr rows (0: the last tile row would hold fewer than the two rows a border piece needs)
+static int pm_batch_tiles(const cvh_context *c, int nr)
+{
+  const int th = 8 * nr, tr = (c->h + th - 1) / th, tc = (c->w + cvh_resident_tile_w() - 1) / cvh_resident_tile_w();
+  return c->h - (tr - 1) * th < 2 ? 0 : tr * tc;
+}
+
+// first fit: member i's plane joins launch b if some band nr lets all of b's planes and it fit `cap` tiles; b takes the smallest such nr
+static bool pm_batch_add(PmBatchLaunch &b, cvh_context *const *ctxs, int i, int cap)
+{
+  for (int nr = 2; nr <= 16; nr *= 2) {
+    int tot = pm_batch_tiles(ctxs[i], nr);
+    for (size_t q = 0; q < b.members.size() && tot > 0; ++q) {
+      const int t = pm_batch_tiles(ctxs[b.members[q]], nr);
+      tot = t > 0 ? tot + t : 0;
+    }
+    if (tot <= 0 || tot > cap) continue;
+    b.nr = nr; b.ntiles = tot;
+    b.members.push_back(i);
+    return true;
+  }
+  return false;
+}
+
+extern "C" int cvh_perona_malik_batch(cvh_context *const *ctxs, int n, const double *K, const double *L, const double *T)
+{
+  int rc = batch_check(ctxs, n, false);
+  if (rc != CVH_OK) return rc;
+  if (!K || !L || !T) return batch_fail(ctxs, n, CVH_ERR_ARG, "pm batch: K, L and T must each hold the n = %d members' values", n);
+  for (int i = 0; i < n; ++i) {   // cvh_perona_malik's own checks (src/main.cpp:863-867), every member before anything runs
+    if (L[i] > 0.25 || L[i] < 0)
+      return batch_fail(ctxs, n, CVH_ERR_ARG, "pm batch: member %d: The Laplacian coefficient in Perona-Malik segmentation must be between 0 and 0.25.", i);
+    if (T[i] < L[i])
+      return batch_fail(ctxs, n, CVH_ERR_ARG, "pm batch: member %d: The segmentation duration must exceed the value of Laplacian coefficient, %f.", i, L[i]);
+    if (K[i] == 0) return batch_fail(ctxs, n, CVH_ERR_ARG, "pm batch: member %d: edge coefficient K must be non-zero", i);
+  }
+  cvh_context *lead = ctxs[0];
+  HIPCHK(lead, hipSetDevice(lead->device));
+  // which members are fused: the automatic or the resident choice, no strip rows, a plane that qualifies on its own, one launch per plane
+  int cap = pm_resident_tiles_cap(lead);
+  const int bcap = cvh_pm_resident_batch_blocks_per_cu() * lead->num_cus;
+  if (bcap < cap) cap = bcap;
+  std::vector<int> trips((size_t)n), fused((size_t)n, 0);
+  for (int i = 0; i < n; ++i) {
+    cvh_context *c = ctxs[i];
+    trips[i] = cvh_pm_trip_count(L[i], T[i]);
+    ResidentGeom rg;
+    const bool fits = trips[i] > 0 && pm_resident_geometry(c, &rg);
+    if (c->pm_kernel == 4 && trips[i] > 0 && !fits)
+      return batch_fail(ctxs, n, CVH_ERR_ARG, "pm batch: member %d: pm_kernel 4 (resident plane) needs an even width, >= 16 rows and columns, and a plane that fits the LDS of the CUs", i);
+    PmBatchLaunch probe;
+    fused[i] = fits && (c->pm_kernel == -1 || c->pm_kernel == 4) && c->pm_strip_rows == 0 && trips[i] <= kPmMaxPerLaunch && pm_batch_add(probe, ctxs, i, cap);
+  }
+  // CSV work that was enqueued and never synchronised is closed first, as cvh_perona_malik does
+  for (int i = 0; i < n; ++i) {
+    cvh_context *c = ctxs[i];
+    if (c->timing_open || c->chain_pending || c->resident_used) {
+      rc = sync_impl(c);
+      if (rc != CVH_OK) return batch_fail(ctxs, n, rc, "pm batch: member %d: %s", i, c->err);
+    }
+  }
+  // packing (include/chanvese_hip.h): round k = channel k; inside a round FAST planes, then STRICT ones; first fit in member order
+  std::vector<PmBatchLaunch> launches;
+  int rounds = 0;
+  for (int i = 0; i < n; ++i) if (fused[i] && ctxs[i]->C > rounds) rounds = ctxs[i]->C;
+  for (int k = 0; k < rounds; ++k)
+    for (int f = 1; f >= 0; --f) {
+      const size_t first = launches.size();
+      for (int i = 0; i < n; ++i) {
+        if (!fused[i] || ctxs[i]->C <= k || (use_fast(ctxs[i]) ? 1 : 0) != f) continue;
+        bool placed = false;
+        for (size_t b = first; b < launches.size() && !placed; ++b) placed = pm_batch_add(launches[b], ctxs, i, cap);
+        if (!placed) {
+          launches.emplace_back();
+          launches.back().round = k; launches.back().fast = f;
+          (void)pm_batch_add(launches.back(), ctxs, i, cap);   // (fits alone: checked above)
+        }
+      }
+    }
+  if (!launches.empty()) {
+    for (int i = 0; i < n; ++i) {
+      cvh_context *c = ctxs[i];
+      if (!fused[i]) continue;
+      for (int k = 0; k < 2; ++k)
+        if (!c->d_pm[k]) HIPCHK(c, hipMalloc((void **)&c->d_pm[k], c->n * sizeof(double)));
+      if (!c->ev_join) HIPCHK(c, hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
+    }
+    rc = ensure_resident_buffers(lead);
+    if (rc == CVH_OK) rc = ensure_pm_halo(lead);
+    if (rc != CVH_OK) return batch_fail(ctxs, n, rc, "pm batch: member 0: %s", lead->err);
+    // the tables of every launch in one upload: [planes][map][load planes][store planes] per launch
+    struct Off { size_t planes, map, io_load, io_store; };
+    std::vector<Off> off(launches.size());
+    size_t bytes = 0;
+    auto take = [&](size_t sz) { const size_t o = (bytes + 255) & ~(size_t)255; bytes = o + sz; return o; };
+    for (size_t b = 0; b < launches.size(); ++b) {
+      const size_t np = launches[b].members.size();
+      off[b].planes = take(np * sizeof(CvhPmBatchPlane));
+      off[b].map = take((size_t)launches[b].ntiles * sizeof(unsigned));
+      off[b].io_load = take(np * sizeof(CvhPmIoPlane));
+      off[b].io_store = take(np * sizeof(CvhPmIoPlane));
+    }
+    std::vector<unsigned char> img(bytes, 0);
+    for (size_t b = 0; b < launches.size(); ++b) {
+      const PmBatchLaunch &bl = launches[b];
+      const unsigned serial = ++lead->pm_res_serial;   // border entries carry {serial, step}: nothing an earlier launch left can match
+      int base = 0;
+      for (size_t q = 0; q < bl.members.size(); ++q) {
+        const int i = bl.members[q];
+        cvh_context *c = ctxs[i];
+        CvhPmBatchPlane pl;
+        memset(&pl, 0, sizeof(pl));
+        CvhPmArgs &a = pl.a;
+        a.in = c->d_pm[0]; a.out = c->d_pm[1];
+        a.h = c->h; a.w = c->w;
+        a.tiles_x = (c->w + cvh_resident_tile_w() - 1) / cvh_resident_tile_w();
+        a.tiles_y = (c->h + 8 * bl.nr - 1) / (8 * bl.nr);
+        a.K2 = K[i] * K[i]; a.L = L[i];
+        a.invK2 = 1.0 / (K[i] * K[i]); a.L4 = L[i] / 4; a.fast = bl.fast;
+        a.resident = lead->d_resident; a.res_halo = lead->d_pm_halo; a.res_serial = serial;
+        a.res_steps = trips[i]; a.res_band_rows = bl.nr; a.res_prio = c->res_prio; a.res_poll_cap = kPmPollCap;
+        pl.tile_base = base;
+        memcpy(img.data() + off[b].planes + q * sizeof(CvhPmBatchPlane), &pl, sizeof(pl));
+        unsigned *map = (unsigned *)(img.data() + off[b].map);
+        for (int t = 0; t < a.tiles_x * a.tiles_y; ++t) map[base + t] = (unsigned)q;
+        base += a.tiles_x * a.tiles_y;
+        const CvhPmIoPlane ld = {c->d_img[bl.round], c->d_pm[0], (unsigned long long)c->n};   // channel `round` into the launch's input
+        const CvhPmIoPlane st = {c->d_img[bl.round], c->d_pm[1], (unsigned long long)c->n};   // its output back (round-half-even, :551)
+        memcpy(img.data() + off[b].io_load + q * sizeof(CvhPmIoPlane), &ld, sizeof(ld));
+        memcpy(img.data() + off[b].io_store + q * sizeof(CvhPmIoPlane), &st, sizeof(st));
+      }
+      if (base != bl.ntiles) return batch_fail(ctxs, n, CVH_ERR_STATE, "pm batch: internal error: launch %d has %d tiles, packed for %d", (int)b, base, bl.ntiles);
+    }
+    if (lead->pm_batch_cap < bytes) {
+      if (lead->d_pm_batch) (void)hipFree(lead->d_pm_batch);
+      lead->d_pm_batch = nullptr; lead->pm_batch_cap = 0;
+      HIPCHK(lead, hipMalloc(&lead->d_pm_batch, bytes));
+      lead->pm_batch_cap = bytes;
+    }
+    // every member's stream joins the leader's; all launches run there
+    for (int i = 1; i < n; ++i) {
+      if (!fused[i]) continue;
+      HIPCHK(ctxs[i], hipEventRecord(ctxs[i]->ev_join, ctxs[i]->stream));
+      HIPCHK(lead, hipStreamWaitEvent(lead->stream, ctxs[i]->ev_join, 0));
+    }
+    unsigned char *const d = (unsigned char *)lead->d_pm_batch;
+    HIPCHK(lead, hipMemcpyAsync(d, img.data(), bytes, hipMemcpyHostToDevice, lead->stream));
+    HIPCHK(lead, hipMemsetAsync(lead->d_resident, 0, sizeof(CvhResident), lead->stream));
+    HIPCHK(lead, hipEventRecord(lead->ev0, lead->stream));
+    for (size_t b = 0; b < launches.size(); ++b) {
+      const PmBatchLaunch &bl = launches[b];
+      const int np = (int)bl.members.size();
+      size_t nmax = 0;
+      for (int i : bl.members) nmax = ctxs[i]->n > nmax ? ctxs[i]->n : nmax;
+      CvhPmBatchArgs ba;
+      ba.planes = (const CvhPmBatchPlane *)(d + off[b].planes); ba.map = (const unsigned *)(d + off[b].map);
+      ba.ntiles = bl.ntiles; ba.nplanes = np;
+      HIPCHK(lead, cvh_launch_pm_load_batch((const CvhPmIoPlane *)(d + off[b].io_load), np, nmax, lead->stream));
+      HIPCHK(lead, cvh_launch_pm_resident_batch(ba, bl.fast, bl.nr, lead->stream));
+      HIPCHK(lead, cvh_launch_pm_store_batch((const CvhPmIoPlane *)(d + off[b].io_store), np, nmax, lead->stream));
+    }
+    HIPCHK(lead, hipEventRecord(lead->ev1, lead->stream));
+    HIPCHK(lead, hipMemcpyAsync(lead->h_resident, lead->d_resident, 4, hipMemcpyDeviceToHost, lead->stream));
+    HIPCHK(lead, hipStreamSynchronize(lead->stream));
+    float ms = 0.f;
+    HIPCHK(lead, hipEventElapsedTime(&ms, lead->ev0, lead->ev1));
+    const bool gave_up = lead->h_resident[0] != 0;
+    lead->h_resident[0] = 0;
+    for (size_t b = 0; b < launches.size(); ++b) {
+      const PmBatchLaunch &bl = launches[b];
+      CvhLaunchNote nb{};
+      CvhPmBatchArgs ba{};
+      ba.ntiles = bl.ntiles;
+      (void)cvh_launch_pm_resident_batch(ba, bl.fast, bl.nr, lead->stream, &nb);
+      for (int i : bl.members) {
+        cvh_context *c = ctxs[i];
+        c->last_pm_ms = ms;
+        c->stop_valid = false;
+        c->sums_valid = false;
+        if (bl.round != 0) continue;   // launch_info describes the launch of the member's first plane
+        snprintf(c->pm_desc, sizeof(c->pm_desc), "kernel=%s grid=%u block=%u lds_bytes=%u steps_per_launch=%d tiles_y=%d tiles_x=%d launches=1 graph_launches=0 trips=%d planes=%d batch_planes=%d batch_launches=%d",
+                 nb.name, nb.grid, nb.block, nb.lds, trips[i], (c->h + 8 * bl.nr - 1) / (8 * bl.nr), (c->w + cvh_resident_tile_w() - 1) / cvh_resident_tile_w(),
+                 trips[i], c->C, (int)bl.members.size(), (int)launches.size());
+      }
+    }
+    if (gave_up)
+      return batch_fail(ctxs, n, CVH_ERR_HIP, "pm batch: a wait of the resident kernel gave up (a workgroup was not resident, or a fault); every member's planes are undefined");
+  }
+  // the members that are not fused: their own flow, as cvh_perona_malik
+  for (int i = 0; i < n; ++i) {
+    if (fused[i]) continue;
+    rc = cvh_perona_malik(ctxs[i], K[i], L[i], T[i]);
+    if (rc != CVH_OK) return batch_fail(ctxs, n, rc, "pm batch: member %d: %s", i, ctxs[i]->err);
+  }
   return CVH_OK;
 }
 

@@ -182,6 +182,14 @@ struct CvhPmArgs {
   CvhLaunchNote *note;   // host only: describe the launch instead of issuing it (CVH_LAUNCH)
 };
 
+// Perona-Malik batch (cvh_perona_malik_batch, api.hip): the planes of several contexts in ONE cooperative launch of pm_resident_batch_kernel.
+// Plane p owns the tiles_y x tiles_x workgroups tile_base .. tile_base + tiles - 1 of the grid (row-major inside the plane); map[wg] = p.
+// The border buffer holds the launch's ntiles tiles per step parity, a plane's tiles at the plane's tile_base.  Uploaded by the host.
+struct CvhPmBatchPlane { CvhPmArgs a; int tile_base, pad; };
+struct CvhPmBatchArgs { const CvhPmBatchPlane *planes; const unsigned *map; int ntiles, nplanes; };
+// uint8 plane <-> FP64 state of one plane of a batch's load / store launch
+struct CvhPmIoPlane { uint8_t *img; double *state; unsigned long long n; };
+
 // ---- launchers (csv_kernels.hip / pm_kernels.hip / misc_kernels.hip) ----
 // rows-per-tile options of the step kernel
 void cvh_step_grid(int h, int w, int tile_rows, int *tiles_x, int *tiles_y);
@@ -195,6 +203,10 @@ size_t cvh_pm_resident_lds_bytes();
 int cvh_pm_resident_halo_doubles();
 int cvh_pm_resident_blocks_per_cu();
 hipError_t cvh_launch_pm_resident(const CvhPmArgs &a, hipStream_t s);
+int cvh_pm_resident_batch_blocks_per_cu();
+hipError_t cvh_launch_pm_resident_batch(const CvhPmBatchArgs &b, int fast, int nr, hipStream_t s, CvhLaunchNote *note = nullptr);
+hipError_t cvh_launch_pm_load_batch(const CvhPmIoPlane *planes, int nplanes, size_t nmax, hipStream_t s);
+hipError_t cvh_launch_pm_store_batch(const CvhPmIoPlane *planes, int nplanes, size_t nmax, hipStream_t s);
 size_t cvh_resident_lds_bytes();
 int cvh_resident_tile_w();
 int cvh_resident_tile_hmax();

@@ -275,6 +275,23 @@ __global__ void pm_store_kernel(const double *state, uint8_t *plane, size_t n)
   }
 }
 
+// Batch forms (cvh_perona_malik_batch): one launch for the planes of a fused launch, blockIdx.y = plane; the same conversions
+__global__ void pm_load_batch_kernel(const CvhPmIoPlane *planes)
+{
+  const CvhPmIoPlane p = planes[blockIdx.y];
+  for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < p.n; q += (size_t)gridDim.x * blockDim.x)
+    p.state[q] = (double)p.img[q];  // :495-496
+}
+
+__global__ void pm_store_batch_kernel(const CvhPmIoPlane *planes)
+{
+  const CvhPmIoPlane p = planes[blockIdx.y];
+  for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < p.n; q += (size_t)gridDim.x * blockDim.x) {
+    const double r = rint(p.state[q]);  // cvRound: round half to even (:551)
+    p.img[q] = (uint8_t)(r < 0.0 ? 0.0 : (r > 255.0 ? 255.0 : r));
+  }
+}
+
 inline int flat_grid(size_t n)
 {
   size_t b = (n + 255) / 256;
@@ -315,5 +332,17 @@ hipError_t cvh_launch_pm_step(const CvhPmArgs &a, hipStream_t s)
 hipError_t cvh_launch_pm_store(const double *state, uint8_t *plane, size_t n, hipStream_t s)
 {
   hipLaunchKernelGGL(pm_store_kernel, dim3(flat_grid(n)), dim3(256), 0, s, state, plane, n);
+  return hipGetLastError();
+}
+
+hipError_t cvh_launch_pm_load_batch(const CvhPmIoPlane *planes, int nplanes, size_t nmax, hipStream_t s)
+{
+  hipLaunchKernelGGL(pm_load_batch_kernel, dim3(flat_grid(nmax), nplanes), dim3(256), 0, s, planes);
+  return hipGetLastError();
+}
+
+hipError_t cvh_launch_pm_store_batch(const CvhPmIoPlane *planes, int nplanes, size_t nmax, hipStream_t s)
+{
+  hipLaunchKernelGGL(pm_store_batch_kernel, dim3(flat_grid(nmax), nplanes), dim3(256), 0, s, planes);
   return hipGetLastError();
 }

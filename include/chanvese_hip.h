@@ -237,6 +237,34 @@ int cvh_perona_malik(cvh_context *ctx, double K, double L, double T);
 /* Trip count of that loop (host arithmetic). */
 int cvh_pm_trip_count(double L, double T);
 
+/* Perona-Malik batch: cvh_perona_malik(ctxs[i], K[i], L[i], T[i]) for n contexts on one device (K, L, T: arrays of n), with
+ * the planes of several members sharing one cooperative launch of the resident kernel.  Per member it does exactly what its
+ * own call does: every channel plane smoothed in place, byte for byte the planes of its own cvh_perona_malik; the stop
+ * condition and the sums invalidated; synchronous.  A Perona-Malik step has no global sum, so a tile waits only for the
+ * tiles of its own plane, and planes with different K, L and step counts share a launch (each plane's tiles leave after
+ * its own steps).
+ * A member is FUSED when its "pm_kernel" is -1 or 4, its "pm_strip_rows" is 0, its plane qualifies for the resident kernel
+ * on its own (even width, >= 16 rows and columns, fits the chip's LDS) and its trip count is <= 65536.  Unlike one context's
+ * automatic choice there is no minimum trip count: the launch cost is shared.  Every other member runs its own
+ * cvh_perona_malik flow inside the same call.
+ * Packing, deterministic: a C-channel member contributes C planes, channel k to round k; a round's FAST planes, then its
+ * STRICT planes; first fit in member order into launches of at most min(resident workgroups the device holds, 256, CUs)
+ * tiles; a launch takes the shortest band, 8 x {2, 4, 8, 16} rows per tile, at which all its planes' tiles fit together.
+ * Each launch is one uint8 -> FP64 load, one resident launch and one FP64 -> uint8 store for all its planes.
+ * All launches run on member 0's stream (after everything already enqueued on every fused member's stream) with member
+ * 0's border buffer and error word; cvh_last_pm_ms of a fused member reports the batch's device interval, and
+ * cvh_launch_info(ctx, 1) describes the fused launch of its first plane, with batch_planes= (planes in that launch) and
+ * batch_launches= (fused launches of the call).
+ * When it pays (MI355X, 400 steps, us per image-step against the per-context sequence): 64 x 256^2 22.6x (one launch of
+ * 64 planes), 32 x 512^2 6.3x, 16 x 512^2 x 3 channels 6.2x, 8 x 1024^2 2.1x; 4 x 2048^2 1.03x -- a 2048^2 plane fills the
+ * chip alone, so such members share only the launch overheads.  No measured size was slower.
+ * CVH_ERR_ARG: ctxs NULL, n < 1, a NULL or duplicate member, members on different devices, K / L / T NULL, a member whose
+ * L, T or K cvh_perona_malik refuses, "pm_kernel" = 4 on a plane that does not qualify; CVH_ERR_STATE: a member without an
+ * image.  Checked for every member before anything runs (the planes stay untouched); the message names the member index
+ * and is cvh_last_error(NULL)'s and member 0's.  CVH_ERR_HIP when a wait of the resident kernel gave up: every member's
+ * planes are undefined. */
+int cvh_perona_malik_batch(cvh_context *const *ctxs, int n, const double *K, const double *L, const double *T);
+
 /* Device time (HIP events on the context's stream) of the last cvh_run / of the span
  * from the first cvh_enqueue_steps after a cvh_sync to that next cvh_sync; and of the
  * last cvh_perona_malik. */
