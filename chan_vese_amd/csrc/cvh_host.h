@@ -1,0 +1,205 @@
+// cvh_host.h -- private header of the library's host units (api.hip, csv_run.hip, csv_batch.hip, pm_run.hip, debug_exports.hip): the
+// context, the launch geometries and the helpers more than one unit calls.  Kernel sources do not include it.
+#pragma once
+#include <limits.h>
+#include <math.h>
+#include <stdarg.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "cvh_internal.h"
+
+// a grow-only device buffer: the tables of the batches a context leads (grow_table, free_table)
+struct DeviceTable { void *d = nullptr; size_t cap = 0; };
+
+constexpr int kGraphSteps = 16;   // steps per captured graph (even: the ping-pong parity repeats)
+struct StepGraph { hipGraphExec_t exec = nullptr; CvhStepArgs key[4]; int kind = -1, flavour = -1; };
+struct BatchCache;   // the device tables of a fused batch whose first member this context is (cvh_enqueue_steps_batch)
+
+struct cvh_context {
+  int h = 0, w = 0, C = 0, device = 0;
+  size_t n = 0;
+  cvh_params p{};
+  hipStream_t stream = nullptr;
+  uint8_t *d_img[CVH_MAX_CHANNELS] = {nullptr, nullptr, nullptr};   // planes inside d_img_slab, img_stride bytes apart
+  uint8_t *d_img_slab = nullptr;
+  size_t img_stride = 0;
+  double *d_u[2] = {nullptr, nullptr};
+  void *d_u_slab = nullptr;
+  // option "state" = 32 (declared FP32-state mode): the iteration kernels read and write d_uf[]; d_u[] stays the exchange format of
+  // set / get / mask / contour / selection and of the initial sums -- a mirror, refreshed lazily (ensure_f64_mirror)
+  int state_bits = 64;
+  float *d_uf[2] = {nullptr, nullptr};
+  void *d_uf_slab = nullptr;
+  bool mirror_valid = true;     // d_u[current] holds the level set (always true with 64-bit state)
+  // automatic cache policy of a run ("wave_pol" = -1): decided when the run's first iteration is enqueued, from the footprint of EVERY
+  // context on this device that holds an image and a level set (live_footprint), and kept until the run counter is reset
+  int co_resident = 1;          // option "co_resident": 0 = a scratch / warm-up context that does not stream beside the others
+  mutable int run_pol = -1;     // the decision of the current run (-1: not taken yet)
+  mutable int run_alone = -1;   // 1: no other co-resident context on the device when the run started (automatic resident flow allowed)
+  int run_chunk = -1;           // iterations of the enqueue at hand (cvh_enqueue_steps / cvh_warm: their argument; cvh_run: its chunk) -- how long a cooperative launch would be (-1: nothing announced yet)
+  CvhState *d_state = nullptr;
+  CvhState *h_state = nullptr;  // pinned, four slots for pipelined polling
+  double *d_partials = nullptr;
+  int partial_rows = 0;
+  double *d_trace = nullptr;
+  int trace_cap = 0;
+  double *d_pm[2] = {nullptr, nullptr};
+  uint8_t *d_mask = nullptr;
+  bool have_image = false, have_u = false, sums_valid = false, stop_valid = false;
+  double stop_norm = 0.0;  // || (sum_k I_k)/C ||_2
+  double stop_cond_h = 0.0; // tol * stop_norm of the current run (a launch argument)
+  int math_mode = CVH_MATH_DEFAULT, finalize_mode = 0, sync_every = 32;
+  int tile_rows = 0 /* auto */, use_lut = 1, use_dma = 0;
+  int kernel = -1;      // -1 auto, 0 tile kernel, 2 wave kernel, 3 wave kernel with 2 pixels per lane
+  int pm_kernel = -1;   // -1 auto (4 where the plane and the run qualify, else 3), 0 tile kernel, 1 wave kernel, 3 two time steps per launch, 4 resident plane
+  int pm_strip_rows = 0;
+  int wave_minw = 5, wave_lds_cap = 0, wave_prio = 1, wave_sync = -1 /* auto: 1 channel 1, 3 channels 0 */, wave_imgv = 1, wave_depth = 4;
+  int res_prio = 1;     // option "res_prio": resident kernels, priority by quarters of a wave's band (csv_resident_kernel.hip)
+  int res_go_share = 5;  // option "res_go_share": log2 of the tiles of an XCD that share one release line of the resident kernel (0: a line per tile, 5: a line per XCD, 6: one line)
+  int near_switch = 1;  // option "near_switch": per-wave, per-group choice of the form of H_eps (csv_wave2_kernel.hip); 0 = far form + correction always
+  double *d_dummy = nullptr;
+  int wave_rev = 0, wave_xcd = 1;
+  int use_graph = 1;
+  StepGraph graphs[4];          // by the chain-mode sum set of the first step, (chain_pb + enqueued) & 3; the ping-pong parity
+                                // follows it (cur_base == chain_pb mod 2: set_levelset / init_checkerboard keep that invariant)
+  char pm_desc[256] = {0};      // what the last cvh_perona_malik launched (cvh_launch_info)
+  hipGraphExec_t pm_graph = nullptr;   // 16 Perona-Malik steps starting from d_pm[0]
+  CvhPmArgs pm_graph_key{};
+  int pm_graph_kind = -1;
+  int wave_skew = 0;            // per-mille: older workgroups get longer strips (see upload_strip_bounds)
+  // chain mode of the 2-pixel wave kernel (cvh_internal.h, CvhChainAcc)
+  CvhChainAcc *d_chain = nullptr;
+  int chain_opt = 1;            // option "chain"
+  int chain_pb = 0;             // sum set that belongs to the level set at run-counter 0
+  bool chain_pending = false;   // chain launches enqueued since the last flush
+  bool chain_acc_valid = false; // the fixed-point sets hold the sums of the current level set
+  int pending_nparts = 0;       // workgroup rows of sum u_diff^2 the pending iteration left (> 0: a per-launch wave kernel's, which the
+                                // next launch on the same grid or the flush kernel books; 0: a resident launch's, booked inside it)
+  int last_nparts = 0;          // workgroups (without the bookkeeper) of the last per-launch wave launch, own or fused (cvh_debug_read)
+  int geom_cus = 0;             // > 0: the CUs the automatic strip count is sized for (a fused batch: this context's share of the chip)
+  BatchCache *batch = nullptr;  // fused batches led by this context: per-member launch arguments of the four phases, workgroup map
+  hipEvent_t ev_join = nullptr; // fused batch: joins this context's stream with the leader's
+  // resident kernel (csv_resident_kernel.hip): cache-resident planes iterate in LDS, one cooperative launch per chunk
+  CvhResident *d_resident = nullptr;
+  double *d_res_halo = nullptr;
+  double *d_pm_halo = nullptr;   // pm_resident_kernel's border entries {value, tag}: its own buffer (tags must never meet foreign data)
+  int *h_resident = nullptr;     // pinned: {arrive, error} of the last launch
+  int res_straight = 1;          // diagnostic option "res_straight": 0 = the generic march of csv_resident_kernel whatever the tile height
+  int pm_resident_cap = -1;      // workgroups of pm_resident_kernel the device holds at once (-1: not asked yet)
+  unsigned pm_res_serial = 0;    // launches of pm_resident_kernel so far (tag of the border entries; 0 = the cleared buffer)
+  DeviceTable pm_batch;          // Perona-Malik batches led by this context (cvh_perona_malik_batch): plane tables, workgroup maps
+  int resident_opt = -1;         // option "resident": -1 auto (on where it applies, unless a per-launch knob was set), 0 off, 1 on where it applies
+  int resident_cap = -1;         // workgroups the device holds at once (-1: not asked yet, 0: unavailable)
+  bool resident_used = false;    // a resident launch since the last sync: its error word is checked there
+  int far_terms = 5;            // terms of the far-field series of H_eps (5: valid from 32 eps, 4: from 64 eps)
+  int wave_pol = -1;            // option "wave_pol": cache policy of the 2-pixel kernel's rows (-1 auto by footprint, 0 plain, 1 write-through)
+  int wave_cls = 1;             // 2-pixel wave kernel: class-major workgroup numbering (dispatch rounds)
+  int wave_cskew = 500;         // per-mille strip-length skew between dispatch rounds (see upload_strip_bounds); measured
+                                // in one process at 4096^2: 0 -> 61.1, 300 -> 59.3, 500 -> 58.7, 750 -> 58.5, 900 -> 59.2 us
+  int *d_bounds = nullptr;      // wave kernel: first row of every strip, [tiles_y + 1]
+  int bounds_key[4] = {-1, -1, -1, -1};
+  int *h_status = nullptr;  // pinned + mapped: {steps_done, stopped} written by the device
+  unsigned long long *d_isums = nullptr, *h_isums = nullptr;   // image_sums_kernel: {sum p, sum p^2} per plane (device / pinned)
+  int strip_rows = 0;   // 0 auto
+  int strips = 0;       // 2-pixel kernel: exact number of strips (0 auto); rows are dealt by cumulative weight, so any count works
+  int num_cus = 256;
+  double *d_atan = nullptr;
+  unsigned long long *d_dbg = nullptr;  // diagnostic stamps (option "debug_times")
+  size_t dbg_words = 0;
+  double sum_img[CVH_MAX_CHANNELS] = {0, 0, 0};
+  int tiles_x = 0, tiles_y = 0;
+  int cur_base = 0;   // buffer that held u when the run counter was last reset
+  int enqueued = 0;   // steps enqueued since then
+  int steps_done = 0; // as of the last sync
+  hipEvent_t ev0 = nullptr, ev1 = nullptr, evp[4] = {nullptr, nullptr, nullptr, nullptr};
+  bool timing_open = false;
+  float last_run_ms = 0.f, last_pm_ms = 0.f;
+  char err[512] = {0};
+};
+
+struct Geometry { int strip; int rows; int tiles_x, tiles_y, strip_rows, nblocks; };
+// Resident mode (csv_resident_kernel.hip): the plane is cut into tr x tc tiles of <= 128 x 128 pixels, one workgroup per tile, all
+// co-resident (one per CU), the level set stays in LDS for a chunk of iterations.  Applies to 1 channel, FAST arithmetic, chain-mode
+// sums, even widths, and planes that fit: tiles <= what the device holds, every tile 16 .. 128 rows.
+struct ResidentGeom { int tr, tc, band; };
+
+constexpr int kPmMaxPerLaunch = 1 << 16;   // time steps of one launch of the resident kernel
+constexpr int kPmPollCap = 2000000;        // polls before a wait of the resident kernel gives up
+
+#define HIPCHK(ctx, call)                                                                      \
+  do {                                                                                         \
+    hipError_t e_ = (call);                                                                    \
+    if (e_ != hipSuccess)                                                                      \
+      return fail((ctx), CVH_ERR_HIP, "HIP error %d (%s) in %s", (int)e_, hipGetErrorString(e_), \
+                  #call);                                                                      \
+  } while (0)
+
+// Helpers shared between the host units: hidden, so that only the C ABI and what it always exported leave the library.
+#pragma GCC visibility push(hidden)
+inline bool use_fast(const cvh_context *c)
+{
+  const int m = c->math_mode == CVH_MATH_DEFAULT ? CVH_MATH_FAST : c->math_mode;
+  return m == CVH_MATH_FAST;
+}
+
+inline int current_buffer(const cvh_context *c) { return (c->cur_base + c->steps_done) & 1; }
+
+extern char g_create_err[512];   // cvh_last_error(NULL): what failed outside a context
+int fail(cvh_context *ctx, int code, const char *fmt, ...);
+
+// api.hip: live-context registry, image statistics, level-set buffers
+bool run_is_alone(const cvh_context *c);
+double live_footprint(const cvh_context *c);
+int image_stats(cvh_context *c, const uint8_t *const *host_planes);
+int ensure_f64_mirror(cvh_context *c);
+int reset_run_impl(cvh_context *c);
+
+// csv_run.hip: geometry, launch arguments and the per-launch / graph / resident flows of one context
+Geometry resolve_geometry(const cvh_context *c);
+bool use_chain(const cvh_context *c, const Geometry &g);
+bool resident_geometry(cvh_context *c, ResidentGeom *rg);
+void fill_args(const cvh_context *c, CvhStepArgs *a, int in_buf, int step);
+int prepare_host(cvh_context *c);
+int prepare(cvh_context *c);
+void compute_strip_bounds(int kind, int h, int tiles_x, int S, int strip_rows, int nblocks, int cls, int cskew, int skew, std::vector<int> &b);
+int upload_strip_bounds(cvh_context *c, const Geometry &g);
+int launch_one_step(cvh_context *c, int in_buf, int step, bool capturing = false, CvhLaunchNote *note = nullptr);
+int flush_for_grid(cvh_context *c, int nparts);
+int ensure_resident_buffers(cvh_context *c);
+int launch_resident(cvh_context *c, const ResidentGeom &rg, int nsteps, CvhLaunchNote *note);
+int sync_impl(cvh_context *c);
+
+// csv_batch.hip: what every batch of contexts shares
+void batch_cache_free(cvh_context *c);
+int batch_fail(cvh_context *const *ctxs, int n, int code, const char *fmt, ...);
+int batch_check(cvh_context *const *ctxs, int n, bool csv = true);
+int join_into_leader(cvh_context *const *ctxs, int n, const int *member = nullptr);
+int grow_table(cvh_context *c, DeviceTable *t, size_t bytes);
+void free_table(DeviceTable *t);
+
+// What launches(), which returns CVH_OK or an error already recorded with fail(), enqueues on c's stream, captured and instantiated into
+// *out.  A capture that does not end in a graph fails with end_fmt (one %s: the HIP error).
+template <class F>
+int capture_graph(cvh_context *c, hipGraphExec_t *out, F launches, const char *end_fmt)
+{
+  HIPCHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
+  const int rc = launches();
+  hipGraph_t graph = nullptr;
+  const hipError_t e_end = hipStreamEndCapture(c->stream, &graph);
+  if (rc != CVH_OK || e_end != hipSuccess || !graph) {
+    if (graph) (void)hipGraphDestroy(graph);
+    return rc != CVH_OK ? rc : fail(c, CVH_ERR_HIP, end_fmt, hipGetErrorString(e_end));
+  }
+  const hipError_t e_inst = hipGraphInstantiate(out, graph, nullptr, nullptr, 0);
+  (void)hipGraphDestroy(graph);
+  if (e_inst != hipSuccess) { *out = nullptr; return fail(c, CVH_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e_inst)); }
+  return CVH_OK;
+}
+#pragma GCC visibility pop

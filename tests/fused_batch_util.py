@@ -1,6 +1,6 @@
 """Helpers of the fused-batch GPU tests (test_gpu_fused_batch.py, test_gpu_fused_batch_matrix.py): members, initial level sets, the
 two reference bars (bits of the member's own run, the oracle with the member's own parameters) and the host arithmetic of a member's
-share geometry (api.hip, batch_share / resolve_geometry)."""
+share geometry (csv_batch.hip batch_share, csv_run.hip resolve_geometry)."""
 import ctypes as C
 
 import numpy as np
@@ -8,7 +8,7 @@ import numpy as np
 from chan_vese_amd import synth
 
 STRICT, FAST = 1, 2
-KBATCH_OWN_ROWS = 32      # api.hip, kBatchOwnRows: members whose own strips have this many rows keep their own geometry
+KBATCH_OWN_ROWS = 32      # csv_batch.hip, kBatchOwnRows: members whose own strips have this many rows keep their own geometry
 
 
 def planes(h, w, ch, seed, noise=16):
@@ -88,7 +88,7 @@ def assert_oracle(oracle, ctx, imgs, u0, pk, steps, what, done=None):
     return done_c
 
 
-# ---- host arithmetic of the share geometry (api.hip): batch_share, then resolve_geometry with the share as the CU count ----
+# ---- host arithmetic of the share geometry (csv_batch.hip): batch_share, then resolve_geometry with the share as the CU count ----
 
 def num_cus(capi, ctx):
     out = C.c_int(0)

@@ -127,7 +127,7 @@ GEOM = [("big0", 1024, 1024, 1, {}), ("big1", 1024, 1024, 1, {}), ("wide", 150, 
 
 
 def test_batch_only_geometries(capi, oracle, pool):
-    """The share geometry of api.hip (batch_share, then resolve_geometry with the share as the CU count), with num_cus from the device.
+    """The share geometry of csv_batch.hip (batch_share, then resolve_geometry with the share as the CU count), with num_cus from the device.
     On the MI355X (256 CUs) and sum n = 2 x 1024^2 + 150 x 1008 + 13 x 1008 + 144 + 144 + 4 + 2100 + 1961 + 51700 = 2,317,509 pixels:
       clamp 13 x 1008 (2-pixel): share = round(256 x 13104 / 2317509) = round(1.45) = 1 CU; wave-columns 8, nbc = 4,
             nstrips = 2 x ((1 x 3) / 4) = 0 -> clamped to 1: ONE strip of 13 rows holds the whole plane (tiles_y = 1, odd);

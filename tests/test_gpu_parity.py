@@ -328,7 +328,7 @@ def test_chain_mode_stop_edges(capi, oracle, shape, channels, kernel):
 def test_graph_chunks_that_are_not_multiples_of_four(capi, oracle, shape, channels, kernel):
     """The captured step arguments have period 4 in chain mode (the sum set of the first step): chunk sizes >= 16 that are
     not multiples of 4 -- sync_every 18 and 50, cvh_enqueue_steps(18) repeated without a sync, a run that follows a run of
-    odd length -- cycle through the four cached graphs (api.hip, ensure_step_graph).  Results equal the oracle's and the
+    odd length -- cycle through the four cached graphs (csv_run.hip, ensure_step_graph).  Results equal the oracle's and the
     plain-launch path's bit for bit."""
     h, w = shape
     rng = np.random.default_rng(11 * h + w + channels)

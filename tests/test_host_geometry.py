@@ -1,4 +1,4 @@
-"""Host logic of the wave kernels' launch geometry, on CPU: the strip table the library uploads (api.hip,
+"""Host logic of the wave kernels' launch geometry, on CPU: the strip table the library uploads (csv_run.hip,
 compute_strip_bounds, reached through the diagnostic export cvh_debug_strip_bounds -- no device needed) and a Python
 restatement of the class-major workgroup numbering the kernels apply (csv_wave2_kernel.hip)."""
 import ctypes as C
@@ -77,7 +77,7 @@ def data_flow(h, w, channels=1, math_mode=2, kernel=-1, state=64, cus=256):
 
 
 def test_which_per_launch_flow_runs():
-    """resolve_geometry() (api.hip) on the host: 3 = wave kernel with 2 pixels per lane, 2 = wave kernel, 0 = tile kernel.  The wave
+    """resolve_geometry() (csv_run.hip) on the host: 3 = wave kernel with 2 pixels per lane, 2 = wave kernel, 0 = tile kernel.  The wave
     kernels address the level set with 32-bit byte offsets and mark dropped lanes with offset 2^31, so planes of 2^28 pixels (2 GiB of
     level set) or more take the tile kernel -- a dispatch no GPU test launches (a 2 GiB level-set pair + planes per context)."""
     assert data_flow(4096, 4096)[0] == 3                              # BASELINE configs[1]

@@ -11,7 +11,7 @@ rng = np.random.default_rng(seed)
 bad = 0
 for n in range(cases):
     h = int(rng.integers(16, maxdim + 1)); w = 2 * int(rng.integers(8, maxdim // 2 + 1))
-    if h % 16 == 1: h += 1      # (a last tile row of ONE row does not qualify for the resident Perona-Malik kernel -- api.hip, pm_resident_geometry)
+    if h % 16 == 1: h += 1      # (a last tile row of ONE row does not qualify for the resident Perona-Malik kernel -- pm_run.hip, pm_resident_geometry)
     C = int(rng.choice([1, 3])); math = int(rng.choice([1, 2])); steps = int(rng.integers(1, 31))
     planes = [rng.integers(0, 256, size=(h, w), dtype=np.uint8) for _ in range(C)]
     K = float(rng.choice([5, 10, 30, 1000])); L = float(rng.choice([0.05, 0.1, 0.25]))
