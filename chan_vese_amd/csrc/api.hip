@@ -25,6 +25,20 @@ void cvh_fill_note(CvhLaunchNote *note, unsigned grid, unsigned block, size_t ld
   note->grid = grid; note->block = block; note->lds = (unsigned)lds;
 }
 
+// The atan tables of the FAST flavour, rounded once from long double: atan(i/128) and pi/2 - atan(i/128) (atan_table), then
+// (pi/4 + atan((j-128)/128)) / pi (heaviside_centred_near).  tab holds 2 * CVH_ATAN_N + CVH_ATAN2_N doubles.
+void fill_atan_tables(double *tab)
+{
+  const long double pil = 3.14159265358979323846264338327950288L;
+  for (int i = 0; i < CVH_ATAN_N; ++i) {
+    const long double at = atanl((long double)i / (CVH_ATAN_N - 1));
+    tab[i] = (double)at;
+    tab[CVH_ATAN_N + i] = (double)(pil / 2 - at);
+  }
+  for (int j = 0; j < CVH_ATAN2_N; ++j)
+    tab[2 * CVH_ATAN_N + j] = (double)((pil / 4 + atanl((long double)(j - 128) / 128)) / pil);
+}
+
 extern "C" void cvh_default_params(cvh_params *p)
 {
   if (!p) return;
@@ -162,16 +176,8 @@ static int create_impl(cvh_context *c)
     if (wave_blocks > step_blocks) step_blocks = wave_blocks;
   }
   {
-    // atan(i/128) and pi/2 - atan(i/128), rounded once from long double
     double tab[2 * CVH_ATAN_N + CVH_ATAN2_N];
-    const long double pil = 3.14159265358979323846264338327950288L;
-    for (int i = 0; i < CVH_ATAN_N; ++i) {
-      const long double at = atanl((long double)i / (CVH_ATAN_N - 1));
-      tab[i] = (double)at;
-      tab[CVH_ATAN_N + i] = (double)(pil / 2 - at);
-    }
-    for (int j = 0; j < CVH_ATAN2_N; ++j)  // (pi/4 + atan((j-128)/128)) / pi
-      tab[2 * CVH_ATAN_N + j] = (double)((pil / 4 + atanl((long double)(j - 128) / 128)) / pil);
+    fill_atan_tables(tab);
     HIPCHK(c, hipMalloc((void **)&c->d_atan, sizeof(tab)));
     HIPCHK(c, hipMemcpy(c->d_atan, tab, sizeof(tab), hipMemcpyHostToDevice));
   }

@@ -31,6 +31,12 @@ __device__ __forceinline__ double rcp_refined(double q)
   return __builtin_fma(__builtin_fma(e, e, e), r, r);
 }
 
+// 1/delta_eps(u) = (pi/eps)(eps^2 + u^2), dk1 = pi/eps: the FAST wave and resident kernels (delta_eps = rcp_refined of it).
+__device__ __forceinline__ double inv_delta_eps(double u, double eps2, double dk1) { return __builtin_fma(u, u, eps2) * dk1; }
+
+// The same as the tile kernel evaluates it: u^2 (pi/eps) + pi eps, dk2 = pi eps.
+__device__ __forceinline__ double inv_delta_eps_tile(double u, double dk1, double dk2) { return __builtin_fma(u * u, dk1, dk2); }
+
 // d+ / sqrt(d+^2 + d0^2 + eta^2): src/main.cpp:365-368 (same-axis pairing).
 template <bool FAST>
 __device__ __forceinline__ double normalised(double up, double uc)
@@ -71,7 +77,8 @@ __device__ __forceinline__ double heaviside_strict(double x, double eps)
 // atan(x) to ~1 ulp with ONE reciprocal: table of atan(c), c = i/128, in LDS plus
 // atan(x) = atan(c) + atan(z), z = (x - c)/(1 + x c); for |x| > 1 the same with t = 1/|x|:
 // atan|x| = pi/2 - atan(c) - atan(z), z = (1 - c|x|)/(|x| + c), c = round(128/|x|)/128.
-// |z| <= 1/256, so z - z^3/3 + z^5/5 truncates below 2e-18.
+// |z| <= 1/256, so z - z^3/3 + z^5/5 truncates below 2e-18 -- absolute: within cell 0 (|x| < 1/256) that is up to 5 ulp of atan(x)
+// itself, 1/50 ulp of the H = 1/2 + atan/pi it feeds (tests/test_gpu_csv_math.py).
 __device__ __forceinline__ double atan_table(double x, const double *tab /*LDS [2][CVH_ATAN_N]*/)
 {
   const double ax = fmin(fabs(x), 1e300);

@@ -209,10 +209,7 @@ __global__ __launch_bounds__(CVH_BLOCK) void csv_step_kernel(const CvhStepArgs a
         reg = __builtin_fma(reg, a.beta, a.gamma);
       }
       ud = __builtin_fma(kappa, a.alpha, reg);                                   // :985
-      const double q = __builtin_fma(u0 * u0, a.dk1, a.dk2);                     // 1/delta_eps(u)
-      const double r0 = __builtin_amdgcn_rcp(q);
-      const double e = __builtin_fma(-q, r0, 1.0);
-      ud = ud * __builtin_fma(__builtin_fma(e, e, e), r0, r0);                   // :992
+      ud = ud * rcp_refined(inv_delta_eps_tile(u0, a.dk1, a.dk2));              // :992
     } else {
       ud = 0.0;  // :965
 #pragma unroll

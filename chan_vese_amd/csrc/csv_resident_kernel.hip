@@ -315,10 +315,7 @@ __global__ __launch_bounds__(RT_THREADS, 1) void csv_resident_kernel(const CvhSt
         const double kappa = __builtin_fma(nx - nxl, fx, ny - nyp);
         const double2_t e = lds_read_d2(kLutAddr + (unsigned)byte);      // `byte`: the entry's byte offset (sample x 16)
         double ud = __builtin_fma(kappa, a.alpha, e.x);                  // :985
-        const double qd = __builtin_fma(c, c, eps2) * a.dk1;             // 1 / delta_eps(u)
-        const double q0 = __builtin_amdgcn_rcp(qd);
-        const double er = __builtin_fma(-qd, q0, 1.0);
-        ud = ud * __builtin_fma(__builtin_fma(er, er, er), q0, q0);      // :992
+        ud = ud * rcp_refined(inv_delta_eps(c, eps2, a.dk1));            // :992
         nyp = ny;
         ud_out = ud; Ik_out = e.y;
         return c + ud;                                                   // :994
@@ -384,8 +381,8 @@ __global__ __launch_bounds__(RT_THREADS, 1) void csv_resident_kernel(const CvhSt
           if (NEARFORM) {   // the rows added nothing for H
             da = heaviside_centred_near(xa, a.inv_eps, satan); db = heaviside_centred_near(xb, a.inv_eps, satan);
           } else {
-            da = (fabs(xa) < fc.thr) ? heaviside_centred_near(xa, a.inv_eps, satan) - heaviside_centred_far(xa, fc) : 0.0;
-            db = (fabs(xb) < fc.thr) ? heaviside_centred_near(xb, a.inv_eps, satan) - heaviside_centred_far(xb, fc) : 0.0;
+            da = near_field_correction(xa, a.inv_eps, satan, fc);
+            db = near_field_correction(xb, a.inv_eps, satan, fc);
           }
           acc[0] += da; acc[0] += db;
           acc[2] = __builtin_fma((double)(smp_keep[k] & 0xff), da, acc[2]);

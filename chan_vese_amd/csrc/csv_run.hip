@@ -216,22 +216,27 @@ void fill_args(const cvh_context *c, CvhStepArgs *a, int in_buf, int step)
   a->inv_eps = 1.0 / c->p.eps;
   a->dk1 = pi / c->p.eps;
   a->dk2 = pi * c->p.eps;
-  {
-    const double e = c->p.eps, e2 = e * e;
-    a->far_k[0] = e / pi; a->far_k[1] = -(e * e2) / (3.0 * pi);
-    a->far_k[2] = (e * e2 * e2) / (5.0 * pi); a->far_k[3] = -(e * e2 * e2 * e2) / (7.0 * pi);
-    // 5 terms (through t^9/9, t = eps/|u|): next term t^11/11 <= 2.5e-18 for |u| >= 32 eps.  With 4 terms the threshold
-    // is 64 eps ("far_terms" = 4: far_k[4] = 0) -- the 4096^2 checkerboard run then spends iterations 3..13 in the near field
-    // (|u| grows from 36 to 64 there), with 5 terms only iterations 1..2.
-    a->far_k[4] = c->far_terms == 5 ? (e * e2 * e2 * e2 * e2) / (9.0 * pi) : 0.0;
-    a->far_thr = (c->far_terms == 5 ? 32.0 : 64.0) * e;
-  }
+  far_coef(c->p.eps, c->far_terms, a->far_k, &a->far_thr);
   a->stop_cond = c->stop_cond_h;
   a->npix = (double)c->n;
   for (int k = 0; k < CVH_MAX_CHANNELS; ++k) a->sum_img[k] = c->sum_img[k];
   a->derive_complement = use_fast(c) ? (g.strip >= 2 ? 2 : 1) : 0;  // 2: the wave kernels sum H - 1/2
   a->use_lut = c->use_lut;
   a->use_dma = c->use_dma;
+}
+
+// The far-field series of the FAST H_eps (wave_math.h, heaviside_centred_far): k_i = (-1)^i eps^(2i+1) / ((2i+1) pi) and its threshold.
+// 5 terms (through t^9/9, t = eps/|u|): next term t^11/11 <= 2.5e-18 for |u| >= 32 eps.  With 4 terms the threshold
+// is 64 eps ("far_terms" = 4: k[4] = 0) -- the 4096^2 checkerboard run then spends iterations 3..13 in the near field
+// (|u| grows from 36 to 64 there), with 5 terms only iterations 1..2.
+void far_coef(double eps, int far_terms, double k[5], double *thr)
+{
+  const double pi = 3.14159265358979323846;
+  const double e = eps, e2 = e * e;
+  k[0] = e / pi; k[1] = -(e * e2) / (3.0 * pi);
+  k[2] = (e * e2 * e2) / (5.0 * pi); k[3] = -(e * e2 * e2 * e2) / (7.0 * pi);
+  k[4] = far_terms == 5 ? (e * e2 * e2 * e2 * e2) / (9.0 * pi) : 0.0;
+  *thr = (far_terms == 5 ? 32.0 : 64.0) * e;
 }
 
 // Host part of prepare(): the tol-free stop norm of planes that changed on the device.

@@ -253,10 +253,7 @@
         const double2_t e = lds_read_d2(kLutAddr + (unsigned)byte);   // FAST: `byte` is the entry's byte offset (sample x 16)
         Ik = e.y;
         ud = __builtin_fma(kappa, a.alpha, e.x);                       // :985
-        const double qd = __builtin_fma(c, c, eps2) * a.dk1;           // 1/delta_eps(u)
-        const double r0 = __builtin_amdgcn_rcp(qd);
-        const double er = __builtin_fma(-qd, r0, 1.0);
-        ud = ud * __builtin_fma(__builtin_fma(er, er, er), r0, r0);    // :992
+        ud = ud * rcp_refined(inv_delta_eps(c, eps2, a.dk1));          // :992
       } else {
         const double kx = (fx == 0.0) ? 0.0 : nx - nxl;                // :371
         const double ky = ny - nyp;                                    // :372
@@ -290,6 +287,8 @@
         }
       }
       double ud = __builtin_fma(kappa, a.alpha, reg);                  // :985
+      // rcp_refined(inv_delta_eps(c, eps2, a.dk1)) spelled out: the same value, but the call changes hipcc's schedule of the
+      // three-channel fused-batch kernel (csv_batch.hip)
       const double qd = __builtin_fma(c, c, eps2) * a.dk1;             // 1/delta_eps(u)
       const double r0 = __builtin_amdgcn_rcp(qd);
       const double er = __builtin_fma(-qd, r0, 1.0);
@@ -431,6 +430,7 @@
         if (TABLE) {
           da = heaviside_centred_near(xa, a.inv_eps, satan); db = heaviside_centred_near(xb, a.inv_eps, satan);
         } else {
+          // near_field_correction() spelled out: the same value, but the call changes hipcc's schedule of the fused-batch kernels
           da = (fabs(xa) < fc.thr) ? heaviside_centred_near(xa, a.inv_eps, satan) - heaviside_centred_far(xa, fc) : 0.0;
           db = (fabs(xb) < fc.thr) ? heaviside_centred_near(xb, a.inv_eps, satan) - heaviside_centred_far(xb, fc) : 0.0;
         }

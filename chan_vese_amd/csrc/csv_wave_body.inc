@@ -273,10 +273,7 @@
           reg = __builtin_fma(reg, a.beta, a.gamma);
         }
         ud = __builtin_fma(kappa, a.alpha, reg);                      // :985
-        const double qd = __builtin_fma(u0, u0, eps2) * a.dk1;        // 1/delta_eps(u) = (pi/eps)(eps^2 + u^2)
-        const double r0 = __builtin_amdgcn_rcp(qd);
-        const double e = __builtin_fma(-qd, r0, 1.0);
-        ud = ud * __builtin_fma(__builtin_fma(e, e, e), r0, r0);      // :992
+        ud = ud * rcp_refined(inv_delta_eps(u0, eps2, a.dk1));        // :992
       } else {
         ud = 0.0;  // :965
 #pragma unroll
@@ -371,12 +368,12 @@
         for (int k = 4 * half; k < 4 * half + 4; ++k) row(ib + k, k, INTERIOR ? true : (ib + k) < s1);
         if (FAST && DEFER && (near_mask[0] | near_mask[1] | near_mask[2] | near_mask[3]) != 0ull) {
           // near_field_correction: replace the clamped far-field value by the table value on the lanes
-          // with |u| < 64 eps (the sums take the difference)
+          // below the far threshold (the sums take the difference)
 #pragma unroll
           for (int k = 4 * half; k < 4 * half + 4; ++k) {
             if (near_mask[k & 3] != 0ull && (INTERIOR || (ib + k) < s1)) {
               const double x = un_keep[k & 3];
-              const double d = (fabs(x) < fc.thr) ? heaviside_centred_near(x, a.inv_eps, satan) - heaviside_centred_far(x, fc) : 0.0;
+              const double d = near_field_correction(x, a.inv_eps, satan, fc);
               acc[0] += d;
 #pragma unroll
               for (int ch = 0; ch < C; ++ch) acc[2 + ch] = __builtin_fma((double)im[ch][k], d, acc[2 + ch]);

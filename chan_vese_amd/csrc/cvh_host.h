@@ -160,12 +160,14 @@ double live_footprint(const cvh_context *c);
 int image_stats(cvh_context *c, const uint8_t *const *host_planes);
 int ensure_f64_mirror(cvh_context *c);
 int reset_run_impl(cvh_context *c);
+void fill_atan_tables(double *tab);
 
 // csv_run.hip: geometry, launch arguments and the per-launch / graph / resident flows of one context
 Geometry resolve_geometry(const cvh_context *c);
 bool use_chain(const cvh_context *c, const Geometry &g);
 bool resident_geometry(cvh_context *c, ResidentGeom *rg);
 void fill_args(const cvh_context *c, CvhStepArgs *a, int in_buf, int step);
+void far_coef(double eps, int far_terms, double k[5], double *thr);
 int prepare_host(cvh_context *c);
 int prepare(cvh_context *c);
 void compute_strip_bounds(int kind, int h, int tiles_x, int S, int strip_rows, int nblocks, int cls, int cskew, int skew, std::vector<int> &b);

@@ -1,5 +1,6 @@
 // debug_exports.hip — diagnostic exports that include/chanvese_hip.h does not declare (the tests and tools/ bind them by name).
 #include "cvh_host.h"
+#include "wave_math.h"
 
 // Diagnostic (not part of include/chanvese_hip.h): the strip table for a geometry, without a device.  out needs S + 1 ints.
 extern "C" int cvh_debug_strip_bounds(int kind, int h, int tiles_x, int S, int strip_rows, int nblocks, int cls, int cskew, int skew, int *out)
@@ -63,5 +64,95 @@ extern "C" int cvh_debug_read(cvh_context *c, unsigned long long *out, long max_
   *words = n;
   if (nblocks) *nblocks = c->last_nparts > 0 ? c->last_nparts : resolve_geometry(c).nblocks;   // the grid the stamps belong to (a fused batch's share)
   if (n > 0 && c->d_dbg) HIPCHK(c, hipMemcpy(out, c->d_dbg, (size_t)n * 8, hipMemcpyDeviceToHost));
+  return CVH_OK;
+}
+
+// Diagnostic (not part of include/chanvese_hip.h): the FAST flavour's per-pixel arithmetic on a vector of arguments, through the very
+// inline functions the step kernels call (wave_math.h, csv_device.h) with the tables api.hip fills and the far-field series csv_run.hip
+// sets up (tests/test_gpu_csv_math.py holds them against tests/golden/csv_math_ref.npz).  Ops (x holds cvh_debug_csv_math_arity(op)
+// vectors of n, one after the other):
+enum {
+  MATH_H_FAR = 0,       // heaviside_centred_far(x) (clamped below 32 eps)
+  MATH_H_NEAR,          // heaviside_centred_near(x), table staged in LDS
+  MATH_H_FAST,          // far + near_field_correction: what a FAST wave / resident kernel's sums carry for a pixel
+  MATH_H_STRICT,        // heaviside_strict(x)
+  MATH_ATAN_TABLE,      // atan_table(x) (eps unused)
+  MATH_INV_DELTA,       // inv_delta_eps: 1/delta_eps(x), wave / resident kernels
+  MATH_DELTA,           // rcp_refined(inv_delta_eps(x))
+  MATH_INV_DELTA_TILE,  // inv_delta_eps_tile: 1/delta_eps(x), tile kernel
+  MATH_DELTA_TILE,      // rcp_refined(inv_delta_eps_tile(x))
+  MATH_RCP,             // rcp_refined(x)
+  MATH_RSQRT,           // rsqrt_refined(x)
+  MATH_NORMALISED,      // normalised<true>(x0, x1)
+  MATH_NORMALISED4,     // normalised4(x0, x1, x2)
+  MATH_NOPS
+};
+
+extern "C" int cvh_debug_csv_math_arity(int op)
+{
+  return op < 0 || op >= MATH_NOPS ? 0 : op == MATH_NORMALISED ? 2 : op == MATH_NORMALISED4 ? 3 : 1;
+}
+
+namespace {
+constexpr int kMathTab = 2 * CVH_ATAN_N + CVH_ATAN2_N;
+
+__global__ void __launch_bounds__(256) csv_math_kernel(int op, int n, const double *x, double eps, double inv_eps, double dk1, double dk2,
+                                                       cvh_dev::FarCoef fc, const double *tab, double *out)
+{
+  using namespace cvh_dev;
+  __shared__ double stab[kMathTab];   // [0, 2 CVH_ATAN_N): atan_table's; then heaviside_centred_near's, as the kernels stage them
+  for (int q = threadIdx.x; q < kMathTab; q += blockDim.x) stab[q] = tab[q];
+  __syncthreads();
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double v = x[i];
+  const double *satan2 = stab + 2 * CVH_ATAN_N;
+  double r = 0.0;
+  switch (op) {
+    case MATH_H_FAR: r = heaviside_centred_far(v, fc); break;
+    case MATH_H_NEAR: r = heaviside_centred_near(v, inv_eps, satan2); break;
+    case MATH_H_FAST: r = heaviside_centred_far(v, fc) + near_field_correction(v, inv_eps, satan2, fc); break;
+    case MATH_H_STRICT: r = heaviside_strict(v, eps); break;
+    case MATH_ATAN_TABLE: r = atan_table(v, stab); break;
+    case MATH_INV_DELTA: r = inv_delta_eps(v, eps * eps, dk1); break;
+    case MATH_DELTA: r = rcp_refined(inv_delta_eps(v, eps * eps, dk1)); break;
+    case MATH_INV_DELTA_TILE: r = inv_delta_eps_tile(v, dk1, dk2); break;
+    case MATH_DELTA_TILE: r = rcp_refined(inv_delta_eps_tile(v, dk1, dk2)); break;
+    case MATH_RCP: r = rcp_refined(v); break;
+    case MATH_RSQRT: r = rsqrt_refined(v); break;
+    case MATH_NORMALISED: r = normalised<true>(v, x[(size_t)n + i]); break;
+    case MATH_NORMALISED4: r = normalised4(v, x[(size_t)n + i], x[2 * (size_t)n + i]); break;
+  }
+  out[i] = r;
+}
+}  // namespace
+
+extern "C" int cvh_debug_csv_math(int op, int n, const double *x, double eps, double *out)
+{
+  const int arity = cvh_debug_csv_math_arity(op);
+  if (!arity || n < 1 || !x || !out || !(eps > 0)) return CVH_ERR_ARG;
+  double tab[kMathTab];
+  fill_atan_tables(tab);
+  cvh_dev::FarCoef fc;
+  {
+    double k[5];
+    far_coef(eps, 5, k, &fc.thr);
+    fc.k0 = k[0]; fc.k1 = k[1]; fc.k2 = k[2]; fc.k3 = k[3]; fc.k4 = k[4];
+  }
+  const double pi = 3.14159265358979323846;   // as fill_args() derives inv_eps, dk1, dk2
+  double *d_x = nullptr, *d_out = nullptr, *d_tab = nullptr;
+  const size_t xbytes = (size_t)arity * (size_t)n * sizeof(double), obytes = (size_t)n * sizeof(double);
+  hipError_t e = hipMalloc((void **)&d_x, xbytes);
+  if (e == hipSuccess) e = hipMalloc((void **)&d_out, obytes);
+  if (e == hipSuccess) e = hipMalloc((void **)&d_tab, sizeof(tab));
+  if (e == hipSuccess) e = hipMemcpy(d_x, x, xbytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_tab, tab, sizeof(tab), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(csv_math_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, op, n, d_x, eps, 1.0 / eps, pi / eps, pi * eps, fc, d_tab, d_out);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy(out, d_out, obytes, hipMemcpyDeviceToHost);
+  hipFree(d_x); hipFree(d_out); hipFree(d_tab);
+  if (e != hipSuccess) return fail(nullptr, CVH_ERR_HIP, "cvh_debug_csv_math: HIP error %d (%s)", (int)e, hipGetErrorString(e));
   return CVH_OK;
 }

@@ -71,6 +71,13 @@ __device__ __forceinline__ double heaviside_centred_near(double u, double inv_ep
   return __builtin_copysign(atpi, x);
 }
 
+// near_field_correction: what turns the clamped far-field value of a lane below the threshold into the table value (the sums add
+// the difference after the group's rows; lanes at or above the threshold add 0).
+__device__ __forceinline__ double near_field_correction(double u, double inv_eps, const double *tab /*LDS, CVH_ATAN2_N*/, const FarCoef &fc)
+{
+  return (fabs(u) < fc.thr) ? heaviside_centred_near(u, inv_eps, tab) - heaviside_centred_far(u, fc) : 0.0;
+}
+
 // FAST form of d+ / sqrt(d+^2 + d0^2 + eta^2) (src/main.cpp:365-368) from the three samples
 // along one axis: evaluated as 2d+ / sqrt((2d+)^2 + (2d0)^2 + 4 eta^2) -- the same value bit for
 // bit (every intermediate is an exact power-of-two multiple), one instruction shorter because

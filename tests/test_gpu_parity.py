@@ -616,3 +616,39 @@ def test_all_near_regime(capi, oracle, case):
         assert rel_err(u_g, u_c) <= 1e-9, (o, rel_err(u_g, u_c))
         assert np.allclose(tr_g, tr_c, rtol=1e-9, atol=0), o
         assert np.array_equal(m_g, oracle.mask(u_c)), o
+
+
+@pytest.mark.parametrize("pm_kernel", [0, 1, 3, 4, -1])
+@pytest.mark.parametrize("K", [0.05, 1e6])
+@pytest.mark.parametrize("kind", ["const", "checker"])
+def test_perona_malik_parity_at_edges(capi, oracle, kind, K, pm_kernel):
+    """Perona-Malik at its edges: K = 0.05 (the conduction g = 1/(1 + (|grad|/K)^2) vanishes wherever there is a gradient) and K = 1e6
+    (g = 1: plain diffusion), L = 0.01 (five trips), on constant planes (every gradient 0) and on a 0/255 checkerboard (the largest
+    gradients an 8-bit plane has), in every data flow -- tile, wave, two steps per launch, resident plane, automatic.  The bars of
+    test_perona_malik_parity: STRICT byte-exact, FAST <= 1 LSB on <= 1e-6 of the pixels."""
+    h, w = 64, 64
+    if kind == "const":
+        planes = [np.full((h, w), v, dtype=np.uint8) for v in (0, 117, 255)]
+    else:
+        ii, jj = np.meshgrid(np.arange(h), np.arange(w), indexing="ij")
+        planes = [np.where((ii + jj + k) % 2 == 0, 255, 0).astype(np.uint8) for k in range(3)]
+    L, T = 0.01, 0.05
+    cpu = oracle.perona_malik(planes, K, L, T)
+    for math in (1, 2):
+        with capi.Context(h, w, 3) as ctx:
+            ctx.set_option("math_mode", math)
+            ctx.set_option("pm_kernel", pm_kernel)
+            ctx.set_image(planes)
+            ctx.perona_malik(K, L, T)
+            gpu = ctx.get_image()
+            info = ctx.launch_info(1)
+        want = {0: "pm_step_kernel", 1: "pm_wave_kernel", 3: "pm_wave_k2_kernel", 4: "pm_resident_kernel"}.get(pm_kernel)
+        assert want is None or info["kernel"].startswith(want), (pm_kernel, info)
+        for g, c in zip(gpu, cpu):
+            if math == 1:
+                assert (g != c).sum() == 0, (kind, K, pm_kernel)
+            else:
+                d = np.abs(g.astype(int) - c.astype(int))
+                assert d.max() <= 1 and (d != 0).sum() <= max(1, int(1e-6 * d.size)), (kind, K, pm_kernel, d.max(), (d != 0).sum())
+    if kind == "const":
+        assert all(np.array_equal(c, p) for c, p in zip(cpu, planes))     # nothing to smooth: the oracle returns the planes

@@ -111,3 +111,48 @@ def test_combine_is_the_addweighted_fold_not_the_unfused_expression(oracle):
     assert not np.array_equal(u_o, u + unfused)
     assert (folded != unfused).mean() > 0.2
     assert np.abs(folded - unfused).max() <= 4 * np.spacing(np.abs(folded).max())
+
+
+@pytest.mark.parametrize("p_i", range(4))
+@pytest.mark.parametrize("k", range(5))
+def test_csv_steps_match_at_parameter_edges(oracle, p_i, k):
+    """The GPU edge cases (tests/test_gpu_param_edges.py) trust the oracle, so the oracle meets the numpy restatement there: every
+    parameter set of the covering design with every start and every image (one and three channels).  Steps are compared while the
+    oracle's own trajectory is well-conditioned -- a 1-ulp perturbation of u0 moves it by < 1e-11 of max|u| -- which mu = 2.5 on
+    near-flat level sets ends after 1-3 iterations (see tests/test_gpu_param_edges.py); the first step is always compared."""
+    import param_edges_util as E
+    pname = list(E.PARAMS)[p_i]
+    st, im = E.STARTS[k], E.IMAGES[(k + p_i) % 5]
+    channels = 3 if (k + p_i) % 2 else 1
+    h, w = 24, 40
+    pk = E.params(pname, channels)
+    planes = E.image(im, h, w, channels, seed=k)
+    u_o = E.start(oracle, st, h, w, pk["eps"], seed=k)
+    u_n = u_o.copy()
+    rng = np.random.default_rng(3)
+    u_p = u_o * (1 + rng.choice([-1.0, 0.0, 1.0], size=u_o.shape) * 2.0 ** -52)
+    p = oracle.make_params(tol=0, **pk)
+    for s in range(1, 6):
+        nrm_o, c1, c2 = oracle.csv_step(planes, u_o, p)
+        oracle.csv_step(planes, u_p, p)
+        u_n, nrm_n, c1n, c2n = R.csv_step(planes, u_n, **pk)
+        scale = max(np.abs(u_o).max(), 1e-300)
+        if s > 1 and np.abs(u_p - u_o).max() / scale > 1e-11:
+            break
+        # region means: 1e-12 over the first three steps; later the two summation orders' difference grows with the trajectory
+        # (P3 -- eps 16, dt 3: every pixel near the contour -- checkerboard on the binary image, three channels: 6.8e-12 at step 5)
+        crt = 1e-12 if s <= 3 else 1e-10
+        assert np.allclose(c1, c1n, rtol=crt, atol=0) and np.allclose(c2, c2n, rtol=crt, atol=0), (s, c1, c1n, c2, c2n)
+        assert nrm_o == pytest.approx(nrm_n, rel=1e-10), s
+        assert np.abs(u_o - u_n).max() <= 1e-9 * scale, (s, np.abs(u_o - u_n).max() / scale)
+
+
+def test_circle_outline_is_the_cli_shape():
+    """tests/param_edges_util.circle_outline restates the CLI's --circ outline: symmetric, 8-connected, ones on zeros, radius kept."""
+    import param_edges_util as E
+    u = E.circle_outline(41, 41, 20, 20, 12)
+    assert set(np.unique(u)) == {0.0, 1.0}
+    assert np.array_equal(u, u[::-1, :]) and np.array_equal(u, u[:, ::-1]) and np.array_equal(u, u.T)
+    ii, jj = np.nonzero(u)
+    r = np.hypot(ii - 20, jj - 20)
+    assert r.min() >= 11.0 and r.max() <= 12.5 and u[20, 8] == 1 and u[8, 20] == 1 and u[20, 20] == 0
