@@ -87,24 +87,28 @@ bool use_chain(const cvh_context *c, const Geometry &g)
   return (g.strip == 3 || g.strip == 2) && use_fast(c) && c->finalize_mode == 0 && c->chain_opt;
 }
 
-// tiles_y x tiles_x tiles of <= 128 rows x 128 columns, at most one per CU
-static bool resident_tiles(const cvh_context *c, int cap_blocks, ResidentGeom *rg)
+// tiles_y x tiles_x tiles of <= 128 (three channels: 96) rows x 128 columns, at most one per CU.  Pure host arithmetic (also exported for
+// the CPU tests: cvh_debug_resident_grid).
+bool resident_tile_grid(int h, int w, int channels, int num_cus, int cap_blocks, ResidentGeom *rg)
 {
-  const int tw = cvh_resident_tile_w(), thmax = cvh_resident_tile_hmax();
-  const int tc = (c->w + tw - 1) / tw;
+  if ((channels != 1 && channels != 3) || (w & 1) || w < 16 || h < 16) return false;
+  const int tw = cvh_resident_tile_w(), thmax = cvh_resident_tile_hmax(channels);
+  const int tc = (w + tw - 1) / tw;
   int cap = cap_blocks < CVH_RESIDENT_MAX_TILES ? cap_blocks : CVH_RESIDENT_MAX_TILES;
-  if (cap > c->num_cus) cap = c->num_cus;                      // one workgroup per CU: a second one on a CU would wait for its slot
+  if (cap > num_cus) cap = num_cus;                            // one workgroup per CU: a second one on a CU would wait for its slot
   int tr = cap / tc;
   if (tr < 1) return false;
-  if (tr > c->h / 16) tr = c->h / 16;                          // tiles of >= 16 rows (every wave's band >= 2 rows)
-  if ((c->h + tr - 1) / tr > thmax) return false;              // does not fit the LDS of the CUs
+  if (tr > h / 16) tr = h / 16;                                // tiles of >= 16 rows (every wave's band >= 2 rows)
+  if ((h + tr - 1) / tr > thmax) return false;                 // does not fit the LDS of the CUs
   rg->tr = tr; rg->tc = tc; rg->band = 0;
   return true;
 }
 
 bool resident_geometry(cvh_context *c, ResidentGeom *rg)
 {
-  if (!c->resident_opt || c->C != 1 || !use_fast(c) || !c->chain_opt || c->finalize_mode != 0 || (c->w & 1) || c->w < 16 || c->h < 16) return false;
+  // three channels (csv_resident_kernel<3, .>): on request only ("resident" = 1); the automatic choice keeps the per-launch flow
+  if (c->C == 3 && c->resident_opt != 1) return false;
+  if (!c->resident_opt || (c->C != 1 && c->C != 3) || !use_fast(c) || !c->chain_opt || c->finalize_mode != 0 || (c->w & 1) || c->w < 16 || c->h < 16) return false;
   if (c->state_bits == 32) return false;      // the FP32-state mode is the 2-pixel per-launch kernel's
   if (!(c->kernel == -1 || c->kernel == 2 || c->kernel == 3)) return false;
   // auto: a caller who chose a per-launch data flow or tuned its geometry / launch path gets that flow (measured, one context per size,
@@ -132,10 +136,10 @@ bool resident_geometry(cvh_context *c, ResidentGeom *rg)
     int coop = 0;
     c->resident_cap = 0;
     if (hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, c->device) == hipSuccess && coop)
-      c->resident_cap = cvh_resident_blocks_per_cu() * c->num_cus;
+      c->resident_cap = cvh_resident_blocks_per_cu(c->C) * c->num_cus;
   }
   if (c->resident_cap <= 0) return false;
-  return resident_tiles(c, c->resident_cap, rg);
+  return resident_tile_grid(c->h, c->w, c->C, c->num_cus, c->resident_cap, rg);
 }
 
 // `step` = index of the launch inside the run (c->enqueued when it is enqueued): selects the chain-mode sum set
@@ -487,9 +491,9 @@ int launch_resident(cvh_context *c, const ResidentGeom &rg, int nsteps, CvhLaunc
     fill_args(c, &a, (c->cur_base + c->enqueued) & 1, c->enqueued);
     if (!a.chain) return fail(c, CVH_ERR_STATE, "resident mode needs chain-mode sums");
     a.tiles_x = rg.tc; a.tiles_y = rg.tr; a.nparts = ntiles;
-    {   // every tile 16, 32, 64 or 128 rows: the straight-line flavour of the march
+    {   // every tile 16, 32, 64 or 128 rows (three channels: up to 64): the straight-line flavour of the march
       const int th = c->h % rg.tr == 0 ? c->h / rg.tr : 0;
-      a.res_band_rows = (c->res_straight && (th == 16 || th == 32 || th == 64 || th == 128)) ? th / 8 : 0;
+      a.res_band_rows = (c->res_straight && (th == 16 || th == 32 || th == 64 || th == 128) && th <= cvh_resident_tile_hmax(c->C)) ? th / 8 : 0;
     }
     a.resident = c->d_resident;
     a.res_halo = c->d_res_halo;
@@ -497,9 +501,9 @@ int launch_resident(cvh_context *c, const ResidentGeom &rg, int nsteps, CvhLaunc
     a.res_t0 = c->enqueued;
     a.res_poll_cap = 2000000;      // seconds of polling before a wait gives up (the grid always drains)
     a.note = note;
-    if (note) { HIPCHK(c, cvh_launch_resident(a, c->stream)); return CVH_OK; }
-    HIPCHK(c, hipMemsetAsync(c->d_resident, 0, sizeof(CvhResident), c->stream));
-    HIPCHK(c, cvh_launch_resident(a, c->stream));
+    if (note) { HIPCHK(c, cvh_launch_resident(a, c->C, c->stream)); return CVH_OK; }
+    HIPCHK(c, hipMemsetAsync(c->d_resident, 0, c->C == 1 ? CVH_RESIDENT_C1_BYTES : sizeof(CvhResident), c->stream));
+    HIPCHK(c, cvh_launch_resident(a, c->C, c->stream));
     c->chain_pending = true;       // the flush kernel writes c1 / c2 of the final level set into the state block at the next sync
     c->pending_nparts = 0;
     c->last_nparts = 0;

@@ -126,8 +126,9 @@ struct cvh_context {
 
 struct Geometry { int strip; int rows; int tiles_x, tiles_y, strip_rows, nblocks; };
 // Resident mode (csv_resident_kernel.hip): the plane is cut into tr x tc tiles of <= 128 x 128 pixels, one workgroup per tile, all
-// co-resident (one per CU), the level set stays in LDS for a chunk of iterations.  Applies to 1 channel, FAST arithmetic, chain-mode
-// sums, even widths, and planes that fit: tiles <= what the device holds, every tile 16 .. 128 rows.
+// co-resident (one per CU), the level set stays in LDS for a chunk of iterations.  Applies to 1 channel (3 channels with "resident" = 1),
+// FAST arithmetic, chain-mode sums, even widths, and planes that fit: tiles <= what the device holds, every tile 16 .. 128 rows (three
+// channels: 16 .. 96).
 struct ResidentGeom { int tr, tc, band; };
 
 constexpr int kPmMaxPerLaunch = 1 << 16;   // time steps of one launch of the resident kernel
@@ -166,6 +167,7 @@ void fill_atan_tables(double *tab);
 Geometry resolve_geometry(const cvh_context *c);
 bool use_chain(const cvh_context *c, const Geometry &g);
 bool resident_geometry(cvh_context *c, ResidentGeom *rg);
+bool resident_tile_grid(int h, int w, int channels, int num_cus, int cap_blocks, ResidentGeom *rg);
 void fill_args(const cvh_context *c, CvhStepArgs *a, int in_buf, int step);
 void far_coef(double eps, int far_terms, double k[5], double *thr);
 int prepare_host(cvh_context *c);

@@ -3,6 +3,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "chanvese_hip.h"
@@ -58,7 +59,14 @@ struct CvhResident {
   unsigned go[CVH_RESIDENT_MAX_TILES * 16];
   // one 64-byte line per tile {generation}: the tile's borders of iteration generation - 1 have reached memory (its neighbours wait for this)
   unsigned hflag[CVH_RESIDENT_MAX_TILES * 16];
+  // ---- three channels only (csv_resident_kernel<3, .>), appended so that nothing the one-channel kernels address moves:
+  // the FIFTH arrival piece of a tile {generation, 0, sum I_2 (H - 1/2)} (pieces 0 .. 3 -- sum u_diff^2, sum (H - 1/2), sum I_0 .., sum I_1 .. -- are `flag`'s four)
+  unsigned flag_c3[CVH_RESIDENT_MAX_TILES * 4];
+  // one 128-byte line per tile, six 16-byte pieces {generation, leave, c1_k} k = 0..2, {generation, leave, c2_k}: the three-channel release
+  unsigned go_c3[CVH_RESIDENT_MAX_TILES * 32];
 };
+// what a one-channel launch and the Perona-Malik kernels (the error word only) need cleared
+constexpr size_t CVH_RESIDENT_C1_BYTES = offsetof(CvhResident, flag_c3);
 
 // Sums carried per workgroup and reduced in a fixed order (deterministic):
 //   [0] sum H(u)  [1] sum (1-H(u))  [2..2+C) sum I_k H  [2+C..2+2C) sum I_k (1-H)  [2+2C] sum u_diff^2
@@ -207,12 +215,12 @@ int cvh_pm_resident_batch_blocks_per_cu();
 hipError_t cvh_launch_pm_resident_batch(const CvhPmBatchArgs &b, int fast, int nr, hipStream_t s, CvhLaunchNote *note = nullptr);
 hipError_t cvh_launch_pm_load_batch(const CvhPmIoPlane *planes, int nplanes, size_t nmax, hipStream_t s);
 hipError_t cvh_launch_pm_store_batch(const CvhPmIoPlane *planes, int nplanes, size_t nmax, hipStream_t s);
-size_t cvh_resident_lds_bytes();
+size_t cvh_resident_lds_bytes(int channels);
 int cvh_resident_tile_w();
-int cvh_resident_tile_hmax();
+int cvh_resident_tile_hmax(int channels);   // most rows of a tile: 128 for one channel, 96 for three (three image tiles and tables in LDS)
 int cvh_resident_halo_doubles();
-int cvh_resident_blocks_per_cu();
-hipError_t cvh_launch_resident(const CvhStepArgs &a, hipStream_t s);   // cooperative launch, a.res_steps iterations in LDS
+int cvh_resident_blocks_per_cu(int channels);
+hipError_t cvh_launch_resident(const CvhStepArgs &a, int channels, hipStream_t s);   // cooperative launch, a.res_steps iterations in LDS
 hipError_t cvh_launch_wave(const CvhStepArgs &a, int channels, int fast, hipStream_t s, const CvhBatchLaunch *batch = nullptr);
 int cvh_wave_cols();
 hipError_t cvh_launch_init_sums(const CvhStepArgs &a, int channels, int fast, int *nparts_out,

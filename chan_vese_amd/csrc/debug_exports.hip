@@ -30,6 +30,21 @@ extern "C" int cvh_debug_data_flow(int h, int w, int channels, int math_mode, in
   return CVH_OK;
 }
 
+// Diagnostic (not part of include/chanvese_hip.h): the tile grid of the resident flow (csv_resident_kernel.hip) for a plane of `channels`
+// channels on `num_cus` CUs, one workgroup per CU, without a device -- the arithmetic resident_geometry() ends in.  Returns 1 and fills
+// tiles_x, tiles_y and the rows of the tallest tile, or 0: the plane does not qualify (odd width, < 16 rows or columns, more rows per tile
+// than the LDS of a CU holds for that channel count).  The options a context adds ("resident", FAST, chain-mode sums ...) are not part of it.
+extern "C" int cvh_debug_resident_grid(int h, int w, int channels, int num_cus, int *tiles_x, int *tiles_y, int *tile_rows)
+{
+  if (h < 1 || w < 1 || num_cus < 1) return 0;
+  ResidentGeom rg;
+  if (!resident_tile_grid(h, w, channels, num_cus, num_cus, &rg)) return 0;
+  if (tiles_x) *tiles_x = rg.tc;
+  if (tiles_y) *tiles_y = rg.tr;
+  if (tile_rows) *tile_rows = (h + rg.tr - 1) / rg.tr;
+  return 1;
+}
+
 // Diagnostic (not part of include/chanvese_hip.h): the synchronisation words of the last resident launch: {error, 0, generation of
 // the arrival line of tile 0 .. n-1, generation of the release line of tile 0 .. n-1}.
 extern "C" int cvh_debug_resident_read(cvh_context *c, unsigned *out, int ngo)

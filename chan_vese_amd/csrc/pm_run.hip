@@ -120,7 +120,7 @@ static int pm_run_resident(cvh_context *c, const CvhPmArgs &base, const Resident
     snprintf(c->pm_desc, sizeof(c->pm_desc), "kernel=%s grid=%u block=%u lds_bytes=%u steps_per_launch=%d tiles_y=%d tiles_x=%d launches=%d graph_launches=0 trips=%d planes=%d",
              nb.name, nb.grid, nb.block, nb.lds, trips < kMaxPerLaunch ? trips : kMaxPerLaunch, rg.tr, rg.tc, (trips + kMaxPerLaunch - 1) / kMaxPerLaunch, trips, c->C);
   }
-  HIPCHK(c, hipMemsetAsync(c->d_resident, 0, sizeof(CvhResident), c->stream));
+  HIPCHK(c, hipMemsetAsync(c->d_resident, 0, CVH_RESIDENT_C1_BYTES, c->stream));
   HIPCHK(c, hipEventRecord(c->ev0, c->stream));
   for (int k = 0; k < c->C; ++k) {
     HIPCHK(c, cvh_launch_pm_load(c->d_img[k], c->d_pm[0], c->n, c->stream));
@@ -404,7 +404,7 @@ extern "C" int cvh_perona_malik_batch(cvh_context *const *ctxs, int n, const dou
     if (rc != CVH_OK) return rc;
     unsigned char *const d = (unsigned char *)lead->pm_batch.d;
     HIPCHK(lead, hipMemcpyAsync(d, img.data(), bytes, hipMemcpyHostToDevice, lead->stream));
-    HIPCHK(lead, hipMemsetAsync(lead->d_resident, 0, sizeof(CvhResident), lead->stream));
+    HIPCHK(lead, hipMemsetAsync(lead->d_resident, 0, CVH_RESIDENT_C1_BYTES, lead->stream));
     HIPCHK(lead, hipEventRecord(lead->ev0, lead->stream));
     for (size_t b = 0; b < launches.size(); ++b) {
       const PmBatchLaunch &bl = launches[b];

@@ -109,6 +109,14 @@ int cvh_set_params(cvh_context *ctx, const cvh_params *p);
  *                    launch after the other wins (eight 2048 x 2048 planes: 12.1-14.7 against 16.2 us per image-iteration).  The two
  *                    flows continue each other on one context and agree to 1e-9, not bit for bit: set 0 or 1 for the same bits
  *                    whatever the chunking
+ *                    THREE CHANNELS take the resident flow on request only: 1 runs csv_resident_kernel<3, NRT> where the plane
+ *                    qualifies under the same conditions (FAST, even width, "state" 64) with tiles of at most 96 rows -- the three
+ *                    image tiles and region tables live in LDS beside the level set -- i.e. up to 256 tiles of 96 x 128: 1536 x 2048
+ *                    (1080 x 1920 fits; 2048 x 2048 x 3 does not).  A plane that does not fit keeps the per-launch flow silently;
+ *                    -1 (auto) keeps the per-launch flow for three channels.  Measured on an MI355X, resident against
+ *                    per launch, us per iteration: 256 x 256 6.6 / 8.1, 512 x 512 6.9 / 9.3, 1024 x 1024 8.3 / 13.4, 1080 x 1920
+ *                    11.9 / 17.8, 1536 x 2048 14.4 / 21.0 -- 1 pays at every three-channel size that fits, for a context that runs
+ *                    alone on its GPU (cooperative launches of different contexts serialise, as with one channel)
  *   "wave_pol"       cache policy of the streamed level-set rows: -1 auto (write-through stores while the ping-pong pairs and planes of
  *                    ALL contexts on the device that hold an image and a level set fit the Infinity Cache, <= 300 MB together; decided
  *                    when a run's first iteration is enqueued, kept for the run), 0 plain, 1 write-through
