@@ -27,7 +27,10 @@ EXPORTS = [
     "cvh_pm_trip_count", "cvh_last_run_ms", "cvh_last_pm_ms", "cvh_ppf_apply",
     "cvh_ppf_apply_device", "cvh_version", "cvh_launch_info", "cvh_enqueue_steps_batch", "cvh_run_batch",
     "cvh_perona_malik_batch",
+    "cvh_set_image_device", "cvh_get_image_device", "cvh_set_levelset_device", "cvh_get_levelset_device",
+    "cvh_get_mask_device", "cvh_set_image_device_batch", "cvh_init_checkerboard_batch", "cvh_get_mask_device_batch",
 ]
+LAYOUT_PLANAR, LAYOUT_INTERLEAVED = 0, 1
 
 
 class Params(C.Structure):
@@ -94,6 +97,14 @@ def lib():
         "cvh_enqueue_steps_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int]),
         "cvh_run_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int, ip, dp]),
         "cvh_perona_malik_batch": (C.c_int, [C.POINTER(vp), C.c_int, dp, dp, dp]),
+        "cvh_set_image_device": (C.c_int, [vp, vp, C.c_int, vp]),
+        "cvh_get_image_device": (C.c_int, [vp, vp, C.c_int, vp]),
+        "cvh_set_levelset_device": (C.c_int, [vp, vp, C.c_int, vp]),
+        "cvh_get_levelset_device": (C.c_int, [vp, vp, C.c_int, vp]),
+        "cvh_get_mask_device": (C.c_int, [vp, vp, C.c_int, vp]),
+        "cvh_set_image_device_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.POINTER(vp), C.c_int, vp]),
+        "cvh_init_checkerboard_batch": (C.c_int, [C.POINTER(vp), C.c_int]),
+        "cvh_get_mask_device_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.POINTER(vp), C.c_int, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -192,6 +203,39 @@ def perona_malik_batch(contexts, K=10.0, L=0.25, T=20.0):
         raise CvhError(rc, lib().cvh_last_error(None).decode())
 
 
+def _address_array(ptrs, n):
+    if len(ptrs) != n:
+        raise ValueError(f"{len(ptrs)} device pointers for {n} members")
+    return (C.c_void_p * max(n, 1))(*[int(p) or None for p in ptrs])
+
+
+def _batch_chk(rc):
+    if rc != CVH_OK:
+        raise CvhError(rc, lib().cvh_last_error(None).decode())
+
+
+def set_image_device_batch(contexts, ptrs, layout=LAYOUT_PLANAR, stream=0):
+    """cvh_set_image_device_batch: every context takes its image from device memory (ptrs: one integer address per context, uint8,
+    planar or interleaved), one launch for all; ordered behind what `stream` (a HIP stream handle as integer, 0 = default) holds."""
+    contexts = list(contexts)
+    n = len(contexts)
+    _batch_chk(lib().cvh_set_image_device_batch(_member_array(contexts), n, _address_array(list(ptrs), n), int(layout), int(stream) or None))
+
+
+def init_checkerboard_batch(contexts):
+    """cvh_init_checkerboard_batch: Context.init_checkerboard for every context with one copy and one launch."""
+    contexts = list(contexts)
+    _batch_chk(lib().cvh_init_checkerboard_batch(_member_array(contexts), len(contexts)))
+
+
+def get_mask_device_batch(contexts, ptrs, invert=False, stream=0):
+    """cvh_get_mask_device_batch: every context's mask into device memory (ptrs: one integer address of h * w bytes per context),
+    one launch for all; work enqueued on `stream` afterwards sees the masks.  Does not block the host."""
+    contexts = list(contexts)
+    n = len(contexts)
+    _batch_chk(lib().cvh_get_mask_device_batch(_member_array(contexts), n, _address_array(list(ptrs), n), int(bool(invert)), int(stream) or None))
+
+
 class Context:
     """One image on one GPU: thin RAII wrapper over cvh_context."""
 
@@ -243,6 +287,22 @@ class Context:
     def set_image(self, planes):
         keep, arr = self._plane_array(planes)
         self._chk(self._L.cvh_set_image(self._h, arr))
+
+    # device-memory forms: `ptr` is an integer device address, `stream` a HIP stream handle as integer (0 = the default stream)
+    def set_image_device(self, ptr, layout=LAYOUT_PLANAR, stream=0):
+        self._chk(self._L.cvh_set_image_device(self._h, int(ptr) or None, int(layout), int(stream) or None))
+
+    def get_image_device(self, ptr, layout=LAYOUT_PLANAR, stream=0):
+        self._chk(self._L.cvh_get_image_device(self._h, int(ptr) or None, int(layout), int(stream) or None))
+
+    def set_levelset_device(self, ptr, bits=64, stream=0):
+        self._chk(self._L.cvh_set_levelset_device(self._h, int(ptr) or None, int(bits), int(stream) or None))
+
+    def get_levelset_device(self, ptr, bits=64, stream=0):
+        self._chk(self._L.cvh_get_levelset_device(self._h, int(ptr) or None, int(bits), int(stream) or None))
+
+    def get_mask_device(self, ptr, invert=False, stream=0):
+        self._chk(self._L.cvh_get_mask_device(self._h, int(ptr) or None, int(bool(invert)), int(stream) or None))
 
     def get_image(self):
         outs = [np.empty((self.h, self.w), dtype=np.uint8) for _ in range(self.channels)]

@@ -132,6 +132,10 @@ extern "C" void cvh_destroy(cvh_context *c)
   if (c->d_res_halo) (void)hipFree(c->d_res_halo);
   if (c->d_pm_halo) (void)hipFree(c->d_pm_halo);
   free_table(&c->pm_batch);
+  free_table(&c->io_table);
+  if (c->h_io) (void)hipHostFree(c->h_io);
+  if (c->ev_io_in) (void)hipEventDestroy(c->ev_io_in);
+  if (c->ev_io_out) (void)hipEventDestroy(c->ev_io_out);
   if (c->h_resident) (void)hipHostFree(c->h_resident);
   if (c->d_bounds) (void)hipFree(c->d_bounds);
   if (c->h_status) (void)hipHostFree(c->h_status);
@@ -241,8 +245,6 @@ extern "C" int cvh_set_params(cvh_context *c, const cvh_params *p)
   c->p = *p;
   return CVH_OK;
 }
-
-static int adopt_f32_state(cvh_context *c);
 
 extern "C" int cvh_set_option(cvh_context *c, const char *key, long value)
 {
@@ -382,7 +384,7 @@ extern "C" int cvh_set_option(cvh_context *c, const char *key, long value)
 // tol-free part of the stop condition, src/main.cpp:950-959 (zero-initialised accumulator, channels added serially in k,
 // scaled by 1/C, L2 norm with four squares per step added left to right).  (sum_k I_k)/C squared takes one of 255 C + 1
 // values: the table keeps the reference's rounding and summation order while the loop is integer adds and lookups.
-static double stop_norm_host(const std::vector<const uint8_t *> &planes, size_t n)
+double stop_norm_host(const std::vector<const uint8_t *> &planes, size_t n)
 {
   const int C = (int)planes.size();
   const double inv = 1.0 / C;
@@ -458,7 +460,7 @@ extern "C" int cvh_get_image(cvh_context *c, uint8_t *const *planes)
 
 // FP32 state: the float buffers (lazily allocated) take over the level set that d_u[current] holds -- rounded to float, and d_u[current]
 // is rewritten with the rounded values, so that whatever reads the mirror (initial sums, mask, get) sees what the kernels iterate on.
-static int adopt_f32_state(cvh_context *c)
+int adopt_f32_state(cvh_context *c)
 {
   if (!c->d_uf_slab) {
     const size_t each = (((c->n + 64) * sizeof(float)) + ((size_t)2 << 20) - 1) & ~(((size_t)2 << 20) - 1);

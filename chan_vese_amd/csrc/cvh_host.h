@@ -94,6 +94,12 @@ struct cvh_context {
   int res_straight = 1;          // diagnostic option "res_straight": 0 = the generic march of csv_resident_kernel whatever the tile height
   int pm_resident_cap = -1;      // workgroups of pm_resident_kernel the device holds at once (-1: not asked yet)
   unsigned pm_res_serial = 0;    // launches of pm_resident_kernel so far (tag of the border entries; 0 = the cleared buffer)
+  // device-memory I/O led by this context (io_run.hip): the member table, sums and sine factors of a call on the device, their pinned
+  // host image (also the landing place of sums and fetched planes), and the events that order a call against the caller's stream
+  DeviceTable io_table;
+  void *h_io = nullptr;
+  size_t h_io_cap = 0;
+  hipEvent_t ev_io_in = nullptr, ev_io_out = nullptr;   // ev_io_out also marks the last read of h_io by a copy still in flight
   DeviceTable pm_batch;          // Perona-Malik batches led by this context (cvh_perona_malik_batch): plane tables, workgroup maps
   int resident_opt = -1;         // option "resident": -1 auto (on where it applies, unless a per-launch knob was set), 0 off, 1 on where it applies
   int resident_cap = -1;         // workgroups the device holds at once (-1: not asked yet, 0: unavailable)
@@ -159,6 +165,8 @@ int fail(cvh_context *ctx, int code, const char *fmt, ...);
 bool run_is_alone(const cvh_context *c);
 double live_footprint(const cvh_context *c);
 int image_stats(cvh_context *c, const uint8_t *const *host_planes);
+double stop_norm_host(const std::vector<const uint8_t *> &planes, size_t n);
+int adopt_f32_state(cvh_context *c);
 int ensure_f64_mirror(cvh_context *c);
 int reset_run_impl(cvh_context *c);
 void fill_atan_tables(double *tab);

@@ -198,7 +198,30 @@ struct CvhPmBatchArgs { const CvhPmBatchPlane *planes; const unsigned *map; int 
 // uint8 plane <-> FP64 state of one plane of a batch's load / store launch
 struct CvhPmIoPlane { uint8_t *img; double *state; unsigned long long n; };
 
-// ---- launchers (csv_kernels.hip / pm_kernels.hip / misc_kernels.hip) ----
+// Device-memory I/O (io_kernels.hip, io_run.hip): one entry per member of a batch kernel's grid.  A kernel reads the fields its operation
+// names; the host leaves the others zero.  The table lives in the leader's device table, 16-byte aligned entries.
+struct CvhIoMember {
+  const void *src;                    // ingest: the caller's bytes; mask: the level set (double); checkerboard: the h row factors
+  const void *src2;                   // checkerboard: the w column factors
+  void *dst;                          // mask / interleaved planes out: the caller's buffer; checkerboard: the level set
+  uint8_t *plane[CVH_MAX_CHANNELS];   // the context's planes (ingest: written; planes out: read)
+  unsigned long long *sums;           // ingest: {sum p, sum p^2} per plane, zeroed before the launch
+  int *state_zero;                    // checkerboard: the four run words of CvhState a new run clears (steps_done, stopped, ticket, pending)
+  long long *chain_zero;              // checkerboard: the chain-mode sum set a new run clears (64 integers)
+  unsigned long long n;               // pixels
+  int h, w, C;
+  int interleaved;                    // ingest: the source is h * w * C interleaved bytes (planar otherwise)
+  unsigned first, nblk;               // workgroups first .. first + nblk - 1 of the grid are this member's (first ascending, member 0 at 0)
+};
+
+// ---- launchers (csv_kernels.hip / pm_kernels.hip / misc_kernels.hip / io_kernels.hip) ----
+unsigned cvh_io_blocks(size_t n);                    // workgroups of a member in the ingest / mask / planes-out grids
+unsigned cvh_io_checkerboard_blocks(int h, int w);
+hipError_t cvh_launch_io_ingest(const CvhIoMember *tab, int nmem, unsigned grid, hipStream_t s);
+hipError_t cvh_launch_io_checkerboard(const CvhIoMember *tab, int nmem, unsigned grid, hipStream_t s);
+hipError_t cvh_launch_io_mask(const CvhIoMember *tab, int nmem, unsigned grid, int invert, hipStream_t s);
+hipError_t cvh_launch_io_image_out3(const CvhIoMember *tab, int nmem, unsigned grid, hipStream_t s);
+hipError_t cvh_launch_io_narrow(const double *u, float *out, size_t n, hipStream_t s);   // out = (float)u
 // rows-per-tile options of the step kernel
 void cvh_step_grid(int h, int w, int tile_rows, int *tiles_x, int *tiles_y);
 int cvh_step_max_blocks(int h, int w);

@@ -1,0 +1,286 @@
+// io_kernels.hip — device-memory input and output of contexts and batches of contexts (gfx950): ingest of uint8 images with their sums,
+// the checkerboard level set, mask / level-set / plane egress.  Batch kernels: ONE grid serves N members, a member owning the workgroups
+// first .. first + nblk - 1; the member table (CvhIoMember, cvh_internal.h) is read with wave-uniform indices, i.e. through the scalar
+// cache.  The single-context entry points launch the same kernels with a table of one member.
+#include "cvh_internal.h"
+
+namespace {
+
+// The table hands the kernels generic pointers; everything they point at is global memory (device, managed or mapped host memory: checked
+// by the host), so the kernels address it in the global address space -- global_load / global_store, not flat operations, which would also
+// count against LDS.
+#define CVH_GLOBAL __attribute__((address_space(1)))
+typedef CVH_GLOBAL const uint8_t *gbytes_in;
+typedef CVH_GLOBAL uint8_t *gbytes_out;
+
+// 16 bytes at ANY byte address (a caller's tensor view): the code object runs in unaligned-access mode, where one global dwordx4
+// instruction takes them; the context's own buffers are addressed as uint4 (16-byte aligned by construction)
+typedef unsigned v4u __attribute__((ext_vector_type(4)));   // (compiler vector types: a class type cannot live in an address space)
+typedef v4u v4u_any __attribute__((aligned(1)));
+typedef double v2d __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ uint4 load16_any(gbytes_in p)
+{
+  const v4u v = *(CVH_GLOBAL const v4u_any *)p;
+  return make_uint4(v.x, v.y, v.z, v.w);
+}
+__device__ __forceinline__ void store16_any(gbytes_out p, uint4 v)
+{
+  const v4u o = {v.x, v.y, v.z, v.w};
+  *(CVH_GLOBAL v4u_any *)p = o;
+}
+__device__ __forceinline__ uint4 load16(gbytes_in p, size_t q)    // piece q of a 16-byte aligned buffer
+{
+  const v4u v = ((CVH_GLOBAL const v4u *)p)[q];
+  return make_uint4(v.x, v.y, v.z, v.w);
+}
+__device__ __forceinline__ void store16(gbytes_out p, size_t q, uint4 v)
+{
+  const v4u o = {v.x, v.y, v.z, v.w};
+  ((CVH_GLOBAL v4u *)p)[q] = o;
+}
+
+// the member whose section holds this workgroup (first is ascending, tab[0].first == 0): wave-uniform
+__device__ __forceinline__ int io_member(const CvhIoMember *tab, int nmem)
+{
+  int lo = 0, hi = nmem - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (tab[mid].first <= blockIdx.x) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+__device__ __forceinline__ void add_bytes(const uint4 v, unsigned &s1, unsigned &s2)
+{
+  const unsigned wds[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+#pragma unroll
+    for (int b = 0; b < 4; ++b) { const unsigned x = (wds[i] >> (8 * b)) & 0xffu; s1 += x; s2 += x * x; }
+  }
+}
+
+// byte `i` (0 .. 11) of the 12 bytes {a, b, c}
+__device__ __forceinline__ unsigned byte12(unsigned a, unsigned b, unsigned c, int i)
+{
+  const unsigned w = i < 4 ? a : (i < 8 ? b : c);
+  return (w >> (8 * (i & 3))) & 0xffu;
+}
+
+// 48 interleaved bytes (16 pixels x 3 channels, in[0..11]) -> 16 bytes per channel
+__device__ __forceinline__ void split3(const unsigned in[12], uint4 out[3])
+{
+  unsigned o[3][4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {   // pixels 4j .. 4j + 3 are the 12 bytes in[3j .. 3j + 2]
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+      o[k][j] = byte12(in[3 * j], in[3 * j + 1], in[3 * j + 2], k) | (byte12(in[3 * j], in[3 * j + 1], in[3 * j + 2], k + 3) << 8) |
+                (byte12(in[3 * j], in[3 * j + 1], in[3 * j + 2], k + 6) << 16) | (byte12(in[3 * j], in[3 * j + 1], in[3 * j + 2], k + 9) << 24);
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) out[k] = make_uint4(o[k][0], o[k][1], o[k][2], o[k][3]);
+}
+
+// 16 bytes per channel -> 48 interleaved bytes
+__device__ __forceinline__ void join3(const uint4 in[3], unsigned out[12])
+{
+  const unsigned p[3][4] = {{in[0].x, in[0].y, in[0].z, in[0].w}, {in[1].x, in[1].y, in[1].z, in[1].w}, {in[2].x, in[2].y, in[2].z, in[2].w}};
+#pragma unroll
+  for (int d = 0; d < 12; ++d) {
+    unsigned v = 0;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const int i = 4 * d + b, px = i / 3, k = i % 3;   // byte i of the 48 is channel k of pixel px
+      v |= ((p[k][px >> 2] >> (8 * (px & 3))) & 0xffu) << (8 * b);
+    }
+    out[d] = v;
+  }
+}
+
+// Ingest: the caller's uint8 bytes become the member's planes, and sum p / sum p^2 of every plane are added to the member's sums as exact
+// 64-bit integers (what image_sums_kernel produces; integer sums do not depend on the order).  A lane moves 16 pixels per trip; the
+// n % 16 last pixels go byte by byte.  Every source byte is read once.
+__global__ void __launch_bounds__(CVH_BLOCK) io_ingest_kernel(const CvhIoMember *tab, int nmem)
+{
+  __shared__ unsigned long long sh[4][6];
+  const CvhIoMember *m = tab + io_member(tab, nmem);
+  const int C = m->C;
+  const size_t n = m->n, pieces = n / 16;
+  const size_t t0 = (size_t)(blockIdx.x - m->first) * CVH_BLOCK + threadIdx.x, stride = (size_t)m->nblk * CVH_BLOCK;
+  const gbytes_in src = (gbytes_in)m->src;
+  const gbytes_out plane[3] = {(gbytes_out)m->plane[0], (gbytes_out)m->plane[1], (gbytes_out)m->plane[2]};
+  unsigned long long acc[6] = {0, 0, 0, 0, 0, 0};
+  if (m->interleaved && C == 3) {   // (wave-uniform: a member's layout)
+    unsigned s1[3] = {0, 0, 0}, s2[3] = {0, 0, 0};   // flushed every 256 pieces: 256 * 16 * 65025 < 2^32
+    int pending = 0;
+    for (size_t q = t0; q < pieces; q += stride) {
+      const uint4 a = load16_any(src + 48 * q), b = load16_any(src + 48 * q + 16), c = load16_any(src + 48 * q + 32);
+      const unsigned in[12] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w};
+      uint4 out[3];
+      split3(in, out);
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        store16(plane[k], q, out[k]);
+        add_bytes(out[k], s1[k], s2[k]);
+      }
+      if (++pending == 256) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { acc[2 * k] += s1[k]; acc[2 * k + 1] += s2[k]; s1[k] = s2[k] = 0; }
+        pending = 0;
+      }
+    }
+    for (size_t q = pieces * 16 + t0; q < n; q += stride) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) { const unsigned x = src[3 * q + k]; plane[k][q] = (uint8_t)x; s1[k] += x; s2[k] += x * x; }
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { acc[2 * k] += s1[k]; acc[2 * k + 1] += s2[k]; }
+  } else {
+    for (int k = 0; k < C; ++k) {
+      const gbytes_in s = src + (size_t)k * n;
+      const gbytes_out d = plane[k];
+      unsigned s1 = 0, s2 = 0;
+      int pending = 0;
+      for (size_t q = t0; q < pieces; q += stride) {
+        const uint4 v = load16_any(s + 16 * q);
+        store16(d, q, v);
+        add_bytes(v, s1, s2);
+        if (++pending == 256) { acc[2 * k] += s1; acc[2 * k + 1] += s2; s1 = s2 = 0; pending = 0; }
+      }
+      for (size_t q = pieces * 16 + t0; q < n; q += stride) { const unsigned x = s[q]; d[q] = (uint8_t)x; s1 += x; s2 += x * x; }
+      acc[2 * k] += s1; acc[2 * k + 1] += s2;
+    }
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int s = 0; s < 6; ++s) {
+    unsigned long long v = acc[s];
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    if (lane == 0) sh[wave][s] = v;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < 2 * C) atomicAdd(&m->sums[threadIdx.x], sh[0][threadIdx.x] + sh[1][threadIdx.x] + sh[2][threadIdx.x] + sh[3][threadIdx.x]);
+}
+
+// levelset_checkerboard for N members (checkerboard_kernel's arithmetic, misc_kernels.hip): src = the h row factors, src2 = the w column
+// factors, both from the host's libm; dst = the level set.  A member's first workgroup also clears what a new run clears (reset_run_impl):
+// the four run words of its state block and the chain-mode sum set behind the current one.
+__global__ void __launch_bounds__(CVH_BLOCK) io_checkerboard_kernel(const CvhIoMember *tab, int nmem)
+{
+  const CvhIoMember *m = tab + io_member(tab, nmem);
+  const int h = m->h, w = m->w, wg = (int)(blockIdx.x - m->first), nblk = (int)m->nblk;
+  CVH_GLOBAL const double *si = (CVH_GLOBAL const double *)m->src, *sj = (CVH_GLOBAL const double *)m->src2;
+  CVH_GLOBAL double *u = (CVH_GLOBAL double *)m->dst;
+  if (wg == 0) {
+    if (threadIdx.x < 4) ((CVH_GLOBAL int *)m->state_zero)[threadIdx.x] = 0;
+    if (threadIdx.x < 64) ((CVH_GLOBAL long long *)m->chain_zero)[threadIdx.x] = 0;
+  }
+  for (int i = wg; i < h; i += nblk) {
+    const double s = si[i];
+    for (int j = (int)threadIdx.x; j < w; j += CVH_BLOCK) {
+      const double z = s * sj[j];
+      u[(size_t)i * w + j] = (z == 0) ? 0.0 : (z < 0 ? -1.0 : 1.0);
+    }
+  }
+}
+
+__device__ __forceinline__ unsigned mask_bit(double u, int invert) { return (((float)u > 0.0f) ? 1u : 0u) ^ (unsigned)invert; }
+
+// mask = ((float)u > 0), optionally inverted (src/main.cpp:395-400), N members: a lane reads 16 doubles (two 64-byte row pieces) and writes
+// 16 bytes to the caller's buffer (any alignment)
+__global__ void __launch_bounds__(CVH_BLOCK) io_mask_kernel(const CvhIoMember *tab, int nmem, int invert)
+{
+  const CvhIoMember *m = tab + io_member(tab, nmem);
+  const size_t n = m->n, pieces = n / 16;
+  const size_t t0 = (size_t)(blockIdx.x - m->first) * CVH_BLOCK + threadIdx.x, stride = (size_t)m->nblk * CVH_BLOCK;
+  CVH_GLOBAL const double *u = (CVH_GLOBAL const double *)m->src;
+  const gbytes_out out = (gbytes_out)m->dst;
+  for (size_t q = t0; q < pieces; q += stride) {
+    CVH_GLOBAL const v2d *p = (CVH_GLOBAL const v2d *)(u + 16 * q);
+    unsigned wds[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const v2d a = p[2 * i], b = p[2 * i + 1];
+      wds[i] = mask_bit(a.x, invert) | (mask_bit(a.y, invert) << 8) | (mask_bit(b.x, invert) << 16) | (mask_bit(b.y, invert) << 24);
+    }
+    store16_any(out + 16 * q, make_uint4(wds[0], wds[1], wds[2], wds[3]));
+  }
+  for (size_t q = pieces * 16 + t0; q < n; q += stride) out[q] = (uint8_t)mask_bit(u[q], invert);
+}
+
+// the member's planes into the caller's interleaved h * w * 3 bytes
+__global__ void __launch_bounds__(CVH_BLOCK) io_image_out3_kernel(const CvhIoMember *tab, int nmem)
+{
+  const CvhIoMember *m = tab + io_member(tab, nmem);
+  const size_t n = m->n, pieces = n / 16;
+  const size_t t0 = (size_t)(blockIdx.x - m->first) * CVH_BLOCK + threadIdx.x, stride = (size_t)m->nblk * CVH_BLOCK;
+  const gbytes_out out = (gbytes_out)m->dst;
+  const gbytes_in plane[3] = {(gbytes_in)m->plane[0], (gbytes_in)m->plane[1], (gbytes_in)m->plane[2]};
+  for (size_t q = t0; q < pieces; q += stride) {
+    uint4 in[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) in[k] = load16(plane[k], q);
+    unsigned o[12];
+    join3(in, o);
+#pragma unroll
+    for (int t = 0; t < 3; ++t) store16_any(out + 48 * q + 16 * t, make_uint4(o[4 * t], o[4 * t + 1], o[4 * t + 2], o[4 * t + 3]));
+  }
+  for (size_t q = pieces * 16 + t0; q < n; q += stride) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) out[3 * q + k] = plane[k][q];
+  }
+}
+
+// level set out as float, rounded to nearest even (state_narrow_kernel's rule); the context's doubles stay as they are
+__global__ void io_narrow_kernel(const double *u, float *out, size_t n)
+{
+  for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < n; q += (size_t)gridDim.x * blockDim.x) out[q] = (float)u[q];
+}
+
+}  // namespace
+
+// workgroups of a member of n pixels in a kernel whose lanes move 16 pixels per trip
+unsigned cvh_io_blocks(size_t n)
+{
+  const size_t b = (n / 16 + CVH_BLOCK) / CVH_BLOCK;
+  return (unsigned)(b > 2048 ? 2048 : b);
+}
+
+unsigned cvh_io_checkerboard_blocks(int h, int w)
+{
+  const size_t b = ((size_t)h * w + 8191) / 8192;
+  const size_t cap = h < 1024 ? h : 1024;
+  return (unsigned)(b > cap ? cap : (b < 1 ? 1 : b));
+}
+
+hipError_t cvh_launch_io_ingest(const CvhIoMember *tab, int nmem, unsigned grid, hipStream_t s)
+{
+  hipLaunchKernelGGL(io_ingest_kernel, dim3(grid), dim3(CVH_BLOCK), 0, s, tab, nmem);
+  return hipGetLastError();
+}
+
+hipError_t cvh_launch_io_checkerboard(const CvhIoMember *tab, int nmem, unsigned grid, hipStream_t s)
+{
+  hipLaunchKernelGGL(io_checkerboard_kernel, dim3(grid), dim3(CVH_BLOCK), 0, s, tab, nmem);
+  return hipGetLastError();
+}
+
+hipError_t cvh_launch_io_mask(const CvhIoMember *tab, int nmem, unsigned grid, int invert, hipStream_t s)
+{
+  hipLaunchKernelGGL(io_mask_kernel, dim3(grid), dim3(CVH_BLOCK), 0, s, tab, nmem, invert ? 1 : 0);
+  return hipGetLastError();
+}
+
+hipError_t cvh_launch_io_image_out3(const CvhIoMember *tab, int nmem, unsigned grid, hipStream_t s)
+{
+  hipLaunchKernelGGL(io_image_out3_kernel, dim3(grid), dim3(CVH_BLOCK), 0, s, tab, nmem);
+  return hipGetLastError();
+}
+
+hipError_t cvh_launch_io_narrow(const double *u, float *out, size_t n, hipStream_t s)
+{
+  hipLaunchKernelGGL(io_narrow_kernel, dim3((unsigned)((n + 255) / 256 < 16384 ? (n + 255) / 256 : 16384)), dim3(256), 0, s, u, out, n);
+  return hipGetLastError();
+}

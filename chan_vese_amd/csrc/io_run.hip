@@ -1,0 +1,424 @@
+// io_run.hip — host side of the device-memory entry points (include/chanvese_hip.h): contexts and batches of contexts are fed from, and
+// read into, device memory the caller owns, ordered against the caller's stream by events; one launch per batch and operation.
+// The single-context calls are batches of one member: one code path.
+#include <thread>
+
+#include "cvh_host.h"
+
+namespace {
+
+inline size_t align_up(size_t v, size_t a) { return (v + a - 1) & ~(a - 1); }
+
+// nothing is thrown across the C boundary: a failed host allocation inside body() becomes CVH_ERR_NOMEM
+template <class F>
+int guarded(cvh_context *const *ctxs, int n, const char *what, F body)
+{
+  try { return body(); }
+  catch (...) { return batch_fail(ctxs, n, CVH_ERR_NOMEM, "%s: out of host memory", what); }
+}
+
+// Who may be in a batch, before anything is touched (the members stay as they were).  `what` names the entry point.
+int members_check(cvh_context *const *ctxs, int n, const char *what)
+{
+  if (!ctxs || n < 1) return batch_fail(ctxs, 0, CVH_ERR_ARG, "%s: empty member list (ctxs = %p, n = %d)", what, (const void *)ctxs, n);
+  for (int i = 0; i < n; ++i) {
+    cvh_context *c = ctxs[i];
+    if (!c) return batch_fail(ctxs, i ? n : 0, CVH_ERR_ARG, "%s: member %d is NULL", what, i);
+    for (int j = 0; j < i; ++j)
+      if (ctxs[j] == c) return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: member %d duplicates member %d", what, i, j);
+    if (c->device != ctxs[0]->device)
+      return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: member %d is on device %d, member 0 on device %d", what, i, c->device, ctxs[0]->device);
+  }
+  return CVH_OK;
+}
+
+// p must be memory that kernels on member i's device can address: device memory of that device, managed memory, or mapped host memory
+int pointer_check(cvh_context *const *ctxs, int n, int i, const void *p, const char *what)
+{
+  if (!p) return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: member %d: the device pointer is NULL", what, i);
+  hipPointerAttribute_t at;
+  memset(&at, 0, sizeof(at));
+  const hipError_t e = hipPointerGetAttributes(&at, p);
+  if (e != hipSuccess) (void)hipGetLastError();   // (an address the runtime does not know: not sticky)
+  const bool ok = e == hipSuccess && ((at.type == hipMemoryTypeDevice && at.device == ctxs[i]->device) || at.type == hipMemoryTypeManaged ||
+                                      (at.type == hipMemoryTypeHost && at.devicePointer != nullptr));
+  if (!ok) return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: member %d: %p is not device-accessible memory of device %d", what, i, p, ctxs[i]->device);
+  return CVH_OK;
+}
+
+// iterations enqueued and never synchronised are closed first, as the host-buffer calls do
+int settle(cvh_context *const *ctxs, int n, const char *what)
+{
+  for (int i = 0; i < n; ++i) {
+    cvh_context *c = ctxs[i];
+    if (!(c->timing_open || c->chain_pending)) continue;
+    const int rc = sync_impl(c);
+    if (rc != CVH_OK) return batch_fail(ctxs, n, rc, "%s: member %d: %s", what, i, c->err);
+  }
+  return CVH_OK;
+}
+
+// The leader's staging of a call: `host_bytes` of pinned memory (its first `dev_bytes` are uploaded to the device table).  The pinned
+// block is rewritten only when the last copy that read it has completed: the HOST WAITS here for the previous table-using call led by
+// this context (ev_io_out, recorded behind that call's launch) -- long past unless that call is still queued behind the caller's stream.
+int stage(cvh_context *lead, size_t host_bytes, size_t dev_bytes)
+{
+  if (!lead->ev_io_in) HIPCHK(lead, hipEventCreateWithFlags(&lead->ev_io_in, hipEventDisableTiming));
+  if (!lead->ev_io_out) HIPCHK(lead, hipEventCreateWithFlags(&lead->ev_io_out, hipEventDisableTiming));
+  HIPCHK(lead, hipEventSynchronize(lead->ev_io_out));
+  if (lead->h_io_cap < host_bytes) {
+    if (lead->h_io) { HIPCHK(lead, hipHostFree(lead->h_io)); lead->h_io = nullptr; lead->h_io_cap = 0; }
+    const size_t cap = align_up(host_bytes + host_bytes / 4, 4096);
+    HIPCHK(lead, hipHostMalloc(&lead->h_io, cap, hipHostMallocDefault));
+    lead->h_io_cap = cap;
+  }
+  return grow_table(lead, &lead->io_table, dev_bytes);
+}
+
+// Before: the leader's stream waits for every member's stream (as cvh_enqueue_steps_batch) and for what the caller has enqueued on
+// `stream` so far.  The host waits for nothing.
+int open_call(cvh_context *const *ctxs, int n, void *stream)
+{
+  cvh_context *lead = ctxs[0];
+  if (!lead->ev_io_in) HIPCHK(lead, hipEventCreateWithFlags(&lead->ev_io_in, hipEventDisableTiming));
+  if (!lead->ev_io_out) HIPCHK(lead, hipEventCreateWithFlags(&lead->ev_io_out, hipEventDisableTiming));
+  for (int i = 1; i < n; ++i)
+    if (!ctxs[i]->ev_join) HIPCHK(ctxs[i], hipEventCreateWithFlags(&ctxs[i]->ev_join, hipEventDisableTiming));
+  { const int rc = join_into_leader(ctxs, n); if (rc != CVH_OK) return rc; }
+  HIPCHK(lead, hipEventRecord(lead->ev_io_in, (hipStream_t)stream));
+  HIPCHK(lead, hipStreamWaitEvent(lead->stream, lead->ev_io_in, 0));
+  return CVH_OK;
+}
+
+// After: every member's stream, and with to_caller the caller's, waits for the leader's last launch
+int close_call(cvh_context *const *ctxs, int n, void *stream, bool to_caller)
+{
+  cvh_context *lead = ctxs[0];
+  HIPCHK(lead, hipEventRecord(lead->ev_io_out, lead->stream));
+  for (int i = 1; i < n; ++i) HIPCHK(ctxs[i], hipStreamWaitEvent(ctxs[i]->stream, lead->ev_io_out, 0));
+  if (to_caller) HIPCHK(lead, hipStreamWaitEvent((hipStream_t)stream, lead->ev_io_out, 0));
+  return CVH_OK;
+}
+
+// sections of the grid: member i owns nblk[i] workgroups behind those of the members before it
+unsigned lay_out(CvhIoMember *tab, int n)
+{
+  unsigned first = 0;
+  for (int i = 0; i < n; ++i) { tab[i].first = first; first += tab[i].nblk; }
+  return first;
+}
+
+int ingest(cvh_context *const *ctxs, int n, const uint8_t *const *d_imgs, int layout, void *stream, const char *what)
+{
+  int rc = members_check(ctxs, n, what);
+  if (rc != CVH_OK) return rc;
+  if (!d_imgs) return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: the list of device pointers is NULL", what);
+  if (layout != CVH_LAYOUT_PLANAR && layout != CVH_LAYOUT_INTERLEAVED)
+    return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: layout must be CVH_LAYOUT_PLANAR (0) or CVH_LAYOUT_INTERLEAVED (1), got %d", what, layout);
+  cvh_context *lead = ctxs[0];
+  HIPCHK(lead, hipSetDevice(lead->device));
+  for (int i = 0; i < n; ++i) { rc = pointer_check(ctxs, n, i, d_imgs[i], what); if (rc != CVH_OK) return rc; }
+  rc = settle(ctxs, n, what);
+  if (rc != CVH_OK) return rc;
+  // staging: [member table][8 sums per member, zero] uploaded; behind them the planes of the members whose stop norm the host takes
+  const size_t sums_off = align_up((size_t)n * sizeof(CvhIoMember), 256), dev_bytes = sums_off + (size_t)n * 8 * sizeof(unsigned long long);
+  std::vector<size_t> fetch_off((size_t)n, 0);
+  size_t host_bytes = dev_bytes;
+  for (int i = 0; i < n; ++i) {
+    const cvh_context *c = ctxs[i];
+    if (c->C == 1 && c->n < ((size_t)1 << 36)) continue;   // exact on the device: 2^36 * 255^2 < 2^53 (image_stats)
+    fetch_off[i] = host_bytes = align_up(host_bytes, 256);
+    host_bytes += c->img_stride * c->C;
+  }
+  rc = stage(lead, host_bytes, dev_bytes);
+  if (rc != CVH_OK) return rc;
+  unsigned char *const hb = (unsigned char *)lead->h_io, *const db = (unsigned char *)lead->io_table.d;
+  memset(hb, 0, dev_bytes);
+  CvhIoMember *tab = (CvhIoMember *)hb;
+  for (int i = 0; i < n; ++i) {
+    const cvh_context *c = ctxs[i];
+    CvhIoMember &m = tab[i];
+    m.src = d_imgs[i];
+    for (int k = 0; k < c->C; ++k) m.plane[k] = c->d_img[k];
+    m.sums = (unsigned long long *)(db + sums_off) + (size_t)8 * i;
+    m.n = c->n; m.h = c->h; m.w = c->w; m.C = c->C;
+    m.interleaved = layout == CVH_LAYOUT_INTERLEAVED;
+    m.nblk = cvh_io_blocks(c->n);
+  }
+  const unsigned grid = lay_out(tab, n);
+  rc = open_call(ctxs, n, stream);
+  if (rc != CVH_OK) return rc;
+  HIPCHK(lead, hipMemcpyAsync(db, hb, dev_bytes, hipMemcpyHostToDevice, lead->stream));
+  HIPCHK(lead, cvh_launch_io_ingest((const CvhIoMember *)db, n, grid, lead->stream));
+  HIPCHK(lead, hipMemcpyAsync(hb + sums_off, db + sums_off, (size_t)n * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, lead->stream));
+  std::vector<int> on_host;
+  for (int i = 0; i < n; ++i) {
+    if (!fetch_off[i]) continue;
+    const cvh_context *c = ctxs[i];
+    HIPCHK(lead, hipMemcpyAsync(hb + fetch_off[i], c->d_img_slab, c->img_stride * (c->C - 1) + c->n, hipMemcpyDeviceToHost, lead->stream));
+    on_host.push_back(i);
+  }
+  rc = close_call(ctxs, n, stream, false);
+  if (rc != CVH_OK) return rc;
+  HIPCHK(lead, hipStreamSynchronize(lead->stream));   // the ONE host wait of the call: the sums come back to host fields
+  const unsigned long long *sums = (const unsigned long long *)(hb + sums_off);
+  // three channels: (sum_k I_k)/3 is rounded per pixel and the reference adds the squares serially (stop_norm_host); members in parallel
+  std::vector<double> norm((size_t)n, 0.0);
+  auto host_norm = [&](int i) {
+    const cvh_context *c = ctxs[i];
+    std::vector<const uint8_t *> pl;
+    for (int k = 0; k < c->C; ++k) pl.push_back(hb + fetch_off[i] + (size_t)k * c->img_stride);
+    norm[i] = stop_norm_host(pl, c->n);
+  };
+  const int nthreads = (int)std::min<size_t>(16, on_host.size());
+  if (nthreads > 1) {
+    std::vector<std::thread> pool;
+    try {
+      for (int t = 0; t < nthreads; ++t)
+        pool.emplace_back([&, t]() { for (size_t q = (size_t)t; q < on_host.size(); q += (size_t)nthreads) host_norm(on_host[q]); });
+    } catch (...) {
+      for (std::thread &th : pool) th.join();
+      pool.clear();
+      for (int i : on_host) host_norm(i);   // (no thread to be had: one after the other)
+    }
+    for (std::thread &th : pool) th.join();
+  } else {
+    for (int i : on_host) host_norm(i);
+  }
+  for (int i = 0; i < n; ++i) {
+    cvh_context *c = ctxs[i];
+    for (int k = 0; k < c->C; ++k) c->sum_img[k] = (double)sums[8 * i + 2 * k];   // exact: < 2^53
+    c->stop_norm = fetch_off[i] ? norm[i] : sqrt((double)sums[8 * i + 1]);
+    c->stop_valid = true;
+    c->have_image = true;
+    c->sums_valid = false;
+  }
+  return CVH_OK;
+}
+
+int mask_out(cvh_context *const *ctxs, int n, uint8_t *const *d_masks, int invert, void *stream, const char *what)
+{
+  int rc = members_check(ctxs, n, what);
+  if (rc != CVH_OK) return rc;
+  if (!d_masks) return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: the list of device pointers is NULL", what);
+  cvh_context *lead = ctxs[0];
+  HIPCHK(lead, hipSetDevice(lead->device));
+  for (int i = 0; i < n; ++i) { rc = pointer_check(ctxs, n, i, d_masks[i], what); if (rc != CVH_OK) return rc; }
+  for (int i = 0; i < n; ++i)   // (the arguments first, then the members' state: as the single-context getters)
+    if (!ctxs[i]->have_u) return batch_fail(ctxs, n, CVH_ERR_STATE, "%s: member %d has no level set", what, i);
+  rc = settle(ctxs, n, what);
+  if (rc != CVH_OK) return rc;
+  for (int i = 0; i < n; ++i) {
+    rc = ensure_f64_mirror(ctxs[i]);
+    if (rc != CVH_OK) return batch_fail(ctxs, n, rc, "%s: member %d: %s", what, i, ctxs[i]->err);
+  }
+  const size_t bytes = (size_t)n * sizeof(CvhIoMember);
+  rc = stage(lead, bytes, bytes);
+  if (rc != CVH_OK) return rc;
+  CvhIoMember *tab = (CvhIoMember *)lead->h_io;
+  memset(tab, 0, bytes);
+  for (int i = 0; i < n; ++i) {
+    const cvh_context *c = ctxs[i];
+    tab[i].src = c->d_u[current_buffer(c)];
+    tab[i].dst = d_masks[i];
+    tab[i].n = c->n; tab[i].h = c->h; tab[i].w = c->w; tab[i].C = c->C;
+    tab[i].nblk = cvh_io_blocks(c->n);
+  }
+  const unsigned grid = lay_out(tab, n);
+  rc = open_call(ctxs, n, stream);
+  if (rc != CVH_OK) return rc;
+  HIPCHK(lead, hipMemcpyAsync(lead->io_table.d, tab, bytes, hipMemcpyHostToDevice, lead->stream));
+  HIPCHK(lead, cvh_launch_io_mask((const CvhIoMember *)lead->io_table.d, n, grid, invert, lead->stream));
+  return close_call(ctxs, n, stream, true);
+}
+
+// a level set moved in or out: bits is 64 (double) or 32 (float), p aligned to its element
+int levelset_args(cvh_context *c, const void *p, int bits, const char *what)
+{
+  if (bits != 64 && bits != 32) return fail(c, CVH_ERR_ARG, "%s: bits must be 64 or 32, got %d", what, bits);
+  if ((uintptr_t)p % (size_t)(bits / 8)) return fail(c, CVH_ERR_ARG, "%s: %p is not aligned to %d bytes", what, p, bits / 8);
+  return CVH_OK;
+}
+
+}  // namespace
+
+extern "C" int cvh_set_image_device_batch(cvh_context *const *ctxs, int n, const uint8_t *const *d_imgs, int layout, void *stream)
+{
+  static const char what[] = "cvh_set_image_device_batch";
+  return guarded(ctxs, n, what, [&]() { return ingest(ctxs, n, d_imgs, layout, stream, what); });
+}
+
+extern "C" int cvh_set_image_device(cvh_context *c, const uint8_t *d_img, int layout, void *stream)
+{
+  if (!c) return CVH_ERR_ARG;
+  static const char what[] = "cvh_set_image_device";
+  return guarded(&c, 1, what, [&]() { return ingest(&c, 1, &d_img, layout, stream, what); });
+}
+
+extern "C" int cvh_get_mask_device_batch(cvh_context *const *ctxs, int n, uint8_t *const *d_masks, int invert, void *stream)
+{
+  return mask_out(ctxs, n, d_masks, invert, stream, "cvh_get_mask_device_batch");
+}
+
+extern "C" int cvh_get_mask_device(cvh_context *c, uint8_t *d_mask, int invert, void *stream)
+{
+  if (!c) return CVH_ERR_ARG;
+  return mask_out(&c, 1, &d_mask, invert, stream, "cvh_get_mask_device");
+}
+
+static int checkerboard_batch(cvh_context *const *ctxs, int n, const char *what)
+{
+  int rc = members_check(ctxs, n, what);
+  if (rc != CVH_OK) return rc;
+  cvh_context *lead = ctxs[0];
+  HIPCHK(lead, hipSetDevice(lead->device));
+  rc = settle(ctxs, n, what);
+  if (rc != CVH_OK) return rc;
+  // the h + w sine factors of every distinct shape, from the host's libm as cvh_init_checkerboard's: ONE copy with the member table
+  const double pi = 3.14159265358979323846;
+  std::vector<int> shape_of((size_t)n);
+  std::vector<size_t> shape_off;
+  std::vector<int> shape_first;
+  size_t bytes = align_up((size_t)n * sizeof(CvhIoMember), 256);
+  for (int i = 0; i < n; ++i) {
+    size_t s = 0;
+    while (s < shape_first.size() && !(ctxs[shape_first[s]]->h == ctxs[i]->h && ctxs[shape_first[s]]->w == ctxs[i]->w)) ++s;
+    if (s == shape_first.size()) {
+      shape_first.push_back(i);
+      shape_off.push_back(bytes);
+      bytes += ((size_t)ctxs[i]->h + ctxs[i]->w) * sizeof(double);
+    }
+    shape_of[i] = (int)s;
+  }
+  rc = stage(lead, bytes, bytes);
+  if (rc != CVH_OK) return rc;
+  unsigned char *const hb = (unsigned char *)lead->h_io, *const db = (unsigned char *)lead->io_table.d;
+  memset(hb, 0, (size_t)n * sizeof(CvhIoMember));
+  for (size_t s = 0; s < shape_first.size(); ++s) {
+    const cvh_context *c = ctxs[shape_first[s]];
+    double *sv = (double *)(hb + shape_off[s]);
+    for (int i = 0; i < c->h; ++i) sv[i] = sin(pi * i / 5);
+    for (int j = 0; j < c->w; ++j) sv[(size_t)c->h + j] = sin(pi * j / 5);
+  }
+  CvhIoMember *tab = (CvhIoMember *)hb;
+  for (int i = 0; i < n; ++i) {
+    cvh_context *c = ctxs[i];
+    CvhIoMember &m = tab[i];
+    m.src = db + shape_off[shape_of[i]];
+    m.src2 = (const double *)m.src + c->h;
+    m.dst = c->d_u[c->chain_pb & 1];   // the buffer whose parity is the chain-mode sum set's: see cvh_set_levelset
+    m.state_zero = &c->d_state->steps_done;
+    m.chain_zero = &c->d_chain->v[(c->chain_pb + 1) & 3][0];
+    m.n = c->n; m.h = c->h; m.w = c->w; m.C = c->C;
+    m.nblk = cvh_io_checkerboard_blocks(c->h, c->w);
+  }
+  const unsigned grid = lay_out(tab, n);
+  rc = open_call(ctxs, n, nullptr);
+  if (rc != CVH_OK) return rc;
+  HIPCHK(lead, hipMemcpyAsync(db, hb, bytes, hipMemcpyHostToDevice, lead->stream));
+  HIPCHK(lead, cvh_launch_io_checkerboard((const CvhIoMember *)db, n, grid, lead->stream));
+  rc = close_call(ctxs, n, nullptr, false);
+  if (rc != CVH_OK) return rc;
+  HIPCHK(lead, hipStreamSynchronize(lead->stream));
+  for (int i = 0; i < n; ++i) {   // the launch has run: only now does the host's bookkeeping follow it
+    cvh_context *c = ctxs[i];
+    c->cur_base = c->chain_pb & 1; c->steps_done = 0; c->enqueued = 0;
+    c->have_u = true;
+    c->sums_valid = false;
+    c->mirror_valid = true;
+    if (c->state_bits == 32) {
+      rc = adopt_f32_state(c);
+      if (rc != CVH_OK) return batch_fail(ctxs, n, rc, "%s: member %d: %s", what, i, c->err);
+    }
+    // the host's share of a new run (reset_run_impl; the device's share ran inside the launch)
+    c->run_pol = -1; c->run_alone = -1; c->run_chunk = -1;
+    c->h_status[0] = 0; c->h_status[1] = 0;
+  }
+  return CVH_OK;
+}
+
+extern "C" int cvh_init_checkerboard_batch(cvh_context *const *ctxs, int n)
+{
+  static const char what[] = "cvh_init_checkerboard_batch";
+  return guarded(ctxs, n, what, [&]() { return checkerboard_batch(ctxs, n, what); });
+}
+
+extern "C" int cvh_get_image_device(cvh_context *c, uint8_t *d_img, int layout, void *stream)
+{
+  static const char what[] = "cvh_get_image_device";
+  if (!c) return CVH_ERR_ARG;
+  if (layout != CVH_LAYOUT_PLANAR && layout != CVH_LAYOUT_INTERLEAVED)
+    return fail(c, CVH_ERR_ARG, "%s: layout must be CVH_LAYOUT_PLANAR (0) or CVH_LAYOUT_INTERLEAVED (1), got %d", what, layout);
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc = pointer_check(&c, 1, 0, d_img, what);
+  if (rc != CVH_OK) return rc;
+  if (!c->have_image) return fail(c, CVH_ERR_STATE, "%s: no image set", what);
+  const bool kernel = layout == CVH_LAYOUT_INTERLEAVED && c->C == 3;
+  if (kernel) {
+    rc = stage(c, sizeof(CvhIoMember), sizeof(CvhIoMember));
+    if (rc != CVH_OK) return rc;
+  }
+  rc = open_call(&c, 1, stream);
+  if (rc != CVH_OK) return rc;
+  if (kernel) {
+    CvhIoMember *m = (CvhIoMember *)c->h_io;
+    memset(m, 0, sizeof(*m));
+    m->dst = d_img;
+    for (int k = 0; k < 3; ++k) m->plane[k] = c->d_img[k];
+    m->n = c->n; m->h = c->h; m->w = c->w; m->C = 3;
+    m->nblk = cvh_io_blocks(c->n);
+    HIPCHK(c, hipMemcpyAsync(c->io_table.d, m, sizeof(*m), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, cvh_launch_io_image_out3((const CvhIoMember *)c->io_table.d, 1, m->nblk, c->stream));
+  } else {
+    for (int k = 0; k < c->C; ++k)
+      HIPCHK(c, hipMemcpyAsync(d_img + (size_t)k * c->n, c->d_img[k], c->n, hipMemcpyDeviceToDevice, c->stream));
+  }
+  return close_call(&c, 1, stream, true);
+}
+
+extern "C" int cvh_set_levelset_device(cvh_context *c, const void *d_u, int bits, void *stream)
+{
+  static const char what[] = "cvh_set_levelset_device";
+  if (!c) return CVH_ERR_ARG;
+  int rc = levelset_args(c, d_u, bits, what);
+  if (rc != CVH_OK) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  rc = pointer_check(&c, 1, 0, d_u, what);
+  if (rc != CVH_OK) return rc;
+  rc = settle(&c, 1, what);
+  if (rc != CVH_OK) return rc;
+  const int base = c->chain_pb & 1;   // see cvh_set_levelset
+  rc = open_call(&c, 1, stream);
+  if (rc != CVH_OK) return rc;
+  if (bits == 64) HIPCHK(c, hipMemcpyAsync(c->d_u[base], d_u, c->n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  else HIPCHK(c, cvh_launch_state_widen((const float *)d_u, c->d_u[base], c->n, c->stream));   // the floats' exact double values
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->cur_base = base; c->steps_done = 0; c->enqueued = 0;   // the level set has arrived: the host's bookkeeping follows it
+  c->have_u = true;
+  c->sums_valid = false;
+  c->mirror_valid = true;
+  if (c->state_bits == 32) { rc = adopt_f32_state(c); if (rc != CVH_OK) return rc; }
+  return reset_run_impl(c);
+}
+
+extern "C" int cvh_get_levelset_device(cvh_context *c, void *d_u, int bits, void *stream)
+{
+  static const char what[] = "cvh_get_levelset_device";
+  if (!c) return CVH_ERR_ARG;
+  int rc = levelset_args(c, d_u, bits, what);
+  if (rc != CVH_OK) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  rc = pointer_check(&c, 1, 0, d_u, what);
+  if (rc != CVH_OK) return rc;
+  if (!c->have_u) return fail(c, CVH_ERR_STATE, "%s: no level set", what);
+  rc = settle(&c, 1, what);
+  if (rc != CVH_OK) return rc;
+  rc = ensure_f64_mirror(c);
+  if (rc != CVH_OK) return rc;
+  rc = open_call(&c, 1, stream);
+  if (rc != CVH_OK) return rc;
+  const double *u = c->d_u[current_buffer(c)];
+  if (bits == 64) HIPCHK(c, hipMemcpyAsync(d_u, u, c->n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  else HIPCHK(c, cvh_launch_io_narrow(u, (float *)d_u, c->n, c->stream));
+  return close_call(&c, 1, stream, true);
+}

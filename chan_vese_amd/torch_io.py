@@ -1,0 +1,141 @@
+"""Torch front end of the device-memory entry points: uint8 device tensors in, mask tensors out, nothing through host memory.
+
+Import torch FIRST (this module does): torch ships its own libamdhip64 and the loader then shares that one HIP runtime with
+libchanvese_hip.so -- the rule of capi.py.  No torch type crosses the C ABI: tensors are passed as `data_ptr()` addresses and the
+current stream as its `cuda_stream` handle; the library orders its work against that stream with events and never synchronises it.
+"""
+import torch
+
+from . import capi
+
+
+def _device_index(device):
+    return device if isinstance(device, int) else (torch.device(device).index or 0)
+
+
+def check_images(images, n, h, w, channels, device=0, layout=None):
+    """Validates a batch of images for Segmenter.segment and returns its layout (capi.LAYOUT_PLANAR / LAYOUT_INTERLEAVED).
+    ValueError for anything but a uint8 tensor of shape (N, H, W) [one channel], (N, C, H, W) or (N, H, W, C) on the CUDA/HIP device
+    `device`, each member contiguous.  A shape that is both forms -- (N, 3, 3, 3): three channels of 3 x w or h x 3 pixels -- is taken
+    as planar unless `layout` says otherwise; a `layout` the shape does not have is a ValueError.  Calls nothing in the library."""
+    if not isinstance(images, torch.Tensor):
+        raise ValueError(f"images must be a torch.Tensor, got {type(images).__name__}")
+    if images.dtype != torch.uint8:
+        raise ValueError(f"images must be uint8, got {images.dtype}")
+    shape = tuple(images.shape)
+    forms = []
+    if (channels == 1 and shape == (n, h, w)) or shape == (n, channels, h, w):
+        forms.append(capi.LAYOUT_PLANAR)
+    if shape == (n, h, w, channels):
+        forms.append(capi.LAYOUT_INTERLEAVED)
+    if forms and layout is None:
+        layout = forms[0]
+    elif forms and layout in forms:
+        pass
+    elif forms:
+        raise ValueError(f"images of shape {shape} do not have layout {layout!r}")
+    else:
+        raise ValueError(f"images of shape {shape} are neither ({n}, {channels}, {h}, {w}) nor ({n}, {h}, {w}, {channels})"
+                         + (f" nor ({n}, {h}, {w})" if channels == 1 else ""))
+    for i in range(n):
+        if not images[i].is_contiguous():
+            raise ValueError(f"images[{i}] is not contiguous (strides {tuple(images[i].stride())}): pitched sources are not supported")
+    _check_device(images, device, "images")
+    return layout
+
+
+def check_levelsets(init, n, h, w, device=0):
+    """Validates a tensor of initial level sets and returns its element width in bits (64 / 32).  ValueError otherwise."""
+    if not isinstance(init, torch.Tensor):
+        raise ValueError(f'init must be "checkerboard" or a torch.Tensor, got {init!r}')
+    if init.dtype not in (torch.float64, torch.float32):
+        raise ValueError(f"init must be float64 or float32, got {init.dtype}")
+    if tuple(init.shape) != (n, h, w):
+        raise ValueError(f"init of shape {tuple(init.shape)} is not ({n}, {h}, {w})")
+    for i in range(n):
+        if not init[i].is_contiguous():
+            raise ValueError(f"init[{i}] is not contiguous")
+    _check_device(init, device, "init")
+    return 64 if init.dtype == torch.float64 else 32
+
+
+def _check_device(t, device, name):
+    if t.device.type != "cuda" or (t.device.index or 0) != device:
+        raise ValueError(f"{name} lives on {t.device}, the contexts on cuda:{device}")
+
+
+class Segmenter:
+    """N contexts of one shape on one GPU, kept for the object's lifetime (cvh_create allocates: a stream of frames reuses them)."""
+
+    def __init__(self, n, h, w, channels=1, params=None, device=0, options=None):
+        if n < 1:
+            raise ValueError(f"n must be >= 1, got {n}")
+        self.n, self.h, self.w, self.channels = n, h, w, channels
+        self.device = _device_index(device)
+        self.contexts = []
+        try:
+            for _ in range(n):
+                ctx = capi.Context(h, w, channels, params, self.device)
+                self.contexts.append(ctx)
+                for key, value in (options or {}).items():
+                    ctx.set_option(key, value)
+        except Exception:
+            self.close()
+            raise
+
+    def close(self):
+        for ctx in self.contexts:
+            ctx.close()
+        self.contexts = []
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def _stream(self):
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def segment(self, images, max_steps=-1, perona_malik=None, init="checkerboard", invert=False, layout=None):
+        """ingest -> (Perona-Malik batch) -> initial level set -> cvh_run_batch -> masks.  Returns (masks, steps, norms): masks a uint8
+        tensor (N, H, W) on the images' device, valid for the next operation on the current stream without a host wait of the caller's;
+        steps / norms the iterations and the last ||u_diff|| of every member.  `layout` (capi.LAYOUT_*) is needed only for a shape that is
+        both planar and interleaved (check_images)."""
+        layout = check_images(images, self.n, self.h, self.w, self.channels, self.device, layout)
+        bits = None if isinstance(init, str) else check_levelsets(init, self.n, self.h, self.w, self.device)
+        if isinstance(init, str) and init != "checkerboard":
+            raise ValueError(f'init must be "checkerboard" or a tensor, got {init!r}')
+        if perona_malik is not None and len(perona_malik) != 3:
+            raise ValueError("perona_malik must be (K, L, T)")
+        stream = self._stream()
+        capi.set_image_device_batch(self.contexts, [images[i].data_ptr() for i in range(self.n)], layout, stream)
+        if perona_malik is not None:
+            K, L, T = perona_malik
+            capi.perona_malik_batch(self.contexts, K, L, T)
+        if bits is None:
+            capi.init_checkerboard_batch(self.contexts)
+        else:
+            for i, ctx in enumerate(self.contexts):
+                ctx.set_levelset_device(init[i].data_ptr(), bits, stream)
+        res = capi.run_batch(self.contexts, max_steps)
+        masks = torch.empty((self.n, self.h, self.w), dtype=torch.uint8, device=images.device)
+        capi.get_mask_device_batch(self.contexts, [masks[i].data_ptr() for i in range(self.n)], invert, stream)
+        return masks, [r[0] for r in res], [r[1] for r in res]
+
+    def levelsets(self, dtype=torch.float64):
+        """The members' level sets as a device tensor (N, H, W), float64 or float32 (rounded to nearest even)."""
+        if dtype not in (torch.float64, torch.float32):
+            raise ValueError(f"dtype must be float64 or float32, got {dtype}")
+        out = torch.empty((self.n, self.h, self.w), dtype=dtype, device=torch.device("cuda", self.device))
+        for i, ctx in enumerate(self.contexts):
+            ctx.get_levelset_device(out[i].data_ptr(), 64 if dtype == torch.float64 else 32, self._stream())
+        return out
+
+    def images(self):
+        """The members' planes as they are now (after Perona-Malik: the smoothed image), (N, H, W) or (N, C, H, W) uint8."""
+        shape = (self.n, self.h, self.w) if self.channels == 1 else (self.n, self.channels, self.h, self.w)
+        out = torch.empty(shape, dtype=torch.uint8, device=torch.device("cuda", self.device))
+        for i, ctx in enumerate(self.contexts):
+            ctx.get_image_device(out[i].data_ptr(), capi.LAYOUT_PLANAR, self._stream())
+        return out

@@ -295,6 +295,55 @@ int cvh_ppf_apply(double *data, int w, long start, long end, int op, double eps,
 /* Same on a device pointer the caller owns (hip stream as void*, NULL = default). */
 int cvh_ppf_apply_device(double *d_data, long n, int op, double eps, void *stream);
 
+/* ---- Device-memory input and output -----------------------------------------------------------------------------------------
+ * The calls above move CALLER-OWNED HOST buffers over PCIe and synchronise the context's stream, one context per call.  The calls
+ * below take memory the caller owns ON THE DEVICE of the context(s) -- device, managed or mapped host memory, checked with
+ * hipPointerGetAttributes -- and are ordered against the caller's HIP stream `stream` (as void *, NULL = the default stream):
+ *   inputs   an event is recorded on `stream` when the call is made and the library's stream waits for it: whatever the caller
+ *            enqueued on `stream` before the call is read complete;
+ *   outputs  an event is recorded behind the library's last launch and `stream` waits for it: work the caller enqueues on `stream`
+ *            after the call sees the result.  The library never synchronises the caller's stream on the host, and an output call does
+ *            not wait for its own work.  It can still block the host in three cases: the context has iterations in flight (enqueued,
+ *            not yet cvh_sync'ed) or "state" = 32 needs its double mirror refreshed -- those are settled first, as the host-buffer
+ *            getters do --; and every call that launches a kernel writes its member table into one pinned block of the leading
+ *            context, so it first waits until the PREVIOUS such call led by that context has run.  That is long past in a frame loop
+ *            that consumes its masks, but a second output call issued while the first is still queued behind the caller's stream
+ *            waits for that stream's work.
+ * The *_batch forms serve n contexts of one device with ONE kernel launch on member 0's stream, joined with every member's stream
+ * before and after (as cvh_enqueue_steps_batch); the single-context forms are the same kernels with n = 1.
+ * Results are those of the host-buffer calls, bit for bit: cvh_set_image_device leaves the planes, the sums, the stop norm and the
+ * validity flags of cvh_set_image of the same bytes; cvh_set_levelset_device those of cvh_set_levelset (bits = 32 takes floats and is
+ * cvh_set_levelset of their exact double values); cvh_get_levelset_device with bits = 32 rounds to nearest even.
+ * Layouts: CVH_LAYOUT_PLANAR is C planes of h*w bytes one behind the other (what cvh_set_image takes), CVH_LAYOUT_INTERLEAVED is
+ * h*w*C bytes (the reference's CV_8UC3, what cv::split consumes at src/main.cpp:934-937).  uint8 pointers may have ANY byte
+ * alignment; level-set pointers are aligned to their element.
+ * Host waits: the ingest calls wait ONCE per call (the sums come back to host fields) where cvh_set_image waits once per context.
+ * One channel is summed entirely on the device (exact integers).  THREE channels: (sum_k I_k)/3 is rounded per pixel and the
+ * reference adds the squares serially, four per step, so the planes are fetched and summed on the host as cvh_set_image's route
+ * does -- for all members of a batch behind the one wait, the members' sums on up to 16 host threads.  Cost of that fetch: 3 bytes
+ * per pixel over PCIe plus the serial sum -- measured on an MI355X for 16 x 480 x 640 x 3: 0.93 ms of a 1.42 ms ingest (the same 48
+ * planes as one-channel members: 0.49 ms; tools/device_io_probe.py).  cvh_init_checkerboard_batch and cvh_set_levelset_device wait once per call as well
+ * ("state" = 64; with "state" = 32 every member's float pair then adopts the level set: one more launch and wait per member).
+ * Buffers of different members that overlap each other are the caller's business: nothing checks it.
+ * CVH_ERR_ARG: NULL pointers, n < 1, a NULL or duplicate member, members on different devices, an unknown layout, bits not 32 or
+ * 64, a pointer that is not device-accessible memory of the context's device; CVH_ERR_STATE: a getter before an image / a level
+ * set exists.  Checked for every member before anything is launched; a batch's message names the member index and is
+ * cvh_last_error(NULL)'s and member 0's; the members stay usable. */
+typedef enum cvh_layout { CVH_LAYOUT_PLANAR = 0, CVH_LAYOUT_INTERLEAVED = 1 } cvh_layout;
+
+int cvh_set_image_device(cvh_context *ctx, const uint8_t *d_img, int layout, void *stream);
+/* The planes as they are now (after cvh_perona_malik: the <stem>_pm image). */
+int cvh_get_image_device(cvh_context *ctx, uint8_t *d_img, int layout, void *stream);
+int cvh_set_levelset_device(cvh_context *ctx, const void *d_u, int bits, void *stream);
+int cvh_get_levelset_device(cvh_context *ctx, void *d_u, int bits, void *stream);
+/* mask = ((float)u > 0), optionally 1 - mask, h*w bytes. */
+int cvh_get_mask_device(cvh_context *ctx, uint8_t *d_mask, int invert, void *stream);
+
+int cvh_set_image_device_batch(cvh_context *const *ctxs, int n, const uint8_t *const *d_imgs, int layout, void *stream);
+/* cvh_init_checkerboard for n contexts: the sine factors of every distinct shape go up in one copy, one launch takes the signs. */
+int cvh_init_checkerboard_batch(cvh_context *const *ctxs, int n);
+int cvh_get_mask_device_batch(cvh_context *const *ctxs, int n, uint8_t *const *d_masks, int invert, void *stream);
+
 /* Library version string, e.g. "chanvese_hip 0.1 (gfx950)". */
 const char *cvh_version(void);
 
