@@ -1,5 +1,6 @@
 // api.hip — host side of the C ABI declared in include/chanvese_hip.h: context lifecycle, options, image and level-set I/O, getters.
-// The flows live in csv_run.hip (CSV steps of one context), csv_batch.hip (fused batch), pm_run.hip (Perona-Malik); never throws.
+// and the transitions of a context's run state.  The flows live in csv_run.hip (CSV steps of one context), csv_batch.hip (fused batch),
+// pm_run.hip (Perona-Malik), io_run.hip (device memory); never throws.
 #include "cvh_host.h"
 
 char g_create_err[512] = "no error";
@@ -198,7 +199,8 @@ static int create_impl(cvh_context *c)
   HIPCHK(c, hipHostMalloc((void **)&c->h_isums, 8 * sizeof(unsigned long long), hipHostMallocDefault));
   HIPCHK(c, hipEventCreate(&c->ev0));
   HIPCHK(c, hipEventCreate(&c->ev1));
-  for (int k = 0; k < 4; ++k) HIPCHK(c, hipEventCreateWithFlags(&c->evp[k], hipEventDisableTiming));
+  for (hipEvent_t *ev : {&c->evp[0], &c->evp[1], &c->evp[2], &c->evp[3], &c->ev_join, &c->ev_io_in, &c->ev_io_out})
+    HIPCHK(c, hipEventCreateWithFlags(ev, hipEventDisableTiming));
   snprintf(c->err, sizeof(c->err), "no error");
   return CVH_OK;
 }
@@ -250,7 +252,7 @@ extern "C" int cvh_set_option(cvh_context *c, const char *key, long value)
 {
   if (!c || !key) return CVH_ERR_ARG;
   HIPCHK(c, hipSetDevice(c->device));
-  if (c->timing_open || c->chain_pending) { const int rc = sync_impl(c); if (rc != CVH_OK) return rc; }  // options apply between runs
+  { const int rc = settle(c); if (rc != CVH_OK) return rc; }  // options apply between runs
   if (!strcmp(key, "math_mode")) {
     if (value < 0 || value > 2) return fail(c, CVH_ERR_ARG, "math_mode must be 0, 1 or 2");
     c->math_mode = (int)value;
@@ -336,7 +338,6 @@ extern "C" int cvh_set_option(cvh_context *c, const char *key, long value)
       if (value == 32) {
         if (c->w % 16 != 0 || c->w < 144 || c->n >= ((size_t)1 << 28))
           return fail(c, CVH_ERR_ARG, "state 32 needs a width that is a multiple of 16 and >= 144, and fewer than 2^28 pixels (the 2-pixel wave kernel)");
-        if (c->have_u) { const int rc = ensure_f64_mirror(c); if (rc != CVH_OK) return rc; }
         c->state_bits = 32;
         if (c->have_u) { const int rc = adopt_f32_state(c); if (rc != CVH_OK) return rc; }
       } else {
@@ -410,7 +411,7 @@ int image_stats(cvh_context *c, const uint8_t *const *host_planes)
   HIPCHK(c, hipMemsetAsync(c->d_isums, 0, 8 * sizeof(unsigned long long), c->stream));
   HIPCHK(c, cvh_launch_image_sums(c->d_img, c->C, c->n, c->d_isums, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->h_isums, c->d_isums, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-  const bool exact_on_device = c->C == 1 && c->n < ((size_t)1 << 36);   // 2^36 * 255^2 < 2^53
+  const bool exact_on_device = stop_norm_exact_on_device(c);
   std::vector<std::vector<uint8_t>> fetched;
   std::vector<const uint8_t *> pl;
   if (!exact_on_device) {
@@ -424,9 +425,8 @@ int image_stats(cvh_context *c, const uint8_t *const *host_planes)
     }
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  for (int k = 0; k < c->C; ++k) c->sum_img[k] = (double)c->h_isums[2 * k];   // exact: < 2^53
-  c->stop_norm = exact_on_device ? sqrt((double)c->h_isums[1]) : stop_norm_host(pl, c->n);
-  c->stop_valid = true;
+  const double host_norm = exact_on_device ? 0.0 : stop_norm_host(pl, c->n);
+  plane_sums_arrived(c, c->h_isums, exact_on_device ? nullptr : &host_norm);
   return CVH_OK;
 }
 
@@ -435,14 +435,10 @@ extern "C" int cvh_set_image(cvh_context *c, const uint8_t *const *planes)
   if (!c || !planes) return CVH_ERR_ARG;
   for (int k = 0; k < c->C; ++k) if (!planes[k]) return fail(c, CVH_ERR_ARG, "cvh_set_image: plane %d is NULL", k);
   HIPCHK(c, hipSetDevice(c->device));
-  if (c->timing_open || c->chain_pending) { const int rc = sync_impl(c); if (rc != CVH_OK) return rc; }
+  { const int rc = settle(c); if (rc != CVH_OK) return rc; }
   for (int k = 0; k < c->C; ++k)
     HIPCHK(c, hipMemcpyAsync(c->d_img[k], planes[k], c->n, hipMemcpyHostToDevice, c->stream));
-  const int rc = image_stats(c, planes);
-  if (rc != CVH_OK) return rc;
-  c->have_image = true;
-  c->sums_valid = false;
-  return CVH_OK;
+  return image_stats(c, planes);
 }
 
 extern "C" int cvh_get_image(cvh_context *c, uint8_t *const *planes)
@@ -456,6 +452,93 @@ extern "C" int cvh_get_image(cvh_context *c, uint8_t *const *planes)
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return CVH_OK;
+}
+
+// ---- The transitions of a context's run state (the group of that name in cvh_context, cvh_host.h): what the context has in flight and
+// which of its cached values are still true.  Every flow calls these instead of assigning the fields; each function states the invariant
+// it keeps.  sync_impl (csv_run.hip), which closes what these open, is the one other place that assigns them. ----
+// Work in flight is settled: iterations enqueued and never synchronised (chain_pending) or a timed interval that is still open are closed
+// before a caller replaces state they read -- options, planes, the level set, the shared CvhResident block.  No third term: a resident
+// launch (resident_used) is enqueued by cvh_enqueue_steps, which has opened the interval by then, or by cvh_run, which ends in sync_impl, and
+// sync_impl alone closes the interval -- together with resident_used.  So resident_used implies timing_open wherever every earlier call
+// succeeded (the Perona-Malik callers used to test it as well; it could add nothing there).
+int settle(cvh_context *c) { return c->timing_open || c->chain_pending ? sync_impl(c) : CVH_OK; }
+
+// A new run begins, host half: counter and stop flag cleared, the automatic choices of a run are taken again (live-context registry).  The
+// buffer holding u becomes the base, and so does the chain-mode sum set that belongs to it.
+static void begin_run_host(cvh_context *c)
+{
+  c->cur_base = current_buffer(c);
+  c->chain_pb = (c->chain_pb + c->steps_done) & 3;
+  c->steps_done = 0;
+  c->enqueued = 0;
+  c->run_pol = -1; c->run_alone = -1; c->run_chunk = -1;
+  c->h_status[0] = 0; c->h_status[1] = 0;
+}
+
+// A new run begins: whatever is in flight is settled, then the host half, then the device half -- the state block's counters and the sum
+// set after the run's own (it may hold the sums of an iteration computed past a stop) are cleared, and the host waits for that.
+int reset_run_impl(cvh_context *c)
+{
+  { const int rc = settle(c); if (rc != CVH_OK) return rc; }
+  begin_run_host(c);
+  static const int zeros[4] = {0, 0, 0, 0};   // steps_done, stopped, ticket, pending
+  HIPCHK(c, hipMemcpyAsync(&c->d_state->steps_done, zeros, sizeof(zeros), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemsetAsync(&c->d_chain->v[(c->chain_pb + 1) & 3][0], 0, sizeof(c->d_chain->v[0]), c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return CVH_OK;
+}
+
+// A level set has arrived in d_u[chain_pb & 1], and the copy or launch that brought it has completed: only now does the bookkeeping follow
+// the data.  The buffer is the one whose parity equals the chain-mode sum set's: the ping-pong parity and the sum-set phase of a launch
+// then stay locked together (cur_base == chain_pb mod 2), and a cached step graph of a phase is valid for every run.  FP32 state takes the
+// level set over; then the new run -- its host half alone where the launch that wrote the level set did the device half (device_cleared).
+int levelset_arrived(cvh_context *c, bool device_cleared)
+{
+  c->cur_base = c->chain_pb & 1; c->steps_done = 0; c->enqueued = 0;
+  c->have_u = true;
+  c->sums_valid = false;
+  c->mirror_valid = true;
+  if (c->state_bits == 32) { const int rc = adopt_f32_state(c); if (rc != CVH_OK) return rc; }
+  if (!device_cleared) return reset_run_impl(c);
+  begin_run_host(c);
+  return CVH_OK;
+}
+
+// n > 0 steps were really enqueued (never called while capturing) on a grid of nparts workgroups.  Chain mode: the last of them has no
+// successor to book it yet -- the next launch on the same grid does, or the flush kernel, which also writes c1 / c2 of the final level set
+// into the state block at the next sync; otherwise the means now live in the state block only.  pending_nparts is 0 for a resident launch,
+// which books its iterations itself and leaves its error word for sync_impl.  FP32 state: the double mirror is behind.
+void steps_enqueued(cvh_context *c, int n, int nparts, bool chain, bool resident)
+{
+  if (resident) { nparts = 0; c->resident_used = true; }
+  if (chain) { c->chain_pending = true; c->pending_nparts = nparts; }
+  else c->chain_acc_valid = false;
+  c->last_nparts = nparts;
+  if (c->state_bits == 32) c->mirror_valid = false;
+  c->enqueued += n;
+}
+
+// The initial sums of the current level set were taken: c1 / c2 are in the state block and, in chain mode, the fixed-point set is seeded.
+void sums_taken(cvh_context *c, bool chain) { c->sums_valid = true; c->chain_acc_valid = chain; }
+
+// One channel and fewer than 2^36 pixels: the stop norm is exact on the device (integers, 2^36 * 255^2 < 2^53).  Three channels round
+// (sum_k I_k)/3 per pixel, so their norm needs the reference's serial order on the host (stop_norm_host).
+bool stop_norm_exact_on_device(const cvh_context *c) { return c->C == 1 && c->n < ((size_t)1 << 36); }
+
+// The planes changed on the device (an upload or ingest replaced them, Perona-Malik smoothed them): the region means were taken against
+// the old planes, and the stop norm is theirs until plane sums come back.
+void planes_changed(cvh_context *c) { c->stop_valid = false; c->sums_valid = false; }
+
+// Plane sums have come back: isums holds {sum p, sum p^2} per plane (exact integers: < 2^53 as doubles), host_norm the norm the host took
+// where the device's is not exact (else nullptr).  The context holds an image whose stop norm is valid and whose means are not.
+void plane_sums_arrived(cvh_context *c, const unsigned long long *isums, const double *host_norm)
+{
+  planes_changed(c);
+  for (int k = 0; k < c->C; ++k) c->sum_img[k] = (double)isums[2 * k];
+  c->stop_norm = host_norm ? *host_norm : sqrt((double)isums[1]);
+  c->stop_valid = true;
+  c->have_image = true;
 }
 
 // FP32 state: the float buffers (lazily allocated) take over the level set that d_u[current] holds -- rounded to float, and d_u[current]
@@ -480,29 +563,11 @@ int adopt_f32_state(cvh_context *c)
 int ensure_f64_mirror(cvh_context *c)
 {
   if (c->state_bits != 32 || c->mirror_valid) return CVH_OK;
-  if (c->timing_open || c->chain_pending) { const int rc = sync_impl(c); if (rc != CVH_OK) return rc; }
+  { const int rc = settle(c); if (rc != CVH_OK) return rc; }
   const int cur = current_buffer(c);
   HIPCHK(c, cvh_launch_state_widen(c->d_uf[cur], c->d_u[cur], c->n, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->mirror_valid = true;
-  return CVH_OK;
-}
-
-int reset_run_impl(cvh_context *c)
-{
-  if (c->timing_open || c->chain_pending) { const int rc = sync_impl(c); if (rc != CVH_OK) return rc; }
-  // new run: counter and stop flag cleared; the buffer holding u becomes the base, and so does the chain-mode sum set
-  // that belongs to it (the set after it may hold the sums of an iteration computed past a stop: cleared)
-  c->cur_base = current_buffer(c);
-  c->chain_pb = (c->chain_pb + c->steps_done) & 3;
-  c->steps_done = 0;
-  c->enqueued = 0;
-  c->run_pol = -1; c->run_alone = -1; c->run_chunk = -1;   // the automatic choices of a run are taken again (live-context registry)
-  static const int zeros[4] = {0, 0, 0, 0};   // steps_done, stopped, ticket, pending
-  HIPCHK(c, hipMemcpyAsync(&c->d_state->steps_done, zeros, sizeof(zeros), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemsetAsync(&c->d_chain->v[(c->chain_pb + 1) & 3][0], 0, sizeof(c->d_chain->v[0]), c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->h_status[0] = 0; c->h_status[1] = 0;
   return CVH_OK;
 }
 
@@ -517,18 +582,11 @@ extern "C" int cvh_set_levelset(cvh_context *c, const double *u)
 {
   if (!c || !u) return CVH_ERR_ARG;
   HIPCHK(c, hipSetDevice(c->device));
-  if (c->timing_open || c->chain_pending) { const int rc = sync_impl(c); if (rc != CVH_OK) return rc; }
+  { const int rc = settle(c); if (rc != CVH_OK) return rc; }
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  // the new level set goes into the buffer whose parity equals the chain-mode sum set's (chain_pb & 1): the ping-pong parity
-  // and the sum-set phase of a launch then stay locked together, and a cached step graph of a phase is valid for every run
-  c->cur_base = c->chain_pb & 1; c->steps_done = 0; c->enqueued = 0;
-  HIPCHK(c, hipMemcpyAsync(c->d_u[c->cur_base], u, c->n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->d_u[c->chain_pb & 1], u, c->n * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->have_u = true;
-  c->sums_valid = false;
-  c->mirror_valid = true;
-  if (c->state_bits == 32) { const int rc = adopt_f32_state(c); if (rc != CVH_OK) return rc; }
-  return reset_run_impl(c);
+  return levelset_arrived(c);
 }
 
 extern "C" void cvh_levelset_checkerboard_host(int h, int w, double *u)
@@ -550,7 +608,7 @@ extern "C" int cvh_init_checkerboard(cvh_context *c)
 {
   if (!c) return CVH_ERR_ARG;
   HIPCHK(c, hipSetDevice(c->device));
-  if (c->timing_open || c->chain_pending) { const int rc = sync_impl(c); if (rc != CVH_OK) return rc; }
+  { const int rc = settle(c); if (rc != CVH_OK) return rc; }
   HIPCHK(c, hipStreamSynchronize(c->stream));
   // the h + w sine factors from the host's libm (as cvh_levelset_checkerboard_host), staged in the idle buffer of the
   // ping-pong pair (h + w <= h w + 1 doubles); the sign of their product is taken on the device
@@ -558,15 +616,11 @@ extern "C" int cvh_init_checkerboard(cvh_context *c)
   const double pi = 3.14159265358979323846;
   for (int i = 0; i < c->h; ++i) sv[i] = sin(pi * i / 5);
   for (int j = 0; j < c->w; ++j) sv[(size_t)c->h + j] = sin(pi * j / 5);
-  c->cur_base = c->chain_pb & 1; c->steps_done = 0; c->enqueued = 0;   // see cvh_set_levelset
-  HIPCHK(c, hipMemcpyAsync(c->d_u[c->cur_base ^ 1], sv.data(), sv.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, cvh_launch_checkerboard(c->d_u[c->cur_base ^ 1], c->d_u[c->cur_base], c->h, c->w, c->stream));
+  const int base = c->chain_pb & 1;   // see levelset_arrived
+  HIPCHK(c, hipMemcpyAsync(c->d_u[base ^ 1], sv.data(), sv.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, cvh_launch_checkerboard(c->d_u[base ^ 1], c->d_u[base], c->h, c->w, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->have_u = true;
-  c->sums_valid = false;
-  c->mirror_valid = true;
-  if (c->state_bits == 32) { const int rc = adopt_f32_state(c); if (rc != CVH_OK) return rc; }
-  return reset_run_impl(c);
+  return levelset_arrived(c);
 }
 
 extern "C" int cvh_get_levelset(cvh_context *c, double *u)

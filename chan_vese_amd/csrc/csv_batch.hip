@@ -58,19 +58,22 @@ int batch_fail(cvh_context *const *ctxs, int n, int code, const char *fmt, ...)
   return code;
 }
 
-// What can be refused before anything is enqueued (the members stay as they were).
-int batch_check(cvh_context *const *ctxs, int n, bool csv)
+// Who may be in a batch: what can be refused before anything is touched (the members stay as they were).  `what` opens the message
+// ("batch", or the entry point's name); `needs` says how much a member must hold -- the list alone (device-memory I/O), an image
+// (a Perona-Malik batch needs no level set and no CSV geometry), or all a fused CSV launch takes (the two batches': their texts say "batch").
+int members_check(cvh_context *const *ctxs, int n, const char *what, MemberNeeds needs)
 {
-  if (!ctxs || n < 1) return batch_fail(ctxs, 0, CVH_ERR_ARG, "batch: empty member list (ctxs = %p, n = %d)", (const void *)ctxs, n);
+  if (!ctxs || n < 1) return batch_fail(ctxs, 0, CVH_ERR_ARG, "%s: empty member list (ctxs = %p, n = %d)", what, (const void *)ctxs, n);
   for (int i = 0; i < n; ++i) {
     cvh_context *c = ctxs[i];
-    if (!c) return batch_fail(ctxs, i ? n : 0, CVH_ERR_ARG, "batch: member %d is NULL", i);
+    if (!c) return batch_fail(ctxs, i ? n : 0, CVH_ERR_ARG, "%s: member %d is NULL", what, i);
     for (int j = 0; j < i; ++j)
-      if (ctxs[j] == c) return batch_fail(ctxs, n, CVH_ERR_ARG, "batch: member %d duplicates member %d", i, j);
+      if (ctxs[j] == c) return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: member %d duplicates member %d", what, i, j);
     if (c->device != ctxs[0]->device)
-      return batch_fail(ctxs, n, CVH_ERR_ARG, "batch: member %d is on device %d, member 0 on device %d", i, c->device, ctxs[0]->device);
+      return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: member %d is on device %d, member 0 on device %d", what, i, c->device, ctxs[0]->device);
+    if (needs == kMembersListed) continue;
     if (!c->have_image) return batch_fail(ctxs, n, CVH_ERR_STATE, "batch: member %d has no image (call cvh_set_image first)", i);
-    if (!csv) continue;   // (a Perona-Malik batch needs no level set and no CSV geometry)
+    if (needs == kMembersWithImage) continue;
     if (!c->have_u) return batch_fail(ctxs, n, CVH_ERR_STATE, "batch: member %d has no level set (call cvh_set_levelset or cvh_init_checkerboard first)", i);
     if (c->finalize_mode != 0) return batch_fail(ctxs, n, CVH_ERR_ARG, "batch: member %d has finalize = 1 (a separate finalise kernel per launch): no fused batch", i);
     const Geometry g = resolve_geometry(c);
@@ -113,7 +116,6 @@ static int batch_prepare(cvh_context *const *ctxs, int n)
     if (rc == CVH_OK) rc = flush_for_grid(c, g.nblocks);
     if (rc == CVH_OK) rc = prepare(c);
     if (rc != CVH_OK) return batch_fail(ctxs, n, rc, "batch: member %d: %s", i, c->err);
-    if (!c->ev_join) HIPCHK(c, hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
   }
   cvh_context *lead = ctxs[0];
   // group the members by CSV-step instantiation (the name cvh_launch_info reports) and dynamic LDS
@@ -242,19 +244,15 @@ static int batch_launch(cvh_context *const *ctxs, int n, int nsteps)
     if (i) HIPCHK(c, hipStreamWaitEvent(c->stream, lead->ev_join, 0));
     if (nsteps > 0) {
       const Geometry g = resolve_geometry(c);
-      if (use_chain(c, g)) { c->chain_pending = true; c->pending_nparts = g.nblocks; }
-      else c->chain_acc_valid = false;   // the means now live in the state block only
-      c->last_nparts = g.nblocks;
-      if (c->state_bits == 32) c->mirror_valid = false;
+      steps_enqueued(c, nsteps, g.nblocks, use_chain(c, g), false);
     }
-    c->enqueued += nsteps;
   }
   return CVH_OK;
 }
 
 extern "C" int cvh_enqueue_steps_batch(cvh_context *const *ctxs, int n, int nsteps)
 {
-  int rc = batch_check(ctxs, n);
+  int rc = members_check(ctxs, n, "batch", kMembersForCsv);
   if (rc != CVH_OK) return rc;
   if (nsteps < 0) return batch_fail(ctxs, n, CVH_ERR_ARG, "batch: nsteps = %d", nsteps);
   HIPCHK(ctxs[0], hipSetDevice(ctxs[0]->device));
@@ -268,7 +266,7 @@ extern "C" int cvh_enqueue_steps_batch(cvh_context *const *ctxs, int n, int nste
 
 extern "C" int cvh_run_batch(cvh_context *const *ctxs, int n, int max_steps, int *steps_done, double *last_norm)
 {
-  int rc = batch_check(ctxs, n);
+  int rc = members_check(ctxs, n, "batch", kMembersForCsv);
   if (rc != CVH_OK) return rc;
   cvh_context *lead = ctxs[0];
   HIPCHK(lead, hipSetDevice(lead->device));
@@ -315,7 +313,6 @@ extern "C" int cvh_run_batch(cvh_context *const *ctxs, int n, int max_steps, int
     c->timing_open = true;   // sync_impl closes the interval opened on the leader's stream before the first fused launch
     rc = sync_impl(c);
     if (rc != CVH_OK) return batch_fail(ctxs, n, rc, "batch: member %d: %s", i, c->err);
-    c->enqueued = c->steps_done;
     if (steps_done) steps_done[i] = c->h_state[0].steps_done;
     if (last_norm) last_norm[i] = c->h_state[0].norm;
   }

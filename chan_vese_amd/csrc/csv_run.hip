@@ -104,6 +104,16 @@ bool resident_tile_grid(int h, int w, int channels, int num_cus, int cap_blocks,
   return true;
 }
 
+// Does the device launch cooperatively?  Asked once per context; both resident geometries (here, pm_run.hip) size their own kernel by it.
+bool launches_cooperatively(cvh_context *c)
+{
+  if (c->coop_launch < 0) {
+    int coop = 0;
+    c->coop_launch = hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, c->device) == hipSuccess && coop ? 1 : 0;
+  }
+  return c->coop_launch != 0;
+}
+
 bool resident_geometry(cvh_context *c, ResidentGeom *rg)
 {
   // three channels (csv_resident_kernel<3, .>): on request only ("resident" = 1); the automatic choice keeps the per-launch flow
@@ -132,14 +142,15 @@ bool resident_geometry(cvh_context *c, ResidentGeom *rg)
     const int need = px >= 3.6e6 ? 48 : px >= 2.9e6 ? 72 : px >= 2.2e6 ? 100 : INT_MAX;
     if (c->run_chunk < need) return false;
   }
-  if (c->resident_cap < 0) {
-    int coop = 0;
-    c->resident_cap = 0;
-    if (hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, c->device) == hipSuccess && coop)
-      c->resident_cap = cvh_resident_blocks_per_cu(c->C) * c->num_cus;
-  }
+  if (c->resident_cap < 0) c->resident_cap = launches_cooperatively(c) ? cvh_resident_blocks_per_cu(c->C) * c->num_cus : 0;
   if (c->resident_cap <= 0) return false;
   return resident_tile_grid(c->h, c->w, c->C, c->num_cus, c->resident_cap, rg);
+}
+
+// Class-major workgroup numbering of the wave kernels: workgroups per XCD per dispatch round (0: off), see compute_strip_bounds.
+static int class_major_cls(const cvh_context *c, const Geometry &g)
+{
+  return (((g.strip == 3 && c->wave_cls) || (g.strip == 2 && c->wave_cls == 2)) && c->wave_xcd) ? (c->num_cus >= 8 ? c->num_cus / 8 : 1) : 0;
 }
 
 // `step` = index of the launch inside the run (c->enqueued when it is enqueued): selects the chain-mode sum set
@@ -214,7 +225,7 @@ void fill_args(const cvh_context *c, CvhStepArgs *a, int in_buf, int step)
     if (c->run_pol < 0 || c->enqueued == 0) c->run_pol = live_footprint(c) <= 300e6 ? 1 : 0;
     a->wave_pol = c->run_pol;
   }
-  a->wave_cls = (((g.strip == 3 && c->wave_cls) || (g.strip == 2 && c->wave_cls == 2)) && c->wave_xcd) ? (c->num_cus >= 8 ? c->num_cus / 8 : 1) : 0;
+  a->wave_cls = class_major_cls(c, g);
   a->host_status = c->h_status;
   a->dbg_times = c->d_dbg;
   a->inv_eps = 1.0 / c->p.eps;
@@ -265,8 +276,7 @@ int prepare(cvh_context *c)
   if (rc0 != CVH_OK) return rc0;
   // (the stop condition travels as a launch argument, CvhStepArgs::stop_cond: no per-enqueue upload inside the timed interval)
   const bool chain = use_chain(c, resolve_geometry(c));
-  if (chain && !c->chain_acc_valid) c->sums_valid = false;   // the means exist only as doubles (another kernel ran): recompute
-  if (!c->sums_valid) {
+  if (!c->sums_valid || (chain && !c->chain_acc_valid)) {   // (chain mode: the means exist only as doubles -- another kernel ran --: recompute)
     CvhStepArgs a;
     fill_args(c, &a, current_buffer(c), c->enqueued);
     if (c->state_bits == 32) {   // the sums of the level set the run starts from are taken of its double mirror (the rounded values)
@@ -278,8 +288,7 @@ int prepare(cvh_context *c)
     HIPCHK(c, cvh_launch_init_sums(a, c->C, use_fast(c), &nparts, c->stream));
     a.nparts = nparts;
     HIPCHK(c, cvh_launch_finalize(a, c->C, 1, c->stream));   // chain mode: also seeds the fixed-point set of this step
-    c->sums_valid = true;
-    c->chain_acc_valid = chain;
+    sums_taken(c, chain);
   }
   return CVH_OK;
 }
@@ -342,7 +351,7 @@ void compute_strip_bounds(int kind, int h, int tiles_x, int S, int strip_rows, i
 
 int upload_strip_bounds(cvh_context *c, const Geometry &g)
 {
-  const int cls = (((g.strip == 3 && c->wave_cls) || (g.strip == 2 && c->wave_cls == 2)) && c->wave_xcd) ? (c->num_cus >= 8 ? c->num_cus / 8 : 1) : 0;
+  const int cls = class_major_cls(c, g);
   const bool alone = run_is_alone(c);
   const int key[4] = {g.tiles_y, g.strip_rows, c->wave_skew + 1000 * (cls ? c->wave_cskew + 1 : 0) + 10000000 * g.strip + (c->state_bits == 32 ? 500000000 : 0) + (alone ? 0 : 250000000), c->h};
   if (!memcmp(key, c->bounds_key, sizeof(key))) return CVH_OK;
@@ -368,7 +377,7 @@ int upload_strip_bounds(cvh_context *c, const Geometry &g)
 }
 
 // `capturing`: the launch is recorded into a stream capture, nothing reaches the GPU -- the context's bookkeeping of what is
-// in flight (chain_pending, chain_acc_valid) is updated by the caller when the graph is really launched
+// in flight (steps_enqueued) is updated by the caller when the graph is really launched
 int launch_one_step(cvh_context *c, int in_buf, int step, bool capturing, CvhLaunchNote *note)
 {
   CvhStepArgs a;
@@ -380,11 +389,7 @@ int launch_one_step(cvh_context *c, int in_buf, int step, bool capturing, CvhLau
   else HIPCHK(c, cvh_launch_step(a, c->C, use_fast(c), c->stream));
   if (note) return CVH_OK;
   if (c->finalize_mode == 1) HIPCHK(c, cvh_launch_finalize(a, c->C, 0, c->stream));
-  if (!capturing) {
-    if (a.chain) { c->chain_pending = true; c->pending_nparts = a.nparts; }
-    else c->chain_acc_valid = false;   // the means now live in the state block only
-    c->last_nparts = a.nparts;
-  }
+  if (!capturing) steps_enqueued(c, 1, a.nparts, a.chain != nullptr, false);
   return CVH_OK;
 }
 
@@ -504,11 +509,7 @@ int launch_resident(cvh_context *c, const ResidentGeom &rg, int nsteps, CvhLaunc
     if (note) { HIPCHK(c, cvh_launch_resident(a, c->C, c->stream)); return CVH_OK; }
     HIPCHK(c, hipMemsetAsync(c->d_resident, 0, c->C == 1 ? CVH_RESIDENT_C1_BYTES : sizeof(CvhResident), c->stream));
     HIPCHK(c, cvh_launch_resident(a, c->C, c->stream));
-    c->chain_pending = true;       // the flush kernel writes c1 / c2 of the final level set into the state block at the next sync
-    c->pending_nparts = 0;
-    c->last_nparts = 0;
-    c->resident_used = true;
-    c->enqueued += n;
+    steps_enqueued(c, n, ntiles, true, true);
     s += n;
   }
   return CVH_OK;
@@ -516,7 +517,6 @@ int launch_resident(cvh_context *c, const ResidentGeom &rg, int nsteps, CvhLaunc
 
 static int enqueue_impl(cvh_context *c, int nsteps)
 {
-  if (c->state_bits == 32 && nsteps > 0) c->mirror_valid = false;
   if (nsteps > 0) c->run_chunk = nsteps;        // (resident_geometry's rule for a batch looks at the length of THIS enqueue)
   {
     ResidentGeom rg;
@@ -533,7 +533,6 @@ static int enqueue_impl(cvh_context *c, int nsteps)
   for (; s < plain; ++s) {
     const int rc = launch_one_step(c, (c->cur_base + c->enqueued) & 1, c->enqueued);
     if (rc != CVH_OK) return rc;
-    c->enqueued++;
   }
   while (nsteps - s >= kGraphSteps) {
     const int parity = (c->cur_base + c->enqueued) & 1;
@@ -541,9 +540,7 @@ static int enqueue_impl(cvh_context *c, int nsteps)
     if (rc != CVH_OK) return rc;
     const StepGraph &sg = c->graphs[(c->chain_pb + c->enqueued) & 3];
     HIPCHK(c, hipGraphLaunch(sg.exec, c->stream));
-    if (sg.key[0].chain) { c->chain_pending = true; c->pending_nparts = sg.key[0].nparts; } else c->chain_acc_valid = false;
-    c->last_nparts = sg.key[0].nparts;
-    c->enqueued += kGraphSteps;
+    steps_enqueued(c, kGraphSteps, sg.key[0].nparts, sg.key[0].chain != nullptr, false);
     s += kGraphSteps;
   }
   return CVH_OK;
@@ -575,13 +572,6 @@ extern "C" int cvh_warm(cvh_context *c, int nsteps)
   return warm_impl(c, nsteps);
 }
 
-static int absorb_state(cvh_context *c, const CvhState *hs)
-{
-  c->steps_done = hs->steps_done;
-  if (hs->stopped) c->enqueued = hs->steps_done;  // launches past the stop were no-ops
-  return CVH_OK;
-}
-
 int sync_impl(cvh_context *c)
 {
   const bool via_flush = c->chain_pending;   // the flush kernel writes {steps_done, stopped, norm} into the pinned host block itself
@@ -607,8 +597,8 @@ int sync_impl(cvh_context *c)
     HIPCHK(c, hipEventElapsedTime(&c->last_run_ms, c->ev0, c->ev1));
     c->timing_open = false;
   }
-  absorb_state(c, &c->h_state[0]);
-  if (!c->h_state[0].stopped) c->enqueued = c->steps_done;
+  c->steps_done = c->h_state[0].steps_done;
+  c->enqueued = c->steps_done;   // everything enqueued has run, and launches past a stop were no-ops
   return CVH_OK;
 }
 
@@ -667,7 +657,6 @@ extern "C" int cvh_run(cvh_context *c, int max_steps, int *steps_done, double *l
   c->timing_open = true;   // sync_impl closes the interval opened at ev0 (after the chain-mode flush)
   rc = sync_impl(c);
   if (rc != CVH_OK) return rc;
-  c->enqueued = c->steps_done;
   if (steps_done) *steps_done = c->h_state[0].steps_done;
   if (last_norm) *last_norm = c->h_state[0].norm;
   return CVH_OK;

@@ -1,5 +1,7 @@
-// cvh_host.h -- private header of the library's host units (api.hip, csv_run.hip, csv_batch.hip, pm_run.hip, debug_exports.hip): the
-// context, the launch geometries and the helpers more than one unit calls.  Kernel sources do not include it.
+// cvh_host.h -- private header of the library's host units: the context, the launch geometries and the helpers more than one unit calls.
+// api.hip (lifecycle, options, host-buffer I/O, getters, the transitions of a context's run state), csv_run.hip (CSV steps of one
+// context), csv_batch.hip (fused batch, and what every batch shares), pm_run.hip (Perona-Malik), io_run.hip (device-memory I/O),
+// debug_exports.hip (diagnostics).  Kernel sources do not include it.
 #pragma once
 #include <limits.h>
 #include <math.h>
@@ -22,39 +24,74 @@ constexpr int kGraphSteps = 16;   // steps per captured graph (even: the ping-po
 struct StepGraph { hipGraphExec_t exec = nullptr; CvhStepArgs key[4]; int kind = -1, flavour = -1; };
 struct BatchCache;   // the device tables of a fused batch whose first member this context is (cvh_enqueue_steps_batch)
 
-struct cvh_context {
+struct cvh_context {   // opaque to callers; four groups
+  // ---- identity and buffers: fixed by cvh_create, or allocated once on first use ----
   int h = 0, w = 0, C = 0, device = 0;
   size_t n = 0;
-  cvh_params p{};
+  int num_cus = 256;
   hipStream_t stream = nullptr;
   uint8_t *d_img[CVH_MAX_CHANNELS] = {nullptr, nullptr, nullptr};   // planes inside d_img_slab, img_stride bytes apart
   uint8_t *d_img_slab = nullptr;
   size_t img_stride = 0;
   double *d_u[2] = {nullptr, nullptr};
   void *d_u_slab = nullptr;
-  // option "state" = 32 (declared FP32-state mode): the iteration kernels read and write d_uf[]; d_u[] stays the exchange format of
-  // set / get / mask / contour / selection and of the initial sums -- a mirror, refreshed lazily (ensure_f64_mirror)
-  int state_bits = 64;
-  float *d_uf[2] = {nullptr, nullptr};
+  float *d_uf[2] = {nullptr, nullptr};   // FP32 state (option "state"): what the iteration kernels read and write
   void *d_uf_slab = nullptr;
-  bool mirror_valid = true;     // d_u[current] holds the level set (always true with 64-bit state)
-  // automatic cache policy of a run ("wave_pol" = -1): decided when the run's first iteration is enqueued, from the footprint of EVERY
-  // context on this device that holds an image and a level set (live_footprint), and kept until the run counter is reset
-  int co_resident = 1;          // option "co_resident": 0 = a scratch / warm-up context that does not stream beside the others
-  mutable int run_pol = -1;     // the decision of the current run (-1: not taken yet)
-  mutable int run_alone = -1;   // 1: no other co-resident context on the device when the run started (automatic resident flow allowed)
-  int run_chunk = -1;           // iterations of the enqueue at hand (cvh_enqueue_steps / cvh_warm: their argument; cvh_run: its chunk) -- how long a cooperative launch would be (-1: nothing announced yet)
   CvhState *d_state = nullptr;
   CvhState *h_state = nullptr;  // pinned, four slots for pipelined polling
+  int *h_status = nullptr;  // pinned + mapped: {steps_done, stopped} written by the device
   double *d_partials = nullptr;
   int partial_rows = 0;
   double *d_trace = nullptr;
   int trace_cap = 0;
   double *d_pm[2] = {nullptr, nullptr};
   uint8_t *d_mask = nullptr;
-  bool have_image = false, have_u = false, sums_valid = false, stop_valid = false;
+  double *d_dummy = nullptr;
+  double *d_atan = nullptr;
+  CvhChainAcc *d_chain = nullptr;   // chain mode of the 2-pixel wave kernel (cvh_internal.h, CvhChainAcc)
+  int *d_bounds = nullptr;      // wave kernel: first row of every strip, [tiles_y + 1]
+  unsigned long long *d_isums = nullptr, *h_isums = nullptr;   // image_sums_kernel: {sum p, sum p^2} per plane (device / pinned)
+  unsigned long long *d_dbg = nullptr;  // diagnostic stamps (option "debug_times")
+  size_t dbg_words = 0;
+  // resident kernel (csv_resident_kernel.hip): cache-resident planes iterate in LDS, one cooperative launch per chunk
+  CvhResident *d_resident = nullptr;
+  double *d_res_halo = nullptr;
+  double *d_pm_halo = nullptr;   // pm_resident_kernel's border entries {value, tag}: its own buffer (tags must never meet foreign data)
+  int *h_resident = nullptr;     // pinned: {arrive, error} of the last launch
+  unsigned pm_res_serial = 0;    // launches of pm_resident_kernel so far (tag of the border entries; 0 = the cleared buffer)
+  char err[512] = {0};
+  // ---- run state: what the context has in flight and which of its cached values are still true.  Assigned by the transitions in
+  // api.hip and by sync_impl, nowhere else -- but for the exceptions named at their field ----
+  bool have_image = false, have_u = false, stop_valid = false;
+  bool sums_valid = false;      // the state block holds c1 / c2 of the current level set (also cleared where eps or "state" change: api.hip)
+  double sum_img[CVH_MAX_CHANNELS] = {0, 0, 0};
   double stop_norm = 0.0;  // || (sum_k I_k)/C ||_2
-  double stop_cond_h = 0.0; // tol * stop_norm of the current run (a launch argument)
+  // option "state" = 32 (declared FP32-state mode): the iteration kernels read and write d_uf[]; d_u[] stays the exchange format of
+  // set / get / mask / contour / selection and of the initial sums -- a mirror, refreshed lazily (ensure_f64_mirror)
+  bool mirror_valid = true;     // d_u[current] holds the level set (always true with 64-bit state)
+  int cur_base = 0;   // buffer that held u when the run counter was last reset
+  int enqueued = 0;   // steps enqueued since then
+  int steps_done = 0; // as of the last sync
+  int chain_pb = 0;             // sum set that belongs to the level set at run-counter 0
+  bool chain_pending = false;   // chain launches enqueued since the last flush
+  bool chain_acc_valid = false; // the fixed-point sets hold the sums of the current level set
+  int pending_nparts = 0;       // workgroup rows of sum u_diff^2 the pending iteration left (> 0: a per-launch wave kernel's, which the
+                                // next launch on the same grid or the flush kernel books; 0: a resident launch's, booked inside it)
+  int last_nparts = 0;          // workgroups (without the bookkeeper) of the last per-launch wave launch, own or fused (cvh_debug_read)
+  bool resident_used = false;    // a resident launch since the last sync: its error word is checked there
+  bool timing_open = false;     // ev0 is recorded and ev1 is not yet (the enqueue entry points open the interval, sync_impl closes it)
+  // automatic cache policy of a run ("wave_pol" = -1): decided when the run's first iteration is enqueued, from the footprint of EVERY
+  // context on this device that holds an image and a level set (live_footprint), and kept until the run counter is reset
+  mutable int run_pol = -1;     // the decision of the current run (-1: not taken yet; taken in fill_args)
+  mutable int run_alone = -1;   // 1: no other co-resident context on the device when the run started (automatic resident flow allowed; taken in run_is_alone)
+  int run_chunk = -1;           // iterations of the enqueue at hand (cvh_enqueue_steps / cvh_warm: their argument; cvh_run: its chunk) -- how long a cooperative launch would be (-1: nothing announced yet; the enqueue entry points announce it)
+  int geom_cus = 0;             // > 0: the CUs the automatic strip count is sized for (a fused batch: this context's share of the chip; batch_share)
+  double stop_cond_h = 0.0; // tol * stop_norm of the current run (a launch argument; prepare_host)
+  float last_run_ms = 0.f, last_pm_ms = 0.f;
+  // ---- options: cvh_set_params, cvh_set_option ----
+  cvh_params p{};
+  int state_bits = 64;          // option "state"
+  int co_resident = 1;          // option "co_resident": 0 = a scratch / warm-up context that does not stream beside the others
   int math_mode = CVH_MATH_DEFAULT, finalize_mode = 0, sync_every = 32;
   int tile_rows = 0 /* auto */, use_lut = 1, use_dma = 0;
   int kernel = -1;      // -1 auto, 0 tile kernel, 2 wave kernel, 3 wave kernel with 2 pixels per lane
@@ -64,70 +101,42 @@ struct cvh_context {
   int res_prio = 1;     // option "res_prio": resident kernels, priority by quarters of a wave's band (csv_resident_kernel.hip)
   int res_go_share = 5;  // option "res_go_share": log2 of the tiles of an XCD that share one release line of the resident kernel (0: a line per tile, 5: a line per XCD, 6: one line)
   int near_switch = 1;  // option "near_switch": per-wave, per-group choice of the form of H_eps (csv_wave2_kernel.hip); 0 = far form + correction always
-  double *d_dummy = nullptr;
   int wave_rev = 0, wave_xcd = 1;
   int use_graph = 1;
+  int wave_skew = 0;            // per-mille: older workgroups get longer strips (see upload_strip_bounds)
+  int chain_opt = 1;            // option "chain"
+  int res_straight = 1;          // diagnostic option "res_straight": 0 = the generic march of csv_resident_kernel whatever the tile height
+  int resident_opt = -1;         // option "resident": -1 auto (on where it applies, unless a per-launch knob was set), 0 off, 1 on where it applies
+  int far_terms = 5;            // terms of the far-field series of H_eps (5: valid from 32 eps, 4: from 64 eps)
+  int wave_pol = -1;            // option "wave_pol": cache policy of the 2-pixel kernel's rows (-1 auto by footprint, 0 plain, 1 write-through)
+  int wave_cls = 1;             // 2-pixel wave kernel: class-major workgroup numbering (dispatch rounds)
+  int wave_cskew = 500;         // per-mille strip-length skew between dispatch rounds (see upload_strip_bounds); measured
+                                // in one process at 4096^2: 0 -> 61.1, 300 -> 59.3, 500 -> 58.7, 750 -> 58.5, 900 -> 59.2 us
+  int strip_rows = 0;   // 0 auto
+  int strips = 0;       // 2-pixel kernel: exact number of strips (0 auto); rows are dealt by cumulative weight, so any count works
+  // ---- caches: graphs, tables, events and what was asked of the device once ----
   StepGraph graphs[4];          // by the chain-mode sum set of the first step, (chain_pb + enqueued) & 3; the ping-pong parity
-                                // follows it (cur_base == chain_pb mod 2: set_levelset / init_checkerboard keep that invariant)
+                                // follows it (cur_base == chain_pb mod 2: levelset_arrived keeps that invariant)
   char pm_desc[256] = {0};      // what the last cvh_perona_malik launched (cvh_launch_info)
   hipGraphExec_t pm_graph = nullptr;   // 16 Perona-Malik steps starting from d_pm[0]
   CvhPmArgs pm_graph_key{};
   int pm_graph_kind = -1;
-  int wave_skew = 0;            // per-mille: older workgroups get longer strips (see upload_strip_bounds)
-  // chain mode of the 2-pixel wave kernel (cvh_internal.h, CvhChainAcc)
-  CvhChainAcc *d_chain = nullptr;
-  int chain_opt = 1;            // option "chain"
-  int chain_pb = 0;             // sum set that belongs to the level set at run-counter 0
-  bool chain_pending = false;   // chain launches enqueued since the last flush
-  bool chain_acc_valid = false; // the fixed-point sets hold the sums of the current level set
-  int pending_nparts = 0;       // workgroup rows of sum u_diff^2 the pending iteration left (> 0: a per-launch wave kernel's, which the
-                                // next launch on the same grid or the flush kernel books; 0: a resident launch's, booked inside it)
-  int last_nparts = 0;          // workgroups (without the bookkeeper) of the last per-launch wave launch, own or fused (cvh_debug_read)
-  int geom_cus = 0;             // > 0: the CUs the automatic strip count is sized for (a fused batch: this context's share of the chip)
+  int bounds_key[4] = {-1, -1, -1, -1};   // what d_bounds was computed for
+  int tiles_x = 0, tiles_y = 0;
   BatchCache *batch = nullptr;  // fused batches led by this context: per-member launch arguments of the four phases, workgroup map
-  hipEvent_t ev_join = nullptr; // fused batch: joins this context's stream with the leader's
-  // resident kernel (csv_resident_kernel.hip): cache-resident planes iterate in LDS, one cooperative launch per chunk
-  CvhResident *d_resident = nullptr;
-  double *d_res_halo = nullptr;
-  double *d_pm_halo = nullptr;   // pm_resident_kernel's border entries {value, tag}: its own buffer (tags must never meet foreign data)
-  int *h_resident = nullptr;     // pinned: {arrive, error} of the last launch
-  int res_straight = 1;          // diagnostic option "res_straight": 0 = the generic march of csv_resident_kernel whatever the tile height
-  int pm_resident_cap = -1;      // workgroups of pm_resident_kernel the device holds at once (-1: not asked yet)
-  unsigned pm_res_serial = 0;    // launches of pm_resident_kernel so far (tag of the border entries; 0 = the cleared buffer)
+  DeviceTable pm_batch;          // Perona-Malik batches led by this context (cvh_perona_malik_batch): plane tables, workgroup maps
   // device-memory I/O led by this context (io_run.hip): the member table, sums and sine factors of a call on the device, their pinned
   // host image (also the landing place of sums and fetched planes), and the events that order a call against the caller's stream
   DeviceTable io_table;
   void *h_io = nullptr;
   size_t h_io_cap = 0;
   hipEvent_t ev_io_in = nullptr, ev_io_out = nullptr;   // ev_io_out also marks the last read of h_io by a copy still in flight
-  DeviceTable pm_batch;          // Perona-Malik batches led by this context (cvh_perona_malik_batch): plane tables, workgroup maps
-  int resident_opt = -1;         // option "resident": -1 auto (on where it applies, unless a per-launch knob was set), 0 off, 1 on where it applies
-  int resident_cap = -1;         // workgroups the device holds at once (-1: not asked yet, 0: unavailable)
-  bool resident_used = false;    // a resident launch since the last sync: its error word is checked there
-  int far_terms = 5;            // terms of the far-field series of H_eps (5: valid from 32 eps, 4: from 64 eps)
-  int wave_pol = -1;            // option "wave_pol": cache policy of the 2-pixel kernel's rows (-1 auto by footprint, 0 plain, 1 write-through)
-  int wave_cls = 1;             // 2-pixel wave kernel: class-major workgroup numbering (dispatch rounds)
-  int wave_cskew = 500;         // per-mille strip-length skew between dispatch rounds (see upload_strip_bounds); measured
-                                // in one process at 4096^2: 0 -> 61.1, 300 -> 59.3, 500 -> 58.7, 750 -> 58.5, 900 -> 59.2 us
-  int *d_bounds = nullptr;      // wave kernel: first row of every strip, [tiles_y + 1]
-  int bounds_key[4] = {-1, -1, -1, -1};
-  int *h_status = nullptr;  // pinned + mapped: {steps_done, stopped} written by the device
-  unsigned long long *d_isums = nullptr, *h_isums = nullptr;   // image_sums_kernel: {sum p, sum p^2} per plane (device / pinned)
-  int strip_rows = 0;   // 0 auto
-  int strips = 0;       // 2-pixel kernel: exact number of strips (0 auto); rows are dealt by cumulative weight, so any count works
-  int num_cus = 256;
-  double *d_atan = nullptr;
-  unsigned long long *d_dbg = nullptr;  // diagnostic stamps (option "debug_times")
-  size_t dbg_words = 0;
-  double sum_img[CVH_MAX_CHANNELS] = {0, 0, 0};
-  int tiles_x = 0, tiles_y = 0;
-  int cur_base = 0;   // buffer that held u when the run counter was last reset
-  int enqueued = 0;   // steps enqueued since then
-  int steps_done = 0; // as of the last sync
+  int coop_launch = -1;          // does the device launch cooperatively (-1: not asked yet; launches_cooperatively)
+  int resident_cap = -1;         // workgroups of csv_resident_kernel the device holds at once (-1: not asked yet, 0: unavailable)
+  int pm_resident_cap = -1;      // workgroups of pm_resident_kernel the device holds at once (-1: not asked yet)
+  // events, all created by cvh_create
   hipEvent_t ev0 = nullptr, ev1 = nullptr, evp[4] = {nullptr, nullptr, nullptr, nullptr};
-  bool timing_open = false;
-  float last_run_ms = 0.f, last_pm_ms = 0.f;
-  char err[512] = {0};
+  hipEvent_t ev_join = nullptr; // fused batch: joins this context's stream with the leader's
 };
 
 struct Geometry { int strip; int rows; int tiles_x, tiles_y, strip_rows, nblocks; };
@@ -161,19 +170,29 @@ inline int current_buffer(const cvh_context *c) { return (c->cur_base + c->steps
 extern char g_create_err[512];   // cvh_last_error(NULL): what failed outside a context
 int fail(cvh_context *ctx, int code, const char *fmt, ...);
 
-// api.hip: live-context registry, image statistics, level-set buffers
+// api.hip: live-context registry, image statistics
 bool run_is_alone(const cvh_context *c);
 double live_footprint(const cvh_context *c);
 int image_stats(cvh_context *c, const uint8_t *const *host_planes);
 double stop_norm_host(const std::vector<const uint8_t *> &planes, size_t n);
+void fill_atan_tables(double *tab);
+
+// api.hip: one function per event that moves a context's run state (the group of that name in cvh_context)
+int settle(cvh_context *c);
+int reset_run_impl(cvh_context *c);
+int levelset_arrived(cvh_context *c, bool device_cleared = false);
+void steps_enqueued(cvh_context *c, int n, int nparts, bool chain, bool resident);
+void sums_taken(cvh_context *c, bool chain);
+bool stop_norm_exact_on_device(const cvh_context *c);
+void planes_changed(cvh_context *c);
+void plane_sums_arrived(cvh_context *c, const unsigned long long *isums, const double *host_norm);
 int adopt_f32_state(cvh_context *c);
 int ensure_f64_mirror(cvh_context *c);
-int reset_run_impl(cvh_context *c);
-void fill_atan_tables(double *tab);
 
 // csv_run.hip: geometry, launch arguments and the per-launch / graph / resident flows of one context
 Geometry resolve_geometry(const cvh_context *c);
 bool use_chain(const cvh_context *c, const Geometry &g);
+bool launches_cooperatively(cvh_context *c);
 bool resident_geometry(cvh_context *c, ResidentGeom *rg);
 bool resident_tile_grid(int h, int w, int channels, int num_cus, int cap_blocks, ResidentGeom *rg);
 void fill_args(const cvh_context *c, CvhStepArgs *a, int in_buf, int step);
@@ -191,7 +210,8 @@ int sync_impl(cvh_context *c);
 // csv_batch.hip: what every batch of contexts shares
 void batch_cache_free(cvh_context *c);
 int batch_fail(cvh_context *const *ctxs, int n, int code, const char *fmt, ...);
-int batch_check(cvh_context *const *ctxs, int n, bool csv = true);
+enum MemberNeeds { kMembersListed, kMembersWithImage, kMembersForCsv };
+int members_check(cvh_context *const *ctxs, int n, const char *what, MemberNeeds needs);
 int join_into_leader(cvh_context *const *ctxs, int n, const int *member = nullptr);
 int grow_table(cvh_context *c, DeviceTable *t, size_t bytes);
 void free_table(DeviceTable *t);

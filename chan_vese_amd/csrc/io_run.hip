@@ -17,21 +17,6 @@ int guarded(cvh_context *const *ctxs, int n, const char *what, F body)
   catch (...) { return batch_fail(ctxs, n, CVH_ERR_NOMEM, "%s: out of host memory", what); }
 }
 
-// Who may be in a batch, before anything is touched (the members stay as they were).  `what` names the entry point.
-int members_check(cvh_context *const *ctxs, int n, const char *what)
-{
-  if (!ctxs || n < 1) return batch_fail(ctxs, 0, CVH_ERR_ARG, "%s: empty member list (ctxs = %p, n = %d)", what, (const void *)ctxs, n);
-  for (int i = 0; i < n; ++i) {
-    cvh_context *c = ctxs[i];
-    if (!c) return batch_fail(ctxs, i ? n : 0, CVH_ERR_ARG, "%s: member %d is NULL", what, i);
-    for (int j = 0; j < i; ++j)
-      if (ctxs[j] == c) return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: member %d duplicates member %d", what, i, j);
-    if (c->device != ctxs[0]->device)
-      return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: member %d is on device %d, member 0 on device %d", what, i, c->device, ctxs[0]->device);
-  }
-  return CVH_OK;
-}
-
 // p must be memory that kernels on member i's device can address: device memory of that device, managed memory, or mapped host memory
 int pointer_check(cvh_context *const *ctxs, int n, int i, const void *p, const char *what)
 {
@@ -47,13 +32,11 @@ int pointer_check(cvh_context *const *ctxs, int n, int i, const void *p, const c
 }
 
 // iterations enqueued and never synchronised are closed first, as the host-buffer calls do
-int settle(cvh_context *const *ctxs, int n, const char *what)
+int settle_all(cvh_context *const *ctxs, int n, const char *what)
 {
   for (int i = 0; i < n; ++i) {
-    cvh_context *c = ctxs[i];
-    if (!(c->timing_open || c->chain_pending)) continue;
-    const int rc = sync_impl(c);
-    if (rc != CVH_OK) return batch_fail(ctxs, n, rc, "%s: member %d: %s", what, i, c->err);
+    const int rc = settle(ctxs[i]);
+    if (rc != CVH_OK) return batch_fail(ctxs, n, rc, "%s: member %d: %s", what, i, ctxs[i]->err);
   }
   return CVH_OK;
 }
@@ -63,8 +46,6 @@ int settle(cvh_context *const *ctxs, int n, const char *what)
 // this context (ev_io_out, recorded behind that call's launch) -- long past unless that call is still queued behind the caller's stream.
 int stage(cvh_context *lead, size_t host_bytes, size_t dev_bytes)
 {
-  if (!lead->ev_io_in) HIPCHK(lead, hipEventCreateWithFlags(&lead->ev_io_in, hipEventDisableTiming));
-  if (!lead->ev_io_out) HIPCHK(lead, hipEventCreateWithFlags(&lead->ev_io_out, hipEventDisableTiming));
   HIPCHK(lead, hipEventSynchronize(lead->ev_io_out));
   if (lead->h_io_cap < host_bytes) {
     if (lead->h_io) { HIPCHK(lead, hipHostFree(lead->h_io)); lead->h_io = nullptr; lead->h_io_cap = 0; }
@@ -80,10 +61,6 @@ int stage(cvh_context *lead, size_t host_bytes, size_t dev_bytes)
 int open_call(cvh_context *const *ctxs, int n, void *stream)
 {
   cvh_context *lead = ctxs[0];
-  if (!lead->ev_io_in) HIPCHK(lead, hipEventCreateWithFlags(&lead->ev_io_in, hipEventDisableTiming));
-  if (!lead->ev_io_out) HIPCHK(lead, hipEventCreateWithFlags(&lead->ev_io_out, hipEventDisableTiming));
-  for (int i = 1; i < n; ++i)
-    if (!ctxs[i]->ev_join) HIPCHK(ctxs[i], hipEventCreateWithFlags(&ctxs[i]->ev_join, hipEventDisableTiming));
   { const int rc = join_into_leader(ctxs, n); if (rc != CVH_OK) return rc; }
   HIPCHK(lead, hipEventRecord(lead->ev_io_in, (hipStream_t)stream));
   HIPCHK(lead, hipStreamWaitEvent(lead->stream, lead->ev_io_in, 0));
@@ -110,7 +87,7 @@ unsigned lay_out(CvhIoMember *tab, int n)
 
 int ingest(cvh_context *const *ctxs, int n, const uint8_t *const *d_imgs, int layout, void *stream, const char *what)
 {
-  int rc = members_check(ctxs, n, what);
+  int rc = members_check(ctxs, n, what, kMembersListed);
   if (rc != CVH_OK) return rc;
   if (!d_imgs) return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: the list of device pointers is NULL", what);
   if (layout != CVH_LAYOUT_PLANAR && layout != CVH_LAYOUT_INTERLEAVED)
@@ -118,7 +95,7 @@ int ingest(cvh_context *const *ctxs, int n, const uint8_t *const *d_imgs, int la
   cvh_context *lead = ctxs[0];
   HIPCHK(lead, hipSetDevice(lead->device));
   for (int i = 0; i < n; ++i) { rc = pointer_check(ctxs, n, i, d_imgs[i], what); if (rc != CVH_OK) return rc; }
-  rc = settle(ctxs, n, what);
+  rc = settle_all(ctxs, n, what);
   if (rc != CVH_OK) return rc;
   // staging: [member table][8 sums per member, zero] uploaded; behind them the planes of the members whose stop norm the host takes
   const size_t sums_off = align_up((size_t)n * sizeof(CvhIoMember), 256), dev_bytes = sums_off + (size_t)n * 8 * sizeof(unsigned long long);
@@ -126,7 +103,7 @@ int ingest(cvh_context *const *ctxs, int n, const uint8_t *const *d_imgs, int la
   size_t host_bytes = dev_bytes;
   for (int i = 0; i < n; ++i) {
     const cvh_context *c = ctxs[i];
-    if (c->C == 1 && c->n < ((size_t)1 << 36)) continue;   // exact on the device: 2^36 * 255^2 < 2^53 (image_stats)
+    if (stop_norm_exact_on_device(c)) continue;
     fetch_off[i] = host_bytes = align_up(host_bytes, 256);
     host_bytes += c->img_stride * c->C;
   }
@@ -185,20 +162,13 @@ int ingest(cvh_context *const *ctxs, int n, const uint8_t *const *d_imgs, int la
   } else {
     for (int i : on_host) host_norm(i);
   }
-  for (int i = 0; i < n; ++i) {
-    cvh_context *c = ctxs[i];
-    for (int k = 0; k < c->C; ++k) c->sum_img[k] = (double)sums[8 * i + 2 * k];   // exact: < 2^53
-    c->stop_norm = fetch_off[i] ? norm[i] : sqrt((double)sums[8 * i + 1]);
-    c->stop_valid = true;
-    c->have_image = true;
-    c->sums_valid = false;
-  }
+  for (int i = 0; i < n; ++i) plane_sums_arrived(ctxs[i], sums + 8 * i, fetch_off[i] ? &norm[i] : nullptr);
   return CVH_OK;
 }
 
 int mask_out(cvh_context *const *ctxs, int n, uint8_t *const *d_masks, int invert, void *stream, const char *what)
 {
-  int rc = members_check(ctxs, n, what);
+  int rc = members_check(ctxs, n, what, kMembersListed);
   if (rc != CVH_OK) return rc;
   if (!d_masks) return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: the list of device pointers is NULL", what);
   cvh_context *lead = ctxs[0];
@@ -206,7 +176,7 @@ int mask_out(cvh_context *const *ctxs, int n, uint8_t *const *d_masks, int inver
   for (int i = 0; i < n; ++i) { rc = pointer_check(ctxs, n, i, d_masks[i], what); if (rc != CVH_OK) return rc; }
   for (int i = 0; i < n; ++i)   // (the arguments first, then the members' state: as the single-context getters)
     if (!ctxs[i]->have_u) return batch_fail(ctxs, n, CVH_ERR_STATE, "%s: member %d has no level set", what, i);
-  rc = settle(ctxs, n, what);
+  rc = settle_all(ctxs, n, what);
   if (rc != CVH_OK) return rc;
   for (int i = 0; i < n; ++i) {
     rc = ensure_f64_mirror(ctxs[i]);
@@ -268,11 +238,11 @@ extern "C" int cvh_get_mask_device(cvh_context *c, uint8_t *d_mask, int invert, 
 
 static int checkerboard_batch(cvh_context *const *ctxs, int n, const char *what)
 {
-  int rc = members_check(ctxs, n, what);
+  int rc = members_check(ctxs, n, what, kMembersListed);
   if (rc != CVH_OK) return rc;
   cvh_context *lead = ctxs[0];
   HIPCHK(lead, hipSetDevice(lead->device));
-  rc = settle(ctxs, n, what);
+  rc = settle_all(ctxs, n, what);
   if (rc != CVH_OK) return rc;
   // the h + w sine factors of every distinct shape, from the host's libm as cvh_init_checkerboard's: ONE copy with the member table
   const double pi = 3.14159265358979323846;
@@ -306,7 +276,7 @@ static int checkerboard_batch(cvh_context *const *ctxs, int n, const char *what)
     CvhIoMember &m = tab[i];
     m.src = db + shape_off[shape_of[i]];
     m.src2 = (const double *)m.src + c->h;
-    m.dst = c->d_u[c->chain_pb & 1];   // the buffer whose parity is the chain-mode sum set's: see cvh_set_levelset
+    m.dst = c->d_u[c->chain_pb & 1];   // the buffer whose parity is the chain-mode sum set's: see levelset_arrived
     m.state_zero = &c->d_state->steps_done;
     m.chain_zero = &c->d_chain->v[(c->chain_pb + 1) & 3][0];
     m.n = c->n; m.h = c->h; m.w = c->w; m.C = c->C;
@@ -320,19 +290,9 @@ static int checkerboard_batch(cvh_context *const *ctxs, int n, const char *what)
   rc = close_call(ctxs, n, nullptr, false);
   if (rc != CVH_OK) return rc;
   HIPCHK(lead, hipStreamSynchronize(lead->stream));
-  for (int i = 0; i < n; ++i) {   // the launch has run: only now does the host's bookkeeping follow it
-    cvh_context *c = ctxs[i];
-    c->cur_base = c->chain_pb & 1; c->steps_done = 0; c->enqueued = 0;
-    c->have_u = true;
-    c->sums_valid = false;
-    c->mirror_valid = true;
-    if (c->state_bits == 32) {
-      rc = adopt_f32_state(c);
-      if (rc != CVH_OK) return batch_fail(ctxs, n, rc, "%s: member %d: %s", what, i, c->err);
-    }
-    // the host's share of a new run (reset_run_impl; the device's share ran inside the launch)
-    c->run_pol = -1; c->run_alone = -1; c->run_chunk = -1;
-    c->h_status[0] = 0; c->h_status[1] = 0;
+  for (int i = 0; i < n; ++i) {   // the launch has run, the device's share of a new run (reset_run_impl) inside it
+    rc = levelset_arrived(ctxs[i], true);
+    if (rc != CVH_OK) return batch_fail(ctxs, n, rc, "%s: member %d: %s", what, i, ctxs[i]->err);
   }
   return CVH_OK;
 }
@@ -385,20 +345,15 @@ extern "C" int cvh_set_levelset_device(cvh_context *c, const void *d_u, int bits
   HIPCHK(c, hipSetDevice(c->device));
   rc = pointer_check(&c, 1, 0, d_u, what);
   if (rc != CVH_OK) return rc;
-  rc = settle(&c, 1, what);
+  rc = settle_all(&c, 1, what);
   if (rc != CVH_OK) return rc;
-  const int base = c->chain_pb & 1;   // see cvh_set_levelset
+  const int base = c->chain_pb & 1;   // see levelset_arrived
   rc = open_call(&c, 1, stream);
   if (rc != CVH_OK) return rc;
   if (bits == 64) HIPCHK(c, hipMemcpyAsync(c->d_u[base], d_u, c->n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   else HIPCHK(c, cvh_launch_state_widen((const float *)d_u, c->d_u[base], c->n, c->stream));   // the floats' exact double values
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->cur_base = base; c->steps_done = 0; c->enqueued = 0;   // the level set has arrived: the host's bookkeeping follows it
-  c->have_u = true;
-  c->sums_valid = false;
-  c->mirror_valid = true;
-  if (c->state_bits == 32) { rc = adopt_f32_state(c); if (rc != CVH_OK) return rc; }
-  return reset_run_impl(c);
+  return levelset_arrived(c);
 }
 
 extern "C" int cvh_get_levelset_device(cvh_context *c, void *d_u, int bits, void *stream)
@@ -411,7 +366,7 @@ extern "C" int cvh_get_levelset_device(cvh_context *c, void *d_u, int bits, void
   rc = pointer_check(&c, 1, 0, d_u, what);
   if (rc != CVH_OK) return rc;
   if (!c->have_u) return fail(c, CVH_ERR_STATE, "%s: no level set", what);
-  rc = settle(&c, 1, what);
+  rc = settle_all(&c, 1, what);
   if (rc != CVH_OK) return rc;
   rc = ensure_f64_mirror(c);
   if (rc != CVH_OK) return rc;

@@ -7,12 +7,7 @@
 // workgroups of pm_resident_kernel the device holds at once, at most one per CU and CVH_RESIDENT_MAX_TILES (0: no cooperative launch)
 static int pm_resident_tiles_cap(cvh_context *c)
 {
-  if (c->pm_resident_cap < 0) {
-    int coop = 0;
-    c->pm_resident_cap = 0;
-    if (hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, c->device) == hipSuccess && coop)
-      c->pm_resident_cap = cvh_pm_resident_blocks_per_cu() * c->num_cus;
-  }
+  if (c->pm_resident_cap < 0) c->pm_resident_cap = launches_cooperatively(c) ? cvh_pm_resident_blocks_per_cu() * c->num_cus : 0;
   if (c->pm_resident_cap <= 0) return 0;
   int cap = c->pm_resident_cap < CVH_RESIDENT_MAX_TILES ? c->pm_resident_cap : CVH_RESIDENT_MAX_TILES;
   if (cap > c->num_cus) cap = c->num_cus;                      // one workgroup per CU
@@ -75,28 +70,12 @@ static int pm_check_args(double K, double L, double T, const char *k_prefix, cha
 static const char kPmNeedsResident[] =
     "pm_kernel 4 (resident plane) needs an even width, >= 16 rows and columns, and a plane that fits the LDS of the CUs";
 
-// CSV work that was enqueued and never synchronised is closed first, as cvh_set_image does: the resident Perona-Malik flow clears the
-// shared CvhResident block (the error word of an unsynchronised csv_resident_kernel launch with it) and reuses ev0 / ev1.
-static int pm_settle(cvh_context *c)
-{
-  if (c->timing_open || c->chain_pending || c->resident_used) return sync_impl(c);
-  return CVH_OK;
-}
-
 // the FP64 ping-pong planes a channel is smoothed in
 static int ensure_pm_planes(cvh_context *c)
 {
   for (int k = 0; k < 2; ++k)
     if (!c->d_pm[k]) HIPCHK(c, hipMalloc((void **)&c->d_pm[k], c->n * sizeof(double)));
   return CVH_OK;
-}
-
-// the planes changed on the device: the stop norm and the region means are taken again
-static void pm_planes_changed(cvh_context *c, float ms)
-{
-  c->last_pm_ms = ms;
-  c->stop_valid = false;
-  c->sums_valid = false;
 }
 
 // Perona-Malik with the plane resident in LDS: per channel uint8 -> FP64 plane, ONE cooperative launch per chunk of time steps,
@@ -238,7 +217,9 @@ extern "C" int cvh_perona_malik(cvh_context *c, double K, double L, double T)
   char msg[256];
   if (pm_check_args(K, L, T, "cvh_perona_malik: ", msg, sizeof(msg)) != CVH_OK) return fail(c, CVH_ERR_ARG, "%s", msg);
   HIPCHK(c, hipSetDevice(c->device));
-  int rc = pm_settle(c);
+  // CSV work that was enqueued and never synchronised is closed first, as cvh_set_image does: the resident Perona-Malik flow clears the
+  // shared CvhResident block (the error word of an unsynchronised csv_resident_kernel launch with it) and reuses ev0 / ev1.
+  int rc = settle(c);
   if (rc == CVH_OK) rc = ensure_pm_planes(c);
   if (rc != CVH_OK) return rc;
   const int trips = cvh_pm_trip_count(L, T);
@@ -260,7 +241,8 @@ extern "C" int cvh_perona_malik(cvh_context *c, double K, double L, double T)
   HIPCHK(c, hipStreamSynchronize(c->stream));
   float ms = 0.f;
   HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-  pm_planes_changed(c, ms);
+  c->last_pm_ms = ms;
+  planes_changed(c);   // the stop norm and the region means are taken again
   if (resident && c->h_resident[0]) {
     c->h_resident[0] = 0;
     return fail(c, CVH_ERR_HIP, "cvh_perona_malik: a wait of the resident kernel gave up (a workgroup was not resident, or a fault); the planes are undefined");
@@ -299,7 +281,7 @@ static bool pm_batch_add(PmBatchLaunch &b, cvh_context *const *ctxs, int i, int 
 
 extern "C" int cvh_perona_malik_batch(cvh_context *const *ctxs, int n, const double *K, const double *L, const double *T)
 {
-  int rc = batch_check(ctxs, n, false);
+  int rc = members_check(ctxs, n, "batch", kMembersWithImage);
   if (rc != CVH_OK) return rc;
   if (!K || !L || !T) return batch_fail(ctxs, n, CVH_ERR_ARG, "pm batch: K, L and T must each hold the n = %d members' values", n);
   char msg[256];
@@ -323,7 +305,7 @@ extern "C" int cvh_perona_malik_batch(cvh_context *const *ctxs, int n, const dou
   }
   // CSV work that was enqueued and never synchronised is closed first, as cvh_perona_malik does
   for (int i = 0; i < n; ++i) {
-    rc = pm_settle(ctxs[i]);
+    rc = settle(ctxs[i]);
     if (rc != CVH_OK) return batch_fail(ctxs, n, rc, "pm batch: member %d: %s", i, ctxs[i]->err);
   }
   // packing (include/chanvese_hip.h): round k = channel k; inside a round FAST planes, then STRICT ones; first fit in member order
@@ -350,7 +332,6 @@ extern "C" int cvh_perona_malik_batch(cvh_context *const *ctxs, int n, const dou
       if (!fused[i]) continue;
       rc = ensure_pm_planes(c);
       if (rc != CVH_OK) return rc;
-      if (!c->ev_join) HIPCHK(c, hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
     }
     rc = ensure_resident_buffers(lead);
     if (rc == CVH_OK) rc = ensure_pm_halo(lead);
@@ -433,7 +414,8 @@ extern "C" int cvh_perona_malik_batch(cvh_context *const *ctxs, int n, const dou
       (void)cvh_launch_pm_resident_batch(ba, bl.fast, bl.nr, lead->stream, &nb);
       for (int i : bl.members) {
         cvh_context *c = ctxs[i];
-        pm_planes_changed(c, ms);
+        c->last_pm_ms = ms;
+        planes_changed(c);
         if (bl.round != 0) continue;   // launch_info describes the launch of the member's first plane
         snprintf(c->pm_desc, sizeof(c->pm_desc), "kernel=%s grid=%u block=%u lds_bytes=%u steps_per_launch=%d tiles_y=%d tiles_x=%d launches=1 graph_launches=0 trips=%d planes=%d batch_planes=%d batch_launches=%d",
                  nb.name, nb.grid, nb.block, nb.lds, trips[i], (c->h + 8 * bl.nr - 1) / (8 * bl.nr), (c->w + cvh_resident_tile_w() - 1) / cvh_resident_tile_w(),
