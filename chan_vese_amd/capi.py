@@ -29,6 +29,7 @@ EXPORTS = [
     "cvh_perona_malik_batch",
     "cvh_set_image_device", "cvh_get_image_device", "cvh_set_levelset_device", "cvh_get_levelset_device",
     "cvh_get_mask_device", "cvh_set_image_device_batch", "cvh_init_checkerboard_batch", "cvh_get_mask_device_batch",
+    "cvh_reinit", "cvh_reinit_batch",
 ]
 LAYOUT_PLANAR, LAYOUT_INTERLEAVED = 0, 1
 
@@ -105,6 +106,8 @@ def lib():
         "cvh_set_image_device_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.POINTER(vp), C.c_int, vp]),
         "cvh_init_checkerboard_batch": (C.c_int, [C.POINTER(vp), C.c_int]),
         "cvh_get_mask_device_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.POINTER(vp), C.c_int, vp]),
+        "cvh_reinit": (C.c_int, [vp, ip]),
+        "cvh_reinit_batch": (C.c_int, [C.POINTER(vp), C.c_int, ip]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -236,6 +239,51 @@ def get_mask_device_batch(contexts, ptrs, invert=False, stream=0):
     _batch_chk(lib().cvh_get_mask_device_batch(_member_array(contexts), n, _address_array(list(ptrs), n), int(bool(invert)), int(stream) or None))
 
 
+def reinit_batch(contexts):
+    """cvh_reinit_batch: Context.reinit for every context (any mix of shapes) with one set of launches.  Returns [changed] per context."""
+    contexts = list(contexts)
+    n = len(contexts)
+    changed = (C.c_int * max(n, 1))()
+    _batch_chk(lib().cvh_reinit_batch(_member_array(contexts), n, changed))
+    return [bool(changed[i]) for i in range(n)]
+
+
+def _segmented(contexts, max_steps, every, run):
+    """run(contexts, k) -> [(steps, norm)] in segments of `every` iterations with a reinit_batch of the members still iterating between
+    segments; a member whose stop rule fired inside a segment leaves for the later ones.  every <= 0: one run(contexts, max_steps)."""
+    if every <= 0 or not contexts:
+        return run(contexts, max_steps)
+    total, norm = [0] * len(contexts), [0.0] * len(contexts)
+    live = list(range(len(contexts)))
+    left = max_steps
+    while live and left != 0:
+        k = every if left < 0 else min(every, left)
+        res = run([contexts[i] for i in live], k)
+        for i, (done, nrm) in zip(live, res):
+            total[i] += done
+            norm[i] = nrm
+        live = [i for i in live if not contexts[i].sync()[2]]   # (nothing is in flight: sync reports whether the stop rule fired)
+        if left > 0:
+            left -= k
+        if live and left != 0:
+            reinit_batch([contexts[i] for i in live])
+    return list(zip(total, norm))
+
+
+def run_with_reinit(ctx, max_steps=-1, every=0):
+    """Context.run in segments of `every` iterations with a reinit between segments; stops as soon as the stop rule fired inside a
+    segment (no reinit follows).  max_steps is the total budget (< 0: unlimited).  Returns (total steps, last norm).  every <= 0 is
+    exactly ctx.run(max_steps)."""
+    return _segmented([ctx], max_steps, every, lambda cs, k: [cs[0].run(k)])[0]
+
+
+def run_batch_with_reinit(contexts, max_steps=-1, every=0):
+    """run_batch in segments of `every` iterations with a reinit_batch between segments.  A member whose stop rule fired inside a
+    segment leaves the batch for the later segments (and is not reinitialised again).  Returns [(total steps, last norm)] per context;
+    every <= 0 is exactly run_batch(contexts, max_steps)."""
+    return _segmented(list(contexts), max_steps, every, run_batch)
+
+
 class Context:
     """One image on one GPU: thin RAII wrapper over cvh_context."""
 
@@ -317,6 +365,13 @@ class Context:
 
     def init_checkerboard(self):
         self._chk(self._L.cvh_init_checkerboard(self._h))
+
+    def reinit(self):
+        """cvh_reinit: the level set becomes the exact signed distance to the pixel-edge front of its own mask, on the device.
+        Returns whether it changed (False: the mask is uniform, nothing about the context moved)."""
+        changed = C.c_int(0)
+        self._chk(self._L.cvh_reinit(self._h, C.byref(changed)))
+        return bool(changed.value)
 
     def get_levelset(self):
         u = np.empty((self.h, self.w), dtype=np.float64)

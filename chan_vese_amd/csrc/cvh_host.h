@@ -11,6 +11,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <atomic>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -88,6 +89,7 @@ struct cvh_context {   // opaque to callers; four groups
   int geom_cus = 0;             // > 0: the CUs the automatic strip count is sized for (a fused batch: this context's share of the chip; batch_share)
   double stop_cond_h = 0.0; // tol * stop_norm of the current run (a launch argument; prepare_host)
   float last_run_ms = 0.f, last_pm_ms = 0.f;
+  float last_reinit_ms = 0.f;   // device interval (table copy, three launches, flag copy) of the last reinitialisation this context led
   // ---- options: cvh_set_params, cvh_set_option ----
   cvh_params p{};
   int state_bits = 64;          // option "state"
@@ -131,6 +133,8 @@ struct cvh_context {   // opaque to callers; four groups
   void *h_io = nullptr;
   size_t h_io_cap = 0;
   hipEvent_t ev_io_in = nullptr, ev_io_out = nullptr;   // ev_io_out also marks the last read of h_io by a copy still in flight
+  void *d_reinit = nullptr;      // workspace of cvh_reinit (class words + the two distance fields, reinit_kernels.hip): allocated by the
+                                 // first call, idle while CSV streams -- not part of live_footprint
   int coop_launch = -1;          // does the device launch cooperatively (-1: not asked yet; launches_cooperatively)
   int resident_cap = -1;         // workgroups of csv_resident_kernel the device holds at once (-1: not asked yet, 0: unavailable)
   int pm_resident_cap = -1;      // workgroups of pm_resident_kernel the device holds at once (-1: not asked yet)
@@ -215,6 +219,9 @@ int members_check(cvh_context *const *ctxs, int n, const char *what, MemberNeeds
 int join_into_leader(cvh_context *const *ctxs, int n, const int *member = nullptr);
 int grow_table(cvh_context *c, DeviceTable *t, size_t bytes);
 void free_table(DeviceTable *t);
+
+// io_run.hip: launch sets (three kernels for all members) of cvh_reinit / cvh_reinit_batch so far in this process (debug_exports.hip)
+extern std::atomic<unsigned long> g_reinit_launch_sets;
 
 // What launches(), which returns CVH_OK or an error already recorded with fail(), enqueues on c's stream, captured and instantiated into
 // *out.  A capture that does not end in a graph fails with end_fmt (one %s: the HIP error).

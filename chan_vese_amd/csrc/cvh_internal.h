@@ -198,16 +198,19 @@ struct CvhPmBatchArgs { const CvhPmBatchPlane *planes; const unsigned *map; int 
 // uint8 plane <-> FP64 state of one plane of a batch's load / store launch
 struct CvhPmIoPlane { uint8_t *img; double *state; unsigned long long n; };
 
-// Device-memory I/O (io_kernels.hip, io_run.hip): one entry per member of a batch kernel's grid.  A kernel reads the fields its operation
-// names; the host leaves the others zero.  The table lives in the leader's device table, 16-byte aligned entries.
+// Device-memory I/O (io_kernels.hip, io_run.hip) and reinitialisation (reinit_kernels.hip): one entry per member of a batch kernel's grid.
+// A kernel reads the fields its operation names; the host leaves the others zero.  The table lives in the leader's device table, 16-byte
+// aligned entries.
 struct CvhIoMember {
-  const void *src;                    // ingest: the caller's bytes; mask: the level set (double); checkerboard: the h row factors
+  const void *src;                    // ingest: the caller's bytes; mask, reinit: the level set (double); checkerboard: the h row factors
   const void *src2;                   // checkerboard: the w column factors
-  void *dst;                          // mask / interleaved planes out: the caller's buffer; checkerboard: the level set
-  uint8_t *plane[CVH_MAX_CHANNELS];   // the context's planes (ingest: written; planes out: read)
-  unsigned long long *sums;           // ingest: {sum p, sum p^2} per plane, zeroed before the launch
-  int *state_zero;                    // checkerboard: the four run words of CvhState a new run clears (steps_done, stopped, ticket, pending)
-  long long *chain_zero;              // checkerboard: the chain-mode sum set a new run clears (64 integers)
+  void *dst;                          // mask / interleaved planes out: the caller's buffer; checkerboard, reinit: the level set written
+  uint8_t *plane[CVH_MAX_CHANNELS];   // the context's planes (ingest: written; planes out: read); reinit: [0] the class words of the
+                                      // bands, [1] the distance fields (the context's workspace)
+  unsigned long long *sums;           // ingest: {sum p, sum p^2} per plane, zeroed before the launch; reinit: the flag word, zeroed
+                                      // (bit 0: an outside pixel exists, bit 1: an inside pixel exists)
+  int *state_zero;                    // checkerboard, reinit: the four run words of CvhState a new run clears (steps_done, stopped, ticket, pending)
+  long long *chain_zero;              // checkerboard, reinit: the chain-mode sum set a new run clears (64 integers)
   unsigned long long n;               // pixels
   int h, w, C;
   int interleaved;                    // ingest: the source is h * w * C interleaved bytes (planar otherwise)
@@ -222,6 +225,16 @@ hipError_t cvh_launch_io_checkerboard(const CvhIoMember *tab, int nmem, unsigned
 hipError_t cvh_launch_io_mask(const CvhIoMember *tab, int nmem, unsigned grid, int invert, hipStream_t s);
 hipError_t cvh_launch_io_image_out3(const CvhIoMember *tab, int nmem, unsigned grid, hipStream_t s);
 hipError_t cvh_launch_io_narrow(const double *u, float *out, size_t n, hipStream_t s);   // out = (float)u
+// reinitialisation (reinit_kernels.hip): bands of CVH_REINIT_BAND rows in the column pass (one class word per band and column), rows of up to
+// CVH_REINIT_LDS_COLS columns staged in LDS by the row pass (8 bytes per column: 64 KiB)
+#define CVH_REINIT_BAND 32
+#define CVH_REINIT_LDS_COLS 8192
+unsigned cvh_reinit_column_blocks(int h, int w);     // workgroups of a member in the two column launches
+unsigned cvh_reinit_row_blocks(int h);               // and in the row launch
+size_t cvh_reinit_bits_bytes(int h, int w);          // the class words' share of the workspace (the distance fields follow)
+size_t cvh_reinit_workspace_bytes(int h, int w);
+hipError_t cvh_launch_reinit(const CvhIoMember *cols, unsigned col_grid, const CvhIoMember *rows, unsigned row_grid, int nmem, int max_w,
+                             hipStream_t s);
 // rows-per-tile options of the step kernel
 void cvh_step_grid(int h, int w, int tile_rows, int *tiles_x, int *tiles_y);
 int cvh_step_max_blocks(int h, int w);

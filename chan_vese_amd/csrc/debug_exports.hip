@@ -69,6 +69,19 @@ extern "C" int cvh_debug_num_cus(cvh_context *c, int *out)
   return CVH_OK;
 }
 
+// Diagnostic (not part of include/chanvese_hip.h): launch sets of cvh_reinit / cvh_reinit_batch so far in this process -- one set is the
+// three kernels of reinit_kernels.hip over all members of the call (tests/test_gpu_reinit.py: a batch of n is one set, not n).
+extern "C" unsigned long cvh_debug_reinit_launch_sets(void) { return g_reinit_launch_sets.load(); }
+
+// Diagnostic (not part of include/chanvese_hip.h): device time (HIP events on the leader's stream: table copy, the three launches, flag
+// copy) of the last cvh_reinit / cvh_reinit_batch this context led (tools/reinit_probe.py).
+extern "C" int cvh_debug_last_reinit_ms(cvh_context *c, float *ms)
+{
+  if (!c || !ms) return CVH_ERR_ARG;
+  *ms = c->last_reinit_ms;
+  return CVH_OK;
+}
+
 // Diagnostic (not part of include/chanvese_hip.h): copies the stamp buffer of "debug_times".
 extern "C" int cvh_debug_read(cvh_context *c, unsigned long long *out, long max_words, long *words, int *nblocks)
 {

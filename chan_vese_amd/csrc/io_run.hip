@@ -1,6 +1,7 @@
 // io_run.hip — host side of the device-memory entry points (include/chanvese_hip.h): contexts and batches of contexts are fed from, and
 // read into, device memory the caller owns, ordered against the caller's stream by events; one launch per batch and operation.
-// The single-context calls are batches of one member: one code path.
+// The single-context calls are batches of one member: one code path.  Reinitialisation (cvh_reinit, cvh_reinit_batch) lives here too: it
+// is a level set leaving and arriving without crossing to the host, on the same member tables and stream joins.
 #include <thread>
 
 #include "cvh_host.h"
@@ -376,4 +377,96 @@ extern "C" int cvh_get_levelset_device(cvh_context *c, void *d_u, int bits, void
   if (bits == 64) HIPCHK(c, hipMemcpyAsync(d_u, u, c->n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   else HIPCHK(c, cvh_launch_io_narrow(u, (float *)d_u, c->n, c->stream));
   return close_call(&c, 1, stream, true);
+}
+
+std::atomic<unsigned long> g_reinit_launch_sets{0};
+
+// Reinitialisation: the level set of every member becomes the signed distance to the pixel-edge front of its mask (reinit_kernels.hip).
+// Per member it is cvh_get_levelset -> the header's definition -> cvh_set_levelset: the result lands in the buffer cvh_set_levelset
+// writes, and a member whose mask is not uniform then begins a new run through levelset_arrived, the device's half of it done by the
+// last launch.  A member with a uniform mask keeps everything, its run state included.
+static int reinit_batch(cvh_context *const *ctxs, int n, int *changed, const char *what)
+{
+  int rc = members_check(ctxs, n, what, kMembersListed);
+  if (rc != CVH_OK) return rc;
+  for (int i = 0; i < n; ++i) {
+    const cvh_context *c = ctxs[i];
+    if (!c->have_u) return batch_fail(ctxs, n, CVH_ERR_STATE, "%s: member %d has no level set", what, i);
+    // squared distances are 32-bit integers, vertical distances 16-bit with one value set aside
+    if ((unsigned long long)c->h * c->h + (unsigned long long)c->w * c->w >= (1ull << 32))
+      return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: member %d: %d x %d is too large, h^2 + w^2 must stay below 2^32", what, i, c->h, c->w);
+  }
+  cvh_context *lead = ctxs[0];
+  HIPCHK(lead, hipSetDevice(lead->device));
+  rc = settle_all(ctxs, n, what);
+  if (rc != CVH_OK) return rc;
+  for (int i = 0; i < n; ++i) {
+    cvh_context *c = ctxs[i];
+    rc = ensure_f64_mirror(c);   // "state" = 32: the class of a float is the class of its double
+    if (rc == CVH_OK && !c->d_reinit) {   // the workspace: allocated on the first call, kept with the context
+      const hipError_t e = hipMalloc(&c->d_reinit, cvh_reinit_workspace_bytes(c->h, c->w));
+      if (e != hipSuccess) { c->d_reinit = nullptr; rc = fail(c, CVH_ERR_HIP, "hipMalloc of the reinitialisation workspace: %s", hipGetErrorString(e)); }
+    }
+    if (rc != CVH_OK) return batch_fail(ctxs, n, rc, "%s: member %d: %s", what, i, c->err);
+  }
+  // staging: [column-pass table][row-pass table][one flag word per member, zero]
+  const size_t tab_bytes = align_up((size_t)n * sizeof(CvhIoMember), 256), flags_off = 2 * tab_bytes;
+  const size_t bytes = flags_off + (size_t)n * sizeof(unsigned long long);
+  rc = stage(lead, bytes, bytes);
+  if (rc != CVH_OK) return rc;
+  unsigned char *const hb = (unsigned char *)lead->h_io, *const db = (unsigned char *)lead->io_table.d;
+  memset(hb, 0, bytes);
+  CvhIoMember *cols = (CvhIoMember *)hb, *rows = (CvhIoMember *)(hb + tab_bytes);
+  int max_w = 0;
+  for (int i = 0; i < n; ++i) {
+    cvh_context *c = ctxs[i];
+    CvhIoMember &m = cols[i];
+    m.src = c->d_u[current_buffer(c)];
+    m.dst = c->d_u[c->chain_pb & 1];   // where cvh_set_levelset puts a level set: see levelset_arrived
+    m.plane[0] = (uint8_t *)c->d_reinit;
+    m.plane[1] = (uint8_t *)c->d_reinit + cvh_reinit_bits_bytes(c->h, c->w);
+    m.sums = (unsigned long long *)(db + flags_off) + i;
+    m.state_zero = &c->d_state->steps_done;
+    m.chain_zero = &c->d_chain->v[(c->chain_pb + 1) & 3][0];
+    m.n = c->n; m.h = c->h; m.w = c->w; m.C = c->C;
+    rows[i] = m;
+    m.nblk = cvh_reinit_column_blocks(c->h, c->w);
+    rows[i].nblk = cvh_reinit_row_blocks(c->h);
+    max_w = std::max(max_w, c->w);
+  }
+  const unsigned col_grid = lay_out(cols, n), row_grid = lay_out(rows, n);
+  rc = open_call(ctxs, n, nullptr);
+  if (rc != CVH_OK) return rc;
+  HIPCHK(lead, hipEventRecord(lead->ev0, lead->stream));   // (free: settle closed any timed run)
+  HIPCHK(lead, hipMemcpyAsync(db, hb, bytes, hipMemcpyHostToDevice, lead->stream));
+  HIPCHK(lead, cvh_launch_reinit((const CvhIoMember *)db, col_grid, (const CvhIoMember *)(db + tab_bytes), row_grid, n, max_w, lead->stream));
+  ++g_reinit_launch_sets;
+  HIPCHK(lead, hipMemcpyAsync(hb + flags_off, db + flags_off, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost, lead->stream));
+  HIPCHK(lead, hipEventRecord(lead->ev1, lead->stream));
+  rc = close_call(ctxs, n, nullptr, false);
+  if (rc != CVH_OK) return rc;
+  HIPCHK(lead, hipStreamSynchronize(lead->stream));   // the ONE host wait of the call: which members changed
+  HIPCHK(lead, hipEventElapsedTime(&lead->last_reinit_ms, lead->ev0, lead->ev1));
+  const unsigned long long *flags = (const unsigned long long *)(hb + flags_off);
+  for (int i = 0; i < n; ++i) {
+    const bool moved = (flags[i] & 3) == 3;
+    if (changed) changed[i] = moved ? 1 : 0;
+    if (!moved) continue;
+    rc = levelset_arrived(ctxs[i], true);
+    if (rc != CVH_OK) return batch_fail(ctxs, n, rc, "%s: member %d: %s", what, i, ctxs[i]->err);
+  }
+  return CVH_OK;
+}
+
+extern "C" int cvh_reinit_batch(cvh_context *const *ctxs, int n, int *changed)
+{
+  static const char what[] = "cvh_reinit_batch";
+  return guarded(ctxs, n, what, [&]() { return reinit_batch(ctxs, n, changed, what); });
+}
+
+extern "C" int cvh_reinit(cvh_context *c, int *changed)
+{
+  if (!c) return CVH_ERR_ARG;
+  static const char what[] = "cvh_reinit";
+  return guarded(&c, 1, what, [&]() { return reinit_batch(&c, 1, changed, what); });
 }

@@ -15,7 +15,7 @@
 // --line-color, one frame for t = 0 and one after every iteration, :926-931,:997); the overlay
 // text of -O is not rendered (no font rasteriser here), --fps has nothing to act on.
 // Additions that do not collide with reference options: --dump-u, --dump-mask, --device, --math,
-// --state, --rect, --circ, --verbose.
+// --state, --rect, --circ, --reinit, --verbose.
 #include <algorithm>
 #include <cctype>
 #include <cerrno>
@@ -168,7 +168,8 @@ const Spec kSpecs[] = {
     {"segment", 'S', 0}, {"grayscale", 'g', 0}, {"video", 'V', 0}, {"overlay-text", 'O', 0},
     {"invert-selection", 'I', 0}, {"select", 's', 0}, {"rectangle", 'R', 0}, {"circle", 'C', 0},
     // additions of this build
-    {"dump-u", 0, 1}, {"dump-mask", 0, 1}, {"device", 0, 1}, {"math", 0, 1}, {"state", 0, 1}, {"rect", 0, 1}, {"circ", 0, 1}, {"verbose", 0, 0}};
+    {"dump-u", 0, 1}, {"dump-mask", 0, 1}, {"device", 0, 1}, {"math", 0, 1}, {"state", 0, 1}, {"rect", 0, 1}, {"circ", 0, 1}, {"reinit", 0, 1},
+    {"verbose", 0, 0}};
 
 struct Parsed {
   std::vector<std::pair<std::string, std::vector<std::string>>> opts;
@@ -299,6 +300,7 @@ void print_help()
       "  --device arg (=0)                  HIP device\n"
       "  --math arg (=fast)                 strict | fast (see include/chanvese_hip.h)\n"
       "  --state arg (=64)                  64 | 32: level set kept as double (the reference's CV_64FC1) or, DECLARED, as float in GPU memory\n"
+      "  --reinit arg (=0)                  reinitialise the level set to a signed distance every arg iterations (0: never); -N stays the total\n"
       "  --verbose                          print the iteration count and last norm to stderr\n"
       "\n";
 }
@@ -343,6 +345,8 @@ int main(int argc, char **argv)
   if (auto v = one("math")) math = *v;
   int state_bits = 64;
   if (auto v = one("state")) state_bits = to_int("state", *v);
+  int reinit_every = 0;
+  if (auto v = one("reinit")) reinit_every = to_int("reinit", *v);
   if (auto v = one("rect")) rect = *v;
   if (auto v = one("circ")) circ = *v;
   segment = vm.count("segment"); grayscale = vm.count("grayscale"); write_video = vm.count("video");
@@ -392,6 +396,8 @@ int main(int argc, char **argv)
   if (!rect.empty() && !circ.empty()) msg_exit("Cannot initialize with both rectangular and circular contour");
   if (math != "strict" && math != "fast") msg_exit("error: the argument ('" + math + "') for option '--math' is invalid");
   if (state_bits != 64 && state_bits != 32) msg_exit("error: the argument ('" + std::to_string(state_bits) + "') for option '--state' is invalid");
+  if (reinit_every < 0) msg_exit("Reinitialisation interval cannot be negative: " + std::to_string(reinit_every) + ".");
+  if (reinit_every > 0 && write_video) msg_exit("Reinitialisation (--reinit) cannot be combined with video output (-V).");
 
   // ---- read the image: src/main.cpp:877-887 (8-bit gray or BGR)
   Image file;
@@ -522,7 +528,19 @@ int main(int argc, char **argv)
   // ---- timestep loop: src/main.cpp:950-1001 (stop condition and every iteration on the GPU)
   int steps_done = 0;
   double last_norm = 0;
-  if (!write_video) {
+  if (reinit_every > 0) {
+    // segments of reinit_every iterations, the level set re-distanced between them; a stop inside a segment ends the run
+    for (int left = max_steps; left > 0;) {
+      const int k = std::min(reinit_every, left);
+      int done = 0, stopped = 0;
+      cvh_check(ctx, cvh_run(ctx, k, &done, &last_norm), "cvh_run");
+      cvh_check(ctx, cvh_sync(ctx, nullptr, nullptr, &stopped), "cvh_sync");
+      steps_done += done;
+      left -= k;
+      if (stopped) break;
+      if (left > 0) cvh_check(ctx, cvh_reinit(ctx, nullptr), "cvh_reinit");
+    }
+  } else if (!write_video) {
     cvh_check(ctx, cvh_run(ctx, max_steps, &steps_done, &last_norm), "cvh_run");
   } else {
     // one iteration per frame; the frame is saved before the stop test (:997-1000)

@@ -97,11 +97,12 @@ class Segmenter:
     def _stream(self):
         return torch.cuda.current_stream(self.device).cuda_stream
 
-    def segment(self, images, max_steps=-1, perona_malik=None, init="checkerboard", invert=False, layout=None):
+    def segment(self, images, max_steps=-1, perona_malik=None, init="checkerboard", invert=False, layout=None, reinit_every=0):
         """ingest -> (Perona-Malik batch) -> initial level set -> cvh_run_batch -> masks.  Returns (masks, steps, norms): masks a uint8
         tensor (N, H, W) on the images' device, valid for the next operation on the current stream without a host wait of the caller's;
         steps / norms the iterations and the last ||u_diff|| of every member.  `layout` (capi.LAYOUT_*) is needed only for a shape that is
-        both planar and interleaved (check_images)."""
+        both planar and interleaved (check_images).  reinit_every = K > 0 runs segments of K iterations with a reinitialisation of the
+        members still iterating between segments (capi.run_batch_with_reinit; max_steps stays the total budget); 0 is one cvh_run_batch."""
         layout = check_images(images, self.n, self.h, self.w, self.channels, self.device, layout)
         bits = None if isinstance(init, str) else check_levelsets(init, self.n, self.h, self.w, self.device)
         if isinstance(init, str) and init != "checkerboard":
@@ -118,7 +119,7 @@ class Segmenter:
         else:
             for i, ctx in enumerate(self.contexts):
                 ctx.set_levelset_device(init[i].data_ptr(), bits, stream)
-        res = capi.run_batch(self.contexts, max_steps)
+        res = capi.run_batch_with_reinit(self.contexts, max_steps, reinit_every)
         masks = torch.empty((self.n, self.h, self.w), dtype=torch.uint8, device=images.device)
         capi.get_mask_device_batch(self.contexts, [masks[i].data_ptr() for i in range(self.n)], invert, stream)
         return masks, [r[0] for r in res], [r[1] for r in res]

@@ -344,6 +344,38 @@ int cvh_set_image_device_batch(cvh_context *const *ctxs, int n, const uint8_t *c
 int cvh_init_checkerboard_batch(cvh_context *const *ctxs, int n);
 int cvh_get_mask_device_batch(cvh_context *const *ctxs, int n, uint8_t *const *d_masks, int invert, void *stream);
 
+/* ---- Level-set reinitialisation --------------------------------------------------------------------------------------------
+ * The reference's README lists it first under "Further ideas" ("add level set reinitialization ... avoids flattening of the
+ * zero-level set"); it has no code for it.  cvh_reinit replaces the current level set u by the exact signed Euclidean distance to the
+ * front of its own mask, on the device -- what a caller otherwise does with cvh_get_levelset, a CPU distance transform and
+ * cvh_set_levelset.  The result is defined in integers:
+ *   m(p)  = ((float)u(p) > 0), cvh_get_mask's rule (NaN, -0.0 and a positive double that rounds to 0.0f are outside);
+ *   d2(p) = min over the pixels q with m(q) != m(p) of (p.row - q.row)^2 + (p.col - q.col)^2;
+ *   u'(p) = m(p) ? sqrt((double)d2) - 0.5 : -(sqrt((double)d2) - 0.5), IEEE sqrt and one subtraction.
+ * The zero level sits halfway between neighbouring pixels of opposite class (the front is quantised to pixel edges), |u'| >= 0.5
+ * everywhere, and the mask is unchanged bit for bit.  A UNIFORM mask (no pixel of the other class) is not an error: the level set
+ * and the context -- its run state included -- stay exactly as they are and *changed is 0.  Otherwise *changed is 1 and a new run
+ * begins exactly as after cvh_set_levelset of the same values (with "state" = 32 the class is taken from the float state and the new
+ * values are the doubles above rounded to float).  Iterations in flight are settled first.  `changed` may be NULL.
+ * cvh_reinit_batch serves n contexts of one device, of any mix of shapes and channel counts, with ONE set of three launches on member
+ * 0's stream, joined with every member's stream before and after as cvh_init_checkerboard_batch; changed is an array of n or NULL.
+ * cvh_reinit is the same kernels with n = 1.  One host wait per call (which members changed).
+ * How: a separable exact distance transform (chan_vese_amd/csrc/reinit_kernels.hip) -- a column pass in bands of 32 rows with a
+ * fix-up across bands gives the vertical distances to both classes, a row pass minimises k^2 + g(j +- k)^2 outwards from LDS-held
+ * rows and stops at k^2 >= best.  Its cost depends on the distances: per pixel the row pass makes at most min(vertical distance,
+ * columns to the farther edge) trips.  Steady-state figures are not measured yet (tools/reinit_probe.py records us per call
+ * beside the us of one CSV iteration of the same plane); host clocks around a context's FIRST call at 4096^2, allocation included:
+ * 9.5 ms for the BASELINE disk's level set (distances in four digits), 1.4 ms for a noisy one -- upper bounds of about 150 and 20
+ * CSV iterations of that plane (profiles/r09_reinit/).  The kernels move 24.25 bytes per pixel (read u 8, class words 0.25, distance
+ * fields 4 + 4, write u' 8) against the floor of 16.
+ * The workspace (4.125 bytes per pixel) is allocated by a context's first reinitialisation and kept; cvh_create allocates nothing
+ * for it and the automatic choices that weigh the contexts of a device do not count it.
+ * CVH_ERR_STATE: a member without a level set.  CVH_ERR_ARG: ctxs NULL, n < 1, a NULL or duplicate member, members on different
+ * devices, a plane with h^2 + w^2 >= 2^32 (d2 is held in 32 bits).  Checked for every member before anything is launched; the message
+ * names the member index and is cvh_last_error(NULL)'s and member 0's. */
+int cvh_reinit(cvh_context *ctx, int *changed);
+int cvh_reinit_batch(cvh_context *const *ctxs, int n, int *changed);
+
 /* Library version string, e.g. "chanvese_hip 0.1 (gfx950)". */
 const char *cvh_version(void);
 
