@@ -220,8 +220,10 @@ __device__ void finalize(const CvhStepArgs &a, int is_init, double *sred, double
       sfin[1] = a.npix - sfin[0];
       for (int k = 0; k < C; ++k) sfin[2 + C + k] = a.sum_img[k] - sfin[2 + k];
     }
+    bool went_nan = false;
     if (!is_init) {
       const double nrm = sqrt(sfin[2 + 2 * C]);
+      went_nan = nrm != nrm;
       const int t = t_pref;  // index of the step just executed
       if (a.trace && t < a.trace_cap) {
         double *row = a.trace + (size_t)t * (2 * C + 1);
@@ -237,6 +239,9 @@ __device__ void finalize(const CvhStepArgs &a, int is_init, double *sred, double
         __hip_atomic_store(&a.host_status[0], t + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
       }
     }
+    // A NaN norm: the update, hence the level set these means belong to, holds a NaN.  The reference's H_eps(NaN) makes every sum
+    // and mean NaN; the FAST H_eps clamps a NaN argument into a finite value, so the sums cannot say it -- the norm does.
+    if (went_nan) sfin[0] = sfin[1] = __builtin_nan("");
     for (int k = 0; k < C; ++k) {
       st->c1[k] = sfin[2 + k] / sfin[0];          // nom / denom, src/main.cpp:280
       st->c2[k] = sfin[2 + C + k] / sfin[1];

@@ -84,6 +84,13 @@
   {
     const long long entry = a.chain->v[a.chain_phase & 3][lane];
     chain_means<C>(a, entry, cm1, cm2);
+    if (t_first > 0) {   // continuing on a level set an earlier iteration left with a NaN (its norm says so): NaN means, as below
+      const double last = a.st->norm;
+      if (last != last) {
+#pragma unroll
+        for (int k = 0; k < C; ++k) cm1[k] = cm2[k] = last;
+      }
+    }
   }
   __syncthreads();
 
@@ -619,7 +626,9 @@
             const double nrm = sqrt(s4);
             const int stop_now = nrm <= a.stop_cond;          // :1000, after the update
             // chain_means' formula (chain_device.h) on the totals
-            const double sh = __builtin_fma((double)q0, a.chain_inv[0], 0.5 * a.npix);
+            // (a NaN norm: u(it + 1) holds a NaN and its means are NaN, as in finalize(), csv_device.h -- through sum H, the divisor of every mean)
+            const double sh_fin = __builtin_fma((double)q0, a.chain_inv[0], 0.5 * a.npix);
+            const double sh = nrm != nrm ? nrm : sh_fin;
             const double sih = __builtin_fma((double)q1, a.chain_inv[1], 0.5 * a.sum_img[0]);
             // (both quotients through one division sequence in lanes 0 / 1 was tried: norm + means 0.28 -> 0.50 us -- the two sequences overlap as they are)
             const double n1 = sih / sh, n2 = (a.sum_img[0] - sih) / (a.npix - sh);

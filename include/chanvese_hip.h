@@ -218,10 +218,18 @@ int cvh_enqueue_steps_batch(cvh_context *const *ctxs, int n, int nsteps);
 int cvh_run_batch(cvh_context *const *ctxs, int n, int max_steps, int *steps_done, double *last_norm);
 
 /* Region means of the current level set (what the next iteration will use),
- * region_variance src/main.cpp:255-281; c1/c2 have `channels` entries. */
+ * region_variance src/main.cpp:255-281; c1/c2 have `channels` entries.
+ * A region that holds no pixel still has a mean: the H_eps-weighted mean of the far tails eps/(pi |u|) of all pixels.
+ * While every region holds a pixel (any |u|/eps up to 1e12, tests/test_gpu_lopsided.py) c1/c2 agree with the reference
+ * to 1e-9.  With NO pixel on one side the reference itself defines that side's mean only to 2e-11 at |u|/eps = 1e7,
+ * 1.5e-9 at 1e9 and 2.4e-6 at 1e12 (cancellation in 1 + 2/pi atan); the flavours with centred sums (FAST wave kernels,
+ * resident, FP32 state, fused batch) are then within 6e-9, 4e-7 and 5e-4 of the accurate value;
+ * the other side's mean, the level set and the norm keep their 1e-9.  From |u|/eps ~ 1e16 the empty side's mean is 0/0:
+ * NaN here as in the reference, and from the iteration that used it on the level set, the norm and both means are NaN. */
 int cvh_get_means(cvh_context *ctx, double *c1, double *c2);
 /* Per-iteration trace rows [c1_0..c1_{C-1}, c2_0..c2_{C-1}, norm] recorded when the
- * "trace" option is on; *rows receives the number of valid rows copied (<= max_rows). */
+ * "trace" option is on; *rows receives the number of valid rows copied (<= max_rows).
+ * c1/c2 of a row are the means the iteration used: see cvh_get_means for empty regions and NaN. */
 int cvh_get_trace(cvh_context *ctx, double *out, int max_rows, int *rows);
 /* tol * || (sum_k I_k)/C ||_2, src/main.cpp:950-959 (valid after set_image). */
 int cvh_get_stop_condition(cvh_context *ctx, double *stop_cond);

@@ -72,10 +72,11 @@ def bar_for(st, s):
     return 1e-6 if (st in E.PLATEAU and s == 10) else 1e-9
 
 
-def check(oracle, what, planes, u0, pk, s, got, float_state=False):
-    u_g, done_g, tr_g, m_g = got
+def oracle_run(oracle, planes, u0, pk, s, float_state=False):
+    """(u, steps_done, trace) of the oracle after at most s iterations; float_state: with its level set rounded to float after every
+    iteration (tests/test_gpu_state32.py)."""
     p = oracle.make_params(**pk)
-    if float_state:   # the oracle with its level set rounded to float after every iteration (tests/test_gpu_state32.py)
+    if float_state:
         f32 = lambda a: a.astype(np.float32).astype(np.float64)
         u_c, done_c, tr_c = f32(u0), 0, []
         for _ in range(s):
@@ -88,6 +89,12 @@ def check(oracle, what, planes, u0, pk, s, got, float_state=False):
         tr_c = np.array(tr_c)
     else:
         u_c, done_c, _, tr_c = oracle.csv_run(planes, u0, p, s)
+    return u_c, done_c, tr_c
+
+
+def check(oracle, what, planes, u0, pk, s, got, float_state=False):
+    u_g, done_g, tr_g, m_g = got
+    u_c, done_c, tr_c = oracle_run(oracle, planes, u0, pk, s, float_state)
     assert done_g == done_c, (what, done_g, done_c)
     scale = np.abs(u_c).max()
     err = float(np.abs(u_g - u_c).max() / scale)
