@@ -321,6 +321,9 @@ extern "C" int cvh_set_option(cvh_context *c, const char *key, long value)
     c->wave_imgv = value != 0;
   } else if (!strcmp(key, "wave_sync")) {
     c->wave_sync = value < 0 ? -1 : (value != 0);
+  } else if (!strcmp(key, "wave_seam")) {
+    if (value != 0 && value != 1) return fail(c, CVH_ERR_ARG, "wave_seam must be 0 or 1");
+    c->wave_seam = (int)value;
   } else if (!strcmp(key, "near_switch")) {
     c->near_switch = value != 0;
   } else if (!strcmp(key, "res_prio")) {
@@ -807,8 +810,9 @@ extern "C" int cvh_launch_info(cvh_context *c, int phase, char *buf, int cap)
   CvhStepArgs a;
   fill_args(c, &a, current_buffer(c), c->enqueued);
   snprintf(buf, (size_t)cap, "kernel=%s grid=%u block=%u lds_bytes=%u data_flow=%d wave_columns=%d strips=%d strip_rows=%d chain=%d "
-           "wave_pol=%d math=%s steps_per_graph=%d", note.name, note.grid, note.block, note.lds, g.strip, g.tiles_x, g.tiles_y,
-           g.strip_rows, a.chain ? 1 : 0, a.wave_pol, use_fast(c) ? "fast" : "strict", c->use_graph ? kGraphSteps : 0);
+           "wave_pol=%d math=%s steps_per_graph=%d wave_seam=%d", note.name, note.grid, note.block, note.lds, g.strip, g.tiles_x, g.tiles_y,
+           g.strip_rows, a.chain ? 1 : 0, a.wave_pol, use_fast(c) ? "fast" : "strict", c->use_graph ? kGraphSteps : 0,
+           (g.strip == 3 && use_fast(c)) ? a.wave_seam : 0);
   return CVH_OK;
 }
 

@@ -194,6 +194,7 @@ void fill_args(const cvh_context *c, CvhStepArgs *a, int in_buf, int step)
   // with three channels the barrier costs more than the locality returns (4096^2 x 3, one context: 73.0-74.4 -> 71.9-73.2 us)
   a->wave_sync = c->wave_sync >= 0 ? c->wave_sync : (c->C == 3 ? 0 : 1);
   a->near_switch = c->near_switch;
+  a->wave_seam = c->wave_seam;
   a->res_prio = c->res_prio;
   a->res_go_shift = c->res_go_share;
   a->wave_depth = c->wave_depth;

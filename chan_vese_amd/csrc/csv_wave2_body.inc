@@ -382,9 +382,15 @@
 
     int prio = 3;
     if (a.wave_prio) __builtin_amdgcn_s_setprio(3);
+    // "wave_seam": the FINAL group of a strip has nothing behind it, so it requests no rows, east extra or image pieces and parks nothing.  (Without
+    // it the final group fetches those of a group that does not exist, every one clamped to the strip's last row, parks them, and the wave's last wait
+    // and the workgroup's closing barriers wait for that.)  Its rows need the ring as the previous park left it, nothing more.  The choice is
+    // wave-uniform and taken inside the edge form: a third compile-time form of group() puts 32-104 bytes of scratch into every FAST instantiation (hipcc, 163-168 of 168 registers in use).
+    const bool skip_dead_prefetch = FAST && a.wave_seam != 0;
     auto group = [&](int ib, auto interior_tag, auto near_tag) {
       constexpr bool INTERIOR = decltype(interior_tag)::value;
       constexpr bool NEARFORM = decltype(near_tag)::value;
+      const bool last = !INTERIOR && skip_dead_prefetch && ib + R >= s1;
       if (a.wave_sync) { __builtin_amdgcn_s_barrier(); ++groups_done; }
       if (a.wave_prio) {
         // At equal priority the SIMD arbiter serves its OLDEST wave first: the 4 waves of a SIMD then run almost
@@ -406,14 +412,17 @@
         }
       }
       raw2_t T[R];
-#pragma unroll
-      for (int j = 0; j < R; ++j) T[j] = INTERIOR ? IO::load2(ru, voff_u, (unsigned)(ib + R + 1 + j) * rowbytes) : U(ib + R + 1 + j);
-      const raw1_t X = INTERIOR ? IO::load1(ru, voff_x, (unsigned)(ib + R + 1) * rowbytes) : UX(ib + R + 1);
+      raw1_t X;
       u32x4_t IQ[NIQ];
-      if (C == 1) IQ[0] = INTERIOR ? buf_load_b128(ri, voff_i, (unsigned)(ib + R) * (unsigned)w) : IMQ(ib + R);
-      else {
+      if (!last) {
 #pragma unroll
-        for (int j = 0; j < NIQ; ++j) IQ[j] = INTERIOR ? buf_load_b128(ri, q_voff[j], (unsigned)(ib + R) * (unsigned)w) : IMQ3(ib + R, j);
+        for (int j = 0; j < R; ++j) T[j] = INTERIOR ? IO::load2(ru, voff_u, (unsigned)(ib + R + 1 + j) * rowbytes) : U(ib + R + 1 + j);
+        X = INTERIOR ? IO::load1(ru, voff_x, (unsigned)(ib + R + 1) * rowbytes) : UX(ib + R + 1);
+        if (C == 1) IQ[0] = INTERIOR ? buf_load_b128(ri, voff_i, (unsigned)(ib + R) * (unsigned)w) : IMQ(ib + R);
+        else {
+#pragma unroll
+          for (int j = 0; j < NIQ; ++j) IQ[j] = INTERIOR ? buf_load_b128(ri, q_voff[j], (unsigned)(ib + R) * (unsigned)w) : IMQ3(ib + R, j);
+        }
       }
 #pragma unroll
       for (int k = 0; k < R; ++k) {
@@ -464,7 +473,7 @@
             for (int ch = 0; ch < C; ++ch) smp3[ch][k] = samples(ch, k);
           }
         }
-        park(T, X, IQ);
+        if (!last) park(T, X, IQ);
 #pragma unroll
         for (int k = 0; k < R; ++k)
           if (INTERIOR || (ib + k) < s1) finish_row(k, smp1[k], std::true_type{});
@@ -473,7 +482,7 @@
       } else {
 #pragma unroll
         for (int k = 0; k < R; ++k) asm volatile("; row %2 of the group: store data still live" :: "v"(keep[k].x), "v"(keep[k].y), "n"(0));
-        park(T, X, IQ);
+        if (!last) park(T, X, IQ);
       }
     };
     const unsigned long long t_first = a.dbg_times ? __builtin_amdgcn_s_memrealtime() : 0ull;   // prologue done

@@ -54,6 +54,7 @@ hipError_t launch_wave2(const CvhStepArgs &a, hipStream_t s, const CvhBatchLaunc
 {
   using L = Wave2Smem<FAST, C>;
   static_assert(L::bytes <= 64 * 1024, "dynamic LDS above 64 KiB would need hipFuncSetAttribute");
+  static_assert(MINW * L::bytes <= 160 * 1024, "the kernel is compiled for MINW workgroups per CU: their LDS must fit the CU's 160 KiB");
   const int extra = (FAST && a.chain) ? 1 : 0;   // the bookkeeping workgroup
   CVH_LAUNCH_B((csv_wave2_kernel<C, FAST, MINW, POL, ST32>), (csv_wave2_batch_kernel<C, FAST, MINW, POL, ST32>), a.nparts + extra, L::bytes, s, a, batch,
                "csv_wave2_kernel<%d, %s, %d, %d, %s>", C, CVH_TF(FAST), MINW, POL, CVH_TF(ST32));

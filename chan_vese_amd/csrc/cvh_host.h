@@ -102,6 +102,7 @@ struct cvh_context {   // opaque to callers; four groups
   int wave_minw = 5, wave_lds_cap = 0, wave_prio = 1, wave_sync = -1 /* auto: 1 channel 1, 3 channels 0 */, wave_imgv = 1, wave_depth = 4;
   int res_prio = 1;     // option "res_prio": resident kernels, priority by quarters of a wave's band (csv_resident_kernel.hip)
   int res_go_share = 5;  // option "res_go_share": log2 of the tiles of an XCD that share one release line of the resident kernel (0: a line per tile, 5: a line per XCD, 6: one line)
+  int wave_seam = 1;    // option "wave_seam": a strip's final group runs without prefetch and park in the 2-pixel kernel (csv_wave2_body.inc); 0 = with both
   int near_switch = 1;  // option "near_switch": per-wave, per-group choice of the form of H_eps (csv_wave2_kernel.hip); 0 = far form + correction always
   int wave_rev = 0, wave_xcd = 1;
   int use_graph = 1;

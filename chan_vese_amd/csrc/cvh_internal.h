@@ -17,6 +17,7 @@
 //   "wave_imgv" 16-byte image pieces (1), "wave_xcd" XCD-contiguous workgroup numbering (1),
 //   "wave_skew" per-mille strip-length skew of the 1-pixel kernel (0), "wave_cls" class-major workgroup numbering (0 off,
 //   1 = 2-pixel kernel (default), 2 = 1-pixel kernel too), "wave_cskew" per-mille strip-length skew between dispatch rounds (500),
+//   "wave_seam" 2-pixel kernel: a strip's final group without prefetch and park (1; 0 = with both: the same bits),
 //   "wave_pol" = 2 (diagnostic value of the public option: plain stores with non-temporal loads),
 //   "chain" fixed-point chained sums + deferred bookkeeping in the wave kernels (1), "far_terms" terms of the far-field series (5; 4), "wave_lds_cap", "wave_rev", "debug_times" (per-wave stamps
 //   read with cvh_debug_read, tools/wave_timeline.py), "res_straight" (1; 0 = csv_resident_kernel's generic march whatever the tile height).
@@ -129,6 +130,8 @@ struct CvhStepArgs {
   int wave_pol;                  // 2-pixel wave kernel: cache policy of the level-set rows (wave2_device.h): 1 write-through stores, 0 plain
   int wave_cls;                  // 2-pixel wave kernel: workgroups per XCD per dispatch round (= CUs per XCD); > 0 numbers the
                                  // workgroups class-major (round 0 of every XCD first), 0 = plain XCD-contiguous numbering
+  int wave_seam;                 // 2-pixel wave kernel, FAST: a strip's final group neither prefetches nor parks (csv_wave2_body.inc); 0 = it does,
+                                 // as every other group
   CvhLaunchNote *note;           // host only: non-null = describe the launch instead of issuing it (CVH_LAUNCH)
   // resident kernel (csv_resident_kernel.hip): tiles_x x tiles_y tiles, one workgroup each
   CvhResident *resident;         // synchronisation words

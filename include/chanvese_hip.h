@@ -131,6 +131,10 @@ int cvh_set_params(cvh_context *ctx, const cvh_params *p);
  *   "near_switch"    1 (default): a wave whose strip / band starts where most pixels are below the far-field threshold of H_eps (32 eps)
  *                    evaluates the table form of H_eps on every pixel of that strip (one form per pixel: a level set that is near
  *                    everywhere, e.g. dt << 1); 0: the far-field series with the per-group correction everywhere
+ *   "wave_seam"      2-pixel wave kernel, FAST arithmetic: 1 (default): the final group of a strip requests and parks no rows, east
+ *                    extra or image pieces of a group that does not exist; 0: it does, like every other group.  The results are the
+ *                    same bit for bit (tests/test_gpu_wave2_seam.py); the key exists for that comparison.  (The name is the seam of a
+ *                    workgroup's two strips: handing its rows over in LDS is the part that does not ship)
  *   "tile_rows"      tile kernel: rows per tile (0 auto, 14/16)
  *   "strip_rows"     wave kernels: rows per strip (0 auto)
  *   "lut"            1 = region term from a per-launch 256-entry table (FAST, default; tile and 1-pixel wave kernels: 0 = computed)
@@ -290,7 +294,7 @@ int cvh_last_pm_ms(cvh_context *ctx, float *ms);
  * the reference: the kernel is an implementation detail; bench.py names it in its roofline object and profiles/ are
  * matched against it).  phase 0: the CSV step as the next cvh_run / cvh_enqueue_steps launches it with the current
  * options -- kernel=<instantiation as rocprofv3 prints it> grid= block= lds_bytes= strips= strip_rows= chain= wave_pol=
- * math= steps_per_graph=; phase 1: what the last cvh_perona_malik launched (CVH_ERR_STATE before the first).
+ * math= steps_per_graph= wave_seam=; phase 1: what the last cvh_perona_malik launched (CVH_ERR_STATE before the first).
  * Launches nothing.  Truncates to cap - 1 characters. */
 int cvh_launch_info(cvh_context *ctx, int phase, char *buf, int cap);
 
