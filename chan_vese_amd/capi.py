@@ -30,7 +30,10 @@ EXPORTS = [
     "cvh_set_image_device", "cvh_get_image_device", "cvh_set_levelset_device", "cvh_get_levelset_device",
     "cvh_get_mask_device", "cvh_set_image_device_batch", "cvh_init_checkerboard_batch", "cvh_get_mask_device_batch",
     "cvh_reinit", "cvh_reinit_batch",
+    "cvh_components", "cvh_components_batch", "cvh_get_mask_clean", "cvh_get_mask_clean_device", "cvh_get_mask_clean_device_batch",
 ]
+# struct cvh_component: row k - 1 of a component table describes label k (first = smallest flat index; the box is inclusive)
+COMPONENT_DTYPE = np.dtype([("first", np.uint32), ("area", np.uint32), ("x0", np.int32), ("y0", np.int32), ("x1", np.int32), ("y1", np.int32)])
 LAYOUT_PLANAR, LAYOUT_INTERLEAVED = 0, 1
 
 
@@ -108,6 +111,11 @@ def lib():
         "cvh_get_mask_device_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.POINTER(vp), C.c_int, vp]),
         "cvh_reinit": (C.c_int, [vp, ip]),
         "cvh_reinit_batch": (C.c_int, [C.POINTER(vp), C.c_int, ip]),
+        "cvh_components": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.c_int, ip, vp]),
+        "cvh_components_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.POINTER(vp), ip, vp]),
+        "cvh_get_mask_clean": (C.c_int, [vp, u8p, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int]),
+        "cvh_get_mask_clean_device": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, vp]),
+        "cvh_get_mask_clean_device_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.POINTER(vp), C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -246,6 +254,26 @@ def reinit_batch(contexts):
     changed = (C.c_int * max(n, 1))()
     _batch_chk(lib().cvh_reinit_batch(_member_array(contexts), n, changed))
     return [bool(changed[i]) for i in range(n)]
+
+
+def components_batch(contexts, ptrs=None, conn=4, invert=False, stream=0):
+    """cvh_components_batch: the connected components of every context's mask with one set of launches.  ptrs: one integer device
+    address of h * w int32 labels per context (0 = no label plane for that member), or None.  Returns [K] per context."""
+    contexts = list(contexts)
+    n = len(contexts)
+    counts = (C.c_int * max(n, 1))()
+    addr = None if ptrs is None else _address_array(list(ptrs), n)
+    _batch_chk(lib().cvh_components_batch(_member_array(contexts), n, int(conn), int(bool(invert)), addr, counts, int(stream) or None))
+    return [counts[i] for i in range(n)]
+
+
+def get_mask_clean_device_batch(contexts, ptrs, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False, stream=0):
+    """cvh_get_mask_clean_device_batch: every context's cleaned mask (Context.get_mask_clean) into device memory, one set of launches
+    for all; work enqueued on `stream` afterwards sees the masks.  Does not block the host."""
+    contexts = list(contexts)
+    n = len(contexts)
+    _batch_chk(lib().cvh_get_mask_clean_device_batch(_member_array(contexts), n, _address_array(list(ptrs), n), int(conn), int(bool(invert)),
+                                                     int(min_area), int(fill_holes), int(keep_largest), int(stream) or None))
 
 
 def _segmented(contexts, max_steps, every, run):
@@ -420,6 +448,35 @@ class Context:
         m = np.empty((self.h, self.w), dtype=np.uint8)
         self._chk(self._L.cvh_get_mask(self._h, _u8p(m), int(bool(invert))))
         return m
+
+    def components(self, conn=4, invert=False, labels_ptr=0, stream=0, cap=None):
+        """cvh_components: label the connected components of the mask on the device.  labels_ptr: integer device address of h * w int32
+        (0 = no label plane).  Returns (K, table): table is a structured array (COMPONENT_DTYPE) of the first min(K, cap) rows;
+        cap = None asks for all K rows and COSTS TWO LABELLINGS (one call for K and the labels, a second one with cap = K for the rows: the
+        host table must exist before the call that fills it); pass a cap where an upper bound of K is known, cap = 0 for no table."""
+        count = C.c_int(0)
+        args = (int(conn), int(bool(invert)))
+        if cap is None:
+            self._chk(self._L.cvh_components(self._h, *args, int(labels_ptr) or None, None, 0, C.byref(count), int(stream) or None))
+            table = np.zeros(count.value, dtype=COMPONENT_DTYPE)
+            if count.value:
+                self._chk(self._L.cvh_components(self._h, *args, None, table.ctypes.data, count.value, C.byref(count), None))
+            return count.value, table
+        table = np.zeros(max(int(cap), 0), dtype=COMPONENT_DTYPE)
+        self._chk(self._L.cvh_components(self._h, *args, int(labels_ptr) or None, table.ctypes.data if table.size else None, int(cap),
+                                         C.byref(count), int(stream) or None))
+        return count.value, table[:min(count.value, table.size)].copy()
+
+    def get_mask_clean(self, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False):
+        """cvh_get_mask_clean: the mask without foreground components below min_area, with the holes of area <= fill_holes filled
+        (-1: any size) and, with keep_largest, only its largest component; (0, 0, False) is get_mask."""
+        m = np.empty((self.h, self.w), dtype=np.uint8)
+        self._chk(self._L.cvh_get_mask_clean(self._h, _u8p(m), int(conn), int(bool(invert)), int(min_area), int(fill_holes), int(keep_largest)))
+        return m
+
+    def get_mask_clean_device(self, ptr, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False, stream=0):
+        self._chk(self._L.cvh_get_mask_clean_device(self._h, int(ptr) or None, int(conn), int(bool(invert)), int(min_area), int(fill_holes),
+                                                    int(keep_largest), int(stream) or None))
 
     def get_contour(self):
         m = np.empty((self.h, self.w), dtype=np.uint8)

@@ -136,6 +136,8 @@ extern "C" void cvh_destroy(cvh_context *c)
   free_table(&c->io_table);
   if (c->h_io) (void)hipHostFree(c->h_io);
   if (c->d_reinit) (void)hipFree(c->d_reinit);
+  if (c->d_cc) (void)hipFree(c->d_cc);
+  if (c->d_cc_table) (void)hipFree(c->d_cc_table);
   if (c->ev_io_in) (void)hipEventDestroy(c->ev_io_in);
   if (c->ev_io_out) (void)hipEventDestroy(c->ev_io_out);
   if (c->h_resident) (void)hipHostFree(c->h_resident);

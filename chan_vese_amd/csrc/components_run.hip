@@ -1,0 +1,212 @@
+// components_run.hip — host side of cvh_components* and cvh_get_mask_clean* (include/chanvese_hip.h, "Connected components"): read-only
+// operations on the level sets of n contexts, on io_run.hip's member tables, stream joins and event ordering.  The single-context calls
+// are batches of one member.  Nothing here touches a context's level set, run state, sums or options.
+#include "cvh_host.h"
+
+namespace {
+
+inline size_t align_up(size_t v, size_t a) { return (v + a - 1) & ~(a - 1); }
+
+int conn_check(cvh_context *const *ctxs, int n, int conn, const char *what)
+{
+  if (conn != 4 && conn != 8) return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: conn must be 4 or 8, got %d", what, conn);
+  return CVH_OK;
+}
+
+// every member has a level set and a plane the 31-bit indices cover; iterations in flight are settled, the double mirror and the
+// workspace exist
+int members_ready(cvh_context *const *ctxs, int n, const char *what)
+{
+  for (int i = 0; i < n; ++i) {
+    const cvh_context *c = ctxs[i];
+    if (c->n >= ((size_t)1 << 31)) return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: member %d: %d x %d is too large, h * w must stay below 2^31", what, i, c->h, c->w);
+  }
+  for (int i = 0; i < n; ++i)
+    if (!ctxs[i]->have_u) return batch_fail(ctxs, n, CVH_ERR_STATE, "%s: member %d has no level set", what, i);
+  cvh_context *lead = ctxs[0];
+  HIPCHK(lead, hipSetDevice(lead->device));
+  int rc = settle_all(ctxs, n, what);
+  if (rc != CVH_OK) return rc;
+  for (int i = 0; i < n; ++i) {
+    cvh_context *c = ctxs[i];
+    rc = ensure_f64_mirror(c);   // "state" = 32: the class of a float is the class of its double
+    if (rc == CVH_OK && !c->d_cc) {   // the workspace: allocated on the first call, kept with the context
+      const hipError_t e = hipMalloc(&c->d_cc, cvh_cc_workspace_bytes(c->n));
+      if (e != hipSuccess) { c->d_cc = nullptr; rc = fail(c, CVH_ERR_HIP, "hipMalloc of the components workspace: %s", hipGetErrorString(e)); }
+    }
+    if (rc != CVH_OK) return batch_fail(ctxs, n, rc, "%s: member %d: %s", what, i, c->err);
+  }
+  return CVH_OK;
+}
+
+// staging: [member table][one word per member, zero]; *words_off is where the words start.  dst[i] is member i's output (may be null)
+int fill_members(cvh_context *const *ctxs, int n, void *const *dst, size_t *words_off, unsigned *grid)
+{
+  cvh_context *lead = ctxs[0];
+  const size_t off = align_up((size_t)n * sizeof(CvhIoMember), 256), bytes = off + (size_t)n * sizeof(unsigned long long);
+  const int rc = stage(lead, bytes, bytes);
+  if (rc != CVH_OK) return rc;
+  unsigned char *const hb = (unsigned char *)lead->h_io, *const db = (unsigned char *)lead->io_table.d;
+  memset(hb, 0, bytes);
+  CvhIoMember *tab = (CvhIoMember *)hb;
+  for (int i = 0; i < n; ++i) {
+    const cvh_context *c = ctxs[i];
+    CvhIoMember &m = tab[i];
+    m.src = c->d_u[current_buffer(c)];
+    m.dst = dst ? dst[i] : nullptr;
+    m.plane[0] = (uint8_t *)c->d_cc;
+    m.plane[1] = m.plane[0] + c->n * sizeof(unsigned);
+    m.plane[2] = m.plane[1] + c->n * sizeof(unsigned);
+    m.sums = (unsigned long long *)(db + off) + i;
+    m.n = c->n; m.h = c->h; m.w = c->w; m.C = c->C;
+    m.nblk = cvh_cc_blocks(c->n);
+  }
+  *grid = lay_out(tab, n);
+  *words_off = off;
+  return CVH_OK;
+}
+
+int components(cvh_context *const *ctxs, int n, int conn, int invert, int32_t *const *d_labels, int *counts, cvh_component *table, int cap,
+               void *stream, const char *what)
+{
+  int rc = members_check(ctxs, n, what, kMembersListed);
+  if (rc != CVH_OK) return rc;
+  rc = conn_check(ctxs, n, conn, what);
+  if (rc != CVH_OK) return rc;
+  if (table && cap < 0) return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: cap must not be negative, got %d", what, cap);
+  cvh_context *lead = ctxs[0];
+  HIPCHK(lead, hipSetDevice(lead->device));
+  bool any_labels = false;
+  for (int i = 0; d_labels && i < n; ++i) {
+    if (!d_labels[i]) continue;   // (no label plane for this member)
+    rc = pointer_check(ctxs, n, i, d_labels[i], what);
+    if (rc != CVH_OK) return rc;
+    if ((uintptr_t)d_labels[i] % sizeof(int32_t))
+      return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: member %d: %p is not aligned to 4 bytes", what, i, (const void *)d_labels[i]);
+    any_labels = true;
+  }
+  rc = members_ready(ctxs, n, what);
+  if (rc != CVH_OK) return rc;
+  size_t words_off = 0;
+  unsigned grid = 0;
+  rc = fill_members(ctxs, n, (void *const *)d_labels, &words_off, &grid);
+  if (rc != CVH_OK) return rc;
+  unsigned char *const hb = (unsigned char *)lead->h_io, *const db = (unsigned char *)lead->io_table.d;
+  const size_t bytes = words_off + (size_t)n * sizeof(unsigned long long);
+  rc = open_call(ctxs, n, stream);
+  if (rc != CVH_OK) return rc;
+  HIPCHK(lead, hipMemcpyAsync(db, hb, bytes, hipMemcpyHostToDevice, lead->stream));
+  HIPCHK(lead, cvh_launch_cc_label((const CvhIoMember *)db, n, grid, conn, invert, any_labels, lead->stream));
+  HIPCHK(lead, hipMemcpyAsync(hb + words_off, db + words_off, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost, lead->stream));
+  rc = close_call(ctxs, n, stream, any_labels);
+  if (rc != CVH_OK) return rc;
+  HIPCHK(lead, hipStreamSynchronize(lead->stream));   // the host wait of the call: the counts
+  const unsigned long long *words = (const unsigned long long *)(hb + words_off);
+  for (int i = 0; counts && i < n; ++i) counts[i] = (int)words[i];
+  const size_t K = (size_t)words[0];
+  const size_t rows = std::min<size_t>(K, table ? (size_t)cap : 0);
+  if (!rows) return CVH_OK;
+  // the table (single-context form): K is known now, so the rows have their place; two more launches on the workspace, then the SECOND wait
+  if (lead->cc_table_rows < K) {
+    if (lead->d_cc_table) { HIPCHK(lead, hipFree(lead->d_cc_table)); lead->d_cc_table = nullptr; lead->cc_table_rows = 0; }
+    const size_t want = K + K / 4;
+    HIPCHK(lead, hipMalloc(&lead->d_cc_table, want * sizeof(cvh_component)));
+    lead->cc_table_rows = want;
+  }
+  CvhIoMember *tab = (CvhIoMember *)hb;
+  tab[0].dst = lead->d_cc_table;   // (the label plane is written: these launches fill the rows)
+  HIPCHK(lead, hipMemcpyAsync(db, hb, sizeof(CvhIoMember), hipMemcpyHostToDevice, lead->stream));
+  HIPCHK(lead, cvh_launch_cc_table((const CvhIoMember *)db, 1, grid, lead->stream));
+  HIPCHK(lead, hipMemcpyAsync(table, lead->d_cc_table, rows * sizeof(cvh_component), hipMemcpyDeviceToHost, lead->stream));
+  HIPCHK(lead, hipEventRecord(lead->ev_io_out, lead->stream));   // (the last read of the pinned block)
+  HIPCHK(lead, hipStreamSynchronize(lead->stream));
+  return CVH_OK;
+}
+
+int clean_args(cvh_context *const *ctxs, int n, int conn, long min_area, long fill_holes, int keep_largest, const char *what)
+{
+  int rc = members_check(ctxs, n, what, kMembersListed);
+  if (rc != CVH_OK) return rc;
+  rc = conn_check(ctxs, n, conn, what);
+  if (rc != CVH_OK) return rc;
+  if (min_area < 0) return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: min_area must not be negative, got %ld", what, min_area);
+  if (fill_holes < -1) return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: fill_holes must be -1 (any size) or an area >= 0, got %ld", what, fill_holes);
+  if (keep_largest != 0 && keep_largest != 1) return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: keep_largest must be 0 or 1, got %d", what, keep_largest);
+  return CVH_OK;
+}
+
+int clean(cvh_context *const *ctxs, int n, uint8_t *const *d_masks, int conn, int invert, long min_area, long fill_holes, int keep_largest,
+          void *stream, const char *what)
+{
+  int rc = clean_args(ctxs, n, conn, min_area, fill_holes, keep_largest, what);
+  if (rc != CVH_OK) return rc;
+  const bool drop = min_area > 1;   // (every component has a pixel)
+  if (!drop && !fill_holes && !keep_largest) return mask_out(ctxs, n, d_masks, invert, stream, what);   // the existing mask kernel alone
+  if (!d_masks) return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: the list of device pointers is NULL", what);
+  cvh_context *lead = ctxs[0];
+  HIPCHK(lead, hipSetDevice(lead->device));
+  for (int i = 0; i < n; ++i) { rc = pointer_check(ctxs, n, i, d_masks[i], what); if (rc != CVH_OK) return rc; }
+  rc = members_ready(ctxs, n, what);
+  if (rc != CVH_OK) return rc;
+  size_t words_off = 0;
+  unsigned grid = 0;
+  rc = fill_members(ctxs, n, (void *const *)d_masks, &words_off, &grid);
+  if (rc != CVH_OK) return rc;
+  unsigned char *const hb = (unsigned char *)lead->h_io, *const db = (unsigned char *)lead->io_table.d;
+  rc = open_call(ctxs, n, stream);
+  if (rc != CVH_OK) return rc;
+  HIPCHK(lead, hipMemcpyAsync(db, hb, words_off + (size_t)n * sizeof(unsigned long long), hipMemcpyHostToDevice, lead->stream));
+  if (!drop) HIPCHK(lead, cvh_launch_io_mask((const CvhIoMember *)db, n, grid, invert, lead->stream));   // step 1 is off: the plain mask
+  const unsigned a = (unsigned)std::min<long>(min_area, 0x7fffffffl);
+  HIPCHK(lead, cvh_launch_cc_clean((const CvhIoMember *)db, n, grid, conn, invert, a, fill_holes, keep_largest, lead->stream));
+  return close_call(ctxs, n, stream, true);
+}
+
+}  // namespace
+
+extern "C" int cvh_components_batch(cvh_context *const *ctxs, int n, int conn, int invert, int32_t *const *d_labels, int *counts, void *stream)
+{
+  static const char what[] = "cvh_components_batch";
+  return guarded(ctxs, n, what, [&]() { return components(ctxs, n, conn, invert, d_labels, counts, nullptr, 0, stream, what); });
+}
+
+extern "C" int cvh_components(cvh_context *c, int conn, int invert, int32_t *d_labels, cvh_component *table, int cap, int *count, void *stream)
+{
+  if (!c) return CVH_ERR_ARG;
+  static const char what[] = "cvh_components";
+  return guarded(&c, 1, what, [&]() { return components(&c, 1, conn, invert, &d_labels, count, table, cap, stream, what); });
+}
+
+extern "C" int cvh_get_mask_clean_device_batch(cvh_context *const *ctxs, int n, uint8_t *const *d_masks, int conn, int invert, long min_area,
+                                               long fill_holes, int keep_largest, void *stream)
+{
+  static const char what[] = "cvh_get_mask_clean_device_batch";
+  return guarded(ctxs, n, what, [&]() { return clean(ctxs, n, d_masks, conn, invert, min_area, fill_holes, keep_largest, stream, what); });
+}
+
+extern "C" int cvh_get_mask_clean_device(cvh_context *c, uint8_t *d_mask, int conn, int invert, long min_area, long fill_holes, int keep_largest,
+                                         void *stream)
+{
+  if (!c) return CVH_ERR_ARG;
+  static const char what[] = "cvh_get_mask_clean_device";
+  return guarded(&c, 1, what, [&]() { return clean(&c, 1, &d_mask, conn, invert, min_area, fill_holes, keep_largest, stream, what); });
+}
+
+extern "C" int cvh_get_mask_clean(cvh_context *c, uint8_t *mask, int conn, int invert, long min_area, long fill_holes, int keep_largest)
+{
+  if (!c) return CVH_ERR_ARG;
+  static const char what[] = "cvh_get_mask_clean";
+  if (!mask) return fail(c, CVH_ERR_ARG, "%s: mask is NULL", what);
+  return guarded(&c, 1, what, [&]() {
+    int rc = clean_args(&c, 1, conn, min_area, fill_holes, keep_largest, what);
+    if (rc != CVH_OK) return rc;
+    if (!c->have_u) return fail(c, CVH_ERR_STATE, "%s: no level set", what);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->d_mask) HIPCHK(c, hipMalloc((void **)&c->d_mask, c->n));   // cvh_get_mask's device buffer
+    rc = clean(&c, 1, &c->d_mask, conn, invert, min_area, fill_holes, keep_largest, c->stream, what);
+    if (rc != CVH_OK) return rc;
+    HIPCHK(c, hipMemcpyAsync(mask, c->d_mask, c->n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return (int)CVH_OK;
+  });
+}

@@ -136,6 +136,9 @@ struct cvh_context {   // opaque to callers; four groups
   hipEvent_t ev_io_in = nullptr, ev_io_out = nullptr;   // ev_io_out also marks the last read of h_io by a copy still in flight
   void *d_reinit = nullptr;      // workspace of cvh_reinit (class words + the two distance fields, reinit_kernels.hip): allocated by the
                                  // first call, idle while CSV streams -- not part of live_footprint
+  void *d_cc = nullptr;          // workspace of cvh_components* / cvh_get_mask_clean* (components_kernels.hip), and the rows of the last
+  void *d_cc_table = nullptr;    // table: allocated by the first call that needs them, kept -- not part of live_footprint either
+  size_t cc_table_rows = 0;
   int coop_launch = -1;          // does the device launch cooperatively (-1: not asked yet; launches_cooperatively)
   int resident_cap = -1;         // workgroups of csv_resident_kernel the device holds at once (-1: not asked yet, 0: unavailable)
   int pm_resident_cap = -1;      // workgroups of pm_resident_kernel the device holds at once (-1: not asked yet)
@@ -223,6 +226,23 @@ void free_table(DeviceTable *t);
 
 // io_run.hip: launch sets (three kernels for all members) of cvh_reinit / cvh_reinit_batch so far in this process (debug_exports.hip)
 extern std::atomic<unsigned long> g_reinit_launch_sets;
+
+// io_run.hip: what every call on device memory shares (the comments are at the definitions)
+int pointer_check(cvh_context *const *ctxs, int n, int i, const void *p, const char *what);
+int settle_all(cvh_context *const *ctxs, int n, const char *what);
+int stage(cvh_context *lead, size_t host_bytes, size_t dev_bytes);
+int open_call(cvh_context *const *ctxs, int n, void *stream);
+int close_call(cvh_context *const *ctxs, int n, void *stream, bool to_caller);
+unsigned lay_out(CvhIoMember *tab, int n);
+int mask_out(cvh_context *const *ctxs, int n, uint8_t *const *d_masks, int invert, void *stream, const char *what);
+
+// nothing is thrown across the C boundary: a failed host allocation inside body() becomes CVH_ERR_NOMEM
+template <class F>
+int guarded(cvh_context *const *ctxs, int n, const char *what, F body)
+{
+  try { return body(); }
+  catch (...) { return batch_fail(ctxs, n, CVH_ERR_NOMEM, "%s: out of host memory", what); }
+}
 
 // What launches(), which returns CVH_OK or an error already recorded with fail(), enqueues on c's stream, captured and instantiated into
 // *out.  A capture that does not end in a graph fails with end_fmt (one %s: the HIP error).

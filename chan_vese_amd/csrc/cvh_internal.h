@@ -238,6 +238,15 @@ size_t cvh_reinit_bits_bytes(int h, int w);          // the class words' share o
 size_t cvh_reinit_workspace_bytes(int h, int w);
 hipError_t cvh_launch_reinit(const CvhIoMember *cols, unsigned col_grid, const CvhIoMember *rows, unsigned row_grid, int nmem, int max_w,
                              hipStream_t s);
+// connected components (components_kernels.hip): a member's section is one lane per pixel; plane[0] the parent words, plane[1] the per-root
+// statistics, plane[2] one count per workgroup (the context's workspace); sums: the member's word (K; keep_largest's bid), zeroed; dst the
+// label plane (may be null), the mask bytes, or the rows of the table
+unsigned cvh_cc_blocks(size_t n);
+size_t cvh_cc_workspace_bytes(size_t n);
+hipError_t cvh_launch_cc_label(const CvhIoMember *tab, int nmem, unsigned grid, int conn, int invert, bool any_labels, hipStream_t s);
+hipError_t cvh_launch_cc_table(const CvhIoMember *tab, int nmem, unsigned grid, hipStream_t s);
+hipError_t cvh_launch_cc_clean(const CvhIoMember *tab, int nmem, unsigned grid, int conn, int invert, unsigned min_area, long fill_holes,
+                               int keep_largest, hipStream_t s);
 // rows-per-tile options of the step kernel
 void cvh_step_grid(int h, int w, int tile_rows, int *tiles_x, int *tiles_y);
 int cvh_step_max_blocks(int h, int w);

@@ -10,13 +10,7 @@ namespace {
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) & ~(a - 1); }
 
-// nothing is thrown across the C boundary: a failed host allocation inside body() becomes CVH_ERR_NOMEM
-template <class F>
-int guarded(cvh_context *const *ctxs, int n, const char *what, F body)
-{
-  try { return body(); }
-  catch (...) { return batch_fail(ctxs, n, CVH_ERR_NOMEM, "%s: out of host memory", what); }
-}
+}  // namespace
 
 // p must be memory that kernels on member i's device can address: device memory of that device, managed memory, or mapped host memory
 int pointer_check(cvh_context *const *ctxs, int n, int i, const void *p, const char *what)
@@ -85,6 +79,8 @@ unsigned lay_out(CvhIoMember *tab, int n)
   for (int i = 0; i < n; ++i) { tab[i].first = first; first += tab[i].nblk; }
   return first;
 }
+
+namespace {
 
 int ingest(cvh_context *const *ctxs, int n, const uint8_t *const *d_imgs, int layout, void *stream, const char *what)
 {
@@ -167,6 +163,8 @@ int ingest(cvh_context *const *ctxs, int n, const uint8_t *const *d_imgs, int la
   return CVH_OK;
 }
 
+}  // namespace
+
 int mask_out(cvh_context *const *ctxs, int n, uint8_t *const *d_masks, int invert, void *stream, const char *what)
 {
   int rc = members_check(ctxs, n, what, kMembersListed);
@@ -202,6 +200,8 @@ int mask_out(cvh_context *const *ctxs, int n, uint8_t *const *d_masks, int inver
   HIPCHK(lead, cvh_launch_io_mask((const CvhIoMember *)lead->io_table.d, n, grid, invert, lead->stream));
   return close_call(ctxs, n, stream, true);
 }
+
+namespace {
 
 // a level set moved in or out: bits is 64 (double) or 32 (float), p aligned to its element
 int levelset_args(cvh_context *c, const void *p, int bits, const char *what)

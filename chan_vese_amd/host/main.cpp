@@ -15,7 +15,7 @@
 // --line-color, one frame for t = 0 and one after every iteration, :926-931,:997); the overlay
 // text of -O is not rendered (no font rasteriser here), --fps has nothing to act on.
 // Additions that do not collide with reference options: --dump-u, --dump-mask, --device, --math,
-// --state, --rect, --circ, --reinit, --verbose.
+// --state, --rect, --circ, --reinit, --connectivity, --min-area, --fill-holes, --largest, --roi, --verbose.
 #include <algorithm>
 #include <cctype>
 #include <cerrno>
@@ -169,6 +169,7 @@ const Spec kSpecs[] = {
     {"invert-selection", 'I', 0}, {"select", 's', 0}, {"rectangle", 'R', 0}, {"circle", 'C', 0},
     // additions of this build
     {"dump-u", 0, 1}, {"dump-mask", 0, 1}, {"device", 0, 1}, {"math", 0, 1}, {"state", 0, 1}, {"rect", 0, 1}, {"circ", 0, 1}, {"reinit", 0, 1},
+    {"connectivity", 0, 1}, {"min-area", 0, 1}, {"fill-holes", 0, 1}, {"largest", 0, 0}, {"roi", 0, 0},
     {"verbose", 0, 0}};
 
 struct Parsed {
@@ -256,6 +257,14 @@ double to_double(const std::string &opt, const std::string &v)
   if (v.empty() || *end != '\0') msg_exit("error: the argument ('" + v + "') for option '--" + opt + "' is invalid");
   return d;
 }
+long to_long(const std::string &opt, const std::string &v)
+{
+  char *end = nullptr;
+  errno = 0;
+  const long d = std::strtol(v.c_str(), &end, 10);
+  if (v.empty() || *end != '\0' || errno == ERANGE) msg_exit("error: the argument ('" + v + "') for option '--" + opt + "' is invalid");
+  return d;
+}
 int to_int(const std::string &opt, const std::string &v)
 {
   char *end = nullptr;
@@ -301,6 +310,12 @@ void print_help()
       "  --math arg (=fast)                 strict | fast (see include/chanvese_hip.h)\n"
       "  --state arg (=64)                  64 | 32: level set kept as double (the reference's CV_64FC1) or, DECLARED, as float in GPU memory\n"
       "  --reinit arg (=0)                  reinitialise the level set to a signed distance every arg iterations (0: never); -N stays the total\n"
+      "  --connectivity arg (=4)            4 | 8: connectivity of the mask's components (the background takes the other one)\n"
+      "  --min-area arg (=0)                drop components of the mask with fewer pixels\n"
+      "  --fill-holes arg (=0)              fill holes of the mask up to arg pixels (-1: of any size)\n"
+      "  --largest                          keep only the largest component of the mask\n"
+      "                                     (with any of these four, _selection and --dump-mask use the cleaned mask)\n"
+      "  --roi                              print 'roi x0 y0 x1 y1 area' of that mask's largest component to stdout\n"
       "  --verbose                          print the iteration count and last norm to stderr\n"
       "\n";
 }
@@ -347,6 +362,13 @@ int main(int argc, char **argv)
   if (auto v = one("state")) state_bits = to_int("state", *v);
   int reinit_every = 0;
   if (auto v = one("reinit")) reinit_every = to_int("reinit", *v);
+  int connectivity = 4;
+  long min_area = 0, fill_holes = 0;
+  if (auto v = one("connectivity")) connectivity = to_int("connectivity", *v);
+  if (auto v = one("min-area")) min_area = to_long("min-area", *v);
+  if (auto v = one("fill-holes")) fill_holes = to_long("fill-holes", *v);
+  const bool largest = vm.count("largest"), roi = vm.count("roi");
+  const bool clean_mask = vm.count("connectivity") || vm.count("min-area") || vm.count("fill-holes") || largest;
   if (auto v = one("rect")) rect = *v;
   if (auto v = one("circ")) circ = *v;
   segment = vm.count("segment"); grayscale = vm.count("grayscale"); write_video = vm.count("video");
@@ -397,6 +419,9 @@ int main(int argc, char **argv)
   if (math != "strict" && math != "fast") msg_exit("error: the argument ('" + math + "') for option '--math' is invalid");
   if (state_bits != 64 && state_bits != 32) msg_exit("error: the argument ('" + std::to_string(state_bits) + "') for option '--state' is invalid");
   if (reinit_every < 0) msg_exit("Reinitialisation interval cannot be negative: " + std::to_string(reinit_every) + ".");
+  if (connectivity != 4 && connectivity != 8) msg_exit("Connectivity must be 4 or 8: " + std::to_string(connectivity) + ".");
+  if (min_area < 0) msg_exit("Minimum component area cannot be negative: " + std::to_string(min_area) + ".");
+  if (fill_holes < -1) msg_exit("Largest hole to fill must be -1 (any size), zero or positive: " + std::to_string(fill_holes) + ".");
   if (reinit_every > 0 && write_video) msg_exit("Reinitialisation (--reinit) cannot be combined with video output (-V).");
 
   // ---- read the image: src/main.cpp:877-887 (8-bit gray or BGR)
@@ -560,9 +585,16 @@ int main(int argc, char **argv)
     out.write(reinterpret_cast<const char *>(u.data()), (std::streamsize)(n * sizeof(double)));
     if (!out) msg_exit("Error: cannot write \"" + dump_u + "\"");
   }
+  // the cleaned mask (-I applied as invert), where a cleaning option was given: what --dump-mask, _selection and --roi then use
+  std::vector<uint8_t> cleaned;
+  if (clean_mask && (!dump_mask.empty() || object_selection || roi)) {
+    cleaned.resize(n);
+    cvh_check(ctx, cvh_get_mask_clean(ctx, cleaned.data(), connectivity, invert ? 1 : 0, min_area, fill_holes, largest ? 1 : 0), "cvh_get_mask_clean");
+  }
   if (!dump_mask.empty()) {
     std::vector<uint8_t> m(n);
-    cvh_check(ctx, cvh_get_mask(ctx, m.data(), invert ? 1 : 0), "cvh_get_mask");
+    if (clean_mask) m = cleaned;
+    else cvh_check(ctx, cvh_get_mask(ctx, m.data(), invert ? 1 : 0), "cvh_get_mask");
     for (auto &v : m) v = v ? 255 : 0;
     if (!write_image(dump_mask, h, w, 1, m.data())) msg_exit("Error: cannot write \"" + dump_mask + "\"");
   }
@@ -570,10 +602,26 @@ int main(int argc, char **argv)
   // ---- selection: src/main.cpp:1004-1005
   if (object_selection) {
     std::vector<uint8_t> sel(n * 3), rgb(n * 3);
-    cvh_check(ctx, cvh_separate(ctx, img_bgr.data(), invert ? 1 : 0, sel.data()), "cvh_separate");
+    if (clean_mask) {   // separate()'s rule (src/main.cpp:386-405) on the cleaned mask: white canvas, the image copied where the mask is set
+      for (size_t q = 0; q < n; ++q)
+        for (int k = 0; k < 3; ++k) sel[3 * q + k] = cleaned[q] ? img_bgr[3 * q + k] : 255;
+    } else {
+      cvh_check(ctx, cvh_separate(ctx, img_bgr.data(), invert ? 1 : 0, sel.data()), "cvh_separate");
+    }
     for (size_t q = 0; q < n; ++q) { rgb[3 * q] = sel[3 * q + 2]; rgb[3 * q + 1] = sel[3 * q + 1]; rgb[3 * q + 2] = sel[3 * q]; }
     if (!write_image(add_suffix(input_filename, "selection"), h, w, 3, rgb.data()))
       msg_exit("Error: cannot write \"" + add_suffix(input_filename, "selection") + "\"");
+  }
+  if (roi) {   // the largest component of the mask the other outputs use (ties: the smaller first index), "roi none" for an empty mask
+    std::vector<uint8_t> m(n);
+    if (largest) m = cleaned;
+    else cvh_check(ctx, cvh_get_mask_clean(ctx, m.data(), connectivity, invert ? 1 : 0, min_area, fill_holes, 1), "cvh_get_mask_clean");
+    long x0 = w, y0 = h, x1 = -1, y1 = -1, area = 0;
+    for (int i = 0; i < h; ++i)
+      for (int j = 0; j < w; ++j)
+        if (m[(size_t)i * w + j]) { x0 = std::min<long>(x0, j); x1 = std::max<long>(x1, j); y0 = std::min<long>(y0, i); y1 = std::max<long>(y1, i); ++area; }
+    if (area) std::printf("roi %ld %ld %ld %ld %ld\n", x0, y0, x1, y1, area);
+    else std::printf("roi none\n");
   }
   if (vm.count("verbose"))  // the reference prints nothing
     std::fprintf(stderr, "chan_vese: %d iterations, last ||u_diff|| = %.17g\n", steps_done, last_norm);

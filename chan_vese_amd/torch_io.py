@@ -124,6 +124,22 @@ class Segmenter:
         capi.get_mask_device_batch(self.contexts, [masks[i].data_ptr() for i in range(self.n)], invert, stream)
         return masks, [r[0] for r in res], [r[1] for r in res]
 
+    def components(self, conn=4, invert=False):
+        """The connected components of every member's mask (cvh_components_batch): (labels, counts), labels an int32 tensor (N, H, W) --
+        0 background, 1..K in the order of scipy.ndimage.label -- valid for the next operation on the current stream, counts the K of
+        every member.  One host wait, for the counts."""
+        labels = torch.empty((self.n, self.h, self.w), dtype=torch.int32, device=torch.device("cuda", self.device))
+        counts = capi.components_batch(self.contexts, [labels[i].data_ptr() for i in range(self.n)], conn, invert, self._stream())
+        return labels, counts
+
+    def clean_masks(self, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False):
+        """Every member's cleaned mask (cvh_get_mask_clean_device_batch; Context.get_mask_clean names the steps) as a uint8 tensor
+        (N, H, W), valid for the next operation on the current stream without a host wait of the caller's."""
+        masks = torch.empty((self.n, self.h, self.w), dtype=torch.uint8, device=torch.device("cuda", self.device))
+        capi.get_mask_clean_device_batch(self.contexts, [masks[i].data_ptr() for i in range(self.n)], conn, invert, min_area, fill_holes,
+                                         keep_largest, self._stream())
+        return masks
+
     def levelsets(self, dtype=torch.float64):
         """The members' level sets as a device tensor (N, H, W), float64 or float32 (rounded to nearest even)."""
         if dtype not in (torch.float64, torch.float32):

@@ -388,6 +388,57 @@ int cvh_get_mask_device_batch(cvh_context *const *ctxs, int n, uint8_t *const *d
 int cvh_reinit(cvh_context *ctx, int *changed);
 int cvh_reinit_batch(cvh_context *const *ctxs, int n, int *changed);
 
+/* ---- Connected components of the mask ----------------------------------------------------------------------------------------
+ * The reference says what its contour is for: "the resulting contour is used to cut out ROI".  On noisy images the mask has speckle,
+ * pin-holes and several blobs; these calls label, measure and clean it ON THE DEVICE -- what a caller otherwise does with
+ * cvh_get_mask, scipy.ndimage.label / cv::connectedComponents on a CPU and an upload.  They only read the level set: level set, run
+ * state, sums and options are not touched, and a run continued after any of them is bit-identical to one without.  Iterations in flight
+ * are settled first, as the getters do.  Everything is defined in integers:
+ *   foreground  f(p) = (((float)u(p) > 0) != invert), cvh_get_mask's rule (NaN, -0.0 and a positive double that rounds to 0.0f are
+ *               outside; with "state" = 32 the class comes from the float state, as in cvh_reinit);
+ *   conn        4 or 8; the BACKGROUND uses the complementary connectivity (8 when conn = 4, 4 when conn = 8);
+ *   labels      int32, row-major h x w, 0 = background; the foreground components are numbered 1..K in increasing order of their
+ *               smallest flat index row*w + col -- scipy.ndimage.label's numbering (cross structure for 4, ones((3,3)) for 8);
+ *   table       row k-1 describes label k: first = its smallest flat index, area, and the inclusive box x0 <= col <= x1, y0 <= row <= y1;
+ *   cleaning    given min_area >= 0, fill_holes >= -1 and keep_largest in {0, 1}, in this order:
+ *               1. foreground components with area < min_area are dropped;
+ *               2. a hole is a background component of the result of 1, in the complementary connectivity, without a pixel in the
+ *                  first or last row or column; every hole of area <= fill_holes becomes foreground (-1: holes of any size, 0: none);
+ *               3. with keep_largest only the largest foreground component (conn) of the result of 2 stays; ties go to the smaller first.
+ *               The output is a 0/1 uint8 mask; with (0, 0, 0) it is cvh_get_mask's, byte for byte (the existing mask kernel alone runs).
+ * An all-background plane has K = 0, an all-zero label plane and an all-zero clean mask: no error.
+ * cvh_components: d_labels (device, 4-byte aligned) may be NULL, table (host, cap rows) may be NULL, count may be NULL.  *count is always
+ * the full K; table receives the first min(K, cap) rows.  cvh_components_batch: d_labels may be NULL and so may any of its entries (no
+ * label plane for that member); counts is an array of n or NULL.
+ * Device pointers follow the rules of "Device-memory input and output" above (hipPointerGetAttributes check, any byte alignment for
+ * uint8, event ordering against `stream`).  The *_batch forms serve n contexts of one device, any mix of shapes and channel counts, with
+ * ONE set of launches on member 0's stream, joined with every member's stream before and after as cvh_reinit_batch; the single-context
+ * forms are the same kernels with n = 1.
+ * Host waits: cvh_components and cvh_components_batch wait ONCE per call, for the counts; cvh_components waits a SECOND time where it
+ * fills a table (K decides where the rows live; the rows are computed behind the first wait).  The clean-mask calls never need K on the
+ * host: the device forms wait only where cvh_get_mask_device does, cvh_get_mask_clean once for its bytes as cvh_get_mask.
+ * How (chan_vese_amd/csrc/components_kernels.hip): union-find with the smallest flat index as root, unions by atomic min on the larger
+ * root, a lane per pixel; the launches are ordered by kernel boundaries alone.  A component's root is its `first` whatever the timing, so
+ * labels, table and clean mask do not depend on the grid or the schedule.  Roots are numbered by per-workgroup counts and a
+ * one-workgroup scan.  Cost: not measured (data flow, bytes per pixel, registers).
+ * The workspace -- 8 bytes per pixel (parent / label words, per-root statistics) plus 4 bytes per 256 pixels (root counts), reused by
+ * the second and third labelling of a clean mask; and 24 bytes per component for the rows of a table, where one is asked for -- is
+ * allocated by a context's first call and kept until cvh_destroy; cvh_create allocates nothing for it and the automatic choices that
+ * weigh the contexts of a device do not count it.
+ * CVH_ERR_ARG: conn not 4 or 8, negative min_area, fill_holes < -1, keep_largest not 0 or 1, negative cap, ctxs NULL, n < 1, a NULL or
+ * duplicate member, members on different devices, a NULL mask pointer, a pointer that is not device-accessible memory of the
+ * context's device or a misaligned label plane, a plane with h*w >= 2^31.  CVH_ERR_STATE: a member without a level set.  Checked for
+ * every member before anything is launched; the message names the member index and is cvh_last_error(NULL)'s and member 0's. */
+typedef struct cvh_component { uint32_t first, area; int32_t x0, y0, x1, y1; } cvh_component;
+
+int cvh_components(cvh_context *ctx, int conn, int invert, int32_t *d_labels, cvh_component *table, int cap, int *count, void *stream);
+int cvh_components_batch(cvh_context *const *ctxs, int n, int conn, int invert, int32_t *const *d_labels, int *counts, void *stream);
+int cvh_get_mask_clean(cvh_context *ctx, uint8_t *mask, int conn, int invert, long min_area, long fill_holes, int keep_largest);
+int cvh_get_mask_clean_device(cvh_context *ctx, uint8_t *d_mask, int conn, int invert, long min_area, long fill_holes, int keep_largest,
+                              void *stream);
+int cvh_get_mask_clean_device_batch(cvh_context *const *ctxs, int n, uint8_t *const *d_masks, int conn, int invert, long min_area,
+                                    long fill_holes, int keep_largest, void *stream);
+
 /* Library version string, e.g. "chanvese_hip 0.1 (gfx950)". */
 const char *cvh_version(void);
 
