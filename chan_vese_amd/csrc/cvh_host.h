@@ -46,6 +46,8 @@ struct cvh_context {   // opaque to callers; four groups
   double *d_trace = nullptr;
   int trace_cap = 0;
   double *d_pm[2] = {nullptr, nullptr};
+  int pm_plane = -1;            // which of d_pm[] pm_store read for the last channel of the most recent Perona-Malik call (-1: no call has
+                                // stored a plane yet, or the last one failed on the device) -- cvh_debug_pm_plane; assigned in pm_run.hip
   uint8_t *d_mask = nullptr;
   double *d_dummy = nullptr;
   double *d_atan = nullptr;

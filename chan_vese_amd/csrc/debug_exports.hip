@@ -60,6 +60,21 @@ extern "C" int cvh_debug_resident_read(cvh_context *c, unsigned *out, int ngo)
   return CVH_OK;
 }
 
+// Diagnostic (not part of include/chanvese_hip.h): the h * w doubles the most recent Perona-Malik call of at least one time step on this
+// context (its own cvh_perona_malik, or a cvh_perona_malik_batch it was a member of) left for its LAST channel -- the very plane pm_store rounded into
+// that channel's uint8 plane (tests/test_gpu_pm_state.py holds every flow's doubles against the oracle's).  CVH_ERR_STATE before the
+// first such call and after one that failed on the device; a call refused for its arguments leaves the previous plane in place.
+extern "C" int cvh_debug_pm_plane(cvh_context *c, double *out)
+{
+  if (!c || !out) return CVH_ERR_ARG;
+  if (c->pm_plane < 0 || c->pm_plane > 1 || !c->d_pm[c->pm_plane])
+    return fail(c, CVH_ERR_STATE, "cvh_debug_pm_plane: no Perona-Malik call has left a plane on this context");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(out, c->d_pm[c->pm_plane], c->n * sizeof(double), hipMemcpyDeviceToHost));
+  return CVH_OK;
+}
+
 // Diagnostic (not part of include/chanvese_hip.h): the CUs of the context's device, what the automatic geometry and a fused batch's
 // shares are sized for (tests/test_gpu_fused_batch_matrix.py recomputes a member's share geometry from it).
 extern "C" int cvh_debug_num_cus(cvh_context *c, int *out)

@@ -114,6 +114,7 @@ static int pm_run_resident(cvh_context *c, const CvhPmArgs &base, const Resident
       t += n;
     }
     HIPCHK(c, cvh_launch_pm_store(c->d_pm[cur], c->d_img[k], c->n, c->stream));
+    c->pm_plane = cur;
   }
   return CVH_OK;
 }
@@ -205,6 +206,7 @@ static int pm_run_per_launch(cvh_context *c, CvhPmArgs a, int trips)
         cur ^= 1;
       }
       HIPCHK(c, cvh_launch_pm_store(c->d_pm[cur], c->d_img[k], c->n, c->stream));
+      c->pm_plane = cur;
     }
   }
   return CVH_OK;
@@ -234,6 +236,9 @@ extern "C" int cvh_perona_malik(cvh_context *c, double K, double L, double T)
   const bool want = c->pm_kernel == 4 || (c->pm_kernel == -1 && c->pm_strip_rows == 0 && trips >= pm_resident_min_trips(c->n));
   const bool resident = want && trips > 0 && pm_resident_geometry(c, &rg);
   if (!resident && c->pm_kernel == 4 && trips > 0) return fail(c, CVH_ERR_ARG, "%s", kPmNeedsResident);
+  // d_pm[] is overwritten from here on: the flow records the plane its last pm_store reads (cvh_debug_pm_plane).  (T = L = 0 is the one
+  // accepted call with no trip: it touches nothing, the plane of the last call that stepped stays.)
+  if (trips > 0) c->pm_plane = -1;
   rc = resident ? pm_run_resident(c, a, rg, trips) : pm_run_per_launch(c, a, trips);
   if (rc != CVH_OK) return rc;
   HIPCHK(c, hipEventRecord(c->ev1, c->stream));
@@ -245,6 +250,7 @@ extern "C" int cvh_perona_malik(cvh_context *c, double K, double L, double T)
   planes_changed(c);   // the stop norm and the region means are taken again
   if (resident && c->h_resident[0]) {
     c->h_resident[0] = 0;
+    c->pm_plane = -1;
     return fail(c, CVH_ERR_HIP, "cvh_perona_malik: a wait of the resident kernel gave up (a workgroup was not resident, or a fault); the planes are undefined");
   }
   return CVH_OK;
@@ -416,6 +422,7 @@ extern "C" int cvh_perona_malik_batch(cvh_context *const *ctxs, int n, const dou
         cvh_context *c = ctxs[i];
         c->last_pm_ms = ms;
         planes_changed(c);
+        c->pm_plane = gave_up ? -1 : 1;   // every launch of a member runs d_pm[0] -> d_pm[1]; the last round's is its last channel's
         if (bl.round != 0) continue;   // launch_info describes the launch of the member's first plane
         snprintf(c->pm_desc, sizeof(c->pm_desc), "kernel=%s grid=%u block=%u lds_bytes=%u steps_per_launch=%d tiles_y=%d tiles_x=%d launches=1 graph_launches=0 trips=%d planes=%d batch_planes=%d batch_launches=%d",
                  nb.name, nb.grid, nb.block, nb.lds, trips[i], (c->h + 8 * bl.nr - 1) / (8 * bl.nr), (c->w + cvh_resident_tile_w() - 1) / cvh_resident_tile_w(),

@@ -1,7 +1,8 @@
 """Perona-Malik on a resident plane (pm_resident_kernel.hip, option "pm_kernel" = 4; the automatic flow for planes that qualify): the
 FP64 state of a channel stays in the LDS of the CUs for all time steps, only the tiles' borders cross workgroups.  Checked against the
 oracle (src/main.cpp:478-560 restated) -- STRICT bit-exact on the uint8 planes, FAST <= 1 LSB on <= 1e-6 of the pixels -- and against the
-per-launch flow, whose doubles it must reproduce exactly."""
+per-launch flow, whose doubles it must reproduce exactly.  The bytes are what this file compares; the doubles themselves -- bit for bit
+across the flows, and against the oracle's state -- are held in tests/test_gpu_pm_state.py."""
 import numpy as np
 import pytest
 

@@ -1,5 +1,5 @@
 """Seeded random shapes / channel counts / flavours / run lengths: the resident-plane kernels against the per-launch flows
-(tools/fuzz_resident.py: Perona-Malik planes identical byte for byte, CSV level sets within 1e-9 and the same iteration count)."""
+(tools/fuzz_resident.py: Perona-Malik planes identical byte for byte and the last channel's doubles bit for bit, CSV level sets within 1e-9 and the same iteration count)."""
 import os
 import subprocess
 import sys

@@ -1,11 +1,18 @@
 """Randomised cross-check of the resident-plane kernels against the per-launch flows (one process, seeded):
-  Perona-Malik: identical uint8 planes (both flavours run the same operations in the same order);
+  Perona-Malik: identical uint8 planes and, for the last channel, identical FP64 planes bit for bit (cvh_debug_pm_plane; both flavours
+  run the same operations in the same order);
   CSV: level set within 1e-9 of the per-launch flow's after the same iterations, same iteration count and stop flag.
 usage: fuzz_resident.py [CASES=60 SEED=1 MAXDIM=700]"""
-import os, sys
+import ctypes, os, sys
 sys.path.insert(0, '.')
 import numpy as np
 from chan_vese_amd import capi
+def pm_plane(ctx):   # the doubles pm_store read for the last channel (debug_exports.hip)
+    fn = capi.lib().cvh_debug_pm_plane
+    fn.restype, fn.argtypes = ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
+    out = np.empty((ctx.h, ctx.w))
+    ctx._chk(fn(ctx._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+    return out.view(np.uint64)
 cases = int(os.environ.get("CASES", "60")); seed = int(os.environ.get("SEED", "1")); maxdim = int(os.environ.get("MAXDIM", "700"))
 rng = np.random.default_rng(seed)
 bad = 0
@@ -20,8 +27,8 @@ for n in range(cases):
         with capi.Context(h, w, C) as ctx:
             ctx.set_option("math_mode", math); ctx.set_option("pm_kernel", pk)
             ctx.set_image(planes); ctx.perona_malik(K, L, L * steps)
-            out[pk] = (ctx.get_image(), ctx.launch_info(1)["kernel"], capi.pm_trip_count(L, L * steps))
-    same = all(np.array_equal(a, b) for a, b in zip(out[4][0], out[3][0]))
+            out[pk] = (ctx.get_image(), ctx.launch_info(1)["kernel"], capi.pm_trip_count(L, L * steps), pm_plane(ctx))
+    same = all(np.array_equal(a, b) for a, b in zip(out[4][0], out[3][0])) and np.array_equal(out[4][3], out[3][3])
     ok_pm = same and out[4][1].startswith("pm_resident_kernel")
     # CSV (1 channel, FAST): resident vs per-launch
     img = planes[0]; its = int(rng.integers(1, 40)); tol = float(rng.choice([0.0, 0.0, 1e-3]))
