@@ -227,7 +227,7 @@ int cvh_run_batch(cvh_context *const *ctxs, int n, int max_steps, int *steps_don
  * While every region holds a pixel (any |u|/eps up to 1e12, tests/test_gpu_lopsided.py) c1/c2 agree with the reference
  * to 1e-9.  With NO pixel on one side the reference itself defines that side's mean only to 2e-11 at |u|/eps = 1e7,
  * 1.5e-9 at 1e9 and 2.4e-6 at 1e12 (cancellation in 1 + 2/pi atan); the flavours with centred sums (FAST wave kernels,
- * resident, FP32 state, fused batch) are then within 6e-9, 4e-7 and 5e-4 of the accurate value;
+ * resident, FP32 state, fused batch) are then within 6e-9, 4e-7 and 5.1e-4 of the accurate value;
  * the other side's mean, the level set and the norm keep their 1e-9.  From |u|/eps ~ 1e16 the empty side's mean is 0/0:
  * NaN here as in the reference, and from the iteration that used it on the level set, the norm and both means are NaN. */
 int cvh_get_means(cvh_context *ctx, double *c1, double *c2);

@@ -13,12 +13,13 @@ import math
 import numpy as np
 
 import param_edges_util as E
-from test_gpu_param_edges import FLAVOURS
+from test_gpu_param_edges import FLAVOURS, INDEX
 
-# the nine flavours of tests/test_gpu_param_edges.py: the eight of its table and a member of a fused batch
+# the flavours of tests/test_gpu_param_edges.py: those of its table and a member of a fused batch, in the order of their pinned indices
+# (a flavour's position chooses its image and seeds below)
 SHAPES = {f: (v[0], v[1]) for f, v in FLAVOURS.items()}
 SHAPES["batch"] = ((40, 160), 1)
-NAMES = list(SHAPES)
+NAMES = sorted(SHAPES, key=INDEX.get)
 NUM_CUS = 256   # MI355X; the GPU test holds launch_info() against the geometry derived here
 
 
@@ -145,7 +146,7 @@ def params(channels, **kw):
 
 
 def conditioned_cases(flavour):
-    """Six cases: every (minority, side) once; every R and every eps at least twice; the pairing rotates with the flavour, so that the nine
+    """Six cases: every (minority, side) once; every R and every eps at least twice; the pairing rotates with the flavour, so that the
     flavours together also meet every (minority, side, R) and (minority, side, eps).  state32: R <= 1e4 (a float level set)."""
     fi = NAMES.index(flavour)
     Rs = (1e2, 1e4) if flavour == "state32" else (1e2, 1e4, 1e6)
@@ -159,7 +160,7 @@ def _empty(R):
     return [dict(minority=0, side=side, R=R, eps=1.0, seed=int(math.log10(R)) + (side > 0)) for side in (+1, -1)]
 
 
-# On the oracle (planes of 33 x 144 .. 48 x 160, both sides, nine images) the empty side's mean is off the long-double value by
+# On the oracle (planes of 33 x 144 .. 48 x 160, both sides, the images of flavours 0 .. 8) the empty side's mean is off the long-double value by
 #   R = 1e7: 4e-14 .. 2e-11   1e8: 4e-12 .. 2e-10   1e9: 4e-12 .. 1.5e-9   1e10: 3e-10 .. 2e-8   1e11: 2e-9 .. 2e-7   1e12: 5e-8 .. 2.4e-6
 # so only R = 1e12 is ill-conditioned (> 1e-9) in every case; at 1e7 and 1e9 the reference neither misses the 1e-9 bar in every case
 # nor keeps 100 x headroom under it: MARGINAL, run under the same assertions (the empty side recorded, not asserted).

@@ -1,8 +1,8 @@
 """Every CSV flavour at the parameter, level-set and image edges of tests/param_edges_util.py, against the oracle.
 
 Flavours (each pinned through launch_info(), so that a case cannot silently run another kernel): the tile kernel (kernel 0) FAST and
-STRICT, the 1-pixel wave kernel (kernel 2) FAST and STRICT, the 2-pixel wave kernel (kernel 3) with 1 and 3 channels, the resident
-kernel, the FP32-state mode and a member of a fused batch (run_batch).  Each flavour runs five cases: every start and every image, and
+STRICT, the 1-pixel wave kernel (kernel 2) FAST and STRICT, both with 1 and 3 channels, the 2-pixel wave kernel (kernel 3) with 1 and 3
+channels, the resident kernel, the FP32-state mode and a member of a fused batch (run_batch).  Each flavour runs five cases: every start and every image, and
 every parameter set of the covering design (so every eps, mu, nu, dt and lambda value meets every flavour).
 
 Bars, the suite's: level set within 1e-9 of max|u| after 1, 3 and 10 iterations, every trace row rtol 1e-9, the same steps_done (the
@@ -33,8 +33,18 @@ FLAVOURS = {
     "wave2_c3": ((33, 144), 3, dict(kernel=3, math_mode=FAST), "csv_wave2_kernel<3, true, 3, ", "fast"),
     "resident": ((48, 160), 1, dict(resident=1), "csv_resident_kernel<", "fast"),
     "state32": ((40, 144), 1, dict(state=32, resident=0), "csv_wave2_kernel<1, true, 3, ", "fast"),
+    # three channels in the 1-pixel wave kernel (every STRICT colour image, FAST below 0.6 Mpixel) and in the tile kernel
+    "wave1_c3_fast": ((41, 136), 3, dict(kernel=2, math_mode=FAST), "csv_wave_kernel<3, true, ", "fast"),
+    "wave1_c3_strict": ((41, 136), 3, dict(kernel=2, math_mode=STRICT), "csv_wave_kernel<3, false, ", "strict"),
+    "tile_c3_fast": ((37, 150), 3, dict(kernel=0, math_mode=FAST), "csv_step_kernel<3, ", "fast"),
+    "tile_c3_strict": ((37, 150), 3, dict(kernel=0, math_mode=STRICT), "csv_step_kernel<3, ", "strict"),
 }
-CASES = [(f, k) for f in list(FLAVOURS) + ["batch"] for k in range(5)]
+# A flavour's index chooses its images and seeds (case_inputs, tests/lopsided_util.py): pinned, so that a flavour added later leaves every
+# earlier case its inputs.  0-7: the first eight of the table; 8: the member of a fused batch; from 9: in the order added.
+INDEX = {f: i for i, f in enumerate(["tile_fast", "tile_strict", "wave1_fast", "wave1_strict", "wave2_c1", "wave2_c3", "resident", "state32",
+                                     "batch", "wave1_c3_fast", "wave1_c3_strict", "tile_c3_fast", "tile_c3_strict"])}
+assert set(INDEX) == set(FLAVOURS) | {"batch"}
+CASES = [(f, k) for f in sorted(INDEX, key=INDEX.get) for k in range(5)]
 CHECKPOINTS = (1, 3, 10)
 
 
@@ -47,7 +57,7 @@ def capi():
 
 
 def case_inputs(oracle, flavour, k, shape, channels):
-    fi = (list(FLAVOURS) + ["batch"]).index(flavour)
+    fi = INDEX[flavour]
     pname = list(E.PARAMS)[k % 4]
     st, im = E.STARTS[k], E.IMAGES[(k + fi) % 5]
     h, w = shape
@@ -55,13 +65,14 @@ def case_inputs(oracle, flavour, k, shape, channels):
     return pname, st, im, pk, E.start(oracle, st, h, w, pk["eps"], seed=k), E.image(im, h, w, channels, seed=fi)
 
 
-def conditioned(oracle, planes, u0, pk):
-    """max |du| / max |u| of the oracle at each checkpoint after a 1-ulp perturbation of u0 (about a third of the pixels up, a third down)."""
+def conditioned(oracle, planes, u0, pk, checkpoints=None):
+    """max |du| / max |u| of the oracle at each checkpoint (CHECKPOINTS when not given) after a 1-ulp perturbation of u0 (about a third of
+    the pixels up, a third down)."""
     rng = np.random.default_rng(5)
     up = u0 * (1 + rng.choice([-1.0, 0.0, 1.0], size=u0.shape) * 2.0 ** -52)
     p = oracle.make_params(**pk)
     out = {}
-    for s in CHECKPOINTS:
+    for s in checkpoints if checkpoints is not None else CHECKPOINTS:
         a, da, _, _ = oracle.csv_run(planes, u0, p, s)
         b, db, _, _ = oracle.csv_run(planes, up, p, s)
         out[s] = np.inf if da != db else float(np.abs(a - b).max() / max(np.abs(a).max(), 1e-300))
