@@ -31,6 +31,8 @@ EXPORTS = [
     "cvh_get_mask_device", "cvh_set_image_device_batch", "cvh_init_checkerboard_batch", "cvh_get_mask_device_batch",
     "cvh_reinit", "cvh_reinit_batch",
     "cvh_components", "cvh_components_batch", "cvh_get_mask_clean", "cvh_get_mask_clean_device", "cvh_get_mask_clean_device_batch",
+    "cvh_histogram", "cvh_histogram_batch", "cvh_otsu_from_histogram", "cvh_otsu_threshold", "cvh_init_threshold", "cvh_init_threshold_batch",
+    "cvh_init_otsu", "cvh_init_otsu_batch", "cvh_init_rect", "cvh_init_rect_batch", "cvh_init_disk", "cvh_init_disk_batch",
 ]
 # struct cvh_component: row k - 1 of a component table describes label k (first = smallest flat index; the box is inclusive)
 COMPONENT_DTYPE = np.dtype([("first", np.uint32), ("area", np.uint32), ("x0", np.int32), ("y0", np.int32), ("x1", np.int32), ("y1", np.int32)])
@@ -116,6 +118,18 @@ def lib():
         "cvh_get_mask_clean": (C.c_int, [vp, u8p, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int]),
         "cvh_get_mask_clean_device": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, vp]),
         "cvh_get_mask_clean_device_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.POINTER(vp), C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, vp]),
+        "cvh_histogram": (C.c_int, [vp, vp, C.c_int, ip]),
+        "cvh_histogram_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.POINTER(vp), ip]),
+        "cvh_otsu_from_histogram": (C.c_int, [vp, C.c_int, ip]),
+        "cvh_otsu_threshold": (C.c_int, [vp, ip]),
+        "cvh_init_threshold": (C.c_int, [vp, C.c_int, C.c_double, C.c_double]),
+        "cvh_init_threshold_batch": (C.c_int, [C.POINTER(vp), C.c_int, ip, C.c_double, C.c_double]),
+        "cvh_init_otsu": (C.c_int, [vp, ip, C.c_double, C.c_double]),
+        "cvh_init_otsu_batch": (C.c_int, [C.POINTER(vp), C.c_int, ip, C.c_double, C.c_double]),
+        "cvh_init_rect": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double]),
+        "cvh_init_rect_batch": (C.c_int, [C.POINTER(vp), C.c_int, ip, C.c_double, C.c_double]),
+        "cvh_init_disk": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double]),
+        "cvh_init_disk_batch": (C.c_int, [C.POINTER(vp), C.c_int, ip, C.c_double, C.c_double]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -276,6 +290,72 @@ def get_mask_clean_device_batch(contexts, ptrs, conn=4, invert=False, min_area=0
                                                      int(min_area), int(fill_holes), int(keep_largest), int(stream) or None))
 
 
+def otsu_from_histogram(hist):
+    """cvh_otsu_from_histogram: Otsu's threshold of a histogram of 1 .. 766 uint32 counts (the header's integer definition), on the host."""
+    hist = np.ascontiguousarray(hist, dtype=np.uint32)
+    t = C.c_int(-1)
+    _batch_chk(lib().cvh_otsu_from_histogram(hist.ctypes.data, int(hist.size), C.byref(t)))
+    return t.value
+
+
+def _int_rows(values, n, width, name):
+    """values: one row of `width` ints for all members, or a sequence of n rows -> a flat ctypes int array of n * width"""
+    rows = [values] * n if (np.ndim(values) == (1 if width > 1 else 0)) else list(values)
+    if len(rows) != n:
+        raise ValueError(f"{name}: {len(rows)} values for {n} members")
+    flat = []
+    for r in rows:
+        r = [r] if width == 1 else list(r)
+        if len(r) != width:
+            raise ValueError(f"{name}: {len(r)} numbers where {width} are needed")
+        flat += [int(v) for v in r]
+    return (C.c_int * max(len(flat), 1))(*flat)
+
+
+def histogram_batch(contexts, caps=None):
+    """cvh_histogram_batch: the grey histograms (g = the sum of the planes) of every context with one launch.  caps: bins wanted per
+    member (None: all 255 C + 1).  Returns [uint32 array] per context."""
+    contexts = list(contexts)
+    n = len(contexts)
+    caps = [255 * c.channels + 1 for c in contexts] if caps is None else [int(v) for v in caps]
+    if len(caps) != n:
+        raise ValueError(f"{len(caps)} capacities for {n} members")
+    outs = [np.zeros(max(k, 0), dtype=np.uint32) for k in caps]
+    ptrs = (C.c_void_p * max(n, 1))(*[o.ctypes.data if o.size else None for o in outs])
+    _batch_chk(lib().cvh_histogram_batch(_member_array(contexts), n, ptrs, (C.c_int * max(n, 1))(*caps)))
+    return [o[:min(o.size, 255 * c.channels + 1)] for o, c in zip(outs, contexts)]
+
+
+def init_threshold_batch(contexts, t, inside=1.0, outside=-1.0):
+    """cvh_init_threshold_batch: Context.init_threshold for every context with one launch; t is one int or one per member."""
+    contexts = list(contexts)
+    n = len(contexts)
+    _batch_chk(lib().cvh_init_threshold_batch(_member_array(contexts), n, _int_rows(t, n, 1, "t"), float(inside), float(outside)))
+
+
+def init_otsu_batch(contexts, inside=1.0, outside=-1.0):
+    """cvh_init_otsu_batch: Context.init_otsu for every context: one histogram launch, one start launch.  Returns [t] per context."""
+    contexts = list(contexts)
+    n = len(contexts)
+    t = (C.c_int * max(n, 1))()
+    _batch_chk(lib().cvh_init_otsu_batch(_member_array(contexts), n, t, float(inside), float(outside)))
+    return [t[i] for i in range(n)]
+
+
+def init_rect_batch(contexts, xywh, inside=1.0, outside=0.0):
+    """cvh_init_rect_batch: Context.init_rect for every context with one launch; xywh is (x, y, w, h) or one such row per member."""
+    contexts = list(contexts)
+    n = len(contexts)
+    _batch_chk(lib().cvh_init_rect_batch(_member_array(contexts), n, _int_rows(xywh, n, 4, "xywh"), float(inside), float(outside)))
+
+
+def init_disk_batch(contexts, cxcyr, inside=1.0, outside=0.0):
+    """cvh_init_disk_batch: Context.init_disk for every context with one launch; cxcyr is (cx, cy, r) or one such row per member."""
+    contexts = list(contexts)
+    n = len(contexts)
+    _batch_chk(lib().cvh_init_disk_batch(_member_array(contexts), n, _int_rows(cxcyr, n, 3, "cxcyr"), float(inside), float(outside)))
+
+
 def _segmented(contexts, max_steps, every, run):
     """run(contexts, k) -> [(steps, norm)] in segments of `every` iterations with a reinit_batch of the members still iterating between
     segments; a member whose stop rule fired inside a segment leaves for the later ones.  every <= 0: one run(contexts, max_steps)."""
@@ -393,6 +473,38 @@ class Context:
 
     def init_checkerboard(self):
         self._chk(self._L.cvh_init_checkerboard(self._h))
+
+    def histogram(self, cap=None):
+        """cvh_histogram: hist[v] = the number of pixels whose grey value g = sum of the planes is v, v = 0 .. 255 C, counted on the device;
+        cap (None: all) copies only the first bins.  Returns a uint32 array."""
+        bins = C.c_int(0)
+        out = np.zeros(255 * self.channels + 1 if cap is None else max(int(cap), 0), dtype=np.uint32)
+        self._chk(self._L.cvh_histogram(self._h, out.ctypes.data if out.size else None, int(out.size if cap is None else cap), C.byref(bins)))
+        return out[:min(out.size, bins.value)]
+
+    def otsu_threshold(self):
+        """cvh_otsu_threshold: Otsu's threshold of the grey values (the header's integer definition)."""
+        t = C.c_int(-1)
+        self._chk(self._L.cvh_otsu_threshold(self._h, C.byref(t)))
+        return t.value
+
+    def init_threshold(self, t, inside=1.0, outside=-1.0):
+        """cvh_init_threshold: u = inside where the grey value exceeds t, outside elsewhere, on the device; begins a new run."""
+        self._chk(self._L.cvh_init_threshold(self._h, int(t), float(inside), float(outside)))
+
+    def init_otsu(self, inside=1.0, outside=-1.0):
+        """cvh_init_otsu: init_threshold at Otsu's threshold, which it returns."""
+        t = C.c_int(-1)
+        self._chk(self._L.cvh_init_otsu(self._h, C.byref(t), float(inside), float(outside)))
+        return t.value
+
+    def init_rect(self, x, y, w, h, inside=1.0, outside=0.0):
+        """cvh_init_rect: u = inside on the rectangle's pixels (clipped to the plane), outside elsewhere, on the device."""
+        self._chk(self._L.cvh_init_rect(self._h, int(x), int(y), int(w), int(h), float(inside), float(outside)))
+
+    def init_disk(self, cx, cy, r, inside=1.0, outside=0.0):
+        """cvh_init_disk: u = inside on the filled disk (col - cx)^2 + (row - cy)^2 <= r^2, outside elsewhere, on the device."""
+        self._chk(self._L.cvh_init_disk(self._h, int(cx), int(cy), int(r), float(inside), float(outside)))
 
     def reinit(self):
         """cvh_reinit: the level set becomes the exact signed distance to the pixel-edge front of its own mask, on the device.

@@ -1,6 +1,6 @@
 // api.hip — host side of the C ABI declared in include/chanvese_hip.h: context lifecycle, options, image and level-set I/O, getters.
 // and the transitions of a context's run state.  The flows live in csv_run.hip (CSV steps of one context), csv_batch.hip (fused batch),
-// pm_run.hip (Perona-Malik), io_run.hip (device memory); never throws.
+// pm_run.hip (Perona-Malik), io_run.hip (device memory), init_run.hip (device-side initial level sets); never throws.
 #include "cvh_host.h"
 
 char g_create_err[512] = "no error";
@@ -138,6 +138,7 @@ extern "C" void cvh_destroy(cvh_context *c)
   if (c->d_reinit) (void)hipFree(c->d_reinit);
   if (c->d_cc) (void)hipFree(c->d_cc);
   if (c->d_cc_table) (void)hipFree(c->d_cc_table);
+  if (c->d_hist) (void)hipFree(c->d_hist);
   if (c->ev_io_in) (void)hipEventDestroy(c->ev_io_in);
   if (c->ev_io_out) (void)hipEventDestroy(c->ev_io_out);
   if (c->h_resident) (void)hipHostFree(c->h_resident);

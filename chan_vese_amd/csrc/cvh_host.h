@@ -1,7 +1,7 @@
 // cvh_host.h -- private header of the library's host units: the context, the launch geometries and the helpers more than one unit calls.
 // api.hip (lifecycle, options, host-buffer I/O, getters, the transitions of a context's run state), csv_run.hip (CSV steps of one
 // context), csv_batch.hip (fused batch, and what every batch shares), pm_run.hip (Perona-Malik), io_run.hip (device-memory I/O),
-// debug_exports.hip (diagnostics).  Kernel sources do not include it.
+// init_run.hip (device-side initial level sets), debug_exports.hip (diagnostics).  Kernel sources do not include it.
 #pragma once
 #include <limits.h>
 #include <math.h>
@@ -141,6 +141,8 @@ struct cvh_context {   // opaque to callers; four groups
   void *d_cc = nullptr;          // workspace of cvh_components* / cvh_get_mask_clean* (components_kernels.hip), and the rows of the last
   void *d_cc_table = nullptr;    // table: allocated by the first call that needs them, kept -- not part of live_footprint either
   size_t cc_table_rows = 0;
+  unsigned *d_hist = nullptr;    // the 255 C + 1 counters of cvh_histogram* / cvh_otsu_threshold / cvh_init_otsu* (init_kernels.hip): allocated by
+                                 // the first call, kept
   int coop_launch = -1;          // does the device launch cooperatively (-1: not asked yet; launches_cooperatively)
   int resident_cap = -1;         // workgroups of csv_resident_kernel the device holds at once (-1: not asked yet, 0: unavailable)
   int pm_resident_cap = -1;      // workgroups of pm_resident_kernel the device holds at once (-1: not asked yet)

@@ -247,6 +247,18 @@ hipError_t cvh_launch_cc_label(const CvhIoMember *tab, int nmem, unsigned grid, 
 hipError_t cvh_launch_cc_table(const CvhIoMember *tab, int nmem, unsigned grid, hipStream_t s);
 hipError_t cvh_launch_cc_clean(const CvhIoMember *tab, int nmem, unsigned grid, int conn, int invert, unsigned min_area, long fill_holes,
                                int keep_largest, hipStream_t s);
+// device-side initial level sets (init_kernels.hip).  Histogram: plane[] the member's planes, sums its 255 C + 1 32-bit counters (zeroed
+// by the host), sections of cvh_io_blocks(n) workgroups.  Start: dst the level set written, plane[] read by the threshold mode,
+// state_zero / chain_zero as the checkerboard's; member i's start is par[i], a table behind the member table:
+//   CVH_START_THRESHOLD  inside where g > a
+//   CVH_START_RECT       inside where a <= col < b and c <= row < d (the host has clipped the rectangle to the plane)
+//   CVH_START_DISK       inside where (col - a)^2 + (row - b)^2 <= c^2, 0 <= c < 2^31
+#define CVH_HIST_MAX_BINS (255 * CVH_MAX_CHANNELS + 1)
+enum { CVH_START_THRESHOLD = 0, CVH_START_RECT = 1, CVH_START_DISK = 2 };
+struct CvhInitStart { double inside, outside; long long a, b, c, d; int mode, pad; };
+unsigned cvh_init_start_blocks(size_t n);
+hipError_t cvh_launch_init_histogram(const CvhIoMember *tab, int nmem, unsigned grid, hipStream_t s);
+hipError_t cvh_launch_init_start(const CvhIoMember *tab, const CvhInitStart *par, int nmem, unsigned grid, hipStream_t s);
 // rows-per-tile options of the step kernel
 void cvh_step_grid(int h, int w, int tile_rows, int *tiles_x, int *tiles_y);
 int cvh_step_max_blocks(int h, int w);

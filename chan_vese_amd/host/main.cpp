@@ -9,13 +9,16 @@
 // Reference GUI code is out of scope: -R/--rectangle and -C/--circle (mouse selection) are parsed
 // and validated as in the reference, then rejected with a message; their non-interactive forms are
 // --rect x,y,w,h (1 inside / 0 outside, src/InteractiveDataRect.cpp:20-27) and --circ cx,cy,r
-// (1-pixel outline of ones on zeros, src/InteractiveDataCirc.cpp:18-25).
+// (1-pixel outline of ones on zeros, src/InteractiveDataCirc.cpp:18-25).  Starts built on the device (chanvese_hip.h, "Device-side
+// initial level sets"): --rect itself (cvh_init_rect), --disk cx,cy,r (a FILLED disk, 1 inside / 0 outside), --init otsu (+1 where the
+// grey value exceeds Otsu's threshold, -1 elsewhere; with -S it is taken again from the smoothed planes) and --threshold T (the same
+// with a given threshold); --init checkerboard is the default.
 // -V/--video: the XVID writer (src/VideoWriterManager.cpp) is replaced by an image sequence
 // <stem>_frames/frame_NNNNNN<ext> holding the same frames (the input with the contour drawn in
 // --line-color, one frame for t = 0 and one after every iteration, :926-931,:997); the overlay
 // text of -O is not rendered (no font rasteriser here), --fps has nothing to act on.
 // Additions that do not collide with reference options: --dump-u, --dump-mask, --device, --math,
-// --state, --rect, --circ, --reinit, --connectivity, --min-area, --fill-holes, --largest, --roi, --verbose.
+// --state, --rect, --circ, --disk, --init, --threshold, --reinit, --connectivity, --min-area, --fill-holes, --largest, --roi, --verbose.
 #include <algorithm>
 #include <cctype>
 #include <cerrno>
@@ -169,6 +172,7 @@ const Spec kSpecs[] = {
     {"invert-selection", 'I', 0}, {"select", 's', 0}, {"rectangle", 'R', 0}, {"circle", 'C', 0},
     // additions of this build
     {"dump-u", 0, 1}, {"dump-mask", 0, 1}, {"device", 0, 1}, {"math", 0, 1}, {"state", 0, 1}, {"rect", 0, 1}, {"circ", 0, 1}, {"reinit", 0, 1},
+    {"disk", 0, 1}, {"init", 0, 1}, {"threshold", 0, 1},
     {"connectivity", 0, 1}, {"min-area", 0, 1}, {"fill-holes", 0, 1}, {"largest", 0, 0}, {"roi", 0, 0},
     {"verbose", 0, 0}};
 
@@ -304,6 +308,10 @@ void print_help()
       "MI355X build additions:\n"
       "  --rect x,y,w,h                     rectangular initial contour (1 inside, 0 outside)\n"
       "  --circ cx,cy,r                     circular initial contour (1-pixel outline of ones on zeros)\n"
+      "  --disk cx,cy,r                     filled disk as initial contour, built on the device (1 inside, 0 outside)\n"
+      "  --init arg (=checkerboard)         checkerboard | otsu: otsu starts from Otsu's threshold of the grey values (the sum of the\n"
+      "                                     channels), +1 above it and -1 elsewhere, built on the device (with -S: of the smoothed image)\n"
+      "  --threshold T                      the same start with the threshold T (0 .. 255 x channels) instead of Otsu's\n"
       "  --dump-u arg                       write the final level set as raw little-endian float64 (h*w)\n"
       "  --dump-mask arg                    write the final mask ((float)u > 0) as PGM or PNG by extension (0/255)\n"
       "  --device arg (=0)                  HIP device\n"
@@ -371,6 +379,11 @@ int main(int argc, char **argv)
   const bool clean_mask = vm.count("connectivity") || vm.count("min-area") || vm.count("fill-holes") || largest;
   if (auto v = one("rect")) rect = *v;
   if (auto v = one("circ")) circ = *v;
+  std::string disk, init_kind = "checkerboard";
+  int threshold = -1;
+  if (auto v = one("disk")) disk = *v;
+  if (auto v = one("init")) init_kind = *v;
+  if (auto v = one("threshold")) threshold = to_int("threshold", *v);
   segment = vm.count("segment"); grayscale = vm.count("grayscale"); write_video = vm.count("video");
   overlay_text = vm.count("overlay-text"); invert = vm.count("invert-selection");
   object_selection = vm.count("select"); rectangle_contour = vm.count("rectangle"); circle_contour = vm.count("circle");
@@ -416,6 +429,25 @@ int main(int argc, char **argv)
   if (rectangle_contour || circle_contour)
     msg_exit("Interactive contour selection (-R/-C) needs a display and is not supported in this build; use --rect x,y,w,h or --circ cx,cy,r.");
   if (!rect.empty() && !circ.empty()) msg_exit("Cannot initialize with both rectangular and circular contour");
+  if (init_kind != "checkerboard" && init_kind != "otsu") msg_exit("error: the argument ('" + init_kind + "') for option '--init' is invalid");
+  const bool init_otsu = init_kind == "otsu", init_threshold = vm.count("threshold") > 0;
+  {
+    std::vector<std::string> given;
+    if (!rect.empty()) given.push_back("--rect");
+    if (!circ.empty()) given.push_back("--circ");
+    if (!disk.empty()) given.push_back("--disk");
+    if (init_otsu) given.push_back("--init otsu");
+    if (init_threshold) given.push_back("--threshold");
+    if (given.size() > 1) msg_exit("Cannot initialize with both " + given[0] + " and " + given[1]);
+  }
+  int disk_cx = 0, disk_cy = 0, disk_r = 0;
+  if (!disk.empty()) {
+    char rest = 0;
+    if (std::sscanf(disk.c_str(), "%d,%d,%d%c", &disk_cx, &disk_cy, &disk_r, &rest) != 3 || disk_r < 0)
+      msg_exit("You must specify the disk as cx,cy,r with a radius that is not negative");
+  }
+  if (init_threshold && (threshold < 0 || threshold > 255 * (grayscale ? 1 : 3)))
+    msg_exit("Threshold must be between 0 and " + std::to_string(255 * (grayscale ? 1 : 3)) + ": " + std::to_string(threshold) + ".");
   if (math != "strict" && math != "fast") msg_exit("error: the argument ('" + math + "') for option '--math' is invalid");
   if (state_bits != 64 && state_bits != 32) msg_exit("error: the argument ('" + std::to_string(state_bits) + "') for option '--state' is invalid");
   if (reinit_every < 0) msg_exit("Reinitialisation interval cannot be negative: " + std::to_string(reinit_every) + ".");
@@ -478,10 +510,13 @@ int main(int argc, char **argv)
     int rx, ry, rw, rh;
     if (std::sscanf(rect.c_str(), "%d,%d,%d,%d", &rx, &ry, &rw, &rh) != 4 || rw <= 0 || rh <= 0)
       msg_exit("You must specify the contour with non-zero dimensions");
-    std::vector<double> u(n, 0.0);  // src/InteractiveDataRect.cpp:24-25
-    for (int i = std::max(ry, 0); i < std::min(ry + rh, h); ++i)
-      for (int j = std::max(rx, 0); j < std::min(rx + rw, w); ++j) u[(size_t)i * w + j] = 1;
-    cvh_check(ctx, cvh_set_levelset(ctx, u.data()), "cvh_set_levelset");
+    cvh_check(ctx, cvh_init_rect(ctx, rx, ry, rw, rh, 1.0, 0.0), "cvh_init_rect");   // src/InteractiveDataRect.cpp:24-25, on the device
+  } else if (!disk.empty()) {
+    cvh_check(ctx, cvh_init_disk(ctx, disk_cx, disk_cy, disk_r, 1.0, 0.0), "cvh_init_disk");   // (parsed with the other options' validation)
+  } else if (init_otsu) {
+    cvh_check(ctx, cvh_init_otsu(ctx, nullptr, 1.0, -1.0), "cvh_init_otsu");
+  } else if (init_threshold) {
+    cvh_check(ctx, cvh_init_threshold(ctx, threshold, 1.0, -1.0), "cvh_init_threshold");
   } else if (!circ.empty()) {
     int cx, cy, cr;
     if (std::sscanf(circ.c_str(), "%d,%d,%d", &cx, &cy, &cr) != 3 || cr <= 0)  // is_ok(): radius > 0
@@ -548,6 +583,9 @@ int main(int argc, char **argv)
     }
     if (!write_image(add_suffix(input_filename, "pm"), h, w, nof_channels, out.data()))
       msg_exit("Error: cannot write \"" + add_suffix(input_filename, "pm") + "\"");
+    // a start taken from the image is taken again from the smoothed planes (the one above served the t = 0 frame)
+    if (init_otsu) cvh_check(ctx, cvh_init_otsu(ctx, nullptr, 1.0, -1.0), "cvh_init_otsu");
+    else if (init_threshold) cvh_check(ctx, cvh_init_threshold(ctx, threshold, 1.0, -1.0), "cvh_init_threshold");
   }
 
   // ---- timestep loop: src/main.cpp:950-1001 (stop condition and every iteration on the GPU)

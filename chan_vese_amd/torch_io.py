@@ -59,6 +59,48 @@ def check_levelsets(init, n, h, w, device=0):
     return 64 if init.dtype == torch.float64 else 32
 
 
+def check_init(init, n, channels=1):
+    """Validates a device-side start of Segmenter.segment and returns (kind, values): ("checkerboard", None), ("otsu", None),
+    ("threshold", [t] * n), ("rect", [(x, y, w, h)] * n) or ("disk", [(cx, cy, r)] * n), every number an int.  A tuple's value is one
+    entry for all members or a list of n.  ValueError for anything else.  Calls nothing in the library."""
+    if isinstance(init, str):
+        if init in ("checkerboard", "otsu"):
+            return init, None
+        raise ValueError(f'init must be "checkerboard", "otsu", a (kind, value) tuple or a tensor, got {init!r}')
+    widths = {"threshold": 1, "rect": 4, "disk": 3}
+    if not (isinstance(init, tuple) and len(init) == 2 and isinstance(init[0], str) and init[0] in widths):
+        raise ValueError(f'init must be "checkerboard", "otsu", ("threshold", t), ("rect", (x, y, w, h)), ("disk", (cx, cy, r)) or a tensor, got {init!r}')
+    kind, value = init
+    width = widths[kind]
+
+    def entry(v):
+        if width == 1:
+            ok = isinstance(v, int) and not isinstance(v, bool)
+        else:
+            ok = isinstance(v, (tuple, list)) and len(v) == width and all(isinstance(x, int) and not isinstance(x, bool) for x in v)
+        if not ok:
+            raise ValueError(f"init {kind!r}: {v!r} is not " + ("an int" if width == 1 else f"{width} ints"))
+        return v if width == 1 else tuple(v)
+
+    one = isinstance(value, int) if width == 1 else (isinstance(value, (tuple, list)) and len(value) == width and not isinstance(value[0], (tuple, list)))
+    if one:
+        rows = [entry(value)] * n
+    elif isinstance(value, list):
+        if len(value) != n:
+            raise ValueError(f"init {kind!r}: {len(value)} entries for {n} members")
+        rows = [entry(v) for v in value]
+    else:
+        raise ValueError(f"init {kind!r}: {value!r} is neither one entry nor a list of {n}")
+    for r in rows:
+        if kind == "threshold" and not 0 <= r <= 255 * channels:
+            raise ValueError(f"init 'threshold': t must be in 0 .. {255 * channels}, got {r}")
+        if kind == "rect" and (r[2] <= 0 or r[3] <= 0):
+            raise ValueError(f"init 'rect': width and height must be positive, got {r}")
+        if kind == "disk" and r[2] < 0:
+            raise ValueError(f"init 'disk': the radius must not be negative, got {r}")
+    return kind, rows
+
+
 def _check_device(t, device, name):
     if t.device.type != "cuda" or (t.device.index or 0) != device:
         raise ValueError(f"{name} lives on {t.device}, the contexts on cuda:{device}")
@@ -72,6 +114,7 @@ class Segmenter:
             raise ValueError(f"n must be >= 1, got {n}")
         self.n, self.h, self.w, self.channels = n, h, w, channels
         self.device = _device_index(device)
+        self.thresholds = None   # Otsu's thresholds of the last segment(init="otsu")
         self.contexts = []
         try:
             for _ in range(n):
@@ -102,11 +145,17 @@ class Segmenter:
         tensor (N, H, W) on the images' device, valid for the next operation on the current stream without a host wait of the caller's;
         steps / norms the iterations and the last ||u_diff|| of every member.  `layout` (capi.LAYOUT_*) is needed only for a shape that is
         both planar and interleaved (check_images).  reinit_every = K > 0 runs segments of K iterations with a reinitialisation of the
-        members still iterating between segments (capi.run_batch_with_reinit; max_steps stays the total budget); 0 is one cvh_run_batch."""
+        members still iterating between segments (capi.run_batch_with_reinit; max_steps stays the total budget); 0 is one cvh_run_batch.
+        init: "checkerboard"; a float64 / float32 tensor (N, H, W); or a start built on the device from the (smoothed) planes or from
+        numbers -- "otsu" (+1 above Otsu's threshold of the grey values, -1 elsewhere; self.thresholds then holds the N thresholds),
+        ("threshold", t), ("rect", (x, y, w, h)) and ("disk", (cx, cy, r)) (1 inside, 0 outside), the tuple's value one entry for all
+        members or a list of N (check_init).  A text or tuple `init` is validated first, before the images; a tensor `init` after them."""
+        kind, bits = None, None
+        if isinstance(init, (str, tuple)):
+            kind, start = check_init(init, self.n, self.channels)
         layout = check_images(images, self.n, self.h, self.w, self.channels, self.device, layout)
-        bits = None if isinstance(init, str) else check_levelsets(init, self.n, self.h, self.w, self.device)
-        if isinstance(init, str) and init != "checkerboard":
-            raise ValueError(f'init must be "checkerboard" or a tensor, got {init!r}')
+        if kind is None:
+            bits = check_levelsets(init, self.n, self.h, self.w, self.device)
         if perona_malik is not None and len(perona_malik) != 3:
             raise ValueError("perona_malik must be (K, L, T)")
         stream = self._stream()
@@ -114,8 +163,16 @@ class Segmenter:
         if perona_malik is not None:
             K, L, T = perona_malik
             capi.perona_malik_batch(self.contexts, K, L, T)
-        if bits is None:
+        if kind == "checkerboard":
             capi.init_checkerboard_batch(self.contexts)
+        elif kind == "otsu":
+            self.thresholds = capi.init_otsu_batch(self.contexts)
+        elif kind == "threshold":
+            capi.init_threshold_batch(self.contexts, start)
+        elif kind == "rect":
+            capi.init_rect_batch(self.contexts, start)
+        elif kind == "disk":
+            capi.init_disk_batch(self.contexts, start)
         else:
             for i, ctx in enumerate(self.contexts):
                 ctx.set_levelset_device(init[i].data_ptr(), bits, stream)

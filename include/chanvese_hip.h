@@ -439,6 +439,59 @@ int cvh_get_mask_clean_device(cvh_context *ctx, uint8_t *d_mask, int conn, int i
 int cvh_get_mask_clean_device_batch(cvh_context *const *ctxs, int n, uint8_t *const *d_masks, int conn, int invert, long min_area,
                                     long fill_holes, int keep_largest, void *stream);
 
+/* ---- Device-side initial level sets -------------------------------------------------------------------------------------------
+ * The reference's "greater picture" wants its input parameters "found by analyzing the original image".  Chan-Vese minimises the
+ * within-region variance and Otsu's threshold minimises the same quantity over thresholds of the grey values, so an Otsu start is
+ * already close to the answer.  These calls build a start ON THE DEVICE -- what a caller otherwise fills on the host and uploads at
+ * 8 bytes per pixel with cvh_set_levelset.  Everything is defined in integers:
+ *   grey value  g(p) = sum_k I_k(p) over the context's C planes as they are now (after cvh_perona_malik: the smoothed planes), 0 .. 255 C;
+ *   histogram   B = 255 C + 1 bins (256 or 766), hist[v] = the number of pixels with g = v;
+ *   Otsu t      with N = h w, S = sum v hist[v], n0(t) = sum_{v<=t} hist[v], s0(t) = sum_{v<=t} v hist[v]: the candidates are the t in
+ *               0 .. B-2 with 0 < n0(t) < N; a candidate's score is ((double)d * (double)d) / (double)q with d = S n0 - N s0 (an exact
+ *               integer: 128 bits) and q = n0 (N - n0) (exact), each conversion rounded to nearest even, one IEEE multiply and one IEEE
+ *               divide -- Python's float(d) * float(d) / float(q) on integers; t is the candidate with the largest score, ties to the
+ *               smallest t.  A plane with a single occupied bin v0 has no candidate: t = v0, no error (its threshold start is uniformly
+ *               outside);
+ *   threshold   u(p) = g(p) > t ? inside : outside;
+ *   rect        (x, y, rw, rh), rw > 0, rh > 0: inside where x <= col < x + rw and y <= row < y + rh, clipped to the plane, else outside;
+ *               an empty intersection gives a uniform plane, no error;
+ *   disk        (cx, cy, r), r >= 0: inside where (col - cx)^2 + (row - cy)^2 <= r^2 in 64-bit integers -- a FILLED disk (the CLI's
+ *               --circ, the reference's 1-pixel outline, is something else and stays on the host).
+ * inside and outside are any doubles, NaN included, stored bit for bit.  Each start leaves the context exactly as cvh_set_levelset of
+ * the same doubles would: a new run begins (counter, stop flag, sums; with "state" = 32 the float pair adopts the level set), done as
+ * cvh_init_checkerboard_batch does it.  Iterations in flight are settled first.  cvh_histogram*, cvh_otsu_threshold only READ the planes:
+ * level set, run state, sums and options are not touched, and a run continued after them is bit-identical to one without.
+ * cvh_histogram: hist is a HOST buffer of cap counters (may be NULL when cap is 0); the first min(B, cap) bins are copied, *bins (may be
+ * NULL) is always B.  cvh_histogram_batch: hists and caps are arrays of n.  cvh_otsu_from_histogram is a host-only helper (1 <= bins <=
+ * 766, CVH_ERR_ARG for an empty histogram), like cvh_levelset_checkerboard_host.  cvh_init_otsu[_batch]: t (one int / an array of n)
+ * receives the thresholds and may be NULL.  xywh holds 4 n ints, cxcyr 3 n.
+ * The *_batch forms serve n contexts of one device, any mix of shapes and channel counts, with ONE launch per kernel on member 0's
+ * stream, joined with every member's stream before and after as cvh_init_checkerboard_batch; the single-context forms are the same
+ * kernels with n = 1.  Host waits: one per call; cvh_init_otsu* two -- the histogram launch, a wait (the maximisation over at most 765
+ * candidates runs on the host), the start launch, the closing wait.
+ * How (chan_vese_amd/csrc/init_kernels.hip): the histogram kernel reads 16-byte pieces of the planes (1 byte per pixel and plane),
+ * counts in LDS with equal values aggregated within a wave first -- a flat image sends every lane to one bin -- and flushes once per
+ * workgroup with 32-bit atomics; the start kernel writes 16-byte pieces of the level set (8 bytes per pixel; the threshold start also
+ * reads the planes).  Cost: not measured.  The histogram workspace (4 B bytes) is allocated by a context's first call
+ * that needs it and kept until cvh_destroy.
+ * CVH_ERR_ARG: NULL pointers, n < 1, a NULL or duplicate member, members on different devices, negative cap, t outside 0 .. B-1, rw or
+ * rh <= 0, r < 0, a plane with h*w >= 2^32 (32-bit counters).  CVH_ERR_STATE: the histogram, Otsu and threshold calls on a member
+ * without an image (rect and disk need none).  Checked for every member before anything is launched; the message names the member index
+ * and is cvh_last_error(NULL)'s and member 0's.  CVH_ERR_HIP: a HIP call failed, or the histogram launch of an Otsu call came back
+ * without a single counted pixel (nothing is started then). */
+int cvh_histogram(cvh_context *ctx, uint32_t *hist, int cap, int *bins);
+int cvh_histogram_batch(cvh_context *const *ctxs, int n, uint32_t *const *hists, const int *caps);
+int cvh_otsu_from_histogram(const uint32_t *hist, int bins, int *t);
+int cvh_otsu_threshold(cvh_context *ctx, int *t);
+int cvh_init_threshold(cvh_context *ctx, int t, double inside, double outside);
+int cvh_init_threshold_batch(cvh_context *const *ctxs, int n, const int *t, double inside, double outside);
+int cvh_init_otsu(cvh_context *ctx, int *t, double inside, double outside);
+int cvh_init_otsu_batch(cvh_context *const *ctxs, int n, int *t, double inside, double outside);
+int cvh_init_rect(cvh_context *ctx, int x, int y, int rw, int rh, double inside, double outside);
+int cvh_init_rect_batch(cvh_context *const *ctxs, int n, const int *xywh, double inside, double outside);
+int cvh_init_disk(cvh_context *ctx, int cx, int cy, int r, double inside, double outside);
+int cvh_init_disk_batch(cvh_context *const *ctxs, int n, const int *cxcyr, double inside, double outside);
+
 /* Library version string, e.g. "chanvese_hip 0.1 (gfx950)". */
 const char *cvh_version(void);
 
