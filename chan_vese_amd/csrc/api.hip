@@ -1,6 +1,8 @@
 // api.hip — host side of the C ABI declared in include/chanvese_hip.h: context lifecycle, options, image and level-set I/O, getters.
 // and the transitions of a context's run state.  The flows live in csv_run.hip (CSV steps of one context), csv_batch.hip (fused batch),
-// pm_run.hip (Perona-Malik), io_run.hip (device memory), init_run.hip (device-side initial level sets); never throws.
+// pm_run.hip (Perona-Malik), io_run.hip (device memory, and the member-table calls every small device operation goes through:
+// cvh_init_checkerboard is there, cvh_get_mask here is mask_out into the context's buffer), init_run.hip (device-side initial level
+// sets); never throws.
 #include "cvh_host.h"
 
 char g_create_err[512] = "no error";
@@ -411,7 +413,7 @@ double stop_norm_host(const std::vector<const uint8_t *> &planes, size_t n)
 }
 
 // Sums of the planes resident on the device: sum(I_k) for the region means and, for one channel, the stop norm (exact
-// integers, image_sums_kernel).  Three channels round (sum_k I_k)/3 per pixel, so their norm needs the reference's serial
+// integers, image_sums_kernel in io_kernels.hip).  Three channels round (sum_k I_k)/3 per pixel, so their norm needs the reference's serial
 // order: `host_planes` (the caller's buffers, or nullptr to fetch the planes) feed stop_norm_host.
 int image_stats(cvh_context *c, const uint8_t *const *host_planes)
 {
@@ -596,38 +598,24 @@ extern "C" int cvh_set_levelset(cvh_context *c, const double *u)
   return levelset_arrived(c);
 }
 
-extern "C" void cvh_levelset_checkerboard_host(int h, int w, double *u)
+// src/main.cpp:226-231: the factors of sign(sin(pi*i/5) * sin(pi*j/5)), host libm, double -- the h row factors, then the w column factors.
+// The ONE place they are computed: the host form below and the device form (checkerboard_batch, io_run.hip) multiply the same doubles.
+void checkerboard_factors(int h, int w, double *out)
 {
-  // src/main.cpp:226-231: sign(sin(pi*i/5) * sin(pi*j/5)), host libm, double
   const double pi = 3.14159265358979323846;
-  std::vector<double> sj((size_t)w);
-  for (int j = 0; j < w; ++j) sj[j] = sin(pi * j / 5);
-  for (int i = 0; i < h; ++i) {
-    const double si = sin(pi * i / 5);
-    for (int j = 0; j < w; ++j) {
-      const double z = si * sj[j];
-      u[(size_t)i * w + j] = (z == 0) ? 0.0 : (z < 0 ? -1.0 : 1.0);
-    }
-  }
+  for (int i = 0; i < h; ++i) out[i] = sin(pi * i / 5);
+  for (int j = 0; j < w; ++j) out[(size_t)h + j] = sin(pi * j / 5);
 }
 
-extern "C" int cvh_init_checkerboard(cvh_context *c)
+extern "C" void cvh_levelset_checkerboard_host(int h, int w, double *u)
 {
-  if (!c) return CVH_ERR_ARG;
-  HIPCHK(c, hipSetDevice(c->device));
-  { const int rc = settle(c); if (rc != CVH_OK) return rc; }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  // the h + w sine factors from the host's libm (as cvh_levelset_checkerboard_host), staged in the idle buffer of the
-  // ping-pong pair (h + w <= h w + 1 doubles); the sign of their product is taken on the device
-  std::vector<double> sv((size_t)c->h + c->w);
-  const double pi = 3.14159265358979323846;
-  for (int i = 0; i < c->h; ++i) sv[i] = sin(pi * i / 5);
-  for (int j = 0; j < c->w; ++j) sv[(size_t)c->h + j] = sin(pi * j / 5);
-  const int base = c->chain_pb & 1;   // see levelset_arrived
-  HIPCHK(c, hipMemcpyAsync(c->d_u[base ^ 1], sv.data(), sv.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, cvh_launch_checkerboard(c->d_u[base ^ 1], c->d_u[base], c->h, c->w, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return levelset_arrived(c);
+  std::vector<double> sv((size_t)h + w);
+  checkerboard_factors(h, w, sv.data());
+  for (int i = 0; i < h; ++i)
+    for (int j = 0; j < w; ++j) {
+      const double z = sv[i] * sv[(size_t)h + j];
+      u[(size_t)i * w + j] = (z == 0) ? 0.0 : (z < 0 ? -1.0 : 1.0);
+    }
 }
 
 extern "C" int cvh_get_levelset(cvh_context *c, double *u)
@@ -683,13 +671,8 @@ extern "C" int cvh_get_mask(cvh_context *c, uint8_t *mask, int invert)
 {
   if (!c || !mask) return CVH_ERR_ARG;
   if (!c->have_u) return fail(c, CVH_ERR_STATE, "cvh_get_mask: no level set");
-  HIPCHK(c, hipSetDevice(c->device));
-  if (!c->d_mask) HIPCHK(c, hipMalloc((void **)&c->d_mask, c->n));
-  { const int rc = ensure_f64_mirror(c); if (rc != CVH_OK) return rc; }
-  HIPCHK(c, cvh_launch_mask(c->d_u[current_buffer(c)], c->d_mask, c->n, invert, c->stream));
-  HIPCHK(c, hipMemcpyAsync(mask, c->d_mask, c->n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return CVH_OK;
+  static const char what[] = "cvh_get_mask";   // a mask batch of one into the context's own buffer: iterations in flight are settled first
+  return mask_to_host(c, mask, [&]() { return mask_out(&c, 1, &c->d_mask, invert, c->stream, what); });
 }
 
 extern "C" int cvh_get_contour(cvh_context *c, uint8_t *contour)

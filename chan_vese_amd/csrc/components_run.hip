@@ -1,11 +1,9 @@
 // components_run.hip — host side of cvh_components* and cvh_get_mask_clean* (include/chanvese_hip.h, "Connected components"): read-only
-// operations on the level sets of n contexts, on io_run.hip's member tables, stream joins and event ordering.  The single-context calls
+// operations on the level sets of n contexts, each ONE MemberCall (cvh_host.h, io_run.hip: member table, stream joins, event ordering).  The single-context calls
 // are batches of one member.  Nothing here touches a context's level set, run state, sums or options.
 #include "cvh_host.h"
 
 namespace {
-
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) & ~(a - 1); }
 
 int conn_check(cvh_context *const *ctxs, int n, int conn, const char *what)
 {
@@ -29,40 +27,28 @@ int members_ready(cvh_context *const *ctxs, int n, const char *what)
   if (rc != CVH_OK) return rc;
   for (int i = 0; i < n; ++i) {
     cvh_context *c = ctxs[i];
-    rc = ensure_f64_mirror(c);   // "state" = 32: the class of a float is the class of its double
-    if (rc == CVH_OK && !c->d_cc) {   // the workspace: allocated on the first call, kept with the context
-      const hipError_t e = hipMalloc(&c->d_cc, cvh_cc_workspace_bytes(c->n));
-      if (e != hipSuccess) { c->d_cc = nullptr; rc = fail(c, CVH_ERR_HIP, "hipMalloc of the components workspace: %s", hipGetErrorString(e)); }
-    }
+    rc = ensure_workspace(c, &c->d_cc, cvh_cc_workspace_bytes(c->n), "components");
     if (rc != CVH_OK) return batch_fail(ctxs, n, rc, "%s: member %d: %s", what, i, c->err);
   }
   return CVH_OK;
 }
 
-// staging: [member table][one word per member, zero]; *words_off is where the words start.  dst[i] is member i's output (may be null)
-int fill_members(cvh_context *const *ctxs, int n, void *const *dst, size_t *words_off, unsigned *grid)
+// staging: [member table][one word per member, zero at extra_off].  dst[i] is member i's output (may be null)
+int fill_members(MemberCall *call, cvh_context *const *ctxs, int n, void *const *dst, const char *what)
 {
-  cvh_context *lead = ctxs[0];
-  const size_t off = align_up((size_t)n * sizeof(CvhIoMember), 256), bytes = off + (size_t)n * sizeof(unsigned long long);
-  const int rc = stage(lead, bytes, bytes);
+  const int rc = call->begin(ctxs, n, what, (size_t)n * sizeof(unsigned long long));
   if (rc != CVH_OK) return rc;
-  unsigned char *const hb = (unsigned char *)lead->h_io, *const db = (unsigned char *)lead->io_table.d;
-  memset(hb, 0, bytes);
-  CvhIoMember *tab = (CvhIoMember *)hb;
   for (int i = 0; i < n; ++i) {
     const cvh_context *c = ctxs[i];
-    CvhIoMember &m = tab[i];
+    CvhIoMember &m = call->tab[i];
     m.src = c->d_u[current_buffer(c)];
     m.dst = dst ? dst[i] : nullptr;
     m.plane[0] = (uint8_t *)c->d_cc;
     m.plane[1] = m.plane[0] + c->n * sizeof(unsigned);
     m.plane[2] = m.plane[1] + c->n * sizeof(unsigned);
-    m.sums = (unsigned long long *)(db + off) + i;
-    m.n = c->n; m.h = c->h; m.w = c->w; m.C = c->C;
+    m.sums = (unsigned long long *)(call->db + call->extra_off) + i;
     m.nblk = cvh_cc_blocks(c->n);
   }
-  *grid = lay_out(tab, n);
-  *words_off = off;
   return CVH_OK;
 }
 
@@ -87,21 +73,16 @@ int components(cvh_context *const *ctxs, int n, int conn, int invert, int32_t *c
   }
   rc = members_ready(ctxs, n, what);
   if (rc != CVH_OK) return rc;
-  size_t words_off = 0;
-  unsigned grid = 0;
-  rc = fill_members(ctxs, n, (void *const *)d_labels, &words_off, &grid);
+  MemberCall call;
+  rc = fill_members(&call, ctxs, n, (void *const *)d_labels, what);
   if (rc != CVH_OK) return rc;
-  unsigned char *const hb = (unsigned char *)lead->h_io, *const db = (unsigned char *)lead->io_table.d;
-  const size_t bytes = words_off + (size_t)n * sizeof(unsigned long long);
-  rc = open_call(ctxs, n, stream);
+  const unsigned long long *words = (const unsigned long long *)(call.hb + call.extra_off);
+  rc = call.run(stream, any_labels, true, [&]() -> int {   // the host wait of the call: the counts
+    HIPCHK(lead, cvh_launch_cc_label(call.dtab(), n, call.grid, conn, invert, any_labels, lead->stream));
+    HIPCHK(lead, hipMemcpyAsync((void *)words, call.db + call.extra_off, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost, lead->stream));
+    return CVH_OK;
+  });
   if (rc != CVH_OK) return rc;
-  HIPCHK(lead, hipMemcpyAsync(db, hb, bytes, hipMemcpyHostToDevice, lead->stream));
-  HIPCHK(lead, cvh_launch_cc_label((const CvhIoMember *)db, n, grid, conn, invert, any_labels, lead->stream));
-  HIPCHK(lead, hipMemcpyAsync(hb + words_off, db + words_off, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost, lead->stream));
-  rc = close_call(ctxs, n, stream, any_labels);
-  if (rc != CVH_OK) return rc;
-  HIPCHK(lead, hipStreamSynchronize(lead->stream));   // the host wait of the call: the counts
-  const unsigned long long *words = (const unsigned long long *)(hb + words_off);
   for (int i = 0; counts && i < n; ++i) counts[i] = (int)words[i];
   const size_t K = (size_t)words[0];
   const size_t rows = std::min<size_t>(K, table ? (size_t)cap : 0);
@@ -113,10 +94,9 @@ int components(cvh_context *const *ctxs, int n, int conn, int invert, int32_t *c
     HIPCHK(lead, hipMalloc(&lead->d_cc_table, want * sizeof(cvh_component)));
     lead->cc_table_rows = want;
   }
-  CvhIoMember *tab = (CvhIoMember *)hb;
-  tab[0].dst = lead->d_cc_table;   // (the label plane is written: these launches fill the rows)
-  HIPCHK(lead, hipMemcpyAsync(db, hb, sizeof(CvhIoMember), hipMemcpyHostToDevice, lead->stream));
-  HIPCHK(lead, cvh_launch_cc_table((const CvhIoMember *)db, 1, grid, lead->stream));
+  call.tab[0].dst = lead->d_cc_table;   // (the label plane is written: these launches fill the rows)
+  HIPCHK(lead, hipMemcpyAsync(call.db, call.hb, sizeof(CvhIoMember), hipMemcpyHostToDevice, lead->stream));
+  HIPCHK(lead, cvh_launch_cc_table(call.dtab(), 1, call.grid, lead->stream));
   HIPCHK(lead, hipMemcpyAsync(table, lead->d_cc_table, rows * sizeof(cvh_component), hipMemcpyDeviceToHost, lead->stream));
   HIPCHK(lead, hipEventRecord(lead->ev_io_out, lead->stream));   // (the last read of the pinned block)
   HIPCHK(lead, hipStreamSynchronize(lead->stream));
@@ -148,18 +128,15 @@ int clean(cvh_context *const *ctxs, int n, uint8_t *const *d_masks, int conn, in
   for (int i = 0; i < n; ++i) { rc = pointer_check(ctxs, n, i, d_masks[i], what); if (rc != CVH_OK) return rc; }
   rc = members_ready(ctxs, n, what);
   if (rc != CVH_OK) return rc;
-  size_t words_off = 0;
-  unsigned grid = 0;
-  rc = fill_members(ctxs, n, (void *const *)d_masks, &words_off, &grid);
+  MemberCall call;
+  rc = fill_members(&call, ctxs, n, (void *const *)d_masks, what);
   if (rc != CVH_OK) return rc;
-  unsigned char *const hb = (unsigned char *)lead->h_io, *const db = (unsigned char *)lead->io_table.d;
-  rc = open_call(ctxs, n, stream);
-  if (rc != CVH_OK) return rc;
-  HIPCHK(lead, hipMemcpyAsync(db, hb, words_off + (size_t)n * sizeof(unsigned long long), hipMemcpyHostToDevice, lead->stream));
-  if (!drop) HIPCHK(lead, cvh_launch_io_mask((const CvhIoMember *)db, n, grid, invert, lead->stream));   // step 1 is off: the plain mask
-  const unsigned a = (unsigned)std::min<long>(min_area, 0x7fffffffl);
-  HIPCHK(lead, cvh_launch_cc_clean((const CvhIoMember *)db, n, grid, conn, invert, a, fill_holes, keep_largest, lead->stream));
-  return close_call(ctxs, n, stream, true);
+  return call.run(stream, true, false, [&]() -> int {
+    if (!drop) HIPCHK(lead, cvh_launch_io_mask(call.dtab(), n, call.grid, invert, lead->stream));   // step 1 is off: the plain mask
+    const unsigned a = (unsigned)std::min<long>(min_area, 0x7fffffffl);
+    HIPCHK(lead, cvh_launch_cc_clean(call.dtab(), n, call.grid, conn, invert, a, fill_holes, keep_largest, lead->stream));
+    return CVH_OK;
+  });
 }
 
 }  // namespace
@@ -201,12 +178,6 @@ extern "C" int cvh_get_mask_clean(cvh_context *c, uint8_t *mask, int conn, int i
     int rc = clean_args(&c, 1, conn, min_area, fill_holes, keep_largest, what);
     if (rc != CVH_OK) return rc;
     if (!c->have_u) return fail(c, CVH_ERR_STATE, "%s: no level set", what);
-    HIPCHK(c, hipSetDevice(c->device));
-    if (!c->d_mask) HIPCHK(c, hipMalloc((void **)&c->d_mask, c->n));   // cvh_get_mask's device buffer
-    rc = clean(&c, 1, &c->d_mask, conn, invert, min_area, fill_holes, keep_largest, c->stream, what);
-    if (rc != CVH_OK) return rc;
-    HIPCHK(c, hipMemcpyAsync(mask, c->d_mask, c->n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return (int)CVH_OK;
+    return mask_to_host(c, mask, [&]() { return clean(&c, 1, &c->d_mask, conn, invert, min_area, fill_holes, keep_largest, c->stream, what); });
   });
 }

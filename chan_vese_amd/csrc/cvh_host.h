@@ -53,7 +53,7 @@ struct cvh_context {   // opaque to callers; four groups
   double *d_atan = nullptr;
   CvhChainAcc *d_chain = nullptr;   // chain mode of the 2-pixel wave kernel (cvh_internal.h, CvhChainAcc)
   int *d_bounds = nullptr;      // wave kernel: first row of every strip, [tiles_y + 1]
-  unsigned long long *d_isums = nullptr, *h_isums = nullptr;   // image_sums_kernel: {sum p, sum p^2} per plane (device / pinned)
+  unsigned long long *d_isums = nullptr, *h_isums = nullptr;   // image_sums_kernel (io_kernels.hip): {sum p, sum p^2} per plane (device / pinned)
   unsigned long long *d_dbg = nullptr;  // diagnostic stamps (option "debug_times")
   size_t dbg_words = 0;
   // resident kernel (csv_resident_kernel.hip): cache-resident planes iterate in LDS, one cooperative launch per chunk
@@ -231,14 +231,73 @@ void free_table(DeviceTable *t);
 // io_run.hip: launch sets (three kernels for all members) of cvh_reinit / cvh_reinit_batch so far in this process (debug_exports.hip)
 extern std::atomic<unsigned long> g_reinit_launch_sets;
 
-// io_run.hip: what every call on device memory shares (the comments are at the definitions)
+// io_run.hip: what every call on device memory or on a member table shares (the comments are at the definitions)
 int pointer_check(cvh_context *const *ctxs, int n, int i, const void *p, const char *what);
 int settle_all(cvh_context *const *ctxs, int n, const char *what);
-int stage(cvh_context *lead, size_t host_bytes, size_t dev_bytes);
 int open_call(cvh_context *const *ctxs, int n, void *stream);
 int close_call(cvh_context *const *ctxs, int n, void *stream, bool to_caller);
 unsigned lay_out(CvhIoMember *tab, int n);
 int mask_out(cvh_context *const *ctxs, int n, uint8_t *const *d_masks, int invert, void *stream, const char *what);
+void checkerboard_factors(int h, int w, double *out);   // api.hip: out[0 .. h-1] = sin(pi i/5), out[h .. h+w-1] = sin(pi j/5), host libm
+void levelset_target(const cvh_context *c, CvhIoMember *m);
+int ensure_workspace(cvh_context *c, void **slot, size_t bytes, const char *name, bool mirror = true);
+
+inline size_t align_up(size_t v, size_t a) { return (v + a - 1) & ~(a - 1); }
+
+// One call on a member table (checked members, iterations in flight settled by the caller).  The leader's pinned block `hb` is
+//   [table][second table, if asked for][extra_dev bytes at extra_off] -- dev_bytes, zeroed, uploaded to `db` by run() --
+//   [extra_host bytes at host_off] -- host only: the landing place of what the launches copy back;
+// extra_off and host_off are 256-byte aligned.  begin() stages once and fills n, h, w, C of every member; the caller fills the rest
+// (both tables stay writable behind run(): the pinned block is this call's until the leader's next begin()).
+struct MemberCall {
+  cvh_context *const *ctxs = nullptr;
+  int n = 0;
+  const char *what = nullptr;
+  cvh_context *lead = nullptr;
+  unsigned char *hb = nullptr, *db = nullptr;
+  CvhIoMember *tab = nullptr, *tab2 = nullptr;
+  size_t extra_off = 0, host_off = 0, dev_bytes = 0;
+  unsigned grid = 0, grid2 = 0;   // of tab / tab2: laid out by run()
+
+  int begin(cvh_context *const *ctxs_, int n_, const char *what_, size_t extra_dev = 0, size_t extra_host = 0, bool two_tables = false);
+  const CvhIoMember *dtab() const { return (const CvhIoMember *)db; }
+  const CvhIoMember *dtab2() const { return (const CvhIoMember *)(db + ((unsigned char *)tab2 - hb)); }
+  // the members begin the run their new level set opens (all, or those with which[i] != 0): the launch did the device's half
+  int arrived(const int *which = nullptr) const;
+
+  // The sections are laid out; the leader's stream is joined with the members' and the caller's; `first` (if any) is recorded; the
+  // device image goes up; launches() enqueues the kernels and what they copy back on the leader's stream; the members' streams, and
+  // with to_caller the caller's, wait for that; with `wait` the host does too -- the ONE host wait of such a call.
+  template <class F>
+  int run(void *stream, bool to_caller, bool wait, F launches, hipEvent_t first = nullptr)
+  {
+    grid = lay_out(tab, n);
+    if (tab2) grid2 = lay_out(tab2, n);
+    int rc = open_call(ctxs, n, stream);
+    if (rc != CVH_OK) return rc;
+    if (first) HIPCHK(lead, hipEventRecord(first, lead->stream));
+    HIPCHK(lead, hipMemcpyAsync(db, hb, dev_bytes, hipMemcpyHostToDevice, lead->stream));
+    rc = launches();
+    if (rc != CVH_OK) return rc;
+    rc = close_call(ctxs, n, stream, to_caller);
+    if (rc != CVH_OK) return rc;
+    if (wait) HIPCHK(lead, hipStreamSynchronize(lead->stream));
+    return CVH_OK;
+  }
+};
+
+// cvh_get_mask / cvh_get_mask_clean: into_d_mask() writes c->d_mask (allocated on first use) on c's stream; the bytes come down, one wait
+template <class F>
+int mask_to_host(cvh_context *c, uint8_t *mask, F into_d_mask)
+{
+  HIPCHK(c, hipSetDevice(c->device));
+  if (!c->d_mask) HIPCHK(c, hipMalloc((void **)&c->d_mask, c->n));
+  const int rc = into_d_mask();
+  if (rc != CVH_OK) return rc;
+  HIPCHK(c, hipMemcpyAsync(mask, c->d_mask, c->n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return CVH_OK;
+}
 
 // nothing is thrown across the C boundary: a failed host allocation inside body() becomes CVH_ERR_NOMEM
 template <class F>

@@ -224,6 +224,8 @@ struct CvhIoMember {
 unsigned cvh_io_blocks(size_t n);                    // workgroups of a member in the ingest / mask / planes-out grids
 unsigned cvh_io_checkerboard_blocks(int h, int w);
 hipError_t cvh_launch_io_ingest(const CvhIoMember *tab, int nmem, unsigned grid, hipStream_t s);
+hipError_t cvh_launch_image_sums(const uint8_t *const *planes, int channels, size_t n, unsigned long long *out /* [2 * channels], zeroed */,
+                                 hipStream_t s);   // the ingest's sums of planes already on the device
 hipError_t cvh_launch_io_checkerboard(const CvhIoMember *tab, int nmem, unsigned grid, hipStream_t s);
 hipError_t cvh_launch_io_mask(const CvhIoMember *tab, int nmem, unsigned grid, int invert, hipStream_t s);
 hipError_t cvh_launch_io_image_out3(const CvhIoMember *tab, int nmem, unsigned grid, hipStream_t s);
@@ -298,10 +300,6 @@ hipError_t cvh_launch_pm_store(const double *state, uint8_t *plane, size_t n, hi
 void cvh_pm_grid(int h, int w, int *tiles_x, int *tiles_y);
 
 hipError_t cvh_launch_contour(const double *u, uint8_t *out, int h, int w, hipStream_t s);
-hipError_t cvh_launch_checkerboard(const double *sv, double *u, int h, int w, hipStream_t s);
-hipError_t cvh_launch_image_sums(const uint8_t *const *planes, int channels, size_t n, unsigned long long *out /* [2 * channels], zeroed */,
-                                 hipStream_t s);
-hipError_t cvh_launch_mask(const double *u, uint8_t *mask, size_t n, int invert, hipStream_t s);
 hipError_t cvh_launch_state_narrow(double *u, float *uf, size_t n, hipStream_t s);       // uf = (float)u, u = (double)uf
 hipError_t cvh_launch_state_widen(const float *uf, double *u, size_t n, hipStream_t s);  // u = (double)uf
 hipError_t cvh_launch_ppf(double *data, size_t n, int op, double eps, hipStream_t s);

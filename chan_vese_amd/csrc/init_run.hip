@@ -1,12 +1,11 @@
 // init_run.hip — host side of the device-side initial level sets (include/chanvese_hip.h, "Device-side initial level sets"): the grey
-// histogram, Otsu's threshold and the threshold / rectangle / disk starts of n contexts, on io_run.hip's member tables, stream joins and
-// event ordering (init_kernels.hip).  The single-context calls are batches of one member.  The histogram calls only read the planes;
+// histogram, Otsu's threshold and the threshold / rectangle / disk starts of n contexts, each ONE MemberCall (cvh_host.h, io_run.hip:
+// member table, stream joins, event ordering) around init_kernels.hip's launches.  The single-context calls are batches of one member.  The histogram calls only read the planes;
 // a start is a level set arriving without crossing to the host, as cvh_init_checkerboard_batch's.
 #include "cvh_host.h"
 
 namespace {
 
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) & ~(a - 1); }
 inline int bins_of(const cvh_context *c) { return 255 * c->C + 1; }
 
 // x as a double, rounded to nearest even (what Python's float(int) does).  The top 64 bits convert with one rounding at bit 11; the bits
@@ -74,45 +73,33 @@ int histograms(cvh_context *const *ctxs, int n, std::vector<size_t> *off, const 
   HIPCHK(lead, hipSetDevice(lead->device));
   int rc = settle_all(ctxs, n, what);
   if (rc != CVH_OK) return rc;
+  size_t host_bytes = 0;
+  off->assign((size_t)n, 0);
   for (int i = 0; i < n; ++i) {
     cvh_context *c = ctxs[i];
-    if (c->d_hist) continue;   // the workspace: allocated on the first call, kept with the context
-    const hipError_t e = hipMalloc((void **)&c->d_hist, (size_t)bins_of(c) * sizeof(unsigned));
-    if (e != hipSuccess) {
-      c->d_hist = nullptr;
-      fail(c, CVH_ERR_HIP, "hipMalloc of the histogram workspace: %s", hipGetErrorString(e));
-      return batch_fail(ctxs, n, CVH_ERR_HIP, "%s: member %d: %s", what, i, c->err);
-    }
+    rc = ensure_workspace(c, (void **)&c->d_hist, (size_t)bins_of(c) * sizeof(unsigned), "histogram", false);
+    if (rc != CVH_OK) return batch_fail(ctxs, n, rc, "%s: member %d: %s", what, i, c->err);
+    (*off)[i] = host_bytes;
+    host_bytes += align_up((size_t)bins_of(c) * sizeof(unsigned), 256);
   }
-  const size_t tab_bytes = (size_t)n * sizeof(CvhIoMember);
-  size_t host_bytes = align_up(tab_bytes, 256);
-  off->assign((size_t)n, 0);
-  for (int i = 0; i < n; ++i) { (*off)[i] = host_bytes; host_bytes += align_up((size_t)bins_of(ctxs[i]) * sizeof(unsigned), 256); }
-  rc = stage(lead, host_bytes, tab_bytes);
+  MemberCall call;
+  rc = call.begin(ctxs, n, what, 0, host_bytes);
   if (rc != CVH_OK) return rc;
-  unsigned char *const hb = (unsigned char *)lead->h_io;
-  CvhIoMember *tab = (CvhIoMember *)hb;
-  memset(tab, 0, tab_bytes);
   for (int i = 0; i < n; ++i) {
     const cvh_context *c = ctxs[i];
-    CvhIoMember &m = tab[i];
+    CvhIoMember &m = call.tab[i];
     for (int k = 0; k < c->C; ++k) m.plane[k] = c->d_img[k];
     m.sums = (unsigned long long *)c->d_hist;
-    m.n = c->n; m.h = c->h; m.w = c->w; m.C = c->C;
     m.nblk = cvh_io_blocks(c->n);
+    (*off)[i] += call.host_off;
   }
-  const unsigned grid = lay_out(tab, n);
-  rc = open_call(ctxs, n, nullptr);
-  if (rc != CVH_OK) return rc;
-  HIPCHK(lead, hipMemcpyAsync(lead->io_table.d, tab, tab_bytes, hipMemcpyHostToDevice, lead->stream));
-  for (int i = 0; i < n; ++i) HIPCHK(lead, hipMemsetAsync(ctxs[i]->d_hist, 0, (size_t)bins_of(ctxs[i]) * sizeof(unsigned), lead->stream));
-  HIPCHK(lead, cvh_launch_init_histogram((const CvhIoMember *)lead->io_table.d, n, grid, lead->stream));
-  for (int i = 0; i < n; ++i)
-    HIPCHK(lead, hipMemcpyAsync(hb + (*off)[i], ctxs[i]->d_hist, (size_t)bins_of(ctxs[i]) * sizeof(unsigned), hipMemcpyDeviceToHost, lead->stream));
-  rc = close_call(ctxs, n, nullptr, false);
-  if (rc != CVH_OK) return rc;
-  HIPCHK(lead, hipStreamSynchronize(lead->stream));   // the ONE host wait: the counts
-  return CVH_OK;
+  return call.run(nullptr, false, true, [&]() -> int {   // the ONE host wait: the counts
+    for (int i = 0; i < n; ++i) HIPCHK(lead, hipMemsetAsync(ctxs[i]->d_hist, 0, (size_t)bins_of(ctxs[i]) * sizeof(unsigned), lead->stream));
+    HIPCHK(lead, cvh_launch_init_histogram(call.dtab(), n, call.grid, lead->stream));
+    for (int i = 0; i < n; ++i)
+      HIPCHK(lead, hipMemcpyAsync(call.hb + (*off)[i], ctxs[i]->d_hist, (size_t)bins_of(ctxs[i]) * sizeof(unsigned), hipMemcpyDeviceToHost, lead->stream));
+    return CVH_OK;
+  });
 }
 
 // The starts par[0 .. n-1] of n members (checked by the caller, iterations in flight settled): ONE launch writes every level set into the
@@ -120,36 +107,20 @@ int histograms(cvh_context *const *ctxs, int n, std::vector<size_t> *off, const 
 int starts(cvh_context *const *ctxs, int n, const CvhInitStart *par, const char *what)
 {
   cvh_context *lead = ctxs[0];
-  const size_t par_off = align_up((size_t)n * sizeof(CvhIoMember), 256), bytes = par_off + (size_t)n * sizeof(CvhInitStart);
-  int rc = stage(lead, bytes, bytes);
+  MemberCall call;
+  int rc = call.begin(ctxs, n, what, (size_t)n * sizeof(CvhInitStart));
   if (rc != CVH_OK) return rc;
-  unsigned char *const hb = (unsigned char *)lead->h_io, *const db = (unsigned char *)lead->io_table.d;
-  memset(hb, 0, bytes);
-  CvhIoMember *tab = (CvhIoMember *)hb;
-  memcpy(hb + par_off, par, (size_t)n * sizeof(CvhInitStart));
+  memcpy(call.hb + call.extra_off, par, (size_t)n * sizeof(CvhInitStart));
   for (int i = 0; i < n; ++i) {
-    cvh_context *c = ctxs[i];
-    CvhIoMember &m = tab[i];
+    const cvh_context *c = ctxs[i];
+    CvhIoMember &m = call.tab[i];
     for (int k = 0; k < c->C; ++k) m.plane[k] = c->d_img[k];
-    m.dst = c->d_u[c->chain_pb & 1];   // the buffer whose parity is the chain-mode sum set's: see levelset_arrived
-    m.state_zero = &c->d_state->steps_done;
-    m.chain_zero = &c->d_chain->v[(c->chain_pb + 1) & 3][0];
-    m.n = c->n; m.h = c->h; m.w = c->w; m.C = c->C;
+    levelset_target(c, &m);
     m.nblk = cvh_init_start_blocks(c->n);
   }
-  const unsigned grid = lay_out(tab, n);
-  rc = open_call(ctxs, n, nullptr);
-  if (rc != CVH_OK) return rc;
-  HIPCHK(lead, hipMemcpyAsync(db, hb, bytes, hipMemcpyHostToDevice, lead->stream));
-  HIPCHK(lead, cvh_launch_init_start((const CvhIoMember *)db, (const CvhInitStart *)(db + par_off), n, grid, lead->stream));
-  rc = close_call(ctxs, n, nullptr, false);
-  if (rc != CVH_OK) return rc;
-  HIPCHK(lead, hipStreamSynchronize(lead->stream));
-  for (int i = 0; i < n; ++i) {   // the launch has run, the device's share of a new run (reset_run_impl) inside it
-    rc = levelset_arrived(ctxs[i], true);
-    if (rc != CVH_OK) return batch_fail(ctxs, n, rc, "%s: member %d: %s", what, i, ctxs[i]->err);
-  }
-  return CVH_OK;
+  const CvhInitStart *d_par = (const CvhInitStart *)(call.db + call.extra_off);
+  rc = call.run(nullptr, false, true, [&]() -> int { HIPCHK(lead, cvh_launch_init_start(call.dtab(), d_par, n, call.grid, lead->stream)); return CVH_OK; });
+  return rc != CVH_OK ? rc : call.arrived();
 }
 
 // a start that needs no histogram: settle, then launch

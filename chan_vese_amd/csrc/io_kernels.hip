@@ -1,7 +1,8 @@
 // io_kernels.hip — device-memory input and output of contexts and batches of contexts (gfx950): ingest of uint8 images with their sums,
-// the checkerboard level set, mask / level-set / plane egress.  Batch kernels: ONE grid serves N members, a member owning the workgroups
+// the plane sums of planes already on the device, the checkerboard level set, mask / level-set / plane egress.  Batch kernels: ONE grid serves N members, a member owning the workgroups
 // first .. first + nblk - 1; the member table (CvhIoMember, cvh_internal.h) is read with wave-uniform indices, i.e. through the scalar
-// cache.  The single-context entry points launch the same kernels with a table of one member.
+// cache.  The single-context entry points launch the same kernels with a table of one member; image_sums_kernel alone takes plain
+// arguments (its planes sit on the device: an ingest would only add a copy) and shares the ingest's sums.
 #include "cvh_internal.h"
 
 namespace {
@@ -51,6 +52,10 @@ __device__ __forceinline__ int io_member(const CvhIoMember *tab, int nmem)
   return lo;
 }
 
+// sum p and sum p^2 of a plane: a lane adds its bytes into 32-bit s1 / s2 (add_bytes) and moves them into the 64-bit pair acc[0 .. 1]
+// every kFlushPieces pieces of 16 bytes -- 256 * 16 * 65025 < 2^32 -- and behind its last byte (flush)
+constexpr int kFlushPieces = 256;
+
 __device__ __forceinline__ void add_bytes(const uint4 v, unsigned &s1, unsigned &s2)
 {
   const unsigned wds[4] = {v.x, v.y, v.z, v.w};
@@ -59,6 +64,27 @@ __device__ __forceinline__ void add_bytes(const uint4 v, unsigned &s1, unsigned 
 #pragma unroll
     for (int b = 0; b < 4; ++b) { const unsigned x = (wds[i] >> (8 * b)) & 0xffu; s1 += x; s2 += x * x; }
   }
+}
+
+__device__ __forceinline__ void flush(unsigned long long *acc, unsigned &s1, unsigned &s2)
+{
+  acc[0] += s1; acc[1] += s2; s1 = s2 = 0;
+}
+
+// the lanes' acc[0 .. 2C-1] of a workgroup of CVH_BLOCK are added to out[0 .. 2C-1]: wave reduction, LDS, ONE 64-bit atomic per sum
+// (exact integers: the result does not depend on the grid or the order)
+__device__ __forceinline__ void add_sums(const unsigned long long acc[6], int C, unsigned long long *out)
+{
+  __shared__ unsigned long long sh[4][6];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int s = 0; s < 6; ++s) {
+    unsigned long long v = acc[s];
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    if (lane == 0) sh[wave][s] = v;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < 2 * C) atomicAdd(&out[threadIdx.x], sh[0][threadIdx.x] + sh[1][threadIdx.x] + sh[2][threadIdx.x] + sh[3][threadIdx.x]);
 }
 
 // byte `i` (0 .. 11) of the 12 bytes {a, b, c}
@@ -100,11 +126,10 @@ __device__ __forceinline__ void join3(const uint4 in[3], unsigned out[12])
 }
 
 // Ingest: the caller's uint8 bytes become the member's planes, and sum p / sum p^2 of every plane are added to the member's sums as exact
-// 64-bit integers (what image_sums_kernel produces; integer sums do not depend on the order).  A lane moves 16 pixels per trip; the
-// n % 16 last pixels go byte by byte.  Every source byte is read once.
+// 64-bit integers (image_sums_kernel's, below: the same adds).  A lane moves 16 pixels per trip; the n % 16 last pixels go byte by
+// byte.  Every source byte is read once.
 __global__ void __launch_bounds__(CVH_BLOCK) io_ingest_kernel(const CvhIoMember *tab, int nmem)
 {
-  __shared__ unsigned long long sh[4][6];
   const CvhIoMember *m = tab + io_member(tab, nmem);
   const int C = m->C;
   const size_t n = m->n, pieces = n / 16;
@@ -113,7 +138,7 @@ __global__ void __launch_bounds__(CVH_BLOCK) io_ingest_kernel(const CvhIoMember 
   const gbytes_out plane[3] = {(gbytes_out)m->plane[0], (gbytes_out)m->plane[1], (gbytes_out)m->plane[2]};
   unsigned long long acc[6] = {0, 0, 0, 0, 0, 0};
   if (m->interleaved && C == 3) {   // (wave-uniform: a member's layout)
-    unsigned s1[3] = {0, 0, 0}, s2[3] = {0, 0, 0};   // flushed every 256 pieces: 256 * 16 * 65025 < 2^32
+    unsigned s1[3] = {0, 0, 0}, s2[3] = {0, 0, 0};
     int pending = 0;
     for (size_t q = t0; q < pieces; q += stride) {
       const uint4 a = load16_any(src + 48 * q), b = load16_any(src + 48 * q + 16), c = load16_any(src + 48 * q + 32);
@@ -125,9 +150,9 @@ __global__ void __launch_bounds__(CVH_BLOCK) io_ingest_kernel(const CvhIoMember 
         store16(plane[k], q, out[k]);
         add_bytes(out[k], s1[k], s2[k]);
       }
-      if (++pending == 256) {
+      if (++pending == kFlushPieces) {
 #pragma unroll
-        for (int k = 0; k < 3; ++k) { acc[2 * k] += s1[k]; acc[2 * k + 1] += s2[k]; s1[k] = s2[k] = 0; }
+        for (int k = 0; k < 3; ++k) flush(acc + 2 * k, s1[k], s2[k]);
         pending = 0;
       }
     }
@@ -136,7 +161,7 @@ __global__ void __launch_bounds__(CVH_BLOCK) io_ingest_kernel(const CvhIoMember 
       for (int k = 0; k < 3; ++k) { const unsigned x = src[3 * q + k]; plane[k][q] = (uint8_t)x; s1[k] += x; s2[k] += x * x; }
     }
 #pragma unroll
-    for (int k = 0; k < 3; ++k) { acc[2 * k] += s1[k]; acc[2 * k + 1] += s2[k]; }
+    for (int k = 0; k < 3; ++k) flush(acc + 2 * k, s1[k], s2[k]);
   } else {
     for (int k = 0; k < C; ++k) {
       const gbytes_in s = src + (size_t)k * n;
@@ -147,25 +172,40 @@ __global__ void __launch_bounds__(CVH_BLOCK) io_ingest_kernel(const CvhIoMember 
         const uint4 v = load16_any(s + 16 * q);
         store16(d, q, v);
         add_bytes(v, s1, s2);
-        if (++pending == 256) { acc[2 * k] += s1; acc[2 * k + 1] += s2; s1 = s2 = 0; pending = 0; }
+        if (++pending == kFlushPieces) { flush(acc + 2 * k, s1, s2); pending = 0; }
       }
       for (size_t q = pieces * 16 + t0; q < n; q += stride) { const unsigned x = s[q]; d[q] = (uint8_t)x; s1 += x; s2 += x * x; }
-      acc[2 * k] += s1; acc[2 * k + 1] += s2;
+      flush(acc + 2 * k, s1, s2);
     }
   }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int s = 0; s < 6; ++s) {
-    unsigned long long v = acc[s];
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    if (lane == 0) sh[wave][s] = v;
-  }
-  __syncthreads();
-  if ((int)threadIdx.x < 2 * C) atomicAdd(&m->sums[threadIdx.x], sh[0][threadIdx.x] + sh[1][threadIdx.x] + sh[2][threadIdx.x] + sh[3][threadIdx.x]);
+  add_sums(acc, C, m->sums);
 }
 
-// levelset_checkerboard for N members (checkerboard_kernel's arithmetic, misc_kernels.hip): src = the h row factors, src2 = the w column
-// factors, both from the host's libm; dst = the level set.  A member's first workgroup also clears what a new run clears (reset_run_impl):
+// Per-plane sum(p) and sum(p^2) of planes that already sit on the device (16-byte aligned), as exact 64-bit integers (out[2k],
+// out[2k+1]; zeroed by the caller): the region means' sum(I) and, for one channel, the tol-free stop norm of src/main.cpp:950-959 (every
+// partial sum of the reference's loop is an integer below 2^53 there, so its result does not depend on the order).
+__global__ void __launch_bounds__(CVH_BLOCK) image_sums_kernel(const uint8_t *p0, const uint8_t *p1, const uint8_t *p2, int C, size_t n,
+                                                               unsigned long long *out)
+{
+  const gbytes_in pl[3] = {(gbytes_in)p0, (gbytes_in)p1, (gbytes_in)p2};
+  unsigned long long acc[6] = {0, 0, 0, 0, 0, 0};
+  const size_t pieces = n / 16, stride = (size_t)gridDim.x * CVH_BLOCK, t0 = (size_t)blockIdx.x * CVH_BLOCK + threadIdx.x;
+  for (int k = 0; k < C; ++k) {
+    unsigned s1 = 0, s2 = 0;
+    int pending = 0;
+    for (size_t q = t0; q < pieces; q += stride) {
+      add_bytes(load16(pl[k], q), s1, s2);
+      if (++pending == kFlushPieces) { flush(acc + 2 * k, s1, s2); pending = 0; }
+    }
+    for (size_t q = pieces * 16 + t0; q < n; q += stride) { const unsigned x = pl[k][q]; s1 += x; s2 += x * x; }
+    flush(acc + 2 * k, s1, s2);
+  }
+  add_sums(acc, C, out);
+}
+
+// levelset_checkerboard, src/main.cpp:226-231: sign(sin(pi i/5) * sin(pi j/5)), for N members.  src = the h row factors, src2 = the w
+// column factors, both from the host's libm (checkerboard_factors); the product is ONE IEEE multiplication, so the device reproduces
+// cvh_levelset_checkerboard_host bit for bit without 8 bytes per pixel crossing PCIe.  dst = the level set.  A member's first workgroup also clears what a new run clears (reset_run_impl):
 // the four run words of its state block and the chain-mode sum set behind the current one.
 __global__ void __launch_bounds__(CVH_BLOCK) io_checkerboard_kernel(const CvhIoMember *tab, int nmem)
 {
@@ -188,7 +228,7 @@ __global__ void __launch_bounds__(CVH_BLOCK) io_checkerboard_kernel(const CvhIoM
 
 __device__ __forceinline__ unsigned mask_bit(double u, int invert) { return (((float)u > 0.0f) ? 1u : 0u) ^ (unsigned)invert; }
 
-// mask = ((float)u > 0), optionally inverted (src/main.cpp:395-400), N members: a lane reads 16 doubles (two 64-byte row pieces) and writes
+// mask = ((float)u > 0), optionally inverted (src/main.cpp:395-400), N members -- the one mask kernel, cvh_get_mask's too: a lane reads 16 doubles (two 64-byte row pieces) and writes
 // 16 bytes to the caller's buffer (any alignment)
 __global__ void __launch_bounds__(CVH_BLOCK) io_mask_kernel(const CvhIoMember *tab, int nmem, int invert)
 {
@@ -258,6 +298,14 @@ unsigned cvh_io_checkerboard_blocks(int h, int w)
 hipError_t cvh_launch_io_ingest(const CvhIoMember *tab, int nmem, unsigned grid, hipStream_t s)
 {
   hipLaunchKernelGGL(io_ingest_kernel, dim3(grid), dim3(CVH_BLOCK), 0, s, tab, nmem);
+  return hipGetLastError();
+}
+
+hipError_t cvh_launch_image_sums(const uint8_t *const *planes, int channels, size_t n, unsigned long long *out, hipStream_t s)
+{
+  const size_t b = (n / 16 + 1 + CVH_BLOCK - 1) / CVH_BLOCK;
+  hipLaunchKernelGGL(image_sums_kernel, dim3((unsigned)(b > 1024 ? 1024 : b)), dim3(CVH_BLOCK), 0, s, planes[0], channels > 1 ? planes[1] : nullptr,
+                     channels > 2 ? planes[2] : nullptr, channels, n, out);
   return hipGetLastError();
 }
 

@@ -1,16 +1,13 @@
 // io_run.hip — host side of the device-memory entry points (include/chanvese_hip.h): contexts and batches of contexts are fed from, and
 // read into, device memory the caller owns, ordered against the caller's stream by events; one launch per batch and operation.
 // The single-context calls are batches of one member: one code path.  Reinitialisation (cvh_reinit, cvh_reinit_batch) lives here too: it
-// is a level set leaving and arriving without crossing to the host, on the same member tables and stream joins.
+// is a level set leaving and arriving without crossing to the host, on the same member tables and stream joins.  MemberCall (cvh_host.h)
+// is the scaffold of every member-table call, here and in init_run.hip and components_run.hip: staging, the level-set target, the
+// joined launch, the members' arrival.  cvh_init_checkerboard is a checkerboard batch of one.
+#include <memory>
 #include <thread>
 
 #include "cvh_host.h"
-
-namespace {
-
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) & ~(a - 1); }
-
-}  // namespace
 
 // p must be memory that kernels on member i's device can address: device memory of that device, managed memory, or mapped host memory
 int pointer_check(cvh_context *const *ctxs, int n, int i, const void *p, const char *what)
@@ -39,7 +36,7 @@ int settle_all(cvh_context *const *ctxs, int n, const char *what)
 // The leader's staging of a call: `host_bytes` of pinned memory (its first `dev_bytes` are uploaded to the device table).  The pinned
 // block is rewritten only when the last copy that read it has completed: the HOST WAITS here for the previous table-using call led by
 // this context (ev_io_out, recorded behind that call's launch) -- long past unless that call is still queued behind the caller's stream.
-int stage(cvh_context *lead, size_t host_bytes, size_t dev_bytes)
+static int stage(cvh_context *lead, size_t host_bytes, size_t dev_bytes)
 {
   HIPCHK(lead, hipEventSynchronize(lead->ev_io_out));
   if (lead->h_io_cap < host_bytes) {
@@ -80,6 +77,56 @@ unsigned lay_out(CvhIoMember *tab, int n)
   return first;
 }
 
+int MemberCall::begin(cvh_context *const *ctxs_, int n_, const char *what_, size_t extra_dev, size_t extra_host, bool two_tables)
+{
+  ctxs = ctxs_; n = n_; what = what_; lead = ctxs[0];
+  const size_t tab_bytes = (size_t)n * sizeof(CvhIoMember), tab_pitch = align_up(tab_bytes, 256);
+  extra_off = two_tables ? 2 * tab_pitch : tab_pitch;
+  dev_bytes = two_tables || extra_dev ? extra_off + extra_dev : tab_bytes;
+  host_off = align_up(dev_bytes, 256);
+  const int rc = stage(lead, extra_host ? host_off + extra_host : dev_bytes, dev_bytes);
+  if (rc != CVH_OK) return rc;
+  hb = (unsigned char *)lead->h_io; db = (unsigned char *)lead->io_table.d;
+  memset(hb, 0, dev_bytes);
+  tab = (CvhIoMember *)hb;
+  tab2 = two_tables ? (CvhIoMember *)(hb + tab_pitch) : nullptr;
+  for (CvhIoMember *t : {tab, tab2})
+    for (int i = 0; t && i < n; ++i) { t[i].n = ctxs[i]->n; t[i].h = ctxs[i]->h; t[i].w = ctxs[i]->w; t[i].C = ctxs[i]->C; }
+  return CVH_OK;
+}
+
+int MemberCall::arrived(const int *which) const
+{
+  for (int i = 0; i < n; ++i) {
+    if (which && !which[i]) continue;
+    const int rc = levelset_arrived(ctxs[i], true);
+    if (rc != CVH_OK) return batch_fail(ctxs, n, rc, "%s: member %d: %s", what, i, ctxs[i]->err);
+  }
+  return CVH_OK;
+}
+
+// A member receives a fresh level set: it lands in the buffer cvh_set_levelset writes -- the one whose parity is the chain-mode sum
+// set's, see levelset_arrived -- and the member's first workgroup clears the device's share of a new run (reset_run_impl): the four run
+// words of the state block and the sum set behind the run's own.
+void levelset_target(const cvh_context *c, CvhIoMember *m)
+{
+  m->dst = c->d_u[c->chain_pb & 1];
+  m->state_zero = &c->d_state->steps_done;
+  m->chain_zero = &c->d_chain->v[(c->chain_pb + 1) & 3][0];
+}
+
+// *slot, a workspace of `bytes` that c allocates on first use and keeps; with mirror, the FP64 mirror of an FP32 state is refreshed first
+// (the class of a float is the class of its double)
+int ensure_workspace(cvh_context *c, void **slot, size_t bytes, const char *name, bool mirror)
+{
+  if (mirror) { const int rc = ensure_f64_mirror(c); if (rc != CVH_OK) return rc; }
+  if (*slot) return CVH_OK;
+  const hipError_t e = hipMalloc(slot, bytes);
+  if (e == hipSuccess) return CVH_OK;
+  *slot = nullptr;
+  return fail(c, CVH_ERR_HIP, "hipMalloc of the %s workspace: %s", name, hipGetErrorString(e));
+}
+
 namespace {
 
 int ingest(cvh_context *const *ctxs, int n, const uint8_t *const *d_imgs, int layout, void *stream, const char *what)
@@ -95,53 +142,47 @@ int ingest(cvh_context *const *ctxs, int n, const uint8_t *const *d_imgs, int la
   rc = settle_all(ctxs, n, what);
   if (rc != CVH_OK) return rc;
   // staging: [member table][8 sums per member, zero] uploaded; behind them the planes of the members whose stop norm the host takes
-  const size_t sums_off = align_up((size_t)n * sizeof(CvhIoMember), 256), dev_bytes = sums_off + (size_t)n * 8 * sizeof(unsigned long long);
-  std::vector<size_t> fetch_off((size_t)n, 0);
-  size_t host_bytes = dev_bytes;
+  const size_t sums_bytes = (size_t)n * 8 * sizeof(unsigned long long);
+  std::vector<int> on_host;
+  std::vector<size_t> fetch_off((size_t)n, 0);   // inside the host-only part
+  size_t fetch_bytes = 0;
   for (int i = 0; i < n; ++i) {
     const cvh_context *c = ctxs[i];
     if (stop_norm_exact_on_device(c)) continue;
-    fetch_off[i] = host_bytes = align_up(host_bytes, 256);
-    host_bytes += c->img_stride * c->C;
+    fetch_off[i] = fetch_bytes = align_up(fetch_bytes, 256);
+    fetch_bytes += c->img_stride * c->C;
+    on_host.push_back(i);
   }
-  rc = stage(lead, host_bytes, dev_bytes);
+  MemberCall call;
+  rc = call.begin(ctxs, n, what, sums_bytes, fetch_bytes);
   if (rc != CVH_OK) return rc;
-  unsigned char *const hb = (unsigned char *)lead->h_io, *const db = (unsigned char *)lead->io_table.d;
-  memset(hb, 0, dev_bytes);
-  CvhIoMember *tab = (CvhIoMember *)hb;
+  unsigned char *const fetched = call.hb + call.host_off;
+  const unsigned long long *sums = (const unsigned long long *)(call.hb + call.extra_off);
   for (int i = 0; i < n; ++i) {
     const cvh_context *c = ctxs[i];
-    CvhIoMember &m = tab[i];
+    CvhIoMember &m = call.tab[i];
     m.src = d_imgs[i];
     for (int k = 0; k < c->C; ++k) m.plane[k] = c->d_img[k];
-    m.sums = (unsigned long long *)(db + sums_off) + (size_t)8 * i;
-    m.n = c->n; m.h = c->h; m.w = c->w; m.C = c->C;
+    m.sums = (unsigned long long *)(call.db + call.extra_off) + (size_t)8 * i;
     m.interleaved = layout == CVH_LAYOUT_INTERLEAVED;
     m.nblk = cvh_io_blocks(c->n);
   }
-  const unsigned grid = lay_out(tab, n);
-  rc = open_call(ctxs, n, stream);
+  rc = call.run(stream, false, true, [&]() -> int {   // the ONE host wait of the call: the sums come back to host fields
+    HIPCHK(lead, cvh_launch_io_ingest(call.dtab(), n, call.grid, lead->stream));
+    HIPCHK(lead, hipMemcpyAsync((void *)sums, call.db + call.extra_off, sums_bytes, hipMemcpyDeviceToHost, lead->stream));
+    for (int i : on_host) {
+      const cvh_context *c = ctxs[i];
+      HIPCHK(lead, hipMemcpyAsync(fetched + fetch_off[i], c->d_img_slab, c->img_stride * (c->C - 1) + c->n, hipMemcpyDeviceToHost, lead->stream));
+    }
+    return CVH_OK;
+  });
   if (rc != CVH_OK) return rc;
-  HIPCHK(lead, hipMemcpyAsync(db, hb, dev_bytes, hipMemcpyHostToDevice, lead->stream));
-  HIPCHK(lead, cvh_launch_io_ingest((const CvhIoMember *)db, n, grid, lead->stream));
-  HIPCHK(lead, hipMemcpyAsync(hb + sums_off, db + sums_off, (size_t)n * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, lead->stream));
-  std::vector<int> on_host;
-  for (int i = 0; i < n; ++i) {
-    if (!fetch_off[i]) continue;
-    const cvh_context *c = ctxs[i];
-    HIPCHK(lead, hipMemcpyAsync(hb + fetch_off[i], c->d_img_slab, c->img_stride * (c->C - 1) + c->n, hipMemcpyDeviceToHost, lead->stream));
-    on_host.push_back(i);
-  }
-  rc = close_call(ctxs, n, stream, false);
-  if (rc != CVH_OK) return rc;
-  HIPCHK(lead, hipStreamSynchronize(lead->stream));   // the ONE host wait of the call: the sums come back to host fields
-  const unsigned long long *sums = (const unsigned long long *)(hb + sums_off);
   // three channels: (sum_k I_k)/3 is rounded per pixel and the reference adds the squares serially (stop_norm_host); members in parallel
   std::vector<double> norm((size_t)n, 0.0);
   auto host_norm = [&](int i) {
     const cvh_context *c = ctxs[i];
     std::vector<const uint8_t *> pl;
-    for (int k = 0; k < c->C; ++k) pl.push_back(hb + fetch_off[i] + (size_t)k * c->img_stride);
+    for (int k = 0; k < c->C; ++k) pl.push_back(fetched + fetch_off[i] + (size_t)k * c->img_stride);
     norm[i] = stop_norm_host(pl, c->n);
   };
   const int nthreads = (int)std::min<size_t>(16, on_host.size());
@@ -159,7 +200,7 @@ int ingest(cvh_context *const *ctxs, int n, const uint8_t *const *d_imgs, int la
   } else {
     for (int i : on_host) host_norm(i);
   }
-  for (int i = 0; i < n; ++i) plane_sums_arrived(ctxs[i], sums + 8 * i, fetch_off[i] ? &norm[i] : nullptr);
+  for (int i = 0; i < n; ++i) plane_sums_arrived(ctxs[i], sums + 8 * i, stop_norm_exact_on_device(ctxs[i]) ? nullptr : &norm[i]);
   return CVH_OK;
 }
 
@@ -181,24 +222,16 @@ int mask_out(cvh_context *const *ctxs, int n, uint8_t *const *d_masks, int inver
     rc = ensure_f64_mirror(ctxs[i]);
     if (rc != CVH_OK) return batch_fail(ctxs, n, rc, "%s: member %d: %s", what, i, ctxs[i]->err);
   }
-  const size_t bytes = (size_t)n * sizeof(CvhIoMember);
-  rc = stage(lead, bytes, bytes);
+  MemberCall call;
+  rc = call.begin(ctxs, n, what);
   if (rc != CVH_OK) return rc;
-  CvhIoMember *tab = (CvhIoMember *)lead->h_io;
-  memset(tab, 0, bytes);
   for (int i = 0; i < n; ++i) {
     const cvh_context *c = ctxs[i];
-    tab[i].src = c->d_u[current_buffer(c)];
-    tab[i].dst = d_masks[i];
-    tab[i].n = c->n; tab[i].h = c->h; tab[i].w = c->w; tab[i].C = c->C;
-    tab[i].nblk = cvh_io_blocks(c->n);
+    call.tab[i].src = c->d_u[current_buffer(c)];
+    call.tab[i].dst = d_masks[i];
+    call.tab[i].nblk = cvh_io_blocks(c->n);
   }
-  const unsigned grid = lay_out(tab, n);
-  rc = open_call(ctxs, n, stream);
-  if (rc != CVH_OK) return rc;
-  HIPCHK(lead, hipMemcpyAsync(lead->io_table.d, tab, bytes, hipMemcpyHostToDevice, lead->stream));
-  HIPCHK(lead, cvh_launch_io_mask((const CvhIoMember *)lead->io_table.d, n, grid, invert, lead->stream));
-  return close_call(ctxs, n, stream, true);
+  return call.run(stream, true, false, [&]() -> int { HIPCHK(lead, cvh_launch_io_mask(call.dtab(), n, call.grid, invert, lead->stream)); return CVH_OK; });
 }
 
 namespace {
@@ -245,12 +278,11 @@ static int checkerboard_batch(cvh_context *const *ctxs, int n, const char *what)
   HIPCHK(lead, hipSetDevice(lead->device));
   rc = settle_all(ctxs, n, what);
   if (rc != CVH_OK) return rc;
-  // the h + w sine factors of every distinct shape, from the host's libm as cvh_init_checkerboard's: ONE copy with the member table
-  const double pi = 3.14159265358979323846;
+  // the h + w sine factors of every distinct shape, from the host's libm: ONE copy with the member table
   std::vector<int> shape_of((size_t)n);
-  std::vector<size_t> shape_off;
+  std::vector<size_t> shape_off;   // inside the extra part
   std::vector<int> shape_first;
-  size_t bytes = align_up((size_t)n * sizeof(CvhIoMember), 256);
+  size_t bytes = 0;
   for (int i = 0; i < n; ++i) {
     size_t s = 0;
     while (s < shape_first.size() && !(ctxs[shape_first[s]]->h == ctxs[i]->h && ctxs[shape_first[s]]->w == ctxs[i]->w)) ++s;
@@ -261,41 +293,28 @@ static int checkerboard_batch(cvh_context *const *ctxs, int n, const char *what)
     }
     shape_of[i] = (int)s;
   }
-  rc = stage(lead, bytes, bytes);
+  MemberCall call;
+  rc = call.begin(ctxs, n, what, bytes);
   if (rc != CVH_OK) return rc;
-  unsigned char *const hb = (unsigned char *)lead->h_io, *const db = (unsigned char *)lead->io_table.d;
-  memset(hb, 0, (size_t)n * sizeof(CvhIoMember));
-  for (size_t s = 0; s < shape_first.size(); ++s) {
-    const cvh_context *c = ctxs[shape_first[s]];
-    double *sv = (double *)(hb + shape_off[s]);
-    for (int i = 0; i < c->h; ++i) sv[i] = sin(pi * i / 5);
-    for (int j = 0; j < c->w; ++j) sv[(size_t)c->h + j] = sin(pi * j / 5);
-  }
-  CvhIoMember *tab = (CvhIoMember *)hb;
+  for (size_t s = 0; s < shape_first.size(); ++s)
+    checkerboard_factors(ctxs[shape_first[s]]->h, ctxs[shape_first[s]]->w, (double *)(call.hb + call.extra_off + shape_off[s]));
   for (int i = 0; i < n; ++i) {
-    cvh_context *c = ctxs[i];
-    CvhIoMember &m = tab[i];
-    m.src = db + shape_off[shape_of[i]];
+    const cvh_context *c = ctxs[i];
+    CvhIoMember &m = call.tab[i];
+    m.src = call.db + call.extra_off + shape_off[shape_of[i]];
     m.src2 = (const double *)m.src + c->h;
-    m.dst = c->d_u[c->chain_pb & 1];   // the buffer whose parity is the chain-mode sum set's: see levelset_arrived
-    m.state_zero = &c->d_state->steps_done;
-    m.chain_zero = &c->d_chain->v[(c->chain_pb + 1) & 3][0];
-    m.n = c->n; m.h = c->h; m.w = c->w; m.C = c->C;
+    levelset_target(c, &m);
     m.nblk = cvh_io_checkerboard_blocks(c->h, c->w);
   }
-  const unsigned grid = lay_out(tab, n);
-  rc = open_call(ctxs, n, nullptr);
-  if (rc != CVH_OK) return rc;
-  HIPCHK(lead, hipMemcpyAsync(db, hb, bytes, hipMemcpyHostToDevice, lead->stream));
-  HIPCHK(lead, cvh_launch_io_checkerboard((const CvhIoMember *)db, n, grid, lead->stream));
-  rc = close_call(ctxs, n, nullptr, false);
-  if (rc != CVH_OK) return rc;
-  HIPCHK(lead, hipStreamSynchronize(lead->stream));
-  for (int i = 0; i < n; ++i) {   // the launch has run, the device's share of a new run (reset_run_impl) inside it
-    rc = levelset_arrived(ctxs[i], true);
-    if (rc != CVH_OK) return batch_fail(ctxs, n, rc, "%s: member %d: %s", what, i, ctxs[i]->err);
-  }
-  return CVH_OK;
+  rc = call.run(nullptr, false, true, [&]() -> int { HIPCHK(lead, cvh_launch_io_checkerboard(call.dtab(), n, call.grid, lead->stream)); return CVH_OK; });
+  return rc != CVH_OK ? rc : call.arrived();
+}
+
+extern "C" int cvh_init_checkerboard(cvh_context *c)
+{
+  if (!c) return CVH_ERR_ARG;
+  static const char what[] = "cvh_init_checkerboard";
+  return guarded(&c, 1, what, [&]() { return checkerboard_batch(&c, 1, what); });
 }
 
 extern "C" int cvh_init_checkerboard_batch(cvh_context *const *ctxs, int n)
@@ -314,26 +333,19 @@ extern "C" int cvh_get_image_device(cvh_context *c, uint8_t *d_img, int layout, 
   int rc = pointer_check(&c, 1, 0, d_img, what);
   if (rc != CVH_OK) return rc;
   if (!c->have_image) return fail(c, CVH_ERR_STATE, "%s: no image set", what);
-  const bool kernel = layout == CVH_LAYOUT_INTERLEAVED && c->C == 3;
-  if (kernel) {
-    rc = stage(c, sizeof(CvhIoMember), sizeof(CvhIoMember));
+  if (layout == CVH_LAYOUT_INTERLEAVED && c->C == 3) {
+    MemberCall call;
+    rc = call.begin(&c, 1, what);
     if (rc != CVH_OK) return rc;
+    call.tab->dst = d_img;
+    for (int k = 0; k < 3; ++k) call.tab->plane[k] = c->d_img[k];
+    call.tab->nblk = cvh_io_blocks(c->n);
+    return call.run(stream, true, false, [&]() -> int { HIPCHK(c, cvh_launch_io_image_out3(call.dtab(), 1, call.grid, c->stream)); return CVH_OK; });
   }
   rc = open_call(&c, 1, stream);
   if (rc != CVH_OK) return rc;
-  if (kernel) {
-    CvhIoMember *m = (CvhIoMember *)c->h_io;
-    memset(m, 0, sizeof(*m));
-    m->dst = d_img;
-    for (int k = 0; k < 3; ++k) m->plane[k] = c->d_img[k];
-    m->n = c->n; m->h = c->h; m->w = c->w; m->C = 3;
-    m->nblk = cvh_io_blocks(c->n);
-    HIPCHK(c, hipMemcpyAsync(c->io_table.d, m, sizeof(*m), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, cvh_launch_io_image_out3((const CvhIoMember *)c->io_table.d, 1, m->nblk, c->stream));
-  } else {
-    for (int k = 0; k < c->C; ++k)
-      HIPCHK(c, hipMemcpyAsync(d_img + (size_t)k * c->n, c->d_img[k], c->n, hipMemcpyDeviceToDevice, c->stream));
-  }
+  for (int k = 0; k < c->C; ++k)
+    HIPCHK(c, hipMemcpyAsync(d_img + (size_t)k * c->n, c->d_img[k], c->n, hipMemcpyDeviceToDevice, c->stream));
   return close_call(&c, 1, stream, true);
 }
 
@@ -402,60 +414,42 @@ static int reinit_batch(cvh_context *const *ctxs, int n, int *changed, const cha
   if (rc != CVH_OK) return rc;
   for (int i = 0; i < n; ++i) {
     cvh_context *c = ctxs[i];
-    rc = ensure_f64_mirror(c);   // "state" = 32: the class of a float is the class of its double
-    if (rc == CVH_OK && !c->d_reinit) {   // the workspace: allocated on the first call, kept with the context
-      const hipError_t e = hipMalloc(&c->d_reinit, cvh_reinit_workspace_bytes(c->h, c->w));
-      if (e != hipSuccess) { c->d_reinit = nullptr; rc = fail(c, CVH_ERR_HIP, "hipMalloc of the reinitialisation workspace: %s", hipGetErrorString(e)); }
-    }
+    rc = ensure_workspace(c, &c->d_reinit, cvh_reinit_workspace_bytes(c->h, c->w), "reinitialisation");
     if (rc != CVH_OK) return batch_fail(ctxs, n, rc, "%s: member %d: %s", what, i, c->err);
   }
   // staging: [column-pass table][row-pass table][one flag word per member, zero]
-  const size_t tab_bytes = align_up((size_t)n * sizeof(CvhIoMember), 256), flags_off = 2 * tab_bytes;
-  const size_t bytes = flags_off + (size_t)n * sizeof(unsigned long long);
-  rc = stage(lead, bytes, bytes);
+  const size_t flag_bytes = (size_t)n * sizeof(unsigned long long);
+  MemberCall call;
+  rc = call.begin(ctxs, n, what, flag_bytes, 0, true);
   if (rc != CVH_OK) return rc;
-  unsigned char *const hb = (unsigned char *)lead->h_io, *const db = (unsigned char *)lead->io_table.d;
-  memset(hb, 0, bytes);
-  CvhIoMember *cols = (CvhIoMember *)hb, *rows = (CvhIoMember *)(hb + tab_bytes);
+  const unsigned long long *flags = (const unsigned long long *)(call.hb + call.extra_off);
   int max_w = 0;
   for (int i = 0; i < n; ++i) {
     cvh_context *c = ctxs[i];
-    CvhIoMember &m = cols[i];
+    CvhIoMember &m = call.tab[i];
     m.src = c->d_u[current_buffer(c)];
-    m.dst = c->d_u[c->chain_pb & 1];   // where cvh_set_levelset puts a level set: see levelset_arrived
+    levelset_target(c, &m);
     m.plane[0] = (uint8_t *)c->d_reinit;
     m.plane[1] = (uint8_t *)c->d_reinit + cvh_reinit_bits_bytes(c->h, c->w);
-    m.sums = (unsigned long long *)(db + flags_off) + i;
-    m.state_zero = &c->d_state->steps_done;
-    m.chain_zero = &c->d_chain->v[(c->chain_pb + 1) & 3][0];
-    m.n = c->n; m.h = c->h; m.w = c->w; m.C = c->C;
-    rows[i] = m;
+    m.sums = (unsigned long long *)(call.db + call.extra_off) + i;
+    call.tab2[i] = m;
     m.nblk = cvh_reinit_column_blocks(c->h, c->w);
-    rows[i].nblk = cvh_reinit_row_blocks(c->h);
+    call.tab2[i].nblk = cvh_reinit_row_blocks(c->h);
     max_w = std::max(max_w, c->w);
   }
-  const unsigned col_grid = lay_out(cols, n), row_grid = lay_out(rows, n);
-  rc = open_call(ctxs, n, nullptr);
+  rc = call.run(nullptr, false, true, [&]() -> int {   // the ONE host wait of the call: which members changed
+    HIPCHK(lead, cvh_launch_reinit(call.dtab(), call.grid, call.dtab2(), call.grid2, n, max_w, lead->stream));
+    ++g_reinit_launch_sets;
+    HIPCHK(lead, hipMemcpyAsync((void *)flags, call.db + call.extra_off, flag_bytes, hipMemcpyDeviceToHost, lead->stream));
+    HIPCHK(lead, hipEventRecord(lead->ev1, lead->stream));
+    return CVH_OK;
+  }, lead->ev0);   // (ev0 is free: settle closed any timed run)
   if (rc != CVH_OK) return rc;
-  HIPCHK(lead, hipEventRecord(lead->ev0, lead->stream));   // (free: settle closed any timed run)
-  HIPCHK(lead, hipMemcpyAsync(db, hb, bytes, hipMemcpyHostToDevice, lead->stream));
-  HIPCHK(lead, cvh_launch_reinit((const CvhIoMember *)db, col_grid, (const CvhIoMember *)(db + tab_bytes), row_grid, n, max_w, lead->stream));
-  ++g_reinit_launch_sets;
-  HIPCHK(lead, hipMemcpyAsync(hb + flags_off, db + flags_off, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost, lead->stream));
-  HIPCHK(lead, hipEventRecord(lead->ev1, lead->stream));
-  rc = close_call(ctxs, n, nullptr, false);
-  if (rc != CVH_OK) return rc;
-  HIPCHK(lead, hipStreamSynchronize(lead->stream));   // the ONE host wait of the call: which members changed
   HIPCHK(lead, hipEventElapsedTime(&lead->last_reinit_ms, lead->ev0, lead->ev1));
-  const unsigned long long *flags = (const unsigned long long *)(hb + flags_off);
-  for (int i = 0; i < n; ++i) {
-    const bool moved = (flags[i] & 3) == 3;
-    if (changed) changed[i] = moved ? 1 : 0;
-    if (!moved) continue;
-    rc = levelset_arrived(ctxs[i], true);
-    if (rc != CVH_OK) return batch_fail(ctxs, n, rc, "%s: member %d: %s", what, i, ctxs[i]->err);
-  }
-  return CVH_OK;
+  std::unique_ptr<int[]> own;
+  if (!changed) { own.reset(new int[n]); changed = own.get(); }
+  for (int i = 0; i < n; ++i) changed[i] = (flags[i] & 3) == 3 ? 1 : 0;
+  return call.arrived(changed);
 }
 
 extern "C" int cvh_reinit_batch(cvh_context *const *ctxs, int n, int *changed)

@@ -165,7 +165,8 @@ int cvh_get_levelset(cvh_context *ctx, double *u);
 /* levelset_checkerboard, src/main.cpp:221-233.  The h + w sine factors are evaluated on the HOST
  * with libm sin (the sign on every fifth row/column is rounding noise that only the host libm
  * reproduces) and uploaded; the sign of their product — one IEEE multiplication — is taken on the
- * device, bit-identical to cvh_levelset_checkerboard_host without 8 bytes per pixel over PCIe. */
+ * device, bit-identical to cvh_levelset_checkerboard_host without 8 bytes per pixel over PCIe.
+ * cvh_init_checkerboard_batch of this one context: one launch, one host wait. */
 int cvh_init_checkerboard(cvh_context *ctx);
 /* Host-only helper with the same arithmetic, for callers that keep u themselves. */
 void cvh_levelset_checkerboard_host(int h, int w, double *u);
@@ -238,7 +239,9 @@ int cvh_get_trace(cvh_context *ctx, double *out, int max_rows, int *rows);
 /* tol * || (sum_k I_k)/C ||_2, src/main.cpp:950-959 (valid after set_image). */
 int cvh_get_stop_condition(cvh_context *ctx, double *stop_cond);
 
-/* mask = ((float)u > 0), optionally 1 - mask: src/main.cpp:395-400. */
+/* mask = ((float)u > 0), optionally 1 - mask: src/main.cpp:395-400.  cvh_get_mask_device of the context's own buffer, then copied
+ * down: iterations enqueued and never synchronised are settled first, as every device-memory getter and cvh_get_mask_clean do (the mask
+ * is that of the level set behind them; a later cvh_sync reports them as done). */
 int cvh_get_mask(cvh_context *ctx, uint8_t *mask, int invert);
 /* Contour map of the reference's video frame, VideoWriterManager::draw_contour
  * src/VideoWriterManager.cpp:60-74: 1 where a frame pixel is painted in the contour colour.
