@@ -33,6 +33,7 @@ EXPORTS = [
     "cvh_components", "cvh_components_batch", "cvh_get_mask_clean", "cvh_get_mask_clean_device", "cvh_get_mask_clean_device_batch",
     "cvh_histogram", "cvh_histogram_batch", "cvh_otsu_from_histogram", "cvh_otsu_threshold", "cvh_init_threshold", "cvh_init_threshold_batch",
     "cvh_init_otsu", "cvh_init_otsu_batch", "cvh_init_rect", "cvh_init_rect_batch", "cvh_init_disk", "cvh_init_disk_batch",
+    "cvh_restrict_image", "cvh_restrict_image_batch", "cvh_prolong_levelset", "cvh_prolong_levelset_batch",
 ]
 # struct cvh_component: row k - 1 of a component table describes label k (first = smallest flat index; the box is inclusive)
 COMPONENT_DTYPE = np.dtype([("first", np.uint32), ("area", np.uint32), ("x0", np.int32), ("y0", np.int32), ("x1", np.int32), ("y1", np.int32)])
@@ -130,6 +131,10 @@ def lib():
         "cvh_init_rect_batch": (C.c_int, [C.POINTER(vp), C.c_int, ip, C.c_double, C.c_double]),
         "cvh_init_disk": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double]),
         "cvh_init_disk_batch": (C.c_int, [C.POINTER(vp), C.c_int, ip, C.c_double, C.c_double]),
+        "cvh_restrict_image": (C.c_int, [vp, vp]),
+        "cvh_restrict_image_batch": (C.c_int, [C.POINTER(vp), C.POINTER(vp), C.c_int]),
+        "cvh_prolong_levelset": (C.c_int, [vp, vp]),
+        "cvh_prolong_levelset_batch": (C.c_int, [C.POINTER(vp), C.POINTER(vp), C.c_int]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -356,6 +361,89 @@ def init_disk_batch(contexts, cxcyr, inside=1.0, outside=0.0):
     _batch_chk(lib().cvh_init_disk_batch(_member_array(contexts), n, _int_rows(cxcyr, n, 3, "cxcyr"), float(inside), float(outside)))
 
 
+def pyramid_shapes(h, w, levels):
+    """The shapes of a pyramid of `levels` levels over an h x w plane, finest first: [(h, w), ((h + 1) // 2, (w + 1) // 2), ...].
+    ValueError when levels < 1 or when the coarsest side would fall below 16.  Calls nothing in the library."""
+    if levels < 1:
+        raise ValueError(f"levels must be >= 1, got {levels}")
+    shapes = [(int(h), int(w))]
+    for _ in range(levels - 1):
+        shapes.append(((shapes[-1][0] + 1) // 2, (shapes[-1][1] + 1) // 2))
+    if min(shapes[-1]) < 16:
+        raise ValueError(f"{levels} levels over {h} x {w} end at {shapes[-1][0]} x {shapes[-1][1]}: the coarsest side must not fall below 16")
+    return shapes
+
+
+def _pairs(a, b):
+    a, b = list(a), list(b)
+    if len(a) != len(b):
+        raise ValueError(f"{len(a)} and {len(b)} contexts do not pair up")
+    return a, b
+
+
+def restrict_image_batch(fines, coarses):
+    """cvh_restrict_image_batch: Context.restrict_image_to for n pairs (any mix of shapes and channel counts) with one launch."""
+    fines, coarses = _pairs(fines, coarses)
+    _batch_chk(lib().cvh_restrict_image_batch(_member_array(fines), _member_array(coarses), len(fines)))
+
+
+def prolong_levelset_batch(coarses, fines):
+    """cvh_prolong_levelset_batch: Context.prolong_levelset_to for n pairs (any mix of shapes and channel counts) with one launch."""
+    coarses, fines = _pairs(coarses, fines)
+    _batch_chk(lib().cvh_prolong_levelset_batch(_member_array(coarses), _member_array(fines), len(coarses)))
+
+
+def _coarse_to_fine(pyramids, max_steps, run):
+    """The pyramids (each a list of contexts, finest first, all of one depth) advance level by level: run(contexts of a level, max_steps)
+    -> [(steps, norm)].  Returns [[(steps, norm)] finest first] per pyramid."""
+    pyramids = [list(p) for p in pyramids]
+    depth = len(pyramids[0]) if pyramids else 0
+    if depth < 1 or any(len(p) != depth for p in pyramids):
+        raise ValueError("every pyramid needs the same number of levels, at least one")
+    before = [p[0].co_resident for p in pyramids]
+    for p in pyramids:   # the levels of a pyramid never stream beside each other
+        for ctx in p:
+            ctx.set_option("co_resident", 0)
+    out = [[None] * depth for _ in pyramids]
+    try:
+        for k in range(depth - 1):
+            restrict_image_batch([p[k] for p in pyramids], [p[k + 1] for p in pyramids])
+        for k in range(depth - 1, -1, -1):
+            level = [p[k] for p in pyramids]
+            if k < depth - 1:
+                prolong_levelset_batch([p[k + 1] for p in pyramids], level)
+            for ctx, was in zip(level, before):
+                ctx.set_option("co_resident", was if k == 0 else 1)
+            for i, res in enumerate(run(level, max_steps)):
+                out[i][k] = res
+            if k:
+                for ctx in level:
+                    ctx.set_option("co_resident", 0)
+    finally:   # (a failed call: the finest level still gets its value back, the helper levels theirs of 0)
+        for p, was in zip(pyramids, before):
+            p[0].set_option("co_resident", was)
+            for ctx in p[1:]:
+                ctx.set_option("co_resident", 0)
+    return out
+
+
+def run_coarse_to_fine(levels, max_steps=-1):
+    """A coarse-to-fine run of one pyramid.  levels: contexts finest first, shaped as pyramid_shapes gives them; the finest holds the image,
+    the coarsest the caller's start (any init_* or set_levelset: planes do not touch a level set, so a start that needs the coarsest planes
+    -- threshold, Otsu -- is built after restrict_image_to down the chain, which this call repeats).  Sequence: restrict down the chain,
+    Context.run on the coarsest, prolong, run the next level, ... -- max_steps applies per level.  Returns [(steps, norm)], finest first.
+    Every level keeps its OWN parameters and options: nothing is rescaled between levels.  While a level runs, the other levels have
+    "co_resident" = 0, so each level makes the automatic choices it makes alone on the device; on return the finest has the value it had
+    before and the helper levels stay 0."""
+    return _coarse_to_fine([levels], max_steps, lambda cs, k: [cs[0].run(k)])[0]
+
+
+def run_coarse_to_fine_batch(pyramids, max_steps=-1):
+    """run_coarse_to_fine over N pyramids of one depth (a list of lists, each finest first): every level of all pyramids is restricted,
+    prolonged (one launch each) and advanced with run_batch together.  Returns [[(steps, norm)] finest first] per pyramid."""
+    return _coarse_to_fine(pyramids, max_steps, run_batch)
+
+
 def _segmented(contexts, max_steps, every, run):
     """run(contexts, k) -> [(steps, norm)] in segments of `every` iterations with a reinit_batch of the members still iterating between
     segments; a member whose stop rule fired inside a segment leaves for the later ones.  every <= 0: one run(contexts, max_steps)."""
@@ -399,6 +487,7 @@ class Context:
         self._L = lib()
         self._h = C.c_void_p(None)
         self.h, self.w, self.channels = h, w, channels
+        self.co_resident = 1   # the option's value, kept for the pyramid drivers (the library has no getter)
         p = params if params is not None else make_params()
         rc = self._L.cvh_create(C.byref(self._h), h, w, channels, C.byref(p), device)
         if rc != CVH_OK:
@@ -431,6 +520,8 @@ class Context:
 
     def set_option(self, key, value):
         self._chk(self._L.cvh_set_option(self._h, key.encode(), int(value)))
+        if key == "co_resident":
+            self.co_resident = int(value != 0)
 
     def _plane_array(self, planes):
         assert len(planes) == self.channels
@@ -505,6 +596,16 @@ class Context:
     def init_disk(self, cx, cy, r, inside=1.0, outside=0.0):
         """cvh_init_disk: u = inside on the filled disk (col - cx)^2 + (row - cy)^2 <= r^2, outside elsewhere, on the device."""
         self._chk(self._L.cvh_init_disk(self._h, int(cx), int(cy), int(r), float(inside), float(outside)))
+
+    def restrict_image_to(self, coarse):
+        """cvh_restrict_image: the planes of this context, averaged 2 x 2 in integers, become the image of `coarse` (a context of
+        ((h + 1) // 2, (w + 1) // 2) and the same channel count), exactly as its set_image of those bytes; this context is only read."""
+        _batch_chk(self._L.cvh_restrict_image(self._h, coarse._h))
+
+    def prolong_levelset_to(self, fine):
+        """cvh_prolong_levelset: the level set of this context, replicated 2 x 2 bit for bit, becomes the level set of `fine`, exactly
+        as its set_levelset of those doubles (a new run begins there); this context is only read."""
+        _batch_chk(self._L.cvh_prolong_levelset(self._h, fine._h))
 
     def reinit(self):
         """cvh_reinit: the level set becomes the exact signed distance to the pixel-edge front of its own mask, on the device.

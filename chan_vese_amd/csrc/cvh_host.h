@@ -1,7 +1,7 @@
 // cvh_host.h -- private header of the library's host units: the context, the launch geometries and the helpers more than one unit calls.
 // api.hip (lifecycle, options, host-buffer I/O, getters, the transitions of a context's run state), csv_run.hip (CSV steps of one
 // context), csv_batch.hip (fused batch, and what every batch shares), pm_run.hip (Perona-Malik), io_run.hip (device-memory I/O),
-// init_run.hip (device-side initial level sets), debug_exports.hip (diagnostics).  Kernel sources do not include it.
+// init_run.hip (device-side initial level sets), pyramid_run.hip (coarse-to-fine), debug_exports.hip (diagnostics).  Kernel sources do not include it.
 #pragma once
 #include <limits.h>
 #include <math.h>
@@ -231,6 +231,9 @@ void free_table(DeviceTable *t);
 // io_run.hip: launch sets (three kernels for all members) of cvh_reinit / cvh_reinit_batch so far in this process (debug_exports.hip)
 extern std::atomic<unsigned long> g_reinit_launch_sets;
 
+// pyramid_run.hip: launches of cvh_restrict_image* / cvh_prolong_levelset* so far in this process (debug_exports.hip)
+extern std::atomic<unsigned long> g_pyramid_launches;
+
 // io_run.hip: what every call on device memory or on a member table shares (the comments are at the definitions)
 int pointer_check(cvh_context *const *ctxs, int n, int i, const void *p, const char *what);
 int settle_all(cvh_context *const *ctxs, int n, const char *what);
@@ -284,6 +287,23 @@ struct MemberCall {
     if (wait) HIPCHK(lead, hipStreamSynchronize(lead->stream));
     return CVH_OK;
   }
+};
+
+// The plane sums of a call whose launch has written the planes of members 0 .. n-1 (an ingest, a restrict), as cvh_set_image takes them:
+// 8 integers per member in the call's device extra (zeroed with it; the kernel adds {sum p, sum p^2} per plane), and for the members whose
+// stop norm the host takes (three channels) the planes themselves, fetched into the call's host-only part.  plan() before
+// MemberCall::begin(.., sums_bytes, fetch_bytes); fetch() inside run()'s launches, behind the kernel; arrive() behind the call's wait.
+struct PlaneSums {
+  cvh_context *const *ctxs = nullptr;
+  int n = 0;
+  size_t sums_bytes = 0, fetch_bytes = 0;
+  std::vector<int> on_host;
+  std::vector<size_t> fetch_off;
+
+  void plan(cvh_context *const *ctxs_, int n_);
+  unsigned long long *device_sums(const MemberCall &call, int i) const { return (unsigned long long *)(call.db + call.extra_off) + (size_t)8 * i; }
+  int fetch(const MemberCall &call);
+  void arrive(const MemberCall &call);
 };
 
 // cvh_get_mask / cvh_get_mask_clean: into_d_mask() writes c->d_mask (allocated on first use) on c's stream; the bytes come down, one wait

@@ -218,6 +218,8 @@ struct CvhIoMember {
   int h, w, C;
   int interleaved;                    // ingest: the source is h * w * C interleaved bytes (planar otherwise)
   unsigned first, nblk;               // workgroups first .. first + nblk - 1 of the grid are this member's (first ascending, member 0 at 0)
+  int h2, w2;                         // restrict: the fine grid the member's planes (h x w) are averaged from, src its first plane
+  unsigned long long src_stride;      // restrict: bytes between the planes of the fine context
 };
 
 // ---- launchers (csv_kernels.hip / pm_kernels.hip / misc_kernels.hip / io_kernels.hip) ----
@@ -261,6 +263,13 @@ struct CvhInitStart { double inside, outside; long long a, b, c, d; int mode, pa
 unsigned cvh_init_start_blocks(size_t n);
 hipError_t cvh_launch_init_histogram(const CvhIoMember *tab, int nmem, unsigned grid, hipStream_t s);
 hipError_t cvh_launch_init_start(const CvhIoMember *tab, const CvhInitStart *par, int nmem, unsigned grid, hipStream_t s);
+// coarse-to-fine (pyramid_kernels.hip).  Restrict: plane[] the coarse member's planes (written), src / src_stride / h2 / w2 the fine
+// planes, sums as the ingest's.  Prolong: src the coarse level set ((h + 1) / 2 x (w + 1) / 2 doubles), dst the fine one (h x w),
+// state_zero / chain_zero as the checkerboard's.
+unsigned cvh_restrict_blocks(int fine_h, int fine_w);
+unsigned cvh_prolong_blocks(int fine_h, int fine_w);
+hipError_t cvh_launch_restrict(const CvhIoMember *tab, int nmem, unsigned grid, hipStream_t s);
+hipError_t cvh_launch_prolong(const CvhIoMember *tab, int nmem, unsigned grid, hipStream_t s);
 // rows-per-tile options of the step kernel
 void cvh_step_grid(int h, int w, int tile_rows, int *tiles_x, int *tiles_y);
 int cvh_step_max_blocks(int h, int w);

@@ -87,6 +87,7 @@ extern "C" int cvh_debug_num_cus(cvh_context *c, int *out)
 // Diagnostic (not part of include/chanvese_hip.h): launch sets of cvh_reinit / cvh_reinit_batch so far in this process -- one set is the
 // three kernels of reinit_kernels.hip over all members of the call (tests/test_gpu_reinit.py: a batch of n is one set, not n).
 extern "C" unsigned long cvh_debug_reinit_launch_sets(void) { return g_reinit_launch_sets.load(); }
+extern "C" unsigned long cvh_debug_pyramid_launches(void) { return g_pyramid_launches.load(); }
 
 // Diagnostic (not part of include/chanvese_hip.h): device time (HIP events on the leader's stream: table copy, the three launches, flag
 // copy) of the last cvh_reinit / cvh_reinit_batch this context led (tools/reinit_probe.py).

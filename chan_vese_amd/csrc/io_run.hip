@@ -127,25 +127,13 @@ int ensure_workspace(cvh_context *c, void **slot, size_t bytes, const char *name
   return fail(c, CVH_ERR_HIP, "hipMalloc of the %s workspace: %s", name, hipGetErrorString(e));
 }
 
-namespace {
-
-int ingest(cvh_context *const *ctxs, int n, const uint8_t *const *d_imgs, int layout, void *stream, const char *what)
+// The members' planes were written by the call's launch; its sums come back as the ingest's do (PlaneSums, cvh_host.h)
+void PlaneSums::plan(cvh_context *const *ctxs_, int n_)
 {
-  int rc = members_check(ctxs, n, what, kMembersListed);
-  if (rc != CVH_OK) return rc;
-  if (!d_imgs) return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: the list of device pointers is NULL", what);
-  if (layout != CVH_LAYOUT_PLANAR && layout != CVH_LAYOUT_INTERLEAVED)
-    return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: layout must be CVH_LAYOUT_PLANAR (0) or CVH_LAYOUT_INTERLEAVED (1), got %d", what, layout);
-  cvh_context *lead = ctxs[0];
-  HIPCHK(lead, hipSetDevice(lead->device));
-  for (int i = 0; i < n; ++i) { rc = pointer_check(ctxs, n, i, d_imgs[i], what); if (rc != CVH_OK) return rc; }
-  rc = settle_all(ctxs, n, what);
-  if (rc != CVH_OK) return rc;
-  // staging: [member table][8 sums per member, zero] uploaded; behind them the planes of the members whose stop norm the host takes
-  const size_t sums_bytes = (size_t)n * 8 * sizeof(unsigned long long);
-  std::vector<int> on_host;
-  std::vector<size_t> fetch_off((size_t)n, 0);   // inside the host-only part
-  size_t fetch_bytes = 0;
+  ctxs = ctxs_; n = n_;
+  sums_bytes = (size_t)n * 8 * sizeof(unsigned long long);
+  fetch_off.assign((size_t)n, 0);   // inside the host-only part
+  fetch_bytes = 0;
   for (int i = 0; i < n; ++i) {
     const cvh_context *c = ctxs[i];
     if (stop_norm_exact_on_device(c)) continue;
@@ -153,30 +141,23 @@ int ingest(cvh_context *const *ctxs, int n, const uint8_t *const *d_imgs, int la
     fetch_bytes += c->img_stride * c->C;
     on_host.push_back(i);
   }
-  MemberCall call;
-  rc = call.begin(ctxs, n, what, sums_bytes, fetch_bytes);
-  if (rc != CVH_OK) return rc;
-  unsigned char *const fetched = call.hb + call.host_off;
-  const unsigned long long *sums = (const unsigned long long *)(call.hb + call.extra_off);
-  for (int i = 0; i < n; ++i) {
+}
+
+int PlaneSums::fetch(const MemberCall &call)
+{
+  cvh_context *lead = call.lead;
+  HIPCHK(lead, hipMemcpyAsync(call.hb + call.extra_off, call.db + call.extra_off, sums_bytes, hipMemcpyDeviceToHost, lead->stream));
+  for (int i : on_host) {
     const cvh_context *c = ctxs[i];
-    CvhIoMember &m = call.tab[i];
-    m.src = d_imgs[i];
-    for (int k = 0; k < c->C; ++k) m.plane[k] = c->d_img[k];
-    m.sums = (unsigned long long *)(call.db + call.extra_off) + (size_t)8 * i;
-    m.interleaved = layout == CVH_LAYOUT_INTERLEAVED;
-    m.nblk = cvh_io_blocks(c->n);
+    HIPCHK(lead, hipMemcpyAsync(call.hb + call.host_off + fetch_off[i], c->d_img_slab, c->img_stride * (c->C - 1) + c->n, hipMemcpyDeviceToHost, lead->stream));
   }
-  rc = call.run(stream, false, true, [&]() -> int {   // the ONE host wait of the call: the sums come back to host fields
-    HIPCHK(lead, cvh_launch_io_ingest(call.dtab(), n, call.grid, lead->stream));
-    HIPCHK(lead, hipMemcpyAsync((void *)sums, call.db + call.extra_off, sums_bytes, hipMemcpyDeviceToHost, lead->stream));
-    for (int i : on_host) {
-      const cvh_context *c = ctxs[i];
-      HIPCHK(lead, hipMemcpyAsync(fetched + fetch_off[i], c->d_img_slab, c->img_stride * (c->C - 1) + c->n, hipMemcpyDeviceToHost, lead->stream));
-    }
-    return CVH_OK;
-  });
-  if (rc != CVH_OK) return rc;
+  return CVH_OK;
+}
+
+void PlaneSums::arrive(const MemberCall &call)
+{
+  const unsigned char *const fetched = call.hb + call.host_off;
+  const unsigned long long *sums = (const unsigned long long *)(call.hb + call.extra_off);
   // three channels: (sum_k I_k)/3 is rounded per pixel and the reference adds the squares serially (stop_norm_host); members in parallel
   std::vector<double> norm((size_t)n, 0.0);
   auto host_norm = [&](int i) {
@@ -201,6 +182,43 @@ int ingest(cvh_context *const *ctxs, int n, const uint8_t *const *d_imgs, int la
     for (int i : on_host) host_norm(i);
   }
   for (int i = 0; i < n; ++i) plane_sums_arrived(ctxs[i], sums + 8 * i, stop_norm_exact_on_device(ctxs[i]) ? nullptr : &norm[i]);
+}
+
+namespace {
+
+int ingest(cvh_context *const *ctxs, int n, const uint8_t *const *d_imgs, int layout, void *stream, const char *what)
+{
+  int rc = members_check(ctxs, n, what, kMembersListed);
+  if (rc != CVH_OK) return rc;
+  if (!d_imgs) return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: the list of device pointers is NULL", what);
+  if (layout != CVH_LAYOUT_PLANAR && layout != CVH_LAYOUT_INTERLEAVED)
+    return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: layout must be CVH_LAYOUT_PLANAR (0) or CVH_LAYOUT_INTERLEAVED (1), got %d", what, layout);
+  cvh_context *lead = ctxs[0];
+  HIPCHK(lead, hipSetDevice(lead->device));
+  for (int i = 0; i < n; ++i) { rc = pointer_check(ctxs, n, i, d_imgs[i], what); if (rc != CVH_OK) return rc; }
+  rc = settle_all(ctxs, n, what);
+  if (rc != CVH_OK) return rc;
+  // staging: [member table][8 sums per member, zero] uploaded; behind them the planes of the members whose stop norm the host takes
+  PlaneSums back;
+  back.plan(ctxs, n);
+  MemberCall call;
+  rc = call.begin(ctxs, n, what, back.sums_bytes, back.fetch_bytes);
+  if (rc != CVH_OK) return rc;
+  for (int i = 0; i < n; ++i) {
+    const cvh_context *c = ctxs[i];
+    CvhIoMember &m = call.tab[i];
+    m.src = d_imgs[i];
+    for (int k = 0; k < c->C; ++k) m.plane[k] = c->d_img[k];
+    m.sums = back.device_sums(call, i);
+    m.interleaved = layout == CVH_LAYOUT_INTERLEAVED;
+    m.nblk = cvh_io_blocks(c->n);
+  }
+  rc = call.run(stream, false, true, [&]() -> int {   // the ONE host wait of the call: the sums come back to host fields
+    HIPCHK(lead, cvh_launch_io_ingest(call.dtab(), n, call.grid, lead->stream));
+    return back.fetch(call);
+  });
+  if (rc != CVH_OK) return rc;
+  back.arrive(call);
   return CVH_OK;
 }
 

@@ -18,7 +18,12 @@
 // --line-color, one frame for t = 0 and one after every iteration, :926-931,:997); the overlay
 // text of -O is not rendered (no font rasteriser here), --fps has nothing to act on.
 // Additions that do not collide with reference options: --dump-u, --dump-mask, --device, --math,
-// --state, --rect, --circ, --disk, --init, --threshold, --reinit, --connectivity, --min-area, --fill-holes, --largest, --roi, --verbose.
+// --state, --rect, --circ, --disk, --init, --threshold, --reinit, --connectivity, --min-area, --fill-holes, --largest, --roi, --verbose,
+// --levels.  --levels L > 1 is a coarse-to-fine run (chanvese_hip.h, "Coarse-to-fine"): L contexts, each half the one before; after -S
+// the planes are restricted down the chain, the start is built on the COARSEST level (the numbers of --rect / --disk, given in pixels of
+// the input, shifted right by L - 1; --init otsu / --threshold on the coarsest planes), and every level runs to its own stop (-N per
+// level) before its level set is prolonged to the next.  Every level has the same parameters; nothing is rescaled.  --state 32 applies to
+// the levels that qualify for it.  All outputs and the -V frames (the first one: the finest level's start) come from the finest level.
 #include <algorithm>
 #include <cctype>
 #include <cerrno>
@@ -172,7 +177,7 @@ const Spec kSpecs[] = {
     {"invert-selection", 'I', 0}, {"select", 's', 0}, {"rectangle", 'R', 0}, {"circle", 'C', 0},
     // additions of this build
     {"dump-u", 0, 1}, {"dump-mask", 0, 1}, {"device", 0, 1}, {"math", 0, 1}, {"state", 0, 1}, {"rect", 0, 1}, {"circ", 0, 1}, {"reinit", 0, 1},
-    {"disk", 0, 1}, {"init", 0, 1}, {"threshold", 0, 1},
+    {"disk", 0, 1}, {"init", 0, 1}, {"threshold", 0, 1}, {"levels", 0, 1},
     {"connectivity", 0, 1}, {"min-area", 0, 1}, {"fill-holes", 0, 1}, {"largest", 0, 0}, {"roi", 0, 0},
     {"verbose", 0, 0}};
 
@@ -324,6 +329,8 @@ void print_help()
       "  --largest                          keep only the largest component of the mask\n"
       "                                     (with any of these four, _selection and --dump-mask use the cleaned mask)\n"
       "  --roi                              print 'roi x0 y0 x1 y1 area' of that mask's largest component to stdout\n"
+      "  --levels arg (=1)                  coarse-to-fine run over arg levels, each half the one before: the start is built and iterated\n"
+      "                                     on the coarsest level, then handed up level by level (-N counts per level); not with --circ, --reinit\n"
       "  --verbose                          print the iteration count and last norm to stderr\n"
       "\n";
 }
@@ -384,6 +391,8 @@ int main(int argc, char **argv)
   if (auto v = one("disk")) disk = *v;
   if (auto v = one("init")) init_kind = *v;
   if (auto v = one("threshold")) threshold = to_int("threshold", *v);
+  int levels = 1;
+  if (auto v = one("levels")) levels = to_int("levels", *v);
   segment = vm.count("segment"); grayscale = vm.count("grayscale"); write_video = vm.count("video");
   overlay_text = vm.count("overlay-text"); invert = vm.count("invert-selection");
   object_selection = vm.count("select"); rectangle_contour = vm.count("rectangle"); circle_contour = vm.count("circle");
@@ -455,6 +464,9 @@ int main(int argc, char **argv)
   if (min_area < 0) msg_exit("Minimum component area cannot be negative: " + std::to_string(min_area) + ".");
   if (fill_holes < -1) msg_exit("Largest hole to fill must be -1 (any size), zero or positive: " + std::to_string(fill_holes) + ".");
   if (reinit_every > 0 && write_video) msg_exit("Reinitialisation (--reinit) cannot be combined with video output (-V).");
+  if (levels < 1) msg_exit("Number of levels must be at least 1: " + std::to_string(levels) + ".");
+  if (levels > 1 && reinit_every > 0) msg_exit("Reinitialisation (--reinit) cannot be combined with a coarse-to-fine run (--levels).");
+  if (levels > 1 && !circ.empty()) msg_exit("A circular outline (--circ) cannot be combined with a coarse-to-fine run (--levels); use --disk.");
 
   // ---- read the image: src/main.cpp:877-887 (8-bit gray or BGR)
   Image file;
@@ -494,29 +506,49 @@ int main(int argc, char **argv)
   prm.mu = mu; prm.nu = nu; prm.dt = dt; prm.eps = eps; prm.tol = tol;
   for (int k = 0; k < nof_channels; ++k) { prm.lambda1[k] = lambda1[k]; prm.lambda2[k] = lambda2[k]; }
 
+  std::vector<std::pair<int, int>> level_shape{{h, w}};   // finest first
+  for (int k = 1; k < levels; ++k) level_shape.push_back({(level_shape.back().first + 1) / 2, (level_shape.back().second + 1) / 2});
+  if (std::min(level_shape.back().first, level_shape.back().second) < 16 && levels > 1)
+    msg_exit("Too many levels for a " + std::to_string(h) + " x " + std::to_string(w) + " image: the coarsest side must not fall below 16.");
+
   cvh_context *ctx = nullptr;
   if (cvh_create(&ctx, h, w, nof_channels, &prm, device) != CVH_OK)
     msg_exit(std::string("Error: cannot initialise the HIP backend: ") + cvh_last_error(nullptr));
   cvh_check(ctx, cvh_set_option(ctx, "math_mode", math == "strict" ? CVH_MATH_STRICT : CVH_MATH_FAST), "math_mode");
   if (state_bits == 32) cvh_check(ctx, cvh_set_option(ctx, "state", 32), "state");   // declared FP32-state mode: never the default
+  std::vector<cvh_context *> level{ctx};   // the helper levels of a coarse-to-fine run: idle while another level runs ("co_resident")
+  for (int k = 1; k < levels; ++k) {
+    cvh_context *c = nullptr;
+    if (cvh_create(&c, level_shape[k].first, level_shape[k].second, nof_channels, &prm, device) != CVH_OK)
+      msg_exit(std::string("Error: cannot initialise the HIP backend: ") + cvh_last_error(nullptr));
+    cvh_check(c, cvh_set_option(c, "math_mode", math == "strict" ? CVH_MATH_STRICT : CVH_MATH_FAST), "math_mode");
+    if (state_bits == 32) (void)cvh_set_option(c, "state", 32);   // (a level too narrow for it keeps 64)
+    cvh_check(c, cvh_set_option(c, "co_resident", 0), "co_resident");
+    level.push_back(c);
+  }
+  cvh_context *const coarsest = level.back();
+  const int shift = levels - 1;
   {
     std::vector<const uint8_t *> pp;
     for (auto &p : planes) pp.push_back(p.data());
     cvh_check(ctx, cvh_set_image(ctx, pp.data()), "cvh_set_image");
   }
 
-  // ---- level set: src/main.cpp:898-923
-  if (!rect.empty()) {
-    int rx, ry, rw, rh;
-    if (std::sscanf(rect.c_str(), "%d,%d,%d,%d", &rx, &ry, &rw, &rh) != 4 || rw <= 0 || rh <= 0)
-      msg_exit("You must specify the contour with non-zero dimensions");
-    cvh_check(ctx, cvh_init_rect(ctx, rx, ry, rw, rh, 1.0, 0.0), "cvh_init_rect");   // src/InteractiveDataRect.cpp:24-25, on the device
-  } else if (!disk.empty()) {
-    cvh_check(ctx, cvh_init_disk(ctx, disk_cx, disk_cy, disk_r, 1.0, 0.0), "cvh_init_disk");   // (parsed with the other options' validation)
-  } else if (init_otsu) {
-    cvh_check(ctx, cvh_init_otsu(ctx, nullptr, 1.0, -1.0), "cvh_init_otsu");
-  } else if (init_threshold) {
-    cvh_check(ctx, cvh_init_threshold(ctx, threshold, 1.0, -1.0), "cvh_init_threshold");
+  // ---- level set: src/main.cpp:898-923.  A coarse-to-fine run builds it on the coarsest level, from planes that are restricted only
+  // after Perona-Malik: not here but through the same lambda below
+  int rx = 0, ry = 0, rw = 0, rh = 0;
+  if (!rect.empty() && (std::sscanf(rect.c_str(), "%d,%d,%d,%d", &rx, &ry, &rw, &rh) != 4 || rw <= 0 || rh <= 0))
+    msg_exit("You must specify the contour with non-zero dimensions");
+  auto device_start = [&](cvh_context *c, int sh) {   // the starts built on the device, their numbers shifted right by sh
+    if (!rect.empty()) cvh_check(c, cvh_init_rect(c, rx >> sh, ry >> sh, rw >> sh, rh >> sh, 1.0, 0.0), "cvh_init_rect");   // src/InteractiveDataRect.cpp:24-25
+    else if (!disk.empty()) cvh_check(c, cvh_init_disk(c, disk_cx >> sh, disk_cy >> sh, disk_r >> sh, 1.0, 0.0), "cvh_init_disk");
+    else if (init_otsu) cvh_check(c, cvh_init_otsu(c, nullptr, 1.0, -1.0), "cvh_init_otsu");
+    else if (init_threshold) cvh_check(c, cvh_init_threshold(c, threshold, 1.0, -1.0), "cvh_init_threshold");
+    else cvh_check(c, cvh_init_checkerboard(c), "cvh_init_checkerboard");
+  };
+  if (levels > 1) {
+  } else if (!rect.empty() || !disk.empty() || init_otsu || init_threshold) {
+    device_start(ctx, 0);
   } else if (!circ.empty()) {
     int cx, cy, cr;
     if (std::sscanf(circ.c_str(), "%d,%d,%d", &cx, &cy, &cr) != 3 || cr <= 0)  // is_ok(): radius > 0
@@ -567,7 +599,7 @@ int main(int argc, char **argv)
   };
   if (write_video) {
     if (mkdir(frames_dir.c_str(), 0777) != 0 && errno != EEXIST) msg_exit("Error: cannot create \"" + frames_dir + "\"");
-    write_frame("t = 0");   // :930
+    if (levels == 1) write_frame("t = 0");   // :930
   }
 
   // ---- Perona-Malik: src/main.cpp:940-947
@@ -584,14 +616,44 @@ int main(int argc, char **argv)
     if (!write_image(add_suffix(input_filename, "pm"), h, w, nof_channels, out.data()))
       msg_exit("Error: cannot write \"" + add_suffix(input_filename, "pm") + "\"");
     // a start taken from the image is taken again from the smoothed planes (the one above served the t = 0 frame)
-    if (init_otsu) cvh_check(ctx, cvh_init_otsu(ctx, nullptr, 1.0, -1.0), "cvh_init_otsu");
+    if (levels > 1) {}
+    else if (init_otsu) cvh_check(ctx, cvh_init_otsu(ctx, nullptr, 1.0, -1.0), "cvh_init_otsu");
     else if (init_threshold) cvh_check(ctx, cvh_init_threshold(ctx, threshold, 1.0, -1.0), "cvh_init_threshold");
   }
 
   // ---- timestep loop: src/main.cpp:950-1001 (stop condition and every iteration on the GPU)
   int steps_done = 0;
   double last_norm = 0;
-  if (reinit_every > 0) {
+  std::vector<int> level_steps((size_t)levels, 0);
+  auto run_with_frames = [&]() {   // one iteration per frame; the frame is saved before the stop test (:997-1000)
+    for (int t = 1; t <= max_steps; ++t) {
+      int stopped = 0;
+      cvh_check(ctx, cvh_enqueue_steps(ctx, 1), "cvh_enqueue_steps");
+      cvh_check(ctx, cvh_sync(ctx, &steps_done, &last_norm, &stopped), "cvh_sync");
+      write_frame("t = " + std::to_string(t));   // :997
+      if (stopped) break;
+    }
+  };
+  if (levels > 1) {
+    // restrict down the chain, start on the coarsest level, then level by level: run, prolong.  While a level runs the others do not
+    // count in its automatic choices ("co_resident"); the finest keeps its own value throughout
+    for (int k = 0; k + 1 < levels; ++k) cvh_check(level[k + 1], cvh_restrict_image(level[k], level[k + 1]), "cvh_restrict_image");
+    device_start(coarsest, shift);
+    for (int k = levels - 1; k >= 0; --k) {
+      if (k + 1 < levels) cvh_check(level[k], cvh_prolong_levelset(level[k + 1], level[k]), "cvh_prolong_levelset");
+      if (k > 0) {
+        cvh_check(level[k], cvh_set_option(level[k], "co_resident", 1), "co_resident");
+        cvh_check(level[k], cvh_run(level[k], max_steps, &level_steps[k], nullptr), "cvh_run");
+        cvh_check(level[k], cvh_set_option(level[k], "co_resident", 0), "co_resident");
+      } else if (!write_video) {
+        cvh_check(ctx, cvh_run(ctx, max_steps, &steps_done, &last_norm), "cvh_run");
+      } else {
+        write_frame("t = 0");
+        run_with_frames();
+      }
+    }
+    level_steps[0] = steps_done;
+  } else if (reinit_every > 0) {
     // segments of reinit_every iterations, the level set re-distanced between them; a stop inside a segment ends the run
     for (int left = max_steps; left > 0;) {
       const int k = std::min(reinit_every, left);
@@ -606,14 +668,7 @@ int main(int argc, char **argv)
   } else if (!write_video) {
     cvh_check(ctx, cvh_run(ctx, max_steps, &steps_done, &last_norm), "cvh_run");
   } else {
-    // one iteration per frame; the frame is saved before the stop test (:997-1000)
-    for (int t = 1; t <= max_steps; ++t) {
-      int stopped = 0;
-      cvh_check(ctx, cvh_enqueue_steps(ctx, 1), "cvh_enqueue_steps");
-      cvh_check(ctx, cvh_sync(ctx, &steps_done, &last_norm, &stopped), "cvh_sync");
-      write_frame("t = " + std::to_string(t));   // :997
-      if (stopped) break;
-    }
+    run_with_frames();
   }
 
   if (!dump_u.empty()) {
@@ -663,6 +718,11 @@ int main(int argc, char **argv)
   }
   if (vm.count("verbose"))  // the reference prints nothing
     std::fprintf(stderr, "chan_vese: %d iterations, last ||u_diff|| = %.17g\n", steps_done, last_norm);
-  cvh_destroy(ctx);
+  if (vm.count("verbose") && levels > 1) {
+    std::fprintf(stderr, "chan_vese: iterations per level, finest first:");
+    for (int s : level_steps) std::fprintf(stderr, " %d", s);
+    std::fprintf(stderr, "\n");
+  }
+  for (int k = levels - 1; k >= 0; --k) cvh_destroy(level[k]);
   return EXIT_SUCCESS;
 }

@@ -101,35 +101,64 @@ def check_init(init, n, channels=1):
     return kind, rows
 
 
+def check_levels(levels, h, w):
+    """Validates Segmenter's `levels` and returns the pyramid's shapes, finest first (capi.pyramid_shapes).  ValueError for anything but
+    an int >= 1 whose coarsest side stays at 16 or above.  Calls nothing in the library."""
+    if not isinstance(levels, int) or isinstance(levels, bool):
+        raise ValueError(f"levels must be an int, got {levels!r}")
+    return capi.pyramid_shapes(h, w, levels)
+
+
+def scale_init(kind, rows, levels):
+    """The numbers of a ("rect", ..) / ("disk", ..) start, given in finest pixels, on the coarsest of `levels` levels: every number is
+    shifted right by levels - 1 (an arithmetic shift: negative coordinates round down).  Other kinds pass through."""
+    if kind not in ("rect", "disk") or levels == 1:
+        return rows
+    return [tuple(v >> (levels - 1) for v in r) for r in rows]
+
+
 def _check_device(t, device, name):
     if t.device.type != "cuda" or (t.device.index or 0) != device:
         raise ValueError(f"{name} lives on {t.device}, the contexts on cuda:{device}")
 
 
 class Segmenter:
-    """N contexts of one shape on one GPU, kept for the object's lifetime (cvh_create allocates: a stream of frames reuses them)."""
+    """N contexts of one shape on one GPU, kept for the object's lifetime (cvh_create allocates: a stream of frames reuses them).
+    levels = L > 1 makes every member a pyramid of L contexts (capi.pyramid_shapes; N x L contexts in all, `pyramids[i]` finest first,
+    `contexts` the finest ones) and segment() a coarse-to-fine run; every level takes `params` and `options` as given, nothing is
+    rescaled.  levels = 1 is the plain path, call for call."""
+    levels = 1
 
-    def __init__(self, n, h, w, channels=1, params=None, device=0, options=None):
+    def __init__(self, n, h, w, channels=1, params=None, device=0, options=None, levels=1):
         if n < 1:
             raise ValueError(f"n must be >= 1, got {n}")
-        self.n, self.h, self.w, self.channels = n, h, w, channels
+        shapes = check_levels(levels, h, w)
+        self.n, self.h, self.w, self.channels, self.levels = n, h, w, channels, levels
         self.device = _device_index(device)
         self.thresholds = None   # Otsu's thresholds of the last segment(init="otsu")
+        self.level_steps = None  # levels > 1: the iterations of the last segment() per member and level, finest first
         self.contexts = []
+        self.pyramids = []
         try:
             for _ in range(n):
-                ctx = capi.Context(h, w, channels, params, self.device)
-                self.contexts.append(ctx)
-                for key, value in (options or {}).items():
-                    ctx.set_option(key, value)
+                self.pyramids.append([])
+                for k, (lh, lw) in enumerate(shapes):
+                    ctx = capi.Context(lh, lw, channels, params, self.device)
+                    self.pyramids[-1].append(ctx)
+                    if k == 0:
+                        self.contexts.append(ctx)
+                    for key, value in (options or {}).items():
+                        ctx.set_option(key, value)
         except Exception:
             self.close()
             raise
 
     def close(self):
-        for ctx in self.contexts:
-            ctx.close()
+        for pyr in self.pyramids:
+            for ctx in pyr:
+                ctx.close()
         self.contexts = []
+        self.pyramids = []
 
     def __enter__(self):
         return self
@@ -149,8 +178,18 @@ class Segmenter:
         init: "checkerboard"; a float64 / float32 tensor (N, H, W); or a start built on the device from the (smoothed) planes or from
         numbers -- "otsu" (+1 above Otsu's threshold of the grey values, -1 elsewhere; self.thresholds then holds the N thresholds),
         ("threshold", t), ("rect", (x, y, w, h)) and ("disk", (cx, cy, r)) (1 inside, 0 outside), the tuple's value one entry for all
-        members or a list of N (check_init).  A text or tuple `init` is validated first, before the images; a tensor `init` after them."""
+        members or a list of N (check_init).  A text or tuple `init` is validated first, before the images; a tensor `init` after them.
+        levels > 1: ingest -> (Perona-Malik batch on the finest level) -> restrict batches downwards -> the start on the COARSEST level ->
+        per level run_batch and a prolong batch (capi.run_coarse_to_fine_batch; max_steps applies per level) -> masks from the finest.
+        "otsu" and ("threshold", t) act on the coarsest planes; the numbers of "rect" and "disk" are given in finest pixels and shifted
+        right by levels - 1 (scale_init).  steps / norms are the finest level's, self.level_steps holds every level's counts.  A tensor
+        `init` and reinit_every > 0 are ValueErrors with levels > 1."""
         kind, bits = None, None
+        if self.levels > 1:
+            if not isinstance(init, (str, tuple)):
+                raise ValueError("a tensor init needs levels = 1: with levels > 1 the start is built on the coarsest level")
+            if reinit_every:
+                raise ValueError("reinit_every needs levels = 1")
         if isinstance(init, (str, tuple)):
             kind, start = check_init(init, self.n, self.channels)
         layout = check_images(images, self.n, self.h, self.w, self.channels, self.device, layout)
@@ -163,20 +202,31 @@ class Segmenter:
         if perona_malik is not None:
             K, L, T = perona_malik
             capi.perona_malik_batch(self.contexts, K, L, T)
+        first = self.contexts   # the level the start is built on
+        if self.levels > 1:
+            for k in range(self.levels - 1):
+                capi.restrict_image_batch([p[k] for p in self.pyramids], [p[k + 1] for p in self.pyramids])
+            first = [p[-1] for p in self.pyramids]
+            start = scale_init(kind, start, self.levels)
         if kind == "checkerboard":
-            capi.init_checkerboard_batch(self.contexts)
+            capi.init_checkerboard_batch(first)
         elif kind == "otsu":
-            self.thresholds = capi.init_otsu_batch(self.contexts)
+            self.thresholds = capi.init_otsu_batch(first)
         elif kind == "threshold":
-            capi.init_threshold_batch(self.contexts, start)
+            capi.init_threshold_batch(first, start)
         elif kind == "rect":
-            capi.init_rect_batch(self.contexts, start)
+            capi.init_rect_batch(first, start)
         elif kind == "disk":
-            capi.init_disk_batch(self.contexts, start)
+            capi.init_disk_batch(first, start)
         else:
             for i, ctx in enumerate(self.contexts):
                 ctx.set_levelset_device(init[i].data_ptr(), bits, stream)
-        res = capi.run_batch_with_reinit(self.contexts, max_steps, reinit_every)
+        if self.levels > 1:
+            per_level = capi.run_coarse_to_fine_batch(self.pyramids, max_steps)
+            self.level_steps = [[r[0] for r in member] for member in per_level]
+            res = [member[0] for member in per_level]
+        else:
+            res = capi.run_batch_with_reinit(self.contexts, max_steps, reinit_every)
         masks = torch.empty((self.n, self.h, self.w), dtype=torch.uint8, device=images.device)
         capi.get_mask_device_batch(self.contexts, [masks[i].data_ptr() for i in range(self.n)], invert, stream)
         return masks, [r[0] for r in res], [r[1] for r in res]

@@ -121,7 +121,10 @@ int cvh_set_params(cvh_context *ctx, const cvh_params *p);
  *                    ALL contexts on the device that hold an image and a level set fit the Infinity Cache, <= 300 MB together; decided
  *                    when a run's first iteration is enqueued, kept for the run), 0 plain, 1 write-through
  *   "co_resident"    1 (default): this context streams beside the others on its GPU and counts in their automatic choices ("wave_pol",
- *                    "resident"); 0: a scratch / warm-up context that is idle while the others run
+ *                    "resident"); 0: a scratch / warm-up context that is idle while the others run.  The levels of a pyramid
+ *                    ("Coarse-to-fine" below) never stream beside each other: while one level runs, a driver sets 0 on the
+ *                    pyramid's other levels, and on return the finest level has the value it had before and the helper levels
+ *                    stay 0 -- the finest level then makes the choices it makes without a pyramid
  *   "state"          64 (default): the level set lives in HBM as double -- the reference's CV_64FC1 (src/main.cpp:225), the parity mode.
  *                    32: a DECLARED fast mode that deliberately departs from the reference's type: float in HBM (9 instead of 17 bytes
  *                    per pixel-iteration; 11 instead of 19 with three channels), every new value rounded to float; arithmetic, tables
@@ -494,6 +497,48 @@ int cvh_init_rect(cvh_context *ctx, int x, int y, int rw, int rh, double inside,
 int cvh_init_rect_batch(cvh_context *const *ctxs, int n, const int *xywh, double inside, double outside);
 int cvh_init_disk(cvh_context *ctx, int cx, int cy, int r, double inside, double outside);
 int cvh_init_disk_batch(cvh_context *const *ctxs, int n, const int *cxcyr, double inside, double outside);
+
+/* ---- Coarse-to-fine ---------------------------------------------------------------------------------------------------------
+ * A plane that fits the LDS of the chip iterates several times cheaper per iteration than a large one (README), so a pyramid does most
+ * of its iterations on small planes and only the last few on the full plane.  These calls move the planes DOWN and the level set UP
+ * between two contexts of one device with the same channel count, the coarse one exactly ((h + 1) / 2) x ((w + 1) / 2) for a fine
+ * h x w (integer division) -- what a caller otherwise does with cvh_get_image, a CPU average and cvh_set_image, and with
+ * cvh_get_levelset, a CPU replication and cvh_set_levelset at 8 bytes per pixel.  Both are defined in integers or as bit copies:
+ *   restrict  per plane k of the fine context as it is now (after cvh_perona_malik: the smoothed plane), for coarse pixel (r, c) with
+ *             r0 = 2r, r1 = min(2r + 1, h - 1), c0 = 2c, c1 = min(2c + 1, w - 1):
+ *               coarse_k(r, c) = (f(r0, c0) + f(r0, c1) + f(r1, c0) + f(r1, c1) + 2) >> 2
+ *             (an odd last row or column counts its pixels twice).  The coarse context is left exactly as cvh_set_image of those bytes
+ *             leaves it -- planes, sums, stop norm, validity flags; its level set, if any, stays as cvh_set_image leaves it.  The fine
+ *             context is only read: level set, run state, sums and options are untouched (iterations it has in flight stay in flight),
+ *             and a run continued after the call is bit-identical to one without.
+ *   prolong   u_fine(r, c) = u_coarse(r >> 1, c >> 1), BIT FOR BIT -- NaN payloads, -0.0, infinities and denormals included; no scaling,
+ *             no interpolation: the sign pattern, and so the mask, is replicated exactly.  The source values are those cvh_get_levelset
+ *             of the coarse context returns (with "state" = 32 the exact doubles of its floats); its iterations in flight are settled
+ *             first, as the getters do, and it is only read.  The fine context is left exactly as cvh_set_levelset of those doubles
+ *             leaves it: a new run begins, and with "state" = 32 its float pair adopts the level set (as cvh_init_*).
+ * The *_batch forms take n pairs (pair i = fines[i], coarses[i]) of any mix of shapes and channel counts in ONE launch on the stream of
+ * pair 0's DESTINATION (restrict: coarses[0]; prolong: fines[0]), ordered after everything already enqueued on the streams of both
+ * contexts of every pair and before anything enqueued on them later; one host wait per call (restrict: the sums come back -- one
+ * channel summed on the device, three channels fetched and summed on the host behind that wait, as cvh_set_image_device_batch).  The
+ * single-pair forms are the same kernels with n = 1.
+ * A pyramid is then: restrict down the chain; build the start on the coarsest level (any cvh_init_*: a threshold or Otsu start acts on
+ * the coarsest planes); run the coarsest level; prolong; run the next level; ... -- every level with its own parameters and options,
+ * nothing is rescaled (the level set's magnitudes carry over; mu, eps and tol mean on every level what they mean on a lone context).
+ * For the automatic choices see "co_resident" above.  capi.run_coarse_to_fine, Segmenter(levels=) and chan_vese --levels do this.
+ * How (chan_vese_amd/csrc/pyramid_kernels.hip): pure streaming over the member table.  Restrict: a lane makes 16 coarse pixels from two
+ * 32-byte runs of fine bytes (16-byte loads, one 16-byte store), 5 bytes per coarse pixel and plane.  Prolong: a lane reads a 16-byte
+ * piece of a coarse row and writes each value twice into two fine rows (16-byte stores), 40 bytes per coarse pixel.  Cost, one run
+ * of tools/pyramid_probe.py on an MI355X: a call with its wait 54 / 59 us at 4096^2 -> 2048^2 -- about one CSV
+ * iteration of the 4096^2 plane; a noisy 4096^2 disk from the checkerboard 44.6 ms of CSV device time in one level, 9.3 ms in three.
+ * CVH_ERR_ARG: NULL lists or members, n < 1, a context listed more than once across both lists (fine == coarse included), contexts on
+ * different devices within or across pairs, different channel counts within a pair, a coarse shape other than the one above, a fine
+ * plane with h*w >= 2^32.  CVH_ERR_STATE: restrict from a context without an image, prolong from one without a level set.  Checked for
+ * every pair before anything is launched; the message names the pair index and is cvh_last_error(NULL)'s (and pair 0's destination's,
+ * once the lists hold no NULL); the contexts stay usable. */
+int cvh_restrict_image(cvh_context *fine, cvh_context *coarse);
+int cvh_restrict_image_batch(cvh_context *const *fines, cvh_context *const *coarses, int n);
+int cvh_prolong_levelset(cvh_context *coarse, cvh_context *fine);
+int cvh_prolong_levelset_batch(cvh_context *const *coarses, cvh_context *const *fines, int n);
 
 /* Library version string, e.g. "chanvese_hip 0.1 (gfx950)". */
 const char *cvh_version(void);
