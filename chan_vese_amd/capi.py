@@ -34,10 +34,14 @@ EXPORTS = [
     "cvh_histogram", "cvh_histogram_batch", "cvh_otsu_from_histogram", "cvh_otsu_threshold", "cvh_init_threshold", "cvh_init_threshold_batch",
     "cvh_init_otsu", "cvh_init_otsu_batch", "cvh_init_rect", "cvh_init_rect_batch", "cvh_init_disk", "cvh_init_disk_batch",
     "cvh_restrict_image", "cvh_restrict_image_batch", "cvh_prolong_levelset", "cvh_prolong_levelset_batch",
+    "cvh_convert_colour", "cvh_convert_colour_batch", "cvh_luma_image", "cvh_luma_image_batch",
 ]
 # struct cvh_component: row k - 1 of a component table describes label k (first = smallest flat index; the box is inclusive)
 COMPONENT_DTYPE = np.dtype([("first", np.uint32), ("area", np.uint32), ("x0", np.int32), ("y0", np.int32), ("x1", np.int32), ("y1", np.int32)])
 LAYOUT_PLANAR, LAYOUT_INTERLEAVED = 0, 1
+# "Colour spaces": which plane is which primary, and the spaces cvh_convert_colour knows
+ORDERS = {"bgr": 0, "rgb": 1}
+COLOUR_SPACES = {"ycrcb": 1, "yuv": 2}
 
 
 class Params(C.Structure):
@@ -135,6 +139,10 @@ def lib():
         "cvh_restrict_image_batch": (C.c_int, [C.POINTER(vp), C.POINTER(vp), C.c_int]),
         "cvh_prolong_levelset": (C.c_int, [vp, vp]),
         "cvh_prolong_levelset_batch": (C.c_int, [C.POINTER(vp), C.POINTER(vp), C.c_int]),
+        "cvh_convert_colour": (C.c_int, [vp, C.c_int, C.c_int, C.c_int]),
+        "cvh_convert_colour_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_int]),
+        "cvh_luma_image": (C.c_int, [vp, vp, C.c_int]),
+        "cvh_luma_image_batch": (C.c_int, [C.POINTER(vp), C.POINTER(vp), C.c_int, C.c_int]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -393,6 +401,34 @@ def prolong_levelset_batch(coarses, fines):
     _batch_chk(lib().cvh_prolong_levelset_batch(_member_array(coarses), _member_array(fines), len(coarses)))
 
 
+def colour_space_code(space):
+    """"ycrcb" / "yuv" -> CVH_COLOUR_*; ValueError for anything else.  Calls nothing in the library."""
+    if not isinstance(space, str) or space.lower() not in COLOUR_SPACES:
+        raise ValueError(f"colour space must be one of {sorted(COLOUR_SPACES)}, got {space!r}")
+    return COLOUR_SPACES[space.lower()]
+
+
+def order_code(order):
+    """"bgr" / "rgb" -> CVH_ORDER_*; ValueError for anything else.  Calls nothing in the library."""
+    if not isinstance(order, str) or order.lower() not in ORDERS:
+        raise ValueError(f"plane order must be one of {sorted(ORDERS)}, got {order!r}")
+    return ORDERS[order.lower()]
+
+
+def convert_colour_batch(contexts, space, order="bgr", inverse=False):
+    """cvh_convert_colour_batch: Context.convert_colour for n three-channel contexts (any mix of shapes) with one launch."""
+    space, order = colour_space_code(space), order_code(order)
+    contexts = list(contexts)
+    _batch_chk(lib().cvh_convert_colour_batch(_member_array(contexts), len(contexts), space, order, int(bool(inverse))))
+
+
+def luma_image_batch(srcs, dsts, order="bgr"):
+    """cvh_luma_image_batch: Context.luma_to for n pairs (any mix of shapes) with one launch."""
+    order = order_code(order)
+    srcs, dsts = _pairs(srcs, dsts)
+    _batch_chk(lib().cvh_luma_image_batch(_member_array(srcs), _member_array(dsts), len(srcs), order))
+
+
 def _coarse_to_fine(pyramids, max_steps, run):
     """The pyramids (each a list of contexts, finest first, all of one depth) advance level by level: run(contexts of a level, max_steps)
     -> [(steps, norm)].  Returns [[(steps, norm)] finest first] per pyramid."""
@@ -606,6 +642,19 @@ class Context:
         """cvh_prolong_levelset: the level set of this context, replicated 2 x 2 bit for bit, becomes the level set of `fine`, exactly
         as its set_levelset of those doubles (a new run begins there); this context is only read."""
         _batch_chk(self._L.cvh_prolong_levelset(self._h, fine._h))
+
+    def convert_colour(self, space, order="bgr", inverse=False):
+        """cvh_convert_colour: the three planes, read as (B, G, R) or (R, G, B) by `order`, become (Y, Cr, Cb) ("ycrcb") or (Y, U, V)
+        ("yuv") in place on the device -- or, with inverse, back --, exactly as set_image of the converted bytes (the header's integer
+        definition).  The library does not remember which space the planes are in."""
+        space, order = colour_space_code(space), order_code(order)
+        _batch_chk(self._L.cvh_convert_colour(self._h, space, order, int(bool(inverse))))
+
+    def luma_to(self, dst, order="bgr"):
+        """cvh_luma_image: the Y of this three-channel context becomes the image of `dst` (a one-channel context of the same shape),
+        exactly as its set_image of that plane; this context is only read."""
+        order = order_code(order)
+        _batch_chk(self._L.cvh_luma_image(self._h, dst._h, order))
 
     def reinit(self):
         """cvh_reinit: the level set becomes the exact signed distance to the pixel-edge front of its own mask, on the device.

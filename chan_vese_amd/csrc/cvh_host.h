@@ -1,7 +1,7 @@
 // cvh_host.h -- private header of the library's host units: the context, the launch geometries and the helpers more than one unit calls.
 // api.hip (lifecycle, options, host-buffer I/O, getters, the transitions of a context's run state), csv_run.hip (CSV steps of one
 // context), csv_batch.hip (fused batch, and what every batch shares), pm_run.hip (Perona-Malik), io_run.hip (device-memory I/O),
-// init_run.hip (device-side initial level sets), pyramid_run.hip (coarse-to-fine), debug_exports.hip (diagnostics).  Kernel sources do not include it.
+// init_run.hip (device-side initial level sets), pyramid_run.hip (coarse-to-fine), colour_run.hip (colour spaces), debug_exports.hip (diagnostics).  Kernel sources do not include it.
 #pragma once
 #include <limits.h>
 #include <math.h>
@@ -233,6 +233,9 @@ extern std::atomic<unsigned long> g_reinit_launch_sets;
 
 // pyramid_run.hip: launches of cvh_restrict_image* / cvh_prolong_levelset* so far in this process (debug_exports.hip)
 extern std::atomic<unsigned long> g_pyramid_launches;
+
+// colour_run.hip: launches of cvh_convert_colour* / cvh_luma_image* so far in this process (debug_exports.hip)
+extern std::atomic<unsigned long> g_colour_launches;
 
 // io_run.hip: what every call on device memory or on a member table shares (the comments are at the definitions)
 int pointer_check(cvh_context *const *ctxs, int n, int i, const void *p, const char *what);

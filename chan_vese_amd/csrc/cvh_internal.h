@@ -219,7 +219,7 @@ struct CvhIoMember {
   int interleaved;                    // ingest: the source is h * w * C interleaved bytes (planar otherwise)
   unsigned first, nblk;               // workgroups first .. first + nblk - 1 of the grid are this member's (first ascending, member 0 at 0)
   int h2, w2;                         // restrict: the fine grid the member's planes (h x w) are averaged from, src its first plane
-  unsigned long long src_stride;      // restrict: bytes between the planes of the fine context
+  unsigned long long src_stride;      // restrict, luma: bytes between the planes of the source context
 };
 
 // ---- launchers (csv_kernels.hip / pm_kernels.hip / misc_kernels.hip / io_kernels.hip) ----
@@ -270,6 +270,13 @@ unsigned cvh_restrict_blocks(int fine_h, int fine_w);
 unsigned cvh_prolong_blocks(int fine_h, int fine_w);
 hipError_t cvh_launch_restrict(const CvhIoMember *tab, int nmem, unsigned grid, hipStream_t s);
 hipError_t cvh_launch_prolong(const CvhIoMember *tab, int nmem, unsigned grid, hipStream_t s);
+// colour spaces (colour_kernels.hip).  Convert: plane[] the member's three planes, replaced in place, sums as the ingest's.  Luma:
+// src / src_stride the three planes of the source, plane[0] the member's single plane (written), sums as the ingest's.  space, order
+// and inverse are the call's (include/chanvese_hip.h).  A lane takes a 16-byte piece per trip, CVH_COLOUR_BLOCK_PIXELS a workgroup.
+#define CVH_COLOUR_BLOCK_PIXELS (16 * CVH_BLOCK)
+unsigned cvh_colour_blocks(size_t n);
+hipError_t cvh_launch_colour_convert(const CvhIoMember *tab, int nmem, unsigned grid, int space, int order, int inverse, hipStream_t s);
+hipError_t cvh_launch_colour_luma(const CvhIoMember *tab, int nmem, unsigned grid, int order, hipStream_t s);
 // rows-per-tile options of the step kernel
 void cvh_step_grid(int h, int w, int tile_rows, int *tiles_x, int *tiles_y);
 int cvh_step_max_blocks(int h, int w);

@@ -24,6 +24,10 @@
 // the input, shifted right by L - 1; --init otsu / --threshold on the coarsest planes), and every level runs to its own stop (-N per
 // level) before its level set is prolonged to the next.  Every level has the same parameters; nothing is rescaled.  --state 32 applies to
 // the levels that qualify for it.  All outputs and the -V frames (the first one: the finest level's start) come from the finest level.
+// --colorspace ycrcb|yuv (chanvese_hip.h, "Colour spaces"; not with -g): the loader's B, G, R planes become (Y, Cr, Cb) / (Y, U, V) on the
+// device behind Perona-Malik -- <stem>_pm stays the RGB picture the reference writes -- and in front of the iterations (with --levels: on
+// the finest level, before the restricts); --lambda1 / --lambda2 then weigh the luma and the two chroma planes, a start of --init otsu /
+// --threshold is taken again from the converted planes, and nothing is converted back: frames, _selection and _contour use the input.
 #include <algorithm>
 #include <cctype>
 #include <cerrno>
@@ -177,7 +181,7 @@ const Spec kSpecs[] = {
     {"invert-selection", 'I', 0}, {"select", 's', 0}, {"rectangle", 'R', 0}, {"circle", 'C', 0},
     // additions of this build
     {"dump-u", 0, 1}, {"dump-mask", 0, 1}, {"device", 0, 1}, {"math", 0, 1}, {"state", 0, 1}, {"rect", 0, 1}, {"circ", 0, 1}, {"reinit", 0, 1},
-    {"disk", 0, 1}, {"init", 0, 1}, {"threshold", 0, 1}, {"levels", 0, 1},
+    {"disk", 0, 1}, {"init", 0, 1}, {"threshold", 0, 1}, {"levels", 0, 1}, {"colorspace", 0, 1},
     {"connectivity", 0, 1}, {"min-area", 0, 1}, {"fill-holes", 0, 1}, {"largest", 0, 0}, {"roi", 0, 0},
     {"verbose", 0, 0}};
 
@@ -331,6 +335,9 @@ void print_help()
       "  --roi                              print 'roi x0 y0 x1 y1 area' of that mask's largest component to stdout\n"
       "  --levels arg (=1)                  coarse-to-fine run over arg levels, each half the one before: the start is built and iterated\n"
       "                                     on the coarsest level, then handed up level by level (-N counts per level); not with --circ, --reinit\n"
+      "  --colorspace arg                   ycrcb | yuv: iterate on (Y, Cr, Cb) / (Y, U, V) planes, converted on the device behind Perona-Malik\n"
+      "                                     (--lambda1 / --lambda2 then weigh Y, the first and the second chroma plane: 0 1 1 ignores shading;\n"
+      "                                     --init otsu / --threshold act on the converted planes); not with -g\n"
       "  --verbose                          print the iteration count and last norm to stderr\n"
       "\n";
 }
@@ -393,6 +400,8 @@ int main(int argc, char **argv)
   if (auto v = one("threshold")) threshold = to_int("threshold", *v);
   int levels = 1;
   if (auto v = one("levels")) levels = to_int("levels", *v);
+  std::string colorspace;
+  if (auto v = one("colorspace")) colorspace = *v;
   segment = vm.count("segment"); grayscale = vm.count("grayscale"); write_video = vm.count("video");
   overlay_text = vm.count("overlay-text"); invert = vm.count("invert-selection");
   object_selection = vm.count("select"); rectangle_contour = vm.count("rectangle"); circle_contour = vm.count("circle");
@@ -467,6 +476,13 @@ int main(int argc, char **argv)
   if (levels < 1) msg_exit("Number of levels must be at least 1: " + std::to_string(levels) + ".");
   if (levels > 1 && reinit_every > 0) msg_exit("Reinitialisation (--reinit) cannot be combined with a coarse-to-fine run (--levels).");
   if (levels > 1 && !circ.empty()) msg_exit("A circular outline (--circ) cannot be combined with a coarse-to-fine run (--levels); use --disk.");
+  int colour_space = 0;   // 0: the planes stay B, G, R
+  if (vm.count("colorspace")) {
+    if (iequals(colorspace, "ycrcb")) colour_space = CVH_COLOUR_YCRCB;
+    else if (iequals(colorspace, "yuv")) colour_space = CVH_COLOUR_YUV;
+    else msg_exit("Invalid colour space requested.\nCorrect values are: ycrcb, yuv.");
+    if (grayscale) msg_exit("A colour space (--colorspace) cannot be combined with a grayscale read (-g): there is one plane.");
+  }
 
   // ---- read the image: src/main.cpp:877-887 (8-bit gray or BGR)
   Image file;
@@ -616,6 +632,16 @@ int main(int argc, char **argv)
     if (!write_image(add_suffix(input_filename, "pm"), h, w, nof_channels, out.data()))
       msg_exit("Error: cannot write \"" + add_suffix(input_filename, "pm") + "\"");
     // a start taken from the image is taken again from the smoothed planes (the one above served the t = 0 frame)
+    if (levels > 1) {}
+    else if (init_otsu) cvh_check(ctx, cvh_init_otsu(ctx, nullptr, 1.0, -1.0), "cvh_init_otsu");
+    else if (init_threshold) cvh_check(ctx, cvh_init_threshold(ctx, threshold, 1.0, -1.0), "cvh_init_threshold");
+  }
+
+  // ---- colour space: behind Perona-Malik (<stem>_pm stays the picture the reference writes), in front of the iterations.  The loader's
+  // planes are B, G, R.  Nothing is converted back: frames, _selection and _contour use the input image.  A start taken from the image
+  // is taken again from the converted planes, as behind -S
+  if (colour_space) {
+    cvh_check(ctx, cvh_convert_colour(ctx, colour_space, CVH_ORDER_BGR, 0), "cvh_convert_colour");
     if (levels > 1) {}
     else if (init_otsu) cvh_check(ctx, cvh_init_otsu(ctx, nullptr, 1.0, -1.0), "cvh_init_otsu");
     else if (init_threshold) cvh_check(ctx, cvh_init_threshold(ctx, threshold, 1.0, -1.0), "cvh_init_threshold");

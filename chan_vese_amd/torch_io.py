@@ -109,6 +109,19 @@ def check_levels(levels, h, w):
     return capi.pyramid_shapes(h, w, levels)
 
 
+def check_colour(colour, order, channels):
+    """Validates Segmenter's `colour` and `order` and returns (colour, order) in lower case (colour None: no conversion).  ValueError for
+    a space other than "ycrcb" / "yuv", an order other than "bgr" / "rgb", or a conversion of anything but 3 channels.  Calls nothing
+    in the library."""
+    capi.order_code(order)
+    if colour is None:
+        return None, order.lower()
+    capi.colour_space_code(colour)
+    if channels != 3:
+        raise ValueError(f"colour={colour!r} converts three planes: channels must be 3, got {channels}")
+    return colour.lower(), order.lower()
+
+
 def scale_init(kind, rows, levels):
     """The numbers of a ("rect", ..) / ("disk", ..) start, given in finest pixels, on the coarsest of `levels` levels: every number is
     shifted right by levels - 1 (an arithmetic shift: negative coordinates round down).  Other kinds pass through."""
@@ -126,13 +139,18 @@ class Segmenter:
     """N contexts of one shape on one GPU, kept for the object's lifetime (cvh_create allocates: a stream of frames reuses them).
     levels = L > 1 makes every member a pyramid of L contexts (capi.pyramid_shapes; N x L contexts in all, `pyramids[i]` finest first,
     `contexts` the finest ones) and segment() a coarse-to-fine run; every level takes `params` and `options` as given, nothing is
-    rescaled.  levels = 1 is the plain path, call for call."""
+    rescaled.  levels = 1 is the plain path, call for call.
+    colour = "ycrcb" / "yuv" (three channels only) makes segment() convert the planes, read as (R, G, B) or (B, G, R) by `order`, into
+    (Y, Cr, Cb) / (Y, U, V) on the device (cvh_convert_colour_batch): params.lambda1[0] / lambda2[0] then weigh the luma.  None (the
+    default) converts nothing."""
     levels = 1
+    colour = None
 
-    def __init__(self, n, h, w, channels=1, params=None, device=0, options=None, levels=1):
+    def __init__(self, n, h, w, channels=1, params=None, device=0, options=None, levels=1, colour=None, order="rgb"):
         if n < 1:
             raise ValueError(f"n must be >= 1, got {n}")
         shapes = check_levels(levels, h, w)
+        self.colour, self.order = check_colour(colour, order, channels)
         self.n, self.h, self.w, self.channels, self.levels = n, h, w, channels, levels
         self.device = _device_index(device)
         self.thresholds = None   # Otsu's thresholds of the last segment(init="otsu")
@@ -183,7 +201,11 @@ class Segmenter:
         per level run_batch and a prolong batch (capi.run_coarse_to_fine_batch; max_steps applies per level) -> masks from the finest.
         "otsu" and ("threshold", t) act on the coarsest planes; the numbers of "rect" and "disk" are given in finest pixels and shifted
         right by levels - 1 (scale_init).  steps / norms are the finest level's, self.level_steps holds every level's counts.  A tensor
-        `init` and reinit_every > 0 are ValueErrors with levels > 1."""
+        `init` and reinit_every > 0 are ValueErrors with levels > 1.
+        colour (the constructor's): all members are converted with ONE cvh_convert_colour_batch AFTER the Perona-Malik batch, if any, and
+        BEFORE the start and the run (with levels > 1: on the finest level, before the restricts -- a restrict of converted planes is just
+        a restrict).  "otsu" and ("threshold", t) therefore see the CONVERTED planes (g = Y + the two chroma bytes), and images() returns
+        them."""
         kind, bits = None, None
         if self.levels > 1:
             if not isinstance(init, (str, tuple)):
@@ -202,6 +224,8 @@ class Segmenter:
         if perona_malik is not None:
             K, L, T = perona_malik
             capi.perona_malik_batch(self.contexts, K, L, T)
+        if self.colour is not None:
+            capi.convert_colour_batch(self.contexts, self.colour, self.order)
         first = self.contexts   # the level the start is built on
         if self.levels > 1:
             for k in range(self.levels - 1):
@@ -257,7 +281,8 @@ class Segmenter:
         return out
 
     def images(self):
-        """The members' planes as they are now (after Perona-Malik: the smoothed image), (N, H, W) or (N, C, H, W) uint8."""
+        """The members' planes as they are now (after Perona-Malik: the smoothed image; with colour=: the converted planes of the last
+        segment(), (Y, Cr, Cb) or (Y, U, V)), (N, H, W) or (N, C, H, W) uint8."""
         shape = (self.n, self.h, self.w) if self.channels == 1 else (self.n, self.channels, self.h, self.w)
         out = torch.empty(shape, dtype=torch.uint8, device=torch.device("cuda", self.device))
         for i, ctx in enumerate(self.contexts):

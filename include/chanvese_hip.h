@@ -540,6 +540,65 @@ int cvh_restrict_image_batch(cvh_context *const *fines, cvh_context *const *coar
 int cvh_prolong_levelset(cvh_context *coarse, cvh_context *fine);
 int cvh_prolong_levelset_batch(cvh_context *const *coarses, cvh_context *const *fines, int n);
 
+/* ---- Colour spaces ----------------------------------------------------------------------------------------------------------
+ * In RGB every plane is "brightness plus a bit of hue", so the per-channel lambda1[k] / lambda2[k] buy little.  Split into a luma plane
+ * and two chroma planes, the same three weights say "ignore shading, follow hue" (lambda = 0, 1, 1).  These calls convert the three
+ * planes of a context in place on the device, and write the luma of a three-channel context into a one-channel context -- what a
+ * caller otherwise does with cvh_get_image, a host conversion and cvh_set_image at 6 bytes per pixel across PCIe.  The reference has
+ * no code for this; the definition below IS the contract.  Its constants are those of OpenCV's 8-bit cvtColor, but parity with OpenCV
+ * is not pinned by any test.
+ *   order  says which plane of the context is which primary: CVH_ORDER_BGR plane 0 = B, 1 = G, 2 = R (cv::split of cv::imread; the
+ *          CLI); CVH_ORDER_RGB plane 0 = R, 1 = G, 2 = B.
+ *   space  CVH_COLOUR_YCRCB or CVH_COLOUR_YUV.
+ * All arithmetic is in signed 32-bit integers; >> is the arithmetic shift (floor); sat(x) = min(max(x, 0), 255); H = 8192;
+ * D = 128 << 14.  Forward, per pixel:
+ *     Y = (4899 R + 9617 G + 1868 B + H) >> 14          (the weights add up to 2^14: 0 <= Y <= 255 without a clamp)
+ *     YCrCb  plane 0 = Y, plane 1 = Cr = sat(((R - Y) * 11682 + D + H) >> 14), plane 2 = Cb = sat(((B - Y) *  9241 + D + H) >> 14)
+ *     YUV    plane 0 = Y, plane 1 = U  = sat(((B - Y) *  8061 + D + H) >> 14), plane 2 = V  = sat(((R - Y) * 14369 + D + H) >> 14)
+ * The output planes are always (Y, second, third), whatever `order` was: lambda1[0] / lambda2[0] weigh the luma.  Inverse, planes
+ * (Y, P1, P2) read and R, G, B written back in `order`, with a(x) = x - 128:
+ *     YCrCb  R = sat(Y + ((a(Cr) * 22987 + H) >> 14)), G = sat(Y + ((a(Cb) * -5636 + a(Cr) * -11698 + H) >> 14)),
+ *            B = sat(Y + ((a(Cb) * 29049 + H) >> 14))
+ *     YUV    R = sat(Y + ((a(V) * 18678 + H) >> 14)),  G = sat(Y + ((a(U) * -6472 + a(V) * -9519 + H) >> 14)),
+ *            B = sat(Y + ((a(U) * 33292 + H) >> 14))
+ * Facts of this definition over all 2^24 colours (tests/test_colour_api.py): Y spans 0 .. 255; the raw Cr (before sat) spans 0 .. 256
+ * -- one value clamps --, the raw Cb 1 .. 255; the raw V spans -29 .. 285 -- it clamps --, the raw U 17 .. 239; a grey pixel
+ * (R = G = B = v) maps to (v, 128, 128) and back to itself exactly, in both spaces; the round trip changes each of R, G, B by at most 1
+ * for YCrCb; for YUV it changes R by up to 34 and G by up to 17, where V clamped, and B by at most 1.
+ *   cvh_convert_colour*  replaces the three planes of every member in place (inverse = 0 forward, 1 back).  The source is the planes as
+ *             they are now (after cvh_perona_malik: the smoothed planes).  Every member is left exactly as cvh_set_image of the
+ *             converted bytes leaves it -- planes, sums, stop norm, validity flags; a level set it already has stays as cvh_set_image
+ *             leaves it; iterations in flight are settled first, as cvh_set_image does.  The library keeps NO record of the space a
+ *             context's planes are in: planes are bytes, and converting twice or inverting what was never converted is the caller's
+ *             business, well defined by the formulas.
+ *   cvh_luma_image*      writes the Y of src (three channels) into the single plane of dst, a one-channel context of the same h x w on
+ *             the same device, which is left exactly as cvh_set_image of that plane leaves it (its sums taken on the device in the
+ *             same launch, exact integers).  src is only read: level set, run state, sums and options are untouched, its iterations in
+ *             flight stay in flight, and a run continued after the call is bit-identical to one without (as cvh_restrict_image).
+ * The *_batch forms take n members or pairs (pair i = srcs[i], dsts[i]) of any mix of shapes in ONE launch -- convert on member 0's
+ * stream, luma on the stream of pair 0's destination --, ordered after everything already enqueued on the stream of every listed
+ * context and before anything enqueued on them later; one host wait per call, for the sums (one channel summed on the device, three
+ * channels fetched and summed on the host behind that wait, as cvh_set_image_device_batch).  The single forms are the same kernels
+ * with n = 1.
+ * How (chan_vese_amd/csrc/colour_kernels.hip): pure streaming over the member table; a lane takes a 16-byte piece (16 pixels) of each
+ * plane, computes from byte-extracted words and stores three pieces in place (6 bytes per pixel) or one (luma: 4 bytes per pixel).
+ * Cost, one run of tools/colour_probe.py on an MI355X (host clock around a call and its wait, 20 calls): luma 47 / 60 /
+ * 75 us at 1024^2 / 2048^2 / 4096^2 -- about one CSV iteration of the 4096^2 x 3 plane (82 us); convert 1.2 / 4.6 / 13.1 ms, nearly
+ * all of it the three-channel stop norm the host takes behind the wait, as for every call that replaces three planes.
+ * CVH_ERR_ARG: NULL lists or members, n < 1, a context listed more than once (across both lists for luma, src == dst included),
+ * contexts on different devices, an unknown space or order, inverse other than 0 or 1, a member of convert or a src of luma that has
+ * not 3 channels, a dst that has not 1 channel or has another shape, h*w >= 2^32.  CVH_ERR_STATE: a member or src without an image.
+ * Checked for every member or pair before anything is launched; the message names its index and is cvh_last_error(NULL)'s (and the
+ * leader's, once the lists hold no NULL); the contexts stay usable and their planes unchanged. */
+#define CVH_ORDER_BGR 0
+#define CVH_ORDER_RGB 1
+#define CVH_COLOUR_YCRCB 1
+#define CVH_COLOUR_YUV 2
+int cvh_convert_colour(cvh_context *ctx, int space, int order, int inverse);
+int cvh_convert_colour_batch(cvh_context *const *ctxs, int n, int space, int order, int inverse);
+int cvh_luma_image(cvh_context *src, cvh_context *dst, int order);
+int cvh_luma_image_batch(cvh_context *const *srcs, cvh_context *const *dsts, int n, int order);
+
 /* Library version string, e.g. "chanvese_hip 0.1 (gfx950)". */
 const char *cvh_version(void);
 
