@@ -1,6 +1,7 @@
 // components_run.hip — host side of cvh_components* and cvh_get_mask_clean* (include/chanvese_hip.h, "Connected components"): read-only
-// operations on the level sets of n contexts, each ONE MemberCall (cvh_host.h, io_run.hip: member table, stream joins, event ordering).  The single-context calls
-// are batches of one member.  Nothing here touches a context's level set, run state, sums or options.
+// operations on the level sets of n contexts, each ONE MemberCall (cvh_host.h, io_run.hip: member table, stream joins, event ordering).
+// The single-context calls are batches of one member (guarded_one); what the members must hold is asked of csv_batch.hip's predicates.
+// Nothing here touches a context's level set, run state, sums or options.
 #include "cvh_host.h"
 
 namespace {
@@ -15,15 +16,12 @@ int conn_check(cvh_context *const *ctxs, int n, int conn, const char *what)
 // workspace exist
 int members_ready(cvh_context *const *ctxs, int n, const char *what)
 {
-  for (int i = 0; i < n; ++i) {
-    const cvh_context *c = ctxs[i];
-    if (c->n >= ((size_t)1 << 31)) return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: member %d: %d x %d is too large, h * w must stay below 2^31", what, i, c->h, c->w);
-  }
-  for (int i = 0; i < n; ++i)
-    if (!ctxs[i]->have_u) return batch_fail(ctxs, n, CVH_ERR_STATE, "%s: member %d has no level set", what, i);
+  int rc = members_below(ctxs, n, what, 31);
+  if (rc == CVH_OK) rc = members_have_levelsets(ctxs, n, what);
+  if (rc != CVH_OK) return rc;
   cvh_context *lead = ctxs[0];
   HIPCHK(lead, hipSetDevice(lead->device));
-  int rc = settle_all(ctxs, n, what);
+  rc = settle_all(ctxs, n, what);
   if (rc != CVH_OK) return rc;
   for (int i = 0; i < n; ++i) {
     cvh_context *c = ctxs[i];
@@ -149,9 +147,7 @@ extern "C" int cvh_components_batch(cvh_context *const *ctxs, int n, int conn, i
 
 extern "C" int cvh_components(cvh_context *c, int conn, int invert, int32_t *d_labels, cvh_component *table, int cap, int *count, void *stream)
 {
-  if (!c) return CVH_ERR_ARG;
-  static const char what[] = "cvh_components";
-  return guarded(&c, 1, what, [&]() { return components(&c, 1, conn, invert, &d_labels, count, table, cap, stream, what); });
+  return guarded_one(c, "cvh_components", [&](const char *what) { return components(&c, 1, conn, invert, &d_labels, count, table, cap, stream, what); });
 }
 
 extern "C" int cvh_get_mask_clean_device_batch(cvh_context *const *ctxs, int n, uint8_t *const *d_masks, int conn, int invert, long min_area,
@@ -164,17 +160,13 @@ extern "C" int cvh_get_mask_clean_device_batch(cvh_context *const *ctxs, int n, 
 extern "C" int cvh_get_mask_clean_device(cvh_context *c, uint8_t *d_mask, int conn, int invert, long min_area, long fill_holes, int keep_largest,
                                          void *stream)
 {
-  if (!c) return CVH_ERR_ARG;
-  static const char what[] = "cvh_get_mask_clean_device";
-  return guarded(&c, 1, what, [&]() { return clean(&c, 1, &d_mask, conn, invert, min_area, fill_holes, keep_largest, stream, what); });
+  return guarded_one(c, "cvh_get_mask_clean_device", [&](const char *what) { return clean(&c, 1, &d_mask, conn, invert, min_area, fill_holes, keep_largest, stream, what); });
 }
 
 extern "C" int cvh_get_mask_clean(cvh_context *c, uint8_t *mask, int conn, int invert, long min_area, long fill_holes, int keep_largest)
 {
-  if (!c) return CVH_ERR_ARG;
-  static const char what[] = "cvh_get_mask_clean";
-  if (!mask) return fail(c, CVH_ERR_ARG, "%s: mask is NULL", what);
-  return guarded(&c, 1, what, [&]() {
+  return guarded_one(c, "cvh_get_mask_clean", [&](const char *what) {
+    if (!mask) return fail(c, CVH_ERR_ARG, "%s: mask is NULL", what);
     int rc = clean_args(&c, 1, conn, min_area, fill_holes, keep_largest, what);
     if (rc != CVH_OK) return rc;
     if (!c->have_u) return fail(c, CVH_ERR_STATE, "%s: no level set", what);

@@ -1,5 +1,5 @@
 // csv_batch.hip — the fused batch: N contexts advance together, one launch per iteration and CSV-step instantiation (cvh_enqueue_steps_batch,
-// cvh_run_batch); and what every batch of contexts shares (member checks, errors, stream joins, device tables).
+// cvh_run_batch); and what every batch of contexts shares (member and pair checks, member predicates, errors, stream joins, device tables).
 #include "cvh_host.h"
 
 // The grid of a group is the concatenation of its members' own grids (nparts workgroups + the chain-mode bookkeeper), each padded to a
@@ -79,6 +79,89 @@ int members_check(cvh_context *const *ctxs, int n, const char *what, MemberNeeds
     const Geometry g = resolve_geometry(c);
     if (g.strip < 2) return batch_fail(ctxs, n, CVH_ERR_ARG, "batch: member %d (%d x %d) takes the tile kernel: no fused batch", i, c->h, c->w);
   }
+  return CVH_OK;
+}
+
+// Member predicates: what a call refuses for its members' shapes and state before anything is touched.  Each goes through members
+// 0 .. n-1 in order -- or, with only >= 0, looks at that member alone: for a caller that interleaves it with a rule of its own.
+
+// planes of fewer than 2^k pixels: what the indices of the call's kernels cover
+int members_below(cvh_context *const *ctxs, int n, const char *what, int k, int only)
+{
+  for (int i = std::max(only, 0); i < (only < 0 ? n : only + 1); ++i)
+    if (ctxs[i]->n >= ((size_t)1 << k))
+      return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: member %d: %d x %d is too large, h * w must stay below 2^%d", what, i, ctxs[i]->h, ctxs[i]->w, k);
+  return CVH_OK;
+}
+
+int members_have_images(cvh_context *const *ctxs, int n, const char *what)
+{
+  for (int i = 0; i < n; ++i)
+    if (!ctxs[i]->have_image) return batch_fail(ctxs, n, CVH_ERR_STATE, "%s: member %d has no image (call cvh_set_image first)", what, i);
+  return CVH_OK;
+}
+
+int members_have_levelsets(cvh_context *const *ctxs, int n, const char *what, int only)
+{
+  for (int i = std::max(only, 0); i < (only < 0 ? n : only + 1); ++i)
+    if (!ctxs[i]->have_u) return batch_fail(ctxs, n, CVH_ERR_STATE, "%s: member %d has no level set", what, i);
+  return CVH_OK;
+}
+
+// the FP64 mirrors of members first .. n-1 hold their level sets (ensure_f64_mirror); a failure names `noun` i - first
+int members_mirrors_fresh(cvh_context *const *ctxs, int n, const char *what, int first, const char *noun)
+{
+  for (int i = first; i < n; ++i) {
+    const int rc = ensure_f64_mirror(ctxs[i]);
+    if (rc != CVH_OK) return batch_fail(ctxs, n, rc, "%s: %s %d: %s", what, noun, i - first, ctxs[i]->err);
+  }
+  return CVH_OK;
+}
+
+// Who may be in a call on n pairs of contexts: what can be refused before anything is touched.  *all = [dst 0 .. n-1, src 0 .. n-1],
+// the call's member list, is filled here.  The lists themselves, then args() (the call's other arguments, if any), then pair by pair:
+// the device, rule(i) -- the call's shape and channel rule, which returns CVH_OK or has called batch_fail on *all --, and the size of
+// the pair's larger context, the first list's (row and column indices and a lane's item index stay 32-bit).
+int pairs_check(const PairRoles &p, int n, const char *what, std::vector<cvh_context *> *all, const std::function<int(int)> &rule,
+                const std::function<int()> &args)
+{
+  if (!p.first || !p.second || n < 1)
+    return batch_fail(nullptr, 0, CVH_ERR_ARG, "%s: empty pair list (%s = %p, %s = %p, n = %d)", what, p.first_name, (const void *)p.first, p.second_name,
+                      (const void *)p.second, n);
+  for (int i = 0; i < n; ++i)
+    if (!p.first[i] || !p.second[i])
+      return batch_fail(nullptr, 0, CVH_ERR_ARG, "%s: pair %d: the %s context is NULL", what, i, p.first[i] ? p.second_role : p.first_role);
+  cvh_context *const *dst = p.second_is_dst ? p.second : p.first, *const *src = p.second_is_dst ? p.first : p.second;
+  all->assign(dst, dst + n);
+  all->insert(all->end(), src, src + n);
+  cvh_context *const *ctxs = all->data();
+  auto role = [&](int i) { return (i < n) == p.second_is_dst ? p.second_role : p.first_role; };
+  for (int i = 0; i < 2 * n; ++i)
+    for (int j = 0; j < i; ++j)
+      if (ctxs[i] == ctxs[j])
+        return batch_fail(ctxs, 2 * n, CVH_ERR_ARG, "%s: pair %d: its %s context is also pair %d's %s context (a context may be listed once)", what, i % n,
+                          role(i), j % n, role(j));
+  if (args) { const int rc = args(); if (rc != CVH_OK) return rc; }
+  for (int i = 0; i < n; ++i) {
+    const cvh_context *a = p.first[i], *b = p.second[i];
+    for (const cvh_context *x : {a, b})
+      if (x->device != ctxs[0]->device)
+        return batch_fail(ctxs, 2 * n, CVH_ERR_ARG, "%s: pair %d: its %s context is on device %d, pair 0's on device %d", what, i,
+                          x == a ? p.first_role : p.second_role, x->device, ctxs[0]->device);
+    const int rc = rule(i);
+    if (rc != CVH_OK) return rc;
+    if (a->n >= ((size_t)1 << 32))
+      return batch_fail(ctxs, 2 * n, CVH_ERR_ARG, "%s: pair %d: %d x %d is too large, h * w must stay below 2^32", what, i, a->h, a->w);
+  }
+  return CVH_OK;
+}
+
+// the sources of a pairs_check'ed call, members n .. 2n-1 of its list, hold images
+int pair_sources_have_images(cvh_context *const *all, int n, const char *what, const char *role)
+{
+  for (int i = 0; i < n; ++i)
+    if (!all[n + i]->have_image)
+      return batch_fail(all, 2 * n, CVH_ERR_STATE, "%s: pair %d: the %s context has no image (call cvh_set_image first)", what, i, role);
   return CVH_OK;
 }
 

@@ -1,7 +1,9 @@
 // cvh_host.h -- private header of the library's host units: the context, the launch geometries and the helpers more than one unit calls.
 // api.hip (lifecycle, options, host-buffer I/O, getters, the transitions of a context's run state), csv_run.hip (CSV steps of one
-// context), csv_batch.hip (fused batch, and what every batch shares), pm_run.hip (Perona-Malik), io_run.hip (device-memory I/O),
-// init_run.hip (device-side initial level sets), pyramid_run.hip (coarse-to-fine), colour_run.hip (colour spaces), debug_exports.hip (diagnostics).  Kernel sources do not include it.
+// context), csv_batch.hip (fused batch, and what every batch shares: the member and pair checks, the member predicates), pm_run.hip
+// (Perona-Malik), io_run.hip (device-memory I/O, reinitialisation, and the scaffolds of the member-table calls: MemberCall, write_planes,
+// the launch counters), init_run.hip (device-side initial level sets), components_run.hip (connected components), pyramid_run.hip
+// (coarse-to-fine), colour_run.hip (colour spaces), debug_exports.hip (diagnostics).  Kernel sources do not include it.
 #pragma once
 #include <limits.h>
 #include <math.h>
@@ -12,6 +14,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <functional>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -224,18 +227,23 @@ void batch_cache_free(cvh_context *c);
 int batch_fail(cvh_context *const *ctxs, int n, int code, const char *fmt, ...);
 enum MemberNeeds { kMembersListed, kMembersWithImage, kMembersForCsv };
 int members_check(cvh_context *const *ctxs, int n, const char *what, MemberNeeds needs);
+int members_below(cvh_context *const *ctxs, int n, const char *what, int k, int only = -1);
+int members_have_images(cvh_context *const *ctxs, int n, const char *what);
+int members_have_levelsets(cvh_context *const *ctxs, int n, const char *what, int only = -1);
+int members_mirrors_fresh(cvh_context *const *ctxs, int n, const char *what, int first = 0, const char *noun = "member");
+// the two lists of a call on pairs in the order its messages name them, their names and role words, and which one is written
+struct PairRoles { cvh_context *const *first, *const *second; const char *first_name, *second_name, *first_role, *second_role; bool second_is_dst; };
+int pairs_check(const PairRoles &p, int n, const char *what, std::vector<cvh_context *> *all, const std::function<int(int)> &rule,
+                const std::function<int()> &args = nullptr);
+int pair_sources_have_images(cvh_context *const *all, int n, const char *what, const char *role);
 int join_into_leader(cvh_context *const *ctxs, int n, const int *member = nullptr);
 int grow_table(cvh_context *c, DeviceTable *t, size_t bytes);
 void free_table(DeviceTable *t);
 
-// io_run.hip: launch sets (three kernels for all members) of cvh_reinit / cvh_reinit_batch so far in this process (debug_exports.hip)
-extern std::atomic<unsigned long> g_reinit_launch_sets;
-
-// pyramid_run.hip: launches of cvh_restrict_image* / cvh_prolong_levelset* so far in this process (debug_exports.hip)
-extern std::atomic<unsigned long> g_pyramid_launches;
-
-// colour_run.hip: launches of cvh_convert_colour* / cvh_luma_image* so far in this process (debug_exports.hip)
-extern std::atomic<unsigned long> g_colour_launches;
+// io_run.hip: launches so far in this process (debug_exports.hip): the launch sets (three kernels for all members) of cvh_reinit*, the
+// launches of cvh_restrict_image* / cvh_prolong_levelset*, and those of cvh_convert_colour* / cvh_luma_image*
+enum LaunchCounter { kReinitLaunchSets, kPyramidLaunches, kColourLaunches, kLaunchCounters };
+extern std::atomic<unsigned long> g_launches[kLaunchCounters];
 
 // io_run.hip: what every call on device memory or on a member table shares (the comments are at the definitions)
 int pointer_check(cvh_context *const *ctxs, int n, int i, const void *p, const char *what);
@@ -292,9 +300,9 @@ struct MemberCall {
   }
 };
 
-// The plane sums of a call whose launch has written the planes of members 0 .. n-1 (an ingest, a restrict), as cvh_set_image takes them:
-// 8 integers per member in the call's device extra (zeroed with it; the kernel adds {sum p, sum p^2} per plane), and for the members whose
-// stop norm the host takes (three channels) the planes themselves, fetched into the call's host-only part.  plan() before
+// The plane sums of a call whose launch has written the planes of members 0 .. n-1, as cvh_set_image takes them: 8 integers per member in
+// the call's device extra (zeroed with it; the kernel adds {sum p, sum p^2} per plane), and for the members whose stop norm the host
+// takes (three channels) the planes themselves, fetched into the call's host-only part.  write_planes' own: plan() before
 // MemberCall::begin(.., sums_bytes, fetch_bytes); fetch() inside run()'s launches, behind the kernel; arrive() behind the call's wait.
 struct PlaneSums {
   cvh_context *const *ctxs = nullptr;
@@ -308,6 +316,9 @@ struct PlaneSums {
   int fetch(const MemberCall &call);
   void arrive(const MemberCall &call);
 };
+// the one path of a call that replaces the planes of ctxs[0 .. n_written-1] (an ingest, a conversion, a luma, a restrict): see io_run.hip
+int write_planes(cvh_context *const *ctxs, int n_written, int n_members, const char *what, void *stream,
+                 const std::function<void(int, CvhIoMember &)> &fill, const std::function<int(const MemberCall &)> &launch);
 
 // cvh_get_mask / cvh_get_mask_clean: into_d_mask() writes c->d_mask (allocated on first use) on c's stream; the bytes come down, one wait
 template <class F>
@@ -328,6 +339,13 @@ int guarded(cvh_context *const *ctxs, int n, const char *what, F body)
 {
   try { return body(); }
   catch (...) { return batch_fail(ctxs, n, CVH_ERR_NOMEM, "%s: out of host memory", what); }
+}
+
+// a single-context entry point that is a batch of one member: a NULL context is CVH_ERR_ARG without a message; body(what) is guarded
+template <class F>
+int guarded_one(cvh_context *c, const char *what, F body)
+{
+  return c ? guarded(&c, 1, what, [&]() { return body(what); }) : CVH_ERR_ARG;
 }
 
 // What launches(), which returns CVH_OK or an error already recorded with fail(), enqueues on c's stream, captured and instantiated into

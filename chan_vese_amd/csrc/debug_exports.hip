@@ -86,11 +86,11 @@ extern "C" int cvh_debug_num_cus(cvh_context *c, int *out)
 
 // Diagnostic (not part of include/chanvese_hip.h): launch sets of cvh_reinit / cvh_reinit_batch so far in this process -- one set is the
 // three kernels of reinit_kernels.hip over all members of the call (tests/test_gpu_reinit.py: a batch of n is one set, not n).
-extern "C" unsigned long cvh_debug_reinit_launch_sets(void) { return g_reinit_launch_sets.load(); }
-extern "C" unsigned long cvh_debug_pyramid_launches(void) { return g_pyramid_launches.load(); }
+extern "C" unsigned long cvh_debug_reinit_launch_sets(void) { return g_launches[kReinitLaunchSets].load(); }
+extern "C" unsigned long cvh_debug_pyramid_launches(void) { return g_launches[kPyramidLaunches].load(); }
 // Diagnostics (not part of include/chanvese_hip.h): launches of cvh_convert_colour* / cvh_luma_image* so far in this process (a batch of n
 // is one), and the pixels a workgroup of colour_kernels.hip takes per trip (tests/colour_util.py sizes a plane of one workgroup + one piece)
-extern "C" unsigned long cvh_debug_colour_launches(void) { return g_colour_launches.load(); }
+extern "C" unsigned long cvh_debug_colour_launches(void) { return g_launches[kColourLaunches].load(); }
 extern "C" int cvh_debug_colour_block_pixels(void) { return CVH_COLOUR_BLOCK_PIXELS; }
 
 // Diagnostic (not part of include/chanvese_hip.h): device time (HIP events on the leader's stream: table copy, the three launches, flag

@@ -1,7 +1,8 @@
 // init_run.hip — host side of the device-side initial level sets (include/chanvese_hip.h, "Device-side initial level sets"): the grey
 // histogram, Otsu's threshold and the threshold / rectangle / disk starts of n contexts, each ONE MemberCall (cvh_host.h, io_run.hip:
-// member table, stream joins, event ordering) around init_kernels.hip's launches.  The single-context calls are batches of one member.  The histogram calls only read the planes;
-// a start is a level set arriving without crossing to the host, as cvh_init_checkerboard_batch's.
+// member table, stream joins, event ordering) around init_kernels.hip's launches.  The single-context calls are batches of one member
+// (guarded_one); what the members must hold is asked of csv_batch.hip's predicates.  The histogram calls only read the planes; a start
+// is a level set arriving without crossing to the host, as cvh_init_checkerboard_batch's.
 #include "cvh_host.h"
 
 namespace {
@@ -50,18 +51,7 @@ int otsu(const uint32_t *hist, int bins, int *t)
 int members_fit(cvh_context *const *ctxs, int n, const char *what)
 {
   const int rc = members_check(ctxs, n, what, kMembersListed);
-  if (rc != CVH_OK) return rc;
-  for (int i = 0; i < n; ++i)
-    if (ctxs[i]->n >= ((size_t)1 << 32))
-      return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: member %d: %d x %d is too large, h * w must stay below 2^32", what, i, ctxs[i]->h, ctxs[i]->w);
-  return CVH_OK;
-}
-
-int members_have_images(cvh_context *const *ctxs, int n, const char *what)
-{
-  for (int i = 0; i < n; ++i)
-    if (!ctxs[i]->have_image) return batch_fail(ctxs, n, CVH_ERR_STATE, "%s: member %d has no image (call cvh_set_image first)", what, i);
-  return CVH_OK;
+  return rc != CVH_OK ? rc : members_below(ctxs, n, what, 32);
 }
 
 // The histograms of n members (checked by the caller): iterations in flight settled, the counters zeroed, ONE launch, the counters
@@ -247,17 +237,14 @@ extern "C" int cvh_histogram_batch(cvh_context *const *ctxs, int n, uint32_t *co
 
 extern "C" int cvh_histogram(cvh_context *c, uint32_t *hist, int cap, int *bins)
 {
-  if (!c) return CVH_ERR_ARG;
-  static const char what[] = "cvh_histogram";
-  return guarded(&c, 1, what, [&]() { return histogram_batch(&c, 1, &hist, &cap, bins, what); });
+  return guarded_one(c, "cvh_histogram", [&](const char *what) { return histogram_batch(&c, 1, &hist, &cap, bins, what); });
 }
 
 extern "C" int cvh_otsu_threshold(cvh_context *c, int *t)
 {
-  if (!c) return CVH_ERR_ARG;
-  static const char what[] = "cvh_otsu_threshold";
-  if (!t) return fail(c, CVH_ERR_ARG, "%s: t is NULL", what);
-  return guarded(&c, 1, what, [&]() { return otsu_batch(&c, 1, t, false, 0.0, 0.0, what); });
+  return guarded_one(c, "cvh_otsu_threshold", [&](const char *what) {
+    return t ? otsu_batch(&c, 1, t, false, 0.0, 0.0, what) : fail(c, CVH_ERR_ARG, "%s: t is NULL", what);
+  });
 }
 
 extern "C" int cvh_init_otsu_batch(cvh_context *const *ctxs, int n, int *t, double inside, double outside)
@@ -268,9 +255,7 @@ extern "C" int cvh_init_otsu_batch(cvh_context *const *ctxs, int n, int *t, doub
 
 extern "C" int cvh_init_otsu(cvh_context *c, int *t, double inside, double outside)
 {
-  if (!c) return CVH_ERR_ARG;
-  static const char what[] = "cvh_init_otsu";
-  return guarded(&c, 1, what, [&]() { return otsu_batch(&c, 1, t, true, inside, outside, what); });
+  return guarded_one(c, "cvh_init_otsu", [&](const char *what) { return otsu_batch(&c, 1, t, true, inside, outside, what); });
 }
 
 extern "C" int cvh_init_threshold_batch(cvh_context *const *ctxs, int n, const int *t, double inside, double outside)
@@ -281,9 +266,7 @@ extern "C" int cvh_init_threshold_batch(cvh_context *const *ctxs, int n, const i
 
 extern "C" int cvh_init_threshold(cvh_context *c, int t, double inside, double outside)
 {
-  if (!c) return CVH_ERR_ARG;
-  static const char what[] = "cvh_init_threshold";
-  return guarded(&c, 1, what, [&]() { return threshold_batch(&c, 1, &t, inside, outside, what); });
+  return guarded_one(c, "cvh_init_threshold", [&](const char *what) { return threshold_batch(&c, 1, &t, inside, outside, what); });
 }
 
 extern "C" int cvh_init_rect_batch(cvh_context *const *ctxs, int n, const int *xywh, double inside, double outside)
@@ -294,10 +277,8 @@ extern "C" int cvh_init_rect_batch(cvh_context *const *ctxs, int n, const int *x
 
 extern "C" int cvh_init_rect(cvh_context *c, int x, int y, int rw, int rh, double inside, double outside)
 {
-  if (!c) return CVH_ERR_ARG;
-  static const char what[] = "cvh_init_rect";
   const int xywh[4] = {x, y, rw, rh};
-  return guarded(&c, 1, what, [&]() { return rect_batch(&c, 1, xywh, inside, outside, what); });
+  return guarded_one(c, "cvh_init_rect", [&](const char *what) { return rect_batch(&c, 1, xywh, inside, outside, what); });
 }
 
 extern "C" int cvh_init_disk_batch(cvh_context *const *ctxs, int n, const int *cxcyr, double inside, double outside)
@@ -308,8 +289,6 @@ extern "C" int cvh_init_disk_batch(cvh_context *const *ctxs, int n, const int *c
 
 extern "C" int cvh_init_disk(cvh_context *c, int cx, int cy, int r, double inside, double outside)
 {
-  if (!c) return CVH_ERR_ARG;
-  static const char what[] = "cvh_init_disk";
   const int cxcyr[3] = {cx, cy, r};
-  return guarded(&c, 1, what, [&]() { return disk_batch(&c, 1, cxcyr, inside, outside, what); });
+  return guarded_one(c, "cvh_init_disk", [&](const char *what) { return disk_batch(&c, 1, cxcyr, inside, outside, what); });
 }

@@ -2,12 +2,16 @@
 // read into, device memory the caller owns, ordered against the caller's stream by events; one launch per batch and operation.
 // The single-context calls are batches of one member: one code path.  Reinitialisation (cvh_reinit, cvh_reinit_batch) lives here too: it
 // is a level set leaving and arriving without crossing to the host, on the same member tables and stream joins.  MemberCall (cvh_host.h)
-// is the scaffold of every member-table call, here and in init_run.hip and components_run.hip: staging, the level-set target, the
-// joined launch, the members' arrival.  cvh_init_checkerboard is a checkerboard batch of one.
+// is the scaffold of every member-table call, here and in init_run.hip, components_run.hip, pyramid_run.hip and colour_run.hip: staging,
+// the level-set target, the joined launch, the members' arrival.  write_planes is the one path of the calls that replace planes -- the
+// ingest here, the conversions and the luma of colour_run.hip, the restrict of pyramid_run.hip -- and g_launches the one table of launch
+// counters.  What a call refuses for its members or pairs is in csv_batch.hip.  cvh_init_checkerboard is a checkerboard batch of one.
 #include <memory>
 #include <thread>
 
 #include "cvh_host.h"
+
+std::atomic<unsigned long> g_launches[kLaunchCounters];
 
 // p must be memory that kernels on member i's device can address: device memory of that device, managed memory, or mapped host memory
 int pointer_check(cvh_context *const *ctxs, int n, int i, const void *p, const char *what)
@@ -184,6 +188,35 @@ void PlaneSums::arrive(const MemberCall &call)
   for (int i = 0; i < n; ++i) plane_sums_arrived(ctxs[i], sums + 8 * i, stop_norm_exact_on_device(ctxs[i]) ? nullptr : &norm[i]);
 }
 
+// A call whose launch replaces the planes of members 0 .. n_written-1 of ctxs (members n_written .. n_members-1 are only read: their
+// iterations stay in flight, ordered before the launch by the stream join).  The written members' iterations in flight are settled, as
+// cvh_set_image does; fill(i, m) sets everything of written member i's table entry but `sums`; launch(call) enqueues the kernel on the
+// leader's stream and counts it.  Staging: [member table][8 sums per member, zero] uploaded; behind them the planes of the members whose
+// stop norm the host takes.  Behind the call's ONE host wait the written members are left as cvh_set_image of those bytes leaves them.
+int write_planes(cvh_context *const *ctxs, int n_written, int n_members, const char *what, void *stream,
+                 const std::function<void(int, CvhIoMember &)> &fill, const std::function<int(const MemberCall &)> &launch)
+{
+  HIPCHK(ctxs[0], hipSetDevice(ctxs[0]->device));
+  int rc = settle_all(ctxs, n_written, what);
+  if (rc != CVH_OK) return rc;
+  PlaneSums back;
+  back.plan(ctxs, n_written);
+  MemberCall call;
+  rc = call.begin(ctxs, n_members, what, back.sums_bytes, back.fetch_bytes);
+  if (rc != CVH_OK) return rc;
+  for (int i = 0; i < n_written; ++i) {
+    fill(i, call.tab[i]);
+    call.tab[i].sums = back.device_sums(call, i);
+  }
+  rc = call.run(stream, false, true, [&]() -> int {   // the sums come back to host fields
+    const int rc_launch = launch(call);
+    return rc_launch != CVH_OK ? rc_launch : back.fetch(call);
+  });
+  if (rc != CVH_OK) return rc;
+  back.arrive(call);
+  return CVH_OK;
+}
+
 namespace {
 
 int ingest(cvh_context *const *ctxs, int n, const uint8_t *const *d_imgs, int layout, void *stream, const char *what)
@@ -196,30 +229,13 @@ int ingest(cvh_context *const *ctxs, int n, const uint8_t *const *d_imgs, int la
   cvh_context *lead = ctxs[0];
   HIPCHK(lead, hipSetDevice(lead->device));
   for (int i = 0; i < n; ++i) { rc = pointer_check(ctxs, n, i, d_imgs[i], what); if (rc != CVH_OK) return rc; }
-  rc = settle_all(ctxs, n, what);
-  if (rc != CVH_OK) return rc;
-  // staging: [member table][8 sums per member, zero] uploaded; behind them the planes of the members whose stop norm the host takes
-  PlaneSums back;
-  back.plan(ctxs, n);
-  MemberCall call;
-  rc = call.begin(ctxs, n, what, back.sums_bytes, back.fetch_bytes);
-  if (rc != CVH_OK) return rc;
-  for (int i = 0; i < n; ++i) {
+  return write_planes(ctxs, n, n, what, stream, [&](int i, CvhIoMember &m) {
     const cvh_context *c = ctxs[i];
-    CvhIoMember &m = call.tab[i];
     m.src = d_imgs[i];
     for (int k = 0; k < c->C; ++k) m.plane[k] = c->d_img[k];
-    m.sums = back.device_sums(call, i);
     m.interleaved = layout == CVH_LAYOUT_INTERLEAVED;
     m.nblk = cvh_io_blocks(c->n);
-  }
-  rc = call.run(stream, false, true, [&]() -> int {   // the ONE host wait of the call: the sums come back to host fields
-    HIPCHK(lead, cvh_launch_io_ingest(call.dtab(), n, call.grid, lead->stream));
-    return back.fetch(call);
-  });
-  if (rc != CVH_OK) return rc;
-  back.arrive(call);
-  return CVH_OK;
+  }, [&](const MemberCall &call) -> int { HIPCHK(lead, cvh_launch_io_ingest(call.dtab(), n, call.grid, lead->stream)); return CVH_OK; });
 }
 
 }  // namespace
@@ -232,14 +248,12 @@ int mask_out(cvh_context *const *ctxs, int n, uint8_t *const *d_masks, int inver
   cvh_context *lead = ctxs[0];
   HIPCHK(lead, hipSetDevice(lead->device));
   for (int i = 0; i < n; ++i) { rc = pointer_check(ctxs, n, i, d_masks[i], what); if (rc != CVH_OK) return rc; }
-  for (int i = 0; i < n; ++i)   // (the arguments first, then the members' state: as the single-context getters)
-    if (!ctxs[i]->have_u) return batch_fail(ctxs, n, CVH_ERR_STATE, "%s: member %d has no level set", what, i);
+  rc = members_have_levelsets(ctxs, n, what);   // (the arguments first, then the members' state: as the single-context getters)
+  if (rc != CVH_OK) return rc;
   rc = settle_all(ctxs, n, what);
   if (rc != CVH_OK) return rc;
-  for (int i = 0; i < n; ++i) {
-    rc = ensure_f64_mirror(ctxs[i]);
-    if (rc != CVH_OK) return batch_fail(ctxs, n, rc, "%s: member %d: %s", what, i, ctxs[i]->err);
-  }
+  rc = members_mirrors_fresh(ctxs, n, what);
+  if (rc != CVH_OK) return rc;
   MemberCall call;
   rc = call.begin(ctxs, n, what);
   if (rc != CVH_OK) return rc;
@@ -272,9 +286,7 @@ extern "C" int cvh_set_image_device_batch(cvh_context *const *ctxs, int n, const
 
 extern "C" int cvh_set_image_device(cvh_context *c, const uint8_t *d_img, int layout, void *stream)
 {
-  if (!c) return CVH_ERR_ARG;
-  static const char what[] = "cvh_set_image_device";
-  return guarded(&c, 1, what, [&]() { return ingest(&c, 1, &d_img, layout, stream, what); });
+  return guarded_one(c, "cvh_set_image_device", [&](const char *what) { return ingest(&c, 1, &d_img, layout, stream, what); });
 }
 
 extern "C" int cvh_get_mask_device_batch(cvh_context *const *ctxs, int n, uint8_t *const *d_masks, int invert, void *stream)
@@ -330,9 +342,7 @@ static int checkerboard_batch(cvh_context *const *ctxs, int n, const char *what)
 
 extern "C" int cvh_init_checkerboard(cvh_context *c)
 {
-  if (!c) return CVH_ERR_ARG;
-  static const char what[] = "cvh_init_checkerboard";
-  return guarded(&c, 1, what, [&]() { return checkerboard_batch(&c, 1, what); });
+  return guarded_one(c, "cvh_init_checkerboard", [&](const char *what) { return checkerboard_batch(&c, 1, what); });
 }
 
 extern "C" int cvh_init_checkerboard_batch(cvh_context *const *ctxs, int n)
@@ -409,8 +419,6 @@ extern "C" int cvh_get_levelset_device(cvh_context *c, void *d_u, int bits, void
   return close_call(&c, 1, stream, true);
 }
 
-std::atomic<unsigned long> g_reinit_launch_sets{0};
-
 // Reinitialisation: the level set of every member becomes the signed distance to the pixel-edge front of its mask (reinit_kernels.hip).
 // Per member it is cvh_get_levelset -> the header's definition -> cvh_set_levelset: the result lands in the buffer cvh_set_levelset
 // writes, and a member whose mask is not uniform then begins a new run through levelset_arrived, the device's half of it done by the
@@ -421,7 +429,8 @@ static int reinit_batch(cvh_context *const *ctxs, int n, int *changed, const cha
   if (rc != CVH_OK) return rc;
   for (int i = 0; i < n; ++i) {
     const cvh_context *c = ctxs[i];
-    if (!c->have_u) return batch_fail(ctxs, n, CVH_ERR_STATE, "%s: member %d has no level set", what, i);
+    rc = members_have_levelsets(ctxs, n, what, i);
+    if (rc != CVH_OK) return rc;
     // squared distances are 32-bit integers, vertical distances 16-bit with one value set aside
     if ((unsigned long long)c->h * c->h + (unsigned long long)c->w * c->w >= (1ull << 32))
       return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: member %d: %d x %d is too large, h^2 + w^2 must stay below 2^32", what, i, c->h, c->w);
@@ -457,7 +466,7 @@ static int reinit_batch(cvh_context *const *ctxs, int n, int *changed, const cha
   }
   rc = call.run(nullptr, false, true, [&]() -> int {   // the ONE host wait of the call: which members changed
     HIPCHK(lead, cvh_launch_reinit(call.dtab(), call.grid, call.dtab2(), call.grid2, n, max_w, lead->stream));
-    ++g_reinit_launch_sets;
+    ++g_launches[kReinitLaunchSets];
     HIPCHK(lead, hipMemcpyAsync((void *)flags, call.db + call.extra_off, flag_bytes, hipMemcpyDeviceToHost, lead->stream));
     HIPCHK(lead, hipEventRecord(lead->ev1, lead->stream));
     return CVH_OK;
@@ -478,7 +487,5 @@ extern "C" int cvh_reinit_batch(cvh_context *const *ctxs, int n, int *changed)
 
 extern "C" int cvh_reinit(cvh_context *c, int *changed)
 {
-  if (!c) return CVH_ERR_ARG;
-  static const char what[] = "cvh_reinit";
-  return guarded(&c, 1, what, [&]() { return reinit_batch(&c, 1, changed, what); });
+  return guarded_one(c, "cvh_reinit", [&](const char *what) { return reinit_batch(&c, 1, changed, what); });
 }

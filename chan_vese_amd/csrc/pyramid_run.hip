@@ -1,91 +1,53 @@
 // pyramid_run.hip — host side of the coarse-to-fine calls (include/chanvese_hip.h, "Coarse-to-fine"): the planes of fine contexts
 // restricted into coarse ones, the level sets of coarse contexts prolonged into fine ones, n pairs in ONE MemberCall (cvh_host.h,
-// io_run.hip: member table, stream joins, event ordering) around pyramid_kernels.hip's launch.  The call's member list is the n
-// destinations followed by the n sources: pair 0's destination leads (its stream carries the launch), the streams of all 2n contexts
-// are joined before and after, and the table's first n entries -- the destinations' -- are the kernel's members.  A restrict ends as
-// an ingest does (PlaneSums), a prolong as a device-side start does (levelset_target, MemberCall::arrived).
+// io_run.hip: member table, stream joins, event ordering) around pyramid_kernels.hip's launch.  The call's member list is pairs_check's
+// (csv_batch.hip), the n destinations followed by the n sources: pair 0's destination leads (its stream carries the launch), the
+// streams of all 2n contexts are joined before and after, and the table's first n entries -- the destinations' -- are the kernel's
+// members.  A restrict is its checks, then one write_planes (io_run.hip: it ends as an ingest does); a prolong ends as a device-side
+// start does (levelset_target, MemberCall::arrived).
 #include "cvh_host.h"
-
-std::atomic<unsigned long> g_pyramid_launches{0};
 
 namespace {
 
 // What every call checks for every pair before anything is touched.  all = [dst 0 .. n-1, src 0 .. n-1] is filled here.
-int pairs_check(cvh_context *const *fines, cvh_context *const *coarses, int n, bool down, const char *what, std::vector<cvh_context *> *all)
+int pyramid_pairs(cvh_context *const *fines, cvh_context *const *coarses, int n, bool down, const char *what, std::vector<cvh_context *> *all)
 {
-  if (!fines || !coarses || n < 1)
-    return batch_fail(nullptr, 0, CVH_ERR_ARG, "%s: empty pair list (fines = %p, coarses = %p, n = %d)", what, (const void *)fines, (const void *)coarses, n);
-  for (int i = 0; i < n; ++i)
-    if (!fines[i] || !coarses[i]) return batch_fail(nullptr, 0, CVH_ERR_ARG, "%s: pair %d: the %s context is NULL", what, i, fines[i] ? "coarse" : "fine");
-  cvh_context *const *dst = down ? coarses : fines, *const *src = down ? fines : coarses;
-  all->assign(dst, dst + n);
-  all->insert(all->end(), src, src + n);
-  cvh_context *const *ctxs = all->data();
-  for (int i = 0; i < 2 * n; ++i)
-    for (int j = 0; j < i; ++j)
-      if (ctxs[i] == ctxs[j])
-        return batch_fail(ctxs, 2 * n, CVH_ERR_ARG, "%s: pair %d: its %s context is also pair %d's %s context (a context may be listed once)", what, i % n,
-                          (i < n) == down ? "coarse" : "fine", j % n, (j < n) == down ? "coarse" : "fine");
-  for (int i = 0; i < n; ++i) {
+  return pairs_check({fines, coarses, "fines", "coarses", "fine", "coarse", down}, n, what, all, [&](int i) -> int {
     const cvh_context *f = fines[i], *c = coarses[i];
-    for (const cvh_context *x : {f, c})
-      if (x->device != ctxs[0]->device)
-        return batch_fail(ctxs, 2 * n, CVH_ERR_ARG, "%s: pair %d: its %s context is on device %d, pair 0's on device %d", what, i, x == f ? "fine" : "coarse",
-                          x->device, ctxs[0]->device);
     if (f->C != c->C)
-      return batch_fail(ctxs, 2 * n, CVH_ERR_ARG, "%s: pair %d: the fine context has %d channel(s), the coarse one %d", what, i, f->C, c->C);
+      return batch_fail(all->data(), 2 * n, CVH_ERR_ARG, "%s: pair %d: the fine context has %d channel(s), the coarse one %d", what, i, f->C, c->C);
     if (c->h != (f->h + 1) / 2 || c->w != (f->w + 1) / 2)
-      return batch_fail(ctxs, 2 * n, CVH_ERR_ARG, "%s: pair %d: the coarse context of a %d x %d plane must be %d x %d, got %d x %d", what, i, f->h, f->w,
+      return batch_fail(all->data(), 2 * n, CVH_ERR_ARG, "%s: pair %d: the coarse context of a %d x %d plane must be %d x %d, got %d x %d", what, i, f->h, f->w,
                         (f->h + 1) / 2, (f->w + 1) / 2, c->h, c->w);
-    if (f->n >= ((size_t)1 << 32))   // (the device-side starts' limit: row and column indices and a lane's item index stay 32-bit)
-      return batch_fail(ctxs, 2 * n, CVH_ERR_ARG, "%s: pair %d: %d x %d is too large, h * w must stay below 2^32", what, i, f->h, f->w);
-  }
-  return CVH_OK;
+    return CVH_OK;
+  });
 }
 
 int restrict_batch(cvh_context *const *fines, cvh_context *const *coarses, int n, const char *what)
 {
   std::vector<cvh_context *> all;
-  int rc = pairs_check(fines, coarses, n, true, what, &all);
+  int rc = pyramid_pairs(fines, coarses, n, true, what, &all);
   if (rc != CVH_OK) return rc;
-  cvh_context *const *ctxs = all.data();
-  for (int i = 0; i < n; ++i)
-    if (!fines[i]->have_image) return batch_fail(ctxs, 2 * n, CVH_ERR_STATE, "%s: pair %d: the fine context has no image (call cvh_set_image first)", what, i);
-  cvh_context *lead = ctxs[0];
-  HIPCHK(lead, hipSetDevice(lead->device));
-  // the coarse contexts' planes are replaced: their iterations in flight are settled, as cvh_set_image does.  The fine contexts are only
-  // read, and no iteration writes planes: theirs stay in flight, ordered before the launch by the stream join
-  rc = settle_all(ctxs, n, what);
+  rc = pair_sources_have_images(all.data(), n, what, "fine");
   if (rc != CVH_OK) return rc;
-  PlaneSums back;
-  back.plan(ctxs, n);
-  MemberCall call;
-  rc = call.begin(ctxs, 2 * n, what, back.sums_bytes, back.fetch_bytes);
-  if (rc != CVH_OK) return rc;
-  for (int i = 0; i < n; ++i) {
+  return write_planes(all.data(), n, 2 * n, what, nullptr, [&](int i, CvhIoMember &m) {
     const cvh_context *c = coarses[i], *f = fines[i];
-    CvhIoMember &m = call.tab[i];
     m.src = f->d_img_slab;
     m.src_stride = f->img_stride;
     m.h2 = f->h; m.w2 = f->w;
     for (int k = 0; k < c->C; ++k) m.plane[k] = c->d_img[k];
-    m.sums = back.device_sums(call, i);
     m.nblk = cvh_restrict_blocks(f->h, f->w);
-  }
-  rc = call.run(nullptr, false, true, [&]() -> int {   // the ONE host wait of the call: the sums come back to host fields
-    HIPCHK(lead, cvh_launch_restrict(call.dtab(), n, call.grid, lead->stream));
-    ++g_pyramid_launches;
-    return back.fetch(call);
+  }, [&](const MemberCall &call) -> int {
+    HIPCHK(call.lead, cvh_launch_restrict(call.dtab(), n, call.grid, call.lead->stream));
+    ++g_launches[kPyramidLaunches];
+    return CVH_OK;
   });
-  if (rc != CVH_OK) return rc;
-  back.arrive(call);
-  return CVH_OK;
 }
 
 int prolong_batch(cvh_context *const *coarses, cvh_context *const *fines, int n, const char *what)
 {
   std::vector<cvh_context *> all;
-  int rc = pairs_check(fines, coarses, n, false, what, &all);
+  int rc = pyramid_pairs(fines, coarses, n, false, what, &all);
   if (rc != CVH_OK) return rc;
   cvh_context *const *ctxs = all.data();
   for (int i = 0; i < n; ++i)
@@ -94,10 +56,8 @@ int prolong_batch(cvh_context *const *coarses, cvh_context *const *fines, int n,
   HIPCHK(lead, hipSetDevice(lead->device));
   rc = settle_all(ctxs, 2 * n, what);   // the fine level sets are replaced, the coarse ones read as the getters read them
   if (rc != CVH_OK) return rc;
-  for (int i = 0; i < n; ++i) {
-    rc = ensure_f64_mirror(coarses[i]);
-    if (rc != CVH_OK) return batch_fail(ctxs, 2 * n, rc, "%s: pair %d: %s", what, i, coarses[i]->err);
-  }
+  rc = members_mirrors_fresh(ctxs, 2 * n, what, n, "pair");   // (the coarse contexts are members n .. 2n-1)
+  if (rc != CVH_OK) return rc;
   MemberCall call;
   rc = call.begin(ctxs, 2 * n, what);
   if (rc != CVH_OK) return rc;
@@ -112,7 +72,7 @@ int prolong_batch(cvh_context *const *coarses, cvh_context *const *fines, int n,
   }
   rc = call.run(nullptr, false, true, [&]() -> int {
     HIPCHK(lead, cvh_launch_prolong(call.dtab(), n, call.grid, lead->stream));
-    ++g_pyramid_launches;
+    ++g_launches[kPyramidLaunches];
     return CVH_OK;
   });
   return rc != CVH_OK ? rc : call.arrived(is_fine.data());
