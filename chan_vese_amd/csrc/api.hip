@@ -5,7 +5,10 @@
 // sets); never throws.
 #include "cvh_host.h"
 
-char g_create_err[512] = "no error";
+// cvh_last_error(NULL): per host thread, the calling thread's own last context-less error.  Reached through create_err() alone, so that
+// no other unit addresses the thread-local storage itself.
+static thread_local char g_create_err[kErrLen] = "no error";
+char *create_err() { return g_create_err; }
 
 int fail(cvh_context *ctx, int code, const char *fmt, ...)
 {
@@ -232,7 +235,7 @@ extern "C" int cvh_create(cvh_context **out, int h, int w, int channels, const c
   c->h = h; c->w = w; c->C = channels; c->device = device; c->n = (size_t)h * w; c->p = *p;
   rc = create_impl(c);
   if (rc != CVH_OK) {
-    snprintf(g_create_err, sizeof(g_create_err), "%s", c->err);
+    snprintf(g_create_err, kErrLen, "%s", c->err);
     cvh_destroy(c);
     return rc;
   }

@@ -53,7 +53,7 @@ int batch_fail(cvh_context *const *ctxs, int n, int code, const char *fmt, ...)
   va_start(ap, fmt);
   vsnprintf(msg, sizeof(msg), fmt, ap);
   va_end(ap);
-  snprintf(g_create_err, sizeof(g_create_err), "%s", msg);
+  snprintf(create_err(), kErrLen, "%s", msg);
   if (ctxs && n >= 1 && ctxs[0]) snprintf(ctxs[0]->err, sizeof(ctxs[0]->err), "%s", msg);
   return code;
 }

@@ -182,7 +182,8 @@ inline bool use_fast(const cvh_context *c)
 
 inline int current_buffer(const cvh_context *c) { return (c->cur_base + c->steps_done) & 1; }
 
-extern char g_create_err[512];   // cvh_last_error(NULL): what failed outside a context
+constexpr size_t kErrLen = 512;
+char *create_err();   // api.hip: the kErrLen bytes behind cvh_last_error(NULL) -- what failed outside a context, on the calling thread
 int fail(cvh_context *ctx, int code, const char *fmt, ...);
 
 // api.hip: live-context registry, image statistics

@@ -14,6 +14,10 @@
  *
  * Threading: calls on one context are not re-entrant; different contexts (different
  * images / GPUs) may be driven from different host threads.
+ *  - A batch call counts as a call on every one of its members: no member may be in
+ *    another call, on any thread, while the batch call runs.
+ *  - cvh_last_error(NULL) is per thread: it returns the last context-less error (a failed
+ *    cvh_create, a refused batch) of the calling thread.
  */
 #ifndef CHANVESE_HIP_H
 #define CHANVESE_HIP_H
@@ -80,8 +84,8 @@ int cvh_create(cvh_context **out, int h, int w, int channels, const cvh_params *
                int device);
 void cvh_destroy(cvh_context *ctx);
 
-/* Text of the last error on this context (or of the last failed cvh_create when ctx is
- * NULL).  Never NULL.  Replaces the reference's msg_exit text, src/main.cpp:173-178. */
+/* Text of the last error on this context (or, when ctx is NULL, of the calling thread's last
+ * context-less failure: a failed cvh_create, a refused batch).  Never NULL.  Replaces the reference's msg_exit text, src/main.cpp:173-178. */
 const char *cvh_last_error(const cvh_context *ctx);
 
 /* Replaces the parameter block (may be called between runs). */
