@@ -5,6 +5,8 @@ with instructions.  In a process that also imports torch, import torch FIRST: to
 its own libamdhip64.so.7 and the loader then shares that one runtime with this library.
 """
 import ctypes as C
+import dataclasses
+import math
 import os
 
 import numpy as np
@@ -35,6 +37,7 @@ EXPORTS = [
     "cvh_init_otsu", "cvh_init_otsu_batch", "cvh_init_rect", "cvh_init_rect_batch", "cvh_init_disk", "cvh_init_disk_batch",
     "cvh_restrict_image", "cvh_restrict_image_batch", "cvh_prolong_levelset", "cvh_prolong_levelset_batch",
     "cvh_convert_colour", "cvh_convert_colour_batch", "cvh_luma_image", "cvh_luma_image_batch",
+    "cvh_energy", "cvh_energy_batch",
 ]
 # struct cvh_component: row k - 1 of a component table describes label k (first = smallest flat index; the box is inclusive)
 COMPONENT_DTYPE = np.dtype([("first", np.uint32), ("area", np.uint32), ("x0", np.int32), ("y0", np.int32), ("x1", np.int32), ("y1", np.int32)])
@@ -49,6 +52,30 @@ class Params(C.Structure):
     _fields_ = [("mu", C.c_double), ("nu", C.c_double), ("dt", C.c_double),
                 ("eps", C.c_double), ("tol", C.c_double),
                 ("lambda1", C.c_double * 3), ("lambda2", C.c_double * 3)]
+
+
+class EnergyTerms(C.Structure):
+    """struct cvh_energy_terms ("Energy" in include/chanvese_hip.h)."""
+    _fields_ = [("total", C.c_double), ("length", C.c_double), ("area", C.c_double),
+                ("fit_in", C.c_double * 3), ("fit_out", C.c_double * 3), ("c1", C.c_double * 3), ("c2", C.c_double * 3)]
+
+
+@dataclasses.dataclass(frozen=True)
+class Energy:
+    """The Chan-Sandberg-Vese functional of a context's current level set, term by term: total = mu length + nu area +
+    (1/C) sum_k (lambda1_k fit_in[k] + lambda2_k fit_out[k]); the tuples hold one entry per channel, c1 / c2 the means the fit terms
+    were taken with (Context.get_means)."""
+    total: float
+    length: float
+    area: float
+    fit_in: tuple
+    fit_out: tuple
+    c1: tuple
+    c2: tuple
+
+
+def _energy_of(t, channels):
+    return Energy(t.total, t.length, t.area, *(tuple(getattr(t, f)[k] for k in range(channels)) for f in ("fit_in", "fit_out", "c1", "c2")))
 
 
 class CvhError(RuntimeError):
@@ -143,6 +170,8 @@ def lib():
         "cvh_convert_colour_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_int]),
         "cvh_luma_image": (C.c_int, [vp, vp, C.c_int]),
         "cvh_luma_image_batch": (C.c_int, [C.POINTER(vp), C.POINTER(vp), C.c_int, C.c_int]),
+        "cvh_energy": (C.c_int, [vp, C.POINTER(EnergyTerms)]),
+        "cvh_energy_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.POINTER(EnergyTerms)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -480,9 +509,11 @@ def run_coarse_to_fine_batch(pyramids, max_steps=-1):
     return _coarse_to_fine(pyramids, max_steps, run_batch)
 
 
-def _segmented(contexts, max_steps, every, run):
-    """run(contexts, k) -> [(steps, norm)] in segments of `every` iterations with a reinit_batch of the members still iterating between
-    segments; a member whose stop rule fired inside a segment leaves for the later ones.  every <= 0: one run(contexts, max_steps)."""
+def _segmented(contexts, max_steps, every, run, between=None, after=None):
+    """run(contexts, k) -> [(steps, norm)] in segments of `every` iterations; a member whose stop rule fired inside a segment leaves for
+    the later ones.  after(ran, live, total) -> live, if given, sees every segment's end -- the indices that ran it, those still
+    iterating, the iterations so far -- and returns who goes on; between(contexts still iterating), if given, runs between two
+    segments.  every <= 0: one run(contexts, max_steps), and nothing else."""
     if every <= 0 or not contexts:
         return run(contexts, max_steps)
     total, norm = [0] * len(contexts), [0.0] * len(contexts)
@@ -490,15 +521,18 @@ def _segmented(contexts, max_steps, every, run):
     left = max_steps
     while live and left != 0:
         k = every if left < 0 else min(every, left)
-        res = run([contexts[i] for i in live], k)
-        for i, (done, nrm) in zip(live, res):
+        ran = live
+        res = run([contexts[i] for i in ran], k)
+        for i, (done, nrm) in zip(ran, res):
             total[i] += done
             norm[i] = nrm
-        live = [i for i in live if not contexts[i].sync()[2]]   # (nothing is in flight: sync reports whether the stop rule fired)
+        live = [i for i in ran if not contexts[i].sync()[2]]   # (nothing is in flight: sync reports whether the stop rule fired)
+        if after is not None:
+            live = after(ran, live, total)
         if left > 0:
             left -= k
-        if live and left != 0:
-            reinit_batch([contexts[i] for i in live])
+        if live and left != 0 and between is not None:
+            between([contexts[i] for i in live])
     return list(zip(total, norm))
 
 
@@ -506,14 +540,74 @@ def run_with_reinit(ctx, max_steps=-1, every=0):
     """Context.run in segments of `every` iterations with a reinit between segments; stops as soon as the stop rule fired inside a
     segment (no reinit follows).  max_steps is the total budget (< 0: unlimited).  Returns (total steps, last norm).  every <= 0 is
     exactly ctx.run(max_steps)."""
-    return _segmented([ctx], max_steps, every, lambda cs, k: [cs[0].run(k)])[0]
+    return _segmented([ctx], max_steps, every, lambda cs, k: [cs[0].run(k)], between=reinit_batch)[0]
 
 
 def run_batch_with_reinit(contexts, max_steps=-1, every=0):
     """run_batch in segments of `every` iterations with a reinit_batch between segments.  A member whose stop rule fired inside a
     segment leaves the batch for the later segments (and is not reinitialised again).  Returns [(total steps, last norm)] per context;
     every <= 0 is exactly run_batch(contexts, max_steps)."""
-    return _segmented(list(contexts), max_steps, every, run_batch)
+    return _segmented(list(contexts), max_steps, every, run_batch, between=reinit_batch)
+
+
+def energy_batch(contexts):
+    """cvh_energy_batch: Context.energy for n contexts (any mix of shapes and channel counts) with one set of launches and one host
+    wait.  Returns [Energy] per context; every value is bit for bit the member's own Context.energy()."""
+    contexts = list(contexts)
+    n = len(contexts)
+    out = (EnergyTerms * max(n, 1))()
+    _batch_chk(lib().cvh_energy_batch(_member_array(contexts), n, out))
+    return [_energy_of(out[i], contexts[i].channels) for i in range(n)]
+
+
+def _monitor_args(max_steps, every, rel_plateau):
+    for name, v in (("max_steps", max_steps), ("every", every)):
+        if not isinstance(v, int) or isinstance(v, bool):
+            raise ValueError(f"{name} must be an int, got {v!r}")
+    if rel_plateau is None:
+        return
+    if isinstance(rel_plateau, bool) or not isinstance(rel_plateau, (int, float)) or not math.isfinite(rel_plateau) or rel_plateau < 0:
+        raise ValueError(f"rel_plateau must be None or a finite number >= 0, got {rel_plateau!r}")
+    if every <= 0:
+        raise ValueError("rel_plateau compares the energies of two segments: it needs every > 0")
+
+
+def _monitored(contexts, max_steps, every, rel_plateau, run):
+    """_segmented with one energy_batch behind every segment, over the members that ran it.  Returns [(steps, norm, series)]."""
+    _monitor_args(max_steps, every, rel_plateau)
+    series = [[] for _ in contexts]
+
+    def after(ran, live, total):
+        plateaued = set()
+        for i, e in zip(ran, energy_batch([contexts[j] for j in ran])):
+            prev = series[i][-1][1].total if series[i] else None
+            series[i].append((total[i], e))
+            if rel_plateau is not None and prev is not None and abs(prev - e.total) <= rel_plateau * abs(prev):
+                plateaued.add(i)
+        return [i for i in live if i not in plateaued]
+
+    if every <= 0:
+        res = run(contexts, max_steps)
+        after(list(range(len(contexts))), [], [r[0] for r in res])
+    else:
+        res = _segmented(contexts, max_steps, every, run, after=after)
+    return [(done, nrm, ser) for (done, nrm), ser in zip(res, series)]
+
+
+def run_monitored(ctx, max_steps=-1, every=16, rel_plateau=None):
+    """Context.run in segments of `every` iterations with the energy (Context.energy) taken after each segment.  Returns (total steps,
+    last norm, [(steps so far, Energy)]).  max_steps is the total budget (< 0: unlimited); the run ends when the stop rule fired inside
+    a segment or the budget is spent, and with rel_plateau = x also as soon as a segment's energy E satisfies |E_prev - E| <= x |E_prev|
+    against the segment before it (the first segment has none).  The stop rule itself is not changed.  every <= 0 is exactly
+    ctx.run(max_steps) plus one final energy."""
+    return _monitored([ctx], max_steps, every, rel_plateau, lambda cs, k: [cs[0].run(k)])[0]
+
+
+def run_batch_monitored(contexts, max_steps=-1, every=16, rel_plateau=None):
+    """run_monitored over run_batch, with one energy_batch per segment.  A member whose stop rule fired or whose energy plateaued leaves
+    the batch for the later segments.  Returns [(total steps, last norm, [(steps so far, Energy)])] per context; every <= 0 is exactly
+    run_batch(contexts, max_steps) plus one energy_batch."""
+    return _monitored(list(contexts), max_steps, every, rel_plateau, run_batch)
 
 
 class Context:
@@ -694,6 +788,13 @@ class Context:
         c1, c2 = np.zeros(3), np.zeros(3)
         self._chk(self._L.cvh_get_means(self._h, _dp(c1), _dp(c2)))
         return c1[:self.channels].copy(), c2[:self.channels].copy()
+
+    def energy(self):
+        """cvh_energy: the Chan-Sandberg-Vese functional of the current level set, term by term, evaluated on the device (Energy).
+        Only reads: a run continued after it is bit-identical to one without."""
+        t = EnergyTerms()
+        _batch_chk(self._L.cvh_energy(self._h, C.byref(t)))
+        return _energy_of(t, self.channels)
 
     def get_trace(self, max_rows):
         out = np.zeros((max(max_rows, 1), 2 * self.channels + 1), dtype=np.float64)

@@ -277,6 +277,19 @@ hipError_t cvh_launch_prolong(const CvhIoMember *tab, int nmem, unsigned grid, h
 unsigned cvh_colour_blocks(size_t n);
 hipError_t cvh_launch_colour_convert(const CvhIoMember *tab, int nmem, unsigned grid, int space, int order, int inverse, hipStream_t s);
 hipError_t cvh_launch_colour_luma(const CvhIoMember *tab, int nmem, unsigned grid, int order, hipStream_t s);
+// energy (energy_kernels.hip).  src the level set, src2 the CvhState that holds its means, plane[] the planes, dst the member's item rows
+// (cvh_energy_items x CVH_ENERGY_SLOTS doubles of the context's workspace), sums a row of CVH_ENERGY_ROW doubles: [0] eps (read), then
+// length, area, fit_in[3], fit_out[3], c1[3], c2[3] (written).  An item is CVH_ENERGY_BAND rows x CVH_ENERGY_COLS columns, a wave's trip.
+#define CVH_ENERGY_BAND 32
+#define CVH_ENERGY_COLS 128
+#define CVH_ENERGY_SLOTS (2 + 2 * CVH_MAX_CHANNELS)
+#define CVH_ENERGY_ROW 16
+__host__ __device__ constexpr unsigned cvh_energy_items(int h, int w)
+{
+  return (((unsigned)h + CVH_ENERGY_BAND - 1) / CVH_ENERGY_BAND) * (((unsigned)w + CVH_ENERGY_COLS - 1) / CVH_ENERGY_COLS);
+}
+unsigned cvh_energy_blocks(int h, int w);
+hipError_t cvh_launch_energy(const CvhIoMember *tab, int nmem, unsigned grid, hipStream_t s);   // the term pass, then the reduce pass
 // rows-per-tile options of the step kernel
 void cvh_step_grid(int h, int w, int tile_rows, int *tiles_x, int *tiles_y);
 int cvh_step_max_blocks(int h, int w);

@@ -92,6 +92,9 @@ extern "C" unsigned long cvh_debug_pyramid_launches(void) { return g_launches[kP
 // is one), and the pixels a workgroup of colour_kernels.hip takes per trip (tests/colour_util.py sizes a plane of one workgroup + one piece)
 extern "C" unsigned long cvh_debug_colour_launches(void) { return g_launches[kColourLaunches].load(); }
 extern "C" int cvh_debug_colour_block_pixels(void) { return CVH_COLOUR_BLOCK_PIXELS; }
+// Diagnostic (not part of include/chanvese_hip.h): launch sets of cvh_energy / cvh_energy_batch so far in this process -- one set is the
+// term pass and the reduce pass of energy_kernels.hip over all members of the call (tests/test_gpu_energy.py: a batch of n is one set)
+extern "C" unsigned long cvh_debug_energy_launch_sets(void) { return g_launches[kEnergyLaunchSets].load(); }
 
 // Diagnostic (not part of include/chanvese_hip.h): device time (HIP events on the leader's stream: table copy, the three launches, flag
 // copy) of the last cvh_reinit / cvh_reinit_batch this context led (tools/reinit_probe.py).

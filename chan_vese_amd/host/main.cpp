@@ -19,7 +19,9 @@
 // text of -O is not rendered (no font rasteriser here), --fps has nothing to act on.
 // Additions that do not collide with reference options: --dump-u, --dump-mask, --device, --math,
 // --state, --rect, --circ, --disk, --init, --threshold, --reinit, --connectivity, --min-area, --fill-holes, --largest, --roi, --verbose,
-// --levels.  --levels L > 1 is a coarse-to-fine run (chanvese_hip.h, "Coarse-to-fine"): L contexts, each half the one before; after -S
+// --levels, --energy, --energy-every.  --energy prints "energy total length area fit_in... fit_out..." (chanvese_hip.h, "Energy"; %.17g, one
+// fit_in and one fit_out per channel) to stdout after the run; --energy-every K runs in segments of K iterations and prints one such line,
+// prefixed by the iteration count, after each (not with -V, --reinit, --levels).  --levels L > 1 is a coarse-to-fine run (chanvese_hip.h, "Coarse-to-fine"): L contexts, each half the one before; after -S
 // the planes are restricted down the chain, the start is built on the COARSEST level (the numbers of --rect / --disk, given in pixels of
 // the input, shifted right by L - 1; --init otsu / --threshold on the coarsest planes), and every level runs to its own stop (-N per
 // level) before its level set is prolonged to the next.  Every level has the same parameters; nothing is rescaled.  --state 32 applies to
@@ -183,7 +185,7 @@ const Spec kSpecs[] = {
     {"dump-u", 0, 1}, {"dump-mask", 0, 1}, {"device", 0, 1}, {"math", 0, 1}, {"state", 0, 1}, {"rect", 0, 1}, {"circ", 0, 1}, {"reinit", 0, 1},
     {"disk", 0, 1}, {"init", 0, 1}, {"threshold", 0, 1}, {"levels", 0, 1}, {"colorspace", 0, 1},
     {"connectivity", 0, 1}, {"min-area", 0, 1}, {"fill-holes", 0, 1}, {"largest", 0, 0}, {"roi", 0, 0},
-    {"verbose", 0, 0}};
+    {"verbose", 0, 0}, {"energy", 0, 0}, {"energy-every", 0, 1}};
 
 struct Parsed {
   std::vector<std::pair<std::string, std::vector<std::string>>> opts;
@@ -338,6 +340,9 @@ void print_help()
       "  --colorspace arg                   ycrcb | yuv: iterate on (Y, Cr, Cb) / (Y, U, V) planes, converted on the device behind Perona-Malik\n"
       "                                     (--lambda1 / --lambda2 then weigh Y, the first and the second chroma plane: 0 1 1 ignores shading;\n"
       "                                     --init otsu / --threshold act on the converted planes); not with -g\n"
+      "  --energy                           print 'energy total length area fit_in... fit_out...' of the final level set to stdout (%.17g)\n"
+      "  --energy-every arg (=0)            run in segments of arg iterations and print such a line, prefixed by the iteration count, after\n"
+      "                                     each (0: never); -N stays the total; not with -V, --reinit, --levels\n"
       "  --verbose                          print the iteration count and last norm to stderr\n"
       "\n";
 }
@@ -402,6 +407,9 @@ int main(int argc, char **argv)
   if (auto v = one("levels")) levels = to_int("levels", *v);
   std::string colorspace;
   if (auto v = one("colorspace")) colorspace = *v;
+  const bool print_energy = vm.count("energy");
+  int energy_every = 0;
+  if (auto v = one("energy-every")) energy_every = to_int("energy-every", *v);
   segment = vm.count("segment"); grayscale = vm.count("grayscale"); write_video = vm.count("video");
   overlay_text = vm.count("overlay-text"); invert = vm.count("invert-selection");
   object_selection = vm.count("select"); rectangle_contour = vm.count("rectangle"); circle_contour = vm.count("circle");
@@ -476,6 +484,10 @@ int main(int argc, char **argv)
   if (levels < 1) msg_exit("Number of levels must be at least 1: " + std::to_string(levels) + ".");
   if (levels > 1 && reinit_every > 0) msg_exit("Reinitialisation (--reinit) cannot be combined with a coarse-to-fine run (--levels).");
   if (levels > 1 && !circ.empty()) msg_exit("A circular outline (--circ) cannot be combined with a coarse-to-fine run (--levels); use --disk.");
+  if (energy_every < 0) msg_exit("Energy interval cannot be negative: " + std::to_string(energy_every) + ".");
+  if (energy_every > 0 && write_video) msg_exit("An energy series (--energy-every) cannot be combined with video output (-V).");
+  if (energy_every > 0 && reinit_every > 0) msg_exit("An energy series (--energy-every) cannot be combined with reinitialisation (--reinit).");
+  if (energy_every > 0 && levels > 1) msg_exit("An energy series (--energy-every) cannot be combined with a coarse-to-fine run (--levels).");
   int colour_space = 0;   // 0: the planes stay B, G, R
   if (vm.count("colorspace")) {
     if (iequals(colorspace, "ycrcb")) colour_space = CVH_COLOUR_YCRCB;
@@ -660,6 +672,16 @@ int main(int argc, char **argv)
       if (stopped) break;
     }
   };
+  auto energy_line = [&](int iteration) {   // "[iteration ]energy total length area fit_in... fit_out...", every number %.17g
+    cvh_energy_terms e;
+    cvh_check(ctx, cvh_energy(ctx, &e), "cvh_energy");
+    if (iteration >= 0) std::printf("%d ", iteration);
+    std::printf("energy %.17g %.17g %.17g", e.total, e.length, e.area);
+    for (int k = 0; k < nof_channels; ++k) std::printf(" %.17g", e.fit_in[k]);
+    for (int k = 0; k < nof_channels; ++k) std::printf(" %.17g", e.fit_out[k]);
+    std::printf("\n");
+    std::fflush(stdout);
+  };
   if (levels > 1) {
     // restrict down the chain, start on the coarsest level, then level by level: run, prolong.  While a level runs the others do not
     // count in its automatic choices ("co_resident"); the finest keeps its own value throughout
@@ -691,11 +713,24 @@ int main(int argc, char **argv)
       if (stopped) break;
       if (left > 0) cvh_check(ctx, cvh_reinit(ctx, nullptr), "cvh_reinit");
     }
+  } else if (energy_every > 0) {
+    // segments of energy_every iterations, the energy taken behind each; a stop inside a segment ends the run
+    for (int left = max_steps; left > 0;) {
+      const int k = std::min(energy_every, left);
+      int done = 0, stopped = 0;
+      cvh_check(ctx, cvh_run(ctx, k, &done, &last_norm), "cvh_run");
+      cvh_check(ctx, cvh_sync(ctx, nullptr, nullptr, &stopped), "cvh_sync");
+      steps_done += done;
+      left -= k;
+      energy_line(steps_done);
+      if (stopped) break;
+    }
   } else if (!write_video) {
     cvh_check(ctx, cvh_run(ctx, max_steps, &steps_done, &last_norm), "cvh_run");
   } else {
     run_with_frames();
   }
+  if (print_energy) energy_line(-1);
 
   if (!dump_u.empty()) {
     std::vector<double> u(n);

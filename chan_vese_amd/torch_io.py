@@ -155,6 +155,7 @@ class Segmenter:
         self.device = _device_index(device)
         self.thresholds = None   # Otsu's thresholds of the last segment(init="otsu")
         self.level_steps = None  # levels > 1: the iterations of the last segment() per member and level, finest first
+        self.energy_series = None   # segment(energy_every=K > 0): [(iterations so far, capi.Energy)] of the last segment() per member
         self.contexts = []
         self.pyramids = []
         try:
@@ -187,7 +188,7 @@ class Segmenter:
     def _stream(self):
         return torch.cuda.current_stream(self.device).cuda_stream
 
-    def segment(self, images, max_steps=-1, perona_malik=None, init="checkerboard", invert=False, layout=None, reinit_every=0):
+    def segment(self, images, max_steps=-1, perona_malik=None, init="checkerboard", invert=False, layout=None, reinit_every=0, energy_every=0):
         """ingest -> (Perona-Malik batch) -> initial level set -> cvh_run_batch -> masks.  Returns (masks, steps, norms): masks a uint8
         tensor (N, H, W) on the images' device, valid for the next operation on the current stream without a host wait of the caller's;
         steps / norms the iterations and the last ||u_diff|| of every member.  `layout` (capi.LAYOUT_*) is needed only for a shape that is
@@ -205,13 +206,23 @@ class Segmenter:
         colour (the constructor's): all members are converted with ONE cvh_convert_colour_batch AFTER the Perona-Malik batch, if any, and
         BEFORE the start and the run (with levels > 1: on the finest level, before the restricts -- a restrict of converted planes is just
         a restrict).  "otsu" and ("threshold", t) therefore see the CONVERTED planes (g = Y + the two chroma bytes), and images() returns
-        them."""
+        them.
+        energy_every = K > 0 runs segments of K iterations with the energy of the members still iterating taken after each
+        (capi.run_batch_monitored, one cvh_energy_batch per segment; max_steps stays the total budget) and stores the series in
+        self.energy_series; 0 takes none and leaves self.energy_series None.  It is a ValueError with levels > 1 or reinit_every > 0.
+        energies() gives the terms of the final level sets either way."""
         kind, bits = None, None
         if self.levels > 1:
             if not isinstance(init, (str, tuple)):
                 raise ValueError("a tensor init needs levels = 1: with levels > 1 the start is built on the coarsest level")
             if reinit_every:
                 raise ValueError("reinit_every needs levels = 1")
+            if energy_every:
+                raise ValueError("energy_every needs levels = 1")
+        if not isinstance(energy_every, int) or isinstance(energy_every, bool) or energy_every < 0:
+            raise ValueError(f"energy_every must be an int >= 0, got {energy_every!r}")
+        if energy_every and reinit_every:
+            raise ValueError("energy_every and reinit_every cannot be combined: a reinitialisation replaces the level set the series follows")
         if isinstance(init, (str, tuple)):
             kind, start = check_init(init, self.n, self.channels)
         layout = check_images(images, self.n, self.h, self.w, self.channels, self.device, layout)
@@ -220,6 +231,7 @@ class Segmenter:
         if perona_malik is not None and len(perona_malik) != 3:
             raise ValueError("perona_malik must be (K, L, T)")
         stream = self._stream()
+        self.energy_series = None
         capi.set_image_device_batch(self.contexts, [images[i].data_ptr() for i in range(self.n)], layout, stream)
         if perona_malik is not None:
             K, L, T = perona_malik
@@ -249,11 +261,20 @@ class Segmenter:
             per_level = capi.run_coarse_to_fine_batch(self.pyramids, max_steps)
             self.level_steps = [[r[0] for r in member] for member in per_level]
             res = [member[0] for member in per_level]
+        elif energy_every:
+            mon = capi.run_batch_monitored(self.contexts, max_steps, energy_every)
+            self.energy_series = [m[2] for m in mon]
+            res = [m[:2] for m in mon]
         else:
             res = capi.run_batch_with_reinit(self.contexts, max_steps, reinit_every)
         masks = torch.empty((self.n, self.h, self.w), dtype=torch.uint8, device=images.device)
         capi.get_mask_device_batch(self.contexts, [masks[i].data_ptr() for i in range(self.n)], invert, stream)
         return masks, [r[0] for r in res], [r[1] for r in res]
+
+    def energies(self):
+        """The Chan-Sandberg-Vese functional of every member's current level set -- after segment(): the final ones --, term by term
+        (cvh_energy_batch: one set of launches, one host wait).  Returns [capi.Energy], each bit for bit its context's Context.energy()."""
+        return capi.energy_batch(self.contexts)
 
     def components(self, conn=4, invert=False):
         """The connected components of every member's mask (cvh_components_batch): (labels, counts), labels an int32 tensor (N, H, W) --

@@ -603,6 +603,50 @@ int cvh_convert_colour_batch(cvh_context *const *ctxs, int n, int space, int ord
 int cvh_luma_image(cvh_context *src, cvh_context *dst, int order);
 int cvh_luma_image_batch(cvh_context *const *srcs, cvh_context *const *dsts, int n, int order);
 
+/* ---- Energy ------------------------------------------------------------------------------------------------------------------
+ * The library minimises the Chan-Sandberg-Vese functional
+ *     E(u) = mu Length + nu Area + (1/C) sum_k [ lambda1_k int (I_k - c1_k)^2 H_eps(u) + lambda2_k int (I_k - c2_k)^2 (1 - H_eps(u)) ];
+ * these calls evaluate it, term by term, on the device -- the one number that says how good the current level set is, which a caller
+ * otherwise takes with cvh_get_levelset, cvh_get_image (8 + C bytes per pixel across PCIe) and a host pass.  The reference states the
+ * functional and never evaluates it; the definition below IS the contract.  For the context's CURRENT level set u (h x w), its planes
+ * I_k and its parameters (cvh_params: mu, nu, eps, lambda1, lambda2), everything in FP64:
+ *     H_eps(x) = 1/2 (1 + (2/pi) atan(x / eps)),  delta_eps(x) = eps / (pi (eps^2 + x^2))             (src/main.cpp:188-210)
+ *     gx(r, c) = (u(r, min(c + 1, w - 1)) - u(r, max(c - 1, 0))) * 0.5,  gy the same along the rows: central differences, replicate border
+ *     length     = sum delta_eps(u) sqrt(gx^2 + gy^2)
+ *     area       = sum H_eps(u)
+ *     fit_in[k]  = sum (I_k - c1_k)^2 H_eps(u)
+ *     fit_out[k] = sum (I_k - c2_k)^2 (1 - H_eps(u))
+ *     total      = mu length + nu area + (1/C) sum_k (lambda1_k fit_in[k] + lambda2_k fit_out[k])
+ * every sum over all h w pixels.  c1_k / c2_k are exactly the values cvh_get_means returns for this level set -- whatever it returns for
+ * a nearly or wholly empty region included -- and come back in c1[] / c2[].  The host combines `total` from the term sums in exactly
+ * the order written, left to right, k ascending.  Entries of the arrays behind the context's channel count are 0.  With "state" = 32
+ * the level set is the one the getters see: the exact doubles of the float state.  A non-finite u gives non-finite terms; that is not
+ * an error.
+ * Determinism: the value of every term depends on the inputs and the member's shape alone -- not on the grid a batch gives the member,
+ * not on the order workgroups arrive in, not on the other members.  Two calls in a row, and a member alone or inside any batch, give
+ * the same bits.  (How: chan_vese_amd/csrc/energy_kernels.hip -- per-item partial sums in a fixed order, then one fixed-order
+ * reduction per member; no atomics.)
+ * The calls only READ: level set, run state, sums, options and planes are untouched; iterations in flight are settled first, as the
+ * getters do; a run continued after the call is bit-identical to one without it.  Where the context's state block does not hold the
+ * means of the current level set (a level set just arrived, planes or eps changed), they are taken inside the call, beside the run's
+ * state and not into it.
+ * cvh_energy_batch takes n contexts of any mix of shapes and channel counts on one device and writes out[0 .. n-1]: one set of launches
+ * (term pass, reduce pass) on member 0's stream, ordered after everything already enqueued on the stream of every member and before
+ * anything enqueued on them later, one host wait per call.  cvh_energy is the same path with n = 1.
+ * Cost, one run of tools/energy_probe.py on an MI355X (host clock around a call and its wait, 20 calls): 72 / 80 / 149 us
+ * at 1024^2 / 2048^2 / 4096^2, 198 us at 4096^2 x 3 -- about 70 us of it fixed (table upload, two launches, copy back, wait), and 2.2 to
+ * 2.5 CSV iterations of the same plane at 4096^2; up to a third more where the means are taken inside the call.
+ * CVH_ERR_ARG: a NULL list, member or out, n < 1, a context listed twice, contexts on different devices, h*w >= 2^32.  CVH_ERR_STATE: a
+ * member without an image or without a level set.  Every member is checked before anything is launched; the message names the member
+ * index and is cvh_last_error(NULL)'s (and the leader's); the contexts stay usable. */
+typedef struct cvh_energy_terms {
+  double total, length, area;
+  double fit_in[CVH_MAX_CHANNELS], fit_out[CVH_MAX_CHANNELS];
+  double c1[CVH_MAX_CHANNELS], c2[CVH_MAX_CHANNELS];
+} cvh_energy_terms;
+int cvh_energy(cvh_context *ctx, cvh_energy_terms *out);
+int cvh_energy_batch(cvh_context *const *ctxs, int n, cvh_energy_terms *out);
+
 /* Library version string, e.g. "chanvese_hip 0.1 (gfx950)". */
 const char *cvh_version(void);
 
