@@ -38,6 +38,7 @@ EXPORTS = [
     "cvh_restrict_image", "cvh_restrict_image_batch", "cvh_prolong_levelset", "cvh_prolong_levelset_batch",
     "cvh_convert_colour", "cvh_convert_colour_batch", "cvh_luma_image", "cvh_luma_image_batch",
     "cvh_energy", "cvh_energy_batch",
+    "cvh_score_mask", "cvh_score_mask_device", "cvh_score_mask_device_batch",
 ]
 # struct cvh_component: row k - 1 of a component table describes label k (first = smallest flat index; the box is inclusive)
 COMPONENT_DTYPE = np.dtype([("first", np.uint32), ("area", np.uint32), ("x0", np.int32), ("y0", np.int32), ("x1", np.int32), ("y1", np.int32)])
@@ -76,6 +77,69 @@ class Energy:
 
 def _energy_of(t, channels):
     return Energy(t.total, t.length, t.area, *(tuple(getattr(t, f)[k] for k in range(channels)) for f in ("fit_in", "fit_out", "c1", "c2")))
+
+
+class MaskScore(C.Structure):
+    """struct cvh_mask_score ("Mask scores" in include/chanvese_hip.h)."""
+    _fields_ = [(f, C.c_uint64) for f in ("tp", "fp", "fn", "tn", "surf_m", "surf_t", "within_m", "within_t", "dist_m_q16", "dist_t_q16")] + \
+               [("hd2_m", C.c_uint32), ("hd2_t", C.c_uint32), ("defined", C.c_int32), ("pad", C.c_int32)]
+
+
+SCORE_FIELDS = tuple(f for f, _ in MaskScore._fields_ if f != "pad")
+
+
+def _ratio(num, den):
+    return num / den if den else math.nan
+
+
+@dataclasses.dataclass(frozen=True)
+class Score:
+    """A mask against a ground truth ("Mask scores" in include/chanvese_hip.h): the exact integers of cvh_mask_score, and the figures the
+    header derives from them -- each NaN where its denominator is 0 or, for the boundary measures, where a surface is empty."""
+    tp: int
+    fp: int
+    fn: int
+    tn: int
+    surf_m: int
+    surf_t: int
+    within_m: int
+    within_t: int
+    dist_m_q16: int
+    dist_t_q16: int
+    hd2_m: int
+    hd2_t: int
+    defined: int
+
+    @property
+    def iou(self):
+        return _ratio(self.tp, self.tp + self.fp + self.fn)
+
+    @property
+    def dice(self):
+        return _ratio(2 * self.tp, 2 * self.tp + self.fp + self.fn)
+
+    @property
+    def hausdorff(self):
+        return math.sqrt(max(self.hd2_m, self.hd2_t)) if self.defined else math.nan
+
+    @property
+    def assd(self):
+        return _ratio((self.dist_m_q16 + self.dist_t_q16) / 65536, self.surf_m + self.surf_t) if self.defined else math.nan
+
+    @property
+    def surface_dice(self):
+        return _ratio(self.within_m + self.within_t, self.surf_m + self.surf_t) if self.defined else math.nan
+
+
+def _score_of(s):
+    return Score(*(int(getattr(s, f)) for f in SCORE_FIELDS))
+
+
+def score_tol2(tol):
+    """The squared tolerance the score calls take: floor(tol^2) for a finite tol >= 0, capped at 2^32 - 1."""
+    if isinstance(tol, bool) or not isinstance(tol, (int, float)) or not math.isfinite(tol) or tol < 0:
+        raise ValueError(f"tol must be a finite number >= 0, got {tol!r}")
+    return min(int(math.floor(tol * tol)), 0xFFFFFFFF)
 
 
 class CvhError(RuntimeError):
@@ -172,6 +236,9 @@ def lib():
         "cvh_luma_image_batch": (C.c_int, [C.POINTER(vp), C.POINTER(vp), C.c_int, C.c_int]),
         "cvh_energy": (C.c_int, [vp, C.POINTER(EnergyTerms)]),
         "cvh_energy_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.POINTER(EnergyTerms)]),
+        "cvh_score_mask": (C.c_int, [vp, u8p, C.c_int, C.c_uint32, C.POINTER(MaskScore)]),
+        "cvh_score_mask_device": (C.c_int, [vp, vp, C.c_int, C.c_uint32, C.POINTER(MaskScore), vp]),
+        "cvh_score_mask_device_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.POINTER(vp), C.c_int, C.c_uint32, C.POINTER(MaskScore), vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -560,6 +627,20 @@ def energy_batch(contexts):
     return [_energy_of(out[i], contexts[i].channels) for i in range(n)]
 
 
+def score_batch(contexts, truths, invert=False, tol=2.0, stream=0):
+    """cvh_score_mask_device_batch: Context.score for n contexts (any mix of shapes and channel counts) against n truth planes in device
+    memory (integer addresses of h * w bytes, non-zero = foreground), with one set of launches and one host wait.  Returns [Score] per
+    context; every integer is the member's own Context.score()."""
+    contexts, truths = list(contexts), [int(t) or None for t in truths]
+    n = len(contexts)
+    if len(truths) != n:
+        raise ValueError(f"{n} contexts but {len(truths)} truth planes")
+    out = (MaskScore * max(n, 1))()
+    ptrs = (C.c_void_p * max(n, 1))(*truths)
+    _batch_chk(lib().cvh_score_mask_device_batch(_member_array(contexts), n, ptrs, int(bool(invert)), score_tol2(tol), out, int(stream) or None))
+    return [_score_of(out[i]) for i in range(n)]
+
+
 def _monitor_args(max_steps, every, rel_plateau):
     for name, v in (("max_steps", max_steps), ("every", every)):
         if not isinstance(v, int) or isinstance(v, bool):
@@ -795,6 +876,21 @@ class Context:
         t = EnergyTerms()
         _batch_chk(self._L.cvh_energy(self._h, C.byref(t)))
         return _energy_of(t, self.channels)
+
+    def score(self, truth, invert=False, tol=2.0, stream=0):
+        """cvh_score_mask / cvh_score_mask_device: the mask of the current level set against a ground truth (non-zero = foreground),
+        scored on the device (Score): overlap counts, surface sizes and the exact surface distances.  truth is a numpy array of
+        (h, w) -- bool or uint8, staged by the library -- or the integer address of h * w bytes in device memory, ordered behind
+        `stream`; tol is the surface tolerance in pixels (tol2 = floor(tol^2)).  Only reads: a run continued after it is bit-identical
+        to one without."""
+        s, tol2 = MaskScore(), score_tol2(tol)
+        if isinstance(truth, np.ndarray):
+            t = np.ascontiguousarray(truth.view(np.uint8) if truth.dtype == np.bool_ else truth, dtype=np.uint8)
+            assert t.shape == (self.h, self.w)
+            _batch_chk(self._L.cvh_score_mask(self._h, _u8p(t), int(bool(invert)), tol2, C.byref(s)))
+        else:
+            _batch_chk(self._L.cvh_score_mask_device(self._h, int(truth) or None, int(bool(invert)), tol2, C.byref(s), int(stream) or None))
+        return _score_of(s)
 
     def get_trace(self, max_rows):
         out = np.zeros((max(max_rows, 1), 2 * self.channels + 1), dtype=np.float64)

@@ -290,6 +290,25 @@ __host__ __device__ constexpr unsigned cvh_energy_items(int h, int w)
 }
 unsigned cvh_energy_blocks(int h, int w);
 hipError_t cvh_launch_energy(const CvhIoMember *tab, int nmem, unsigned grid, hipStream_t s);   // the term pass, then the reduce pass
+// mask scores (score_kernels.hip).  src the level set, src2 the truth bytes, plane[0] the member's four planes of band words (class of the
+// mask, class of the truth, surface of the mask, surface of the truth: cvh_score_words_bytes apart), plane[1] the two vertical distance
+// fields (one unsigned per pixel: low half to the nearest pixel of surf(T) in the column, high half to surf(M), 0xffff = none) -- the
+// context's workspace --, sums the member's result row of CVH_SCORE_ROW 64-bit words, zeroed: tp, fp, fn, tn, surf_m, surf_t, within_m,
+// within_t, dist_m_q16, dist_t_q16, hd2_m, hd2_t (the maxima in the words' low halves).  Bands and chunks are the reinitialisation's.
+#define CVH_SCORE_ROW 16
+enum { CVH_SCORE_TP, CVH_SCORE_FP, CVH_SCORE_FN, CVH_SCORE_TN, CVH_SCORE_SURF_M, CVH_SCORE_SURF_T, CVH_SCORE_WITHIN_M, CVH_SCORE_WITHIN_T,
+       CVH_SCORE_DIST_M, CVH_SCORE_DIST_T, CVH_SCORE_HD2_M, CVH_SCORE_HD2_T };
+__host__ __device__ constexpr size_t cvh_score_words_bytes(int h, int w)
+{
+  return ((size_t)((h + CVH_REINIT_BAND - 1) / CVH_REINIT_BAND) * (size_t)w * sizeof(unsigned) + 255) & ~(size_t)255;
+}
+// bytes of a member's workspace: [four planes of band words][distance fields][truth plane of the host form]
+inline size_t cvh_score_truth_offset(int h, int w) { return 4 * cvh_score_words_bytes(h, w) + (size_t)h * (size_t)w * sizeof(unsigned); }
+inline size_t cvh_score_workspace_bytes(int h, int w) { return cvh_score_truth_offset(h, w) + (size_t)h * (size_t)w; }
+// the four launches of one call: cols / rows are the member tables of launches 1 - 3 and of launch 4 (cvh_reinit_column_blocks /
+// cvh_reinit_row_blocks workgroups per member), max_w the widest member (sizes the LDS window of launch 4)
+hipError_t cvh_launch_score(const CvhIoMember *cols, unsigned col_grid, const CvhIoMember *rows, unsigned row_grid, int nmem, int max_w,
+                            int invert, unsigned tol2, hipStream_t s);
 // rows-per-tile options of the step kernel
 void cvh_step_grid(int h, int w, int tile_rows, int *tiles_x, int *tiles_y);
 int cvh_step_max_blocks(int h, int w);

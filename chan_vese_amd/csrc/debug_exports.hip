@@ -95,6 +95,9 @@ extern "C" int cvh_debug_colour_block_pixels(void) { return CVH_COLOUR_BLOCK_PIX
 // Diagnostic (not part of include/chanvese_hip.h): launch sets of cvh_energy / cvh_energy_batch so far in this process -- one set is the
 // term pass and the reduce pass of energy_kernels.hip over all members of the call (tests/test_gpu_energy.py: a batch of n is one set)
 extern "C" unsigned long cvh_debug_energy_launch_sets(void) { return g_launches[kEnergyLaunchSets].load(); }
+// Diagnostic (not part of include/chanvese_hip.h): launch sets of cvh_score_mask* so far in this process -- one set is the four launches of
+// score_kernels.hip over all members of the call (tests/test_gpu_score.py: a batch of n is one set)
+extern "C" unsigned long cvh_debug_score_launch_sets(void) { return g_launches[kScoreLaunchSets].load(); }
 
 // Diagnostic (not part of include/chanvese_hip.h): device time (HIP events on the leader's stream: table copy, the three launches, flag
 // copy) of the last cvh_reinit / cvh_reinit_batch this context led (tools/reinit_probe.py).

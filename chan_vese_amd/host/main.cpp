@@ -19,7 +19,9 @@
 // text of -O is not rendered (no font rasteriser here), --fps has nothing to act on.
 // Additions that do not collide with reference options: --dump-u, --dump-mask, --device, --math,
 // --state, --rect, --circ, --disk, --init, --threshold, --reinit, --connectivity, --min-area, --fill-holes, --largest, --roi, --verbose,
-// --levels, --energy, --energy-every.  --energy prints "energy total length area fit_in... fit_out..." (chanvese_hip.h, "Energy"; %.17g, one
+// --levels, --energy, --energy-every, --truth, --score-tol.  --truth FILE scores the final mask (inverted with -i) against a ground-truth PNG / PGM of
+// the input's size (non-zero = foreground) on the device (chanvese_hip.h, "Mask scores") and prints one line "score: iou=... dice=...
+// hausdorff=... assd=... surface_dice=... tp=... fp=... fn=... tn=..." to stdout; --score-tol T is the surface tolerance in pixels.  --energy prints "energy total length area fit_in... fit_out..." (chanvese_hip.h, "Energy"; %.17g, one
 // fit_in and one fit_out per channel) to stdout after the run; --energy-every K runs in segments of K iterations and prints one such line,
 // prefixed by the iteration count, after each (not with -V, --reinit, --levels).  --levels L > 1 is a coarse-to-fine run (chanvese_hip.h, "Coarse-to-fine"): L contexts, each half the one before; after -S
 // the planes are restricted down the chain, the start is built on the COARSEST level (the numbers of --rect / --disk, given in pixels of
@@ -185,7 +187,7 @@ const Spec kSpecs[] = {
     {"dump-u", 0, 1}, {"dump-mask", 0, 1}, {"device", 0, 1}, {"math", 0, 1}, {"state", 0, 1}, {"rect", 0, 1}, {"circ", 0, 1}, {"reinit", 0, 1},
     {"disk", 0, 1}, {"init", 0, 1}, {"threshold", 0, 1}, {"levels", 0, 1}, {"colorspace", 0, 1},
     {"connectivity", 0, 1}, {"min-area", 0, 1}, {"fill-holes", 0, 1}, {"largest", 0, 0}, {"roi", 0, 0},
-    {"verbose", 0, 0}, {"energy", 0, 0}, {"energy-every", 0, 1}};
+    {"verbose", 0, 0}, {"energy", 0, 0}, {"energy-every", 0, 1}, {"truth", 0, 1}, {"score-tol", 0, 1}};
 
 struct Parsed {
   std::vector<std::pair<std::string, std::vector<std::string>>> opts;
@@ -343,6 +345,9 @@ void print_help()
       "  --energy                           print 'energy total length area fit_in... fit_out...' of the final level set to stdout (%.17g)\n"
       "  --energy-every arg (=0)            run in segments of arg iterations and print such a line, prefixed by the iteration count, after\n"
       "                                     each (0: never); -N stays the total; not with -V, --reinit, --levels\n"
+      "  --truth arg                        ground-truth PNG / PGM of the input's size (non-zero = foreground): print 'score: iou= dice=\n"
+      "                                     hausdorff= assd= surface_dice= tp= fp= fn= tn=' of the final mask (inverted with -i) to stdout\n"
+      "  --score-tol arg (=2)               surface tolerance of --truth in pixels (surface_dice counts distances <= arg)\n"
       "  --verbose                          print the iteration count and last norm to stderr\n"
       "\n";
 }
@@ -410,6 +415,10 @@ int main(int argc, char **argv)
   const bool print_energy = vm.count("energy");
   int energy_every = 0;
   if (auto v = one("energy-every")) energy_every = to_int("energy-every", *v);
+  std::string truth_filename;
+  if (auto v = one("truth")) truth_filename = *v;
+  double score_tol = 2.0;
+  if (auto v = one("score-tol")) score_tol = to_double("score-tol", *v);
   segment = vm.count("segment"); grayscale = vm.count("grayscale"); write_video = vm.count("video");
   overlay_text = vm.count("overlay-text"); invert = vm.count("invert-selection");
   object_selection = vm.count("select"); rectangle_contour = vm.count("rectangle"); circle_contour = vm.count("circle");
@@ -488,6 +497,8 @@ int main(int argc, char **argv)
   if (energy_every > 0 && write_video) msg_exit("An energy series (--energy-every) cannot be combined with video output (-V).");
   if (energy_every > 0 && reinit_every > 0) msg_exit("An energy series (--energy-every) cannot be combined with reinitialisation (--reinit).");
   if (energy_every > 0 && levels > 1) msg_exit("An energy series (--energy-every) cannot be combined with a coarse-to-fine run (--levels).");
+  if (vm.count("score-tol") && truth_filename.empty()) msg_exit("A score tolerance (--score-tol) needs a ground truth (--truth).");
+  if (!(score_tol >= 0.0) || !std::isfinite(score_tol)) msg_exit("Score tolerance must be a finite number >= 0.");
   int colour_space = 0;   // 0: the planes stay B, G, R
   if (vm.count("colorspace")) {
     if (iequals(colorspace, "ycrcb")) colour_space = CVH_COLOUR_YCRCB;
@@ -504,6 +515,21 @@ int main(int argc, char **argv)
   const int h = file.h, w = file.w;
   const size_t n = (size_t)h * w;
   const int nof_channels = grayscale ? 1 : 3;
+  std::vector<uint8_t> truth;   // --truth: one byte per pixel, non-zero = foreground
+  if (!truth_filename.empty()) {
+    Image t;
+    bool truth_is_png = false;
+    if (!read_image(truth_filename, t, truth_is_png)) msg_exit("Error on opening \"" + truth_filename + "\" (probably not an image)!");
+    if (t.h != h || t.w != w)
+      msg_exit("The ground truth \"" + truth_filename + "\" is " + std::to_string(t.w) + " x " + std::to_string(t.h) + ", the input " +
+               std::to_string(w) + " x " + std::to_string(h) + ": they must have the same size.");
+    truth.resize(n);
+    for (size_t q = 0; q < n; ++q) {
+      uint8_t any = 0;
+      for (int k = 0; k < t.channels; ++k) any |= t.px[(size_t)t.channels * q + k];
+      truth[q] = any;
+    }
+  }
   // img: what the reference calls `img` (3 channels, BGR); planes: what cv::split leaves (:934-937)
   std::vector<uint8_t> img_bgr(n * 3);
   std::vector<std::vector<uint8_t>> planes(nof_channels, std::vector<uint8_t>(n));
@@ -731,6 +757,20 @@ int main(int argc, char **argv)
     run_with_frames();
   }
   if (print_energy) energy_line(-1);
+  if (!truth.empty()) {   // the derived figures as the header spells them; nan where a denominator is 0 or a surface is empty
+    cvh_mask_score s;
+    const double t2 = std::floor(score_tol * score_tol);
+    cvh_check(ctx, cvh_score_mask(ctx, truth.data(), invert ? 1 : 0, t2 >= 4294967295.0 ? 0xffffffffu : (uint32_t)t2, &s), "cvh_score_mask");
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    auto ratio = [&](double num, double den) { return den != 0.0 ? num / den : nan; };
+    const double surf = (double)(s.surf_m + s.surf_t);
+    std::printf("score: iou=%.17g dice=%.17g hausdorff=%.17g assd=%.17g surface_dice=%.17g tp=%llu fp=%llu fn=%llu tn=%llu\n",
+                ratio((double)s.tp, (double)(s.tp + s.fp + s.fn)), ratio(2.0 * (double)s.tp, (double)(2 * s.tp + s.fp + s.fn)),
+                s.defined ? std::sqrt((double)std::max(s.hd2_m, s.hd2_t)) : nan,
+                s.defined ? ratio((double)(s.dist_m_q16 + s.dist_t_q16) / 65536.0, surf) : nan,
+                s.defined ? ratio((double)(s.within_m + s.within_t), surf) : nan, (unsigned long long)s.tp, (unsigned long long)s.fp,
+                (unsigned long long)s.fn, (unsigned long long)s.tn);
+  }
 
   if (!dump_u.empty()) {
     std::vector<double> u(n);

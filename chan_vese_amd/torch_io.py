@@ -276,6 +276,20 @@ class Segmenter:
         (cvh_energy_batch: one set of launches, one host wait).  Returns [capi.Energy], each bit for bit its context's Context.energy()."""
         return capi.energy_batch(self.contexts)
 
+    def score(self, truths, invert=False, tol=2.0):
+        """Every member's mask against its ground truth (cvh_score_mask_device_batch: one set of launches on the device, one host wait):
+        truths is a uint8 or bool device tensor (N, H, W), non-zero = foreground (a bool tensor is viewed as uint8, no copy), ordered
+        behind the current stream; tol the surface tolerance in pixels.  Returns [capi.Score], each integer its context's Context.score()."""
+        if not isinstance(truths, torch.Tensor) or truths.dtype not in (torch.uint8, torch.bool):
+            raise ValueError(f"truths must be a uint8 or bool tensor, got {getattr(truths, 'dtype', type(truths))}")
+        if tuple(truths.shape) != (self.n, self.h, self.w):
+            raise ValueError(f"truths must have shape {(self.n, self.h, self.w)}, got {tuple(truths.shape)}")
+        _check_device(truths, self.device, "truths")
+        t = truths.view(torch.uint8) if truths.dtype == torch.bool else truths
+        if not t.is_contiguous():
+            t = t.contiguous()
+        return capi.score_batch(self.contexts, [t[i].data_ptr() for i in range(self.n)], invert, tol, self._stream())
+
     def components(self, conn=4, invert=False):
         """The connected components of every member's mask (cvh_components_batch): (labels, counts), labels an int32 tensor (N, H, W) --
         0 background, 1..K in the order of scipy.ndimage.label -- valid for the next operation on the current stream, counts the K of

@@ -647,6 +647,61 @@ typedef struct cvh_energy_terms {
 int cvh_energy(cvh_context *ctx, cvh_energy_terms *out);
 int cvh_energy_batch(cvh_context *const *ctxs, int n, cvh_energy_terms *out);
 
+/* ---- Mask scores ------------------------------------------------------------------------------------------------------------
+ * How far the current segmentation is from a ground-truth mask, on the device: overlap (IoU, Dice) and boundary measures (Hausdorff
+ * distance, average symmetric surface distance, surface Dice at a tolerance) -- what a caller otherwise takes with cvh_get_mask (one
+ * byte per pixel across PCIe), a host pass and a Euclidean distance transform.  Everything is defined in INTEGERS, so every field of
+ * cvh_mask_score is exact and can be compared with ==; no result depends on the grid, the schedule or the batch.
+ * Masks.  For a context of h x w and a truth plane t of h x w bytes, row-major:
+ *     M(p) = (((float)u(p) > 0) != invert)    cvh_get_mask's rule: NaN, -0.0 and a positive double that rounds to 0.0f are outside;
+ *                                             with "state" = 32 the class comes from the float state, as in cvh_reinit / cvh_components
+ *     T(p) = (t(p) != 0)
+ * Overlap.  tp, fp, fn, tn count the pixels with (M, T) = (1,1), (1,0), (0,1), (0,0).
+ * Surface.  surf(S) is the set of pixels of S with a 4-neighbour that is not in S; a neighbour outside the plane counts as not in S, so a
+ * foreground pixel in the first or last row or column is always surface (S & ~binary_erosion(S, cross, border_value = 0)).  surf_m and
+ * surf_t are the sizes of surf(M) and surf(T).
+ * Distances.  For p in surf(M), d2_m(p) is the minimum over q in surf(T) of the squared pixel distance (row difference^2 + column
+ * difference^2), an exact integer; d2_t(p) for p in surf(T) is the same against surf(M).
+ *     q16(d2) = llrint(sqrt((double)d2) * 65536)     an IEEE sqrt, an exact multiply by 2^16, a round-half-even: 16.16 fixed point
+ *     hd2_m, hd2_t             the maximum of d2_m / d2_t over its surface: the two directed Hausdorff distances, squared
+ *     dist_m_q16, dist_t_q16   the sum of q16(d2) over the surface
+ *     within_m, within_t       the surface pixels with d2 <= tol2 (tol2: the call's squared tolerance in pixels)
+ *     defined                  1 when both surfaces are non-empty, else 0: then the six distance fields are 0, the overlap and surface
+ *                              counts are still valid, and the call succeeds
+ * Bounds: h^2 + w^2 < 2^32 and h w < 2^31; under them a 16.16 term is at most 2^32 and the sums cannot overflow 64 bits.
+ * Derived figures (host arithmetic in doubles; chan_vese_amd/capi.py Score implements them once):
+ *     iou = tp / (tp + fp + fn)                 dice = 2 tp / (2 tp + fp + fn)
+ *     hausdorff = sqrt(max(hd2_m, hd2_t))       assd = (dist_m_q16 + dist_t_q16) / 65536 / (surf_m + surf_t)
+ *     surface_dice = (within_m + within_t) / (surf_m + surf_t)
+ * each NaN where its denominator is 0 or, for the last three, `defined` is 0.
+ * Determinism: the sums are integers, combined by 64-bit adds and 32-bit maxima (vector atomics, one per workgroup and field): a member
+ * alone or inside any batch, and two calls in a row, give the same bits (chan_vese_amd/csrc/score_kernels.hip).
+ * cvh_score_mask takes host bytes: they are staged into the context's workspace and the device path runs.  cvh_score_mask_device and
+ * cvh_score_mask_device_batch take device pointers under the rules of "Device-memory input and output": any byte alignment, memory
+ * that kernels on the context's device can address, ordered behind what `stream` holds at the call.  The batch form serves n contexts of
+ * one device, any mix of shapes and channel counts, and writes out[0 .. n-1]: ONE set of launches on member 0's stream, joined with
+ * every member's stream before and after, and ONE host wait, for the result rows (the truth planes have been read when the call
+ * returns).  The single forms are the same path with n = 1.
+ * The calls only READ the level set: iterations in flight are settled first and the FP64 mirror of a float state is refreshed, as the
+ * getters do; level set, run state, sums, options and planes are untouched, and a run continued after the call is bit-identical to one
+ * without it.  An image is not required.  A context's first call allocates its workspace (5.5 bytes per pixel), kept until cvh_destroy.
+ * Cost, one run of tools/score_probe.py on an MI355X (host clock around a call and its wait, 20 calls, measured once):
+ * 142 / 999 / 512 us at 1024^2 / 2048^2 / 4096^2 for a noisy disk after 50 iterations against the clean disk -- the cost follows the
+ * number of surface pixels and the length of their searches, not the plane -- beside 116 / 458 / 1712 ms for the same integers from
+ * cvh_get_mask, numpy and scipy's distance transform.
+ * CVH_ERR_ARG: out, truth or d_truths NULL or a NULL entry of d_truths; a pointer that is not device-accessible memory of the context's
+ * device; ctxs NULL, n < 1, a NULL or duplicate member, members on different devices; a plane beyond the bounds.  CVH_ERR_STATE: a member
+ * without a level set.  Every member is checked before anything is launched and `out` is written only by a call that succeeds; the
+ * message names the member index and is cvh_last_error(NULL)'s (and member 0's). */
+typedef struct cvh_mask_score {
+  uint64_t tp, fp, fn, tn, surf_m, surf_t, within_m, within_t, dist_m_q16, dist_t_q16;
+  uint32_t hd2_m, hd2_t; int32_t defined, pad;
+} cvh_mask_score;
+int cvh_score_mask(cvh_context *ctx, const uint8_t *truth, int invert, uint32_t tol2, cvh_mask_score *out);              /* host bytes */
+int cvh_score_mask_device(cvh_context *ctx, const uint8_t *d_truth, int invert, uint32_t tol2, cvh_mask_score *out, void *stream);
+int cvh_score_mask_device_batch(cvh_context *const *ctxs, int n, const uint8_t *const *d_truths, int invert, uint32_t tol2,
+                                cvh_mask_score *out, void *stream);
+
 /* Library version string, e.g. "chanvese_hip 0.1 (gfx950)". */
 const char *cvh_version(void);
 
