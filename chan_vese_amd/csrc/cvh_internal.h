@@ -266,6 +266,8 @@ hipError_t cvh_launch_init_start(const CvhIoMember *tab, const CvhInitStart *par
 // coarse-to-fine (pyramid_kernels.hip).  Restrict: plane[] the coarse member's planes (written), src / src_stride / h2 / w2 the fine
 // planes, sums as the ingest's.  Prolong: src the coarse level set ((h + 1) / 2 x (w + 1) / 2 doubles), dst the fine one (h x w),
 // state_zero / chain_zero as the checkerboard's.
+size_t cvh_restrict_items(int fine_h, int fine_w);   // what a pair's lanes share out, an item per lane and trip
+size_t cvh_prolong_items(int fine_h, int fine_w);
 unsigned cvh_restrict_blocks(int fine_h, int fine_w);
 unsigned cvh_prolong_blocks(int fine_h, int fine_w);
 hipError_t cvh_launch_restrict(const CvhIoMember *tab, int nmem, unsigned grid, hipStream_t s);

@@ -30,6 +30,42 @@ extern "C" int cvh_debug_data_flow(int h, int w, int channels, int math_mode, in
   return CVH_OK;
 }
 
+// Diagnostic (not part of include/chanvese_hip.h): the grid section and the work of ONE member of h x w pixels in a member-table kernel,
+// without a device -- from the very functions the host units size a member's section with.  *items: the units the section's lanes, waves
+// or workgroups share out; *nblk: its workgroups; *takers: how many units a workgroup takes per trip (CVH_BLOCK lanes, CVH_BLOCK / 64
+// waves, or 1 where a workgroup owns a whole row or slot).  A unit i >= nblk * takers is taken on a second or later trip
+// (tests/test_trip_counts.py pins the shapes of tests/test_gpu_second_trips.py to that).  For the two pyramid operations h x w is the FINE
+// grid, as for cvh_restrict_blocks / cvh_prolong_blocks.
+enum {
+  TRIPS_IO = 0,          // ingest, image out, mask, histogram: 16-pixel pieces over lanes (the n % 16 last pixels go apart)
+  TRIPS_START,           // threshold / rect / disk starts: pixel pairs over lanes (an odd last pixel goes apart)
+  TRIPS_RESTRICT,        // 16 coarse pixels of a row, or the row's tail, over lanes
+  TRIPS_PROLONG,         // two coarse pixels of a row over lanes
+  TRIPS_ENERGY_TERMS,    // items (CVH_ENERGY_BAND rows x CVH_ENERGY_COLS columns) over waves
+  TRIPS_ENERGY_REDUCE,   // item rows over the lanes of the member's one workgroup
+  TRIPS_ROWS,            // reinit and score, row launch: rows over workgroups
+  TRIPS_COLUMNS,         // reinit and score, column launches: band x 256-column slots, a workgroup each
+  TRIPS_NOPS
+};
+
+extern "C" int cvh_debug_trip_counts(int op, int h, int w, unsigned long long *items, unsigned *nblk, unsigned *takers)
+{
+  if (op < 0 || op >= TRIPS_NOPS || h < 1 || w < 1 || !items || !nblk || !takers) return CVH_ERR_ARG;
+  const size_t n = (size_t)h * (size_t)w;
+  const unsigned bands = ((unsigned)h + CVH_REINIT_BAND - 1) / CVH_REINIT_BAND, chunks = ((unsigned)w + CVH_BLOCK - 1) / CVH_BLOCK;
+  switch (op) {
+    case TRIPS_IO: *items = n / 16; *nblk = cvh_io_blocks(n); *takers = CVH_BLOCK; break;
+    case TRIPS_START: *items = n / 2; *nblk = cvh_init_start_blocks(n); *takers = CVH_BLOCK; break;
+    case TRIPS_RESTRICT: *items = cvh_restrict_items(h, w); *nblk = cvh_restrict_blocks(h, w); *takers = CVH_BLOCK; break;
+    case TRIPS_PROLONG: *items = cvh_prolong_items(h, w); *nblk = cvh_prolong_blocks(h, w); *takers = CVH_BLOCK; break;
+    case TRIPS_ENERGY_TERMS: *items = cvh_energy_items(h, w); *nblk = cvh_energy_blocks(h, w); *takers = CVH_BLOCK / 64; break;
+    case TRIPS_ENERGY_REDUCE: *items = cvh_energy_items(h, w); *nblk = 1; *takers = CVH_BLOCK; break;
+    case TRIPS_ROWS: *items = (unsigned long long)h; *nblk = cvh_reinit_row_blocks(h); *takers = 1; break;
+    case TRIPS_COLUMNS: *items = (unsigned long long)bands * chunks; *nblk = cvh_reinit_column_blocks(h, w); *takers = 1; break;
+  }
+  return CVH_OK;
+}
+
 // Diagnostic (not part of include/chanvese_hip.h): the tile grid of the resident flow (csv_resident_kernel.hip) for a plane of `channels`
 // channels on `num_cus` CUs, one workgroup per CU, without a device -- the arithmetic resident_geometry() ends in.  Returns 1 and fills
 // tiles_x, tiles_y and the rows of the tallest tile, or 0: the plane does not qualify (odd width, < 16 rows or columns, more rows per tile

@@ -120,19 +120,23 @@ unsigned capped_blocks(size_t items)
 
 }  // namespace
 
-// workgroups of a pair in the restrict kernel: an item is 16 coarse pixels of a row, or the row's tail
-unsigned cvh_restrict_blocks(int fine_h, int fine_w)
+// items of a pair in the restrict kernel: an item is 16 coarse pixels of a row, or the row's tail (the kernel's hc * per_row)
+size_t cvh_restrict_items(int fine_h, int fine_w)
 {
   const unsigned wc = ((unsigned)fine_w + 1) / 2, full = (unsigned)fine_w / 32;
-  return capped_blocks((size_t)(((unsigned)fine_h + 1) / 2) * (full + (16 * full < wc ? 1u : 0u)));
+  return (size_t)(((unsigned)fine_h + 1) / 2) * (full + (16 * full < wc ? 1u : 0u));
 }
 
-// workgroups of a pair in the prolong kernel: an item is two coarse pixels of a row
-unsigned cvh_prolong_blocks(int fine_h, int fine_w)
+// items of a pair in the prolong kernel: an item is two coarse pixels of a row
+size_t cvh_prolong_items(int fine_h, int fine_w)
 {
   const unsigned wc = ((unsigned)fine_w + 1) / 2;
-  return capped_blocks((size_t)(((unsigned)fine_h + 1) / 2) * ((wc + 1) / 2));
+  return (size_t)(((unsigned)fine_h + 1) / 2) * ((wc + 1) / 2);
 }
+
+// workgroups of a pair in the two kernels: a lane takes an item per trip
+unsigned cvh_restrict_blocks(int fine_h, int fine_w) { return capped_blocks(cvh_restrict_items(fine_h, fine_w)); }
+unsigned cvh_prolong_blocks(int fine_h, int fine_w) { return capped_blocks(cvh_prolong_items(fine_h, fine_w)); }
 
 hipError_t cvh_launch_restrict(const CvhIoMember *tab, int nmem, unsigned grid, hipStream_t s)
 {
