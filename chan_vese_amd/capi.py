@@ -39,9 +39,17 @@ EXPORTS = [
     "cvh_convert_colour", "cvh_convert_colour_batch", "cvh_luma_image", "cvh_luma_image_batch",
     "cvh_energy", "cvh_energy_batch",
     "cvh_score_mask", "cvh_score_mask_device", "cvh_score_mask_device_batch",
+    "cvh_measure", "cvh_measure_batch", "cvh_region_shape_of",
 ]
 # struct cvh_component: row k - 1 of a component table describes label k (first = smallest flat index; the box is inclusive)
 COMPONENT_DTYPE = np.dtype([("first", np.uint32), ("area", np.uint32), ("x0", np.int32), ("y0", np.int32), ("x1", np.int32), ("y1", np.int32)])
+# struct cvh_region (128 bytes): row k - 1 of a measure table describes label k ("Component measures" in include/chanvese_hip.h)
+REGION_DTYPE = np.dtype([("first", np.uint32), ("area", np.uint32), ("x0", np.int32), ("y0", np.int32), ("x1", np.int32), ("y1", np.int32),
+                         ("border", np.uint32), ("reserved", np.uint32)] +
+                        [(f, np.uint64) for f in ("perimeter", "sx", "sy", "sxx", "syy", "sxy")] + [("s1", np.uint64, 3), ("s2", np.uint64, 3)])
+# struct cvh_region_shape: what cvh_region_shape_of derives from a row
+REGION_SHAPE_DTYPE = np.dtype([(f, np.float64) for f in ("cx", "cy", "mu20", "mu02", "mu11", "theta", "major", "minor")] +
+                              [("mean", np.float64, 3), ("var", np.float64, 3)])
 LAYOUT_PLANAR, LAYOUT_INTERLEAVED = 0, 1
 # "Colour spaces": which plane is which primary, and the spaces cvh_convert_colour knows
 ORDERS = {"bgr": 0, "rgb": 1}
@@ -239,6 +247,9 @@ def lib():
         "cvh_score_mask": (C.c_int, [vp, u8p, C.c_int, C.c_uint32, C.POINTER(MaskScore)]),
         "cvh_score_mask_device": (C.c_int, [vp, vp, C.c_int, C.c_uint32, C.POINTER(MaskScore), vp]),
         "cvh_score_mask_device_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.POINTER(vp), C.c_int, C.c_uint32, C.POINTER(MaskScore), vp]),
+        "cvh_measure": (C.c_int, [vp, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, vp, C.c_int, ip, vp]),
+        "cvh_measure_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, C.POINTER(vp), ip, ip, vp]),
+        "cvh_region_shape_of": (C.c_int, [vp, C.c_int, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -641,6 +652,45 @@ def score_batch(contexts, truths, invert=False, tol=2.0, stream=0):
     return [_score_of(out[i]) for i in range(n)]
 
 
+def _clean_args(conn, invert, min_area, fill_holes, keep_largest):
+    return int(conn), int(bool(invert)), int(min_area), int(fill_holes), int(keep_largest)
+
+
+def measure_batch(contexts, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False, cap=None, stream=0):
+    """cvh_measure_batch: Context.measure for n contexts (any mix of shapes and channel counts) with one set of launches.  cap: None
+    (all rows, at the price of a first call for the counts), one number for every member or one per member.  Returns [(K, table)] per
+    context; every row is bit for bit the member's own Context.measure()."""
+    contexts = list(contexts)
+    n = len(contexts)
+    args = _clean_args(conn, invert, min_area, fill_holes, keep_largest)
+    counts = (C.c_int * max(n, 1))()
+    if cap is None:
+        _batch_chk(lib().cvh_measure_batch(_member_array(contexts), n, *args, None, None, counts, int(stream) or None))
+        caps = [counts[i] for i in range(n)]
+    else:
+        caps = [int(c) for c in cap] if np.ndim(cap) else [int(cap)] * n
+        if len(caps) != n:
+            raise ValueError(f"cap: {len(caps)} values for {n} members")
+    tables = [np.zeros(max(c, 0), dtype=REGION_DTYPE) for c in caps]
+    if any(t.size for t in tables) or cap is not None:
+        ptrs = (C.c_void_p * max(n, 1))(*[t.ctypes.data if t.size else None for t in tables])
+        _batch_chk(lib().cvh_measure_batch(_member_array(contexts), n, *args, ptrs, (C.c_int * max(n, 1))(*caps), counts, int(stream) or None))
+    return [(counts[i], tables[i][:min(counts[i], tables[i].size)].copy()) for i in range(n)]
+
+
+def region_shapes(table, channels):
+    """cvh_region_shape_of for every row of a measure table (REGION_DTYPE): a structured array (REGION_SHAPE_DTYPE) of centroid, central
+    moments, orientation, the axes of the ellipse with the same moments, and mean and variance per channel.  Host arithmetic, no device."""
+    table = np.ascontiguousarray(table, dtype=REGION_DTYPE).reshape(-1)
+    out = np.zeros(table.size, dtype=REGION_SHAPE_DTYPE)
+    L = lib()
+    for i in range(table.size):
+        rc = L.cvh_region_shape_of(table.ctypes.data + i * REGION_DTYPE.itemsize, int(channels), out.ctypes.data + i * REGION_SHAPE_DTYPE.itemsize)
+        if rc != CVH_OK:
+            raise CvhError(rc, f"cvh_region_shape_of: row {i} (area {int(table['area'][i])}), channels {channels}")
+    return out
+
+
 def _monitor_args(max_steps, every, rel_plateau):
     for name, v in (("max_steps", max_steps), ("every", every)):
         if not isinstance(v, int) or isinstance(v, bool):
@@ -924,6 +974,23 @@ class Context:
         table = np.zeros(max(int(cap), 0), dtype=COMPONENT_DTYPE)
         self._chk(self._L.cvh_components(self._h, *args, int(labels_ptr) or None, table.ctypes.data if table.size else None, int(cap),
                                          C.byref(count), int(stream) or None))
+        return count.value, table[:min(count.value, table.size)].copy()
+
+    def measure(self, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False, cap=None, stream=0):
+        """cvh_measure: the components of the mask -- get_mask_clean's for the same five options, (0, 0, False) the raw one -- measured
+        on the device.  Returns (K, table): table is a structured array (REGION_DTYPE) of the first min(K, cap) rows: first, area, box,
+        border, perimeter, coordinate sums and the sums of the image planes and their squares (region_shapes derives centroid, moments,
+        axes, mean and variance).  cap = None asks for all K rows and COSTS TWO LABELLINGS (as components); pass a cap where an upper
+        bound of K is known, cap = 0 for the count alone.  Only reads: a run continued after it is bit-identical to one without."""
+        count = C.c_int(0)
+        args = _clean_args(conn, invert, min_area, fill_holes, keep_largest)
+        if cap is None:
+            _batch_chk(self._L.cvh_measure(self._h, *args, None, 0, C.byref(count), int(stream) or None))
+            if not count.value:
+                return 0, np.zeros(0, dtype=REGION_DTYPE)
+            cap = count.value
+        table = np.zeros(max(int(cap), 0), dtype=REGION_DTYPE)
+        _batch_chk(self._L.cvh_measure(self._h, *args, table.ctypes.data if table.size else None, int(cap), C.byref(count), int(stream) or None))
         return count.value, table[:min(count.value, table.size)].copy()
 
     def get_mask_clean(self, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False):

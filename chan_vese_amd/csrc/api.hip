@@ -143,6 +143,7 @@ extern "C" void cvh_destroy(cvh_context *c)
   if (c->d_reinit) (void)hipFree(c->d_reinit);
   if (c->d_cc) (void)hipFree(c->d_cc);
   if (c->d_cc_table) (void)hipFree(c->d_cc_table);
+  if (c->d_regions) (void)hipFree(c->d_regions);
   if (c->d_hist) (void)hipFree(c->d_hist);
   if (c->d_energy) (void)hipFree(c->d_energy);
   if (c->d_score) (void)hipFree(c->d_score);

@@ -305,6 +305,17 @@ hipError_t cvh_launch_cc_label(const CvhIoMember *tab, int nmem, unsigned grid, 
   return hipGetLastError();
 }
 
+// cvh_measure*: the numbered forest alone, K into the member's word.  mode 0 labels the class of the level set (with `invert`), mode 1 the
+// bytes of the mask in the member's dst
+hipError_t cvh_launch_cc_number(const CvhIoMember *tab, int nmem, unsigned grid, int mode, int conn, int invert, hipStream_t s)
+{
+  cc_launch_forest(tab, nmem, grid, mode, mode == 0 ? invert : 0, conn, s);
+  CC_LAUNCH(cc_flatten_count_kernel, grid);
+  CC_LAUNCH(cc_scan_kernel, (unsigned)nmem);
+  CC_LAUNCH(cc_number_kernel, grid);
+  return hipGetLastError();
+}
+
 // behind cvh_launch_cc_label: the rows of every member's table (dst, K rows)
 hipError_t cvh_launch_cc_table(const CvhIoMember *tab, int nmem, unsigned grid, hipStream_t s)
 {

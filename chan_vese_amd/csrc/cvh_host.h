@@ -3,7 +3,7 @@
 // context), csv_batch.hip (fused batch, and what every batch shares: the member and pair checks, the member predicates), pm_run.hip
 // (Perona-Malik), io_run.hip (device-memory I/O, reinitialisation, and the scaffolds of the member-table calls: MemberCall, write_planes,
 // the launch counters), init_run.hip (device-side initial level sets), components_run.hip (connected components), pyramid_run.hip
-// (coarse-to-fine), colour_run.hip (colour spaces), energy_run.hip (the functional's terms), score_run.hip (mask scores), debug_exports.hip (diagnostics).  Kernel sources do not include it.
+// (coarse-to-fine), colour_run.hip (colour spaces), energy_run.hip (the functional's terms), score_run.hip (mask scores), measure_run.hip (component measures), debug_exports.hip (diagnostics).  Kernel sources do not include it.
 #pragma once
 #include <limits.h>
 #include <math.h>
@@ -144,6 +144,8 @@ struct cvh_context {   // opaque to callers; four groups
   void *d_cc = nullptr;          // workspace of cvh_components* / cvh_get_mask_clean* (components_kernels.hip), and the rows of the last
   void *d_cc_table = nullptr;    // table: allocated by the first call that needs them, kept -- not part of live_footprint either
   size_t cc_table_rows = 0;
+  void *d_regions = nullptr;     // the rows of this context's last cvh_measure* table (measure_run.hip): 128 bytes per row asked for, grown on demand, kept
+  size_t region_rows = 0;
   unsigned *d_hist = nullptr;    // the 255 C + 1 counters of cvh_histogram* / cvh_otsu_threshold / cvh_init_otsu* (init_kernels.hip): allocated by
                                  // the first call, kept
   void *d_energy = nullptr;      // workspace of cvh_energy* (energy_run.hip): a CvhState for means taken beside the run's, then the item rows of
@@ -261,6 +263,13 @@ int mask_out(cvh_context *const *ctxs, int n, uint8_t *const *d_masks, int inver
 void checkerboard_factors(int h, int w, double *out);   // api.hip: out[0 .. h-1] = sin(pi i/5), out[h .. h+w-1] = sin(pi j/5), host libm
 void levelset_target(const cvh_context *c, CvhIoMember *m);
 int ensure_workspace(cvh_context *c, void **slot, size_t bytes, const char *name, bool mirror = true);
+
+// components_run.hip: what measure_run.hip shares with the components calls -- cvh_get_mask_clean*'s argument checks; every member has
+// a level set, is settled and has its workspace; the member table of the components launches (with two_tables the second table is the caller's)
+struct MemberCall;
+int cc_clean_args(cvh_context *const *ctxs, int n, int conn, long min_area, long fill_holes, int keep_largest, const char *what);
+int cc_members_ready(cvh_context *const *ctxs, int n, const char *what);
+int cc_fill_members(MemberCall *call, cvh_context *const *ctxs, int n, void *const *dst, const char *what, bool two_tables);
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) & ~(a - 1); }
 

@@ -251,6 +251,15 @@ hipError_t cvh_launch_cc_label(const CvhIoMember *tab, int nmem, unsigned grid, 
 hipError_t cvh_launch_cc_table(const CvhIoMember *tab, int nmem, unsigned grid, hipStream_t s);
 hipError_t cvh_launch_cc_clean(const CvhIoMember *tab, int nmem, unsigned grid, int conn, int invert, unsigned min_area, long fill_holes,
                                int keep_largest, hipStream_t s);
+hipError_t cvh_launch_cc_number(const CvhIoMember *tab, int nmem, unsigned grid, int mode, int conn, int invert, hipStream_t s);
+// component measures (measure_kernels.hip), behind cvh_launch_cc_number.  The numbering launches read the member table above (plane[] the
+// workspace); the measure launches read a SECOND table of the same members, because they need the image as well: src the parent words of
+// the numbered forest (the workspace's first plane), plane[] the context's C image planes, dst the member's rows (cvh_region), h2 the
+// number of rows dst holds -- min(K, cap); 0: the member's workgroups return at once --, sections of cvh_measure_blocks(n) workgroups,
+// CVH_MEASURE_TILE pixels in flat raster order each.  any_c1 / any_c3: a member with one / three channels exists (one launch each).
+#define CVH_MEASURE_TILE 8192
+unsigned cvh_measure_blocks(size_t n);
+hipError_t cvh_launch_measure(const CvhIoMember *tab, int nmem, unsigned grid, bool any_c1, bool any_c3, hipStream_t s);
 // device-side initial level sets (init_kernels.hip).  Histogram: plane[] the member's planes, sums its 255 C + 1 32-bit counters (zeroed
 // by the host), sections of cvh_io_blocks(n) workgroups.  Start: dst the level set written, plane[] read by the threshold mode,
 // state_zero / chain_zero as the checkerboard's; member i's start is par[i], a table behind the member table:

@@ -19,7 +19,9 @@
 // text of -O is not rendered (no font rasteriser here), --fps has nothing to act on.
 // Additions that do not collide with reference options: --dump-u, --dump-mask, --device, --math,
 // --state, --rect, --circ, --disk, --init, --threshold, --reinit, --connectivity, --min-area, --fill-holes, --largest, --roi, --verbose,
-// --levels, --energy, --energy-every, --truth, --score-tol.  --truth FILE scores the final mask (inverted with -i) against a ground-truth PNG / PGM of
+// --levels, --energy, --energy-every, --truth, --score-tol, --measure.  --measure FILE writes one CSV line per component of the mask --dump-mask
+// uses (the cleaning options and -I apply), measured on the device (chanvese_hip.h, "Component measures"): label, the integers of the row,
+// then centroid, central moments, orientation, axes, and mean and variance per channel (%.17g).  --truth FILE scores the final mask (inverted with -i) against a ground-truth PNG / PGM of
 // the input's size (non-zero = foreground) on the device (chanvese_hip.h, "Mask scores") and prints one line "score: iou=... dice=...
 // hausdorff=... assd=... surface_dice=... tp=... fp=... fn=... tn=..." to stdout; --score-tol T is the surface tolerance in pixels.  --energy prints "energy total length area fit_in... fit_out..." (chanvese_hip.h, "Energy"; %.17g, one
 // fit_in and one fit_out per channel) to stdout after the run; --energy-every K runs in segments of K iterations and prints one such line,
@@ -187,7 +189,7 @@ const Spec kSpecs[] = {
     {"dump-u", 0, 1}, {"dump-mask", 0, 1}, {"device", 0, 1}, {"math", 0, 1}, {"state", 0, 1}, {"rect", 0, 1}, {"circ", 0, 1}, {"reinit", 0, 1},
     {"disk", 0, 1}, {"init", 0, 1}, {"threshold", 0, 1}, {"levels", 0, 1}, {"colorspace", 0, 1},
     {"connectivity", 0, 1}, {"min-area", 0, 1}, {"fill-holes", 0, 1}, {"largest", 0, 0}, {"roi", 0, 0},
-    {"verbose", 0, 0}, {"energy", 0, 0}, {"energy-every", 0, 1}, {"truth", 0, 1}, {"score-tol", 0, 1}};
+    {"verbose", 0, 0}, {"energy", 0, 0}, {"energy-every", 0, 1}, {"truth", 0, 1}, {"score-tol", 0, 1}, {"measure", 0, 1}};
 
 struct Parsed {
   std::vector<std::pair<std::string, std::vector<std::string>>> opts;
@@ -348,6 +350,8 @@ void print_help()
       "  --truth arg                        ground-truth PNG / PGM of the input's size (non-zero = foreground): print 'score: iou= dice=\n"
       "                                     hausdorff= assd= surface_dice= tp= fp= fn= tn=' of the final mask (inverted with -i) to stdout\n"
       "  --score-tol arg (=2)               surface tolerance of --truth in pixels (surface_dice counts distances <= arg)\n"
+      "  --measure arg                      write one CSV line per component of the mask --dump-mask uses (cleaning options, -I): label,\n"
+      "                                     first,area,x0,y0,x1,y1,border,perimeter,cx,cy,mu20,mu02,mu11,theta,major,minor,mean..,var..\n"
       "  --verbose                          print the iteration count and last norm to stderr\n"
       "\n";
 }
@@ -417,6 +421,8 @@ int main(int argc, char **argv)
   if (auto v = one("energy-every")) energy_every = to_int("energy-every", *v);
   std::string truth_filename;
   if (auto v = one("truth")) truth_filename = *v;
+  std::string measure_filename;
+  if (auto v = one("measure")) measure_filename = *v;
   double score_tol = 2.0;
   if (auto v = one("score-tol")) score_tol = to_double("score-tol", *v);
   segment = vm.count("segment"); grayscale = vm.count("grayscale"); write_video = vm.count("video");
@@ -791,6 +797,31 @@ int main(int argc, char **argv)
     else cvh_check(ctx, cvh_get_mask(ctx, m.data(), invert ? 1 : 0), "cvh_get_mask");
     for (auto &v : m) v = v ? 255 : 0;
     if (!write_image(dump_mask, h, w, 1, m.data())) msg_exit("Error: cannot write \"" + dump_mask + "\"");
+  }
+
+  if (!measure_filename.empty()) {   // the components of that mask, measured on the device: one CSV line each
+    int count = 0;
+    cvh_check(ctx, cvh_measure(ctx, connectivity, invert ? 1 : 0, min_area, fill_holes, largest ? 1 : 0, nullptr, 0, &count, nullptr), "cvh_measure");
+    std::vector<cvh_region> table((size_t)count);
+    if (count)
+      cvh_check(ctx, cvh_measure(ctx, connectivity, invert ? 1 : 0, min_area, fill_holes, largest ? 1 : 0, table.data(), count, &count, nullptr), "cvh_measure");
+    FILE *f = std::fopen(measure_filename.c_str(), "w");
+    if (!f) msg_exit("Error: cannot write \"" + measure_filename + "\"");
+    std::fprintf(f, "label,first,area,x0,y0,x1,y1,border,perimeter,cx,cy,mu20,mu02,mu11,theta,major,minor");
+    for (const char *name : {"mean", "var"})
+      for (int k = 0; k < nof_channels; ++k) std::fprintf(f, ",%s%d", name, k);
+    std::fprintf(f, "\n");
+    for (int k = 0; k < count; ++k) {
+      const cvh_region &r = table[(size_t)k];
+      cvh_region_shape s;
+      if (cvh_region_shape_of(&r, nof_channels, &s) != CVH_OK) msg_exit("Error: cvh_region_shape_of refused row " + std::to_string(k));
+      std::fprintf(f, "%d,%u,%u,%d,%d,%d,%d,%u,%llu,%.17g,%.17g,%.17g,%.17g,%.17g,%.17g,%.17g,%.17g", k + 1, r.first, r.area, r.x0, r.y0, r.x1, r.y1,
+                   r.border, (unsigned long long)r.perimeter, s.cx, s.cy, s.mu20, s.mu02, s.mu11, s.theta, s.major, s.minor);
+      for (int j = 0; j < nof_channels; ++j) std::fprintf(f, ",%.17g", s.mean[j]);
+      for (int j = 0; j < nof_channels; ++j) std::fprintf(f, ",%.17g", s.var[j]);
+      std::fprintf(f, "\n");
+    }
+    if (std::fclose(f) != 0) msg_exit("Error: cannot write \"" + measure_filename + "\"");
   }
 
   // ---- selection: src/main.cpp:1004-1005

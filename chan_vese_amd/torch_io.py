@@ -306,6 +306,13 @@ class Segmenter:
                                          keep_largest, self._stream())
         return masks
 
+    def measure(self, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False, cap=None):
+        """The components of every member's mask -- clean_masks' for the same options, (0, 0, False) the raw one -- measured on the device
+        (cvh_measure_batch: one set of launches, ordered behind the current stream): one (K, table) per member, table a numpy structured
+        array (capi.REGION_DTYPE) of the first min(K, cap) rows, bit for bit its context's Context.measure(); capi.region_shapes derives
+        centroid, moments, axes, mean and variance from it.  cap = None asks for every row at the price of a first call for the counts."""
+        return capi.measure_batch(self.contexts, conn, invert, min_area, fill_holes, keep_largest, cap, self._stream())
+
     def levelsets(self, dtype=torch.float64):
         """The members' level sets as a device tensor (N, H, W), float64 or float32 (rounded to nearest even)."""
         if dtype not in (torch.float64, torch.float32):

@@ -702,6 +702,73 @@ int cvh_score_mask_device(cvh_context *ctx, const uint8_t *d_truth, int invert, 
 int cvh_score_mask_device_batch(cvh_context *const *ctxs, int n, const uint8_t *const *d_truths, int invert, uint32_t tol2,
                                 cvh_mask_score *out, void *stream);
 
+/* ---- Component measures -------------------------------------------------------------------------------------------------------
+ * "Connected components of the mask" labels, boxes and cleans; these calls MEASURE: per component where it is, how large, how
+ * elongated and how bright -- what a caller otherwise takes with cvh_get_mask, cvh_get_image (both across PCIe) and a pass of
+ * scipy.ndimage / skimage.regionprops on a CPU.  Every field of cvh_region is a sum (or a minimum / maximum) of INTEGERS: a member alone
+ * or inside any batch, and two calls in a row, give the same bits, and every field can be compared with ==.
+ * The mask measured is the one cvh_get_mask_clean defines for (conn, invert, min_area, fill_holes, keep_largest) -- with (0, 0, 0) the
+ * raw mask of cvh_get_mask --, labelled with `conn` in cvh_components' numbering: row k-1 describes label k.  With (0, 0, 0) the
+ * fields first, area, x0 .. y1 are cvh_components' table byte for byte.  Over the pixels p = (row r, column c) of label k:
+ *     first, area, x0, y0, x1, y1   as cvh_component
+ *     border      the number of the component's pixels in the first or last row or column
+ *     perimeter   the number of pixel edges of the component's pixels whose 4-neighbour across the edge is background or lies outside
+ *                 the plane (a foreground 4-neighbour always belongs to the same component, for either conn)
+ *     sx = sum c, sy = sum r, sxx = sum c^2, syy = sum r^2, sxy = sum r c
+ *     s1[k] = sum I_k(p), s2[k] = sum I_k(p)^2   over the context's C planes as they are now (after cvh_perona_malik: the smoothed
+ *                 planes), the bytes cvh_histogram reads; the entries of channels >= C are 0
+ *     reserved    0
+ * Bounds: h <= 65535, w <= 65535 and h w < 2^31; under them sxx, syy and sxy stay below 2^31 2^32 = 2^63 and every other sum far
+ * below that.
+ * cvh_region_shape_of (host only, no device, no context) derives the usual figures from a row, with A = area:
+ *     cx = (double)sx / (double)A, cy likewise
+ *     mu20 = (double)(A sxx - sx^2) / ((double)A (double)A)   the numerator an exact 128-bit integer, converted ONCE with round to
+ *                 nearest even; mu02 the same from syy and sy, mu11 the same from the signed A sxy - sx sy
+ *     mean[k] = (double)s1[k] / (double)A,  var[k] = (double)(A s2[k] - s1[k]^2) / ((double)A (double)A)    for k < channels, else 0
+ *     theta = 0.5 atan2(2 mu11, mu20 - mu02)
+ *     major, minor = 4 sqrt(l+), 4 sqrt(l-) with l+- = (mu20 + mu02) / 2 +- sqrt(((mu20 - mu02) / 2)^2 + mu11^2); minor is 0 where l-
+ *                 rounds below 0
+ * Everything up to and including var is IEEE arithmetic on exact integers (Python's float(int) arithmetic reproduces it bit for bit);
+ * theta, major and minor go through libm.  CVH_ERR_ARG: area == 0, a NULL pointer, channels not 1 or 3.
+ * cvh_measure: table (host, cap rows) may be NULL, count may be NULL.  *count is always the full K; table receives the first
+ * min(K, cap) rows.  cvh_measure_batch: tables may be NULL and so may any of its entries (no rows for that member; caps is read only
+ * for the members with a table); counts is an array of n or NULL.  A member with K = 0 is no error.  The batch form serves n contexts
+ * of one device, any mix of shapes and channel counts, with ONE set of launches on member 0's stream, joined with every member's
+ * stream before and after as cvh_components_batch; cvh_measure is the same kernels with n = 1.  `stream`: the call is ordered behind
+ * what it holds at the call.
+ * Host waits: ONE for the counts, and a SECOND where any rows are asked for (K decides where the rows live; they are computed behind
+ * the first wait).
+ * The calls only READ: iterations in flight are settled first and the FP64 mirror of a float state is refreshed, as the getters do;
+ * level set, run state, sums, options and planes are untouched, and a run continued after the call is bit-identical to one without.
+ * How (chan_vese_amd/csrc/measure_kernels.hip): the forest, flatten, count, scan and number launches of cvh_components (for a cleaned
+ * mask: the launches of cvh_get_mask_clean into the context's own mask buffer, labelled from its bytes); then a workgroup takes 8192
+ * pixels in raster order, forms the sums of every horizontal run inside a wave (a segmented reduction for perimeter, border, s1 and
+ * s2; closed forms of row, first column and length for the others), combines the runs of a label in a small label -> sums cache in LDS,
+ * and sends a cached row to the global row with 64-bit atomics only when another label takes its slot and once at the end: a plane
+ * that is one component costs one set of atomics per workgroup, not per run.
+ * Cost, one run of tools/measure_probe.py on an MI355X (host clock around a call with a full table and its two waits,
+ * 20 calls, measured once): 680 us at 4096^2 for a noisy disk after 50 iterations (350 components), 1130 us for the plane wholly inside
+ * (one component: 1.7 x, the contention is cut, not gone), beside 331 / 1140 ms for the same rows from cvh_get_mask, cvh_get_image and numpy.
+ * Memory: the components workspace (8 bytes per pixel), cvh_get_mask's byte per pixel where the mask is cleaned, and 128 bytes per row
+ * asked for; allocated on first use, kept until cvh_destroy.
+ * CVH_ERR_ARG: what cvh_get_mask_clean refuses for conn, min_area, fill_holes and keep_largest; a negative cap; ctxs NULL, n < 1, a
+ * NULL or duplicate member, members on different devices; h > 65535, w > 65535 or h w >= 2^31.  CVH_ERR_STATE: a member without an image
+ * or without a level set.  Checked for every member before anything is launched; the message names the member index and is
+ * cvh_last_error(NULL)'s and member 0's. */
+typedef struct cvh_region {            /* 128 bytes */
+  uint32_t first, area; int32_t x0, y0, x1, y1;   /* exactly cvh_component's fields */
+  uint32_t border, reserved;
+  uint64_t perimeter, sx, sy, sxx, syy, sxy;
+  uint64_t s1[3], s2[3];
+} cvh_region;
+typedef struct cvh_region_shape { double cx, cy, mu20, mu02, mu11, theta, major, minor, mean[3], var[3]; } cvh_region_shape;
+
+int cvh_measure(cvh_context *ctx, int conn, int invert, long min_area, long fill_holes, int keep_largest,
+                cvh_region *table, int cap, int *count, void *stream);
+int cvh_measure_batch(cvh_context *const *ctxs, int n, int conn, int invert, long min_area, long fill_holes, int keep_largest,
+                      cvh_region *const *tables, const int *caps, int *counts, void *stream);
+int cvh_region_shape_of(const cvh_region *r, int channels, cvh_region_shape *out);   /* host only */
+
 /* Library version string, e.g. "chanvese_hip 0.1 (gfx950)". */
 const char *cvh_version(void);
 
