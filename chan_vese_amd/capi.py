@@ -40,6 +40,7 @@ EXPORTS = [
     "cvh_energy", "cvh_energy_batch",
     "cvh_score_mask", "cvh_score_mask_device", "cvh_score_mask_device_batch",
     "cvh_measure", "cvh_measure_batch", "cvh_region_shape_of",
+    "cvh_contours", "cvh_contours_device", "cvh_contours_device_batch",
 ]
 # struct cvh_component: row k - 1 of a component table describes label k (first = smallest flat index; the box is inclusive)
 COMPONENT_DTYPE = np.dtype([("first", np.uint32), ("area", np.uint32), ("x0", np.int32), ("y0", np.int32), ("x1", np.int32), ("y1", np.int32)])
@@ -50,6 +51,9 @@ REGION_DTYPE = np.dtype([("first", np.uint32), ("area", np.uint32), ("x0", np.in
 # struct cvh_region_shape: what cvh_region_shape_of derives from a row
 REGION_SHAPE_DTYPE = np.dtype([(f, np.float64) for f in ("cx", "cy", "mu20", "mu02", "mu11", "theta", "major", "minor")] +
                               [("mean", np.float64, 3), ("var", np.float64, 3)])
+# struct cvh_contour_loop (32 bytes): one closed loop of the mask's boundary ("Contours" in include/chanvese_hip.h)
+CONTOUR_LOOP_DTYPE = np.dtype([("first", np.uint32), ("edges", np.uint32), ("points", np.uint32), ("pad", np.uint32), ("offset", np.uint64),
+                               ("area2", np.int64)])
 LAYOUT_PLANAR, LAYOUT_INTERLEAVED = 0, 1
 # "Colour spaces": which plane is which primary, and the spaces cvh_convert_colour knows
 ORDERS = {"bgr": 0, "rgb": 1}
@@ -170,7 +174,7 @@ def lib():
             "There is no CPU fallback.")
     L = C.CDLL(LIB_PATH)
     dp, u8p, ip = C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(C.c_int)
-    u8pp, vp = C.POINTER(u8p), C.c_void_p
+    u8pp, vp, lp = C.POINTER(u8p), C.c_void_p, C.POINTER(C.c_long)
     sig = {
         "cvh_default_params": (None, [C.POINTER(Params)]),
         "cvh_device_count": (C.c_int, [ip]),
@@ -250,6 +254,10 @@ def lib():
         "cvh_measure": (C.c_int, [vp, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, vp, C.c_int, ip, vp]),
         "cvh_measure_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, C.POINTER(vp), ip, ip, vp]),
         "cvh_region_shape_of": (C.c_int, [vp, C.c_int, vp]),
+        "cvh_contours": (C.c_int, [vp, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, C.c_int, vp, C.c_long, vp, C.c_long, lp, lp]),
+        "cvh_contours_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, C.c_int, vp, C.c_long, vp, C.c_long, lp, lp, vp]),
+        "cvh_contours_device_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, C.c_int, C.POINTER(vp), lp,
+                                                C.POINTER(vp), lp, lp, lp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -678,6 +686,37 @@ def measure_batch(contexts, conn=4, invert=False, min_area=0, fill_holes=0, keep
     return [(counts[i], tables[i][:min(counts[i], tables[i].size)].copy()) for i in range(n)]
 
 
+def contours_batch(contexts, d_points=None, point_caps=None, conn=8, invert=False, min_area=0, fill_holes=0, keep_largest=False, simplify=True,
+                   loop_caps=None, stream=0):
+    """cvh_contours_device_batch: Context.contours for n contexts (any mix of shapes and channel counts) with one set of launches.
+    d_points: None (no points), or per member the integer address of device memory for point_caps[i] points (two int32 each; 0: none
+    for that member).  loop_caps: None (every row, at the price of a first call for the counts) or one number per member.  Returns
+    [(nloops, npoints, loops)] per context, loops a structured array (CONTOUR_LOOP_DTYPE) of the first min(nloops, cap) rows; rows and
+    points are bit for bit the member's own Context.contours()."""
+    contexts = list(contexts)
+    n = len(contexts)
+    args = _clean_args(conn, invert, min_area, fill_holes, keep_largest) + (int(bool(simplify)),)
+    longs = C.c_long * max(n, 1)
+    nloops, npoints = longs(), longs()
+    if loop_caps is None:
+        _batch_chk(lib().cvh_contours_device_batch(_member_array(contexts), n, *args, None, None, None, None, nloops, npoints, int(stream) or None))
+        loop_caps = [nloops[i] for i in range(n)]
+    loop_caps = [int(c) for c in loop_caps]
+    if len(loop_caps) != n:
+        raise ValueError(f"loop_caps: {len(loop_caps)} values for {n} members")
+    tables = [np.zeros(max(c, 0), dtype=CONTOUR_LOOP_DTYPE) for c in loop_caps]
+    tptrs = (C.c_void_p * max(n, 1))(*[t.ctypes.data if t.size else None for t in tables])
+    pptrs, pcaps = None, None
+    if d_points is not None:
+        d_points, point_caps = [int(p) or None for p in d_points], [int(c) for c in point_caps]
+        if len(d_points) != n or len(point_caps) != n:
+            raise ValueError(f"{n} contexts but {len(d_points)} point arrays and {len(point_caps)} caps")
+        pptrs, pcaps = (C.c_void_p * max(n, 1))(*d_points), longs(*point_caps)
+    _batch_chk(lib().cvh_contours_device_batch(_member_array(contexts), n, *args, tptrs, longs(*loop_caps), pptrs, pcaps, nloops, npoints,
+                                               int(stream) or None))
+    return [(nloops[i], npoints[i], tables[i][:min(nloops[i], tables[i].size)].copy()) for i in range(n)]
+
+
 def region_shapes(table, channels):
     """cvh_region_shape_of for every row of a measure table (REGION_DTYPE): a structured array (REGION_SHAPE_DTYPE) of centroid, central
     moments, orientation, the axes of the ellipse with the same moments, and mean and variance per channel.  Host arithmetic, no device."""
@@ -992,6 +1031,27 @@ class Context:
         table = np.zeros(max(int(cap), 0), dtype=REGION_DTYPE)
         _batch_chk(self._L.cvh_measure(self._h, *args, table.ctypes.data if table.size else None, int(cap), C.byref(count), int(stream) or None))
         return count.value, table[:min(count.value, table.size)].copy()
+
+    def contour_counts(self, conn=8, invert=False, min_area=0, fill_holes=0, keep_largest=False, simplify=True):
+        """cvh_contours without outputs: (nloops, npoints) of the boundary of the mask."""
+        nloops, npoints = C.c_long(0), C.c_long(0)
+        args = _clean_args(conn, invert, min_area, fill_holes, keep_largest) + (int(bool(simplify)),)
+        _batch_chk(self._L.cvh_contours(self._h, *args, None, 0, None, 0, C.byref(nloops), C.byref(npoints)))
+        return nloops.value, npoints.value
+
+    def contours(self, conn=8, invert=False, min_area=0, fill_holes=0, keep_largest=False, simplify=True):
+        """cvh_contours: the boundary of the mask -- get_mask_clean's for the same five options, (0, 0, False) the raw one -- as ordered
+        closed loops of lattice points, traced on the device.  Returns (loops, points): loops a structured array (CONTOUR_LOOP_DTYPE:
+        first, edges, points, offset, area2 -- twice the enclosed area, negative for a hole), points an int32 array (P, 2) of x, y;
+        loop k's points are points[offset : offset + points] in cycle order, the foreground on their right.  simplify keeps the corners
+        only.  COSTS TWO TRACES (the counts size the arrays).  Only reads: a run continued after it is bit-identical to one without."""
+        nl, npts = self.contour_counts(conn, invert, min_area, fill_holes, keep_largest, simplify)
+        loops, points = np.zeros(nl, dtype=CONTOUR_LOOP_DTYPE), np.zeros((npts, 2), dtype=np.int32)
+        if nl:
+            nloops, npoints = C.c_long(0), C.c_long(0)
+            args = _clean_args(conn, invert, min_area, fill_holes, keep_largest) + (int(bool(simplify)),)
+            _batch_chk(self._L.cvh_contours(self._h, *args, loops.ctypes.data, nl, points.ctypes.data, npts, C.byref(nloops), C.byref(npoints)))
+        return loops, points
 
     def get_mask_clean(self, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False):
         """cvh_get_mask_clean: the mask without foreground components below min_area, with the holes of area <= fill_holes filled

@@ -144,6 +144,9 @@ extern "C" void cvh_destroy(cvh_context *c)
   if (c->d_cc) (void)hipFree(c->d_cc);
   if (c->d_cc_table) (void)hipFree(c->d_cc_table);
   if (c->d_regions) (void)hipFree(c->d_regions);
+  if (c->d_contour) (void)hipFree(c->d_contour);
+  if (c->d_contour_edges) (void)hipFree(c->d_contour_edges);
+  if (c->d_contour_points) (void)hipFree(c->d_contour_points);
   if (c->d_hist) (void)hipFree(c->d_hist);
   if (c->d_energy) (void)hipFree(c->d_energy);
   if (c->d_score) (void)hipFree(c->d_score);

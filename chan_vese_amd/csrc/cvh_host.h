@@ -3,7 +3,7 @@
 // context), csv_batch.hip (fused batch, and what every batch shares: the member and pair checks, the member predicates), pm_run.hip
 // (Perona-Malik), io_run.hip (device-memory I/O, reinitialisation, and the scaffolds of the member-table calls: MemberCall, write_planes,
 // the launch counters), init_run.hip (device-side initial level sets), components_run.hip (connected components), pyramid_run.hip
-// (coarse-to-fine), colour_run.hip (colour spaces), energy_run.hip (the functional's terms), score_run.hip (mask scores), measure_run.hip (component measures), debug_exports.hip (diagnostics).  Kernel sources do not include it.
+// (coarse-to-fine), colour_run.hip (colour spaces), energy_run.hip (the functional's terms), score_run.hip (mask scores), measure_run.hip (component measures), contour_run.hip (contours), debug_exports.hip (diagnostics).  Kernel sources do not include it.
 #pragma once
 #include <limits.h>
 #include <math.h>
@@ -146,6 +146,11 @@ struct cvh_context {   // opaque to callers; four groups
   size_t cc_table_rows = 0;
   void *d_regions = nullptr;     // the rows of this context's last cvh_measure* table (measure_run.hip): 128 bytes per row asked for, grown on demand, kept
   size_t region_rows = 0;
+  void *d_contour = nullptr;     // per-pixel workspace of cvh_contours* (contour_run.hip; 6 bytes per pixel): allocated by the first call, kept
+  void *d_contour_edges = nullptr;   // its per-edge workspace (45 bytes per edge of the largest call so far), grown on demand, kept
+  size_t contour_edge_cap = 0;
+  void *d_contour_points = nullptr;  // cvh_contours (host form): the points on their way down (8 bytes per point asked for), grown on demand, kept
+  size_t contour_point_cap = 0;
   unsigned *d_hist = nullptr;    // the 255 C + 1 counters of cvh_histogram* / cvh_otsu_threshold / cvh_init_otsu* (init_kernels.hip): allocated by
                                  // the first call, kept
   void *d_energy = nullptr;      // workspace of cvh_energy* (energy_run.hip): a CvhState for means taken beside the run's, then the item rows of

@@ -260,6 +260,21 @@ hipError_t cvh_launch_cc_number(const CvhIoMember *tab, int nmem, unsigned grid,
 #define CVH_MEASURE_TILE 8192
 unsigned cvh_measure_blocks(size_t n);
 hipError_t cvh_launch_measure(const CvhIoMember *tab, int nmem, unsigned grid, bool any_c1, bool any_c3, hipStream_t s);
+// contours (contour_kernels.hip, whose head comment describes a member's entry).  The pixel launches take sections of cvh_cc_blocks(n)
+// workgroups; behind the host's wait for E the edge launches take sections of cvh_contour_edge_blocks(E, n) workgroups (none for a member
+// without edges), a lane per edge -- or per pixel -- and trip.  The per-pixel workspace is [mask bytes][edge sets][prefix words][a count
+// per 256 pixels] at the offsets below; the per-edge workspace, sized for `cap` edges, holds the loops' rows at cvh_contour_rows_offset.
+unsigned cvh_contour_scan_trip();                    // counts the one-wave scan of a member takes per trip
+unsigned cvh_contour_edge_blocks(size_t edges, size_t n);
+size_t cvh_contour_bits_offset(size_t n);
+size_t cvh_contour_prefix_offset(size_t n);
+size_t cvh_contour_counts_offset(size_t n);
+size_t cvh_contour_pixel_bytes(size_t n);
+size_t cvh_contour_edge_bytes(size_t cap);
+size_t cvh_contour_rows_offset(size_t cap);
+hipError_t cvh_launch_contours_count(const CvhIoMember *tab, int nmem, unsigned grid, hipStream_t s);
+hipError_t cvh_launch_contours_trace(const CvhIoMember *tab, int nmem, unsigned grid, int conn, int simplify, int rounds, bool any_points,
+                                     hipStream_t s);
 // device-side initial level sets (init_kernels.hip).  Histogram: plane[] the member's planes, sums its 255 C + 1 32-bit counters (zeroed
 // by the host), sections of cvh_io_blocks(n) workgroups.  Start: dst the level set written, plane[] read by the threshold mode,
 // state_zero / chain_zero as the checkerboard's; member i's start is par[i], a table behind the member table:

@@ -66,6 +66,21 @@ extern "C" int cvh_debug_trip_counts(int op, int h, int w, unsigned long long *i
   return CVH_OK;
 }
 
+// Diagnostic (not part of include/chanvese_hip.h): the sections of a member of h x w pixels and `edges` boundary edges in the launches of
+// cvh_contours*, from the functions contour_run.hip sizes them with.  *pixel_blocks: workgroups of the pixel launches, one count each;
+// *scan_trip: counts the member's one-wave scan takes per trip; *edge_blocks: workgroups of the edge launches; *edge_lanes: edges (or
+// pixels) their lanes cover per trip.
+extern "C" int cvh_debug_contour_trips(int h, int w, unsigned long long edges, unsigned *pixel_blocks, unsigned *scan_trip, unsigned *edge_blocks,
+                                       unsigned long long *edge_lanes)
+{
+  if (h < 1 || w < 1 || !pixel_blocks || !scan_trip || !edge_blocks || !edge_lanes) return CVH_ERR_ARG;
+  *pixel_blocks = cvh_cc_blocks((size_t)h * (size_t)w);
+  *scan_trip = cvh_contour_scan_trip();
+  *edge_blocks = cvh_contour_edge_blocks((size_t)edges, (size_t)h * (size_t)w);
+  *edge_lanes = (unsigned long long)*edge_blocks * CVH_BLOCK;
+  return CVH_OK;
+}
+
 // Diagnostic (not part of include/chanvese_hip.h): the tile grid of the resident flow (csv_resident_kernel.hip) for a plane of `channels`
 // channels on `num_cus` CUs, one workgroup per CU, without a device -- the arithmetic resident_geometry() ends in.  Returns 1 and fills
 // tiles_x, tiles_y and the rows of the tallest tile, or 0: the plane does not qualify (odd width, < 16 rows or columns, more rows per tile

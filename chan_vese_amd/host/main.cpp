@@ -19,7 +19,9 @@
 // text of -O is not rendered (no font rasteriser here), --fps has nothing to act on.
 // Additions that do not collide with reference options: --dump-u, --dump-mask, --device, --math,
 // --state, --rect, --circ, --disk, --init, --threshold, --reinit, --connectivity, --min-area, --fill-holes, --largest, --roi, --verbose,
-// --levels, --energy, --energy-every, --truth, --score-tol, --measure.  --measure FILE writes one CSV line per component of the mask --dump-mask
+// --levels, --energy, --energy-every, --truth, --score-tol, --measure, --contours, --contours-all.  --contours FILE writes the boundary of
+// the mask --dump-mask uses (the cleaning options and -I apply) as ordered closed loops traced on the device (chanvese_hip.h, "Contours"),
+// one text line per loop: "first edges area2 :" and the x,y pairs of its corners, with --contours-all of every lattice vertex.  --measure FILE writes one CSV line per component of the mask --dump-mask
 // uses (the cleaning options and -I apply), measured on the device (chanvese_hip.h, "Component measures"): label, the integers of the row,
 // then centroid, central moments, orientation, axes, and mean and variance per channel (%.17g).  --truth FILE scores the final mask (inverted with -i) against a ground-truth PNG / PGM of
 // the input's size (non-zero = foreground) on the device (chanvese_hip.h, "Mask scores") and prints one line "score: iou=... dice=...
@@ -189,7 +191,7 @@ const Spec kSpecs[] = {
     {"dump-u", 0, 1}, {"dump-mask", 0, 1}, {"device", 0, 1}, {"math", 0, 1}, {"state", 0, 1}, {"rect", 0, 1}, {"circ", 0, 1}, {"reinit", 0, 1},
     {"disk", 0, 1}, {"init", 0, 1}, {"threshold", 0, 1}, {"levels", 0, 1}, {"colorspace", 0, 1},
     {"connectivity", 0, 1}, {"min-area", 0, 1}, {"fill-holes", 0, 1}, {"largest", 0, 0}, {"roi", 0, 0},
-    {"verbose", 0, 0}, {"energy", 0, 0}, {"energy-every", 0, 1}, {"truth", 0, 1}, {"score-tol", 0, 1}, {"measure", 0, 1}};
+    {"verbose", 0, 0}, {"energy", 0, 0}, {"energy-every", 0, 1}, {"truth", 0, 1}, {"score-tol", 0, 1}, {"measure", 0, 1}, {"contours", 0, 1}, {"contours-all", 0, 0}};
 
 struct Parsed {
   std::vector<std::pair<std::string, std::vector<std::string>>> opts;
@@ -352,6 +354,9 @@ void print_help()
       "  --score-tol arg (=2)               surface tolerance of --truth in pixels (surface_dice counts distances <= arg)\n"
       "  --measure arg                      write one CSV line per component of the mask --dump-mask uses (cleaning options, -I): label,\n"
       "                                     first,area,x0,y0,x1,y1,border,perimeter,cx,cy,mu20,mu02,mu11,theta,major,minor,mean..,var..\n"
+      "  --contours arg                     write the boundary of the mask --dump-mask uses (cleaning options, -I) as closed loops, one\n"
+      "                                     line per loop: 'first edges area2 :' and the x,y pairs of its corners in order\n"
+      "  --contours-all                     --contours keeps every lattice vertex, not the corners alone\n"
       "  --verbose                          print the iteration count and last norm to stderr\n"
       "\n";
 }
@@ -423,6 +428,9 @@ int main(int argc, char **argv)
   if (auto v = one("truth")) truth_filename = *v;
   std::string measure_filename;
   if (auto v = one("measure")) measure_filename = *v;
+  std::string contours_filename;
+  if (auto v = one("contours")) contours_filename = *v;
+  const bool contours_all = vm.count("contours-all") > 0;
   double score_tol = 2.0;
   if (auto v = one("score-tol")) score_tol = to_double("score-tol", *v);
   segment = vm.count("segment"); grayscale = vm.count("grayscale"); write_video = vm.count("video");
@@ -500,6 +508,8 @@ int main(int argc, char **argv)
   if (levels > 1 && reinit_every > 0) msg_exit("Reinitialisation (--reinit) cannot be combined with a coarse-to-fine run (--levels).");
   if (levels > 1 && !circ.empty()) msg_exit("A circular outline (--circ) cannot be combined with a coarse-to-fine run (--levels); use --disk.");
   if (energy_every < 0) msg_exit("Energy interval cannot be negative: " + std::to_string(energy_every) + ".");
+  if (!contours_filename.empty() && write_video) msg_exit("A contour file (--contours) cannot be combined with video output (-V).");
+  if (contours_all && contours_filename.empty()) msg_exit("Every lattice vertex (--contours-all) needs a contour file (--contours).");
   if (energy_every > 0 && write_video) msg_exit("An energy series (--energy-every) cannot be combined with video output (-V).");
   if (energy_every > 0 && reinit_every > 0) msg_exit("An energy series (--energy-every) cannot be combined with reinitialisation (--reinit).");
   if (energy_every > 0 && levels > 1) msg_exit("An energy series (--energy-every) cannot be combined with a coarse-to-fine run (--levels).");
@@ -822,6 +832,26 @@ int main(int argc, char **argv)
       std::fprintf(f, "\n");
     }
     if (std::fclose(f) != 0) msg_exit("Error: cannot write \"" + measure_filename + "\"");
+  }
+
+  if (!contours_filename.empty()) {   // the boundary of that mask as ordered closed loops, traced on the device: one text line each
+    const int simplify = contours_all ? 0 : 1;
+    long nloops = 0, npoints = 0;
+    cvh_check(ctx, cvh_contours(ctx, connectivity, invert ? 1 : 0, min_area, fill_holes, largest ? 1 : 0, simplify, nullptr, 0, nullptr, 0, &nloops, &npoints),
+              "cvh_contours");
+    std::vector<cvh_contour_loop> loops((size_t)nloops);
+    std::vector<int32_t> points(2 * (size_t)npoints);
+    if (nloops)
+      cvh_check(ctx, cvh_contours(ctx, connectivity, invert ? 1 : 0, min_area, fill_holes, largest ? 1 : 0, simplify, loops.data(), nloops, points.data(),
+                                  npoints, &nloops, &npoints), "cvh_contours");
+    FILE *f = std::fopen(contours_filename.c_str(), "w");
+    if (!f) msg_exit("Error: cannot write \"" + contours_filename + "\"");
+    for (const cvh_contour_loop &l : loops) {
+      std::fprintf(f, "%u %u %lld :", l.first, l.edges, (long long)l.area2);
+      for (uint64_t q = l.offset; q < l.offset + l.points; ++q) std::fprintf(f, " %d,%d", points[2 * q], points[2 * q + 1]);
+      std::fprintf(f, "\n");
+    }
+    if (std::fclose(f) != 0) msg_exit("Error: cannot write \"" + contours_filename + "\"");
   }
 
   // ---- selection: src/main.cpp:1004-1005

@@ -313,6 +313,18 @@ class Segmenter:
         centroid, moments, axes, mean and variance from it.  cap = None asks for every row at the price of a first call for the counts."""
         return capi.measure_batch(self.contexts, conn, invert, min_area, fill_holes, keep_largest, cap, self._stream())
 
+    def contours(self, conn=8, invert=False, min_area=0, fill_holes=0, keep_largest=False, simplify=True):
+        """The boundary of every member's mask -- clean_masks' for the same options -- as ordered closed loops, traced on the device
+        (cvh_contours_device_batch, ordered behind the current stream): one (loops, points) per member, loops a numpy structured array
+        (capi.CONTOUR_LOOP_DTYPE), points an int32 device tensor (P, 2) of x, y, valid for the next operation on the current stream;
+        bit for bit the member's own Context.contours().  Two sets of launches: the first for the counts that size the tensors."""
+        opts = dict(conn=conn, invert=invert, min_area=min_area, fill_holes=fill_holes, keep_largest=keep_largest, simplify=simplify)
+        counts = capi.contours_batch(self.contexts, loop_caps=[0] * self.n, stream=self._stream(), **opts)
+        points = [torch.empty((c[1], 2), dtype=torch.int32, device=torch.device("cuda", self.device)) for c in counts]
+        rows = capi.contours_batch(self.contexts, [p.data_ptr() if p.numel() else 0 for p in points], [c[1] for c in counts],
+                                   loop_caps=[c[0] for c in counts], stream=self._stream(), **opts)
+        return [(r[2], p) for r, p in zip(rows, points)]
+
     def levelsets(self, dtype=torch.float64):
         """The members' level sets as a device tensor (N, H, W), float64 or float32 (rounded to nearest even)."""
         if dtype not in (torch.float64, torch.float32):

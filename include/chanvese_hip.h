@@ -769,6 +769,74 @@ int cvh_measure_batch(cvh_context *const *ctxs, int n, int conn, int invert, lon
                       cvh_region *const *tables, const int *caps, int *counts, void *stream);
 int cvh_region_shape_of(const cvh_region *r, int channels, cvh_region_shape *out);   /* host only */
 
+/* ---- Contours -----------------------------------------------------------------------------------------------------------------
+ * The boundary of the mask as ORDERED CLOSED LOOPS of lattice points -- what cv::findContours gives, and what a caller otherwise takes
+ * with cvh_get_mask (a byte per pixel across PCIe) and a tracer on a CPU.  (cvh_get_contour is something else: a byte map of painted
+ * pixels.)  Everything is defined in integers: a member alone or inside any batch, and two calls in a row, give the same bits, and every
+ * field can be compared with ==.
+ * Mask.  f(p) is the foreground of cvh_get_mask_clean for the call's (conn, invert, min_area, fill_holes, keep_largest); with
+ * (., ., 0, 0, 0) it is cvh_get_mask's rule and the labelling launches do not run.  With "state" = 32 the class comes from the float
+ * state, as everywhere else.
+ * Lattice.  Vertices are (x, y) with 0 <= x <= w and 0 <= y <= h; pixel (row r, column c) is the square [c, c+1] x [r, r+1].
+ * Edges.  A boundary edge is a side of a foreground pixel whose neighbour across it is not foreground or lies outside the plane.  Its
+ * id is 4 (r w + c) + k.  Edges are directed so that the foreground is on the right (y grows downwards):
+ *     k = 0 top     (c, r)     -> (c+1, r)          k = 1 right   (c+1, r)   -> (c+1, r+1)
+ *     k = 2 bottom  (c+1, r+1) -> (c, r+1)          k = 3 left    (c, r+1)   -> (c, r)
+ * Successor.  The successor of an edge is the boundary edge that leaves its head vertex; where two leave (two foreground pixels meet
+ * diagonally) it is the left turn for conn = 8 and the right turn for conn = 4.  Every edge then has exactly one successor and one
+ * predecessor: the edges fall into disjoint cycles.
+ * Loop.  A loop is one cycle.  first is its smallest edge id, edges its length, area2 = sum (x_tail y_head - x_head y_tail) over its
+ * edges -- twice the enclosed area, positive for an outer boundary, negative for a hole.  Loops are numbered in increasing order of
+ * first.  The pixel first >> 2 is a foreground pixel on the loop: its label in cvh_components' label plane names the component.
+ * Points.  With simplify = 0 a loop's points are the tail vertices of its edges in cycle order, starting at edge first.  With
+ * simplify = 1 only corners stay -- a corner is the tail of an edge whose predecessor has another direction --, in the same order,
+ * starting at the first corner met from edge first, that edge included.  points is their number, offset the loop's first index in the
+ * point array: loop k's points follow loop k-1's.  A point is two int32, x then y.
+ * Caps.  *nloops and *npoints are always the full counts; the loop table receives the first min(nloops, loop_cap) rows, the point
+ * array the points with index < point_cap; nothing behind is written.  Either output may be NULL (counts only; no member with a point
+ * array: the scatter launch is skipped), and so may nloops and npoints.  An empty mask gives 0 loops: no error.
+ * cvh_contours writes the points to host memory, cvh_contours_device to device memory the caller owns (the rules of "Device-memory input
+ * and output"; 4-byte aligned), ordered against `stream` by events: behind what it holds at the call, and it waits for the points.
+ * The loop table is host memory in every form.  cvh_contours_device_batch serves n contexts of one device, any mix of shapes and
+ * channel counts: loops, d_points and their entries may be NULL, the caps are read for the members with an output, nloops and npoints
+ * are arrays of n or NULL; ONE set of launches on member 0's stream, joined with every member's stream before and after as
+ * cvh_reinit_batch.  The single forms are the same kernels with n = 1.
+ * The calls only READ: iterations in flight are settled first and the FP64 mirror of a float state is refreshed, as the getters do;
+ * level set, run state, sums, options and planes are untouched, and a run continued after the call is bit-identical to one without.
+ * How (chan_vese_amd/csrc/contour_kernels.hip): the mask bytes (the mask kernel, or the launches of cvh_get_mask_clean); per pixel the
+ * 4-bit set of its boundary edges, counted per workgroup and scanned -- E, the number of edges; then, over the E edges in the order of
+ * their ids: successor links, ceil(log2 E) rounds of pointer doubling (one launch each, double-buffered, ordered by kernel boundaries)
+ * that give every edge its loop's smallest edge and the points between itself and it; the heads counted and scanned (the loop index);
+ * edges, points and area2 per loop by integer atomics behind a reduction inside the wave; a scan of the points (offset); the scatter.
+ * No kernel waits for another workgroup.
+ * Host waits: TWO -- for the edge counts (they size the per-edge workspace, the grids and the rounds), then for the loop and point
+ * counts and the rows.  A call whose masks are all empty ends at the first.
+ * Memory: 6 bytes per pixel (mask, edge sets, prefix words), allocated by a context's first call; 45 bytes per edge, grown to the
+ * largest E the context has met (plus a quarter); the host form also 8 bytes per point asked for; with cleaning, the components
+ * workspace (8 bytes per pixel).  All kept until cvh_destroy; cvh_create allocates none of it.
+ * Cost, one run of tools/contour_probe.py on an MI355X (host clock around a call with full outputs and its two waits, 20
+ * calls, measured once): 1023 / 904 / 1223 us at 1024^2 / 2048^2 / 4096^2 for a noisy disk after 50 iterations, 593 / 741 / 1266 us for
+ * the plane wholly inside (one loop) -- about twenty CSV iterations at 4096^2, nearly all of it launches, waits and scans that a call
+ * without outputs pays too; cvh_get_mask alone takes 0.2 to 2 ms.
+ * CVH_ERR_ARG: what cvh_get_mask_clean refuses for conn, min_area, fill_holes and keep_largest; simplify not 0 or 1; a negative cap;
+ * h w >= 2^30 (an edge id is 32 bits); a point pointer that is not device-accessible memory of the context's device or not 4-byte
+ * aligned; ctxs NULL, n < 1, a NULL or duplicate member, members on different devices; tables without caps.  CVH_ERR_STATE: a member
+ * without a level set.  Checked for every member before anything is launched; the message names the member index and is
+ * cvh_last_error(NULL)'s and member 0's. */
+typedef struct cvh_contour_loop {      /* 32 bytes */
+  uint32_t first, edges, points, pad;
+  uint64_t offset;
+  int64_t  area2;
+} cvh_contour_loop;
+int cvh_contours(cvh_context *ctx, int conn, int invert, long min_area, long fill_holes, int keep_largest, int simplify,
+                 cvh_contour_loop *loops, long loop_cap, int32_t *points, long point_cap, long *nloops, long *npoints);   /* host points */
+int cvh_contours_device(cvh_context *ctx, int conn, int invert, long min_area, long fill_holes, int keep_largest, int simplify,
+                        cvh_contour_loop *loops, long loop_cap, int32_t *d_points, long point_cap, long *nloops, long *npoints,
+                        void *stream);
+int cvh_contours_device_batch(cvh_context *const *ctxs, int n, int conn, int invert, long min_area, long fill_holes, int keep_largest,
+                              int simplify, cvh_contour_loop *const *loops, const long *loop_caps, int32_t *const *d_points,
+                              const long *point_caps, long *nloops, long *npoints, void *stream);
+
 /* Library version string, e.g. "chanvese_hip 0.1 (gfx950)". */
 const char *cvh_version(void);
 
