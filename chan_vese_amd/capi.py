@@ -41,7 +41,12 @@ EXPORTS = [
     "cvh_score_mask", "cvh_score_mask_device", "cvh_score_mask_device_batch",
     "cvh_measure", "cvh_measure_batch", "cvh_region_shape_of",
     "cvh_contours", "cvh_contours_device", "cvh_contours_device_batch",
+    "cvh_get_mask_morph", "cvh_get_mask_morph_device", "cvh_get_mask_morph_device_batch", "cvh_morph_levelset", "cvh_morph_levelset_batch",
+    "cvh_init_mask", "cvh_init_mask_device", "cvh_init_mask_device_batch",
 ]
+# "Mask morphology": the operations of cvh_get_mask_morph* / cvh_morph_levelset*, by code and by name
+MORPH_NONE, MORPH_DILATE, MORPH_ERODE, MORPH_OPEN, MORPH_CLOSE = 0, 1, 2, 3, 4
+MORPH_OPS = {"none": MORPH_NONE, "dilate": MORPH_DILATE, "erode": MORPH_ERODE, "open": MORPH_OPEN, "close": MORPH_CLOSE}
 # struct cvh_component: row k - 1 of a component table describes label k (first = smallest flat index; the box is inclusive)
 COMPONENT_DTYPE = np.dtype([("first", np.uint32), ("area", np.uint32), ("x0", np.int32), ("y0", np.int32), ("x1", np.int32), ("y1", np.int32)])
 # struct cvh_region (128 bytes): row k - 1 of a measure table describes label k ("Component measures" in include/chanvese_hip.h)
@@ -154,6 +159,36 @@ def score_tol2(tol):
     return min(int(math.floor(tol * tol)), 0xFFFFFFFF)
 
 
+def r2_of(radius):
+    """The squared radius the morphology calls take: floor(radius^2) for a finite radius >= 0, capped at 2^32 - 1."""
+    if isinstance(radius, bool) or not isinstance(radius, (int, float)) or not math.isfinite(radius) or radius < 0:
+        raise ValueError(f"radius must be a finite number >= 0, got {radius!r}")
+    return min(int(math.floor(radius * radius)), 0xFFFFFFFF)
+
+
+def morph_code(op):
+    """CVH_MORPH_*: from its code or from "none" / "dilate" / "erode" / "open" / "close" (None is "none")"""
+    if op is None:
+        return MORPH_NONE
+    if isinstance(op, str):
+        if op.lower() not in MORPH_OPS:
+            raise ValueError(f"morph must be one of {sorted(MORPH_OPS)}, got {op!r}")
+        return MORPH_OPS[op.lower()]
+    return int(op)
+
+
+def _morph_r2(r2, radius):
+    """the one squared radius of a call: r2 (an integer 0 .. 2^32 - 1) or radius (r2_of), not both; neither is 0"""
+    if r2 is not None and radius is not None:
+        raise ValueError("give r2 or radius, not both")
+    if radius is not None:
+        return r2_of(radius)
+    r2 = 0 if r2 is None else int(r2)
+    if not 0 <= r2 <= 0xFFFFFFFF:
+        raise ValueError(f"r2 must be in 0 .. 2^32 - 1, got {r2}")
+    return r2
+
+
 class CvhError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"chanvese_hip error {code}: {msg}")
@@ -258,6 +293,16 @@ def lib():
         "cvh_contours_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, C.c_int, vp, C.c_long, vp, C.c_long, lp, lp, vp]),
         "cvh_contours_device_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, C.c_int, C.POINTER(vp), lp,
                                                 C.POINTER(vp), lp, lp, lp, vp]),
+        "cvh_get_mask_morph": (C.c_int, [vp, u8p, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, C.c_int, C.c_uint32]),
+        "cvh_get_mask_morph_device": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, C.c_int, C.c_uint32, vp]),
+        "cvh_get_mask_morph_device_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.POINTER(vp), C.c_int, C.c_int, C.c_long, C.c_long, C.c_int,
+                                                      C.c_int, C.POINTER(C.c_uint32), vp]),
+        "cvh_morph_levelset": (C.c_int, [vp, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, C.c_int, C.c_uint32, C.c_double, C.c_double]),
+        "cvh_morph_levelset_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, C.c_int,
+                                               C.POINTER(C.c_uint32), C.c_double, C.c_double]),
+        "cvh_init_mask": (C.c_int, [vp, u8p, C.c_double, C.c_double]),
+        "cvh_init_mask_device": (C.c_int, [vp, vp, C.c_double, C.c_double, vp]),
+        "cvh_init_mask_device_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.POINTER(vp), C.c_double, C.c_double, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -664,6 +709,47 @@ def _clean_args(conn, invert, min_area, fill_holes, keep_largest):
     return int(conn), int(bool(invert)), int(min_area), int(fill_holes), int(keep_largest)
 
 
+def _r2_array(r2, radius, n):
+    """one squared radius per member: r2 / radius are one number for all members or one per member"""
+    def per_member(v):
+        vals = list(v) if np.ndim(v) else [v] * n
+        if len(vals) != n:
+            raise ValueError(f"{len(vals)} radii for {n} members")
+        return vals
+    if r2 is not None and radius is not None:
+        raise ValueError("give r2 or radius, not both")
+    vals = [_morph_r2(None, float(v)) for v in per_member(radius)] if radius is not None else [_morph_r2(v, None) for v in per_member(0 if r2 is None else r2)]
+    return (C.c_uint32 * max(n, 1))(*vals)
+
+
+def mask_morph_batch(contexts, ptrs, op, r2=None, radius=None, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False, stream=0):
+    """cvh_get_mask_morph_device_batch: Context.mask_morph for n contexts (any mix of shapes and channel counts) into device memory (ptrs:
+    one integer address of h * w bytes per context), one set of launches for all; r2 / radius are one number or one per member, op is
+    shared.  Work enqueued on `stream` afterwards sees the masks.  Does not block the host."""
+    contexts = list(contexts)
+    n = len(contexts)
+    args = _clean_args(conn, invert, min_area, fill_holes, keep_largest) + (morph_code(op), _r2_array(r2, radius, n))
+    _batch_chk(lib().cvh_get_mask_morph_device_batch(_member_array(contexts), n, _address_array(list(ptrs), n), *args, int(stream) or None))
+
+
+def morph_levelset_batch(contexts, op, r2=None, radius=None, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False, inside=1.0,
+                         outside=-1.0):
+    """cvh_morph_levelset_batch: Context.morph_levelset for n contexts with one set of launches; r2 / radius as in mask_morph_batch."""
+    contexts = list(contexts)
+    n = len(contexts)
+    args = _clean_args(conn, invert, min_area, fill_holes, keep_largest) + (morph_code(op), _r2_array(r2, radius, n))
+    _batch_chk(lib().cvh_morph_levelset_batch(_member_array(contexts), n, *args, float(inside), float(outside)))
+
+
+def init_mask_batch(contexts, ptrs, inside=1.0, outside=-1.0, stream=0):
+    """cvh_init_mask_device_batch: Context.init_mask for n contexts from byte masks in device memory (ptrs: one integer address of h * w
+    bytes per context, read behind what `stream` holds), one launch for all."""
+    contexts = list(contexts)
+    n = len(contexts)
+    _batch_chk(lib().cvh_init_mask_device_batch(_member_array(contexts), n, _address_array(list(ptrs), n), float(inside), float(outside),
+                                                int(stream) or None))
+
+
 def measure_batch(contexts, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False, cap=None, stream=0):
     """cvh_measure_batch: Context.measure for n contexts (any mix of shapes and channel counts) with one set of launches.  cap: None
     (all rows, at the price of a first call for the counts), one number for every member or one per member.  Returns [(K, table)] per
@@ -1063,6 +1149,39 @@ class Context:
     def get_mask_clean_device(self, ptr, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False, stream=0):
         self._chk(self._L.cvh_get_mask_clean_device(self._h, int(ptr) or None, int(conn), int(bool(invert)), int(min_area), int(fill_holes),
                                                     int(keep_largest), int(stream) or None))
+
+    def mask_morph(self, op, r2=None, radius=None, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False, out=None, stream=0):
+        """cvh_get_mask_morph / cvh_get_mask_morph_device: the cleaned mask (get_mask_clean's arguments) dilated, eroded, opened or closed
+        by the disk dx^2 + dy^2 <= r2 (or radius: r2 = floor(radius^2)) on the device; op is a MORPH_* code or its name.  out is None (a
+        new (h, w) uint8 array is returned), a contiguous uint8 array of (h, w) to fill, or the integer address of h * w bytes in device
+        memory, written behind what `stream` holds.  Only reads: a run continued after it is bit-identical to one without."""
+        args = _clean_args(conn, invert, min_area, fill_holes, keep_largest) + (morph_code(op), _morph_r2(r2, radius))
+        if out is None or isinstance(out, np.ndarray):
+            m = np.empty((self.h, self.w), dtype=np.uint8) if out is None else out
+            assert m.dtype == np.uint8 and m.shape == (self.h, self.w) and m.flags["C_CONTIGUOUS"]
+            _batch_chk(self._L.cvh_get_mask_morph(self._h, _u8p(m), *args))
+            return m
+        _batch_chk(self._L.cvh_get_mask_morph_device(self._h, int(out) or None, *args, int(stream) or None))
+        return out
+
+    def morph_levelset(self, op, r2=None, radius=None, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False, inside=1.0,
+                       outside=-1.0):
+        """cvh_morph_levelset: mask_morph in place -- the level set becomes `inside` where that mask is 1 and `outside` elsewhere, and a
+        new run begins as after set_levelset; the mask never leaves the device.  With MORPH_NONE the cleaned mask is baked in."""
+        args = _clean_args(conn, invert, min_area, fill_holes, keep_largest) + (morph_code(op), _morph_r2(r2, radius))
+        _batch_chk(self._L.cvh_morph_levelset(self._h, *args, float(inside), float(outside)))
+
+    def init_mask(self, mask, inside=1.0, outside=-1.0, stream=0):
+        """cvh_init_mask / cvh_init_mask_device: u = inside where the mask's byte is nonzero, outside elsewhere, written on the device (one
+        byte per pixel crosses, not eight); the context is left as set_levelset of those doubles leaves it.  mask is a numpy array of
+        (h, w), bool or uint8, or the integer address of h * w bytes in device memory, read behind what `stream` holds.  Needs neither
+        an image nor a level set."""
+        if isinstance(mask, np.ndarray):
+            m = np.ascontiguousarray(mask.view(np.uint8) if mask.dtype == np.bool_ else mask, dtype=np.uint8)
+            assert m.shape == (self.h, self.w)
+            _batch_chk(self._L.cvh_init_mask(self._h, _u8p(m), float(inside), float(outside)))
+        else:
+            _batch_chk(self._L.cvh_init_mask_device(self._h, int(mask) or None, float(inside), float(outside), int(stream) or None))
 
     def get_contour(self):
         m = np.empty((self.h, self.w), dtype=np.uint8)

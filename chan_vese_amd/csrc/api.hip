@@ -150,6 +150,7 @@ extern "C" void cvh_destroy(cvh_context *c)
   if (c->d_hist) (void)hipFree(c->d_hist);
   if (c->d_energy) (void)hipFree(c->d_energy);
   if (c->d_score) (void)hipFree(c->d_score);
+  if (c->d_morph) (void)hipFree(c->d_morph);
   if (c->ev_io_in) (void)hipEventDestroy(c->ev_io_in);
   if (c->ev_io_out) (void)hipEventDestroy(c->ev_io_out);
   if (c->h_resident) (void)hipHostFree(c->h_resident);

@@ -3,7 +3,7 @@
 // context), csv_batch.hip (fused batch, and what every batch shares: the member and pair checks, the member predicates), pm_run.hip
 // (Perona-Malik), io_run.hip (device-memory I/O, reinitialisation, and the scaffolds of the member-table calls: MemberCall, write_planes,
 // the launch counters), init_run.hip (device-side initial level sets), components_run.hip (connected components), pyramid_run.hip
-// (coarse-to-fine), colour_run.hip (colour spaces), energy_run.hip (the functional's terms), score_run.hip (mask scores), measure_run.hip (component measures), contour_run.hip (contours), debug_exports.hip (diagnostics).  Kernel sources do not include it.
+// (coarse-to-fine), colour_run.hip (colour spaces), energy_run.hip (the functional's terms), score_run.hip (mask scores), morph_run.hip (mask morphology, mask starts), measure_run.hip (component measures), contour_run.hip (contours), debug_exports.hip (diagnostics).  Kernel sources do not include it.
 #pragma once
 #include <limits.h>
 #include <math.h>
@@ -157,6 +157,8 @@ struct cvh_context {   // opaque to callers; four groups
                                  // energy_kernels.hip: allocated by the first call, kept -- not part of live_footprint either
   void *d_score = nullptr;       // workspace of cvh_score_mask* (score_run.hip): class and surface words, the distance fields and the truth plane the
                                  // host form stages (5.5 bytes per pixel): allocated by the first call, kept -- not part of live_footprint either
+  void *d_morph = nullptr;       // workspace of cvh_get_mask_morph* / cvh_morph_levelset* / cvh_init_mask (morph_run.hip): two planes of band words, the
+                                 // 16-bit distance field and a byte plane (3.25 bytes per pixel): allocated by the first call, kept -- not part of live_footprint either
   int coop_launch = -1;          // does the device launch cooperatively (-1: not asked yet; launches_cooperatively)
   int resident_cap = -1;         // workgroups of csv_resident_kernel the device holds at once (-1: not asked yet, 0: unavailable)
   int pm_resident_cap = -1;      // workgroups of pm_resident_kernel the device holds at once (-1: not asked yet)
@@ -254,8 +256,9 @@ void free_table(DeviceTable *t);
 
 // io_run.hip: launches so far in this process (debug_exports.hip): the launch sets (three kernels for all members) of cvh_reinit*, the
 // launches of cvh_restrict_image* / cvh_prolong_levelset*, those of cvh_convert_colour* / cvh_luma_image*, and the launch sets (term pass and
-// reduce pass for all members) of cvh_energy*, and the launch sets (four kernels for all members) of cvh_score_mask*
-enum LaunchCounter { kReinitLaunchSets, kPyramidLaunches, kColourLaunches, kEnergyLaunchSets, kScoreLaunchSets, kLaunchCounters };
+// reduce pass for all members) of cvh_energy*, the launch sets (four kernels for all members) of cvh_score_mask*, and the launch sets (every
+// kernel of the call, for all members) of cvh_get_mask_morph* / cvh_morph_levelset* / cvh_init_mask*
+enum LaunchCounter { kReinitLaunchSets, kPyramidLaunches, kColourLaunches, kEnergyLaunchSets, kScoreLaunchSets, kMorphLaunchSets, kLaunchCounters };
 extern std::atomic<unsigned long> g_launches[kLaunchCounters];
 
 // io_run.hip: what every call on device memory or on a member table shares (the comments are at the definitions)

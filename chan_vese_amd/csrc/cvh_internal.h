@@ -335,6 +335,26 @@ inline size_t cvh_score_workspace_bytes(int h, int w) { return cvh_score_truth_o
 // cvh_reinit_row_blocks workgroups per member), max_w the widest member (sizes the LDS window of launch 4)
 hipError_t cvh_launch_score(const CvhIoMember *cols, unsigned col_grid, const CvhIoMember *rows, unsigned row_grid, int nmem, int max_w,
                             int invert, unsigned tol2, hipStream_t s);
+// mask morphology and mask starts (morph_kernels.hip).  Three tables of the same members.  The mask launches' (cvh_launch_io_mask /
+// cvh_launch_cc_clean, only where the call cleans): dst the member's byte plane.  The column table (cvh_reinit_column_blocks workgroups per
+// member): src the level set, src2 the byte plane of the cleaned mask, plane[0] / plane[1] the two planes of band words the passes ping-pong
+// between (cvh_score_words_bytes each), plane[2] the vertical distance field (one 16-bit word per pixel, 0xffff = none within reach).  The
+// emit table (cvh_io_blocks workgroups per member, 16 pixels per lane and trip): plane[0] the band words of the result, or src bytes at any
+// alignment (nonzero = set: a mask start); dst bytes at any alignment, or the level set with state_zero / chain_zero as the checkerboard's.
+// par[i] is member i's: the squared radius, its integer root, and the two doubles of a level-set write.
+struct CvhMorphPar { double inside, outside; unsigned r2, root, pad[2]; };
+// bytes of a member's workspace: [two planes of band words][distance field][byte plane: the cleaned mask, or the bytes a host form stages]
+inline size_t cvh_morph_dist_offset(int h, int w) { return 2 * cvh_score_words_bytes(h, w); }
+inline size_t cvh_morph_bytes_offset(int h, int w) { return cvh_morph_dist_offset(h, w) + (((size_t)h * (size_t)w * sizeof(unsigned short) + 255) & ~(size_t)255); }
+inline size_t cvh_morph_workspace_bytes(int h, int w) { return cvh_morph_bytes_offset(h, w) + (size_t)h * (size_t)w; }
+// the band words of the start set into plane[0]: from the level set (cvh_get_mask's rule, invert applied) or from the byte plane
+hipError_t cvh_launch_morph_bits(const CvhIoMember *cols, int nmem, unsigned col_grid, bool from_levelset, int invert, hipStream_t s);
+// pass k = 0 .. npass-1 reads plane[k & 1] and writes plane[(k + 1) & 1]: a dilation by D(r2), of the complement within the plane where
+// complement[k] (an erosion).  Two launches per pass, ordered by kernel boundaries
+hipError_t cvh_launch_morph_passes(const CvhIoMember *cols, const CvhMorphPar *par, int nmem, unsigned col_grid, int npass, const bool *complement,
+                                   hipStream_t s);
+hipError_t cvh_launch_morph_emit(const CvhIoMember *tab, const CvhMorphPar *par, int nmem, unsigned grid, bool from_bytes, bool to_levelset,
+                                 hipStream_t s);
 // rows-per-tile options of the step kernel
 void cvh_step_grid(int h, int w, int tile_rows, int *tiles_x, int *tiles_y);
 int cvh_step_max_blocks(int h, int w);

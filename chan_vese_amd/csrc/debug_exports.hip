@@ -45,12 +45,16 @@ enum {
   TRIPS_ENERGY_REDUCE,   // item rows over the lanes of the member's one workgroup
   TRIPS_ROWS,            // reinit and score, row launch: rows over workgroups
   TRIPS_COLUMNS,         // reinit and score, column launches: band x 256-column slots, a workgroup each
-  TRIPS_NOPS
+  TRIPS_NOPS,            // = 8: the end of the ORIGINAL, contiguous codes -- no longer the number of operations
+  // Codes added later start at 16 and 8 .. 15 stay refused for good (tests/test_trip_counts.py pins the first code behind the original
+  // eight as refused): the enum has a permanent gap, the valid codes are 0 .. TRIPS_NOPS - 1 and TRIPS_MORPH_EMIT .. TRIPS_END - 1
+  TRIPS_MORPH_EMIT = 16, // morphology and mask starts, emit launch: 16-pixel pieces over lanes (the n % 16 last pixels go apart)
+  TRIPS_END
 };
 
 extern "C" int cvh_debug_trip_counts(int op, int h, int w, unsigned long long *items, unsigned *nblk, unsigned *takers)
 {
-  if (op < 0 || op >= TRIPS_NOPS || h < 1 || w < 1 || !items || !nblk || !takers) return CVH_ERR_ARG;
+  if (op < 0 || (op >= TRIPS_NOPS && op < TRIPS_MORPH_EMIT) || op >= TRIPS_END || h < 1 || w < 1 || !items || !nblk || !takers) return CVH_ERR_ARG;
   const size_t n = (size_t)h * (size_t)w;
   const unsigned bands = ((unsigned)h + CVH_REINIT_BAND - 1) / CVH_REINIT_BAND, chunks = ((unsigned)w + CVH_BLOCK - 1) / CVH_BLOCK;
   switch (op) {
@@ -62,6 +66,7 @@ extern "C" int cvh_debug_trip_counts(int op, int h, int w, unsigned long long *i
     case TRIPS_ENERGY_REDUCE: *items = cvh_energy_items(h, w); *nblk = 1; *takers = CVH_BLOCK; break;
     case TRIPS_ROWS: *items = (unsigned long long)h; *nblk = cvh_reinit_row_blocks(h); *takers = 1; break;
     case TRIPS_COLUMNS: *items = (unsigned long long)bands * chunks; *nblk = cvh_reinit_column_blocks(h, w); *takers = 1; break;
+    case TRIPS_MORPH_EMIT: *items = n / 16; *nblk = cvh_io_blocks(n); *takers = CVH_BLOCK; break;
   }
   return CVH_OK;
 }
@@ -149,6 +154,10 @@ extern "C" unsigned long cvh_debug_energy_launch_sets(void) { return g_launches[
 // Diagnostic (not part of include/chanvese_hip.h): launch sets of cvh_score_mask* so far in this process -- one set is the four launches of
 // score_kernels.hip over all members of the call (tests/test_gpu_score.py: a batch of n is one set)
 extern "C" unsigned long cvh_debug_score_launch_sets(void) { return g_launches[kScoreLaunchSets].load(); }
+// Diagnostic (not part of include/chanvese_hip.h): launch sets of cvh_get_mask_morph* / cvh_morph_levelset* / cvh_init_mask* so far in this
+// process -- one set is every launch of morph_kernels.hip (and of the cleaning) over all members of the call (tests/test_gpu_morph.py: a
+// batch of n is one set)
+extern "C" unsigned long cvh_debug_morph_launch_sets(void) { return g_launches[kMorphLaunchSets].load(); }
 
 // Diagnostic (not part of include/chanvese_hip.h): device time (HIP events on the leader's stream: table copy, the three launches, flag
 // copy) of the last cvh_reinit / cvh_reinit_batch this context led (tools/reinit_probe.py).

@@ -17,9 +17,11 @@
 // <stem>_frames/frame_NNNNNN<ext> holding the same frames (the input with the contour drawn in
 // --line-color, one frame for t = 0 and one after every iteration, :926-931,:997); the overlay
 // text of -O is not rendered (no font rasteriser here), --fps has nothing to act on.
+// --morph dilate|erode|open|close with --morph-radius R applies that operation by a disk to the cleaned mask on the device (chanvese_hip.h,
+// "Mask morphology") for --dump-mask, --roi, --measure, --contours and _selection; --init-mask FILE starts from a binary PGM.
 // Additions that do not collide with reference options: --dump-u, --dump-mask, --device, --math,
 // --state, --rect, --circ, --disk, --init, --threshold, --reinit, --connectivity, --min-area, --fill-holes, --largest, --roi, --verbose,
-// --levels, --energy, --energy-every, --truth, --score-tol, --measure, --contours, --contours-all.  --contours FILE writes the boundary of
+// --levels, --energy, --energy-every, --truth, --score-tol, --measure, --contours, --contours-all, --morph, --morph-radius, --init-mask.  --contours FILE writes the boundary of
 // the mask --dump-mask uses (the cleaning options and -I apply) as ordered closed loops traced on the device (chanvese_hip.h, "Contours"),
 // one text line per loop: "first edges area2 :" and the x,y pairs of its corners, with --contours-all of every lattice vertex.  --measure FILE writes one CSV line per component of the mask --dump-mask
 // uses (the cleaning options and -I apply), measured on the device (chanvese_hip.h, "Component measures"): label, the integers of the row,
@@ -191,7 +193,8 @@ const Spec kSpecs[] = {
     {"dump-u", 0, 1}, {"dump-mask", 0, 1}, {"device", 0, 1}, {"math", 0, 1}, {"state", 0, 1}, {"rect", 0, 1}, {"circ", 0, 1}, {"reinit", 0, 1},
     {"disk", 0, 1}, {"init", 0, 1}, {"threshold", 0, 1}, {"levels", 0, 1}, {"colorspace", 0, 1},
     {"connectivity", 0, 1}, {"min-area", 0, 1}, {"fill-holes", 0, 1}, {"largest", 0, 0}, {"roi", 0, 0},
-    {"verbose", 0, 0}, {"energy", 0, 0}, {"energy-every", 0, 1}, {"truth", 0, 1}, {"score-tol", 0, 1}, {"measure", 0, 1}, {"contours", 0, 1}, {"contours-all", 0, 0}};
+    {"verbose", 0, 0}, {"energy", 0, 0}, {"energy-every", 0, 1}, {"truth", 0, 1}, {"score-tol", 0, 1}, {"measure", 0, 1}, {"contours", 0, 1}, {"contours-all", 0, 0},
+    {"morph", 0, 1}, {"morph-radius", 0, 1}, {"init-mask", 0, 1}};
 
 struct Parsed {
   std::vector<std::pair<std::string, std::vector<std::string>>> opts;
@@ -357,6 +360,11 @@ void print_help()
       "  --contours arg                     write the boundary of the mask --dump-mask uses (cleaning options, -I) as closed loops, one\n"
       "                                     line per loop: 'first edges area2 :' and the x,y pairs of its corners in order\n"
       "  --contours-all                     --contours keeps every lattice vertex, not the corners alone\n"
+      "  --morph arg                        dilate | erode | open | close: that operation by a disk of --morph-radius pixels, on the device,\n"
+      "                                     behind the cleaning options: --dump-mask, --roi, --measure, --contours and _selection use its result\n"
+      "  --morph-radius arg (=1)            radius R of that disk in pixels: the offsets with dx^2 + dy^2 <= floor(R^2) (1: the 4-neighbour cross)\n"
+      "  --init-mask arg                    binary PGM of the input's size as the initial contour (+1 where it is non-zero, -1 elsewhere),\n"
+      "                                     written on the device at a byte per pixel; not with --levels\n"
       "  --verbose                          print the iteration count and last norm to stderr\n"
       "\n";
 }
@@ -408,8 +416,14 @@ int main(int argc, char **argv)
   if (auto v = one("connectivity")) connectivity = to_int("connectivity", *v);
   if (auto v = one("min-area")) min_area = to_long("min-area", *v);
   if (auto v = one("fill-holes")) fill_holes = to_long("fill-holes", *v);
-  const bool largest = vm.count("largest"), roi = vm.count("roi");
-  const bool clean_mask = vm.count("connectivity") || vm.count("min-area") || vm.count("fill-holes") || largest;
+  bool largest = vm.count("largest");
+  const bool roi = vm.count("roi");
+  bool clean_mask = vm.count("connectivity") || vm.count("min-area") || vm.count("fill-holes") || largest;
+  std::string morph_name, init_mask_filename;
+  double morph_radius = 1.0;
+  if (auto v = one("morph")) morph_name = *v;
+  if (auto v = one("morph-radius")) morph_radius = to_double("morph-radius", *v);
+  if (auto v = one("init-mask")) init_mask_filename = *v;
   if (auto v = one("rect")) rect = *v;
   if (auto v = one("circ")) circ = *v;
   std::string disk, init_kind = "checkerboard";
@@ -487,6 +501,7 @@ int main(int argc, char **argv)
     if (!disk.empty()) given.push_back("--disk");
     if (init_otsu) given.push_back("--init otsu");
     if (init_threshold) given.push_back("--threshold");
+    if (!init_mask_filename.empty()) given.push_back("--init-mask");
     if (given.size() > 1) msg_exit("Cannot initialize with both " + given[0] + " and " + given[1]);
   }
   int disk_cx = 0, disk_cy = 0, disk_r = 0;
@@ -515,6 +530,22 @@ int main(int argc, char **argv)
   if (energy_every > 0 && levels > 1) msg_exit("An energy series (--energy-every) cannot be combined with a coarse-to-fine run (--levels).");
   if (vm.count("score-tol") && truth_filename.empty()) msg_exit("A score tolerance (--score-tol) needs a ground truth (--truth).");
   if (!(score_tol >= 0.0) || !std::isfinite(score_tol)) msg_exit("Score tolerance must be a finite number >= 0.");
+  int morph_op = CVH_MORPH_NONE;
+  if (vm.count("morph")) {
+    if (morph_name == "dilate") morph_op = CVH_MORPH_DILATE;
+    else if (morph_name == "erode") morph_op = CVH_MORPH_ERODE;
+    else if (morph_name == "open") morph_op = CVH_MORPH_OPEN;
+    else if (morph_name == "close") morph_op = CVH_MORPH_CLOSE;
+    else msg_exit("Invalid morphology requested.\nCorrect values are: dilate, erode, open, close.");
+  }
+  if (vm.count("morph-radius") && !vm.count("morph")) msg_exit("A radius (--morph-radius) needs an operation (--morph).");
+  if (!(morph_radius >= 0.0) || !std::isfinite(morph_radius)) msg_exit("Morphology radius must be a finite number >= 0.");
+  const double morph_r2d = std::floor(morph_radius * morph_radius);
+  const uint32_t morph_r2 = morph_r2d >= 4294967295.0 ? 0xffffffffu : (uint32_t)morph_r2d;
+  if (!init_mask_filename.empty() && levels > 1)
+    msg_exit("A mask start (--init-mask) cannot be combined with a coarse-to-fine run (--levels): a mask is not resampled.");
+  if (!init_mask_filename.empty() && !std::ifstream(init_mask_filename).good())
+    msg_exit("Error: file \"" + init_mask_filename + "\" does not exists!");
   int colour_space = 0;   // 0: the planes stay B, G, R
   if (vm.count("colorspace")) {
     if (iequals(colorspace, "ycrcb")) colour_space = CVH_COLOUR_YCRCB;
@@ -545,6 +576,16 @@ int main(int argc, char **argv)
       for (int k = 0; k < t.channels; ++k) any |= t.px[(size_t)t.channels * q + k];
       truth[q] = any;
     }
+  }
+  std::vector<uint8_t> init_mask;   // --init-mask: one byte per pixel, non-zero = inside
+  if (!init_mask_filename.empty()) {
+    Image t;
+    if (!read_pnm(init_mask_filename, t) || t.channels != 1)
+      msg_exit("Error on opening \"" + init_mask_filename + "\" (a mask start must be a binary PGM)!");
+    if (t.h != h || t.w != w)
+      msg_exit("The mask start \"" + init_mask_filename + "\" is " + std::to_string(t.w) + " x " + std::to_string(t.h) + ", the input " +
+               std::to_string(w) + " x " + std::to_string(h) + ": they must have the same size.");
+    init_mask.assign(t.px.begin(), t.px.begin() + (std::ptrdiff_t)n);
   }
   // img: what the reference calls `img` (3 channels, BGR); planes: what cv::split leaves (:934-937)
   std::vector<uint8_t> img_bgr(n * 3);
@@ -619,6 +660,8 @@ int main(int argc, char **argv)
   if (levels > 1) {
   } else if (!rect.empty() || !disk.empty() || init_otsu || init_threshold) {
     device_start(ctx, 0);
+  } else if (!init_mask.empty()) {
+    cvh_check(ctx, cvh_init_mask(ctx, init_mask.data(), 1.0, -1.0), "cvh_init_mask");
   } else if (!circ.empty()) {
     int cx, cy, cr;
     if (std::sscanf(circ.c_str(), "%d,%d,%d", &cx, &cy, &cr) != 3 || cr <= 0)  // is_ok(): radius > 0
@@ -794,6 +837,13 @@ int main(int argc, char **argv)
     std::ofstream out(dump_u, std::ios::binary);
     out.write(reinterpret_cast<const char *>(u.data()), (std::streamsize)(n * sizeof(double)));
     if (!out) msg_exit("Error: cannot write \"" + dump_u + "\"");
+  }
+  // --morph: the cleaned mask (-I applied as invert), morphed, becomes the level set on the device -- behind --dump-u, --energy and
+  // --truth, which speak of the run's own level set; everything below then reads the result as a plain mask
+  if (morph_op != CVH_MORPH_NONE) {
+    cvh_check(ctx, cvh_morph_levelset(ctx, connectivity, invert ? 1 : 0, min_area, fill_holes, largest ? 1 : 0, morph_op, morph_r2, 1.0, -1.0),
+              "cvh_morph_levelset");
+    invert = false; min_area = 0; fill_holes = 0; largest = false; clean_mask = false;
   }
   // the cleaned mask (-I applied as invert), where a cleaning option was given: what --dump-mask, _selection and --roi then use
   std::vector<uint8_t> cleaned;

@@ -197,12 +197,14 @@ class Segmenter:
         init: "checkerboard"; a float64 / float32 tensor (N, H, W); or a start built on the device from the (smoothed) planes or from
         numbers -- "otsu" (+1 above Otsu's threshold of the grey values, -1 elsewhere; self.thresholds then holds the N thresholds),
         ("threshold", t), ("rect", (x, y, w, h)) and ("disk", (cx, cy, r)) (1 inside, 0 outside), the tuple's value one entry for all
-        members or a list of N (check_init).  A text or tuple `init` is validated first, before the images; a tensor `init` after them.
+        members or a list of N (check_init); or ("mask", t), t a uint8 or bool device tensor (N, H, W): +1 where it is nonzero, -1 elsewhere,
+        written on the device at a byte per pixel (cvh_init_mask_device_batch) -- a network's prediction, the previous frame's masks,
+        clean_masks' output.  A text or tuple `init` is validated first, before the images; a tensor `init`, or a mask's tensor, after them.
         levels > 1: ingest -> (Perona-Malik batch on the finest level) -> restrict batches downwards -> the start on the COARSEST level ->
         per level run_batch and a prolong batch (capi.run_coarse_to_fine_batch; max_steps applies per level) -> masks from the finest.
         "otsu" and ("threshold", t) act on the coarsest planes; the numbers of "rect" and "disk" are given in finest pixels and shifted
         right by levels - 1 (scale_init).  steps / norms are the finest level's, self.level_steps holds every level's counts.  A tensor
-        `init` and reinit_every > 0 are ValueErrors with levels > 1.
+        `init`, a ("mask", t) init (a mask is not resampled through the pyramid) and reinit_every > 0 are ValueErrors with levels > 1.
         colour (the constructor's): all members are converted with ONE cvh_convert_colour_batch AFTER the Perona-Malik batch, if any, and
         BEFORE the start and the run (with levels > 1: on the finest level, before the restricts -- a restrict of converted planes is just
         a restrict).  "otsu" and ("threshold", t) therefore see the CONVERTED planes (g = Y + the two chroma bytes), and images() returns
@@ -212,6 +214,9 @@ class Segmenter:
         self.energy_series; 0 takes none and leaves self.energy_series None.  It is a ValueError with levels > 1 or reinit_every > 0.
         energies() gives the terms of the final level sets either way."""
         kind, bits = None, None
+        mask_init = isinstance(init, tuple) and len(init) == 2 and init[0] == "mask"
+        if mask_init and self.levels > 1:
+            raise ValueError("a mask init needs levels = 1: a mask is not resampled through the pyramid")
         if self.levels > 1:
             if not isinstance(init, (str, tuple)):
                 raise ValueError("a tensor init needs levels = 1: with levels > 1 the start is built on the coarsest level")
@@ -223,10 +228,14 @@ class Segmenter:
             raise ValueError(f"energy_every must be an int >= 0, got {energy_every!r}")
         if energy_every and reinit_every:
             raise ValueError("energy_every and reinit_every cannot be combined: a reinitialisation replaces the level set the series follows")
-        if isinstance(init, (str, tuple)):
+        if mask_init:
+            kind = "mask"
+        elif isinstance(init, (str, tuple)):
             kind, start = check_init(init, self.n, self.channels)
         layout = check_images(images, self.n, self.h, self.w, self.channels, self.device, layout)
-        if kind is None:
+        if mask_init:
+            start = self._byte_planes(init[1], "the mask of init")
+        elif kind is None:
             bits = check_levelsets(init, self.n, self.h, self.w, self.device)
         if perona_malik is not None and len(perona_malik) != 3:
             raise ValueError("perona_malik must be (K, L, T)")
@@ -254,6 +263,8 @@ class Segmenter:
             capi.init_rect_batch(first, start)
         elif kind == "disk":
             capi.init_disk_batch(first, start)
+        elif kind == "mask":
+            capi.init_mask_batch(first, [start[i].data_ptr() for i in range(self.n)], 1.0, -1.0, stream)
         else:
             for i, ctx in enumerate(self.contexts):
                 ctx.set_levelset_device(init[i].data_ptr(), bits, stream)
@@ -298,13 +309,37 @@ class Segmenter:
         counts = capi.components_batch(self.contexts, [labels[i].data_ptr() for i in range(self.n)], conn, invert, self._stream())
         return labels, counts
 
-    def clean_masks(self, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False):
+    def _byte_planes(self, t, name):
+        """a uint8 or bool device tensor (N, H, W) as contiguous uint8 (a bool tensor is viewed, no copy); ValueError for anything else"""
+        if not isinstance(t, torch.Tensor) or t.dtype not in (torch.uint8, torch.bool):
+            raise ValueError(f"{name} must be a uint8 or bool tensor, got {getattr(t, 'dtype', type(t))}")
+        if tuple(t.shape) != (self.n, self.h, self.w):
+            raise ValueError(f"{name} must have shape {(self.n, self.h, self.w)}, got {tuple(t.shape)}")
+        _check_device(t, self.device, name)
+        t = t.view(torch.uint8) if t.dtype == torch.bool else t
+        return t if t.is_contiguous() else t.contiguous()
+
+    def clean_masks(self, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False, morph=None, radius=0.0):
         """Every member's cleaned mask (cvh_get_mask_clean_device_batch; Context.get_mask_clean names the steps) as a uint8 tensor
-        (N, H, W), valid for the next operation on the current stream without a host wait of the caller's."""
+        (N, H, W), valid for the next operation on the current stream without a host wait of the caller's.  morph = "dilate" / "erode" /
+        "open" / "close" (or a capi.MORPH_* code) applies that operation by a disk of `radius` pixels (one number or one per member) behind
+        the cleaning (cvh_get_mask_morph_device_batch: one set of launches); None is the cleaned mask alone."""
         masks = torch.empty((self.n, self.h, self.w), dtype=torch.uint8, device=torch.device("cuda", self.device))
-        capi.get_mask_clean_device_batch(self.contexts, [masks[i].data_ptr() for i in range(self.n)], conn, invert, min_area, fill_holes,
-                                         keep_largest, self._stream())
+        ptrs = [masks[i].data_ptr() for i in range(self.n)]
+        if morph is None:
+            capi.get_mask_clean_device_batch(self.contexts, ptrs, conn, invert, min_area, fill_holes, keep_largest, self._stream())
+        else:
+            capi.mask_morph_batch(self.contexts, ptrs, morph, radius=radius, conn=conn, invert=invert, min_area=min_area, fill_holes=fill_holes,
+                                  keep_largest=keep_largest, stream=self._stream())
         return masks
+
+    def morph(self, op, radius, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False, inside=1.0, outside=-1.0):
+        """clean_masks(morph=op, radius=radius) IN PLACE (cvh_morph_levelset_batch: one set of launches, one host wait): every member's
+        level set becomes `inside` where that mask is 1 and `outside` elsewhere, and a new run begins as after a fresh level set.
+        components(), measure(), contours(), score(), levelsets() and further iterations then see the result; the masks never leave the
+        device.  op None bakes the cleaned mask in."""
+        capi.morph_levelset_batch(self.contexts, op, radius=radius, conn=conn, invert=invert, min_area=min_area, fill_holes=fill_holes,
+                                  keep_largest=keep_largest, inside=inside, outside=outside)
 
     def measure(self, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False, cap=None):
         """The components of every member's mask -- clean_masks' for the same options, (0, 0, False) the raw one -- measured on the device

@@ -837,6 +837,79 @@ int cvh_contours_device_batch(cvh_context *const *ctxs, int n, int conn, int inv
                               int simplify, cvh_contour_loop *const *loops, const long *loop_caps, int32_t *const *d_points,
                               const long *point_caps, long *nloops, long *npoints, void *stream);
 
+/* ---- Mask morphology ----------------------------------------------------------------------------------------------------------
+ * Open, close, dilate or erode the mask by a disk ON THE DEVICE, and turn a byte mask into a level set there -- what a caller otherwise
+ * does with cvh_get_mask, scipy.ndimage.binary_opening / cv::morphologyEx on a CPU, and cvh_set_levelset at 8 bytes per pixel.  Together
+ * they close the loop segment -> clean or morph -> write back as the level set, after which cvh_components, cvh_measure, cvh_contours,
+ * cvh_score_mask*, cvh_reinit and further iterations see the result.  Everything is defined in integers: a member alone or inside any
+ * batch, and two calls in a row, give the same bytes, and every byte can be compared with ==.
+ *   plane       P is the set of the plane's pixels;
+ *   start set   F0 is the clean mask: exactly the set cvh_get_mask_clean gives for (conn, invert, min_area, fill_holes, keep_largest);
+ *               with (., invert, 0, 0, 0) it is cvh_get_mask's.  With "state" = 32 the class comes from the float state, as elsewhere;
+ *   disk        D(r2) = { (dx, dy) in Z^2 : dx^2 + dy^2 <= r2 } in 64-bit integers, r2 any uint32_t: r2 = 0 is the identity, r2 = 1 the
+ *               4-neighbour cross, r2 = 2 the 3 x 3 square;
+ *   dilate(F)   = { p in P : some d in D has p + d in F } -- p belongs iff the exact squared Euclidean distance from p to the nearest
+ *               pixel of F is <= r2; an empty F gives an empty result;
+ *   erode(F)    = { p in P : every d in D with p + d in P has p + d in F } = P \ dilate(P \ F);
+ *   open(F)     = dilate(erode(F)), close(F) = erode(dilate(F));
+ *   border      pixels outside the plane belong to neither set: only background pixels OF THE PLANE erode, so erosion and dilation are
+ *               exact duals under complement.  In scipy's terms: binary_dilation(F, disk, border_value=0) and
+ *               binary_erosion(F, disk, border_value=1);
+ *   op          CVH_MORPH_NONE, _DILATE, _ERODE, _OPEN, _CLOSE; with CVH_MORPH_NONE, or with r2 = 0, the result is F0;
+ *   mask start  given h*w bytes, u(p) = (byte(p) != 0) ? inside : outside;
+ *   level sets  inside and outside are any doubles, NaN included, stored bit for bit.  Every call here that writes a level set leaves
+ *               the context exactly as cvh_set_levelset of the same doubles would -- a new run, cleared counter, stop flag and sums, with
+ *               "state" = 32 the float pair adopted --, done the way the cvh_init_* calls do it; iterations in flight are settled first.
+ * cvh_get_mask_morph* only READ (as cvh_get_mask_clean*): a run continued after them is bit-identical to one without.  The output is a
+ * 0/1 uint8 mask, in host memory or in device memory the caller owns.
+ * cvh_morph_levelset* is IN PLACE: the level set becomes inside where that mask is 1 and outside elsewhere.  The morphed mask never
+ * leaves the device and needs no caller buffer; with CVH_MORPH_NONE the call bakes the cleaned mask into the level set.
+ * cvh_init_mask* needs neither an image nor a level set.  cvh_init_mask takes host bytes: 1 byte per pixel goes up, not 8.
+ * Device pointers follow the rules of "Device-memory input and output" above (hipPointerGetAttributes check, any byte alignment, event
+ * ordering against `stream`).  The *_batch forms serve n contexts of one device, any mix of shapes and channel counts, with ONE set of
+ * launches on member 0's stream, joined with every member's stream before and after as cvh_get_mask_clean_device_batch and
+ * cvh_init_checkerboard_batch; r2 is per member (an array of n), op is shared.  The single forms are the same kernels with n = 1.  A
+ * member's output depends on its inputs and shape alone: no atomic and no floating-point sum is involved.
+ * Host waits: cvh_get_mask_morph_device[_batch] NONE beyond what cvh_get_mask_clean_device makes (the caller's stream waits, the host
+ * does not); cvh_get_mask_morph ONE, for its bytes, as cvh_get_mask_clean; cvh_morph_levelset[_batch] and cvh_init_mask* ONE, as
+ * cvh_init_rect, behind which the members begin their new run.
+ * How (chan_vese_amd/csrc/morph_kernels.hip): the start set packed into one word per band of 32 rows and column (from the level set,
+ * or from the bytes the cleaning launches left); per pass a column launch -- each pixel's vertical distance to the nearest set pixel,
+ * cut off at floor(sqrt(r2)), with the reinitialisation's fix-up across bands -- and a row launch that accepts pixel j iff some
+ * |k| <= floor(sqrt(r2)) has k^2 + g(j + k)^2 <= r2 (a pixel of the set is accepted without a search) and packs the result again; an
+ * erosion is the same pass on the complement within the plane; open and close are two passes; an emit launch writes bytes or level-set
+ * doubles in 16-byte pieces.  The launches are ordered by kernel boundaries alone.
+ * Memory: 3.25 bytes per pixel (two planes of band words, a 16-bit distance field, a byte plane for the cleaned mask or the host
+ * form's bytes), allocated by a context's first call and kept until cvh_destroy; with cleaning, the components workspace as well.
+ * cvh_create allocates none of it and the automatic choices that weigh the contexts of a device do not count it.
+ * Cost, one run of tools/morph_probe.py on an MI355X (host clock around a call and its wait, 20 calls, measured once):
+ * open / close of a noisy disk after 50 iterations at r2 = 2, 25, 400: 109 - 384 us at 1024^2, 126 - 418 us at 2048^2, 192 - 694 us at
+ * 4096^2; cvh_init_mask_device 28 / 38 / 66 us.  cvh_get_mask + scipy + cvh_set_levelset took 15 ms to 9.1 s for the same bytes.
+ * CVH_ERR_ARG: op outside 0 .. 4; what cvh_get_mask_clean refuses for conn, min_area, fill_holes and keep_largest; a NULL r2, mask or
+ * pointer array; a pointer that is not device-accessible memory of the context's device; a plane with h^2 + w^2 >= 2^32 (cvh_reinit's
+ * cap; cvh_init_mask*: h w >= 2^32); ctxs NULL, n < 1, a NULL or duplicate member, members on different devices.  CVH_ERR_STATE: the
+ * morph calls on a member without a level set.  Checked for every member before anything is launched; the message names the member
+ * index and is cvh_last_error(NULL)'s and member 0's. */
+#define CVH_MORPH_NONE   0
+#define CVH_MORPH_DILATE 1
+#define CVH_MORPH_ERODE  2
+#define CVH_MORPH_OPEN   3
+#define CVH_MORPH_CLOSE  4
+int cvh_get_mask_morph(cvh_context *ctx, uint8_t *mask, int conn, int invert, long min_area, long fill_holes, int keep_largest, int op,
+                       uint32_t r2);   /* host bytes, 0/1 */
+int cvh_get_mask_morph_device(cvh_context *ctx, uint8_t *d_mask, int conn, int invert, long min_area, long fill_holes, int keep_largest,
+                              int op, uint32_t r2, void *stream);
+int cvh_get_mask_morph_device_batch(cvh_context *const *ctxs, int n, uint8_t *const *d_masks, int conn, int invert, long min_area,
+                                    long fill_holes, int keep_largest, int op, const uint32_t *r2, void *stream);
+int cvh_morph_levelset(cvh_context *ctx, int conn, int invert, long min_area, long fill_holes, int keep_largest, int op, uint32_t r2,
+                       double inside, double outside);
+int cvh_morph_levelset_batch(cvh_context *const *ctxs, int n, int conn, int invert, long min_area, long fill_holes, int keep_largest,
+                             int op, const uint32_t *r2, double inside, double outside);
+int cvh_init_mask(cvh_context *ctx, const uint8_t *mask, double inside, double outside);   /* host bytes */
+int cvh_init_mask_device(cvh_context *ctx, const uint8_t *d_mask, double inside, double outside, void *stream);
+int cvh_init_mask_device_batch(cvh_context *const *ctxs, int n, const uint8_t *const *d_masks, double inside, double outside,
+                               void *stream);
+
 /* Library version string, e.g. "chanvese_hip 0.1 (gfx950)". */
 const char *cvh_version(void);
 
