@@ -40,6 +40,7 @@ EXPORTS = [
     "cvh_energy", "cvh_energy_batch",
     "cvh_score_mask", "cvh_score_mask_device", "cvh_score_mask_device_batch",
     "cvh_measure", "cvh_measure_batch", "cvh_region_shape_of",
+    "cvh_overlaps", "cvh_overlaps_device", "cvh_overlaps_device_batch", "cvh_match_overlaps",
     "cvh_contours", "cvh_contours_device", "cvh_contours_device_batch",
     "cvh_get_mask_morph", "cvh_get_mask_morph_device", "cvh_get_mask_morph_device_batch", "cvh_morph_levelset", "cvh_morph_levelset_batch",
     "cvh_init_mask", "cvh_init_mask_device", "cvh_init_mask_device_batch",
@@ -59,6 +60,8 @@ REGION_SHAPE_DTYPE = np.dtype([(f, np.float64) for f in ("cx", "cy", "mu20", "mu
 # struct cvh_contour_loop (32 bytes): one closed loop of the mask's boundary ("Contours" in include/chanvese_hip.h)
 CONTOUR_LOOP_DTYPE = np.dtype([("first", np.uint32), ("edges", np.uint32), ("points", np.uint32), ("pad", np.uint32), ("offset", np.uint64),
                                ("area2", np.int64)])
+# struct cvh_overlap (16 bytes): one row of the contingency table ("Component overlaps" in include/chanvese_hip.h)
+OVERLAP_DTYPE = np.dtype([("a", np.int32), ("b", np.int32), ("count", np.uint32), ("pad", np.uint32)])
 LAYOUT_PLANAR, LAYOUT_INTERLEAVED = 0, 1
 # "Colour spaces": which plane is which primary, and the spaces cvh_convert_colour knows
 ORDERS = {"bgr": 0, "rgb": 1}
@@ -146,6 +149,48 @@ class Score:
     @property
     def surface_dice(self):
         return _ratio(self.within_m + self.within_t, self.surf_m + self.surf_t) if self.defined else math.nan
+
+
+class Match(C.Structure):
+    """struct cvh_match ("Component overlaps" in include/chanvese_hip.h)."""
+    _fields_ = [(f, C.c_uint32) for f in ("objects_a", "objects_b", "tp", "fp", "fn", "pad")]
+
+
+@dataclasses.dataclass(frozen=True)
+class ObjectScore:
+    """The components of a mask against a set of objects ("Component overlaps" in include/chanvese_hip.h): the exact integers of
+    cvh_match at one IoU threshold, the figures the header derives from them -- each NaN where its denominator is 0 --, and, where
+    match_overlaps took them, tp at the thresholds 10/20 .. 19/20 for mean_ap."""
+    objects_a: int
+    objects_b: int
+    tp: int
+    fp: int
+    fn: int
+    tp_at: tuple = ()
+
+    @property
+    def precision(self):
+        return _ratio(self.tp, self.tp + self.fp)
+
+    @property
+    def recall(self):
+        return _ratio(self.tp, self.tp + self.fn)
+
+    @property
+    def f1(self):
+        return _ratio(2 * self.tp, 2 * self.tp + self.fp + self.fn)
+
+    @property
+    def ap(self):
+        return _ratio(self.tp, self.tp + self.fp + self.fn)
+
+    @property
+    def mean_ap(self):
+        """the mean over num / den = 10/20 .. 19/20 of tp / (tp + fp + fn); NaN without objects on either side, or without tp_at"""
+        total = self.objects_a + self.objects_b
+        if len(self.tp_at) != 10 or not total:
+            return math.nan
+        return sum(t / (total - t) for t in self.tp_at) / 10
 
 
 def _score_of(s):
@@ -289,6 +334,11 @@ def lib():
         "cvh_measure": (C.c_int, [vp, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, vp, C.c_int, ip, vp]),
         "cvh_measure_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, C.POINTER(vp), ip, ip, vp]),
         "cvh_region_shape_of": (C.c_int, [vp, C.c_int, vp]),
+        "cvh_overlaps": (C.c_int, [vp, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, vp, vp, C.c_long, lp, ip]),
+        "cvh_overlaps_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, vp, vp, C.c_long, lp, ip, vp]),
+        "cvh_overlaps_device_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, C.POINTER(vp), C.POINTER(vp),
+                                                lp, lp, ip, vp]),
+        "cvh_match_overlaps": (C.c_int, [vp, C.c_long, C.c_uint32, C.c_uint32, vp, C.c_int, C.POINTER(Match)]),
         "cvh_contours": (C.c_int, [vp, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, C.c_int, vp, C.c_long, vp, C.c_long, lp, lp]),
         "cvh_contours_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, C.c_int, vp, C.c_long, vp, C.c_long, lp, lp, vp]),
         "cvh_contours_device_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, C.c_int, C.POINTER(vp), lp,
@@ -772,6 +822,68 @@ def measure_batch(contexts, conn=4, invert=False, min_area=0, fill_holes=0, keep
     return [(counts[i], tables[i][:min(counts[i], tables[i].size)].copy()) for i in range(n)]
 
 
+def overlaps_batch(contexts, others, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False, cap=None, stream=0):
+    """cvh_overlaps_device_batch: Context.overlaps for n contexts (any mix of shapes and channel counts) against n int32 label planes in
+    device memory (integer addresses of h * w int32), with one set of launches.  cap: None (all rows, at the price of a first call for
+    the counts), one number for every member or one per member.  Returns [(rows, K)] per context; every row is byte for byte the
+    member's own Context.overlaps()."""
+    contexts = list(contexts)
+    n = len(contexts)
+    args = _clean_args(conn, invert, min_area, fill_holes, keep_largest)
+    longs = C.c_long * max(n, 1)
+    pairs, counts = longs(), (C.c_int * max(n, 1))()
+    ptrs = _address_array(list(others), n)
+    if cap is None:
+        _batch_chk(lib().cvh_overlaps_device_batch(_member_array(contexts), n, *args, ptrs, None, None, pairs, counts, int(stream) or None))
+        caps = [pairs[i] for i in range(n)]
+    else:
+        caps = [int(c) for c in cap] if np.ndim(cap) else [int(cap)] * n
+        if len(caps) != n:
+            raise ValueError(f"cap: {len(caps)} values for {n} members")
+    tables = [np.zeros(max(c, 0), dtype=OVERLAP_DTYPE) for c in caps]
+    tptrs = (C.c_void_p * max(n, 1))(*[t.ctypes.data if t.size else None for t in tables])
+    _batch_chk(lib().cvh_overlaps_device_batch(_member_array(contexts), n, *args, ptrs, tptrs, longs(*caps), pairs, counts, int(stream) or None))
+    return [(tables[i][:min(pairs[i], tables[i].size)].copy(), counts[i]) for i in range(n)]
+
+
+def _threshold(threshold):
+    """(num, den) of an IoU threshold: a pair of integers as it is, a number as the nearest multiple of 1/1000"""
+    if np.ndim(threshold):
+        num, den = (int(v) for v in threshold)
+        return num, den
+    return int(round(float(threshold) * 1000)), 1000
+
+
+def match_overlaps(rows, threshold=(1, 2)):
+    """cvh_match_overlaps on a table of Context.overlaps (OVERLAP_DTYPE, all P rows): the components (a != 0) against the objects of
+    the other plane (b != 0) at the IoU threshold num / den (a pair of integers, or a number taken in thousandths; 1/2 <= t <= 1,
+    strictly-above).  Returns (score, match_of_a, ious): score an ObjectScore at the threshold, with tp at 10/20 .. 19/20 for mean_ap;
+    match_of_a an int32 array whose entry a - 1 is the b that component a matched, or 0; ious a list of (a, b, num, den) per matched
+    pair, the exact IoU count / (area_a + area_b - count) in Python integers.  Host arithmetic, no device."""
+    rows = np.ascontiguousarray(rows, dtype=OVERLAP_DTYPE).reshape(-1)
+    num, den = _threshold(threshold)
+    k = int(rows["a"].max()) if rows.size else 0
+    match_of_a = np.zeros(max(k, 0), np.int32)
+    L = lib()
+
+    def at(nu, de, out_match):
+        m = Match()
+        rc = L.cvh_match_overlaps(rows.ctypes.data if rows.size else None, rows.size, nu, de,
+                                  out_match.ctypes.data if out_match is not None and out_match.size else None, max(k, 0), C.byref(m))
+        if rc != CVH_OK:
+            raise CvhError(rc, f"cvh_match_overlaps: {rows.size} rows at {nu}/{de}")
+        return m
+    m = at(num, den, match_of_a)
+    tp_at = tuple(int(at(t, 20, None).tp) for t in range(10, 20))
+    area_a, area_b = {}, {}
+    for a, b, c in zip(rows["a"].tolist(), rows["b"].tolist(), rows["count"].tolist()):
+        area_a[a] = area_a.get(a, 0) + c
+        area_b[b] = area_b.get(b, 0) + c
+    ious = [(a, b, c, area_a[a] + area_b[b] - c) for a, b, c in zip(rows["a"].tolist(), rows["b"].tolist(), rows["count"].tolist())
+            if a != 0 and b != 0 and match_of_a[a - 1] == b]
+    return ObjectScore(int(m.objects_a), int(m.objects_b), int(m.tp), int(m.fp), int(m.fn), tp_at), match_of_a, ious
+
+
 def contours_batch(contexts, d_points=None, point_caps=None, conn=8, invert=False, min_area=0, fill_holes=0, keep_largest=False, simplify=True,
                    loop_caps=None, stream=0):
     """cvh_contours_device_batch: Context.contours for n contexts (any mix of shapes and channel counts) with one set of launches.
@@ -1117,6 +1229,32 @@ class Context:
         table = np.zeros(max(int(cap), 0), dtype=REGION_DTYPE)
         _batch_chk(self._L.cvh_measure(self._h, *args, table.ctypes.data if table.size else None, int(cap), C.byref(count), int(stream) or None))
         return count.value, table[:min(count.value, table.size)].copy()
+
+    def overlaps(self, other, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False, cap=None, stream=0):
+        """cvh_overlaps / cvh_overlaps_device: the contingency table of the mask's components -- measure's for the same five options --
+        against a second label plane, on the device.  other is a numpy array of (h, w), taken as int32 and staged by the library, or
+        the integer address of h * w int32 in device memory (for instance the label plane components() wrote for the previous frame),
+        ordered behind `stream`.  Returns (rows, K): rows a structured array (OVERLAP_DTYPE) of the first min(P, cap) rows (a, b, count),
+        sorted by a, then by b as signed integers, the rows with a = 0 or b = 0 included; cap = None asks for all P rows and COSTS TWO
+        CALLS (as measure); cap = 0 gives K alone.  Only reads: a run continued after it is bit-identical to one without."""
+        pairs, count = C.c_long(0), C.c_int(0)
+        args = _clean_args(conn, invert, min_area, fill_holes, keep_largest)
+        if isinstance(other, np.ndarray):
+            plane = np.ascontiguousarray(other, dtype=np.int32)
+            assert plane.shape == (self.h, self.w)
+
+            def call(table, cap_):
+                _batch_chk(self._L.cvh_overlaps(self._h, *args, plane.ctypes.data, table, cap_, C.byref(pairs), C.byref(count)))
+        else:
+            def call(table, cap_):
+                _batch_chk(self._L.cvh_overlaps_device(self._h, *args, int(other) or None, table, cap_, C.byref(pairs), C.byref(count),
+                                                       int(stream) or None))
+        if cap is None:
+            call(None, 0)
+            cap = pairs.value
+        table = np.zeros(max(int(cap), 0), dtype=OVERLAP_DTYPE)
+        call(table.ctypes.data if table.size else None, int(cap))
+        return table[:min(pairs.value, table.size)].copy(), count.value
 
     def contour_counts(self, conn=8, invert=False, min_area=0, fill_holes=0, keep_largest=False, simplify=True):
         """cvh_contours without outputs: (nloops, npoints) of the boundary of the mask."""

@@ -31,11 +31,11 @@ int members_ready(cvh_context *const *ctxs, int n, const char *what)
   return CVH_OK;
 }
 
-// staging: [member table][a second one, if asked for: the caller's][one word per member, zero at extra_off].  dst[i] is member i's
-// output (may be null)
-int fill_members(MemberCall *call, cvh_context *const *ctxs, int n, void *const *dst, const char *what, bool two_tables = false)
+// staging: [member table][a second one, if asked for: the caller's][one word per member, zero at extra_off][`more` bytes of the
+// caller's, zero].  dst[i] is member i's output (may be null)
+int fill_members(MemberCall *call, cvh_context *const *ctxs, int n, void *const *dst, const char *what, bool two_tables = false, size_t more = 0)
 {
-  const int rc = call->begin(ctxs, n, what, (size_t)n * sizeof(unsigned long long), 0, two_tables);
+  const int rc = call->begin(ctxs, n, what, (size_t)n * sizeof(unsigned long long) + more, 0, two_tables);
   if (rc != CVH_OK) return rc;
   for (int i = 0; i < n; ++i) {
     const cvh_context *c = ctxs[i];
@@ -146,9 +146,9 @@ int cc_clean_args(cvh_context *const *ctxs, int n, int conn, long min_area, long
   return clean_args(ctxs, n, conn, min_area, fill_holes, keep_largest, what);
 }
 int cc_members_ready(cvh_context *const *ctxs, int n, const char *what) { return members_ready(ctxs, n, what); }
-int cc_fill_members(MemberCall *call, cvh_context *const *ctxs, int n, void *const *dst, const char *what, bool two_tables)
+int cc_fill_members(MemberCall *call, cvh_context *const *ctxs, int n, void *const *dst, const char *what, bool two_tables, size_t more)
 {
-  return fill_members(call, ctxs, n, dst, what, two_tables);
+  return fill_members(call, ctxs, n, dst, what, two_tables, more);
 }
 
 extern "C" int cvh_components_batch(cvh_context *const *ctxs, int n, int conn, int invert, int32_t *const *d_labels, int *counts, void *stream)

@@ -3,7 +3,7 @@
 // context), csv_batch.hip (fused batch, and what every batch shares: the member and pair checks, the member predicates), pm_run.hip
 // (Perona-Malik), io_run.hip (device-memory I/O, reinitialisation, and the scaffolds of the member-table calls: MemberCall, write_planes,
 // the launch counters), init_run.hip (device-side initial level sets), components_run.hip (connected components), pyramid_run.hip
-// (coarse-to-fine), colour_run.hip (colour spaces), energy_run.hip (the functional's terms), score_run.hip (mask scores), morph_run.hip (mask morphology, mask starts), measure_run.hip (component measures), contour_run.hip (contours), debug_exports.hip (diagnostics).  Kernel sources do not include it.
+// (coarse-to-fine), colour_run.hip (colour spaces), energy_run.hip (the functional's terms), score_run.hip (mask scores), morph_run.hip (mask morphology, mask starts), measure_run.hip (component measures), contour_run.hip (contours), overlap_run.hip (component overlaps), debug_exports.hip (diagnostics).  Kernel sources do not include it.
 #pragma once
 #include <limits.h>
 #include <math.h>
@@ -159,6 +159,9 @@ struct cvh_context {   // opaque to callers; four groups
                                  // host form stages (5.5 bytes per pixel): allocated by the first call, kept -- not part of live_footprint either
   void *d_morph = nullptr;       // workspace of cvh_get_mask_morph* / cvh_morph_levelset* / cvh_init_mask (morph_run.hip): two planes of band words, the
                                  // 16-bit distance field and a byte plane (3.25 bytes per pixel): allocated by the first call, kept -- not part of live_footprint either
+  void *d_overlap = nullptr;     // cvh_overlaps* (overlap_run.hip): overlap_slots slots of the pair table and overlap_slots / 2 rows behind them (24 bytes
+  size_t overlap_slots = 0;      // per slot), grown where a call's table overflows, kept; d_overlap_plane: the int32 plane the host form stages
+  void *d_overlap_plane = nullptr;   // (4 bytes per pixel) -- allocated by the first call that needs them, not part of live_footprint either
   int coop_launch = -1;          // does the device launch cooperatively (-1: not asked yet; launches_cooperatively)
   int resident_cap = -1;         // workgroups of csv_resident_kernel the device holds at once (-1: not asked yet, 0: unavailable)
   int pm_resident_cap = -1;      // workgroups of pm_resident_kernel the device holds at once (-1: not asked yet)
@@ -257,8 +260,9 @@ void free_table(DeviceTable *t);
 // io_run.hip: launches so far in this process (debug_exports.hip): the launch sets (three kernels for all members) of cvh_reinit*, the
 // launches of cvh_restrict_image* / cvh_prolong_levelset*, those of cvh_convert_colour* / cvh_luma_image*, and the launch sets (term pass and
 // reduce pass for all members) of cvh_energy*, the launch sets (four kernels for all members) of cvh_score_mask*, and the launch sets (every
-// kernel of the call, for all members) of cvh_get_mask_morph* / cvh_morph_levelset* / cvh_init_mask*
-enum LaunchCounter { kReinitLaunchSets, kPyramidLaunches, kColourLaunches, kEnergyLaunchSets, kScoreLaunchSets, kMorphLaunchSets, kLaunchCounters };
+// kernel of the call, for all members) of cvh_get_mask_morph* / cvh_morph_levelset* / cvh_init_mask*, and the pair launches of cvh_overlaps*
+// (one per call, and one more each time a member's table had to grow)
+enum LaunchCounter { kReinitLaunchSets, kPyramidLaunches, kColourLaunches, kEnergyLaunchSets, kScoreLaunchSets, kMorphLaunchSets, kOverlapLaunchSets, kLaunchCounters };
 extern std::atomic<unsigned long> g_launches[kLaunchCounters];
 
 // io_run.hip: what every call on device memory or on a member table shares (the comments are at the definitions)
@@ -273,11 +277,12 @@ void levelset_target(const cvh_context *c, CvhIoMember *m);
 int ensure_workspace(cvh_context *c, void **slot, size_t bytes, const char *name, bool mirror = true);
 
 // components_run.hip: what measure_run.hip shares with the components calls -- cvh_get_mask_clean*'s argument checks; every member has
-// a level set, is settled and has its workspace; the member table of the components launches (with two_tables the second table is the caller's)
+// a level set, is settled and has its workspace; the member table of the components launches (with two_tables the second table is the
+// caller's, and `more` bytes of the device extra behind the members' words are the caller's too) -- overlap_run.hip shares them as well
 struct MemberCall;
 int cc_clean_args(cvh_context *const *ctxs, int n, int conn, long min_area, long fill_holes, int keep_largest, const char *what);
 int cc_members_ready(cvh_context *const *ctxs, int n, const char *what);
-int cc_fill_members(MemberCall *call, cvh_context *const *ctxs, int n, void *const *dst, const char *what, bool two_tables);
+int cc_fill_members(MemberCall *call, cvh_context *const *ctxs, int n, void *const *dst, const char *what, bool two_tables, size_t more = 0);
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) & ~(a - 1); }
 

@@ -260,6 +260,15 @@ hipError_t cvh_launch_cc_number(const CvhIoMember *tab, int nmem, unsigned grid,
 #define CVH_MEASURE_TILE 8192
 unsigned cvh_measure_blocks(size_t n);
 hipError_t cvh_launch_measure(const CvhIoMember *tab, int nmem, unsigned grid, bool any_c1, bool any_c3, hipStream_t s);
+// component overlaps (overlap_kernels.hip), behind cvh_launch_cc_number, on a SECOND table of the same members in sections of
+// cvh_measure_blocks(n) workgroups: src the parent words of the numbered forest, src2 the caller's int32 plane, dst the member's
+// src_stride slots (a power of two; cleared by the host), plane[0] the src_stride / 2 rows behind them (cvh_overlap, unsorted), sums the
+// member's CVH_OVERLAP_CTL 32-bit control words, zeroed: slots claimed (P), overflow, rows written; w2 != 0: rows are asked for;
+// h2 != 0: the member sits the launch out (a second launch for the members whose table overflowed).  An empty slot has key 0; the key of
+// (a, b) is ((a + 1) << 32) | (uint32_t)b.
+struct CvhOverlapSlot { unsigned long long key; unsigned count, pad; };
+#define CVH_OVERLAP_CTL 4
+hipError_t cvh_launch_overlap(const CvhIoMember *tab, int nmem, unsigned grid, bool any_rows, hipStream_t s);
 // contours (contour_kernels.hip, whose head comment describes a member's entry).  The pixel launches take sections of cvh_cc_blocks(n)
 // workgroups; behind the host's wait for E the edge launches take sections of cvh_contour_edge_blocks(E, n) workgroups (none for a member
 // without edges), a lane per edge -- or per pixel -- and trip.  The per-pixel workspace is [mask bytes][edge sets][prefix words][a count

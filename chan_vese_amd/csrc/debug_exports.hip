@@ -158,6 +158,9 @@ extern "C" unsigned long cvh_debug_score_launch_sets(void) { return g_launches[k
 // process -- one set is every launch of morph_kernels.hip (and of the cleaning) over all members of the call (tests/test_gpu_morph.py: a
 // batch of n is one set)
 extern "C" unsigned long cvh_debug_morph_launch_sets(void) { return g_launches[kMorphLaunchSets].load(); }
+// Diagnostic (not part of include/chanvese_hip.h): pair launches of cvh_overlaps* so far in this process -- one per call for all its
+// members, and one more each time a member's table overflowed and grew (tests/test_gpu_overlap.py: a table of 9216 pairs grows)
+extern "C" unsigned long cvh_debug_overlap_launch_sets(void) { return g_launches[kOverlapLaunchSets].load(); }
 
 // Diagnostic (not part of include/chanvese_hip.h): device time (HIP events on the leader's stream: table copy, the three launches, flag
 // copy) of the last cvh_reinit / cvh_reinit_batch this context led (tools/reinit_probe.py).

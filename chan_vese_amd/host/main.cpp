@@ -21,7 +21,11 @@
 // "Mask morphology") for --dump-mask, --roi, --measure, --contours and _selection; --init-mask FILE starts from a binary PGM.
 // Additions that do not collide with reference options: --dump-u, --dump-mask, --device, --math,
 // --state, --rect, --circ, --disk, --init, --threshold, --reinit, --connectivity, --min-area, --fill-holes, --largest, --roi, --verbose,
-// --levels, --energy, --energy-every, --truth, --score-tol, --measure, --contours, --contours-all, --morph, --morph-radius, --init-mask.  --contours FILE writes the boundary of
+// --levels, --energy, --energy-every, --truth, --score-tol, --measure, --contours, --contours-all, --morph, --morph-radius, --init-mask, --truth-labels.  --truth-labels FILE
+// relates the components of the mask --dump-mask uses (the cleaning options and -I apply) to the objects of a label image of the input's
+// size (a binary PGM with maxval <= 65535 or an 8-bit grey PNG; the values are the labels, 0 = no object) on the device (chanvese_hip.h,
+// "Component overlaps") and prints one line "objects: objects_a=... objects_b=... tp=... fp=... fn=... mean_ap=..." to stdout: the counts at
+// IoU > 1/2, and the mean over 0.50 .. 0.95 of tp / (tp + fp + fn).  --contours FILE writes the boundary of
 // the mask --dump-mask uses (the cleaning options and -I apply) as ordered closed loops traced on the device (chanvese_hip.h, "Contours"),
 // one text line per loop: "first edges area2 :" and the x,y pairs of its corners, with --contours-all of every lattice vertex.  --measure FILE writes one CSV line per component of the mask --dump-mask
 // uses (the cleaning options and -I apply), measured on the device (chanvese_hip.h, "Component measures"): label, the integers of the row,
@@ -126,6 +130,38 @@ bool read_pnm(const std::string &path, Image &img)
   return (size_t)in.gcount() == img.px.size();
 }
 
+// --truth-labels: a binary PGM with maxval <= 65535 (two bytes per sample, most significant first, above 255) or an 8-bit grey PNG; the
+// values are the labels
+bool read_labels(const std::string &path, int &h_out, int &w_out, std::vector<int32_t> &labels)
+{
+  if (pngio::is_png(path)) {
+    pngio::Decoded d;
+    const std::string err = pngio::read(path, d);
+    if (!err.empty()) { std::cerr << "PNG: " << err << "\n"; return false; }
+    if (d.channels != 1) return false;
+    h_out = d.h; w_out = d.w;
+    labels.assign(d.px.begin(), d.px.end());
+    return true;
+  }
+  std::ifstream in(path, std::ios::binary);
+  if (!in) return false;
+  std::string magic, sw, sh, smax;
+  if (!read_token(in, magic) || magic != "P5") return false;
+  if (!read_token(in, sw) || !read_token(in, sh) || !read_token(in, smax)) return false;
+  const long w = std::strtol(sw.c_str(), nullptr, 10), h = std::strtol(sh.c_str(), nullptr, 10);
+  const long maxv = std::strtol(smax.c_str(), nullptr, 10);
+  if (w <= 0 || h <= 0 || w > INT_MAX / 4 || h > INT_MAX / 4 || maxv < 1 || maxv > 65535) return false;
+  in.get();  // the single whitespace after maxval
+  const size_t n = (size_t)h * w, width = maxv > 255 ? 2 : 1;
+  std::vector<uint8_t> raw(n * width);
+  in.read(reinterpret_cast<char *>(raw.data()), (std::streamsize)raw.size());
+  if ((size_t)in.gcount() != raw.size()) return false;
+  h_out = (int)h; w_out = (int)w;
+  labels.resize(n);
+  for (size_t q = 0; q < n; ++q) labels[q] = width == 2 ? (int32_t)raw[2 * q] << 8 | raw[2 * q + 1] : (int32_t)raw[q];
+  return true;
+}
+
 bool write_pnm(const std::string &path, int h, int w, int channels, const uint8_t *px)
 {
   std::ofstream out(path, std::ios::binary);
@@ -194,7 +230,7 @@ const Spec kSpecs[] = {
     {"disk", 0, 1}, {"init", 0, 1}, {"threshold", 0, 1}, {"levels", 0, 1}, {"colorspace", 0, 1},
     {"connectivity", 0, 1}, {"min-area", 0, 1}, {"fill-holes", 0, 1}, {"largest", 0, 0}, {"roi", 0, 0},
     {"verbose", 0, 0}, {"energy", 0, 0}, {"energy-every", 0, 1}, {"truth", 0, 1}, {"score-tol", 0, 1}, {"measure", 0, 1}, {"contours", 0, 1}, {"contours-all", 0, 0},
-    {"morph", 0, 1}, {"morph-radius", 0, 1}, {"init-mask", 0, 1}};
+    {"morph", 0, 1}, {"morph-radius", 0, 1}, {"init-mask", 0, 1}, {"truth-labels", 0, 1}};
 
 struct Parsed {
   std::vector<std::pair<std::string, std::vector<std::string>>> opts;
@@ -354,6 +390,9 @@ void print_help()
       "                                     each (0: never); -N stays the total; not with -V, --reinit, --levels\n"
       "  --truth arg                        ground-truth PNG / PGM of the input's size (non-zero = foreground): print 'score: iou= dice=\n"
       "                                     hausdorff= assd= surface_dice= tp= fp= fn= tn=' of the final mask (inverted with -i) to stdout\n"
+      "  --truth-labels arg                 label image of the input's size (binary PGM, maxval <= 65535, or 8-bit grey PNG; 0 = no object):\n"
+      "                                     print 'objects: objects_a= objects_b= tp= fp= fn= mean_ap=' for the components of the mask (the\n"
+      "                                     cleaning options and -I apply) against its objects at IoU > 1/2, mean_ap over 0.50 .. 0.95\n"
       "  --score-tol arg (=2)               surface tolerance of --truth in pixels (surface_dice counts distances <= arg)\n"
       "  --measure arg                      write one CSV line per component of the mask --dump-mask uses (cleaning options, -I): label,\n"
       "                                     first,area,x0,y0,x1,y1,border,perimeter,cx,cy,mu20,mu02,mu11,theta,major,minor,mean..,var..\n"
@@ -440,6 +479,8 @@ int main(int argc, char **argv)
   if (auto v = one("energy-every")) energy_every = to_int("energy-every", *v);
   std::string truth_filename;
   if (auto v = one("truth")) truth_filename = *v;
+  std::string truth_labels_filename;
+  if (auto v = one("truth-labels")) truth_labels_filename = *v;
   std::string measure_filename;
   if (auto v = one("measure")) measure_filename = *v;
   std::string contours_filename;
@@ -576,6 +617,15 @@ int main(int argc, char **argv)
       for (int k = 0; k < t.channels; ++k) any |= t.px[(size_t)t.channels * q + k];
       truth[q] = any;
     }
+  }
+  std::vector<int32_t> truth_labels;   // --truth-labels: one label per pixel
+  if (!truth_labels_filename.empty()) {
+    int th = 0, tw = 0;
+    if (!read_labels(truth_labels_filename, th, tw, truth_labels))
+      msg_exit("Error on opening \"" + truth_labels_filename + "\" (a label image must be a binary PGM with maxval <= 65535 or an 8-bit grey PNG)!");
+    if (th != h || tw != w)
+      msg_exit("The label image \"" + truth_labels_filename + "\" is " + std::to_string(tw) + " x " + std::to_string(th) + ", the input " +
+               std::to_string(w) + " x " + std::to_string(h) + ": they must have the same size.");
   }
   std::vector<uint8_t> init_mask;   // --init-mask: one byte per pixel, non-zero = inside
   if (!init_mask_filename.empty()) {
@@ -844,6 +894,27 @@ int main(int argc, char **argv)
     cvh_check(ctx, cvh_morph_levelset(ctx, connectivity, invert ? 1 : 0, min_area, fill_holes, largest ? 1 : 0, morph_op, morph_r2, 1.0, -1.0),
               "cvh_morph_levelset");
     invert = false; min_area = 0; fill_holes = 0; largest = false; clean_mask = false;
+  }
+  // --truth-labels: the components of the mask --dump-mask uses against the objects of the label image, read off one table
+  if (!truth_labels.empty()) {
+    long pairs = 0;
+    const int inv = invert ? 1 : 0, big = largest ? 1 : 0;
+    cvh_check(ctx, cvh_overlaps(ctx, connectivity, inv, min_area, fill_holes, big, truth_labels.data(), nullptr, 0, &pairs, nullptr), "cvh_overlaps");
+    std::vector<cvh_overlap> table((size_t)pairs);
+    cvh_check(ctx, cvh_overlaps(ctx, connectivity, inv, min_area, fill_holes, big, truth_labels.data(), table.data(), pairs, &pairs, nullptr),
+              "cvh_overlaps");
+    cvh_match half;
+    if (cvh_match_overlaps(table.data(), pairs, 1, 2, nullptr, 0, &half) != CVH_OK) msg_exit("Error: cvh_match_overlaps refused the table");
+    double mean_ap = 0.0;
+    const double objects = (double)half.objects_a + (double)half.objects_b;
+    for (uint32_t t = 10; t < 20; ++t) {
+      cvh_match m;
+      if (cvh_match_overlaps(table.data(), pairs, t, 20, nullptr, 0, &m) != CVH_OK) msg_exit("Error: cvh_match_overlaps refused the table");
+      mean_ap += (double)m.tp / (objects - (double)m.tp);   // (tp + fp + fn = objects_a + objects_b - tp)
+    }
+    mean_ap = objects != 0.0 ? mean_ap / 10.0 : std::numeric_limits<double>::quiet_NaN();
+    std::printf("objects: objects_a=%u objects_b=%u tp=%u fp=%u fn=%u mean_ap=%.17g\n", half.objects_a, half.objects_b, half.tp, half.fp, half.fn,
+                mean_ap);
   }
   // the cleaned mask (-I applied as invert), where a cleaning option was given: what --dump-mask, _selection and --roi then use
   std::vector<uint8_t> cleaned;

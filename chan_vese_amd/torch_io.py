@@ -348,6 +348,37 @@ class Segmenter:
         centroid, moments, axes, mean and variance from it.  cap = None asks for every row at the price of a first call for the counts."""
         return capi.measure_batch(self.contexts, conn, invert, min_area, fill_holes, keep_largest, cap, self._stream())
 
+    def _label_planes(self, labels):
+        """an int32 device tensor (N, H, W), or a list of N tensors (H, W), as N contiguous planes; ValueError for anything else"""
+        planes = list(labels) if not isinstance(labels, torch.Tensor) else ([labels[i] for i in range(labels.shape[0])] if labels.dim() == 3 else None)
+        if planes is None or len(planes) != self.n:
+            raise ValueError(f"labels must be an int32 tensor of shape {(self.n, self.h, self.w)} or a list of {self.n} tensors")
+        out = []
+        for i, p in enumerate(planes):
+            if not isinstance(p, torch.Tensor) or p.dtype != torch.int32 or tuple(p.shape) != (self.h, self.w):
+                raise ValueError(f"labels[{i}] must be an int32 tensor of shape {(self.h, self.w)}, got {getattr(p, 'dtype', type(p))} "
+                                 f"{tuple(getattr(p, 'shape', ()))}")
+            _check_device(p, self.device, f"labels[{i}]")
+            out.append(p if p.is_contiguous() else p.contiguous())
+        return out
+
+    def overlaps(self, labels, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False, cap=None):
+        """The contingency table of every member's components -- measure's for the same options -- against a second label plane each
+        (cvh_overlaps_device_batch: one set of launches, ordered behind the current stream).  labels is an int32 device tensor
+        (N, H, W) or a list of N tensors (H, W): an instance ground truth, or the tensors components() returned for the PREVIOUS FRAME
+        (frame-to-frame correspondence: the labels never leave the device).  Returns one row array per member (capi.OVERLAP_DTYPE: a, b,
+        count; sorted by a, then b; a = 0 and b = 0 included), byte for byte its context's Context.overlaps()."""
+        planes = self._label_planes(labels)
+        res = capi.overlaps_batch(self.contexts, [p.data_ptr() for p in planes], conn, invert, min_area, fill_holes, keep_largest, cap, self._stream())
+        return [rows for rows, _ in res]
+
+    def match(self, labels, threshold=0.5, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False):
+        """overlaps() read as object-level scores (capi.match_overlaps on every member's table): one (score, match_of_a, ious) per member
+        -- score a capi.ObjectScore at the IoU threshold (strictly above; a number >= 0.5 taken in thousandths, or a pair (num, den)),
+        with mean_ap over 0.50 .. 0.95; match_of_a[a - 1] the label component a matched, or 0; ious the exact (a, b, num, den) of the
+        matched pairs.  labels as in overlaps(): a ground truth, or components() of the previous frame."""
+        return [capi.match_overlaps(rows, threshold) for rows in self.overlaps(labels, conn, invert, min_area, fill_holes, keep_largest)]
+
     def contours(self, conn=8, invert=False, min_area=0, fill_holes=0, keep_largest=False, simplify=True):
         """The boundary of every member's mask -- clean_masks' for the same options -- as ordered closed loops, traced on the device
         (cvh_contours_device_batch, ordered behind the current stream): one (loops, points) per member, loops a numpy structured array

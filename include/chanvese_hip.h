@@ -702,6 +702,94 @@ int cvh_score_mask_device(cvh_context *ctx, const uint8_t *d_truth, int invert, 
 int cvh_score_mask_device_batch(cvh_context *const *ctxs, int n, const uint8_t *const *d_truths, int invert, uint32_t tol2,
                                 cvh_mask_score *out, void *stream);
 
+/* ---- Component overlaps -------------------------------------------------------------------------------------------------------
+ * "Mask scores" compares the mask with a ground-truth MASK; these calls relate the mask's OBJECTS to another set of objects: an instance
+ * ground truth (per-object IoU, detections at an IoU threshold, precision, recall, F1, the threshold-averaged precision of the
+ * cell-segmentation benchmarks), the components of the previous frame (cvh_components writes a device label plane: frame-to-frame
+ * correspondence), or any labelling in which splits and merges are to be found.  All of it is read off one integer object, the
+ * CONTINGENCY TABLE of two labelings -- what a caller otherwise takes by fetching 4 bytes of labels per pixel across PCIe and running
+ * np.unique over h w pairs on a CPU.  Every field is an integer count: every row can be compared with ==.
+ * For a context of h x w:
+ *     A(p)    the label cvh_components gives pixel p on the mask cvh_get_mask_clean defines for (conn, invert, min_area, fill_holes,
+ *             keep_largest) -- with (0, 0, 0) the raw mask of cvh_get_mask, exactly the arguments of cvh_measure: 0 is background,
+ *             1 .. K are the components, numbered by their smallest flat index AFTER cleaning;
+ *     B(p)    the caller's plane of h x w int32_t, row-major.  Any 32-bit value is allowed, negative ones included; the device treats it
+ *             as opaque, and only the derived figures below read B == 0 as "no object";
+ *     table   one row cvh_overlap { a, b, count, pad = 0 } (16 bytes) for every pair with count = #{p : A(p) = a, B(p) = b} > 0.  The
+ *             pairs with a = 0 or b = 0, and (0, 0), are included;
+ *     order   by a ascending, then by b ascending as a signed int32_t;
+ *     P       the number of rows.  The counts add up to h w, and the area of component a is the sum of its rows (cvh_components' and
+ *             cvh_measure's area is the cross-check).
+ * Bound: h w < 2^31, so a count fits 32 bits.
+ * Determinism: integer adds are order-free and the order of the rows is the sort's, not the schedule's: a member alone or inside any
+ * batch, and two calls in a row, give the same P and the same bytes.
+ * cvh_overlaps takes the plane from host memory: it is staged into the context (4 bytes per pixel) and the device path runs.
+ * cvh_overlaps_device and cvh_overlaps_device_batch take device pointers under the rules of "Device-memory input and output": memory
+ * that kernels on the context's device can address, aligned to 4 bytes as d_labels is, ordered behind what `stream` holds at the call
+ * (the tensors cvh_components wrote for the previous frame qualify as they are).  `table` is HOST memory of `cap` rows, like
+ * cvh_components' table; it may be NULL, and so may `tables` or any entry of it (caps is read only for the members with a table).
+ * *pairs is always the full P, the table receives the first min(P, cap) rows in the defined order, *count is K; pairs, count and their
+ * arrays may be NULL.  The batch form serves n contexts of one device, any mix of shapes and channel counts, with ONE set of launches
+ * on member 0's stream, joined with every member's stream before and after as cvh_components_batch; the single forms are the same
+ * kernels with n = 1.
+ * The calls only READ: iterations in flight are settled first and the FP64 mirror of a float state is refreshed, as the getters do;
+ * level set, run state, sums, options and planes are untouched, and a run continued after the call is bit-identical to one without.
+ * An image is not required.
+ * How (chan_vese_amd/csrc/overlap_kernels.hip): the cleaning and numbering launches of cvh_measure on the components workspace; then a
+ * workgroup streams 8192 pixels of A and B in raster order, once, at 8 bytes per pixel; a lane forms the 64-bit key (a, b); the first
+ * lane of every run of equal keys inside a wave adds the run's length to a 512-slot table in LDS (open addressing, at most 8 probes;
+ * beyond them straight to global memory), and every occupied LDS slot goes once to the member's global open-addressing table: a key is
+ * claimed by a 64-bit compare-and-swap against the empty key (whose a-half is -1), the count added by a 32-bit add, plain vector atomics
+ * at agent scope.  A plane that is one pair -- the contended case -- costs one global atomic per workgroup.  Every probe loop is bounded
+ * by the table's size and no workgroup waits for another: a table more than half full sets an overflow word, the remaining inserts are
+ * dropped, and the host runs the pair launch again for that member on a table four times as large.  The table keeps its size in the
+ * context, so the growth is paid once.  A last launch compacts the occupied slots into rows (one atomic per wave); they come down
+ * unsorted and are SORTED ON THE HOST behind the wait for them (std::sort on 16-byte rows; P is the number of pairs, not of pixels).
+ * Host waits: ONE for K, P and the overflow words; ONE MORE per growth of a member's table (none once the context's table has grown to
+ * its content); and ONE MORE where any rows are asked for and P > 0 (P decides how many bytes come down).
+ * Memory: the components workspace (8 bytes per pixel), cvh_get_mask's byte per pixel where the mask is cleaned, 4 bytes per pixel in
+ * the host form, and 24 bytes per slot of the pair table: 4096 slots (96 KiB) at first, four times as many after each overflow, so at
+ * most 8 P + 8 slots in use -- and in the worst case, every pixel its own pair, the first power of two above 2 h w: at most 96 bytes
+ * per pixel.  Allocated on first use, kept until cvh_destroy; cvh_create allocates none of it.
+ * Cost, one run of tools/overlap_probe.py on an MI355X (host clock around a call with a full table, its waits and the
+ * sort, 20 calls, measured once): at 4096^2, a noisy disk after 50 iterations (350 components) against the clean disk's labels (P = 351)
+ * 527 us, against a grid of 32 x 32 squares (P = 16975) 1628 us, of which about 1.0 ms are the rows' compaction, wait, fetch and sort
+ * together (the count alone: 578 us); the plane wholly inside 651 / 1703 us; beside 73 - 126 ms for the same rows from cvh_components
+ * with a label plane, a fetch and np.unique.  One case loses: at 1024^2 the same disk is still 90602 components, P = 90604, and the full
+ * table takes 7.0 ms beside 6.7 ms the old way (the count alone 0.5 ms): with P near h w the fetch and the host's sort are the call.
+ * CVH_ERR_ARG: what cvh_get_mask_clean refuses for conn, min_area, fill_holes and keep_largest; other or d_others NULL or a NULL entry
+ * of d_others; a pointer that is not device-accessible memory of the context's device or not aligned to 4 bytes; a negative cap of a
+ * member with a table; ctxs NULL, n < 1, a NULL or duplicate member, members on different devices; h w >= 2^31.  CVH_ERR_STATE: a member
+ * without a level set.  Every member is checked before anything is launched, and the outputs are written only by a call that succeeds;
+ * the message names the member index and is cvh_last_error(NULL)'s and member 0's.
+ * cvh_match_overlaps (host only, no device, no context) derives the object-level counts from a table of `pairs` rows at the IoU
+ * threshold num / den:
+ *     objects_a, objects_b   the number of distinct a != 0, of distinct b != 0
+ *     area_a, area_b         the sum of the counts of the rows with that a, with that b
+ *     match                  a pair (a != 0, b != 0) matches when count den > num (area_a + area_b - count) in 64-bit unsigned arithmetic:
+ *                            IoU strictly above num / den
+ *     tp                     the number of matches; fp = objects_a - tp, fn = objects_b - tp
+ * The call requires 0 < den <= 65535 and den <= 2 num <= 2 den: with IoU > 1/2 an a matches at most one b and a b at most one a (two
+ * disjoint sets cannot each hold more than half of a third), so NO ASSIGNMENT PROBLEM arises and the matches are read off the rows.
+ * match_of_a may be NULL; otherwise it holds k >= the largest a entries, and entry a - 1 receives the b that a matched, or 0.
+ * Derived figures (host arithmetic in doubles; chan_vese_amd/capi.py ObjectScore implements them once):
+ *     precision = tp / (tp + fp)      recall = tp / (tp + fn)      f1 = 2 tp / (2 tp + fp + fn)      ap = tp / (tp + fp + fn)
+ *     mean_ap   the mean of ap over num / den = 10/20, 11/20 .. 19/20
+ * each NaN where its denominator is 0.
+ * CVH_ERR_ARG: out NULL, table NULL with pairs > 0, pairs < 0; a threshold outside the range above; a table that is not in the defined
+ * order (a pair twice included), has a zero count or a negative a; k smaller than the largest a (with match_of_a). */
+typedef struct cvh_overlap { int32_t a, b; uint32_t count, pad; } cvh_overlap;   /* 16 bytes */
+typedef struct cvh_match { uint32_t objects_a, objects_b, tp, fp, fn, pad; } cvh_match;
+int cvh_overlaps(cvh_context *ctx, int conn, int invert, long min_area, long fill_holes, int keep_largest,
+                 const int32_t *other /* host */, cvh_overlap *table, long cap, long *pairs, int *count);
+int cvh_overlaps_device(cvh_context *ctx, int conn, int invert, long min_area, long fill_holes, int keep_largest,
+                        const int32_t *d_other, cvh_overlap *table, long cap, long *pairs, int *count, void *stream);
+int cvh_overlaps_device_batch(cvh_context *const *ctxs, int n, int conn, int invert, long min_area, long fill_holes, int keep_largest,
+                              const int32_t *const *d_others, cvh_overlap *const *tables, const long *caps, long *pairs, int *counts,
+                              void *stream);
+int cvh_match_overlaps(const cvh_overlap *table, long pairs, uint32_t num, uint32_t den, int32_t *match_of_a, int k,
+                       cvh_match *out);   /* host only */
+
 /* ---- Component measures -------------------------------------------------------------------------------------------------------
  * "Connected components of the mask" labels, boxes and cleans; these calls MEASURE: per component where it is, how large, how
  * elongated and how bright -- what a caller otherwise takes with cvh_get_mask, cvh_get_image (both across PCIe) and a pass of
