@@ -142,16 +142,12 @@ extern "C" void cvh_destroy(cvh_context *c)
   if (c->h_io) (void)hipHostFree(c->h_io);
   if (c->d_reinit) (void)hipFree(c->d_reinit);
   if (c->d_cc) (void)hipFree(c->d_cc);
-  if (c->d_cc_table) (void)hipFree(c->d_cc_table);
-  if (c->d_regions) (void)hipFree(c->d_regions);
+  for (DeviceTable *t : {&c->cc_table, &c->regions, &c->contour_edges, &c->contour_points, &c->overlap}) free_table(t);
   if (c->d_contour) (void)hipFree(c->d_contour);
-  if (c->d_contour_edges) (void)hipFree(c->d_contour_edges);
-  if (c->d_contour_points) (void)hipFree(c->d_contour_points);
   if (c->d_hist) (void)hipFree(c->d_hist);
   if (c->d_energy) (void)hipFree(c->d_energy);
   if (c->d_score) (void)hipFree(c->d_score);
   if (c->d_morph) (void)hipFree(c->d_morph);
-  if (c->d_overlap) (void)hipFree(c->d_overlap);
   if (c->d_overlap_plane) (void)hipFree(c->d_overlap_plane);
   if (c->ev_io_in) (void)hipEventDestroy(c->ev_io_in);
   if (c->ev_io_out) (void)hipEventDestroy(c->ev_io_out);

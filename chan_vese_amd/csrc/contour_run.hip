@@ -1,7 +1,7 @@
 // contour_run.hip — host side of cvh_contours* (include/chanvese_hip.h, "Contours"): the boundaries of the masks of n contexts, raw or
-// cleaned, as ordered closed loops -- ONE MemberCall (cvh_host.h, io_run.hip) with two member tables: the components calls' layout (the
-// level set in src, the mask bytes in dst, the components workspace in plane[]) for the mask or cleaning launches, and a second one for
-// contour_kernels.hip.  The single-context forms are batches of one.  The calls only read: nothing of a member's level set, run state,
+// cleaned, as ordered closed loops -- ONE MemberCall (cvh_host.h, io_run.hip) with two member tables: the mask source's (MaskSource,
+// components_run.hip: the level set in src, the mask bytes in dst, the components workspace in plane[]) for the mask or cleaning
+// launches, and a second one for contour_kernels.hip.  The single-context forms are batches of one.  The calls only read: nothing of a member's level set, run state,
 // sums, options or planes is assigned here.  Two host waits: the edge counts (they size the per-edge workspace, the sections of the
 // edge launches and the rounds of the doubling), then the loop and point counts with the rows.
 #include "cvh_host.h"
@@ -17,31 +17,15 @@ struct Outputs {
   bool on_host;
 };
 
-int grow(cvh_context *lead, void **slot, size_t *have, size_t want, size_t unit)
+int contours(cvh_context *const *ctxs, int n, const MaskSource &src, int simplify, const Outputs &out, void *stream, const char *what)
 {
-  if (*have >= want) return CVH_OK;
-  if (*slot) { HIPCHK(lead, hipFree(*slot)); *slot = nullptr; *have = 0; }
-  const size_t cap = want + want / 4;
-  HIPCHK(lead, hipMalloc(slot, unit ? cap * unit : cvh_contour_edge_bytes(cap)));
-  *have = cap;
-  return CVH_OK;
-}
-
-int contours(cvh_context *const *ctxs, int n, int conn, int invert, long min_area, long fill_holes, int keep_largest, int simplify,
-             const Outputs &out, void *stream, const char *what)
-{
-  int rc = cc_clean_args(ctxs, n, conn, min_area, fill_holes, keep_largest, what);
+  int rc = src.check(ctxs, n, what);
   if (rc != CVH_OK) return rc;
   if (simplify != 0 && simplify != 1) return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: simplify must be 0 or 1, got %d", what, simplify);
-  for (int i = 0; i < n; ++i) {
-    if (out.loops && out.loops[i]) {
-      if (!out.loop_caps) return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: loop tables without loop_caps", what);
-      if (out.loop_caps[i] < 0) return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: member %d: loop_cap must not be negative, got %ld", what, i, out.loop_caps[i]);
-    }
-    if (out.points && out.points[i]) {
-      if (!out.point_caps) return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: point arrays without point_caps", what);
-      if (out.point_caps[i] < 0) return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: member %d: point_cap must not be negative, got %ld", what, i, out.point_caps[i]);
-    }
+  for (int i = 0; i < n; ++i) {   // (member by member: a member's points before the next member's loops)
+    rc = members_caps_fit(ctxs, n, what, (const void *const *)out.loops, out.loop_caps, "loop_cap", "loop tables without loop_caps", i);
+    if (rc == CVH_OK) rc = members_caps_fit(ctxs, n, what, (const void *const *)out.points, out.point_caps, "point_cap", "point arrays without point_caps", i);
+    if (rc != CVH_OK) return rc;
   }
   rc = members_below(ctxs, n, what, 30);   // (an edge id, 4 p + k, is 32 bits)
   if (rc != CVH_OK) return rc;
@@ -49,18 +33,10 @@ int contours(cvh_context *const *ctxs, int n, int conn, int invert, long min_are
   HIPCHK(lead, hipSetDevice(lead->device));
   for (int i = 0; !out.on_host && out.points && i < n; ++i) {
     if (!out.points[i]) continue;
-    rc = pointer_check(ctxs, n, i, out.points[i], what);
+    rc = element_pointer_check(ctxs, n, i, out.points[i], sizeof(int32_t), what);
     if (rc != CVH_OK) return rc;
-    if ((uintptr_t)out.points[i] % sizeof(int32_t))
-      return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: member %d: %p is not aligned to 4 bytes", what, i, (const void *)out.points[i]);
   }
-  const bool drop = min_area > 1, cleaned = drop || fill_holes || keep_largest;
-  if (cleaned) rc = cc_members_ready(ctxs, n, what);
-  else {
-    rc = members_have_levelsets(ctxs, n, what);
-    if (rc == CVH_OK) rc = settle_all(ctxs, n, what);
-    if (rc == CVH_OK) rc = members_mirrors_fresh(ctxs, n, what);
-  }
+  rc = src.ready(ctxs, n, what, false);
   if (rc != CVH_OK) return rc;
   for (int i = 0; i < n; ++i) {
     cvh_context *c = ctxs[i];
@@ -76,16 +52,7 @@ int contours(cvh_context *const *ctxs, int n, int conn, int invert, long min_are
   for (int i = 0; i < n; ++i) {
     const cvh_context *c = ctxs[i];
     uint8_t *const base = (uint8_t *)c->d_contour;
-    CvhIoMember &m = call.tab[i];
-    m.src = c->d_u[current_buffer(c)];
-    m.dst = base;
-    if (cleaned) {
-      m.plane[0] = (uint8_t *)c->d_cc;
-      m.plane[1] = m.plane[0] + c->n * sizeof(unsigned);
-      m.plane[2] = m.plane[1] + c->n * sizeof(unsigned);
-    }
-    m.sums = (unsigned long long *)(call.db + call.extra_off) + i;
-    m.nblk = cvh_cc_blocks(c->n);
+    src.fill(&call, i, base, (unsigned long long *)(call.db + call.extra_off) + i, false);
     CvhIoMember &t = call.tab2[i];
     t.src = base;
     t.plane[0] = base + cvh_contour_bits_offset(c->n);
@@ -95,11 +62,8 @@ int contours(cvh_context *const *ctxs, int n, int conn, int invert, long min_are
     t.nblk = cvh_cc_blocks(c->n);
   }
   rc = call.run(stream, false, true, [&]() -> int {   // the first host wait of the call: the edge counts
-    if (!drop) HIPCHK(lead, cvh_launch_io_mask(call.dtab(), n, call.grid, invert, lead->stream));   // the plain mask (step 1 of the cleaning is off)
-    if (cleaned) {
-      const unsigned a = (unsigned)std::min<long>(min_area, 0x7fffffffl);
-      HIPCHK(lead, cvh_launch_cc_clean(call.dtab(), n, call.grid, conn, invert, a, fill_holes, keep_largest, lead->stream));
-    }
+    const int rc_mask = src.launch(call, true);   // (a raw mask too: the count launch reads the mask bytes)
+    if (rc_mask != CVH_OK) return rc_mask;
     HIPCHK(lead, cvh_launch_contours_count(call.dtab2(), n, call.grid2, lead->stream));
     HIPCHK(lead, hipMemcpyAsync(words, d_words, (size_t)n * 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, lead->stream));
     return CVH_OK;
@@ -122,19 +86,20 @@ int contours(cvh_context *const *ctxs, int n, int conn, int invert, long min_are
     CvhIoMember &t = call.tab2[i];
     t.nblk = cvh_contour_edge_blocks(E, c->n);
     if (!E) continue;
-    rc = grow(lead, &c->d_contour_edges, &c->contour_edge_cap, E, 0);
+    rc = grow_table_to(lead, &c->contour_edges, E, E + E / 4, cvh_contour_edge_bytes(E + E / 4));
     if (rc != CVH_OK) return rc;
-    t.dst = c->d_contour_edges;
-    t.src_stride = c->contour_edge_cap;
+    t.dst = c->contour_edges.d;
+    t.src_stride = c->contour_edges.count;
     if (out.loops && out.loops[i]) row_room[(size_t)i] = std::min<size_t>((size_t)out.loop_caps[i], E / 4);
     if (!out.points || !out.points[i]) continue;
     const unsigned long long cap = (unsigned long long)out.point_caps[i];
     point_room[(size_t)i] = (size_t)std::min<unsigned long long>(cap, E);
     if (out.on_host) {
       if (!point_room[(size_t)i]) continue;
-      rc = grow(lead, &c->d_contour_points, &c->contour_point_cap, point_room[(size_t)i], 2 * sizeof(int32_t));
+      const size_t room = point_room[(size_t)i];
+      rc = grow_table_to(lead, &c->contour_points, room, room + room / 4, (room + room / 4) * 2 * sizeof(int32_t));
       if (rc != CVH_OK) return rc;
-      t.src2 = c->d_contour_points;
+      t.src2 = c->contour_points.d;
     } else {
       t.src2 = out.points[i];
     }
@@ -144,24 +109,24 @@ int contours(cvh_context *const *ctxs, int n, int conn, int invert, long min_are
   call.grid2 = lay_out(call.tab2, n);
   std::vector<std::vector<cvh_contour_loop>> rows((size_t)n);
   std::vector<std::vector<int32_t>> pts((size_t)n);
-  HIPCHK(lead, hipMemcpyAsync((void *)call.dtab2(), call.tab2, (size_t)n * sizeof(CvhIoMember), hipMemcpyHostToDevice, lead->stream));
-  HIPCHK(lead, cvh_launch_contours_trace(call.dtab2(), n, call.grid2, conn, simplify, rounds, any_points, lead->stream));
+  rc = call.upload_again(call.tab2);
+  if (rc != CVH_OK) return rc;
+  HIPCHK(lead, cvh_launch_contours_trace(call.dtab2(), n, call.grid2, src.conn, simplify, rounds, any_points, lead->stream));
   HIPCHK(lead, hipMemcpyAsync(words, d_words, (size_t)n * 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, lead->stream));
   for (int i = 0; i < n; ++i) {
     const cvh_context *c = ctxs[i];
     if (row_room[(size_t)i]) {
       rows[(size_t)i].resize(row_room[(size_t)i]);
-      HIPCHK(lead, hipMemcpyAsync(rows[(size_t)i].data(), (const uint8_t *)c->d_contour_edges + cvh_contour_rows_offset(c->contour_edge_cap),
+      HIPCHK(lead, hipMemcpyAsync(rows[(size_t)i].data(), (const uint8_t *)c->contour_edges.d + cvh_contour_rows_offset(c->contour_edges.count),
                                   row_room[(size_t)i] * sizeof(cvh_contour_loop), hipMemcpyDeviceToHost, lead->stream));
     }
     if (out.on_host && point_room[(size_t)i]) {
       pts[(size_t)i].resize(2 * point_room[(size_t)i]);
-      HIPCHK(lead, hipMemcpyAsync(pts[(size_t)i].data(), c->d_contour_points, point_room[(size_t)i] * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, lead->stream));
+      HIPCHK(lead, hipMemcpyAsync(pts[(size_t)i].data(), c->contour_points.d, point_room[(size_t)i] * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, lead->stream));
     }
   }
-  rc = close_call(ctxs, n, stream, !out.on_host && any_points);   // (the last read of the pinned block; the caller's stream waits for its points)
+  rc = call.wait_again(stream, !out.on_host && any_points);   // the SECOND host wait: counts and rows (the caller's stream waits for its points)
   if (rc != CVH_OK) return rc;
-  HIPCHK(lead, hipStreamSynchronize(lead->stream));   // the SECOND host wait: counts and rows
   for (int i = 0; i < n; ++i) {
     const size_t L = (size_t)words[4 * i + 1], P = (size_t)words[4 * i + 2];
     if (out.nloops) out.nloops[i] = (long)L;
@@ -178,7 +143,7 @@ int single(cvh_context *c, int conn, int invert, long min_area, long fill_holes,
   if (loop_cap < 0) return batch_fail(&c, 1, CVH_ERR_ARG, "%s: loop_cap must not be negative, got %ld", what, loop_cap);
   if (point_cap < 0) return batch_fail(&c, 1, CVH_ERR_ARG, "%s: point_cap must not be negative, got %ld", what, point_cap);
   const Outputs out = {&loops, &loop_cap, &points, &point_cap, nloops, npoints, on_host};
-  return contours(&c, 1, conn, invert, min_area, fill_holes, keep_largest, simplify, out, stream, what);
+  return contours(&c, 1, {conn, invert, min_area, fill_holes, keep_largest}, simplify, out, stream, what);
 }
 
 }  // namespace
@@ -189,7 +154,7 @@ extern "C" int cvh_contours_device_batch(cvh_context *const *ctxs, int n, int co
 {
   static const char what[] = "cvh_contours_device_batch";
   const Outputs out = {loops, loop_caps, d_points, point_caps, nloops, npoints, false};
-  return guarded(ctxs, n, what, [&]() { return contours(ctxs, n, conn, invert, min_area, fill_holes, keep_largest, simplify, out, stream, what); });
+  return guarded(ctxs, n, what, [&]() { return contours(ctxs, n, {conn, invert, min_area, fill_holes, keep_largest}, simplify, out, stream, what); });
 }
 
 extern "C" int cvh_contours_device(cvh_context *c, int conn, int invert, long min_area, long fill_holes, int keep_largest, int simplify,

@@ -1,5 +1,6 @@
 // csv_batch.hip — the fused batch: N contexts advance together, one launch per iteration and CSV-step instantiation (cvh_enqueue_steps_batch,
-// cvh_run_batch); and what every batch of contexts shares (member and pair checks, member predicates, errors, stream joins, device tables).
+// cvh_run_batch); and what every batch of contexts shares (member and pair checks, member predicates -- shapes, state, the capacities of
+// output arrays --, errors, stream joins, the grow-only device buffers: grow_table by bytes, grow_table_to by elements).
 #include "cvh_host.h"
 
 // The grid of a group is the concatenation of its members' own grids (nparts workgroups + the chain-mode bookkeeper), each padded to a
@@ -31,10 +32,21 @@ int grow_table(cvh_context *c, DeviceTable *t, size_t bytes)
   return CVH_OK;
 }
 
+// t holds at least `want` elements afterwards: where it has fewer it is allocated anew, `count` elements in `bytes` bytes -- the rule
+// that sizes both is the caller's (what it held is lost when it grows)
+int grow_table_to(cvh_context *c, DeviceTable *t, size_t want, size_t count, size_t bytes)
+{
+  if (t->count >= want) return CVH_OK;
+  free_table(t);
+  HIPCHK(c, hipMalloc(&t->d, bytes));
+  t->cap = bytes; t->count = count;
+  return CVH_OK;
+}
+
 void free_table(DeviceTable *t)
 {
   if (t->d) (void)hipFree(t->d);
-  t->d = nullptr; t->cap = 0;
+  t->d = nullptr; t->cap = t->count = 0;
 }
 
 void batch_cache_free(cvh_context *c)
@@ -93,6 +105,33 @@ int members_below(cvh_context *const *ctxs, int n, const char *what, int k, int 
       return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: member %d: %d x %d is too large, h * w must stay below 2^%d", what, i, ctxs[i]->h, ctxs[i]->w, k);
   return CVH_OK;
 }
+
+// squared distances are 32-bit integers, vertical distances 16-bit with one value set aside: cvh_reinit's passes and the calls that share them
+int members_distances_fit(cvh_context *const *ctxs, int n, const char *what, int only)
+{
+  for (int i = std::max(only, 0); i < (only < 0 ? n : only + 1); ++i) {
+    const cvh_context *c = ctxs[i];
+    if ((unsigned long long)c->h * c->h + (unsigned long long)c->w * c->w >= (1ull << 32))
+      return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: member %d: %d x %d is too large, h^2 + w^2 must stay below 2^32", what, i, c->h, c->w);
+  }
+  return CVH_OK;
+}
+
+// the capacities of the members' output arrays: where lists[i] is given (lists may be null, and so may an entry) there are caps --
+// `without` is the refusal otherwise -- and caps[i], which the refusal calls `noun`, is not negative
+template <class T>
+int members_caps_fit(cvh_context *const *ctxs, int n, const char *what, const void *const *lists, const T *caps, const char *noun, const char *without,
+                     int only)
+{
+  for (int i = std::max(only, 0); lists && i < (only < 0 ? n : only + 1); ++i) {
+    if (!lists[i]) continue;
+    if (!caps) return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: %s", what, without);
+    if (caps[i] < 0) return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: member %d: %s must not be negative, got %ld", what, i, noun, (long)caps[i]);
+  }
+  return CVH_OK;
+}
+template int members_caps_fit<int>(cvh_context *const *, int, const char *, const void *const *, const int *, const char *, const char *, int);
+template int members_caps_fit<long>(cvh_context *const *, int, const char *, const void *const *, const long *, const char *, const char *, int);
 
 int members_have_images(cvh_context *const *ctxs, int n, const char *what)
 {

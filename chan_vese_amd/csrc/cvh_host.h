@@ -1,9 +1,12 @@
 // cvh_host.h -- private header of the library's host units: the context, the launch geometries and the helpers more than one unit calls.
 // api.hip (lifecycle, options, host-buffer I/O, getters, the transitions of a context's run state), csv_run.hip (CSV steps of one
-// context), csv_batch.hip (fused batch, and what every batch shares: the member and pair checks, the member predicates), pm_run.hip
-// (Perona-Malik), io_run.hip (device-memory I/O, reinitialisation, and the scaffolds of the member-table calls: MemberCall, write_planes,
-// the launch counters), init_run.hip (device-side initial level sets), components_run.hip (connected components), pyramid_run.hip
-// (coarse-to-fine), colour_run.hip (colour spaces), energy_run.hip (the functional's terms), score_run.hip (mask scores), morph_run.hip (mask morphology, mask starts), measure_run.hip (component measures), contour_run.hip (contours), overlap_run.hip (component overlaps), debug_exports.hip (diagnostics).  Kernel sources do not include it.
+// context), csv_batch.hip (fused batch, and what every batch shares: the member and pair checks, the member predicates, the grow-only
+// device buffers), pm_run.hip (Perona-Malik), io_run.hip (device-memory I/O, reinitialisation, and the scaffolds of the member-table
+// calls: MemberCall with its further waits, write_planes, the pointer checks, the launch counters), init_run.hip (device-side initial
+// level sets), components_run.hip (connected components, and MaskSource: the raw or cleaned mask every mask-derived call starts from),
+// pyramid_run.hip (coarse-to-fine), colour_run.hip (colour spaces), energy_run.hip (the functional's terms), score_run.hip (mask scores),
+// morph_run.hip (mask morphology, mask starts), measure_run.hip (component measures), contour_run.hip (contours), overlap_run.hip
+// (component overlaps), debug_exports.hip (diagnostics).  Kernel sources do not include it.
 #pragma once
 #include <limits.h>
 #include <math.h>
@@ -21,8 +24,9 @@
 
 #include "cvh_internal.h"
 
-// a grow-only device buffer: the tables of the batches a context leads (grow_table, free_table)
-struct DeviceTable { void *d = nullptr; size_t cap = 0; };
+// a grow-only device buffer of cap bytes: the tables of the batches a context leads (grow_table), and the buffers whose owner counts in
+// elements -- rows, edges, points, slots -- and hands that count to its kernels (grow_table_to); free_table frees either
+struct DeviceTable { void *d = nullptr; size_t cap = 0, count = 0; };
 
 constexpr int kGraphSteps = 16;   // steps per captured graph (even: the ping-pong parity repeats)
 struct StepGraph { hipGraphExec_t exec = nullptr; CvhStepArgs key[4]; int kind = -1, flavour = -1; };
@@ -142,15 +146,11 @@ struct cvh_context {   // opaque to callers; four groups
   void *d_reinit = nullptr;      // workspace of cvh_reinit (class words + the two distance fields, reinit_kernels.hip): allocated by the
                                  // first call, idle while CSV streams -- not part of live_footprint
   void *d_cc = nullptr;          // workspace of cvh_components* / cvh_get_mask_clean* (components_kernels.hip), and the rows of the last
-  void *d_cc_table = nullptr;    // table: allocated by the first call that needs them, kept -- not part of live_footprint either
-  size_t cc_table_rows = 0;
-  void *d_regions = nullptr;     // the rows of this context's last cvh_measure* table (measure_run.hip): 128 bytes per row asked for, grown on demand, kept
-  size_t region_rows = 0;
+  DeviceTable cc_table;          // table: allocated by the first call that needs them, kept -- not part of live_footprint either
+  DeviceTable regions;           // the rows of this context's last cvh_measure* table (measure_run.hip): 128 bytes per row asked for, grown on demand, kept
   void *d_contour = nullptr;     // per-pixel workspace of cvh_contours* (contour_run.hip; 6 bytes per pixel): allocated by the first call, kept
-  void *d_contour_edges = nullptr;   // its per-edge workspace (45 bytes per edge of the largest call so far), grown on demand, kept
-  size_t contour_edge_cap = 0;
-  void *d_contour_points = nullptr;  // cvh_contours (host form): the points on their way down (8 bytes per point asked for), grown on demand, kept
-  size_t contour_point_cap = 0;
+  DeviceTable contour_edges;     // its per-edge workspace (45 bytes per edge of the largest call so far), grown on demand, kept
+  DeviceTable contour_points;    // cvh_contours (host form): the points on their way down (8 bytes per point asked for), grown on demand, kept
   unsigned *d_hist = nullptr;    // the 255 C + 1 counters of cvh_histogram* / cvh_otsu_threshold / cvh_init_otsu* (init_kernels.hip): allocated by
                                  // the first call, kept
   void *d_energy = nullptr;      // workspace of cvh_energy* (energy_run.hip): a CvhState for means taken beside the run's, then the item rows of
@@ -159,8 +159,8 @@ struct cvh_context {   // opaque to callers; four groups
                                  // host form stages (5.5 bytes per pixel): allocated by the first call, kept -- not part of live_footprint either
   void *d_morph = nullptr;       // workspace of cvh_get_mask_morph* / cvh_morph_levelset* / cvh_init_mask (morph_run.hip): two planes of band words, the
                                  // 16-bit distance field and a byte plane (3.25 bytes per pixel): allocated by the first call, kept -- not part of live_footprint either
-  void *d_overlap = nullptr;     // cvh_overlaps* (overlap_run.hip): overlap_slots slots of the pair table and overlap_slots / 2 rows behind them (24 bytes
-  size_t overlap_slots = 0;      // per slot), grown where a call's table overflows, kept; d_overlap_plane: the int32 plane the host form stages
+  DeviceTable overlap;           // cvh_overlaps* (overlap_run.hip): overlap.count slots of the pair table and overlap.count / 2 rows behind them (24 bytes
+                                 // per slot), grown where a call's table overflows, kept; d_overlap_plane: the int32 plane the host form stages
   void *d_overlap_plane = nullptr;   // (4 bytes per pixel) -- allocated by the first call that needs them, not part of live_footprint either
   int coop_launch = -1;          // does the device launch cooperatively (-1: not asked yet; launches_cooperatively)
   int resident_cap = -1;         // workgroups of csv_resident_kernel the device holds at once (-1: not asked yet, 0: unavailable)
@@ -245,6 +245,10 @@ int batch_fail(cvh_context *const *ctxs, int n, int code, const char *fmt, ...);
 enum MemberNeeds { kMembersListed, kMembersWithImage, kMembersForCsv };
 int members_check(cvh_context *const *ctxs, int n, const char *what, MemberNeeds needs);
 int members_below(cvh_context *const *ctxs, int n, const char *what, int k, int only = -1);
+int members_distances_fit(cvh_context *const *ctxs, int n, const char *what, int only = -1);
+template <class T>   // int or long
+int members_caps_fit(cvh_context *const *ctxs, int n, const char *what, const void *const *lists, const T *caps, const char *noun, const char *without,
+                     int only = -1);
 int members_have_images(cvh_context *const *ctxs, int n, const char *what);
 int members_have_levelsets(cvh_context *const *ctxs, int n, const char *what, int only = -1);
 int members_mirrors_fresh(cvh_context *const *ctxs, int n, const char *what, int first = 0, const char *noun = "member");
@@ -255,6 +259,7 @@ int pairs_check(const PairRoles &p, int n, const char *what, std::vector<cvh_con
 int pair_sources_have_images(cvh_context *const *all, int n, const char *what, const char *role);
 int join_into_leader(cvh_context *const *ctxs, int n, const int *member = nullptr);
 int grow_table(cvh_context *c, DeviceTable *t, size_t bytes);
+int grow_table_to(cvh_context *c, DeviceTable *t, size_t want, size_t count, size_t bytes);
 void free_table(DeviceTable *t);
 
 // io_run.hip: launches so far in this process (debug_exports.hip): the launch sets (three kernels for all members) of cvh_reinit*, the
@@ -267,6 +272,7 @@ extern std::atomic<unsigned long> g_launches[kLaunchCounters];
 
 // io_run.hip: what every call on device memory or on a member table shares (the comments are at the definitions)
 int pointer_check(cvh_context *const *ctxs, int n, int i, const void *p, const char *what);
+int element_pointer_check(cvh_context *const *ctxs, int n, int i, const void *p, size_t size, const char *what);
 int settle_all(cvh_context *const *ctxs, int n, const char *what);
 int open_call(cvh_context *const *ctxs, int n, void *stream);
 int close_call(cvh_context *const *ctxs, int n, void *stream, bool to_caller);
@@ -276,13 +282,29 @@ void checkerboard_factors(int h, int w, double *out);   // api.hip: out[0 .. h-1
 void levelset_target(const cvh_context *c, CvhIoMember *m);
 int ensure_workspace(cvh_context *c, void **slot, size_t bytes, const char *name, bool mirror = true);
 
-// components_run.hip: what measure_run.hip shares with the components calls -- cvh_get_mask_clean*'s argument checks; every member has
-// a level set, is settled and has its workspace; the member table of the components launches (with two_tables the second table is the
-// caller's, and `more` bytes of the device extra behind the members' words are the caller's too) -- overlap_run.hip shares them as well
+// components_run.hip: the mask of every member that a call starts from -- raw, or cleaned as cvh_get_mask_clean* cleans it -- for the
+// components calls there and for measure_run.hip, overlap_run.hip, contour_run.hip and morph_run.hip.  The first member table of such a
+// call is the mask launches': the level set in src, the mask bytes in dst, the components workspace in plane[], a word per member in sums.
+// need_cc: the caller's own launches take the components workspace even for a raw mask (the numbering launch of measure and overlap).
 struct MemberCall;
-int cc_clean_args(cvh_context *const *ctxs, int n, int conn, long min_area, long fill_holes, int keep_largest, const char *what);
-int cc_members_ready(cvh_context *const *ctxs, int n, const char *what);
-int cc_fill_members(MemberCall *call, cvh_context *const *ctxs, int n, void *const *dst, const char *what, bool two_tables, size_t more = 0);
+struct MaskSource {
+  int conn = 4, invert = 0;
+  long min_area = 0, fill_holes = 0;
+  int keep_largest = 0;
+
+  bool drop() const { return min_area > 1; }   // (every component has a pixel)
+  bool cleaned() const { return drop() || fill_holes || keep_largest; }
+  // the member list and cvh_get_mask_clean*'s argument checks
+  int check(cvh_context *const *ctxs, int n, const char *what) const;
+  // every member has a level set and is settled; with need_cc or a cleaned mask it has its components workspace and a plane the 31-bit
+  // indices cover, else a fresh FP64 mirror alone
+  int ready(cvh_context *const *ctxs, int n, const char *what, bool need_cc) const;
+  // member i's entry of the call's first table: dst and the device address of its word are the caller's
+  void fill(MemberCall *call, int i, void *dst, unsigned long long *sums, bool need_cc) const;
+  // the mask launches on the leader's stream: a cleaned mask's (the plain mask first where step 1, the drop, is off); of a raw mask
+  // the plain mask with raw_too, nothing without (the caller's own launches read the level set)
+  int launch(const MemberCall &call, bool raw_too) const;
+};
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) & ~(a - 1); }
 
@@ -306,6 +328,10 @@ struct MemberCall {
   const CvhIoMember *dtab2() const { return (const CvhIoMember *)(db + ((unsigned char *)tab2 - hb)); }
   // the members begin the run their new level set opens (all, or those with which[i] != 0): the launch did the device's half
   int arrived(const int *which = nullptr) const;
+  // a call with a further host wait: t (tab or tab2), which the caller has written again behind run(), goes up again; then, behind the
+  // launches and copies the caller enqueues, what run() does behind its own
+  int upload_again(const CvhIoMember *t) const;
+  int wait_again(void *stream, bool to_caller) const;
 
   // The sections are laid out; the leader's stream is joined with the members' and the caller's; `first` (if any) is recorded; the
   // device image goes up; launches() enqueues the kernels and what they copy back on the leader's stream; the members' streams, and

@@ -3,7 +3,7 @@
 // The single-context calls are batches of one member: one code path.  Reinitialisation (cvh_reinit, cvh_reinit_batch) lives here too: it
 // is a level set leaving and arriving without crossing to the host, on the same member tables and stream joins.  MemberCall (cvh_host.h)
 // is the scaffold of every member-table call, here and in init_run.hip, components_run.hip, pyramid_run.hip and colour_run.hip: staging,
-// the level-set target, the joined launch, the members' arrival.  write_planes is the one path of the calls that replace planes -- the
+// the level-set target, the joined launch, the members' arrival, a further host wait (upload_again, wait_again).  write_planes is the one path of the calls that replace planes -- the
 // ingest here, the conversions and the luma of colour_run.hip, the restrict of pyramid_run.hip -- and g_launches the one table of launch
 // counters.  What a call refuses for its members or pairs is in csv_batch.hip.  cvh_init_checkerboard is a checkerboard batch of one.
 #include <memory>
@@ -24,6 +24,15 @@ int pointer_check(cvh_context *const *ctxs, int n, int i, const void *p, const c
   const bool ok = e == hipSuccess && ((at.type == hipMemoryTypeDevice && at.device == ctxs[i]->device) || at.type == hipMemoryTypeManaged ||
                                       (at.type == hipMemoryTypeHost && at.devicePointer != nullptr));
   if (!ok) return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: member %d: %p is not device-accessible memory of device %d", what, i, p, ctxs[i]->device);
+  return CVH_OK;
+}
+
+// pointer_check for an array of elements of `size` bytes, to which p must be aligned
+int element_pointer_check(cvh_context *const *ctxs, int n, int i, const void *p, size_t size, const char *what)
+{
+  const int rc = pointer_check(ctxs, n, i, p, what);
+  if (rc != CVH_OK) return rc;
+  if ((uintptr_t)p % size) return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: member %d: %p is not aligned to %zu bytes", what, i, p, size);
   return CVH_OK;
 }
 
@@ -106,6 +115,21 @@ int MemberCall::arrived(const int *which) const
     const int rc = levelset_arrived(ctxs[i], true);
     if (rc != CVH_OK) return batch_fail(ctxs, n, rc, "%s: member %d: %s", what, i, ctxs[i]->err);
   }
+  return CVH_OK;
+}
+
+int MemberCall::upload_again(const CvhIoMember *t) const
+{
+  HIPCHK(lead, hipMemcpyAsync(db + ((const unsigned char *)t - hb), t, (size_t)n * sizeof(CvhIoMember), hipMemcpyHostToDevice, lead->stream));
+  return CVH_OK;
+}
+
+// (the event is also the last read of the pinned block; the members' streams wait for the launches on their buffers)
+int MemberCall::wait_again(void *stream, bool to_caller) const
+{
+  const int rc = close_call(ctxs, n, stream, to_caller);
+  if (rc != CVH_OK) return rc;
+  HIPCHK(lead, hipStreamSynchronize(lead->stream));
   return CVH_OK;
 }
 
@@ -427,13 +451,10 @@ static int reinit_batch(cvh_context *const *ctxs, int n, int *changed, const cha
 {
   int rc = members_check(ctxs, n, what, kMembersListed);
   if (rc != CVH_OK) return rc;
-  for (int i = 0; i < n; ++i) {
-    const cvh_context *c = ctxs[i];
+  for (int i = 0; i < n; ++i) {   // (member by member: a member without a level set before a later one that is too large)
     rc = members_have_levelsets(ctxs, n, what, i);
+    if (rc == CVH_OK) rc = members_distances_fit(ctxs, n, what, i);
     if (rc != CVH_OK) return rc;
-    // squared distances are 32-bit integers, vertical distances 16-bit with one value set aside
-    if ((unsigned long long)c->h * c->h + (unsigned long long)c->w * c->w >= (1ull << 32))
-      return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: member %d: %d x %d is too large, h^2 + w^2 must stay below 2^32", what, i, c->h, c->w);
   }
   cvh_context *lead = ctxs[0];
   HIPCHK(lead, hipSetDevice(lead->device));

@@ -1,43 +1,41 @@
 // measure_run.hip — host side of cvh_measure* (include/chanvese_hip.h, "Component measures"): the components of the masks of n contexts,
-// raw or cleaned, measured on the device -- ONE MemberCall (cvh_host.h, io_run.hip) with two member tables: the components calls' own
-// (components_run.hip; the workspace in plane[]) for the cleaning and numbering launches, and a second one (the image in plane[]) for
-// measure_kernels.hip.  The single-context form is a batch of one.  The calls only read: nothing of a member's level set, run state,
+// raw or cleaned, measured on the device -- ONE MemberCall (cvh_host.h, io_run.hip) with two member tables: the mask source's
+// (MaskSource, components_run.hip; the workspace in plane[]) for the cleaning and numbering launches, and a second one (the image in
+// plane[]) for measure_kernels.hip.  The single-context form is a batch of one.  The calls only read: nothing of a member's level set, run state,
 // sums, options or planes is assigned here.  cvh_region_shape_of, the host arithmetic on a row, lives here too.
 #include "cvh_host.h"
 
 namespace {
 
-int measure(cvh_context *const *ctxs, int n, int conn, int invert, long min_area, long fill_holes, int keep_largest,
-            cvh_region *const *tables, const int *caps, int *counts, void *stream, const char *what)
+int measure(cvh_context *const *ctxs, int n, const MaskSource &src, cvh_region *const *tables, const int *caps, int *counts, void *stream,
+            const char *what)
 {
-  int rc = cc_clean_args(ctxs, n, conn, min_area, fill_holes, keep_largest, what);
+  int rc = src.check(ctxs, n, what);
+  if (rc == CVH_OK) rc = members_caps_fit(ctxs, n, what, (const void *const *)tables, caps, "cap", "tables without caps");
   if (rc != CVH_OK) return rc;
-  for (int i = 0; tables && i < n; ++i) {
-    if (!tables[i]) continue;   // (no rows for this member)
-    if (!caps) return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: tables without caps", what);
-    if (caps[i] < 0) return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: member %d: cap must not be negative, got %d", what, i, caps[i]);
-  }
   for (int i = 0; i < n; ++i)   // (with h w < 2^31 this keeps every sum below 2^63)
     if (ctxs[i]->h > 65535 || ctxs[i]->w > 65535)
       return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: member %d: %d x %d is too large, h and w must stay below 65536", what, i, ctxs[i]->h, ctxs[i]->w);
   rc = members_below(ctxs, n, what, 31);
   if (rc == CVH_OK) rc = members_have_images(ctxs, n, what);
-  if (rc == CVH_OK) rc = cc_members_ready(ctxs, n, what);
+  if (rc == CVH_OK) rc = src.ready(ctxs, n, what, true);
   if (rc != CVH_OK) return rc;
   cvh_context *lead = ctxs[0];
-  const bool drop = min_area > 1, cleaned = drop || fill_holes || keep_largest;
+  const bool cleaned = src.cleaned();
   std::vector<void *> masks((size_t)n, nullptr);
   for (int i = 0; cleaned && i < n; ++i) {   // the cleaned mask goes to the context's own mask buffer (cvh_get_mask's) and is labelled there
     cvh_context *c = ctxs[i];
     if (!c->d_mask) HIPCHK(lead, hipMalloc((void **)&c->d_mask, c->n));
     masks[(size_t)i] = c->d_mask;
   }
+  // staging: [the mask launches' table][the measure launches' table][one word per member, zero]
   MemberCall call;
-  rc = cc_fill_members(&call, ctxs, n, masks.data(), what, true);
+  rc = call.begin(ctxs, n, what, (size_t)n * sizeof(unsigned long long), 0, true);
   if (rc != CVH_OK) return rc;
   bool any_c1 = false, any_c3 = false;
   for (int i = 0; i < n; ++i) {
     const cvh_context *c = ctxs[i];
+    src.fill(&call, i, masks[(size_t)i], (unsigned long long *)(call.db + call.extra_off) + i, true);
     CvhIoMember &m = call.tab2[i];
     m.src = c->d_cc;
     for (int k = 0; k < c->C; ++k) m.plane[k] = c->d_img[k];
@@ -46,12 +44,9 @@ int measure(cvh_context *const *ctxs, int n, int conn, int invert, long min_area
   }
   const unsigned long long *words = (const unsigned long long *)(call.hb + call.extra_off);
   rc = call.run(stream, false, true, [&]() -> int {   // the first host wait of the call: the counts
-    if (cleaned) {
-      if (!drop) HIPCHK(lead, cvh_launch_io_mask(call.dtab(), n, call.grid, invert, lead->stream));   // step 1 is off: the plain mask
-      const unsigned a = (unsigned)std::min<long>(min_area, 0x7fffffffl);
-      HIPCHK(lead, cvh_launch_cc_clean(call.dtab(), n, call.grid, conn, invert, a, fill_holes, keep_largest, lead->stream));
-    }   // (keep_largest has used the members' words for its bids: the scan of the numbering stores K over them)
-    HIPCHK(lead, cvh_launch_cc_number(call.dtab(), n, call.grid, cleaned ? 1 : 0, conn, invert, lead->stream));
+    const int rc_mask = src.launch(call, false);   // (keep_largest has used the members' words for its bids: the scan of the numbering stores K over them)
+    if (rc_mask != CVH_OK) return rc_mask;
+    HIPCHK(lead, cvh_launch_cc_number(call.dtab(), n, call.grid, cleaned ? 1 : 0, src.conn, src.invert, lead->stream));
     HIPCHK(lead, hipMemcpyAsync((void *)words, call.db + call.extra_off, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost, lead->stream));
     return CVH_OK;
   });
@@ -63,26 +58,20 @@ int measure(cvh_context *const *ctxs, int n, int conn, int invert, long min_area
     cvh_context *c = ctxs[i];
     const size_t rows = std::min<size_t>((size_t)words[i], tables && tables[i] ? (size_t)caps[i] : 0);
     if (!rows) continue;
-    if (c->region_rows < rows) {
-      if (c->d_regions) { HIPCHK(lead, hipFree(c->d_regions)); c->d_regions = nullptr; c->region_rows = 0; }
-      const size_t want = rows + rows / 4;
-      HIPCHK(lead, hipMalloc(&c->d_regions, want * sizeof(cvh_region)));
-      c->region_rows = want;
-    }
-    call.tab2[i].dst = c->d_regions;
+    rc = grow_table_to(lead, &c->regions, rows, rows + rows / 4, (rows + rows / 4) * sizeof(cvh_region));
+    if (rc != CVH_OK) return rc;
+    call.tab2[i].dst = c->regions.d;
     call.tab2[i].h2 = (int)rows;
     any_rows = true;
   }
   if (!any_rows) return CVH_OK;
-  HIPCHK(lead, hipMemcpyAsync((void *)call.dtab2(), call.tab2, (size_t)n * sizeof(CvhIoMember), hipMemcpyHostToDevice, lead->stream));
+  rc = call.upload_again(call.tab2);
+  if (rc != CVH_OK) return rc;
   HIPCHK(lead, cvh_launch_measure(call.dtab2(), n, call.grid2, any_c1, any_c3, lead->stream));
   for (int i = 0; i < n; ++i)
     if (call.tab2[i].h2)
-      HIPCHK(lead, hipMemcpyAsync(tables[i], ctxs[i]->d_regions, (size_t)call.tab2[i].h2 * sizeof(cvh_region), hipMemcpyDeviceToHost, lead->stream));
-  rc = close_call(ctxs, n, stream, false);   // (the last read of the pinned block; the members' streams wait for the launches on their buffers)
-  if (rc != CVH_OK) return rc;
-  HIPCHK(lead, hipStreamSynchronize(lead->stream));
-  return CVH_OK;
+      HIPCHK(lead, hipMemcpyAsync(tables[i], ctxs[i]->regions.d, (size_t)call.tab2[i].h2 * sizeof(cvh_region), hipMemcpyDeviceToHost, lead->stream));
+  return call.wait_again(stream, false);
 }
 
 // v as a double, rounded to nearest even ONCE (what Python's float(int) gives)
@@ -109,7 +98,7 @@ extern "C" int cvh_measure_batch(cvh_context *const *ctxs, int n, int conn, int 
                                  cvh_region *const *tables, const int *caps, int *counts, void *stream)
 {
   static const char what[] = "cvh_measure_batch";
-  return guarded(ctxs, n, what, [&]() { return measure(ctxs, n, conn, invert, min_area, fill_holes, keep_largest, tables, caps, counts, stream, what); });
+  return guarded(ctxs, n, what, [&]() { return measure(ctxs, n, {conn, invert, min_area, fill_holes, keep_largest}, tables, caps, counts, stream, what); });
 }
 
 extern "C" int cvh_measure(cvh_context *c, int conn, int invert, long min_area, long fill_holes, int keep_largest, cvh_region *table, int cap,
@@ -117,7 +106,7 @@ extern "C" int cvh_measure(cvh_context *c, int conn, int invert, long min_area, 
 {
   return guarded_one(c, "cvh_measure", [&](const char *what) {
     if (table && cap < 0) return batch_fail(&c, 1, CVH_ERR_ARG, "%s: cap must not be negative, got %d", what, cap);
-    return measure(&c, 1, conn, invert, min_area, fill_holes, keep_largest, &table, &cap, count, stream, what);
+    return measure(&c, 1, {conn, invert, min_area, fill_holes, keep_largest}, &table, &cap, count, stream, what);
   });
 }
 

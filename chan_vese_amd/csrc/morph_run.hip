@@ -1,7 +1,7 @@
 // morph_run.hip — host side of the mask morphology and the mask starts (include/chanvese_hip.h, "Mask morphology"): the cleaned mask of n
 // contexts dilated, eroded, opened or closed by a disk, as 0/1 bytes for the caller or baked into the members' level sets, and byte masks
 // the caller holds as level sets.  Each call is ONE MemberCall (cvh_host.h, io_run.hip: member tables, stream joins, event ordering against
-// the caller's stream) around morph_kernels.hip's launches and, where the call cleans, the launches of cvh_get_mask_clean; the single forms
+// the caller's stream) around morph_kernels.hip's launches and, where the call cleans, the mask source's (MaskSource, components_run.hip); the single forms
 // are batches of one member (guarded_one), and the host forms move their bytes on the context's stream and are then the device forms on
 // that stream.  The byte-mask calls only read; a level-set write ends as the cvh_init_* calls do (MemberCall::arrived).
 #include "cvh_host.h"
@@ -47,31 +47,21 @@ struct Staged {
   }
 };
 
-int morph(cvh_context *const *ctxs, int n, uint8_t *const *d_masks, int conn, int invert, long min_area, long fill_holes, int keep_largest, int op,
-          const uint32_t *r2, const Levelset &ls, void *stream, const char *what)
+int morph(cvh_context *const *ctxs, int n, uint8_t *const *d_masks, const MaskSource &src, int op, const uint32_t *r2, const Levelset &ls,
+          void *stream, const char *what)
 {
-  int rc = cc_clean_args(ctxs, n, conn, min_area, fill_holes, keep_largest, what);
+  int rc = src.check(ctxs, n, what);
   if (rc != CVH_OK) return rc;
   if (op < CVH_MORPH_NONE || op > CVH_MORPH_CLOSE)
     return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: op must be CVH_MORPH_NONE (0) .. CVH_MORPH_CLOSE (4), got %d", what, op);
   if (!r2) return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: the list of squared radii is NULL", what);
   if (!ls.write && !d_masks) return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: the list of device pointers is NULL", what);
-  for (int i = 0; i < n; ++i) {
-    const cvh_context *c = ctxs[i];
-    // vertical distances are 16-bit with one value set aside, squared distances 32-bit (as cvh_reinit)
-    if ((unsigned long long)c->h * c->h + (unsigned long long)c->w * c->w >= (1ull << 32))
-      return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: member %d: %d x %d is too large, h^2 + w^2 must stay below 2^32", what, i, c->h, c->w);
-  }
+  rc = members_distances_fit(ctxs, n, what);
+  if (rc != CVH_OK) return rc;
   cvh_context *lead = ctxs[0];
   HIPCHK(lead, hipSetDevice(lead->device));
   for (int i = 0; !ls.write && i < n; ++i) { rc = pointer_check(ctxs, n, i, d_masks[i], what); if (rc != CVH_OK) return rc; }
-  const bool drop = min_area > 1, cleaned = drop || fill_holes || keep_largest;
-  if (cleaned) rc = cc_members_ready(ctxs, n, what);
-  else {
-    rc = members_have_levelsets(ctxs, n, what);
-    if (rc == CVH_OK) rc = settle_all(ctxs, n, what);
-    if (rc == CVH_OK) rc = members_mirrors_fresh(ctxs, n, what);
-  }
+  rc = src.ready(ctxs, n, what, false);
   if (rc != CVH_OK) return rc;
   for (int i = 0; i < n; ++i) {
     cvh_context *c = ctxs[i];
@@ -88,18 +78,9 @@ int morph(cvh_context *const *ctxs, int n, uint8_t *const *d_masks, int conn, in
   for (int i = 0; i < n; ++i) {
     const cvh_context *c = ctxs[i];
     uint8_t *const base = (uint8_t *)c->d_morph, *const bytes = base + cvh_morph_bytes_offset(c->h, c->w);
-    CvhIoMember &m = call.tab[i];   // the mask launches
-    m.src = c->d_u[current_buffer(c)];
-    m.dst = bytes;
-    if (cleaned) {
-      m.plane[0] = (uint8_t *)c->d_cc;
-      m.plane[1] = m.plane[0] + c->n * sizeof(unsigned);
-      m.plane[2] = m.plane[1] + c->n * sizeof(unsigned);
-    }
-    m.sums = st.d_words + i;
-    m.nblk = cvh_cc_blocks(c->n);
+    src.fill(&call, i, bytes, st.d_words + i, false);   // the mask launches
     CvhIoMember &t = call.tab2[i];   // the column launches
-    t.src = m.src;
+    t.src = call.tab[i].src;
     t.src2 = bytes;
     t.plane[0] = base;
     t.plane[1] = base + cvh_score_words_bytes(c->h, c->w);
@@ -115,12 +96,9 @@ int morph(cvh_context *const *ctxs, int n, uint8_t *const *d_masks, int conn, in
   // a byte mask goes to the caller's stream without a host wait, as cvh_get_mask_clean_device; a level set arrives behind ONE wait, as
   // cvh_init_rect
   rc = call.run(stream, !ls.write, ls.write, [&]() -> int {
-    if (cleaned) {
-      if (!drop) HIPCHK(lead, cvh_launch_io_mask(call.dtab(), n, call.grid, invert, lead->stream));   // the plain mask (step 1 of the cleaning is off)
-      const unsigned a = (unsigned)std::min<long>(min_area, 0x7fffffffl);
-      HIPCHK(lead, cvh_launch_cc_clean(call.dtab(), n, call.grid, conn, invert, a, fill_holes, keep_largest, lead->stream));
-    }
-    HIPCHK(lead, cvh_launch_morph_bits(call.dtab2(), n, call.grid2, !cleaned, invert, lead->stream));
+    const int rc_mask = src.launch(call, false);   // (of a raw mask nothing: the bits launch reads the level sets)
+    if (rc_mask != CVH_OK) return rc_mask;
+    HIPCHK(lead, cvh_launch_morph_bits(call.dtab2(), n, call.grid2, !src.cleaned(), src.invert, lead->stream));
     HIPCHK(lead, cvh_launch_morph_passes(call.dtab2(), st.d_par, n, call.grid2, npass, kPasses[op], lead->stream));
     HIPCHK(lead, cvh_launch_morph_emit(st.d_emit, st.d_par, n, st.emit_grid, false, ls.write, lead->stream));
     ++g_launches[kMorphLaunchSets];
@@ -165,14 +143,16 @@ extern "C" int cvh_get_mask_morph_device_batch(cvh_context *const *ctxs, int n, 
                                                long fill_holes, int keep_largest, int op, const uint32_t *r2, void *stream)
 {
   static const char what[] = "cvh_get_mask_morph_device_batch";
-  return guarded(ctxs, n, what, [&]() { return morph(ctxs, n, d_masks, conn, invert, min_area, fill_holes, keep_largest, op, r2, {false, 0.0, 0.0}, stream, what); });
+  return guarded(ctxs, n, what, [&]() {
+    return morph(ctxs, n, d_masks, {conn, invert, min_area, fill_holes, keep_largest}, op, r2, {false, 0.0, 0.0}, stream, what);
+  });
 }
 
 extern "C" int cvh_get_mask_morph_device(cvh_context *c, uint8_t *d_mask, int conn, int invert, long min_area, long fill_holes, int keep_largest,
                                          int op, uint32_t r2, void *stream)
 {
   return guarded_one(c, "cvh_get_mask_morph_device", [&](const char *what) {
-    return morph(&c, 1, &d_mask, conn, invert, min_area, fill_holes, keep_largest, op, &r2, {false, 0.0, 0.0}, stream, what);
+    return morph(&c, 1, &d_mask, {conn, invert, min_area, fill_holes, keep_largest}, op, &r2, {false, 0.0, 0.0}, stream, what);
   });
 }
 
@@ -182,7 +162,7 @@ extern "C" int cvh_get_mask_morph(cvh_context *c, uint8_t *mask, int conn, int i
   return guarded_one(c, "cvh_get_mask_morph", [&](const char *what) {
     if (!mask) return batch_fail(&c, 1, CVH_ERR_ARG, "%s: mask is NULL", what);
     return mask_to_host(c, mask, [&]() {
-      return morph(&c, 1, &c->d_mask, conn, invert, min_area, fill_holes, keep_largest, op, &r2, {false, 0.0, 0.0}, c->stream, what);
+      return morph(&c, 1, &c->d_mask, {conn, invert, min_area, fill_holes, keep_largest}, op, &r2, {false, 0.0, 0.0}, c->stream, what);
     });
   });
 }
@@ -191,14 +171,16 @@ extern "C" int cvh_morph_levelset_batch(cvh_context *const *ctxs, int n, int con
                                         int op, const uint32_t *r2, double inside, double outside)
 {
   static const char what[] = "cvh_morph_levelset_batch";
-  return guarded(ctxs, n, what, [&]() { return morph(ctxs, n, nullptr, conn, invert, min_area, fill_holes, keep_largest, op, r2, {true, inside, outside}, nullptr, what); });
+  return guarded(ctxs, n, what, [&]() {
+    return morph(ctxs, n, nullptr, {conn, invert, min_area, fill_holes, keep_largest}, op, r2, {true, inside, outside}, nullptr, what);
+  });
 }
 
 extern "C" int cvh_morph_levelset(cvh_context *c, int conn, int invert, long min_area, long fill_holes, int keep_largest, int op, uint32_t r2,
                                   double inside, double outside)
 {
   return guarded_one(c, "cvh_morph_levelset", [&](const char *what) {
-    return morph(&c, 1, nullptr, conn, invert, min_area, fill_holes, keep_largest, op, &r2, {true, inside, outside}, nullptr, what);
+    return morph(&c, 1, nullptr, {conn, invert, min_area, fill_holes, keep_largest}, op, &r2, {true, inside, outside}, nullptr, what);
   });
 }
 

@@ -1,8 +1,8 @@
 // overlap_run.hip — host side of cvh_overlaps* (include/chanvese_hip.h, "Component overlaps"): the contingency table of the components of
 // the masks of n contexts, raw or cleaned, against a second label plane each -- ONE MemberCall (cvh_host.h, io_run.hip) with two member
-// tables, as measure_run.hip: the components calls' own (components_run.hip) for the cleaning and numbering launches, and a second one
+// tables, as measure_run.hip: the mask source's (MaskSource, components_run.hip) for the cleaning and numbering launches, and a second one
 // for overlap_kernels.hip.  The single-context forms are batches of one; the host form stages its plane on the context's stream and is
-// then the device form on that stream.  The pair table of a member lives in the context (d_overlap) and keeps the size it has grown to:
+// then the device form on that stream.  The pair table of a member lives in the context (overlap) and keeps the size it has grown to:
 // a launch whose table overflows is run again, for the members concerned, on a table four times as large.  The rows come down in slot
 // order and are SORTED HERE, behind the wait for them.  The calls only read: nothing of a member's level set, run state, sums, options
 // or planes is assigned here.  cvh_match_overlaps, the host arithmetic on a table, lives here too.
@@ -21,41 +21,32 @@ size_t max_slots(size_t n)
   return s;
 }
 
+// c's table has `slots` slots, and half as many rows behind them, afterwards
 int set_slots(cvh_context *lead, cvh_context *c, size_t slots)
 {
-  if (c->d_overlap) { HIPCHK(lead, hipFree(c->d_overlap)); c->d_overlap = nullptr; c->overlap_slots = 0; }
-  HIPCHK(lead, hipMalloc(&c->d_overlap, slots * kSlotBytes + slots / 2 * kRowBytes));
-  c->overlap_slots = slots;
-  return CVH_OK;
+  return grow_table_to(lead, &c->overlap, slots, slots, slots * kSlotBytes + slots / 2 * kRowBytes);
 }
 
 bool row_less(const cvh_overlap &x, const cvh_overlap &y) { return x.a != y.a ? x.a < y.a : x.b < y.b; }
 
-int overlaps(cvh_context *const *ctxs, int n, int conn, int invert, long min_area, long fill_holes, int keep_largest,
-             const int32_t *const *d_others, cvh_overlap *const *tables, const long *caps, long *pairs, int *counts, void *stream,
-             const char *what)
+int overlaps(cvh_context *const *ctxs, int n, const MaskSource &src, const int32_t *const *d_others, cvh_overlap *const *tables, const long *caps,
+             long *pairs, int *counts, void *stream, const char *what)
 {
-  int rc = cc_clean_args(ctxs, n, conn, min_area, fill_holes, keep_largest, what);
+  int rc = src.check(ctxs, n, what);
   if (rc != CVH_OK) return rc;
   if (!d_others) return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: the list of device pointers is NULL", what);
-  for (int i = 0; tables && i < n; ++i) {
-    if (!tables[i]) continue;   // (no rows for this member)
-    if (!caps) return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: tables without caps", what);
-    if (caps[i] < 0) return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: member %d: cap must not be negative, got %ld", what, i, caps[i]);
-  }
-  rc = members_below(ctxs, n, what, 31);   // (a count fits 32 bits)
+  rc = members_caps_fit(ctxs, n, what, (const void *const *)tables, caps, "cap", "tables without caps");
+  if (rc == CVH_OK) rc = members_below(ctxs, n, what, 31);   // (a count fits 32 bits)
   if (rc != CVH_OK) return rc;
   cvh_context *lead = ctxs[0];
   HIPCHK(lead, hipSetDevice(lead->device));
   for (int i = 0; i < n; ++i) {
-    rc = pointer_check(ctxs, n, i, d_others[i], what);
+    rc = element_pointer_check(ctxs, n, i, d_others[i], sizeof(int32_t), what);
     if (rc != CVH_OK) return rc;
-    if ((uintptr_t)d_others[i] % sizeof(int32_t))
-      return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: member %d: %p is not aligned to 4 bytes", what, i, (const void *)d_others[i]);
   }
-  rc = cc_members_ready(ctxs, n, what);
+  rc = src.ready(ctxs, n, what, true);
   if (rc != CVH_OK) return rc;
-  const bool drop = min_area > 1, cleaned = drop || fill_holes || keep_largest;
+  const bool cleaned = src.cleaned();
   std::vector<void *> masks((size_t)n, nullptr);
   std::vector<size_t> want_rows((size_t)n, 0);   // rows the caller has room for
   bool any_rows = false;
@@ -65,13 +56,14 @@ int overlaps(cvh_context *const *ctxs, int n, int conn, int invert, long min_are
       if (!c->d_mask) HIPCHK(lead, hipMalloc((void **)&c->d_mask, c->n));
       masks[(size_t)i] = c->d_mask;
     }
-    if (!c->d_overlap) { rc = set_slots(lead, c, kFirstSlots); if (rc != CVH_OK) return rc; }
+    rc = set_slots(lead, c, kFirstSlots);   // (the first call's: a table that exists has at least as many)
+    if (rc != CVH_OK) return rc;
     if (tables && tables[i] && caps[i] > 0) { want_rows[(size_t)i] = (size_t)caps[i]; any_rows = true; }
   }
-  // staging: the components calls' two tables and words, then CVH_OVERLAP_CTL control words per member, zero
+  // staging: [the mask launches' table][the pair launches' table][one word per member][CVH_OVERLAP_CTL control words per member], zero
   const size_t word_bytes = (size_t)n * sizeof(unsigned long long), ctl_bytes = (size_t)n * CVH_OVERLAP_CTL * sizeof(unsigned);
   MemberCall call;
-  rc = cc_fill_members(&call, ctxs, n, masks.data(), what, true, ctl_bytes);
+  rc = call.begin(ctxs, n, what, word_bytes + ctl_bytes, 0, true);
   if (rc != CVH_OK) return rc;
   unsigned char *const d_ctl = call.db + call.extra_off + word_bytes;
   const unsigned long long *words = (const unsigned long long *)(call.hb + call.extra_off);
@@ -79,12 +71,13 @@ int overlaps(cvh_context *const *ctxs, int n, int conn, int invert, long min_are
   auto point_at_table = [&](int i) {
     const cvh_context *c = ctxs[i];
     CvhIoMember &m = call.tab2[i];
-    m.dst = c->d_overlap;
-    m.plane[0] = (uint8_t *)c->d_overlap + c->overlap_slots * kSlotBytes;
-    m.src_stride = c->overlap_slots;
+    m.dst = c->overlap.d;
+    m.plane[0] = (uint8_t *)c->overlap.d + c->overlap.count * kSlotBytes;
+    m.src_stride = c->overlap.count;
   };
   for (int i = 0; i < n; ++i) {
     const cvh_context *c = ctxs[i];
+    src.fill(&call, i, masks[(size_t)i], (unsigned long long *)(call.db + call.extra_off) + i, true);
     CvhIoMember &m = call.tab2[i];
     m.src = c->d_cc;
     m.src2 = d_others[i];
@@ -96,19 +89,16 @@ int overlaps(cvh_context *const *ctxs, int n, int conn, int invert, long min_are
   // the pair launch for the members that do not sit out, and what it leaves: K, and per member {P, overflow, rows written}
   auto pair_launch = [&]() -> int {
     for (int i = 0; i < n; ++i)
-      if (!call.tab2[i].h2) HIPCHK(lead, hipMemsetAsync(ctxs[i]->d_overlap, 0, ctxs[i]->overlap_slots * kSlotBytes, lead->stream));
+      if (!call.tab2[i].h2) HIPCHK(lead, hipMemsetAsync(ctxs[i]->overlap.d, 0, ctxs[i]->overlap.count * kSlotBytes, lead->stream));
     HIPCHK(lead, cvh_launch_overlap(call.dtab2(), n, call.grid2, any_rows, lead->stream));
     ++g_launches[kOverlapLaunchSets];
     HIPCHK(lead, hipMemcpyAsync((void *)words, call.db + call.extra_off, word_bytes + ctl_bytes, hipMemcpyDeviceToHost, lead->stream));
     return CVH_OK;
   };
   rc = call.run(stream, false, true, [&]() -> int {   // the first host wait of the call: K and P
-    if (cleaned) {
-      if (!drop) HIPCHK(lead, cvh_launch_io_mask(call.dtab(), n, call.grid, invert, lead->stream));   // step 1 is off: the plain mask
-      const unsigned a = (unsigned)std::min<long>(min_area, 0x7fffffffl);
-      HIPCHK(lead, cvh_launch_cc_clean(call.dtab(), n, call.grid, conn, invert, a, fill_holes, keep_largest, lead->stream));
-    }
-    HIPCHK(lead, cvh_launch_cc_number(call.dtab(), n, call.grid, cleaned ? 1 : 0, conn, invert, lead->stream));
+    const int rc_mask = src.launch(call, false);
+    if (rc_mask != CVH_OK) return rc_mask;
+    HIPCHK(lead, cvh_launch_cc_number(call.dtab(), n, call.grid, cleaned ? 1 : 0, src.conn, src.invert, lead->stream));
     return pair_launch();
   });
   if (rc != CVH_OK) return rc;
@@ -121,20 +111,19 @@ int overlaps(cvh_context *const *ctxs, int n, int conn, int invert, long min_are
       const bool over = !call.tab2[i].h2 && ctl[(size_t)i * CVH_OVERLAP_CTL + 1] != 0;
       call.tab2[i].h2 = over ? 0 : 1;
       if (!over) continue;
-      if (c->overlap_slots >= max_slots(c->n))
-        return batch_fail(ctxs, n, CVH_ERR_HIP, "%s: member %d: the pair table of %zu slots overflowed", what, i, c->overlap_slots);
-      rc = set_slots(lead, c, std::min(c->overlap_slots * 4, max_slots(c->n)));
+      if (c->overlap.count >= max_slots(c->n))
+        return batch_fail(ctxs, n, CVH_ERR_HIP, "%s: member %d: the pair table of %zu slots overflowed", what, i, c->overlap.count);
+      rc = set_slots(lead, c, std::min(c->overlap.count * 4, max_slots(c->n)));
       if (rc != CVH_OK) return batch_fail(ctxs, n, rc, "%s: member %d: %s", what, i, std::string(lead->err).c_str());
       point_at_table(i);
       HIPCHK(lead, hipMemsetAsync((void *)call.tab2[i].sums, 0, CVH_OVERLAP_CTL * sizeof(unsigned), lead->stream));
       again = true;
     }
     if (!again) break;
-    HIPCHK(lead, hipMemcpyAsync((void *)call.dtab2(), call.tab2, (size_t)n * sizeof(CvhIoMember), hipMemcpyHostToDevice, lead->stream));
-    rc = pair_launch();
-    if (rc == CVH_OK) rc = close_call(ctxs, n, stream, false);
+    rc = call.upload_again(call.tab2);
+    if (rc == CVH_OK) rc = pair_launch();
+    if (rc == CVH_OK) rc = call.wait_again(stream, false);
     if (rc != CVH_OK) return rc;
-    HIPCHK(lead, hipStreamSynchronize(lead->stream));
   }
   // the rows: P is known now; they come down unsorted (the SECOND wait, only where rows are asked for) and are sorted here
   std::vector<std::vector<cvh_overlap>> rows((size_t)n);
@@ -145,14 +134,13 @@ int overlaps(cvh_context *const *ctxs, int n, int conn, int invert, long min_are
     if (ctl[(size_t)i * CVH_OVERLAP_CTL + 2] != P)
       return batch_fail(ctxs, n, CVH_ERR_HIP, "%s: member %d: %u rows written for %zu pairs", what, i, ctl[(size_t)i * CVH_OVERLAP_CTL + 2], P);
     rows[(size_t)i].resize(P);
-    HIPCHK(lead, hipMemcpyAsync(rows[(size_t)i].data(), (const uint8_t *)ctxs[i]->d_overlap + ctxs[i]->overlap_slots * kSlotBytes, P * kRowBytes,
+    HIPCHK(lead, hipMemcpyAsync(rows[(size_t)i].data(), (const uint8_t *)ctxs[i]->overlap.d + ctxs[i]->overlap.count * kSlotBytes, P * kRowBytes,
                                 hipMemcpyDeviceToHost, lead->stream));
     fetch = true;
   }
   if (fetch) {
-    rc = close_call(ctxs, n, stream, false);
+    rc = call.wait_again(stream, false);
     if (rc != CVH_OK) return rc;
-    HIPCHK(lead, hipStreamSynchronize(lead->stream));
   }
   for (int i = 0; i < n; ++i) {
     std::vector<cvh_overlap> &r = rows[(size_t)i];
@@ -175,7 +163,7 @@ extern "C" int cvh_overlaps_device_batch(cvh_context *const *ctxs, int n, int co
 {
   static const char what[] = "cvh_overlaps_device_batch";
   return guarded(ctxs, n, what, [&]() {
-    return overlaps(ctxs, n, conn, invert, min_area, fill_holes, keep_largest, d_others, tables, caps, pairs, counts, stream, what);
+    return overlaps(ctxs, n, {conn, invert, min_area, fill_holes, keep_largest}, d_others, tables, caps, pairs, counts, stream, what);
   });
 }
 
@@ -183,7 +171,7 @@ extern "C" int cvh_overlaps_device(cvh_context *c, int conn, int invert, long mi
                                    const int32_t *d_other, cvh_overlap *table, long cap, long *pairs, int *count, void *stream)
 {
   return guarded_one(c, "cvh_overlaps_device", [&](const char *what) {
-    return overlaps(&c, 1, conn, invert, min_area, fill_holes, keep_largest, &d_other, &table, &cap, pairs, count, stream, what);
+    return overlaps(&c, 1, {conn, invert, min_area, fill_holes, keep_largest}, &d_other, &table, &cap, pairs, count, stream, what);
   });
 }
 
@@ -191,7 +179,8 @@ extern "C" int cvh_overlaps(cvh_context *c, int conn, int invert, long min_area,
                             cvh_overlap *table, long cap, long *pairs, int *count)
 {
   return guarded_one(c, "cvh_overlaps", [&](const char *what) {
-    int rc = cc_clean_args(&c, 1, conn, min_area, fill_holes, keep_largest, what);
+    const MaskSource src = {conn, invert, min_area, fill_holes, keep_largest};
+    int rc = src.check(&c, 1, what);
     if (rc != CVH_OK) return rc;
     if (!other) return batch_fail(&c, 1, CVH_ERR_ARG, "%s: other is NULL", what);
     if (table && cap < 0) return batch_fail(&c, 1, CVH_ERR_ARG, "%s: member 0: cap must not be negative, got %ld", what, cap);
@@ -204,7 +193,7 @@ extern "C" int cvh_overlaps(cvh_context *c, int conn, int invert, long min_area,
     // behind the copy and, by the call's host wait, in front of the next call's copy)
     HIPCHK(c, hipMemcpyAsync(c->d_overlap_plane, other, c->n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     const int32_t *d_other = (const int32_t *)c->d_overlap_plane;
-    return overlaps(&c, 1, conn, invert, min_area, fill_holes, keep_largest, &d_other, &table, &cap, pairs, count, c->stream, what);
+    return overlaps(&c, 1, src, &d_other, &table, &cap, pairs, count, c->stream, what);
   });
 }
 

@@ -15,13 +15,8 @@ int score_batch(cvh_context *const *ctxs, int n, const uint8_t *const *d_truths,
   if (!out) return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: out is NULL", what);
   if (!d_truths) return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: the list of device pointers is NULL", what);
   rc = members_below(ctxs, n, what, 31);
+  if (rc == CVH_OK) rc = members_distances_fit(ctxs, n, what);   // (the passes are cvh_reinit's)
   if (rc != CVH_OK) return rc;
-  for (int i = 0; i < n; ++i) {
-    const cvh_context *c = ctxs[i];
-    // squared distances are 32-bit integers, vertical distances 16-bit with one value set aside (as cvh_reinit)
-    if ((unsigned long long)c->h * c->h + (unsigned long long)c->w * c->w >= (1ull << 32))
-      return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: member %d: %d x %d is too large, h^2 + w^2 must stay below 2^32", what, i, c->h, c->w);
-  }
   cvh_context *lead = ctxs[0];
   HIPCHK(lead, hipSetDevice(lead->device));
   for (int i = 0; i < n; ++i) { rc = pointer_check(ctxs, n, i, d_truths[i], what); if (rc != CVH_OK) return rc; }
