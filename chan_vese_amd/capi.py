@@ -37,6 +37,7 @@ EXPORTS = [
     "cvh_init_otsu", "cvh_init_otsu_batch", "cvh_init_rect", "cvh_init_rect_batch", "cvh_init_disk", "cvh_init_disk_batch",
     "cvh_restrict_image", "cvh_restrict_image_batch", "cvh_prolong_levelset", "cvh_prolong_levelset_batch",
     "cvh_convert_colour", "cvh_convert_colour_batch", "cvh_luma_image", "cvh_luma_image_batch",
+    "cvh_local_planes", "cvh_local_planes_batch",
     "cvh_energy", "cvh_energy_batch",
     "cvh_score_mask", "cvh_score_mask_device", "cvh_score_mask_device_batch",
     "cvh_measure", "cvh_measure_batch", "cvh_region_shape_of",
@@ -66,6 +67,10 @@ LAYOUT_PLANAR, LAYOUT_INTERLEAVED = 0, 1
 # "Colour spaces": which plane is which primary, and the spaces cvh_convert_colour knows
 ORDERS = {"bgr": 0, "rgb": 1}
 COLOUR_SPACES = {"ycrcb": 1, "yuv": 2}
+# "Local statistics": what plane k of the destination of cvh_local_planes becomes, by code and -- whole tuples -- by name
+LOCAL_COPY, LOCAL_MEAN, LOCAL_DEV = 0, 1, 2
+LOCAL_RADIUS_MAX = 127
+LOCAL_WHATS = {"mean": (LOCAL_MEAN,) * 3, "dev": (LOCAL_DEV,) * 3, "stack": (LOCAL_COPY, LOCAL_MEAN, LOCAL_DEV)}
 
 
 class Params(C.Structure):
@@ -326,6 +331,8 @@ def lib():
         "cvh_convert_colour_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_int]),
         "cvh_luma_image": (C.c_int, [vp, vp, C.c_int]),
         "cvh_luma_image_batch": (C.c_int, [C.POINTER(vp), C.POINTER(vp), C.c_int, C.c_int]),
+        "cvh_local_planes": (C.c_int, [vp, vp, C.c_int, ip]),
+        "cvh_local_planes_batch": (C.c_int, [C.POINTER(vp), C.POINTER(vp), C.c_int, ip, ip]),
         "cvh_energy": (C.c_int, [vp, C.POINTER(EnergyTerms)]),
         "cvh_energy_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.POINTER(EnergyTerms)]),
         "cvh_score_mask": (C.c_int, [vp, u8p, C.c_int, C.c_uint32, C.POINTER(MaskScore)]),
@@ -637,6 +644,49 @@ def luma_image_batch(srcs, dsts, order="bgr"):
     order = order_code(order)
     srcs, dsts = _pairs(srcs, dsts)
     _batch_chk(lib().cvh_luma_image_batch(_member_array(srcs), _member_array(dsts), len(srcs), order))
+
+
+def local_what_codes(what):
+    """A name -- "mean", "dev" (every plane) or "stack" (copy, mean, deviation) -- or 1 to 3 codes -> the three codes cvh_local_planes
+    reads; entries a destination has no plane for are ignored by the library and filled with LOCAL_COPY here.  ValueError for anything
+    else.  Calls nothing in the library."""
+    if isinstance(what, str):
+        if what.lower() not in LOCAL_WHATS:
+            raise ValueError(f"local statistic must be one of {sorted(LOCAL_WHATS)} or a tuple of codes, got {what!r}")
+        return LOCAL_WHATS[what.lower()]
+    try:
+        codes = tuple(what)
+    except TypeError:
+        codes = None
+    if not codes or len(codes) > 3 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v not in (0, 1, 2) for v in codes):
+        raise ValueError(f"local statistic must be one of {sorted(LOCAL_WHATS)} or 1 to 3 codes out of LOCAL_COPY (0), LOCAL_MEAN (1), "
+                         f"LOCAL_DEV (2), got {what!r}")
+    return tuple(int(v) for v in codes) + (LOCAL_COPY,) * (3 - len(codes))
+
+
+def local_radius(radius):
+    """An integer 0 .. LOCAL_RADIUS_MAX; ValueError for anything else.  Calls nothing in the library."""
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 0 <= radius <= LOCAL_RADIUS_MAX:
+        raise ValueError(f"local radius must be an integer 0 .. {LOCAL_RADIUS_MAX}, got {radius!r}")
+    return int(radius)
+
+
+def _is_one_what(what):
+    return isinstance(what, str) or (len(what) > 0 and not isinstance(what[0], (str, tuple, list)))
+
+
+def local_planes_batch(srcs, dsts, radius, what):
+    """cvh_local_planes_batch: Context.local_planes_to for n pairs (any mix of shapes, channel counts, radii and codes) with one set of
+    launches.  A scalar `radius` and ONE `what` (a name or a tuple of codes) go to every pair; else one per pair."""
+    srcs, dsts = _pairs(srcs, dsts)
+    n = len(srcs)
+    radii = [radius] * n if isinstance(radius, (int, np.integer)) else list(radius)
+    whats = [what] * n if _is_one_what(what) else list(what)
+    if len(radii) != n or len(whats) != n:
+        raise ValueError(f"{n} pairs need {n} radii and {n} codes tuples (or one of each), got {len(radii)} and {len(whats)}")
+    radii = (C.c_int * max(n, 1))(*[local_radius(r) for r in radii])
+    flat = [v for w in whats for v in local_what_codes(w)]
+    _batch_chk(lib().cvh_local_planes_batch(_member_array(srcs), _member_array(dsts), n, radii, (C.c_int * max(3 * n, 1))(*flat)))
 
 
 def _coarse_to_fine(pyramids, max_steps, run):
@@ -1117,6 +1167,13 @@ class Context:
         exactly as its set_image of that plane; this context is only read."""
         order = order_code(order)
         _batch_chk(self._L.cvh_luma_image(self._h, dst._h, order))
+
+    def local_planes_to(self, dst, radius, what):
+        """cvh_local_planes: plane k of `dst` (another context of the same shape, 1 or 3 channels) becomes the copy, the local mean or
+        the local deviation over the (2 radius + 1)^2 window of plane min(k, channels - 1) of this context, which is only read.  `what`
+        is "mean", "dev", "stack" or a tuple of LOCAL_COPY / LOCAL_MEAN / LOCAL_DEV; `dst` is left as set_image of those planes."""
+        radius, codes = local_radius(radius), local_what_codes(what)
+        _batch_chk(self._L.cvh_local_planes(self._h, dst._h, radius, (C.c_int * 3)(*codes)))
 
     def reinit(self):
         """cvh_reinit: the level set becomes the exact signed distance to the pixel-edge front of its own mask, on the device.

@@ -312,6 +312,18 @@ hipError_t cvh_launch_prolong(const CvhIoMember *tab, int nmem, unsigned grid, h
 unsigned cvh_colour_blocks(size_t n);
 hipError_t cvh_launch_colour_convert(const CvhIoMember *tab, int nmem, unsigned grid, int space, int order, int inverse, hipStream_t s);
 hipError_t cvh_launch_colour_luma(const CvhIoMember *tab, int nmem, unsigned grid, int order, hipStream_t s);
+// local statistics (local_kernels.hip).  src / src_stride the planes of the source context and w2 their number; plane[] the member's C
+// planes (written), sums as the ingest's; h2 the radius; interleaved the member's codes, what[k] << 2 k; dst the member's workspace: a
+// slot of cvh_local_slot_bytes(h, w) per source plane, the row sums of p^2 (32-bit) and behind them those of p (16-bit), rows
+// cvh_local_pitch(w) entries apart.  Two launches over ONE table: in the row pass a workgroup takes a row segment of
+// CVH_LOCAL_SEGMENT columns per trip, in the column pass a wave takes CVH_LOCAL_BAND rows x CVH_LOCAL_STRIP columns per trip.
+#define CVH_LOCAL_SEGMENT 1024
+#define CVH_LOCAL_BAND 32
+#define CVH_LOCAL_STRIP 256
+size_t cvh_local_pitch(int w);
+size_t cvh_local_slot_bytes(int h, int w);
+unsigned cvh_local_blocks(int h, int w, int planes_read);
+hipError_t cvh_launch_local(const CvhIoMember *tab, int nmem, unsigned grid, bool any_rows, hipStream_t s);
 // energy (energy_kernels.hip).  src the level set, src2 the CvhState that holds its means, plane[] the planes, dst the member's item rows
 // (cvh_energy_items x CVH_ENERGY_SLOTS doubles of the context's workspace), sums a row of CVH_ENERGY_ROW doubles: [0] eps (read), then
 // length, area, fit_in[3], fit_out[3], c1[3], c2[3] (written).  An item is CVH_ENERGY_BAND rows x CVH_ENERGY_COLS columns, a wave's trip.

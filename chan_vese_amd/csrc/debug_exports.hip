@@ -1,6 +1,7 @@
 // debug_exports.hip — diagnostic exports that include/chanvese_hip.h does not declare (the tests and tools/ bind them by name).
 #include "cvh_host.h"
 #include "wave_math.h"
+#include "local_math.h"
 
 // Diagnostic (not part of include/chanvese_hip.h): the strip table for a geometry, without a device.  out needs S + 1 ints.
 extern "C" int cvh_debug_strip_bounds(int kind, int h, int tiles_x, int S, int strip_rows, int nblocks, int cls, int cskew, int skew, int *out)
@@ -148,6 +149,19 @@ extern "C" unsigned long cvh_debug_pyramid_launches(void) { return g_launches[kP
 // is one), and the pixels a workgroup of colour_kernels.hip takes per trip (tests/colour_util.py sizes a plane of one workgroup + one piece)
 extern "C" unsigned long cvh_debug_colour_launches(void) { return g_launches[kColourLaunches].load(); }
 extern "C" int cvh_debug_colour_block_pixels(void) { return CVH_COLOUR_BLOCK_PIXELS; }
+// Diagnostics (not part of include/chanvese_hip.h) of cvh_local_planes*: launch sets so far in this process (a batch of n pairs is one:
+// the row pass, where a pair takes a mean or a deviation, and the column pass); the geometry of local_kernels.hip, from which
+// tests/local_util.py derives the seam shapes -- out[0] rows of a band, out[1] columns of a strip, out[2] columns of a row segment --;
+// and the per-pixel arithmetic of local_math.h compiled for the host: the floor square root (q <= 65025), and MEAN and DEV of a
+// window of n pixels with sum S and sum of squares Q (tests/test_local_restatement.py holds both against Python integers)
+extern "C" unsigned long cvh_debug_local_launch_sets(void) { return g_launches[kLocalLaunchSets].load(); }
+extern "C" void cvh_debug_local_geometry(int *out) { out[0] = CVH_LOCAL_BAND; out[1] = CVH_LOCAL_STRIP; out[2] = CVH_LOCAL_SEGMENT; }
+extern "C" unsigned cvh_debug_local_isqrt(unsigned q) { return cvh_local_isqrt(q); }
+extern "C" void cvh_debug_local_stats(unsigned n, unsigned S, unsigned Q, unsigned *mean, unsigned *dev)
+{
+  *mean = cvh_local_mean(n, S);
+  *dev = cvh_local_dev(n, S, Q);
+}
 // Diagnostic (not part of include/chanvese_hip.h): launch sets of cvh_energy / cvh_energy_batch so far in this process -- one set is the
 // term pass and the reduce pass of energy_kernels.hip over all members of the call (tests/test_gpu_energy.py: a batch of n is one set)
 extern "C" unsigned long cvh_debug_energy_launch_sets(void) { return g_launches[kEnergyLaunchSets].load(); }

@@ -38,6 +38,10 @@
 // the input, shifted right by L - 1; --init otsu / --threshold on the coarsest planes), and every level runs to its own stop (-N per
 // level) before its level set is prolonged to the next.  Every level has the same parameters; nothing is rescaled.  --state 32 applies to
 // the levels that qualify for it.  All outputs and the -V frames (the first one: the finest level's start) come from the finest level.
+// --local mean|dev|stack with --local-radius R (chanvese_hip.h, "Local statistics"): the run iterates on the local mean / local deviation
+// of every plane over the (2R+1)^2 window, or (stack, with -g) on the grey plane, its mean and its deviation as three planes, to which
+// --lambda1 / --lambda2 with three values then apply; made on the device behind Perona-Malik and --colorspace, in front of the start, so
+// --init otsu acts on the planes the run sees; --dump-planes FILE writes those planes.
 // --colorspace ycrcb|yuv (chanvese_hip.h, "Colour spaces"; not with -g): the loader's B, G, R planes become (Y, Cr, Cb) / (Y, U, V) on the
 // device behind Perona-Malik -- <stem>_pm stays the RGB picture the reference writes -- and in front of the iterations (with --levels: on
 // the finest level, before the restricts); --lambda1 / --lambda2 then weigh the luma and the two chroma planes, a start of --init otsu /
@@ -227,7 +231,7 @@ const Spec kSpecs[] = {
     {"invert-selection", 'I', 0}, {"select", 's', 0}, {"rectangle", 'R', 0}, {"circle", 'C', 0},
     // additions of this build
     {"dump-u", 0, 1}, {"dump-mask", 0, 1}, {"device", 0, 1}, {"math", 0, 1}, {"state", 0, 1}, {"rect", 0, 1}, {"circ", 0, 1}, {"reinit", 0, 1},
-    {"disk", 0, 1}, {"init", 0, 1}, {"threshold", 0, 1}, {"levels", 0, 1}, {"colorspace", 0, 1},
+    {"disk", 0, 1}, {"init", 0, 1}, {"threshold", 0, 1}, {"levels", 0, 1}, {"colorspace", 0, 1}, {"local", 0, 1}, {"local-radius", 0, 1}, {"dump-planes", 0, 1},
     {"connectivity", 0, 1}, {"min-area", 0, 1}, {"fill-holes", 0, 1}, {"largest", 0, 0}, {"roi", 0, 0},
     {"verbose", 0, 0}, {"energy", 0, 0}, {"energy-every", 0, 1}, {"truth", 0, 1}, {"score-tol", 0, 1}, {"measure", 0, 1}, {"contours", 0, 1}, {"contours-all", 0, 0},
     {"morph", 0, 1}, {"morph-radius", 0, 1}, {"init-mask", 0, 1}, {"truth-labels", 0, 1}};
@@ -382,6 +386,11 @@ void print_help()
       "  --roi                              print 'roi x0 y0 x1 y1 area' of that mask's largest component to stdout\n"
       "  --levels arg (=1)                  coarse-to-fine run over arg levels, each half the one before: the start is built and iterated\n"
       "                                     on the coarsest level, then handed up level by level (-N counts per level); not with --circ, --reinit\n"
+      "  --local arg                        mean | dev | stack: iterate on the local mean / local deviation of every plane, or (with -g) on\n"
+      "                                     the grey plane, its local mean and its local deviation as three planes; made on the device behind\n"
+      "                                     Perona-Malik and --colorspace, in front of the initial level set\n"
+      "  --local-radius arg (=2)            radius R of the (2R+1) x (2R+1) window of --local, 0 .. 127\n"
+      "  --dump-planes arg                  write the planes the run iterated on, one under the other, as PGM or PNG by extension\n"
       "  --colorspace arg                   ycrcb | yuv: iterate on (Y, Cr, Cb) / (Y, U, V) planes, converted on the device behind Perona-Malik\n"
       "                                     (--lambda1 / --lambda2 then weigh Y, the first and the second chroma plane: 0 1 1 ignores shading;\n"
       "                                     --init otsu / --threshold act on the converted planes); not with -g\n"
@@ -474,6 +483,11 @@ int main(int argc, char **argv)
   if (auto v = one("levels")) levels = to_int("levels", *v);
   std::string colorspace;
   if (auto v = one("colorspace")) colorspace = *v;
+  std::string local_name, dump_planes;
+  if (auto v = one("local")) local_name = *v;
+  if (auto v = one("dump-planes")) dump_planes = *v;
+  int local_radius = 2;
+  if (auto v = one("local-radius")) local_radius = to_int("local-radius", *v);
   const bool print_energy = vm.count("energy");
   int energy_every = 0;
   if (auto v = one("energy-every")) energy_every = to_int("energy-every", *v);
@@ -499,21 +513,36 @@ int main(int argc, char **argv)
   else if (!std::ifstream(input_filename).good()) msg_exit("Error: file \"" + input_filename + "\" does not exists!");
   if (dt <= 0) msg_exit("Cannot have negative or zero timestep: " + std::to_string(dt) + ".");
   if (mu < 0) msg_exit("Length penalty parameter cannot be negative: " + std::to_string(mu) + ".");
+  // --local: the run iterates on local statistics of the planes (chanvese_hip.h, "Local statistics"); stack turns the grey plane into three
+  int local_what[3] = {CVH_LOCAL_COPY, CVH_LOCAL_COPY, CVH_LOCAL_COPY};
+  const bool local = vm.count("local") > 0, local_stack = local && iequals(local_name, "stack");
+  if (local) {
+    if (iequals(local_name, "mean")) local_what[0] = local_what[1] = local_what[2] = CVH_LOCAL_MEAN;
+    else if (iequals(local_name, "dev")) local_what[0] = local_what[1] = local_what[2] = CVH_LOCAL_DEV;
+    else if (local_stack) { local_what[1] = CVH_LOCAL_MEAN; local_what[2] = CVH_LOCAL_DEV; }
+    else msg_exit("Invalid local statistic requested.\nCorrect values are: mean, dev, stack.");
+    if (local_stack && !grayscale) msg_exit("The local stack (--local stack) needs a grayscale read (-g): it makes three planes of one.");
+    if (local_radius < 0 || local_radius > CVH_LOCAL_RADIUS_MAX)
+      msg_exit("Local radius must be between 0 and " + std::to_string(CVH_LOCAL_RADIUS_MAX) + ": " + std::to_string(local_radius) + ".");
+  } else if (vm.count("local-radius")) {
+    msg_exit("A radius (--local-radius) needs a statistic (--local).");
+  }
+  const bool one_plane = grayscale && !local_stack;   // the run has one plane: what the lambda counts and the threshold range follow
   if (vm.count("lambda1")) {
-    if (grayscale && lambda1.size() != 1) msg_exit("Too many lambda1 values for a grayscale image.");
-    else if (!grayscale && lambda1.size() != 3) msg_exit("Number of lambda1 values must be 3 for a colored input image.");
-    else if (grayscale && lambda1[0] < 0) msg_exit("The value of lambda1 cannot be negative.");
-    else if (!grayscale && (lambda1[0] < 0 || lambda1[1] < 0 || lambda1[2] < 0)) msg_exit("Any value of lambda1 cannot be negative.");
+    if (one_plane && lambda1.size() != 1) msg_exit("Too many lambda1 values for a grayscale image.");
+    else if (!one_plane && lambda1.size() != 3) msg_exit("Number of lambda1 values must be 3 for a colored input image.");
+    else if (one_plane && lambda1[0] < 0) msg_exit("The value of lambda1 cannot be negative.");
+    else if (!one_plane && (lambda1[0] < 0 || lambda1[1] < 0 || lambda1[2] < 0)) msg_exit("Any value of lambda1 cannot be negative.");
   } else {
-    lambda1 = grayscale ? std::vector<double>{1} : std::vector<double>{1, 1, 1};
+    lambda1 = one_plane ? std::vector<double>{1} : std::vector<double>{1, 1, 1};
   }
   if (vm.count("lambda2")) {
-    if (grayscale && lambda2.size() != 1) msg_exit("Too many lambda2 values for a grayscale image.");
-    else if (!grayscale && lambda2.size() != 3) msg_exit("Number of lambda2 values must be 3 for a colored input image.");
-    else if (grayscale && lambda2[0] < 0) msg_exit("The value of lambda2 cannot be negative.");
-    else if (!grayscale && (lambda2[0] < 0 || lambda2[1] < 0 || lambda2[2] < 0)) msg_exit("Any value of lambda2 cannot be negative.");
+    if (one_plane && lambda2.size() != 1) msg_exit("Too many lambda2 values for a grayscale image.");
+    else if (!one_plane && lambda2.size() != 3) msg_exit("Number of lambda2 values must be 3 for a colored input image.");
+    else if (one_plane && lambda2[0] < 0) msg_exit("The value of lambda2 cannot be negative.");
+    else if (!one_plane && (lambda2[0] < 0 || lambda2[1] < 0 || lambda2[2] < 0)) msg_exit("Any value of lambda2 cannot be negative.");
   } else {
-    lambda2 = grayscale ? std::vector<double>{1} : std::vector<double>{1, 1, 1};
+    lambda2 = one_plane ? std::vector<double>{1} : std::vector<double>{1, 1, 1};
   }
   // (the reference's eps/tol checks look up non-existent keys and never fire: src/main.cpp:831-834)
   if (!(iequals(text_position, "TL") || iequals(text_position, "BL") || iequals(text_position, "TR") || iequals(text_position, "BR")))
@@ -551,8 +580,8 @@ int main(int argc, char **argv)
     if (std::sscanf(disk.c_str(), "%d,%d,%d%c", &disk_cx, &disk_cy, &disk_r, &rest) != 3 || disk_r < 0)
       msg_exit("You must specify the disk as cx,cy,r with a radius that is not negative");
   }
-  if (init_threshold && (threshold < 0 || threshold > 255 * (grayscale ? 1 : 3)))
-    msg_exit("Threshold must be between 0 and " + std::to_string(255 * (grayscale ? 1 : 3)) + ": " + std::to_string(threshold) + ".");
+  if (init_threshold && (threshold < 0 || threshold > 255 * (one_plane ? 1 : 3)))
+    msg_exit("Threshold must be between 0 and " + std::to_string(255 * (one_plane ? 1 : 3)) + ": " + std::to_string(threshold) + ".");
   if (math != "strict" && math != "fast") msg_exit("error: the argument ('" + math + "') for option '--math' is invalid");
   if (state_bits != 64 && state_bits != 32) msg_exit("error: the argument ('" + std::to_string(state_bits) + "') for option '--state' is invalid");
   if (reinit_every < 0) msg_exit("Reinitialisation interval cannot be negative: " + std::to_string(reinit_every) + ".");
@@ -602,7 +631,8 @@ int main(int argc, char **argv)
   if (!input_is_png && has_ext(input_filename, ".png")) msg_exit("Error on opening \"" + input_filename + "\" (probably not an image)!");
   const int h = file.h, w = file.w;
   const size_t n = (size_t)h * w;
-  const int nof_channels = grayscale ? 1 : 3;
+  const int nof_channels = grayscale ? 1 : 3;          // planes read from the file
+  const int run_channels = one_plane ? 1 : 3;           // planes the run iterates on (--local stack: three of one)
   std::vector<uint8_t> truth;   // --truth: one byte per pixel, non-zero = foreground
   if (!truth_filename.empty()) {
     Image t;
@@ -665,7 +695,7 @@ int main(int argc, char **argv)
   cvh_params prm;
   cvh_default_params(&prm);
   prm.mu = mu; prm.nu = nu; prm.dt = dt; prm.eps = eps; prm.tol = tol;
-  for (int k = 0; k < nof_channels; ++k) { prm.lambda1[k] = lambda1[k]; prm.lambda2[k] = lambda2[k]; }
+  for (int k = 0; k < run_channels; ++k) { prm.lambda1[k] = lambda1[k]; prm.lambda2[k] = lambda2[k]; }
 
   std::vector<std::pair<int, int>> level_shape{{h, w}};   // finest first
   for (int k = 1; k < levels; ++k) level_shape.push_back({(level_shape.back().first + 1) / 2, (level_shape.back().second + 1) / 2});
@@ -673,14 +703,14 @@ int main(int argc, char **argv)
     msg_exit("Too many levels for a " + std::to_string(h) + " x " + std::to_string(w) + " image: the coarsest side must not fall below 16.");
 
   cvh_context *ctx = nullptr;
-  if (cvh_create(&ctx, h, w, nof_channels, &prm, device) != CVH_OK)
+  if (cvh_create(&ctx, h, w, run_channels, &prm, device) != CVH_OK)
     msg_exit(std::string("Error: cannot initialise the HIP backend: ") + cvh_last_error(nullptr));
   cvh_check(ctx, cvh_set_option(ctx, "math_mode", math == "strict" ? CVH_MATH_STRICT : CVH_MATH_FAST), "math_mode");
   if (state_bits == 32) cvh_check(ctx, cvh_set_option(ctx, "state", 32), "state");   // declared FP32-state mode: never the default
   std::vector<cvh_context *> level{ctx};   // the helper levels of a coarse-to-fine run: idle while another level runs ("co_resident")
   for (int k = 1; k < levels; ++k) {
     cvh_context *c = nullptr;
-    if (cvh_create(&c, level_shape[k].first, level_shape[k].second, nof_channels, &prm, device) != CVH_OK)
+    if (cvh_create(&c, level_shape[k].first, level_shape[k].second, run_channels, &prm, device) != CVH_OK)
       msg_exit(std::string("Error: cannot initialise the HIP backend: ") + cvh_last_error(nullptr));
     cvh_check(c, cvh_set_option(c, "math_mode", math == "strict" ? CVH_MATH_STRICT : CVH_MATH_FAST), "math_mode");
     if (state_bits == 32) (void)cvh_set_option(c, "state", 32);   // (a level too narrow for it keeps 64)
@@ -689,10 +719,22 @@ int main(int argc, char **argv)
   }
   cvh_context *const coarsest = level.back();
   const int shift = levels - 1;
+  // --local: the file's planes go into a context of their own, where they are smoothed and converted; ctx, the one that runs, receives
+  // their local statistics -- here, for a start taken from the image and the t = 0 frame, and again behind -S and --colorspace
+  cvh_context *ingest = ctx;
+  if (local) {
+    if (cvh_create(&ingest, h, w, nof_channels, nullptr, device) != CVH_OK)
+      msg_exit(std::string("Error: cannot initialise the HIP backend: ") + cvh_last_error(nullptr));
+    cvh_check(ingest, cvh_set_option(ingest, "co_resident", 0), "co_resident");
+  }
+  auto local_planes = [&]() {
+    if (local) cvh_check(ctx, cvh_local_planes(ingest, ctx, local_radius, local_what), "cvh_local_planes");
+  };
   {
     std::vector<const uint8_t *> pp;
     for (auto &p : planes) pp.push_back(p.data());
-    cvh_check(ctx, cvh_set_image(ctx, pp.data()), "cvh_set_image");
+    cvh_check(ingest, cvh_set_image(ingest, pp.data()), "cvh_set_image");
+    local_planes();
   }
 
   // ---- level set: src/main.cpp:898-923.  A coarse-to-fine run builds it on the coarsest level, from planes that are restricted only
@@ -767,10 +809,11 @@ int main(int argc, char **argv)
 
   // ---- Perona-Malik: src/main.cpp:940-947
   if (segment) {
-    cvh_check(ctx, cvh_perona_malik(ctx, K, L, T), "cvh_perona_malik");
+    cvh_check(ingest, cvh_perona_malik(ingest, K, L, T), "cvh_perona_malik");
     std::vector<uint8_t *> pp;
     for (auto &p : planes) pp.push_back(p.data());
-    cvh_check(ctx, cvh_get_image(ctx, pp.data()), "cvh_get_image");
+    cvh_check(ingest, cvh_get_image(ingest, pp.data()), "cvh_get_image");
+    local_planes();
     std::vector<uint8_t> out(n * nof_channels);
     for (size_t q = 0; q < n; ++q) {
       if (nof_channels == 1) out[q] = planes[0][q];
@@ -788,7 +831,8 @@ int main(int argc, char **argv)
   // planes are B, G, R.  Nothing is converted back: frames, _selection and _contour use the input image.  A start taken from the image
   // is taken again from the converted planes, as behind -S
   if (colour_space) {
-    cvh_check(ctx, cvh_convert_colour(ctx, colour_space, CVH_ORDER_BGR, 0), "cvh_convert_colour");
+    cvh_check(ingest, cvh_convert_colour(ingest, colour_space, CVH_ORDER_BGR, 0), "cvh_convert_colour");
+    local_planes();
     if (levels > 1) {}
     else if (init_otsu) cvh_check(ctx, cvh_init_otsu(ctx, nullptr, 1.0, -1.0), "cvh_init_otsu");
     else if (init_threshold) cvh_check(ctx, cvh_init_threshold(ctx, threshold, 1.0, -1.0), "cvh_init_threshold");
@@ -812,8 +856,8 @@ int main(int argc, char **argv)
     cvh_check(ctx, cvh_energy(ctx, &e), "cvh_energy");
     if (iteration >= 0) std::printf("%d ", iteration);
     std::printf("energy %.17g %.17g %.17g", e.total, e.length, e.area);
-    for (int k = 0; k < nof_channels; ++k) std::printf(" %.17g", e.fit_in[k]);
-    for (int k = 0; k < nof_channels; ++k) std::printf(" %.17g", e.fit_out[k]);
+    for (int k = 0; k < run_channels; ++k) std::printf(" %.17g", e.fit_in[k]);
+    for (int k = 0; k < run_channels; ++k) std::printf(" %.17g", e.fit_out[k]);
     std::printf("\n");
     std::fflush(stdout);
   };
@@ -881,6 +925,13 @@ int main(int argc, char **argv)
                 (unsigned long long)s.fn, (unsigned long long)s.tn);
   }
 
+  if (!dump_planes.empty()) {   // the planes the run iterated on, one under the other
+    std::vector<uint8_t> all(n * run_channels);
+    std::vector<uint8_t *> pp;
+    for (int k = 0; k < run_channels; ++k) pp.push_back(all.data() + (size_t)k * n);
+    cvh_check(ctx, cvh_get_image(ctx, pp.data()), "cvh_get_image");
+    if (!write_image(dump_planes, h * run_channels, w, 1, all.data())) msg_exit("Error: cannot write \"" + dump_planes + "\"");
+  }
   if (!dump_u.empty()) {
     std::vector<double> u(n);
     cvh_check(ctx, cvh_get_levelset(ctx, u.data()), "cvh_get_levelset");
@@ -940,16 +991,16 @@ int main(int argc, char **argv)
     if (!f) msg_exit("Error: cannot write \"" + measure_filename + "\"");
     std::fprintf(f, "label,first,area,x0,y0,x1,y1,border,perimeter,cx,cy,mu20,mu02,mu11,theta,major,minor");
     for (const char *name : {"mean", "var"})
-      for (int k = 0; k < nof_channels; ++k) std::fprintf(f, ",%s%d", name, k);
+      for (int k = 0; k < run_channels; ++k) std::fprintf(f, ",%s%d", name, k);
     std::fprintf(f, "\n");
     for (int k = 0; k < count; ++k) {
       const cvh_region &r = table[(size_t)k];
       cvh_region_shape s;
-      if (cvh_region_shape_of(&r, nof_channels, &s) != CVH_OK) msg_exit("Error: cvh_region_shape_of refused row " + std::to_string(k));
+      if (cvh_region_shape_of(&r, run_channels, &s) != CVH_OK) msg_exit("Error: cvh_region_shape_of refused row " + std::to_string(k));
       std::fprintf(f, "%d,%u,%u,%d,%d,%d,%d,%u,%llu,%.17g,%.17g,%.17g,%.17g,%.17g,%.17g,%.17g,%.17g", k + 1, r.first, r.area, r.x0, r.y0, r.x1, r.y1,
                    r.border, (unsigned long long)r.perimeter, s.cx, s.cy, s.mu20, s.mu02, s.mu11, s.theta, s.major, s.minor);
-      for (int j = 0; j < nof_channels; ++j) std::fprintf(f, ",%.17g", s.mean[j]);
-      for (int j = 0; j < nof_channels; ++j) std::fprintf(f, ",%.17g", s.var[j]);
+      for (int j = 0; j < run_channels; ++j) std::fprintf(f, ",%.17g", s.mean[j]);
+      for (int j = 0; j < run_channels; ++j) std::fprintf(f, ",%.17g", s.var[j]);
       std::fprintf(f, "\n");
     }
     if (std::fclose(f) != 0) msg_exit("Error: cannot write \"" + measure_filename + "\"");
@@ -1006,6 +1057,7 @@ int main(int argc, char **argv)
     for (int s : level_steps) std::fprintf(stderr, " %d", s);
     std::fprintf(stderr, "\n");
   }
+  if (local) cvh_destroy(ingest);
   for (int k = levels - 1; k >= 0; --k) cvh_destroy(level[k]);
   return EXIT_SUCCESS;
 }

@@ -122,6 +122,26 @@ def check_colour(colour, order, channels):
     return colour.lower(), order.lower()
 
 
+def check_local(local, channels):
+    """Validates Segmenter's `local` and returns (radius, codes, channels of the planes the run iterates on), or None for None.  `local`
+    is (radius, what): what "mean" / "dev" (every plane; as many planes as are ingested), "stack" (copy, mean, deviation of ONE ingested
+    plane: three planes) or a tuple of 1 or 3 capi.LOCAL_* codes (as many planes as codes).  ValueError for anything else.  Calls
+    nothing in the library."""
+    if local is None:
+        return None
+    if not isinstance(local, (tuple, list)) or len(local) != 2:
+        raise ValueError(f"local must be (radius, what), got {local!r}")
+    radius, what = capi.local_radius(local[0]), local[1]
+    codes = capi.local_what_codes(what)
+    if isinstance(what, str):
+        if what.lower() == "stack" and channels != 1:
+            raise ValueError(f'local "stack" makes three planes of one: channels must be 1, got {channels}')
+        return radius, codes, 3 if what.lower() == "stack" else channels
+    if len(tuple(what)) not in (1, 3):
+        raise ValueError(f"a tuple of local codes names 1 or 3 planes, got {what!r}")
+    return radius, codes, len(tuple(what))
+
+
 def scale_init(kind, rows, levels):
     """The numbers of a ("rect", ..) / ("disk", ..) start, given in finest pixels, on the coarsest of `levels` levels: every number is
     shifted right by levels - 1 (an arithmetic shift: negative coordinates round down).  Other kinds pass through."""
@@ -142,16 +162,29 @@ class Segmenter:
     rescaled.  levels = 1 is the plain path, call for call.
     colour = "ycrcb" / "yuv" (three channels only) makes segment() convert the planes, read as (R, G, B) or (B, G, R) by `order`, into
     (Y, Cr, Cb) / (Y, U, V) on the device (cvh_convert_colour_batch): params.lambda1[0] / lambda2[0] then weigh the luma.  None (the
-    default) converts nothing."""
+    default) converts nothing.
+    local = (radius, what) makes the run iterate on local statistics of the ingested planes (check_local; cvh_local_planes_batch): the
+    N members ingest into `sources`, contexts of `channels` channels of their own, and `contexts` -- the ones that iterate, `run_channels`
+    channels, which `params`, `options` and every other method refer to -- receive the local planes.  None (the default): `contexts`
+    ingest themselves."""
     levels = 1
     colour = None
+    local = None
+    sources = ()
 
-    def __init__(self, n, h, w, channels=1, params=None, device=0, options=None, levels=1, colour=None, order="rgb"):
+    @property
+    def run_channels(self):
+        """channels of the planes the run iterates on: the ingested ones', or with local= what its codes make of them"""
+        return self.local[2] if self.local else self.channels
+
+    def __init__(self, n, h, w, channels=1, params=None, device=0, options=None, levels=1, colour=None, order="rgb", local=None):
         if n < 1:
             raise ValueError(f"n must be >= 1, got {n}")
         shapes = check_levels(levels, h, w)
         self.colour, self.order = check_colour(colour, order, channels)
+        self.local = check_local(local, channels)
         self.n, self.h, self.w, self.channels, self.levels = n, h, w, channels, levels
+        self.sources = []
         self.device = _device_index(device)
         self.thresholds = None   # Otsu's thresholds of the last segment(init="otsu")
         self.level_steps = None  # levels > 1: the iterations of the last segment() per member and level, finest first
@@ -162,12 +195,14 @@ class Segmenter:
             for _ in range(n):
                 self.pyramids.append([])
                 for k, (lh, lw) in enumerate(shapes):
-                    ctx = capi.Context(lh, lw, channels, params, self.device)
+                    ctx = capi.Context(lh, lw, self.run_channels, params, self.device)
                     self.pyramids[-1].append(ctx)
                     if k == 0:
                         self.contexts.append(ctx)
                     for key, value in (options or {}).items():
                         ctx.set_option(key, value)
+                if self.local:
+                    self.sources.append(capi.Context(h, w, channels, None, self.device))
         except Exception:
             self.close()
             raise
@@ -176,8 +211,11 @@ class Segmenter:
         for pyr in self.pyramids:
             for ctx in pyr:
                 ctx.close()
+        for ctx in self.sources:
+            ctx.close()
         self.contexts = []
         self.pyramids = []
+        self.sources = []
 
     def __enter__(self):
         return self
@@ -209,6 +247,9 @@ class Segmenter:
         BEFORE the start and the run (with levels > 1: on the finest level, before the restricts -- a restrict of converted planes is just
         a restrict).  "otsu" and ("threshold", t) therefore see the CONVERTED planes (g = Y + the two chroma bytes), and images() returns
         them.
+        local (the constructor's): the images are ingested, smoothed and converted in `sources`; ONE cvh_local_planes_batch then writes the
+        planes the run iterates on into `contexts`, BEFORE the restricts, the start and the run.  "otsu" and ("threshold", t) see the
+        LOCAL planes, and images() returns them; masks come out as before.
         energy_every = K > 0 runs segments of K iterations with the energy of the members still iterating taken after each
         (capi.run_batch_monitored, one cvh_energy_batch per segment; max_steps stays the total budget) and stores the series in
         self.energy_series; 0 takes none and leaves self.energy_series None.  It is a ValueError with levels > 1 or reinit_every > 0.
@@ -231,7 +272,7 @@ class Segmenter:
         if mask_init:
             kind = "mask"
         elif isinstance(init, (str, tuple)):
-            kind, start = check_init(init, self.n, self.channels)
+            kind, start = check_init(init, self.n, self.run_channels)
         layout = check_images(images, self.n, self.h, self.w, self.channels, self.device, layout)
         if mask_init:
             start = self._byte_planes(init[1], "the mask of init")
@@ -241,12 +282,15 @@ class Segmenter:
             raise ValueError("perona_malik must be (K, L, T)")
         stream = self._stream()
         self.energy_series = None
-        capi.set_image_device_batch(self.contexts, [images[i].data_ptr() for i in range(self.n)], layout, stream)
+        ingested = self.sources if self.local else self.contexts
+        capi.set_image_device_batch(ingested, [images[i].data_ptr() for i in range(self.n)], layout, stream)
         if perona_malik is not None:
             K, L, T = perona_malik
-            capi.perona_malik_batch(self.contexts, K, L, T)
+            capi.perona_malik_batch(ingested, K, L, T)
         if self.colour is not None:
-            capi.convert_colour_batch(self.contexts, self.colour, self.order)
+            capi.convert_colour_batch(ingested, self.colour, self.order)
+        if self.local:
+            capi.local_planes_batch(self.sources, self.contexts, self.local[0], self.local[1])
         first = self.contexts   # the level the start is built on
         if self.levels > 1:
             for k in range(self.levels - 1):
@@ -402,8 +446,8 @@ class Segmenter:
 
     def images(self):
         """The members' planes as they are now (after Perona-Malik: the smoothed image; with colour=: the converted planes of the last
-        segment(), (Y, Cr, Cb) or (Y, U, V)), (N, H, W) or (N, C, H, W) uint8."""
-        shape = (self.n, self.h, self.w) if self.channels == 1 else (self.n, self.channels, self.h, self.w)
+        segment(), (Y, Cr, Cb) or (Y, U, V); with local=: the local planes the run iterates on), (N, H, W) or (N, C, H, W) uint8."""
+        shape = (self.n, self.h, self.w) if self.run_channels == 1 else (self.n, self.run_channels, self.h, self.w)
         out = torch.empty(shape, dtype=torch.uint8, device=torch.device("cuda", self.device))
         for i, ctx in enumerate(self.contexts):
             ctx.get_image_device(out[i].data_ptr(), capi.LAYOUT_PLANAR, self._stream())

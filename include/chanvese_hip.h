@@ -603,6 +603,59 @@ int cvh_convert_colour_batch(cvh_context *const *ctxs, int n, int space, int ord
 int cvh_luma_image(cvh_context *src, cvh_context *dst, int order);
 int cvh_luma_image_batch(cvh_context *const *srcs, cvh_context *const *dsts, int n, int order);
 
+/* ---- Local statistics ---------------------------------------------------------------------------------------------------------
+ * The model separates regions by their per-channel means, so two regions of the same mean and different texture look alike to it.
+ * A plane of the local standard deviation tells them apart, and it is a uint8 plane like any other: the iteration kernels run on it
+ * unchanged, and lambda1[k] / lambda2[k] say how much each of brightness and texture counts.  These calls write such planes on the
+ * device -- what a caller otherwise does with cvh_get_image, a host filter and cvh_set_image.  The reference has no code for this;
+ * the definition below IS the contract.
+ *   Pairs.  src and dst are different contexts of the same h x w on the same device; each has 1 or 3 channels, independently.  Plane
+ *          k of dst becomes f_what[k] of plane min(k, C_src - 1) of src, taken as the planes are now (after cvh_perona_malik: the
+ *          smoothed planes).  Entries of `what` at k >= C_dst are ignored.  A grey src and a three-channel dst with what = (COPY,
+ *          MEAN, DEV) is the texture stack; 3 -> 3 with (DEV, DEV, DEV) is per-channel texture; 1 -> 1 with DEV the texture plane alone.
+ *   Definition.  All arithmetic is unsigned 64-bit and / is floor division.  For pixel (r, c) and radius R the window is rows
+ *          max(r - R, 0) .. min(r + R, h - 1) and columns max(c - R, 0) .. min(c + R, w - 1): truncated at the border, nothing is
+ *          padded.  With n the window's pixel count, S = sum p and Q = sum p^2 over the window:
+ *              CVH_LOCAL_COPY   p
+ *              CVH_LOCAL_MEAN   (2 S + n) / (2 n)                     round-half-up; never above 255
+ *              CVH_LOCAL_DEV    isqrt(4 (n Q - S^2) / n^2)            isqrt: the exact floor square root
+ *          DEV is floor(2 sigma) of the window's population deviation; 4 sigma^2 <= 255^2 = 65025, so DEV <= 255 without a clamp.
+ *          With R <= CVH_LOCAL_RADIUS_MAX: n <= 65025 and 4 n Q < 2^51.  R = 0 gives MEAN = p and DEV = 0; a constant plane gives MEAN = the constant and DEV = 0; a window half a and half b gives DEV = |a - b|.
+ *   State. dst is left exactly as cvh_set_image of those bytes leaves it -- planes, sums, stop norm, validity flags; a level set it
+ *          already has stays as cvh_set_image leaves it; its iterations in flight are settled first.  src is only read: level set,
+ *          run state, sums and options are untouched, its iterations in flight stay in flight, and a run continued after the call is
+ *          bit-identical to one without (as cvh_luma_image).
+ * The *_batch form takes n pairs (pair i = srcs[i], dsts[i], radius[i], what[CVH_MAX_CHANNELS * i ..]) of any mix of shapes, channel
+ * counts, radii and codes in ONE set of launches on the stream of pair 0's destination, ordered after everything already enqueued on
+ * the stream of every listed context and before anything enqueued on them later; one host wait per call, for the sums (one channel
+ * summed on the device, three channels fetched and summed on the host behind that wait, as cvh_luma_image_batch).  The single form is
+ * the batch with n = 1; a member alone or in any batch gets the same bytes.
+ * How (chan_vese_amd/csrc/local_kernels.hip): the window sums are separable, so the work per pixel does not grow with R^2.  A row
+ * pass writes the horizontal window sums of every source plane a MEAN or DEV plane reads -- prefix sums of a row segment in LDS, a
+ * pixel's sum the difference of two entries -- into a workspace the destination owns (6 bytes per pixel and plane, allocated by its
+ * first such call, freed by cvh_destroy).  In the column pass a wave takes a band of 32 rows by 256 columns, each lane holding the
+ * running vertical sums of four columns in registers; it reads the 2 R + 1 rows about the band's first row, then adds one row and
+ * subtracts one per row written.  A call of COPY planes alone skips the row pass.
+ * Cost, one run of tools/local_probe.py on an MI355X (profiles/r19_local/; host clock around a call and its wait, 20
+ * calls after 3): the 1 -> 1 deviation plane at R = 2 / 8 / 32 / 127 takes 115 / 120 / 134 / 198 us at 1024^2, 128 / 134 / 153 / 209 us
+ * at 2048^2 and 181 / 186 / 201 / 281 us at 4096^2 -- NOT flat in R: the row pass does not depend on R, but a band of 32 rows starts
+ * from 2 R + 1 rows of row sums (69 row reads per band at R = 2, 319 at R = 127), and the call is 55 - 70 % dearer at R = 127 than at
+ * R = 2.  One CSV iteration of the same plane: 10 / 14 / 65 us.  The 1 -> 3 stack takes 1.1 / 4.0 / 12.9 ms at every radius, nearly
+ * all of it the three-channel stop norm the host takes behind the wait, as for every call that replaces three planes.  The round trip
+ * the call replaces (cvh_get_image, numpy cumulative sums, cvh_set_image) took 56 ms / 0.39 s / 3.2 s in the same run.
+ * CVH_ERR_ARG: NULL lists or members, n < 1, a context listed more than once across both lists (src == dst included), contexts on
+ * different devices, different shapes within a pair, a radius outside 0 .. CVH_LOCAL_RADIUS_MAX, a `what` entry below C_dst that is
+ * none of the three codes, h*w >= 2^32.  CVH_ERR_STATE: a src without an image.  Checked for every pair before anything is launched;
+ * the message names the pair index and is cvh_last_error(NULL)'s (and pair 0's destination's, once the lists hold no NULL); the
+ * contexts stay usable and their planes unchanged. */
+#define CVH_LOCAL_COPY 0
+#define CVH_LOCAL_MEAN 1
+#define CVH_LOCAL_DEV  2
+#define CVH_LOCAL_RADIUS_MAX 127
+int cvh_local_planes(cvh_context *src, cvh_context *dst, int radius, const int *what);
+int cvh_local_planes_batch(cvh_context *const *srcs, cvh_context *const *dsts, int n,
+                           const int *radius /* n */, const int *what /* CVH_MAX_CHANNELS per pair */);
+
 /* ---- Energy ------------------------------------------------------------------------------------------------------------------
  * The library minimises the Chan-Sandberg-Vese functional
  *     E(u) = mu Length + nu Area + (1/C) sum_k [ lambda1_k int (I_k - c1_k)^2 H_eps(u) + lambda2_k int (I_k - c2_k)^2 (1 - H_eps(u)) ];
