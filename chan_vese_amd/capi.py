@@ -38,6 +38,7 @@ EXPORTS = [
     "cvh_restrict_image", "cvh_restrict_image_batch", "cvh_prolong_levelset", "cvh_prolong_levelset_batch",
     "cvh_convert_colour", "cvh_convert_colour_batch", "cvh_luma_image", "cvh_luma_image_batch",
     "cvh_local_planes", "cvh_local_planes_batch",
+    "cvh_rank_planes", "cvh_rank_planes_batch",
     "cvh_energy", "cvh_energy_batch",
     "cvh_score_mask", "cvh_score_mask_device", "cvh_score_mask_device_batch",
     "cvh_measure", "cvh_measure_batch", "cvh_region_shape_of",
@@ -71,6 +72,11 @@ COLOUR_SPACES = {"ycrcb": 1, "yuv": 2}
 LOCAL_COPY, LOCAL_MEAN, LOCAL_DEV = 0, 1, 2
 LOCAL_RADIUS_MAX = 127
 LOCAL_WHATS = {"mean": (LOCAL_MEAN,) * 3, "dev": (LOCAL_DEV,) * 3, "stack": (LOCAL_COPY, LOCAL_MEAN, LOCAL_DEV)}
+# "Rank planes": what plane k of the destination of cvh_rank_planes becomes, by code and -- every plane alike -- by name
+RANK_COPY, RANK_MIN, RANK_MAX, RANK_MEDIAN, RANK_OPEN, RANK_CLOSE, RANK_TOPHAT, RANK_BOTHAT = range(8)
+RANK_RADIUS_MAX, RANK_MEDIAN_RADIUS_MAX = 127, 7
+RANK_WHATS = {"min": RANK_MIN, "max": RANK_MAX, "median": RANK_MEDIAN, "open": RANK_OPEN, "close": RANK_CLOSE, "tophat": RANK_TOPHAT,
+              "bothat": RANK_BOTHAT}
 
 
 class Params(C.Structure):
@@ -333,6 +339,8 @@ def lib():
         "cvh_luma_image_batch": (C.c_int, [C.POINTER(vp), C.POINTER(vp), C.c_int, C.c_int]),
         "cvh_local_planes": (C.c_int, [vp, vp, C.c_int, ip]),
         "cvh_local_planes_batch": (C.c_int, [C.POINTER(vp), C.POINTER(vp), C.c_int, ip, ip]),
+        "cvh_rank_planes": (C.c_int, [vp, vp, C.c_int, ip]),
+        "cvh_rank_planes_batch": (C.c_int, [C.POINTER(vp), C.POINTER(vp), C.c_int, ip, ip]),
         "cvh_energy": (C.c_int, [vp, C.POINTER(EnergyTerms)]),
         "cvh_energy_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.POINTER(EnergyTerms)]),
         "cvh_score_mask": (C.c_int, [vp, u8p, C.c_int, C.c_uint32, C.POINTER(MaskScore)]),
@@ -687,6 +695,49 @@ def local_planes_batch(srcs, dsts, radius, what):
     radii = (C.c_int * max(n, 1))(*[local_radius(r) for r in radii])
     flat = [v for w in whats for v in local_what_codes(w)]
     _batch_chk(lib().cvh_local_planes_batch(_member_array(srcs), _member_array(dsts), n, radii, (C.c_int * max(3 * n, 1))(*flat)))
+
+
+def rank_what_codes(what):
+    """A name -- "min", "max", "median", "open", "close", "tophat", "bothat" (every plane) -- or 1 to 3 codes -> the three codes
+    cvh_rank_planes reads; entries a destination has no plane for are ignored by the library and filled with RANK_COPY here.
+    ValueError for anything else.  Calls nothing in the library."""
+    if isinstance(what, str):
+        if what.lower() not in RANK_WHATS:
+            raise ValueError(f"rank filter must be one of {sorted(RANK_WHATS)} or a tuple of codes, got {what!r}")
+        return (RANK_WHATS[what.lower()],) * 3
+    try:
+        codes = tuple(what)
+    except TypeError:
+        codes = None
+    if not codes or len(codes) > 3 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= 7 for v in codes):
+        raise ValueError(f"rank filter must be one of {sorted(RANK_WHATS)} or 1 to 3 codes out of RANK_COPY (0) .. RANK_BOTHAT (7), "
+                         f"got {what!r}")
+    return tuple(int(v) for v in codes) + (RANK_COPY,) * (3 - len(codes))
+
+
+def rank_radius(radius, codes=()):
+    """An integer 0 .. RANK_RADIUS_MAX, and 0 .. RANK_MEDIAN_RADIUS_MAX where `codes` hold RANK_MEDIAN; ValueError for anything else.
+    Calls nothing in the library."""
+    top = RANK_MEDIAN_RADIUS_MAX if RANK_MEDIAN in tuple(codes) else RANK_RADIUS_MAX
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 0 <= radius <= top:
+        raise ValueError(f"rank radius must be an integer 0 .. {top}{' for a median' if top == RANK_MEDIAN_RADIUS_MAX else ''}, got {radius!r}")
+    return int(radius)
+
+
+def rank_planes_batch(srcs, dsts, radius, what):
+    """cvh_rank_planes_batch: Context.rank_planes_to for n pairs (any mix of shapes, channel counts, radii and codes) with one set of
+    launches.  A scalar `radius` and ONE `what` (a name or a tuple of codes) go to every pair; else one per pair.  A median's radius
+    limit is checked against the codes a destination has planes for."""
+    srcs, dsts = _pairs(srcs, dsts)
+    n = len(srcs)
+    radii = [radius] * n if isinstance(radius, (int, np.integer)) else list(radius)
+    whats = [what] * n if _is_one_what(what) else list(what)
+    if len(radii) != n or len(whats) != n:
+        raise ValueError(f"{n} pairs need {n} radii and {n} codes tuples (or one of each), got {len(radii)} and {len(whats)}")
+    codes = [rank_what_codes(w) for w in whats]
+    radii = (C.c_int * max(n, 1))(*[rank_radius(r, c[:getattr(d, "channels", 3)]) for r, c, d in zip(radii, codes, dsts)])
+    flat = [v for c in codes for v in c]
+    _batch_chk(lib().cvh_rank_planes_batch(_member_array(srcs), _member_array(dsts), n, radii, (C.c_int * max(3 * n, 1))(*flat)))
 
 
 def _coarse_to_fine(pyramids, max_steps, run):
@@ -1174,6 +1225,15 @@ class Context:
         is "mean", "dev", "stack" or a tuple of LOCAL_COPY / LOCAL_MEAN / LOCAL_DEV; `dst` is left as set_image of those planes."""
         radius, codes = local_radius(radius), local_what_codes(what)
         _batch_chk(self._L.cvh_local_planes(self._h, dst._h, radius, (C.c_int * 3)(*codes)))
+
+    def rank_planes_to(self, dst, radius, what):
+        """cvh_rank_planes: plane k of `dst` (another context of the same shape, 1 or 3 channels) becomes the copy, minimum, maximum,
+        median, opening, closing, white or black top-hat over the (2 radius + 1)^2 window of plane min(k, channels - 1) of this context,
+        which is only read.  `what` is "min", "max", "median", "open", "close", "tophat", "bothat" or a tuple of RANK_* codes; `dst` is
+        left as set_image of those planes."""
+        codes = rank_what_codes(what)
+        radius = rank_radius(radius, codes[:getattr(dst, "channels", 3)])
+        _batch_chk(self._L.cvh_rank_planes(self._h, dst._h, radius, (C.c_int * 3)(*codes)))
 
     def reinit(self):
         """cvh_reinit: the level set becomes the exact signed distance to the pixel-edge front of its own mask, on the device.

@@ -149,6 +149,7 @@ extern "C" void cvh_destroy(cvh_context *c)
   if (c->d_score) (void)hipFree(c->d_score);
   if (c->d_morph) (void)hipFree(c->d_morph);
   if (c->d_local) (void)hipFree(c->d_local);
+  if (c->d_rank) (void)hipFree(c->d_rank);
   if (c->d_overlap_plane) (void)hipFree(c->d_overlap_plane);
   if (c->ev_io_in) (void)hipEventDestroy(c->ev_io_in);
   if (c->ev_io_out) (void)hipEventDestroy(c->ev_io_out);

@@ -4,7 +4,7 @@
 // device buffers), pm_run.hip (Perona-Malik), io_run.hip (device-memory I/O, reinitialisation, and the scaffolds of the member-table
 // calls: MemberCall with its further waits, write_planes, the pointer checks, the launch counters), init_run.hip (device-side initial
 // level sets), components_run.hip (connected components, and MaskSource: the raw or cleaned mask every mask-derived call starts from),
-// pyramid_run.hip (coarse-to-fine), colour_run.hip (colour spaces), local_run.hip (local statistics), energy_run.hip (the functional's terms), score_run.hip (mask scores),
+// pyramid_run.hip (coarse-to-fine), colour_run.hip (colour spaces), local_run.hip (local statistics), rank_run.hip (rank planes), energy_run.hip (the functional's terms), score_run.hip (mask scores),
 // morph_run.hip (mask morphology, mask starts), measure_run.hip (component measures), contour_run.hip (contours), overlap_run.hip
 // (component overlaps), debug_exports.hip (diagnostics).  Kernel sources do not include it.
 #pragma once
@@ -162,6 +162,9 @@ struct cvh_context {   // opaque to callers; four groups
   void *d_local = nullptr;       // workspace of cvh_local_planes* (local_run.hip) as their DESTINATION: the row sums of the source planes it reads, a
                                  // slot of 6 bytes per pixel per plane of this context: allocated by the first call that takes a mean or a
                                  // deviation, kept -- not part of live_footprint either
+  void *d_rank = nullptr;        // workspace of cvh_rank_planes* (rank_run.hip) as their DESTINATION: CVH_RANK_SLOTS byte planes per plane of this context
+                                 // (7 bytes per pixel and plane): allocated by the first call that takes anything but copies, kept -- not part
+                                 // of live_footprint either
   DeviceTable overlap;           // cvh_overlaps* (overlap_run.hip): overlap.count slots of the pair table and overlap.count / 2 rows behind them (24 bytes
                                  // per slot), grown where a call's table overflows, kept; d_overlap_plane: the int32 plane the host form stages
   void *d_overlap_plane = nullptr;   // (4 bytes per pixel) -- allocated by the first call that needs them, not part of live_footprint either
@@ -270,8 +273,8 @@ void free_table(DeviceTable *t);
 // reduce pass for all members) of cvh_energy*, the launch sets (four kernels for all members) of cvh_score_mask*, and the launch sets (every
 // kernel of the call, for all members) of cvh_get_mask_morph* / cvh_morph_levelset* / cvh_init_mask*, and the pair launches of cvh_overlaps*
 // (one per call, and one more each time a member's table had to grow), and the launch sets (row pass and column pass for all pairs) of
-// cvh_local_planes*
-enum LaunchCounter { kReinitLaunchSets, kPyramidLaunches, kColourLaunches, kEnergyLaunchSets, kScoreLaunchSets, kMorphLaunchSets, kOverlapLaunchSets, kLocalLaunchSets, kLaunchCounters };
+// cvh_local_planes*, and the launch sets (every pass for all pairs) of cvh_rank_planes*
+enum LaunchCounter { kReinitLaunchSets, kPyramidLaunches, kColourLaunches, kEnergyLaunchSets, kScoreLaunchSets, kMorphLaunchSets, kOverlapLaunchSets, kLocalLaunchSets, kRankLaunchSets, kLaunchCounters };
 extern std::atomic<unsigned long> g_launches[kLaunchCounters];
 
 // io_run.hip: what every call on device memory or on a member table shares (the comments are at the definitions)
@@ -374,7 +377,7 @@ struct PlaneSums {
   int fetch(const MemberCall &call);
   void arrive(const MemberCall &call);
 };
-// the one path of a call that replaces the planes of ctxs[0 .. n_written-1] (an ingest, a conversion, a luma, local statistics, a restrict): see io_run.hip
+// the one path of a call that replaces the planes of ctxs[0 .. n_written-1] (an ingest, a conversion, a luma, local statistics, rank planes, a restrict): see io_run.hip
 int write_planes(cvh_context *const *ctxs, int n_written, int n_members, const char *what, void *stream,
                  const std::function<void(int, CvhIoMember &)> &fill, const std::function<int(const MemberCall &)> &launch);
 

@@ -324,6 +324,27 @@ size_t cvh_local_pitch(int w);
 size_t cvh_local_slot_bytes(int h, int w);
 unsigned cvh_local_blocks(int h, int w, int planes_read);
 hipError_t cvh_launch_local(const CvhIoMember *tab, int nmem, unsigned grid, bool any_rows, hipStream_t s);
+// rank planes (rank_kernels.hip).  src / src_stride the planes of the source context and w2 their number; plane[] the member's C planes
+// (written), sums as the ingest's; h2 the radius; interleaved the member's codes, what[k] << 3 k; dst the member's workspace:
+// CVH_RANK_SLOTS byte planes of cvh_rank_slot_bytes(h, w) per source plane, rows cvh_rank_pitch(w) bytes apart (rank_kernels.hip says
+// which is which).  Up to five launches over ONE table, chosen by `passes`: the row pass of every chain (CVH_RANK_PASS_ROWS), the column
+// and the second row pass of the chains that run twice (CVH_RANK_PASS_TWICE), the median (CVH_RANK_PASS_MEDIAN), and always the final
+// pass, which writes the planes.  The row pass takes a row segment of CVH_RANK_SEGMENT columns per workgroup and trip, the column passes
+// cvh_rank_band_rows(R, CVH_RANK_BAND) rows x CVH_RANK_STRIP columns per wave and trip (rank_math.h), the median CVH_RANK_MEDIAN_BAND
+// rows x CVH_RANK_MEDIAN_STRIP columns per wave and trip.
+#define CVH_RANK_SEGMENT CVH_LOCAL_SEGMENT
+#define CVH_RANK_BAND CVH_LOCAL_BAND
+#define CVH_RANK_STRIP CVH_LOCAL_STRIP
+#define CVH_RANK_MEDIAN_BAND 32
+#define CVH_RANK_MEDIAN_STRIP 64
+#define CVH_RANK_SLOTS 7
+#define CVH_RANK_PASS_ROWS 1u
+#define CVH_RANK_PASS_TWICE 2u
+#define CVH_RANK_PASS_MEDIAN 4u
+size_t cvh_rank_pitch(int w);
+size_t cvh_rank_slot_bytes(int h, int w);
+unsigned cvh_rank_blocks(int h, int w, int R, int row_jobs, int median_planes);
+hipError_t cvh_launch_rank(const CvhIoMember *tab, int nmem, unsigned grid, unsigned passes, hipStream_t s);
 // energy (energy_kernels.hip).  src the level set, src2 the CvhState that holds its means, plane[] the planes, dst the member's item rows
 // (cvh_energy_items x CVH_ENERGY_SLOTS doubles of the context's workspace), sums a row of CVH_ENERGY_ROW doubles: [0] eps (read), then
 // length, area, fit_in[3], fit_out[3], c1[3], c2[3] (written).  An item is CVH_ENERGY_BAND rows x CVH_ENERGY_COLS columns, a wave's trip.

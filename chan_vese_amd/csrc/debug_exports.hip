@@ -2,6 +2,7 @@
 #include "cvh_host.h"
 #include "wave_math.h"
 #include "local_math.h"
+#include "rank_math.h"
 
 // Diagnostic (not part of include/chanvese_hip.h): the strip table for a geometry, without a device.  out needs S + 1 ints.
 extern "C" int cvh_debug_strip_bounds(int kind, int h, int tiles_x, int S, int strip_rows, int nblocks, int cls, int cskew, int skew, int *out)
@@ -162,6 +163,21 @@ extern "C" void cvh_debug_local_stats(unsigned n, unsigned S, unsigned Q, unsign
   *mean = cvh_local_mean(n, S);
   *dev = cvh_local_dev(n, S, Q);
 }
+// Diagnostics (not part of include/chanvese_hip.h) of cvh_rank_planes*: launch sets so far in this process (a batch of n pairs is one: up to
+// five launches); the geometry of rank_kernels.hip, from which tests/rank_util.py derives the seam shapes -- out[0] rows of a column band
+// at R = 0 (at radius R: cvh_debug_rank_band_rows), out[1] columns of a strip, out[2] columns of a row segment, out[3] rows and out[4]
+// columns of a median trip --; and the integer arithmetic of rank_math.h compiled for the host: a code's chain and whether it runs twice,
+// the rows of a band at a radius, the rank of the lower median, and the walk over sixteen packed byte counters
+extern "C" unsigned long cvh_debug_rank_launch_sets(void) { return g_launches[kRankLaunchSets].load(); }
+extern "C" void cvh_debug_rank_geometry(int *out)
+{
+  out[0] = CVH_RANK_BAND; out[1] = CVH_RANK_STRIP; out[2] = CVH_RANK_SEGMENT; out[3] = CVH_RANK_MEDIAN_BAND; out[4] = CVH_RANK_MEDIAN_STRIP;
+}
+extern "C" int cvh_debug_rank_chain(int code) { return cvh_rank_chain(code); }
+extern "C" int cvh_debug_rank_twice(int code) { return cvh_rank_twice(code); }
+extern "C" int cvh_debug_rank_band_rows(int R) { return cvh_rank_band_rows(R, CVH_RANK_BAND); }
+extern "C" unsigned cvh_debug_rank_median_index(unsigned n) { return cvh_rank_median_index(n); }
+extern "C" int cvh_debug_rank_walk(const unsigned *words, unsigned *before, unsigned t) { return cvh_rank_walk(words, before, t); }
 // Diagnostic (not part of include/chanvese_hip.h): launch sets of cvh_energy / cvh_energy_batch so far in this process -- one set is the
 // term pass and the reduce pass of energy_kernels.hip over all members of the call (tests/test_gpu_energy.py: a batch of n is one set)
 extern "C" unsigned long cvh_debug_energy_launch_sets(void) { return g_launches[kEnergyLaunchSets].load(); }

@@ -42,6 +42,10 @@
 // of every plane over the (2R+1)^2 window, or (stack, with -g) on the grey plane, its mean and its deviation as three planes, to which
 // --lambda1 / --lambda2 with three values then apply; made on the device behind Perona-Malik and --colorspace, in front of the start, so
 // --init otsu acts on the planes the run sees; --dump-planes FILE writes those planes.
+// --rank median|min|max|open|close|tophat|bothat with --rank-radius R (chanvese_hip.h, "Rank planes"): the run iterates on that rank
+// filter of every plane over the (2R+1)^2 window -- a median against impulse noise, a top-hat against a shading ramp; made on the device
+// behind Perona-Malik and --colorspace, in front of --local (which then works on its result) and of the start; --dump-planes FILE writes
+// the planes the run iterated on.
 // --colorspace ycrcb|yuv (chanvese_hip.h, "Colour spaces"; not with -g): the loader's B, G, R planes become (Y, Cr, Cb) / (Y, U, V) on the
 // device behind Perona-Malik -- <stem>_pm stays the RGB picture the reference writes -- and in front of the iterations (with --levels: on
 // the finest level, before the restricts); --lambda1 / --lambda2 then weigh the luma and the two chroma planes, a start of --init otsu /
@@ -231,7 +235,7 @@ const Spec kSpecs[] = {
     {"invert-selection", 'I', 0}, {"select", 's', 0}, {"rectangle", 'R', 0}, {"circle", 'C', 0},
     // additions of this build
     {"dump-u", 0, 1}, {"dump-mask", 0, 1}, {"device", 0, 1}, {"math", 0, 1}, {"state", 0, 1}, {"rect", 0, 1}, {"circ", 0, 1}, {"reinit", 0, 1},
-    {"disk", 0, 1}, {"init", 0, 1}, {"threshold", 0, 1}, {"levels", 0, 1}, {"colorspace", 0, 1}, {"local", 0, 1}, {"local-radius", 0, 1}, {"dump-planes", 0, 1},
+    {"disk", 0, 1}, {"init", 0, 1}, {"threshold", 0, 1}, {"levels", 0, 1}, {"colorspace", 0, 1}, {"local", 0, 1}, {"local-radius", 0, 1}, {"dump-planes", 0, 1}, {"rank", 0, 1}, {"rank-radius", 0, 1},
     {"connectivity", 0, 1}, {"min-area", 0, 1}, {"fill-holes", 0, 1}, {"largest", 0, 0}, {"roi", 0, 0},
     {"verbose", 0, 0}, {"energy", 0, 0}, {"energy-every", 0, 1}, {"truth", 0, 1}, {"score-tol", 0, 1}, {"measure", 0, 1}, {"contours", 0, 1}, {"contours-all", 0, 0},
     {"morph", 0, 1}, {"morph-radius", 0, 1}, {"init-mask", 0, 1}, {"truth-labels", 0, 1}};
@@ -390,6 +394,9 @@ void print_help()
       "                                     the grey plane, its local mean and its local deviation as three planes; made on the device behind\n"
       "                                     Perona-Malik and --colorspace, in front of the initial level set\n"
       "  --local-radius arg (=2)            radius R of the (2R+1) x (2R+1) window of --local, 0 .. 127\n"
+      "  --rank arg                         median | min | max | open | close | tophat | bothat: iterate on that rank filter of every plane;\n"
+      "                                     made on the device behind Perona-Malik and --colorspace, in front of --local and the initial level set\n"
+      "  --rank-radius arg (=1)             radius R of the (2R+1) x (2R+1) window of --rank, 0 .. 127 (median: 0 .. 7)\n"
       "  --dump-planes arg                  write the planes the run iterated on, one under the other, as PGM or PNG by extension\n"
       "  --colorspace arg                   ycrcb | yuv: iterate on (Y, Cr, Cb) / (Y, U, V) planes, converted on the device behind Perona-Malik\n"
       "                                     (--lambda1 / --lambda2 then weigh Y, the first and the second chroma plane: 0 1 1 ignores shading;\n"
@@ -486,6 +493,10 @@ int main(int argc, char **argv)
   std::string local_name, dump_planes;
   if (auto v = one("local")) local_name = *v;
   if (auto v = one("dump-planes")) dump_planes = *v;
+  std::string rank_name;
+  if (auto v = one("rank")) rank_name = *v;
+  int rank_radius = 1;
+  if (auto v = one("rank-radius")) rank_radius = to_int("rank-radius", *v);
   int local_radius = 2;
   if (auto v = one("local-radius")) local_radius = to_int("local-radius", *v);
   const bool print_energy = vm.count("energy");
@@ -526,6 +537,22 @@ int main(int argc, char **argv)
       msg_exit("Local radius must be between 0 and " + std::to_string(CVH_LOCAL_RADIUS_MAX) + ": " + std::to_string(local_radius) + ".");
   } else if (vm.count("local-radius")) {
     msg_exit("A radius (--local-radius) needs a statistic (--local).");
+  }
+  // --rank: the run iterates on a rank filter of the planes (chanvese_hip.h, "Rank planes"), every plane alike
+  int rank_what[3] = {CVH_RANK_COPY, CVH_RANK_COPY, CVH_RANK_COPY};
+  const bool rank = vm.count("rank") > 0;
+  if (rank) {
+    static const std::pair<const char *, int> names[] = {{"min", CVH_RANK_MIN}, {"max", CVH_RANK_MAX}, {"median", CVH_RANK_MEDIAN}, {"open", CVH_RANK_OPEN},
+                                                         {"close", CVH_RANK_CLOSE}, {"tophat", CVH_RANK_TOPHAT}, {"bothat", CVH_RANK_BOTHAT}};
+    for (const auto &nm : names)
+      if (iequals(rank_name, nm.first)) rank_what[0] = rank_what[1] = rank_what[2] = nm.second;
+    if (rank_what[0] == CVH_RANK_COPY) msg_exit("Invalid rank filter requested.\nCorrect values are: median, min, max, open, close, tophat, bothat.");
+    const int top = rank_what[0] == CVH_RANK_MEDIAN ? CVH_RANK_MEDIAN_RADIUS_MAX : CVH_RANK_RADIUS_MAX;
+    if (rank_radius < 0 || rank_radius > top)
+      msg_exit("Rank radius must be between 0 and " + std::to_string(top) + (top == CVH_RANK_MEDIAN_RADIUS_MAX ? " for a median: " : ": ") +
+               std::to_string(rank_radius) + ".");
+  } else if (vm.count("rank-radius")) {
+    msg_exit("A radius (--rank-radius) needs a filter (--rank).");
   }
   const bool one_plane = grayscale && !local_stack;   // the run has one plane: what the lambda counts and the threshold range follow
   if (vm.count("lambda1")) {
@@ -721,14 +748,21 @@ int main(int argc, char **argv)
   const int shift = levels - 1;
   // --local: the file's planes go into a context of their own, where they are smoothed and converted; ctx, the one that runs, receives
   // their local statistics -- here, for a start taken from the image and the t = 0 frame, and again behind -S and --colorspace
-  cvh_context *ingest = ctx;
-  if (local) {
+  // --rank goes the same way and in front of --local: with both, the rank planes land in a context of their own that --local reads
+  cvh_context *ingest = ctx, *ranked = ctx;
+  if (local || rank) {
     if (cvh_create(&ingest, h, w, nof_channels, nullptr, device) != CVH_OK)
       msg_exit(std::string("Error: cannot initialise the HIP backend: ") + cvh_last_error(nullptr));
     cvh_check(ingest, cvh_set_option(ingest, "co_resident", 0), "co_resident");
   }
+  if (local && rank) {
+    if (cvh_create(&ranked, h, w, nof_channels, nullptr, device) != CVH_OK)
+      msg_exit(std::string("Error: cannot initialise the HIP backend: ") + cvh_last_error(nullptr));
+    cvh_check(ranked, cvh_set_option(ranked, "co_resident", 0), "co_resident");
+  }
   auto local_planes = [&]() {
-    if (local) cvh_check(ctx, cvh_local_planes(ingest, ctx, local_radius, local_what), "cvh_local_planes");
+    if (rank) cvh_check(ranked, cvh_rank_planes(ingest, ranked, rank_radius, rank_what), "cvh_rank_planes");
+    if (local) cvh_check(ctx, cvh_local_planes(rank ? ranked : ingest, ctx, local_radius, local_what), "cvh_local_planes");
   };
   {
     std::vector<const uint8_t *> pp;
@@ -1057,7 +1091,8 @@ int main(int argc, char **argv)
     for (int s : level_steps) std::fprintf(stderr, " %d", s);
     std::fprintf(stderr, "\n");
   }
-  if (local) cvh_destroy(ingest);
+  if (local && rank) cvh_destroy(ranked);
+  if (local || rank) cvh_destroy(ingest);
   for (int k = levels - 1; k >= 0; --k) cvh_destroy(level[k]);
   return EXIT_SUCCESS;
 }

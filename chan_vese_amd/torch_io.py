@@ -142,6 +142,25 @@ def check_local(local, channels):
     return radius, codes, len(tuple(what))
 
 
+def check_rank(rank, channels):
+    """Validates Segmenter's `rank` and returns (radius, codes, channels of the planes the filter makes), or None for None.  `rank` is
+    (radius, what): what "min" / "max" / "median" / "open" / "close" / "tophat" / "bothat" (every plane; as many planes as are
+    ingested) or a tuple of 1 or 3 capi.RANK_* codes (as many planes as codes).  A median binds the radius to
+    capi.RANK_MEDIAN_RADIUS_MAX.  ValueError for anything else.  Calls nothing in the library."""
+    if rank is None:
+        return None
+    if not isinstance(rank, (tuple, list)) or len(rank) != 2:
+        raise ValueError(f"rank must be (radius, what), got {rank!r}")
+    what = rank[1]
+    codes = capi.rank_what_codes(what)
+    made = channels
+    if not isinstance(what, str):
+        if len(tuple(what)) not in (1, 3):
+            raise ValueError(f"a tuple of rank codes names 1 or 3 planes, got {what!r}")
+        made = len(tuple(what))
+    return capi.rank_radius(rank[0], codes[:made]), codes, made
+
+
 def scale_init(kind, rows, levels):
     """The numbers of a ("rect", ..) / ("disk", ..) start, given in finest pixels, on the coarsest of `levels` levels: every number is
     shifted right by levels - 1 (an arithmetic shift: negative coordinates round down).  Other kinds pass through."""
@@ -166,25 +185,32 @@ class Segmenter:
     local = (radius, what) makes the run iterate on local statistics of the ingested planes (check_local; cvh_local_planes_batch): the
     N members ingest into `sources`, contexts of `channels` channels of their own, and `contexts` -- the ones that iterate, `run_channels`
     channels, which `params`, `options` and every other method refer to -- receive the local planes.  None (the default): `contexts`
-    ingest themselves."""
+    ingest themselves.
+    rank = (radius, what) makes the run iterate on rank planes of the ingested planes -- a median against impulse noise, a top-hat
+    against a shading ramp (check_rank; cvh_rank_planes_batch) -- in source contexts of its own, as local= does.  With both given the
+    rank filter runs FIRST, into `ranked`, contexts of the filter's channels, and local= works on its result."""
     levels = 1
     colour = None
     local = None
+    rank = None
     sources = ()
+    ranked = ()
 
     @property
     def run_channels(self):
-        """channels of the planes the run iterates on: the ingested ones', or with local= what its codes make of them"""
-        return self.local[2] if self.local else self.channels
+        """channels of the planes the run iterates on: the ingested ones', or with rank= and local= what their codes make of them"""
+        return self.local[2] if self.local else self.rank[2] if self.rank else self.channels
 
-    def __init__(self, n, h, w, channels=1, params=None, device=0, options=None, levels=1, colour=None, order="rgb", local=None):
+    def __init__(self, n, h, w, channels=1, params=None, device=0, options=None, levels=1, colour=None, order="rgb", local=None, rank=None):
         if n < 1:
             raise ValueError(f"n must be >= 1, got {n}")
         shapes = check_levels(levels, h, w)
         self.colour, self.order = check_colour(colour, order, channels)
-        self.local = check_local(local, channels)
+        self.rank = check_rank(rank, channels)
+        self.local = check_local(local, self.rank[2] if self.rank else channels)
         self.n, self.h, self.w, self.channels, self.levels = n, h, w, channels, levels
         self.sources = []
+        self.ranked = []
         self.device = _device_index(device)
         self.thresholds = None   # Otsu's thresholds of the last segment(init="otsu")
         self.level_steps = None  # levels > 1: the iterations of the last segment() per member and level, finest first
@@ -201,8 +227,10 @@ class Segmenter:
                         self.contexts.append(ctx)
                     for key, value in (options or {}).items():
                         ctx.set_option(key, value)
-                if self.local:
+                if self.local or self.rank:
                     self.sources.append(capi.Context(h, w, channels, None, self.device))
+                if self.local and self.rank:
+                    self.ranked.append(capi.Context(h, w, self.rank[2], None, self.device))
         except Exception:
             self.close()
             raise
@@ -211,11 +239,12 @@ class Segmenter:
         for pyr in self.pyramids:
             for ctx in pyr:
                 ctx.close()
-        for ctx in self.sources:
+        for ctx in list(self.sources) + list(self.ranked):
             ctx.close()
         self.contexts = []
         self.pyramids = []
         self.sources = []
+        self.ranked = []
 
     def __enter__(self):
         return self
@@ -250,6 +279,8 @@ class Segmenter:
         local (the constructor's): the images are ingested, smoothed and converted in `sources`; ONE cvh_local_planes_batch then writes the
         planes the run iterates on into `contexts`, BEFORE the restricts, the start and the run.  "otsu" and ("threshold", t) see the
         LOCAL planes, and images() returns them; masks come out as before.
+        rank (the constructor's): as local, with ONE cvh_rank_planes_batch; "otsu" and ("threshold", t) see the RANK planes.  With both,
+        the rank call writes into `ranked` and the local call reads from there.
         energy_every = K > 0 runs segments of K iterations with the energy of the members still iterating taken after each
         (capi.run_batch_monitored, one cvh_energy_batch per segment; max_steps stays the total budget) and stores the series in
         self.energy_series; 0 takes none and leaves self.energy_series None.  It is a ValueError with levels > 1 or reinit_every > 0.
@@ -282,15 +313,17 @@ class Segmenter:
             raise ValueError("perona_malik must be (K, L, T)")
         stream = self._stream()
         self.energy_series = None
-        ingested = self.sources if self.local else self.contexts
+        ingested = self.sources if (self.local or self.rank) else self.contexts
         capi.set_image_device_batch(ingested, [images[i].data_ptr() for i in range(self.n)], layout, stream)
         if perona_malik is not None:
             K, L, T = perona_malik
             capi.perona_malik_batch(ingested, K, L, T)
         if self.colour is not None:
             capi.convert_colour_batch(ingested, self.colour, self.order)
+        if self.rank:
+            capi.rank_planes_batch(self.sources, self.ranked if self.local else self.contexts, self.rank[0], self.rank[1])
         if self.local:
-            capi.local_planes_batch(self.sources, self.contexts, self.local[0], self.local[1])
+            capi.local_planes_batch(self.ranked if self.rank else self.sources, self.contexts, self.local[0], self.local[1])
         first = self.contexts   # the level the start is built on
         if self.levels > 1:
             for k in range(self.levels - 1):
@@ -446,7 +479,7 @@ class Segmenter:
 
     def images(self):
         """The members' planes as they are now (after Perona-Malik: the smoothed image; with colour=: the converted planes of the last
-        segment(), (Y, Cr, Cb) or (Y, U, V); with local=: the local planes the run iterates on), (N, H, W) or (N, C, H, W) uint8."""
+        segment(), (Y, Cr, Cb) or (Y, U, V); with local= / rank=: the local / rank planes the run iterates on), (N, H, W) or (N, C, H, W) uint8."""
         shape = (self.n, self.h, self.w) if self.run_channels == 1 else (self.n, self.run_channels, self.h, self.w)
         out = torch.empty(shape, dtype=torch.uint8, device=torch.device("cuda", self.device))
         for i, ctx in enumerate(self.contexts):

@@ -656,6 +656,74 @@ int cvh_local_planes(cvh_context *src, cvh_context *dst, int radius, const int *
 int cvh_local_planes_batch(cvh_context *const *srcs, cvh_context *const *dsts, int n,
                            const int *radius /* n */, const int *what /* CVH_MAX_CHANNELS per pair */);
 
+/* ---- Rank planes --------------------------------------------------------------------------------------------------------------
+ * Two failures of a model that separates regions by their global means have classical answers in rank filters.  Impulse noise: an
+ * isolated 0 or 255 pixel survives Perona-Malik as an edge; a median removes it.  Uneven illumination of a grey image: the run
+ * segments the shading ramp, not the objects; the white top-hat -- the image minus its grey opening by a window wider than the
+ * objects -- removes the ramp.  These calls write such planes on the device -- what a caller otherwise does with cvh_get_image, a
+ * host filter and cvh_set_image.  The reference has no code for this; the definition below IS the contract.
+ *   Pairs.  Exactly as "Local statistics": src and dst are different contexts of the same h x w on the same device; each has 1 or 3
+ *          channels, independently.  Plane k of dst becomes f_what[k] of plane min(k, C_src - 1) of src, taken as the planes are now.
+ *          Entries of `what` at k >= C_dst are ignored.
+ *   Definition.  For pixel (r, c) and radius R the window is rows max(r - R, 0) .. min(r + R, h - 1) and columns max(c - R, 0) ..
+ *          min(c + R, w - 1): truncated at the border, nothing is padded.  With n the window's pixel count and s[0] <= .. <= s[n-1]
+ *          its bytes sorted:
+ *              CVH_RANK_COPY    p
+ *              CVH_RANK_MIN     s[0]
+ *              CVH_RANK_MAX     s[n-1]
+ *              CVH_RANK_MEDIAN  s[(n-1)/2]                            the lower median under floor division
+ *              CVH_RANK_OPEN    MAX_R(MIN_R(p))                       both windows truncated as above
+ *              CVH_RANK_CLOSE   MIN_R(MAX_R(p))
+ *              CVH_RANK_TOPHAT  p - OPEN
+ *              CVH_RANK_BOTHAT  CLOSE - p
+ *          Truncated MIN and MAX are an adjoint erosion and dilation on the plane's own domain, so OPEN <= p <= CLOSE at every
+ *          pixel, and TOPHAT and BOTHAT need no clamp.  R = 0 gives p for the first six codes and 0 for the two hats; a constant
+ *          plane gives the constant and 0.  n <= 225 at R <= CVH_RANK_MEDIAN_RADIUS_MAX, so a count of window samples fits a byte:
+ *          that is why the median's limit is 7.  The window is a square; there is no disk-shaped grey structuring element.
+ *   State. As "Local statistics", word for word: dst is left exactly as cvh_set_image of those bytes leaves it -- planes, sums, stop
+ *          norm, validity flags; a level set it already has stays as cvh_set_image leaves it; its iterations in flight are settled
+ *          first.  src is only read: level set, run state, sums and options are untouched, its iterations in flight stay in flight,
+ *          and a run continued after the call is bit-identical to one without.
+ * The *_batch form takes n pairs (pair i = srcs[i], dsts[i], radius[i], what[CVH_MAX_CHANNELS * i ..]) of any mix of shapes, channel
+ * counts, radii and codes in ONE set of launches on the stream of pair 0's destination, ordered after everything already enqueued on
+ * the stream of every listed context and before anything enqueued on them later; one host wait per call, for the sums (one channel
+ * summed on the device, three channels fetched and summed on the host behind that wait).  The single form is the batch with n = 1; a
+ * member alone or in any batch gets the same bytes.
+ * How (chan_vese_amd/csrc/rank_kernels.hip): MIN and MAX are separable, a row pass then a column pass, each by van Herk / Gil-Werman
+ * (running extrema from both ends of blocks of 2 R + 1), so the work per pixel does not grow with R; OPEN and CLOSE are four passes,
+ * the hats subtract in the last one; a plane that several codes of one member derive from is eroded and dilated once.  The median for
+ * R = 1 .. 7 keeps a histogram of 256 byte counters per lane in LDS while the lane marches down a column: work per pixel O(R).
+ * Between the passes the planes live at one byte per pixel in a workspace the destination owns (7 byte planes per plane of the
+ * destination, allocated by its first call that takes anything but copies, freed by cvh_destroy); it shares no storage with the
+ * workspace of "Local statistics".  A call of COPY planes alone launches only the writer.
+ * Cost, MEASURED ONCE: one run of tools/rank_probe.py on an MI355X (profiles/r20_rank/; host clock around a call and
+ * its wait, 20 calls after 3), 1 -> 1 at 1024^2 / 2048^2 / 4096^2: MAX at R = 2 takes 98 / 107 / 190 us and at R = 127 377 / 394 /
+ * 511 us, TOPHAT 136 / 163 / 327 us and 680 / 719 / 939 us -- NOT flat in R: the work per pixel is, but a column band is 255 rows tall
+ * at R = 127 and the column passes run out of parallel waves.  MEDIAN grows about linearly with R: 112 / 126 / 345 us at R = 1, 215 /
+ * 243 / 869 us at R = 7.  One CSV iteration of the same plane: 8 / 14 / 67 us.  The round trip each call replaces (cvh_get_image, a
+ * scipy filter, cvh_set_image) took 12 ms - 30 s in the same run: every call measured beats it.  A three-channel destination adds the
+ * stop norm the host takes behind the wait (1 - 14 ms), as for every call that replaces three planes.  Device times of the kernels
+ * alone were not taken.
+ * CVH_ERR_ARG: everything cvh_local_planes_batch refuses, with the radius bound 0 .. CVH_RANK_RADIUS_MAX -- NULL lists or members,
+ * n < 1, a context listed more than once across both lists (src == dst included), contexts on different devices, different shapes
+ * within a pair, h*w >= 2^32 --; a `what` entry below C_dst outside 0 .. 7; a pair with a MEDIAN entry below C_dst and a radius above
+ * CVH_RANK_MEDIAN_RADIUS_MAX.  CVH_ERR_STATE: a src without an image.  Checked for every pair before anything is launched; the message
+ * names the pair index and is cvh_last_error(NULL)'s (and pair 0's destination's, once the lists hold no NULL); the contexts stay
+ * usable and their planes unchanged. */
+#define CVH_RANK_COPY   0
+#define CVH_RANK_MIN    1
+#define CVH_RANK_MAX    2
+#define CVH_RANK_MEDIAN 3
+#define CVH_RANK_OPEN   4
+#define CVH_RANK_CLOSE  5
+#define CVH_RANK_TOPHAT 6
+#define CVH_RANK_BOTHAT 7
+#define CVH_RANK_RADIUS_MAX        127
+#define CVH_RANK_MEDIAN_RADIUS_MAX 7
+int cvh_rank_planes(cvh_context *src, cvh_context *dst, int radius, const int *what);
+int cvh_rank_planes_batch(cvh_context *const *srcs, cvh_context *const *dsts, int n,
+                          const int *radius /* n */, const int *what /* CVH_MAX_CHANNELS per pair */);
+
 /* ---- Energy ------------------------------------------------------------------------------------------------------------------
  * The library minimises the Chan-Sandberg-Vese functional
  *     E(u) = mu Length + nu Area + (1/C) sum_k [ lambda1_k int (I_k - c1_k)^2 H_eps(u) + lambda2_k int (I_k - c2_k)^2 (1 - H_eps(u)) ];
