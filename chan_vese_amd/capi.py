@@ -654,90 +654,95 @@ def luma_image_batch(srcs, dsts, order="bgr"):
     _batch_chk(lib().cvh_luma_image_batch(_member_array(srcs), _member_array(dsts), len(srcs), order))
 
 
-def local_what_codes(what):
-    """A name -- "mean", "dev" (every plane) or "stack" (copy, mean, deviation) -- or 1 to 3 codes -> the three codes cvh_local_planes
-    reads; entries a destination has no plane for are ignored by the library and filled with LOCAL_COPY here.  ValueError for anything
-    else.  Calls nothing in the library."""
+def _what_codes(what, kind, names, top, range_text):
+    """A name out of `names` or 1 to 3 codes 0 .. top -> three codes, filled with 0 (the copy)."""
     if isinstance(what, str):
-        if what.lower() not in LOCAL_WHATS:
-            raise ValueError(f"local statistic must be one of {sorted(LOCAL_WHATS)} or a tuple of codes, got {what!r}")
-        return LOCAL_WHATS[what.lower()]
+        if what.lower() not in names:
+            raise ValueError(f"{kind} must be one of {sorted(names)} or a tuple of codes, got {what!r}")
+        named = names[what.lower()]
+        return named if isinstance(named, tuple) else (named,) * 3
     try:
         codes = tuple(what)
     except TypeError:
         codes = None
-    if not codes or len(codes) > 3 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v not in (0, 1, 2) for v in codes):
-        raise ValueError(f"local statistic must be one of {sorted(LOCAL_WHATS)} or 1 to 3 codes out of LOCAL_COPY (0), LOCAL_MEAN (1), "
-                         f"LOCAL_DEV (2), got {what!r}")
-    return tuple(int(v) for v in codes) + (LOCAL_COPY,) * (3 - len(codes))
+    if not codes or len(codes) > 3 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= top for v in codes):
+        raise ValueError(f"{kind} must be one of {sorted(names)} or 1 to 3 codes out of {range_text}, got {what!r}")
+    return tuple(int(v) for v in codes) + (0,) * (3 - len(codes))
+
+
+def _radius(radius, kind, top, note=""):
+    """An integer 0 .. top."""
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 0 <= radius <= top:
+        raise ValueError(f"{kind} radius must be an integer 0 .. {top}{note}, got {radius!r}")
+    return int(radius)
+
+
+def local_what_codes(what):
+    """A name -- "mean", "dev" (every plane) or "stack" (copy, mean, deviation) -- or 1 to 3 codes -> the three codes cvh_local_planes
+    reads; entries a destination has no plane for are ignored by the library and filled with LOCAL_COPY here.  ValueError for anything
+    else.  Calls nothing in the library."""
+    return _what_codes(what, "local statistic", LOCAL_WHATS, LOCAL_DEV, "LOCAL_COPY (0), LOCAL_MEAN (1), LOCAL_DEV (2)")
 
 
 def local_radius(radius):
     """An integer 0 .. LOCAL_RADIUS_MAX; ValueError for anything else.  Calls nothing in the library."""
-    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 0 <= radius <= LOCAL_RADIUS_MAX:
-        raise ValueError(f"local radius must be an integer 0 .. {LOCAL_RADIUS_MAX}, got {radius!r}")
-    return int(radius)
-
-
-def _is_one_what(what):
-    return isinstance(what, str) or (len(what) > 0 and not isinstance(what[0], (str, tuple, list)))
-
-
-def local_planes_batch(srcs, dsts, radius, what):
-    """cvh_local_planes_batch: Context.local_planes_to for n pairs (any mix of shapes, channel counts, radii and codes) with one set of
-    launches.  A scalar `radius` and ONE `what` (a name or a tuple of codes) go to every pair; else one per pair."""
-    srcs, dsts = _pairs(srcs, dsts)
-    n = len(srcs)
-    radii = [radius] * n if isinstance(radius, (int, np.integer)) else list(radius)
-    whats = [what] * n if _is_one_what(what) else list(what)
-    if len(radii) != n or len(whats) != n:
-        raise ValueError(f"{n} pairs need {n} radii and {n} codes tuples (or one of each), got {len(radii)} and {len(whats)}")
-    radii = (C.c_int * max(n, 1))(*[local_radius(r) for r in radii])
-    flat = [v for w in whats for v in local_what_codes(w)]
-    _batch_chk(lib().cvh_local_planes_batch(_member_array(srcs), _member_array(dsts), n, radii, (C.c_int * max(3 * n, 1))(*flat)))
+    return _radius(radius, "local", LOCAL_RADIUS_MAX)
 
 
 def rank_what_codes(what):
     """A name -- "min", "max", "median", "open", "close", "tophat", "bothat" (every plane) -- or 1 to 3 codes -> the three codes
     cvh_rank_planes reads; entries a destination has no plane for are ignored by the library and filled with RANK_COPY here.
     ValueError for anything else.  Calls nothing in the library."""
-    if isinstance(what, str):
-        if what.lower() not in RANK_WHATS:
-            raise ValueError(f"rank filter must be one of {sorted(RANK_WHATS)} or a tuple of codes, got {what!r}")
-        return (RANK_WHATS[what.lower()],) * 3
-    try:
-        codes = tuple(what)
-    except TypeError:
-        codes = None
-    if not codes or len(codes) > 3 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= 7 for v in codes):
-        raise ValueError(f"rank filter must be one of {sorted(RANK_WHATS)} or 1 to 3 codes out of RANK_COPY (0) .. RANK_BOTHAT (7), "
-                         f"got {what!r}")
-    return tuple(int(v) for v in codes) + (RANK_COPY,) * (3 - len(codes))
+    return _what_codes(what, "rank filter", RANK_WHATS, RANK_BOTHAT, "RANK_COPY (0) .. RANK_BOTHAT (7)")
 
 
 def rank_radius(radius, codes=()):
     """An integer 0 .. RANK_RADIUS_MAX, and 0 .. RANK_MEDIAN_RADIUS_MAX where `codes` hold RANK_MEDIAN; ValueError for anything else.
     Calls nothing in the library."""
-    top = RANK_MEDIAN_RADIUS_MAX if RANK_MEDIAN in tuple(codes) else RANK_RADIUS_MAX
-    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 0 <= radius <= top:
-        raise ValueError(f"rank radius must be an integer 0 .. {top}{' for a median' if top == RANK_MEDIAN_RADIUS_MAX else ''}, got {radius!r}")
-    return int(radius)
+    if RANK_MEDIAN in tuple(codes):
+        return _radius(radius, "rank", RANK_MEDIAN_RADIUS_MAX, " for a median")
+    return _radius(radius, "rank", RANK_RADIUS_MAX)
 
 
-def rank_planes_batch(srcs, dsts, radius, what):
-    """cvh_rank_planes_batch: Context.rank_planes_to for n pairs (any mix of shapes, channel counts, radii and codes) with one set of
-    launches.  A scalar `radius` and ONE `what` (a name or a tuple of codes) go to every pair; else one per pair.  A median's radius
-    limit is checked against the codes a destination has planes for."""
+def _is_one_what(what):
+    return isinstance(what, str) or (len(what) > 0 and not isinstance(what[0], (str, tuple, list)))
+
+
+def _window_args(family, radii, whats, dsts):
+    """(radii, codes per pair) of the pairs of a windowed-plane family, checked.  "local": every radius, then every what.  "rank": every
+    what, then every radius against the codes its destination has planes for (the median's limit)."""
+    if family == "local":
+        radii = [local_radius(r) for r in radii]
+        return radii, [local_what_codes(w) for w in whats]
+    codes = [rank_what_codes(w) for w in whats]
+    return [rank_radius(r, c[:getattr(d, "channels", 3)]) for r, c, d in zip(radii, codes, dsts)], codes
+
+
+def _window_planes_batch(family, srcs, dsts, radius, what):
+    """cvh_<family>_planes_batch: a scalar `radius` and ONE `what` go to every pair, else one per pair."""
     srcs, dsts = _pairs(srcs, dsts)
     n = len(srcs)
     radii = [radius] * n if isinstance(radius, (int, np.integer)) else list(radius)
     whats = [what] * n if _is_one_what(what) else list(what)
     if len(radii) != n or len(whats) != n:
         raise ValueError(f"{n} pairs need {n} radii and {n} codes tuples (or one of each), got {len(radii)} and {len(whats)}")
-    codes = [rank_what_codes(w) for w in whats]
-    radii = (C.c_int * max(n, 1))(*[rank_radius(r, c[:getattr(d, "channels", 3)]) for r, c, d in zip(radii, codes, dsts)])
+    radii, codes = _window_args(family, radii, whats, dsts)
     flat = [v for c in codes for v in c]
-    _batch_chk(lib().cvh_rank_planes_batch(_member_array(srcs), _member_array(dsts), n, radii, (C.c_int * max(3 * n, 1))(*flat)))
+    call = getattr(lib(), f"cvh_{family}_planes_batch")
+    _batch_chk(call(_member_array(srcs), _member_array(dsts), n, (C.c_int * max(n, 1))(*radii), (C.c_int * max(3 * n, 1))(*flat)))
+
+
+def local_planes_batch(srcs, dsts, radius, what):
+    """cvh_local_planes_batch: Context.local_planes_to for n pairs (any mix of shapes, channel counts, radii and codes) with one set of
+    launches.  A scalar `radius` and ONE `what` (a name or a tuple of codes) go to every pair; else one per pair."""
+    _window_planes_batch("local", srcs, dsts, radius, what)
+
+
+def rank_planes_batch(srcs, dsts, radius, what):
+    """cvh_rank_planes_batch: Context.rank_planes_to for n pairs (any mix of shapes, channel counts, radii and codes) with one set of
+    launches.  A scalar `radius` and ONE `what` (a name or a tuple of codes) go to every pair; else one per pair.  A median's radius
+    limit is checked against the codes a destination has planes for."""
+    _window_planes_batch("rank", srcs, dsts, radius, what)
 
 
 def _coarse_to_fine(pyramids, max_steps, run):
@@ -1219,21 +1224,22 @@ class Context:
         order = order_code(order)
         _batch_chk(self._L.cvh_luma_image(self._h, dst._h, order))
 
+    def _window_planes_to(self, family, dst, radius, what):
+        radii, codes = _window_args(family, [radius], [what], [dst])   # (checked before the library is reached)
+        _batch_chk(getattr(self._L, f"cvh_{family}_planes")(self._h, dst._h, radii[0], (C.c_int * 3)(*codes[0])))
+
     def local_planes_to(self, dst, radius, what):
         """cvh_local_planes: plane k of `dst` (another context of the same shape, 1 or 3 channels) becomes the copy, the local mean or
         the local deviation over the (2 radius + 1)^2 window of plane min(k, channels - 1) of this context, which is only read.  `what`
         is "mean", "dev", "stack" or a tuple of LOCAL_COPY / LOCAL_MEAN / LOCAL_DEV; `dst` is left as set_image of those planes."""
-        radius, codes = local_radius(radius), local_what_codes(what)
-        _batch_chk(self._L.cvh_local_planes(self._h, dst._h, radius, (C.c_int * 3)(*codes)))
+        self._window_planes_to("local", dst, radius, what)
 
     def rank_planes_to(self, dst, radius, what):
         """cvh_rank_planes: plane k of `dst` (another context of the same shape, 1 or 3 channels) becomes the copy, minimum, maximum,
         median, opening, closing, white or black top-hat over the (2 radius + 1)^2 window of plane min(k, channels - 1) of this context,
         which is only read.  `what` is "min", "max", "median", "open", "close", "tophat", "bothat" or a tuple of RANK_* codes; `dst` is
         left as set_image of those planes."""
-        codes = rank_what_codes(what)
-        radius = rank_radius(radius, codes[:getattr(dst, "channels", 3)])
-        _batch_chk(self._L.cvh_rank_planes(self._h, dst._h, radius, (C.c_int * 3)(*codes)))
+        self._window_planes_to("rank", dst, radius, what)
 
     def reinit(self):
         """cvh_reinit: the level set becomes the exact signed distance to the pixel-edge front of its own mask, on the device.

@@ -4,7 +4,7 @@
 // device buffers), pm_run.hip (Perona-Malik), io_run.hip (device-memory I/O, reinitialisation, and the scaffolds of the member-table
 // calls: MemberCall with its further waits, write_planes, the pointer checks, the launch counters), init_run.hip (device-side initial
 // level sets), components_run.hip (connected components, and MaskSource: the raw or cleaned mask every mask-derived call starts from),
-// pyramid_run.hip (coarse-to-fine), colour_run.hip (colour spaces), local_run.hip (local statistics), rank_run.hip (rank planes), energy_run.hip (the functional's terms), score_run.hip (mask scores),
+// pyramid_run.hip (coarse-to-fine), colour_run.hip (colour spaces), window_run.hip (local statistics and rank planes: the windowed-plane calls), energy_run.hip (the functional's terms), score_run.hip (mask scores),
 // morph_run.hip (mask morphology, mask starts), measure_run.hip (component measures), contour_run.hip (contours), overlap_run.hip
 // (component overlaps), debug_exports.hip (diagnostics).  Kernel sources do not include it.
 #pragma once
@@ -159,10 +159,10 @@ struct cvh_context {   // opaque to callers; four groups
                                  // host form stages (5.5 bytes per pixel): allocated by the first call, kept -- not part of live_footprint either
   void *d_morph = nullptr;       // workspace of cvh_get_mask_morph* / cvh_morph_levelset* / cvh_init_mask (morph_run.hip): two planes of band words, the
                                  // 16-bit distance field and a byte plane (3.25 bytes per pixel): allocated by the first call, kept -- not part of live_footprint either
-  void *d_local = nullptr;       // workspace of cvh_local_planes* (local_run.hip) as their DESTINATION: the row sums of the source planes it reads, a
+  void *d_local = nullptr;       // workspace of cvh_local_planes* (window_run.hip) as their DESTINATION: the row sums of the source planes it reads, a
                                  // slot of 6 bytes per pixel per plane of this context: allocated by the first call that takes a mean or a
                                  // deviation, kept -- not part of live_footprint either
-  void *d_rank = nullptr;        // workspace of cvh_rank_planes* (rank_run.hip) as their DESTINATION: CVH_RANK_SLOTS byte planes per plane of this context
+  void *d_rank = nullptr;        // workspace of cvh_rank_planes* (window_run.hip) as their DESTINATION: CVH_RANK_SLOTS byte planes per plane of this context
                                  // (7 bytes per pixel and plane): allocated by the first call that takes anything but copies, kept -- not part
                                  // of live_footprint either
   DeviceTable overlap;           // cvh_overlaps* (overlap_run.hip): overlap.count slots of the pair table and overlap.count / 2 rows behind them (24 bytes
@@ -272,8 +272,8 @@ void free_table(DeviceTable *t);
 // launches of cvh_restrict_image* / cvh_prolong_levelset*, those of cvh_convert_colour* / cvh_luma_image*, and the launch sets (term pass and
 // reduce pass for all members) of cvh_energy*, the launch sets (four kernels for all members) of cvh_score_mask*, and the launch sets (every
 // kernel of the call, for all members) of cvh_get_mask_morph* / cvh_morph_levelset* / cvh_init_mask*, and the pair launches of cvh_overlaps*
-// (one per call, and one more each time a member's table had to grow), and the launch sets (row pass and column pass for all pairs) of
-// cvh_local_planes*, and the launch sets (every pass for all pairs) of cvh_rank_planes*
+// (one per call, and one more each time a member's table had to grow), and the launch sets (every pass of the family for all pairs) of
+// cvh_local_planes* and of cvh_rank_planes* (window_run.hip: a Family names its counter)
 enum LaunchCounter { kReinitLaunchSets, kPyramidLaunches, kColourLaunches, kEnergyLaunchSets, kScoreLaunchSets, kMorphLaunchSets, kOverlapLaunchSets, kLocalLaunchSets, kRankLaunchSets, kLaunchCounters };
 extern std::atomic<unsigned long> g_launches[kLaunchCounters];
 

@@ -312,37 +312,38 @@ hipError_t cvh_launch_prolong(const CvhIoMember *tab, int nmem, unsigned grid, h
 unsigned cvh_colour_blocks(size_t n);
 hipError_t cvh_launch_colour_convert(const CvhIoMember *tab, int nmem, unsigned grid, int space, int order, int inverse, hipStream_t s);
 hipError_t cvh_launch_colour_luma(const CvhIoMember *tab, int nmem, unsigned grid, int order, hipStream_t s);
-// local statistics (local_kernels.hip).  src / src_stride the planes of the source context and w2 their number; plane[] the member's C
-// planes (written), sums as the ingest's; h2 the radius; interleaved the member's codes, what[k] << 2 k; dst the member's workspace: a
-// slot of cvh_local_slot_bytes(h, w) per source plane, the row sums of p^2 (32-bit) and behind them those of p (16-bit), rows
-// cvh_local_pitch(w) entries apart.  Two launches over ONE table: in the row pass a workgroup takes a row segment of
-// CVH_LOCAL_SEGMENT columns per trip, in the column pass a wave takes CVH_LOCAL_BAND rows x CVH_LOCAL_STRIP columns per trip.
-#define CVH_LOCAL_SEGMENT 1024
-#define CVH_LOCAL_BAND 32
-#define CVH_LOCAL_STRIP 256
-size_t cvh_local_pitch(int w);
-size_t cvh_local_slot_bytes(int h, int w);
-unsigned cvh_local_blocks(int h, int w, int planes_read);
-hipError_t cvh_launch_local(const CvhIoMember *tab, int nmem, unsigned grid, bool any_rows, hipStream_t s);
-// rank planes (rank_kernels.hip).  src / src_stride the planes of the source context and w2 their number; plane[] the member's C planes
-// (written), sums as the ingest's; h2 the radius; interleaved the member's codes, what[k] << 3 k; dst the member's workspace:
-// CVH_RANK_SLOTS byte planes of cvh_rank_slot_bytes(h, w) per source plane, rows cvh_rank_pitch(w) bytes apart (rank_kernels.hip says
-// which is which).  Up to five launches over ONE table, chosen by `passes`: the row pass of every chain (CVH_RANK_PASS_ROWS), the column
-// and the second row pass of the chains that run twice (CVH_RANK_PASS_TWICE), the median (CVH_RANK_PASS_MEDIAN), and always the final
-// pass, which writes the planes.  The row pass takes a row segment of CVH_RANK_SEGMENT columns per workgroup and trip, the column passes
-// cvh_rank_band_rows(R, CVH_RANK_BAND) rows x CVH_RANK_STRIP columns per wave and trip (rank_math.h), the median CVH_RANK_MEDIAN_BAND
-// rows x CVH_RANK_MEDIAN_STRIP columns per wave and trip.
+// windowed planes (window_device.h; local_kernels.hip, rank_kernels.hip).  src / src_stride the planes of the source context and w2
+// their number; plane[] the member's C planes (written), sums as the ingest's; h2 the radius; interleaved the member's codes, a family's
+// bits per code apart; dst the member's workspace, rows cvh_window_pitch(w) entries apart.  A family's launches read ONE table: in a
+// row pass a workgroup takes a row segment of CVH_WINDOW_SEGMENT columns per trip, in a column pass a wave takes a band of rows
+// (CVH_WINDOW_BAND, or a family's own) x CVH_WINDOW_STRIP columns per trip.
+#define CVH_WINDOW_SEGMENT 1024
+#define CVH_WINDOW_BAND 32
+#define CVH_WINDOW_STRIP 256
+// (the geometry's earlier names, used by no code: tests/test_rank_api.py pins the two CVH_RANK_ lines -- the rank passes take the local ones' geometry)
+#define CVH_LOCAL_SEGMENT CVH_WINDOW_SEGMENT
+#define CVH_LOCAL_BAND CVH_WINDOW_BAND
 #define CVH_RANK_SEGMENT CVH_LOCAL_SEGMENT
 #define CVH_RANK_BAND CVH_LOCAL_BAND
-#define CVH_RANK_STRIP CVH_LOCAL_STRIP
+__host__ __device__ constexpr size_t cvh_window_pitch(int w) { return ((size_t)w + 3) & ~(size_t)3; }   // whole words per lane of a column pass
+// local statistics (local_kernels.hip): codes what[k] << 2 k; the workspace a slot of cvh_local_slot_bytes(h, w) per source plane, the
+// row sums of p^2 (32-bit) and behind them those of p (16-bit).  Two launches: the row pass where a pair has `passes`, and the column pass.
+__host__ __device__ constexpr size_t cvh_local_slot_bytes(int h, int w) { return (6 * (size_t)h * cvh_window_pitch(w) + 15) & ~(size_t)15; }
+unsigned cvh_local_blocks(int h, int w, int planes_read);
+hipError_t cvh_launch_local(const CvhIoMember *tab, int nmem, unsigned grid, unsigned passes, hipStream_t s);
+// rank planes (rank_kernels.hip): codes what[k] << 3 k; the workspace CVH_RANK_SLOTS byte planes of cvh_rank_slot_bytes(h, w) per source
+// plane (rank_kernels.hip says which is which).  Up to five launches, chosen by `passes`: the row pass of every chain
+// (CVH_RANK_PASS_ROWS), the column and the second row pass of the chains that run twice (CVH_RANK_PASS_TWICE), the median
+// (CVH_RANK_PASS_MEDIAN), and always the final pass, which writes the planes.  The column passes' band is
+// cvh_rank_band_rows(R, CVH_WINDOW_BAND) rows (rank_math.h); the median takes CVH_RANK_MEDIAN_BAND rows x CVH_RANK_MEDIAN_STRIP columns
+// per wave and trip.
 #define CVH_RANK_MEDIAN_BAND 32
 #define CVH_RANK_MEDIAN_STRIP 64
 #define CVH_RANK_SLOTS 7
 #define CVH_RANK_PASS_ROWS 1u
 #define CVH_RANK_PASS_TWICE 2u
 #define CVH_RANK_PASS_MEDIAN 4u
-size_t cvh_rank_pitch(int w);
-size_t cvh_rank_slot_bytes(int h, int w);
+__host__ __device__ constexpr size_t cvh_rank_slot_bytes(int h, int w) { return ((size_t)h * cvh_window_pitch(w) + 255) & ~(size_t)255; }
 unsigned cvh_rank_blocks(int h, int w, int R, int row_jobs, int median_planes);
 hipError_t cvh_launch_rank(const CvhIoMember *tab, int nmem, unsigned grid, unsigned passes, hipStream_t s);
 // energy (energy_kernels.hip).  src the level set, src2 the CvhState that holds its means, plane[] the planes, dst the member's item rows

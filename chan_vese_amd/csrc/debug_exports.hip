@@ -151,12 +151,12 @@ extern "C" unsigned long cvh_debug_pyramid_launches(void) { return g_launches[kP
 extern "C" unsigned long cvh_debug_colour_launches(void) { return g_launches[kColourLaunches].load(); }
 extern "C" int cvh_debug_colour_block_pixels(void) { return CVH_COLOUR_BLOCK_PIXELS; }
 // Diagnostics (not part of include/chanvese_hip.h) of cvh_local_planes*: launch sets so far in this process (a batch of n pairs is one:
-// the row pass, where a pair takes a mean or a deviation, and the column pass); the geometry of local_kernels.hip, from which
+// the row pass, where a pair takes a mean or a deviation, and the column pass); the windowed passes' geometry (CVH_WINDOW_*), from which
 // tests/local_util.py derives the seam shapes -- out[0] rows of a band, out[1] columns of a strip, out[2] columns of a row segment --;
 // and the per-pixel arithmetic of local_math.h compiled for the host: the floor square root (q <= 65025), and MEAN and DEV of a
 // window of n pixels with sum S and sum of squares Q (tests/test_local_restatement.py holds both against Python integers)
 extern "C" unsigned long cvh_debug_local_launch_sets(void) { return g_launches[kLocalLaunchSets].load(); }
-extern "C" void cvh_debug_local_geometry(int *out) { out[0] = CVH_LOCAL_BAND; out[1] = CVH_LOCAL_STRIP; out[2] = CVH_LOCAL_SEGMENT; }
+extern "C" void cvh_debug_local_geometry(int *out) { out[0] = CVH_WINDOW_BAND; out[1] = CVH_WINDOW_STRIP; out[2] = CVH_WINDOW_SEGMENT; }
 extern "C" unsigned cvh_debug_local_isqrt(unsigned q) { return cvh_local_isqrt(q); }
 extern "C" void cvh_debug_local_stats(unsigned n, unsigned S, unsigned Q, unsigned *mean, unsigned *dev)
 {
@@ -164,18 +164,18 @@ extern "C" void cvh_debug_local_stats(unsigned n, unsigned S, unsigned Q, unsign
   *dev = cvh_local_dev(n, S, Q);
 }
 // Diagnostics (not part of include/chanvese_hip.h) of cvh_rank_planes*: launch sets so far in this process (a batch of n pairs is one: up to
-// five launches); the geometry of rank_kernels.hip, from which tests/rank_util.py derives the seam shapes -- out[0] rows of a column band
+// five launches); the same geometry and the median's, from which tests/rank_util.py derives the seam shapes -- out[0] rows of a column band
 // at R = 0 (at radius R: cvh_debug_rank_band_rows), out[1] columns of a strip, out[2] columns of a row segment, out[3] rows and out[4]
 // columns of a median trip --; and the integer arithmetic of rank_math.h compiled for the host: a code's chain and whether it runs twice,
 // the rows of a band at a radius, the rank of the lower median, and the walk over sixteen packed byte counters
 extern "C" unsigned long cvh_debug_rank_launch_sets(void) { return g_launches[kRankLaunchSets].load(); }
 extern "C" void cvh_debug_rank_geometry(int *out)
 {
-  out[0] = CVH_RANK_BAND; out[1] = CVH_RANK_STRIP; out[2] = CVH_RANK_SEGMENT; out[3] = CVH_RANK_MEDIAN_BAND; out[4] = CVH_RANK_MEDIAN_STRIP;
+  out[0] = CVH_WINDOW_BAND; out[1] = CVH_WINDOW_STRIP; out[2] = CVH_WINDOW_SEGMENT; out[3] = CVH_RANK_MEDIAN_BAND; out[4] = CVH_RANK_MEDIAN_STRIP;
 }
 extern "C" int cvh_debug_rank_chain(int code) { return cvh_rank_chain(code); }
 extern "C" int cvh_debug_rank_twice(int code) { return cvh_rank_twice(code); }
-extern "C" int cvh_debug_rank_band_rows(int R) { return cvh_rank_band_rows(R, CVH_RANK_BAND); }
+extern "C" int cvh_debug_rank_band_rows(int R) { return cvh_rank_band_rows(R, CVH_WINDOW_BAND); }
 extern "C" unsigned cvh_debug_rank_median_index(unsigned n) { return cvh_rank_median_index(n); }
 extern "C" int cvh_debug_rank_walk(const unsigned *words, unsigned *before, unsigned t) { return cvh_rank_walk(words, before, t); }
 // Diagnostic (not part of include/chanvese_hip.h): launch sets of cvh_energy / cvh_energy_batch so far in this process -- one set is the

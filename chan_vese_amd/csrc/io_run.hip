@@ -4,7 +4,7 @@
 // is a level set leaving and arriving without crossing to the host, on the same member tables and stream joins.  MemberCall (cvh_host.h)
 // is the scaffold of every member-table call, here and in init_run.hip, components_run.hip, pyramid_run.hip and colour_run.hip: staging,
 // the level-set target, the joined launch, the members' arrival, a further host wait (upload_again, wait_again).  write_planes is the one path of the calls that replace planes -- the
-// ingest here, the conversions and the luma of colour_run.hip, the local statistics of local_run.hip, the rank planes of rank_run.hip, the restrict of pyramid_run.hip -- and g_launches the one table of launch
+// ingest here, the conversions and the luma of colour_run.hip, the local statistics and the rank planes of window_run.hip, the restrict of pyramid_run.hip -- and g_launches the one table of launch
 // counters.  What a call refuses for its members or pairs is in csv_batch.hip.  cvh_init_checkerboard is a checkerboard batch of one.
 #include <memory>
 #include <thread>

@@ -1,39 +1,27 @@
 // local_kernels.hip — local mean and local deviation planes on the device (gfx950): plane k of a member is COPY, MEAN or DEV of a plane
 // of its source context over the (2 R + 1)^2 window truncated at the border (include/chanvese_hip.h, "Local statistics": exact integers,
 // local_math.h).  Batch kernels over io_run.hip's member table like colour_kernels.hip's: ONE grid serves N members of any mix of shapes,
-// channel counts, radii and codes, a member owning the workgroups first .. first + nblk - 1; both launches read the same table.
+// channel counts, radii and codes, a member owning the workgroups first .. first + nblk - 1; both launches read the same table.  The
+// passes' geometry, the staging of a row span and the sharing out of items are window_device.h's; here are the arithmetic and the writer.
 // The window sums are separable, so the work per pixel does not grow with R^2:
 //   row pass     per source plane that a MEAN or DEV plane reads, the horizontal window sums of p (16-bit) and p^2 (32-bit) go into the
-//                member's workspace.  A workgroup takes a row segment of CVH_LOCAL_SEGMENT columns per trip: the bytes of the segment and
-//                of R columns on either side are staged in LDS by aligned words, a lane adds up kRowLane consecutive bytes, a wave scan and a
-//                carry across the four waves turn that into the inclusive prefix sums of the span in LDS, and a pixel's window sum is the
-//                difference of two prefix entries.
-//   column pass  a wave takes CVH_LOCAL_BAND rows x CVH_LOCAL_STRIP columns per trip, a lane four adjacent columns.  The lane holds the
-//                vertical sums of its columns' row sums in registers (both fit 32 bits: 255^2 * 255^2 < 2^32), fills them from the
-//                2 R + 1 rows about the band's first row and marches down, adding row r + R + 1 and subtracting row r - R, both
-//                clipped; a row of the workspace is read as one 16-byte and one 8-byte piece per lane.  It writes the member's planes,
-//                the COPY planes included, four bytes per lane and row, and adds {sum p, sum p^2} of every plane written to the
-//                member's sums as the ingest does (io_device.h: exact integers, whatever the grid).
+//                member's workspace.  Of the staged span a lane adds up kRowLane consecutive bytes, a wave scan and a carry across the
+//                four waves turn that into the inclusive prefix sums of the span in LDS, and a pixel's window sum is the difference
+//                of two prefix entries.
+//   column pass  a band is kBand rows.  The lane holds the vertical sums of its columns' row sums in registers (both fit 32 bits:
+//                255^2 * 255^2 < 2^32), fills them from the 2 R + 1 rows about the band's first row and marches down, adding row
+//                r + R + 1 and subtracting row r - R, both clipped; a row of the workspace is read as one 16-byte and one 8-byte piece
+//                per lane.  It writes the member's planes, the COPY planes included.
 // The source is only read.  No kernel waits for another workgroup; the column launch follows the row launch on the same stream.
-#include "io_device.h"
+#include "window_device.h"
 #include "local_math.h"
 
 namespace {
 
-constexpr int kSegment = CVH_LOCAL_SEGMENT, kBand = CVH_LOCAL_BAND, kStrip = CVH_LOCAL_STRIP;
-constexpr int kSpan = kSegment + 2 * CVH_LOCAL_RADIUS_MAX;        // bytes a segment's window sums read at most
-constexpr int kRowLane = (kSpan + CVH_BLOCK - 1) / CVH_BLOCK;     // consecutive bytes a lane of the row pass adds up
-constexpr int kRawWords = (kSpan + 3) / 4 + 1;                    // the span as aligned words: up to 3 bytes in front of it
-static_assert(kStrip == 4 * 64, "a lane of the column pass owns four columns");
-static_assert(kBand * 4 * 65025 < (1ll << 32), "a lane's 32-bit plane sums hold one trip");
-
 typedef unsigned v2u __attribute__((ext_vector_type(2)));
-typedef unsigned u32_any __attribute__((aligned(1)));
-typedef CVH_GLOBAL const unsigned *gwords_in;
 typedef CVH_GLOBAL const uint16_t *ghalves_in;
 
 __device__ __forceinline__ int what_of(const CvhIoMember *m, int k) { return (m->interleaved >> (2 * k)) & 3; }
-__device__ __forceinline__ int source_of(const CvhIoMember *m, int k) { return min(k, m->w2 - 1); }
 
 // bit s: a MEAN or DEV plane of the member reads plane s of the source
 __device__ __forceinline__ unsigned planes_read(const CvhIoMember *m)
@@ -43,9 +31,6 @@ __device__ __forceinline__ unsigned planes_read(const CvhIoMember *m)
     if (what_of(m, k) != CVH_LOCAL_COPY) need |= 1u << source_of(m, k);
   return need;
 }
-
-__device__ __forceinline__ size_t pitch_of(int w) { return ((size_t)w + 3) & ~(size_t)3; }
-__device__ __forceinline__ size_t slot_bytes_of(int h, int w) { return (6 * (size_t)h * pitch_of(w) + 15) & ~(size_t)15; }
 
 __global__ void __launch_bounds__(CVH_BLOCK) local_rows_kernel(const CvhIoMember *tab, int nmem)
 {
@@ -57,28 +42,20 @@ __global__ void __launch_bounds__(CVH_BLOCK) local_rows_kernel(const CvhIoMember
   if (!need) return;   // (the whole workgroup)
   const int h = m->h, w = m->w, R = m->h2;
   const int nseg = (w + kSegment - 1) / kSegment;
-  const size_t pitch = pitch_of(w), slot = slot_bytes_of(h, w);
+  const size_t pitch = cvh_window_pitch(w), slot = cvh_local_slot_bytes(h, w);
   const unsigned long long per_plane = (unsigned long long)h * nseg, items = per_plane * __popc(need);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   for (unsigned long long item = blockIdx.x - m->first; item < items; item += m->nblk) {
-    const int nth = (int)(item / per_plane), r = (int)((item % per_plane) / nseg), g = (int)(item % nseg);
-    int s = 0;   // the nth plane that is read
-    for (int b = 0, seen = 0; b < CVH_MAX_CHANNELS; ++b)
-      if ((need >> b) & 1u) { if (seen == nth) s = b; ++seen; }
+    const RowItem it = row_item(item, per_plane, nseg);
+    const int r = it.r, s = nth_set_bit<CVH_MAX_CHANNELS>(need, it.nth);   // the nth plane that is read
     const gbytes_in plane = (gbytes_in)m->src + (size_t)s * m->src_stride;
-    const int c0 = g * kSegment, cend = min(c0 + kSegment, w);
-    const int first = max(c0 - R, 0), last = min(cend - 1 + R, w - 1), len = last - first + 1;   // the span: columns first .. last
-    // Aligned words that cover the span: the last one ends at or before the plane's h * w bytes rounded up to 4, inside the plane's own
-    // padding (cvh_create pads every plane to a multiple of 256 bytes)
-    const size_t a0 = (size_t)r * w + first, al = a0 & ~(size_t)3;
-    const int mis = (int)(a0 - al), nwords = (mis + len + 3) / 4;
-    for (int t = tid; t < nwords; t += CVH_BLOCK) raw[t] = *(gwords_in)(plane + al + 4 * (size_t)t);
-    __syncthreads();
+    const int c0 = it.g * kSegment, cend = min(c0 + kSegment, w);
+    const RowSpan sp = stage_row_span(raw, plane, r, (size_t)w, c0, cend, R, w, 0u);
     unsigned p1[kRowLane], p2[kRowLane], t1 = 0, t2 = 0;
 #pragma unroll
     for (int j = 0; j < kRowLane; ++j) {
-      const int i = kRowLane * tid + j, b = mis + i;
-      const unsigned x = i < len ? (raw[b >> 2] >> (8 * (b & 3))) & 0xffu : 0u;
+      const int i = kRowLane * tid + j;
+      const unsigned x = i < sp.len ? span_byte(raw, sp, i) : 0u;
       t1 += x; t2 += x * x;
       p1[j] = t1; p2[j] = t2;
     }
@@ -98,10 +75,10 @@ __global__ void __launch_bounds__(CVH_BLOCK) local_rows_kernel(const CvhIoMember
     CVH_GLOBAL uint16_t *const q1 = (CVH_GLOBAL uint16_t *)(q2 + (size_t)h * pitch);
     for (int c = c0 + tid; c < cend; c += CVH_BLOCK) {
       const int lo = max(c - R, 0), hi = min(c + R, w - 1);   // first <= lo <= hi <= last
-      const unsigned b1 = lo > first ? pre1[lo - 1 - first] : 0u, b2 = lo > first ? pre2[lo - 1 - first] : 0u;
+      const unsigned b1 = lo > sp.first ? pre1[lo - 1 - sp.first] : 0u, b2 = lo > sp.first ? pre2[lo - 1 - sp.first] : 0u;
       const size_t at = (size_t)r * pitch + c;
-      q2[at] = pre2[hi - first] - b2;
-      q1[at] = (uint16_t)(pre1[hi - first] - b1);
+      q2[at] = pre2[hi - sp.first] - b2;
+      q1[at] = (uint16_t)(pre1[hi - sp.first] - b1);
     }
     __syncthreads();   // the next trip rewrites the staging
   }
@@ -117,34 +94,19 @@ __device__ __forceinline__ RowSums load_row(gwords_in q2, ghalves_in q1, size_t 
   return RowSums{{b.x & 0xffffu, b.x >> 16, b.y & 0xffffu, b.y >> 16}, {a.x, a.y, a.z, a.w}};
 }
 
-// `valid` bytes (1 .. 4) of a plane at any byte address, as a word whose other bytes are zero
-__device__ __forceinline__ unsigned load_bytes(gbytes_in p, int valid)
-{
-  if (valid == 4) return *(CVH_GLOBAL const u32_any *)p;
-  unsigned v = 0;
-  for (int j = 0; j < valid; ++j) v |= (unsigned)p[j] << (8 * j);
-  return v;
-}
-__device__ __forceinline__ void store_bytes(gbytes_out p, unsigned v, int valid)
-{
-  if (valid == 4) { *(CVH_GLOBAL u32_any *)p = v; return; }
-  for (int j = 0; j < valid; ++j) p[j] = (uint8_t)(v >> (8 * j));
-}
-
 __global__ void __launch_bounds__(CVH_BLOCK) local_columns_kernel(const CvhIoMember *tab, int nmem)
 {
   const CvhIoMember *m = tab + io_member(tab, nmem);
   const int h = m->h, w = m->w, R = m->h2, C = m->C, Cs = m->w2;
   const int nstrip = (w + kStrip - 1) / kStrip, nband = (h + kBand - 1) / kBand;
-  const size_t pitch = pitch_of(w), slot = slot_bytes_of(h, w);
+  const size_t pitch = cvh_window_pitch(w), slot = cvh_local_slot_bytes(h, w);
   const unsigned long long items = (unsigned long long)nband * nstrip;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const unsigned long long nwaves = (unsigned long long)m->nblk * (CVH_BLOCK / 64);
+  const unsigned long long nwaves = wave_item_step(m, CVH_BLOCK / 64);
   unsigned long long acc[6] = {0, 0, 0, 0, 0, 0};
-  for (unsigned long long item = (unsigned long long)(blockIdx.x - m->first) * (CVH_BLOCK / 64) + wave; item < items; item += nwaves) {
-    const int r0 = (int)(item / nstrip) * kBand, r1 = min(r0 + kBand, h), cc = (int)(item % nstrip) * kStrip + 4 * lane;
-    const int valid = min(4, w - cc);   // columns of this lane inside the plane (<= 0: none)
-    unsigned nc[4];                     // columns of a pixel's window
+  for (unsigned long long item = first_wave_item(m, CVH_BLOCK / 64); item < items; item += nwaves) {
+    const ColumnItem it = column_item(item, nstrip, kBand, h, w);
+    const int r0 = it.r0, r1 = it.r1, cc = it.cc, valid = it.valid;
+    unsigned nc[4];   // columns of a pixel's window
 #pragma unroll
     for (int j = 0; j < 4; ++j) nc[j] = (unsigned)(min(cc + j + R, w - 1) - max(cc + j - R, 0) + 1);
     unsigned s1[3] = {0, 0, 0}, s2[3] = {0, 0, 0};
@@ -211,12 +173,6 @@ __global__ void __launch_bounds__(CVH_BLOCK) local_columns_kernel(const CvhIoMem
 
 }  // namespace
 
-// entries between the rows of a workspace slot: whole 16-byte and 8-byte pieces per lane of the column pass
-size_t cvh_local_pitch(int w) { return ((size_t)w + 3) & ~(size_t)3; }
-
-// a slot: the row sums of one source plane, 32-bit sums of p^2 and behind them 16-bit sums of p
-size_t cvh_local_slot_bytes(int h, int w) { return (6 * (size_t)h * cvh_local_pitch(w) + 15) & ~(size_t)15; }
-
 // workgroups of a member: the larger of what the two passes share out, a trip per workgroup (rows) or per wave (columns); the rest is
 // taken on further trips
 unsigned cvh_local_blocks(int h, int w, int planes_read)
@@ -227,9 +183,9 @@ unsigned cvh_local_blocks(int h, int w, int planes_read)
   return (unsigned)(b > 1024 ? 1024 : (b < 1 ? 1 : b));
 }
 
-hipError_t cvh_launch_local(const CvhIoMember *tab, int nmem, unsigned grid, bool any_rows, hipStream_t s)
+hipError_t cvh_launch_local(const CvhIoMember *tab, int nmem, unsigned grid, unsigned passes, hipStream_t s)
 {
-  if (any_rows) hipLaunchKernelGGL(local_rows_kernel, dim3(grid), dim3(CVH_BLOCK), 0, s, tab, nmem);
+  if (passes) hipLaunchKernelGGL(local_rows_kernel, dim3(grid), dim3(CVH_BLOCK), 0, s, tab, nmem);
   hipLaunchKernelGGL(local_columns_kernel, dim3(grid), dim3(CVH_BLOCK), 0, s, tab, nmem);
   return hipGetLastError();
 }

@@ -1,50 +1,38 @@
 // rank_kernels.hip — rank and grey-morphology planes on the device (gfx950): plane k of a member is COPY, MIN, MAX, MEDIAN, OPEN, CLOSE,
 // TOPHAT or BOTHAT of a plane of its source context over the (2 R + 1)^2 window truncated at the border (include/chanvese_hip.h, "Rank
 // planes").  Batch kernels over io_run.hip's member table like local_kernels.hip's: ONE grid serves N members of any mix of shapes, channel
-// counts, radii and codes, a member owning the workgroups first .. first + nblk - 1; every launch reads the same table.
+// counts, radii and codes, a member owning the workgroups first .. first + nblk - 1; every launch reads the same table.  The passes'
+// geometry, the staging of a row span and the sharing out of items are window_device.h's; here are the arithmetic and the writer.
 // MIN and MAX are separable, and by van Herk / Gil-Werman the work per pixel does not grow with R: with the row (or column) padded by R
 // neutral entries on either side -- which IS the truncated window -- and cut into blocks of K = 2 R + 1, g the running minimum from a
 // block's start and hh the one back from its end, the window of K entries that starts at padded position x is min(hh[x], g[x + 2 R]).  A
 // maximum is the minimum of the inverted bytes; the kernels only ever take minima of bytes that are inverted where they are read or
 // written.  A member's workspace (the destination's) holds, per source plane s it reads, CVH_RANK_SLOTS byte planes, rows
-// cvh_rank_pitch(w) apart: for chain c (0 begins with an erosion, 1 with a dilation; rank_math.h) 3 c + 0 the row pass's result T, 3 c + 1
+// cvh_window_pitch(w) apart: for chain c (0 begins with an erosion, 1 with a dilation; rank_math.h) 3 c + 0 the row pass's result T, 3 c + 1
 // the eroded / dilated plane E, 3 c + 2 the column passes' hh; 6 the median M.
-//   row pass      rank_rows_kernel, once for the first half of a chain (from the source plane) and once for the second (from E).  A
-//                 workgroup takes a row segment of CVH_RANK_SEGMENT columns per trip: the bytes of the segment and of R columns on
-//                 either side are staged in LDS by aligned words, a lane scans kRowLane consecutive entries, a segmented wave scan and a
-//                 carry across the four waves make g and hh of the span in LDS, and a lane writes four results as one word of T.
-//   column pass   column_min: a wave takes cvh_rank_band_rows(R) rows x CVH_RANK_STRIP columns per trip, a lane four adjacent columns as
-//                 one word.  The band starts on a block seam.  The lane marches up its band once for hh, which it writes to the
-//                 workspace and alone reads again, then down with g in registers.  rank_columns_kernel writes E, for the chains that run
-//                 twice; rank_final_kernel is the last column pass of every chain AND the writer: it subtracts for the hats (the source
-//                 plane is read there), copies the COPY planes and the median, writes the member's planes four bytes per lane and row and
-//                 adds {sum p, sum p^2} of every plane written to the member's sums as the ingest does.
+//   row pass      rank_rows_kernel, once for the first half of a chain (from the source plane) and once for the second (from E).  Of
+//                 the staged span a lane scans kRowLane consecutive entries, a segmented wave scan and a carry across the four waves
+//                 make g and hh of the span in LDS, and a lane writes four results as one word of T.
+//   column pass   column_min: a band is cvh_rank_band_rows(R) rows, a lane's four adjacent columns one word.  The band starts on a
+//                 block seam.  The lane marches up its band once for hh, which it writes to the workspace and alone reads again, then
+//                 down with g in registers.  rank_columns_kernel writes E, for the chains that run twice; rank_final_kernel is the last
+//                 column pass of every chain AND the writer: it subtracts for the hats (the source plane is read there), copies the
+//                 COPY planes and the median, and writes the member's planes.
 //   median        rank_median_kernel, R = 1 .. 7: a lane marches down a column with a private histogram of 256 byte counters in LDS, four
 //                 bins per word, word (bin / 4) * 64 + lane, and sixteen coarse counters behind them: no two lanes share a word.  It adds
 //                 the 2 R + 1 bytes of the row entering and removes those of the row leaving (clipped), and finds the bin of rank
 //                 (n - 1) / 2 by a coarse and a fine walk of sixteen counters each (rank_math.h); n follows the truncated window.
 // The source is only read.  No kernel waits for another workgroup; the launches follow each other on the stream.
-#include "io_device.h"
+#include "window_device.h"
 #include "rank_math.h"
 
 namespace {
 
-constexpr int kSegment = CVH_RANK_SEGMENT, kBand = CVH_RANK_BAND, kStrip = CVH_RANK_STRIP;
-constexpr int kSpan = kSegment + 2 * CVH_RANK_RADIUS_MAX;         // padded entries a segment's windows read at most
-constexpr int kRowLane = (kSpan + CVH_BLOCK - 1) / CVH_BLOCK;     // consecutive entries a lane of the row pass scans
-constexpr int kRawWords = (kSpan + 3) / 4 + 1;                    // the span as aligned words: up to 3 bytes in front of it
 constexpr int kMedianBlock = 128, kHistWords = 64 + 4;            // threads of a median workgroup; a lane's fine and coarse words
-static_assert(kStrip == 4 * 64, "a lane of the column passes owns four columns");
 static_assert(kSegment == 4 * CVH_BLOCK, "a lane of the row pass writes four results");
-static_assert(255ll * 4 * 65025 < (1ll << 32), "a lane's 32-bit plane sums hold one trip of the tallest band");
 static_assert(CVH_RANK_MEDIAN_RADIUS_MAX == 7 && 15 * 15 < 256, "a window's samples fit a byte counter");
 
-typedef unsigned u32_any __attribute__((aligned(1)));
-typedef CVH_GLOBAL const unsigned *gwords_in;
-typedef CVH_GLOBAL unsigned *gwords_out;
-
 __device__ __forceinline__ int what_of(const CvhIoMember *m, int k) { return (m->interleaved >> (3 * k)) & 7; }
-__device__ __forceinline__ int source_of(const CvhIoMember *m, int k) { return min(k, m->w2 - 1); }
 
 // what the member's planes ask of chain c of source plane s: bit 0 its first half alone (MIN, MAX), bit 1 both halves
 __device__ __forceinline__ unsigned use_of(const CvhIoMember *m, int s, int c)
@@ -55,11 +43,9 @@ __device__ __forceinline__ unsigned use_of(const CvhIoMember *m, int s, int c)
   return u;
 }
 
-__device__ __forceinline__ size_t pitch_of(int w) { return ((size_t)w + 3) & ~(size_t)3; }
-__device__ __forceinline__ size_t slot_bytes_of(int h, int w) { return ((size_t)h * pitch_of(w) + 255) & ~(size_t)255; }
 __device__ __forceinline__ gbytes_out slot_of(const CvhIoMember *m, int s, int which)
 {
-  return (gbytes_out)m->dst + (size_t)(s * CVH_RANK_SLOTS + which) * slot_bytes_of(m->h, m->w);
+  return (gbytes_out)m->dst + (size_t)(s * CVH_RANK_SLOTS + which) * cvh_rank_slot_bytes(m->h, m->w);
 }
 
 __global__ void __launch_bounds__(CVH_BLOCK) rank_rows_kernel(const CvhIoMember *tab, int nmem, int second)
@@ -77,33 +63,22 @@ __global__ void __launch_bounds__(CVH_BLOCK) rank_rows_kernel(const CvhIoMember 
   if (!jobs) return;   // (the whole workgroup)
   const int h = m->h, w = m->w, R = m->h2, K = 2 * R + 1;
   const int nseg = (w + kSegment - 1) / kSegment;
-  const size_t pitch = pitch_of(w);
+  const size_t pitch = cvh_window_pitch(w);
   const unsigned long long per_job = (unsigned long long)h * nseg, items = per_job * __popc(jobs);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   for (unsigned long long item = blockIdx.x - m->first; item < items; item += m->nblk) {
-    const int nth = (int)(item / per_job), r = (int)((item % per_job) / nseg), g = (int)(item % nseg);
-    int job = 0;   // the nth job
-    for (int b = 0, seen = 0; b < 2 * CVH_MAX_CHANNELS; ++b)
-      if ((jobs >> b) & 1u) { if (seen == nth) job = b; ++seen; }
-    const int s = job >> 1, c = job & 1;
+    const RowItem it = row_item(item, per_job, nseg);
+    const int r = it.r, job = nth_set_bit<2 * CVH_MAX_CHANNELS>(jobs, it.nth), s = job >> 1, c = job & 1;
     // the first half of chain 1 and the second half of chain 0 are dilations: their bytes are inverted as they are read
     const unsigned flip = ((c != 0) != (second != 0)) ? 0xffffffffu : 0u;
     const gbytes_in in = second ? (gbytes_in)slot_of(m, s, 3 * c + 1) : (gbytes_in)m->src + (size_t)s * m->src_stride;
     const size_t stride = second ? pitch : (size_t)w;
-    const int c0 = g * kSegment, cend = min(c0 + kSegment, w);
-    const int first = max(c0 - R, 0), last = min(cend - 1 + R, w - 1), len = last - first + 1;   // the columns read: first .. last
+    const int c0 = it.g * kSegment, cend = min(c0 + kSegment, w);
     const int span = cend - c0 + 2 * R;   // padded entries: entry i is column c0 + i - R, neutral outside the plane
-    // Aligned words that cover the columns read: the last one ends at or before the row's end rounded up to 4, inside the plane's own
-    // padding (cvh_create pads every plane to a multiple of 256 bytes) or inside the slot's row pitch
-    const size_t a0 = (size_t)r * stride + first, al = a0 & ~(size_t)3;
-    const int mis = (int)(a0 - al), nwords = (mis + len + 3) / 4;
-    for (int t = tid; t < nwords; t += CVH_BLOCK) raw[t] = *(gwords_in)(in + al + 4 * (size_t)t) ^ flip;
-    __syncthreads();
+    const RowSpan sp = stage_row_span(raw, in, r, stride, c0, cend, R, w, flip);
     auto entry = [&](int i) -> unsigned {
       const int x = c0 + i - R;
-      if (x < first || x > last) return 255u;
-      const int b = mis + x - first;
-      return (raw[b >> 2] >> (8 * (b & 3))) & 0xffu;
+      return x < sp.first || x > sp.last ? 255u : span_byte(raw, sp, x - sp.first);
     };
     // g (back == false) or hh (back == true) of the span: a lane scans its kRowLane entries in scan order, restarting where a block
     // starts; a segmented scan over the lanes' (minimum, restarted) pairs gives every lane what lies in front of it in its block
@@ -212,13 +187,13 @@ __global__ void __launch_bounds__(CVH_BLOCK) rank_columns_kernel(const CvhIoMemb
   const int h = m->h, w = m->w, R = m->h2, Cs = m->w2;
   const int rows = cvh_rank_band_rows(R, kBand);
   const int nstrip = (w + kStrip - 1) / kStrip, nband = (h + rows - 1) / rows;
-  const size_t pw = pitch_of(w) / 4;
+  const size_t pw = cvh_window_pitch(w) / 4;
   const unsigned long long items = (unsigned long long)nband * nstrip;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const unsigned long long nwaves = (unsigned long long)m->nblk * (CVH_BLOCK / 64);
-  for (unsigned long long item = (unsigned long long)(blockIdx.x - m->first) * (CVH_BLOCK / 64) + wave; item < items; item += nwaves) {
-    const int r0 = (int)(item / nstrip) * rows, r1 = min(r0 + rows, h), cc = (int)(item % nstrip) * kStrip + 4 * lane;
-    if (cc >= w) continue;
+  const unsigned long long nwaves = wave_item_step(m, CVH_BLOCK / 64);
+  for (unsigned long long item = first_wave_item(m, CVH_BLOCK / 64); item < items; item += nwaves) {
+    const ColumnItem it = column_item(item, nstrip, rows, h, w);
+    const int r0 = it.r0, r1 = it.r1, cc = it.cc;
+    if (it.valid <= 0) continue;
     for (int s = 0; s < Cs; ++s)
       for (int c = 0; c < 2; ++c) {
         if (!(use_of(m, s, c) & 2u)) continue;
@@ -230,20 +205,6 @@ __global__ void __launch_bounds__(CVH_BLOCK) rank_columns_kernel(const CvhIoMemb
   }
 }
 
-// `valid` bytes (1 .. 4) of a plane at any byte address, as a word whose other bytes are zero
-__device__ __forceinline__ unsigned load_bytes(gbytes_in p, int valid)
-{
-  if (valid == 4) return *(CVH_GLOBAL const u32_any *)p;
-  unsigned v = 0;
-  for (int j = 0; j < valid; ++j) v |= (unsigned)p[j] << (8 * j);
-  return v;
-}
-__device__ __forceinline__ void store_bytes(gbytes_out p, unsigned v, int valid)
-{
-  if (valid == 4) { *(CVH_GLOBAL u32_any *)p = v; return; }
-  for (int j = 0; j < valid; ++j) p[j] = (uint8_t)(v >> (8 * j));
-}
-
 // the last column pass of every chain and the writer of every plane
 __global__ void __launch_bounds__(CVH_BLOCK) rank_final_kernel(const CvhIoMember *tab, int nmem)
 {
@@ -251,14 +212,13 @@ __global__ void __launch_bounds__(CVH_BLOCK) rank_final_kernel(const CvhIoMember
   const int h = m->h, w = m->w, R = m->h2, C = m->C, Cs = m->w2;
   const int rows = cvh_rank_band_rows(R, kBand);
   const int nstrip = (w + kStrip - 1) / kStrip, nband = (h + rows - 1) / rows;
-  const size_t pw = pitch_of(w) / 4;
+  const size_t pw = cvh_window_pitch(w) / 4;
   const unsigned long long items = (unsigned long long)nband * nstrip;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const unsigned long long nwaves = (unsigned long long)m->nblk * (CVH_BLOCK / 64);
+  const unsigned long long nwaves = wave_item_step(m, CVH_BLOCK / 64);
   unsigned long long acc[6] = {0, 0, 0, 0, 0, 0};
-  for (unsigned long long item = (unsigned long long)(blockIdx.x - m->first) * (CVH_BLOCK / 64) + wave; item < items; item += nwaves) {
-    const int r0 = (int)(item / nstrip) * rows, r1 = min(r0 + rows, h), cc = (int)(item % nstrip) * kStrip + 4 * lane;
-    const int valid = min(4, w - cc);   // columns of this lane inside the plane (<= 0: none)
+  for (unsigned long long item = first_wave_item(m, CVH_BLOCK / 64); item < items; item += nwaves) {
+    const ColumnItem it = column_item(item, nstrip, rows, h, w);
+    const int r0 = it.r0, r1 = it.r1, cc = it.cc, valid = it.valid;
     if (valid <= 0) continue;
     const unsigned keep = valid == 4 ? 0xffffffffu : (1u << (8 * valid)) - 1u;
     unsigned s1[3] = {0, 0, 0}, s2[3] = {0, 0, 0};
@@ -330,17 +290,15 @@ __global__ void __launch_bounds__(kMedianBlock) rank_median_kernel(const CvhIoMe
     if (what_of(m, k) == CVH_RANK_MEDIAN) need |= 1u << source_of(m, k);
   if (!need || R == 0) return;
   const int nstrip = (w + 63) / 64, nband = (h + CVH_RANK_MEDIAN_BAND - 1) / CVH_RANK_MEDIAN_BAND;
-  const size_t pitch = pitch_of(w);
+  const size_t pitch = cvh_window_pitch(w);
   const unsigned long long per_plane = (unsigned long long)nband * nstrip, items = per_plane * __popc(need);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   unsigned *const mine = hist[wave] + lane;   // word q of this lane: mine[64 q]
-  const unsigned long long nwaves = (unsigned long long)m->nblk * (kMedianBlock / 64);
-  for (unsigned long long item = (unsigned long long)(blockIdx.x - m->first) * (kMedianBlock / 64) + wave; item < items; item += nwaves) {
+  const unsigned long long nwaves = wave_item_step(m, kMedianBlock / 64);
+  for (unsigned long long item = first_wave_item(m, kMedianBlock / 64); item < items; item += nwaves) {
     const int nth = (int)(item / per_plane), band = (int)((item % per_plane) / nstrip), col = (int)(item % nstrip) * 64 + lane;
     if (col >= w) continue;
-    int s = 0;   // the nth plane that is read
-    for (int b = 0, seen = 0; b < CVH_MAX_CHANNELS; ++b)
-      if ((need >> b) & 1u) { if (seen == nth) s = b; ++seen; }
+    const int s = nth_set_bit<CVH_MAX_CHANNELS>(need, nth);   // the nth plane that is read
     const gbytes_in plane = (gbytes_in)m->src + (size_t)s * m->src_stride;
     const gbytes_out M = slot_of(m, s, 6);
     const int r0 = band * CVH_RANK_MEDIAN_BAND, r1 = min(r0 + CVH_RANK_MEDIAN_BAND, h);
@@ -373,12 +331,6 @@ __global__ void __launch_bounds__(kMedianBlock) rank_median_kernel(const CvhIoMe
 }
 
 }  // namespace
-
-// bytes between the rows of a workspace plane: whole words per lane of the column passes
-size_t cvh_rank_pitch(int w) { return ((size_t)w + 3) & ~(size_t)3; }
-
-// one byte plane of the workspace; a destination owns CVH_RANK_SLOTS of them per plane it has
-size_t cvh_rank_slot_bytes(int h, int w) { return ((size_t)h * cvh_rank_pitch(w) + 255) & ~(size_t)255; }
 
 // workgroups of a member: the largest of what the passes share out -- a trip per workgroup (rows of `row_jobs` chains) or per wave
 // (columns; `median_planes` source planes of the median) --; the rest is taken on further trips

@@ -1,5 +1,5 @@
 // rank_math.h — the small integer arithmetic of the rank planes (include/chanvese_hip.h, "Rank planes") that the kernels
-// (rank_kernels.hip) and the host (rank_run.hip; debug_exports.hip, which tests/test_rank_api.py and tests/test_rank_restatement.py hold
+// (rank_kernels.hip) and the host (window_run.hip; debug_exports.hip, which tests/test_rank_api.py and tests/test_rank_restatement.py hold
 // against Python integers) share: which chain of erosions and dilations a code needs, the rows of a column band at a radius, the rank of
 // the lower median, and the walk over sixteen packed byte counters that finds the bin of a rank.
 #pragma once

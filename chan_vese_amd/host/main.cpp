@@ -341,6 +341,40 @@ int to_int(const std::string &opt, const std::string &v)
   return (int)d;
 }
 
+// --local and --rank: a windowed filter by name, which stands for the code of every plane, and the radius of its window
+// (--local-radius, --rank-radius), which one name (`bound`) may bind to less than radius_max
+struct WindowName { const char *name; int code; };   // (a table ends with a null name)
+struct WindowOption { const char *key, *label, *noun; const WindowName *names; int radius_max; const char *bound; int bound_max; };
+const WindowName kLocalNames[] = {{"mean", CVH_LOCAL_MEAN}, {"dev", CVH_LOCAL_DEV}, {"stack", CVH_LOCAL_COPY}, {nullptr, 0}};   // (stack: main)
+const WindowName kRankNames[] = {{"median", CVH_RANK_MEDIAN}, {"min", CVH_RANK_MIN}, {"max", CVH_RANK_MAX}, {"open", CVH_RANK_OPEN},
+                                 {"close", CVH_RANK_CLOSE}, {"tophat", CVH_RANK_TOPHAT}, {"bothat", CVH_RANK_BOTHAT}, {nullptr, 0}};
+const WindowOption kLocalOption = {"local", "Local", "statistic", kLocalNames, CVH_LOCAL_RADIUS_MAX, "", 0};
+const WindowOption kRankOption = {"rank", "Rank", "filter", kRankNames, CVH_RANK_RADIUS_MAX, "median", CVH_RANK_MEDIAN_RADIUS_MAX};
+
+// Whether the option is given; then every what[k] receives the code of `name` and `radius` is checked against the name's range.
+// Refuses an unknown name and a radius without a name.
+bool window_option(const Parsed &vm, const WindowOption &o, const std::string &name, int radius, int what[3])
+{
+  const std::string key = o.key;
+  if (!vm.count(key)) {
+    if (vm.count(key + "-radius")) msg_exit("A radius (--" + key + "-radius) needs a " + o.noun + " (--" + key + ").");
+    return false;
+  }
+  const WindowName *hit = nullptr;
+  std::string list;
+  for (const WindowName *nm = o.names; nm->name; ++nm) {
+    if (iequals(name, nm->name)) hit = nm;
+    list += std::string(list.empty() ? "" : ", ") + nm->name;
+  }
+  if (!hit) msg_exit("Invalid " + key + " " + o.noun + " requested.\nCorrect values are: " + list + ".");
+  const bool bound = iequals(name, o.bound);
+  const int top = bound ? o.bound_max : o.radius_max;
+  if (radius < 0 || radius > top)
+    msg_exit(std::string(o.label) + " radius must be between 0 and " + std::to_string(top) + (bound ? " for a " + std::string(o.bound) : "") + ": " + std::to_string(radius) + ".");
+  what[0] = what[1] = what[2] = hit->code;
+  return true;
+}
+
 void print_help()
 {
   std::cout <<
@@ -526,34 +560,13 @@ int main(int argc, char **argv)
   if (mu < 0) msg_exit("Length penalty parameter cannot be negative: " + std::to_string(mu) + ".");
   // --local: the run iterates on local statistics of the planes (chanvese_hip.h, "Local statistics"); stack turns the grey plane into three
   int local_what[3] = {CVH_LOCAL_COPY, CVH_LOCAL_COPY, CVH_LOCAL_COPY};
-  const bool local = vm.count("local") > 0, local_stack = local && iequals(local_name, "stack");
-  if (local) {
-    if (iequals(local_name, "mean")) local_what[0] = local_what[1] = local_what[2] = CVH_LOCAL_MEAN;
-    else if (iequals(local_name, "dev")) local_what[0] = local_what[1] = local_what[2] = CVH_LOCAL_DEV;
-    else if (local_stack) { local_what[1] = CVH_LOCAL_MEAN; local_what[2] = CVH_LOCAL_DEV; }
-    else msg_exit("Invalid local statistic requested.\nCorrect values are: mean, dev, stack.");
-    if (local_stack && !grayscale) msg_exit("The local stack (--local stack) needs a grayscale read (-g): it makes three planes of one.");
-    if (local_radius < 0 || local_radius > CVH_LOCAL_RADIUS_MAX)
-      msg_exit("Local radius must be between 0 and " + std::to_string(CVH_LOCAL_RADIUS_MAX) + ": " + std::to_string(local_radius) + ".");
-  } else if (vm.count("local-radius")) {
-    msg_exit("A radius (--local-radius) needs a statistic (--local).");
-  }
+  const bool local_stack = vm.count("local") > 0 && iequals(local_name, "stack");
+  if (local_stack && !grayscale) msg_exit("The local stack (--local stack) needs a grayscale read (-g): it makes three planes of one.");
+  const bool local = window_option(vm, kLocalOption, local_name, local_radius, local_what);
+  if (local_stack) { local_what[1] = CVH_LOCAL_MEAN; local_what[2] = CVH_LOCAL_DEV; }
   // --rank: the run iterates on a rank filter of the planes (chanvese_hip.h, "Rank planes"), every plane alike
   int rank_what[3] = {CVH_RANK_COPY, CVH_RANK_COPY, CVH_RANK_COPY};
-  const bool rank = vm.count("rank") > 0;
-  if (rank) {
-    static const std::pair<const char *, int> names[] = {{"min", CVH_RANK_MIN}, {"max", CVH_RANK_MAX}, {"median", CVH_RANK_MEDIAN}, {"open", CVH_RANK_OPEN},
-                                                         {"close", CVH_RANK_CLOSE}, {"tophat", CVH_RANK_TOPHAT}, {"bothat", CVH_RANK_BOTHAT}};
-    for (const auto &nm : names)
-      if (iequals(rank_name, nm.first)) rank_what[0] = rank_what[1] = rank_what[2] = nm.second;
-    if (rank_what[0] == CVH_RANK_COPY) msg_exit("Invalid rank filter requested.\nCorrect values are: median, min, max, open, close, tophat, bothat.");
-    const int top = rank_what[0] == CVH_RANK_MEDIAN ? CVH_RANK_MEDIAN_RADIUS_MAX : CVH_RANK_RADIUS_MAX;
-    if (rank_radius < 0 || rank_radius > top)
-      msg_exit("Rank radius must be between 0 and " + std::to_string(top) + (top == CVH_RANK_MEDIAN_RADIUS_MAX ? " for a median: " : ": ") +
-               std::to_string(rank_radius) + ".");
-  } else if (vm.count("rank-radius")) {
-    msg_exit("A radius (--rank-radius) needs a filter (--rank).");
-  }
+  const bool rank = window_option(vm, kRankOption, rank_name, rank_radius, rank_what);
   const bool one_plane = grayscale && !local_stack;   // the run has one plane: what the lambda counts and the threshold range follow
   if (vm.count("lambda1")) {
     if (one_plane && lambda1.size() != 1) msg_exit("Too many lambda1 values for a grayscale image.");

@@ -122,6 +122,23 @@ def check_colour(colour, order, channels):
     return colour.lower(), order.lower()
 
 
+def _check_window(given, name, channels, what_codes, radius_of, radius_first=False):
+    """(radius, codes, planes made) of Segmenter's `local` / `rank`: a name makes as many planes as are ingested, a tuple of 1 or 3 codes
+    as many as it has; radius_of(radius, codes of the planes made) checks the radius, in front of the codes where it needs none."""
+    if not isinstance(given, (tuple, list)) or len(given) != 2:
+        raise ValueError(f"{name} must be (radius, what), got {given!r}")
+    radius, what = given
+    if radius_first:
+        radius_of(radius, ())
+    codes = what_codes(what)
+    made = channels
+    if not isinstance(what, str):
+        if len(tuple(what)) not in (1, 3):
+            raise ValueError(f"a tuple of {name} codes names 1 or 3 planes, got {what!r}")
+        made = len(tuple(what))
+    return radius_of(radius, codes[:made]), codes, made
+
+
 def check_local(local, channels):
     """Validates Segmenter's `local` and returns (radius, codes, channels of the planes the run iterates on), or None for None.  `local`
     is (radius, what): what "mean" / "dev" (every plane; as many planes as are ingested), "stack" (copy, mean, deviation of ONE ingested
@@ -129,17 +146,12 @@ def check_local(local, channels):
     nothing in the library."""
     if local is None:
         return None
-    if not isinstance(local, (tuple, list)) or len(local) != 2:
-        raise ValueError(f"local must be (radius, what), got {local!r}")
-    radius, what = capi.local_radius(local[0]), local[1]
-    codes = capi.local_what_codes(what)
-    if isinstance(what, str):
-        if what.lower() == "stack" and channels != 1:
+    radius, codes, made = _check_window(local, "local", channels, capi.local_what_codes, lambda r, _: capi.local_radius(r), radius_first=True)
+    if isinstance(local[1], str) and local[1].lower() == "stack":
+        if channels != 1:
             raise ValueError(f'local "stack" makes three planes of one: channels must be 1, got {channels}')
-        return radius, codes, 3 if what.lower() == "stack" else channels
-    if len(tuple(what)) not in (1, 3):
-        raise ValueError(f"a tuple of local codes names 1 or 3 planes, got {what!r}")
-    return radius, codes, len(tuple(what))
+        made = 3
+    return radius, codes, made
 
 
 def check_rank(rank, channels):
@@ -147,18 +159,7 @@ def check_rank(rank, channels):
     (radius, what): what "min" / "max" / "median" / "open" / "close" / "tophat" / "bothat" (every plane; as many planes as are
     ingested) or a tuple of 1 or 3 capi.RANK_* codes (as many planes as codes).  A median binds the radius to
     capi.RANK_MEDIAN_RADIUS_MAX.  ValueError for anything else.  Calls nothing in the library."""
-    if rank is None:
-        return None
-    if not isinstance(rank, (tuple, list)) or len(rank) != 2:
-        raise ValueError(f"rank must be (radius, what), got {rank!r}")
-    what = rank[1]
-    codes = capi.rank_what_codes(what)
-    made = channels
-    if not isinstance(what, str):
-        if len(tuple(what)) not in (1, 3):
-            raise ValueError(f"a tuple of rank codes names 1 or 3 planes, got {what!r}")
-        made = len(tuple(what))
-    return capi.rank_radius(rank[0], codes[:made]), codes, made
+    return None if rank is None else _check_window(rank, "rank", channels, capi.rank_what_codes, capi.rank_radius)
 
 
 def scale_init(kind, rows, levels):

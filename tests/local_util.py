@@ -12,7 +12,7 @@ COPY, MEAN, DEV = 0, 1, 2
 RADIUS_MAX = 127
 STACK = (COPY, MEAN, DEV)
 # local_kernels.hip: a wave of the column pass takes BAND rows x STRIP columns per trip, a workgroup of the row pass SEGMENT columns of
-# a row (cvh_internal.h, CVH_LOCAL_*; test_local_api.py compares these numbers with the library's)
+# a row (cvh_internal.h, CVH_WINDOW_*; test_local_api.py compares these numbers with the library's)
 BAND, STRIP, SEGMENT = 32, 256, 1024
 
 _ISQRT = np.array([math.isqrt(q) for q in range(255 * 255 + 1)], dtype=np.int64)

@@ -14,7 +14,7 @@ CODES = (COPY, MIN, MAX, MEDIAN, OPEN, CLOSE, TOPHAT, BOTHAT)
 NAMES = {"min": MIN, "max": MAX, "median": MEDIAN, "open": OPEN, "close": CLOSE, "tophat": TOPHAT, "bothat": BOTHAT}
 RADIUS_MAX, MEDIAN_RADIUS_MAX = 127, 7
 # rank_kernels.hip: a wave of the column passes takes band_rows(R) rows x STRIP columns per trip, a workgroup of the row pass SEGMENT
-# columns of a row, a wave of the median MEDIAN_BAND rows x MEDIAN_STRIP columns (cvh_internal.h, CVH_RANK_*; test_rank_api.py compares
+# columns of a row, a wave of the median MEDIAN_BAND rows x MEDIAN_STRIP columns (cvh_internal.h, CVH_WINDOW_* and CVH_RANK_MEDIAN_*; test_rank_api.py compares
 # these numbers with the library's)
 BAND, STRIP, SEGMENT, MEDIAN_BAND, MEDIAN_STRIP = 32, 256, 1024, 32, 64
 

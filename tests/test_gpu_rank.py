@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import rank_util as U
+from window_util import alone, bits, device_capi, launch_sets, refusal_check, same_planes, smooth_levelset
 
 pytestmark = pytest.mark.gpu
 ERR_ARG, ERR_STATE = 1, 3
@@ -18,37 +19,7 @@ SEPARABLE = (U.MIN, U.MAX, U.OPEN, U.CLOSE, U.TOPHAT, U.BOTHAT)
 
 @pytest.fixture(scope="module")
 def capi():
-    from chan_vese_amd import capi as m
-    m.lib()
-    assert m.device_count() >= 1, "no HIP device: the product path has no CPU fallback"
-    return m
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def alone(ctx, **opts):
-    """contexts compared in bits must not see each other in their automatic choices (tests/test_gpu_device_io.py, same_choices)"""
-    ctx.set_option("co_resident", 0)
-    for k, v in opts.items():
-        ctx.set_option(k, v)
-    return ctx
-
-
-def same_planes(got, want):
-    return len(got) == len(want) and all(np.array_equal(a, b) for a, b in zip(got, want))
-
-
-def smooth_levelset(h, w):
-    ii, jj = np.mgrid[0:h, 0:w]
-    return min(h, w) / 3.0 - np.hypot(ii - h / 2.0, jj - w / 2.0)
-
-
-def launch_sets():
-    fn = ctypes.CDLL(__import__("chan_vese_amd").capi.LIB_PATH).cvh_debug_rank_launch_sets
-    fn.restype = ctypes.c_ulong
-    return fn()
+    return device_capi()
 
 
 @pytest.mark.parametrize("case", U.CASES, ids=lambda c: "%dx%d-R%d-%s" % c)
@@ -123,9 +94,9 @@ def test_mixed_batch_equals_the_single_calls(capi):
             c.set_image(img)
         for c in dst_b + dst_s:
             c.set_levelset(smooth_levelset(c.h, c.w))               # (the stop condition is asked of a context with a level set)
-        n0 = launch_sets()
+        n0 = launch_sets("rank")
         capi.rank_planes_batch(srcs, dst_b, [p[3] for p in pairs], [p[4] for p in pairs])
-        assert launch_sets() == n0 + 1                              # five pairs, ONE set of launches
+        assert launch_sets("rank") == n0 + 1                              # five pairs, ONE set of launches
         for s, d, p in zip(srcs, dst_s, pairs):
             s.rank_planes_to(d, p[3], p[4])
         for b, s, img, p in zip(dst_b, dst_s, imgs, pairs):
@@ -221,29 +192,34 @@ def test_refusals_leave_the_planes_unchanged(capi):
             return same_planes(a.get_image(), planes) and same_planes(b.get_image(), planes) and same_planes(one.get_image(), planes[:1]) \
                 and same_planes(dst.get_image(), planes[:1]) and not wide.get_image()[0].any()
 
-        def refused(rc, code, *words):
-            assert rc == code
-            msg = L.cvh_last_error(None).decode()
-            assert all(word in msg for word in words), msg
-            assert unchanged()
+        refused = refusal_check(L, unchanged)                        # (whole=: the message byte for byte)
 
         ok = I3(U.OPEN, U.MAX, U.COPY)
         two = lambda x, y: (ctypes.c_int * 2)(x, y)
         refused(L.cvh_rank_planes(a._h, a._h, 1, ok), ERR_ARG, "cvh_rank_planes", "pair 0")                      # src == dst
         refused(L.cvh_rank_planes_batch(arr(a, b), arr(dst, dst), 2, two(1, 1), (ctypes.c_int * 6)()), ERR_ARG, "cvh_rank_planes_batch", "pair 1", "pair 0")
         refused(L.cvh_rank_planes_batch(arr(a, one), arr(dst, a), 2, two(1, 1), (ctypes.c_int * 6)()), ERR_ARG, "pair 1", "pair 0")
-        refused(L.cvh_rank_planes_batch(arr(a, b), arr(dst, wide), 2, two(1, 1), (ctypes.c_int * 6)()), ERR_ARG, "pair 1", f"{h} x {w}")
-        for bad in (-1, 128, 1 << 20):
-            refused(L.cvh_rank_planes(a._h, dst._h, bad, ok), ERR_ARG, "pair 0", "radius")
-        refused(L.cvh_rank_planes_batch(arr(a, b), arr(dst, one), 2, two(1, 200), (ctypes.c_int * 6)()), ERR_ARG, "pair 1", "radius")
-        for bad in (I3(8, 0, 0), I3(-1, 0, 0)):
-            refused(L.cvh_rank_planes(a._h, dst._h, 1, bad), ERR_ARG, "pair 0", "what[0]")
+        refused(L.cvh_rank_planes_batch(arr(a, b), arr(dst, wide), 2, two(1, 1), (ctypes.c_int * 6)()), ERR_ARG, "pair 1", f"{h} x {w}",
+                whole="cvh_rank_planes_batch: pair 1: the destination of a 17 x 19 source must be 17 x 19 too, got 17 x 20")
+        for bad, whole in ((-1, "cvh_rank_planes: pair 0: the radius must be 0 .. 127, got -1"),
+                           (128, "cvh_rank_planes: pair 0: the radius must be 0 .. 127, got 128"),
+                           (1 << 20, "cvh_rank_planes: pair 0: the radius must be 0 .. 127, got 1048576")):
+            refused(L.cvh_rank_planes(a._h, dst._h, bad, ok), ERR_ARG, "pair 0", "radius", whole=whole)
+        refused(L.cvh_rank_planes_batch(arr(a, b), arr(dst, one), 2, two(1, 200), (ctypes.c_int * 6)()), ERR_ARG, "pair 1", "radius",
+                whole="cvh_rank_planes_batch: pair 1: the radius must be 0 .. 127, got 200")
+        for bad, whole in ((I3(8, 0, 0), "cvh_rank_planes: pair 0: what[0] must be one of CVH_RANK_COPY (0) .. CVH_RANK_BOTHAT (7), got 8"),
+                           (I3(-1, 0, 0), "cvh_rank_planes: pair 0: what[0] must be one of CVH_RANK_COPY (0) .. CVH_RANK_BOTHAT (7), got -1")):
+            refused(L.cvh_rank_planes(a._h, dst._h, 1, bad), ERR_ARG, "pair 0", "what[0]", whole=whole)
         refused(L.cvh_rank_planes(a._h, b._h, 1, I3(0, 1, 9)), ERR_ARG, "pair 0", "what[2]")
-        refused(L.cvh_rank_planes(a._h, dst._h, 8, I3(U.MEDIAN, 0, 0)), ERR_ARG, "pair 0", "median", "radius")      # the median's limit
-        refused(L.cvh_rank_planes(a._h, b._h, 127, I3(U.MAX, U.OPEN, U.MEDIAN)), ERR_ARG, "pair 0", "median", "what[2]")
-        refused(L.cvh_rank_planes_batch(arr(a, b), arr(dst, one), 2, two(7, 8), (ctypes.c_int * 6)(3, 0, 0, 3, 0, 0)), ERR_ARG, "pair 1", "median")
-        refused(L.cvh_rank_planes(a._h, dst._h, 1, None), ERR_ARG, "cvh_rank_planes", "NULL")
-        refused(L.cvh_rank_planes_batch(arr(a), arr(dst), 1, None, ok), ERR_ARG, "cvh_rank_planes_batch", "NULL")
+        refused(L.cvh_rank_planes(a._h, dst._h, 8, I3(U.MEDIAN, 0, 0)), ERR_ARG, "pair 0", "median", "radius",      # the median's limit
+                whole="cvh_rank_planes: pair 0: the radius of a median (what[0]) must be 0 .. 7, got 8")
+        refused(L.cvh_rank_planes(a._h, b._h, 127, I3(U.MAX, U.OPEN, U.MEDIAN)), ERR_ARG, "pair 0", "median", "what[2]",
+                whole="cvh_rank_planes: pair 0: the radius of a median (what[2]) must be 0 .. 7, got 127")
+        refused(L.cvh_rank_planes_batch(arr(a, b), arr(dst, one), 2, two(7, 8), (ctypes.c_int * 6)(3, 0, 0, 3, 0, 0)), ERR_ARG, "pair 1", "median",
+                whole="cvh_rank_planes_batch: pair 1: the radius of a median (what[0]) must be 0 .. 7, got 8")
+        refused(L.cvh_rank_planes(a._h, dst._h, 1, None), ERR_ARG, "cvh_rank_planes", "NULL", whole="cvh_rank_planes: the list of codes (what) is NULL")
+        refused(L.cvh_rank_planes_batch(arr(a), arr(dst), 1, None, ok), ERR_ARG, "cvh_rank_planes_batch", "NULL",
+                whole="cvh_rank_planes_batch: the list of radii is NULL")
         refused(L.cvh_rank_planes_batch(arr(a), arr(dst), 0, (ctypes.c_int * 1)(1), ok), ERR_ARG, "cvh_rank_planes_batch")
         refused(L.cvh_rank_planes(empty._h, dst._h, 1, ok), ERR_STATE, "pair 0", "no image")
         refused(L.cvh_rank_planes_batch(arr(a, empty), arr(dst, one), 2, two(1, 1), (ctypes.c_int * 6)()), ERR_STATE, "pair 1", "no image")

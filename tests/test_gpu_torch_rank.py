@@ -15,6 +15,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_segmenter_rank_equals_the_capi_sequence():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "torch_rank_child.py")], capture_output=True, text=True, timeout=600)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "torch_window_child.py"), "rank"], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, (out.stdout[-2000:], out.stderr[-4000:])
     assert "torch_rank child ok" in out.stdout
