@@ -121,6 +121,8 @@ extern "C" void cvh_destroy(cvh_context *c)
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->d_img_slab) (void)hipFree(c->d_img_slab);
   if (c->d_u_slab) (void)hipFree(c->d_u_slab);
+  if (c->d_ob) (void)hipFree(c->d_ob);
+  if (c->d_ob_tab) (void)hipFree(c->d_ob_tab);
   if (c->d_uf_slab) (void)hipFree(c->d_uf_slab);
   for (int k = 0; k < 2; ++k) if (c->d_pm[k]) (void)hipFree(c->d_pm[k]);
   if (c->d_state) (void)hipFree(c->d_state);
@@ -269,6 +271,7 @@ extern "C" int cvh_set_option(cvh_context *c, const char *key, long value)
   if (!c || !key) return CVH_ERR_ARG;
   HIPCHK(c, hipSetDevice(c->device));
   { const int rc = settle(c); if (rc != CVH_OK) return rc; }  // options apply between runs
+  { const int rc = one_buffer_leave(c); if (rc != CVH_OK) return rc; }   // and to the level set in d_u[] (the next enqueue chooses the flow again)
   if (!strcmp(key, "math_mode")) {
     if (value < 0 || value > 2) return fail(c, CVH_ERR_ARG, "math_mode must be 0, 1 or 2");
     c->math_mode = (int)value;
@@ -339,6 +342,9 @@ extern "C" int cvh_set_option(cvh_context *c, const char *key, long value)
   } else if (!strcmp(key, "wave_seam")) {
     if (value != 0 && value != 1) return fail(c, CVH_ERR_ARG, "wave_seam must be 0 or 1");
     c->wave_seam = (int)value;
+  } else if (!strcmp(key, "one_buffer")) {
+    if (value < -1 || value > 1) return fail(c, CVH_ERR_ARG, "one_buffer must be -1 (auto), 0 or 1");
+    c->one_buffer = (int)value;
   } else if (!strcmp(key, "near_switch")) {
     c->near_switch = value != 0;
   } else if (!strcmp(key, "res_prio")) {
@@ -518,6 +524,7 @@ int levelset_arrived(cvh_context *c, bool device_cleared)
   c->have_u = true;
   c->sums_valid = false;
   c->mirror_valid = true;
+  c->ob_live = false;            // (the one-buffer slab held the level set this one replaces)
   if (c->state_bits == 32) { const int rc = adopt_f32_state(c); if (rc != CVH_OK) return rc; }
   if (!device_cleared) return reset_run_impl(c);
   begin_run_host(c);
@@ -534,7 +541,7 @@ void steps_enqueued(cvh_context *c, int n, int nparts, bool chain, bool resident
   if (chain) { c->chain_pending = true; c->pending_nparts = nparts; }
   else c->chain_acc_valid = false;
   c->last_nparts = nparts;
-  if (c->state_bits == 32) c->mirror_valid = false;
+  if (c->state_bits == 32 || c->ob_live) c->mirror_valid = false;
   c->enqueued += n;
 }
 
@@ -579,11 +586,18 @@ int adopt_f32_state(cvh_context *c)
 }
 
 // FP32 state: d_u[current] = (double) d_uf[current] if launches have run since the mirror was last refreshed (call behind a sync).
+// One-buffer flow: d_u[current] = the plane rows of the slab, likewise.
 int ensure_f64_mirror(cvh_context *c)
 {
-  if (c->state_bits != 32 || c->mirror_valid) return CVH_OK;
+  if ((c->state_bits != 32 && !c->ob_live) || c->mirror_valid) return CVH_OK;
   { const int rc = settle(c); if (rc != CVH_OK) return rc; }
   const int cur = current_buffer(c);
+  if (c->ob_live) {
+    HIPCHK(c, cvh_launch_ob_unpack(c->d_ob, c->d_u[cur], c->h, c->w, (c->w + cvh_wave2_cols() - 1) / cvh_wave2_cols(), c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->mirror_valid = true;
+    return CVH_OK;
+  }
   HIPCHK(c, cvh_launch_state_widen(c->d_uf[cur], c->d_u[cur], c->n, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->mirror_valid = true;
@@ -806,9 +820,9 @@ extern "C" int cvh_launch_info(cvh_context *c, int phase, char *buf, int cap)
   CvhStepArgs a;
   fill_args(c, &a, current_buffer(c), c->enqueued);
   snprintf(buf, (size_t)cap, "kernel=%s grid=%u block=%u lds_bytes=%u data_flow=%d wave_columns=%d strips=%d strip_rows=%d chain=%d "
-           "wave_pol=%d math=%s steps_per_graph=%d wave_seam=%d", note.name, note.grid, note.block, note.lds, g.strip, g.tiles_x, g.tiles_y,
+           "wave_pol=%d math=%s steps_per_graph=%d wave_seam=%d one_buffer=%d", note.name, note.grid, note.block, note.lds, g.strip, g.tiles_x, g.tiles_y,
            g.strip_rows, a.chain ? 1 : 0, a.wave_pol, use_fast(c) ? "fast" : "strict", c->use_graph ? kGraphSteps : 0,
-           (g.strip == 3 && use_fast(c)) ? a.wave_seam : 0);
+           (g.strip == 3 && use_fast(c)) ? a.wave_seam : 0, a.one_buffer);
   return CVH_OK;
 }
 

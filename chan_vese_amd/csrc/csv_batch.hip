@@ -218,6 +218,7 @@ static void batch_share(cvh_context *const *ctxs, int n, bool on)
   for (int i = 0; i < n; ++i) {
     cvh_context *c = ctxs[i];
     c->geom_cus = 0;
+    c->in_batch = on;
     if (!on || resolve_geometry(c).strip_rows >= kBatchOwnRows) continue;
     const int share = (int)((double)c->num_cus * (double)c->n / tot + 0.5);
     c->geom_cus = share < 1 ? 1 : share;
@@ -235,6 +236,7 @@ static int batch_prepare(cvh_context *const *ctxs, int n)
     if (rc != CVH_OK) return batch_fail(ctxs, n, rc, "batch: member %d: %s", i, c->err);
     const Geometry g = resolve_geometry(c);
     rc = upload_strip_bounds(c, g);
+    if (rc == CVH_OK) rc = one_buffer_leave(c);   // a fused batch iterates the pair
     if (rc == CVH_OK) rc = flush_for_grid(c, g.nblocks);
     if (rc == CVH_OK) rc = prepare(c);
     if (rc != CVH_OK) return batch_fail(ctxs, n, rc, "batch: member %d: %s", i, c->err);

@@ -87,6 +87,99 @@ bool use_chain(const cvh_context *c, const Geometry &g)
   return (g.strip == 3 || g.strip == 2) && use_fast(c) && c->finalize_mode == 0 && c->chain_opt;
 }
 
+// ---- One-buffer flow of the 2-pixel kernel (csv_wave2_ob_kernel, csv_wave2_kernel.hip; layout: cvh_internal.h, cvh_ob_*).  The ping-pong pair of a 4096^2 plane
+// (285 MB with the image) does not fit the 256 MiB Infinity Cache, one padded buffer (160 MB) does.  The flow exists for one channel, FAST
+// arithmetic, the FP64 state and a context's own per-launch launches.  It is taken only where the run cannot stop (tol == 0): in chain
+// mode the launch behind a stop has already computed one more iteration when the bookkeeper fires the rule, which the pair survives (the
+// stopped level set is the buffer that launch read) and one buffer would not -- every run with tol > 0 keeps the pair.  (A tol = 0 run
+// stops only on a norm of exactly 0, where the iteration beside the stop rewrites every cell with the value it holds.)
+bool one_buffer_rule(const cvh_context *c, const Geometry &g, bool alone)
+{
+  if (c->one_buffer == 0 || g.strip != 3 || c->C != 1 || !use_fast(c) || c->state_bits != 64 || c->p.tol != 0.0) return false;
+  if (c->wave_pol == 2 || c->in_batch) return false;   // the diagnostic load policy; a fused batch's member
+  if (c->resident_opt != 0) {   // planes the resident flow may take stay its
+    ResidentGeom rg;
+    if (resident_tile_grid(c->h, c->w, c->C, c->num_cus, c->num_cus, &rg)) return false;
+  }
+  const double slab = (double)cvh_ob_rows(c->h, g.tiles_y) * cvh_ob_pitch(c->w, g.tiles_x) * sizeof(double);
+  if (slab >= 2147483648.0) return false;   // 32-bit byte offsets, dropped lanes at 2^31
+  if (c->one_buffer == 1) return true;
+  // auto: a single live context whose pair exceeds what the cache holds reliably while one buffer (pads, shadow rows, image) stays below it
+  // -- in the automatic geometry, where the flow was measured against the pair; a caller who chose the kernel or tuned
+  // its strips keeps the flow that choice was made for (as the resident flow's automatic rule steps aside, resident_geometry)
+  if (c->kernel != -1 || c->strip_rows != 0 || c->strips != 0 || c->wave_cls != 1 || c->wave_cskew != 500 || c->wave_skew != 0) return false;
+  return alone && (double)c->n * 17.0 > kCachedFootprint && slab + (double)c->n <= kCachedFootprint;
+}
+
+bool wants_one_buffer(const cvh_context *c, const Geometry &g) { return one_buffer_rule(c, g, run_is_alone(c)); }
+
+// The strips' shadow-row table (CVH_OB_TAB ints per strip, cvh_internal.h) from the strip table b[0 .. S]: a strip reads rows
+// max(s0 - 2, 0), s0 - 1 and s1 of its neighbours through its three shadow rows; each of those rows is written there by the strip that owns
+// it.  Strips without rows own nothing and need nothing.
+void one_buffer_table(const std::vector<int> &b, int h, std::vector<int> &tab)
+{
+  const int S = (int)b.size() - 1;
+  tab.assign((size_t)S * CVH_OB_TAB, -1);
+  std::vector<int> ne;
+  for (int k = 0; k < S; ++k) if (b[k + 1] > b[k]) ne.push_back(k);
+  for (size_t t = 0; t < ne.size(); ++t) {
+    const int k = ne[t], kp = t > 0 ? ne[t - 1] : -1, kn = t + 1 < ne.size() ? ne[t + 1] : -1, knn = t + 2 < ne.size() ? ne[t + 2] : -1;
+    const int s0 = b[k], s1 = b[k + 1];
+    int *T = &tab[(size_t)k * CVH_OB_TAB];
+    if (kp >= 0) T[0] = 3 * kp + 2;                          // first row: row s1 of the strip above
+    if (kn >= 0) {
+      T[1] = 3 * kn + 1;                                     // last row: row s0 - 1 of the strip below
+      if (s1 - s0 >= 2) T[3] = 3 * kn;                       // last row but one: its row s0 - 2
+      else if (s0 == 0) T[2] = 3 * kn;                       // (a one-row strip at the top: max(s0 - 2, 0) of the strip below is that row)
+    }
+    if (knn >= 0 && b[kn + 1] - b[kn] == 1) T[4] = 3 * knn;  // last row: row s0 - 2 of the strip behind a one-row strip
+    if (s0 > 0) { T[5] = s0 >= 2 ? s0 - 2 : 0; T[6] = s0 - 1; }
+    if (s1 < h) T[7] = s1;
+  }
+}
+
+// Called where a context's own per-launch launches are about to be enqueued, behind upload_strip_bounds: enters the one-buffer flow (the
+// slab takes the level set over from d_u[], with the pads and shadow rows of the parity the next launch reads), keeps it, or leaves it.
+int one_buffer_flow(cvh_context *c, const Geometry &g)
+{
+  if (!wants_one_buffer(c, g)) return one_buffer_leave(c);
+  const int pitch = cvh_ob_pitch(c->w, g.tiles_x), rows = cvh_ob_rows(c->h, g.tiles_y);
+  const int key[6] = {c->bounds_key[0], c->bounds_key[1], c->bounds_key[2], c->bounds_key[3], pitch, rows};
+  if (c->ob_live && !memcmp(key, c->ob_key, sizeof(key))) return CVH_OK;
+  int rc = c->ob_live ? one_buffer_leave(c) : settle(c);     // (another strip table: through the mirror)
+  if (rc == CVH_OK) rc = ensure_f64_mirror(c);
+  if (rc != CVH_OK) return rc;
+  const size_t bytes = (size_t)rows * pitch * sizeof(double);
+  if (bytes > c->ob_cap) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->d_ob) { HIPCHK(c, hipFree(c->d_ob)); c->d_ob = nullptr; c->ob_cap = 0; }
+    HIPCHK(c, hipMalloc((void **)&c->d_ob, bytes));
+    c->ob_cap = bytes;
+  }
+  // (cleared: the pads of the shadow rows are never written, and a lane that owns no pixel computes with what it reads there)
+  HIPCHK(c, hipMemsetAsync(c->d_ob, 0, bytes, c->stream));
+  if (!c->d_ob_tab) HIPCHK(c, hipMalloc((void **)&c->d_ob_tab, (size_t)(c->h + 1) * CVH_OB_TAB * sizeof(int)));
+  std::vector<int> tab;
+  one_buffer_table(c->h_bounds, c->h, tab);
+  if ((int)tab.size() != g.tiles_y * CVH_OB_TAB) return fail(c, CVH_ERR_STATE, "one-buffer flow: the strip table does not match the geometry");
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(c->d_ob_tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice));
+  const int par = (c->cur_base + c->enqueued) & 1;
+  HIPCHK(c, cvh_launch_ob_pack(c->d_u[par], c->d_ob, c->d_ob_tab, c->h, c->w, g.tiles_x, g.tiles_y, par, c->stream));
+  memcpy(c->ob_key, key, sizeof(key));
+  c->ob_live = true;
+  return CVH_OK;
+}
+
+// d_u[] takes the level set back (whatever is in flight is settled first).
+int one_buffer_leave(cvh_context *c)
+{
+  if (!c->ob_live) return CVH_OK;
+  const int rc = ensure_f64_mirror(c);
+  if (rc == CVH_OK) c->ob_live = false;
+  return rc;
+}
+
 // tiles_y x tiles_x tiles of <= 128 (three channels: 96) rows x 128 columns, at most one per CU.  Pure host arithmetic (also exported for
 // the CPU tests: cvh_debug_resident_grid).
 bool resident_tile_grid(int h, int w, int channels, int num_cus, int cap_blocks, ResidentGeom *rg)
@@ -178,6 +271,14 @@ void fill_args(const cvh_context *c, CvhStepArgs *a, int in_buf, int step)
   a->tile_rows = g.rows;
   a->strip_rows = g.strip_rows;
   a->fused_finalize = c->finalize_mode == 0;
+  if (wants_one_buffer(c, g)) {   // the slab is both; in_buf is the parity of the pads and shadow rows the launch reads
+    a->u_in = c->d_ob; a->u_out = c->d_ob;
+    a->one_buffer = 1;
+    a->ob_pitch = cvh_ob_pitch(c->w, g.tiles_x);
+    a->ob_rows = cvh_ob_rows(c->h, g.tiles_y);
+    a->ob_par = in_buf;
+    a->ob_tab = c->d_ob_tab;
+  }
   // src/main.cpp:985: dt * (mu*kappa - nu + u_diff/N) evaluates as one addWeighted
   a->alpha = c->p.mu * c->p.dt;
   a->beta = (1.0 / c->C) * c->p.dt;
@@ -285,6 +386,11 @@ int prepare(cvh_context *c)
       if (rc != CVH_OK) return rc;
       a.u_in = c->d_u[current_buffer(c)];
     }
+    if (a.one_buffer) {   // one-buffer flow: of the dense mirror as well
+      const int rc = ensure_f64_mirror(c);
+      if (rc != CVH_OK) return rc;
+      a.u_in = c->d_u[current_buffer(c)];
+    }
     int nparts = 0;
     HIPCHK(c, cvh_launch_init_sums(a, c->C, use_fast(c), &nparts, c->stream));
     a.nparts = nparts;
@@ -373,6 +479,7 @@ int upload_strip_bounds(cvh_context *c, const Geometry &g)
   compute_strip_bounds(g.strip, c->h, g.tiles_x, g.tiles_y, g.strip_rows, g.nblocks, cls, cskew, c->wave_skew, b);
   HIPCHK(c, hipStreamSynchronize(c->stream));  // launches already enqueued read the old table
   HIPCHK(c, hipMemcpy(c->d_bounds, b.data(), b.size() * sizeof(int), hipMemcpyHostToDevice));
+  c->h_bounds = b;
   memcpy(c->bounds_key, key, sizeof(key));
   return CVH_OK;
 }
@@ -455,9 +562,10 @@ static int ensure_step_graph(cvh_context *c, int parity)
 static int warm_impl(cvh_context *c, long nsteps)
 {
   if (nsteps > 0) c->run_chunk = (int)(nsteps < 1024 ? nsteps : 1024);   // (the caller announces its next enqueue)
-  { ResidentGeom rg; if (resident_geometry(c, &rg)) return CVH_OK; }   // one cooperative launch per chunk: nothing to capture
+  { ResidentGeom rg; if (resident_geometry(c, &rg)) return one_buffer_leave(c); }   // one cooperative launch per chunk: nothing to capture
   const Geometry g = resolve_geometry(c);
   if (g.strip >= 2) { const int rc = upload_strip_bounds(c, g); if (rc != CVH_OK) return rc; }
+  { const int rc = one_buffer_flow(c, g); if (rc != CVH_OK) return rc; }
   if (c->use_graph && nsteps >= kGraphSteps) {
     // every graph launch of one call starts on the same ping-pong parity / sum-set phase (kGraphSteps is a multiple of 4),
     // after the nsteps % kGraphSteps plain launches that enqueue_impl() issues first
@@ -489,6 +597,7 @@ int launch_resident(cvh_context *c, const ResidentGeom &rg, int nsteps, CvhLaunc
 {
   const int ntiles = rg.tr * rg.tc;
   if (!note) { const int rc = ensure_resident_buffers(c); if (rc != CVH_OK) return rc; }
+  if (!note) { const int rc = one_buffer_leave(c); if (rc != CVH_OK) return rc; }
   if (!note) { const int rc = flush_for_grid(c, -1); if (rc != CVH_OK) return rc; }
   constexpr int kMaxPerLaunch = 4096;
   for (int s = 0; s < nsteps || note;) {
@@ -524,6 +633,7 @@ static int enqueue_impl(cvh_context *c, int nsteps)
     if (resident_geometry(c, &rg)) return launch_resident(c, rg, nsteps, nullptr);
     const Geometry g = resolve_geometry(c);
     if (g.strip >= 2) { const int rc = upload_strip_bounds(c, g); if (rc != CVH_OK) return rc; }
+    { const int rc = one_buffer_flow(c, g); if (rc != CVH_OK) return rc; }
     const int rc = flush_for_grid(c, g.nblocks);
     if (rc != CVH_OK) return rc;
   }

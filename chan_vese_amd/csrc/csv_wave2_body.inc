@@ -137,15 +137,44 @@
     using raw2_t = typename IO::raw2_t;
     using raw1_t = typename IO::raw1_t;
     constexpr unsigned SB = IO::kBytes;                          // bytes of a level-set value in HBM
-    const unsigned rowbytes = (unsigned)w * SB, ubytes = (unsigned)h * rowbytes;
-    const unsigned voff_u = (unsigned)cl * SB;
+    // OB (one-buffer flow, csv_wave2_kernel.hip): rows of the padded slab; the cells other waves write are read from the pads / shadow rows
+    const unsigned pitch = OB ? (unsigned)a.ob_pitch : (unsigned)w;
+    const unsigned rowbytes = pitch * SB, ubytes = (unsigned)(OB ? a.ob_rows : h) * rowbytes;
+    // lane 0's halo pair: the west neighbour's slot A of the read parity; the east extra: the east neighbour's slot B
+    const unsigned voff_u = (OB && lane == 0 && wc > 0) ? (unsigned)cvh_ob_slot(w, nwc, a.ob_par, wc - 1, 0) * SB : (unsigned)cl * SB;
     const unsigned voff_st = lane_valid ? (unsigned)c0 * SB : kOobOffset;
-    const unsigned voff_x = ((unsigned)xrow * (unsigned)w + (unsigned)xcol) * SB;
+    const unsigned xoff = (OB && wc + 1 < nwc) ? (unsigned)cvh_ob_slot(w, nwc, a.ob_par, wc + 1, 1) : (unsigned)xcol;
+    const unsigned voff_x = ((unsigned)xrow * pitch + xoff) * SB;
+    // OB: the one added store of a row -- lane 63 writes its pair into slot A and lane 1 into slot B of the parity the NEXT launch reads, where
+    // a neighbour exists; every other lane's offset is out of range (the hardware drops it)
+    const unsigned voff_sh = !OB ? 0u
+        : (lane == 63 && wc + 1 < nwc) ? (unsigned)cvh_ob_slot(w, nwc, a.ob_par ^ 1, wc, 0) * SB
+        : (lane == 1 && wc > 0) ? (unsigned)cvh_ob_slot(w, nwc, a.ob_par ^ 1, wc, 1) * SB : kOobOffset;
     const __amdgpu_buffer_rsrc_t ru = make_rsrc(a.u_in, ubytes);
     const int ulast = s1 < h - 1 ? s1 : h - 1, ilast = s1 - 1;
-    auto U = [&](int r) -> raw2_t { return IO::load2(ru, voff_u, (unsigned)clampi(r, 0, ulast) * rowbytes); };
+    const int llast = OB ? ilast : ulast;     // the last row the plane itself is asked for: OB takes row s1 from the strip's shadow rows
+    // OB: the strip's shadow rows of the read parity (rows s0 - 2, s0 - 1, s1), first row of the written parity's, and where this strip's rows go
+    const int sh_rd = OB ? cvh_ob_shadow_row(h, nstrips, a.ob_par, 3 * ws) : 0, sh_wr = OB ? cvh_ob_shadow_row(h, nstrips, a.ob_par ^ 1, 0) : 0;
+    int pub[5] = {-1, -1, -1, -1, -1};
+    if (OB) {
+      const const_int_p t = (const_int_p)a.ob_tab + ws * CVH_OB_TAB;
+#pragma unroll
+      for (int q = 0; q < 5; ++q) pub[q] = t[q];
+    }
+    // the slab row that holds row r as this iteration found it (wave-uniform): rows of other strips come from the shadow rows
+    auto rowsel = [&](int r) -> int {
+      if (!OB) return clampi(r, 0, ulast);
+      if (r < s0) return s0 == 0 ? 0 : sh_rd + (r - (s0 - 2));
+      if (r >= s1) return s1 < h ? sh_rd + 2 : h - 1;
+      return r;
+    };
+    auto U = [&](int r) -> raw2_t { return IO::load2(ru, voff_u, (unsigned)rowsel(r) * rowbytes); };
     auto UX = [&](int r0) -> raw1_t {
-      if (r0 + R - 1 <= ulast) return IO::load1(ru, voff_x, (unsigned)r0 * rowbytes);
+      if (r0 + R - 1 <= llast) return IO::load1(ru, voff_x, (unsigned)r0 * rowbytes);
+      if (OB) {
+        const int rr = r0 + xrow;
+        return IO::load1(ru, ((unsigned)(rr >= s1 ? (s1 < h ? sh_rd + 2 : h - 1) : rr) * pitch + xoff) * SB, 0u);
+      }
       return IO::load1(ru, ((unsigned)clampi(r0 + xrow, 0, ulast) * (unsigned)w + (unsigned)xcol) * SB, 0u);
     };
     // image: 9 aligned 16-byte pieces per row, R rows by 9R lanes, staged in the per-wave tile
@@ -356,6 +385,7 @@
         hva = heaviside_strict(va, eps); hvb = heaviside_strict(vb, eps);
       }
       IO::store2(keep[k], make_rsrc(a.u_out, live ? ubytes : 0u), voff_st, (unsigned)i * rowbytes);
+      if (OB) IO::store2(keep[k], make_rsrc(a.u_out, live ? ubytes : 0u), voff_sh, (unsigned)i * rowbytes);   // the row's column shadow
       if (live) {
         if (FAST && DEFER && NEARFORM) {   // the sums of H follow behind the rows
           acc[2 + 2 * C] = __builtin_fma(uda, uda, acc[2 + 2 * C]); acc[2 + 2 * C] = __builtin_fma(udb, udb, acc[2 + 2 * C]);
@@ -429,6 +459,22 @@
         if (INTERIOR || (ib + k) < s1) row(ib + k, k, true, near_tag);   // wave-uniform: rows past the strip end cost nothing
         else near_mask[k] = 0ull;
       }
+      if (OB && !INTERIOR) {
+        // the rows other strips read of this one -- its first, its last and its last but one -- go into those strips' shadow rows of the written
+        // parity as well (wave-uniform; the strip's first group and its edge groups take this form)
+        auto put = [&](int k, int d) {
+          if (d >= 0) IO::store2(keep[k], make_rsrc(a.u_out, ubytes), voff_st, (unsigned)(sh_wr + d) * rowbytes);
+        };
+#pragma unroll
+        for (int k = 0; k < R; ++k) {
+          const int i = ib + k;
+          if (i < s1) {
+            if (i == s0) put(k, pub[0]);
+            if (i == s1 - 1) { put(k, pub[1]); put(k, pub[2]); put(k, pub[4]); }
+            if (i == s1 - 2) put(k, pub[3]);
+          }
+        }
+      }
       const bool any_near = DEFER && !NEARFORM && (near_mask[0] | near_mask[1] | near_mask[2] | near_mask[3]) != 0ull;
       // H_eps - 1/2 of row k's pair from keep[k]: TABLE true = the table form of every pixel (the rows of a NEARFORM group added nothing for H),
       // else the per-group correction of the lanes below the far-field threshold (the rows added the far form on every lane)
@@ -494,7 +540,19 @@
     // -- valid for any u, nothing to correct: one form per pixel instead of three (far + near + far again in the correction).
     const bool near_strip = DEFER && a.near_switch &&
         __builtin_popcountll(__builtin_amdgcn_ballot_w64(lane_valid && (fabs(u0.x) < fc.thr || fabs(u0.y) < fc.thr))) >= 32;
-    if (__builtin_expect(DEFER && near_strip, 0)) {   // cold for the register allocator: whatever has to spill spills in this copy, not in the far-field march
+    if (OB) {
+      // one-buffer flow: the strip's FIRST group takes the edge form too (it publishes row s0 to the strip above), and the interior form ends
+      // one row earlier (row s1 is a shadow row)
+      if (__builtin_expect(near_strip, 0)) {
+        if (ib < s1) { group(ib, std::false_type{}, std::true_type{}); ib += R; }
+        for (; ib + 2 * R <= llast; ib += R) group(ib, std::true_type{}, std::true_type{});
+        for (; ib < s1; ib += R) group(ib, std::false_type{}, std::true_type{});
+      } else {
+        if (ib < s1) { group(ib, std::false_type{}, std::false_type{}); ib += R; }
+        for (; ib + 2 * R <= llast; ib += R) group(ib, std::true_type{}, std::false_type{});
+        for (; ib < s1; ib += R) group(ib, std::false_type{}, std::false_type{});
+      }
+    } else if (__builtin_expect(DEFER && near_strip, 0)) {   // cold for the register allocator: whatever has to spill spills in this copy, not in the far-field march
       for (; ib + 2 * R <= ulast; ib += R) group(ib, std::true_type{}, std::true_type{});
       for (; ib < s1; ib += R) group(ib, std::false_type{}, std::true_type{});
     } else {

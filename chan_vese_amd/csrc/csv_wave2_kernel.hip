@@ -33,6 +33,7 @@ namespace {
 template <int C, bool FAST, int MINW, int POL, bool ST32>
 __global__ __launch_bounds__(CVH_BLOCK, MINW) void csv_wave2_kernel(const CvhStepArgs a)
 {
+  constexpr bool OB = false;
   const unsigned blk = blockIdx.x;
 #include "csv_wave2_body.inc"
 }
@@ -46,7 +47,49 @@ __global__ __launch_bounds__(CVH_BLOCK, MINW) void csv_wave2_batch_kernel(const 
   const CvhStepArgs *const ap = batch_member(b, &blk);
   if (!ap) return;   // padding of the member's section
   const CvhStepArgs &a = *ap;
+  constexpr bool OB = false;
 #include "csv_wave2_body.inc"
+}
+
+// One-buffer flow (one channel, FAST, FP64 state; no batch entry point): the same body with OB = true updates the level set in place in the
+// padded slab of cvh_internal.h (cvh_ob_*).  What a wave reads of cells that ANOTHER wave writes -- lane 0's halo pair, the east extra, the
+// rows s0 - 2, s0 - 1 and s1 around its strip -- comes from the row pads and the shadow rows of the launch's read parity, which their owners
+// wrote one iteration earlier; every wave writes the other parity beside its rows.  Its own rows it has loaded before it stores them.
+template <int POL>
+__global__ __launch_bounds__(CVH_BLOCK, 3) void csv_wave2_ob_kernel(const CvhStepArgs a)
+{
+  constexpr int C = 1, MINW = 3;
+  constexpr bool FAST = true, ST32 = false, OB = true;
+  const unsigned blk = blockIdx.x;
+#include "csv_wave2_body.inc"
+}
+
+// dense plane -> slab: workgroup r < h copies row r and fills its pad of parity `par`; workgroup h + q fills shadow row q of that parity
+__global__ __launch_bounds__(CVH_BLOCK) void ob_pack_kernel(const double *dense, double *slab, const int *tab, int h, int w, int nwc, int nstrips, int par)
+{
+  const int pitch = cvh_ob_pitch(w, nwc), r = (int)blockIdx.x;
+  if (r < h) {
+    const double *src = dense + (size_t)r * w;
+    double *dst = slab + (size_t)r * pitch;
+    for (int j = threadIdx.x; j < w; j += CVH_BLOCK) dst[j] = src[j];
+    for (int q = threadIdx.x; q < 4 * nwc; q += CVH_BLOCK) {
+      const int wc = q >> 2, b = (q >> 1) & 1, col = W2 * wc + (b ? 0 : W2 - 2) + (q & 1);
+      dst[cvh_ob_slot(w, nwc, par, wc, b) + (q & 1)] = col < w ? src[col] : 0.0;
+    }
+    return;
+  }
+  const int q = r - h, from = tab[(q / 3) * CVH_OB_TAB + 5 + q % 3];
+  if (from < 0) return;
+  const double *src = dense + (size_t)from * w;
+  double *dst = slab + (size_t)cvh_ob_shadow_row(h, nstrips, par, q) * pitch;
+  for (int j = threadIdx.x; j < w; j += CVH_BLOCK) dst[j] = src[j];
+}
+
+__global__ __launch_bounds__(CVH_BLOCK) void ob_unpack_kernel(const double *slab, double *dense, int w, int pitch)
+{
+  const double *src = slab + (size_t)blockIdx.x * pitch;
+  double *dst = dense + (size_t)blockIdx.x * w;
+  for (int j = threadIdx.x; j < w; j += CVH_BLOCK) dst[j] = src[j];
 }
 
 template <int C, bool FAST, int MINW, int POL, bool ST32 = false>
@@ -61,9 +104,29 @@ hipError_t launch_wave2(const CvhStepArgs &a, hipStream_t s, const CvhBatchLaunc
   return hipGetLastError();
 }
 
+template <int POL>
+hipError_t launch_wave2_ob(const CvhStepArgs &a, hipStream_t s)
+{
+  using L = Wave2Smem<true, 1>;
+  CVH_LAUNCH((csv_wave2_ob_kernel<POL>), a.nparts + (a.chain ? 1 : 0), L::bytes, s, a, "csv_wave2_ob_kernel<%d>", POL);
+  return hipGetLastError();
+}
+
 }  // namespace
 
 int cvh_wave2_cols() { return W2; }
+
+hipError_t cvh_launch_ob_pack(const double *dense, double *slab, const int *tab, int h, int w, int nwc, int nstrips, int par, hipStream_t s)
+{
+  hipLaunchKernelGGL(ob_pack_kernel, dim3(h + 3 * nstrips), dim3(CVH_BLOCK), 0, s, dense, slab, tab, h, w, nwc, nstrips, par);
+  return hipGetLastError();
+}
+
+hipError_t cvh_launch_ob_unpack(const double *slab, double *dense, int h, int w, int nwc, hipStream_t s)
+{
+  hipLaunchKernelGGL(ob_unpack_kernel, dim3(h), dim3(CVH_BLOCK), 0, s, slab, dense, w, cvh_ob_pitch(w, nwc));
+  return hipGetLastError();
+}
 
 // Instantiations <channels, FAST, waves per SIMD, cache policy of the rows, FP32 state>: <1, false, 2, 1, false> STRICT; <1 | 3, true, 3,
 // POL, false> FAST (wave2_device.h: POL 1 write-through stores + sc0 loads, 0 plain, 2 plain stores + non-temporal loads -- diagnostic);
@@ -78,6 +141,10 @@ hipError_t cvh_launch_wave2(const CvhStepArgs &a, int channels, int fast, hipStr
   }
   if (channels == 3) return a.wave_pol ? launch_wave2<3, true, 3, 1>(a, s, batch) : launch_wave2<3, true, 3, 0>(a, s, batch);   // FAST only (api.hip routes STRICT to kernel 2)
   if (!fast) return launch_wave2<1, false, 2, 1>(a, s, batch);
+  if (a.one_buffer) {   // csv_run.hip selects it for a context's own launches only, with "wave_pol" 0 or 1
+    if (batch || a.wave_pol == 2) return hipErrorInvalidValue;
+    return a.wave_pol ? launch_wave2_ob<1>(a, s) : launch_wave2_ob<0>(a, s);
+  }
   if (a.wave_pol == 2) return launch_wave2<1, true, 3, 2>(a, s, batch);
   return a.wave_pol ? launch_wave2<1, true, 3, 1>(a, s, batch) : launch_wave2<1, true, 3, 0>(a, s, batch);
 }

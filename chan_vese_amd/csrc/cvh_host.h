@@ -28,6 +28,10 @@
 // elements -- rows, edges, points, slots -- and hands that count to its kernels (grow_table_to); free_table frees either
 struct DeviceTable { void *d = nullptr; size_t cap = 0, count = 0; };
 
+// One-buffer flow of the 2-pixel kernel: what option "one_buffer" starts as (DESIGN.md 4.1 holds the measurement that decides it), and the
+// footprint the Infinity Cache holds reliably (tools/mall_sweep_probe.hip: at <= ~204 MB a ping-pong stream stays in the fast regime)
+constexpr int CVH_ONE_BUFFER_DEFAULT = -1;
+constexpr double kCachedFootprint = 205e6;
 constexpr int kGraphSteps = 16;   // steps per captured graph (even: the ping-pong parity repeats)
 struct StepGraph { hipGraphExec_t exec = nullptr; CvhStepArgs key[4]; int kind = -1, flavour = -1; };
 struct BatchCache;   // the device tables of a fused batch whose first member this context is (cvh_enqueue_steps_batch)
@@ -60,6 +64,10 @@ struct cvh_context {   // opaque to callers; four groups
   double *d_atan = nullptr;
   CvhChainAcc *d_chain = nullptr;   // chain mode of the 2-pixel wave kernel (cvh_internal.h, CvhChainAcc)
   int *d_bounds = nullptr;      // wave kernel: first row of every strip, [tiles_y + 1]
+  std::vector<int> h_bounds;    // the table d_bounds holds (upload_strip_bounds)
+  double *d_ob = nullptr;       // one-buffer flow: the padded slab (cvh_internal.h, cvh_ob_*), allocated on first use, grown on demand
+  size_t ob_cap = 0;            // its bytes
+  int *d_ob_tab = nullptr;      // and the strips' shadow-row table, [h][CVH_OB_TAB]
   unsigned long long *d_isums = nullptr, *h_isums = nullptr;   // image_sums_kernel (io_kernels.hip): {sum p, sum p^2} per plane (device / pinned)
   unsigned long long *d_dbg = nullptr;  // diagnostic stamps (option "debug_times")
   size_t dbg_words = 0;
@@ -79,6 +87,11 @@ struct cvh_context {   // opaque to callers; four groups
   // option "state" = 32 (declared FP32-state mode): the iteration kernels read and write d_uf[]; d_u[] stays the exchange format of
   // set / get / mask / contour / selection and of the initial sums -- a mirror, refreshed lazily (ensure_f64_mirror)
   bool mirror_valid = true;     // d_u[current] holds the level set (always true with 64-bit state)
+  // one-buffer flow (csv_run.hip, one_buffer_flow): while ob_live the padded slab d_ob holds the level set and d_u[] is its mirror, refreshed
+  // lazily like the FP32 state's (mirror_valid, ensure_f64_mirror).  Entered and left by one_buffer_flow / one_buffer_leave alone; a new
+  // level set (levelset_arrived) lands in d_u[] and ends it.
+  bool ob_live = false;
+  int ob_key[6] = {0, 0, 0, 0, 0, 0};   // the strip table (bounds_key) and slab geometry the shadow rows were filled for
   int cur_base = 0;   // buffer that held u when the run counter was last reset
   int enqueued = 0;   // steps enqueued since then
   int steps_done = 0; // as of the last sync
@@ -96,6 +109,7 @@ struct cvh_context {   // opaque to callers; four groups
   mutable int run_alone = -1;   // 1: no other co-resident context on the device when the run started (automatic resident flow allowed; taken in run_is_alone)
   int run_chunk = -1;           // iterations of the enqueue at hand (cvh_enqueue_steps / cvh_warm: their argument; cvh_run: its chunk) -- how long a cooperative launch would be (-1: nothing announced yet; the enqueue entry points announce it)
   int geom_cus = 0;             // > 0: the CUs the automatic strip count is sized for (a fused batch: this context's share of the chip; batch_share)
+  bool in_batch = false;        // a fused batch is preparing or enqueuing this member's launches (batch_share): they iterate the ping-pong pair
   double stop_cond_h = 0.0; // tol * stop_norm of the current run (a launch argument; prepare_host)
   float last_run_ms = 0.f, last_pm_ms = 0.f;
   float last_reinit_ms = 0.f;   // device interval (table copy, three launches, flag copy) of the last reinitialisation this context led
@@ -111,6 +125,7 @@ struct cvh_context {   // opaque to callers; four groups
   int wave_minw = 5, wave_lds_cap = 0, wave_prio = 1, wave_sync = -1 /* auto: 1 channel 1, 3 channels 0 */, wave_imgv = 1, wave_depth = 4;
   int res_prio = 1;     // option "res_prio": resident kernels, priority by quarters of a wave's band (csv_resident_kernel.hip)
   int res_go_share = 5;  // option "res_go_share": log2 of the tiles of an XCD that share one release line of the resident kernel (0: a line per tile, 5: a line per XCD, 6: one line)
+  int one_buffer = CVH_ONE_BUFFER_DEFAULT;   // option "one_buffer": the 2-pixel kernel updates ONE padded level-set buffer in place (-1 auto by footprint, 0 off, 1 on wherever the flow exists)
   int wave_seam = 1;    // option "wave_seam": a strip's final group runs without prefetch and park in the 2-pixel kernel (csv_wave2_body.inc); 0 = with both
   int near_switch = 1;  // option "near_switch": per-wave, per-group choice of the form of H_eps (csv_wave2_kernel.hip); 0 = far form + correction always
   int wave_rev = 0, wave_xcd = 1;
@@ -239,6 +254,11 @@ int prepare_host(cvh_context *c);
 int prepare(cvh_context *c);
 void compute_strip_bounds(int kind, int h, int tiles_x, int S, int strip_rows, int nblocks, int cls, int cskew, int skew, std::vector<int> &b);
 int upload_strip_bounds(cvh_context *c, const Geometry &g);
+bool one_buffer_rule(const cvh_context *c, const Geometry &g, bool alone);
+bool wants_one_buffer(const cvh_context *c, const Geometry &g);
+void one_buffer_table(const std::vector<int> &b, int h, std::vector<int> &tab);
+int one_buffer_flow(cvh_context *c, const Geometry &g);
+int one_buffer_leave(cvh_context *c);
 int launch_one_step(cvh_context *c, int in_buf, int step, bool capturing = false, CvhLaunchNote *note = nullptr);
 int flush_for_grid(cvh_context *c, int nparts);
 int ensure_resident_buffers(cvh_context *c);

@@ -141,7 +141,25 @@ struct CvhStepArgs {
   int res_prio;                  // resident kernels: a wave lowers its priority with every quarter of its band (the two waves of a SIMD finish together)
   int res_band_rows;             // rows per wave when every tile has 8 x that many rows (2, 4, 8, 16: straight-line march), else 0
   int res_go_shift;              // 2^shift tiles of one XCD share a release line (csv_resident_kernel.hip, go_line)
+  // one-buffer flow of the 2-pixel wave kernel (csv_wave2_ob_kernel, csv_wave2_kernel.hip; cvh_ob_* below): u_in == u_out == the padded slab
+  int one_buffer;                // 1: this launch updates the level set in place
+  int ob_pitch;                  // doubles per row of the slab: w columns + the column shadow (cvh_ob_pitch)
+  int ob_rows;                   // rows of the slab: h of the plane + 2 x 3 shadow rows per strip
+  int ob_par;                    // parity of the shadow this launch READS (it writes the other one)
+  const int *ob_tab;             // [tiles_y][CVH_OB_TAB] shadow-row table of the strips (cvh_ob_fill_table)
 };
+
+// One-buffer flow: the slab's layout, shared by the kernel, the pack / unpack kernels and the host.
+//   row r of the plane (pitch doubles): [w columns][parity 0: per wave-column {A.x A.y B.x B.y}][parity 1: the same] -- A is the pair of
+//   the wave-column's lane 63 (the halo pair of its east neighbour's lane 0), B the pair of its lane 1 (B.x is the east extra of its west
+//   neighbour); behind the h rows, per parity and strip three shadow rows: rows s0 - 2, s0 - 1 and s1 of the strip as they were when the
+//   iteration of that parity began.  Parity p of the pads and shadow rows belongs to the iterations that read buffer p of the pair.
+#define CVH_OB_TAB 8   // ints per strip: [0] where its first row goes, [1] [2] [4] where its last row goes, [3] its last row but one (shadow-row
+                       // index strip * 3 + j, -1 none); [5 .. 7] the plane rows its own three shadow rows are copies of (-1 none)
+__host__ __device__ constexpr int cvh_ob_pitch(int w, int nwc) { return (w + 8 * nwc + 15) & ~15; }
+__host__ __device__ constexpr int cvh_ob_slot(int w, int nwc, int par, int wc, int b) { return w + 4 * nwc * par + 4 * wc + 2 * b; }   // in doubles
+__host__ __device__ constexpr int cvh_ob_rows(int h, int nstrips) { return h + 6 * nstrips; }
+__host__ __device__ constexpr int cvh_ob_shadow_row(int h, int nstrips, int par, int idx) { return h + 3 * nstrips * par + idx; }
 
 // Fused batch (cvh_enqueue_steps_batch, api.hip): one grid holds the sections of several contexts, each the context's own grid
 // (nparts workgroups + the chain-mode bookkeeper) padded to a multiple of 8 workgroups, so that blockIdx.x & 7 still names the
@@ -405,6 +423,9 @@ hipError_t cvh_launch_step(const CvhStepArgs &a, int channels, int fast, hipStre
 int cvh_wave2_cols();
 // batch non-null: the same instantiation's batch entry point over a fused grid (a = any member's arguments: selects the flavour)
 hipError_t cvh_launch_wave2(const CvhStepArgs &a, int channels, int fast, hipStream_t s, const CvhBatchLaunch *batch = nullptr);
+// one-buffer flow (csv_wave2_kernel.hip): dense plane -> slab with the pads and shadow rows of parity `par`; slab -> dense plane
+hipError_t cvh_launch_ob_pack(const double *dense, double *slab, const int *tab, int h, int w, int nwc, int nstrips, int par, hipStream_t s);
+hipError_t cvh_launch_ob_unpack(const double *slab, double *dense, int h, int w, int nwc, hipStream_t s);
 hipError_t cvh_launch_chain_flush(const CvhStepArgs &a, int channels, hipStream_t s);
 size_t cvh_pm_resident_lds_bytes();
 int cvh_pm_resident_halo_doubles();

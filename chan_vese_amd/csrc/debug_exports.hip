@@ -32,6 +32,30 @@ extern "C" int cvh_debug_data_flow(int h, int w, int channels, int math_mode, in
   return CVH_OK;
 }
 
+// Diagnostic (not part of include/chanvese_hip.h): does the one-buffer flow of the 2-pixel kernel run (one_buffer_rule, csv_run.hip) for a
+// shape and option set, without a device -- `live` = the co-resident contexts on the device (1: this one alone), `option` = "one_buffer".
+extern "C" int cvh_debug_one_buffer(int h, int w, int channels, int math_mode, int kernel, int state_bits, int num_cus, int live, double tol,
+                                    int option)
+{
+  if (h < 1 || w < 1 || (channels != 1 && channels != 3)) return -1;
+  cvh_context c;
+  c.h = h; c.w = w; c.C = channels; c.n = (size_t)h * (size_t)w;
+  c.math_mode = math_mode; c.kernel = kernel; c.state_bits = state_bits; c.num_cus = num_cus > 0 ? num_cus : 256;
+  c.p.tol = tol; c.one_buffer = option;
+  return one_buffer_rule(&c, resolve_geometry(&c), live <= 1) ? 1 : 0;
+}
+
+// Diagnostic (not part of include/chanvese_hip.h): the one-buffer flow's shadow-row table (one_buffer_table, csv_run.hip) of a strip table
+// b[0 .. S]; out needs S * 8 ints.
+extern "C" int cvh_debug_one_buffer_table(const int *b, int S, int h, int *out)
+{
+  if (!b || !out || S < 1) return CVH_ERR_ARG;
+  std::vector<int> tab;
+  one_buffer_table(std::vector<int>(b, b + S + 1), h, tab);
+  memcpy(out, tab.data(), tab.size() * sizeof(int));
+  return CVH_OK;
+}
+
 // Diagnostic (not part of include/chanvese_hip.h): the grid section and the work of ONE member of h x w pixels in a member-table kernel,
 // without a device -- from the very functions the host units size a member's section with.  *items: the units the section's lanes, waves
 // or workgroups share out; *nblk: its workgroups; *takers: how many units a workgroup takes per trip (CVH_BLOCK lanes, CVH_BLOCK / 64

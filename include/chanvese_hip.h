@@ -138,6 +138,14 @@ int cvh_set_params(cvh_context *ctx, const cvh_params *p);
  *   "near_switch"    1 (default): a wave whose strip / band starts where most pixels are below the far-field threshold of H_eps (32 eps)
  *                    evaluates the table form of H_eps on every pixel of that strip (one form per pixel: a level set that is near
  *                    everywhere, e.g. dt << 1); 0: the far-field series with the per-group correction everywhere
+ *   "one_buffer"     2-pixel wave kernel, one channel, FAST arithmetic, FP64 state, a context's own launches of a run that cannot stop
+ *                    (tol == 0): the iterations update ONE padded level-set buffer in place instead of the ping-pong pair; what a wave
+ *                    reads of its neighbours comes from row pads and shadow rows, double-buffered by iteration parity.
+ *                    -1 (default): automatic -- a single live context whose pair (with the image) exceeds what the 256 MiB Infinity
+ *                    Cache holds while one buffer fits (4096^2: 285 against 160 MB), in the automatic geometry ("kernel", "strip_rows",
+ *                    "strips" and the strip skews untouched); 0: the pair; 1: one buffer wherever the flow
+ *                    exists.  The results are the same bit for bit (tests/test_gpu_one_buffer.py).  Every caller of the level set
+ *                    (get, mask, set, the device-side calls) sees the dense plane: the padded buffer is converted on demand.
  *   "wave_seam"      2-pixel wave kernel, FAST arithmetic: 1 (default): the final group of a strip requests and parks no rows, east
  *                    extra or image pieces of a group that does not exist; 0: it does, like every other group.  The results are the
  *                    same bit for bit (tests/test_gpu_wave2_seam.py); the key exists for that comparison.  (The name is the seam of a
@@ -304,7 +312,7 @@ int cvh_last_pm_ms(cvh_context *ctx, float *ms);
  * the reference: the kernel is an implementation detail; bench.py names it in its roofline object and profiles/ are
  * matched against it).  phase 0: the CSV step as the next cvh_run / cvh_enqueue_steps launches it with the current
  * options -- kernel=<instantiation as rocprofv3 prints it> grid= block= lds_bytes= strips= strip_rows= chain= wave_pol=
- * math= steps_per_graph= wave_seam=; phase 1: what the last cvh_perona_malik launched (CVH_ERR_STATE before the first).
+ * math= steps_per_graph= wave_seam= one_buffer=; phase 1: what the last cvh_perona_malik launched (CVH_ERR_STATE before the first).
  * Launches nothing.  Truncates to cap - 1 characters. */
 int cvh_launch_info(cvh_context *ctx, int phase, char *buf, int cap);
 
