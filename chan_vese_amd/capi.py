@@ -44,6 +44,7 @@ EXPORTS = [
     "cvh_measure", "cvh_measure_batch", "cvh_region_shape_of",
     "cvh_overlaps", "cvh_overlaps_device", "cvh_overlaps_device_batch", "cvh_match_overlaps",
     "cvh_contours", "cvh_contours_device", "cvh_contours_device_batch",
+    "cvh_contours_subpixel", "cvh_contours_subpixel_device", "cvh_contours_subpixel_device_batch", "cvh_contour_subpixel_measure",
     "cvh_get_mask_morph", "cvh_get_mask_morph_device", "cvh_get_mask_morph_device_batch", "cvh_morph_levelset", "cvh_morph_levelset_batch",
     "cvh_init_mask", "cvh_init_mask_device", "cvh_init_mask_device_batch",
 ]
@@ -358,6 +359,11 @@ def lib():
         "cvh_contours_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, C.c_int, vp, C.c_long, vp, C.c_long, lp, lp, vp]),
         "cvh_contours_device_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, C.c_int, C.POINTER(vp), lp,
                                                 C.POINTER(vp), lp, lp, lp, vp]),
+        "cvh_contours_subpixel": (C.c_int, [vp, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, vp, C.c_long, vp, C.c_long, lp, lp]),
+        "cvh_contours_subpixel_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, vp, C.c_long, vp, C.c_long, lp, lp, vp]),
+        "cvh_contours_subpixel_device_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, C.POINTER(vp), lp,
+                                                         C.POINTER(vp), lp, lp, lp, vp]),
+        "cvh_contour_subpixel_measure": (C.c_int, [vp, C.c_long, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "cvh_get_mask_morph": (C.c_int, [vp, u8p, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, C.c_int, C.c_uint32]),
         "cvh_get_mask_morph_device": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, C.c_int, C.c_uint32, vp]),
         "cvh_get_mask_morph_device_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.POINTER(vp), C.c_int, C.c_int, C.c_long, C.c_long, C.c_int,
@@ -990,20 +996,14 @@ def match_overlaps(rows, threshold=(1, 2)):
     return ObjectScore(int(m.objects_a), int(m.objects_b), int(m.tp), int(m.fp), int(m.fn), tp_at), match_of_a, ious
 
 
-def contours_batch(contexts, d_points=None, point_caps=None, conn=8, invert=False, min_area=0, fill_holes=0, keep_largest=False, simplify=True,
-                   loop_caps=None, stream=0):
-    """cvh_contours_device_batch: Context.contours for n contexts (any mix of shapes and channel counts) with one set of launches.
-    d_points: None (no points), or per member the integer address of device memory for point_caps[i] points (two int32 each; 0: none
-    for that member).  loop_caps: None (every row, at the price of a first call for the counts) or one number per member.  Returns
-    [(nloops, npoints, loops)] per context, loops a structured array (CONTOUR_LOOP_DTYPE) of the first min(nloops, cap) rows; rows and
-    points are bit for bit the member's own Context.contours()."""
+def _contours_batch(fn, args, contexts, d_points, point_caps, loop_caps, stream):
+    """cvh_contours_device_batch or cvh_contours_subpixel_device_batch (fn) with the options args: what contours_batch documents"""
     contexts = list(contexts)
     n = len(contexts)
-    args = _clean_args(conn, invert, min_area, fill_holes, keep_largest) + (int(bool(simplify)),)
     longs = C.c_long * max(n, 1)
     nloops, npoints = longs(), longs()
     if loop_caps is None:
-        _batch_chk(lib().cvh_contours_device_batch(_member_array(contexts), n, *args, None, None, None, None, nloops, npoints, int(stream) or None))
+        _batch_chk(fn(_member_array(contexts), n, *args, None, None, None, None, nloops, npoints, int(stream) or None))
         loop_caps = [nloops[i] for i in range(n)]
     loop_caps = [int(c) for c in loop_caps]
     if len(loop_caps) != n:
@@ -1016,9 +1016,49 @@ def contours_batch(contexts, d_points=None, point_caps=None, conn=8, invert=Fals
         if len(d_points) != n or len(point_caps) != n:
             raise ValueError(f"{n} contexts but {len(d_points)} point arrays and {len(point_caps)} caps")
         pptrs, pcaps = (C.c_void_p * max(n, 1))(*d_points), longs(*point_caps)
-    _batch_chk(lib().cvh_contours_device_batch(_member_array(contexts), n, *args, tptrs, longs(*loop_caps), pptrs, pcaps, nloops, npoints,
-                                               int(stream) or None))
+    _batch_chk(fn(_member_array(contexts), n, *args, tptrs, longs(*loop_caps), pptrs, pcaps, nloops, npoints, int(stream) or None))
     return [(nloops[i], npoints[i], tables[i][:min(nloops[i], tables[i].size)].copy()) for i in range(n)]
+
+
+def contours_batch(contexts, d_points=None, point_caps=None, conn=8, invert=False, min_area=0, fill_holes=0, keep_largest=False, simplify=True,
+                   loop_caps=None, stream=0):
+    """cvh_contours_device_batch: Context.contours for n contexts (any mix of shapes and channel counts) with one set of launches.
+    d_points: None (no points), or per member the integer address of device memory for point_caps[i] points (two int32 each; 0: none
+    for that member).  loop_caps: None (every row, at the price of a first call for the counts) or one number per member.  Returns
+    [(nloops, npoints, loops)] per context, loops a structured array (CONTOUR_LOOP_DTYPE) of the first min(nloops, cap) rows; rows and
+    points are bit for bit the member's own Context.contours()."""
+    args = _clean_args(conn, invert, min_area, fill_holes, keep_largest) + (int(bool(simplify)),)
+    return _contours_batch(lib().cvh_contours_device_batch, args, contexts, d_points, point_caps, loop_caps, stream)
+
+
+def contours_subpixel_batch(contexts, d_points=None, point_caps=None, conn=8, invert=False, min_area=0, fill_holes=0, keep_largest=False,
+                            loop_caps=None, stream=0):
+    """cvh_contours_subpixel_device_batch: Context.contours_subpixel for n contexts with one set of launches -- contours_batch without
+    simplify; a point is two float64 (16 bytes, the address 8-byte aligned).  Rows and points are bit for bit the member's own
+    Context.contours_subpixel()."""
+    args = _clean_args(conn, invert, min_area, fill_holes, keep_largest)
+    return _contours_batch(lib().cvh_contours_subpixel_device_batch, args, contexts, d_points, point_caps, loop_caps, stream)
+
+
+def contour_subpixel_measures(loops, points):
+    """cvh_contour_subpixel_measure for every loop of Context.contours_subpixel(): (area, length), two float64 arrays with one entry per
+    loop -- the polygon's signed area (positive for an outer boundary, negative for a hole) and its perimeter, each a sequential FP64
+    sum over the loop's points in order.  Host arithmetic, no device."""
+    loops = np.ascontiguousarray(loops, dtype=CONTOUR_LOOP_DTYPE).reshape(-1)
+    points = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 2)
+    area, length = np.zeros(loops.size), np.zeros(loops.size)
+    spare = np.zeros(2)   # (an address for a loop without points)
+    L = lib()
+    for k in range(loops.size):
+        first, n = int(loops["offset"][k]), int(loops["points"][k])
+        if first + n > points.shape[0]:
+            raise ValueError(f"loop {k}: points {first} .. {first + n - 1} of {points.shape[0]}")
+        a, ln = C.c_double(0.0), C.c_double(0.0)
+        rc = L.cvh_contour_subpixel_measure(points.ctypes.data + 16 * first if n else spare.ctypes.data, n, C.byref(a), C.byref(ln))
+        if rc != CVH_OK:
+            raise CvhError(rc, f"cvh_contour_subpixel_measure: loop {k}, {n} points")
+        area[k], length[k] = a.value, ln.value
+    return area, length
 
 
 def region_shapes(table, channels):
@@ -1398,6 +1438,21 @@ class Context:
             nloops, npoints = C.c_long(0), C.c_long(0)
             args = _clean_args(conn, invert, min_area, fill_holes, keep_largest) + (int(bool(simplify)),)
             _batch_chk(self._L.cvh_contours(self._h, *args, loops.ctypes.data, nl, points.ctypes.data, npts, C.byref(nloops), C.byref(npoints)))
+        return loops, points
+
+    def contours_subpixel(self, conn=8, invert=False, min_area=0, fill_holes=0, keep_largest=False):
+        """cvh_contours_subpixel: the zero level of the level set as ordered closed polygons -- the loops of contours(simplify=False) for
+        the same five options, each lattice point replaced by the point where u changes sign across that edge (the edge's midpoint
+        where it does not: the plane's border, a pixel cleaning reclassified, NaN, zeros, infinities).  Returns (loops, points): loops
+        as contours() gives them with simplify=False, points a float64 array (P, 2) of x, y with pixel centres at half-integers.
+        COSTS TWO TRACES (the counts size the arrays).  Only reads: a run continued after it is bit-identical to one without."""
+        args = _clean_args(conn, invert, min_area, fill_holes, keep_largest)
+        nloops, npoints = C.c_long(0), C.c_long(0)
+        _batch_chk(self._L.cvh_contours_subpixel(self._h, *args, None, 0, None, 0, C.byref(nloops), C.byref(npoints)))
+        nl, npts = nloops.value, npoints.value
+        loops, points = np.zeros(nl, dtype=CONTOUR_LOOP_DTYPE), np.zeros((npts, 2), dtype=np.float64)
+        if nl:
+            _batch_chk(self._L.cvh_contours_subpixel(self._h, *args, loops.ctypes.data, nl, points.ctypes.data, npts, C.byref(nloops), C.byref(npoints)))
         return loops, points
 
     def get_mask_clean(self, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False):

@@ -15,7 +15,9 @@
 //     sums      edges, points and area2 per loop: runs of one loop inside a wave are combined first (ballots, a segmented 64-bit
 //               reduction), one set of 64-bit / 32-bit vector atomics per run -- a plane that is one loop sends one set per wave
 //     offsets   points summed per 256 loops, scan, then the exclusive prefix: offset; the point count
-//     scatter   every (corner) edge writes its tail vertex at offset + (points - weight in front of the head) mod points
+//     scatter   every (corner) edge writes its tail vertex at offset + (points - weight in front of the head) mod points -- or, for
+//               cvh_contours_subpixel* (every edge a point), the zero level's crossing of the edge at that place: two doubles, gathered
+//               from the level set (the ONE use of floating point here; the member's src2 is then double x, y)
 #include "cvh_internal.h"
 
 namespace {
@@ -26,6 +28,7 @@ typedef unsigned quad __attribute__((ext_vector_type(4)));   // one 16-byte load
 typedef CVH_GLOBAL quad *gquads;
 __device__ __forceinline__ quad make_quad(unsigned x, unsigned y, unsigned z, unsigned w) { quad q = {x, y, z, w}; return q; }
 typedef CVH_GLOBAL const uint8_t *gbytes;
+typedef double point2 __attribute__((ext_vector_type(2), aligned(8)));   // a subpixel point, x then y: one 16-byte store to an 8-byte aligned place
 
 static_assert(CVH_BLOCK == 256, "the per-wave counts below are summed as four waves");
 static_assert(sizeof(cvh_contour_loop) == 32, "a loop row is 32 bytes");
@@ -369,6 +372,51 @@ __global__ void __launch_bounds__(CVH_BLOCK) contour_scatter_kernel(const CvhIoM
   }
 }
 
+// direction k of an edge: the step from its pixel to the neighbour across it, as (columns, rows)
+__device__ __forceinline__ void across(unsigned k, int *dx, int *dy)
+{
+  *dx = k == 1 ? 1 : (k == 3 ? -1 : 0);
+  *dy = k == 2 ? 1 : (k == 0 ? -1 : 0);
+}
+
+// the scatter of cvh_contours_subpixel* ("Subpixel contours"; the trace ran with every weight 1): every edge writes, at the place of
+// its tail vertex, the point where the zero level crosses the segment between the centres of its pixel and the neighbour across it.
+// levels: the mask launches' table of the same members, src the FP64 level set.  FP64 as written: a division, a product with -1, 0 or 1
+// and a sum, one rounding each (the build contracts nothing)
+__global__ void __launch_bounds__(CVH_BLOCK) contour_scatter_subpixel_kernel(const CvhIoMember *tab, int nmem, int res, const CvhIoMember *levels,
+                                                                            int invert)
+{
+  const CvhIoMember *m = section(tab, nmem);
+  if (!m->src2) return;   // (no points for this member: wave-uniform)
+  const unsigned E = edges_of(m), stride = m->nblk * CVH_BLOCK, w = (unsigned)m->w;
+  const int h = m->h;
+  const unsigned long long cap = (unsigned long long)(unsigned)m->h2 | ((unsigned long long)(unsigned)m->w2 << 32);
+  const EdgeSpace s = edge_space(m);
+  const CVH_GLOBAL double *u = (const CVH_GLOBAL double *)levels[m - tab].src;
+  const double sign = invert ? -1.0 : 1.0;
+  CVH_GLOBAL point2 *out = (CVH_GLOBAL point2 *)m->src2;
+  for (unsigned e = (blockIdx.x - m->first) * CVH_BLOCK + threadIdx.x; e < E; e += stride) {
+    const quad a = s.buf[res][e];
+    const unsigned loop = ((gwords)(s.buf[res ^ 1] + a.y))[0];
+    if (loop >= (unsigned)m->sums[1]) continue;   // (never a row that does not exist)
+    const CVH_GLOBAL cvh_contour_loop *row = s.rows + loop;
+    const unsigned long long at = row->offset + (a.y == e ? 0u : row->points - a.z);
+    if (at >= cap) continue;
+    const unsigned id = s.id[e], p = id >> 2;
+    const int r = (int)(p / w), c = (int)(p % w);
+    int dx, dy;
+    across(id & 3u, &dx, &dy);
+    const int rq = r + dy, cq = c + dx;
+    double t = 0.5;
+    if (rq >= 0 && rq < h && cq >= 0 && cq < (int)w) {
+      const double va = sign * u[p], vb = sign * u[(size_t)rq * w + (unsigned)cq], d = va - vb;
+      if (va > 0.0 && vb <= 0.0 && __builtin_isfinite(d)) t = va / d;
+    }
+    point2 xy = {((double)c + 0.5) + (double)dx * t, ((double)r + 0.5) + (double)dy * t};
+    out[at] = xy;
+  }
+}
+
 }  // namespace
 
 unsigned cvh_contour_scan_trip() { return 64; }   // counts per trip of contour_scan_kernel's one wave
@@ -408,9 +456,10 @@ hipError_t cvh_launch_contours_count(const CvhIoMember *tab, int nmem, unsigned 
 }
 
 // the edge launches, `rounds` of doubling among them (2^rounds >= the largest E): the rows of every member's loops in its edge
-// workspace, the loop and point counts in its words 1 and 2, with any_points the points where a member has an array
+// workspace, the loop and point counts in its words 1 and 2, with any_points the points where a member has an array: lattice points
+// (int32 x, y), or with `levels` -- the mask launches' table, the level sets in src; simplify 0 -- the subpixel points (double x, y)
 hipError_t cvh_launch_contours_trace(const CvhIoMember *tab, int nmem, unsigned grid, int conn, int simplify, int rounds, bool any_points,
-                                     hipStream_t s)
+                                     const CvhIoMember *levels, int invert, hipStream_t s)
 {
   CT_LAUNCH(contour_prefix_kernel, grid, CVH_BLOCK);
   CT_LAUNCH(contour_link_kernel, grid, CVH_BLOCK, conn, simplify ? 1 : 0);
@@ -423,6 +472,7 @@ hipError_t cvh_launch_contours_trace(const CvhIoMember *tab, int nmem, unsigned 
   CT_LAUNCH(contour_loop_sums_kernel, grid, CVH_BLOCK);
   CT_LAUNCH(contour_scan_kernel, (unsigned)nmem, 64, 2);
   CT_LAUNCH(contour_offsets_kernel, grid, CVH_BLOCK);
-  if (any_points) CT_LAUNCH(contour_scatter_kernel, grid, CVH_BLOCK, res);
+  if (any_points && !levels) CT_LAUNCH(contour_scatter_kernel, grid, CVH_BLOCK, res);
+  if (any_points && levels) CT_LAUNCH(contour_scatter_subpixel_kernel, grid, CVH_BLOCK, res, levels, invert ? 1 : 0);
   return hipGetLastError();
 }

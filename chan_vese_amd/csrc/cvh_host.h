@@ -165,7 +165,7 @@ struct cvh_context {   // opaque to callers; four groups
   DeviceTable regions;           // the rows of this context's last cvh_measure* table (measure_run.hip): 128 bytes per row asked for, grown on demand, kept
   void *d_contour = nullptr;     // per-pixel workspace of cvh_contours* (contour_run.hip; 6 bytes per pixel): allocated by the first call, kept
   DeviceTable contour_edges;     // its per-edge workspace (45 bytes per edge of the largest call so far), grown on demand, kept
-  DeviceTable contour_points;    // cvh_contours (host form): the points on their way down (8 bytes per point asked for), grown on demand, kept
+  DeviceTable contour_points;    // cvh_contours / cvh_contours_subpixel (host forms): the points on their way down (8 / 16 bytes per point asked for), grown on demand, kept
   unsigned *d_hist = nullptr;    // the 255 C + 1 counters of cvh_histogram* / cvh_otsu_threshold / cvh_init_otsu* (init_kernels.hip): allocated by
                                  // the first call, kept
   void *d_energy = nullptr;      // workspace of cvh_energy* (energy_run.hip): a CvhState for means taken beside the run's, then the item rows of

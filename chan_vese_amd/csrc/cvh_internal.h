@@ -301,6 +301,7 @@ size_t cvh_contour_edge_bytes(size_t cap);
 size_t cvh_contour_rows_offset(size_t cap);
 hipError_t cvh_launch_contours_count(const CvhIoMember *tab, int nmem, unsigned grid, hipStream_t s);
 hipError_t cvh_launch_contours_trace(const CvhIoMember *tab, int nmem, unsigned grid, int conn, int simplify, int rounds, bool any_points,
+                                     const CvhIoMember *levels /* null: lattice points; else subpixel points from these level sets */, int invert,
                                      hipStream_t s);
 // device-side initial level sets (init_kernels.hip).  Histogram: plane[] the member's planes, sums its 255 C + 1 32-bit counters (zeroed
 // by the host), sections of cvh_io_blocks(n) workgroups.  Start: dst the level set written, plane[] read by the threshold mode,

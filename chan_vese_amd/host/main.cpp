@@ -21,13 +21,14 @@
 // "Mask morphology") for --dump-mask, --roi, --measure, --contours and _selection; --init-mask FILE starts from a binary PGM.
 // Additions that do not collide with reference options: --dump-u, --dump-mask, --device, --math,
 // --state, --rect, --circ, --disk, --init, --threshold, --reinit, --connectivity, --min-area, --fill-holes, --largest, --roi, --verbose,
-// --levels, --energy, --energy-every, --truth, --score-tol, --measure, --contours, --contours-all, --morph, --morph-radius, --init-mask, --truth-labels.  --truth-labels FILE
+// --levels, --energy, --energy-every, --truth, --score-tol, --measure, --contours, --contours-all, --contours-subpixel, --morph, --morph-radius, --init-mask, --truth-labels.  --truth-labels FILE
 // relates the components of the mask --dump-mask uses (the cleaning options and -I apply) to the objects of a label image of the input's
 // size (a binary PGM with maxval <= 65535 or an 8-bit grey PNG; the values are the labels, 0 = no object) on the device (chanvese_hip.h,
 // "Component overlaps") and prints one line "objects: objects_a=... objects_b=... tp=... fp=... fn=... mean_ap=..." to stdout: the counts at
 // IoU > 1/2, and the mean over 0.50 .. 0.95 of tp / (tp + fp + fn).  --contours FILE writes the boundary of
 // the mask --dump-mask uses (the cleaning options and -I apply) as ordered closed loops traced on the device (chanvese_hip.h, "Contours"),
-// one text line per loop: "first edges area2 :" and the x,y pairs of its corners, with --contours-all of every lattice vertex.  --measure FILE writes one CSV line per component of the mask --dump-mask
+// one text line per loop: "first edges area2 :" and the x,y pairs of its corners, with --contours-all of every lattice vertex, with --contours-subpixel
+// of the zero level's crossing of every edge (chanvese_hip.h, "Subpixel contours"; %.17g).  --measure FILE writes one CSV line per component of the mask --dump-mask
 // uses (the cleaning options and -I apply), measured on the device (chanvese_hip.h, "Component measures"): label, the integers of the row,
 // then centroid, central moments, orientation, axes, and mean and variance per channel (%.17g).  --truth FILE scores the final mask (inverted with -i) against a ground-truth PNG / PGM of
 // the input's size (non-zero = foreground) on the device (chanvese_hip.h, "Mask scores") and prints one line "score: iou=... dice=...
@@ -237,7 +238,7 @@ const Spec kSpecs[] = {
     {"dump-u", 0, 1}, {"dump-mask", 0, 1}, {"device", 0, 1}, {"math", 0, 1}, {"state", 0, 1}, {"rect", 0, 1}, {"circ", 0, 1}, {"reinit", 0, 1},
     {"disk", 0, 1}, {"init", 0, 1}, {"threshold", 0, 1}, {"levels", 0, 1}, {"colorspace", 0, 1}, {"local", 0, 1}, {"local-radius", 0, 1}, {"dump-planes", 0, 1}, {"rank", 0, 1}, {"rank-radius", 0, 1},
     {"connectivity", 0, 1}, {"min-area", 0, 1}, {"fill-holes", 0, 1}, {"largest", 0, 0}, {"roi", 0, 0},
-    {"verbose", 0, 0}, {"energy", 0, 0}, {"energy-every", 0, 1}, {"truth", 0, 1}, {"score-tol", 0, 1}, {"measure", 0, 1}, {"contours", 0, 1}, {"contours-all", 0, 0},
+    {"verbose", 0, 0}, {"energy", 0, 0}, {"energy-every", 0, 1}, {"truth", 0, 1}, {"score-tol", 0, 1}, {"measure", 0, 1}, {"contours", 0, 1}, {"contours-all", 0, 0}, {"contours-subpixel", 0, 0},
     {"morph", 0, 1}, {"morph-radius", 0, 1}, {"init-mask", 0, 1}, {"truth-labels", 0, 1}};
 
 struct Parsed {
@@ -449,6 +450,8 @@ void print_help()
       "  --contours arg                     write the boundary of the mask --dump-mask uses (cleaning options, -I) as closed loops, one\n"
       "                                     line per loop: 'first edges area2 :' and the x,y pairs of its corners in order\n"
       "  --contours-all                     --contours keeps every lattice vertex, not the corners alone\n"
+      "  --contours-subpixel                --contours writes the zero level of the level set instead: one x,y pair (%.17g) per edge of\n"
+      "                                     the loop, where the level set changes sign across it\n"
       "  --morph arg                        dilate | erode | open | close: that operation by a disk of --morph-radius pixels, on the device,\n"
       "                                     behind the cleaning options: --dump-mask, --roi, --measure, --contours and _selection use its result\n"
       "  --morph-radius arg (=1)            radius R of that disk in pixels: the offsets with dx^2 + dy^2 <= floor(R^2) (1: the 4-neighbour cross)\n"
@@ -545,6 +548,7 @@ int main(int argc, char **argv)
   std::string contours_filename;
   if (auto v = one("contours")) contours_filename = *v;
   const bool contours_all = vm.count("contours-all") > 0;
+  const bool contours_subpixel = vm.count("contours-subpixel") > 0;
   double score_tol = 2.0;
   if (auto v = one("score-tol")) score_tol = to_double("score-tol", *v);
   segment = vm.count("segment"); grayscale = vm.count("grayscale"); write_video = vm.count("video");
@@ -635,6 +639,8 @@ int main(int argc, char **argv)
   if (energy_every < 0) msg_exit("Energy interval cannot be negative: " + std::to_string(energy_every) + ".");
   if (!contours_filename.empty() && write_video) msg_exit("A contour file (--contours) cannot be combined with video output (-V).");
   if (contours_all && contours_filename.empty()) msg_exit("Every lattice vertex (--contours-all) needs a contour file (--contours).");
+  if (contours_subpixel && contours_filename.empty()) msg_exit("Subpixel points (--contours-subpixel) need a contour file (--contours).");
+  if (contours_subpixel && contours_all) msg_exit("Subpixel points (--contours-subpixel) cannot be combined with every lattice vertex (--contours-all).");
   if (energy_every > 0 && write_video) msg_exit("An energy series (--energy-every) cannot be combined with video output (-V).");
   if (energy_every > 0 && reinit_every > 0) msg_exit("An energy series (--energy-every) cannot be combined with reinitialisation (--reinit).");
   if (energy_every > 0 && levels > 1) msg_exit("An energy series (--energy-every) cannot be combined with a coarse-to-fine run (--levels).");
@@ -1053,7 +1059,24 @@ int main(int argc, char **argv)
     if (std::fclose(f) != 0) msg_exit("Error: cannot write \"" + measure_filename + "\"");
   }
 
-  if (!contours_filename.empty()) {   // the boundary of that mask as ordered closed loops, traced on the device: one text line each
+  if (!contours_filename.empty() && contours_subpixel) {   // the zero level as ordered closed polygons: the same lines, a point per edge
+    long nloops = 0, npoints = 0;
+    cvh_check(ctx, cvh_contours_subpixel(ctx, connectivity, invert ? 1 : 0, min_area, fill_holes, largest ? 1 : 0, nullptr, 0, nullptr, 0, &nloops, &npoints),
+              "cvh_contours_subpixel");
+    std::vector<cvh_contour_loop> loops((size_t)nloops);
+    std::vector<double> points(2 * (size_t)npoints);
+    if (nloops)
+      cvh_check(ctx, cvh_contours_subpixel(ctx, connectivity, invert ? 1 : 0, min_area, fill_holes, largest ? 1 : 0, loops.data(), nloops, points.data(),
+                                           npoints, &nloops, &npoints), "cvh_contours_subpixel");
+    FILE *f = std::fopen(contours_filename.c_str(), "w");
+    if (!f) msg_exit("Error: cannot write \"" + contours_filename + "\"");
+    for (const cvh_contour_loop &l : loops) {
+      std::fprintf(f, "%u %u %lld :", l.first, l.edges, (long long)l.area2);
+      for (uint64_t q = l.offset; q < l.offset + l.points; ++q) std::fprintf(f, " %.17g,%.17g", points[2 * q], points[2 * q + 1]);
+      std::fprintf(f, "\n");
+    }
+    if (std::fclose(f) != 0) msg_exit("Error: cannot write \"" + contours_filename + "\"");
+  } else if (!contours_filename.empty()) {   // the boundary of that mask as ordered closed loops, traced on the device: one text line each
     const int simplify = contours_all ? 0 : 1;
     long nloops = 0, npoints = 0;
     cvh_check(ctx, cvh_contours(ctx, connectivity, invert ? 1 : 0, min_area, fill_holes, largest ? 1 : 0, simplify, nullptr, 0, nullptr, 0, &nloops, &npoints),

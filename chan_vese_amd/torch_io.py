@@ -457,16 +457,26 @@ class Segmenter:
         matched pairs.  labels as in overlaps(): a ground truth, or components() of the previous frame."""
         return [capi.match_overlaps(rows, threshold) for rows in self.overlaps(labels, conn, invert, min_area, fill_holes, keep_largest)]
 
-    def contours(self, conn=8, invert=False, min_area=0, fill_holes=0, keep_largest=False, simplify=True):
+    def contours(self, conn=8, invert=False, min_area=0, fill_holes=0, keep_largest=False, simplify=None, subpixel=False):
         """The boundary of every member's mask -- clean_masks' for the same options -- as ordered closed loops, traced on the device
         (cvh_contours_device_batch, ordered behind the current stream): one (loops, points) per member, loops a numpy structured array
         (capi.CONTOUR_LOOP_DTYPE), points an int32 device tensor (P, 2) of x, y, valid for the next operation on the current stream;
-        bit for bit the member's own Context.contours().  Two sets of launches: the first for the counts that size the tensors."""
-        opts = dict(conn=conn, invert=invert, min_area=min_area, fill_holes=fill_holes, keep_largest=keep_largest, simplify=simplify)
-        counts = capi.contours_batch(self.contexts, loop_caps=[0] * self.n, stream=self._stream(), **opts)
-        points = [torch.empty((c[1], 2), dtype=torch.int32, device=torch.device("cuda", self.device)) for c in counts]
-        rows = capi.contours_batch(self.contexts, [p.data_ptr() if p.numel() else 0 for p in points], [c[1] for c in counts],
-                                   loop_caps=[c[0] for c in counts], stream=self._stream(), **opts)
+        bit for bit the member's own Context.contours().  Two sets of launches: the first for the counts that size the tensors.
+        simplify (None: True) keeps the corners only.  subpixel=True (cvh_contours_subpixel_device_batch): the zero level of the level
+        set instead -- one point per edge of the loops, where u changes sign across it; points a float64 device tensor (P, 2), bit for
+        bit Context.contours_subpixel().  There is nothing to simplify then: simplify together with subpixel raises ValueError."""
+        opts = dict(conn=conn, invert=invert, min_area=min_area, fill_holes=fill_holes, keep_largest=keep_largest)
+        if subpixel:
+            if simplify is not None:
+                raise ValueError(f"contours: simplify = {simplify!r} together with subpixel=True (a subpixel loop has one point per edge)")
+            batch, dtype = capi.contours_subpixel_batch, torch.float64
+        else:
+            batch, dtype = capi.contours_batch, torch.int32
+            opts["simplify"] = True if simplify is None else simplify
+        counts = batch(self.contexts, loop_caps=[0] * self.n, stream=self._stream(), **opts)
+        points = [torch.empty((c[1], 2), dtype=dtype, device=torch.device("cuda", self.device)) for c in counts]
+        rows = batch(self.contexts, [p.data_ptr() if p.numel() else 0 for p in points], [c[1] for c in counts],
+                     loop_caps=[c[0] for c in counts], stream=self._stream(), **opts)
         return [(r[2], p) for r, p in zip(rows, points)]
 
     def levelsets(self, dtype=torch.float64):

@@ -1054,6 +1054,55 @@ int cvh_contours_device_batch(cvh_context *const *ctxs, int n, int conn, int inv
                               int simplify, cvh_contour_loop *const *loops, const long *loop_caps, int32_t *const *d_points,
                               const long *point_caps, long *nloops, long *npoints, void *stream);
 
+/* ---- Subpixel contours --------------------------------------------------------------------------------------------------------
+ * The ZERO LEVEL of the level set as ordered closed POLYGONS with subpixel vertices: the loops of "Contours", each lattice point
+ * replaced by the point where u changes sign across the loop's edge.  A lattice point lies up to half a pixel from the zero level; these
+ * lie on it to within the curvature of u inside a pixel.  What a caller otherwise does with cvh_get_levelset (8 bytes per pixel across
+ * PCIe) and a marching-squares tracer on a CPU.
+ * Why no new tracing: a boundary edge of the mask separates a foreground pixel from a background pixel (or the plane's border); the
+ * segment that joins the two pixel centres carries exactly one marching-squares vertex; so a loop's edges in their cycle order ARE the
+ * vertices of the marching-squares polygon in order, and the diagonal ambiguity is settled by conn as in "Contours".
+ * Mask, loops, edges, successor rule.  Exactly those of "Contours" for the call's (conn, invert, min_area, fill_holes, keep_largest).
+ * The loop table is the one cvh_contours writes with simplify = 0: points == edges, offset is the prefix of edges, area2 is the LATTICE
+ * loop's.
+ * One point per edge.  A loop's points are in cycle order and start at edge first.  For edge id 4 (r w + c) + k:
+ *     p = (r, c) is the foreground pixel, q its neighbour across side k;
+ *     (dx, dy) = (0, -1) for k = 0 (top), (1, 0) for k = 1 (right), (0, 1) for k = 2 (bottom), (-1, 0) for k = 3 (left);
+ *     s = invert ? -1 : +1;  a = s u(p), b = s u(q) as FP64 (with "state" = 32 the floats widened, which is exact);
+ *     t = a / (a - b), one IEEE division, when q lies inside the plane AND a > 0 AND b <= 0 AND a - b is finite; otherwise t = 0.5 --
+ *         a plane-border edge; a pixel whose class was changed by cleaning; NaN, zeros of either sign, or a positive double that rounds
+ *         to 0.0f (background by the mask's rule); an infinite a; an overflowing difference.  So t lies in [0, 1];
+ *     x = (c + 0.5) + dx t,  y = (r + 0.5) + dy t, one rounding each: pixel centres are at half-integers, in the lattice of "Contours".
+ * A point is two doubles, x then y.  Every bit is defined: the result can be compared with == against a numpy restatement, and a member
+ * gives the same bits alone or in any batch (the library is built without floating-point contraction and without fast-math).
+ * Caps, NULL outputs, empty masks, host waits, stream ordering, the batch form: as "Contours".  A point is 16 bytes; a device pointer
+ * must be 8-byte aligned; the host form takes 16 bytes per point asked for on the device.  No new per-edge or per-pixel workspace: the
+ * last launch of the trace is another scatter (a gather of u(p) and u(q) per edge, one 16-byte store), everything before it is the
+ * integer path's.
+ * The calls only READ, as cvh_contours: iterations in flight are settled, the FP64 mirror of a float state is refreshed, and a run
+ * continued afterwards is bit-identical to one without.
+ * After cvh_reinit every point is its edge's MIDPOINT: the distance to a pixel-edge front gives a = 0.5 and b = -0.5 on every edge.  The
+ * subpixel position lives in the evolved u, not in a reinitialised one -- take the polygon before reinitialising.
+ * cvh_contour_subpixel_measure (host only; no device, no context): for the n points of ONE loop
+ *     area = 1/2 sum (x_i y_{i+1} - x_{i+1} y_i),   length = sum sqrt((x_{i+1} - x_i)^2 + (y_{i+1} - y_i)^2),   i = 0 .. n-1 cyclic,
+ * each accumulated left to right in FP64 in index order, so that sequential double arithmetic reproduces it bit for bit; the sign is
+ * area2's (positive for an outer boundary, negative for a hole).  n = 0 gives 0 and 0.  CVH_ERR_ARG: n < 0 or a NULL argument.
+ * Cost, one run of tools/subpixel_probe.py on an MI355X (host clock around a call with full outputs and its two waits, 20
+ * calls, measured once): 757 / 748 / 1009 us at 1024^2 / 2048^2 / 4096^2 for a noisy disk after 50 iterations, 410 / 536 / 1057 us for
+ * the plane wholly inside -- beside 755 / 747 / 1054 and 412 / 535 / 1058 us for cvh_contours_device(simplify = 0) on the same level
+ * sets in the same process: the two calls cannot be told apart (one gather of 16 bytes per edge beside about thirty launches).
+ * CVH_ERR_ARG / CVH_ERR_STATE: what cvh_contours* refuses (there is no simplify), and a device point pointer that is not 8-byte
+ * aligned. */
+int cvh_contours_subpixel(cvh_context *ctx, int conn, int invert, long min_area, long fill_holes, int keep_largest,
+                          cvh_contour_loop *loops, long loop_cap, double *points, long point_cap, long *nloops, long *npoints);   /* host points */
+int cvh_contours_subpixel_device(cvh_context *ctx, int conn, int invert, long min_area, long fill_holes, int keep_largest,
+                                 cvh_contour_loop *loops, long loop_cap, double *d_points, long point_cap, long *nloops, long *npoints,
+                                 void *stream);
+int cvh_contours_subpixel_device_batch(cvh_context *const *ctxs, int n, int conn, int invert, long min_area, long fill_holes, int keep_largest,
+                                       cvh_contour_loop *const *loops, const long *loop_caps, double *const *d_points,
+                                       const long *point_caps, long *nloops, long *npoints, void *stream);
+int cvh_contour_subpixel_measure(const double *points, long n, double *area, double *length);   /* host only */
+
 /* ---- Mask morphology ----------------------------------------------------------------------------------------------------------
  * Open, close, dilate or erode the mask by a disk ON THE DEVICE, and turn a byte mask into a level set there -- what a caller otherwise
  * does with cvh_get_mask, scipy.ndimage.binary_opening / cv::morphologyEx on a CPU, and cvh_set_levelset at 8 bytes per pixel.  Together
