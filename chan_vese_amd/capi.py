@@ -47,6 +47,7 @@ EXPORTS = [
     "cvh_contours_subpixel", "cvh_contours_subpixel_device", "cvh_contours_subpixel_device_batch", "cvh_contour_subpixel_measure",
     "cvh_get_mask_morph", "cvh_get_mask_morph_device", "cvh_get_mask_morph_device_batch", "cvh_morph_levelset", "cvh_morph_levelset_batch",
     "cvh_init_mask", "cvh_init_mask_device", "cvh_init_mask_device_batch",
+    "cvh_multiphase_run", "cvh_multiphase_means", "cvh_multiphase_labels", "cvh_multiphase_labels_device", "cvh_multiphase_geometry",
 ]
 # "Mask morphology": the operations of cvh_get_mask_morph* / cvh_morph_levelset*, by code and by name
 MORPH_NONE, MORPH_DILATE, MORPH_ERODE, MORPH_OPEN, MORPH_CLOSE = 0, 1, 2, 3, 4
@@ -374,6 +375,11 @@ def lib():
         "cvh_init_mask": (C.c_int, [vp, u8p, C.c_double, C.c_double]),
         "cvh_init_mask_device": (C.c_int, [vp, vp, C.c_double, C.c_double, vp]),
         "cvh_init_mask_device_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.POINTER(vp), C.c_double, C.c_double, vp]),
+        "cvh_multiphase_run": (C.c_int, [vp, vp, C.c_int, ip, dp, dp, C.c_int, ip]),
+        "cvh_multiphase_means": (C.c_int, [vp, vp, dp]),
+        "cvh_multiphase_labels": (C.c_int, [vp, vp, u8p]),
+        "cvh_multiphase_labels_device": (C.c_int, [vp, vp, vp, vp]),
+        "cvh_multiphase_geometry": (None, [C.c_int, C.c_int, ip, ip, ip]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -1108,6 +1114,36 @@ def _monitored(contexts, max_steps, every, rel_plateau, run):
     return [(done, nrm, ser) for (done, nrm), ser in zip(res, series)]
 
 
+def multiphase_geometry(h, w):
+    """cvh_multiphase_geometry: (columns per wave, rows per strip, items) of the fixed partition the four-phase sums are taken over;
+    pure host arithmetic (rows and items are 0 for a plane the calls refuse)."""
+    cols, rows, items = C.c_int(0), C.c_int(0), C.c_int(0)
+    lib().cvh_multiphase_geometry(int(h), int(w), C.byref(cols), C.byref(rows), C.byref(items))
+    return cols.value, rows.value, items.value
+
+
+def multiphase_run(a, b, max_steps=-1, trace=False):
+    """cvh_multiphase_run ("Four phases" in include/chanvese_hip.h): contexts a and b hold phi1 and phi2 of a Vese-Chan pair and are
+    iterated together until max_steps iterations are done (negative: no bound) or the pair stops.  Returns (steps_done, (norm1, norm2),
+    trace): trace is None, or with trace=True (all rows; needs max_steps >= 0) or trace=<rows> an array of one row of 4 C + 2 doubles
+    per iteration -- the means c11, c10, c01, c00 it used and its two norms.  Both contexts are left as set_levelset of the new level
+    sets leaves them."""
+    want = 0 if trace is False or trace is None else (int(max_steps) if trace is True else int(trace))
+    if want < 0:
+        raise ValueError("trace=True needs max_steps >= 0 (or pass the number of rows)")
+    done, rows, norms = C.c_int(0), C.c_int(0), (C.c_double * 2)()
+    out = np.zeros((max(want, 1), 4 * a.channels + 2), dtype=np.float64) if want or trace is True else None
+    _batch_chk(lib().cvh_multiphase_run(a._h, b._h, int(max_steps), C.byref(done), norms, None if out is None else _dp(out), want, C.byref(rows)))
+    return done.value, (norms[0], norms[1]), None if out is None else out[:rows.value].copy()
+
+
+def multiphase_means(a, b):
+    """cvh_multiphase_means: the means of the current pair as an array of (4, C), rows c11, c10, c01, c00.  Only reads."""
+    c = np.zeros((4, a.channels), dtype=np.float64)
+    _batch_chk(lib().cvh_multiphase_means(a._h, b._h, _dp(c)))
+    return c
+
+
 def run_monitored(ctx, max_steps=-1, every=16, rel_plateau=None):
     """Context.run in segments of `every` iterations with the energy (Context.energy) taken after each segment.  Returns (total steps,
     last norm, [(steps so far, Energy)]).  max_steps is the total budget (< 0: unlimited); the run ends when the stop rule fired inside
@@ -1347,6 +1383,16 @@ class Context:
         rows = C.c_int(0)
         self._chk(self._L.cvh_get_trace(self._h, _dp(out), int(max_rows), C.byref(rows)))
         return out[:rows.value].copy()
+
+    def multiphase_labels_with(self, b, ptr=0, stream=0):
+        """cvh_multiphase_labels / _device: label = mask(self) + 2 mask(b) per pixel, one launch.  Returns a uint8 array of (h, w), or
+        with ptr (an integer device address of h * w bytes, ordered behind `stream`) writes there without a host wait.  Only reads."""
+        if ptr:
+            _batch_chk(self._L.cvh_multiphase_labels_device(self._h, b._h, int(ptr), int(stream) or None))
+            return None
+        out = np.empty((self.h, self.w), dtype=np.uint8)
+        _batch_chk(self._L.cvh_multiphase_labels(self._h, b._h, _u8p(out)))
+        return out
 
     def get_stop_condition(self):
         v = C.c_double(0.0)

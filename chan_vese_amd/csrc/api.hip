@@ -153,6 +153,8 @@ extern "C" void cvh_destroy(cvh_context *c)
   if (c->d_local) (void)hipFree(c->d_local);
   if (c->d_rank) (void)hipFree(c->d_rank);
   if (c->d_overlap_plane) (void)hipFree(c->d_overlap_plane);
+  if (c->d_multiphase) (void)hipFree(c->d_multiphase);
+  free_table(&c->mp_trace);
   if (c->ev_io_in) (void)hipEventDestroy(c->ev_io_in);
   if (c->ev_io_out) (void)hipEventDestroy(c->ev_io_out);
   if (c->h_resident) (void)hipHostFree(c->h_resident);

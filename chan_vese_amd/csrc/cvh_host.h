@@ -6,7 +6,8 @@
 // level sets), components_run.hip (connected components, and MaskSource: the raw or cleaned mask every mask-derived call starts from),
 // pyramid_run.hip (coarse-to-fine), colour_run.hip (colour spaces), window_run.hip (local statistics and rank planes: the windowed-plane calls), energy_run.hip (the functional's terms), score_run.hip (mask scores),
 // morph_run.hip (mask morphology, mask starts), measure_run.hip (component measures), contour_run.hip (contours), overlap_run.hip
-// (component overlaps), debug_exports.hip (diagnostics).  Kernel sources do not include it.
+// (component overlaps), multiphase_run.hip (four phases: a pair of contexts iterated together), debug_exports.hip (diagnostics).  Kernel
+// sources do not include it.
 #pragma once
 #include <limits.h>
 #include <math.h>
@@ -183,6 +184,9 @@ struct cvh_context {   // opaque to callers; four groups
   DeviceTable overlap;           // cvh_overlaps* (overlap_run.hip): overlap.count slots of the pair table and overlap.count / 2 rows behind them (24 bytes
                                  // per slot), grown where a call's table overflows, kept; d_overlap_plane: the int32 plane the host form stages
   void *d_overlap_plane = nullptr;   // (4 bytes per pixel) -- allocated by the first call that needs them, not part of live_footprint either
+  void *d_multiphase = nullptr;  // workspace of cvh_multiphase_* as their FIRST context (multiphase_run.hip): the pair's state block and the items'
+                                 // partial sums: allocated by the first call, kept -- not part of live_footprint either
+  DeviceTable mp_trace;          // and the trace rows of the longest cvh_multiphase_run so far that asked for them, grown on demand, kept
   int coop_launch = -1;          // does the device launch cooperatively (-1: not asked yet; launches_cooperatively)
   int resident_cap = -1;         // workgroups of csv_resident_kernel the device holds at once (-1: not asked yet, 0: unavailable)
   int pm_resident_cap = -1;      // workgroups of pm_resident_kernel the device holds at once (-1: not asked yet)

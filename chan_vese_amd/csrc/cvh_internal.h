@@ -417,6 +417,45 @@ hipError_t cvh_launch_morph_passes(const CvhIoMember *cols, const CvhMorphPar *p
                                    hipStream_t s);
 hipError_t cvh_launch_morph_emit(const CvhIoMember *tab, const CvhMorphPar *par, int nmem, unsigned grid, bool from_bytes, bool to_levelset,
                                  hipStream_t s);
+// four phases (multiphase_kernels.hip; include/chanvese_hip.h, "Four phases").  A wave's ITEM is a strip of strip_rows rows x
+// CVH_MP_COLS columns of the plane; the partition -- hence every sum -- is a function of the shape alone (cvh_mp_geometry).  An item's
+// row of partial sums holds cvh_mp_nsums(C) doubles:
+//   [0..4) sum w11, w10, w01, w00   [4 + ab C + k] sum I_k w_ab (ab = 0..3 in that order)   [4 + 4C] sum d1^2   [5 + 4C] sum d2^2
+// The pair's state block lives in A's workspace and is written by the one-workgroup finalise launch alone.
+#define CVH_MP_COLS 61          // output columns per wave: lanes 2 .. 62 (lanes 0, 1 and 63 hold the strip's halo columns)
+#define CVH_MP_TARGET_WAVES 4096
+#define CVH_MP_MIN_ROWS 8
+__host__ __device__ constexpr int cvh_mp_nsums(int C) { return 6 + 4 * C; }
+struct CvhMpGeom { int nwc, strip_rows, nstrips, nitems; unsigned grid; };
+CvhMpGeom cvh_mp_geometry(int h, int w);
+struct CvhMpState {
+  double c[4][CVH_MAX_CHANNELS];   // c11, c10, c01, c00: the means of the current pair, read by the next iteration
+  double norm[2];                  // ||d1||_2, ||d2||_2 of the last executed iteration
+  int steps_done;                  // iterations executed in this call
+  int stopped;                     // sticky: the stop rule fired; every later launch of the call returns at once
+};
+struct CvhMpArgs {
+  const double *in[2];             // phi1, phi2 read
+  double *out[2];                  // phi1, phi2 written (sums pass: unused)
+  const uint8_t *img[CVH_MAX_CHANNELS];
+  CvhMpState *st;
+  double *partials;                // [nitems][cvh_mp_nsums(C)]
+  double *trace;                   // [trace_cap][4C + 2] or null
+  int trace_cap;
+  int h, w;
+  CvhMpGeom g;
+  double alpha[2], beta[2], gamma[2];          // dt mu, dt / C, -dt nu of A (phi1's equation) and of B (phi2's)
+  double lambda1[2][CVH_MAX_CHANNELS], lambda2[2][CVH_MAX_CHANNELS];
+  double eps, inv_eps, dk1;                    // FAST: 1 / eps, pi / eps
+  double far_k[5], far_thr;                    // FAST: far-field series of H_eps (wave_math.h)
+  const double *atan2_tab;                     // FAST: [CVH_ATAN2_N]
+  double stop[2];                              // what cvh_get_stop_condition returns for A and for B
+};
+hipError_t cvh_launch_mp_sums(const CvhMpArgs &a, int channels, int fast, hipStream_t s);      // the sums of in[] into partials
+hipError_t cvh_launch_mp_step(const CvhMpArgs &a, int channels, int fast, hipStream_t s);      // one iteration, and the sums of out[]
+hipError_t cvh_launch_mp_finalize(const CvhMpArgs &a, int channels, int is_init, hipStream_t s);
+// labels: one member; src phi1, src2 phi2, dst the bytes (any alignment), sections of cvh_io_blocks(n) workgroups
+hipError_t cvh_launch_mp_labels(const CvhIoMember *tab, int nmem, unsigned grid, hipStream_t s);
 // rows-per-tile options of the step kernel
 void cvh_step_grid(int h, int w, int tile_rows, int *tiles_x, int *tiles_y);
 int cvh_step_max_blocks(int h, int w);

@@ -21,7 +21,7 @@
 // "Mask morphology") for --dump-mask, --roi, --measure, --contours and _selection; --init-mask FILE starts from a binary PGM.
 // Additions that do not collide with reference options: --dump-u, --dump-mask, --device, --math,
 // --state, --rect, --circ, --disk, --init, --threshold, --reinit, --connectivity, --min-area, --fill-holes, --largest, --roi, --verbose,
-// --levels, --energy, --energy-every, --truth, --score-tol, --measure, --contours, --contours-all, --contours-subpixel, --morph, --morph-radius, --init-mask, --truth-labels.  --truth-labels FILE
+// --levels, --energy, --energy-every, --truth, --score-tol, --measure, --contours, --contours-all, --contours-subpixel, --morph, --morph-radius, --init-mask, --truth-labels, --phases, --init2, --dump-labels (--phases 4: chanvese_hip.h, "Four phases" -- two contexts, cvh_multiphase_run, the labels; what does not compose with it is refused).  --truth-labels FILE
 // relates the components of the mask --dump-mask uses (the cleaning options and -I apply) to the objects of a label image of the input's
 // size (a binary PGM with maxval <= 65535 or an 8-bit grey PNG; the values are the labels, 0 = no object) on the device (chanvese_hip.h,
 // "Component overlaps") and prints one line "objects: objects_a=... objects_b=... tp=... fp=... fn=... mean_ap=..." to stdout: the counts at
@@ -239,7 +239,8 @@ const Spec kSpecs[] = {
     {"disk", 0, 1}, {"init", 0, 1}, {"threshold", 0, 1}, {"levels", 0, 1}, {"colorspace", 0, 1}, {"local", 0, 1}, {"local-radius", 0, 1}, {"dump-planes", 0, 1}, {"rank", 0, 1}, {"rank-radius", 0, 1},
     {"connectivity", 0, 1}, {"min-area", 0, 1}, {"fill-holes", 0, 1}, {"largest", 0, 0}, {"roi", 0, 0},
     {"verbose", 0, 0}, {"energy", 0, 0}, {"energy-every", 0, 1}, {"truth", 0, 1}, {"score-tol", 0, 1}, {"measure", 0, 1}, {"contours", 0, 1}, {"contours-all", 0, 0}, {"contours-subpixel", 0, 0},
-    {"morph", 0, 1}, {"morph-radius", 0, 1}, {"init-mask", 0, 1}, {"truth-labels", 0, 1}};
+    {"morph", 0, 1}, {"morph-radius", 0, 1}, {"init-mask", 0, 1}, {"truth-labels", 0, 1},
+    {"phases", 0, 1}, {"init2", 0, 2}, {"dump-labels", 0, 1}};
 
 struct Parsed {
   std::vector<std::pair<std::string, std::vector<std::string>>> opts;
@@ -455,6 +456,12 @@ void print_help()
       "  --morph arg                        dilate | erode | open | close: that operation by a disk of --morph-radius pixels, on the device,\n"
       "                                     behind the cleaning options: --dump-mask, --roi, --measure, --contours and _selection use its result\n"
       "  --morph-radius arg (=1)            radius R of that disk in pixels: the offsets with dx^2 + dy^2 <= floor(R^2) (1: the 4-neighbour cross)\n"
+      "  --phases arg (=2)                  2 | 4: four phases evolve TWO level sets together (Vese-Chan), whose sign pairs name four classes;\n"
+      "                                     -s then writes the label plane as a grey image (label x 85); not with -V, --levels, --energy,\n"
+      "                                     --energy-every, --reinit (nor the mask-based outputs, which take one level set)\n"
+      "  --init2 arg (=checkerboard)        checkerboard | otsu | threshold T: the start of the second level set (--phases 4); the\n"
+      "                                     checkerboard is --init's rolled by (2, 3) pixels\n"
+      "  --dump-labels arg                  write the labels (mask 1 + 2 mask 2, one byte per pixel, h*w) of a --phases 4 run\n"
       "  --init-mask arg                    binary PGM of the input's size as the initial contour (+1 where it is non-zero, -1 elsewhere),\n"
       "                                     written on the device at a byte per pixel; not with --levels\n"
       "  --verbose                          print the iteration count and last norm to stderr\n"
@@ -551,6 +558,10 @@ int main(int argc, char **argv)
   const bool contours_subpixel = vm.count("contours-subpixel") > 0;
   double score_tol = 2.0;
   if (auto v = one("score-tol")) score_tol = to_double("score-tol", *v);
+  int phases = 2;
+  if (auto v = one("phases")) phases = to_int("phases", *v);
+  std::string dump_labels;
+  if (auto v = one("dump-labels")) dump_labels = *v;
   segment = vm.count("segment"); grayscale = vm.count("grayscale"); write_video = vm.count("video");
   overlay_text = vm.count("overlay-text"); invert = vm.count("invert-selection");
   object_selection = vm.count("select"); rectangle_contour = vm.count("rectangle"); circle_contour = vm.count("circle");
@@ -644,6 +655,38 @@ int main(int argc, char **argv)
   if (energy_every > 0 && write_video) msg_exit("An energy series (--energy-every) cannot be combined with video output (-V).");
   if (energy_every > 0 && reinit_every > 0) msg_exit("An energy series (--energy-every) cannot be combined with reinitialisation (--reinit).");
   if (energy_every > 0 && levels > 1) msg_exit("An energy series (--energy-every) cannot be combined with a coarse-to-fine run (--levels).");
+  // --phases 4 (chanvese_hip.h, "Four phases"): two level sets, the second one started by --init2; what does not compose with it is refused
+  if (phases != 2 && phases != 4) msg_exit("Number of phases must be 2 or 4: " + std::to_string(phases) + ".");
+  std::string init2_kind = "checkerboard";
+  int threshold2 = -1;
+  if (auto v = vm.get("init2")) {
+    if (phases != 4) msg_exit("A second start (--init2) needs four phases (--phases 4).");
+    if (v->empty()) msg_exit("error: the required argument for option '--init2' is missing");
+    init2_kind = (*v)[0];
+    if (init2_kind == "threshold") {
+      if (v->size() != 2) msg_exit("A threshold start (--init2 threshold T) needs its threshold.");
+      threshold2 = to_int("init2", (*v)[1]);
+      if (threshold2 < 0 || threshold2 > 255 * (one_plane ? 1 : 3))
+        msg_exit("Threshold must be between 0 and " + std::to_string(255 * (one_plane ? 1 : 3)) + ": " + std::to_string(threshold2) + ".");
+    } else if ((init2_kind != "checkerboard" && init2_kind != "otsu") || v->size() != 1) {
+      msg_exit("error: the argument ('" + init2_kind + "') for option '--init2' is invalid");
+    }
+  }
+  if (!dump_labels.empty() && phases != 4) msg_exit("A label file (--dump-labels) needs four phases (--phases 4).");
+  if (phases == 4) {
+    const std::pair<bool, const char *> refused[] = {
+        {write_video, "video output (-V)"}, {levels > 1, "a coarse-to-fine run (--levels)"}, {print_energy, "an energy line (--energy)"},
+        {energy_every > 0, "an energy series (--energy-every)"}, {reinit_every > 0, "reinitialisation (--reinit)"},
+        // the rest of what this build does not carry through two level sets: nothing is silently ignored
+        {state_bits == 32, "FP32 state (--state 32)"}, {!rect.empty(), "--rect"}, {!circ.empty(), "--circ"}, {!disk.empty(), "--disk"},
+        {!init_mask_filename.empty(), "--init-mask"}, {vm.count("local") > 0, "--local"}, {vm.count("rank") > 0, "--rank"},
+        {vm.count("colorspace") > 0, "--colorspace"}, {!dump_planes.empty(), "--dump-planes"}, {!dump_u.empty(), "--dump-u"},
+        {!dump_mask.empty(), "--dump-mask"}, {clean_mask, "the cleaning options"}, {roi, "--roi"}, {vm.count("morph") > 0, "--morph"},
+        {!truth_filename.empty(), "--truth"}, {!truth_labels_filename.empty(), "--truth-labels"}, {!measure_filename.empty(), "--measure"},
+        {!contours_filename.empty(), "--contours"}, {invert, "an inverted selection (-I)"}};
+    for (auto &r : refused)
+      if (r.first) msg_exit(std::string("Four phases (--phases 4) cannot be combined with ") + r.second + ".");
+  }
   if (vm.count("score-tol") && truth_filename.empty()) msg_exit("A score tolerance (--score-tol) needs a ground truth (--truth).");
   if (!(score_tol >= 0.0) || !std::isfinite(score_tol)) msg_exit("Score tolerance must be a finite number >= 0.");
   int morph_op = CVH_MORPH_NONE;
@@ -742,6 +785,66 @@ int main(int argc, char **argv)
   cvh_default_params(&prm);
   prm.mu = mu; prm.nu = nu; prm.dt = dt; prm.eps = eps; prm.tol = tol;
   for (int k = 0; k < run_channels; ++k) { prm.lambda1[k] = lambda1[k]; prm.lambda2[k] = lambda2[k]; }
+
+  // ---- four phases: two contexts hold phi1 and phi2 and the same planes; everything of this run is here
+  if (phases == 4) {
+    cvh_context *pa = nullptr, *pb = nullptr;
+    for (cvh_context **c : {&pa, &pb}) {
+      if (cvh_create(c, h, w, run_channels, &prm, device) != CVH_OK)
+        msg_exit(std::string("Error: cannot initialise the HIP backend: ") + cvh_last_error(nullptr));
+      cvh_check(*c, cvh_set_option(*c, "math_mode", math == "strict" ? CVH_MATH_STRICT : CVH_MATH_FAST), "math_mode");
+    }
+    std::vector<uint8_t *> pp;
+    for (auto &p : planes) pp.push_back(p.data());
+    cvh_check(pa, cvh_set_image(pa, pp.data()), "cvh_set_image");
+    if (segment) {   // src/main.cpp:940-947, once: B takes the smoothed bytes
+      cvh_check(pa, cvh_perona_malik(pa, K, L, T), "cvh_perona_malik");
+      cvh_check(pa, cvh_get_image(pa, pp.data()), "cvh_get_image");
+      std::vector<uint8_t> out(n * nof_channels);
+      for (size_t q = 0; q < n; ++q) {
+        if (nof_channels == 1) out[q] = planes[0][q];
+        else { out[3 * q] = planes[2][q]; out[3 * q + 1] = planes[1][q]; out[3 * q + 2] = planes[0][q]; }
+      }
+      if (!write_image(add_suffix(input_filename, "pm"), h, w, nof_channels, out.data()))
+        msg_exit("Error: cannot write \"" + add_suffix(input_filename, "pm") + "\"");
+    }
+    cvh_check(pb, cvh_set_image(pb, pp.data()), "cvh_set_image");
+    if (init_otsu) cvh_check(pa, cvh_init_otsu(pa, nullptr, 1.0, -1.0), "cvh_init_otsu");
+    else if (init_threshold) cvh_check(pa, cvh_init_threshold(pa, threshold, 1.0, -1.0), "cvh_init_threshold");
+    else cvh_check(pa, cvh_init_checkerboard(pa), "cvh_init_checkerboard");
+    if (init2_kind == "otsu") cvh_check(pb, cvh_init_otsu(pb, nullptr, 1.0, -1.0), "cvh_init_otsu");
+    else if (init2_kind == "threshold") cvh_check(pb, cvh_init_threshold(pb, threshold2, 1.0, -1.0), "cvh_init_threshold");
+    else {   // the checkerboard rolled by (2, 3) pixels: two identical starts would stay identical forever
+      std::vector<double> cb(n), u2(n);
+      cvh_levelset_checkerboard_host(h, w, cb.data());
+      for (int i = 0; i < h; ++i)
+        for (int j = 0; j < w; ++j) u2[(size_t)((i + 2) % h) * w + (size_t)((j + 3) % w)] = cb[(size_t)i * w + j];
+      cvh_check(pb, cvh_set_levelset(pb, u2.data()), "cvh_set_levelset");
+    }
+    int steps4 = 0;
+    double norms4[2] = {0, 0};
+    if (cvh_multiphase_run(pa, pb, max_steps, &steps4, norms4, nullptr, 0, nullptr) != CVH_OK)
+      msg_exit(std::string("Error: cvh_multiphase_run: ") + cvh_last_error(nullptr));
+    std::vector<uint8_t> labels(n);
+    if (cvh_multiphase_labels(pa, pb, labels.data()) != CVH_OK)
+      msg_exit(std::string("Error: cvh_multiphase_labels: ") + cvh_last_error(nullptr));
+    if (!dump_labels.empty()) {
+      std::ofstream out(dump_labels, std::ios::binary);
+      out.write(reinterpret_cast<const char *>(labels.data()), (std::streamsize)n);
+      if (!out) msg_exit("Error: cannot write \"" + dump_labels + "\"");
+    }
+    if (object_selection) {   // the label plane as a grey image: label x 85
+      std::vector<uint8_t> grey(n);
+      for (size_t q = 0; q < n; ++q) grey[q] = (uint8_t)(labels[q] * 85);
+      if (!write_image(add_suffix(input_filename, "selection"), h, w, 1, grey.data()))
+        msg_exit("Error: cannot write \"" + add_suffix(input_filename, "selection") + "\"");
+    }
+    if (vm.count("verbose"))
+      std::fprintf(stderr, "four phases: %d iterations, norms %.17g %.17g\n", steps4, norms4[0], norms4[1]);
+    cvh_destroy(pb);
+    cvh_destroy(pa);
+    return EXIT_SUCCESS;
+  }
 
   std::vector<std::pair<int, int>> level_shape{{h, w}};   // finest first
   for (int k = 1; k < levels; ++k) level_shape.push_back({(level_shape.back().first + 1) / 2, (level_shape.back().second + 1) / 2});

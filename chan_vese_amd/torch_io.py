@@ -189,8 +189,14 @@ class Segmenter:
     ingest themselves.
     rank = (radius, what) makes the run iterate on rank planes of the ingested planes -- a median against impulse noise, a top-hat
     against a shading ramp (check_rank; cvh_rank_planes_batch) -- in source contexts of its own, as local= does.  With both given the
-    rank filter runs FIRST, into `ranked`, contexts of the filter's channels, and local= works on its result."""
+    rank filter runs FIRST, into `ranked`, contexts of the filter's channels, and local= works on its result.
+    phases = 4 (include/chanvese_hip.h, "Four phases") makes every member a PAIR of contexts, `contexts[i]` holding phi1 and `contexts_b[i]`
+    phi2, both fed the same device tensor; segment() then iterates the pairs (cvh_multiphase_run) and returns labels 0 .. 3, phase_masks()
+    gives the two mask tensors, and the post-processing methods take phase = 0 | 1.  It needs levels = 1 and neither local= nor rank=.
+    phases = 2 (the default) is the plain path, call for call."""
     levels = 1
+    phases = 2
+    contexts_b = ()
     colour = None
     local = None
     rank = None
@@ -202,9 +208,16 @@ class Segmenter:
         """channels of the planes the run iterates on: the ingested ones', or with rank= and local= what their codes make of them"""
         return self.local[2] if self.local else self.rank[2] if self.rank else self.channels
 
-    def __init__(self, n, h, w, channels=1, params=None, device=0, options=None, levels=1, colour=None, order="rgb", local=None, rank=None):
+    def __init__(self, n, h, w, channels=1, params=None, device=0, options=None, levels=1, colour=None, order="rgb", local=None, rank=None,
+                 phases=2, params2=None):
         if n < 1:
             raise ValueError(f"n must be >= 1, got {n}")
+        if phases not in (2, 4) or isinstance(phases, bool):
+            raise ValueError(f"phases must be 2 or 4, got {phases!r}")
+        if phases == 4 and (levels != 1 or local is not None or rank is not None):
+            raise ValueError("phases=4 needs levels = 1 and neither local= nor rank=")
+        if phases != 4 and params2 is not None:
+            raise ValueError("params2 (the parameters of the second level set) needs phases=4")
         shapes = check_levels(levels, h, w)
         self.colour, self.order = check_colour(colour, order, channels)
         self.rank = check_rank(rank, channels)
@@ -218,7 +231,14 @@ class Segmenter:
         self.energy_series = None   # segment(energy_every=K > 0): [(iterations so far, capi.Energy)] of the last segment() per member
         self.contexts = []
         self.pyramids = []
+        self.phases = phases
+        self.contexts_b = []
         try:
+            for _ in range(n if phases == 4 else 0):   # the second level sets: params2 (None: params), the same options
+                ctx = capi.Context(h, w, channels, params2 if params2 is not None else params, self.device)
+                self.contexts_b.append(ctx)
+                for key, value in (options or {}).items():
+                    ctx.set_option(key, value)
             for _ in range(n):
                 self.pyramids.append([])
                 for k, (lh, lw) in enumerate(shapes):
@@ -240,8 +260,9 @@ class Segmenter:
         for pyr in self.pyramids:
             for ctx in pyr:
                 ctx.close()
-        for ctx in list(self.sources) + list(self.ranked):
+        for ctx in list(self.sources) + list(self.ranked) + list(self.contexts_b):
             ctx.close()
+        self.contexts_b = []
         self.contexts = []
         self.pyramids = []
         self.sources = []
@@ -256,7 +277,78 @@ class Segmenter:
     def _stream(self):
         return torch.cuda.current_stream(self.device).cuda_stream
 
-    def segment(self, images, max_steps=-1, perona_malik=None, init="checkerboard", invert=False, layout=None, reinit_every=0, energy_every=0):
+    def _phase(self, phase):
+        """the contexts a post-processing method works on: phase 0 the first level sets (all there are with phases = 2), 1 the second"""
+        if phase not in (0, 1) or isinstance(phase, bool) or (phase == 1 and self.phases != 4):
+            raise ValueError(f"phase must be 0" + (" or 1" if self.phases == 4 else " (phases = 2: there is one level set)") + f", got {phase!r}")
+        return self.contexts_b if phase == 1 else self.contexts
+
+    def _start(self, contexts, kind, start, init, bits, stream):
+        """the initial level sets of `contexts` (phases = 4: of either phase), as segment() builds them"""
+        if kind == "checkerboard":
+            capi.init_checkerboard_batch(contexts)
+        elif kind == "otsu":
+            return capi.init_otsu_batch(contexts)
+        elif kind == "threshold":
+            capi.init_threshold_batch(contexts, start)
+        elif kind == "rect":
+            capi.init_rect_batch(contexts, start)
+        elif kind == "disk":
+            capi.init_disk_batch(contexts, start)
+        else:
+            for i, ctx in enumerate(contexts):
+                ctx.set_levelset_device(init[i].data_ptr(), bits, stream)
+        return None
+
+    def _segment4(self, images, max_steps, perona_malik, init, init2, layout):
+        """segment() with phases = 4: ingest into both contexts of every pair -> (Perona-Malik, colour on both) -> phi1 from init, phi2 from
+        init2 -> cvh_multiphase_run per pair -> labels.  Returns (labels, steps, norms): labels a uint8 tensor (N, H, W) of 0 .. 3 =
+        mask(phi1) + 2 mask(phi2), steps the iterations and norms the (||d1||, ||d2||) of every pair."""
+        kinds = []
+        for name, given in (("init", init), ("init2", init2)):
+            if isinstance(given, tuple) and len(given) == 2 and given[0] == "mask":
+                raise ValueError(f"{name}: a mask start is not built with phases=4")
+            kinds.append(check_init(given, self.n, self.channels) if isinstance(given, (str, tuple)) else (None, None))
+        layout = check_images(images, self.n, self.h, self.w, self.channels, self.device, layout)
+        bits = [None if k[0] is not None else check_levelsets(g, self.n, self.h, self.w, self.device) for k, g in zip(kinds, (init, init2))]
+        if perona_malik is not None and len(perona_malik) != 3:
+            raise ValueError("perona_malik must be (K, L, T)")
+        stream = self._stream()
+        both = list(self.contexts) + list(self.contexts_b)
+        capi.set_image_device_batch(both, [images[i].data_ptr() for i in range(self.n)] * 2, layout, stream)
+        if perona_malik is not None:
+            capi.perona_malik_batch(both, *perona_malik)
+        if self.colour is not None:
+            capi.convert_colour_batch(both, self.colour, self.order)
+        th = self._start(self.contexts, kinds[0][0], kinds[0][1], init, bits[0], stream)
+        if th is not None:
+            self.thresholds = th
+        self._start(self.contexts_b, kinds[1][0], kinds[1][1], init2, bits[1], stream)
+        res = [capi.multiphase_run(a, b, max_steps) for a, b in zip(self.contexts, self.contexts_b)]
+        labels = torch.empty((self.n, self.h, self.w), dtype=torch.uint8, device=images.device)
+        for i, (a, b) in enumerate(zip(self.contexts, self.contexts_b)):
+            a.multiphase_labels_with(b, labels[i].data_ptr(), stream)
+        return labels, [r[0] for r in res], [r[1] for r in res]
+
+    def default_init2(self):
+        """the default start of the second level sets: the checkerboard of cvh_levelset_checkerboard_host rolled by (2, 3) pixels (two
+        identical starts stay identical forever), as a float64 device tensor (N, H, W)"""
+        one = torch.from_numpy(capi.checkerboard_host(self.h, self.w)).roll((2, 3), dims=(0, 1))
+        return one.to(torch.device("cuda", self.device)).unsqueeze(0).repeat(self.n, 1, 1).contiguous()
+
+    def phase_masks(self, invert=False):
+        """phases = 4: the masks of the two level sets, two uint8 tensors (N, H, W); labels = masks[0] + 2 masks[1] (invert = False)"""
+        if self.phases != 4:
+            raise ValueError("phase_masks needs phases=4")
+        out = []
+        for contexts in (self.contexts, self.contexts_b):
+            masks = torch.empty((self.n, self.h, self.w), dtype=torch.uint8, device=torch.device("cuda", self.device))
+            capi.get_mask_device_batch(contexts, [masks[i].data_ptr() for i in range(self.n)], invert, self._stream())
+            out.append(masks)
+        return tuple(out)
+
+    def segment(self, images, max_steps=-1, perona_malik=None, init="checkerboard", invert=False, layout=None, reinit_every=0, energy_every=0,
+                init2=None):
         """ingest -> (Perona-Malik batch) -> initial level set -> cvh_run_batch -> masks.  Returns (masks, steps, norms): masks a uint8
         tensor (N, H, W) on the images' device, valid for the next operation on the current stream without a host wait of the caller's;
         steps / norms the iterations and the last ||u_diff|| of every member.  `layout` (capi.LAYOUT_*) is needed only for a shape that is
@@ -285,7 +377,16 @@ class Segmenter:
         energy_every = K > 0 runs segments of K iterations with the energy of the members still iterating taken after each
         (capi.run_batch_monitored, one cvh_energy_batch per segment; max_steps stays the total budget) and stores the series in
         self.energy_series; 0 takes none and leaves self.energy_series None.  It is a ValueError with levels > 1 or reinit_every > 0.
-        energies() gives the terms of the final level sets either way."""
+        energies() gives the terms of the final level sets either way.
+        phases = 4 (the constructor's): phi1 starts as `init` says, phi2 as `init2` does -- the same forms but a mask; None: the checkerboard
+        rolled by (2, 3) pixels (default_init2) -- and the result is (labels, steps, norms) of _segment4; invert, reinit_every and
+        energy_every are ValueErrors there."""
+        if self.phases == 4:
+            if invert or reinit_every or energy_every:
+                raise ValueError("phases=4: invert, reinit_every and energy_every are not built for a pair of level sets")
+            return self._segment4(images, max_steps, perona_malik, init, self.default_init2() if init2 is None else init2, layout)
+        if init2 is not None:
+            raise ValueError("init2 (the start of the second level set) needs phases=4")
         kind, bits = None, None
         mask_init = isinstance(init, tuple) and len(init) == 2 and init[0] == "mask"
         if mask_init and self.levels > 1:
@@ -365,7 +466,7 @@ class Segmenter:
         (cvh_energy_batch: one set of launches, one host wait).  Returns [capi.Energy], each bit for bit its context's Context.energy()."""
         return capi.energy_batch(self.contexts)
 
-    def score(self, truths, invert=False, tol=2.0):
+    def score(self, truths, invert=False, tol=2.0, phase=0):
         """Every member's mask against its ground truth (cvh_score_mask_device_batch: one set of launches on the device, one host wait):
         truths is a uint8 or bool device tensor (N, H, W), non-zero = foreground (a bool tensor is viewed as uint8, no copy), ordered
         behind the current stream; tol the surface tolerance in pixels.  Returns [capi.Score], each integer its context's Context.score()."""
@@ -377,14 +478,14 @@ class Segmenter:
         t = truths.view(torch.uint8) if truths.dtype == torch.bool else truths
         if not t.is_contiguous():
             t = t.contiguous()
-        return capi.score_batch(self.contexts, [t[i].data_ptr() for i in range(self.n)], invert, tol, self._stream())
+        return capi.score_batch(self._phase(phase), [t[i].data_ptr() for i in range(self.n)], invert, tol, self._stream())
 
-    def components(self, conn=4, invert=False):
+    def components(self, conn=4, invert=False, phase=0):
         """The connected components of every member's mask (cvh_components_batch): (labels, counts), labels an int32 tensor (N, H, W) --
         0 background, 1..K in the order of scipy.ndimage.label -- valid for the next operation on the current stream, counts the K of
         every member.  One host wait, for the counts."""
         labels = torch.empty((self.n, self.h, self.w), dtype=torch.int32, device=torch.device("cuda", self.device))
-        counts = capi.components_batch(self.contexts, [labels[i].data_ptr() for i in range(self.n)], conn, invert, self._stream())
+        counts = capi.components_batch(self._phase(phase), [labels[i].data_ptr() for i in range(self.n)], conn, invert, self._stream())
         return labels, counts
 
     def _byte_planes(self, t, name):
@@ -397,7 +498,7 @@ class Segmenter:
         t = t.view(torch.uint8) if t.dtype == torch.bool else t
         return t if t.is_contiguous() else t.contiguous()
 
-    def clean_masks(self, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False, morph=None, radius=0.0):
+    def clean_masks(self, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False, morph=None, radius=0.0, phase=0):
         """Every member's cleaned mask (cvh_get_mask_clean_device_batch; Context.get_mask_clean names the steps) as a uint8 tensor
         (N, H, W), valid for the next operation on the current stream without a host wait of the caller's.  morph = "dilate" / "erode" /
         "open" / "close" (or a capi.MORPH_* code) applies that operation by a disk of `radius` pixels (one number or one per member) behind
@@ -405,26 +506,26 @@ class Segmenter:
         masks = torch.empty((self.n, self.h, self.w), dtype=torch.uint8, device=torch.device("cuda", self.device))
         ptrs = [masks[i].data_ptr() for i in range(self.n)]
         if morph is None:
-            capi.get_mask_clean_device_batch(self.contexts, ptrs, conn, invert, min_area, fill_holes, keep_largest, self._stream())
+            capi.get_mask_clean_device_batch(self._phase(phase), ptrs, conn, invert, min_area, fill_holes, keep_largest, self._stream())
         else:
-            capi.mask_morph_batch(self.contexts, ptrs, morph, radius=radius, conn=conn, invert=invert, min_area=min_area, fill_holes=fill_holes,
+            capi.mask_morph_batch(self._phase(phase), ptrs, morph, radius=radius, conn=conn, invert=invert, min_area=min_area, fill_holes=fill_holes,
                                   keep_largest=keep_largest, stream=self._stream())
         return masks
 
-    def morph(self, op, radius, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False, inside=1.0, outside=-1.0):
+    def morph(self, op, radius, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False, inside=1.0, outside=-1.0, phase=0):
         """clean_masks(morph=op, radius=radius) IN PLACE (cvh_morph_levelset_batch: one set of launches, one host wait): every member's
         level set becomes `inside` where that mask is 1 and `outside` elsewhere, and a new run begins as after a fresh level set.
         components(), measure(), contours(), score(), levelsets() and further iterations then see the result; the masks never leave the
         device.  op None bakes the cleaned mask in."""
-        capi.morph_levelset_batch(self.contexts, op, radius=radius, conn=conn, invert=invert, min_area=min_area, fill_holes=fill_holes,
+        capi.morph_levelset_batch(self._phase(phase), op, radius=radius, conn=conn, invert=invert, min_area=min_area, fill_holes=fill_holes,
                                   keep_largest=keep_largest, inside=inside, outside=outside)
 
-    def measure(self, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False, cap=None):
+    def measure(self, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False, cap=None, phase=0):
         """The components of every member's mask -- clean_masks' for the same options, (0, 0, False) the raw one -- measured on the device
         (cvh_measure_batch: one set of launches, ordered behind the current stream): one (K, table) per member, table a numpy structured
         array (capi.REGION_DTYPE) of the first min(K, cap) rows, bit for bit its context's Context.measure(); capi.region_shapes derives
         centroid, moments, axes, mean and variance from it.  cap = None asks for every row at the price of a first call for the counts."""
-        return capi.measure_batch(self.contexts, conn, invert, min_area, fill_holes, keep_largest, cap, self._stream())
+        return capi.measure_batch(self._phase(phase), conn, invert, min_area, fill_holes, keep_largest, cap, self._stream())
 
     def _label_planes(self, labels):
         """an int32 device tensor (N, H, W), or a list of N tensors (H, W), as N contiguous planes; ValueError for anything else"""
@@ -440,24 +541,24 @@ class Segmenter:
             out.append(p if p.is_contiguous() else p.contiguous())
         return out
 
-    def overlaps(self, labels, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False, cap=None):
+    def overlaps(self, labels, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False, cap=None, phase=0):
         """The contingency table of every member's components -- measure's for the same options -- against a second label plane each
         (cvh_overlaps_device_batch: one set of launches, ordered behind the current stream).  labels is an int32 device tensor
         (N, H, W) or a list of N tensors (H, W): an instance ground truth, or the tensors components() returned for the PREVIOUS FRAME
         (frame-to-frame correspondence: the labels never leave the device).  Returns one row array per member (capi.OVERLAP_DTYPE: a, b,
         count; sorted by a, then b; a = 0 and b = 0 included), byte for byte its context's Context.overlaps()."""
         planes = self._label_planes(labels)
-        res = capi.overlaps_batch(self.contexts, [p.data_ptr() for p in planes], conn, invert, min_area, fill_holes, keep_largest, cap, self._stream())
+        res = capi.overlaps_batch(self._phase(phase), [p.data_ptr() for p in planes], conn, invert, min_area, fill_holes, keep_largest, cap, self._stream())
         return [rows for rows, _ in res]
 
-    def match(self, labels, threshold=0.5, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False):
+    def match(self, labels, threshold=0.5, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False, phase=0):
         """overlaps() read as object-level scores (capi.match_overlaps on every member's table): one (score, match_of_a, ious) per member
         -- score a capi.ObjectScore at the IoU threshold (strictly above; a number >= 0.5 taken in thousandths, or a pair (num, den)),
         with mean_ap over 0.50 .. 0.95; match_of_a[a - 1] the label component a matched, or 0; ious the exact (a, b, num, den) of the
         matched pairs.  labels as in overlaps(): a ground truth, or components() of the previous frame."""
-        return [capi.match_overlaps(rows, threshold) for rows in self.overlaps(labels, conn, invert, min_area, fill_holes, keep_largest)]
+        return [capi.match_overlaps(rows, threshold) for rows in self.overlaps(labels, conn, invert, min_area, fill_holes, keep_largest, phase=phase)]
 
-    def contours(self, conn=8, invert=False, min_area=0, fill_holes=0, keep_largest=False, simplify=None, subpixel=False):
+    def contours(self, conn=8, invert=False, min_area=0, fill_holes=0, keep_largest=False, simplify=None, subpixel=False, phase=0):
         """The boundary of every member's mask -- clean_masks' for the same options -- as ordered closed loops, traced on the device
         (cvh_contours_device_batch, ordered behind the current stream): one (loops, points) per member, loops a numpy structured array
         (capi.CONTOUR_LOOP_DTYPE), points an int32 device tensor (P, 2) of x, y, valid for the next operation on the current stream;
@@ -473,18 +574,18 @@ class Segmenter:
         else:
             batch, dtype = capi.contours_batch, torch.int32
             opts["simplify"] = True if simplify is None else simplify
-        counts = batch(self.contexts, loop_caps=[0] * self.n, stream=self._stream(), **opts)
+        counts = batch(self._phase(phase), loop_caps=[0] * self.n, stream=self._stream(), **opts)
         points = [torch.empty((c[1], 2), dtype=dtype, device=torch.device("cuda", self.device)) for c in counts]
-        rows = batch(self.contexts, [p.data_ptr() if p.numel() else 0 for p in points], [c[1] for c in counts],
+        rows = batch(self._phase(phase), [p.data_ptr() if p.numel() else 0 for p in points], [c[1] for c in counts],
                      loop_caps=[c[0] for c in counts], stream=self._stream(), **opts)
         return [(r[2], p) for r, p in zip(rows, points)]
 
-    def levelsets(self, dtype=torch.float64):
+    def levelsets(self, dtype=torch.float64, phase=0):
         """The members' level sets as a device tensor (N, H, W), float64 or float32 (rounded to nearest even)."""
         if dtype not in (torch.float64, torch.float32):
             raise ValueError(f"dtype must be float64 or float32, got {dtype}")
         out = torch.empty((self.n, self.h, self.w), dtype=dtype, device=torch.device("cuda", self.device))
-        for i, ctx in enumerate(self.contexts):
+        for i, ctx in enumerate(self._phase(phase)):
             ctx.get_levelset_device(out[i].data_ptr(), 64 if dtype == torch.float64 else 32, self._stream())
         return out
 

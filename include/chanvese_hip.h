@@ -1176,6 +1176,67 @@ int cvh_init_mask_device(cvh_context *ctx, const uint8_t *d_mask, double inside,
 int cvh_init_mask_device_batch(cvh_context *const *ctxs, int n, const uint8_t *const *d_masks, double inside, double outside,
                                void *stream);
 
+/* ---- Four phases ----------------------------------------------------------------------------------------------------------------
+ * Vese and Chan's multiphase model: TWO level sets evolved together, whose sign pairs name four regions -- what an image with three or
+ * four grey classes needs and one level set cannot give.  A PAIR is two contexts A and B on one device with the same h, w and channel
+ * count C: A holds phi1, B holds phi2.  The image is A's planes; B's planes are not read by the iteration (B must still hold an image:
+ * its stop condition and its later mask calls are defined by it).  The pair has no object of its own and keeps nothing between calls;
+ * every mask-based call (cvh_components, cvh_measure, cvh_contours*, cvh_score_mask*, cvh_morph_levelset, cvh_reinit, cvh_overlaps*)
+ * works on either context unchanged.  The reference has no such model; the definition below IS the contract.
+ *     H1 = H_eps(phi1), H2 = H_eps(phi2), f = I_k as double (H_eps, delta_eps, kappa exactly those of the two-phase step: the
+ *     reference's regularized_heaviside, regularized_delta and curvature with its border rule)
+ *     w11 = H1 H2, w10 = H1 (1 - H2), w01 = (1 - H1) H2, w00 = (1 - H1)(1 - H2);  c_ab[k] = sum f w_ab / sum w_ab over all pixels
+ * One iteration updates both level sets from the OLD pair (Jacobi):
+ *     F1 = sum_k [ H2 (-l1A[k] (f - c11[k])^2 + l2A[k] (f - c01[k])^2) + (1 - H2)(-l1A[k] (f - c10[k])^2 + l2A[k] (f - c00[k])^2) ]
+ *     F2 = sum_k [ H1 (-l1B[k] (f - c11[k])^2 + l2B[k] (f - c10[k])^2) + (1 - H1)(-l1B[k] (f - c01[k])^2 + l2B[k] (f - c00[k])^2) ]
+ *     d1 = dtA (muA kappa(phi1) - nuA + F1 / C) delta_eps(phi1),  phi1 <- phi1 + d1
+ *     d2 = dtB (muB kappa(phi2) - nuB + F2 / C) delta_eps(phi2),  phi2 <- phi2 + d2
+ * A's cvh_params govern phi1's equation (l1A = lambda1, l2A = lambda2 of A), B's govern phi2's; eps must be equal in both.  Per level
+ * set this is the two-phase combine (src/main.cpp:985, folded as there: kappa (dt mu) + F (dt / C) - dt nu) with the region term
+ * blended by the other level set's Heaviside.  The stop rule is tested after the update, as in the reference: the pair stops at the
+ * first iteration with ||d1||_2 <= stop(A) and ||d2||_2 <= stop(B), stop(X) what cvh_get_stop_condition(X) returns; the stopping
+ * iteration's update is kept, later iterations of the same call change nothing.  Arithmetic is A's "math_mode": CVH_MATH_STRICT the
+ * op-by-op forms, CVH_MATH_FAST (the default) the forms and refinements of the wave kernels; both agree with a numpy restatement of
+ * the definition to 1e-9 (tests/test_gpu_multiphase.py).
+ * cvh_multiphase_run iterates until max_steps iterations are done (max_steps < 0: no bound) or the pair stops.  steps_done, norms
+ * ({||d1||, ||d2||} of the last executed iteration) and trace may be NULL.  Row t of the trace (4 C + 2 doubles, at most trace_rows rows,
+ * *rows written) is [c11[0..C), c10[..], c01[..], c00[..], ||d1||, ||d2||]: the means iteration t used and its two norms.  The call
+ * settles both contexts as the getters do, takes the pair's initial sums itself, and ends with both contexts exactly as
+ * cvh_set_levelset of the new doubles leaves them (a new run begins on each: counters 0, the two-phase means not yet taken); a
+ * one-context run continued afterwards is bit for bit what it is after cvh_set_levelset of the fetched doubles.  Device work runs on
+ * A's stream, joined with B's before and after; the host enqueues A's "sync_every" iterations at a time (two launches each) and waits
+ * once per chunk for the pair's state block.  Launches enqueued behind a stop return at once.  Workspaces (state block, partial sums,
+ * trace) are A's, allocated on first use and kept; the level sets iterate in the contexts' own buffer pairs.  cvh_last_run_ms(A)
+ * afterwards is the device's time from the first iteration's launch to the end of the last chunk (the waits between chunks included).
+ * Determinism: every result depends on the inputs and the shape alone.  Partial sums are taken per ITEM of a fixed partition of the
+ * plane (cvh_multiphase_geometry: strips of *strip_rows rows x *cols columns, *items of them; a function of h and w alone, not of the
+ * device) and added in a fixed order by a one-workgroup launch; no atomics.  Two runs of the same pair give the same bits.  One call of
+ * m + n iterations and two calls of m and of n give the same bits as well, in both arithmetic modes: the second call takes its initial
+ * sums again, but over the same partition, in the same order and with the same form of H_eps per pixel (in CVH_MATH_FAST the form is
+ * chosen per wave and row by the row's own pixels alone), of the very doubles the first call stored.
+ * cvh_multiphase_means returns the 4 C means of the CURRENT pair, c[ab C + k] in the order 11, 10, 01, 00; it only reads.
+ * cvh_multiphase_labels / _device write label = mask(A) + 2 mask(B) per pixel (0 .. 3), mask as cvh_get_mask(.., invert = 0) defines
+ * it: one launch on A's stream; they only read.  The device form is ordered behind `stream` and in front of what is enqueued on it
+ * later, and does not make the host wait.  A run of either context continued after a read-only call is bit-identical to one without it.
+ * CVH_ERR_ARG: a NULL or identical pair, different devices, shapes or channel counts, different eps, "state" = 32 on either context,
+ * h*w >= 2^28, a NULL output (c, labels, d_labels) or memory the device cannot address, a trace without rows or with trace_rows < 0.
+ * CVH_ERR_STATE: a context without a level set, or (run, means) without an image.  Everything is checked before anything is touched;
+ * the message is cvh_last_error(NULL)'s (and A's); after such a refusal the contexts are as they were and stay usable.  (A HIP error
+ * inside a run -- CVH_ERR_HIP -- is another matter: the level sets may be partly iterated; give both contexts new level sets.)
+ * Empty regions: there is no guard.  A region whose weight sum is exactly 0 has the means 0 / 0 = NaN, as IEEE division gives and as
+ * cvh_get_means gives for a wholly empty side of one level set; a nearly empty region has whatever the quotient of its two sums is.
+ * H_eps reaches 0 or 1 exactly only far from the front -- in CVH_MATH_FAST from |phi| of about 1e16 eps on, over the WHOLE plane.  The
+ * NaN then reaches both level sets and both norms with the next iteration, the stop rule never fires on a NaN norm (the run ends at
+ * max_steps), and none of it is an error.
+ * Not here: batches of pairs in shared launches, the resident (LDS) flow, FP32 state, a four-phase energy, pyramids and
+ * reinitialisation inside the run (cvh_reinit on each context between runs works), more than two level sets. */
+int cvh_multiphase_run(cvh_context *a, cvh_context *b, int max_steps, int *steps_done, double *norms /* 2 */, double *trace, int trace_rows,
+                       int *rows);
+int cvh_multiphase_means(cvh_context *a, cvh_context *b, double *c /* 4 C */);
+int cvh_multiphase_labels(cvh_context *a, cvh_context *b, uint8_t *labels);   /* host bytes, 0 .. 3 */
+int cvh_multiphase_labels_device(cvh_context *a, cvh_context *b, uint8_t *d_labels, void *stream);
+void cvh_multiphase_geometry(int h, int w, int *cols, int *strip_rows, int *items);   /* pure host arithmetic; 0 rows / items: not a plane the calls take */
+
 /* Library version string, e.g. "chanvese_hip 0.1 (gfx950)". */
 const char *cvh_version(void);
 
