@@ -48,6 +48,7 @@ EXPORTS = [
     "cvh_get_mask_morph", "cvh_get_mask_morph_device", "cvh_get_mask_morph_device_batch", "cvh_morph_levelset", "cvh_morph_levelset_batch",
     "cvh_init_mask", "cvh_init_mask_device", "cvh_init_mask_device_batch",
     "cvh_multiphase_run", "cvh_multiphase_means", "cvh_multiphase_labels", "cvh_multiphase_labels_device", "cvh_multiphase_geometry",
+    "cvh_localized_run", "cvh_localized_means", "cvh_localized_geometry",
 ]
 # "Mask morphology": the operations of cvh_get_mask_morph* / cvh_morph_levelset*, by code and by name
 MORPH_NONE, MORPH_DILATE, MORPH_ERODE, MORPH_OPEN, MORPH_CLOSE = 0, 1, 2, 3, 4
@@ -380,6 +381,9 @@ def lib():
         "cvh_multiphase_labels": (C.c_int, [vp, vp, u8p]),
         "cvh_multiphase_labels_device": (C.c_int, [vp, vp, vp, vp]),
         "cvh_multiphase_geometry": (None, [C.c_int, C.c_int, ip, ip, ip]),
+        "cvh_localized_run": (C.c_int, [vp, C.c_int, C.c_int, ip, dp, dp, C.c_int, ip]),
+        "cvh_localized_means": (C.c_int, [vp, C.c_int, dp, dp, vp, vp, vp]),
+        "cvh_localized_geometry": (None, [C.c_int, C.c_int, C.c_int, ip, ip, ip, ip]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -1144,6 +1148,31 @@ def multiphase_means(a, b):
     return c
 
 
+def localized_geometry(h, w, radius):
+    """cvh_localized_geometry: (columns per wave, rows per item, items, rows per strip) -- the fixed partition the norm of the localised
+    run is summed over (a function of h and w alone) and the rows one wave marches down at this radius; pure host arithmetic (rows and
+    items are 0 for a plane or radius the calls refuse)."""
+    cols, rows, items, strip = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+    lib().cvh_localized_geometry(int(h), int(w), int(radius), C.byref(cols), C.byref(rows), C.byref(items), C.byref(strip))
+    return cols.value, rows.value, items.value, strip.value
+
+
+def localized_run(ctx, radius, max_steps=-1, trace=False):
+    """cvh_localized_run ("Localised regions" in include/chanvese_hip.h): localised Chan-Vese with the region means taken over the
+    (2 radius + 1)^2 window of every pixel, until max_steps iterations are done (negative: no bound) or the stop rule fires.  Returns
+    (steps_done, norm, trace): trace is None, or with trace=True (all rows; needs max_steps >= 0) or trace=<rows> an array of the
+    iterations' ||d||.  The context is left as set_levelset of the new level set leaves it.  The local force is small: start near the
+    object and raise mu."""
+    want = 0 if trace is False or trace is None else (int(max_steps) if trace is True else int(trace))
+    if want < 0:
+        raise ValueError("trace=True needs max_steps >= 0 (or pass the number of rows)")
+    done, rows, norm = C.c_int(0), C.c_int(0), C.c_double(0.0)
+    out = np.zeros(max(want, 1), dtype=np.float64) if want or trace is True else None
+    ctx._chk(lib().cvh_localized_run(ctx._h, int(radius), int(max_steps), C.byref(done), C.byref(norm), None if out is None else _dp(out), want,
+                                     C.byref(rows)))
+    return done.value, norm.value, None if out is None else out[:rows.value].copy()
+
+
 def run_monitored(ctx, max_steps=-1, every=16, rel_plateau=None):
     """Context.run in segments of `every` iterations with the energy (Context.energy) taken after each segment.  Returns (total steps,
     last norm, [(steps so far, Energy)]).  max_steps is the total budget (< 0: unlimited); the run ends when the stop rule fired inside
@@ -1383,6 +1412,16 @@ class Context:
         rows = C.c_int(0)
         self._chk(self._L.cvh_get_trace(self._h, _dp(out), int(max_rows), C.byref(rows)))
         return out[:rows.value].copy()
+
+    def localized_means(self, radius, want=("c1", "c2", "wq", "a", "s")):
+        """cvh_localized_means: the local means of the CURRENT level set and the integer sums they are quotients of, as a dict of the
+        planes named in `want`: c1, c2 float64 (C, h, w); wq, a uint64 (h, w); s uint64 (C, h, w).  Only reads."""
+        shapes = {"c1": (np.float64, True), "c2": (np.float64, True), "wq": (np.uint64, False), "a": (np.uint64, False), "s": (np.uint64, True)}
+        out = {k: np.zeros((self.channels, self.h, self.w) if shapes[k][1] else (self.h, self.w), dtype=shapes[k][0]) for k in want}
+        ptr = lambda k, cast: cast(out[k]) if k in out else None
+        addr = lambda a: a.ctypes.data
+        self._chk(self._L.cvh_localized_means(self._h, int(radius), ptr("c1", _dp), ptr("c2", _dp), ptr("wq", addr), ptr("a", addr), ptr("s", addr)))
+        return out
 
     def multiphase_labels_with(self, b, ptr=0, stream=0):
         """cvh_multiphase_labels / _device: label = mask(self) + 2 mask(b) per pixel, one launch.  Returns a uint8 array of (h, w), or

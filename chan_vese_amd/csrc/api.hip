@@ -155,6 +155,8 @@ extern "C" void cvh_destroy(cvh_context *c)
   if (c->d_overlap_plane) (void)hipFree(c->d_overlap_plane);
   if (c->d_multiphase) (void)hipFree(c->d_multiphase);
   free_table(&c->mp_trace);
+  if (c->d_localized) (void)hipFree(c->d_localized);
+  free_table(&c->loc_trace);
   if (c->ev_io_in) (void)hipEventDestroy(c->ev_io_in);
   if (c->ev_io_out) (void)hipEventDestroy(c->ev_io_out);
   if (c->h_resident) (void)hipHostFree(c->h_resident);

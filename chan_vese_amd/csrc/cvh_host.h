@@ -6,7 +6,7 @@
 // level sets), components_run.hip (connected components, and MaskSource: the raw or cleaned mask every mask-derived call starts from),
 // pyramid_run.hip (coarse-to-fine), colour_run.hip (colour spaces), window_run.hip (local statistics and rank planes: the windowed-plane calls), energy_run.hip (the functional's terms), score_run.hip (mask scores),
 // morph_run.hip (mask morphology, mask starts), measure_run.hip (component measures), contour_run.hip (contours), overlap_run.hip
-// (component overlaps), multiphase_run.hip (four phases: a pair of contexts iterated together), debug_exports.hip (diagnostics).  Kernel
+// (component overlaps), multiphase_run.hip (four phases: a pair of contexts iterated together), localized_run.hip (localised regions), debug_exports.hip (diagnostics).  Kernel
 // sources do not include it.
 #pragma once
 #include <limits.h>
@@ -187,6 +187,9 @@ struct cvh_context {   // opaque to callers; four groups
   void *d_multiphase = nullptr;  // workspace of cvh_multiphase_* as their FIRST context (multiphase_run.hip): the pair's state block and the items'
                                  // partial sums: allocated by the first call, kept -- not part of live_footprint either
   DeviceTable mp_trace;          // and the trace rows of the longest cvh_multiphase_run so far that asked for them, grown on demand, kept
+  void *d_localized = nullptr;   // workspace of cvh_localized_* (localized_run.hip): state block, the items' partial sums, the 1 + C planes of
+                                 // horizontal window sums and the C planes of T_k: (8 + 12 C) bytes per pixel, allocated by the first call, kept
+  DeviceTable loc_trace;         // and the trace rows of the longest cvh_localized_run so far that asked for them, grown on demand, kept
   int coop_launch = -1;          // does the device launch cooperatively (-1: not asked yet; launches_cooperatively)
   int resident_cap = -1;         // workgroups of csv_resident_kernel the device holds at once (-1: not asked yet, 0: unavailable)
   int pm_resident_cap = -1;      // workgroups of pm_resident_kernel the device holds at once (-1: not asked yet)

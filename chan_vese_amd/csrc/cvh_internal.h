@@ -456,6 +456,53 @@ hipError_t cvh_launch_mp_step(const CvhMpArgs &a, int channels, int fast, hipStr
 hipError_t cvh_launch_mp_finalize(const CvhMpArgs &a, int channels, int is_init, hipStream_t s);
 // labels: one member; src phi1, src2 phi2, dst the bytes (any alignment), sections of cvh_io_blocks(n) workgroups
 hipError_t cvh_launch_mp_labels(const CvhIoMember *tab, int nmem, unsigned grid, hipStream_t s);
+// localised regions (localized_kernels.hip; include/chanvese_hip.h, "Localised regions").  Per iteration a ROW pass (a workgroup per row
+// segment of CVH_WINDOW_SEGMENT columns) writes the horizontal window sums of wq and wq f_k -- 1 + C planes of unsigned 64-bit integers
+// -- into the context's workspace; a STEP kernel's waves march down strips of strip_rows rows x CVH_LOC_COLS columns with the vertical
+// running sums of those planes in registers.  ||d||^2 is stored per ITEM -- item_rows rows x CVH_LOC_COLS columns, a function of the
+// shape alone; a strip is a whole number of items, that number a function of the radius -- and added by the one-workgroup finalise.
+#define CVH_LOC_COLS 61          // output columns per wave: lanes 2 .. 62 (lanes 0, 1 and 63 hold the strip's halo columns)
+#define CVH_LOC_RADIUS_MAX 127
+#define CVH_LOC_FRAC_BITS 40     // wq = rint(H_eps 2^40)
+#define CVH_LOC_TARGET_WAVES 4096
+#define CVH_LOC_MIN_ROWS 8
+#define CVH_LOC_LEAD 2           // a strip has at least CVH_LOC_LEAD (2 R + 1) rows: its lead-in is at most a third of the workspace rows it reads
+static_assert((2ull * CVH_LOC_RADIUS_MAX + 1) * (2 * CVH_LOC_RADIUS_MAX + 1) * 255 < (1ull << (64 - CVH_LOC_FRAC_BITS)),
+              "every window sum fits in 64 unsigned bits: 65025 * 255 * 2^40 < 2^64");
+struct CvhLocGeom { int nwc, item_rows, nitem_rows, nitems, strip_rows, nstrips, nseg; unsigned grid, row_grid; };
+CvhLocGeom cvh_loc_geometry(int h, int w, int radius);
+struct CvhLocState {
+  double norm;                     // ||d||_2 of the last executed iteration
+  int steps_done;                  // iterations executed in this call
+  int stopped;                     // sticky: the stop rule fired; every later launch of the call returns at once
+};
+struct CvhLocArgs {
+  const double *in;                // u read
+  double *out;                     // u written (step alone)
+  const uint8_t *img[CVH_MAX_CHANNELS];
+  CvhLocState *st;
+  double *partials;                // [nitems]
+  unsigned long long *hw;          // [1 + C][h][w]: horizontal window sums of wq, wq f_k (plane-sum pass: of 1, f_k)
+  unsigned *tsum;                  // [C][h][w]: T_k, the window sums of f_k
+  double *trace;                   // [trace_cap] or null
+  int trace_cap;
+  int h, w, radius;
+  CvhLocGeom g;
+  double alpha, beta, gamma;       // dt mu, dt / C, -dt nu
+  double lambda1[CVH_MAX_CHANNELS], lambda2[CVH_MAX_CHANNELS];
+  double eps, inv_eps, dk1;        // FAST: 1 / eps, pi / eps
+  double far_k[5], far_thr;        // FAST: far-field series of H_eps (wave_math.h)
+  const double *atan2_tab;         // FAST: [CVH_ATAN2_N]
+  double stop;                     // what cvh_get_stop_condition returns
+  // cvh_localized_means: device planes or null
+  unsigned long long *wq_out, *a_out, *s_out;
+  double *c1_out, *c2_out;
+};
+enum { CVH_LOC_STEP = 0, CVH_LOC_MEANS = 1, CVH_LOC_TSUM = 2 };
+// the row pass that goes with the wave kernel of kind `pass`: STEP reads the run's stop flag, MEANS does not, TSUM has wq = 1 (the plane sums)
+hipError_t cvh_launch_loc_rows(const CvhLocArgs &a, int channels, int fast, int pass, hipStream_t s);
+hipError_t cvh_launch_loc_wave(const CvhLocArgs &a, int channels, int fast, int kind, hipStream_t s);
+hipError_t cvh_launch_loc_finalize(const CvhLocArgs &a, hipStream_t s);
 // rows-per-tile options of the step kernel
 void cvh_step_grid(int h, int w, int tile_rows, int *tiles_x, int *tiles_y);
 int cvh_step_max_blocks(int h, int w);

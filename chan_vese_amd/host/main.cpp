@@ -21,7 +21,7 @@
 // "Mask morphology") for --dump-mask, --roi, --measure, --contours and _selection; --init-mask FILE starts from a binary PGM.
 // Additions that do not collide with reference options: --dump-u, --dump-mask, --device, --math,
 // --state, --rect, --circ, --disk, --init, --threshold, --reinit, --connectivity, --min-area, --fill-holes, --largest, --roi, --verbose,
-// --levels, --energy, --energy-every, --truth, --score-tol, --measure, --contours, --contours-all, --contours-subpixel, --morph, --morph-radius, --init-mask, --truth-labels, --phases, --init2, --dump-labels (--phases 4: chanvese_hip.h, "Four phases" -- two contexts, cvh_multiphase_run, the labels; what does not compose with it is refused).  --truth-labels FILE
+// --levels, --energy, --energy-every, --truth, --score-tol, --measure, --contours, --contours-all, --contours-subpixel, --morph, --morph-radius, --init-mask, --truth-labels, --phases, --init2, --dump-labels, --localized (--localized R: cvh_localized_run, "Localised regions"; --phases 4: chanvese_hip.h, "Four phases" -- two contexts, cvh_multiphase_run, the labels; what does not compose with it is refused).  --truth-labels FILE
 // relates the components of the mask --dump-mask uses (the cleaning options and -I apply) to the objects of a label image of the input's
 // size (a binary PGM with maxval <= 65535 or an 8-bit grey PNG; the values are the labels, 0 = no object) on the device (chanvese_hip.h,
 // "Component overlaps") and prints one line "objects: objects_a=... objects_b=... tp=... fp=... fn=... mean_ap=..." to stdout: the counts at
@@ -240,7 +240,7 @@ const Spec kSpecs[] = {
     {"connectivity", 0, 1}, {"min-area", 0, 1}, {"fill-holes", 0, 1}, {"largest", 0, 0}, {"roi", 0, 0},
     {"verbose", 0, 0}, {"energy", 0, 0}, {"energy-every", 0, 1}, {"truth", 0, 1}, {"score-tol", 0, 1}, {"measure", 0, 1}, {"contours", 0, 1}, {"contours-all", 0, 0}, {"contours-subpixel", 0, 0},
     {"morph", 0, 1}, {"morph-radius", 0, 1}, {"init-mask", 0, 1}, {"truth-labels", 0, 1},
-    {"phases", 0, 1}, {"init2", 0, 2}, {"dump-labels", 0, 1}};
+    {"phases", 0, 1}, {"init2", 0, 2}, {"dump-labels", 0, 1}, {"localized", 0, 1}};
 
 struct Parsed {
   std::vector<std::pair<std::string, std::vector<std::string>>> opts;
@@ -462,6 +462,10 @@ void print_help()
       "  --init2 arg (=checkerboard)        checkerboard | otsu | threshold T: the start of the second level set (--phases 4); the\n"
       "                                     checkerboard is --init's rolled by (2, 3) pixels\n"
       "  --dump-labels arg                  write the labels (mask 1 + 2 mask 2, one byte per pixel, h*w) of a --phases 4 run\n"
+      "  --localized arg                    R, 1 .. 127: localised Chan-Vese -- the two region means are taken over the (2R+1)^2 window of every\n"
+      "                                     pixel and retaken every iteration (uneven illumination); honours --init, --rect, --circ, --disk and\n"
+      "                                     --init-mask; start near the object and raise --mu (of the order of 100); not with --phases 4,\n"
+      "                                     --levels, --energy, --energy-every, --reinit, -V\n"
       "  --init-mask arg                    binary PGM of the input's size as the initial contour (+1 where it is non-zero, -1 elsewhere),\n"
       "                                     written on the device at a byte per pixel; not with --levels\n"
       "  --verbose                          print the iteration count and last norm to stderr\n"
@@ -562,6 +566,11 @@ int main(int argc, char **argv)
   if (auto v = one("phases")) phases = to_int("phases", *v);
   std::string dump_labels;
   if (auto v = one("dump-labels")) dump_labels = *v;
+  int localized = 0;   // --localized R (chanvese_hip.h, "Localised regions"): cvh_localized_run in place of cvh_run
+  if (auto v = one("localized")) {
+    localized = to_int("localized", *v);
+    if (localized < 1 || localized > 127) msg_exit("Window radius (--localized) must be between 1 and 127: " + std::to_string(localized) + ".");
+  }
   segment = vm.count("segment"); grayscale = vm.count("grayscale"); write_video = vm.count("video");
   overlay_text = vm.count("overlay-text"); invert = vm.count("invert-selection");
   object_selection = vm.count("select"); rectangle_contour = vm.count("rectangle"); circle_contour = vm.count("circle");
@@ -686,6 +695,14 @@ int main(int argc, char **argv)
         {!contours_filename.empty(), "--contours"}, {invert, "an inverted selection (-I)"}};
     for (auto &r : refused)
       if (r.first) msg_exit(std::string("Four phases (--phases 4) cannot be combined with ") + r.second + ".");
+  }
+  if (localized) {
+    const std::pair<bool, const char *> refused[] = {
+        {phases == 4, "four phases (--phases 4)"}, {levels > 1, "a coarse-to-fine run (--levels)"}, {print_energy, "an energy line (--energy)"},
+        {energy_every > 0, "an energy series (--energy-every)"}, {reinit_every > 0, "reinitialisation (--reinit)"},
+        {write_video, "video output (-V)"}, {state_bits == 32, "FP32 state (--state 32)"}};
+    for (auto &r : refused)
+      if (r.first) msg_exit(std::string("Localised regions (--localized) cannot be combined with ") + r.second + ".");
   }
   if (vm.count("score-tol") && truth_filename.empty()) msg_exit("A score tolerance (--score-tol) needs a ground truth (--truth).");
   if (!(score_tol >= 0.0) || !std::isfinite(score_tol)) msg_exit("Score tolerance must be a finite number >= 0.");
@@ -1060,6 +1077,8 @@ int main(int argc, char **argv)
       energy_line(steps_done);
       if (stopped) break;
     }
+  } else if (localized) {
+    cvh_check(ctx, cvh_localized_run(ctx, localized, max_steps, &steps_done, &last_norm, nullptr, 0, nullptr), "cvh_localized_run");
   } else if (!write_video) {
     cvh_check(ctx, cvh_run(ctx, max_steps, &steps_done, &last_norm), "cvh_run");
   } else {

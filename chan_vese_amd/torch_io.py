@@ -193,9 +193,14 @@ class Segmenter:
     phases = 4 (include/chanvese_hip.h, "Four phases") makes every member a PAIR of contexts, `contexts[i]` holding phi1 and `contexts_b[i]`
     phi2, both fed the same device tensor; segment() then iterates the pairs (cvh_multiphase_run) and returns labels 0 .. 3, phase_masks()
     gives the two mask tensors, and the post-processing methods take phase = 0 | 1.  It needs levels = 1 and neither local= nor rank=.
-    phases = 2 (the default) is the plain path, call for call."""
+    phases = 2 (the default) is the plain path, call for call.
+    localized = R (1 .. 127; include/chanvese_hip.h, "Localised regions") makes every member run cvh_localized_run -- region means over
+    the (2 R + 1)^2 window of every pixel -- instead of the two-phase run, from whatever init= gives; everything after the run is
+    unchanged.  The local force is small: start near the object (init="otsu", a rect, a disk, a mask) and raise mu.  It needs phases = 2
+    and levels = 1, and segment() refuses energy_every and reinit_every with it.  None (the default) is the plain path, call for call."""
     levels = 1
     phases = 2
+    localized = None
     contexts_b = ()
     colour = None
     local = None
@@ -209,9 +214,14 @@ class Segmenter:
         return self.local[2] if self.local else self.rank[2] if self.rank else self.channels
 
     def __init__(self, n, h, w, channels=1, params=None, device=0, options=None, levels=1, colour=None, order="rgb", local=None, rank=None,
-                 phases=2, params2=None):
+                 phases=2, params2=None, localized=None):
         if n < 1:
             raise ValueError(f"n must be >= 1, got {n}")
+        if localized is not None:
+            if not isinstance(localized, int) or isinstance(localized, bool) or not 1 <= localized <= 127:
+                raise ValueError(f"localized must be None or a window radius 1 .. 127, got {localized!r}")
+            if phases == 4 or levels != 1:
+                raise ValueError("localized= needs phases = 2 and levels = 1: the localised run iterates one level set on one level")
         if phases not in (2, 4) or isinstance(phases, bool):
             raise ValueError(f"phases must be 2 or 4, got {phases!r}")
         if phases == 4 and (levels != 1 or local is not None or rank is not None):
@@ -232,6 +242,7 @@ class Segmenter:
         self.contexts = []
         self.pyramids = []
         self.phases = phases
+        self.localized = localized
         self.contexts_b = []
         try:
             for _ in range(n if phases == 4 else 0):   # the second level sets: params2 (None: params), the same options
@@ -387,6 +398,8 @@ class Segmenter:
             return self._segment4(images, max_steps, perona_malik, init, self.default_init2() if init2 is None else init2, layout)
         if init2 is not None:
             raise ValueError("init2 (the start of the second level set) needs phases=4")
+        if self.localized is not None and (reinit_every or energy_every):
+            raise ValueError("localized=: reinit_every and energy_every are not built for the localised run")
         kind, bits = None, None
         mask_init = isinstance(init, tuple) and len(init) == 2 and init[0] == "mask"
         if mask_init and self.levels > 1:
@@ -455,6 +468,8 @@ class Segmenter:
             mon = capi.run_batch_monitored(self.contexts, max_steps, energy_every)
             self.energy_series = [m[2] for m in mon]
             res = [m[:2] for m in mon]
+        elif self.localized is not None:
+            res = [capi.localized_run(ctx, self.localized, max_steps)[:2] for ctx in self.contexts]
         else:
             res = capi.run_batch_with_reinit(self.contexts, max_steps, reinit_every)
         masks = torch.empty((self.n, self.h, self.w), dtype=torch.uint8, device=images.device)

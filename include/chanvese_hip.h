@@ -1237,6 +1237,59 @@ int cvh_multiphase_labels(cvh_context *a, cvh_context *b, uint8_t *labels);   /*
 int cvh_multiphase_labels_device(cvh_context *a, cvh_context *b, uint8_t *d_labels, void *stream);
 void cvh_multiphase_geometry(int h, int w, int *cols, int *strip_rows, int *items);   /* pure host arithmetic; 0 rows / items: not a plane the calls take */
 
+/* ---- Localised regions ----------------------------------------------------------------------------------------------------------
+ * Localised (local region-based) Chan-Vese, after Lankton and Tannenbaum, Brox and Cremers, and Li's LBF: the two region means become
+ * functions of the pixel, c1(p) and c2(p), taken over a window around p and retaken every iteration.  Every other flow of this library
+ * fits each side of the contour with ONE mean per channel, which fails by construction under uneven illumination; this one changes the
+ * model, not the image.  The reference has no such model; the definition below IS the contract.
+ * Window: W(p) is the (2 R + 1)^2 square around p truncated at the plane's border -- exactly the window of "Local statistics" --
+ * 1 <= R <= 127, n(p) = |W(p)|.
+ * Weights are fixed-point: wq(p) = rint(H_eps(u(p)) 2^40) as an unsigned 64-bit integer in [0, 2^40], H_eps the two-phase step's
+ * (regularized_heaviside) in the context's "math_mode"; the outside weight is the exact complement 2^40 - wq(p).  wq(p) is a function
+ * of the stored double u(p) alone.
+ * Sums are exact integers, f_k = I_k as an integer:
+ *     A(p) = sum_{q in W(p)} wq(q)      S_k(p) = sum_W wq(q) f_k(q)      T_k(p) = sum_W f_k(q)
+ *     B(p) = n(p) 2^40 - A(p)           S'_k(p) = T_k(p) 2^40 - S_k(p)
+ * all below 2^64 (65025 * 255 * 2^40 < 2^64: a static_assert in the library); n and T_k do not depend on u and are taken once per call.
+ * Means: c1_k(p) = (double)S_k(p) / (double)A(p), c2_k(p) = (double)S'_k(p) / (double)B(p): each conversion rounds to nearest, then
+ * one IEEE division.  There is no guard: A = 0 or B = 0 gives 0 / 0 = NaN, as the other flows give for an empty side.  wq reaches 0
+ * or 2^40 from |u| of about 2^41 eps / pi (7e11 eps) on, so that needs a whole window that far on one side of the front.
+ * Update (Jacobi: every window sum of iteration t is taken from the u that iteration t reads):
+ *     F(p) = sum_k [ -lambda1[k] (f_k - c1_k(p))^2 + lambda2[k] (f_k - c2_k(p))^2 ]
+ *     d = dt (mu kappa(u) - nu + F / C) delta_eps(u), folded exactly as the two-phase combine (kappa (dt mu) + F (dt / C) - dt nu);  u <- u + d
+ * kappa, delta_eps, the border rule, the stop rule (||d||_2 <= cvh_get_stop_condition, tested after the update) and the kept stopping
+ * iteration are as in "Four phases".  Arithmetic is the context's "math_mode": CVH_MATH_STRICT the op-by-op forms, CVH_MATH_FAST (the
+ * default) the wave kernels' forms of H_eps and delta_eps -- the form of H_eps chosen per pixel by the pixel's own stored value.  Both
+ * agree with a numpy restatement of this definition within a bound derived from perturbing H_eps by 2 ulp (tests/localized_util.py).
+ * The local force is small: far from the front both local means tend to the window mean and F is noise.  Start near the object (Otsu,
+ * rect, disk, mask: "Initial level sets") and raise mu (of the order of 100 for 8-bit images with the default lambdas).
+ * cvh_localized_run iterates until max_steps iterations are done (max_steps < 0: no bound) or the stop rule fires.  steps_done, norm
+ * (||d|| of the last executed iteration) and trace may be NULL; row t of the trace is ONE double, iteration t's ||d|| (at most
+ * trace_rows rows, *rows written).  The call settles the context as the getters do and ends with it exactly as cvh_set_levelset of
+ * the new doubles leaves it (a new run begins: counters 0, the two-phase means not yet taken); a two-phase run continued afterwards is
+ * bit for bit what it is after cvh_set_levelset of the fetched doubles.  The host enqueues "sync_every" iterations at a time (three
+ * launches each: row pass, step, finalise) and waits once per chunk for the state block; launches enqueued behind a stop return at
+ * once.  The workspace (state block, partial sums, 1 + C planes of horizontal window sums, C planes of T_k: 8 + 12 C bytes per pixel,
+ * whatever R) and the trace are the context's, allocated on first use and kept.  cvh_last_run_ms afterwards is the device's time from
+ * the first iteration's launch to the end of the last chunk.
+ * Determinism: the window sums are integers -- the same bits in any order and for any neighbour in the plane.  ||d||^2 is summed per
+ * ITEM of a fixed partition (cvh_localized_geometry: *items items of *item_rows rows x *cols columns, a function of h and w alone) and
+ * the items are added in index order by a one-workgroup launch; no atomics.  *strip_rows, the rows one wave marches down, is a whole
+ * number of items chosen from R (at least 2 (2 R + 1) rows: a strip's lead-in of 2 R + 1 workspace rows is at most a third of what it
+ * reads) and has no bearing on any result.  Two runs give the same bits; m + n iterations in one call equal m then n in two calls bit
+ * for bit, in both arithmetic modes.
+ * cvh_localized_means returns, for the CURRENT level set, the host planes c1, c2 (C h w doubles, plane k first), wq and a (h w) and
+ * s (C h w): the bias-field picture.  Any may be NULL, not all.  It only reads: a run continued after it is bit-identical to one
+ * without it.  The planes are staged on the device for the length of the call.
+ * CVH_ERR_ARG: R outside 1 .. 127, "state" = 32, h*w >= 2^28, every output NULL, a trace without rows or with trace_rows < 0.
+ * CVH_ERR_STATE: no image or no level set.  Everything is checked before anything is touched; the message is cvh_last_error's; after
+ * such a refusal the context is as it was and stays usable.
+ * Not here: batches in shared launches, the resident (LDS) flow, FP32 state, a localised energy, four phases with local means,
+ * pyramids or reinitialisation inside the run, Gaussian windows, a global / local blend. */
+int cvh_localized_run(cvh_context *ctx, int radius, int max_steps, int *steps_done, double *norm, double *trace, int trace_rows, int *rows);
+int cvh_localized_means(cvh_context *ctx, int radius, double *c1, double *c2, uint64_t *wq, uint64_t *a, uint64_t *s);
+void cvh_localized_geometry(int h, int w, int radius, int *cols, int *item_rows, int *items, int *strip_rows);   /* pure host arithmetic; 0 rows / items: not a plane or radius the calls take */
+
 /* Library version string, e.g. "chanvese_hip 0.1 (gfx950)". */
 const char *cvh_version(void);
 
