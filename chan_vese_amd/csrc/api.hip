@@ -505,15 +505,23 @@ static void begin_run_host(cvh_context *c)
   c->h_status[0] = 0; c->h_status[1] = 0;
 }
 
-// A new run begins: whatever is in flight is settled, then the host half, then the device half -- the state block's counters and the sum
-// set after the run's own (it may hold the sums of an iteration computed past a stop) are cleared, and the host waits for that.
+// A new run begins, device half, enqueued on s: the state block's counters and the sum set after the run's own (it may hold the sums of an
+// iteration computed past a stop) are cleared.  The ONE place that says what that is for the host (the kernels that write a level set do
+// the same through CvhIoMember's state_zero / chain_zero).
+hipError_t clear_run_device(cvh_context *c, hipStream_t s)
+{
+  static const int zeros[4] = {0, 0, 0, 0};   // steps_done, stopped, ticket, pending
+  const hipError_t e = hipMemcpyAsync(&c->d_state->steps_done, zeros, sizeof(zeros), hipMemcpyHostToDevice, s);
+  if (e != hipSuccess) return e;
+  return hipMemsetAsync(&c->d_chain->v[(c->chain_pb + 1) & 3][0], 0, sizeof(c->d_chain->v[0]), s);
+}
+
+// A new run begins: whatever is in flight is settled, then the host half, then the device half, and the host waits for that.
 int reset_run_impl(cvh_context *c)
 {
   { const int rc = settle(c); if (rc != CVH_OK) return rc; }
   begin_run_host(c);
-  static const int zeros[4] = {0, 0, 0, 0};   // steps_done, stopped, ticket, pending
-  HIPCHK(c, hipMemcpyAsync(&c->d_state->steps_done, zeros, sizeof(zeros), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemsetAsync(&c->d_chain->v[(c->chain_pb + 1) & 3][0], 0, sizeof(c->d_chain->v[0]), c->stream));
+  HIPCHK(c, clear_run_device(c, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return CVH_OK;
 }

@@ -60,6 +60,15 @@ __device__ __forceinline__ double from_left_lane(double v, double edge)
   return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
 }
 
+// value of `v` in lane+1; lane 63 of the wave receives `edge`.
+__device__ __forceinline__ double from_right_lane(double v, double edge)
+{
+  const long long vb = __double_as_longlong(v), eb = __double_as_longlong(edge);
+  const int lo = __builtin_amdgcn_update_dpp((int)eb, (int)vb, 0x130 /*wave_shl:1*/, 0xf, 0xf, false);
+  const int hi = __builtin_amdgcn_update_dpp((int)(eb >> 32), (int)(vb >> 32), 0x130, 0xf, 0xf, false);
+  return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
+}
+
 __device__ __forceinline__ double read_lane(double v, int l)
 {
   const long long vb = __double_as_longlong(v);

@@ -6,7 +6,7 @@
 // level sets), components_run.hip (connected components, and MaskSource: the raw or cleaned mask every mask-derived call starts from),
 // pyramid_run.hip (coarse-to-fine), colour_run.hip (colour spaces), window_run.hip (local statistics and rank planes: the windowed-plane calls), energy_run.hip (the functional's terms), score_run.hip (mask scores),
 // morph_run.hip (mask morphology, mask starts), measure_run.hip (component measures), contour_run.hip (contours), overlap_run.hip
-// (component overlaps), multiphase_run.hip (four phases: a pair of contexts iterated together), localized_run.hip (localised regions), debug_exports.hip (diagnostics).  Kernel
+// (component overlaps), multiphase_run.hip (four phases: a pair of contexts iterated together), localized_run.hip (localised regions), march_run.hip (the driver under those two), debug_exports.hip (diagnostics).  Kernel
 // sources do not include it.
 #pragma once
 #include <limits.h>
@@ -240,6 +240,7 @@ void fill_atan_tables(double *tab);
 // api.hip: one function per event that moves a context's run state (the group of that name in cvh_context)
 int settle(cvh_context *c);
 int reset_run_impl(cvh_context *c);
+hipError_t clear_run_device(cvh_context *c, hipStream_t s);   // the device's half of a new run, enqueued on s
 int levelset_arrived(cvh_context *c, bool device_cleared = false);
 void steps_enqueued(cvh_context *c, int n, int nparts, bool chain, bool resident);
 void sums_taken(cvh_context *c, bool chain);
@@ -315,6 +316,27 @@ int mask_out(cvh_context *const *ctxs, int n, uint8_t *const *d_masks, int inver
 void checkerboard_factors(int h, int w, double *out);   // api.hip: out[0 .. h-1] = sin(pi i/5), out[h .. h+w-1] = sin(pi j/5), host libm
 void levelset_target(const cvh_context *c, CvhIoMember *m);
 int ensure_workspace(cvh_context *c, void **slot, size_t bytes, const char *name, bool mirror = true);
+
+// march_run.hip: what the four-phase and localised flows share -- "iterate the level sets of N contexts on the leader's stream"
+void fill_front_args(const cvh_context *c, CvhFrontArgs *f);
+int state_down(cvh_context *a, const void *d_state, void *out, size_t bytes);   // on a's stream, through its pinned state slots; waits
+// One run of n = 1 or 2 contexts (leader ctxs[0]; names[e] is member e's letter in a message).  The caller has checked the members; then
+//   begin:   refuses a trace's bad arguments, settles max_steps;                 -- the caller makes the members and its workspace ready --
+//   open:    grows the trace table to the rows wanted, opens the call;           -- the caller fills its arguments, enqueues what precedes t = 0 --
+//   iterate: times the run, enqueues sync_every iterations at a time through step(in, out) and reads the state block -- which begins
+//            with a CvhMarchCount -- behind each chunk (its only wait per chunk); then brings every level set into the buffer a new one
+//            lands in (at most ONE copy each, by the parity of steps_done), does the device's half of a new run, copies the trace rows
+//            out, closes the call, waits, and books the level sets as arrived.
+struct MarchRun {
+  cvh_context *const *ctxs; int n; const char *what, *names;
+  int max_steps = 0, trace_cap = 0, nrows = 0;
+  double *trace = nullptr, *d_trace = nullptr;
+  int *rows = nullptr;
+  int begin(int max_steps, double *trace, int trace_rows, int *rows);
+  int open(DeviceTable *table, int row_width);
+  int iterate(const void *d_state, void *st, size_t state_bytes, const std::function<int(const double *const *in, double *const *out)> &step);
+  DeviceTable *table = nullptr; int row_width = 0;   // (open's)
+};
 
 // components_run.hip: the mask of every member that a call starts from -- raw, or cleaned as cvh_get_mask_clean* cleans it -- for the
 // components calls there and for measure_run.hip, overlap_run.hip, contour_run.hip and morph_run.hip.  The first member table of such a

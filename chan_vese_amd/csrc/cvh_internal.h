@@ -417,22 +417,42 @@ hipError_t cvh_launch_morph_passes(const CvhIoMember *cols, const CvhMorphPar *p
                                    hipStream_t s);
 hipError_t cvh_launch_morph_emit(const CvhIoMember *tab, const CvhMorphPar *par, int nmem, unsigned grid, bool from_bytes, bool to_levelset,
                                  hipStream_t s);
+// the marching wave of the four-phase and localised step kernels (march_device.h) and what their host flows share (march_run.hip)
+#define CVH_MARCH_COLS 61       // output columns per wave: lanes 2 .. 62 (lanes 0, 1 and 63 hold the strip's halo columns)
+#define CVH_MARCH_TARGET_WAVES 4096
+#define CVH_MARCH_MIN_ROWS 8
+// rows per item of a plane of h rows and nwc wave-columns: enough item rows for about CVH_MARCH_TARGET_WAVES waves, a multiple of four
+// rows, at least CVH_MARCH_MIN_ROWS.  A function of the shape ALONE -- not of the device -- because the sums' order follows it.
+inline int cvh_march_rows(int h, int nwc)
+{
+  const int target = CVH_MARCH_TARGET_WAVES / nwc > 1 ? CVH_MARCH_TARGET_WAVES / nwc : 1;
+  int rows = (int)(((long long)h + target - 1) / target);
+  rows = (int)(((long long)rows + 3) & ~3ll);
+  return rows > CVH_MARCH_MIN_ROWS ? rows : CVH_MARCH_MIN_ROWS;
+}
+// the head of both state blocks: what the host's chunk loop reads without knowing the model
+struct CvhMarchCount {
+  int steps_done;                  // iterations executed in this call
+  int stopped;                     // sticky: the stop rule fired; every later launch of the call returns at once
+};
+// the FAST forms' constants, from eps / far_terms / the context's atan tables (fill_front_args)
+struct CvhFrontArgs {
+  double eps, inv_eps, dk1;        // FAST: 1 / eps, pi / eps
+  double far_k[5], far_thr;        // FAST: far-field series of H_eps (wave_math.h)
+  const double *atan2_tab;         // FAST: [CVH_ATAN2_N]
+};
 // four phases (multiphase_kernels.hip; include/chanvese_hip.h, "Four phases").  A wave's ITEM is a strip of strip_rows rows x
-// CVH_MP_COLS columns of the plane; the partition -- hence every sum -- is a function of the shape alone (cvh_mp_geometry).  An item's
+// CVH_MARCH_COLS columns of the plane; the partition -- hence every sum -- is a function of the shape alone (cvh_mp_geometry).  An item's
 // row of partial sums holds cvh_mp_nsums(C) doubles:
 //   [0..4) sum w11, w10, w01, w00   [4 + ab C + k] sum I_k w_ab (ab = 0..3 in that order)   [4 + 4C] sum d1^2   [5 + 4C] sum d2^2
 // The pair's state block lives in A's workspace and is written by the one-workgroup finalise launch alone.
-#define CVH_MP_COLS 61          // output columns per wave: lanes 2 .. 62 (lanes 0, 1 and 63 hold the strip's halo columns)
-#define CVH_MP_TARGET_WAVES 4096
-#define CVH_MP_MIN_ROWS 8
 __host__ __device__ constexpr int cvh_mp_nsums(int C) { return 6 + 4 * C; }
 struct CvhMpGeom { int nwc, strip_rows, nstrips, nitems; unsigned grid; };
 CvhMpGeom cvh_mp_geometry(int h, int w);
 struct CvhMpState {
+  CvhMarchCount run;
   double c[4][CVH_MAX_CHANNELS];   // c11, c10, c01, c00: the means of the current pair, read by the next iteration
   double norm[2];                  // ||d1||_2, ||d2||_2 of the last executed iteration
-  int steps_done;                  // iterations executed in this call
-  int stopped;                     // sticky: the stop rule fired; every later launch of the call returns at once
 };
 struct CvhMpArgs {
   const double *in[2];             // phi1, phi2 read
@@ -446,9 +466,7 @@ struct CvhMpArgs {
   CvhMpGeom g;
   double alpha[2], beta[2], gamma[2];          // dt mu, dt / C, -dt nu of A (phi1's equation) and of B (phi2's)
   double lambda1[2][CVH_MAX_CHANNELS], lambda2[2][CVH_MAX_CHANNELS];
-  double eps, inv_eps, dk1;                    // FAST: 1 / eps, pi / eps
-  double far_k[5], far_thr;                    // FAST: far-field series of H_eps (wave_math.h)
-  const double *atan2_tab;                     // FAST: [CVH_ATAN2_N]
+  CvhFrontArgs f;
   double stop[2];                              // what cvh_get_stop_condition returns for A and for B
 };
 hipError_t cvh_launch_mp_sums(const CvhMpArgs &a, int channels, int fast, hipStream_t s);      // the sums of in[] into partials
@@ -458,23 +476,19 @@ hipError_t cvh_launch_mp_finalize(const CvhMpArgs &a, int channels, int is_init,
 hipError_t cvh_launch_mp_labels(const CvhIoMember *tab, int nmem, unsigned grid, hipStream_t s);
 // localised regions (localized_kernels.hip; include/chanvese_hip.h, "Localised regions").  Per iteration a ROW pass (a workgroup per row
 // segment of CVH_WINDOW_SEGMENT columns) writes the horizontal window sums of wq and wq f_k -- 1 + C planes of unsigned 64-bit integers
-// -- into the context's workspace; a STEP kernel's waves march down strips of strip_rows rows x CVH_LOC_COLS columns with the vertical
-// running sums of those planes in registers.  ||d||^2 is stored per ITEM -- item_rows rows x CVH_LOC_COLS columns, a function of the
+// -- into the context's workspace; a STEP kernel's waves march down strips of strip_rows rows x CVH_MARCH_COLS columns with the vertical
+// running sums of those planes in registers.  ||d||^2 is stored per ITEM -- item_rows rows x CVH_MARCH_COLS columns, a function of the
 // shape alone; a strip is a whole number of items, that number a function of the radius -- and added by the one-workgroup finalise.
-#define CVH_LOC_COLS 61          // output columns per wave: lanes 2 .. 62 (lanes 0, 1 and 63 hold the strip's halo columns)
 #define CVH_LOC_RADIUS_MAX 127
 #define CVH_LOC_FRAC_BITS 40     // wq = rint(H_eps 2^40)
-#define CVH_LOC_TARGET_WAVES 4096
-#define CVH_LOC_MIN_ROWS 8
 #define CVH_LOC_LEAD 2           // a strip has at least CVH_LOC_LEAD (2 R + 1) rows: its lead-in is at most a third of the workspace rows it reads
 static_assert((2ull * CVH_LOC_RADIUS_MAX + 1) * (2 * CVH_LOC_RADIUS_MAX + 1) * 255 < (1ull << (64 - CVH_LOC_FRAC_BITS)),
               "every window sum fits in 64 unsigned bits: 65025 * 255 * 2^40 < 2^64");
 struct CvhLocGeom { int nwc, item_rows, nitem_rows, nitems, strip_rows, nstrips, nseg; unsigned grid, row_grid; };
 CvhLocGeom cvh_loc_geometry(int h, int w, int radius);
 struct CvhLocState {
+  CvhMarchCount run;
   double norm;                     // ||d||_2 of the last executed iteration
-  int steps_done;                  // iterations executed in this call
-  int stopped;                     // sticky: the stop rule fired; every later launch of the call returns at once
 };
 struct CvhLocArgs {
   const double *in;                // u read
@@ -490,9 +504,7 @@ struct CvhLocArgs {
   CvhLocGeom g;
   double alpha, beta, gamma;       // dt mu, dt / C, -dt nu
   double lambda1[CVH_MAX_CHANNELS], lambda2[CVH_MAX_CHANNELS];
-  double eps, inv_eps, dk1;        // FAST: 1 / eps, pi / eps
-  double far_k[5], far_thr;        // FAST: far-field series of H_eps (wave_math.h)
-  const double *atan2_tab;         // FAST: [CVH_ATAN2_N]
+  CvhFrontArgs f;
   double stop;                     // what cvh_get_stop_condition returns
   // cvh_localized_means: device planes or null
   unsigned long long *wq_out, *a_out, *s_out;

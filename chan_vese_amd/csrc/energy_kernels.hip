@@ -28,15 +28,6 @@ typedef CVH_GLOBAL const double *gdoubles_in;
 
 constexpr int kSlots = CVH_ENERGY_SLOTS;   // an item's row: length, area, fit_in[3], fit_out[3] (unused channels: zeros)
 
-// value of `v` in lane+1; lane 63 of the wave receives `edge`
-__device__ __forceinline__ double from_right_lane(double v, double edge)
-{
-  const long long vb = __double_as_longlong(v), eb = __double_as_longlong(edge);
-  const int lo = __builtin_amdgcn_update_dpp((int)eb, (int)vb, 0x130 /*wave_shl:1*/, 0xf, 0xf, false);
-  const int hi = __builtin_amdgcn_update_dpp((int)(eb >> 32), (int)(vb >> 32), 0x130, 0xf, 0xf, false);
-  return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-
 struct Pair { double a, b; };
 
 // u(r, ca) and u(r, ca + 1) of a row, both columns clamped to w - 1: one 16-byte load where the row has two columns

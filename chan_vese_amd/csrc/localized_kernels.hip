@@ -7,11 +7,10 @@
 // threads' totals, the four waves' totals); the horizontal window sum of a column is the difference of two prefix entries, so the work
 // per pixel does not grow with R.  The sums are unsigned 64-bit integers: a pixel that lies in two segments' spans has the same wq in
 // both (the form of H_eps is chosen per PIXEL by its own stored value), and every sum is the same bits in any order.
-// STEP kernel, in the manner of multiphase_kernels.hip: a WAVE owns a strip of g.strip_rows rows x CVH_LOC_COLS (61) columns and
-// marches down its rows, lane l on column 61 wc - 2 + l.  The vertical running sums of the 1 + C workspace planes live in registers:
-// the strip's start adds the up to 2 R + 1 rows of its first window, every later row adds the row entering the window and subtracts
-// the row leaving it -- exact, they are integers.  Beside them u(r-1), u(r), u(r+1) for the curvature (its row footprint by DPP lane
-// moves), the bytes of the image and T_k.  The loads of row r + 1 are issued before row r is computed.  Per pixel: A, S_k -> B, S'_k
+// STEP kernel: march_device.h's marching wave down a strip of g.strip_rows rows.  The vertical running sums of the 1 + C workspace
+// planes live in registers: the strip's start adds the up to 2 R + 1 rows of its first window, every later row adds the row entering
+// the window and subtracts the row leaving it -- exact, they are integers.  Beside them u(r-1), u(r), u(r+1) for the curvature, the
+// bytes of the image and T_k.  The loads of row r + 1 are issued before row r is computed.  Per pixel: A, S_k -> B, S'_k
 // -> the 2 C means (one IEEE division each) -> F -> d; the other buffer of the pair is written, d^2 is added per lane, and at every
 // item boundary (g.item_rows rows: a function of the shape alone) wave_sum's fixed tree adds the lanes and lane 0 stores the item's sum.
 // The same kernel without the update writes the means and sums of the current level set (cvh_localized_means) or, behind a row pass
@@ -22,9 +21,8 @@
 // run and never read the state block: a stop that an earlier run left there does not concern them.
 #include <algorithm>
 
-#include "csv_device.h"
 #include "io_device.h"
-#include "wave_math.h"
+#include "march_device.h"
 
 using namespace cvh_dev;
 
@@ -44,18 +42,10 @@ constexpr unsigned long long kOne = 1ull << CVH_LOC_FRAC_BITS;
 static_assert(kPer * CVH_BLOCK >= kSpanMax, "the workgroup covers the longest span");
 static_assert((1 + CVH_MAX_CHANNELS) * (kSpanMax + 1) * 8 + (CVH_ATAN2_N + 1) * 8 + 256 <= 64 * 1024, "the row pass's LDS");
 
-// value of `v` in lane+1; lane 63 of the wave receives `edge`
-__device__ __forceinline__ double from_right_lane(double v, double edge)
-{
-  const long long vb = __double_as_longlong(v), eb = __double_as_longlong(edge);
-  const int lo = __builtin_amdgcn_update_dpp((int)eb, (int)vb, 0x130 /*wave_shl:1*/, 0xf, 0xf, false);
-  const int hi = __builtin_amdgcn_update_dpp((int)(eb >> 32), (int)(vb >> 32), 0x130, 0xf, 0xf, false);
-  return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-
 // wq of a pixel: a function of its stored double alone.  FAST: wave_math.h's far-field series from the threshold on, its table form below
+// (per PIXEL, where the four-phase kernel votes per wave row: a pixel in two segments' spans must give the same wq in both)
 template <bool FAST>
-__device__ __forceinline__ unsigned long long weight_of(double x, const CvhLocArgs &a, const FarCoef &fc, const double *satan)
+__device__ __forceinline__ unsigned long long weight_of(double x, const CvhFrontArgs &a, const FarCoef &fc, const double *satan)
 {
   double H;
   if (!FAST) H = heaviside_strict(x, a.eps);
@@ -73,18 +63,15 @@ __global__ __launch_bounds__(CVH_BLOCK) void loc_row_kernel(const CvhLocArgs a)
   __shared__ unsigned long long pre[NQ][kSpanMax + 1];   // pre[q][i]: the sum of the span's first i entries
   __shared__ unsigned long long wtot[NQ][CVH_BLOCK / 64];
   __shared__ double satan[MODE == 1 ? CVH_ATAN2_N + 1 : 1];
-  if (IN_RUN && a.st->stopped) return;   // (uniform: before the barriers)
-  if (MODE == 1) {
-    for (int q = threadIdx.x; q < CVH_ATAN2_N; q += CVH_BLOCK) satan[q] = a.atan2_tab[q];
-    __syncthreads();
-  }
+  if (IN_RUN && a.st->run.stopped) return;   // (uniform: before the barriers)
+  if (MODE == 1) stage_atan2(satan, a.f);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int h = a.h, w = a.w, R = a.radius;
   const int r = (int)(blockIdx.x / (unsigned)a.g.nseg), seg = (int)(blockIdx.x % (unsigned)a.g.nseg);
   if (r >= h) return;
   const int c0 = seg * kSeg, cend = min(c0 + kSeg, w);
   const int first = max(c0 - R, 0), last = min(cend - 1 + R, w - 1), len = last - first + 1;   // len <= kSpanMax
-  const FarCoef fc = {a.far_k[0], a.far_k[1], a.far_k[2], a.far_k[3], a.far_k[4], a.far_thr};
+  const FarCoef fc = far_coef_of(a.f);
   const size_t row = (size_t)r * w, n = (size_t)h * w;
   const gdoubles_in in = (gdoubles_in)a.in;
   const gbytes_in plane[CVH_MAX_CHANNELS] = {(gbytes_in)a.img[0], (gbytes_in)a.img[1], (gbytes_in)a.img[2]};
@@ -97,7 +84,7 @@ __global__ __launch_bounds__(CVH_BLOCK) void loc_row_kernel(const CvhLocArgs a)
     const int col = first + (ok ? i : 0);   // (inside the row)
     unsigned long long wq = 1;
     if (MODE != 2) {
-      wq = weight_of<MODE == 1>(in[row + col], a, fc, satan);
+      wq = weight_of<MODE == 1>(in[row + col], a.f, fc, satan);
       if (a.wq_out && ok && col >= c0 && col < cend) ((gu64_out)a.wq_out)[row + col] = wq;
     }
     if (!ok) wq = 0;
@@ -146,19 +133,16 @@ __global__ __launch_bounds__(CVH_BLOCK) void loc_wave_kernel(const CvhLocArgs a)
 {
   constexpr int NQ = 1 + C;
   constexpr bool STEP = KIND == CVH_LOC_STEP, TSUM = KIND == CVH_LOC_TSUM;
-  if (STEP && a.st->stopped) return;
-  const int lane = threadIdx.x & 63;
+  if (STEP && a.st->run.stopped) return;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const long long witem = (long long)blockIdx.x * (CVH_BLOCK / 64) + wave;
   if (witem >= (long long)a.g.nstrips * a.g.nwc) return;
   const int h = a.h, w = a.w, R = a.radius;
-  const int strip = (int)(witem / a.g.nwc), wc = (int)(witem - (long long)strip * a.g.nwc);
-  const int s0 = (int)min((long long)strip * a.g.strip_rows, (long long)h), s1 = (int)min((long long)s0 + a.g.strip_rows, (long long)h);
-  const int col = CVH_LOC_COLS * wc - 2 + lane;
-  const int colc = clampi(col, 0, w - 1);
-  const bool lane_valid = lane >= 2 && lane <= 62 && col < w;
+  const MarchLane ml = march_lane(witem, a.g.nwc, a.g.strip_rows, h, w);
+  const int wc = ml.wc, s0 = ml.s0, s1 = ml.s1, col = ml.col, colc = ml.colc;
+  const bool lane_valid = ml.valid;
   const size_t n = (size_t)h * w;
-  const double eps = a.eps, eps2 = eps * eps;
+  const double eps = a.f.eps, eps2 = eps * eps;
   const gdoubles_in in = (gdoubles_in)a.in;
   const gdoubles_out out = (gdoubles_out)a.out;
   const gu64_in hw = (gu64_in)a.hw;
@@ -178,7 +162,8 @@ __global__ __launch_bounds__(CVH_BLOCK) void loc_wave_kernel(const CvhLocArgs a)
     for (int q = 0; q < NQ; ++q) V[q] += hw[(size_t)q * n + (size_t)j * w + colc];
   }
 
-  // what row r needs beside the running sums; every index is clamped into the plane, so no load leaves the buffers
+  // what row r needs beside the running sums; every index is clamped into the plane, so no load leaves the buffers.  (ONE row ahead,
+  // where the four-phase kernel asks for four: a row here is also the 2 (1 + C) sums entering and leaving the window)
   struct RowData { double up; unsigned f[C], T[C]; unsigned long long E[NQ], L[NQ]; };
   auto request = [&](int r, RowData &d) {
     const size_t o = (size_t)clampi(r, 0, h - 1) * w + colc;
@@ -198,18 +183,13 @@ __global__ __launch_bounds__(CVH_BLOCK) void loc_wave_kernel(const CvhLocArgs a)
   };
 
   double um = 0.0, u0 = 0.0, nyp = 0.0, acc = 0.0;
-  const double fx = (col <= 0) ? 0.0 : 1.0;   // kappa_x(., 0) = 0
+  const double fx = (col <= 0) ? 0.0 : 1.0;
   RowData cur;
   if (s0 < s1) request(s0, cur);
   if (STEP && s0 < s1) {
     auto at = [&](int r) -> double { return in[(size_t)clampi(r, 0, h - 1) * w + colc]; };
     um = at(s0 - 1); u0 = at(s0);
-    // ny of row s0 - 1; on the plane's first row that row's own ny, by the very expression the row uses: ny - ny_prev is an exact zero
-    if (s0 == 0) nyp = FAST ? normalised4(cur.up, um, u0 + u0) : normalised<false>(cur.up - u0, central(um, cur.up));
-    else {
-      const double um2 = at(s0 - 2);
-      nyp = FAST ? normalised4(u0, um2, um + um) : normalised<false>(u0 - um, central(um2, u0));
-    }
+    nyp = ny_above<FAST>(s0, [&] { return at(s0 - 2); }, um, u0, cur.up);
   }
 
   for (int r = s0; r < s1; ++r) {
@@ -242,30 +222,13 @@ __global__ __launch_bounds__(CVH_BLOCK) void loc_wave_kernel(const CvhLocArgs a)
       if (!STEP && lane_valid && a.a_out) ((gu64_out)a.a_out)[o] = A;
       if (STEP) {
         const double up = cur.up;
-        const double uw = from_left_lane(u0, u0), ue = from_right_lane(u0, u0);
-        double kappa, ny, d;
-        if (FAST) {
-          const double u2 = u0 + u0;
-          const double nx = normalised4(ue, uw, u2);
-          ny = normalised4(up, um, u2);
-          kappa = __builtin_fma(nx - from_left_lane(nx, 0.0), fx, ny - nyp);
-          d = __builtin_fma(kappa, a.alpha, __builtin_fma(F, a.beta, a.gamma)) * rcp_refined(inv_delta_eps(u0, eps2, a.dk1));
-        } else {
-          const double nx = normalised<false>(ue - u0, central(uw, ue));
-          ny = normalised<false>(up - u0, central(um, up));
-          const double nxl = from_left_lane(nx, 0.0);
-          const double kx = (col <= 0) ? 0.0 : nx - nxl;
-          kappa = kx + (ny - nyp);
-          const double ud = kappa * a.alpha + F * a.beta + a.gamma;   // the two-phase combine, folded
-          d = ud * (eps / (kPi * (eps2 + u0 * u0)));
-        }
-        nyp = ny;
+        const double kappa = march_curvature<FAST>(um, u0, up, nyp, fx, col);
+        const double d = march_update<FAST>(kappa, F, u0, a.alpha, a.beta, a.gamma, eps, eps2, a.f.dk1);
         if (lane_valid) out[o] = u0 + d;
         acc += d * d;
         um = u0; u0 = up;
         if ((r + 1) % a.g.item_rows == 0 || !more) {   // (wave-uniform) the item ends: strips begin on item boundaries
-          const double t = wave_sum(lane_valid ? acc : 0.0);   // halo lanes and lanes behind the last column add nothing
-          if (lane == 0) a.partials[(size_t)(r / a.g.item_rows) * a.g.nwc + wc] = t;
+          march_store_sum(ml, acc, a.partials + (size_t)(r / a.g.item_rows) * a.g.nwc + wc);
           acc = 0.0;
         }
       }
@@ -281,17 +244,17 @@ __global__ __launch_bounds__(CVH_BLOCK) void loc_finalize_kernel(const CvhLocArg
 {
   __shared__ double sred[4];
   CvhLocState *st = a.st;
-  if (st->stopped) return;
+  if (st->run.stopped) return;
   double acc[1] = {0.0};
   for (int it = threadIdx.x; it < a.g.nitems; it += CVH_BLOCK) acc[0] += a.partials[it];
   const double total = block_reduce<1>(acc, sred);
   if (threadIdx.x != 0) return;
   const double nrm = sqrt(total);
-  const int t = st->steps_done;   // index of the iteration just executed
+  const int t = st->run.steps_done;   // index of the iteration just executed
   if (a.trace && t < a.trace_cap) a.trace[t] = nrm;
   st->norm = nrm;
-  st->steps_done = t + 1;
-  if (nrm <= a.stop) st->stopped = 1;   // after the update
+  st->run.steps_done = t + 1;
+  if (nrm <= a.stop) st->run.stopped = 1;   // after the update
 }
 
 template <int C>
@@ -320,17 +283,13 @@ hipError_t launch_rows(const CvhLocArgs &a, int fast, int pass, hipStream_t s)
 
 }  // namespace
 
-// Items: rows per item and their number follow the shape ALONE (the order of the norm's sum follows them): enough item rows for about
-// CVH_LOC_TARGET_WAVES waves, a multiple of four rows, at least CVH_LOC_MIN_ROWS.  A strip -- what one wave marches down -- is the
-// smallest whole number of items with at least CVH_LOC_LEAD (2 R + 1) rows.
+// Items: cvh_march_rows rows each (the order of the norm's sum follows them).  A strip -- what one wave marches down -- is the smallest
+// whole number of items with at least CVH_LOC_LEAD (2 R + 1) rows.
 CvhLocGeom cvh_loc_geometry(int h, int w, int radius)
 {
   CvhLocGeom g;
-  g.nwc = (w + CVH_LOC_COLS - 1) / CVH_LOC_COLS;
-  const int target = std::max(CVH_LOC_TARGET_WAVES / g.nwc, 1);
-  int rows = (int)(((long long)h + target - 1) / target);
-  rows = (int)(((long long)rows + 3) & ~3ll);
-  g.item_rows = std::max(rows, CVH_LOC_MIN_ROWS);
+  g.nwc = (w + CVH_MARCH_COLS - 1) / CVH_MARCH_COLS;
+  g.item_rows = cvh_march_rows(h, g.nwc);
   g.nitem_rows = (h + g.item_rows - 1) / g.item_rows;
   g.nitems = g.nitem_rows * g.nwc;
   const int lead = CVH_LOC_LEAD * (2 * radius + 1);

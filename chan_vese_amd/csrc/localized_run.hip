@@ -1,11 +1,7 @@
 // localized_run.hip — host side of the localised-regions calls (include/chanvese_hip.h, "Localised regions"; kernels in
-// localized_kernels.hip).  A call checks everything, settles the context as the getters do, takes the planes T_k once, and --
-// cvh_localized_run -- ends with the context exactly as a device-side start leaves it (the level set in the buffer cvh_set_levelset
-// writes, the device's half of a new run done on the stream, then levelset_arrived), as cvh_multiphase_run does for each of its two.
-// Data flow of a run: iteration t reads d_u[(current + t) & 1] and writes the other buffer of the pair; three launches per iteration
-// on the context's stream -- row pass, step, finalise.  The host enqueues "sync_every" iterations at a time and reads the state block
-// behind each chunk: its only wait per chunk.  Launches enqueued behind a stop return at once, so the level set stays as the stopping
-// iteration left it and the host picks the buffer by the parity of steps_done.
+// localized_kernels.hip).  A call checks everything, settles the context as the getters do and takes the planes T_k once;
+// cvh_localized_run then hands the iterations to march_run.hip's driver: three launches per iteration on the context's stream -- row
+// pass, step, finalise.
 // The workspace, kept by the context: [state block][the items' partial sums][1 + C planes of 8 bytes: the horizontal window sums][C
 // planes of 4 bytes: T_k] -- 8 + 12 C bytes per pixel, whatever the radius.
 #include "cvh_host.h"
@@ -65,12 +61,7 @@ void loc_args(const cvh_context *c, int radius, const CvhLocGeom &g, CvhLocArgs 
   m->gamma = -c->p.nu * c->p.dt;
   for (int k = 0; k < c->C; ++k) { m->lambda1[k] = c->p.lambda1[k]; m->lambda2[k] = c->p.lambda2[k]; }
   m->stop = c->p.tol * c->stop_norm;
-  const double pi = 3.14159265358979323846;
-  m->eps = c->p.eps;
-  m->inv_eps = 1.0 / c->p.eps;
-  m->dk1 = pi / c->p.eps;
-  far_coef(c->p.eps, c->far_terms, m->far_k, &m->far_thr);
-  m->atan2_tab = c->d_atan + 2 * CVH_ATAN_N;
+  fill_front_args(c, &m->f);
 }
 
 // T_k, once per call: a row pass with wq = 1 and the wave kernel's vertical sums of it
@@ -81,79 +72,41 @@ int plane_sums(cvh_context *c, const CvhLocArgs &m)
   return CVH_OK;
 }
 
-int state_down(cvh_context *c, CvhLocState *out)
-{
-  HIPCHK(c, hipMemcpyAsync(c->h_state, c->d_localized, sizeof(CvhLocState), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  memcpy(out, c->h_state, sizeof(CvhLocState));
-  return CVH_OK;
-}
-
 int localized_run(cvh_context *c, int radius, int max_steps, int *steps_done, double *norm, double *trace, int trace_rows, int *rows,
                   const char *what)
 {
   cvh_context *ctxs[1] = {c};
   int rc = loc_check(c, radius, what);
   if (rc != CVH_OK) return rc;
-  if (trace && (trace_rows < 0 || !rows))
-    return batch_fail(ctxs, 1, CVH_ERR_ARG, "%s: a trace needs trace_rows >= 0 and rows, got trace_rows = %d, rows = %p", what, trace_rows, (void *)rows);
-  if (max_steps < 0) max_steps = INT_MAX;   // (as cvh_run: until the stop rule fires)
+  MarchRun run{ctxs, 1, what, ""};
+  rc = run.begin(max_steps, trace, trace_rows, rows);
+  if (rc != CVH_OK) return rc;
   const CvhLocGeom g = cvh_loc_geometry(c->h, c->w, radius);
   rc = loc_ready(c, what, g);
   if (rc != CVH_OK) return rc;
   rc = prepare_host(c);   // the stop norm (taken again where the planes changed on the device)
   if (rc != CVH_OK) return batch_fail(ctxs, 1, rc, "%s: %s", what, c->err);
   const int C = c->C, fast = use_fast(c);
-  const int trace_cap = trace ? std::min(trace_rows, max_steps) : 0;
-  if (trace_cap > 0) {
-    rc = grow_table(c, &c->loc_trace, (size_t)trace_cap * sizeof(double));
-    if (rc != CVH_OK) return batch_fail(ctxs, 1, rc, "%s: %s", what, c->err);
-  }
+  rc = run.open(&c->loc_trace, 1);
+  if (rc != CVH_OK) return rc;
   CvhLocArgs m;
   loc_args(c, radius, g, &m);
-  if (trace_cap > 0) { m.trace = (double *)c->loc_trace.d; m.trace_cap = trace_cap; }
-  // (open_call / close_call only order streams -- the context's behind the legacy stream, and back -- and hold nothing: a HIP error
-  // between them leaves no call open; what such an error does leave is the header's "partly iterated" level set)
-  rc = open_call(ctxs, 1, nullptr);
-  if (rc != CVH_OK) return rc;
+  m.trace = run.d_trace; m.trace_cap = run.trace_cap;
+  // no launch in front of the first iteration writes the state block (the four-phase flow's initial finalise does): zeroed here
   HIPCHK(c, hipMemsetAsync(c->d_localized, 0, kLocStateBytes, c->stream));
   rc = plane_sums(c, m);
   if (rc != CVH_OK) return rc;
-  const int cur = current_buffer(c);
   CvhLocState st;
-  memset(&st, 0, sizeof(st));
-  HIPCHK(c, hipEventRecord(c->ev0, c->stream));   // (ev0 / ev1 are free: settle closed any timed run)
-  int enq = 0;
-  while (enq < max_steps && !st.stopped) {
-    const int chunk = std::min(c->sync_every, max_steps - enq);
-    for (int t = enq; t < enq + chunk; ++t) {
-      m.in = c->d_u[(cur + t) & 1]; m.out = c->d_u[(cur + t + 1) & 1];
-      HIPCHK(c, cvh_launch_loc_rows(m, C, fast, CVH_LOC_STEP, c->stream));
-      HIPCHK(c, cvh_launch_loc_wave(m, C, fast, CVH_LOC_STEP, c->stream));
-      HIPCHK(c, cvh_launch_loc_finalize(m, c->stream));
-    }
-    enq += chunk;
-    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-    rc = state_down(c, &st);   // the ONE host wait of the chunk
-    if (rc != CVH_OK) return rc;
-  }
-  if (enq > 0) HIPCHK(c, hipEventElapsedTime(&c->last_run_ms, c->ev0, c->ev1));
-  // the level set of iteration steps_done - 1 into the buffer a new level set lands in, and the device's half of the run it begins
-  static const int zeros[4] = {0, 0, 0, 0};   // steps_done, stopped, ticket, pending
-  const int from = (cur + st.steps_done) & 1, to = c->chain_pb & 1;
-  if (from != to) HIPCHK(c, hipMemcpyAsync(c->d_u[to], c->d_u[from], c->n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(&c->d_state->steps_done, zeros, sizeof(zeros), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemsetAsync(&c->d_chain->v[(c->chain_pb + 1) & 3][0], 0, sizeof(c->d_chain->v[0]), c->stream));
-  const int nrows = std::min(st.steps_done, trace_cap);
-  if (nrows > 0) HIPCHK(c, hipMemcpyAsync(trace, c->loc_trace.d, (size_t)nrows * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  rc = close_call(ctxs, 1, nullptr, false);
+  rc = run.iterate(c->d_localized, &st, sizeof(st), [&](const double *const *in, double *const *out) -> int {
+    m.in = in[0]; m.out = out[0];
+    HIPCHK(c, cvh_launch_loc_rows(m, C, fast, CVH_LOC_STEP, c->stream));
+    HIPCHK(c, cvh_launch_loc_wave(m, C, fast, CVH_LOC_STEP, c->stream));
+    HIPCHK(c, cvh_launch_loc_finalize(m, c->stream));
+    return CVH_OK;
+  });
   if (rc != CVH_OK) return rc;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  rc = levelset_arrived(c, true);
-  if (rc != CVH_OK) return batch_fail(ctxs, 1, rc, "%s: %s", what, c->err);
-  if (steps_done) *steps_done = st.steps_done;
+  if (steps_done) *steps_done = st.run.steps_done;
   if (norm) *norm = st.norm;
-  if (rows) *rows = nrows;
   return CVH_OK;
 }
 
@@ -220,7 +173,7 @@ extern "C" void cvh_localized_geometry(int h, int w, int radius, int *cols, int 
   CvhLocGeom g;
   memset(&g, 0, sizeof(g));
   if (h > 0 && w > 0 && (long long)h * w < (1ll << 28) && radius >= 1 && radius <= CVH_LOC_RADIUS_MAX) g = cvh_loc_geometry(h, w, radius);
-  if (cols) *cols = CVH_LOC_COLS;
+  if (cols) *cols = CVH_MARCH_COLS;
   if (item_rows) *item_rows = g.item_rows;
   if (items) *items = g.nitems;
   if (strip_rows) *strip_rows = g.strip_rows;

@@ -1,25 +1,17 @@
 // multiphase_kernels.hip — four-phase (Vese-Chan) iteration of TWO level sets (gfx950, wave64; include/chanvese_hip.h, "Four phases").
 //
-// Step kernel, in the manner of csv_wave_kernel.hip: a WAVE owns an item -- a strip of g.strip_rows rows x CVH_MP_COLS (61) columns --
-// and marches down its rows.  Lane l holds column 61 wc - 2 + l of BOTH level sets: u(r-1), u(r), u(r+1) of each live in registers,
-// the rows of the next group of four are requested while the current group is computed (every row index clamped into the plane:
-// replicate border, and no load leaves the buffers).  The four-wide footprint of the curvature along a row -- columns c-2 .. c+1 --
-// comes from lane moves alone: u(c-1) and u(c+1) by DPP wave shifts, the left neighbour's normalised x-gradient by another; so lanes
-// 0, 1 and 63 only carry halo columns and lanes 2 .. 62 produce pixels.  A double of phi1 / phi2 is read once per iteration apart
-// from a strip's three halo columns and three halo rows, and written once: 32 + C bytes per pixel.
+// Step kernel: march_device.h's marching wave over BOTH level sets.  An item is a strip of g.strip_rows rows x CVH_MARCH_COLS columns;
+// the rows of the next group of four are requested while the current group is computed.  A double of phi1 / phi2 is read once per
+// iteration apart from a strip's three halo columns and three halo rows, and written once: 32 + C bytes per pixel.
 // Per pixel: H_eps of the OLD pair (the other level set's blends the region term), the two updates, H_eps of the NEW pair (the sums
-// the next iteration's means are taken from).  FAST: wave_math.h's far-field series / table form of H_eps chosen per wave and row,
-// rcp_refined for delta_eps, normalised4; STRICT: the op-by-op forms of the reference (libm-grade atan, IEEE divide and sqrt).
+// the next iteration's means are taken from).  FAST: the far-field series / table form of H_eps chosen per wave and row.
 // Sums: a lane adds its pixels down the strip, wave_sum's fixed tree adds the lanes, lane 0 stores the ITEM's row.  The partition into
 // items is a function of the shape alone (cvh_mp_geometry), the finalise kernel -- ONE workgroup -- adds the rows in an order the
 // shape alone fixes: no atomics, nothing depends on the grid, on timing or on the order workgroups arrive in.
 // Finalise: next means, the two norms, the trace row, the iteration count and the stop flag, into the pair's state block.  Every
 // workgroup of every launch reads the flag first and returns where it is set: launches enqueued behind a stop write nothing.
-#include <algorithm>
-
-#include "csv_device.h"
 #include "io_device.h"
-#include "wave_math.h"
+#include "march_device.h"
 
 using namespace cvh_dev;
 
@@ -30,31 +22,16 @@ typedef CVH_GLOBAL double *gdoubles_out;
 
 constexpr int R = 4;   // rows per group = rows in flight per level set
 
-// value of `v` in lane+1; lane 63 of the wave receives `edge`
-__device__ __forceinline__ double from_right_lane(double v, double edge)
-{
-  const long long vb = __double_as_longlong(v), eb = __double_as_longlong(edge);
-  const int lo = __builtin_amdgcn_update_dpp((int)eb, (int)vb, 0x130 /*wave_shl:1*/, 0xf, 0xf, false);
-  const int hi = __builtin_amdgcn_update_dpp((int)(eb >> 32), (int)(vb >> 32), 0x130, 0xf, 0xf, false);
-  return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-
 // H_eps(x).  FAST: 1/2 + the centred value of wave_math.h, the far-field series where every pixel of the wave's row is in the far field,
 // else the table form.  Only lanes that own a pixel vote (`owner`): the choice is then a function of the row's stored values alone,
 // the same in the step kernel (which holds phi + d in registers) and in a later sums pass over what it stored.
+// (Per wave ROW, by ballot, where the localised kernels choose per pixel: here no sum has to be the same bits in two workgroups.)
 template <bool FAST>
-__device__ __forceinline__ double heaviside(double x, bool owner, const CvhMpArgs &a, const FarCoef &fc, const double *satan)
+__device__ __forceinline__ double heaviside(double x, bool owner, const CvhFrontArgs &a, const FarCoef &fc, const double *satan)
 {
   if (!FAST) return heaviside_strict(x, a.eps);
   if (__builtin_amdgcn_ballot_w64(owner && fabs(x) < fc.thr) == 0ull) return 0.5 + heaviside_centred_far(x, fc);
   return 0.5 + heaviside_centred_near(x, a.inv_eps, satan);
-}
-
-// ny of row r - 1 from u(r - 2), u(r - 1), u(r)
-template <bool FAST>
-__device__ __forceinline__ double ny_of(double um2, double um, double u0)
-{
-  return FAST ? normalised4(u0, um2, um + um) : normalised<false>(u0 - um, central(um2, u0));
 }
 
 // the pixel's contribution to the sums of a pair with Heavisides h1, h2
@@ -77,23 +54,17 @@ __global__ __launch_bounds__(CVH_BLOCK) void mp_wave_kernel(const CvhMpArgs a)
 {
   constexpr int NS = cvh_mp_nsums(C);
   __shared__ double satan[FAST ? CVH_ATAN2_N + 1 : 1];
-  if (STEP && a.st->stopped) return;   // (uniform: before the barrier)
-  if (FAST) {
-    for (int q = threadIdx.x; q < CVH_ATAN2_N; q += CVH_BLOCK) satan[q] = a.atan2_tab[q];
-    __syncthreads();
-  }
-  const int lane = threadIdx.x & 63;
+  if (STEP && a.st->run.stopped) return;   // (uniform: before the barrier)
+  if (FAST) stage_atan2(satan, a.f);
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const long long item = (long long)blockIdx.x * (CVH_BLOCK / 64) + wave;
   if (item >= a.g.nitems) return;
   const int h = a.h, w = a.w;
-  const int strip = (int)(item / a.g.nwc), wc = (int)(item - (long long)strip * a.g.nwc);
-  const int s0 = strip * a.g.strip_rows, s1 = min(s0 + a.g.strip_rows, h);
-  const int col = CVH_MP_COLS * wc - 2 + lane;
-  const int colc = clampi(col, 0, w - 1);
-  const bool lane_valid = lane >= 2 && lane <= 62 && col < w;
-  const FarCoef fc = {a.far_k[0], a.far_k[1], a.far_k[2], a.far_k[3], a.far_k[4], a.far_thr};
-  const double eps = a.eps, eps2 = eps * eps;
+  const MarchLane ml = march_lane(item, a.g.nwc, a.g.strip_rows, h, w);
+  const int s0 = ml.s0, s1 = ml.s1, col = ml.col, colc = ml.colc;
+  const bool lane_valid = ml.valid;
+  const FarCoef fc = far_coef_of(a.f);
+  const double eps = a.f.eps, eps2 = eps * eps;
   const gdoubles_in in1 = (gdoubles_in)a.in[0], in2 = (gdoubles_in)a.in[1];
   const gdoubles_out out1 = (gdoubles_out)a.out[0], out2 = (gdoubles_out)a.out[1];
   const gbytes_in plane[CVH_MAX_CHANNELS] = {(gbytes_in)a.img[0], (gbytes_in)a.img[1], (gbytes_in)a.img[2]};
@@ -115,7 +86,8 @@ __global__ __launch_bounds__(CVH_BLOCK) void mp_wave_kernel(const CvhMpArgs a)
   for (int s = 0; s < NS; ++s) acc[s] = 0.0;
 
   auto at = [&](gdoubles_in u, int r) -> double { return u[(size_t)clampi(r, 0, h - 1) * w + colc]; };
-  // rows g0 + 1 .. g0 + R of both level sets and rows g0 .. g0 + R - 1 of the planes
+  // rows g0 + 1 .. g0 + R of both level sets and rows g0 .. g0 + R - 1 of the planes.  (A group of four rows ahead, where the localised
+  // kernel asks for one: a row here is two doubles and C bytes, nothing enters or leaves a window)
   auto request = [&](int g0, double (&t1)[R], double (&t2)[R], int (&ti)[C][R]) {
 #pragma unroll
     for (int j = 0; j < R; ++j) {
@@ -132,38 +104,12 @@ __global__ __launch_bounds__(CVH_BLOCK) void mp_wave_kernel(const CvhMpArgs a)
   int im[C][R];
   request(s0, n1, n2, im);
   if (STEP) {
-    // ny of row s0 - 1.  kappa_y(0, .) = 0 (src/main.cpp:372): on the plane's first row it is that row's own ny, by the very expression
-    // the row uses, so that ny - ny_prev is an exact zero there
-    if (s0 == 0) { nyp1 = ny_of<FAST>(um1, u01, n1[0]); nyp2 = ny_of<FAST>(um2, u02, n2[0]); }
-    else { nyp1 = ny_of<FAST>(at(in1, s0 - 2), um1, u01); nyp2 = ny_of<FAST>(at(in2, s0 - 2), um2, u02); }
+    nyp1 = ny_above<FAST>(s0, [&] { return at(in1, s0 - 2); }, um1, u01, n1[0]);
+    nyp2 = ny_above<FAST>(s0, [&] { return at(in2, s0 - 2); }, um2, u02, n2[0]);
   }
-  const double fx = (col <= 0) ? 0.0 : 1.0;   // kappa_x(., 0) = 0 (:371)
-
-  // curvature of one level set at the lane's pixel of this row; ny_prev moves on
-  auto curvature = [&](double um, double u0, double up, double &ny_prev) -> double {
-    const double uw = from_left_lane(u0, u0), ue = from_right_lane(u0, u0);
-    double nx, ny, kappa;
-    if (FAST) {
-      const double u2 = u0 + u0;
-      nx = normalised4(ue, uw, u2);
-      ny = normalised4(up, um, u2);
-      kappa = __builtin_fma(nx - from_left_lane(nx, 0.0), fx, ny - ny_prev);
-    } else {
-      nx = normalised<false>(ue - u0, central(uw, ue));   // :365-366
-      ny = normalised<false>(up - u0, central(um, up));   // :367-368
-      const double nxl = from_left_lane(nx, 0.0);
-      const double kx = (col <= 0) ? 0.0 : nx - nxl;      // :371
-      kappa = kx + (ny - ny_prev);                        // :372-373
-    }
-    ny_prev = ny;
-    return kappa;
-  };
-  // dt (mu kappa - nu + F / C) delta_eps(u0), folded as the one-level-set step folds it (:985, :992)
-  auto update = [&](double kappa, double F, double u0, int e) -> double {
-    if (FAST) return __builtin_fma(kappa, a.alpha[e], __builtin_fma(F, a.beta[e], a.gamma[e])) * rcp_refined(inv_delta_eps(u0, eps2, a.dk1));
-    const double ud = kappa * a.alpha[e] + F * a.beta[e] + a.gamma[e];
-    return ud * (eps / (kPi * (eps2 + u0 * u0)));
-  };
+  const double fx = (col <= 0) ? 0.0 : 1.0;
+  auto curvature = [&](double um, double u0, double up, double &ny_prev) { return march_curvature<FAST>(um, u0, up, ny_prev, fx, col); };
+  auto update = [&](double kappa, double F, double u0, int e) { return march_update<FAST>(kappa, F, u0, a.alpha[e], a.beta[e], a.gamma[e], eps, eps2, a.f.dk1); };
 
   for (int g0 = s0; g0 < s1; g0 += R) {
     double t1[R], t2[R];
@@ -179,7 +125,7 @@ __global__ __launch_bounds__(CVH_BLOCK) void mp_wave_kernel(const CvhMpArgs a)
 #pragma unroll
         for (int k = 0; k < C; ++k) f[k] = (double)im[k][j];
         if (STEP) {
-          const double h1 = heaviside<FAST>(u01, lane_valid, a, fc, satan), h2 = heaviside<FAST>(u02, lane_valid, a, fc, satan);
+          const double h1 = heaviside<FAST>(u01, lane_valid, a.f, fc, satan), h2 = heaviside<FAST>(u02, lane_valid, a.f, fc, satan);
           const double k1 = curvature(um1, u01, up1, nyp1), k2 = curvature(um2, u02, up2, nyp2);
           double F1 = 0.0, F2 = 0.0;
 #pragma unroll
@@ -196,11 +142,11 @@ __global__ __launch_bounds__(CVH_BLOCK) void mp_wave_kernel(const CvhMpArgs a)
             out1[o] = v1;
             out2[o] = v2;
           }
-          add_pixel<C>(acc, heaviside<FAST>(v1, lane_valid, a, fc, satan), heaviside<FAST>(v2, lane_valid, a, fc, satan), f);
+          add_pixel<C>(acc, heaviside<FAST>(v1, lane_valid, a.f, fc, satan), heaviside<FAST>(v2, lane_valid, a.f, fc, satan), f);
           acc[4 + 4 * C] += d1 * d1;
           acc[5 + 4 * C] += d2 * d2;
         } else {
-          add_pixel<C>(acc, heaviside<FAST>(u01, lane_valid, a, fc, satan), heaviside<FAST>(u02, lane_valid, a, fc, satan), f);
+          add_pixel<C>(acc, heaviside<FAST>(u01, lane_valid, a.f, fc, satan), heaviside<FAST>(u02, lane_valid, a.f, fc, satan), f);
         }
         um1 = u01; u01 = up1; um2 = u02; u02 = up2;
       }
@@ -216,10 +162,7 @@ __global__ __launch_bounds__(CVH_BLOCK) void mp_wave_kernel(const CvhMpArgs a)
   }
   double *row = a.partials + (size_t)item * NS;
 #pragma unroll
-  for (int s = 0; s < NS; ++s) {
-    const double t = wave_sum(lane_valid ? acc[s] : 0.0);   // halo lanes and lanes behind the last column add nothing
-    if (lane == 0) row[s] = t;
-  }
+  for (int s = 0; s < NS; ++s) march_store_sum(ml, acc[s], row + s);
 }
 
 // ONE workgroup: thread t adds the items' rows t, t + 256, ... in that order, block_reduce's fixed tree adds the threads; thread 0 writes
@@ -231,7 +174,7 @@ __global__ __launch_bounds__(CVH_BLOCK) void mp_finalize_kernel(const CvhMpArgs 
   __shared__ double sred[4 * NS];
   __shared__ double sfin[NS];
   CvhMpState *st = a.st;
-  if (!is_init && st->stopped) return;
+  if (!is_init && st->run.stopped) return;
   double acc[NS];
 #pragma unroll
   for (int s = 0; s < NS; ++s) acc[s] = 0.0;
@@ -245,7 +188,7 @@ __global__ __launch_bounds__(CVH_BLOCK) void mp_finalize_kernel(const CvhMpArgs 
   if (threadIdx.x != 0) return;
   if (!is_init) {
     const double nrm1 = sqrt(sfin[4 + 4 * C]), nrm2 = sqrt(sfin[5 + 4 * C]);
-    const int t = st->steps_done;   // index of the iteration just executed
+    const int t = st->run.steps_done;   // index of the iteration just executed
     if (a.trace && t < a.trace_cap) {
       double *row = a.trace + (size_t)t * (4 * C + 2);
       for (int ab = 0; ab < 4; ++ab)
@@ -255,12 +198,12 @@ __global__ __launch_bounds__(CVH_BLOCK) void mp_finalize_kernel(const CvhMpArgs 
     }
     st->norm[0] = nrm1;
     st->norm[1] = nrm2;
-    st->steps_done = t + 1;
-    if (nrm1 <= a.stop[0] && nrm2 <= a.stop[1]) st->stopped = 1;   // after the update, as src/main.cpp:1000
+    st->run.steps_done = t + 1;
+    if (nrm1 <= a.stop[0] && nrm2 <= a.stop[1]) st->run.stopped = 1;   // after the update, as src/main.cpp:1000
   } else {
     st->norm[0] = st->norm[1] = 0.0;
-    st->steps_done = 0;
-    st->stopped = 0;
+    st->run.steps_done = 0;
+    st->run.stopped = 0;
   }
   for (int ab = 0; ab < 4; ++ab)
     for (int k = 0; k < C; ++k) st->c[ab][k] = sfin[4 + ab * C + k] / sfin[ab];
@@ -306,16 +249,12 @@ hipError_t launch_wave(const CvhMpArgs &a, int channels, int fast, hipStream_t s
 
 }  // namespace
 
-// The partition of a plane into items: enough strips for about CVH_MP_TARGET_WAVES waves, of a multiple of four rows and at least
-// CVH_MP_MIN_ROWS.  A function of the shape ALONE -- not of the device -- because the sums' order follows it.
+// The partition of a plane into items: a strip is one item of cvh_march_rows rows
 CvhMpGeom cvh_mp_geometry(int h, int w)
 {
   CvhMpGeom g;
-  g.nwc = (w + CVH_MP_COLS - 1) / CVH_MP_COLS;
-  const int strips = std::max(CVH_MP_TARGET_WAVES / g.nwc, 1);
-  int rows = (int)(((long long)h + strips - 1) / strips);
-  rows = (int)(((long long)rows + 3) & ~3ll);
-  g.strip_rows = std::max(rows, CVH_MP_MIN_ROWS);
+  g.nwc = (w + CVH_MARCH_COLS - 1) / CVH_MARCH_COLS;
+  g.strip_rows = cvh_march_rows(h, g.nwc);
   g.nstrips = (h + g.strip_rows - 1) / g.strip_rows;
   g.nitems = g.nstrips * g.nwc;   // (< 2^28 / (8 * 61) + ...: the host has refused planes of 2^28 pixels)
   g.grid = (unsigned)((g.nitems + CVH_BLOCK / 64 - 1) / (CVH_BLOCK / 64));

@@ -1,15 +1,9 @@
 // multiphase_run.hip — host side of the four-phase calls (include/chanvese_hip.h, "Four phases"): two contexts A and B hold phi1 and
 // phi2 of a Vese-Chan pair and are iterated together by multiphase_kernels.hip.  The pair has no object of its own: a call checks the
-// pair, settles both contexts as the getters do, takes the pair's initial sums itself, and -- cvh_multiphase_run -- ends with both
-// contexts exactly as a device-side start leaves them (the level sets in the buffers cvh_set_levelset writes, the device's half of a
-// new run done on the leader's stream, then levelset_arrived), so that every existing call sees the new level sets.
-// Data flow of a run: iteration t reads d_u[(current + t) & 1] of each context and writes the other buffer of its pair -- the
-// contexts' own ping-pong pairs, no copy of a level set but at most ONE at the end, where the last iteration's buffer is not the one
-// a new level set lands in.  Per iteration two launches on A's stream: the step kernel (the update of both level sets and the items'
+// pair, settles both contexts as the getters do and takes the pair's initial sums itself; cvh_multiphase_run then hands the iterations
+// to march_run.hip's driver.  Per iteration two launches on A's stream: the step kernel (the update of both level sets and the items'
 // partial sums of the new pair) and the one-workgroup finalise (means, norms, trace row, count, stop flag into the state block of A's
-// workspace).  The host enqueues A's "sync_every" iterations at a time and reads the state block behind each chunk: its only wait per
-// chunk.  Launches enqueued behind a stop return at once (every workgroup reads the flag), so the level sets stay as the stopping
-// iteration left them and the host picks the buffers by the parity of steps_done.
+// workspace).
 #include "cvh_host.h"
 
 namespace {
@@ -72,12 +66,7 @@ void pair_args(cvh_context *const *ctxs, const CvhMpGeom &g, CvhMpArgs *m)
     for (int k = 0; k < c->C; ++k) { m->lambda1[e][k] = c->p.lambda1[k]; m->lambda2[e][k] = c->p.lambda2[k]; }
     m->stop[e] = c->p.tol * c->stop_norm;
   }
-  const double pi = 3.14159265358979323846;
-  m->eps = a->p.eps;
-  m->inv_eps = 1.0 / a->p.eps;
-  m->dk1 = pi / a->p.eps;
-  far_coef(a->p.eps, a->far_terms, m->far_k, &m->far_thr);
-  m->atan2_tab = a->d_atan + 2 * CVH_ATAN_N;
+  fill_front_args(a, &m->f);
 }
 
 // the sums of the current pair and the means they give, into the state block, on A's stream
@@ -90,23 +79,15 @@ int initial_sums(cvh_context *const *ctxs, CvhMpArgs *m)
   return CVH_OK;
 }
 
-int state_down(cvh_context *a, CvhMpState *out)
-{
-  HIPCHK(a, hipMemcpyAsync(a->h_state, a->d_multiphase, sizeof(CvhMpState), hipMemcpyDeviceToHost, a->stream));
-  HIPCHK(a, hipStreamSynchronize(a->stream));
-  memcpy(out, a->h_state, sizeof(CvhMpState));
-  return CVH_OK;
-}
-
 int multiphase_run(cvh_context *a, cvh_context *b, int max_steps, int *steps_done, double *norms, double *trace, int trace_rows, int *rows,
                    const char *what)
 {
   cvh_context *ctxs[2];
   int rc = pair_check(a, b, what, true, ctxs);
   if (rc != CVH_OK) return rc;
-  if (trace && (trace_rows < 0 || !rows))
-    return batch_fail(ctxs, 2, CVH_ERR_ARG, "%s: a trace needs trace_rows >= 0 and rows, got trace_rows = %d, rows = %p", what, trace_rows, (void *)rows);
-  if (max_steps < 0) max_steps = INT_MAX;   // (as cvh_run: until the pair stops)
+  MarchRun run{ctxs, 2, what, "ab"};
+  rc = run.begin(max_steps, trace, trace_rows, rows);
+  if (rc != CVH_OK) return rc;
   const CvhMpGeom g = cvh_mp_geometry(a->h, a->w);
   rc = pair_ready(ctxs, what, g);
   if (rc != CVH_OK) return rc;
@@ -114,58 +95,24 @@ int multiphase_run(cvh_context *a, cvh_context *b, int max_steps, int *steps_don
     rc = prepare_host(ctxs[e]);
     if (rc != CVH_OK) return batch_fail(ctxs, 2, rc, "%s: context %c: %s", what, "ab"[e], ctxs[e]->err);
   }
-  const int C = a->C, TR = 4 * C + 2, fast = use_fast(a);
-  const int trace_cap = trace ? std::min(trace_rows, max_steps) : 0;
-  if (trace_cap > 0) {
-    rc = grow_table(a, &a->mp_trace, (size_t)trace_cap * TR * sizeof(double));
-    if (rc != CVH_OK) return batch_fail(ctxs, 2, rc, "%s: %s", what, a->err);
-  }
+  const int C = a->C, fast = use_fast(a);
+  rc = run.open(&a->mp_trace, 4 * C + 2);
+  if (rc != CVH_OK) return rc;
   CvhMpArgs m;
   pair_args(ctxs, g, &m);
-  if (trace_cap > 0) { m.trace = (double *)a->mp_trace.d; m.trace_cap = trace_cap; }
-  rc = open_call(ctxs, 2, nullptr);
+  m.trace = run.d_trace; m.trace_cap = run.trace_cap;
+  rc = initial_sums(ctxs, &m);   // (its finalise writes the whole state block: where the localised flow zeroes its own)
   if (rc != CVH_OK) return rc;
-  rc = initial_sums(ctxs, &m);
-  if (rc != CVH_OK) return rc;
-  const int cur[2] = {current_buffer(a), current_buffer(b)};
   CvhMpState st;
-  memset(&st, 0, sizeof(st));
-  HIPCHK(a, hipEventRecord(a->ev0, a->stream));   // (ev0 / ev1 are free: settle closed any timed run)
-  int enq = 0;
-  while (enq < max_steps && !st.stopped) {
-    const int chunk = std::min(a->sync_every, max_steps - enq);
-    for (int t = enq; t < enq + chunk; ++t) {
-      for (int e = 0; e < 2; ++e) { m.in[e] = ctxs[e]->d_u[(cur[e] + t) & 1]; m.out[e] = ctxs[e]->d_u[(cur[e] + t + 1) & 1]; }
-      HIPCHK(a, cvh_launch_mp_step(m, C, fast, a->stream));
-      HIPCHK(a, cvh_launch_mp_finalize(m, C, 0, a->stream));
-    }
-    enq += chunk;
-    HIPCHK(a, hipEventRecord(a->ev1, a->stream));
-    rc = state_down(a, &st);   // the ONE host wait of the chunk
-    if (rc != CVH_OK) return rc;
-  }
-  if (enq > 0) HIPCHK(a, hipEventElapsedTime(&a->last_run_ms, a->ev0, a->ev1));
-  // the level sets of iteration steps_done - 1 into the buffers a new level set lands in, and the device's half of the run it begins
-  static const int zeros[4] = {0, 0, 0, 0};   // steps_done, stopped, ticket, pending
-  for (int e = 0; e < 2; ++e) {
-    cvh_context *c = ctxs[e];
-    const int from = (cur[e] + st.steps_done) & 1, to = c->chain_pb & 1;
-    if (from != to) HIPCHK(a, hipMemcpyAsync(c->d_u[to], c->d_u[from], c->n * sizeof(double), hipMemcpyDeviceToDevice, a->stream));
-    HIPCHK(a, hipMemcpyAsync(&c->d_state->steps_done, zeros, sizeof(zeros), hipMemcpyHostToDevice, a->stream));
-    HIPCHK(a, hipMemsetAsync(&c->d_chain->v[(c->chain_pb + 1) & 3][0], 0, sizeof(c->d_chain->v[0]), a->stream));
-  }
-  const int nrows = std::min(st.steps_done, trace_cap);
-  if (nrows > 0) HIPCHK(a, hipMemcpyAsync(trace, a->mp_trace.d, (size_t)nrows * TR * sizeof(double), hipMemcpyDeviceToHost, a->stream));
-  rc = close_call(ctxs, 2, nullptr, false);
+  rc = run.iterate(a->d_multiphase, &st, sizeof(st), [&](const double *const *in, double *const *out) -> int {
+    for (int e = 0; e < 2; ++e) { m.in[e] = in[e]; m.out[e] = out[e]; }
+    HIPCHK(a, cvh_launch_mp_step(m, C, fast, a->stream));
+    HIPCHK(a, cvh_launch_mp_finalize(m, C, 0, a->stream));
+    return CVH_OK;
+  });
   if (rc != CVH_OK) return rc;
-  HIPCHK(a, hipStreamSynchronize(a->stream));
-  for (int e = 0; e < 2; ++e) {
-    rc = levelset_arrived(ctxs[e], true);
-    if (rc != CVH_OK) return batch_fail(ctxs, 2, rc, "%s: context %c: %s", what, "ab"[e], ctxs[e]->err);
-  }
-  if (steps_done) *steps_done = st.steps_done;
+  if (steps_done) *steps_done = st.run.steps_done;
   if (norms) { norms[0] = st.norm[0]; norms[1] = st.norm[1]; }
-  if (rows) *rows = nrows;
   return CVH_OK;
 }
 
@@ -187,7 +134,7 @@ int multiphase_means(cvh_context *a, cvh_context *b, double *c, const char *what
   rc = close_call(ctxs, 2, nullptr, false);
   if (rc != CVH_OK) return rc;
   CvhMpState st;
-  rc = state_down(a, &st);
+  rc = state_down(a, a->d_multiphase, &st, sizeof(st));
   if (rc != CVH_OK) return rc;
   for (int ab = 0; ab < 4; ++ab)
     for (int k = 0; k < a->C; ++k) c[ab * a->C + k] = st.c[ab][k];
@@ -254,7 +201,7 @@ extern "C" void cvh_multiphase_geometry(int h, int w, int *cols, int *strip_rows
 {
   CvhMpGeom g{0, 0, 0, 0, 0};
   if (h > 0 && w > 0 && (long long)h * w < (1ll << 28)) g = cvh_mp_geometry(h, w);
-  if (cols) *cols = CVH_MP_COLS;
+  if (cols) *cols = CVH_MARCH_COLS;
   if (strip_rows) *strip_rows = g.strip_rows;
   if (items) *items = g.nitems;
 }

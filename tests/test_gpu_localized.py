@@ -121,10 +121,11 @@ def test_determinism_split_calls_and_the_read_only_call(capi, mode):
     assert runs[0][1].shape == L.case_reference(case)[2].shape
 
 
-@pytest.mark.parametrize("sync_every", [None, "k"], ids=["inside-a-chunk", "last-of-a-chunk"])
-def test_stop_rule(capi, sync_every):
+@pytest.mark.parametrize("sync_every,before", [(None, 0), ("k", 0), (None, 1)], ids=["inside-a-chunk", "last-of-a-chunk", "even-count"])
+def test_stop_rule(capi, sync_every, before):
     """the restatement stops at iteration k: so does the card, with exactly k trace rows, and launches enqueued behind the stop change
-    nothing -- the level set is that of a run with max_steps = k, bit for bit"""
+    nothing -- the level set is that of a run with max_steps = k, bit for bit.  k is odd: the stopping call ends with its one copy of the
+    level set; with `before` = 1 iteration done by an earlier call it counts k - 1, even, and ends without"""
     tol, k = L.stop_case()
     h, w, ch, rad = L.STOP_CASE
     planes, u = L.case_inputs(h, w, ch)
@@ -132,6 +133,10 @@ def test_stop_rule(capi, sync_every):
     try:
         stop = a.get_stop_condition()
         assert stop > 0
+        if before:
+            assert capi.localized_run(a, rad, before)[0] == before and capi.localized_run(b, rad, before)[0] == before
+            k -= before
+            assert k % 2 == 0 and k >= 2
         if sync_every:
             a.set_option("sync_every", k)
         steps, norm, trace = capi.localized_run(a, rad, 10 * k, trace=True)

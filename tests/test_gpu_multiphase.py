@@ -86,14 +86,19 @@ def stop_pair(capi, mode="fast", **kw):
     return make_pair(capi, planes, u1, u2, p, p, mode), k
 
 
-@pytest.mark.parametrize("sync_every", [None, "k"], ids=["inside-a-chunk", "last-of-a-chunk"])
-def test_stop_rule(capi, sync_every):
+@pytest.mark.parametrize("sync_every,before", [(None, 0), ("k", 0), (None, 1)], ids=["inside-a-chunk", "last-of-a-chunk", "even-count"])
+def test_stop_rule(capi, sync_every, before):
     """the restatement stops at iteration k (2 < k < the chunk of 32): so does the card, with exactly k trace rows, and launches enqueued
-    behind the stop change nothing -- the level sets are those of a run with max_steps = k, bit for bit"""
+    behind the stop change nothing -- the level sets are those of a run with max_steps = k, bit for bit.  k is odd: the stopping call ends
+    with its one copy of each level set; with `before` = 1 iteration done by an earlier call it counts k - 1, even, and ends without"""
     (a, b), k = stop_pair(capi)
     (c, d), _ = stop_pair(capi)
     try:
         assert a.get_stop_condition() > 0
+        if before:
+            assert capi.multiphase_run(a, b, before)[0] == before and capi.multiphase_run(c, d, before)[0] == before
+            k -= before
+            assert k % 2 == 0 and k > 2
         if sync_every:
             a.set_option("sync_every", k)
         steps, norms, trace = capi.multiphase_run(a, b, 10 * k, trace=True)
