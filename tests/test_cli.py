@@ -1,6 +1,7 @@
 """bin/chan_vese: the reference's command-line surface (src/main.cpp:752-874).  Validation
 needs no GPU (it runs before the backend is touched); the end-to-end run is a -m gpu test."""
 import os
+import re
 import subprocess
 
 import numpy as np
@@ -9,42 +10,7 @@ import pytest
 from chan_vese_amd import synth
 
 import png_util
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "bin", "chan_vese")
-
-
-@pytest.fixture(scope="module")
-def cli():
-    import __graft_entry__ as g
-    g.build()
-    assert os.path.exists(BIN)
-    return BIN
-
-
-def write_pgm(path, img):
-    with open(path, "wb") as f:
-        f.write(b"P5\n# synthetic\n%d %d\n255\n" % (img.shape[1], img.shape[0]))
-        f.write(np.ascontiguousarray(img, dtype=np.uint8).tobytes())
-
-
-def write_ppm(path, rgb):
-    with open(path, "wb") as f:
-        f.write(b"P6\n%d %d\n255\n" % (rgb.shape[1], rgb.shape[0]))
-        f.write(np.ascontiguousarray(rgb, dtype=np.uint8).tobytes())
-
-
-def read_pnm(path):
-    data = open(path, "rb").read()
-    parts = data.split(b"\n", 3)
-    magic, dims, maxv, body = parts[0], parts[1], parts[2], parts[3]
-    w, h = map(int, dims.split())
-    c = 1 if magic == b"P5" else 3
-    return np.frombuffer(body, dtype=np.uint8).reshape(h, w, c).squeeze()
-
-
-def run(cli, *args):
-    return subprocess.run([cli, *args], capture_output=True, text=True, timeout=600)
+from cli_util import cli, read_pnm, ROOT, run, write_pgm, write_ppm
 
 
 def test_help_lists_reference_options(cli):
@@ -55,6 +21,22 @@ def test_help_lists_reference_options(cli):
                 "--segment-time", "--segment", "--grayscale", "--video", "--overlay-text",
                 "--invert-selection", "--select", "--rectangle", "--circle"]:
         assert opt in r.stdout
+
+
+LONG_NAMES = """help input mu nu dt lambda1 lambda2 epsilon tolerance max-steps fps overlay-pos line-color edge-coef laplacian-coef
+    segment-time segment grayscale video overlay-text invert-selection select rectangle circle dump-u dump-mask device math state rect circ
+    reinit disk init threshold levels colorspace local local-radius dump-planes rank rank-radius connectivity min-area fill-holes largest roi
+    verbose energy energy-every truth score-tol measure contours contours-all contours-subpixel morph morph-radius init-mask truth-labels
+    phases init2 dump-labels localized""".split()
+
+
+def test_help_lists_every_long_name_the_parser_accepts(cli):
+    """Every row of the parser's table (options.hpp, kSpecs) is in LONG_NAMES, and -h shows every one of them as --name."""
+    table = open(os.path.join(ROOT, "chan_vese_amd", "host", "options.hpp")).read().split("kSpecs[] = {")[1].split("};")[0]
+    assert re.findall(r'\{"([a-z0-9-]+)",', table) == LONG_NAMES
+    text = run(cli, "-h").stdout
+    for name in LONG_NAMES:
+        assert re.search(r"--%s(?![a-z0-9-])" % re.escape(name), text), name
 
 
 def test_validation_messages_match_reference(cli, tmp_path):

@@ -1,14 +1,11 @@
 """chan_vese --colorspace without a GPU: the option is refused together with -g and for an unknown name, each with its message, before any
 device is touched; -h lists it."""
-import os
-import subprocess
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(ROOT, "bin", "chan_vese")
+import cli_util
+from cli_util import BIN as CLI, head_comment
 
 
 def run(*args):
-    return subprocess.run([CLI, *args], capture_output=True, text=True, timeout=120)
+    return cli_util.run(CLI, *args, timeout=120)
 
 
 def test_colorspace_is_validated(tmp_path):
@@ -29,4 +26,4 @@ def test_colorspace_is_validated(tmp_path):
 def test_help_lists_colorspace():
     text = run("-h").stdout
     assert "--colorspace arg" in text and "ycrcb | yuv" in text and "not with -g" in text
-    assert "--colorspace" in open(os.path.join(ROOT, "chan_vese_amd", "host", "main.cpp")).read().split("#include")[0]
+    assert "--colorspace" in head_comment()

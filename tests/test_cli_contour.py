@@ -1,41 +1,19 @@
 """bin/chan_vese --contours FILE: -h lists it and the refusals hold (CPU); on the GPU the text file of a small synthetic image parses back
 into the restatement's loops and points (contour_util.py) of the mask --dump-mask writes in the same run."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import contour_util as ct
 from chan_vese_amd import synth
+from cli_util import cli, head_comment, run, write_pgm
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "bin", "chan_vese")
 H, W = 40, 56
-
-
-@pytest.fixture(scope="module")
-def cli():
-    import __graft_entry__ as g
-    g.build()
-    assert os.path.exists(BIN)
-    return BIN
-
-
-def run(cli, *args):
-    return subprocess.run([cli, *args], capture_output=True, text=True, timeout=600)
-
-
-def write_pgm(path, img):
-    with open(path, "wb") as f:
-        f.write(b"P5\n%d %d\n255\n" % (img.shape[1], img.shape[0]))
-        f.write(np.ascontiguousarray(img, dtype=np.uint8).tobytes())
 
 
 def test_help_and_refusals(cli, tmp_path):
     text = run(cli, "-h").stdout
     assert "--contours arg" in text and "'first edges area2 :'" in text and "--contours-all" in text
-    head = open(os.path.join(ROOT, "chan_vese_amd", "host", "main.cpp")).read().split("#include")[0]
+    head = head_comment()
     assert "--contours" in head
     r = run(cli, "-i", "x.pgm", "--contours")
     assert r.returncode == 1 and "error: the required argument for option '--contours' is missing" in r.stderr

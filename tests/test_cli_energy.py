@@ -1,41 +1,13 @@
 """bin/chan_vese --energy / --energy-every: the flags are validated before any device is touched and -h lists them (CPU); on the GPU the
 printed lines parse, hold %.17g numbers that are capi's Context.energy() for the same run bit for bit, and a run without the flags
 prints what it printed before them -- nothing on stdout -- and leaves the same level set."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 from chan_vese_amd import synth
+from cli_util import cli, head_comment, run, write_pgm, write_ppm
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "bin", "chan_vese")
 H, W = 40, 56
-
-
-@pytest.fixture(scope="module")
-def cli():
-    import __graft_entry__ as g
-    g.build()
-    assert os.path.exists(BIN)
-    return BIN
-
-
-def run(cli, *args):
-    return subprocess.run([cli, *args], capture_output=True, text=True, timeout=600)
-
-
-def write_pgm(path, img):
-    with open(path, "wb") as f:
-        f.write(b"P5\n%d %d\n255\n" % (img.shape[1], img.shape[0]))
-        f.write(np.ascontiguousarray(img, dtype=np.uint8).tobytes())
-
-
-def write_ppm(path, rgb):
-    with open(path, "wb") as f:
-        f.write(b"P6\n%d %d\n255\n" % (rgb.shape[1], rgb.shape[0]))
-        f.write(np.ascontiguousarray(rgb, dtype=np.uint8).tobytes())
 
 
 def parse(line, channels, with_iteration):
@@ -65,7 +37,7 @@ def test_energy_flags_are_validated(cli, tmp_path):
 def test_help_lists_the_energy_flags(cli):
     text = run(cli, "-h").stdout
     assert "--energy  " in text and "--energy-every arg (=0)" in text and "fit_in... fit_out..." in text
-    head = open(os.path.join(ROOT, "chan_vese_amd", "host", "main.cpp")).read().split("#include")[0]
+    head = head_comment()
     assert "--energy" in head and "--energy-every" in head
 
 

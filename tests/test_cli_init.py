@@ -1,6 +1,5 @@
 """bin/chan_vese with the device-side starts: --rect (now cvh_init_rect) against a host-filled run of the same rectangle, --init otsu,
 --threshold and --disk against the restated starts (init_util), with and without -S.  The runs need a GPU."""
-import os
 import subprocess
 
 import numpy as np
@@ -9,30 +8,9 @@ import pytest
 from chan_vese_amd import synth
 
 import init_util as U
+from cli_util import cli, write_pgm, write_ppm
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "bin", "chan_vese")
 H, W = 40, 56
-
-
-@pytest.fixture(scope="module")
-def cli():
-    import __graft_entry__ as g
-    g.build()
-    assert os.path.exists(BIN)
-    return BIN
-
-
-def write_pgm(path, img):
-    with open(path, "wb") as f:
-        f.write(b"P5\n%d %d\n255\n" % (img.shape[1], img.shape[0]))
-        f.write(np.ascontiguousarray(img, dtype=np.uint8).tobytes())
-
-
-def write_ppm(path, rgb):
-    with open(path, "wb") as f:
-        f.write(b"P6\n%d %d\n255\n" % (rgb.shape[1], rgb.shape[0]))
-        f.write(np.ascontiguousarray(rgb, dtype=np.uint8).tobytes())
 
 
 def dump_u(cli, tmp_path, image, *args):

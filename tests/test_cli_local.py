@@ -1,26 +1,16 @@
 """chan_vese --local / --local-radius: without a GPU the options are validated, each refusal with its message, before any device is
 touched, and -h lists them; on the GPU (marked) the flags give the planes and the mask of the capi sequence -- set_image,
 local_planes_to, the start, run, get_mask -- for the deviation plane of the proposition's image and for the stack with three lambdas."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import local_util as U
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(ROOT, "bin", "chan_vese")
+import cli_util
+from cli_util import BIN as CLI, head_comment, write_pgm
 
 
 def run(*args):
-    return subprocess.run([CLI, *args], capture_output=True, text=True, timeout=120)
-
-
-def write_pgm(path, plane):
-    h, w = plane.shape
-    with open(path, "wb") as f:
-        f.write(b"P5\n%d %d\n255\n" % (w, h) + np.ascontiguousarray(plane).tobytes())
+    return cli_util.run(CLI, *args, timeout=120)
 
 
 def read_pgm_tail(path, h, w):
@@ -53,7 +43,7 @@ def test_local_is_validated(tmp_path):
 def test_help_lists_local():
     text = run("-h").stdout
     assert "--local arg" in text and "mean | dev | stack" in text and "--local-radius arg (=2)" in text and "--dump-planes arg" in text
-    assert "--local mean|dev|stack" in open(os.path.join(ROOT, "chan_vese_amd", "host", "main.cpp")).read().split("#include")[0]
+    assert "--local mean|dev|stack" in head_comment()
 
 
 @pytest.mark.gpu

@@ -1,34 +1,12 @@
 """bin/chan_vese --localized R: the option is validated before any device is touched and -h lists it (CPU); on the GPU the mask and
 the level set are the C ABI's for the same start, and a run without --localized writes what it wrote before the option existed."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import localized_util as L
+from cli_util import cli, head_comment, run, write_pgm
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "bin", "chan_vese")
 H, W = 40, 56
-
-
-@pytest.fixture(scope="module")
-def cli():
-    import __graft_entry__ as g
-    g.build()
-    assert os.path.exists(BIN)
-    return BIN
-
-
-def run(cli, *args):
-    return subprocess.run([cli, *args], capture_output=True, text=True, timeout=600)
-
-
-def write_pgm(path, img):
-    with open(path, "wb") as f:
-        f.write(b"P5\n%d %d\n255\n" % (img.shape[1], img.shape[0]))
-        f.write(np.ascontiguousarray(img, dtype=np.uint8).tobytes())
 
 
 def test_refused_combinations_exit_with_their_message(cli, tmp_path):
@@ -49,7 +27,7 @@ def test_refused_combinations_exit_with_their_message(cli, tmp_path):
 def test_help_lists_the_option(cli):
     text = run(cli, "-h").stdout
     assert "--localized arg" in text
-    head = open(os.path.join(ROOT, "chan_vese_amd", "host", "main.cpp")).read().split("#include")[0]
+    head = head_comment()
     assert "--localized" in head
 
 

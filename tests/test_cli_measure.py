@@ -1,43 +1,21 @@
 """bin/chan_vese --measure FILE: -h lists it (CPU); on the GPU the CSV of a small synthetic image parses, its integer columns are the
 restatement's (measure_util.py) on the mask --dump-mask writes in the same run, and its doubles are capi.region_shapes' of that table."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import measure_util as mu
 from chan_vese_amd import synth
+from cli_util import cli, head_comment, run, write_pgm
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "bin", "chan_vese")
 H, W = 40, 56
 INT_COLS = ["first", "area", "x0", "y0", "x1", "y1", "border", "perimeter"]
 DOUBLE_COLS = ["cx", "cy", "mu20", "mu02", "mu11", "theta", "major", "minor"]
 
 
-@pytest.fixture(scope="module")
-def cli():
-    import __graft_entry__ as g
-    g.build()
-    assert os.path.exists(BIN)
-    return BIN
-
-
-def run(cli, *args):
-    return subprocess.run([cli, *args], capture_output=True, text=True, timeout=600)
-
-
-def write_pgm(path, img):
-    with open(path, "wb") as f:
-        f.write(b"P5\n%d %d\n255\n" % (img.shape[1], img.shape[0]))
-        f.write(np.ascontiguousarray(img, dtype=np.uint8).tobytes())
-
-
 def test_help_lists_the_measure_flag(cli):
     text = run(cli, "-h").stdout
     assert "--measure arg" in text and "first,area,x0,y0,x1,y1,border,perimeter,cx,cy,mu20,mu02,mu11,theta,major,minor" in text
-    head = open(os.path.join(ROOT, "chan_vese_amd", "host", "main.cpp")).read().split("#include")[0]
+    head = head_comment()
     assert "--measure" in head
     r = run(cli, "-i", "x.pgm", "--measure")
     assert r.returncode == 1 and "error: the required argument for option '--measure' is missing" in r.stderr

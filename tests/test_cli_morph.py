@@ -2,9 +2,6 @@
 touched (CPU); on the GPU `--morph open --morph-radius 2 --dump-mask` is the restatement (morph_util.py) of the `--dump-mask` without it --
 with and without cleaning flags, and --roi, --measure and --contours speak of the same morphed mask --, and `--init-mask` with `-N 0` dumps
 the mask it was given."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
@@ -12,22 +9,9 @@ import components_util as CU
 import contour_util as CT
 import morph_util as M
 from chan_vese_amd import synth
+from cli_util import cli, head_comment, read_pnm as read_pgm, run
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "bin", "chan_vese")
 H, W = 40, 56
-
-
-@pytest.fixture(scope="module")
-def cli():
-    import __graft_entry__ as g
-    g.build()
-    assert os.path.exists(BIN)
-    return BIN
-
-
-def run(cli, *args):
-    return subprocess.run([cli, *args], capture_output=True, text=True, timeout=600)
 
 
 def write_pnm(path, img):
@@ -37,17 +21,10 @@ def write_pnm(path, img):
         f.write(img.tobytes())
 
 
-def read_pgm(path):
-    raw = open(path, "rb").read()
-    magic, w, h, maxv = raw.split(None, 4)[:4]
-    assert magic == b"P5" and maxv == b"255"
-    return np.frombuffer(raw[-int(w) * int(h):], dtype=np.uint8).reshape(int(h), int(w))
-
-
 def test_help_lists_the_morph_flags(cli):
     text = run(cli, "-h").stdout
     assert "--morph arg" in text and "--morph-radius arg (=1)" in text and "--init-mask arg" in text and "dilate | erode | open | close" in text
-    head = open(os.path.join(ROOT, "chan_vese_amd", "host", "main.cpp")).read().split("#include")[0]
+    head = head_comment()
     assert "--morph" in head and "--morph-radius" in head and "--init-mask" in head
 
 

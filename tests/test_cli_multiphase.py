@@ -1,42 +1,13 @@
 """bin/chan_vese --phases 4: the options are validated before any device is touched and -h lists them (CPU); on the GPU --dump-labels
 writes the bytes the capi path gives, -s the label plane times 85, and a run without --phases writes what the parent's program wrote for
 an existing CLI case (test_cli_energy.py's: the level set capi leaves for the same run, bit for bit, and nothing on stdout)."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import multiphase_util as M
+from cli_util import cli, head_comment, read_pnm as read_pgm, run, write_pgm
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "bin", "chan_vese")
 H, W = 40, 56
-
-
-@pytest.fixture(scope="module")
-def cli():
-    import __graft_entry__ as g
-    g.build()
-    assert os.path.exists(BIN)
-    return BIN
-
-
-def run(cli, *args):
-    return subprocess.run([cli, *args], capture_output=True, text=True, timeout=600)
-
-
-def write_pgm(path, img):
-    with open(path, "wb") as f:
-        f.write(b"P5\n%d %d\n255\n" % (img.shape[1], img.shape[0]))
-        f.write(np.ascontiguousarray(img, dtype=np.uint8).tobytes())
-
-
-def read_pgm(path):
-    data = open(path, "rb").read()
-    magic, w, h, maxval = data.split(None, 4)[:4]
-    assert magic == b"P5" and maxval == b"255"
-    return np.frombuffer(data[-int(w) * int(h):], dtype=np.uint8).reshape(int(h), int(w))
 
 
 def test_refused_combinations_exit_with_their_message(cli, tmp_path):
@@ -66,7 +37,7 @@ def test_refused_combinations_exit_with_their_message(cli, tmp_path):
 def test_help_lists_the_options(cli):
     text = run(cli, "-h").stdout
     assert "--phases arg (=2)" in text and "--init2 arg (=checkerboard)" in text and "--dump-labels arg" in text
-    head = open(os.path.join(ROOT, "chan_vese_amd", "host", "main.cpp")).read().split("#include")[0]
+    head = head_comment()
     assert "--phases" in head and "--init2" in head and "--dump-labels" in head
 
 

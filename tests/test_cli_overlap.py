@@ -2,37 +2,16 @@
 printed integers are the restatement's (overlap_util.py) for the level set the run leaves, with the cleaning options applied, and mean_ap
 is capi.ObjectScore's."""
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import components_util as cu
 import overlap_util as ou
+from cli_util import cli, head_comment, run, write_pgm
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "bin", "chan_vese")
 H, W = 64, 64
 SQUARES = [(6, 8, 1), (10, 40, 2), (38, 20, 300)]   # top, left, label: 16 x 16 each
-
-
-@pytest.fixture(scope="module")
-def cli():
-    import __graft_entry__ as g
-    g.build()
-    assert os.path.exists(BIN)
-    return BIN
-
-
-def run(cli, *args):
-    return subprocess.run([cli, *args], capture_output=True, text=True, timeout=600)
-
-
-def write_pgm(path, img, maxval=255):
-    with open(path, "wb") as f:
-        f.write(b"P5\n%d %d\n%d\n" % (img.shape[1], img.shape[0], maxval))
-        f.write(np.ascontiguousarray(img, dtype=np.uint8 if maxval < 256 else ">u2").tobytes())
 
 
 def planes():
@@ -60,7 +39,7 @@ def parse(line):
 def test_help_lists_the_flag(cli):
     text = run(cli, "-h").stdout
     assert "--truth-labels arg" in text and "objects_a= objects_b= tp= fp= fn= mean_ap=" in text
-    head = open(os.path.join(ROOT, "chan_vese_amd", "host", "main.cpp")).read().split("#include")[0]
+    head = head_comment()
     assert "--truth-labels" in head
 
 

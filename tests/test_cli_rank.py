@@ -2,27 +2,17 @@
 touched, and -h lists them; on the GPU (marked) every spelling gives the restatement's planes (--dump-planes) and the mask of the capi
 sequence -- set_image, rank_planes_to, the start, run, get_mask --, --init otsu acts on the rank planes, and with --local the rank filter
 runs first."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import local_util as LU
 import rank_util as U
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(ROOT, "bin", "chan_vese")
+import cli_util
+from cli_util import BIN as CLI, head_comment, write_pgm
 
 
 def run(*args):
-    return subprocess.run([CLI, *args], capture_output=True, text=True, timeout=120)
-
-
-def write_pgm(path, plane):
-    h, w = plane.shape
-    with open(path, "wb") as f:
-        f.write(b"P5\n%d %d\n255\n" % (w, h) + np.ascontiguousarray(plane).tobytes())
+    return cli_util.run(CLI, *args, timeout=120)
 
 
 def read_pgm_tail(path, h, w):
@@ -53,7 +43,7 @@ def test_rank_is_validated(tmp_path):
 def test_help_lists_rank():
     text = run("-h").stdout
     assert "--rank arg" in text and "median | min | max | open | close | tophat | bothat" in text and "--rank-radius arg (=1)" in text
-    assert "--rank median|min|max|open|close|tophat|bothat" in open(os.path.join(ROOT, "chan_vese_amd", "host", "main.cpp")).read().split("#include")[0]
+    assert "--rank median|min|max|open|close|tophat|bothat" in head_comment()
 
 
 @pytest.mark.gpu

@@ -1,36 +1,15 @@
 """bin/chan_vese --truth / --score-tol: -h lists them and a truth of another size is refused before any device is touched (CPU); on the
 GPU the printed integers are the restatement's (score_util.py) for the level set the run leaves, and the figures are capi.Score's."""
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import score_util as S
 from chan_vese_amd import synth
+from cli_util import cli, head_comment, run, write_pgm
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "bin", "chan_vese")
 H, W = 40, 56
-
-
-@pytest.fixture(scope="module")
-def cli():
-    import __graft_entry__ as g
-    g.build()
-    assert os.path.exists(BIN)
-    return BIN
-
-
-def run(cli, *args):
-    return subprocess.run([cli, *args], capture_output=True, text=True, timeout=600)
-
-
-def write_pgm(path, img):
-    with open(path, "wb") as f:
-        f.write(b"P5\n%d %d\n255\n" % (img.shape[1], img.shape[0]))
-        f.write(np.ascontiguousarray(img, dtype=np.uint8).tobytes())
 
 
 def parse(line):
@@ -43,7 +22,7 @@ def parse(line):
 def test_help_lists_the_score_flags(cli):
     text = run(cli, "-h").stdout
     assert "--truth arg" in text and "--score-tol arg (=2)" in text and "surface_dice=" in text
-    head = open(os.path.join(ROOT, "chan_vese_amd", "host", "main.cpp")).read().split("#include")[0]
+    head = head_comment()
     assert "--truth" in head and "--score-tol" in head
 
 

@@ -1,40 +1,18 @@
 """bin/chan_vese --contours FILE --contours-subpixel: -h lists it and the refusals hold (CPU); on the GPU the text file of a 64 x 64
 synthetic disk parses back into what Context.contours_subpixel() gives for the level set --dump-u writes in the same run."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 from chan_vese_amd import synth
+from cli_util import cli, head_comment, run, write_pgm
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "bin", "chan_vese")
 N = 64
-
-
-@pytest.fixture(scope="module")
-def cli():
-    import __graft_entry__ as g
-    g.build()
-    assert os.path.exists(BIN)
-    return BIN
-
-
-def run(cli, *args):
-    return subprocess.run([cli, *args], capture_output=True, text=True, timeout=600)
-
-
-def write_pgm(path, img):
-    with open(path, "wb") as f:
-        f.write(b"P5\n%d %d\n255\n" % (img.shape[1], img.shape[0]))
-        f.write(np.ascontiguousarray(img, dtype=np.uint8).tobytes())
 
 
 def test_help_and_refusals(cli, tmp_path):
     text = run(cli, "-h").stdout
     assert "--contours-subpixel" in text and "%.17g" in text
-    head = open(os.path.join(ROOT, "chan_vese_amd", "host", "main.cpp")).read().split("#include")[0]
+    head = head_comment()
     assert "--contours-subpixel" in head and "Subpixel contours" in head
     write_pgm(tmp_path / "a.pgm", synth.disk(N, 190, 60, noise=48, seed=4))
     r = run(cli, "-i", str(tmp_path / "a.pgm"), "--contours-subpixel")

@@ -19,7 +19,7 @@ import numpy as np
 import pytest
 
 from chan_vese_amd import synth
-from test_cli import BIN, read_pnm, write_pgm, write_ppm
+from cli_util import BIN, read_pnm, write_pgm, write_ppm
 
 pytestmark = pytest.mark.gpu
 
