@@ -47,6 +47,7 @@ EXPORTS = [
     "cvh_contours_subpixel", "cvh_contours_subpixel_device", "cvh_contours_subpixel_device_batch", "cvh_contour_subpixel_measure",
     "cvh_get_mask_morph", "cvh_get_mask_morph_device", "cvh_get_mask_morph_device_batch", "cvh_morph_levelset", "cvh_morph_levelset_batch",
     "cvh_init_mask", "cvh_init_mask_device", "cvh_init_mask_device_batch",
+    "cvh_split", "cvh_split_host", "cvh_split_batch", "cvh_split_levelset", "cvh_split_levelset_batch", "cvh_split_geometry",
     "cvh_multiphase_run", "cvh_multiphase_means", "cvh_multiphase_labels", "cvh_multiphase_labels_device", "cvh_multiphase_geometry",
     "cvh_localized_run", "cvh_localized_means", "cvh_localized_geometry",
 ]
@@ -376,6 +377,14 @@ def lib():
         "cvh_init_mask": (C.c_int, [vp, u8p, C.c_double, C.c_double]),
         "cvh_init_mask_device": (C.c_int, [vp, vp, C.c_double, C.c_double, vp]),
         "cvh_init_mask_device_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.POINTER(vp), C.c_double, C.c_double, vp]),
+        "cvh_split": (C.c_int, [vp, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, C.c_uint32, vp, vp, C.c_int, ip, vp]),
+        "cvh_split_host": (C.c_int, [vp, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, C.c_uint32, vp, vp, C.c_int, ip]),
+        "cvh_split_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, C.POINTER(C.c_uint32), C.POINTER(vp),
+                                      ip, vp]),
+        "cvh_split_levelset": (C.c_int, [vp, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, C.c_uint32, C.c_double, C.c_double]),
+        "cvh_split_levelset_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, C.POINTER(C.c_uint32),
+                                               C.c_double, C.c_double]),
+        "cvh_split_geometry": (None, [ip, ip, ip]),
         "cvh_multiphase_run": (C.c_int, [vp, vp, C.c_int, ip, dp, dp, C.c_int, ip]),
         "cvh_multiphase_means": (C.c_int, [vp, vp, dp]),
         "cvh_multiphase_labels": (C.c_int, [vp, vp, u8p]),
@@ -911,6 +920,35 @@ def morph_levelset_batch(contexts, op, r2=None, radius=None, conn=4, invert=Fals
     n = len(contexts)
     args = _clean_args(conn, invert, min_area, fill_holes, keep_largest) + (morph_code(op), _r2_array(r2, radius, n))
     _batch_chk(lib().cvh_morph_levelset_batch(_member_array(contexts), n, *args, float(inside), float(outside)))
+
+
+def split_geometry():
+    """cvh_split_geometry: (tile_rows, tile_cols, group) -- the tile of the growth's sweeps and the sweeps enqueued per host wait."""
+    tr, tc, g = C.c_int(0), C.c_int(0), C.c_int(0)
+    lib().cvh_split_geometry(C.byref(tr), C.byref(tc), C.byref(g))
+    return tr.value, tc.value, g.value
+
+
+def split_batch(contexts, ptrs=None, r2=None, radius=None, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False, stream=0):
+    """cvh_split_batch: Context.split for n contexts (any mix of shapes and channel counts) with one set of launches.  ptrs: one integer
+    device address of h * w int32 labels per context (0 = no label plane for that member), or None; r2 / radius are one number or one per
+    member.  Returns [K] per context."""
+    contexts = list(contexts)
+    n = len(contexts)
+    counts = (C.c_int * max(n, 1))()
+    addr = None if ptrs is None else _address_array(list(ptrs), n)
+    args = _clean_args(conn, invert, min_area, fill_holes, keep_largest) + (_r2_array(r2, radius, n),)
+    _batch_chk(lib().cvh_split_batch(_member_array(contexts), n, *args, addr, counts, int(stream) or None))
+    return [counts[i] for i in range(n)]
+
+
+def split_levelset_batch(contexts, r2=None, radius=None, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False, inside=1.0,
+                         outside=-1.0):
+    """cvh_split_levelset_batch: Context.split_levelset for n contexts with one set of launches; r2 / radius as in split_batch."""
+    contexts = list(contexts)
+    n = len(contexts)
+    args = _clean_args(conn, invert, min_area, fill_holes, keep_largest) + (_r2_array(r2, radius, n),)
+    _batch_chk(lib().cvh_split_levelset_batch(_member_array(contexts), n, *args, float(inside), float(outside)))
 
 
 def init_mask_batch(contexts, ptrs, inside=1.0, outside=-1.0, stream=0):
@@ -1564,6 +1602,39 @@ class Context:
             return m
         _batch_chk(self._L.cvh_get_mask_morph_device(self._h, int(out) or None, *args, int(stream) or None))
         return out
+
+    def split(self, r2=None, radius=None, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False, labels_ptr=0, cap=None, stream=0):
+        """cvh_split: the cleaned mask (get_mask_clean's arguments) taken apart into one object per core of its erosion by the disk
+        dx^2 + dy^2 <= r2 (r2, or radius with r2 = floor(radius^2)): "Object split" in include/chanvese_hip.h.  labels_ptr: integer device
+        address of h * w int32 (0 = no label plane).  Returns (labels, table, K): labels is labels_ptr or None; table is a structured array
+        (COMPONENT_DTYPE) of the first min(K, cap) rows -- `first` the marker's smallest flat index, area and box those of the grown
+        object.  cap = None asks for all K rows and COSTS TWO CALLS (as components); cap = 0 for no table.  Only reads."""
+        count = C.c_int(0)
+        args = _clean_args(conn, invert, min_area, fill_holes, keep_largest) + (_morph_r2(r2, radius),)
+        labels = int(labels_ptr) or None
+        if cap is None:
+            _batch_chk(self._L.cvh_split(self._h, *args, labels, None, 0, C.byref(count), int(stream) or None))
+            table = np.zeros(count.value, dtype=COMPONENT_DTYPE)
+            if count.value:
+                _batch_chk(self._L.cvh_split(self._h, *args, None, table.ctypes.data, count.value, C.byref(count), None))
+            return labels, table, count.value
+        table = np.zeros(max(int(cap), 0), dtype=COMPONENT_DTYPE)
+        _batch_chk(self._L.cvh_split(self._h, *args, labels, table.ctypes.data if table.size else None, int(cap), C.byref(count), int(stream) or None))
+        return labels, table[:min(count.value, table.size)].copy(), count.value
+
+    def split_labels(self, r2=None, radius=None, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False):
+        """cvh_split_host: split()'s label plane as a numpy int32 array (h, w) in host memory, and K: (labels, K)."""
+        count = C.c_int(0)
+        labels = np.empty((self.h, self.w), dtype=np.int32)
+        args = _clean_args(conn, invert, min_area, fill_holes, keep_largest) + (_morph_r2(r2, radius),)
+        _batch_chk(self._L.cvh_split_host(self._h, *args, labels.ctypes.data, None, 0, C.byref(count)))
+        return labels, count.value
+
+    def split_levelset(self, r2=None, radius=None, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False, inside=1.0, outside=-1.0):
+        """cvh_split_levelset: split in place -- the level set becomes `inside` on the split objects and `outside` on the cut lines and the
+        background, and a new run begins; components, measure, contours, overlaps and further iterations then see the split objects."""
+        args = _clean_args(conn, invert, min_area, fill_holes, keep_largest) + (_morph_r2(r2, radius),)
+        _batch_chk(self._L.cvh_split_levelset(self._h, *args, float(inside), float(outside)))
 
     def morph_levelset(self, op, r2=None, radius=None, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False, inside=1.0,
                        outside=-1.0):

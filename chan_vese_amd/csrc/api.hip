@@ -150,6 +150,7 @@ extern "C" void cvh_destroy(cvh_context *c)
   if (c->d_energy) (void)hipFree(c->d_energy);
   if (c->d_score) (void)hipFree(c->d_score);
   if (c->d_morph) (void)hipFree(c->d_morph);
+  if (c->d_split) (void)hipFree(c->d_split);
   if (c->d_local) (void)hipFree(c->d_local);
   if (c->d_rank) (void)hipFree(c->d_rank);
   if (c->d_overlap_plane) (void)hipFree(c->d_overlap_plane);

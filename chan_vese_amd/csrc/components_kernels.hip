@@ -13,9 +13,7 @@
 // Numbering (cvh_components): roots counted per workgroup, one workgroup per member scans the counts, the roots take their numbers in
 // raster order (root p then holds kNumbered | k), the labels follow.  The table (after the host knows K) is filled per horizontal run.
 // Cleaning (cvh_get_mask_clean*): area (and "touches the border") per root in stat[root], a 64-bit atomic max finds the largest component.
-#include <limits.h>
-
-#include "cvh_internal.h"
+#include "cc_device.h"
 
 namespace {
 
@@ -23,8 +21,7 @@ namespace {
 typedef CVH_GLOBAL unsigned *gwords;
 
 static_assert(CVH_BLOCK == 256, "the per-wave counts below are summed as four waves");
-constexpr unsigned kNone = 0xffffffffu;       // not a pixel of the class
-constexpr unsigned kNumbered = 0x80000000u;   // a root after cc_number_kernel: kNumbered | k, k = 1 .. K <= 2^30
+constexpr unsigned kNone = kCcNone, kNumbered = kCcNumbered;   // (cc_device.h)
 constexpr unsigned kBorder = 0x80000000u;     // stat[root]: the component has a pixel in the first / last row / column (areas are < 2^31)
 
 // the member whose section holds this workgroup (reinit_kernels.hip's reinit_member)
@@ -202,19 +199,10 @@ __global__ void __launch_bounds__(CVH_BLOCK) cc_table_init_kernel(const CvhIoMem
   const unsigned v = ((gwords)x.m->plane[0])[x.p];
   if (v == kNone || !(v & kNumbered)) return;
   CVH_GLOBAL cvh_component *row = (CVH_GLOBAL cvh_component *)x.m->dst + ((v & ~kNumbered) - 1u);
-  row->first = x.p; row->area = 0;
-  row->x0 = INT_MAX; row->y0 = INT_MAX; row->x1 = -1; row->y1 = -1;
+  cc_row_init(row, x.p);
 }
 
-// lanes i .. i + len - 1 of the wave hold the same key and lane i starts the run (len = 0: not a start); cut > 0 also starts a run
-__device__ __forceinline__ unsigned run_length(unsigned key, bool cut)
-{
-  const unsigned lane = lane_id(), prev = __shfl_up(key, 1, 64);
-  const bool start = key != kNone && (lane == 0 || prev != key || cut);
-  const unsigned long long ends = __ballot(start || key == kNone) & ~upto(lane);
-  if (!start) return 0;
-  return (ends ? (unsigned)__builtin_ctzll(ends) : 64u) - lane;
-}
+__device__ __forceinline__ unsigned run_length(unsigned key, bool cut) { return cc_run_length(key, cut); }   // (cc_device.h)
 
 // area and box per component: one set of atomics per horizontal run inside a wave; min and max only where they would move the value
 __global__ void __launch_bounds__(CVH_BLOCK) cc_table_stats_kernel(const CvhIoMember *tab, int nmem)
@@ -225,12 +213,7 @@ __global__ void __launch_bounds__(CVH_BLOCK) cc_table_stats_kernel(const CvhIoMe
   const unsigned len = run_length(k ? k : kNone, c == 0);
   if (!len) return;
   CVH_GLOBAL cvh_component *row = (CVH_GLOBAL cvh_component *)x.m->dst + (k - 1u);
-  const int r = (int)(x.p / w), c0 = (int)c, c1 = (int)(c + len - 1u);
-  __hip_atomic_fetch_add(&row->area, len, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (c0 < __hip_atomic_load(&row->x0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) __hip_atomic_fetch_min(&row->x0, c0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (r < __hip_atomic_load(&row->y0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) __hip_atomic_fetch_min(&row->y0, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (c1 > __hip_atomic_load(&row->x1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) __hip_atomic_fetch_max(&row->x1, c1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (r > __hip_atomic_load(&row->y1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) __hip_atomic_fetch_max(&row->y1, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  cc_row_add_run(row, len, (int)(x.p / w), (int)c);
 }
 
 // cleaning: flatten, and add the areas into stat[root], one add per run of a root inside a wave; border = 1 also marks the roots whose

@@ -5,7 +5,7 @@
 // calls: MemberCall with its further waits, write_planes, the pointer checks, the launch counters), init_run.hip (device-side initial
 // level sets), components_run.hip (connected components, and MaskSource: the raw or cleaned mask every mask-derived call starts from),
 // pyramid_run.hip (coarse-to-fine), colour_run.hip (colour spaces), window_run.hip (local statistics and rank planes: the windowed-plane calls), energy_run.hip (the functional's terms), score_run.hip (mask scores),
-// morph_run.hip (mask morphology, mask starts), measure_run.hip (component measures), contour_run.hip (contours), overlap_run.hip
+// morph_run.hip (mask morphology, mask starts), split_run.hip (object split), measure_run.hip (component measures), contour_run.hip (contours), overlap_run.hip
 // (component overlaps), multiphase_run.hip (four phases: a pair of contexts iterated together), localized_run.hip (localised regions), march_run.hip (the driver under those two), debug_exports.hip (diagnostics).  Kernel
 // sources do not include it.
 #pragma once
@@ -175,6 +175,9 @@ struct cvh_context {   // opaque to callers; four groups
                                  // host form stages (5.5 bytes per pixel): allocated by the first call, kept -- not part of live_footprint either
   void *d_morph = nullptr;       // workspace of cvh_get_mask_morph* / cvh_morph_levelset* / cvh_init_mask (morph_run.hip): two planes of band words, the
                                  // 16-bit distance field and a byte plane (3.25 bytes per pixel): allocated by the first call, kept -- not part of live_footprint either
+  void *d_split = nullptr;       // workspace of cvh_split* / cvh_split_levelset* (split_run.hip): the growth's 64-bit keys, 8 bytes per pixel of the plane
+                                 // rounded up to whole tiles: allocated (and its padding cleared) by the first call, kept -- not part of
+                                 // live_footprint either; the calls also take the morphology and the components workspaces
   void *d_local = nullptr;       // workspace of cvh_local_planes* (window_run.hip) as their DESTINATION: the row sums of the source planes it reads, a
                                  // slot of 6 bytes per pixel per plane of this context: allocated by the first call that takes a mean or a
                                  // deviation, kept -- not part of live_footprint either
@@ -301,8 +304,9 @@ void free_table(DeviceTable *t);
 // reduce pass for all members) of cvh_energy*, the launch sets (four kernels for all members) of cvh_score_mask*, and the launch sets (every
 // kernel of the call, for all members) of cvh_get_mask_morph* / cvh_morph_levelset* / cvh_init_mask*, and the pair launches of cvh_overlaps*
 // (one per call, and one more each time a member's table had to grow), and the launch sets (every pass of the family for all pairs) of
-// cvh_local_planes* and of cvh_rank_planes* (window_run.hip: a Family names its counter)
-enum LaunchCounter { kReinitLaunchSets, kPyramidLaunches, kColourLaunches, kEnergyLaunchSets, kScoreLaunchSets, kMorphLaunchSets, kOverlapLaunchSets, kLocalLaunchSets, kRankLaunchSets, kLaunchCounters };
+// cvh_local_planes* and of cvh_rank_planes* (window_run.hip: a Family names its counter), and the calls of cvh_split* / cvh_split_levelset*
+// with the growth sweeps that ran in them (a sweep that returned at once is not counted)
+enum LaunchCounter { kReinitLaunchSets, kPyramidLaunches, kColourLaunches, kEnergyLaunchSets, kScoreLaunchSets, kMorphLaunchSets, kOverlapLaunchSets, kLocalLaunchSets, kRankLaunchSets, kSplitLaunchSets, kSplitSweeps, kLaunchCounters };
 extern std::atomic<unsigned long> g_launches[kLaunchCounters];
 
 // io_run.hip: what every call on device memory or on a member table shares (the comments are at the definitions)
@@ -361,6 +365,15 @@ struct MaskSource {
   // the plain mask with raw_too, nothing without (the caller's own launches read the level set)
   int launch(const MemberCall &call, bool raw_too) const;
 };
+
+// floor(sqrt(r2)), exactly: the rows and columns a disk D(r2) reaches (morph_run.hip, split_run.hip)
+inline unsigned disk_root(uint32_t r2)
+{
+  unsigned long long r = (unsigned long long)sqrt((double)r2);
+  while (r * r > r2) --r;
+  while ((r + 1) * (r + 1) <= r2) ++r;
+  return (unsigned)r;
+}
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) & ~(a - 1); }
 

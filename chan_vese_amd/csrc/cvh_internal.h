@@ -417,6 +417,26 @@ hipError_t cvh_launch_morph_passes(const CvhIoMember *cols, const CvhMorphPar *p
                                    hipStream_t s);
 hipError_t cvh_launch_morph_emit(const CvhIoMember *tab, const CvhMorphPar *par, int nmem, unsigned grid, bool from_bytes, bool to_levelset,
                                  hipStream_t s);
+// object split (split_kernels.hip, whose head comment names every table's fields).  The growth's key plane is the member's plane rounded
+// up to whole tiles of CVH_SPLIT_TILE_ROWS x CVH_SPLIT_TILE_COLS 64-bit keys (the context's workspace, the padding zero); the sweeps are
+// enqueued CVH_SPLIT_GROUP at a time, sweep j reading the members' counters of slot j and adding to those of slot j + 1 (32-bit words,
+// nmem apart).  The pixel launches take sections of cvh_cc_blocks(n) workgroups, the sweeps one workgroup per tile, the emit launch
+// cvh_split_emit_blocks(n).
+#define CVH_SPLIT_TILE_ROWS 32
+#define CVH_SPLIT_TILE_COLS 64
+#define CVH_SPLIT_GROUP 4
+inline int cvh_split_tiles_y(int h) { return (h + CVH_SPLIT_TILE_ROWS - 1) / CVH_SPLIT_TILE_ROWS; }
+inline int cvh_split_tiles_x(int w) { return (w + CVH_SPLIT_TILE_COLS - 1) / CVH_SPLIT_TILE_COLS; }
+inline size_t cvh_split_workspace_bytes(int h, int w)
+{
+  return (size_t)cvh_split_tiles_y(h) * CVH_SPLIT_TILE_ROWS * (size_t)cvh_split_tiles_x(w) * CVH_SPLIT_TILE_COLS * sizeof(unsigned long long);
+}
+unsigned cvh_split_emit_blocks(size_t n);
+hipError_t cvh_launch_split_markers(const CvhIoMember *tab, int nmem, unsigned grid, hipStream_t s);
+hipError_t cvh_launch_split_keys(const CvhIoMember *tab, int nmem, unsigned grid, hipStream_t s);
+hipError_t cvh_launch_split_sweeps(const CvhIoMember *tiles, int nmem, unsigned tile_grid, int conn, int sweeps, hipStream_t s);
+hipError_t cvh_launch_split_emit(const CvhIoMember *tab, const CvhMorphPar *par, int nmem, unsigned grid, bool to_levelset, hipStream_t s);
+hipError_t cvh_launch_split_table(const CvhIoMember *tab, int nmem, unsigned grid, hipStream_t s);
 // the marching wave of the four-phase and localised step kernels (march_device.h) and what their host flows share (march_run.hip)
 #define CVH_MARCH_COLS 61       // output columns per wave: lanes 2 .. 62 (lanes 0, 1 and 63 hold the strip's halo columns)
 #define CVH_MARCH_TARGET_WAVES 4096

@@ -212,6 +212,11 @@ extern "C" unsigned long cvh_debug_score_launch_sets(void) { return g_launches[k
 // process -- one set is every launch of morph_kernels.hip (and of the cleaning) over all members of the call (tests/test_gpu_morph.py: a
 // batch of n is one set)
 extern "C" unsigned long cvh_debug_morph_launch_sets(void) { return g_launches[kMorphLaunchSets].load(); }
+// Diagnostic (not part of include/chanvese_hip.h): calls of cvh_split* / cvh_split_levelset* so far in this process (a batch of n is one), and
+// the growth sweeps that ran in them -- a sweep that returned at once behind a sweep without changes is not counted, the sweep that found
+// no change is (tests/test_gpu_split.py: the spiral takes more sweeps than a group holds)
+extern "C" unsigned long cvh_debug_split_launch_sets(void) { return g_launches[kSplitLaunchSets].load(); }
+extern "C" unsigned long cvh_debug_split_sweeps(void) { return g_launches[kSplitSweeps].load(); }
 // Diagnostic (not part of include/chanvese_hip.h): pair launches of cvh_overlaps* so far in this process -- one per call for all its
 // members, and one more each time a member's table overflowed and grew (tests/test_gpu_overlap.py: a table of 9216 pairs grows)
 extern "C" unsigned long cvh_debug_overlap_launch_sets(void) { return g_launches[kOverlapLaunchSets].load(); }

@@ -8,15 +8,6 @@
 
 namespace {
 
-// floor(sqrt(r2)), exactly
-unsigned root_of(uint32_t r2)
-{
-  unsigned long long r = (unsigned long long)sqrt((double)r2);
-  while (r * r > r2) --r;
-  while ((r + 1) * (r + 1) <= r2) ++r;
-  return (unsigned)r;
-}
-
 struct Levelset { bool write; double inside, outside; };
 
 // staging: [the mask launches' table][the column table][the emit table][one word per member for the cleaning][the members' parameters]
@@ -91,7 +82,7 @@ int morph(cvh_context *const *ctxs, int n, uint8_t *const *d_masks, const MaskSo
     if (ls.write) levelset_target(c, &e);
     else e.dst = d_masks[i];
     CvhMorphPar &p = st.par[i];
-    p.inside = ls.inside; p.outside = ls.outside; p.r2 = r2[i]; p.root = root_of(r2[i]);
+    p.inside = ls.inside; p.outside = ls.outside; p.r2 = r2[i]; p.root = disk_root(r2[i]);
   }
   // a byte mask goes to the caller's stream without a host wait, as cvh_get_mask_clean_device; a level set arrives behind ONE wait, as
   // cvh_init_rect

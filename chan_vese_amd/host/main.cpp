@@ -21,7 +21,7 @@
 // "Mask morphology") for --dump-mask, --roi, --measure, --contours and _selection; --init-mask FILE starts from a binary PGM.
 // Additions that do not collide with reference options: --dump-u, --dump-mask, --device, --math,
 // --state, --rect, --circ, --disk, --init, --threshold, --reinit, --connectivity, --min-area, --fill-holes, --largest, --roi, --verbose,
-// --levels, --energy, --energy-every, --truth, --score-tol, --measure, --contours, --contours-all, --contours-subpixel, --morph, --morph-radius, --init-mask, --truth-labels, --phases, --init2, --dump-labels, --localized (--localized R: cvh_localized_run, "Localised regions"; --phases 4: chanvese_hip.h, "Four phases" -- two contexts, cvh_multiphase_run, the labels; what does not compose with it is refused).  --truth-labels FILE
+// --levels, --energy, --energy-every, --truth, --score-tol, --measure, --contours, --contours-all, --contours-subpixel, --morph, --morph-radius, --init-mask, --truth-labels, --phases, --init2, --dump-labels, --localized, --split, --split-labels (--split R: cvh_split_levelset, "Object split", bakes a cut between touching objects in front of the mask outputs; --split-labels FILE: the labels as raw int32; both are listed by --help --verbose, the plain --help being pinned; --localized R: cvh_localized_run, "Localised regions"; --phases 4: chanvese_hip.h, "Four phases" -- two contexts, cvh_multiphase_run, the labels; what does not compose with it is refused).  --truth-labels FILE
 // relates the components of the mask --dump-mask uses (the cleaning options and -I apply) to the objects of a label image of the input's
 // size (a binary PGM with maxval <= 65535 or an 8-bit grey PNG; the values are the labels, 0 = no object) on the device (chanvese_hip.h,
 // "Component overlaps") and prints one line "objects: objects_a=... objects_b=... tp=... fp=... fn=... mean_ap=..." to stdout: the counts at
@@ -52,7 +52,8 @@
 // the finest level, before the restricts); --lambda1 / --lambda2 then weigh the luma and the two chroma planes, a start of --init otsu /
 // --threshold is taken again from the converted planes, and nothing is converted back: frames, _selection and _contour use the input.
 // The stages, in main()'s order: read_options (options.hpp), load_inputs, the parameters, then either run_four_phase or make_run,
-// the first start, the t = 0 frame, smooth_and_write_pm, convert_colour, iterate and the reports and outputs.
+// the first start, the t = 0 frame, smooth_and_write_pm, convert_colour, iterate, the reports, split_objects (--split) or the morph
+// bake, and the mask outputs.
 #include <algorithm>
 #include <cerrno>
 #include <cmath>
@@ -629,6 +630,19 @@ void print_roi(cvh_context *ctx, const Inputs &in, CleanArgs clean, const std::v
   else std::printf("roi none\n");
 }
 
+// --split R: the cleaned mask (-I applied as invert) taken apart on the device (chanvese_hip.h, "Object split").  --split-labels gets the
+// label plane, cut pixels included; then the cut is baked into the level set -- behind --dump-u, --energy and --truth, as --morph --, and
+// everything that speaks of the mask reads the split objects as a plain mask
+void split_objects(cvh_context *ctx, const Options &opt, const Inputs &in)
+{
+  if (!opt.split_labels.empty()) {
+    std::vector<int32_t> labels(in.n);
+    cvh_check(ctx, with_clean(cvh_split_host, ctx, opt.clean, opt.split_r2, labels.data(), nullptr, 0, nullptr), "cvh_split_host");
+    write_raw_or_exit(opt.split_labels, labels.data(), in.n * sizeof(int32_t));
+  }
+  cvh_check(ctx, with_clean(cvh_split_levelset, ctx, opt.clean, opt.split_r2, 1.0, -1.0), "cvh_split_levelset");
+}
+
 // Everything that speaks of the mask, for the cleaning values it is to use
 void mask_outputs(cvh_context *ctx, const Options &opt, const Inputs &in, const CleanArgs &clean, bool clean_mask)
 {
@@ -706,7 +720,10 @@ void run_two_phase(const Options &opt, Inputs &in, const cvh_params &prm)
   if (!opt.dump_u.empty()) dump_levelset(ctx, opt, in);
   // --morph: the cleaned mask (-I applied as invert), morphed, becomes the level set on the device -- behind --dump-u, --energy and
   // --truth, which speak of the run's own level set; everything below then reads the result as a plain mask
-  if (opt.morph_op != CVH_MORPH_NONE) {
+  if (opt.split) {
+    split_objects(ctx, opt, in);
+    mask_outputs(ctx, opt, in, CleanArgs{opt.clean.conn, 0, 0, 0, 0}, false);
+  } else if (opt.morph_op != CVH_MORPH_NONE) {
     cvh_check(ctx, with_clean(cvh_morph_levelset, ctx, opt.clean, opt.morph_op, opt.morph_r2, 1.0, -1.0), "cvh_morph_levelset");
     mask_outputs(ctx, opt, in, CleanArgs{opt.clean.conn, 0, 0, 0, 0}, false);
   } else {
@@ -726,7 +743,7 @@ void run_two_phase(const Options &opt, Inputs &in, const cvh_params &prm)
 int main(int argc, char **argv)
 {
   const Options opt = read_options(parse_args(argc, argv));
-  if (opt.help) { print_help(); return EXIT_SUCCESS; }
+  if (opt.help) { print_help(opt.verbose); return EXIT_SUCCESS; }
   Inputs in = load_inputs(opt);
   // ---- constants: src/main.cpp:890-895
   cvh_params prm;

@@ -40,6 +40,9 @@ const Spec kSpecs[] = {
     {"verbose", 0, 0}, {"energy", 0, 0}, {"energy-every", 0, 1}, {"truth", 0, 1}, {"score-tol", 0, 1}, {"measure", 0, 1}, {"contours", 0, 1}, {"contours-all", 0, 0}, {"contours-subpixel", 0, 0},
     {"morph", 0, 1}, {"morph-radius", 0, 1}, {"init-mask", 0, 1}, {"truth-labels", 0, 1},
     {"phases", 0, 1}, {"init2", 0, 2}, {"dump-labels", 0, 1}, {"localized", 0, 1}};
+// what came after the table above and the --help text were pinned (tests/test_cli.py, tests/golden/cli_refusals.json): long names only,
+// listed by --help --verbose
+const Spec kLaterSpecs[] = {{"split", 0, 1}, {"split-labels", 0, 1}};
 
 struct Parsed {
   std::vector<std::pair<std::string, std::vector<std::string>>> opts;
@@ -56,9 +59,13 @@ inline const Spec *find_long(const std::string &n)
 {
   const Spec *hit = nullptr;
   int hits = 0;
-  for (const Spec &s : kSpecs) {
-    if (n == s.lname) return &s;
-    if (std::string(s.lname).compare(0, n.size(), n) == 0) { hit = &s; ++hits; }  // unambiguous prefix
+  for (const Spec *table : {kSpecs, kLaterSpecs}) {
+    const size_t rows = table == kSpecs ? sizeof(kSpecs) / sizeof(Spec) : sizeof(kLaterSpecs) / sizeof(Spec);
+    for (size_t k = 0; k < rows; ++k) {
+      const Spec &s = table[k];
+      if (n == s.lname) return &s;
+      if (std::string(s.lname).compare(0, n.size(), n) == 0) { hit = &s; ++hits; }  // unambiguous prefix
+    }
   }
   return hits == 1 ? hit : nullptr;
 }
@@ -206,7 +213,7 @@ struct Options {
   uint8_t contour_bgr[3] = {255, 0, 0};            // blue
   bool segment = false, grayscale = false, video = false, overlay_text = false, select = false;
   // additions of this build
-  std::string dump_u, dump_mask, dump_planes, dump_labels, measure, contours, truth, truth_labels, init_mask;
+  std::string dump_u, dump_mask, dump_planes, dump_labels, measure, contours, truth, truth_labels, init_mask, split_labels;
   int device = 0, math_mode = CVH_MATH_FAST, state_bits = 64, reinit_every = 0, levels = 1, energy_every = 0, phases = 2, localized = 0;
   CleanArgs clean = {4, 0, 0, 0, 0};
   bool clean_mask = false;                         // a cleaning option is given: _selection, --dump-mask and --roi use the cleaned mask
@@ -220,6 +227,8 @@ struct Options {
   int colour_space = 0;                            // 0: the planes stay B, G, R
   int morph_op = CVH_MORPH_NONE;
   uint32_t morph_r2 = 1, score_tol2 = 4;           // floor(R^2) of --morph-radius and --score-tol
+  bool split = false;                              // --split R: the stage split_objects (main.cpp) bakes the cut in front of the mask outputs
+  uint32_t split_r2 = 0;                           // floor(R^2)
   bool one_plane = false;                          // the run has one plane: what the lambda counts and the threshold range follow
 
   int nof_channels() const { return grayscale ? 1 : 3; }   // planes read from the file
@@ -275,7 +284,7 @@ inline Options read_options(const Parsed &vm)
   const ReadOne read{vm};
   std::string text_position = "TL", line_color = "blue", math = "fast", rect, circ, disk, init_kind = "checkerboard", colorspace, local_name,
               rank_name, morph_name;
-  double morph_radius = 1.0, score_tol = 2.0;
+  double morph_radius = 1.0, score_tol = 2.0, split_radius = 0.0;
   int threshold = -1;
   read("input", o.input);
   read("mu", o.mu);
@@ -324,6 +333,9 @@ inline Options read_options(const Parsed &vm)
   read("score-tol", score_tol);
   read("phases", o.phases);
   read("dump-labels", o.dump_labels);
+  read("split", split_radius);
+  read("split-labels", o.split_labels);
+  o.split = given("split");
   read("localized", o.localized);   // --localized R (chanvese_hip.h, "Localised regions"): cvh_localized_run in place of cvh_run
   if (given("localized") && (o.localized < 1 || o.localized > 127))
     msg_exit("Window radius (--localized) must be between 1 and 127: " + std::to_string(o.localized) + ".");
@@ -440,7 +452,7 @@ inline Options read_options(const Parsed &vm)
         {given("colorspace"), "--colorspace"}, {!o.dump_planes.empty(), "--dump-planes"}, {!o.dump_u.empty(), "--dump-u"},
         {!o.dump_mask.empty(), "--dump-mask"}, {o.clean_mask, "the cleaning options"}, {o.roi, "--roi"}, {given("morph"), "--morph"},
         {!o.truth.empty(), "--truth"}, {!o.truth_labels.empty(), "--truth-labels"}, {!o.measure.empty(), "--measure"},
-        {!o.contours.empty(), "--contours"}, {o.clean.invert != 0, "an inverted selection (-I)"}});
+        {!o.contours.empty(), "--contours"}, {o.clean.invert != 0, "an inverted selection (-I)"}, {o.split, "an object split (--split)"}});
   if (o.localized)
     refuse_combinations("Localised regions (--localized)", {
         {o.phases == 4, "four phases (--phases 4)"}, {o.levels > 1, "a coarse-to-fine run (--levels)"}, {o.energy, "an energy line (--energy)"},
@@ -459,6 +471,11 @@ inline Options read_options(const Parsed &vm)
   if (given("morph-radius") && !given("morph")) msg_exit("A radius (--morph-radius) needs an operation (--morph).");
   if (!(morph_radius >= 0.0) || !std::isfinite(morph_radius)) msg_exit("Morphology radius must be a finite number >= 0.");
   o.morph_r2 = squared_capped(morph_radius);
+  // --split R (chanvese_hip.h, "Object split"): one level set, and the cleaned mask as it is -- a morphed mask is not split
+  if (!o.split_labels.empty() && !o.split) msg_exit("A split label file (--split-labels) needs an object split (--split).");
+  if (o.split && given("morph")) msg_exit("An object split (--split) cannot be combined with --morph.");
+  if (!(split_radius >= 0.0) || !std::isfinite(split_radius)) msg_exit("Split radius must be a finite number >= 0.");
+  o.split_r2 = squared_capped(split_radius);
   if (!o.init_mask.empty() && o.levels > 1)
     msg_exit("A mask start (--init-mask) cannot be combined with a coarse-to-fine run (--levels): a mask is not resampled.");
   if (!o.init_mask.empty() && !std::ifstream(o.init_mask).good())
@@ -472,9 +489,9 @@ inline Options read_options(const Parsed &vm)
   return o;
 }
 
-inline void print_help()
+inline void print_help(bool later = false)
 {
-  std::cout <<
+  const char *text =
       "Allowed options:\n"
       "  -h [ --help ]                      this message\n"
       "  -i [ --input ] arg                 input image (binary PGM/PPM)\n"
@@ -564,5 +581,17 @@ inline void print_help()
       "  --init-mask arg                    binary PGM of the input's size as the initial contour (+1 where it is non-zero, -1 elsewhere),\n"
       "                                     written on the device at a byte per pixel; not with --levels\n"
       "  --verbose                          print the iteration count and last norm to stderr\n"
+      "\n";
+  std::cout << text;
+  // (the list above is pinned byte for byte by tests/golden/cli_refusals.json; what came later is listed by --help --verbose)
+  if (!later) return;
+  std::cout <<
+      "Later additions:\n"
+      "  --split arg                        R >= 0: take touching objects apart on the device -- the mask --dump-mask uses (cleaning options, -I)\n"
+      "                                     is eroded by a disk of R pixels (dx^2 + dy^2 <= floor(R^2)), its cores grown back inside it, and a\n"
+      "                                     one-pixel cut baked in where two objects meet; --dump-mask, --roi, --measure, --contours,\n"
+      "                                     --truth-labels and _selection then see the split objects; not with --phases 4, --morph\n"
+      "  --split-labels arg                 write the object labels of --split (cut pixels included, 0 = background, 1 .. K in raster order of\n"
+      "                                     the cores) as raw little-endian int32 (h*w), the way --dump-u writes its raw plane\n"
       "\n";
 }

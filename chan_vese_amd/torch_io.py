@@ -535,6 +535,23 @@ class Segmenter:
         capi.morph_levelset_batch(self._phase(phase), op, radius=radius, conn=conn, invert=invert, min_area=min_area, fill_holes=fill_holes,
                                   keep_largest=keep_largest, inside=inside, outside=outside)
 
+    def split(self, radius, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False, phase=0):
+        """Touching objects taken apart (cvh_split_batch, "Object split" in include/chanvese_hip.h): every member's cleaned mask eroded by
+        a disk of `radius` pixels (one number or one per member), its cores labelled and grown back inside the mask.  Returns
+        (labels, counts): labels an int32 tensor (N, H, W) -- 0 background, 1..K one label per core, cut pixels included -- valid for the
+        next operation on the current stream, counts the K of every member.  Only reads."""
+        labels = torch.empty((self.n, self.h, self.w), dtype=torch.int32, device=torch.device("cuda", self.device))
+        counts = capi.split_batch(self._phase(phase), [labels[i].data_ptr() for i in range(self.n)], radius=radius, conn=conn, invert=invert,
+                                  min_area=min_area, fill_holes=fill_holes, keep_largest=keep_largest, stream=self._stream())
+        return labels, counts
+
+    def split_levelset(self, radius, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False, inside=1.0, outside=-1.0, phase=0):
+        """split() IN PLACE (cvh_split_levelset_batch): every member's level set becomes `inside` on the split objects and `outside` on the
+        one-pixel cut lines and the background, and a new run begins as after a fresh level set.  components(), measure(), contours(),
+        overlaps(), match() and further iterations then see the split objects."""
+        capi.split_levelset_batch(self._phase(phase), radius=radius, conn=conn, invert=invert, min_area=min_area, fill_holes=fill_holes,
+                                  keep_largest=keep_largest, inside=inside, outside=outside)
+
     def measure(self, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False, cap=None, phase=0):
         """The components of every member's mask -- clean_masks' for the same options, (0, 0, False) the raw one -- measured on the device
         (cvh_measure_batch: one set of launches, ordered behind the current stream): one (K, table) per member, table a numpy structured

@@ -1176,6 +1176,87 @@ int cvh_init_mask_device(cvh_context *ctx, const uint8_t *d_mask, double inside,
 int cvh_init_mask_device_batch(cvh_context *const *ctxs, int n, const uint8_t *const *d_masks, double inside, double outside,
                                void *stream);
 
+/* ---- Object split ---------------------------------------------------------------------------------------------------------------
+ * Take touching objects apart ON THE DEVICE: erode, label, grow back, cut.  Every object-level call here (cvh_components, cvh_measure,
+ * cvh_contours, cvh_overlaps, cvh_match_overlaps) takes one connected component for one object; where objects touch (cells, grains,
+ * droplets) the mask holds one blob for two, and what a caller otherwise does is cvh_get_mask, a distance transform, a labelling and a
+ * watershed on a CPU, and cvh_init_mask.  This is the classical "reconstruction by geodesic influence zones", not a grey-level watershed:
+ * it is defined in integers, independent of schedule and grid, so a member alone or inside any batch, and two calls in a row, give the
+ * same bytes, and every output can be compared with ==.
+ * Given (conn, invert, min_area, fill_holes, keep_largest) and r2, any uint32_t:
+ *   start set   F0 is the clean mask, exactly cvh_get_mask_clean's set; with (., invert, 0, 0, 0) it is cvh_get_mask's.  With "state" =
+ *               32 the class comes from the float state, as elsewhere;
+ *   eroded set  E = erode(F0) by the disk D(r2) of "Mask morphology": pixels outside the plane belong to neither set; r2 = 0 gives E = F0;
+ *   markers     M = E  u  { p in F0 : the conn-component of F0 that holds p has no pixel in E }.  A component the erosion wipes out stays
+ *               whole: it is its own marker, so nothing is ever lost.  The conn-components of M are numbered 1 .. K in increasing order
+ *               of their smallest flat index -- cvh_components' numbering --, m(p) is that number for a pixel p of M;
+ *   growth      for p in F0, d(p) is the length of the shortest conn-path inside F0 from p to M (d = 0 on M), and
+ *                   L(p) = m(p) on M;   L(p) = min { L(q) : q a conn-neighbour of p in F0 with d(q) = d(p) - 1 } elsewhere in F0;
+ *                   L = 0 outside F0;
+ *   fixpoint    equivalently, with key(p) = (d(p), L(p)) compared lexicographically, the keys are the unique fixpoint of
+ *                   key(p) = min(key(p), min over the conn-neighbours q of p in F0 of (d(q) + 1, L(q))),   key = (0, m(p)) fixed on M.
+ *               The operator is monotone and keys only fall from (infinity, .), so every key stays an upper bound of the fixpoint and
+ *               ANY order of relaxation -- synchronous, tile by tile, lanes racing, a neighbour's key read a sweep late -- ends in the
+ *               same bits once no relaxation changes anything.  That is what lets the kernel iterate freely;
+ *   reach       every pixel of F0 is reached: every component of F0 holds a marker;
+ *   table       row k - 1 is a cvh_component for label k: first the smallest flat index of the MARKER, area and the inclusive box those
+ *               of { p : L(p) = k }, cut pixels included;
+ *   cut         cut(p) <=> L(p) > 0 and some 8-neighbour q of p has L(q) > L(p).  One-sided, so the lines are one pixel wide.  After the
+ *               cut no two pixels of different labels are 8-adjacent: of such a pair the one with the smaller label sees a larger label
+ *               beside it and is cut.  The pieces are therefore separate under either connectivity;
+ *   unchanged   with r2 = 0, or with r2 so large that E is empty, M = F0: L is cvh_components' label plane of the clean mask and the table is
+ *               cvh_components' table; the cut is empty (but, with conn = 4, between components that touch diagonally: the rule above
+ *               holds them apart as well).  K = 0 on an all-background plane is not an error.
+ * cvh_split only READS (as cvh_components): a run continued after it is bit-identical to one without.  d_labels (h w int32 in device
+ * memory the caller owns, 4-byte aligned, the rules of "Device-memory input and output") may be NULL, and so may table (host, cap rows:
+ * the first min(K, cap)) and count (always the full K).  cvh_split_batch serves n contexts of one device, any mix of shapes and channel
+ * counts, with ONE set of launches on member 0's stream, joined with every member's stream before and after as cvh_components_batch; r2
+ * is per member (an array of n); d_labels and its entries may be NULL, counts is an array of n or NULL.  cvh_split_host writes the labels to
+ * host memory (not NULL): they are staged in the int32 plane of cvh_overlaps' host form (4 bytes per pixel, the context's) and come down
+ * behind one more wait.
+ * cvh_split_levelset[_batch] is IN PLACE: u = inside on F0 \ cut and outside elsewhere, any doubles, stored bit for bit; the context is
+ * left exactly as cvh_set_levelset of those doubles would leave it, as cvh_morph_levelset does.  After it every mask-based call --
+ * cvh_components, cvh_measure, cvh_contours, cvh_overlaps, cvh_score_mask*, cvh_reinit, further iterations -- sees the split objects.
+ * Because the cut looks at 8 neighbours whatever conn is, cvh_split_levelset(r2 = 0, conn = 4) is NOT a no-op on a mask whose
+ * 4-components touch diagonally: it cuts the smaller-labelled pixel of every such contact (with conn = 8 and r2 = 0 it changes no class).
+ * How (chan_vese_amd/csrc/split_kernels.hip): F0 as bytes (the mask kernel, or cvh_get_mask_clean's launches); the erosion pass of
+ * "Mask morphology"; the forest launches of cvh_components on F0's bytes; a flag per component "has an eroded pixel" (a vector atomic OR
+ * on the component's root) and M as bytes; the numbering launches of cvh_components on M; then the growth.  A key is 64 bits,
+ * (d << 32) | L: d < h w < 2^31 and L <= K <= 2^30 fit, so the cap is the labelling's.  A workgroup owns a tile of 32 x 64 keys plus a
+ * one-pixel halo in LDS, relaxes it until it is stable, stores the keys that fell and adds their number to the member's counter; a
+ * launch is one such sweep over all tiles of all members; no workgroup waits for another.  Sweeps are enqueued in groups of 4
+ * (cvh_split_geometry): a sweep of a member whose sweep before changed nothing returns at once, and the host reads the counters once
+ * per group.  One launch then takes the cut and writes labels or level-set doubles in 16-byte pieces; the single form's table is two
+ * more launches on L.
+ * Host waits: ceil(sweeps / 4), the first of which also brings the counts, and ONE more behind the outputs (labels, rows or level set;
+ * none where only counts are asked for) -- cvh_components' one or two, plus the groups.  sweeps is 1 + the number of tile seams the
+ * longest growth path crosses, give or take what racing workgroups pass on within a sweep: 4 to 6 in the fields measured below.   
+ * Memory: 8 bytes per pixel of the plane rounded up to whole tiles (the keys), allocated by a context's first call and kept until
+ * cvh_destroy, beside the morphology workspace (3.25 bytes per pixel) and the components workspace (8 bytes per pixel), which the calls
+ * share with those families.  cvh_create allocates none of it.
+ * The result depends on the radius: too small splits nothing, too large erodes small objects away (they stay whole), and in between a
+ * neck can leave a spurious sliver as a core of its own (README.md shows one).  The radius is the caller's choice; nothing here picks it.
+ * Cost, one run of tools/split_probe.py on an MI355X (host clock around a call with a label plane, a full table and its
+ * waits, 20 calls, measured once): a field of touching disks built so that every case splits, R = 4 / 16 / 64: 1.5 / 1.3 / 3.0 ms at 1024^2,
+ * 2.2 / 1.9 / 3.5 ms at 2048^2, 5.9 / 4.8 / 6.9 ms at 4096^2 with 4 to 6 sweeps; a speckled mask with nothing to grow 0.88 / 2.96 / 10.7 ms
+ * beside 0.77 / 2.74 / 9.9 ms for cvh_components with its table.  cvh_get_mask + the numpy restatement + cvh_init_mask took 65 - 3458 ms at
+ * 1024^2 for the same labels.
+ * CVH_ERR_ARG: what cvh_get_mask_clean refuses for conn, min_area, fill_holes and keep_largest; a NULL r2 list; a negative cap; a label
+ * pointer that is not device-accessible memory of the context's device or not 4-byte aligned; h^2 + w^2 >= 2^32 or h w >= 2^31; ctxs
+ * NULL, n < 1, a NULL or duplicate member, members on different devices.  CVH_ERR_STATE: a member without a level set.  Checked for every
+ * member before anything is launched; the message names the member index and is cvh_last_error(NULL)'s and member 0's. */
+int cvh_split(cvh_context *ctx, int conn, int invert, long min_area, long fill_holes, int keep_largest, uint32_t r2, int32_t *d_labels,
+              cvh_component *table, int cap, int *count, void *stream);
+int cvh_split_host(cvh_context *ctx, int conn, int invert, long min_area, long fill_holes, int keep_largest, uint32_t r2, int32_t *labels,
+                   cvh_component *table, int cap, int *count);   /* host labels */
+int cvh_split_batch(cvh_context *const *ctxs, int n, int conn, int invert, long min_area, long fill_holes, int keep_largest,
+                    const uint32_t *r2, int32_t *const *d_labels, int *counts, void *stream);
+int cvh_split_levelset(cvh_context *ctx, int conn, int invert, long min_area, long fill_holes, int keep_largest, uint32_t r2,
+                       double inside, double outside);
+int cvh_split_levelset_batch(cvh_context *const *ctxs, int n, int conn, int invert, long min_area, long fill_holes, int keep_largest,
+                             const uint32_t *r2, double inside, double outside);
+void cvh_split_geometry(int *tile_rows, int *tile_cols, int *group);   /* pure host arithmetic: the growth's tile and the sweeps per group */
+
 /* ---- Four phases ----------------------------------------------------------------------------------------------------------------
  * Vese and Chan's multiphase model: TWO level sets evolved together, whose sign pairs name four regions -- what an image with three or
  * four grey classes needs and one level set cannot give.  A PAIR is two contexts A and B on one device with the same h, w and channel
