@@ -48,8 +48,8 @@ EXPORTS = [
     "cvh_get_mask_morph", "cvh_get_mask_morph_device", "cvh_get_mask_morph_device_batch", "cvh_morph_levelset", "cvh_morph_levelset_batch",
     "cvh_init_mask", "cvh_init_mask_device", "cvh_init_mask_device_batch",
     "cvh_split", "cvh_split_host", "cvh_split_batch", "cvh_split_levelset", "cvh_split_levelset_batch", "cvh_split_geometry",
-    "cvh_multiphase_run", "cvh_multiphase_means", "cvh_multiphase_labels", "cvh_multiphase_labels_device", "cvh_multiphase_geometry",
-    "cvh_localized_run", "cvh_localized_means", "cvh_localized_geometry",
+    "cvh_multiphase_run", "cvh_multiphase_run_batch", "cvh_multiphase_means", "cvh_multiphase_labels", "cvh_multiphase_labels_device", "cvh_multiphase_geometry",
+    "cvh_localized_run", "cvh_localized_run_batch", "cvh_localized_means", "cvh_localized_geometry",
 ]
 # "Mask morphology": the operations of cvh_get_mask_morph* / cvh_morph_levelset*, by code and by name
 MORPH_NONE, MORPH_DILATE, MORPH_ERODE, MORPH_OPEN, MORPH_CLOSE = 0, 1, 2, 3, 4
@@ -386,11 +386,13 @@ def lib():
                                                C.c_double, C.c_double]),
         "cvh_split_geometry": (None, [ip, ip, ip]),
         "cvh_multiphase_run": (C.c_int, [vp, vp, C.c_int, ip, dp, dp, C.c_int, ip]),
+        "cvh_multiphase_run_batch": (C.c_int, [vp, vp, C.c_int, C.c_int, ip, dp, vp, C.c_int, ip]),
         "cvh_multiphase_means": (C.c_int, [vp, vp, dp]),
         "cvh_multiphase_labels": (C.c_int, [vp, vp, u8p]),
         "cvh_multiphase_labels_device": (C.c_int, [vp, vp, vp, vp]),
         "cvh_multiphase_geometry": (None, [C.c_int, C.c_int, ip, ip, ip]),
         "cvh_localized_run": (C.c_int, [vp, C.c_int, C.c_int, ip, dp, dp, C.c_int, ip]),
+        "cvh_localized_run_batch": (C.c_int, [vp, C.c_int, ip, C.c_int, ip, dp, vp, C.c_int, ip]),
         "cvh_localized_means": (C.c_int, [vp, C.c_int, dp, dp, vp, vp, vp]),
         "cvh_localized_geometry": (None, [C.c_int, C.c_int, C.c_int, ip, ip, ip, ip]),
     }
@@ -1179,6 +1181,33 @@ def multiphase_run(a, b, max_steps=-1, trace=False):
     return done.value, (norms[0], norms[1]), None if out is None else out[:rows.value].copy()
 
 
+def _trace_rows_wanted(max_steps, trace):
+    want = 0 if trace is False or trace is None else (int(max_steps) if trace is True else int(trace))
+    if want < 0:
+        raise ValueError("trace=True needs max_steps >= 0 (or pass the number of rows)")
+    return want
+
+
+def multiphase_run_batch(pairs, max_steps=-1, trace=False):
+    """cvh_multiphase_run_batch: multiphase_run for every pair (a, b) of `pairs` at once -- per iteration one step launch and one
+    finalise launch for all pairs of a (channel count, math mode) class.  Every pair iterates and stops on its own and is bit for bit
+    what multiphase_run gives for it alone.  Returns a list of (steps_done, (norm1, norm2), trace), one per pair; trace as there."""
+    pairs = [tuple(p) for p in pairs]
+    n = len(pairs)
+    if n == 0:
+        raise ValueError("multiphase_run_batch: no pairs")
+    if any(len(p) != 2 for p in pairs):
+        raise ValueError("multiphase_run_batch: every member is a pair (a, b) of contexts")
+    want = _trace_rows_wanted(max_steps, trace)
+    wanted = bool(want) or trace is True
+    done, rows, norms = (C.c_int * n)(), (C.c_int * n)(), (C.c_double * (2 * n))()
+    outs = [np.zeros((max(want, 1), 4 * a.channels + 2), dtype=np.float64) for a, _ in pairs] if wanted else None
+    traces = (C.c_void_p * n)(*[o.ctypes.data for o in outs]) if wanted else None
+    _batch_chk(lib().cvh_multiphase_run_batch(_member_array([a for a, _ in pairs]), _member_array([b for _, b in pairs]), n, int(max_steps), done, norms,
+                                              traces, want, rows))
+    return [(done[i], (norms[2 * i], norms[2 * i + 1]), outs[i][:rows[i]].copy() if wanted else None) for i in range(n)]
+
+
 def multiphase_means(a, b):
     """cvh_multiphase_means: the means of the current pair as an array of (4, C), rows c11, c10, c01, c00.  Only reads."""
     c = np.zeros((4, a.channels), dtype=np.float64)
@@ -1209,6 +1238,27 @@ def localized_run(ctx, radius, max_steps=-1, trace=False):
     ctx._chk(lib().cvh_localized_run(ctx._h, int(radius), int(max_steps), C.byref(done), C.byref(norm), None if out is None else _dp(out), want,
                                      C.byref(rows)))
     return done.value, norm.value, None if out is None else out[:rows.value].copy()
+
+
+def localized_run_batch(contexts, radius, max_steps=-1, trace=False):
+    """cvh_localized_run_batch: localized_run for every context at once -- per iteration one row-pass, one step and one finalise launch
+    for all members of a (channel count, math mode) class.  radius is an int (the same for every member) or a sequence of one value per
+    member.  Every member iterates and stops on its own and is bit for bit what localized_run gives for it alone.  Returns a list of
+    (steps_done, norm, trace), one per member; trace as there."""
+    contexts = list(contexts)
+    n = len(contexts)
+    if n == 0:
+        raise ValueError("localized_run_batch: no members")
+    radii = [int(r) for r in radius] if np.ndim(radius) else [int(radius)] * n
+    if len(radii) != n:
+        raise ValueError(f"radius: {len(radii)} values for {n} members")
+    want = _trace_rows_wanted(max_steps, trace)
+    wanted = bool(want) or trace is True
+    done, rows, norms = (C.c_int * n)(), (C.c_int * n)(), (C.c_double * n)()
+    outs = [np.zeros(max(want, 1), dtype=np.float64) for _ in contexts] if wanted else None
+    traces = (C.c_void_p * n)(*[o.ctypes.data for o in outs]) if wanted else None
+    _batch_chk(lib().cvh_localized_run_batch(_member_array(contexts), n, (C.c_int * n)(*radii), int(max_steps), done, norms, traces, want, rows))
+    return [(done[i], norms[i], outs[i][:rows[i]].copy() if wanted else None) for i in range(n)]
 
 
 def run_monitored(ctx, max_steps=-1, every=16, rel_plateau=None):

@@ -158,6 +158,8 @@ extern "C" void cvh_destroy(cvh_context *c)
   free_table(&c->mp_trace);
   if (c->d_localized) (void)hipFree(c->d_localized);
   free_table(&c->loc_trace);
+  free_table(&c->march_table);
+  if (c->h_march) (void)hipHostFree(c->h_march);
   if (c->ev_io_in) (void)hipEventDestroy(c->ev_io_in);
   if (c->ev_io_out) (void)hipEventDestroy(c->ev_io_out);
   if (c->h_resident) (void)hipHostFree(c->h_resident);

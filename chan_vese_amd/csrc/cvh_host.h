@@ -193,6 +193,9 @@ struct cvh_context {   // opaque to callers; four groups
   void *d_localized = nullptr;   // workspace of cvh_localized_* (localized_run.hip): state block, the items' partial sums, the 1 + C planes of
                                  // horizontal window sums and the C planes of T_k: (8 + 12 C) bytes per pixel, allocated by the first call, kept
   DeviceTable loc_trace;         // and the trace rows of the longest cvh_localized_run so far that asked for them, grown on demand, kept
+  DeviceTable march_table;       // four-phase / localised calls led by this context (march_run.hip): the members' argument records and their
+  void *h_march = nullptr;       // state table; h_march: its pinned host image and the landing place of the states, h_march_cap bytes --
+  size_t h_march_cap = 0;        // grown on demand, kept
   int coop_launch = -1;          // does the device launch cooperatively (-1: not asked yet; launches_cooperatively)
   int resident_cap = -1;         // workgroups of csv_resident_kernel the device holds at once (-1: not asked yet, 0: unavailable)
   int pm_resident_cap = -1;      // workgroups of pm_resident_kernel the device holds at once (-1: not asked yet)
@@ -324,23 +327,51 @@ int ensure_workspace(cvh_context *c, void **slot, size_t bytes, const char *name
 // march_run.hip: what the four-phase and localised flows share -- "iterate the level sets of N contexts on the leader's stream"
 void fill_front_args(const cvh_context *c, CvhFrontArgs *f);
 int state_down(cvh_context *a, const void *d_state, void *out, size_t bytes);   // on a's stream, through its pinned state slots; waits
-// One run of n = 1 or 2 contexts (leader ctxs[0]; names[e] is member e's letter in a message).  The caller has checked the members; then
-//   begin:   refuses a trace's bad arguments, settles max_steps;                 -- the caller makes the members and its workspace ready --
-//   open:    grows the trace table to the rows wanted, opens the call;           -- the caller fills its arguments, enqueues what precedes t = 0 --
-//   iterate: times the run, enqueues sync_every iterations at a time through step(in, out) and reads the state block -- which begins
-//            with a CvhMarchCount -- behind each chunk (its only wait per chunk); then brings every level set into the buffer a new one
-//            lands in (at most ONE copy each, by the parity of steps_done), does the device's half of a new run, copies the trace rows
-//            out, closes the call, waits, and books the level sets as arrived.
+// The leader's table of a call: *h is `host_bytes` of zeroed pinned memory whose first `dev_bytes` the caller uploads to *d.  Every call
+// that uses it ends with a host wait on the leader's stream, so the pinned block is free when the next one begins.
+int march_stage(cvh_context *lead, size_t dev_bytes, size_t host_bytes, unsigned char **h, unsigned char **d);
+// One run of n members of `per` contexts each (1: a localised member; 2: a four-phase pair A, B); ctxs is flat, [member][role], the
+// leader is ctxs[0]; who(k) opens what a message says about context k ("", "context a: ", "member 3: ", ...).  The caller has checked
+// the members; then
+//   begin:   refuses a trace's bad arguments, settles max_steps;                 -- the caller makes the members and their workspaces ready --
+//   open:    grows every member's own trace table to the rows wanted, stages the leader's table -- [n records of rec_size bytes][n state
+//            slots of state_stride bytes, each beginning with a CvhMarchCount] -- and opens the call;
+//                                                                               -- the caller fills the records (record, d_state, cur) --
+//   upload:  the table goes up, ONCE per call;                                   -- the caller enqueues what precedes t = 0 --
+//   iterate: times the run, enqueues the leader's sync_every iterations at a time through step(parity) -- iteration t has parity t & 1 and
+//            reads buffer (cur + t) & 1 of every context -- and copies the state table (own_state, if set) down behind each chunk: ONE copy and ONE wait per
+//            chunk, whatever n; ends when every member has stopped or max_steps iterations are enqueued.  Then it brings every level set
+//            into the buffer a new one lands in (at most ONE copy each, by the parity of the member's own steps_done), does the device's
+//            half of a new run, copies the trace rows out, closes the call, waits, and books the level sets as arrived.  state(i) is
+//            member i's state afterwards.
 struct MarchRun {
-  cvh_context *const *ctxs; int n; const char *what, *names;
-  int max_steps = 0, trace_cap = 0, nrows = 0;
-  double *trace = nullptr, *d_trace = nullptr;
-  int *rows = nullptr;
-  int begin(int max_steps, double *trace, int trace_rows, int *rows);
-  int open(DeviceTable *table, int row_width);
-  int iterate(const void *d_state, void *st, size_t state_bytes, const std::function<int(const double *const *in, double *const *out)> &step);
-  DeviceTable *table = nullptr; int row_width = 0;   // (open's)
+  cvh_context *const *ctxs; int n, per; const char *what;
+  std::function<std::string(int)> who;
+  int max_steps = 0;
+  double *const *traces = nullptr;
+  int trace_rows = 0, *rows = nullptr;
+  std::vector<int> trace_cap, row_width, cur;   // per member, per member, per context
+  std::vector<double *> d_trace;                // per member: its own table, or null
+  unsigned char *h_tab = nullptr, *d_tab = nullptr;
+  size_t rec_size = 0, state_off = 0, state_stride = 0, dev_bytes = 0, land_off = 0;
+  const void *own_state = nullptr;   // n == 1, launches by value: the member's own state block, which comes down in place of the table's slot
+
+  int begin(int max_steps, double *const *traces, int trace_rows, int *rows);
+  int open(const std::function<DeviceTable *(int)> &table_of, const std::function<int(int)> &width_of, size_t rec_size, size_t state_stride);
+  void *record(int r) const { return h_tab + (size_t)r * rec_size; }
+  const void *d_record(int r) const { return d_tab + (size_t)r * rec_size; }
+  void *d_state(int i) const { return d_tab + state_off + (size_t)i * state_stride; }
+  const void *state(int i) const { return h_tab + land_off + (size_t)i * state_stride; }
+  int upload();
+  int iterate(const std::function<int(int parity)> &step);
 };
+
+// the (channel count, math mode) classes of a march launch: members of one class share a kernel instantiation and a section of the table
+constexpr int kMarchClasses = 4;
+inline int march_class(const cvh_context *c) { return (c->C == 1 ? 0 : 2) + (use_fast(c) ? 1 : 0); }
+struct MarchClass { int first = 0, n = 0, C = 1, fast = 0; unsigned grid = 0, grid2 = 0; };   // records first .. first + n - 1; the sums of their grids
+// order[r]: the member record r describes -- members sorted by class, in member order inside a class; cls[k]: class k's section
+void march_classes(cvh_context *const *leaders, int n, int stride, std::vector<int> *order, MarchClass *cls);
 
 // components_run.hip: the mask of every member that a call starts from -- raw, or cleaned as cvh_get_mask_clean* cleans it -- for the
 // components calls there and for measure_run.hip, overlap_run.hip, contour_run.hip and morph_run.hip.  The first member table of such a

@@ -474,11 +474,13 @@ struct CvhMpState {
   double c[4][CVH_MAX_CHANNELS];   // c11, c10, c01, c00: the means of the current pair, read by the next iteration
   double norm[2];                  // ||d1||_2, ||d2||_2 of the last executed iteration
 };
+// A member (pair) of a four-phase launch: the kernels read a device table of these records (constant address space: a wave-uniform
+// record comes in scalar loads, as a by-value kernel argument does), a workgroup finds its record through `first`, the prefix block
+// counts of the step grid.  A launch of parity p reads u[e][p] and writes u[e][p ^ 1]: the table is uploaded once per call.
 struct CvhMpArgs {
-  const double *in[2];             // phi1, phi2 read
-  double *out[2];                  // phi1, phi2 written (sums pass: unused)
+  double *u[2][2];                 // [parity][phi1, phi2]: both buffers of both level sets (by value: u[0] read, u[1] written)
   const uint8_t *img[CVH_MAX_CHANNELS];
-  CvhMpState *st;
+  CvhMpState *st;                  // the pair's own state block (A's workspace)
   double *partials;                // [nitems][cvh_mp_nsums(C)]
   double *trace;                   // [trace_cap][4C + 2] or null
   int trace_cap;
@@ -488,10 +490,15 @@ struct CvhMpArgs {
   double lambda1[2][CVH_MAX_CHANNELS], lambda2[2][CVH_MAX_CHANNELS];
   CvhFrontArgs f;
   double stop[2];                              // what cvh_get_stop_condition returns for A and for B
+  // what the table form alone reads, behind everything the by-value form shares with it (whose kernel arguments stay laid out as they were)
+  CvhMpState *st_mirror;           // the pair's slot of the leader's contiguous state table: what the host reads, ONE copy for all members
+  unsigned first;                  // workgroups of the step grid in front of this member's
 };
-hipError_t cvh_launch_mp_sums(const CvhMpArgs &a, int channels, int fast, hipStream_t s);      // the sums of in[] into partials
-hipError_t cvh_launch_mp_step(const CvhMpArgs &a, int channels, int fast, hipStream_t s);      // one iteration, and the sums of out[]
-hipError_t cvh_launch_mp_finalize(const CvhMpArgs &a, int channels, int is_init, hipStream_t s);
+// tab[0 .. nmem-1]: the members of ONE (channel count, math mode) class; grid: the sum of their step grids.  one (a HOST record,
+// first = 0) non-null: the call has one member, whose record travels by value instead -- the single calls' launch
+hipError_t cvh_launch_mp_sums(const CvhMpArgs *tab, int nmem, unsigned grid, int parity, int channels, int fast, hipStream_t s, const CvhMpArgs *one);   // the sums of u[.][parity] into partials
+hipError_t cvh_launch_mp_step(const CvhMpArgs *tab, int nmem, unsigned grid, int parity, int channels, int fast, hipStream_t s, const CvhMpArgs *one);   // one iteration, and the sums of what it wrote
+hipError_t cvh_launch_mp_finalize(const CvhMpArgs *tab, int nmem, int channels, int is_init, hipStream_t s, const CvhMpArgs *one);                      // a workgroup per member
 // labels: one member; src phi1, src2 phi2, dst the bytes (any alignment), sections of cvh_io_blocks(n) workgroups
 hipError_t cvh_launch_mp_labels(const CvhIoMember *tab, int nmem, unsigned grid, hipStream_t s);
 // localised regions (localized_kernels.hip; include/chanvese_hip.h, "Localised regions").  Per iteration a ROW pass (a workgroup per row
@@ -510,11 +517,12 @@ struct CvhLocState {
   CvhMarchCount run;
   double norm;                     // ||d||_2 of the last executed iteration
 };
+// A member of a localised launch: a record of the device table the kernels read (as CvhMpArgs above).  row_first / wave_first: the
+// prefix block counts of the row pass's and the wave kernel's grids.  A launch of parity p reads u[p] and (step) writes u[p ^ 1].
 struct CvhLocArgs {
-  const double *in;                // u read
-  double *out;                     // u written (step alone)
+  double *u[2];                    // both buffers of the level set
   const uint8_t *img[CVH_MAX_CHANNELS];
-  CvhLocState *st;
+  CvhLocState *st;                 // the member's own state block (its workspace)
   double *partials;                // [nitems]
   unsigned long long *hw;          // [1 + C][h][w]: horizontal window sums of wq, wq f_k (plane-sum pass: of 1, f_k)
   unsigned *tsum;                  // [C][h][w]: T_k, the window sums of f_k
@@ -529,12 +537,17 @@ struct CvhLocArgs {
   // cvh_localized_means: device planes or null
   unsigned long long *wq_out, *a_out, *s_out;
   double *c1_out, *c2_out;
+  // what the table form alone reads, behind everything the by-value form shares with it (whose kernel arguments stay laid out as they were)
+  CvhLocState *st_mirror;          // the member's slot of the leader's contiguous state table: what the host reads, ONE copy for all members
+  unsigned row_first, wave_first;  // workgroups of the row pass's / the wave kernel's grid in front of this member's
 };
 enum { CVH_LOC_STEP = 0, CVH_LOC_MEANS = 1, CVH_LOC_TSUM = 2 };
-// the row pass that goes with the wave kernel of kind `pass`: STEP reads the run's stop flag, MEANS does not, TSUM has wq = 1 (the plane sums)
-hipError_t cvh_launch_loc_rows(const CvhLocArgs &a, int channels, int fast, int pass, hipStream_t s);
-hipError_t cvh_launch_loc_wave(const CvhLocArgs &a, int channels, int fast, int kind, hipStream_t s);
-hipError_t cvh_launch_loc_finalize(const CvhLocArgs &a, hipStream_t s);
+// tab[0 .. nmem-1]: the members of ONE (channel count, math mode) class; grid: the sum of their grids of that kernel.
+// The row pass that goes with the wave kernel of kind `pass`: STEP reads the run's stop flag, MEANS does not, TSUM has wq = 1 (the plane sums)
+// one (a HOST record, row_first = wave_first = 0) non-null: the call has one member, whose record travels by value instead (as above)
+hipError_t cvh_launch_loc_rows(const CvhLocArgs *tab, int nmem, unsigned grid, int parity, int channels, int fast, int pass, hipStream_t s, const CvhLocArgs *one);
+hipError_t cvh_launch_loc_wave(const CvhLocArgs *tab, int nmem, unsigned grid, int parity, int channels, int fast, int kind, hipStream_t s, const CvhLocArgs *one);
+hipError_t cvh_launch_loc_finalize(const CvhLocArgs *tab, int nmem, hipStream_t s, const CvhLocArgs *one);   // a workgroup per member
 // rows-per-tile options of the step kernel
 void cvh_step_grid(int h, int w, int tile_rows, int *tiles_x, int *tiles_y);
 int cvh_step_max_blocks(int h, int w);

@@ -44,8 +44,8 @@ static_assert((1 + CVH_MAX_CHANNELS) * (kSpanMax + 1) * 8 + (CVH_ATAN2_N + 1) * 
 
 // wq of a pixel: a function of its stored double alone.  FAST: wave_math.h's far-field series from the threshold on, its table form below
 // (per PIXEL, where the four-phase kernel votes per wave row: a pixel in two segments' spans must give the same wq in both)
-template <bool FAST>
-__device__ __forceinline__ unsigned long long weight_of(double x, const CvhFrontArgs &a, const FarCoef &fc, const double *satan)
+template <bool FAST, class F>
+__device__ __forceinline__ unsigned long long weight_of(double x, const F &a, const FarCoef &fc, const double *satan)
 {
   double H;
   if (!FAST) H = heaviside_strict(x, a.eps);
@@ -55,10 +55,17 @@ __device__ __forceinline__ unsigned long long weight_of(double x, const CvhFront
 }
 
 // MODE 0: STRICT, 1: FAST, 2: wq = 1 (the sums of the planes alone, for T_k).  IN_RUN: a launch of an iteration of cvh_localized_run, which
-// returns where the run's stop flag is set; the other launches (T_k, cvh_localized_means) do not read the state block at all
-template <int C, int MODE, bool IN_RUN>
-__global__ __launch_bounds__(CVH_BLOCK) void loc_row_kernel(const CvhLocArgs a)
+// returns where the member's stop flag is set; the other launches (T_k, cvh_localized_means) do not read the state block at all.
+// tab: the members of the launch; a workgroup finds its own through the prefix block counts row_first
+typedef const CVH_CONSTANT CvhLocArgs *loc_table;
+
+// (Rec: a CvhLocArgs in the constant address space -- a record of the table -- or the by-value argument of the one-member entry point)
+// TABLE: the record is one of a table's -- the member's workgroups lie behind `first` others, the buffer read is u[parity].  Else the
+// launch is the member's alone, reads u[0] and writes u[1] (the host swaps them per iteration): the parent single-call kernel
+template <int C, int MODE, bool IN_RUN, bool TABLE, class Rec>
+__device__ __forceinline__ void loc_row_body(const Rec &a, int parity)
 {
+  const unsigned blk = TABLE ? blockIdx.x - a.row_first : blockIdx.x;
   constexpr int NQ = 1 + C;
   __shared__ unsigned long long pre[NQ][kSpanMax + 1];   // pre[q][i]: the sum of the span's first i entries
   __shared__ unsigned long long wtot[NQ][CVH_BLOCK / 64];
@@ -67,13 +74,13 @@ __global__ __launch_bounds__(CVH_BLOCK) void loc_row_kernel(const CvhLocArgs a)
   if (MODE == 1) stage_atan2(satan, a.f);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int h = a.h, w = a.w, R = a.radius;
-  const int r = (int)(blockIdx.x / (unsigned)a.g.nseg), seg = (int)(blockIdx.x % (unsigned)a.g.nseg);
+  const int r = (int)(blk / (unsigned)a.g.nseg), seg = (int)(blk % (unsigned)a.g.nseg);
   if (r >= h) return;
   const int c0 = seg * kSeg, cend = min(c0 + kSeg, w);
   const int first = max(c0 - R, 0), last = min(cend - 1 + R, w - 1), len = last - first + 1;   // len <= kSpanMax
   const FarCoef fc = far_coef_of(a.f);
   const size_t row = (size_t)r * w, n = (size_t)h * w;
-  const gdoubles_in in = (gdoubles_in)a.in;
+  const gdoubles_in in = (gdoubles_in)(TABLE && parity ? a.u[1] : a.u[0]);
   const gbytes_in plane[CVH_MAX_CHANNELS] = {(gbytes_in)a.img[0], (gbytes_in)a.img[1], (gbytes_in)a.img[2]};
 
   unsigned long long v[NQ][kPer];
@@ -128,14 +135,28 @@ __global__ __launch_bounds__(CVH_BLOCK) void loc_row_kernel(const CvhLocArgs a)
   }
 }
 
-template <int C, bool FAST, int KIND>
-__global__ __launch_bounds__(CVH_BLOCK) void loc_wave_kernel(const CvhLocArgs a)
+template <int C, int MODE, bool IN_RUN>
+__global__ __launch_bounds__(CVH_BLOCK) void loc_row_kernel(const CvhLocArgs *tab, int nmem, int parity)
+{
+  loc_row_body<C, MODE, IN_RUN, true>(((loc_table)tab)[march_member((loc_table)tab, nmem, [](const CVH_CONSTANT CvhLocArgs &m) { return m.row_first; })], parity);
+}
+
+// ONE member, its record by value: what a call with one member launches -- the single call's kernel as it was before the batch
+// existed (reads u[0], writes u[1], no prefix count, no mirror of the state block)
+template <int C, int MODE, bool IN_RUN>
+__global__ __launch_bounds__(CVH_BLOCK) void loc_row_kernel_one(const CvhLocArgs a)
+{
+  loc_row_body<C, MODE, IN_RUN, false>(a, 0);
+}
+
+template <int C, bool FAST, int KIND, bool TABLE, class Rec>
+__device__ __forceinline__ void loc_wave_body(const Rec &a, int parity)
 {
   constexpr int NQ = 1 + C;
   constexpr bool STEP = KIND == CVH_LOC_STEP, TSUM = KIND == CVH_LOC_TSUM;
   if (STEP && a.st->run.stopped) return;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const long long witem = (long long)blockIdx.x * (CVH_BLOCK / 64) + wave;
+  const long long witem = (long long)(TABLE ? blockIdx.x - a.wave_first : blockIdx.x) * (CVH_BLOCK / 64) + wave;
   if (witem >= (long long)a.g.nstrips * a.g.nwc) return;
   const int h = a.h, w = a.w, R = a.radius;
   const MarchLane ml = march_lane(witem, a.g.nwc, a.g.strip_rows, h, w);
@@ -143,8 +164,8 @@ __global__ __launch_bounds__(CVH_BLOCK) void loc_wave_kernel(const CvhLocArgs a)
   const bool lane_valid = ml.valid;
   const size_t n = (size_t)h * w;
   const double eps = a.f.eps, eps2 = eps * eps;
-  const gdoubles_in in = (gdoubles_in)a.in;
-  const gdoubles_out out = (gdoubles_out)a.out;
+  const gdoubles_in in = (gdoubles_in)(TABLE && parity ? a.u[1] : a.u[0]);
+  const gdoubles_out out = (gdoubles_out)(TABLE && parity ? a.u[0] : a.u[1]);
   const gu64_in hw = (gu64_in)a.hw;
   const gbytes_in plane[CVH_MAX_CHANNELS] = {(gbytes_in)a.img[0], (gbytes_in)a.img[1], (gbytes_in)a.img[2]};
   const int ncols = min(colc + R, w - 1) - max(colc - R, 0) + 1;
@@ -239,8 +260,22 @@ __global__ __launch_bounds__(CVH_BLOCK) void loc_wave_kernel(const CvhLocArgs a)
   }
 }
 
-// ONE workgroup: thread t adds items t, t + 256, ... in that order, block_reduce's fixed tree adds the threads; thread 0 writes the state
-__global__ __launch_bounds__(CVH_BLOCK) void loc_finalize_kernel(const CvhLocArgs a)
+template <int C, bool FAST, int KIND>
+__global__ __launch_bounds__(CVH_BLOCK) void loc_wave_kernel(const CvhLocArgs *tab, int nmem, int parity)
+{
+  loc_wave_body<C, FAST, KIND, true>(((loc_table)tab)[march_member((loc_table)tab, nmem, [](const CVH_CONSTANT CvhLocArgs &m) { return m.wave_first; })], parity);
+}
+
+template <int C, bool FAST, int KIND>
+__global__ __launch_bounds__(CVH_BLOCK) void loc_wave_kernel_one(const CvhLocArgs a)
+{
+  loc_wave_body<C, FAST, KIND, false>(a, 0);
+}
+
+// ONE workgroup per member: thread t adds items t, t + 256, ... in that order, block_reduce's fixed tree adds the threads; thread 0 writes
+// the member's state block and (TABLE) its mirror in the leader's state table
+template <bool TABLE, class Rec>
+__device__ __forceinline__ void loc_finalize_body(const Rec &a)
 {
   __shared__ double sred[4];
   CvhLocState *st = a.st;
@@ -252,32 +287,58 @@ __global__ __launch_bounds__(CVH_BLOCK) void loc_finalize_kernel(const CvhLocArg
   const double nrm = sqrt(total);
   const int t = st->run.steps_done;   // index of the iteration just executed
   if (a.trace && t < a.trace_cap) a.trace[t] = nrm;
+  const int stopped = nrm <= a.stop ? 1 : 0;   // after the update
   st->norm = nrm;
   st->run.steps_done = t + 1;
-  if (nrm <= a.stop) st->run.stopped = 1;   // after the update
+  if (stopped) st->run.stopped = 1;
+  if (TABLE) {
+    CvhLocState *mirror = a.st_mirror;
+    mirror->norm = nrm;
+    mirror->run.steps_done = t + 1;
+    mirror->run.stopped = stopped;
+  }
 }
 
+__global__ __launch_bounds__(CVH_BLOCK) void loc_finalize_kernel(const CvhLocArgs *tab) { loc_finalize_body<true>(((loc_table)tab)[blockIdx.x]); }
+__global__ __launch_bounds__(CVH_BLOCK) void loc_finalize_kernel_one(const CvhLocArgs a) { loc_finalize_body<false>(a); }
+
 template <int C>
-hipError_t launch_wave(const CvhLocArgs &a, int fast, int kind, hipStream_t s)
+hipError_t launch_wave(const CvhLocArgs *tab, int nmem, unsigned grid_, int parity, int fast, int kind, hipStream_t s, const CvhLocArgs *one)
 {
-  const dim3 grid(a.g.grid), block(CVH_BLOCK);
-  if (kind == CVH_LOC_TSUM) hipLaunchKernelGGL((loc_wave_kernel<C, false, CVH_LOC_TSUM>), grid, block, 0, s, a);
-  else if (kind == CVH_LOC_MEANS) hipLaunchKernelGGL((loc_wave_kernel<C, false, CVH_LOC_MEANS>), grid, block, 0, s, a);
-  else if (fast) hipLaunchKernelGGL((loc_wave_kernel<C, true, CVH_LOC_STEP>), grid, block, 0, s, a);
-  else hipLaunchKernelGGL((loc_wave_kernel<C, false, CVH_LOC_STEP>), grid, block, 0, s, a);
+  const dim3 grid(grid_), block(CVH_BLOCK);
+  if (one) {
+    if (kind == CVH_LOC_TSUM) hipLaunchKernelGGL((loc_wave_kernel_one<C, false, CVH_LOC_TSUM>), grid, block, 0, s, *one);
+    else if (kind == CVH_LOC_MEANS) hipLaunchKernelGGL((loc_wave_kernel_one<C, false, CVH_LOC_MEANS>), grid, block, 0, s, *one);
+    else if (fast) hipLaunchKernelGGL((loc_wave_kernel_one<C, true, CVH_LOC_STEP>), grid, block, 0, s, *one);
+    else hipLaunchKernelGGL((loc_wave_kernel_one<C, false, CVH_LOC_STEP>), grid, block, 0, s, *one);
+    return hipGetLastError();
+  }
+  if (kind == CVH_LOC_TSUM) hipLaunchKernelGGL((loc_wave_kernel<C, false, CVH_LOC_TSUM>), grid, block, 0, s, tab, nmem, parity);
+  else if (kind == CVH_LOC_MEANS) hipLaunchKernelGGL((loc_wave_kernel<C, false, CVH_LOC_MEANS>), grid, block, 0, s, tab, nmem, parity);
+  else if (fast) hipLaunchKernelGGL((loc_wave_kernel<C, true, CVH_LOC_STEP>), grid, block, 0, s, tab, nmem, parity);
+  else hipLaunchKernelGGL((loc_wave_kernel<C, false, CVH_LOC_STEP>), grid, block, 0, s, tab, nmem, parity);
   return hipGetLastError();
 }
 
 template <int C>
-hipError_t launch_rows(const CvhLocArgs &a, int fast, int pass, hipStream_t s)
+hipError_t launch_rows(const CvhLocArgs *tab, int nmem, unsigned grid_, int parity, int fast, int pass, hipStream_t s, const CvhLocArgs *one)
 {
-  const dim3 grid(a.g.row_grid), block(CVH_BLOCK);
-  if (pass == CVH_LOC_TSUM) hipLaunchKernelGGL((loc_row_kernel<C, 2, false>), grid, block, 0, s, a);
+  const dim3 grid(grid_), block(CVH_BLOCK);
+  if (one) {
+    if (pass == CVH_LOC_TSUM) hipLaunchKernelGGL((loc_row_kernel_one<C, 2, false>), grid, block, 0, s, *one);
+    else if (pass == CVH_LOC_MEANS) {
+      if (fast) hipLaunchKernelGGL((loc_row_kernel_one<C, 1, false>), grid, block, 0, s, *one);
+      else hipLaunchKernelGGL((loc_row_kernel_one<C, 0, false>), grid, block, 0, s, *one);
+    } else if (fast) hipLaunchKernelGGL((loc_row_kernel_one<C, 1, true>), grid, block, 0, s, *one);
+    else hipLaunchKernelGGL((loc_row_kernel_one<C, 0, true>), grid, block, 0, s, *one);
+    return hipGetLastError();
+  }
+  if (pass == CVH_LOC_TSUM) hipLaunchKernelGGL((loc_row_kernel<C, 2, false>), grid, block, 0, s, tab, nmem, parity);
   else if (pass == CVH_LOC_MEANS) {
-    if (fast) hipLaunchKernelGGL((loc_row_kernel<C, 1, false>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((loc_row_kernel<C, 0, false>), grid, block, 0, s, a);
-  } else if (fast) hipLaunchKernelGGL((loc_row_kernel<C, 1, true>), grid, block, 0, s, a);
-  else hipLaunchKernelGGL((loc_row_kernel<C, 0, true>), grid, block, 0, s, a);
+    if (fast) hipLaunchKernelGGL((loc_row_kernel<C, 1, false>), grid, block, 0, s, tab, nmem, parity);
+    else hipLaunchKernelGGL((loc_row_kernel<C, 0, false>), grid, block, 0, s, tab, nmem, parity);
+  } else if (fast) hipLaunchKernelGGL((loc_row_kernel<C, 1, true>), grid, block, 0, s, tab, nmem, parity);
+  else hipLaunchKernelGGL((loc_row_kernel<C, 0, true>), grid, block, 0, s, tab, nmem, parity);
   return hipGetLastError();
 }
 
@@ -302,18 +363,19 @@ CvhLocGeom cvh_loc_geometry(int h, int w, int radius)
   return g;
 }
 
-hipError_t cvh_launch_loc_rows(const CvhLocArgs &a, int channels, int fast, int pass, hipStream_t s)
+hipError_t cvh_launch_loc_rows(const CvhLocArgs *tab, int nmem, unsigned grid, int parity, int channels, int fast, int pass, hipStream_t s, const CvhLocArgs *one)
 {
-  return channels == 1 ? launch_rows<1>(a, fast, pass, s) : launch_rows<3>(a, fast, pass, s);
+  return channels == 1 ? launch_rows<1>(tab, nmem, grid, parity, fast, pass, s, one) : launch_rows<3>(tab, nmem, grid, parity, fast, pass, s, one);
 }
 
-hipError_t cvh_launch_loc_wave(const CvhLocArgs &a, int channels, int fast, int kind, hipStream_t s)
+hipError_t cvh_launch_loc_wave(const CvhLocArgs *tab, int nmem, unsigned grid, int parity, int channels, int fast, int kind, hipStream_t s, const CvhLocArgs *one)
 {
-  return channels == 1 ? launch_wave<1>(a, fast, kind, s) : launch_wave<3>(a, fast, kind, s);
+  return channels == 1 ? launch_wave<1>(tab, nmem, grid, parity, fast, kind, s, one) : launch_wave<3>(tab, nmem, grid, parity, fast, kind, s, one);
 }
 
-hipError_t cvh_launch_loc_finalize(const CvhLocArgs &a, hipStream_t s)
+hipError_t cvh_launch_loc_finalize(const CvhLocArgs *tab, int nmem, hipStream_t s, const CvhLocArgs *one)
 {
-  hipLaunchKernelGGL(loc_finalize_kernel, dim3(1), dim3(CVH_BLOCK), 0, s, a);
+  if (one) hipLaunchKernelGGL(loc_finalize_kernel_one, dim3(1), dim3(CVH_BLOCK), 0, s, *one);
+  else hipLaunchKernelGGL(loc_finalize_kernel, dim3((unsigned)nmem), dim3(CVH_BLOCK), 0, s, tab);
   return hipGetLastError();
 }

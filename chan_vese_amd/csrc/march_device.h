@@ -27,14 +27,33 @@ __device__ __forceinline__ MarchLane march_lane(long long item, int nwc, int str
   return m;
 }
 
-// the second atan table into LDS (uniform: every thread of the workgroup arrives)
-__device__ __forceinline__ void stage_atan2(double *satan, const CvhFrontArgs &f)
+// The member table of a launch is read in the constant address space: nothing writes it while a kernel runs, and a record chosen by
+// blockIdx alone is wave-uniform, so its fields arrive in scalar loads -- as the fields of a by-value kernel argument do.
+#define CVH_CONSTANT __attribute__((address_space(4)))
+
+// the member whose section of the grid holds this workgroup: first(tab[i]) is ascending, first(tab[0]) == 0 (as io_member; wave-uniform)
+template <class A, class First>
+__device__ __forceinline__ int march_member(const CVH_CONSTANT A *tab, int nmem, First first)
 {
-  for (int q = threadIdx.x; q < CVH_ATAN2_N; q += CVH_BLOCK) satan[q] = f.atan2_tab[q];
+  int lo = 0, hi = nmem - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (first(tab[mid]) <= blockIdx.x) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+// the second atan table into LDS (uniform: every thread of the workgroup arrives).  F: a CvhFrontArgs in any address space
+template <class F>
+__device__ __forceinline__ void stage_atan2(double *satan, const F &f)
+{
+  const double *tab = f.atan2_tab;
+  for (int q = threadIdx.x; q < CVH_ATAN2_N; q += CVH_BLOCK) satan[q] = tab[q];
   __syncthreads();
 }
 
-__device__ __forceinline__ FarCoef far_coef_of(const CvhFrontArgs &f) { return {f.far_k[0], f.far_k[1], f.far_k[2], f.far_k[3], f.far_k[4], f.far_thr}; }
+template <class F>
+__device__ __forceinline__ FarCoef far_coef_of(const F &f) { return {f.far_k[0], f.far_k[1], f.far_k[2], f.far_k[3], f.far_k[4], f.far_thr}; }
 
 // ny of row r - 1 from u(r - 2), u(r - 1), u(r)
 template <bool FAST>

@@ -1,11 +1,18 @@
-// march_run.hip — the host driver under cvh_multiphase_run and cvh_localized_run (MarchRun, cvh_host.h): the level sets of N contexts are
-// iterated together on the leader's stream.  Data flow: iteration t reads d_u[(current + t) & 1] of each context and writes the other
-// buffer of its pair -- the contexts' own ping-pong pairs, no copy of a level set but at most ONE at the end, where the last iteration's
-// buffer is not the one a new level set lands in.  The host enqueues the leader's "sync_every" iterations at a time and reads the state
-// block behind each chunk: its only wait per chunk.  Launches enqueued behind a stop return at once (every workgroup reads the flag), so
-// the level sets stay as the stopping iteration left them and the host picks the buffers by the parity of steps_done.  A run ends with
-// every context exactly as a device-side start leaves it: the level set in the buffer cvh_set_levelset writes, the device's half of a
-// new run done on the leader's stream, then levelset_arrived -- every existing call sees the new level sets.
+// march_run.hip — the host driver under cvh_multiphase_run[_batch] and cvh_localized_run[_batch] (MarchRun, cvh_host.h): the level sets of
+// N members (contexts, or pairs of contexts) are iterated together on the leader's stream; a single call is a batch of one member.
+// Data flow: the leader's table holds one argument record per member -- both buffers of every level set in it -- and one state slot
+// per member; it is uploaded once per call.  Iteration t reads d_u[(current + t) & 1] of each context and writes the other buffer of
+// its pair -- the contexts' own ping-pong pairs; the parity t & 1 is a kernel argument -- with no copy of a level set but at most ONE
+// at the end, where the member's last iteration's buffer is not the one a new level set lands in.  A member's finalise workgroup
+// writes the member's own state block and mirrors it in its slot of the table.  The host enqueues the leader's "sync_every" iterations
+// at a time and copies the state slots down behind each chunk: one copy and one wait per chunk, whatever N.  Launches enqueued behind
+// a member's stop return at once for that member (every workgroup reads its member's flag), so its level set stays as its stopping
+// iteration left it and the host picks the buffers by the parity of the member's steps_done.  A run ends with every context exactly as
+// a device-side start leaves it: the level set in the buffer cvh_set_levelset writes, the device's half of a new run done on the
+// leader's stream, then levelset_arrived -- every existing call sees the new level sets.
+// A call with ONE member keeps the single call's launches as they were before the batch existed (own_state): its record travels by
+// value, the caller swaps the two buffers in it between iterations, nothing is uploaded, no mirror is written, and the member's own
+// state block comes down behind a chunk.
 #include "cvh_host.h"
 
 // the FAST forms' constants; the values fill_args (csv_run.hip) computes into CvhStepArgs, whose layout keeps them apart
@@ -27,72 +34,127 @@ int state_down(cvh_context *a, const void *d_state, void *out, size_t bytes)
   return CVH_OK;
 }
 
-int MarchRun::begin(int max_steps_, double *trace_, int trace_rows, int *rows_)
+int march_stage(cvh_context *lead, size_t dev_bytes, size_t host_bytes, unsigned char **h, unsigned char **d)
 {
-  if (trace_ && (trace_rows < 0 || !rows_))
-    return batch_fail(ctxs, n, CVH_ERR_ARG, "%s: a trace needs trace_rows >= 0 and rows, got trace_rows = %d, rows = %p", what, trace_rows, (void *)rows_);
-  max_steps = max_steps_ < 0 ? INT_MAX : max_steps_;   // (as cvh_run: until the stop rule fires)
-  trace = trace_; rows = rows_;
-  trace_cap = trace ? std::min(trace_rows, max_steps) : 0;
+  if (lead->h_march_cap < host_bytes) {
+    if (lead->h_march) { HIPCHK(lead, hipHostFree(lead->h_march)); lead->h_march = nullptr; lead->h_march_cap = 0; }
+    const size_t cap = align_up(host_bytes + host_bytes / 4, 4096);
+    HIPCHK(lead, hipHostMalloc(&lead->h_march, cap, hipHostMallocDefault));
+    lead->h_march_cap = cap;
+  }
+  const int rc = grow_table(lead, &lead->march_table, dev_bytes);
+  if (rc != CVH_OK) return rc;
+  memset(lead->h_march, 0, host_bytes);
+  *h = (unsigned char *)lead->h_march;
+  *d = (unsigned char *)lead->march_table.d;
   return CVH_OK;
 }
 
-// (open_call / close_call only order streams -- the leader's behind the legacy stream, and back -- and hold nothing: a HIP error between
-// them leaves no call open; what such an error does leave is the header's "partly iterated" level set)
-int MarchRun::open(DeviceTable *table_, int row_width_)
+void march_classes(cvh_context *const *leaders, int n, int stride, std::vector<int> *order, MarchClass *cls)
 {
-  cvh_context *a = ctxs[0];
-  table = table_; row_width = row_width_;
-  if (trace_cap > 0) {
-    const int rc = grow_table(a, table, (size_t)trace_cap * row_width * sizeof(double));
-    if (rc != CVH_OK) return batch_fail(ctxs, n, rc, "%s: %s", what, a->err);
-    d_trace = (double *)table->d;
+  order->clear();
+  for (int k = 0; k < kMarchClasses; ++k) {
+    cls[k] = MarchClass{};
+    cls[k].first = (int)order->size();
+    cls[k].C = k < 2 ? 1 : 3;
+    cls[k].fast = k & 1;
+    for (int i = 0; i < n; ++i)
+      if (march_class(leaders[(size_t)i * stride]) == k) order->push_back(i);
+    cls[k].n = (int)order->size() - cls[k].first;
   }
-  return open_call(ctxs, n, nullptr);
 }
 
-int MarchRun::iterate(const void *d_state, void *st, size_t state_bytes, const std::function<int(const double *const *in, double *const *out)> &step)
+int MarchRun::begin(int max_steps_, double *const *traces_, int trace_rows_, int *rows_)
+{
+  bool any = false;
+  for (int i = 0; traces_ && i < n; ++i) any = any || traces_[i];
+  if (any && (trace_rows_ < 0 || !rows_))
+    return batch_fail(ctxs, n * per, CVH_ERR_ARG, "%s: a trace needs trace_rows >= 0 and rows, got trace_rows = %d, rows = %p", what, trace_rows_, (void *)rows_);
+  max_steps = max_steps_ < 0 ? INT_MAX : max_steps_;   // (as cvh_run: until the stop rule fires)
+  traces = any ? traces_ : nullptr; trace_rows = trace_rows_; rows = rows_;
+  trace_cap.assign((size_t)n, 0);
+  for (int i = 0; traces && i < n; ++i) trace_cap[i] = traces[i] ? std::min(trace_rows, max_steps) : 0;
+  return CVH_OK;
+}
+
+// (open_call / close_call only order streams -- the leader's behind every member's, and back -- and hold nothing: a HIP error between
+// them leaves no call open; what such an error does leave is the header's "partly iterated" level set)
+int MarchRun::open(const std::function<DeviceTable *(int)> &table_of, const std::function<int(int)> &width_of, size_t rec_size_, size_t state_stride_)
+{
+  cvh_context *lead = ctxs[0];
+  d_trace.assign((size_t)n, nullptr);
+  row_width.assign((size_t)n, 0);
+  for (int i = 0; i < n; ++i) {
+    row_width[i] = width_of(i);
+    if (trace_cap[i] <= 0) continue;
+    cvh_context *owner = ctxs[(size_t)i * per];
+    DeviceTable *t = table_of(i);
+    const int rc = grow_table(owner, t, (size_t)trace_cap[i] * row_width[i] * sizeof(double));
+    if (rc != CVH_OK) return batch_fail(ctxs, n * per, rc, "%s: %s%s", what, who(i * per).c_str(), owner->err);
+    d_trace[i] = (double *)t->d;
+  }
+  rec_size = rec_size_; state_stride = state_stride_;
+  state_off = align_up((size_t)n * rec_size, 256);
+  dev_bytes = state_off + (size_t)n * state_stride;
+  land_off = align_up(dev_bytes, 256);
+  const int rc = march_stage(lead, dev_bytes, land_off + (size_t)n * state_stride, &h_tab, &d_tab);
+  if (rc != CVH_OK) return batch_fail(ctxs, n * per, rc, "%s: %s", what, lead->err);
+  cur.assign((size_t)n * per, 0);
+  for (int k = 0; k < n * per; ++k) cur[k] = current_buffer(ctxs[k]);
+  return open_call(ctxs, n * per, nullptr);
+}
+
+int MarchRun::upload()
+{
+  cvh_context *lead = ctxs[0];
+  HIPCHK(lead, hipMemcpyAsync(d_tab, h_tab, dev_bytes, hipMemcpyHostToDevice, lead->stream));   // (the state slots: zeros)
+  return CVH_OK;
+}
+
+int MarchRun::iterate(const std::function<int(int parity)> &step)
 {
   cvh_context *a = ctxs[0];
-  const CvhMarchCount *count = (const CvhMarchCount *)st;
-  int cur[2] = {0, 0};
-  for (int e = 0; e < n; ++e) cur[e] = current_buffer(ctxs[e]);
-  memset(st, 0, state_bytes);
+  auto count = [&](int i) { return (const CvhMarchCount *)state(i); };
+  auto all_stopped = [&]() {
+    for (int i = 0; i < n; ++i)
+      if (!count(i)->stopped) return false;
+    return true;
+  };
   HIPCHK(a, hipEventRecord(a->ev0, a->stream));   // (ev0 / ev1 are free: settle closed any timed run)
   int enq = 0;
-  while (enq < max_steps && !count->stopped) {
+  while (enq < max_steps && !all_stopped()) {
     const int chunk = std::min(a->sync_every, max_steps - enq);
     for (int t = enq; t < enq + chunk; ++t) {
-      const double *in[2] = {nullptr, nullptr};
-      double *out[2] = {nullptr, nullptr};
-      for (int e = 0; e < n; ++e) { in[e] = ctxs[e]->d_u[(cur[e] + t) & 1]; out[e] = ctxs[e]->d_u[(cur[e] + t + 1) & 1]; }
-      const int rc = step(in, out);
+      const int rc = step(t & 1);
       if (rc != CVH_OK) return rc;
     }
     enq += chunk;
     HIPCHK(a, hipEventRecord(a->ev1, a->stream));
-    const int rc = state_down(a, d_state, st, state_bytes);   // the ONE host wait of the chunk
-    if (rc != CVH_OK) return rc;
+    HIPCHK(a, hipMemcpyAsync(h_tab + land_off, own_state ? own_state : d_tab + state_off, (size_t)n * state_stride, hipMemcpyDeviceToHost, a->stream));
+    HIPCHK(a, hipStreamSynchronize(a->stream));   // the ONE host wait of the chunk
   }
   if (enq > 0) HIPCHK(a, hipEventElapsedTime(&a->last_run_ms, a->ev0, a->ev1));
-  // the level sets of iteration steps_done - 1 into the buffers a new level set lands in, and the device's half of the run it begins
-  for (int e = 0; e < n; ++e) {
-    cvh_context *c = ctxs[e];
-    const int from = (cur[e] + count->steps_done) & 1, to = c->chain_pb & 1;
-    if (from != to) HIPCHK(a, hipMemcpyAsync(c->d_u[to], c->d_u[from], c->n * sizeof(double), hipMemcpyDeviceToDevice, a->stream));
-    HIPCHK(a, clear_run_device(c, a->stream));
+  // each level set of its member's iteration steps_done - 1 into the buffer a new level set lands in, and the device's half of the run it begins
+  std::vector<int> nrows((size_t)n, 0);
+  for (int i = 0; i < n; ++i) {
+    const int done = count(i)->steps_done;
+    for (int e = 0; e < per; ++e) {
+      cvh_context *c = ctxs[(size_t)i * per + e];
+      const int from = (cur[(size_t)i * per + e] + done) & 1, to = c->chain_pb & 1;
+      if (from != to) HIPCHK(a, hipMemcpyAsync(c->d_u[to], c->d_u[from], c->n * sizeof(double), hipMemcpyDeviceToDevice, a->stream));
+      HIPCHK(a, clear_run_device(c, a->stream));
+    }
+    nrows[i] = std::min(done, trace_cap[i]);
+    if (nrows[i] > 0)
+      HIPCHK(a, hipMemcpyAsync(traces[i], d_trace[i], (size_t)nrows[i] * row_width[i] * sizeof(double), hipMemcpyDeviceToHost, a->stream));
   }
-  nrows = std::min(count->steps_done, trace_cap);
-  if (nrows > 0) HIPCHK(a, hipMemcpyAsync(trace, table->d, (size_t)nrows * row_width * sizeof(double), hipMemcpyDeviceToHost, a->stream));
-  int rc = close_call(ctxs, n, nullptr, false);
+  int rc = close_call(ctxs, n * per, nullptr, false);
   if (rc != CVH_OK) return rc;
   HIPCHK(a, hipStreamSynchronize(a->stream));
-  for (int e = 0; e < n; ++e) {
-    rc = levelset_arrived(ctxs[e], true);
-    if (rc == CVH_OK) continue;
-    if (n == 1) return batch_fail(ctxs, n, rc, "%s: %s", what, ctxs[e]->err);
-    return batch_fail(ctxs, n, rc, "%s: context %c: %s", what, names[e], ctxs[e]->err);
+  for (int k = 0; k < n * per; ++k) {
+    rc = levelset_arrived(ctxs[k], true);
+    if (rc != CVH_OK) return batch_fail(ctxs, n * per, rc, "%s: %s%s", what, who(k).c_str(), ctxs[k]->err);
   }
-  if (rows) *rows = nrows;
+  for (int i = 0; rows && i < n; ++i) rows[i] = nrows[i];
   return CVH_OK;
 }

@@ -26,8 +26,8 @@ constexpr int R = 4;   // rows per group = rows in flight per level set
 // else the table form.  Only lanes that own a pixel vote (`owner`): the choice is then a function of the row's stored values alone,
 // the same in the step kernel (which holds phi + d in registers) and in a later sums pass over what it stored.
 // (Per wave ROW, by ballot, where the localised kernels choose per pixel: here no sum has to be the same bits in two workgroups.)
-template <bool FAST>
-__device__ __forceinline__ double heaviside(double x, bool owner, const CvhFrontArgs &a, const FarCoef &fc, const double *satan)
+template <bool FAST, class F>
+__device__ __forceinline__ double heaviside(double x, bool owner, const F &a, const FarCoef &fc, const double *satan)
 {
   if (!FAST) return heaviside_strict(x, a.eps);
   if (__builtin_amdgcn_ballot_w64(owner && fabs(x) < fc.thr) == 0ull) return 0.5 + heaviside_centred_far(x, fc);
@@ -48,127 +48,33 @@ __device__ __forceinline__ void add_pixel(double (&acc)[cvh_mp_nsums(C)], double
   }
 }
 
-// STEP: one iteration and the sums of the new pair; else the sums of in[] alone (the call's initial sums, cvh_multiphase_means)
+typedef const CVH_CONSTANT CvhMpArgs *mp_table;
+
+// STEP: one iteration and the sums of the new pair; else the sums of the pair read alone (the call's initial sums, cvh_multiphase_means).
+// tab: the members of the launch; a workgroup finds its own through the prefix block counts `first`.  The body is mp_wave_body.inc.
 template <int C, bool FAST, bool STEP>
-__global__ __launch_bounds__(CVH_BLOCK) void mp_wave_kernel(const CvhMpArgs a)
+__global__ __launch_bounds__(CVH_BLOCK) void mp_wave_kernel(const CvhMpArgs *tab, int nmem, int parity)
 {
-  constexpr int NS = cvh_mp_nsums(C);
-  __shared__ double satan[FAST ? CVH_ATAN2_N + 1 : 1];
-  if (STEP && a.st->run.stopped) return;   // (uniform: before the barrier)
-  if (FAST) stage_atan2(satan, a.f);
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const long long item = (long long)blockIdx.x * (CVH_BLOCK / 64) + wave;
-  if (item >= a.g.nitems) return;
-  const int h = a.h, w = a.w;
-  const MarchLane ml = march_lane(item, a.g.nwc, a.g.strip_rows, h, w);
-  const int s0 = ml.s0, s1 = ml.s1, col = ml.col, colc = ml.colc;
-  const bool lane_valid = ml.valid;
-  const FarCoef fc = far_coef_of(a.f);
-  const double eps = a.f.eps, eps2 = eps * eps;
-  const gdoubles_in in1 = (gdoubles_in)a.in[0], in2 = (gdoubles_in)a.in[1];
-  const gdoubles_out out1 = (gdoubles_out)a.out[0], out2 = (gdoubles_out)a.out[1];
-  const gbytes_in plane[CVH_MAX_CHANNELS] = {(gbytes_in)a.img[0], (gbytes_in)a.img[1], (gbytes_in)a.img[2]};
-
-  // the means this iteration uses and the parameters of the two equations: wave-uniform
-  double c[4][C], l1[2][C], l2[2][C];
-  if (STEP) {
-#pragma unroll
-    for (int k = 0; k < C; ++k) {
-#pragma unroll
-      for (int ab = 0; ab < 4; ++ab) c[ab][k] = a.st->c[ab][k];
-#pragma unroll
-      for (int e = 0; e < 2; ++e) { l1[e][k] = a.lambda1[e][k]; l2[e][k] = a.lambda2[e][k]; }
-    }
-  }
-
-  double acc[NS];
-#pragma unroll
-  for (int s = 0; s < NS; ++s) acc[s] = 0.0;
-
-  auto at = [&](gdoubles_in u, int r) -> double { return u[(size_t)clampi(r, 0, h - 1) * w + colc]; };
-  // rows g0 + 1 .. g0 + R of both level sets and rows g0 .. g0 + R - 1 of the planes.  (A group of four rows ahead, where the localised
-  // kernel asks for one: a row here is two doubles and C bytes, nothing enters or leaves a window)
-  auto request = [&](int g0, double (&t1)[R], double (&t2)[R], int (&ti)[C][R]) {
-#pragma unroll
-    for (int j = 0; j < R; ++j) {
-      t1[j] = at(in1, g0 + 1 + j);
-      t2[j] = at(in2, g0 + 1 + j);
-#pragma unroll
-      for (int k = 0; k < C; ++k) ti[k][j] = plane[k][(size_t)clampi(g0 + j, 0, h - 1) * w + colc];
-    }
-  };
-
-  double um1 = at(in1, s0 - 1), u01 = at(in1, s0), um2 = at(in2, s0 - 1), u02 = at(in2, s0);
-  double nyp1 = 0.0, nyp2 = 0.0;
-  double n1[R], n2[R];
-  int im[C][R];
-  request(s0, n1, n2, im);
-  if (STEP) {
-    nyp1 = ny_above<FAST>(s0, [&] { return at(in1, s0 - 2); }, um1, u01, n1[0]);
-    nyp2 = ny_above<FAST>(s0, [&] { return at(in2, s0 - 2); }, um2, u02, n2[0]);
-  }
-  const double fx = (col <= 0) ? 0.0 : 1.0;
-  auto curvature = [&](double um, double u0, double up, double &ny_prev) { return march_curvature<FAST>(um, u0, up, ny_prev, fx, col); };
-  auto update = [&](double kappa, double F, double u0, int e) { return march_update<FAST>(kappa, F, u0, a.alpha[e], a.beta[e], a.gamma[e], eps, eps2, a.f.dk1); };
-
-  for (int g0 = s0; g0 < s1; g0 += R) {
-    double t1[R], t2[R];
-    int ti[C][R];
-    const bool more = g0 + R < s1;   // (wave-uniform)
-    if (more) request(g0 + R, t1, t2, ti);
-#pragma unroll
-    for (int j = 0; j < R; ++j) {
-      const int r = g0 + j;
-      if (r < s1) {   // (wave-uniform: rows past the strip's end belong to the next strip)
-        const double up1 = n1[j], up2 = n2[j];
-        double f[C];
-#pragma unroll
-        for (int k = 0; k < C; ++k) f[k] = (double)im[k][j];
-        if (STEP) {
-          const double h1 = heaviside<FAST>(u01, lane_valid, a.f, fc, satan), h2 = heaviside<FAST>(u02, lane_valid, a.f, fc, satan);
-          const double k1 = curvature(um1, u01, up1, nyp1), k2 = curvature(um2, u02, up2, nyp2);
-          double F1 = 0.0, F2 = 0.0;
-#pragma unroll
-          for (int k = 0; k < C; ++k) {
-            const double q11 = (f[k] - c[0][k]) * (f[k] - c[0][k]), q10 = (f[k] - c[1][k]) * (f[k] - c[1][k]);
-            const double q01 = (f[k] - c[2][k]) * (f[k] - c[2][k]), q00 = (f[k] - c[3][k]) * (f[k] - c[3][k]);
-            F1 += h2 * (l2[0][k] * q01 - l1[0][k] * q11) + (1 - h2) * (l2[0][k] * q00 - l1[0][k] * q10);
-            F2 += h1 * (l2[1][k] * q10 - l1[1][k] * q11) + (1 - h1) * (l2[1][k] * q00 - l1[1][k] * q01);
-          }
-          const double d1 = update(k1, F1, u01, 0), d2 = update(k2, F2, u02, 1);
-          const double v1 = u01 + d1, v2 = u02 + d2;
-          if (lane_valid) {
-            const size_t o = (size_t)r * w + col;
-            out1[o] = v1;
-            out2[o] = v2;
-          }
-          add_pixel<C>(acc, heaviside<FAST>(v1, lane_valid, a.f, fc, satan), heaviside<FAST>(v2, lane_valid, a.f, fc, satan), f);
-          acc[4 + 4 * C] += d1 * d1;
-          acc[5 + 4 * C] += d2 * d2;
-        } else {
-          add_pixel<C>(acc, heaviside<FAST>(u01, lane_valid, a.f, fc, satan), heaviside<FAST>(u02, lane_valid, a.f, fc, satan), f);
-        }
-        um1 = u01; u01 = up1; um2 = u02; u02 = up2;
-      }
-    }
-    if (more) {
-#pragma unroll
-      for (int j = 0; j < R; ++j) {
-        n1[j] = t1[j]; n2[j] = t2[j];
-#pragma unroll
-        for (int k = 0; k < C; ++k) im[k][j] = ti[k][j];
-      }
-    }
-  }
-  double *row = a.partials + (size_t)item * NS;
-#pragma unroll
-  for (int s = 0; s < NS; ++s) march_store_sum(ml, acc[s], row + s);
+  constexpr bool TABLE = true;
+  const CVH_CONSTANT CvhMpArgs &a = ((mp_table)tab)[march_member((mp_table)tab, nmem, [](const CVH_CONSTANT CvhMpArgs &m) { return m.first; })];
+#include "mp_wave_body.inc"
 }
 
-// ONE workgroup: thread t adds the items' rows t, t + 256, ... in that order, block_reduce's fixed tree adds the threads; thread 0 writes
-// the state block.  is_init: the sums are of the pair the call starts from (or reads): the means alone.
-template <int C>
-__global__ __launch_bounds__(CVH_BLOCK) void mp_finalize_kernel(const CvhMpArgs a, int is_init)
+// ONE pair, its record by value: what a call with one pair launches -- the single call's kernel as it was before the batch existed
+// (reads u[0][.], writes u[1][.], no prefix count, no mirror of the state block)
+template <int C, bool FAST, bool STEP>
+__global__ __launch_bounds__(CVH_BLOCK) void mp_wave_kernel_one(const CvhMpArgs a)
+{
+  constexpr bool TABLE = false;
+  constexpr int parity = 0;
+#include "mp_wave_body.inc"
+}
+
+// ONE workgroup per member: thread t adds the items' rows t, t + 256, ... in that order, block_reduce's fixed tree adds the threads; thread 0
+// writes the pair's state block and (TABLE) its mirror in the leader's state table.  is_init: the sums are of the pair the call starts from (or
+// reads): the means alone.
+template <int C, bool TABLE, class Rec>
+__device__ __forceinline__ void mp_finalize_body(const Rec &a, int is_init)
 {
   constexpr int NS = cvh_mp_nsums(C);
   __shared__ double sred[4 * NS];
@@ -207,7 +113,19 @@ __global__ __launch_bounds__(CVH_BLOCK) void mp_finalize_kernel(const CvhMpArgs 
   }
   for (int ab = 0; ab < 4; ++ab)
     for (int k = 0; k < C; ++k) st->c[ab][k] = sfin[4 + ab * C + k] / sfin[ab];
+  if (!TABLE) return;
+  CvhMpState *mirror = a.st_mirror;   // (this thread's own stores, read back)
+  mirror->run = st->run;
+  mirror->norm[0] = st->norm[0];
+  mirror->norm[1] = st->norm[1];
+  for (int ab = 0; ab < 4; ++ab)
+    for (int k = 0; k < C; ++k) mirror->c[ab][k] = st->c[ab][k];
 }
+
+template <int C>
+__global__ __launch_bounds__(CVH_BLOCK) void mp_finalize_kernel(const CvhMpArgs *tab, int is_init) { mp_finalize_body<C, true>(((mp_table)tab)[blockIdx.x], is_init); }
+template <int C>
+__global__ __launch_bounds__(CVH_BLOCK) void mp_finalize_kernel_one(const CvhMpArgs a, int is_init) { mp_finalize_body<C, false>(a, is_init); }
 
 __device__ __forceinline__ unsigned label_of(double u1, double u2) { return (((float)u1 > 0.0f) ? 1u : 0u) | (((float)u2 > 0.0f) ? 2u : 0u); }
 
@@ -234,15 +152,25 @@ __global__ void __launch_bounds__(CVH_BLOCK) mp_labels_kernel(const CvhIoMember 
 }
 
 template <bool STEP>
-hipError_t launch_wave(const CvhMpArgs &a, int channels, int fast, hipStream_t s)
+hipError_t launch_wave(const CvhMpArgs *tab, int nmem, unsigned grid_, int parity, int channels, int fast, hipStream_t s, const CvhMpArgs *one)
 {
-  const dim3 grid(a.g.grid), block(CVH_BLOCK);
+  const dim3 grid(grid_), block(CVH_BLOCK);
+  if (one) {
+    if (channels == 1) {
+      if (fast) hipLaunchKernelGGL((mp_wave_kernel_one<1, true, STEP>), grid, block, 0, s, *one);
+      else hipLaunchKernelGGL((mp_wave_kernel_one<1, false, STEP>), grid, block, 0, s, *one);
+    } else {
+      if (fast) hipLaunchKernelGGL((mp_wave_kernel_one<3, true, STEP>), grid, block, 0, s, *one);
+      else hipLaunchKernelGGL((mp_wave_kernel_one<3, false, STEP>), grid, block, 0, s, *one);
+    }
+    return hipGetLastError();
+  }
   if (channels == 1) {
-    if (fast) hipLaunchKernelGGL((mp_wave_kernel<1, true, STEP>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((mp_wave_kernel<1, false, STEP>), grid, block, 0, s, a);
+    if (fast) hipLaunchKernelGGL((mp_wave_kernel<1, true, STEP>), grid, block, 0, s, tab, nmem, parity);
+    else hipLaunchKernelGGL((mp_wave_kernel<1, false, STEP>), grid, block, 0, s, tab, nmem, parity);
   } else {
-    if (fast) hipLaunchKernelGGL((mp_wave_kernel<3, true, STEP>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((mp_wave_kernel<3, false, STEP>), grid, block, 0, s, a);
+    if (fast) hipLaunchKernelGGL((mp_wave_kernel<3, true, STEP>), grid, block, 0, s, tab, nmem, parity);
+    else hipLaunchKernelGGL((mp_wave_kernel<3, false, STEP>), grid, block, 0, s, tab, nmem, parity);
   }
   return hipGetLastError();
 }
@@ -261,14 +189,25 @@ CvhMpGeom cvh_mp_geometry(int h, int w)
   return g;
 }
 
-hipError_t cvh_launch_mp_sums(const CvhMpArgs &a, int channels, int fast, hipStream_t s) { return launch_wave<false>(a, channels, fast, s); }
-
-hipError_t cvh_launch_mp_step(const CvhMpArgs &a, int channels, int fast, hipStream_t s) { return launch_wave<true>(a, channels, fast, s); }
-
-hipError_t cvh_launch_mp_finalize(const CvhMpArgs &a, int channels, int is_init, hipStream_t s)
+hipError_t cvh_launch_mp_sums(const CvhMpArgs *tab, int nmem, unsigned grid, int parity, int channels, int fast, hipStream_t s, const CvhMpArgs *one)
 {
-  if (channels == 1) hipLaunchKernelGGL(mp_finalize_kernel<1>, dim3(1), dim3(CVH_BLOCK), 0, s, a, is_init);
-  else hipLaunchKernelGGL(mp_finalize_kernel<3>, dim3(1), dim3(CVH_BLOCK), 0, s, a, is_init);
+  return launch_wave<false>(tab, nmem, grid, parity, channels, fast, s, one);
+}
+
+hipError_t cvh_launch_mp_step(const CvhMpArgs *tab, int nmem, unsigned grid, int parity, int channels, int fast, hipStream_t s, const CvhMpArgs *one)
+{
+  return launch_wave<true>(tab, nmem, grid, parity, channels, fast, s, one);
+}
+
+hipError_t cvh_launch_mp_finalize(const CvhMpArgs *tab, int nmem, int channels, int is_init, hipStream_t s, const CvhMpArgs *one)
+{
+  if (one) {
+    if (channels == 1) hipLaunchKernelGGL(mp_finalize_kernel_one<1>, dim3(1), dim3(CVH_BLOCK), 0, s, *one, is_init);
+    else hipLaunchKernelGGL(mp_finalize_kernel_one<3>, dim3(1), dim3(CVH_BLOCK), 0, s, *one, is_init);
+    return hipGetLastError();
+  }
+  if (channels == 1) hipLaunchKernelGGL(mp_finalize_kernel<1>, dim3((unsigned)nmem), dim3(CVH_BLOCK), 0, s, tab, is_init);
+  else hipLaunchKernelGGL(mp_finalize_kernel<3>, dim3((unsigned)nmem), dim3(CVH_BLOCK), 0, s, tab, is_init);
   return hipGetLastError();
 }
 

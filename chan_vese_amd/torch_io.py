@@ -191,10 +191,10 @@ class Segmenter:
     against a shading ramp (check_rank; cvh_rank_planes_batch) -- in source contexts of its own, as local= does.  With both given the
     rank filter runs FIRST, into `ranked`, contexts of the filter's channels, and local= works on its result.
     phases = 4 (include/chanvese_hip.h, "Four phases") makes every member a PAIR of contexts, `contexts[i]` holding phi1 and `contexts_b[i]`
-    phi2, both fed the same device tensor; segment() then iterates the pairs (cvh_multiphase_run) and returns labels 0 .. 3, phase_masks()
+    phi2, both fed the same device tensor; segment() then iterates the pairs (cvh_multiphase_run_batch) and returns labels 0 .. 3, phase_masks()
     gives the two mask tensors, and the post-processing methods take phase = 0 | 1.  It needs levels = 1 and neither local= nor rank=.
     phases = 2 (the default) is the plain path, call for call.
-    localized = R (1 .. 127; include/chanvese_hip.h, "Localised regions") makes every member run cvh_localized_run -- region means over
+    localized = R (1 .. 127; include/chanvese_hip.h, "Localised regions") makes the members run cvh_localized_run_batch -- region means over
     the (2 R + 1)^2 window of every pixel -- instead of the two-phase run, from whatever init= gives; everything after the run is
     unchanged.  The local force is small: start near the object (init="otsu", a rect, a disk, a mask) and raise mu.  It needs phases = 2
     and levels = 1, and segment() refuses energy_every and reinit_every with it.  None (the default) is the plain path, call for call."""
@@ -313,7 +313,7 @@ class Segmenter:
 
     def _segment4(self, images, max_steps, perona_malik, init, init2, layout):
         """segment() with phases = 4: ingest into both contexts of every pair -> (Perona-Malik, colour on both) -> phi1 from init, phi2 from
-        init2 -> cvh_multiphase_run per pair -> labels.  Returns (labels, steps, norms): labels a uint8 tensor (N, H, W) of 0 .. 3 =
+        init2 -> cvh_multiphase_run_batch (all pairs in shared launches) -> labels.  Returns (labels, steps, norms): labels a uint8 tensor (N, H, W) of 0 .. 3 =
         mask(phi1) + 2 mask(phi2), steps the iterations and norms the (||d1||, ||d2||) of every pair."""
         kinds = []
         for name, given in (("init", init), ("init2", init2)):
@@ -335,7 +335,7 @@ class Segmenter:
         if th is not None:
             self.thresholds = th
         self._start(self.contexts_b, kinds[1][0], kinds[1][1], init2, bits[1], stream)
-        res = [capi.multiphase_run(a, b, max_steps) for a, b in zip(self.contexts, self.contexts_b)]
+        res = capi.multiphase_run_batch(list(zip(self.contexts, self.contexts_b)), max_steps)
         labels = torch.empty((self.n, self.h, self.w), dtype=torch.uint8, device=images.device)
         for i, (a, b) in enumerate(zip(self.contexts, self.contexts_b)):
             a.multiphase_labels_with(b, labels[i].data_ptr(), stream)
@@ -469,7 +469,7 @@ class Segmenter:
             self.energy_series = [m[2] for m in mon]
             res = [m[:2] for m in mon]
         elif self.localized is not None:
-            res = [capi.localized_run(ctx, self.localized, max_steps)[:2] for ctx in self.contexts]
+            res = [r[:2] for r in capi.localized_run_batch(self.contexts, self.localized, max_steps)]
         else:
             res = capi.run_batch_with_reinit(self.contexts, max_steps, reinit_every)
         masks = torch.empty((self.n, self.h, self.w), dtype=torch.uint8, device=images.device)

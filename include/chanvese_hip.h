@@ -1286,7 +1286,7 @@ void cvh_split_geometry(int *tile_rows, int *tile_cols, int *group);   /* pure h
  * cvh_set_levelset of the new doubles leaves them (a new run begins on each: counters 0, the two-phase means not yet taken); a
  * one-context run continued afterwards is bit for bit what it is after cvh_set_levelset of the fetched doubles.  Device work runs on
  * A's stream, joined with B's before and after; the host enqueues A's "sync_every" iterations at a time (two launches each) and waits
- * once per chunk for the pair's state block.  Launches enqueued behind a stop return at once.  Workspaces (state block, partial sums,
+ * once per chunk for the pair's state.  Launches enqueued behind a stop return at once.  Workspaces (state block, partial sums,
  * trace) are A's, allocated on first use and kept; the level sets iterate in the contexts' own buffer pairs.  cvh_last_run_ms(A)
  * afterwards is the device's time from the first iteration's launch to the end of the last chunk (the waits between chunks included).
  * Determinism: every result depends on the inputs and the shape alone.  Partial sums are taken per ITEM of a fixed partition of the
@@ -1309,10 +1309,37 @@ void cvh_split_geometry(int *tile_rows, int *tile_cols, int *group);   /* pure h
  * H_eps reaches 0 or 1 exactly only far from the front -- in CVH_MATH_FAST from |phi| of about 1e16 eps on, over the WHOLE plane.  The
  * NaN then reaches both level sets and both norms with the next iteration, the stop rule never fires on a NaN norm (the run ends at
  * max_steps), and none of it is an error.
- * Not here: batches of pairs in shared launches, the resident (LDS) flow, FP32 state, a four-phase energy, pyramids and
- * reinitialisation inside the run (cvh_reinit on each context between runs works), more than two level sets. */
+ * cvh_multiphase_run_batch runs n pairs (as[i], bs[i]) in shared launches: steps_done[i], norms[2 i], norms[2 i + 1], traces[i] (NULL:
+ * no trace for that pair; traces itself may be NULL) and rows[i] are pair i's, with cvh_multiphase_run's meaning; "the same context
+ * twice" counts across as and bs.
+ * A member is its own run: level set(s), steps_done[i], norm(s) and every trace row of member i are bit for bit what the single call
+ * gives for that member alone from the same state -- in both "math_mode"s, for any n, any order of the members and any mix of shapes,
+ * channel counts (1 and 3), radii, parameters and "math_mode"s -- and the member is left exactly as the single call leaves it.  (Both
+ * kernels take their partial sums per item of a partition that depends on h and w alone and add them in a fixed order: a member's
+ * bits cannot depend on who shares the launch.  The single call IS the batch of one member -- one host path; a call with one member hands its record to the kernels by value.)
+ * Members stop independently: each keeps its own state block and stop flag, workgroups of a stopped member return at once, a stopped
+ * member keeps its stopping iteration's update, and the call ends when every member has stopped or max_steps iterations are enqueued.
+ * Launches: per iteration ONE launch per kernel and per (channel count, math mode) class present in the batch (the kernels are
+ * templates on both); a finalise launch has one workgroup per member.  The member table -- one argument record per member with BOTH
+ * buffers of every level set, blocks find their member through prefix block counts -- is uploaded once per call; an iteration's
+ * parity travels as a kernel argument and nothing is uploaded between iterations.  The planes T_k / the initial sums are taken the
+ * same way, once per call for all members.  The host waits ONCE per chunk of member 0's "sync_every" iterations, whatever n: every
+ * finalise workgroup mirrors its member's state block in a contiguous state table, which comes down in one copy.
+ * Work runs on member 0's stream (A0's for pairs), joined with every member's stream before and after.  Workspaces, traces and state
+ * blocks stay the members' own; the table is member 0's, grown on demand and kept.  cvh_last_run_ms(member 0) is as for the single call.
+ * Refusals: everything is checked before anything is touched, the message names the member index and is cvh_last_error(NULL)'s and
+ * member 0's, and the contexts are as they were afterwards.  CVH_ERR_ARG: n <= 0, a NULL array or member, the same context twice
+ * anywhere in the call, members on different devices, 2^31 or more workgroups in one launch, and every per-member refusal of the
+ * single call; CVH_ERR_STATE as for the single call.  max_steps = 0 iterates nothing and returns zeros.
+ * When it pays: measured once on an MI355X (tools/march_batch_probe.py, 64 iterations, us per pair-iteration, batch against a loop of
+ * cvh_multiphase_run; one / three channels): 64 x 256^2 1.5 against 14.9 (9.7x) / 1.9 against 19.6 (10.5x); 32 x 512^2 3.8x / 3.9x; 8 x 1024^2 2.0x /
+ * 2.1x; 2 x 2048^2 1.20x / 1.28x.  It lost at no shape measured.  A call with one pair launches the single call's by-value kernels.
+ * Not here: the resident (LDS) flow, FP32 state, a four-phase energy, pyramids and reinitialisation inside the run (cvh_reinit on each
+ * context between runs works), more than two level sets, batches across devices. */
 int cvh_multiphase_run(cvh_context *a, cvh_context *b, int max_steps, int *steps_done, double *norms /* 2 */, double *trace, int trace_rows,
                        int *rows);
+extern int cvh_multiphase_run_batch(cvh_context *const *as, cvh_context *const *bs, int n, int max_steps, int *steps_done /* n */, double *norms /* 2 n */,
+                             double *const *traces /* n or NULL */, int trace_rows, int *rows /* n */);
 int cvh_multiphase_means(cvh_context *a, cvh_context *b, double *c /* 4 C */);
 int cvh_multiphase_labels(cvh_context *a, cvh_context *b, uint8_t *labels);   /* host bytes, 0 .. 3 */
 int cvh_multiphase_labels_device(cvh_context *a, cvh_context *b, uint8_t *d_labels, void *stream);
@@ -1365,9 +1392,36 @@ void cvh_multiphase_geometry(int h, int w, int *cols, int *strip_rows, int *item
  * CVH_ERR_ARG: R outside 1 .. 127, "state" = 32, h*w >= 2^28, every output NULL, a trace without rows or with trace_rows < 0.
  * CVH_ERR_STATE: no image or no level set.  Everything is checked before anything is touched; the message is cvh_last_error's; after
  * such a refusal the context is as it was and stays usable.
- * Not here: batches in shared launches, the resident (LDS) flow, FP32 state, a localised energy, four phases with local means,
- * pyramids or reinitialisation inside the run, Gaussian windows, a global / local blend. */
+ * cvh_localized_run_batch runs n contexts in shared launches, member i with radius[i]: steps_done[i], norms[i], traces[i] (NULL: no
+ * trace for that member; traces itself may be NULL) and rows[i] are member i's, with cvh_localized_run's meaning.
+ * A member is its own run: level set(s), steps_done[i], norm(s) and every trace row of member i are bit for bit what the single call
+ * gives for that member alone from the same state -- in both "math_mode"s, for any n, any order of the members and any mix of shapes,
+ * channel counts (1 and 3), radii, parameters and "math_mode"s -- and the member is left exactly as the single call leaves it.  (Both
+ * kernels take their partial sums per item of a partition that depends on h and w alone and add them in a fixed order: a member's
+ * bits cannot depend on who shares the launch.  The single call IS the batch of one member -- one host path; a call with one member hands its record to the kernels by value.)
+ * Members stop independently: each keeps its own state block and stop flag, workgroups of a stopped member return at once, a stopped
+ * member keeps its stopping iteration's update, and the call ends when every member has stopped or max_steps iterations are enqueued.
+ * Launches: per iteration ONE launch per kernel and per (channel count, math mode) class present in the batch (the kernels are
+ * templates on both); a finalise launch has one workgroup per member.  The member table -- one argument record per member with BOTH
+ * buffers of every level set, blocks find their member through prefix block counts -- is uploaded once per call; an iteration's
+ * parity travels as a kernel argument and nothing is uploaded between iterations.  The planes T_k / the initial sums are taken the
+ * same way, once per call for all members.  The host waits ONCE per chunk of member 0's "sync_every" iterations, whatever n: every
+ * finalise workgroup mirrors its member's state block in a contiguous state table, which comes down in one copy.
+ * Work runs on member 0's stream (A0's for pairs), joined with every member's stream before and after.  Workspaces, traces and state
+ * blocks stay the members' own; the table is member 0's, grown on demand and kept.  cvh_last_run_ms(member 0) is as for the single call.
+ * Refusals: everything is checked before anything is touched, the message names the member index and is cvh_last_error(NULL)'s and
+ * member 0's, and the contexts are as they were afterwards.  CVH_ERR_ARG: n <= 0, a NULL array or member, the same context twice
+ * anywhere in the call, members on different devices, 2^31 or more workgroups in one launch, and every per-member refusal of the
+ * single call; CVH_ERR_STATE as for the single call.  max_steps = 0 iterates nothing and returns zeros.
+ * When it pays: measured once on an MI355X (tools/march_batch_probe.py, 64 iterations, us per member-iteration, batch against a loop of
+ * cvh_localized_run): 64 x 256^2 2.1 against 25.3 at R = 2 (11.9x) and 2.4 against 53.7 at R = 10 (22.7x), three channels 7.9x / 16.5x; 32 x 512^2
+ * 5.2x / 9.7x (three channels 3.6x / 6.5x); 8 x 1024^2 2.1x / 3.6x (1.6x / 2.4x); 2 x 2048^2 1.08x / 1.24x, and with three channels NOTHING (0.99x /
+ * 1.01x: one member fills the card).  A call with one member launches the single call's by-value kernels.
+ * Not here: the resident (LDS) flow, FP32 state, a localised energy, four phases with local means, pyramids or reinitialisation inside
+ * the run, Gaussian windows, a global / local blend, batches across devices. */
 int cvh_localized_run(cvh_context *ctx, int radius, int max_steps, int *steps_done, double *norm, double *trace, int trace_rows, int *rows);
+extern int cvh_localized_run_batch(cvh_context *const *ctxs, int n, const int *radius /* n */, int max_steps, int *steps_done /* n */, double *norms /* n */,
+                            double *const *traces /* n or NULL */, int trace_rows, int *rows /* n */);
 int cvh_localized_means(cvh_context *ctx, int radius, double *c1, double *c2, uint64_t *wq, uint64_t *a, uint64_t *s);
 void cvh_localized_geometry(int h, int w, int radius, int *cols, int *item_rows, int *items, int *strip_rows);   /* pure host arithmetic; 0 rows / items: not a plane or radius the calls take */
 
