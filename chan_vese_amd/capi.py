@@ -50,6 +50,8 @@ EXPORTS = [
     "cvh_split", "cvh_split_host", "cvh_split_batch", "cvh_split_levelset", "cvh_split_levelset_batch", "cvh_split_geometry",
     "cvh_multiphase_run", "cvh_multiphase_run_batch", "cvh_multiphase_means", "cvh_multiphase_labels", "cvh_multiphase_labels_device", "cvh_multiphase_geometry",
     "cvh_localized_run", "cvh_localized_run_batch", "cvh_localized_means", "cvh_localized_geometry",
+    "cvh_set_edge_map", "cvh_get_edge_map", "cvh_set_edge_map_device", "cvh_get_edge_map_device", "cvh_edge_map", "cvh_edge_map_batch",
+    "cvh_geodesic_run", "cvh_geodesic_run_batch", "cvh_geodesic_geometry",
 ]
 # "Mask morphology": the operations of cvh_get_mask_morph* / cvh_morph_levelset*, by code and by name
 MORPH_NONE, MORPH_DILATE, MORPH_ERODE, MORPH_OPEN, MORPH_CLOSE = 0, 1, 2, 3, 4
@@ -395,6 +397,15 @@ def lib():
         "cvh_localized_run_batch": (C.c_int, [vp, C.c_int, ip, C.c_int, ip, dp, vp, C.c_int, ip]),
         "cvh_localized_means": (C.c_int, [vp, C.c_int, dp, dp, vp, vp, vp]),
         "cvh_localized_geometry": (None, [C.c_int, C.c_int, C.c_int, ip, ip, ip, ip]),
+        "cvh_set_edge_map": (C.c_int, [vp, vp]),
+        "cvh_get_edge_map": (C.c_int, [vp, vp]),
+        "cvh_set_edge_map_device": (C.c_int, [vp, vp, vp]),
+        "cvh_get_edge_map_device": (C.c_int, [vp, vp, vp]),
+        "cvh_edge_map": (C.c_int, [vp, vp, C.c_double]),
+        "cvh_edge_map_batch": (C.c_int, [vp, vp, C.c_int, dp]),
+        "cvh_geodesic_run": (C.c_int, [vp, C.c_int, ip, dp, dp, C.c_int, ip]),
+        "cvh_geodesic_run_batch": (C.c_int, [vp, C.c_int, C.c_int, ip, dp, vp, C.c_int, ip]),
+        "cvh_geodesic_geometry": (None, [C.c_int, C.c_int, ip, ip, ip]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -1261,6 +1272,56 @@ def localized_run_batch(contexts, radius, max_steps=-1, trace=False):
     return [(done[i], norms[i], outs[i][:rows[i]].copy() if wanted else None) for i in range(n)]
 
 
+def geodesic_geometry(h, w):
+    """cvh_geodesic_geometry: (columns per wave, rows per strip, items) of the fixed partition the edge-weighted run's sums are taken
+    over -- the four-phase partition; pure host arithmetic (rows and items are 0 for a plane the calls refuse)."""
+    cols, rows, items = C.c_int(0), C.c_int(0), C.c_int(0)
+    lib().cvh_geodesic_geometry(int(h), int(w), C.byref(cols), C.byref(rows), C.byref(items))
+    return cols.value, rows.value, items.value
+
+
+def edge_map_batch(dsts, srcs, K):
+    """cvh_edge_map_batch: Context.edge_map_from for n pairs (any mix of shapes and channel counts) in one launch.  K is one value for
+    every pair or one per pair."""
+    dsts, srcs = list(dsts), list(srcs)
+    n = len(dsts)
+    if n == 0 or len(srcs) != n:
+        raise ValueError(f"edge_map_batch: {n} destinations, {len(srcs)} sources")
+    ks = [float(k) for k in K] if np.ndim(K) else [float(K)] * n
+    if len(ks) != n:
+        raise ValueError(f"K: {len(ks)} values for {n} pairs")
+    _batch_chk(lib().cvh_edge_map_batch(_member_array(dsts), _member_array(srcs), n, (C.c_double * n)(*ks)))
+
+
+def geodesic_run(ctx, max_steps=-1, trace=False):
+    """cvh_geodesic_run ("Edge-weighted length" in include/chanvese_hip.h): Chan-Vese with the length term weighted by the context's
+    edge plane, until max_steps iterations are done (negative: no bound) or the stop rule fires.  Returns (steps_done, norm, trace):
+    trace is None, or with trace=True (all rows; needs max_steps >= 0) or trace=<rows> an array of one row of 2 C + 1 doubles per
+    iteration -- the means c1, c2 it used and its norm.  The context is left as set_levelset of the new level set leaves it."""
+    want = _trace_rows_wanted(max_steps, trace)
+    done, rows, norm = C.c_int(0), C.c_int(0), C.c_double(0.0)
+    out = np.zeros((max(want, 1), 2 * ctx.channels + 1), dtype=np.float64) if want or trace is True else None
+    ctx._chk(lib().cvh_geodesic_run(ctx._h, int(max_steps), C.byref(done), C.byref(norm), None if out is None else _dp(out), want, C.byref(rows)))
+    return done.value, norm.value, None if out is None else out[:rows.value].copy()
+
+
+def geodesic_run_batch(contexts, max_steps=-1, trace=False):
+    """cvh_geodesic_run_batch: geodesic_run for every context at once -- per iteration one step and one finalise launch for all members
+    of a (channel count, math mode) class.  Every member iterates and stops on its own and is bit for bit what geodesic_run gives for
+    it alone.  Returns a list of (steps_done, norm, trace), one per member; trace as there."""
+    contexts = list(contexts)
+    n = len(contexts)
+    if n == 0:
+        raise ValueError("geodesic_run_batch: no members")
+    want = _trace_rows_wanted(max_steps, trace)
+    wanted = bool(want) or trace is True
+    done, rows, norms = (C.c_int * n)(), (C.c_int * n)(), (C.c_double * n)()
+    outs = [np.zeros((max(want, 1), 2 * c.channels + 1), dtype=np.float64) for c in contexts] if wanted else None
+    traces = (C.c_void_p * n)(*[o.ctypes.data for o in outs]) if wanted else None
+    _batch_chk(lib().cvh_geodesic_run_batch(_member_array(contexts), n, int(max_steps), done, norms, traces, want, rows))
+    return [(done[i], norms[i], outs[i][:rows[i]].copy() if wanted else None) for i in range(n)]
+
+
 def run_monitored(ctx, max_steps=-1, every=16, rel_plateau=None):
     """Context.run in segments of `every` iterations with the energy (Context.energy) taken after each segment.  Returns (total steps,
     last norm, [(steps so far, Energy)]).  max_steps is the total budget (< 0: unlimited); the run ends when the stop rule fired inside
@@ -1510,6 +1571,34 @@ class Context:
         addr = lambda a: a.ctypes.data
         self._chk(self._L.cvh_localized_means(self._h, int(radius), ptr("c1", _dp), ptr("c2", _dp), ptr("wq", addr), ptr("a", addr), ptr("s", addr)))
         return out
+
+    def set_edge_map(self, gq, stream=0):
+        """cvh_set_edge_map / cvh_set_edge_map_device: the context's edge plane, g = gq 2^-15, from a numpy array of (h, w) uint16
+        values 0 .. 32768 (above: refused), or from the integer address of h * w uint16 in device memory, ordered behind `stream`
+        (above 32768: clamped on the device)."""
+        if isinstance(gq, np.ndarray):
+            if gq.dtype != np.uint16 or gq.shape != (self.h, self.w):   # (no conversion: a wider integer would wrap, a float truncate)
+                raise ValueError(f"set_edge_map: a uint16 array of shape {(self.h, self.w)}, got {gq.dtype} {gq.shape}")
+            a = np.ascontiguousarray(gq)
+            self._chk(self._L.cvh_set_edge_map(self._h, a.ctypes.data))
+        elif isinstance(gq, (int, np.integer)) and not isinstance(gq, bool):
+            self._chk(self._L.cvh_set_edge_map_device(self._h, int(gq) or None, int(stream) or None))
+        else:
+            raise ValueError(f"set_edge_map: a uint16 numpy array or the integer address of device memory, got {type(gq).__name__}")
+
+    def get_edge_map(self, ptr=0, stream=0):
+        """cvh_get_edge_map / cvh_get_edge_map_device: the edge plane as a uint16 array of (h, w), or written to device memory at `ptr`."""
+        if ptr:
+            self._chk(self._L.cvh_get_edge_map_device(self._h, int(ptr), int(stream) or None))
+            return None
+        out = np.empty((self.h, self.w), dtype=np.uint16)
+        self._chk(self._L.cvh_get_edge_map(self._h, out.ctypes.data))
+        return out
+
+    def edge_map_from(self, src, K):
+        """cvh_edge_map: this context's edge plane from the planes of `src` (may be self) as they are now:
+        gq = rint(32768 / (1 + |Sobel gradient|^2 / (64 C K^2))).  Smooth first (perona_malik, or a local mean in a second context)."""
+        _batch_chk(self._L.cvh_edge_map(self._h, src._h, float(K)))
 
     def multiphase_labels_with(self, b, ptr=0, stream=0):
         """cvh_multiphase_labels / _device: label = mask(self) + 2 mask(b) per pixel, one launch.  Returns a uint8 array of (h, w), or

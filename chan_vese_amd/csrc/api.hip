@@ -158,6 +158,9 @@ extern "C" void cvh_destroy(cvh_context *c)
   free_table(&c->mp_trace);
   if (c->d_localized) (void)hipFree(c->d_localized);
   free_table(&c->loc_trace);
+  if (c->d_gq) (void)hipFree(c->d_gq);
+  if (c->d_geodesic) (void)hipFree(c->d_geodesic);
+  free_table(&c->geo_trace);
   free_table(&c->march_table);
   if (c->h_march) (void)hipHostFree(c->h_march);
   if (c->ev_io_in) (void)hipEventDestroy(c->ev_io_in);

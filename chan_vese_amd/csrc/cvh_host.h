@@ -6,7 +6,7 @@
 // level sets), components_run.hip (connected components, and MaskSource: the raw or cleaned mask every mask-derived call starts from),
 // pyramid_run.hip (coarse-to-fine), colour_run.hip (colour spaces), window_run.hip (local statistics and rank planes: the windowed-plane calls), energy_run.hip (the functional's terms), score_run.hip (mask scores),
 // morph_run.hip (mask morphology, mask starts), split_run.hip (object split), measure_run.hip (component measures), contour_run.hip (contours), overlap_run.hip
-// (component overlaps), multiphase_run.hip (four phases: a pair of contexts iterated together), localized_run.hip (localised regions), march_run.hip (the driver under those two), debug_exports.hip (diagnostics).  Kernel
+// (component overlaps), multiphase_run.hip (four phases: a pair of contexts iterated together), localized_run.hip (localised regions), geodesic_run.hip (edge-weighted length), march_run.hip (the driver under those three), edge_run.hip (the edge plane), debug_exports.hip (diagnostics).  Kernel
 // sources do not include it.
 #pragma once
 #include <limits.h>
@@ -193,7 +193,12 @@ struct cvh_context {   // opaque to callers; four groups
   void *d_localized = nullptr;   // workspace of cvh_localized_* (localized_run.hip): state block, the items' partial sums, the 1 + C planes of
                                  // horizontal window sums and the C planes of T_k: (8 + 12 C) bytes per pixel, allocated by the first call, kept
   DeviceTable loc_trace;         // and the trace rows of the longest cvh_localized_run so far that asked for them, grown on demand, kept
-  DeviceTable march_table;       // four-phase / localised calls led by this context (march_run.hip): the members' argument records and their
+  uint16_t *d_gq = nullptr;      // the edge plane of "Edge-weighted length" (edge_run.hip): h w values 0 .. 32768, g = gq 2^-15; allocated by the first
+  bool have_gq = false;          // call that sets it, kept until replaced; no image or level-set call touches it
+  void *d_geodesic = nullptr;    // workspace of cvh_geodesic_run* (geodesic_run.hip): the state block and the items' partial sums: allocated by the
+                                 // first call, kept -- not part of live_footprint either
+  DeviceTable geo_trace;         // and the trace rows of the longest cvh_geodesic_run so far that asked for them, grown on demand, kept
+  DeviceTable march_table;       // four-phase / localised / geodesic calls led by this context (march_run.hip): the members' argument records and their
   void *h_march = nullptr;       // state table; h_march: its pinned host image and the landing place of the states, h_march_cap bytes --
   size_t h_march_cap = 0;        // grown on demand, kept
   int coop_launch = -1;          // does the device launch cooperatively (-1: not asked yet; launches_cooperatively)
@@ -326,6 +331,7 @@ int ensure_workspace(cvh_context *c, void **slot, size_t bytes, const char *name
 
 // march_run.hip: what the four-phase and localised flows share -- "iterate the level sets of N contexts on the leader's stream"
 void fill_front_args(const cvh_context *c, CvhFrontArgs *f);
+std::string member_prefix(int i);   // "member 3: ": what opens a batch's message about member i
 int state_down(cvh_context *a, const void *d_state, void *out, size_t bytes);   // on a's stream, through its pinned state slots; waits
 // The leader's table of a call: *h is `host_bytes` of zeroed pinned memory whose first `dev_bytes` the caller uploads to *d.  Every call
 // that uses it ends with a host wait on the leader's stream, so the pinned block is free when the next one begins.

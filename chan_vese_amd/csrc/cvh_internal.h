@@ -548,6 +548,47 @@ enum { CVH_LOC_STEP = 0, CVH_LOC_MEANS = 1, CVH_LOC_TSUM = 2 };
 hipError_t cvh_launch_loc_rows(const CvhLocArgs *tab, int nmem, unsigned grid, int parity, int channels, int fast, int pass, hipStream_t s, const CvhLocArgs *one);
 hipError_t cvh_launch_loc_wave(const CvhLocArgs *tab, int nmem, unsigned grid, int parity, int channels, int fast, int kind, hipStream_t s, const CvhLocArgs *one);
 hipError_t cvh_launch_loc_finalize(const CvhLocArgs *tab, int nmem, hipStream_t s, const CvhLocArgs *one);   // a workgroup per member
+// edge-weighted length (geodesic_kernels.hip, edge_kernels.hip; include/chanvese_hip.h, "Edge-weighted length").  ONE level set with
+// global means on the four-phase partition (cvh_mp_geometry: the items are strips of strip_rows rows x CVH_MARCH_COLS columns).  An
+// item's row of partial sums holds cvh_geo_nsums(C) doubles:  [0] sum H   [1 + k] sum I_k H   [1 + C] sum d^2.  The complements come
+// from npix and sum_img, which do not depend on the level set: c2 = (sum I_k - sum I_k H) / (npix - sum H).
+#define CVH_EDGE_ONE 32768       // gq of g = 1: g = gq 2^-15
+__host__ __device__ constexpr int cvh_geo_nsums(int C) { return 2 + C; }
+struct CvhGeoState {
+  CvhMarchCount run;
+  double c1[CVH_MAX_CHANNELS], c2[CVH_MAX_CHANNELS];   // the means of the current level set, read by the next iteration
+  double norm;                     // ||d||_2 of the last executed iteration
+};
+// A member of a geodesic launch: a record of the device table the kernels read (as CvhMpArgs above)
+struct CvhGeoArgs {
+  double *u[2];                    // both buffers of the level set (by value: u[0] read, u[1] written)
+  const uint8_t *img[CVH_MAX_CHANNELS];
+  const uint16_t *gq;              // the edge plane
+  CvhGeoState *st;                 // the member's own state block (its workspace)
+  double *partials;                // [nitems][cvh_geo_nsums(C)]
+  double *trace;                   // [trace_cap][2C + 1] or null
+  int trace_cap;
+  int h, w;
+  CvhMpGeom g;
+  double alpha, beta, gamma;       // dt mu, dt / C, -dt nu
+  double lambda1[CVH_MAX_CHANNELS], lambda2[CVH_MAX_CHANNELS];
+  CvhFrontArgs f;
+  double stop;                     // what cvh_get_stop_condition returns
+  double npix, sum_img[CVH_MAX_CHANNELS];   // h w and the exact plane sums
+  // what the table form alone reads
+  CvhGeoState *st_mirror;          // the member's slot of the leader's contiguous state table
+  unsigned first;                  // workgroups of the step grid in front of this member's
+};
+// as the four-phase launchers: tab[0 .. nmem-1] the members of ONE (channel count, math mode) class, `one` a host record that travels by value
+hipError_t cvh_launch_geo_sums(const CvhGeoArgs *tab, int nmem, unsigned grid, int parity, int channels, int fast, hipStream_t s, const CvhGeoArgs *one);
+hipError_t cvh_launch_geo_step(const CvhGeoArgs *tab, int nmem, unsigned grid, int parity, int channels, int fast, hipStream_t s, const CvhGeoArgs *one);
+hipError_t cvh_launch_geo_finalize(const CvhGeoArgs *tab, int nmem, int channels, int is_init, hipStream_t s, const CvhGeoArgs *one);
+// the Sobel edge map (edge_kernels.hip) on the member table: src / src_stride / w2 the planes of the source context and their number,
+// dst the member's edge plane (uint16), den[i] member i's ((64 C) K) K, a table behind the member table; a lane takes a pixel per trip,
+// sections of cvh_edge_blocks(n) workgroups.  The device-pointer forms: a clamped copy in, a plain copy out.
+unsigned cvh_edge_blocks(size_t n);
+hipError_t cvh_launch_edge_map(const CvhIoMember *tab, const double *den, int nmem, unsigned grid, hipStream_t s);
+hipError_t cvh_launch_edge_clamp(const uint16_t *src, uint16_t *dst, size_t n, hipStream_t s);   // dst = min(src, CVH_EDGE_ONE)
 // rows-per-tile options of the step kernel
 void cvh_step_grid(int h, int w, int tile_rows, int *tiles_x, int *tiles_y);
 int cvh_step_max_blocks(int h, int w);

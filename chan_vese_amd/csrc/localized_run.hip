@@ -29,8 +29,6 @@ int loc_check(cvh_context *const *ctxs, int n, cvh_context *c, int radius, const
   return CVH_OK;
 }
 
-std::string member_prefix(int i) { return "member " + std::to_string(i) + ": "; }
-
 size_t partial_bytes(const CvhLocGeom &g) { return align_up((size_t)g.nitems * sizeof(double), 256); }
 
 // the members settled, their FP64 mirrors fresh, their workspaces there

@@ -94,6 +94,38 @@ __device__ __forceinline__ double march_curvature(double um, double u0, double u
   return kappa;
 }
 
+// The edge-weighted forms (geodesic_kernels.hip): the normal is scaled by g at its own pixel before the backward differences,
+// Gx = g nx, Gy = g ny (one rounding each), and gy_prev -- Gy of the row above -- moves on where ny_prev does above.
+// Gy of the row above a strip: g_above() is g(s0 - 1, .), read only off the plane's first row, where the row's own Gy -- g0 ny, by the
+// very expression the row uses -- makes Gy - gy_prev an exact zero
+template <bool FAST, class Above, class GAbove>
+__device__ __forceinline__ double gy_above(int s0, Above um2, GAbove g_above, double um, double u0, double up, double g0)
+{
+  if (s0 == 0) return g0 * ny_of<FAST>(um, u0, up);
+  return g_above() * ny_of<FAST>(um2(), um, u0);
+}
+
+template <bool FAST>
+__device__ __forceinline__ double march_curvature_weighted(double um, double u0, double up, double g, double &gy_prev, double fx, int col)
+{
+  const double uw = from_left_lane(u0, u0), ue = from_right_lane(u0, u0);
+  double gx, gy, kappa;
+  if (FAST) {
+    const double u2 = u0 + u0;
+    gx = g * normalised4(ue, uw, u2);
+    gy = g * normalised4(up, um, u2);
+    kappa = __builtin_fma(gx - from_left_lane(gx, 0.0), fx, gy - gy_prev);
+  } else {
+    gx = g * normalised<false>(ue - u0, central(uw, ue));
+    gy = g * normalised<false>(up - u0, central(um, up));
+    const double gxl = from_left_lane(gx, 0.0);
+    const double kx = (col <= 0) ? 0.0 : gx - gxl;
+    kappa = kx + (gy - gy_prev);
+  }
+  gy_prev = gy;
+  return kappa;
+}
+
 // dt (mu kappa - nu + F / C) delta_eps(u0), folded as the one-level-set step folds it (:985, :992).  eps2 = eps * eps comes in, taken
 // once per kernel: squared in here, the FAST three-channel four-phase kernel spilled scalar registers (profiles/march_refactor)
 template <bool FAST>

@@ -26,6 +26,8 @@ void fill_front_args(const cvh_context *c, CvhFrontArgs *f)
   f->atan2_tab = c->d_atan + 2 * CVH_ATAN_N;
 }
 
+std::string member_prefix(int i) { return "member " + std::to_string(i) + ": "; }
+
 int state_down(cvh_context *a, const void *d_state, void *out, size_t bytes)
 {
   HIPCHK(a, hipMemcpyAsync(a->h_state, d_state, bytes, hipMemcpyDeviceToHost, a->stream));

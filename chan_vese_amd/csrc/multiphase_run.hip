@@ -46,8 +46,6 @@ int pair_check(cvh_context *a, cvh_context *b, const char *what, bool need_image
   return pair_rules(ctxs, 2, a, b, what, "", need_images);
 }
 
-std::string member_prefix(int i) { return "member " + std::to_string(i) + ": "; }
-
 // The batch's own refusals, then every pair's; *all = [A0, B0, A1, B1, ...], the call's member list, is filled here
 int pairs_batch_check(cvh_context *const *as, cvh_context *const *bs, int n, const char *what, std::vector<cvh_context *> *all)
 {

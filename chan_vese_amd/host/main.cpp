@@ -467,6 +467,14 @@ Progress iterate(const Run &run, const Options &opt, const Inputs &in, Frames &f
     run_in_segments(ctx, opt.energy_every, opt.steps(), p, [&](bool, int) { energy_line(ctx, opt.run_channels(), p.steps); });
   } else if (opt.localized) {
     cvh_check(ctx, cvh_localized_run(ctx, opt.localized, opt.steps(), &p.steps, &p.norm, nullptr, 0, nullptr), "cvh_localized_run");
+  } else if (opt.edge > 0.0) {   // the map from the planes as every stage in front of the run has left them
+    cvh_check(ctx, cvh_edge_map(ctx, ctx, opt.edge), "cvh_edge_map");
+    if (!opt.dump_edge.empty()) {
+      std::vector<uint16_t> gq(in.n);
+      cvh_check(ctx, cvh_get_edge_map(ctx, gq.data()), "cvh_get_edge_map");
+      write_raw_or_exit(opt.dump_edge, gq.data(), in.n * sizeof(uint16_t));
+    }
+    cvh_check(ctx, cvh_geodesic_run(ctx, opt.steps(), &p.steps, &p.norm, nullptr, 0, nullptr), "cvh_geodesic_run");
   } else if (!opt.video) {
     cvh_check(ctx, cvh_run(ctx, opt.steps(), &p.steps, &p.norm), "cvh_run");
   } else {

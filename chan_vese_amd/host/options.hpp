@@ -42,7 +42,7 @@ const Spec kSpecs[] = {
     {"phases", 0, 1}, {"init2", 0, 2}, {"dump-labels", 0, 1}, {"localized", 0, 1}};
 // what came after the table above and the --help text were pinned (tests/test_cli.py, tests/golden/cli_refusals.json): long names only,
 // listed by --help --verbose
-const Spec kLaterSpecs[] = {{"split", 0, 1}, {"split-labels", 0, 1}};
+const Spec kLaterSpecs[] = {{"split", 0, 1}, {"split-labels", 0, 1}, {"edge", 0, 1}, {"dump-edge", 0, 1}};
 
 struct Parsed {
   std::vector<std::pair<std::string, std::vector<std::string>>> opts;
@@ -213,8 +213,9 @@ struct Options {
   uint8_t contour_bgr[3] = {255, 0, 0};            // blue
   bool segment = false, grayscale = false, video = false, overlay_text = false, select = false;
   // additions of this build
-  std::string dump_u, dump_mask, dump_planes, dump_labels, measure, contours, truth, truth_labels, init_mask, split_labels;
+  std::string dump_u, dump_mask, dump_planes, dump_labels, measure, contours, truth, truth_labels, init_mask, split_labels, dump_edge;
   int device = 0, math_mode = CVH_MATH_FAST, state_bits = 64, reinit_every = 0, levels = 1, energy_every = 0, phases = 2, localized = 0;
+  double edge = 0.0;   // --edge K: > 0 where given
   CleanArgs clean = {4, 0, 0, 0, 0};
   bool clean_mask = false;                         // a cleaning option is given: _selection, --dump-mask and --roi use the cleaned mask
   bool roi = false, energy = false, contours_all = false, contours_subpixel = false, verbose = false;
@@ -339,6 +340,10 @@ inline Options read_options(const Parsed &vm)
   read("localized", o.localized);   // --localized R (chanvese_hip.h, "Localised regions"): cvh_localized_run in place of cvh_run
   if (given("localized") && (o.localized < 1 || o.localized > 127))
     msg_exit("Window radius (--localized) must be between 1 and 127: " + std::to_string(o.localized) + ".");
+  read("edge", o.edge);             // --edge K (chanvese_hip.h, "Edge-weighted length"): cvh_edge_map behind the Perona-Malik stage, cvh_geodesic_run in place of cvh_run
+  read("dump-edge", o.dump_edge);
+  if (given("edge") && (!(o.edge > 0.0) || !std::isfinite(o.edge)))
+    msg_exit("Edge contrast (--edge) must be a finite number > 0: " + std::to_string(o.edge) + ".");
   o.segment = given("segment"); o.grayscale = given("grayscale"); o.video = given("video"); o.overlay_text = given("overlay-text");
   o.select = given("select"); o.roi = given("roi"); o.energy = given("energy"); o.verbose = given("verbose");
   o.contours_all = given("contours-all"); o.contours_subpixel = given("contours-subpixel");
@@ -458,6 +463,12 @@ inline Options read_options(const Parsed &vm)
         {o.phases == 4, "four phases (--phases 4)"}, {o.levels > 1, "a coarse-to-fine run (--levels)"}, {o.energy, "an energy line (--energy)"},
         {o.energy_every > 0, "an energy series (--energy-every)"}, {o.reinit_every > 0, "reinitialisation (--reinit)"},
         {o.video, "video output (-V)"}, {o.state_bits == 32, "FP32 state (--state 32)"}});
+  if (!o.dump_edge.empty() && !given("edge")) msg_exit("An edge map file (--dump-edge) needs an edge-weighted run (--edge).");
+  if (given("edge"))
+    refuse_combinations("Edge-weighted length (--edge)", {
+        {o.phases == 4, "four phases (--phases 4)"}, {o.localized != 0, "localised regions (--localized)"}, {o.levels > 1, "a coarse-to-fine run (--levels)"},
+        {o.energy, "an energy line (--energy)"}, {o.energy_every > 0, "an energy series (--energy-every)"},
+        {o.reinit_every > 0, "reinitialisation (--reinit)"}, {o.video, "video output (-V)"}, {o.state_bits == 32, "FP32 state (--state 32)"}});
   if (given("score-tol") && o.truth.empty()) msg_exit("A score tolerance (--score-tol) needs a ground truth (--truth).");
   if (!(score_tol >= 0.0) || !std::isfinite(score_tol)) msg_exit("Score tolerance must be a finite number >= 0.");
   o.score_tol2 = squared_capped(score_tol);
@@ -593,5 +604,10 @@ inline void print_help(bool later = false)
       "                                     --truth-labels and _selection then see the split objects; not with --phases 4, --morph\n"
       "  --split-labels arg                 write the object labels of --split (cut pixels included, 0 = background, 1 .. K in raster order of\n"
       "                                     the cores) as raw little-endian int32 (h*w), the way --dump-u writes its raw plane\n"
+      "  --edge arg                         K > 0: edge-weighted (geodesic) length term -- an edge map g = 1 / (1 + |grad I|^2 / K^2) is built on the\n"
+      "                                     device from the planes the run iterates on, after the Perona-Malik stage (-S), and mu weighs g times the\n"
+      "                                     contour length; honours --init / --rect / --circ / --disk / --init-mask; not with --phases 4, --localized,\n"
+      "                                     --levels, --energy, --energy-every, --reinit, -V, --state 32\n"
+      "  --dump-edge arg                    write the edge map of --edge as raw little-endian uint16 (h*w; 32768 = 1)\n"
       "\n";
 }

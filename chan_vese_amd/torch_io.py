@@ -4,6 +4,8 @@ Import torch FIRST (this module does): torch ships its own libamdhip64 and the l
 libchanvese_hip.so -- the rule of capi.py.  No torch type crosses the C ABI: tensors are passed as `data_ptr()` addresses and the
 current stream as its `cuda_stream` handle; the library orders its work against that stream with events and never synchronises it.
 """
+import math
+
 import torch
 
 from . import capi
@@ -197,10 +199,15 @@ class Segmenter:
     localized = R (1 .. 127; include/chanvese_hip.h, "Localised regions") makes the members run cvh_localized_run_batch -- region means over
     the (2 R + 1)^2 window of every pixel -- instead of the two-phase run, from whatever init= gives; everything after the run is
     unchanged.  The local force is small: start near the object (init="otsu", a rect, a disk, a mask) and raise mu.  It needs phases = 2
-    and levels = 1, and segment() refuses energy_every and reinit_every with it.  None (the default) is the plain path, call for call."""
+    and levels = 1, and segment() refuses energy_every and reinit_every with it.  None (the default) is the plain path, call for call.
+    edge = K (finite, > 0; include/chanvese_hip.h, "Edge-weighted length") makes segment() build every member's edge plane from its own
+    planes as they stand after the preprocessing above (cvh_edge_map_batch with that K) and iterate with cvh_geodesic_run_batch -- the
+    length term weighted by the plane -- instead of the two-phase run; edge_maps() returns the planes.  It needs phases = 2, levels = 1 and
+    no localized=, and segment() refuses energy_every and reinit_every with it.  None (the default) is the plain path, call for call."""
     levels = 1
     phases = 2
     localized = None
+    edge = None
     contexts_b = ()
     colour = None
     local = None
@@ -214,9 +221,14 @@ class Segmenter:
         return self.local[2] if self.local else self.rank[2] if self.rank else self.channels
 
     def __init__(self, n, h, w, channels=1, params=None, device=0, options=None, levels=1, colour=None, order="rgb", local=None, rank=None,
-                 phases=2, params2=None, localized=None):
+                 phases=2, params2=None, localized=None, edge=None):
         if n < 1:
             raise ValueError(f"n must be >= 1, got {n}")
+        if edge is not None:
+            if isinstance(edge, bool) or not isinstance(edge, (int, float)) or not math.isfinite(edge) or edge <= 0:
+                raise ValueError(f"edge must be None or a finite K > 0, got {edge!r}")
+            if phases == 4 or levels != 1 or localized is not None:
+                raise ValueError("edge= needs phases = 2, levels = 1 and no localized=: the edge-weighted run iterates one level set on one level")
         if localized is not None:
             if not isinstance(localized, int) or isinstance(localized, bool) or not 1 <= localized <= 127:
                 raise ValueError(f"localized must be None or a window radius 1 .. 127, got {localized!r}")
@@ -243,6 +255,7 @@ class Segmenter:
         self.pyramids = []
         self.phases = phases
         self.localized = localized
+        self.edge = None if edge is None else float(edge)
         self.contexts_b = []
         try:
             for _ in range(n if phases == 4 else 0):   # the second level sets: params2 (None: params), the same options
@@ -400,6 +413,8 @@ class Segmenter:
             raise ValueError("init2 (the start of the second level set) needs phases=4")
         if self.localized is not None and (reinit_every or energy_every):
             raise ValueError("localized=: reinit_every and energy_every are not built for the localised run")
+        if self.edge is not None and (reinit_every or energy_every):
+            raise ValueError("edge=: reinit_every and energy_every are not built for the edge-weighted run")
         kind, bits = None, None
         mask_init = isinstance(init, tuple) and len(init) == 2 and init[0] == "mask"
         if mask_init and self.levels > 1:
@@ -470,11 +485,24 @@ class Segmenter:
             res = [m[:2] for m in mon]
         elif self.localized is not None:
             res = [r[:2] for r in capi.localized_run_batch(self.contexts, self.localized, max_steps)]
+        elif self.edge is not None:   # (the planes the run iterates on, as every stage above has left them)
+            capi.edge_map_batch(self.contexts, self.contexts, self.edge)
+            res = [r[:2] for r in capi.geodesic_run_batch(self.contexts, max_steps)]
         else:
             res = capi.run_batch_with_reinit(self.contexts, max_steps, reinit_every)
         masks = torch.empty((self.n, self.h, self.w), dtype=torch.uint8, device=images.device)
         capi.get_mask_device_batch(self.contexts, [masks[i].data_ptr() for i in range(self.n)], invert, stream)
         return masks, [r[0] for r in res], [r[1] for r in res]
+
+    def edge_maps(self):
+        """edge=: the members' edge planes as the last segment() built them, a uint16 device tensor (N, H, W), g = value / 32768
+        (cvh_get_edge_map_device), valid for the next operation on the current stream."""
+        if self.edge is None:
+            raise ValueError("edge_maps needs edge=K")
+        out = torch.empty((self.n, self.h, self.w), dtype=torch.uint16, device=torch.device("cuda", self.device))
+        for i, ctx in enumerate(self.contexts):
+            ctx.get_edge_map(out[i].data_ptr(), self._stream())
+        return out
 
     def energies(self):
         """The Chan-Sandberg-Vese functional of every member's current level set -- after segment(): the final ones --, term by term

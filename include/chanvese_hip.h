@@ -1425,6 +1425,68 @@ extern int cvh_localized_run_batch(cvh_context *const *ctxs, int n, const int *r
 int cvh_localized_means(cvh_context *ctx, int radius, double *c1, double *c2, uint64_t *wq, uint64_t *a, uint64_t *s);
 void cvh_localized_geometry(int h, int w, int radius, int *cols, int *item_rows, int *items, int *strip_rows);   /* pure host arithmetic; 0 rows / items: not a plane or radius the calls take */
 
+/* ---- Edge-weighted length ---------------------------------------------------------------------------------------------------------
+ * Geodesic (edge-weighted) Chan-Vese, after Caselles, Kimmel and Sapiro and Bresson et al.: the length term mu int |grad H(u)| of every
+ * other flow of this library becomes mu int g |grad H(u)| with an edge-stopping weight g, about 1 in flat areas and near 0 on image
+ * edges: the contour is smoothed hard where nothing happens and left alone where the image says "boundary".  One level set, global
+ * means.  The reference has no such model; the definitions below ARE the contract.
+ * The EDGE PLANE gq of a context: h w uint16_t, row-major, values 0 .. 32768, g = gq 2^-15 exactly (g = 1 is representable; the step
+ * reads 2 bytes per pixel).  It is allocated by the first call that writes it and kept until replaced.  cvh_set_image*, the calls that
+ * write planes (Perona-Malik, colour, local, rank, restrict) and the level-set calls do NOT touch it: after the planes change, build it again.
+ * cvh_set_edge_map / cvh_get_edge_map move it from / to host memory; a value above 32768 is CVH_ERR_ARG, checked on the host before
+ * anything is touched.  cvh_set_edge_map_device / cvh_get_edge_map_device take device memory (2-byte aligned) and a stream: ordered
+ * behind `stream` and in front of what is enqueued on it later by events, as the other _device calls, and they do not make the host
+ * wait; there the range check is a device-side CLAMP to 32768.
+ * cvh_edge_map(dst, src, K) builds dst's edge plane from the planes of src as they are now; src may be dst, must have dst's h and w and
+ * device, and is only read; C below is src's channel count.  cvh_edge_map_batch does n pairs of any mix of shapes and channel counts
+ * in one launch; a destination may be listed once, sources freely.  Integer and IEEE, so that every value is defined exactly:
+ *     f_k = plane k as an integer, coordinates clamped to the plane (replicate border)
+ *     sx_k, sy_k = the 3 x 3 Sobel sums (weights 1, 2, 1; differences of the columns / rows +-1) as int32
+ *     m2 = sum_k (sx_k^2 + sy_k^2)                      (at most 3 * 2 * 1020^2)
+ *     den = ((64.0 * C) * K) * K, taken once on the host   (64: Sobel sums -> unit-spacing gradient; C: the mean over channels, as F / C)
+ *     gq = (uint16) rint(32768.0 / (1.0 + (double)m2 / den))   -- one conversion, a division, an addition, a division, round-half-even
+ * This is the edge-stopping function 1 / (1 + |grad I|^2 / K^2) of cvh_perona_malik.  CVH_ERR_ARG: K not finite, K <= 0, den not finite,
+ * NULL or differently shaped pairs, different devices; CVH_ERR_STATE: a source without an image.  Smoothing before the gradient is the
+ * caller's, with calls that exist: run cvh_perona_malik on the context first, or build the map from a second context that holds
+ * cvh_local_planes' mean.  There is no Gaussian here.
+ * The iteration, with nx, ny, H_eps, delta_eps and the border rule exactly those of the two-phase step:
+ *     Gx(p) = g(p) nx(p)      Gy(p) = g(p) ny(p)                                      (one rounding each)
+ *     kappa_g(r, c) = (c > 0 ? Gx(r, c) - Gx(r, c-1) : 0) + (r > 0 ? Gy(r, c) - Gy(r-1, c) : 0)
+ *     c1[k] = sum f_k H / sum H      c2[k] = sum f_k (1 - H) / sum (1 - H)   over all pixels, no guard (0 / 0 = NaN, as elsewhere);
+ *             the outside sums are taken as complements, (sum f_k - sum f_k H) / (h w - sum H): sum f_k is an exact integer
+ *     F = sum_k [ -lambda1[k] (f_k - c1[k])^2 + lambda2[k] (f_k - c2[k])^2 ]
+ *     d = dt (mu kappa_g - nu + F / C) delta_eps(u), folded as the two-phase combine;   u <- u + d
+ * With gq = 32768 everywhere this is the two-phase model.  Everything else reads as in "Four phases": Jacobi iteration; the stop rule
+ * ||d||_2 <= cvh_get_stop_condition tested after the update, the stopping iteration kept, later launches returning at once;
+ * "math_mode" STRICT and FAST (the form of H_eps chosen per wave and row by the row's own pixels); both agree with a numpy restatement
+ * to 1e-9 (tests/test_gpu_geodesic.py).  cvh_geodesic_run iterates until max_steps iterations are done (< 0: no bound) or the stop rule
+ * fires; steps_done, norm and trace may be NULL; row t of the trace (2 C + 1 doubles, at most trace_rows rows, *rows written) is
+ * [c1[0..C), c2[0..C), ||d||]: the means iteration t used and its norm.  The call settles the context, takes the initial sums itself
+ * and leaves the context exactly as cvh_set_levelset of the new doubles leaves it; a two-phase run continued afterwards is bit for bit
+ * what it is after cvh_set_levelset of the fetched doubles.  The edge plane is only read.  The host enqueues "sync_every" iterations at
+ * a time (two launches each) and waits once per chunk; cvh_last_run_ms is as for "Four phases".
+ * Determinism: partial sums per ITEM of the four-phase partition (cvh_geodesic_geometry: strips of *strip_rows rows x *cols columns,
+ * *items of them, a function of h and w alone) added in a fixed order by a one-workgroup launch; no atomics.  Two runs give the same
+ * bits; m + n iterations in one call equal m then n in two calls bit for bit, in both modes.
+ * cvh_geodesic_run_batch runs n contexts in shared launches with the meaning, the guarantees (a member is bit for bit its own single
+ * run, for any mix of shapes, channel counts, parameters and modes, in any order), the launches and the refusals of
+ * cvh_localized_run_batch; a batch of one launches the single call's by-value kernels.
+ * CVH_ERR_STATE: no image, no level set or no edge plane.  CVH_ERR_ARG: "state" = 32, h*w >= 2^28, a trace without rows or with
+ * trace_rows < 0, and for the batch n <= 0, a NULL array or member, the same context twice, different devices, 2^31 workgroups.
+ * Everything is checked before anything is touched; after a refusal the contexts are as they were.
+ * Not here: an edge-weighted energy (cvh_energy does not know g: it reports the unweighted functional), the resident flow, FP32 state,
+ * edge weighting inside four-phase or localised runs, pyramids or reinitialisation inside the run, a g-weighted balloon term. */
+int cvh_set_edge_map(cvh_context *ctx, const uint16_t *gq);   /* host, h w values */
+int cvh_get_edge_map(cvh_context *ctx, uint16_t *gq);
+int cvh_set_edge_map_device(cvh_context *ctx, const uint16_t *d_gq, void *stream);
+int cvh_get_edge_map_device(cvh_context *ctx, uint16_t *d_gq, void *stream);
+int cvh_edge_map(cvh_context *dst, cvh_context *src, double K);
+int cvh_edge_map_batch(cvh_context *const *dsts, cvh_context *const *srcs, int n, const double *K /* n */);
+int cvh_geodesic_run(cvh_context *ctx, int max_steps, int *steps_done, double *norm, double *trace, int trace_rows, int *rows);
+int cvh_geodesic_run_batch(cvh_context *const *ctxs, int n, int max_steps, int *steps_done /* n */, double *norms /* n */,
+                           double *const *traces /* n or NULL */, int trace_rows, int *rows /* n */);
+void cvh_geodesic_geometry(int h, int w, int *cols, int *strip_rows, int *items);   /* pure host arithmetic; 0 rows / items: not a plane the calls take */
+
 /* Library version string, e.g. "chanvese_hip 0.1 (gfx950)". */
 const char *cvh_version(void);
 
