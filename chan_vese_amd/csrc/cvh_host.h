@@ -6,7 +6,7 @@
 // level sets), components_run.hip (connected components, and MaskSource: the raw or cleaned mask every mask-derived call starts from),
 // pyramid_run.hip (coarse-to-fine), colour_run.hip (colour spaces), window_run.hip (local statistics and rank planes: the windowed-plane calls), energy_run.hip (the functional's terms), score_run.hip (mask scores),
 // morph_run.hip (mask morphology, mask starts), split_run.hip (object split), measure_run.hip (component measures), contour_run.hip (contours), overlap_run.hip
-// (component overlaps), multiphase_run.hip (four phases: a pair of contexts iterated together), localized_run.hip (localised regions), geodesic_run.hip (edge-weighted length), march_run.hip (the driver under those three), edge_run.hip (the edge plane), debug_exports.hip (diagnostics).  Kernel
+// (component overlaps), multiphase_run.hip (four phases: a pair of contexts iterated together), localized_run.hip (localised regions), geodesic_run.hip (edge-weighted length), march_run.hip (the driver under those three; march_flow.h: their one call sequence, over each file's flow description), edge_run.hip (the edge plane), debug_exports.hip (diagnostics).  Kernel
 // sources do not include it.
 #pragma once
 #include <limits.h>
@@ -329,21 +329,29 @@ void checkerboard_factors(int h, int w, double *out);   // api.hip: out[0 .. h-1
 void levelset_target(const cvh_context *c, CvhIoMember *m);
 int ensure_workspace(cvh_context *c, void **slot, size_t bytes, const char *name, bool mirror = true);
 
-// march_run.hip: what the four-phase and localised flows share -- "iterate the level sets of N contexts on the leader's stream"
+// march_run.hip: what the four-phase, localised and geodesic flows share -- "iterate the level sets of N contexts on the leader's stream".
+// march_flow.h runs the whole call over a flow's description: ready, prepare, open, classes, records, lay-out, one-or-upload, iterate, results
 void fill_front_args(const cvh_context *c, CvhFrontArgs *f);
+// alpha = dt mu, beta = dt / C, gamma = -dt nu, the lambdas and stop = tol * stop_norm of c's equation into a record's fields
+void march_params(const cvh_context *c, double *alpha, double *beta, double *gamma, double *lambda1, double *lambda2, double *stop);
 std::string member_prefix(int i);   // "member 3: ": what opens a batch's message about member i
+// What every march call refuses for a member m[0 .. per-1] before anything is touched, in this order: "state" = 32, h * w >= 2^28, no
+// image (need_images), no level set.  The message goes to lead[0] and opens with `who` ("" or "member 3: "); it names "the context"
+// (per = 1) or "context a" / "context b" (per = 2)
+int march_rules(cvh_context *const *lead, int nlead, cvh_context *const *m, int per, const char *what, const char *who, bool need_images);
+void march_strip_geometry(int h, int w, int *cols, int *strip_rows, int *items);   // cvh_multiphase_geometry / cvh_geodesic_geometry
 int state_down(cvh_context *a, const void *d_state, void *out, size_t bytes);   // on a's stream, through its pinned state slots; waits
 // The leader's table of a call: *h is `host_bytes` of zeroed pinned memory whose first `dev_bytes` the caller uploads to *d.  Every call
 // that uses it ends with a host wait on the leader's stream, so the pinned block is free when the next one begins.
 int march_stage(cvh_context *lead, size_t dev_bytes, size_t host_bytes, unsigned char **h, unsigned char **d);
-// One run of n members of `per` contexts each (1: a localised member; 2: a four-phase pair A, B); ctxs is flat, [member][role], the
-// leader is ctxs[0]; who(k) opens what a message says about context k ("", "context a: ", "member 3: ", ...).  The caller has checked
-// the members; then
-//   begin:   refuses a trace's bad arguments, settles max_steps;                 -- the caller makes the members and their workspaces ready --
+// One run of n members of `per` contexts each (1: a localised or geodesic member; 2: a four-phase pair A, B); ctxs is flat,
+// [member][role], the leader is ctxs[0]; who(k) opens what a message says about context k ("", "context a: ", "member 3: ", ...).  Its
+// one caller is march_run (march_flow.h), after the flow has checked the members; then
+//   begin:   refuses a trace's bad arguments, settles max_steps;                 -- march_run makes the members and their workspaces ready --
 //   open:    grows every member's own trace table to the rows wanted, stages the leader's table -- [n records of rec_size bytes][n state
 //            slots of state_stride bytes, each beginning with a CvhMarchCount] -- and opens the call;
-//                                                                               -- the caller fills the records (record, d_state, cur) --
-//   upload:  the table goes up, ONCE per call;                                   -- the caller enqueues what precedes t = 0 --
+//                                                                               -- march_run fills the records (record, d_state, cur) --
+//   upload:  the table goes up, ONCE per call;                                   -- march_run enqueues what the flow puts in front of t = 0 --
 //   iterate: times the run, enqueues the leader's sync_every iterations at a time through step(parity) -- iteration t has parity t & 1 and
 //            reads buffer (cur + t) & 1 of every context -- and copies the state table (own_state, if set) down behind each chunk: ONE copy and ONE wait per
 //            chunk, whatever n; ends when every member has stopped or max_steps iterations are enqueued.  Then it brings every level set
@@ -375,9 +383,7 @@ struct MarchRun {
 // the (channel count, math mode) classes of a march launch: members of one class share a kernel instantiation and a section of the table
 constexpr int kMarchClasses = 4;
 inline int march_class(const cvh_context *c) { return (c->C == 1 ? 0 : 2) + (use_fast(c) ? 1 : 0); }
-struct MarchClass { int first = 0, n = 0, C = 1, fast = 0; unsigned grid = 0, grid2 = 0; };   // records first .. first + n - 1; the sums of their grids
-// order[r]: the member record r describes -- members sorted by class, in member order inside a class; cls[k]: class k's section
-void march_classes(cvh_context *const *leaders, int n, int stride, std::vector<int> *order, MarchClass *cls);
+struct MarchClass { int first = 0, n = 0, C = 1, fast = 0; unsigned grid = 0, grid2 = 0; };   // records first .. first + n - 1; the sums of their grids (march_flow.h)
 
 // components_run.hip: the mask of every member that a call starts from -- raw, or cleaned as cvh_get_mask_clean* cleans it -- for the
 // components calls there and for measure_run.hip, overlap_run.hip, contour_run.hip and morph_run.hip.  The first member table of such a

@@ -1,5 +1,7 @@
-// march_run.hip — the host driver under cvh_multiphase_run[_batch] and cvh_localized_run[_batch] (MarchRun, cvh_host.h): the level sets of
-// N members (contexts, or pairs of contexts) are iterated together on the leader's stream; a single call is a batch of one member.
+// march_run.hip — the host driver under the marching-wave calls: cvh_multiphase_run[_batch], cvh_localized_run[_batch] and
+// cvh_geodesic_run[_batch] (MarchRun, cvh_host.h; the call sequence around it, written once over a flow description, is march_flow.h's).
+// The level sets of N members (contexts, or pairs of contexts) are iterated together on the leader's stream; a single call is a batch
+// of one member.
 // Data flow: the leader's table holds one argument record per member -- both buffers of every level set in it -- and one state slot
 // per member; it is uploaded once per call.  Iteration t reads d_u[(current + t) & 1] of each context and writes the other buffer of
 // its pair -- the contexts' own ping-pong pairs; the parity t & 1 is a kernel argument -- with no copy of a level set but at most ONE
@@ -52,18 +54,39 @@ int march_stage(cvh_context *lead, size_t dev_bytes, size_t host_bytes, unsigned
   return CVH_OK;
 }
 
-void march_classes(cvh_context *const *leaders, int n, int stride, std::vector<int> *order, MarchClass *cls)
+// the folded parameters of one level set's equation, as fill_args (csv_run.hip): the addWeighted form of src/main.cpp:985
+void march_params(const cvh_context *c, double *alpha, double *beta, double *gamma, double *lambda1, double *lambda2, double *stop)
 {
-  order->clear();
-  for (int k = 0; k < kMarchClasses; ++k) {
-    cls[k] = MarchClass{};
-    cls[k].first = (int)order->size();
-    cls[k].C = k < 2 ? 1 : 3;
-    cls[k].fast = k & 1;
-    for (int i = 0; i < n; ++i)
-      if (march_class(leaders[(size_t)i * stride]) == k) order->push_back(i);
-    cls[k].n = (int)order->size() - cls[k].first;
+  *alpha = c->p.mu * c->p.dt;
+  *beta = (1.0 / c->C) * c->p.dt;
+  *gamma = -c->p.nu * c->p.dt;
+  for (int k = 0; k < c->C; ++k) { lambda1[k] = c->p.lambda1[k]; lambda2[k] = c->p.lambda2[k]; }
+  *stop = c->p.tol * c->stop_norm;
+}
+
+int march_rules(cvh_context *const *lead, int nlead, cvh_context *const *m, int per, const char *what, const char *who, bool need_images)
+{
+  auto noun = [&](int e) { return per == 1 ? std::string("the context") : std::string("context ") + "ab"[e]; };
+  for (int e = 0; e < per; ++e)
+    if (m[e]->state_bits == 32)
+      return batch_fail(lead, nlead, CVH_ERR_ARG, "%s: %s%s has \"state\" = 32: %s", what, who, noun(e).c_str(),
+                        per == 1 ? "the call iterates an FP64 level set" : "the pair iterates FP64 level sets");
+  if (m[0]->n >= ((size_t)1 << 28)) return batch_fail(lead, nlead, CVH_ERR_ARG, "%s: %s%d x %d is too large, h * w must stay below 2^28", what, who, m[0]->h, m[0]->w);
+  for (int e = 0; e < per; ++e) {
+    if (need_images && !m[e]->have_image)
+      return batch_fail(lead, nlead, CVH_ERR_STATE, "%s: %s%s has no image (call cvh_set_image first)", what, who, noun(e).c_str());
+    if (!m[e]->have_u) return batch_fail(lead, nlead, CVH_ERR_STATE, "%s: %s%s has no level set", what, who, noun(e).c_str());
   }
+  return CVH_OK;
+}
+
+void march_strip_geometry(int h, int w, int *cols, int *strip_rows, int *items)
+{
+  CvhMpGeom g{0, 0, 0, 0, 0};
+  if (h > 0 && w > 0 && (long long)h * w < (1ll << 28)) g = cvh_mp_geometry(h, w);
+  if (cols) *cols = CVH_MARCH_COLS;
+  if (strip_rows) *strip_rows = g.strip_rows;
+  if (items) *items = g.nitems;
 }
 
 int MarchRun::begin(int max_steps_, double *const *traces_, int trace_rows_, int *rows_)
