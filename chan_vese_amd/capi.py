@@ -7,95 +7,14 @@ its own libamdhip64.so.7 and the loader then shares that one runtime with this l
 import ctypes as C
 import dataclasses
 import math
-import os
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-# CHANVESE_HIP_LIB selects another BUILD of the same library (A/B variants under csrc/variants/, tools/build_variant.sh)
-LIB_PATH = os.environ.get("CHANVESE_HIP_LIB") or os.path.join(_HERE, "csrc", "libchanvese_hip.so")
-
-CVH_OK = 0
-OP_DELTA, OP_HEAVISIDE, OP_ONE_MINUS_HEAVISIDE = 0, 1, 2
-MATH_DEFAULT, MATH_STRICT, MATH_FAST = 0, 1, 2
-
-# every symbol include/chanvese_hip.h declares
-EXPORTS = [
-    "cvh_default_params", "cvh_device_count", "cvh_create", "cvh_destroy", "cvh_last_error",
-    "cvh_set_params", "cvh_set_option", "cvh_set_image", "cvh_get_image", "cvh_set_levelset",
-    "cvh_get_levelset", "cvh_init_checkerboard", "cvh_levelset_checkerboard_host", "cvh_run",
-    "cvh_enqueue_steps", "cvh_warm", "cvh_sync", "cvh_reset_run", "cvh_get_means", "cvh_get_trace",
-    "cvh_get_stop_condition", "cvh_get_mask", "cvh_get_contour", "cvh_separate", "cvh_perona_malik",
-    "cvh_pm_trip_count", "cvh_last_run_ms", "cvh_last_pm_ms", "cvh_ppf_apply",
-    "cvh_ppf_apply_device", "cvh_version", "cvh_launch_info", "cvh_enqueue_steps_batch", "cvh_run_batch",
-    "cvh_perona_malik_batch",
-    "cvh_set_image_device", "cvh_get_image_device", "cvh_set_levelset_device", "cvh_get_levelset_device",
-    "cvh_get_mask_device", "cvh_set_image_device_batch", "cvh_init_checkerboard_batch", "cvh_get_mask_device_batch",
-    "cvh_reinit", "cvh_reinit_batch",
-    "cvh_components", "cvh_components_batch", "cvh_get_mask_clean", "cvh_get_mask_clean_device", "cvh_get_mask_clean_device_batch",
-    "cvh_histogram", "cvh_histogram_batch", "cvh_otsu_from_histogram", "cvh_otsu_threshold", "cvh_init_threshold", "cvh_init_threshold_batch",
-    "cvh_init_otsu", "cvh_init_otsu_batch", "cvh_init_rect", "cvh_init_rect_batch", "cvh_init_disk", "cvh_init_disk_batch",
-    "cvh_restrict_image", "cvh_restrict_image_batch", "cvh_prolong_levelset", "cvh_prolong_levelset_batch",
-    "cvh_convert_colour", "cvh_convert_colour_batch", "cvh_luma_image", "cvh_luma_image_batch",
-    "cvh_local_planes", "cvh_local_planes_batch",
-    "cvh_rank_planes", "cvh_rank_planes_batch",
-    "cvh_energy", "cvh_energy_batch",
-    "cvh_score_mask", "cvh_score_mask_device", "cvh_score_mask_device_batch",
-    "cvh_measure", "cvh_measure_batch", "cvh_region_shape_of",
-    "cvh_overlaps", "cvh_overlaps_device", "cvh_overlaps_device_batch", "cvh_match_overlaps",
-    "cvh_contours", "cvh_contours_device", "cvh_contours_device_batch",
-    "cvh_contours_subpixel", "cvh_contours_subpixel_device", "cvh_contours_subpixel_device_batch", "cvh_contour_subpixel_measure",
-    "cvh_get_mask_morph", "cvh_get_mask_morph_device", "cvh_get_mask_morph_device_batch", "cvh_morph_levelset", "cvh_morph_levelset_batch",
-    "cvh_init_mask", "cvh_init_mask_device", "cvh_init_mask_device_batch",
-    "cvh_split", "cvh_split_host", "cvh_split_batch", "cvh_split_levelset", "cvh_split_levelset_batch", "cvh_split_geometry",
-    "cvh_multiphase_run", "cvh_multiphase_run_batch", "cvh_multiphase_means", "cvh_multiphase_labels", "cvh_multiphase_labels_device", "cvh_multiphase_geometry",
-    "cvh_localized_run", "cvh_localized_run_batch", "cvh_localized_means", "cvh_localized_geometry",
-    "cvh_set_edge_map", "cvh_get_edge_map", "cvh_set_edge_map_device", "cvh_get_edge_map_device", "cvh_edge_map", "cvh_edge_map_batch",
-    "cvh_geodesic_run", "cvh_geodesic_run_batch", "cvh_geodesic_geometry",
-]
-# "Mask morphology": the operations of cvh_get_mask_morph* / cvh_morph_levelset*, by code and by name
-MORPH_NONE, MORPH_DILATE, MORPH_ERODE, MORPH_OPEN, MORPH_CLOSE = 0, 1, 2, 3, 4
-MORPH_OPS = {"none": MORPH_NONE, "dilate": MORPH_DILATE, "erode": MORPH_ERODE, "open": MORPH_OPEN, "close": MORPH_CLOSE}
-# struct cvh_component: row k - 1 of a component table describes label k (first = smallest flat index; the box is inclusive)
-COMPONENT_DTYPE = np.dtype([("first", np.uint32), ("area", np.uint32), ("x0", np.int32), ("y0", np.int32), ("x1", np.int32), ("y1", np.int32)])
-# struct cvh_region (128 bytes): row k - 1 of a measure table describes label k ("Component measures" in include/chanvese_hip.h)
-REGION_DTYPE = np.dtype([("first", np.uint32), ("area", np.uint32), ("x0", np.int32), ("y0", np.int32), ("x1", np.int32), ("y1", np.int32),
-                         ("border", np.uint32), ("reserved", np.uint32)] +
-                        [(f, np.uint64) for f in ("perimeter", "sx", "sy", "sxx", "syy", "sxy")] + [("s1", np.uint64, 3), ("s2", np.uint64, 3)])
-# struct cvh_region_shape: what cvh_region_shape_of derives from a row
-REGION_SHAPE_DTYPE = np.dtype([(f, np.float64) for f in ("cx", "cy", "mu20", "mu02", "mu11", "theta", "major", "minor")] +
-                              [("mean", np.float64, 3), ("var", np.float64, 3)])
-# struct cvh_contour_loop (32 bytes): one closed loop of the mask's boundary ("Contours" in include/chanvese_hip.h)
-CONTOUR_LOOP_DTYPE = np.dtype([("first", np.uint32), ("edges", np.uint32), ("points", np.uint32), ("pad", np.uint32), ("offset", np.uint64),
-                               ("area2", np.int64)])
-# struct cvh_overlap (16 bytes): one row of the contingency table ("Component overlaps" in include/chanvese_hip.h)
-OVERLAP_DTYPE = np.dtype([("a", np.int32), ("b", np.int32), ("count", np.uint32), ("pad", np.uint32)])
-LAYOUT_PLANAR, LAYOUT_INTERLEAVED = 0, 1
-# "Colour spaces": which plane is which primary, and the spaces cvh_convert_colour knows
-ORDERS = {"bgr": 0, "rgb": 1}
-COLOUR_SPACES = {"ycrcb": 1, "yuv": 2}
-# "Local statistics": what plane k of the destination of cvh_local_planes becomes, by code and -- whole tuples -- by name
-LOCAL_COPY, LOCAL_MEAN, LOCAL_DEV = 0, 1, 2
-LOCAL_RADIUS_MAX = 127
-LOCAL_WHATS = {"mean": (LOCAL_MEAN,) * 3, "dev": (LOCAL_DEV,) * 3, "stack": (LOCAL_COPY, LOCAL_MEAN, LOCAL_DEV)}
-# "Rank planes": what plane k of the destination of cvh_rank_planes becomes, by code and -- every plane alike -- by name
-RANK_COPY, RANK_MIN, RANK_MAX, RANK_MEDIAN, RANK_OPEN, RANK_CLOSE, RANK_TOPHAT, RANK_BOTHAT = range(8)
-RANK_RADIUS_MAX, RANK_MEDIAN_RADIUS_MAX = 127, 7
-RANK_WHATS = {"min": RANK_MIN, "max": RANK_MAX, "median": RANK_MEDIAN, "open": RANK_OPEN, "close": RANK_CLOSE, "tophat": RANK_TOPHAT,
-              "bothat": RANK_BOTHAT}
-
-
-class Params(C.Structure):
-    """struct cvh_params (src/main.cpp:731-734 of the reference)."""
-    _fields_ = [("mu", C.c_double), ("nu", C.c_double), ("dt", C.c_double),
-                ("eps", C.c_double), ("tol", C.c_double),
-                ("lambda1", C.c_double * 3), ("lambda2", C.c_double * 3)]
-
-
-class EnergyTerms(C.Structure):
-    """struct cvh_energy_terms ("Energy" in include/chanvese_hip.h)."""
-    _fields_ = [("total", C.c_double), ("length", C.c_double), ("area", C.c_double),
-                ("fit_in", C.c_double * 3), ("fit_out", C.c_double * 3), ("c1", C.c_double * 3), ("c2", C.c_double * 3)]
+from ._abi import (COLOUR_SPACES, COMPONENT_DTYPE, CONTOUR_LOOP_DTYPE, CVH_OK, EXPORTS, LAYOUT_INTERLEAVED, LAYOUT_PLANAR, LIB_PATH, LOCAL_COPY, LOCAL_DEV,
+                   LOCAL_MEAN, LOCAL_RADIUS_MAX, LOCAL_WHATS, MATH_DEFAULT, MATH_FAST, MATH_STRICT, MORPH_CLOSE, MORPH_DILATE, MORPH_ERODE, MORPH_NONE,
+                   MORPH_OPEN, MORPH_OPS, OP_DELTA, OP_HEAVISIDE, OP_ONE_MINUS_HEAVISIDE, ORDERS, OVERLAP_DTYPE, RANK_BOTHAT, RANK_CLOSE, RANK_COPY, RANK_MAX,
+                   RANK_MEDIAN, RANK_MEDIAN_RADIUS_MAX, RANK_MIN, RANK_OPEN, RANK_RADIUS_MAX, RANK_TOPHAT, RANK_WHATS, REGION_DTYPE, REGION_SHAPE_DTYPE,
+                   SIGNATURES, CvhError, EnergyTerms, MaskScore, Match, Params, lib)
 
 
 @dataclasses.dataclass(frozen=True)
@@ -114,12 +33,6 @@ class Energy:
 
 def _energy_of(t, channels):
     return Energy(t.total, t.length, t.area, *(tuple(getattr(t, f)[k] for k in range(channels)) for f in ("fit_in", "fit_out", "c1", "c2")))
-
-
-class MaskScore(C.Structure):
-    """struct cvh_mask_score ("Mask scores" in include/chanvese_hip.h)."""
-    _fields_ = [(f, C.c_uint64) for f in ("tp", "fp", "fn", "tn", "surf_m", "surf_t", "within_m", "within_t", "dist_m_q16", "dist_t_q16")] + \
-               [("hd2_m", C.c_uint32), ("hd2_t", C.c_uint32), ("defined", C.c_int32), ("pad", C.c_int32)]
 
 
 SCORE_FIELDS = tuple(f for f, _ in MaskScore._fields_ if f != "pad")
@@ -166,11 +79,6 @@ class Score:
     @property
     def surface_dice(self):
         return _ratio(self.within_m + self.within_t, self.surf_m + self.surf_t) if self.defined else math.nan
-
-
-class Match(C.Structure):
-    """struct cvh_match ("Component overlaps" in include/chanvese_hip.h)."""
-    _fields_ = [(f, C.c_uint32) for f in ("objects_a", "objects_b", "tp", "fp", "fn", "pad")]
 
 
 @dataclasses.dataclass(frozen=True)
@@ -251,175 +159,91 @@ def _morph_r2(r2, radius):
     return r2
 
 
-class CvhError(RuntimeError):
-    def __init__(self, code, msg):
-        super().__init__(f"chanvese_hip error {code}: {msg}")
-        self.code = code
-
-
-_lib = None
-
-
-def lib():
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise ImportError(
-            f"{LIB_PATH} is missing: build the HIP extension first "
-            "(python -c 'import __graft_entry__ as g; g.build()' or make -C chan_vese_amd/csrc). "
-            "There is no CPU fallback.")
-    L = C.CDLL(LIB_PATH)
-    dp, u8p, ip = C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(C.c_int)
-    u8pp, vp, lp = C.POINTER(u8p), C.c_void_p, C.POINTER(C.c_long)
-    sig = {
-        "cvh_default_params": (None, [C.POINTER(Params)]),
-        "cvh_device_count": (C.c_int, [ip]),
-        "cvh_create": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.POINTER(Params), C.c_int]),
-        "cvh_destroy": (None, [vp]),
-        "cvh_last_error": (C.c_char_p, [vp]),
-        "cvh_set_params": (C.c_int, [vp, C.POINTER(Params)]),
-        "cvh_set_option": (C.c_int, [vp, C.c_char_p, C.c_long]),
-        "cvh_set_image": (C.c_int, [vp, u8pp]),
-        "cvh_get_image": (C.c_int, [vp, u8pp]),
-        "cvh_set_levelset": (C.c_int, [vp, dp]),
-        "cvh_get_levelset": (C.c_int, [vp, dp]),
-        "cvh_init_checkerboard": (C.c_int, [vp]),
-        "cvh_levelset_checkerboard_host": (None, [C.c_int, C.c_int, dp]),
-        "cvh_run": (C.c_int, [vp, C.c_int, ip, dp]),
-        "cvh_enqueue_steps": (C.c_int, [vp, C.c_int]),
-        "cvh_warm": (C.c_int, [vp, C.c_int]),
-        "cvh_sync": (C.c_int, [vp, ip, dp, ip]),
-        "cvh_reset_run": (C.c_int, [vp]),
-        "cvh_get_means": (C.c_int, [vp, dp, dp]),
-        "cvh_get_trace": (C.c_int, [vp, dp, C.c_int, ip]),
-        "cvh_get_stop_condition": (C.c_int, [vp, dp]),
-        "cvh_get_mask": (C.c_int, [vp, u8p, C.c_int]),
-        "cvh_get_contour": (C.c_int, [vp, u8p]),
-        "cvh_separate": (C.c_int, [vp, u8p, C.c_int, u8p]),
-        "cvh_perona_malik": (C.c_int, [vp, C.c_double, C.c_double, C.c_double]),
-        "cvh_pm_trip_count": (C.c_int, [C.c_double, C.c_double]),
-        "cvh_last_run_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
-        "cvh_last_pm_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
-        "cvh_ppf_apply": (C.c_int, [dp, C.c_int, C.c_long, C.c_long, C.c_int, C.c_double, C.c_int]),
-        "cvh_ppf_apply_device": (C.c_int, [dp, C.c_long, C.c_int, C.c_double, vp]),
-        "cvh_version": (C.c_char_p, []),
-        "cvh_launch_info": (C.c_int, [vp, C.c_int, C.c_char_p, C.c_int]),
-        "cvh_enqueue_steps_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int]),
-        "cvh_run_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int, ip, dp]),
-        "cvh_perona_malik_batch": (C.c_int, [C.POINTER(vp), C.c_int, dp, dp, dp]),
-        "cvh_set_image_device": (C.c_int, [vp, vp, C.c_int, vp]),
-        "cvh_get_image_device": (C.c_int, [vp, vp, C.c_int, vp]),
-        "cvh_set_levelset_device": (C.c_int, [vp, vp, C.c_int, vp]),
-        "cvh_get_levelset_device": (C.c_int, [vp, vp, C.c_int, vp]),
-        "cvh_get_mask_device": (C.c_int, [vp, vp, C.c_int, vp]),
-        "cvh_set_image_device_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.POINTER(vp), C.c_int, vp]),
-        "cvh_init_checkerboard_batch": (C.c_int, [C.POINTER(vp), C.c_int]),
-        "cvh_get_mask_device_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.POINTER(vp), C.c_int, vp]),
-        "cvh_reinit": (C.c_int, [vp, ip]),
-        "cvh_reinit_batch": (C.c_int, [C.POINTER(vp), C.c_int, ip]),
-        "cvh_components": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.c_int, ip, vp]),
-        "cvh_components_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.POINTER(vp), ip, vp]),
-        "cvh_get_mask_clean": (C.c_int, [vp, u8p, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int]),
-        "cvh_get_mask_clean_device": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, vp]),
-        "cvh_get_mask_clean_device_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.POINTER(vp), C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, vp]),
-        "cvh_histogram": (C.c_int, [vp, vp, C.c_int, ip]),
-        "cvh_histogram_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.POINTER(vp), ip]),
-        "cvh_otsu_from_histogram": (C.c_int, [vp, C.c_int, ip]),
-        "cvh_otsu_threshold": (C.c_int, [vp, ip]),
-        "cvh_init_threshold": (C.c_int, [vp, C.c_int, C.c_double, C.c_double]),
-        "cvh_init_threshold_batch": (C.c_int, [C.POINTER(vp), C.c_int, ip, C.c_double, C.c_double]),
-        "cvh_init_otsu": (C.c_int, [vp, ip, C.c_double, C.c_double]),
-        "cvh_init_otsu_batch": (C.c_int, [C.POINTER(vp), C.c_int, ip, C.c_double, C.c_double]),
-        "cvh_init_rect": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double]),
-        "cvh_init_rect_batch": (C.c_int, [C.POINTER(vp), C.c_int, ip, C.c_double, C.c_double]),
-        "cvh_init_disk": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double]),
-        "cvh_init_disk_batch": (C.c_int, [C.POINTER(vp), C.c_int, ip, C.c_double, C.c_double]),
-        "cvh_restrict_image": (C.c_int, [vp, vp]),
-        "cvh_restrict_image_batch": (C.c_int, [C.POINTER(vp), C.POINTER(vp), C.c_int]),
-        "cvh_prolong_levelset": (C.c_int, [vp, vp]),
-        "cvh_prolong_levelset_batch": (C.c_int, [C.POINTER(vp), C.POINTER(vp), C.c_int]),
-        "cvh_convert_colour": (C.c_int, [vp, C.c_int, C.c_int, C.c_int]),
-        "cvh_convert_colour_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_int]),
-        "cvh_luma_image": (C.c_int, [vp, vp, C.c_int]),
-        "cvh_luma_image_batch": (C.c_int, [C.POINTER(vp), C.POINTER(vp), C.c_int, C.c_int]),
-        "cvh_local_planes": (C.c_int, [vp, vp, C.c_int, ip]),
-        "cvh_local_planes_batch": (C.c_int, [C.POINTER(vp), C.POINTER(vp), C.c_int, ip, ip]),
-        "cvh_rank_planes": (C.c_int, [vp, vp, C.c_int, ip]),
-        "cvh_rank_planes_batch": (C.c_int, [C.POINTER(vp), C.POINTER(vp), C.c_int, ip, ip]),
-        "cvh_energy": (C.c_int, [vp, C.POINTER(EnergyTerms)]),
-        "cvh_energy_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.POINTER(EnergyTerms)]),
-        "cvh_score_mask": (C.c_int, [vp, u8p, C.c_int, C.c_uint32, C.POINTER(MaskScore)]),
-        "cvh_score_mask_device": (C.c_int, [vp, vp, C.c_int, C.c_uint32, C.POINTER(MaskScore), vp]),
-        "cvh_score_mask_device_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.POINTER(vp), C.c_int, C.c_uint32, C.POINTER(MaskScore), vp]),
-        "cvh_measure": (C.c_int, [vp, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, vp, C.c_int, ip, vp]),
-        "cvh_measure_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, C.POINTER(vp), ip, ip, vp]),
-        "cvh_region_shape_of": (C.c_int, [vp, C.c_int, vp]),
-        "cvh_overlaps": (C.c_int, [vp, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, vp, vp, C.c_long, lp, ip]),
-        "cvh_overlaps_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, vp, vp, C.c_long, lp, ip, vp]),
-        "cvh_overlaps_device_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, C.POINTER(vp), C.POINTER(vp),
-                                                lp, lp, ip, vp]),
-        "cvh_match_overlaps": (C.c_int, [vp, C.c_long, C.c_uint32, C.c_uint32, vp, C.c_int, C.POINTER(Match)]),
-        "cvh_contours": (C.c_int, [vp, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, C.c_int, vp, C.c_long, vp, C.c_long, lp, lp]),
-        "cvh_contours_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, C.c_int, vp, C.c_long, vp, C.c_long, lp, lp, vp]),
-        "cvh_contours_device_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, C.c_int, C.POINTER(vp), lp,
-                                                C.POINTER(vp), lp, lp, lp, vp]),
-        "cvh_contours_subpixel": (C.c_int, [vp, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, vp, C.c_long, vp, C.c_long, lp, lp]),
-        "cvh_contours_subpixel_device": (C.c_int, [vp, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, vp, C.c_long, vp, C.c_long, lp, lp, vp]),
-        "cvh_contours_subpixel_device_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, C.POINTER(vp), lp,
-                                                         C.POINTER(vp), lp, lp, lp, vp]),
-        "cvh_contour_subpixel_measure": (C.c_int, [vp, C.c_long, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
-        "cvh_get_mask_morph": (C.c_int, [vp, u8p, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, C.c_int, C.c_uint32]),
-        "cvh_get_mask_morph_device": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, C.c_int, C.c_uint32, vp]),
-        "cvh_get_mask_morph_device_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.POINTER(vp), C.c_int, C.c_int, C.c_long, C.c_long, C.c_int,
-                                                      C.c_int, C.POINTER(C.c_uint32), vp]),
-        "cvh_morph_levelset": (C.c_int, [vp, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, C.c_int, C.c_uint32, C.c_double, C.c_double]),
-        "cvh_morph_levelset_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, C.c_int,
-                                               C.POINTER(C.c_uint32), C.c_double, C.c_double]),
-        "cvh_init_mask": (C.c_int, [vp, u8p, C.c_double, C.c_double]),
-        "cvh_init_mask_device": (C.c_int, [vp, vp, C.c_double, C.c_double, vp]),
-        "cvh_init_mask_device_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.POINTER(vp), C.c_double, C.c_double, vp]),
-        "cvh_split": (C.c_int, [vp, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, C.c_uint32, vp, vp, C.c_int, ip, vp]),
-        "cvh_split_host": (C.c_int, [vp, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, C.c_uint32, vp, vp, C.c_int, ip]),
-        "cvh_split_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, C.POINTER(C.c_uint32), C.POINTER(vp),
-                                      ip, vp]),
-        "cvh_split_levelset": (C.c_int, [vp, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, C.c_uint32, C.c_double, C.c_double]),
-        "cvh_split_levelset_batch": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_int, C.POINTER(C.c_uint32),
-                                               C.c_double, C.c_double]),
-        "cvh_split_geometry": (None, [ip, ip, ip]),
-        "cvh_multiphase_run": (C.c_int, [vp, vp, C.c_int, ip, dp, dp, C.c_int, ip]),
-        "cvh_multiphase_run_batch": (C.c_int, [vp, vp, C.c_int, C.c_int, ip, dp, vp, C.c_int, ip]),
-        "cvh_multiphase_means": (C.c_int, [vp, vp, dp]),
-        "cvh_multiphase_labels": (C.c_int, [vp, vp, u8p]),
-        "cvh_multiphase_labels_device": (C.c_int, [vp, vp, vp, vp]),
-        "cvh_multiphase_geometry": (None, [C.c_int, C.c_int, ip, ip, ip]),
-        "cvh_localized_run": (C.c_int, [vp, C.c_int, C.c_int, ip, dp, dp, C.c_int, ip]),
-        "cvh_localized_run_batch": (C.c_int, [vp, C.c_int, ip, C.c_int, ip, dp, vp, C.c_int, ip]),
-        "cvh_localized_means": (C.c_int, [vp, C.c_int, dp, dp, vp, vp, vp]),
-        "cvh_localized_geometry": (None, [C.c_int, C.c_int, C.c_int, ip, ip, ip, ip]),
-        "cvh_set_edge_map": (C.c_int, [vp, vp]),
-        "cvh_get_edge_map": (C.c_int, [vp, vp]),
-        "cvh_set_edge_map_device": (C.c_int, [vp, vp, vp]),
-        "cvh_get_edge_map_device": (C.c_int, [vp, vp, vp]),
-        "cvh_edge_map": (C.c_int, [vp, vp, C.c_double]),
-        "cvh_edge_map_batch": (C.c_int, [vp, vp, C.c_int, dp]),
-        "cvh_geodesic_run": (C.c_int, [vp, C.c_int, ip, dp, dp, C.c_int, ip]),
-        "cvh_geodesic_run_batch": (C.c_int, [vp, C.c_int, C.c_int, ip, dp, vp, C.c_int, ip]),
-        "cvh_geodesic_geometry": (None, [C.c_int, C.c_int, ip, ip, ip]),
-    }
-    for name, (res, args) in sig.items():
-        fn = getattr(L, name)
-        fn.restype, fn.argtypes = res, args
-    _lib = L
-    return L
-
-
 def _dp(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
 
 
 def _u8p(a):
     return a.ctypes.data_as(C.POINTER(C.c_uint8))
+
+
+# ---- the marshalling idioms, once each: a new wrapper uses these and spells none of them out
+def _ptr(x):
+    """a device address or a stream handle, held as an integer, as a void * argument: 0 is NULL"""
+    return int(x) or None
+
+
+def _array(ctype, n, values=()):
+    """a ctypes array of n entries -- of one where n is 0, so that an empty batch still hands the library an address"""
+    return (ctype * max(n, 1))(*values)
+
+
+def _member_array(contexts):
+    return _array(C.c_void_p, len(contexts), [c._h.value for c in contexts])
+
+
+def _members(contexts):
+    """(the members as a list, n); their handles are read by _member_array in the call itself, behind every check of the other arguments"""
+    contexts = list(contexts)
+    return contexts, len(contexts)
+
+
+def _address_array(ptrs, n):
+    ptrs = list(ptrs)
+    if len(ptrs) != n:
+        raise ValueError(f"{len(ptrs)} device pointers for {n} members")
+    return _array(C.c_void_p, n, [_ptr(p) for p in ptrs])
+
+
+def _per_member(value, n, name, conv, ndim=0):
+    """[conv(v)] per member: `value` is one value for all members (an array of `ndim` dimensions, 0 = a scalar) or a sequence of exactly n"""
+    vals = list(value) if np.ndim(value) > ndim else [value] * n
+    if len(vals) != n:
+        raise ValueError(f"{name}: {len(vals)} values for {n} members")
+    return [conv(v) for v in vals]
+
+
+def _check(rc):
+    """raises on an error code of a call that leaves its message with the thread (cvh_last_error(NULL)); Context._chk reads the context's"""
+    if rc != CVH_OK:
+        raise CvhError(rc, lib().cvh_last_error(None).decode())
+
+
+def _table_pointers(tables, n):
+    return _array(C.c_void_p, n, [t.ctypes.data if t.size else None for t in tables])
+
+
+def _rows(call, dtype, cap):
+    """One call for the first rows of a table: call(table_pointer, cap) makes the library call and returns the count it reports.
+    Returns (count, the first min(count, cap) rows)."""
+    table = np.zeros(max(int(cap), 0), dtype=dtype)
+    count = call(table.ctypes.data if table.size else None, int(cap))
+    return count, table[:min(count, table.size)].copy()
+
+
+def _count_then_rows(call, dtype, cap):
+    """_rows, and for cap = None every row at the price of a first call(None, 0) for the count: the host table must exist before the call
+    that fills it.  No rows: no second call."""
+    if cap is None:
+        cap = call(None, 0)
+        if not cap:
+            return 0, np.zeros(0, dtype=dtype)
+    return _rows(call, dtype, cap)
+
+
+def _caps_batch(call, cap, n, name):
+    """the row capacities of a batch: cap is one number for every member or one per member, or None for the counts a first
+    call(None, None) reports"""
+    return call(None, None) if cap is None else _per_member(cap, n, name, int)
+
+
+def _rows_batch(call, dtype, caps, ctype):
+    """_rows for a batch: call(table_pointers, caps) makes the library call and returns the members' counts; caps as a ctypes array of
+    `ctype`.  Returns [the first min(count, cap) rows] per member."""
+    n = len(caps)
+    tables = [np.zeros(max(c, 0), dtype=dtype) for c in caps]
+    counts = call(_table_pointers(tables, n), _array(ctype, n, caps))
+    return [t[:min(k, t.size)].copy() for k, t in zip(counts, tables)]
 
 
 def make_params(mu=0.5, nu=0.0, dt=1.0, eps=1.0, tol=1e-3, lambda1=None, lambda2=None):
@@ -454,15 +278,8 @@ def ppf_apply(data, op, eps=1.0, start=0, end=None, device=0):
     """ParallelPixelFunction(data, w, f)(Range(start, end)) on the GPU, in place."""
     assert data.dtype == np.float64 and data.flags.c_contiguous and data.ndim == 2
     end = data.size if end is None else end
-    rc = lib().cvh_ppf_apply(_dp(data), data.shape[1], start, end, int(op), float(eps), device)
-    if rc != CVH_OK:
-        raise CvhError(rc, lib().cvh_last_error(None).decode())
+    _check(lib().cvh_ppf_apply(_dp(data), data.shape[1], start, end, int(op), float(eps), device))
     return data
-
-
-def _member_array(contexts):
-    hs = [c._h.value for c in contexts]
-    return (C.c_void_p * max(len(hs), 1))(*hs)
 
 
 def enqueue_steps_batch(contexts, n):
@@ -470,8 +287,8 @@ def enqueue_steps_batch(contexts, n):
     CSV-step instantiation; follow with sync() on each context, as after Context.enqueue_steps."""
     contexts = list(contexts)
     rc = lib().cvh_enqueue_steps_batch(_member_array(contexts), len(contexts), int(n))
-    if rc != CVH_OK:
-        raise CvhError(rc, lib().cvh_last_error(None).decode())
+    if rc != CVH_OK:   # (tested here: the timed path gains no call where the library succeeds)
+        _check(rc)
 
 
 def run_batch(contexts, max_steps=-1):
@@ -481,155 +298,117 @@ def run_batch(contexts, max_steps=-1):
     n = len(contexts)
     done, nrm = (C.c_int * max(n, 1))(), (C.c_double * max(n, 1))()
     rc = lib().cvh_run_batch(_member_array(contexts), n, int(max_steps), done, nrm)
-    if rc != CVH_OK:
-        raise CvhError(rc, lib().cvh_last_error(None).decode())
+    if rc != CVH_OK:   # (as in enqueue_steps_batch)
+        _check(rc)
     return [(done[i], nrm[i]) for i in range(n)]
 
 
 def perona_malik_batch(contexts, K=10.0, L=0.25, T=20.0):
     """Perona-Malik batch (cvh_perona_malik_batch): Context.perona_malik for every context at once, the planes of several
     contexts sharing resident launches.  K, L and T are scalars (the same for every member) or sequences of one value per member."""
-    contexts = list(contexts)
-    n = len(contexts)
-
-    def per_member(v, name):
-        vals = [float(x) for x in v] if np.ndim(v) else [float(v)] * n
-        if len(vals) != n:
-            raise ValueError(f"{name}: {len(vals)} values for {n} members")
-        return (C.c_double * max(n, 1))(*vals)
-
-    k, l, t = per_member(K, "K"), per_member(L, "L"), per_member(T, "T")
-    rc = lib().cvh_perona_malik_batch(_member_array(contexts), n, k, l, t)
-    if rc != CVH_OK:
-        raise CvhError(rc, lib().cvh_last_error(None).decode())
-
-
-def _address_array(ptrs, n):
-    if len(ptrs) != n:
-        raise ValueError(f"{len(ptrs)} device pointers for {n} members")
-    return (C.c_void_p * max(n, 1))(*[int(p) or None for p in ptrs])
-
-
-def _batch_chk(rc):
-    if rc != CVH_OK:
-        raise CvhError(rc, lib().cvh_last_error(None).decode())
+    contexts, n = _members(contexts)
+    k, l, t = (_array(C.c_double, n, _per_member(v, n, name, float)) for v, name in ((K, "K"), (L, "L"), (T, "T")))
+    _check(lib().cvh_perona_malik_batch(_member_array(contexts), n, k, l, t))
 
 
 def set_image_device_batch(contexts, ptrs, layout=LAYOUT_PLANAR, stream=0):
     """cvh_set_image_device_batch: every context takes its image from device memory (ptrs: one integer address per context, uint8,
     planar or interleaved), one launch for all; ordered behind what `stream` (a HIP stream handle as integer, 0 = default) holds."""
-    contexts = list(contexts)
-    n = len(contexts)
-    _batch_chk(lib().cvh_set_image_device_batch(_member_array(contexts), n, _address_array(list(ptrs), n), int(layout), int(stream) or None))
+    contexts, n = _members(contexts)
+    _check(lib().cvh_set_image_device_batch(_member_array(contexts), n, _address_array(ptrs, n), int(layout), _ptr(stream)))
 
 
 def init_checkerboard_batch(contexts):
     """cvh_init_checkerboard_batch: Context.init_checkerboard for every context with one copy and one launch."""
-    contexts = list(contexts)
-    _batch_chk(lib().cvh_init_checkerboard_batch(_member_array(contexts), len(contexts)))
+    contexts, n = _members(contexts)
+    _check(lib().cvh_init_checkerboard_batch(_member_array(contexts), n))
 
 
 def get_mask_device_batch(contexts, ptrs, invert=False, stream=0):
     """cvh_get_mask_device_batch: every context's mask into device memory (ptrs: one integer address of h * w bytes per context),
     one launch for all; work enqueued on `stream` afterwards sees the masks.  Does not block the host."""
-    contexts = list(contexts)
-    n = len(contexts)
-    _batch_chk(lib().cvh_get_mask_device_batch(_member_array(contexts), n, _address_array(list(ptrs), n), int(bool(invert)), int(stream) or None))
+    contexts, n = _members(contexts)
+    _check(lib().cvh_get_mask_device_batch(_member_array(contexts), n, _address_array(ptrs, n), int(bool(invert)), _ptr(stream)))
 
 
 def reinit_batch(contexts):
     """cvh_reinit_batch: Context.reinit for every context (any mix of shapes) with one set of launches.  Returns [changed] per context."""
-    contexts = list(contexts)
-    n = len(contexts)
-    changed = (C.c_int * max(n, 1))()
-    _batch_chk(lib().cvh_reinit_batch(_member_array(contexts), n, changed))
+    contexts, n = _members(contexts)
+    changed = _array(C.c_int, n)
+    _check(lib().cvh_reinit_batch(_member_array(contexts), n, changed))
     return [bool(changed[i]) for i in range(n)]
 
 
 def components_batch(contexts, ptrs=None, conn=4, invert=False, stream=0):
     """cvh_components_batch: the connected components of every context's mask with one set of launches.  ptrs: one integer device
     address of h * w int32 labels per context (0 = no label plane for that member), or None.  Returns [K] per context."""
-    contexts = list(contexts)
-    n = len(contexts)
-    counts = (C.c_int * max(n, 1))()
-    addr = None if ptrs is None else _address_array(list(ptrs), n)
-    _batch_chk(lib().cvh_components_batch(_member_array(contexts), n, int(conn), int(bool(invert)), addr, counts, int(stream) or None))
+    contexts, n = _members(contexts)
+    counts = _array(C.c_int, n)
+    addr = None if ptrs is None else _address_array(ptrs, n)
+    _check(lib().cvh_components_batch(_member_array(contexts), n, int(conn), int(bool(invert)), addr, counts, _ptr(stream)))
     return [counts[i] for i in range(n)]
 
 
 def get_mask_clean_device_batch(contexts, ptrs, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False, stream=0):
     """cvh_get_mask_clean_device_batch: every context's cleaned mask (Context.get_mask_clean) into device memory, one set of launches
     for all; work enqueued on `stream` afterwards sees the masks.  Does not block the host."""
-    contexts = list(contexts)
-    n = len(contexts)
-    _batch_chk(lib().cvh_get_mask_clean_device_batch(_member_array(contexts), n, _address_array(list(ptrs), n), int(conn), int(bool(invert)),
-                                                     int(min_area), int(fill_holes), int(keep_largest), int(stream) or None))
+    contexts, n = _members(contexts)
+    _check(lib().cvh_get_mask_clean_device_batch(_member_array(contexts), n, _address_array(ptrs, n), int(conn), int(bool(invert)),
+                                                     int(min_area), int(fill_holes), int(keep_largest), _ptr(stream)))
 
 
 def otsu_from_histogram(hist):
     """cvh_otsu_from_histogram: Otsu's threshold of a histogram of 1 .. 766 uint32 counts (the header's integer definition), on the host."""
     hist = np.ascontiguousarray(hist, dtype=np.uint32)
     t = C.c_int(-1)
-    _batch_chk(lib().cvh_otsu_from_histogram(hist.ctypes.data, int(hist.size), C.byref(t)))
+    _check(lib().cvh_otsu_from_histogram(hist.ctypes.data, int(hist.size), C.byref(t)))
     return t.value
 
 
 def _int_rows(values, n, width, name):
     """values: one row of `width` ints for all members, or a sequence of n rows -> a flat ctypes int array of n * width"""
-    rows = [values] * n if (np.ndim(values) == (1 if width > 1 else 0)) else list(values)
-    if len(rows) != n:
-        raise ValueError(f"{name}: {len(rows)} values for {n} members")
     flat = []
-    for r in rows:
-        r = [r] if width == 1 else list(r)
+    for r in _per_member(values, n, name, lambda r: [r] if width == 1 else list(r), ndim=int(width > 1)):
         if len(r) != width:
             raise ValueError(f"{name}: {len(r)} numbers where {width} are needed")
         flat += [int(v) for v in r]
-    return (C.c_int * max(len(flat), 1))(*flat)
+    return _array(C.c_int, len(flat), flat)
 
 
 def histogram_batch(contexts, caps=None):
     """cvh_histogram_batch: the grey histograms (g = the sum of the planes) of every context with one launch.  caps: bins wanted per
     member (None: all 255 C + 1).  Returns [uint32 array] per context."""
-    contexts = list(contexts)
-    n = len(contexts)
-    caps = [255 * c.channels + 1 for c in contexts] if caps is None else [int(v) for v in caps]
-    if len(caps) != n:
-        raise ValueError(f"{len(caps)} capacities for {n} members")
+    contexts, n = _members(contexts)
+    caps = [255 * c.channels + 1 for c in contexts] if caps is None else _per_member(caps, n, "caps", int)
     outs = [np.zeros(max(k, 0), dtype=np.uint32) for k in caps]
-    ptrs = (C.c_void_p * max(n, 1))(*[o.ctypes.data if o.size else None for o in outs])
-    _batch_chk(lib().cvh_histogram_batch(_member_array(contexts), n, ptrs, (C.c_int * max(n, 1))(*caps)))
+    _check(lib().cvh_histogram_batch(_member_array(contexts), n, _table_pointers(outs, n), _array(C.c_int, n, caps)))
     return [o[:min(o.size, 255 * c.channels + 1)] for o, c in zip(outs, contexts)]
 
 
 def init_threshold_batch(contexts, t, inside=1.0, outside=-1.0):
     """cvh_init_threshold_batch: Context.init_threshold for every context with one launch; t is one int or one per member."""
-    contexts = list(contexts)
-    n = len(contexts)
-    _batch_chk(lib().cvh_init_threshold_batch(_member_array(contexts), n, _int_rows(t, n, 1, "t"), float(inside), float(outside)))
+    contexts, n = _members(contexts)
+    _check(lib().cvh_init_threshold_batch(_member_array(contexts), n, _int_rows(t, n, 1, "t"), float(inside), float(outside)))
 
 
 def init_otsu_batch(contexts, inside=1.0, outside=-1.0):
     """cvh_init_otsu_batch: Context.init_otsu for every context: one histogram launch, one start launch.  Returns [t] per context."""
-    contexts = list(contexts)
-    n = len(contexts)
-    t = (C.c_int * max(n, 1))()
-    _batch_chk(lib().cvh_init_otsu_batch(_member_array(contexts), n, t, float(inside), float(outside)))
+    contexts, n = _members(contexts)
+    t = _array(C.c_int, n)
+    _check(lib().cvh_init_otsu_batch(_member_array(contexts), n, t, float(inside), float(outside)))
     return [t[i] for i in range(n)]
 
 
 def init_rect_batch(contexts, xywh, inside=1.0, outside=0.0):
     """cvh_init_rect_batch: Context.init_rect for every context with one launch; xywh is (x, y, w, h) or one such row per member."""
-    contexts = list(contexts)
-    n = len(contexts)
-    _batch_chk(lib().cvh_init_rect_batch(_member_array(contexts), n, _int_rows(xywh, n, 4, "xywh"), float(inside), float(outside)))
+    contexts, n = _members(contexts)
+    _check(lib().cvh_init_rect_batch(_member_array(contexts), n, _int_rows(xywh, n, 4, "xywh"), float(inside), float(outside)))
 
 
 def init_disk_batch(contexts, cxcyr, inside=1.0, outside=0.0):
     """cvh_init_disk_batch: Context.init_disk for every context with one launch; cxcyr is (cx, cy, r) or one such row per member."""
-    contexts = list(contexts)
-    n = len(contexts)
-    _batch_chk(lib().cvh_init_disk_batch(_member_array(contexts), n, _int_rows(cxcyr, n, 3, "cxcyr"), float(inside), float(outside)))
+    contexts, n = _members(contexts)
+    _check(lib().cvh_init_disk_batch(_member_array(contexts), n, _int_rows(cxcyr, n, 3, "cxcyr"), float(inside), float(outside)))
 
 
 def pyramid_shapes(h, w, levels):
@@ -655,13 +434,13 @@ def _pairs(a, b):
 def restrict_image_batch(fines, coarses):
     """cvh_restrict_image_batch: Context.restrict_image_to for n pairs (any mix of shapes and channel counts) with one launch."""
     fines, coarses = _pairs(fines, coarses)
-    _batch_chk(lib().cvh_restrict_image_batch(_member_array(fines), _member_array(coarses), len(fines)))
+    _check(lib().cvh_restrict_image_batch(_member_array(fines), _member_array(coarses), len(fines)))
 
 
 def prolong_levelset_batch(coarses, fines):
     """cvh_prolong_levelset_batch: Context.prolong_levelset_to for n pairs (any mix of shapes and channel counts) with one launch."""
     coarses, fines = _pairs(coarses, fines)
-    _batch_chk(lib().cvh_prolong_levelset_batch(_member_array(coarses), _member_array(fines), len(coarses)))
+    _check(lib().cvh_prolong_levelset_batch(_member_array(coarses), _member_array(fines), len(coarses)))
 
 
 def colour_space_code(space):
@@ -681,15 +460,15 @@ def order_code(order):
 def convert_colour_batch(contexts, space, order="bgr", inverse=False):
     """cvh_convert_colour_batch: Context.convert_colour for n three-channel contexts (any mix of shapes) with one launch."""
     space, order = colour_space_code(space), order_code(order)
-    contexts = list(contexts)
-    _batch_chk(lib().cvh_convert_colour_batch(_member_array(contexts), len(contexts), space, order, int(bool(inverse))))
+    contexts, n = _members(contexts)
+    _check(lib().cvh_convert_colour_batch(_member_array(contexts), n, space, order, int(bool(inverse))))
 
 
 def luma_image_batch(srcs, dsts, order="bgr"):
     """cvh_luma_image_batch: Context.luma_to for n pairs (any mix of shapes) with one launch."""
     order = order_code(order)
     srcs, dsts = _pairs(srcs, dsts)
-    _batch_chk(lib().cvh_luma_image_batch(_member_array(srcs), _member_array(dsts), len(srcs), order))
+    _check(lib().cvh_luma_image_batch(_member_array(srcs), _member_array(dsts), len(srcs), order))
 
 
 def _what_codes(what, kind, names, top, range_text):
@@ -767,7 +546,7 @@ def _window_planes_batch(family, srcs, dsts, radius, what):
     radii, codes = _window_args(family, radii, whats, dsts)
     flat = [v for c in codes for v in c]
     call = getattr(lib(), f"cvh_{family}_planes_batch")
-    _batch_chk(call(_member_array(srcs), _member_array(dsts), n, (C.c_int * max(n, 1))(*radii), (C.c_int * max(3 * n, 1))(*flat)))
+    _check(call(_member_array(srcs), _member_array(dsts), n, _array(C.c_int, n, radii), _array(C.c_int, 3 * n, flat)))
 
 
 def local_planes_batch(srcs, dsts, radius, what):
@@ -878,10 +657,9 @@ def run_batch_with_reinit(contexts, max_steps=-1, every=0):
 def energy_batch(contexts):
     """cvh_energy_batch: Context.energy for n contexts (any mix of shapes and channel counts) with one set of launches and one host
     wait.  Returns [Energy] per context; every value is bit for bit the member's own Context.energy()."""
-    contexts = list(contexts)
-    n = len(contexts)
-    out = (EnergyTerms * max(n, 1))()
-    _batch_chk(lib().cvh_energy_batch(_member_array(contexts), n, out))
+    contexts, n = _members(contexts)
+    out = _array(EnergyTerms, n)
+    _check(lib().cvh_energy_batch(_member_array(contexts), n, out))
     return [_energy_of(out[i], contexts[i].channels) for i in range(n)]
 
 
@@ -889,13 +667,9 @@ def score_batch(contexts, truths, invert=False, tol=2.0, stream=0):
     """cvh_score_mask_device_batch: Context.score for n contexts (any mix of shapes and channel counts) against n truth planes in device
     memory (integer addresses of h * w bytes, non-zero = foreground), with one set of launches and one host wait.  Returns [Score] per
     context; every integer is the member's own Context.score()."""
-    contexts, truths = list(contexts), [int(t) or None for t in truths]
-    n = len(contexts)
-    if len(truths) != n:
-        raise ValueError(f"{n} contexts but {len(truths)} truth planes")
-    out = (MaskScore * max(n, 1))()
-    ptrs = (C.c_void_p * max(n, 1))(*truths)
-    _batch_chk(lib().cvh_score_mask_device_batch(_member_array(contexts), n, ptrs, int(bool(invert)), score_tol2(tol), out, int(stream) or None))
+    contexts, n = _members(contexts)
+    out = _array(MaskScore, n)
+    _check(lib().cvh_score_mask_device_batch(_member_array(contexts), n, _address_array(truths, n), int(bool(invert)), score_tol2(tol), out, _ptr(stream)))
     return [_score_of(out[i]) for i in range(n)]
 
 
@@ -905,34 +679,28 @@ def _clean_args(conn, invert, min_area, fill_holes, keep_largest):
 
 def _r2_array(r2, radius, n):
     """one squared radius per member: r2 / radius are one number for all members or one per member"""
-    def per_member(v):
-        vals = list(v) if np.ndim(v) else [v] * n
-        if len(vals) != n:
-            raise ValueError(f"{len(vals)} radii for {n} members")
-        return vals
     if r2 is not None and radius is not None:
         raise ValueError("give r2 or radius, not both")
-    vals = [_morph_r2(None, float(v)) for v in per_member(radius)] if radius is not None else [_morph_r2(v, None) for v in per_member(0 if r2 is None else r2)]
-    return (C.c_uint32 * max(n, 1))(*vals)
+    if radius is not None:
+        return _array(C.c_uint32, n, _per_member(radius, n, "radius", lambda v: _morph_r2(None, float(v))))
+    return _array(C.c_uint32, n, _per_member(0 if r2 is None else r2, n, "r2", lambda v: _morph_r2(v, None)))
 
 
 def mask_morph_batch(contexts, ptrs, op, r2=None, radius=None, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False, stream=0):
     """cvh_get_mask_morph_device_batch: Context.mask_morph for n contexts (any mix of shapes and channel counts) into device memory (ptrs:
     one integer address of h * w bytes per context), one set of launches for all; r2 / radius are one number or one per member, op is
     shared.  Work enqueued on `stream` afterwards sees the masks.  Does not block the host."""
-    contexts = list(contexts)
-    n = len(contexts)
+    contexts, n = _members(contexts)
     args = _clean_args(conn, invert, min_area, fill_holes, keep_largest) + (morph_code(op), _r2_array(r2, radius, n))
-    _batch_chk(lib().cvh_get_mask_morph_device_batch(_member_array(contexts), n, _address_array(list(ptrs), n), *args, int(stream) or None))
+    _check(lib().cvh_get_mask_morph_device_batch(_member_array(contexts), n, _address_array(ptrs, n), *args, _ptr(stream)))
 
 
 def morph_levelset_batch(contexts, op, r2=None, radius=None, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False, inside=1.0,
                          outside=-1.0):
     """cvh_morph_levelset_batch: Context.morph_levelset for n contexts with one set of launches; r2 / radius as in mask_morph_batch."""
-    contexts = list(contexts)
-    n = len(contexts)
+    contexts, n = _members(contexts)
     args = _clean_args(conn, invert, min_area, fill_holes, keep_largest) + (morph_code(op), _r2_array(r2, radius, n))
-    _batch_chk(lib().cvh_morph_levelset_batch(_member_array(contexts), n, *args, float(inside), float(outside)))
+    _check(lib().cvh_morph_levelset_batch(_member_array(contexts), n, *args, float(inside), float(outside)))
 
 
 def split_geometry():
@@ -946,53 +714,46 @@ def split_batch(contexts, ptrs=None, r2=None, radius=None, conn=4, invert=False,
     """cvh_split_batch: Context.split for n contexts (any mix of shapes and channel counts) with one set of launches.  ptrs: one integer
     device address of h * w int32 labels per context (0 = no label plane for that member), or None; r2 / radius are one number or one per
     member.  Returns [K] per context."""
-    contexts = list(contexts)
-    n = len(contexts)
-    counts = (C.c_int * max(n, 1))()
-    addr = None if ptrs is None else _address_array(list(ptrs), n)
+    contexts, n = _members(contexts)
+    counts = _array(C.c_int, n)
+    addr = None if ptrs is None else _address_array(ptrs, n)
     args = _clean_args(conn, invert, min_area, fill_holes, keep_largest) + (_r2_array(r2, radius, n),)
-    _batch_chk(lib().cvh_split_batch(_member_array(contexts), n, *args, addr, counts, int(stream) or None))
+    _check(lib().cvh_split_batch(_member_array(contexts), n, *args, addr, counts, _ptr(stream)))
     return [counts[i] for i in range(n)]
 
 
 def split_levelset_batch(contexts, r2=None, radius=None, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False, inside=1.0,
                          outside=-1.0):
     """cvh_split_levelset_batch: Context.split_levelset for n contexts with one set of launches; r2 / radius as in split_batch."""
-    contexts = list(contexts)
-    n = len(contexts)
+    contexts, n = _members(contexts)
     args = _clean_args(conn, invert, min_area, fill_holes, keep_largest) + (_r2_array(r2, radius, n),)
-    _batch_chk(lib().cvh_split_levelset_batch(_member_array(contexts), n, *args, float(inside), float(outside)))
+    _check(lib().cvh_split_levelset_batch(_member_array(contexts), n, *args, float(inside), float(outside)))
 
 
 def init_mask_batch(contexts, ptrs, inside=1.0, outside=-1.0, stream=0):
     """cvh_init_mask_device_batch: Context.init_mask for n contexts from byte masks in device memory (ptrs: one integer address of h * w
     bytes per context, read behind what `stream` holds), one launch for all."""
-    contexts = list(contexts)
-    n = len(contexts)
-    _batch_chk(lib().cvh_init_mask_device_batch(_member_array(contexts), n, _address_array(list(ptrs), n), float(inside), float(outside),
-                                                int(stream) or None))
+    contexts, n = _members(contexts)
+    _check(lib().cvh_init_mask_device_batch(_member_array(contexts), n, _address_array(ptrs, n), float(inside), float(outside),
+                                                _ptr(stream)))
 
 
 def measure_batch(contexts, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False, cap=None, stream=0):
     """cvh_measure_batch: Context.measure for n contexts (any mix of shapes and channel counts) with one set of launches.  cap: None
     (all rows, at the price of a first call for the counts), one number for every member or one per member.  Returns [(K, table)] per
     context; every row is bit for bit the member's own Context.measure()."""
-    contexts = list(contexts)
-    n = len(contexts)
+    contexts, n = _members(contexts)
     args = _clean_args(conn, invert, min_area, fill_holes, keep_largest)
-    counts = (C.c_int * max(n, 1))()
-    if cap is None:
-        _batch_chk(lib().cvh_measure_batch(_member_array(contexts), n, *args, None, None, counts, int(stream) or None))
-        caps = [counts[i] for i in range(n)]
-    else:
-        caps = [int(c) for c in cap] if np.ndim(cap) else [int(cap)] * n
-        if len(caps) != n:
-            raise ValueError(f"cap: {len(caps)} values for {n} members")
-    tables = [np.zeros(max(c, 0), dtype=REGION_DTYPE) for c in caps]
-    if any(t.size for t in tables) or cap is not None:
-        ptrs = (C.c_void_p * max(n, 1))(*[t.ctypes.data if t.size else None for t in tables])
-        _batch_chk(lib().cvh_measure_batch(_member_array(contexts), n, *args, ptrs, (C.c_int * max(n, 1))(*caps), counts, int(stream) or None))
-    return [(counts[i], tables[i][:min(counts[i], tables[i].size)].copy()) for i in range(n)]
+    counts = _array(C.c_int, n)
+
+    def call(tables, caps):
+        _check(lib().cvh_measure_batch(_member_array(contexts), n, *args, tables, caps, counts, _ptr(stream)))
+        return counts[:n]
+    caps = _caps_batch(call, cap, n, "cap")
+    if cap is None and not any(c > 0 for c in caps):   # (counted, and nothing to fetch: no second call)
+        return [(c, np.zeros(0, dtype=REGION_DTYPE)) for c in caps]
+    rows = _rows_batch(call, REGION_DTYPE, caps, C.c_int)
+    return list(zip(counts[:n], rows))
 
 
 def overlaps_batch(contexts, others, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False, cap=None, stream=0):
@@ -1000,23 +761,16 @@ def overlaps_batch(contexts, others, conn=4, invert=False, min_area=0, fill_hole
     device memory (integer addresses of h * w int32), with one set of launches.  cap: None (all rows, at the price of a first call for
     the counts), one number for every member or one per member.  Returns [(rows, K)] per context; every row is byte for byte the
     member's own Context.overlaps()."""
-    contexts = list(contexts)
-    n = len(contexts)
+    contexts, n = _members(contexts)
     args = _clean_args(conn, invert, min_area, fill_holes, keep_largest)
-    longs = C.c_long * max(n, 1)
-    pairs, counts = longs(), (C.c_int * max(n, 1))()
-    ptrs = _address_array(list(others), n)
-    if cap is None:
-        _batch_chk(lib().cvh_overlaps_device_batch(_member_array(contexts), n, *args, ptrs, None, None, pairs, counts, int(stream) or None))
-        caps = [pairs[i] for i in range(n)]
-    else:
-        caps = [int(c) for c in cap] if np.ndim(cap) else [int(cap)] * n
-        if len(caps) != n:
-            raise ValueError(f"cap: {len(caps)} values for {n} members")
-    tables = [np.zeros(max(c, 0), dtype=OVERLAP_DTYPE) for c in caps]
-    tptrs = (C.c_void_p * max(n, 1))(*[t.ctypes.data if t.size else None for t in tables])
-    _batch_chk(lib().cvh_overlaps_device_batch(_member_array(contexts), n, *args, ptrs, tptrs, longs(*caps), pairs, counts, int(stream) or None))
-    return [(tables[i][:min(pairs[i], tables[i].size)].copy(), counts[i]) for i in range(n)]
+    pairs, counts = _array(C.c_long, n), _array(C.c_int, n)
+    ptrs = _address_array(others, n)
+
+    def call(tables, caps):
+        _check(lib().cvh_overlaps_device_batch(_member_array(contexts), n, *args, ptrs, tables, caps, pairs, counts, _ptr(stream)))
+        return pairs[:n]
+    rows = _rows_batch(call, OVERLAP_DTYPE, _caps_batch(call, cap, n, "cap"), C.c_long)   # (the second call is always made)
+    return list(zip(rows, counts[:n]))
 
 
 def _threshold(threshold):
@@ -1059,26 +813,21 @@ def match_overlaps(rows, threshold=(1, 2)):
 
 def _contours_batch(fn, args, contexts, d_points, point_caps, loop_caps, stream):
     """cvh_contours_device_batch or cvh_contours_subpixel_device_batch (fn) with the options args: what contours_batch documents"""
-    contexts = list(contexts)
-    n = len(contexts)
-    longs = C.c_long * max(n, 1)
-    nloops, npoints = longs(), longs()
-    if loop_caps is None:
-        _batch_chk(fn(_member_array(contexts), n, *args, None, None, None, None, nloops, npoints, int(stream) or None))
-        loop_caps = [nloops[i] for i in range(n)]
-    loop_caps = [int(c) for c in loop_caps]
-    if len(loop_caps) != n:
-        raise ValueError(f"loop_caps: {len(loop_caps)} values for {n} members")
-    tables = [np.zeros(max(c, 0), dtype=CONTOUR_LOOP_DTYPE) for c in loop_caps]
-    tptrs = (C.c_void_p * max(n, 1))(*[t.ctypes.data if t.size else None for t in tables])
-    pptrs, pcaps = None, None
+    contexts, n = _members(contexts)
+    nloops, npoints = _array(C.c_long, n), _array(C.c_long, n)
+    points = None, None   # (the point arrays and their caps: a first call for the counts comes before they are looked at)
+
+    def call(tables, caps):
+        _check(fn(_member_array(contexts), n, *args, tables, caps, *points, nloops, npoints, _ptr(stream)))
+        return nloops[:n]
+    loop_caps = _caps_batch(call, loop_caps, n, "loop_caps")
     if d_points is not None:
-        d_points, point_caps = [int(p) or None for p in d_points], [int(c) for c in point_caps]
+        d_points, point_caps = list(d_points), [int(c) for c in point_caps]
         if len(d_points) != n or len(point_caps) != n:
             raise ValueError(f"{n} contexts but {len(d_points)} point arrays and {len(point_caps)} caps")
-        pptrs, pcaps = (C.c_void_p * max(n, 1))(*d_points), longs(*point_caps)
-    _batch_chk(fn(_member_array(contexts), n, *args, tptrs, longs(*loop_caps), pptrs, pcaps, nloops, npoints, int(stream) or None))
-    return [(nloops[i], npoints[i], tables[i][:min(nloops[i], tables[i].size)].copy()) for i in range(n)]
+        points = _address_array(d_points, n), _array(C.c_long, n, point_caps)
+    rows = _rows_batch(call, CONTOUR_LOOP_DTYPE, loop_caps, C.c_long)   # (the second call is always made)
+    return list(zip(nloops[:n], npoints[:n], rows))
 
 
 def contours_batch(contexts, d_points=None, point_caps=None, conn=8, invert=False, min_area=0, fill_holes=0, keep_largest=False, simplify=True,
@@ -1177,21 +926,6 @@ def multiphase_geometry(h, w):
     return cols.value, rows.value, items.value
 
 
-def multiphase_run(a, b, max_steps=-1, trace=False):
-    """cvh_multiphase_run ("Four phases" in include/chanvese_hip.h): contexts a and b hold phi1 and phi2 of a Vese-Chan pair and are
-    iterated together until max_steps iterations are done (negative: no bound) or the pair stops.  Returns (steps_done, (norm1, norm2),
-    trace): trace is None, or with trace=True (all rows; needs max_steps >= 0) or trace=<rows> an array of one row of 4 C + 2 doubles
-    per iteration -- the means c11, c10, c01, c00 it used and its two norms.  Both contexts are left as set_levelset of the new level
-    sets leaves them."""
-    want = 0 if trace is False or trace is None else (int(max_steps) if trace is True else int(trace))
-    if want < 0:
-        raise ValueError("trace=True needs max_steps >= 0 (or pass the number of rows)")
-    done, rows, norms = C.c_int(0), C.c_int(0), (C.c_double * 2)()
-    out = np.zeros((max(want, 1), 4 * a.channels + 2), dtype=np.float64) if want or trace is True else None
-    _batch_chk(lib().cvh_multiphase_run(a._h, b._h, int(max_steps), C.byref(done), norms, None if out is None else _dp(out), want, C.byref(rows)))
-    return done.value, (norms[0], norms[1]), None if out is None else out[:rows.value].copy()
-
-
 def _trace_rows_wanted(max_steps, trace):
     want = 0 if trace is False or trace is None else (int(max_steps) if trace is True else int(trace))
     if want < 0:
@@ -1199,30 +933,61 @@ def _trace_rows_wanted(max_steps, trace):
     return want
 
 
+def _trace_out(want, trace, tail):
+    """the buffer a march call writes its trace into, max(want, 1) rows of shape `tail` -- or None where no trace is asked for"""
+    return np.zeros((max(want, 1),) + tail, dtype=np.float64) if want or trace is True else None
+
+
+def _trace_of(out, rows):
+    return None if out is None else out[:rows].copy()
+
+
+def _march_run_batch(what, fn, lists, leading, tail, norms_per, max_steps, trace):
+    """What the three *_run_batch wrappers share.  lists: the member lists (two: the halves of n pairs); leading(n): the arguments the
+    call takes between n and max_steps, checked before any handle is read; tail(member of the first list): the shape of one of its
+    trace rows; norms_per: the norms the call reports per member.  Returns [(steps_done, norm or tuple of norms, trace)]."""
+    lists = [list(m) for m in lists]
+    n = len(lists[0])
+    if n == 0:
+        raise ValueError(f"{what}: no {'pairs' if len(lists) > 1 else 'members'}")
+    lead = leading(n)
+    want = _trace_rows_wanted(max_steps, trace)
+    done, rows, norms = _array(C.c_int, n), _array(C.c_int, n), _array(C.c_double, norms_per * n)
+    outs = [_trace_out(want, trace, tail(m)) for m in lists[0]]
+    traces = None if outs[0] is None else _array(C.c_void_p, n, [o.ctypes.data for o in outs])
+    _check(fn(*[_member_array(m) for m in lists], n, *lead, int(max_steps), done, norms, traces, want, rows))
+    norm_of = (lambda i: norms[i]) if norms_per == 1 else (lambda i: tuple(norms[norms_per * i:norms_per * (i + 1)]))
+    return [(done[i], norm_of(i), _trace_of(outs[i], rows[i])) for i in range(n)]
+
+
+def multiphase_run(a, b, max_steps=-1, trace=False):
+    """cvh_multiphase_run ("Four phases" in include/chanvese_hip.h): contexts a and b hold phi1 and phi2 of a Vese-Chan pair and are
+    iterated together until max_steps iterations are done (negative: no bound) or the pair stops.  Returns (steps_done, (norm1, norm2),
+    trace): trace is None, or with trace=True (all rows; needs max_steps >= 0) or trace=<rows> an array of one row of 4 C + 2 doubles
+    per iteration -- the means c11, c10, c01, c00 it used and its two norms.  Both contexts are left as set_levelset of the new level
+    sets leaves them."""
+    want = _trace_rows_wanted(max_steps, trace)
+    done, rows, norms = C.c_int(0), C.c_int(0), (C.c_double * 2)()
+    out = _trace_out(want, trace, (4 * a.channels + 2,))
+    _check(lib().cvh_multiphase_run(a._h, b._h, int(max_steps), C.byref(done), norms, None if out is None else _dp(out), want, C.byref(rows)))
+    return done.value, (norms[0], norms[1]), _trace_of(out, rows.value)
+
+
 def multiphase_run_batch(pairs, max_steps=-1, trace=False):
     """cvh_multiphase_run_batch: multiphase_run for every pair (a, b) of `pairs` at once -- per iteration one step launch and one
     finalise launch for all pairs of a (channel count, math mode) class.  Every pair iterates and stops on its own and is bit for bit
     what multiphase_run gives for it alone.  Returns a list of (steps_done, (norm1, norm2), trace), one per pair; trace as there."""
     pairs = [tuple(p) for p in pairs]
-    n = len(pairs)
-    if n == 0:
-        raise ValueError("multiphase_run_batch: no pairs")
     if any(len(p) != 2 for p in pairs):
         raise ValueError("multiphase_run_batch: every member is a pair (a, b) of contexts")
-    want = _trace_rows_wanted(max_steps, trace)
-    wanted = bool(want) or trace is True
-    done, rows, norms = (C.c_int * n)(), (C.c_int * n)(), (C.c_double * (2 * n))()
-    outs = [np.zeros((max(want, 1), 4 * a.channels + 2), dtype=np.float64) for a, _ in pairs] if wanted else None
-    traces = (C.c_void_p * n)(*[o.ctypes.data for o in outs]) if wanted else None
-    _batch_chk(lib().cvh_multiphase_run_batch(_member_array([a for a, _ in pairs]), _member_array([b for _, b in pairs]), n, int(max_steps), done, norms,
-                                              traces, want, rows))
-    return [(done[i], (norms[2 * i], norms[2 * i + 1]), outs[i][:rows[i]].copy() if wanted else None) for i in range(n)]
+    return _march_run_batch("multiphase_run_batch", lib().cvh_multiphase_run_batch, ([a for a, _ in pairs], [b for _, b in pairs]), lambda n: (),
+                            lambda a: (4 * a.channels + 2,), 2, max_steps, trace)
 
 
 def multiphase_means(a, b):
     """cvh_multiphase_means: the means of the current pair as an array of (4, C), rows c11, c10, c01, c00.  Only reads."""
     c = np.zeros((4, a.channels), dtype=np.float64)
-    _batch_chk(lib().cvh_multiphase_means(a._h, b._h, _dp(c)))
+    _check(lib().cvh_multiphase_means(a._h, b._h, _dp(c)))
     return c
 
 
@@ -1241,14 +1006,12 @@ def localized_run(ctx, radius, max_steps=-1, trace=False):
     (steps_done, norm, trace): trace is None, or with trace=True (all rows; needs max_steps >= 0) or trace=<rows> an array of the
     iterations' ||d||.  The context is left as set_levelset of the new level set leaves it.  The local force is small: start near the
     object and raise mu."""
-    want = 0 if trace is False or trace is None else (int(max_steps) if trace is True else int(trace))
-    if want < 0:
-        raise ValueError("trace=True needs max_steps >= 0 (or pass the number of rows)")
+    want = _trace_rows_wanted(max_steps, trace)
     done, rows, norm = C.c_int(0), C.c_int(0), C.c_double(0.0)
-    out = np.zeros(max(want, 1), dtype=np.float64) if want or trace is True else None
+    out = _trace_out(want, trace, ())
     ctx._chk(lib().cvh_localized_run(ctx._h, int(radius), int(max_steps), C.byref(done), C.byref(norm), None if out is None else _dp(out), want,
                                      C.byref(rows)))
-    return done.value, norm.value, None if out is None else out[:rows.value].copy()
+    return done.value, norm.value, _trace_of(out, rows.value)
 
 
 def localized_run_batch(contexts, radius, max_steps=-1, trace=False):
@@ -1256,20 +1019,8 @@ def localized_run_batch(contexts, radius, max_steps=-1, trace=False):
     for all members of a (channel count, math mode) class.  radius is an int (the same for every member) or a sequence of one value per
     member.  Every member iterates and stops on its own and is bit for bit what localized_run gives for it alone.  Returns a list of
     (steps_done, norm, trace), one per member; trace as there."""
-    contexts = list(contexts)
-    n = len(contexts)
-    if n == 0:
-        raise ValueError("localized_run_batch: no members")
-    radii = [int(r) for r in radius] if np.ndim(radius) else [int(radius)] * n
-    if len(radii) != n:
-        raise ValueError(f"radius: {len(radii)} values for {n} members")
-    want = _trace_rows_wanted(max_steps, trace)
-    wanted = bool(want) or trace is True
-    done, rows, norms = (C.c_int * n)(), (C.c_int * n)(), (C.c_double * n)()
-    outs = [np.zeros(max(want, 1), dtype=np.float64) for _ in contexts] if wanted else None
-    traces = (C.c_void_p * n)(*[o.ctypes.data for o in outs]) if wanted else None
-    _batch_chk(lib().cvh_localized_run_batch(_member_array(contexts), n, (C.c_int * n)(*radii), int(max_steps), done, norms, traces, want, rows))
-    return [(done[i], norms[i], outs[i][:rows[i]].copy() if wanted else None) for i in range(n)]
+    return _march_run_batch("localized_run_batch", lib().cvh_localized_run_batch, (contexts,),
+                            lambda n: (_array(C.c_int, n, _per_member(radius, n, "radius", int)),), lambda c: (), 1, max_steps, trace)
 
 
 def geodesic_geometry(h, w):
@@ -1287,10 +1038,8 @@ def edge_map_batch(dsts, srcs, K):
     n = len(dsts)
     if n == 0 or len(srcs) != n:
         raise ValueError(f"edge_map_batch: {n} destinations, {len(srcs)} sources")
-    ks = [float(k) for k in K] if np.ndim(K) else [float(K)] * n
-    if len(ks) != n:
-        raise ValueError(f"K: {len(ks)} values for {n} pairs")
-    _batch_chk(lib().cvh_edge_map_batch(_member_array(dsts), _member_array(srcs), n, (C.c_double * n)(*ks)))
+    ks = _array(C.c_double, n, _per_member(K, n, "K", float))
+    _check(lib().cvh_edge_map_batch(_member_array(dsts), _member_array(srcs), n, ks))
 
 
 def geodesic_run(ctx, max_steps=-1, trace=False):
@@ -1300,26 +1049,17 @@ def geodesic_run(ctx, max_steps=-1, trace=False):
     iteration -- the means c1, c2 it used and its norm.  The context is left as set_levelset of the new level set leaves it."""
     want = _trace_rows_wanted(max_steps, trace)
     done, rows, norm = C.c_int(0), C.c_int(0), C.c_double(0.0)
-    out = np.zeros((max(want, 1), 2 * ctx.channels + 1), dtype=np.float64) if want or trace is True else None
+    out = _trace_out(want, trace, (2 * ctx.channels + 1,))
     ctx._chk(lib().cvh_geodesic_run(ctx._h, int(max_steps), C.byref(done), C.byref(norm), None if out is None else _dp(out), want, C.byref(rows)))
-    return done.value, norm.value, None if out is None else out[:rows.value].copy()
+    return done.value, norm.value, _trace_of(out, rows.value)
 
 
 def geodesic_run_batch(contexts, max_steps=-1, trace=False):
     """cvh_geodesic_run_batch: geodesic_run for every context at once -- per iteration one step and one finalise launch for all members
     of a (channel count, math mode) class.  Every member iterates and stops on its own and is bit for bit what geodesic_run gives for
     it alone.  Returns a list of (steps_done, norm, trace), one per member; trace as there."""
-    contexts = list(contexts)
-    n = len(contexts)
-    if n == 0:
-        raise ValueError("geodesic_run_batch: no members")
-    want = _trace_rows_wanted(max_steps, trace)
-    wanted = bool(want) or trace is True
-    done, rows, norms = (C.c_int * n)(), (C.c_int * n)(), (C.c_double * n)()
-    outs = [np.zeros((max(want, 1), 2 * c.channels + 1), dtype=np.float64) for c in contexts] if wanted else None
-    traces = (C.c_void_p * n)(*[o.ctypes.data for o in outs]) if wanted else None
-    _batch_chk(lib().cvh_geodesic_run_batch(_member_array(contexts), n, int(max_steps), done, norms, traces, want, rows))
-    return [(done[i], norms[i], outs[i][:rows[i]].copy() if wanted else None) for i in range(n)]
+    return _march_run_batch("geodesic_run_batch", lib().cvh_geodesic_run_batch, (contexts,), lambda n: (), lambda c: (2 * c.channels + 1,), 1,
+                            max_steps, trace)
 
 
 def run_monitored(ctx, max_steps=-1, every=16, rel_plateau=None):
@@ -1350,7 +1090,7 @@ class Context:
         rc = self._L.cvh_create(C.byref(self._h), h, w, channels, C.byref(p), device)
         if rc != CVH_OK:
             self._h = C.c_void_p(None)
-            raise CvhError(rc, self._L.cvh_last_error(None).decode())
+            _check(rc)
 
     def _chk(self, rc):
         if rc != CVH_OK:
@@ -1395,19 +1135,19 @@ class Context:
 
     # device-memory forms: `ptr` is an integer device address, `stream` a HIP stream handle as integer (0 = the default stream)
     def set_image_device(self, ptr, layout=LAYOUT_PLANAR, stream=0):
-        self._chk(self._L.cvh_set_image_device(self._h, int(ptr) or None, int(layout), int(stream) or None))
+        self._chk(self._L.cvh_set_image_device(self._h, _ptr(ptr), int(layout), _ptr(stream)))
 
     def get_image_device(self, ptr, layout=LAYOUT_PLANAR, stream=0):
-        self._chk(self._L.cvh_get_image_device(self._h, int(ptr) or None, int(layout), int(stream) or None))
+        self._chk(self._L.cvh_get_image_device(self._h, _ptr(ptr), int(layout), _ptr(stream)))
 
     def set_levelset_device(self, ptr, bits=64, stream=0):
-        self._chk(self._L.cvh_set_levelset_device(self._h, int(ptr) or None, int(bits), int(stream) or None))
+        self._chk(self._L.cvh_set_levelset_device(self._h, _ptr(ptr), int(bits), _ptr(stream)))
 
     def get_levelset_device(self, ptr, bits=64, stream=0):
-        self._chk(self._L.cvh_get_levelset_device(self._h, int(ptr) or None, int(bits), int(stream) or None))
+        self._chk(self._L.cvh_get_levelset_device(self._h, _ptr(ptr), int(bits), _ptr(stream)))
 
     def get_mask_device(self, ptr, invert=False, stream=0):
-        self._chk(self._L.cvh_get_mask_device(self._h, int(ptr) or None, int(bool(invert)), int(stream) or None))
+        self._chk(self._L.cvh_get_mask_device(self._h, _ptr(ptr), int(bool(invert)), _ptr(stream)))
 
     def get_image(self):
         outs = [np.empty((self.h, self.w), dtype=np.uint8) for _ in range(self.channels)]
@@ -1458,29 +1198,29 @@ class Context:
     def restrict_image_to(self, coarse):
         """cvh_restrict_image: the planes of this context, averaged 2 x 2 in integers, become the image of `coarse` (a context of
         ((h + 1) // 2, (w + 1) // 2) and the same channel count), exactly as its set_image of those bytes; this context is only read."""
-        _batch_chk(self._L.cvh_restrict_image(self._h, coarse._h))
+        _check(self._L.cvh_restrict_image(self._h, coarse._h))
 
     def prolong_levelset_to(self, fine):
         """cvh_prolong_levelset: the level set of this context, replicated 2 x 2 bit for bit, becomes the level set of `fine`, exactly
         as its set_levelset of those doubles (a new run begins there); this context is only read."""
-        _batch_chk(self._L.cvh_prolong_levelset(self._h, fine._h))
+        _check(self._L.cvh_prolong_levelset(self._h, fine._h))
 
     def convert_colour(self, space, order="bgr", inverse=False):
         """cvh_convert_colour: the three planes, read as (B, G, R) or (R, G, B) by `order`, become (Y, Cr, Cb) ("ycrcb") or (Y, U, V)
         ("yuv") in place on the device -- or, with inverse, back --, exactly as set_image of the converted bytes (the header's integer
         definition).  The library does not remember which space the planes are in."""
         space, order = colour_space_code(space), order_code(order)
-        _batch_chk(self._L.cvh_convert_colour(self._h, space, order, int(bool(inverse))))
+        _check(self._L.cvh_convert_colour(self._h, space, order, int(bool(inverse))))
 
     def luma_to(self, dst, order="bgr"):
         """cvh_luma_image: the Y of this three-channel context becomes the image of `dst` (a one-channel context of the same shape),
         exactly as its set_image of that plane; this context is only read."""
         order = order_code(order)
-        _batch_chk(self._L.cvh_luma_image(self._h, dst._h, order))
+        _check(self._L.cvh_luma_image(self._h, dst._h, order))
 
     def _window_planes_to(self, family, dst, radius, what):
         radii, codes = _window_args(family, [radius], [what], [dst])   # (checked before the library is reached)
-        _batch_chk(getattr(self._L, f"cvh_{family}_planes")(self._h, dst._h, radii[0], (C.c_int * 3)(*codes[0])))
+        _check(getattr(self._L, f"cvh_{family}_planes")(self._h, dst._h, radii[0], (C.c_int * 3)(*codes[0])))
 
     def local_planes_to(self, dst, radius, what):
         """cvh_local_planes: plane k of `dst` (another context of the same shape, 1 or 3 channels) becomes the copy, the local mean or
@@ -1538,7 +1278,7 @@ class Context:
         """cvh_energy: the Chan-Sandberg-Vese functional of the current level set, term by term, evaluated on the device (Energy).
         Only reads: a run continued after it is bit-identical to one without."""
         t = EnergyTerms()
-        _batch_chk(self._L.cvh_energy(self._h, C.byref(t)))
+        _check(self._L.cvh_energy(self._h, C.byref(t)))
         return _energy_of(t, self.channels)
 
     def score(self, truth, invert=False, tol=2.0, stream=0):
@@ -1551,9 +1291,9 @@ class Context:
         if isinstance(truth, np.ndarray):
             t = np.ascontiguousarray(truth.view(np.uint8) if truth.dtype == np.bool_ else truth, dtype=np.uint8)
             assert t.shape == (self.h, self.w)
-            _batch_chk(self._L.cvh_score_mask(self._h, _u8p(t), int(bool(invert)), tol2, C.byref(s)))
+            _check(self._L.cvh_score_mask(self._h, _u8p(t), int(bool(invert)), tol2, C.byref(s)))
         else:
-            _batch_chk(self._L.cvh_score_mask_device(self._h, int(truth) or None, int(bool(invert)), tol2, C.byref(s), int(stream) or None))
+            _check(self._L.cvh_score_mask_device(self._h, _ptr(truth), int(bool(invert)), tol2, C.byref(s), _ptr(stream)))
         return _score_of(s)
 
     def get_trace(self, max_rows):
@@ -1582,14 +1322,14 @@ class Context:
             a = np.ascontiguousarray(gq)
             self._chk(self._L.cvh_set_edge_map(self._h, a.ctypes.data))
         elif isinstance(gq, (int, np.integer)) and not isinstance(gq, bool):
-            self._chk(self._L.cvh_set_edge_map_device(self._h, int(gq) or None, int(stream) or None))
+            self._chk(self._L.cvh_set_edge_map_device(self._h, _ptr(gq), _ptr(stream)))
         else:
             raise ValueError(f"set_edge_map: a uint16 numpy array or the integer address of device memory, got {type(gq).__name__}")
 
     def get_edge_map(self, ptr=0, stream=0):
         """cvh_get_edge_map / cvh_get_edge_map_device: the edge plane as a uint16 array of (h, w), or written to device memory at `ptr`."""
         if ptr:
-            self._chk(self._L.cvh_get_edge_map_device(self._h, int(ptr), int(stream) or None))
+            self._chk(self._L.cvh_get_edge_map_device(self._h, int(ptr), _ptr(stream)))
             return None
         out = np.empty((self.h, self.w), dtype=np.uint16)
         self._chk(self._L.cvh_get_edge_map(self._h, out.ctypes.data))
@@ -1598,16 +1338,16 @@ class Context:
     def edge_map_from(self, src, K):
         """cvh_edge_map: this context's edge plane from the planes of `src` (may be self) as they are now:
         gq = rint(32768 / (1 + |Sobel gradient|^2 / (64 C K^2))).  Smooth first (perona_malik, or a local mean in a second context)."""
-        _batch_chk(self._L.cvh_edge_map(self._h, src._h, float(K)))
+        _check(self._L.cvh_edge_map(self._h, src._h, float(K)))
 
     def multiphase_labels_with(self, b, ptr=0, stream=0):
         """cvh_multiphase_labels / _device: label = mask(self) + 2 mask(b) per pixel, one launch.  Returns a uint8 array of (h, w), or
         with ptr (an integer device address of h * w bytes, ordered behind `stream`) writes there without a host wait.  Only reads."""
         if ptr:
-            _batch_chk(self._L.cvh_multiphase_labels_device(self._h, b._h, int(ptr), int(stream) or None))
+            _check(self._L.cvh_multiphase_labels_device(self._h, b._h, int(ptr), _ptr(stream)))
             return None
         out = np.empty((self.h, self.w), dtype=np.uint8)
-        _batch_chk(self._L.cvh_multiphase_labels(self._h, b._h, _u8p(out)))
+        _check(self._L.cvh_multiphase_labels(self._h, b._h, _u8p(out)))
         return out
 
     def get_stop_condition(self):
@@ -1626,17 +1366,13 @@ class Context:
         cap = None asks for all K rows and COSTS TWO LABELLINGS (one call for K and the labels, a second one with cap = K for the rows: the
         host table must exist before the call that fills it); pass a cap where an upper bound of K is known, cap = 0 for no table."""
         count = C.c_int(0)
-        args = (int(conn), int(bool(invert)))
-        if cap is None:
-            self._chk(self._L.cvh_components(self._h, *args, int(labels_ptr) or None, None, 0, C.byref(count), int(stream) or None))
-            table = np.zeros(count.value, dtype=COMPONENT_DTYPE)
-            if count.value:
-                self._chk(self._L.cvh_components(self._h, *args, None, table.ctypes.data, count.value, C.byref(count), None))
-            return count.value, table
-        table = np.zeros(max(int(cap), 0), dtype=COMPONENT_DTYPE)
-        self._chk(self._L.cvh_components(self._h, *args, int(labels_ptr) or None, table.ctypes.data if table.size else None, int(cap),
-                                         C.byref(count), int(stream) or None))
-        return count.value, table[:min(count.value, table.size)].copy()
+
+        def call(table, cap_):
+            rows_only = cap is None and table is not None   # (the second of two calls: no label plane again, and no stream)
+            self._chk(self._L.cvh_components(self._h, int(conn), int(bool(invert)), None if rows_only else _ptr(labels_ptr), table, cap_,
+                                             C.byref(count), None if rows_only else _ptr(stream)))
+            return count.value
+        return _count_then_rows(call, COMPONENT_DTYPE, cap)
 
     def measure(self, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False, cap=None, stream=0):
         """cvh_measure: the components of the mask -- get_mask_clean's for the same five options, (0, 0, False) the raw one -- measured
@@ -1646,14 +1382,11 @@ class Context:
         bound of K is known, cap = 0 for the count alone.  Only reads: a run continued after it is bit-identical to one without."""
         count = C.c_int(0)
         args = _clean_args(conn, invert, min_area, fill_holes, keep_largest)
-        if cap is None:
-            _batch_chk(self._L.cvh_measure(self._h, *args, None, 0, C.byref(count), int(stream) or None))
-            if not count.value:
-                return 0, np.zeros(0, dtype=REGION_DTYPE)
-            cap = count.value
-        table = np.zeros(max(int(cap), 0), dtype=REGION_DTYPE)
-        _batch_chk(self._L.cvh_measure(self._h, *args, table.ctypes.data if table.size else None, int(cap), C.byref(count), int(stream) or None))
-        return count.value, table[:min(count.value, table.size)].copy()
+
+        def call(table, cap_):
+            _check(self._L.cvh_measure(self._h, *args, table, cap_, C.byref(count), _ptr(stream)))
+            return count.value
+        return _count_then_rows(call, REGION_DTYPE, cap)
 
     def overlaps(self, other, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False, cap=None, stream=0):
         """cvh_overlaps / cvh_overlaps_device: the contingency table of the mask's components -- measure's for the same five options --
@@ -1669,23 +1402,21 @@ class Context:
             assert plane.shape == (self.h, self.w)
 
             def call(table, cap_):
-                _batch_chk(self._L.cvh_overlaps(self._h, *args, plane.ctypes.data, table, cap_, C.byref(pairs), C.byref(count)))
+                _check(self._L.cvh_overlaps(self._h, *args, plane.ctypes.data, table, cap_, C.byref(pairs), C.byref(count)))
+                return pairs.value
         else:
             def call(table, cap_):
-                _batch_chk(self._L.cvh_overlaps_device(self._h, *args, int(other) or None, table, cap_, C.byref(pairs), C.byref(count),
-                                                       int(stream) or None))
-        if cap is None:
-            call(None, 0)
-            cap = pairs.value
-        table = np.zeros(max(int(cap), 0), dtype=OVERLAP_DTYPE)
-        call(table.ctypes.data if table.size else None, int(cap))
-        return table[:min(pairs.value, table.size)].copy(), count.value
+                _check(self._L.cvh_overlaps_device(self._h, *args, _ptr(other), table, cap_, C.byref(pairs), C.byref(count),
+                                                       _ptr(stream)))
+                return pairs.value
+        _, rows = _rows(call, OVERLAP_DTYPE, call(None, 0) if cap is None else cap)   # (the rows are asked for even where the count is 0)
+        return rows, count.value
 
     def contour_counts(self, conn=8, invert=False, min_area=0, fill_holes=0, keep_largest=False, simplify=True):
         """cvh_contours without outputs: (nloops, npoints) of the boundary of the mask."""
         nloops, npoints = C.c_long(0), C.c_long(0)
         args = _clean_args(conn, invert, min_area, fill_holes, keep_largest) + (int(bool(simplify)),)
-        _batch_chk(self._L.cvh_contours(self._h, *args, None, 0, None, 0, C.byref(nloops), C.byref(npoints)))
+        _check(self._L.cvh_contours(self._h, *args, None, 0, None, 0, C.byref(nloops), C.byref(npoints)))
         return nloops.value, npoints.value
 
     def contours(self, conn=8, invert=False, min_area=0, fill_holes=0, keep_largest=False, simplify=True):
@@ -1699,7 +1430,7 @@ class Context:
         if nl:
             nloops, npoints = C.c_long(0), C.c_long(0)
             args = _clean_args(conn, invert, min_area, fill_holes, keep_largest) + (int(bool(simplify)),)
-            _batch_chk(self._L.cvh_contours(self._h, *args, loops.ctypes.data, nl, points.ctypes.data, npts, C.byref(nloops), C.byref(npoints)))
+            _check(self._L.cvh_contours(self._h, *args, loops.ctypes.data, nl, points.ctypes.data, npts, C.byref(nloops), C.byref(npoints)))
         return loops, points
 
     def contours_subpixel(self, conn=8, invert=False, min_area=0, fill_holes=0, keep_largest=False):
@@ -1710,11 +1441,11 @@ class Context:
         COSTS TWO TRACES (the counts size the arrays).  Only reads: a run continued after it is bit-identical to one without."""
         args = _clean_args(conn, invert, min_area, fill_holes, keep_largest)
         nloops, npoints = C.c_long(0), C.c_long(0)
-        _batch_chk(self._L.cvh_contours_subpixel(self._h, *args, None, 0, None, 0, C.byref(nloops), C.byref(npoints)))
+        _check(self._L.cvh_contours_subpixel(self._h, *args, None, 0, None, 0, C.byref(nloops), C.byref(npoints)))
         nl, npts = nloops.value, npoints.value
         loops, points = np.zeros(nl, dtype=CONTOUR_LOOP_DTYPE), np.zeros((npts, 2), dtype=np.float64)
         if nl:
-            _batch_chk(self._L.cvh_contours_subpixel(self._h, *args, loops.ctypes.data, nl, points.ctypes.data, npts, C.byref(nloops), C.byref(npoints)))
+            _check(self._L.cvh_contours_subpixel(self._h, *args, loops.ctypes.data, nl, points.ctypes.data, npts, C.byref(nloops), C.byref(npoints)))
         return loops, points
 
     def get_mask_clean(self, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False):
@@ -1725,8 +1456,8 @@ class Context:
         return m
 
     def get_mask_clean_device(self, ptr, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False, stream=0):
-        self._chk(self._L.cvh_get_mask_clean_device(self._h, int(ptr) or None, int(conn), int(bool(invert)), int(min_area), int(fill_holes),
-                                                    int(keep_largest), int(stream) or None))
+        self._chk(self._L.cvh_get_mask_clean_device(self._h, _ptr(ptr), int(conn), int(bool(invert)), int(min_area), int(fill_holes),
+                                                    int(keep_largest), _ptr(stream)))
 
     def mask_morph(self, op, r2=None, radius=None, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False, out=None, stream=0):
         """cvh_get_mask_morph / cvh_get_mask_morph_device: the cleaned mask (get_mask_clean's arguments) dilated, eroded, opened or closed
@@ -1737,9 +1468,9 @@ class Context:
         if out is None or isinstance(out, np.ndarray):
             m = np.empty((self.h, self.w), dtype=np.uint8) if out is None else out
             assert m.dtype == np.uint8 and m.shape == (self.h, self.w) and m.flags["C_CONTIGUOUS"]
-            _batch_chk(self._L.cvh_get_mask_morph(self._h, _u8p(m), *args))
+            _check(self._L.cvh_get_mask_morph(self._h, _u8p(m), *args))
             return m
-        _batch_chk(self._L.cvh_get_mask_morph_device(self._h, int(out) or None, *args, int(stream) or None))
+        _check(self._L.cvh_get_mask_morph_device(self._h, _ptr(out), *args, _ptr(stream)))
         return out
 
     def split(self, r2=None, radius=None, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False, labels_ptr=0, cap=None, stream=0):
@@ -1750,37 +1481,35 @@ class Context:
         object.  cap = None asks for all K rows and COSTS TWO CALLS (as components); cap = 0 for no table.  Only reads."""
         count = C.c_int(0)
         args = _clean_args(conn, invert, min_area, fill_holes, keep_largest) + (_morph_r2(r2, radius),)
-        labels = int(labels_ptr) or None
-        if cap is None:
-            _batch_chk(self._L.cvh_split(self._h, *args, labels, None, 0, C.byref(count), int(stream) or None))
-            table = np.zeros(count.value, dtype=COMPONENT_DTYPE)
-            if count.value:
-                _batch_chk(self._L.cvh_split(self._h, *args, None, table.ctypes.data, count.value, C.byref(count), None))
-            return labels, table, count.value
-        table = np.zeros(max(int(cap), 0), dtype=COMPONENT_DTYPE)
-        _batch_chk(self._L.cvh_split(self._h, *args, labels, table.ctypes.data if table.size else None, int(cap), C.byref(count), int(stream) or None))
-        return labels, table[:min(count.value, table.size)].copy(), count.value
+        labels = _ptr(labels_ptr)
+
+        def call(table, cap_):
+            rows_only = cap is None and table is not None   # (as in components)
+            _check(self._L.cvh_split(self._h, *args, None if rows_only else labels, table, cap_, C.byref(count), None if rows_only else _ptr(stream)))
+            return count.value
+        k, table = _count_then_rows(call, COMPONENT_DTYPE, cap)
+        return labels, table, k
 
     def split_labels(self, r2=None, radius=None, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False):
         """cvh_split_host: split()'s label plane as a numpy int32 array (h, w) in host memory, and K: (labels, K)."""
         count = C.c_int(0)
         labels = np.empty((self.h, self.w), dtype=np.int32)
         args = _clean_args(conn, invert, min_area, fill_holes, keep_largest) + (_morph_r2(r2, radius),)
-        _batch_chk(self._L.cvh_split_host(self._h, *args, labels.ctypes.data, None, 0, C.byref(count)))
+        _check(self._L.cvh_split_host(self._h, *args, labels.ctypes.data, None, 0, C.byref(count)))
         return labels, count.value
 
     def split_levelset(self, r2=None, radius=None, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False, inside=1.0, outside=-1.0):
         """cvh_split_levelset: split in place -- the level set becomes `inside` on the split objects and `outside` on the cut lines and the
         background, and a new run begins; components, measure, contours, overlaps and further iterations then see the split objects."""
         args = _clean_args(conn, invert, min_area, fill_holes, keep_largest) + (_morph_r2(r2, radius),)
-        _batch_chk(self._L.cvh_split_levelset(self._h, *args, float(inside), float(outside)))
+        _check(self._L.cvh_split_levelset(self._h, *args, float(inside), float(outside)))
 
     def morph_levelset(self, op, r2=None, radius=None, conn=4, invert=False, min_area=0, fill_holes=0, keep_largest=False, inside=1.0,
                        outside=-1.0):
         """cvh_morph_levelset: mask_morph in place -- the level set becomes `inside` where that mask is 1 and `outside` elsewhere, and a
         new run begins as after set_levelset; the mask never leaves the device.  With MORPH_NONE the cleaned mask is baked in."""
         args = _clean_args(conn, invert, min_area, fill_holes, keep_largest) + (morph_code(op), _morph_r2(r2, radius))
-        _batch_chk(self._L.cvh_morph_levelset(self._h, *args, float(inside), float(outside)))
+        _check(self._L.cvh_morph_levelset(self._h, *args, float(inside), float(outside)))
 
     def init_mask(self, mask, inside=1.0, outside=-1.0, stream=0):
         """cvh_init_mask / cvh_init_mask_device: u = inside where the mask's byte is nonzero, outside elsewhere, written on the device (one
@@ -1790,9 +1519,9 @@ class Context:
         if isinstance(mask, np.ndarray):
             m = np.ascontiguousarray(mask.view(np.uint8) if mask.dtype == np.bool_ else mask, dtype=np.uint8)
             assert m.shape == (self.h, self.w)
-            _batch_chk(self._L.cvh_init_mask(self._h, _u8p(m), float(inside), float(outside)))
+            _check(self._L.cvh_init_mask(self._h, _u8p(m), float(inside), float(outside)))
         else:
-            _batch_chk(self._L.cvh_init_mask_device(self._h, int(mask) or None, float(inside), float(outside), int(stream) or None))
+            _check(self._L.cvh_init_mask_device(self._h, _ptr(mask), float(inside), float(outside), _ptr(stream)))
 
     def get_contour(self):
         m = np.empty((self.h, self.w), dtype=np.uint8)

@@ -4,12 +4,12 @@ usage: pm_ab_libs.py path/to/libA.so path/to/libB.so ...   [N=2048 REPS=4 STEPS=
 import os, sys
 sys.path.insert(0, '.')
 import numpy as np
-from chan_vese_amd import capi, synth
+from chan_vese_amd import _abi, capi, synth
 n = int(os.environ.get("N", "2048")); reps = int(os.environ.get("REPS", "4")); steps = int(os.environ.get("STEPS", "400"))
 img = synth.disk(n, 200, 50, noise=40, seed=1)
 ctxs = []
 for path in sys.argv[1:]:
-    capi._lib = None; capi.LIB_PATH = os.path.abspath(path)      # bind a fresh handle of this build
+    _abi._lib = None; _abi.LIB_PATH = os.path.abspath(path)      # bind a fresh handle of this build
     capi.lib()
     ctx = capi.Context(n, n, 1)
     for kv in os.environ.get("OPTS", "").split(","):
