@@ -43,6 +43,10 @@ RANK_COPY, RANK_MIN, RANK_MAX, RANK_MEDIAN, RANK_OPEN, RANK_CLOSE, RANK_TOPHAT, 
 RANK_RADIUS_MAX, RANK_MEDIAN_RADIUS_MAX = 127, 7
 RANK_WHATS = {"min": RANK_MIN, "max": RANK_MAX, "median": RANK_MEDIAN, "open": RANK_OPEN, "close": RANK_CLOSE, "tophat": RANK_TOPHAT,
               "bothat": RANK_BOTHAT}
+# "Smoothing": what plane k of the destination of cvh_smooth_planes becomes, by code and -- every plane alike -- by name
+SMOOTH_COPY, SMOOTH_BLUR, SMOOTH_DETAIL = 0, 1, 2
+SMOOTH_RADIUS_MAX, SMOOTH_TAP_SUM = 63, 32768
+SMOOTH_WHATS = {"blur": SMOOTH_BLUR, "detail": SMOOTH_DETAIL}
 
 
 class Params(C.Structure):
@@ -79,6 +83,7 @@ class CvhError(RuntimeError):
 _int, _long, _dbl, _u32, _vp = C.c_int, C.c_long, C.c_double, C.c_uint32, C.c_void_p
 _ip, _lp, _dp, _fp, _u8p, _u32p = (C.POINTER(t) for t in (_int, _long, _dbl, C.c_float, C.c_uint8, _u32))
 _u8pp, _vpp = C.POINTER(_u8p), C.POINTER(_vp)
+_u16p = C.POINTER(C.c_uint16)
 # the argument groups that recur (a context, a device address, a host table and a stream are all void *)
 MEMBERS = [_vpp, _int]                        # member list + n
 MARCH_MEMBERS = [_vp, _int]                   # the same of the march batches, which declare their lists void *
@@ -174,6 +179,9 @@ SIGNATURES = {
     "cvh_local_planes_batch": _sig(PAIRS, _ip, _ip),
     "cvh_rank_planes": _sig(_vp, _vp, _int, _ip),
     "cvh_rank_planes_batch": _sig(PAIRS, _ip, _ip),
+    "cvh_gauss_taps": _sig(_dbl, _u16p, _ip),
+    "cvh_smooth_planes": _sig(_vp, _vp, _int, _u16p, _ip),
+    "cvh_smooth_planes_batch": _sig(PAIRS, _ip, C.POINTER(_u16p), _ip),
     "cvh_energy": _sig(_vp, C.POINTER(EnergyTerms)),
     "cvh_energy_batch": _sig(MEMBERS, C.POINTER(EnergyTerms)),
     "cvh_score_mask": _sig(_vp, _u8p, _int, _u32, C.POINTER(MaskScore)),

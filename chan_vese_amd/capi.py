@@ -14,7 +14,7 @@ from ._abi import (COLOUR_SPACES, COMPONENT_DTYPE, CONTOUR_LOOP_DTYPE, CVH_OK, E
                    LOCAL_MEAN, LOCAL_RADIUS_MAX, LOCAL_WHATS, MATH_DEFAULT, MATH_FAST, MATH_STRICT, MORPH_CLOSE, MORPH_DILATE, MORPH_ERODE, MORPH_NONE,
                    MORPH_OPEN, MORPH_OPS, OP_DELTA, OP_HEAVISIDE, OP_ONE_MINUS_HEAVISIDE, ORDERS, OVERLAP_DTYPE, RANK_BOTHAT, RANK_CLOSE, RANK_COPY, RANK_MAX,
                    RANK_MEDIAN, RANK_MEDIAN_RADIUS_MAX, RANK_MIN, RANK_OPEN, RANK_RADIUS_MAX, RANK_TOPHAT, RANK_WHATS, REGION_DTYPE, REGION_SHAPE_DTYPE,
-                   SIGNATURES, CvhError, EnergyTerms, MaskScore, Match, Params, lib)
+                   SIGNATURES, SMOOTH_BLUR, SMOOTH_COPY, SMOOTH_DETAIL, SMOOTH_RADIUS_MAX, SMOOTH_TAP_SUM, SMOOTH_WHATS, CvhError, EnergyTerms, MaskScore, Match, Params, lib)
 
 
 @dataclasses.dataclass(frozen=True)
@@ -560,6 +560,71 @@ def rank_planes_batch(srcs, dsts, radius, what):
     launches.  A scalar `radius` and ONE `what` (a name or a tuple of codes) go to every pair; else one per pair.  A median's radius
     limit is checked against the codes a destination has planes for."""
     _window_planes_batch("rank", srcs, dsts, radius, what)
+
+
+def smooth_what_codes(what):
+    """A name -- "blur", "detail" (every plane) -- or 1 to 3 codes -> the three codes cvh_smooth_planes reads; entries a destination has
+    no plane for are ignored by the library and filled with SMOOTH_COPY here.  ValueError for anything else.  Calls nothing in the
+    library."""
+    return _what_codes(what, "smoothing", SMOOTH_WHATS, SMOOTH_DETAIL, "SMOOTH_COPY (0), SMOOTH_BLUR (1), SMOOTH_DETAIL (2)")
+
+
+def gauss_taps(sigma):
+    """cvh_gauss_taps: (radius, taps) of the library's Gaussian of that sigma (0 < sigma <= 21) -- radius = ceil(3 sigma) and radius + 1
+    np.uint16 taps whose symmetric sum is 32768.  The C function is the definition; ValueError for what it refuses."""
+    if isinstance(sigma, bool) or not isinstance(sigma, (int, float, np.integer, np.floating)):
+        raise ValueError(f"smoothing sigma must be a number in (0, 21], got {sigma!r}")
+    taps, radius = (C.c_uint16 * (SMOOTH_RADIUS_MAX + 1))(), C.c_int(0)
+    if lib().cvh_gauss_taps(float(sigma), taps, C.byref(radius)) != CVH_OK:
+        raise ValueError(f"smoothing sigma must be a finite number in (0, 21], got {sigma!r}")
+    return radius.value, np.array(taps[:radius.value + 1], dtype=np.uint16)
+
+
+def smooth_kernel(kernel):
+    """(radius, np.uint16 taps) of a smoothing kernel: a number (float or int) is the Gaussian of that sigma (gauss_taps), an integer SEQUENCE the taps
+    t[0 .. R] as given -- 1 to SMOOTH_RADIUS_MAX + 1 of them, each 0 .. 65535, t[0] + 2 (t[1] + .. + t[R]) = 32768.  ValueError for
+    anything else.  Only the Gaussian calls the library (a host function that needs no device)."""
+    if isinstance(kernel, (int, float, np.integer, np.floating)) and not isinstance(kernel, bool):   # (a bare integer is a sigma, not a tap)
+        return gauss_taps(kernel)
+    try:
+        taps = list(kernel)
+    except TypeError:
+        taps = None
+    if isinstance(kernel, (str, bytes)) or not taps or len(taps) > SMOOTH_RADIUS_MAX + 1 or \
+            any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= 65535 for v in taps):
+        raise ValueError(f"a smoothing kernel is a float sigma or 1 to {SMOOTH_RADIUS_MAX + 1} integer taps 0 .. 65535, got {kernel!r}")
+    total = int(taps[0]) + 2 * sum(int(v) for v in taps[1:])
+    if total != SMOOTH_TAP_SUM:
+        raise ValueError(f"smoothing taps must add up to {SMOOTH_TAP_SUM} over the window (t[0] + 2 sum t[i]), got {total}")
+    return len(taps) - 1, np.array(taps, dtype=np.uint16)
+
+
+def _is_one_kernel(kernel):
+    """a float, or a sequence of integers: ONE kernel for every pair (a sequence of floats or of sequences is one per pair)"""
+    if isinstance(kernel, (int, float, np.integer, np.floating)) or isinstance(kernel, np.ndarray) and kernel.ndim == 1 and kernel.dtype.kind in "iu":
+        return True
+    try:
+        return len(kernel) > 0 and all(isinstance(v, (int, np.integer)) for v in kernel)
+    except TypeError:
+        return True                                        # (smooth_kernel says what is wrong with it)
+
+
+def smooth_planes_batch(srcs, dsts, kernel, what):
+    """cvh_smooth_planes_batch: Context.smooth_planes_to for n pairs (any mix of shapes, channel counts, kernels and codes) with one set
+    of launches.  ONE `kernel` (a float sigma or a sequence of integer taps) and ONE `what` (a name or a tuple of codes) go to every
+    pair; else a list of one per pair."""
+    srcs, dsts = _pairs(srcs, dsts)
+    n = len(srcs)
+    kernels = [kernel] * n if _is_one_kernel(kernel) else list(kernel)
+    whats = [what] * n if _is_one_what(what) else list(what)
+    if len(kernels) != n or len(whats) != n:
+        raise ValueError(f"{n} pairs need {n} kernels and {n} codes tuples (or one of each), got {len(kernels)} and {len(whats)}")
+    kernels = [smooth_kernel(k) for k in kernels]
+    flat = [v for w in whats for v in smooth_what_codes(w)]
+    rows = [_array(C.c_uint16, len(t), [int(v) for v in t]) for _, t in kernels]
+    taps = (C.POINTER(C.c_uint16) * n)(*[C.cast(r, C.POINTER(C.c_uint16)) for r in rows])
+    _check(lib().cvh_smooth_planes_batch(_member_array(srcs), _member_array(dsts), n, _array(C.c_int, n, [r for r, _ in kernels]), taps,
+                                         _array(C.c_int, 3 * n, flat)))
 
 
 def _coarse_to_fine(pyramids, max_steps, run):
@@ -1234,6 +1299,16 @@ class Context:
         which is only read.  `what` is "min", "max", "median", "open", "close", "tophat", "bothat" or a tuple of RANK_* codes; `dst` is
         left as set_image of those planes."""
         self._window_planes_to("rank", dst, radius, what)
+
+    def smooth_planes_to(self, dst, kernel, what):
+        """cvh_smooth_planes: plane k of `dst` (another context of the same shape, 1 or 3 channels) becomes the copy, the blur or the
+        detail (128 + p - blur, clamped) of plane min(k, channels - 1) of this context, which is only read, under a symmetric separable
+        kernel with a replicated border.  `kernel` is a float (the Gaussian of that sigma, gauss_taps) or a sequence of integer taps;
+        `what` is "blur", "detail" or a tuple of SMOOTH_COPY / SMOOTH_BLUR / SMOOTH_DETAIL; `dst` is left as set_image of those planes."""
+        codes = smooth_what_codes(what)                        # (checked before the library is reached)
+        radius, taps = smooth_kernel(kernel)
+        row = (C.c_uint16 * len(taps))(*[int(v) for v in taps])
+        _check(self._L.cvh_smooth_planes(self._h, dst._h, radius, row, (C.c_int * 3)(*codes)))
 
     def reinit(self):
         """cvh_reinit: the level set becomes the exact signed distance to the pixel-edge front of its own mask, on the device.

@@ -153,6 +153,7 @@ extern "C" void cvh_destroy(cvh_context *c)
   if (c->d_split) (void)hipFree(c->d_split);
   if (c->d_local) (void)hipFree(c->d_local);
   if (c->d_rank) (void)hipFree(c->d_rank);
+  if (c->d_smooth) (void)hipFree(c->d_smooth);
   if (c->d_overlap_plane) (void)hipFree(c->d_overlap_plane);
   if (c->d_multiphase) (void)hipFree(c->d_multiphase);
   free_table(&c->mp_trace);

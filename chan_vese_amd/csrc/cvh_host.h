@@ -4,7 +4,7 @@
 // device buffers), pm_run.hip (Perona-Malik), io_run.hip (device-memory I/O, reinitialisation, and the scaffolds of the member-table
 // calls: MemberCall with its further waits, write_planes, the pointer checks, the launch counters), init_run.hip (device-side initial
 // level sets), components_run.hip (connected components, and MaskSource: the raw or cleaned mask every mask-derived call starts from),
-// pyramid_run.hip (coarse-to-fine), colour_run.hip (colour spaces), window_run.hip (local statistics and rank planes: the windowed-plane calls), energy_run.hip (the functional's terms), score_run.hip (mask scores),
+// pyramid_run.hip (coarse-to-fine), colour_run.hip (colour spaces), window_run.hip (local statistics, rank planes and smoothing: the windowed-plane calls), energy_run.hip (the functional's terms), score_run.hip (mask scores),
 // morph_run.hip (mask morphology, mask starts), split_run.hip (object split), measure_run.hip (component measures), contour_run.hip (contours), overlap_run.hip
 // (component overlaps), multiphase_run.hip (four phases: a pair of contexts iterated together), localized_run.hip (localised regions), geodesic_run.hip (edge-weighted length), march_run.hip (the driver under those three; march_flow.h: their one call sequence, over each file's flow description), edge_run.hip (the edge plane), debug_exports.hip (diagnostics).  Kernel
 // sources do not include it.
@@ -184,6 +184,9 @@ struct cvh_context {   // opaque to callers; four groups
   void *d_rank = nullptr;        // workspace of cvh_rank_planes* (window_run.hip) as their DESTINATION: CVH_RANK_SLOTS byte planes per plane of this context
                                  // (7 bytes per pixel and plane): allocated by the first call that takes anything but copies, kept -- not part
                                  // of live_footprint either
+  void *d_smooth = nullptr;      // workspace of cvh_smooth_planes* (window_run.hip) as their DESTINATION: the row pass's 16-bit values, a slot of 2 bytes
+                                 // per pixel per plane of this context: allocated by the first call that takes anything but copies, kept -- not
+                                 // part of live_footprint either; a member of its own, since a workspace is sized by the family that allocated it
   DeviceTable overlap;           // cvh_overlaps* (overlap_run.hip): overlap.count slots of the pair table and overlap.count / 2 rows behind them (24 bytes
                                  // per slot), grown where a call's table overflows, kept; d_overlap_plane: the int32 plane the host form stages
   void *d_overlap_plane = nullptr;   // (4 bytes per pixel) -- allocated by the first call that needs them, not part of live_footprint either
@@ -312,9 +315,9 @@ void free_table(DeviceTable *t);
 // reduce pass for all members) of cvh_energy*, the launch sets (four kernels for all members) of cvh_score_mask*, and the launch sets (every
 // kernel of the call, for all members) of cvh_get_mask_morph* / cvh_morph_levelset* / cvh_init_mask*, and the pair launches of cvh_overlaps*
 // (one per call, and one more each time a member's table had to grow), and the launch sets (every pass of the family for all pairs) of
-// cvh_local_planes* and of cvh_rank_planes* (window_run.hip: a Family names its counter), and the calls of cvh_split* / cvh_split_levelset*
+// cvh_local_planes*, of cvh_rank_planes* and of cvh_smooth_planes* (window_run.hip: a Family names its counter), and the calls of cvh_split* / cvh_split_levelset*
 // with the growth sweeps that ran in them (a sweep that returned at once is not counted)
-enum LaunchCounter { kReinitLaunchSets, kPyramidLaunches, kColourLaunches, kEnergyLaunchSets, kScoreLaunchSets, kMorphLaunchSets, kOverlapLaunchSets, kLocalLaunchSets, kRankLaunchSets, kSplitLaunchSets, kSplitSweeps, kLaunchCounters };
+enum LaunchCounter { kReinitLaunchSets, kPyramidLaunches, kColourLaunches, kEnergyLaunchSets, kScoreLaunchSets, kMorphLaunchSets, kOverlapLaunchSets, kLocalLaunchSets, kRankLaunchSets, kSmoothLaunchSets, kSplitLaunchSets, kSplitSweeps, kLaunchCounters };
 extern std::atomic<unsigned long> g_launches[kLaunchCounters];
 
 // io_run.hip: what every call on device memory or on a member table shares (the comments are at the definitions)
@@ -482,9 +485,10 @@ struct PlaneSums {
   int fetch(const MemberCall &call);
   void arrive(const MemberCall &call);
 };
-// the one path of a call that replaces the planes of ctxs[0 .. n_written-1] (an ingest, a conversion, a luma, local statistics, rank planes, a restrict): see io_run.hip
+// the one path of a call that replaces the planes of ctxs[0 .. n_written-1] (an ingest, a conversion, a luma, local statistics, rank planes, smoothing, a restrict): see io_run.hip
 int write_planes(cvh_context *const *ctxs, int n_written, int n_members, const char *what, void *stream,
-                 const std::function<void(int, CvhIoMember &)> &fill, const std::function<int(const MemberCall &)> &launch);
+                 const std::function<void(int, CvhIoMember &)> &fill, const std::function<int(const MemberCall &)> &launch,
+                 size_t payload_bytes = 0, const std::function<void(int, void *)> &payload = nullptr);
 
 // cvh_get_mask / cvh_get_mask_clean: into_d_mask() writes c->d_mask (allocated on first use) on c's stream; the bytes come down, one wait
 template <class F>

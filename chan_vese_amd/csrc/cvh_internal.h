@@ -224,7 +224,7 @@ struct CvhPmIoPlane { uint8_t *img; double *state; unsigned long long n; };
 // aligned entries.
 struct CvhIoMember {
   const void *src;                    // ingest: the caller's bytes; mask, reinit: the level set (double); checkerboard: the h row factors
-  const void *src2;                   // checkerboard: the w column factors
+  const void *src2;                   // checkerboard: the w column factors; smoothing: the pair's taps
   void *dst;                          // mask / interleaved planes out: the caller's buffer; checkerboard, reinit: the level set written
   uint8_t *plane[CVH_MAX_CHANNELS];   // the context's planes (ingest: written; planes out: read); reinit: [0] the class words of the
                                       // bands, [1] the distance fields (the context's workspace)
@@ -365,6 +365,17 @@ hipError_t cvh_launch_local(const CvhIoMember *tab, int nmem, unsigned grid, uns
 __host__ __device__ constexpr size_t cvh_rank_slot_bytes(int h, int w) { return ((size_t)h * cvh_window_pitch(w) + 255) & ~(size_t)255; }
 unsigned cvh_rank_blocks(int h, int w, int R, int row_jobs, int median_planes);
 hipError_t cvh_launch_rank(const CvhIoMember *tab, int nmem, unsigned grid, unsigned passes, hipStream_t s);
+// smoothing (smooth_kernels.hip): codes what[k] << 2 k; src2 the pair's payload, CVH_SMOOTH_TAPS taps of 16 bits (zero behind the radius);
+// the workspace a slot of cvh_smooth_slot_bytes(h, w) per source plane, the row pass's 8.8 fixed-point values.  Two launches: the row
+// pass where a pair has `passes`, and the column pass, in which a WORKGROUP takes a band of cvh_smooth_band_rows(R) rows x
+// CVH_SMOOTH_STRIP columns per trip: the band and R rows on either side are the CVH_SMOOTH_TILE_ROWS rows of its LDS tile.
+#define CVH_SMOOTH_TAPS (CVH_SMOOTH_RADIUS_MAX + 1)
+#define CVH_SMOOTH_STRIP 64
+#define CVH_SMOOTH_TILE_ROWS 256
+__host__ __device__ constexpr int cvh_smooth_band_rows(int R) { return CVH_SMOOTH_TILE_ROWS - 2 * R; }
+__host__ __device__ constexpr size_t cvh_smooth_slot_bytes(int h, int w) { return (2 * (size_t)h * cvh_window_pitch(w) + 15) & ~(size_t)15; }
+unsigned cvh_smooth_blocks(int h, int w, int R, int planes_read);
+hipError_t cvh_launch_smooth(const CvhIoMember *tab, int nmem, unsigned grid, unsigned passes, hipStream_t s);
 // energy (energy_kernels.hip).  src the level set, src2 the CvhState that holds its means, plane[] the planes, dst the member's item rows
 // (cvh_energy_items x CVH_ENERGY_SLOTS doubles of the context's workspace), sums a row of CVH_ENERGY_ROW doubles: [0] eps (read), then
 // length, area, fit_in[3], fit_out[3], c1[3], c2[3] (written).  An item is CVH_ENERGY_BAND rows x CVH_ENERGY_COLS columns, a wave's trip.

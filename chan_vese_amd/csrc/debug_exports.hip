@@ -2,6 +2,7 @@
 #include "cvh_host.h"
 #include "wave_math.h"
 #include "local_math.h"
+#include "smooth_math.h"
 #include "rank_math.h"
 
 // Diagnostic (not part of include/chanvese_hip.h): the strip table for a geometry, without a device.  out needs S + 1 ints.
@@ -202,6 +203,18 @@ extern "C" int cvh_debug_rank_twice(int code) { return cvh_rank_twice(code); }
 extern "C" int cvh_debug_rank_band_rows(int R) { return cvh_rank_band_rows(R, CVH_WINDOW_BAND); }
 extern "C" unsigned cvh_debug_rank_median_index(unsigned n) { return cvh_rank_median_index(n); }
 extern "C" int cvh_debug_rank_walk(const unsigned *words, unsigned *before, unsigned t) { return cvh_rank_walk(words, before, t); }
+// Diagnostics (not part of include/chanvese_hip.h) of cvh_smooth_planes*: launch sets so far in this process (a batch of n pairs is one: the
+// row pass, where a pair takes a blur or a detail plane, and the column pass); the passes' geometry at a radius, from which
+// tests/smooth_util.py derives the seam shapes -- *band rows x *strip columns a workgroup of the column pass takes per trip, *segment
+// columns of a row segment --; and the roundings of smooth_math.h compiled for the host (tests/test_smooth_restatement.py)
+extern "C" unsigned long cvh_debug_smooth_launch_sets(void) { return g_launches[kSmoothLaunchSets].load(); }
+extern "C" void cvh_debug_smooth_geometry(int radius, int *band, int *strip, int *segment)
+{
+  *band = cvh_smooth_band_rows(radius); *strip = CVH_SMOOTH_STRIP; *segment = CVH_WINDOW_SEGMENT;
+}
+extern "C" unsigned cvh_debug_smooth_row(unsigned a) { return cvh_smooth_row(a); }
+extern "C" unsigned cvh_debug_smooth_blur(unsigned b) { return cvh_smooth_blur(b); }
+extern "C" unsigned cvh_debug_smooth_detail(unsigned p, unsigned blur) { return cvh_smooth_detail(p, blur); }
 // Diagnostic (not part of include/chanvese_hip.h): launch sets of cvh_energy / cvh_energy_batch so far in this process -- one set is the
 // term pass and the reduce pass of energy_kernels.hip over all members of the call (tests/test_gpu_energy.py: a batch of n is one set)
 extern "C" unsigned long cvh_debug_energy_launch_sets(void) { return g_launches[kEnergyLaunchSets].load(); }

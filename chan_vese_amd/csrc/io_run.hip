@@ -217,8 +217,11 @@ void PlaneSums::arrive(const MemberCall &call)
 // cvh_set_image does; fill(i, m) sets everything of written member i's table entry but `sums`; launch(call) enqueues the kernel on the
 // leader's stream and counts it.  Staging: [member table][8 sums per member, zero] uploaded; behind them the planes of the members whose
 // stop norm the host takes.  Behind the call's ONE host wait the written members are left as cvh_set_image of those bytes leaves them.
+// With payload_bytes, every written member has that many bytes more (a multiple of 16) behind the sums, uploaded with the table in the
+// same copy: payload(i, p) fills member i's, and its device address is the entry's src2.
 int write_planes(cvh_context *const *ctxs, int n_written, int n_members, const char *what, void *stream,
-                 const std::function<void(int, CvhIoMember &)> &fill, const std::function<int(const MemberCall &)> &launch)
+                 const std::function<void(int, CvhIoMember &)> &fill, const std::function<int(const MemberCall &)> &launch,
+                 size_t payload_bytes, const std::function<void(int, void *)> &payload)
 {
   HIPCHK(ctxs[0], hipSetDevice(ctxs[0]->device));
   int rc = settle_all(ctxs, n_written, what);
@@ -226,11 +229,16 @@ int write_planes(cvh_context *const *ctxs, int n_written, int n_members, const c
   PlaneSums back;
   back.plan(ctxs, n_written);
   MemberCall call;
-  rc = call.begin(ctxs, n_members, what, back.sums_bytes, back.fetch_bytes);
+  const size_t payload_off = align_up(back.sums_bytes, 256);   // from the call's device extra
+  rc = call.begin(ctxs, n_members, what, payload_bytes ? payload_off + (size_t)n_written * payload_bytes : back.sums_bytes, back.fetch_bytes);
   if (rc != CVH_OK) return rc;
   for (int i = 0; i < n_written; ++i) {
     fill(i, call.tab[i]);
     call.tab[i].sums = back.device_sums(call, i);
+    if (!payload_bytes) continue;
+    const size_t at = call.extra_off + payload_off + (size_t)i * payload_bytes;
+    payload(i, call.hb + at);
+    call.tab[i].src2 = call.db + at;
   }
   rc = call.run(stream, false, true, [&]() -> int {   // the sums come back to host fields
     const int rc_launch = launch(call);

@@ -47,6 +47,9 @@
 // filter of every plane over the (2R+1)^2 window -- a median against impulse noise, a top-hat against a shading ramp; made on the device
 // behind Perona-Malik and --colorspace, in front of --local (which then works on its result) and of the start; --dump-planes FILE writes
 // the planes the run iterated on.
+// --smooth blur|detail with --smooth-sigma S (chanvese_hip.h, "Smoothing"): the run iterates on the Gaussian blur of every plane, or on
+// 128 + plane - blur; made on the device behind --rank and in front of --local.  --edge-sigma S (with --edge K): the edge map is built
+// from a blurred scratch copy of the planes; the taps of both are cvh_gauss_taps'.
 // --colorspace ycrcb|yuv (chanvese_hip.h, "Colour spaces"; not with -g): the loader's B, G, R planes become (Y, Cr, Cb) / (Y, U, V) on the
 // device behind Perona-Malik -- <stem>_pm stays the RGB picture the reference writes -- and in front of the iterations (with --levels: on
 // the finest level, before the restricts); --lambda1 / --lambda2 then weigh the luma and the two chroma planes, a start of --init otsu /
@@ -254,20 +257,27 @@ cvh_context *make_context(int h, int w, int channels, const cvh_params *prm, int
 // coarse-to-fine run, each half the one before (idle while another level runs: "co_resident"), or the second level set of a four-phase
 // run.  --local: the file's planes go into a context of their own (ingest), where they are smoothed and converted; ctx receives their
 // local statistics.  --rank goes the same way and in front of --local: with both, the rank planes land in a context of their own
-// (ranked) that --local reads.
+// (ranked) that --local reads.  --smooth stands between the two: the stages run rank, smooth, local, each reading what the one before
+// made; the last one writes ctx, the others a context of their own (ranked, smoothed).
 struct Run {
   const Options &opt;
-  cvh_context *ctx = nullptr, *ingest = nullptr, *ranked = nullptr;
+  cvh_context *ctx = nullptr, *ingest = nullptr, *ranked = nullptr, *smoothed = nullptr;
   std::vector<cvh_context *> level;
   explicit Run(const Options &o) : opt(o) {}
   Run(const Run &) = delete;
   void refresh_planes() const   // ctx's planes from ingest's: at the start, and again behind -S and --colorspace
   {
-    if (opt.rank) cvh_check(ranked, cvh_rank_planes(ingest, ranked, opt.rank_radius, opt.rank_what), "cvh_rank_planes");
-    if (opt.local) cvh_check(ctx, cvh_local_planes(opt.rank ? ranked : ingest, ctx, opt.local_radius, opt.local_what), "cvh_local_planes");
+    cvh_context *made = ingest;   // where the last stage has left the planes
+    if (opt.rank) { cvh_check(ranked, cvh_rank_planes(made, ranked, opt.rank_radius, opt.rank_what), "cvh_rank_planes"); made = ranked; }
+    if (opt.smooth) {
+      cvh_check(smoothed, cvh_smooth_planes(made, smoothed, opt.smooth_radius, opt.smooth_taps, opt.smooth_what), "cvh_smooth_planes");
+      made = smoothed;
+    }
+    if (opt.local) cvh_check(ctx, cvh_local_planes(made, ctx, opt.local_radius, opt.local_what), "cvh_local_planes");
   }
   ~Run()
   {
+    if (smoothed != ctx) cvh_destroy(smoothed);
     if (ranked != ctx) cvh_destroy(ranked);
     if (ingest != ctx) cvh_destroy(ingest);
     for (size_t k = level.size(); k-- > 0;) cvh_destroy(level[k]);
@@ -282,14 +292,15 @@ void make_run(Run &run, const Options &opt, Inputs &in, const cvh_params &prm)
     msg_exit("Too many levels for a " + std::to_string(in.h) + " x " + std::to_string(in.w) + " image: the coarsest side must not fall below 16.");
   ContextOptions co;
   co.math_mode = opt.math_mode; co.state = opt.state_bits;
-  run.ctx = run.ingest = run.ranked = make_context(in.h, in.w, opt.run_channels(), &prm, opt.device, co);
+  run.ctx = run.ingest = run.ranked = run.smoothed = make_context(in.h, in.w, opt.run_channels(), &prm, opt.device, co);
   run.level.push_back(run.ctx);
   co.state_may_fail = true; co.co_resident = 0;
   for (int k = 1; k < opt.levels; ++k) run.level.push_back(make_context(shape[k].first, shape[k].second, opt.run_channels(), &prm, opt.device, co));
   ContextOptions planes_only;
   planes_only.co_resident = 0;
-  if (opt.local || opt.rank) run.ingest = make_context(in.h, in.w, opt.nof_channels(), nullptr, opt.device, planes_only);
-  if (opt.local && opt.rank) run.ranked = make_context(in.h, in.w, opt.nof_channels(), nullptr, opt.device, planes_only);
+  if (opt.local || opt.rank || opt.smooth) run.ingest = make_context(in.h, in.w, opt.nof_channels(), nullptr, opt.device, planes_only);
+  if (opt.rank && (opt.smooth || opt.local)) run.ranked = make_context(in.h, in.w, opt.nof_channels(), nullptr, opt.device, planes_only);
+  if (opt.smooth && opt.local) run.smoothed = make_context(in.h, in.w, opt.nof_channels(), nullptr, opt.device, planes_only);
   cvh_check(run.ingest, cvh_set_image(run.ingest, in.plane_pointers().data()), "cvh_set_image");
   run.refresh_planes();
 }
@@ -468,7 +479,17 @@ Progress iterate(const Run &run, const Options &opt, const Inputs &in, Frames &f
   } else if (opt.localized) {
     cvh_check(ctx, cvh_localized_run(ctx, opt.localized, opt.steps(), &p.steps, &p.norm, nullptr, 0, nullptr), "cvh_localized_run");
   } else if (opt.edge > 0.0) {   // the map from the planes as every stage in front of the run has left them
-    cvh_check(ctx, cvh_edge_map(ctx, ctx, opt.edge), "cvh_edge_map");
+    if (opt.edge_sigma > 0.0) {   // g from G_sigma * I: a blurred scratch copy is the map's source, the run keeps the planes
+      ContextOptions planes_only;
+      planes_only.co_resident = 0;
+      cvh_context *scratch = make_context(in.h, in.w, opt.run_channels(), nullptr, opt.device, planes_only);
+      const int blur[3] = {CVH_SMOOTH_BLUR, CVH_SMOOTH_BLUR, CVH_SMOOTH_BLUR};
+      cvh_check(scratch, cvh_smooth_planes(ctx, scratch, opt.edge_radius, opt.edge_taps, blur), "cvh_smooth_planes");
+      cvh_check(ctx, cvh_edge_map(ctx, scratch, opt.edge), "cvh_edge_map");
+      cvh_destroy(scratch);
+    } else {
+      cvh_check(ctx, cvh_edge_map(ctx, ctx, opt.edge), "cvh_edge_map");
+    }
     if (!opt.dump_edge.empty()) {
       std::vector<uint16_t> gq(in.n);
       cvh_check(ctx, cvh_get_edge_map(ctx, gq.data()), "cvh_get_edge_map");
@@ -675,7 +696,7 @@ void run_four_phase(const Options &opt, Inputs &in, const cvh_params &prm)
   ContextOptions co;
   co.math_mode = opt.math_mode;
   for (int k = 0; k < 2; ++k) run.level.push_back(make_context(in.h, in.w, opt.run_channels(), &prm, opt.device, co));
-  cvh_context *pa = run.ctx = run.ingest = run.ranked = run.level[0], *pb = run.level[1];
+  cvh_context *pa = run.ctx = run.ingest = run.ranked = run.smoothed = run.level[0], *pb = run.level[1];
   cvh_check(pa, cvh_set_image(pa, in.plane_pointers().data()), "cvh_set_image");
   if (opt.segment) smooth_and_write_pm(run, opt, in);   // once: B takes the smoothed bytes
   cvh_check(pb, cvh_set_image(pb, in.plane_pointers().data()), "cvh_set_image");

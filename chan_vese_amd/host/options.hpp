@@ -42,7 +42,7 @@ const Spec kSpecs[] = {
     {"phases", 0, 1}, {"init2", 0, 2}, {"dump-labels", 0, 1}, {"localized", 0, 1}};
 // what came after the table above and the --help text were pinned (tests/test_cli.py, tests/golden/cli_refusals.json): long names only,
 // listed by --help --verbose
-const Spec kLaterSpecs[] = {{"split", 0, 1}, {"split-labels", 0, 1}, {"edge", 0, 1}, {"dump-edge", 0, 1}};
+const Spec kLaterSpecs[] = {{"split", 0, 1}, {"split-labels", 0, 1}, {"edge", 0, 1}, {"dump-edge", 0, 1}, {"smooth", 0, 1}, {"smooth-sigma", 0, 1}, {"edge-sigma", 0, 1}};
 
 struct Parsed {
   std::vector<std::pair<std::string, std::vector<std::string>>> opts;
@@ -216,6 +216,11 @@ struct Options {
   std::string dump_u, dump_mask, dump_planes, dump_labels, measure, contours, truth, truth_labels, init_mask, split_labels, dump_edge;
   int device = 0, math_mode = CVH_MATH_FAST, state_bits = 64, reinit_every = 0, levels = 1, energy_every = 0, phases = 2, localized = 0;
   double edge = 0.0;   // --edge K: > 0 where given
+  // --smooth blur|detail with --smooth-sigma S, and --edge-sigma S: the taps are cvh_gauss_taps' (chanvese_hip.h, "Smoothing")
+  bool smooth = false;
+  double smooth_sigma = 1.0, edge_sigma = 0.0;   // edge_sigma > 0 where given
+  int smooth_what[3] = {CVH_SMOOTH_COPY, CVH_SMOOTH_COPY, CVH_SMOOTH_COPY}, smooth_radius = 0, edge_radius = 0;
+  uint16_t smooth_taps[CVH_SMOOTH_RADIUS_MAX + 1] = {0}, edge_taps[CVH_SMOOTH_RADIUS_MAX + 1] = {0};
   CleanArgs clean = {4, 0, 0, 0, 0};
   bool clean_mask = false;                         // a cleaning option is given: _selection, --dump-mask and --roi use the cleaned mask
   bool roi = false, energy = false, contours_all = false, contours_subpixel = false, verbose = false;
@@ -284,7 +289,7 @@ inline Options read_options(const Parsed &vm)
   auto given = [&](const char *n) { return vm.count(n) > 0; };
   const ReadOne read{vm};
   std::string text_position = "TL", line_color = "blue", math = "fast", rect, circ, disk, init_kind = "checkerboard", colorspace, local_name,
-              rank_name, morph_name;
+              rank_name, morph_name, smooth_name;
   double morph_radius = 1.0, score_tol = 2.0, split_radius = 0.0;
   int threshold = -1;
   read("input", o.input);
@@ -344,6 +349,9 @@ inline Options read_options(const Parsed &vm)
   read("dump-edge", o.dump_edge);
   if (given("edge") && (!(o.edge > 0.0) || !std::isfinite(o.edge)))
     msg_exit("Edge contrast (--edge) must be a finite number > 0: " + std::to_string(o.edge) + ".");
+  read("smooth", smooth_name);      // --smooth blur|detail (chanvese_hip.h, "Smoothing"): cvh_smooth_planes behind --rank, in front of --local
+  read("smooth-sigma", o.smooth_sigma);
+  read("edge-sigma", o.edge_sigma);  // --edge-sigma S: the edge map of --edge is built from a blurred scratch copy of the planes
   o.segment = given("segment"); o.grayscale = given("grayscale"); o.video = given("video"); o.overlay_text = given("overlay-text");
   o.select = given("select"); o.roi = given("roi"); o.energy = given("energy"); o.verbose = given("verbose");
   o.contours_all = given("contours-all"); o.contours_subpixel = given("contours-subpixel");
@@ -364,6 +372,16 @@ inline Options read_options(const Parsed &vm)
   if (o.local_stack) { o.local_what[1] = CVH_LOCAL_MEAN; o.local_what[2] = CVH_LOCAL_DEV; }
   // --rank: the run iterates on a rank filter of the planes (chanvese_hip.h, "Rank planes"), every plane alike
   o.rank = window_option(vm, kRankOption, rank_name, o.rank_radius, o.rank_what);
+  // --smooth: the run iterates on the Gaussian blur of the planes or on what the blur leaves of them, every plane alike
+  if (given("smooth-sigma") && !given("smooth")) msg_exit("A scale (--smooth-sigma) needs a smoothing (--smooth).");
+  if (given("smooth")) {
+    if (iequals(smooth_name, "blur")) o.smooth_what[0] = o.smooth_what[1] = o.smooth_what[2] = CVH_SMOOTH_BLUR;
+    else if (iequals(smooth_name, "detail")) o.smooth_what[0] = o.smooth_what[1] = o.smooth_what[2] = CVH_SMOOTH_DETAIL;
+    else msg_exit("Invalid smoothing requested.\nCorrect values are: blur, detail.");
+    if (cvh_gauss_taps(o.smooth_sigma, o.smooth_taps, &o.smooth_radius) != CVH_OK)
+      msg_exit("Smoothing scale (--smooth-sigma) must be a finite number > 0 and at most 21: " + std::to_string(o.smooth_sigma) + ".");
+    o.smooth = true;
+  }
   o.one_plane = o.grayscale && !o.local_stack;
   check_lambdas(vm, "lambda1", o.one_plane, o.lambda1);
   check_lambdas(vm, "lambda2", o.one_plane, o.lambda2);
@@ -457,13 +475,17 @@ inline Options read_options(const Parsed &vm)
         {given("colorspace"), "--colorspace"}, {!o.dump_planes.empty(), "--dump-planes"}, {!o.dump_u.empty(), "--dump-u"},
         {!o.dump_mask.empty(), "--dump-mask"}, {o.clean_mask, "the cleaning options"}, {o.roi, "--roi"}, {given("morph"), "--morph"},
         {!o.truth.empty(), "--truth"}, {!o.truth_labels.empty(), "--truth-labels"}, {!o.measure.empty(), "--measure"},
-        {!o.contours.empty(), "--contours"}, {o.clean.invert != 0, "an inverted selection (-I)"}, {o.split, "an object split (--split)"}});
+        {!o.contours.empty(), "--contours"}, {o.clean.invert != 0, "an inverted selection (-I)"}, {o.split, "an object split (--split)"}, {given("smooth"), "--smooth"}});
   if (o.localized)
     refuse_combinations("Localised regions (--localized)", {
         {o.phases == 4, "four phases (--phases 4)"}, {o.levels > 1, "a coarse-to-fine run (--levels)"}, {o.energy, "an energy line (--energy)"},
         {o.energy_every > 0, "an energy series (--energy-every)"}, {o.reinit_every > 0, "reinitialisation (--reinit)"},
         {o.video, "video output (-V)"}, {o.state_bits == 32, "FP32 state (--state 32)"}});
   if (!o.dump_edge.empty() && !given("edge")) msg_exit("An edge map file (--dump-edge) needs an edge-weighted run (--edge).");
+  if (given("edge-sigma") && !given("edge")) msg_exit("A blurred edge map (--edge-sigma) needs an edge-weighted run (--edge).");
+  if (given("edge-sigma") && cvh_gauss_taps(o.edge_sigma, o.edge_taps, &o.edge_radius) != CVH_OK)
+    msg_exit("Edge scale (--edge-sigma) must be a finite number > 0 and at most 21: " + std::to_string(o.edge_sigma) + ".");
+  if (!given("edge-sigma")) o.edge_sigma = 0.0;
   if (given("edge"))
     refuse_combinations("Edge-weighted length (--edge)", {
         {o.phases == 4, "four phases (--phases 4)"}, {o.localized != 0, "localised regions (--localized)"}, {o.levels > 1, "a coarse-to-fine run (--levels)"},
@@ -609,5 +631,11 @@ inline void print_help(bool later = false)
       "                                     contour length; honours --init / --rect / --circ / --disk / --init-mask; not with --phases 4, --localized,\n"
       "                                     --levels, --energy, --energy-every, --reinit, -V, --state 32\n"
       "  --dump-edge arg                    write the edge map of --edge as raw little-endian uint16 (h*w; 32768 = 1)\n"
+      "  --smooth arg                       blur | detail: iterate on the Gaussian blur of every plane, or on 128 + plane - blur (the plane\n"
+      "                                     without its smooth background); integer taps, replicated border; made on the device behind\n"
+      "                                     Perona-Malik, --colorspace and --rank, in front of --local and the initial level set; not with --phases 4\n"
+      "  --smooth-sigma arg (=1)            sigma of that Gaussian, 0 < sigma <= 21 (its radius is ceil(3 sigma))\n"
+      "  --edge-sigma arg                   sigma, 0 < sigma <= 21: --edge builds its map from a Gaussian-blurred scratch copy of the planes,\n"
+      "                                     g = 1 / (1 + |grad (G_sigma * I)|^2 / K^2), while the run iterates on the unblurred planes\n"
       "\n";
 }

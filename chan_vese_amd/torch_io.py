@@ -164,6 +164,27 @@ def check_rank(rank, channels):
     return None if rank is None else _check_window(rank, "rank", channels, capi.rank_what_codes, capi.rank_radius)
 
 
+def check_smooth(smooth, channels):
+    """Validates Segmenter's `smooth` and returns ((radius, taps), codes, channels of the planes the stage makes), or None for None.
+    `smooth` is (kernel, what): kernel a float sigma (the library's Gaussian, capi.gauss_taps) or a sequence of integer taps
+    (capi.smooth_kernel); what "blur" / "detail" (every plane; as many planes as it is given) or a tuple of 1 or 3 capi.SMOOTH_* codes
+    (as many planes as codes).  ValueError for anything else.  Only a Gaussian calls the library (a host function that needs no device)."""
+    if smooth is None:
+        return None
+    return _check_window(smooth, "smooth", channels, capi.smooth_what_codes, lambda k, _: capi.smooth_kernel(k), radius_first=True)
+
+
+def check_edge_sigma(edge_sigma, edge):
+    """Validates Segmenter's `edge_sigma` and returns its (radius, taps), or None for None.  It needs edge=K."""
+    if edge_sigma is None:
+        return None
+    if edge is None:
+        raise ValueError("edge_sigma= needs edge=K: it blurs the planes the edge map is built from")
+    if isinstance(edge_sigma, bool) or not isinstance(edge_sigma, (int, float)) or not math.isfinite(edge_sigma) or not 0 < edge_sigma <= 21:
+        raise ValueError(f"edge_sigma must be None or a finite sigma in (0, 21], got {edge_sigma!r}")
+    return capi.gauss_taps(float(edge_sigma))
+
+
 def scale_init(kind, rows, levels):
     """The numbers of a ("rect", ..) / ("disk", ..) start, given in finest pixels, on the coarsest of `levels` levels: every number is
     shifted right by levels - 1 (an arithmetic shift: negative coordinates round down).  Other kinds pass through."""
@@ -192,6 +213,10 @@ class Segmenter:
     rank = (radius, what) makes the run iterate on rank planes of the ingested planes -- a median against impulse noise, a top-hat
     against a shading ramp (check_rank; cvh_rank_planes_batch) -- in source contexts of its own, as local= does.  With both given the
     rank filter runs FIRST, into `ranked`, contexts of the filter's channels, and local= works on its result.
+    smooth = (kernel, what) makes the run iterate on smoothed planes -- the blur under a Gaussian of sigma `kernel` (a float) or under the
+    integer taps given, or the detail the blur leaves (check_smooth; cvh_smooth_planes_batch) -- in source contexts of its own, as rank=
+    does, and is accepted and refused where rank= is.  The stages run colour -> rank -> smooth -> local; a stage that another follows
+    writes into contexts of its own (`ranked`, `smoothed`).
     phases = 4 (include/chanvese_hip.h, "Four phases") makes every member a PAIR of contexts, `contexts[i]` holding phi1 and `contexts_b[i]`
     phi2, both fed the same device tensor; segment() then iterates the pairs (cvh_multiphase_run_batch) and returns labels 0 .. 3, phase_masks()
     gives the two mask tensors, and the post-processing methods take phase = 0 | 1.  It needs levels = 1 and neither local= nor rank=.
@@ -203,7 +228,11 @@ class Segmenter:
     edge = K (finite, > 0; include/chanvese_hip.h, "Edge-weighted length") makes segment() build every member's edge plane from its own
     planes as they stand after the preprocessing above (cvh_edge_map_batch with that K) and iterate with cvh_geodesic_run_batch -- the
     length term weighted by the plane -- instead of the two-phase run; edge_maps() returns the planes.  It needs phases = 2, levels = 1 and
-    no localized=, and segment() refuses energy_every and reinit_every with it.  None (the default) is the plain path, call for call."""
+    no localized=, and segment() refuses energy_every and reinit_every with it.  None (the default) is the plain path, call for call.
+    edge_sigma = sigma (0 < sigma <= 21; needs edge=K) builds the edge plane from G_sigma * I, the textbook edge function: every member's
+    planes, as the preprocessing left them, are blurred into scratch contexts (`edge_sources`; cvh_smooth_planes_batch) and
+    cvh_edge_map_batch takes those as its sources, while the run iterates on the unblurred planes.  None: the map is built from the
+    planes themselves."""
     levels = 1
     phases = 2
     localized = None
@@ -212,16 +241,20 @@ class Segmenter:
     colour = None
     local = None
     rank = None
+    smooth = None
+    edge_kernel = None
     sources = ()
     ranked = ()
+    smoothed = ()
+    edge_sources = ()
 
     @property
     def run_channels(self):
-        """channels of the planes the run iterates on: the ingested ones', or with rank= and local= what their codes make of them"""
-        return self.local[2] if self.local else self.rank[2] if self.rank else self.channels
+        """channels of the planes the run iterates on: the ingested ones', or with rank=, smooth= and local= what their codes make of them"""
+        return self.local[2] if self.local else self.smooth[2] if self.smooth else self.rank[2] if self.rank else self.channels
 
     def __init__(self, n, h, w, channels=1, params=None, device=0, options=None, levels=1, colour=None, order="rgb", local=None, rank=None,
-                 phases=2, params2=None, localized=None, edge=None):
+                 phases=2, params2=None, localized=None, edge=None, smooth=None, edge_sigma=None):
         if n < 1:
             raise ValueError(f"n must be >= 1, got {n}")
         if edge is not None:
@@ -238,15 +271,21 @@ class Segmenter:
             raise ValueError(f"phases must be 2 or 4, got {phases!r}")
         if phases == 4 and (levels != 1 or local is not None or rank is not None):
             raise ValueError("phases=4 needs levels = 1 and neither local= nor rank=")
+        if phases == 4 and smooth is not None:
+            raise ValueError("phases=4 needs levels = 1 and none of local=, rank= and smooth=")
         if phases != 4 and params2 is not None:
             raise ValueError("params2 (the parameters of the second level set) needs phases=4")
         shapes = check_levels(levels, h, w)
         self.colour, self.order = check_colour(colour, order, channels)
         self.rank = check_rank(rank, channels)
-        self.local = check_local(local, self.rank[2] if self.rank else channels)
+        self.smooth = check_smooth(smooth, self.rank[2] if self.rank else channels)
+        self.local = check_local(local, self.smooth[2] if self.smooth else self.rank[2] if self.rank else channels)
+        self.edge_kernel = check_edge_sigma(edge_sigma, edge)
         self.n, self.h, self.w, self.channels, self.levels = n, h, w, channels, levels
         self.sources = []
         self.ranked = []
+        self.smoothed = []
+        self.edge_sources = []
         self.device = _device_index(device)
         self.thresholds = None   # Otsu's thresholds of the last segment(init="otsu")
         self.level_steps = None  # levels > 1: the iterations of the last segment() per member and level, finest first
@@ -272,10 +311,14 @@ class Segmenter:
                         self.contexts.append(ctx)
                     for key, value in (options or {}).items():
                         ctx.set_option(key, value)
-                if self.local or self.rank:
+                if self.local or self.rank or self.smooth:
                     self.sources.append(capi.Context(h, w, channels, None, self.device))
-                if self.local and self.rank:
+                if self.rank and (self.local or self.smooth):
                     self.ranked.append(capi.Context(h, w, self.rank[2], None, self.device))
+                if self.smooth and self.local:
+                    self.smoothed.append(capi.Context(h, w, self.smooth[2], None, self.device))
+                if self.edge_kernel:
+                    self.edge_sources.append(capi.Context(h, w, self.run_channels, None, self.device))
         except Exception:
             self.close()
             raise
@@ -284,8 +327,10 @@ class Segmenter:
         for pyr in self.pyramids:
             for ctx in pyr:
                 ctx.close()
-        for ctx in list(self.sources) + list(self.ranked) + list(self.contexts_b):
+        for ctx in list(self.sources) + list(self.ranked) + list(self.smoothed) + list(self.edge_sources) + list(self.contexts_b):
             ctx.close()
+        self.smoothed = []
+        self.edge_sources = []
         self.contexts_b = []
         self.contexts = []
         self.pyramids = []
@@ -398,6 +443,9 @@ class Segmenter:
         LOCAL planes, and images() returns them; masks come out as before.
         rank (the constructor's): as local, with ONE cvh_rank_planes_batch; "otsu" and ("threshold", t) see the RANK planes.  With both,
         the rank call writes into `ranked` and the local call reads from there.
+        smooth (the constructor's): as rank, with ONE cvh_smooth_planes_batch behind the rank call and in front of the local call; "otsu"
+        and ("threshold", t) see the SMOOTHED planes.  edge_sigma (the constructor's): ONE more cvh_smooth_planes_batch blurs the planes
+        the run iterates on into `edge_sources`, from which cvh_edge_map_batch builds the edge planes.
         energy_every = K > 0 runs segments of K iterations with the energy of the members still iterating taken after each
         (capi.run_batch_monitored, one cvh_energy_batch per segment; max_steps stays the total budget) and stores the series in
         self.energy_series; 0 takes none and leaves self.energy_series None.  It is a ValueError with levels > 1 or reinit_every > 0.
@@ -443,17 +491,22 @@ class Segmenter:
             raise ValueError("perona_malik must be (K, L, T)")
         stream = self._stream()
         self.energy_series = None
-        ingested = self.sources if (self.local or self.rank) else self.contexts
+        ingested = self.sources if (self.local or self.rank or self.smooth) else self.contexts
         capi.set_image_device_batch(ingested, [images[i].data_ptr() for i in range(self.n)], layout, stream)
         if perona_malik is not None:
             K, L, T = perona_malik
             capi.perona_malik_batch(ingested, K, L, T)
         if self.colour is not None:
             capi.convert_colour_batch(ingested, self.colour, self.order)
+        made = self.sources   # where the last stage has left the planes
         if self.rank:
-            capi.rank_planes_batch(self.sources, self.ranked if self.local else self.contexts, self.rank[0], self.rank[1])
+            capi.rank_planes_batch(made, self.ranked or self.contexts, self.rank[0], self.rank[1])
+            made = self.ranked
+        if self.smooth:
+            capi.smooth_planes_batch(made, self.smoothed or self.contexts, [int(t) for t in self.smooth[0][1]], self.smooth[1])
+            made = self.smoothed
         if self.local:
-            capi.local_planes_batch(self.ranked if self.rank else self.sources, self.contexts, self.local[0], self.local[1])
+            capi.local_planes_batch(made, self.contexts, self.local[0], self.local[1])
         first = self.contexts   # the level the start is built on
         if self.levels > 1:
             for k in range(self.levels - 1):
@@ -486,7 +539,9 @@ class Segmenter:
         elif self.localized is not None:
             res = [r[:2] for r in capi.localized_run_batch(self.contexts, self.localized, max_steps)]
         elif self.edge is not None:   # (the planes the run iterates on, as every stage above has left them)
-            capi.edge_map_batch(self.contexts, self.contexts, self.edge)
+            if self.edge_kernel:   # g from G_sigma * I; the run keeps the unblurred planes
+                capi.smooth_planes_batch(self.contexts, self.edge_sources, [int(t) for t in self.edge_kernel[1]], "blur")
+            capi.edge_map_batch(self.contexts, self.edge_sources or self.contexts, self.edge)
             res = [r[:2] for r in capi.geodesic_run_batch(self.contexts, max_steps)]
         else:
             res = capi.run_batch_with_reinit(self.contexts, max_steps, reinit_every)

@@ -732,6 +732,70 @@ int cvh_rank_planes(cvh_context *src, cvh_context *dst, int radius, const int *w
 int cvh_rank_planes_batch(cvh_context *const *srcs, cvh_context *const *dsts, int n,
                           const int *radius /* n */, const int *what /* CVH_MAX_CHANNELS per pair */);
 
+/* ---- Smoothing ----------------------------------------------------------------------------------------------------------------
+ * A weighted window: the Gaussian blur that the two sections above do not have, and any other symmetric separable kernel.  Its uses
+ * here: the textbook edge function of "Edge-weighted length", g = 1 / (1 + |grad (G_sigma * I)|^2 / K^2), built from a blurred copy
+ * while the run keeps the unsmoothed planes; and p minus its smooth background, the flat-field step of microscopy.  These calls
+ * write such planes on the device -- what a caller otherwise does with cvh_get_image, a host filter and cvh_set_image.  The
+ * reference has no code for this; the definition below IS the contract, in integers, so every byte is defined.
+ *   Pairs.  Exactly as "Local statistics": src and dst are different contexts of the same h x w on the same device; each has 1 or 3
+ *          channels, independently.  Plane k of dst becomes f_what[k] of plane min(k, C_src - 1) of src, taken as the planes are now.
+ *          Entries of `what` at k >= C_dst are ignored.
+ *   Taps.  A pair has a radius R, 0 <= R <= CVH_SMOOTH_RADIUS_MAX, and R + 1 taps t[0 .. R] of 15-bit fixed point; the kernel is
+ *          symmetric, t[-i] = t[i], and t[0] + 2 sum_{i >= 1} t[i] must be exactly 32768.  Nothing else is asked: a box or a
+ *          binomial is as legal as a Gaussian, and the taps need not decay.
+ *   Border. Indices are CLAMPED to the plane (replicate; scipy's mode='nearest') -- NOT the truncated window of the two sections
+ *          above: a weight sum that changes per pixel would cost a division per pixel and pass.
+ *   Definition.  All sums are exact integers and >> is the arithmetic shift; each rounding is shown once.
+ *              row pass     a(x, y) = sum_{i = -R .. R} t[|i|] p(clamp(x + i, 0, w - 1), y)             below 2^23
+ *                           v = (a + 64) >> 7                    8.8 fixed point, at most 65280: a uint16_t
+ *              column pass  b(x, y) = sum_{j = -R .. R} t[|j|] v(x, clamp(y + j, 0, h - 1))             at most 65280 * 32768 < 2^31
+ *                           BLUR = (b + 2^22) >> 23              0 .. 255
+ *              CVH_SMOOTH_COPY    p
+ *              CVH_SMOOTH_BLUR    as above
+ *              CVH_SMOOTH_DETAIL  min(255, max(0, 128 + p - BLUR))
+ *          A constant plane c gives BLUR = c and DETAIL = 128; R = 0 (t[0] = 32768) gives BLUR = p.
+ *   State. As "Local statistics", word for word: dst is left exactly as cvh_set_image of those bytes leaves it; src is only read.
+ * cvh_gauss_taps(sigma, taps, radius) is the definition of THE Gaussian of this library (host only, no context; the Python binding
+ * and the command line call it and never restate it): sigma finite, 0 < sigma <= 21; *radius = R = ceil(3 sigma); in double,
+ * e_i = exp(-i^2 / (2 sigma^2)) and S = e_0 + 2 sum_{i >= 1} e_i; taps[i] = floor(32768 e_i / S + 0.5) for i = 1 .. R and taps[0] =
+ * 32768 - 2 sum_{i >= 1} taps[i].  `taps` has room for CVH_SMOOTH_RADIUS_MAX + 1 entries; those behind R are set to 0.  The centre
+ * tap absorbs the rounding residue, so it need not be the largest: at sigma = 21 it is 618 below taps[1] = 623.  That is expected,
+ * and legal.  CVH_ERR_ARG (message in cvh_last_error(NULL)): a sigma outside that range or not finite, a NULL pointer.
+ * The *_batch form takes n pairs (pair i = srcs[i], dsts[i], radius[i], taps[i][0 .. radius[i]], what[CVH_MAX_CHANNELS * i ..]) of any
+ * mix of shapes, channel counts, radii, taps and codes in ONE set of launches on the stream of pair 0's destination, ordered and
+ * waited for as cvh_local_planes_batch.  The single form is the batch with n = 1; a member alone or in any batch gets the same bytes.
+ * How (chan_vese_amd/csrc/smooth_kernels.hip; the two roundings: smooth_math.h): the pairs' taps go up beside the member table, 128
+ * bytes per pair.  The row pass stages a row segment of 1024 columns and R columns on either side in LDS, clamped, and a lane adds
+ * up t[i] (p[x - i] + p[x + i]) for its columns; v goes as 16 bits into a workspace the destination owns (2 bytes per pixel and
+ * plane of the destination, allocated by its first call that takes anything but copies, freed by cvh_destroy; it shares no storage
+ * with the workspaces of the two sections above).  In the column pass a workgroup holds 256 rows of v by 64 columns in LDS (32 KiB):
+ * the 256 - 2 R rows of its band and R rows on either side, clamped; a lane owns a column.  The work per pixel grows linearly with R,
+ * as the median's does; larger scales are what cvh_restrict_image is for.  A call of COPY planes alone launches only the writer and
+ * allocates nothing.
+ * Cost, MEASURED ONCE: one run of tools/smooth_probe.py on an MI355X (profiles/smooth/; host clock around a call and
+ * its wait, 20 calls after 3), BLUR 1 -> 1 at sigma = 1 / 3 / 10 / 21 (R = 3 / 9 / 30 / 63): 84 / 91 / 116 / 134 us at 1024^2, 93 / 103 /
+ * 145 / 184 us at 2048^2, 138 / 176 / 282 / 466 us at 4096^2 -- it grows with R, as said.  cvh_local_planes MEAN at the same R in the
+ * same run: 92 / 97 / 111 / 131, 106 / 111 / 126 / 146 and 151 / 157 / 174 / 203 us: the blur is the cheaper call up to R = 9 and LOSES
+ * from R = 30 on, by 2.3 x at 4096^2 and R = 63.  One CSV iteration of the same plane: 7 / 14 / 67 us.  The round trip the call replaces
+ * (cvh_get_image, scipy's gaussian_filter, cvh_set_image) took 10 - 45 ms, 37 - 188 ms and 0.22 - 0.89 s.
+ * CVH_ERR_ARG: everything cvh_local_planes_batch refuses, with the radius bound 0 .. CVH_SMOOTH_RADIUS_MAX -- NULL lists or members,
+ * n < 1, a context listed more than once across both lists (src == dst included), contexts on different devices, different shapes
+ * within a pair, h*w >= 2^32 --; a `what` entry below C_dst outside 0 .. 2; a NULL list of taps or a NULL entry of it; taps whose
+ * t[0] + 2 sum t[i] is not 32768.  CVH_ERR_STATE: a src without an image.  Checked for every pair before anything is launched; the
+ * message names the pair index and is cvh_last_error(NULL)'s (and pair 0's destination's, once the lists hold no NULL); the contexts
+ * stay usable and their planes unchanged. */
+#define CVH_SMOOTH_COPY   0
+#define CVH_SMOOTH_BLUR   1
+#define CVH_SMOOTH_DETAIL 2
+#define CVH_SMOOTH_RADIUS_MAX 63
+#define CVH_SMOOTH_TAP_SUM 32768
+int cvh_gauss_taps(double sigma, uint16_t *taps /* CVH_SMOOTH_RADIUS_MAX + 1 */, int *radius);
+int cvh_smooth_planes(cvh_context *src, cvh_context *dst, int radius, const uint16_t *taps, const int *what);
+int cvh_smooth_planes_batch(cvh_context *const *srcs, cvh_context *const *dsts, int n,
+                            const int *radius /* n */, const uint16_t *const *taps /* n lists of radius[i] + 1 */,
+                            const int *what /* CVH_MAX_CHANNELS per pair */);
+
 /* ---- Energy ------------------------------------------------------------------------------------------------------------------
  * The library minimises the Chan-Sandberg-Vese functional
  *     E(u) = mu Length + nu Area + (1/C) sum_k [ lambda1_k int (I_k - c1_k)^2 H_eps(u) + lambda2_k int (I_k - c2_k)^2 (1 - H_eps(u)) ];
@@ -1448,7 +1512,8 @@ void cvh_localized_geometry(int h, int w, int radius, int *cols, int *item_rows,
  * This is the edge-stopping function 1 / (1 + |grad I|^2 / K^2) of cvh_perona_malik.  CVH_ERR_ARG: K not finite, K <= 0, den not finite,
  * NULL or differently shaped pairs, different devices; CVH_ERR_STATE: a source without an image.  Smoothing before the gradient is the
  * caller's, with calls that exist: run cvh_perona_malik on the context first, or build the map from a second context that holds
- * cvh_local_planes' mean.  There is no Gaussian here.
+ * cvh_local_planes' mean.  There is no Gaussian in these calls themselves: for the textbook G_sigma * I, build the map from a
+ * context that holds the BLUR planes of cvh_smooth_planes ("Smoothing").
  * The iteration, with nx, ny, H_eps, delta_eps and the border rule exactly those of the two-phase step:
  *     Gx(p) = g(p) nx(p)      Gy(p) = g(p) ny(p)                                      (one rounding each)
  *     kappa_g(r, c) = (c > 0 ? Gx(r, c) - Gx(r, c-1) : 0) + (r > 0 ? Gy(r, c) - Gy(r-1, c) : 0)
