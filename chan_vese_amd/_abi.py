@@ -68,6 +68,12 @@ class MaskScore(C.Structure):
                [("hd2_m", C.c_uint32), ("hd2_t", C.c_uint32), ("defined", C.c_int32), ("pad", C.c_int32)]
 
 
+class ConvexParams(C.Structure):
+    """struct cvh_convex_params ("Convex relaxation" in include/chanvese_hip.h)."""
+    _fields_ = [("tau", C.c_double), ("sigma", C.c_double), ("stop_rms", C.c_double),
+                ("means_every", C.c_int), ("use_edge", C.c_int), ("resume", C.c_int)]
+
+
 class Match(C.Structure):
     """struct cvh_match ("Component overlaps" in include/chanvese_hip.h)."""
     _fields_ = [(f, C.c_uint32) for f in ("objects_a", "objects_b", "tp", "fp", "fn", "pad")]
@@ -234,6 +240,11 @@ SIGNATURES = {
     "cvh_geodesic_run": _sig(_vp, RUN, _dp, TRACE),
     "cvh_geodesic_run_batch": _sig(MARCH_MEMBERS, RUN, _vp, TRACE),
     "cvh_geodesic_geometry": _sig(_int, _int, _ip, _ip, _ip, res=None),
+    "cvh_convex_run": _sig(_vp, _int, C.POINTER(ConvexParams), _ip, _dp, _dp, TRACE),
+    "cvh_convex_run_batch": _sig(MARCH_MEMBERS, _int, C.POINTER(ConvexParams), _ip, _dp, _vp, TRACE),
+    "cvh_get_relaxed": _sig(_vp, _dp, _dp, _dp),
+    "cvh_get_relaxed_device": _sig(_vp, _vp, _vp),
+    "cvh_convex_geometry": _sig(_int, _int, _ip, _ip, _ip, res=None),
 }
 EXPORTS = list(SIGNATURES)
 

@@ -14,7 +14,7 @@ from ._abi import (COLOUR_SPACES, COMPONENT_DTYPE, CONTOUR_LOOP_DTYPE, CVH_OK, E
                    LOCAL_MEAN, LOCAL_RADIUS_MAX, LOCAL_WHATS, MATH_DEFAULT, MATH_FAST, MATH_STRICT, MORPH_CLOSE, MORPH_DILATE, MORPH_ERODE, MORPH_NONE,
                    MORPH_OPEN, MORPH_OPS, OP_DELTA, OP_HEAVISIDE, OP_ONE_MINUS_HEAVISIDE, ORDERS, OVERLAP_DTYPE, RANK_BOTHAT, RANK_CLOSE, RANK_COPY, RANK_MAX,
                    RANK_MEDIAN, RANK_MEDIAN_RADIUS_MAX, RANK_MIN, RANK_OPEN, RANK_RADIUS_MAX, RANK_TOPHAT, RANK_WHATS, REGION_DTYPE, REGION_SHAPE_DTYPE,
-                   SIGNATURES, SMOOTH_BLUR, SMOOTH_COPY, SMOOTH_DETAIL, SMOOTH_RADIUS_MAX, SMOOTH_TAP_SUM, SMOOTH_WHATS, CvhError, EnergyTerms, MaskScore, Match, Params, lib)
+                   SIGNATURES, SMOOTH_BLUR, SMOOTH_COPY, SMOOTH_DETAIL, SMOOTH_RADIUS_MAX, SMOOTH_TAP_SUM, SMOOTH_WHATS, ConvexParams, CvhError, EnergyTerms, MaskScore, Match, Params, lib)
 
 
 @dataclasses.dataclass(frozen=True)
@@ -1127,6 +1127,55 @@ def geodesic_run_batch(contexts, max_steps=-1, trace=False):
                             max_steps, trace)
 
 
+def convex_geometry(h, w):
+    """cvh_convex_geometry: (columns per wave, rows per strip, items) of the fixed partition the convex run's sums are taken over -- the
+    four-phase partition; pure host arithmetic (rows and items are 0 for a plane the calls refuse)."""
+    cols, rows, items = C.c_int(0), C.c_int(0), C.c_int(0)
+    lib().cvh_convex_geometry(int(h), int(w), C.byref(cols), C.byref(rows), C.byref(items))
+    return cols.value, rows.value, items.value
+
+
+def make_convex_params(tau=0.25, sigma=None, stop_rms=0.0, means_every=1, use_edge=False, resume=False):
+    """struct cvh_convex_params ("Convex relaxation" in include/chanvese_hip.h); sigma defaults to 1 / (8 tau), the largest the
+    step-size bound 8 tau sigma <= 1 allows."""
+    tau = float(tau)
+    return ConvexParams(tau, 1.0 / (8.0 * tau) if sigma is None else float(sigma), float(stop_rms), int(means_every), int(bool(use_edge)),
+                        int(bool(resume)))
+
+
+def _convex_params(params):
+    return params if isinstance(params, ConvexParams) else make_convex_params(**dict(params or {}))
+
+
+def convex_run(ctx, max_steps=-1, params=None, trace=False):
+    """cvh_convex_run ("Convex relaxation" in include/chanvese_hip.h): the primal-dual iteration of the relaxed two-phase model from the
+    mask of the context's level set (or, with resume, from the stored relaxation state), until max_steps iterations are done
+    (negative: no bound) or the stop rule of `params` (a ConvexParams, or a dict of make_convex_params' arguments) fires.  Returns
+    (steps_done, norm, trace): trace is None, or with trace=True (all rows; needs max_steps >= 0) or trace=<rows> an array of one row of
+    2 C + 1 doubles per iteration -- the means c1, c2 it used and its norm.  The context's level set becomes v - 0.5."""
+    p = _convex_params(params)
+    want = _trace_rows_wanted(max_steps, trace)
+    done, rows, norm = C.c_int(0), C.c_int(0), C.c_double(0.0)
+    out = _trace_out(want, trace, (2 * ctx.channels + 1,))
+    ctx._chk(lib().cvh_convex_run(ctx._h, int(max_steps), C.byref(p), C.byref(done), C.byref(norm), None if out is None else _dp(out), want,
+                                  C.byref(rows)))
+    return done.value, norm.value, _trace_of(out, rows.value)
+
+
+def convex_run_batch(contexts, max_steps=-1, params=None, trace=False):
+    """cvh_convex_run_batch: convex_run for every context at once -- per iteration one step and one finalise launch for all members of a
+    (channel count, math mode) class.  params is one set for every member or a sequence of one per member.  Every member iterates and
+    stops on its own and is bit for bit what convex_run gives for it alone.  Returns a list of (steps_done, norm, trace), one per member."""
+    contexts = list(contexts)
+    n = len(contexts)
+    each = [_convex_params(q) for q in params] if isinstance(params, (list, tuple)) else [_convex_params(params)] * n
+    if len(each) != n:
+        raise ValueError(f"convex_run_batch: {len(each)} parameter sets for {n} members")
+    table = _array(ConvexParams, n, each)
+    fn = lambda members, count, steps, *rest: lib().cvh_convex_run_batch(members, count, steps, table, *rest)
+    return _march_run_batch("convex_run_batch", fn, (contexts,), lambda k: (), lambda c: (2 * c.channels + 1,), 1, max_steps, trace)
+
+
 def run_monitored(ctx, max_steps=-1, every=16, rel_plateau=None):
     """Context.run in segments of `every` iterations with the energy (Context.energy) taken after each segment.  Returns (total steps,
     last norm, [(steps so far, Energy)]).  max_steps is the total budget (< 0: unlimited); the run ends when the stop rule fired inside
@@ -1409,6 +1458,16 @@ class Context:
         out = np.empty((self.h, self.w), dtype=np.uint16)
         self._chk(self._L.cvh_get_edge_map(self._h, out.ctypes.data))
         return out
+
+    def relaxed(self, duals=False, ptr=0, stream=0):
+        """cvh_get_relaxed / cvh_get_relaxed_device: v of the context's relaxation state as a float64 array of (h, w) -- with duals
+        (v, qx, qy) --, or v written to device memory at `ptr`, ordered behind `stream`."""
+        if ptr:
+            self._chk(self._L.cvh_get_relaxed_device(self._h, int(ptr), _ptr(stream)))
+            return None
+        out = [np.empty((self.h, self.w), dtype=np.float64) for _ in range(3 if duals else 1)]
+        self._chk(self._L.cvh_get_relaxed(self._h, *[_dp(a) for a in out], *([None] * (3 - len(out)))))
+        return tuple(out) if duals else out[0]
 
     def edge_map_from(self, src, K):
         """cvh_edge_map: this context's edge plane from the planes of `src` (may be self) as they are now:

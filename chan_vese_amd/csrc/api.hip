@@ -162,6 +162,8 @@ extern "C" void cvh_destroy(cvh_context *c)
   if (c->d_gq) (void)hipFree(c->d_gq);
   if (c->d_geodesic) (void)hipFree(c->d_geodesic);
   free_table(&c->geo_trace);
+  if (c->d_convex) (void)hipFree(c->d_convex);
+  free_table(&c->cvx_trace);
   free_table(&c->march_table);
   if (c->h_march) (void)hipHostFree(c->h_march);
   if (c->ev_io_in) (void)hipEventDestroy(c->ev_io_in);

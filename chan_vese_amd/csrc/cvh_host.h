@@ -6,7 +6,7 @@
 // level sets), components_run.hip (connected components, and MaskSource: the raw or cleaned mask every mask-derived call starts from),
 // pyramid_run.hip (coarse-to-fine), colour_run.hip (colour spaces), window_run.hip (local statistics, rank planes and smoothing: the windowed-plane calls), energy_run.hip (the functional's terms), score_run.hip (mask scores),
 // morph_run.hip (mask morphology, mask starts), split_run.hip (object split), measure_run.hip (component measures), contour_run.hip (contours), overlap_run.hip
-// (component overlaps), multiphase_run.hip (four phases: a pair of contexts iterated together), localized_run.hip (localised regions), geodesic_run.hip (edge-weighted length), march_run.hip (the driver under those three; march_flow.h: their one call sequence, over each file's flow description), edge_run.hip (the edge plane), debug_exports.hip (diagnostics).  Kernel
+// (component overlaps), multiphase_run.hip (four phases: a pair of contexts iterated together), localized_run.hip (localised regions), geodesic_run.hip (edge-weighted length), convex_run.hip (convex relaxation), march_run.hip (the driver under those four; march_flow.h: their one call sequence, over each file's flow description), edge_run.hip (the edge plane), debug_exports.hip (diagnostics).  Kernel
 // sources do not include it.
 #pragma once
 #include <limits.h>
@@ -201,7 +201,12 @@ struct cvh_context {   // opaque to callers; four groups
   void *d_geodesic = nullptr;    // workspace of cvh_geodesic_run* (geodesic_run.hip): the state block and the items' partial sums: allocated by the
                                  // first call, kept -- not part of live_footprint either
   DeviceTable geo_trace;         // and the trace rows of the longest cvh_geodesic_run so far that asked for them, grown on demand, kept
-  DeviceTable march_table;       // four-phase / localised / geodesic calls led by this context (march_run.hip): the members' argument records and their
+  void *d_convex = nullptr;      // workspace of cvh_convex_run* (convex_run.hip): the state block, the items' partial sums and the relaxation state -- v and
+                                 // two sets of vbar, qx, qy, 56 bytes per pixel: allocated by the first call, kept -- not part of live_footprint either
+  bool have_convex = false;      // a call has completed: the workspace holds a relaxation state, convex_cur names the set that is current.  Assigned
+  int convex_cur = 0;            // in convex_run.hip alone; no other call reads or clears them
+  DeviceTable cvx_trace;         // and the trace rows of the longest cvh_convex_run so far that asked for them, grown on demand, kept
+  DeviceTable march_table;       // four-phase / localised / geodesic / convex calls led by this context (march_run.hip): the members' argument records and their
   void *h_march = nullptr;       // state table; h_march: its pinned host image and the landing place of the states, h_march_cap bytes --
   size_t h_march_cap = 0;        // grown on demand, kept
   int coop_launch = -1;          // does the device launch cooperatively (-1: not asked yet; launches_cooperatively)
@@ -372,6 +377,8 @@ struct MarchRun {
   unsigned char *h_tab = nullptr, *d_tab = nullptr;
   size_t rec_size = 0, state_off = 0, state_stride = 0, dev_bytes = 0, land_off = 0;
   const void *own_state = nullptr;   // n == 1, launches by value: the member's own state block, which comes down in place of the table's slot
+  std::function<int(int k, int done)> bake;   // set: iterate calls it for context k, whose member did `done` iterations, in place of the copy that
+                                              // brings a level set into the buffer a new one lands in -- the flow writes that buffer itself
 
   int begin(int max_steps, double *const *traces, int trace_rows, int *rows);
   int open(const std::function<DeviceTable *(int)> &table_of, const std::function<int(int)> &width_of, size_t rec_size, size_t state_stride);

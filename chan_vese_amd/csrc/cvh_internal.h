@@ -594,6 +594,49 @@ struct CvhGeoArgs {
 hipError_t cvh_launch_geo_sums(const CvhGeoArgs *tab, int nmem, unsigned grid, int parity, int channels, int fast, hipStream_t s, const CvhGeoArgs *one);
 hipError_t cvh_launch_geo_step(const CvhGeoArgs *tab, int nmem, unsigned grid, int parity, int channels, int fast, hipStream_t s, const CvhGeoArgs *one);
 hipError_t cvh_launch_geo_finalize(const CvhGeoArgs *tab, int nmem, int channels, int is_init, hipStream_t s, const CvhGeoArgs *one);
+// convex relaxation (convex_kernels.hip; include/chanvese_hip.h, "Convex relaxation").  The primal-dual iteration of the relaxed
+// two-phase model on the four-phase partition (cvh_mp_geometry).  The relaxation state of a context lives in its workspace:
+//   [state block][the items' rows of partial sums][v][vbar 0][qx 0][qy 0][vbar 1][qx 1][qy 1]      -- 7 planes of h w doubles, 56 bytes per pixel
+// v is updated in place (an iteration reads it at the pixel's own place alone); vbar, qx and qy are double-buffered, because a wave
+// recomputes the dual of its halo column and of the row above its strip from the OLD values.  An item's row of partial sums holds
+// cvh_cvx_nsums(C) doubles:  [0] sum v'   [1 + k] sum I_k v'   [1 + C] sum d^2.
+__host__ __device__ constexpr int cvh_cvx_nsums(int C) { return 2 + C; }
+struct CvhCvxState {
+  CvhMarchCount run;
+  double c1[CVH_MAX_CHANNELS], c2[CVH_MAX_CHANNELS];   // the means the next iteration uses
+  double norm;                     // ||d||_2 of the last executed iteration
+  int since, pad;                  // iterations since the means were last retaken: kept across calls (resume)
+};
+struct CvhCvxBufs { double *vbar, *qx, *qy; };   // one set of the double-buffered planes
+// A member of a convex launch: a record of the device table the kernels read (as CvhMpArgs above)
+struct CvhCvxArgs {
+  CvhCvxBufs u[2];                 // both sets (by value: u[0] read, u[1] written); the start launch writes u[0]
+  double *v;                       // updated in place
+  const double *levelset;          // the start launch: the level set whose mask v0 is
+  const uint8_t *img[CVH_MAX_CHANNELS];
+  const uint16_t *gq;              // the edge plane, or null: g = 1
+  CvhCvxState *st;                 // the member's own state block (its workspace)
+  double *partials;                // [nitems][cvh_cvx_nsums(C)]
+  double *trace;                   // [trace_cap][2C + 1] or null
+  int trace_cap;
+  int h, w;
+  CvhMpGeom g;
+  double tau, sigma, mu, nu;
+  double lambda1[CVH_MAX_CHANNELS], lambda2[CVH_MAX_CHANNELS];
+  double stop;                     // stop_rms sqrt(h w), taken once on the host; negative: no rule
+  double npix, sum_img[CVH_MAX_CHANNELS];   // h w and the exact plane sums
+  int means_every, resume;
+  // what the table form alone reads
+  CvhCvxState *st_mirror;          // the member's slot of the leader's contiguous state table
+  unsigned first;                  // workgroups of the step grid in front of this member's
+};
+// as the four-phase launchers: tab[0 .. nmem-1] the members of ONE (channel count, math mode) class, `one` a host record that travels by
+// value.  start: v0, vbar0 = v0, q = 0 into u[parity] and the sums of v0 (a member with `resume` returns at once); finalize with is_init:
+// the whole state block from those sums, or -- a member with `resume` -- the run counters alone
+hipError_t cvh_launch_cvx_start(const CvhCvxArgs *tab, int nmem, unsigned grid, int parity, int channels, int fast, hipStream_t s, const CvhCvxArgs *one);
+hipError_t cvh_launch_cvx_step(const CvhCvxArgs *tab, int nmem, unsigned grid, int parity, int channels, int fast, hipStream_t s, const CvhCvxArgs *one);
+hipError_t cvh_launch_cvx_finalize(const CvhCvxArgs *tab, int nmem, int channels, int is_init, hipStream_t s, const CvhCvxArgs *one);
+hipError_t cvh_launch_cvx_bake(const double *v, double *u, size_t n, hipStream_t s);   // u = v - 0.5
 // the Sobel edge map (edge_kernels.hip) on the member table: src / src_stride / w2 the planes of the source context and their number,
 // dst the member's edge plane (uint16), den[i] member i's ((64 C) K) K, a table behind the member table; a lane takes a pixel per trip,
 // sections of cvh_edge_blocks(n) workgroups.  The device-pointer forms: a clamped copy in, a plain copy out.

@@ -1,5 +1,5 @@
-// march_flow.h — the ONE call sequence of the marching-wave flows (four phases, localised regions, edge-weighted length) over a flow
-// description F, which multiphase_run.hip, localized_run.hip and geodesic_run.hip each supply and a new march flow has to:
+// march_flow.h — the ONE call sequence of the marching-wave flows (four phases, localised regions, edge-weighted length, convex relaxation) over a flow
+// description F, which multiphase_run.hip, localized_run.hip, geodesic_run.hip and convex_run.hip each supply and a new march flow has to:
 //   types      Args (the record: its fields u, st_mirror, trace, trace_cap by those names), State (begins with CvhMarchCount run), Geom
 //   constants  kStateBytes (the workspace's state section), kSlotBytes (a slot of the leader's state table), kPer (contexts per member),
 //              kWorkspace (its name in messages), kZeroState (no launch in front of iteration 0 writes the state block: zeroed here)
@@ -114,16 +114,18 @@ int march_single(const F &f, const char *what, typename F::Args *m, MarchClass *
 }
 
 // A run of n checked members (MarchRun, cvh_host.h); who(k) opens what a message says about context f.all[k].  steps_done[n], norms
-// (as F::norms_out lays them out), traces[n] / rows[n] may be null
+// (as F::norms_out lays them out), traces[n] / rows[n] may be null.  bake(k, done), if given, brings context k's level set into the buffer a new
+// one lands in itself (MarchRun::bake): a flow whose iterated planes are not the level set
 template <class F>
 int march_run(const F &f, int n, int max_steps, int *steps_done, double *norms, double *const *traces, int trace_rows, int *rows, const char *what,
-              const std::function<std::string(int)> &who)
+              const std::function<std::string(int)> &who, const std::function<int(int, int)> &bake = nullptr)
 {
   using Args = typename F::Args;
   cvh_context *const *all = f.all;
   cvh_context *lead = all[0];
   auto first_of = [&](int i) { return all[(size_t)i * F::kPer]; };
   MarchRun run{all, n, F::kPer, what, who};
+  run.bake = bake;
   int rc = run.begin(max_steps, traces, trace_rows, rows);
   if (rc != CVH_OK) return rc;
   std::vector<typename F::Geom> g((size_t)n);

@@ -1,5 +1,5 @@
-// march_run.hip — the host driver under the marching-wave calls: cvh_multiphase_run[_batch], cvh_localized_run[_batch] and
-// cvh_geodesic_run[_batch] (MarchRun, cvh_host.h; the call sequence around it, written once over a flow description, is march_flow.h's).
+// march_run.hip — the host driver under the marching-wave calls: cvh_multiphase_run[_batch], cvh_localized_run[_batch],
+// cvh_geodesic_run[_batch] and cvh_convex_run[_batch] (MarchRun, cvh_host.h; the call sequence around it, written once over a flow description, is march_flow.h's).
 // The level sets of N members (contexts, or pairs of contexts) are iterated together on the leader's stream; a single call is a batch
 // of one member.
 // Data flow: the leader's table holds one argument record per member -- both buffers of every level set in it -- and one state slot
@@ -166,7 +166,8 @@ int MarchRun::iterate(const std::function<int(int parity)> &step)
     for (int e = 0; e < per; ++e) {
       cvh_context *c = ctxs[(size_t)i * per + e];
       const int from = (cur[(size_t)i * per + e] + done) & 1, to = c->chain_pb & 1;
-      if (from != to) HIPCHK(a, hipMemcpyAsync(c->d_u[to], c->d_u[from], c->n * sizeof(double), hipMemcpyDeviceToDevice, a->stream));
+      if (bake) { const int rc = bake(i * per + e, done); if (rc != CVH_OK) return rc; }
+      else if (from != to) HIPCHK(a, hipMemcpyAsync(c->d_u[to], c->d_u[from], c->n * sizeof(double), hipMemcpyDeviceToDevice, a->stream));
       HIPCHK(a, clear_run_device(c, a->stream));
     }
     nrows[i] = std::min(done, trace_cap[i]);

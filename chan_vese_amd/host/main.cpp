@@ -57,6 +57,9 @@
 // The stages, in main()'s order: read_options (options.hpp), load_inputs, the parameters, then either run_four_phase or make_run,
 // the first start, the t = 0 frame, smooth_and_write_pm, convert_colour, iterate, the reports, split_objects (--split) or the morph
 // bake, and the mask outputs.
+// --convex TAU[,SIGMA] with --convex-means M and --convex-stop S runs the convex relaxation of the two-phase model by primal-dual
+// iterations from the mask of the start (chanvese_hip.h, "Convex relaxation": cvh_convex_run in place of cvh_run), with --edge K the
+// weighted model on the edge map; the level set written is v - 1/2.
 #include <algorithm>
 #include <cerrno>
 #include <cmath>
@@ -495,7 +498,10 @@ Progress iterate(const Run &run, const Options &opt, const Inputs &in, Frames &f
       cvh_check(ctx, cvh_get_edge_map(ctx, gq.data()), "cvh_get_edge_map");
       write_raw_or_exit(opt.dump_edge, gq.data(), in.n * sizeof(uint16_t));
     }
-    cvh_check(ctx, cvh_geodesic_run(ctx, opt.steps(), &p.steps, &p.norm, nullptr, 0, nullptr), "cvh_geodesic_run");
+    if (opt.convex) cvh_check(ctx, cvh_convex_run(ctx, opt.steps(), &opt.convex_params, &p.steps, &p.norm, nullptr, 0, nullptr), "cvh_convex_run");
+    else cvh_check(ctx, cvh_geodesic_run(ctx, opt.steps(), &p.steps, &p.norm, nullptr, 0, nullptr), "cvh_geodesic_run");
+  } else if (opt.convex) {
+    cvh_check(ctx, cvh_convex_run(ctx, opt.steps(), &opt.convex_params, &p.steps, &p.norm, nullptr, 0, nullptr), "cvh_convex_run");
   } else if (!opt.video) {
     cvh_check(ctx, cvh_run(ctx, opt.steps(), &p.steps, &p.norm), "cvh_run");
   } else {

@@ -42,7 +42,8 @@ const Spec kSpecs[] = {
     {"phases", 0, 1}, {"init2", 0, 2}, {"dump-labels", 0, 1}, {"localized", 0, 1}};
 // what came after the table above and the --help text were pinned (tests/test_cli.py, tests/golden/cli_refusals.json): long names only,
 // listed by --help --verbose
-const Spec kLaterSpecs[] = {{"split", 0, 1}, {"split-labels", 0, 1}, {"edge", 0, 1}, {"dump-edge", 0, 1}, {"smooth", 0, 1}, {"smooth-sigma", 0, 1}, {"edge-sigma", 0, 1}};
+const Spec kLaterSpecs[] = {{"split", 0, 1}, {"split-labels", 0, 1}, {"edge", 0, 1}, {"dump-edge", 0, 1}, {"smooth", 0, 1}, {"smooth-sigma", 0, 1}, {"edge-sigma", 0, 1},
+                            {"convex", 0, 1}, {"convex-means", 0, 1}, {"convex-stop", 0, 1}};
 
 struct Parsed {
   std::vector<std::pair<std::string, std::vector<std::string>>> opts;
@@ -216,6 +217,9 @@ struct Options {
   std::string dump_u, dump_mask, dump_planes, dump_labels, measure, contours, truth, truth_labels, init_mask, split_labels, dump_edge;
   int device = 0, math_mode = CVH_MATH_FAST, state_bits = 64, reinit_every = 0, levels = 1, energy_every = 0, phases = 2, localized = 0;
   double edge = 0.0;   // --edge K: > 0 where given
+  // --convex TAU[,SIGMA] with --convex-means M and --convex-stop S (chanvese_hip.h, "Convex relaxation"): cvh_convex_run in place of cvh_run
+  bool convex = false;
+  cvh_convex_params convex_params = {0.25, 0.5, 0.0, 1, 0, 0};
   // --smooth blur|detail with --smooth-sigma S, and --edge-sigma S: the taps are cvh_gauss_taps' (chanvese_hip.h, "Smoothing")
   bool smooth = false;
   double smooth_sigma = 1.0, edge_sigma = 0.0;   // edge_sigma > 0 where given
@@ -289,7 +293,7 @@ inline Options read_options(const Parsed &vm)
   auto given = [&](const char *n) { return vm.count(n) > 0; };
   const ReadOne read{vm};
   std::string text_position = "TL", line_color = "blue", math = "fast", rect, circ, disk, init_kind = "checkerboard", colorspace, local_name,
-              rank_name, morph_name, smooth_name;
+              rank_name, morph_name, smooth_name, convex_steps;
   double morph_radius = 1.0, score_tol = 2.0, split_radius = 0.0;
   int threshold = -1;
   read("input", o.input);
@@ -352,6 +356,10 @@ inline Options read_options(const Parsed &vm)
   read("smooth", smooth_name);      // --smooth blur|detail (chanvese_hip.h, "Smoothing"): cvh_smooth_planes behind --rank, in front of --local
   read("smooth-sigma", o.smooth_sigma);
   read("edge-sigma", o.edge_sigma);  // --edge-sigma S: the edge map of --edge is built from a blurred scratch copy of the planes
+  read("convex", convex_steps);      // --convex TAU[,SIGMA]: the primal and the dual step; sigma defaults to 1 / (8 tau)
+  read("convex-means", o.convex_params.means_every);
+  read("convex-stop", o.convex_params.stop_rms);
+  o.convex = given("convex");
   o.segment = given("segment"); o.grayscale = given("grayscale"); o.video = given("video"); o.overlay_text = given("overlay-text");
   o.select = given("select"); o.roi = given("roi"); o.energy = given("energy"); o.verbose = given("verbose");
   o.contours_all = given("contours-all"); o.contours_subpixel = given("contours-subpixel");
@@ -491,6 +499,23 @@ inline Options read_options(const Parsed &vm)
         {o.phases == 4, "four phases (--phases 4)"}, {o.localized != 0, "localised regions (--localized)"}, {o.levels > 1, "a coarse-to-fine run (--levels)"},
         {o.energy, "an energy line (--energy)"}, {o.energy_every > 0, "an energy series (--energy-every)"},
         {o.reinit_every > 0, "reinitialisation (--reinit)"}, {o.video, "video output (-V)"}, {o.state_bits == 32, "FP32 state (--state 32)"}});
+  // --convex (chanvese_hip.h, "Convex relaxation"): the relaxed model from the mask of the start; with --edge K the weighted model
+  if ((given("convex-means") || given("convex-stop")) && !o.convex) msg_exit("The options --convex-means and --convex-stop need a convex run (--convex).");
+  if (o.convex) {
+    cvh_convex_params &q = o.convex_params;
+    const size_t comma = convex_steps.find(',');
+    q.tau = to_double("convex", convex_steps.substr(0, comma));
+    q.sigma = comma == std::string::npos ? 1.0 / (8.0 * q.tau) : to_double("convex", convex_steps.substr(comma + 1));
+    if (!(q.tau > 0.0) || !std::isfinite(q.tau) || !(q.sigma > 0.0) || !std::isfinite(q.sigma) || !(8.0 * q.tau * q.sigma <= 1.0))
+      msg_exit("Convex steps (--convex TAU[,SIGMA]) must be finite numbers > 0 with 8 TAU SIGMA <= 1: " + convex_steps + ".");
+    if (q.means_every < 0) msg_exit("Means interval (--convex-means) cannot be negative: " + std::to_string(q.means_every) + ".");
+    if (std::isnan(q.stop_rms)) msg_exit("Stop level (--convex-stop) must be a number (negative: no stop rule).");
+    q.use_edge = given("edge") ? 1 : 0;
+    refuse_combinations("Convex relaxation (--convex)", {
+        {o.phases == 4, "four phases (--phases 4)"}, {o.localized != 0, "localised regions (--localized)"}, {o.levels > 1, "a coarse-to-fine run (--levels)"},
+        {o.energy, "an energy line (--energy)"}, {o.energy_every > 0, "an energy series (--energy-every)"},
+        {o.reinit_every > 0, "reinitialisation (--reinit)"}, {o.video, "video output (-V)"}, {o.state_bits == 32, "FP32 state (--state 32)"}});
+  }
   if (given("score-tol") && o.truth.empty()) msg_exit("A score tolerance (--score-tol) needs a ground truth (--truth).");
   if (!(score_tol >= 0.0) || !std::isfinite(score_tol)) msg_exit("Score tolerance must be a finite number >= 0.");
   o.score_tol2 = squared_capped(score_tol);
@@ -637,5 +662,14 @@ inline void print_help(bool later = false)
       "  --smooth-sigma arg (=1)            sigma of that Gaussian, 0 < sigma <= 21 (its radius is ceil(3 sigma))\n"
       "  --edge-sigma arg                   sigma, 0 < sigma <= 21: --edge builds its map from a Gaussian-blurred scratch copy of the planes,\n"
       "                                     g = 1 / (1 + |grad (G_sigma * I)|^2 / K^2), while the run iterates on the unblurred planes\n"
+      "  --convex arg                       TAU[,SIGMA]: the convex relaxation of the two-phase model by primal-dual iterations from the mask of\n"
+      "                                     the start -- for fixed means the result does not depend on it; the steps need 8 TAU SIGMA <= 1, SIGMA\n"
+      "                                     defaults to 1 / (8 TAU); --mu, --nu, --lambda1, --lambda2 apply (scale the lambdas to about 1e-3), --dt,\n"
+      "                                     -e and -t do not; honours --init / --rect / --circ / --disk / --init-mask / --threshold, and with\n"
+      "                                     --edge K weighs the length by the edge map; the level set written is v - 1/2; not with --phases 4,\n"
+      "                                     --localized, --levels, --energy, --energy-every, --reinit, -V, --state 32\n"
+      "  --convex-means arg (=1)            retake the region means after every arg iterations (0: never after the start)\n"
+      "  --convex-stop arg (=0)             stop once the root mean square of the update is at most arg (0: at an exact fixed point; negative:\n"
+      "                                     never); -N stays the bound\n"
       "\n";
 }

@@ -174,6 +174,30 @@ def check_smooth(smooth, channels):
     return _check_window(smooth, "smooth", channels, capi.smooth_what_codes, lambda k, _: capi.smooth_kernel(k), radius_first=True)
 
 
+def check_convex(convex):
+    """Validates Segmenter's `convex` -- tau, (tau, sigma), or a dict of capi.make_convex_params' arguments but use_edge and resume -- and
+    returns the dict, or None for None.  sigma defaults to 1 / (8 tau)."""
+    if convex is None:
+        return None
+    if isinstance(convex, dict):
+        out = dict(convex)
+        if set(out) - {"tau", "sigma", "stop_rms", "means_every"}:
+            raise ValueError(f"convex: unknown keys {sorted(set(out) - {'tau', 'sigma', 'stop_rms', 'means_every'})} (tau, sigma, stop_rms, means_every)")
+    elif isinstance(convex, tuple) and len(convex) == 2:
+        out = dict(tau=convex[0], sigma=convex[1])
+    else:
+        out = dict(tau=convex)
+    tau, sigma = out.get("tau", 0.25), out.get("sigma")
+    for name, x in (("tau", tau), ("sigma", sigma)):
+        if x is None and name == "sigma":
+            continue
+        if isinstance(x, bool) or not isinstance(x, (int, float)) or not math.isfinite(x) or x <= 0:
+            raise ValueError(f"convex must be None, tau, (tau, sigma) or a dict with finite steps > 0, got {name} = {x!r}")
+    if sigma is not None and 8.0 * tau * sigma > 1.0:
+        raise ValueError(f"convex: 8 tau sigma must not exceed 1, got tau = {tau!r}, sigma = {sigma!r}")
+    return out
+
+
 def check_edge_sigma(edge_sigma, edge):
     """Validates Segmenter's `edge_sigma` and returns its (radius, taps), or None for None.  It needs edge=K."""
     if edge_sigma is None:
@@ -229,6 +253,11 @@ class Segmenter:
     planes as they stand after the preprocessing above (cvh_edge_map_batch with that K) and iterate with cvh_geodesic_run_batch -- the
     length term weighted by the plane -- instead of the two-phase run; edge_maps() returns the planes.  It needs phases = 2, levels = 1 and
     no localized=, and segment() refuses energy_every and reinit_every with it.  None (the default) is the plain path, call for call.
+    convex = tau, (tau, sigma) or a dict of tau, sigma, stop_rms, means_every (include/chanvese_hip.h, "Convex relaxation"; sigma defaults
+    to 1 / (8 tau), stop_rms to 0, means_every to 1) makes segment() run the primal-dual iteration of the convex relaxation from the mask
+    of the start (cvh_convex_run_batch) instead of a level-set descent: the result does not depend on the start for fixed means.  With
+    edge=K it runs the weighted model on the edge planes the map stage builds; relaxed() returns v.  It needs phases = 2, levels = 1 and
+    no localized=; reinit_every and energy_every are refused.
     edge_sigma = sigma (0 < sigma <= 21; needs edge=K) builds the edge plane from G_sigma * I, the textbook edge function: every member's
     planes, as the preprocessing left them, are blurred into scratch contexts (`edge_sources`; cvh_smooth_planes_batch) and
     cvh_edge_map_batch takes those as its sources, while the run iterates on the unblurred planes.  None: the map is built from the
@@ -237,6 +266,7 @@ class Segmenter:
     phases = 2
     localized = None
     edge = None
+    convex = None
     contexts_b = ()
     colour = None
     local = None
@@ -254,9 +284,12 @@ class Segmenter:
         return self.local[2] if self.local else self.smooth[2] if self.smooth else self.rank[2] if self.rank else self.channels
 
     def __init__(self, n, h, w, channels=1, params=None, device=0, options=None, levels=1, colour=None, order="rgb", local=None, rank=None,
-                 phases=2, params2=None, localized=None, edge=None, smooth=None, edge_sigma=None):
+                 phases=2, params2=None, localized=None, edge=None, smooth=None, edge_sigma=None, convex=None):
         if n < 1:
             raise ValueError(f"n must be >= 1, got {n}")
+        self.convex = check_convex(convex)
+        if self.convex is not None and (phases == 4 or levels != 1 or localized is not None):
+            raise ValueError("convex= needs phases = 2, levels = 1 and no localized=: the relaxation iterates one function v on one level")
         if edge is not None:
             if isinstance(edge, bool) or not isinstance(edge, (int, float)) or not math.isfinite(edge) or edge <= 0:
                 raise ValueError(f"edge must be None or a finite K > 0, got {edge!r}")
@@ -463,6 +496,8 @@ class Segmenter:
             raise ValueError("localized=: reinit_every and energy_every are not built for the localised run")
         if self.edge is not None and (reinit_every or energy_every):
             raise ValueError("edge=: reinit_every and energy_every are not built for the edge-weighted run")
+        if self.convex is not None and (reinit_every or energy_every):
+            raise ValueError("convex=: reinit_every and energy_every are not built for the relaxation (it has no level set to reinitialise)")
         kind, bits = None, None
         mask_init = isinstance(init, tuple) and len(init) == 2 and init[0] == "mask"
         if mask_init and self.levels > 1:
@@ -542,12 +577,27 @@ class Segmenter:
             if self.edge_kernel:   # g from G_sigma * I; the run keeps the unblurred planes
                 capi.smooth_planes_batch(self.contexts, self.edge_sources, [int(t) for t in self.edge_kernel[1]], "blur")
             capi.edge_map_batch(self.contexts, self.edge_sources or self.contexts, self.edge)
-            res = [r[:2] for r in capi.geodesic_run_batch(self.contexts, max_steps)]
+            if self.convex is not None:   # the weighted relaxation: rho = mu g
+                res = [r[:2] for r in capi.convex_run_batch(self.contexts, max_steps, dict(self.convex, use_edge=True))]
+            else:
+                res = [r[:2] for r in capi.geodesic_run_batch(self.contexts, max_steps)]
+        elif self.convex is not None:
+            res = [r[:2] for r in capi.convex_run_batch(self.contexts, max_steps, self.convex)]
         else:
             res = capi.run_batch_with_reinit(self.contexts, max_steps, reinit_every)
         masks = torch.empty((self.n, self.h, self.w), dtype=torch.uint8, device=images.device)
         capi.get_mask_device_batch(self.contexts, [masks[i].data_ptr() for i in range(self.n)], invert, stream)
         return masks, [r[0] for r in res], [r[1] for r in res]
+
+    def relaxed(self):
+        """convex=: the members' relaxed functions v as the last segment() left them, a float64 device tensor (N, H, W) with values in
+        [0, 1] (cvh_get_relaxed_device), valid for the next operation on the current stream; the masks are v > 1/2."""
+        if self.convex is None:
+            raise ValueError("relaxed needs convex=")
+        out = torch.empty((self.n, self.h, self.w), dtype=torch.float64, device=torch.device("cuda", self.device))
+        for i, ctx in enumerate(self.contexts):
+            ctx.relaxed(ptr=out[i].data_ptr(), stream=self._stream())
+        return out
 
     def edge_maps(self):
         """edge=: the members' edge planes as the last segment() built them, a uint16 device tensor (N, H, W), g = value / 32768

@@ -1552,6 +1552,75 @@ int cvh_geodesic_run_batch(cvh_context *const *ctxs, int n, int max_steps, int *
                            double *const *traces /* n or NULL */, int trace_rows, int *rows /* n */);
 void cvh_geodesic_geometry(int h, int w, int *cols, int *strip_rows, int *items);   /* pure host arithmetic; 0 rows / items: not a plane the calls take */
 
+/* ---- Convex relaxation -------------------------------------------------------------------------------------------------------------
+ * The convex relaxation of two-phase Chan-Vese (Chan, Esedoglu and Nikolova), solved by the primal-dual iteration of Chambolle and
+ * Pock; with an edge plane it is the weighted model of Bresson et al.  Every other flow of this library descends on a level set and
+ * ends in a minimum that depends on the start.  Here, for fixed means, a function v with 0 <= v <= 1 takes the place of H(u), the
+ * problem in v is convex, and any threshold of a minimiser is a global minimiser of the two-phase functional: no eps, no delta
+ * function, no reinitialisation.  The reference has no such model; the definitions below ARE the contract.
+ * STATE.  A context gets a relaxation state in a workspace it owns, allocated by the first call and kept: v, the extrapolated vbar and
+ * the dual field q = (qx, qy), h w doubles each, row-major; vbar, qx and qy are double-buffered (a wave recomputes halo values from the
+ * old ones), v is updated in place: 7 planes, 56 bytes per pixel.  No other call reads or clears it.
+ * START (resume = 0): v0 = 1 where (float)u > 0, else 0 -- the bytes of cvh_get_mask with invert = 0 --, vbar0 = v0, q = 0.  The sums of
+ * v0 and of f_k v0 are exact integers in any order, so the first means are bit-defined.
+ * ONE ITERATION, everything taken from the old v, vbar and q (Jacobi); f_k = plane k, tau and sigma the call's, mu, nu, lambda1[k],
+ * lambda2[k] the context's as they are now (dt and eps are not read), C the channel count.  In STRICT mode the operation order is
+ * exactly this, one rounding per operation and no contraction:
+ *     a_k = f_k - c1[k];  b_k = f_k - c2[k];  t_k = lambda1[k] (a_k a_k) - lambda2[k] (b_k b_k)
+ *     r   = nu + ((t_0 + t_1) + t_2) / C                                  (C = 1: nu + t_0)
+ *     dx  = c < w-1 ? vbar(r, c+1) - vbar(r, c) : 0;   dy = r < h-1 ? vbar(r+1, c) - vbar(r, c) : 0
+ *     tx  = qx + sigma dx;  ty = qy + sigma dy;  s = sqrt(tx tx + ty ty);  rho = mu g        (g = gq 2^-15, or 1 with use_edge = 0)
+ *     s > rho ?  k = rho / s, qx' = tx k, qy' = ty k   :   qx' = tx, qy' = ty
+ *     div = (qx' - (c > 0 ? qx'(r, c-1) : 0)) + (qy' - (r > 0 ? qy'(r-1, c) : 0))
+ *     x   = v + tau (div - r);   v' = x < 0 ? 0 : (x > 1 ? 1 : x)                          (a NaN stays a NaN: no guard, as elsewhere)
+ *     vbar' = (v' + v') - v;     d = v' - v
+ * MEANS.  c1[k] = sum f_k v / sum v, c2[k] = (sum f_k - sum f_k v) / (h w - sum v), the complement as the geodesic flow takes it, no
+ * guard.  They are taken at the start and retaken after every means_every-th iteration (means_every = 0: never after the start); the
+ * count since the last retake belongs to the state and goes on across resumed calls.  Row t of the trace (2 C + 1 doubles, at most
+ * trace_rows rows, *rows written) is [c1[0..C), c2[0..C), ||d||_2]: the means iteration t used and its norm.
+ * STOP.  The run stops after the iteration with ||d||_2 <= stop_rms sqrt(h w), the product taken once on the host; stop_rms < 0: no
+ * rule; stop_rms = 0 stops at an exact fixed point alone (the noisy disk of tests/convex_util.py reaches one in 5 iterations, every v in {0, 1}; the
+ * harder demonstration scenes were run with stop_rms = 1e-5).  The stopping iteration is kept,
+ * later launches return at once.  cvh_get_stop_condition is in grey-level units and is not used here.  max_steps < 0: no bound.
+ * RESUME (resume = 1) continues the stored v, vbar, q, the means and the count since the last retake with the planes and parameters as
+ * they are now, and does not read the level set: m + n iterations in one call equal m then n (resumed) bit for bit, in both math modes
+ * and for any means_every.
+ * END of every call: the level set becomes u = v - 0.5, one rounding per pixel, and the context is left exactly as cvh_set_levelset of
+ * those doubles leaves it: the mask calls, components, contours, scores, cvh_reinit and further level-set iterations see the
+ * thresholded result; a two-phase run continued afterwards is bit for bit what it is after cvh_set_levelset of the fetched doubles.
+ * "math_mode": STRICT follows the lines above -- with means_every = 0 every value is bit-defined, and v, qx, qy equal a numpy
+ * restatement (tests/convex_util.py) bit for bit; FAST uses fused multiply-adds and the refined reciprocal square root in the
+ * projection (taken where tx tx + ty ty > rho rho).  Otherwise both agree with the restatement to 1e-9.
+ * Determinism: partial sums per ITEM of the four-phase partition (cvh_convex_geometry: strips of *strip_rows rows x *cols columns,
+ * *items of them, a function of h and w alone) added in a fixed order by a one-workgroup launch; no atomics.  Two runs give the same
+ * bits.  The host enqueues "sync_every" iterations at a time (two launches each) and waits once per chunk.
+ * cvh_convex_run_batch runs n contexts, member i with params[i], in shared launches with the meaning, the guarantees (a member is bit
+ * for bit its own single run, for any mix of shapes, channel counts, parameters and modes, in any order; members stop on their own),
+ * the launches and the refusals of cvh_geodesic_run_batch; a batch of one launches the single call's by-value kernels.
+ * cvh_get_relaxed copies v and the current qx, qy to host memory (any pointer may be NULL); cvh_get_relaxed_device copies v to device
+ * memory (8-byte aligned), ordered against `stream` by events as the other _device calls, without a host wait.
+ * CVH_ERR_ARG: NULL params; tau or sigma not finite or <= 0; 8 tau sigma > 1 (the step-size bound of the forward-difference gradient);
+ * a NaN stop_rms; means_every < 0; "state" = 32; h*w >= 2^28; a trace without rows or with trace_rows < 0; and for the batch what
+ * cvh_geodesic_run_batch refuses.  CVH_ERR_STATE: no image; no level set with resume = 0; no relaxation state with resume = 1, or in
+ * cvh_get_relaxed*; no edge plane with use_edge = 1.  Everything is checked before anything is touched; after a refusal the contexts
+ * are as they were.
+ * Not here: the primal-dual gap or a relaxed energy, FP32 dual state, the resident flow, four-phase or localised convex models,
+ * pyramids inside the run. */
+typedef struct cvh_convex_params {
+  double tau, sigma;                /* primal and dual step: finite, > 0, 8 tau sigma <= 1 */
+  double stop_rms;                  /* stop at ||d||_2 <= stop_rms sqrt(h w); < 0: no rule */
+  int means_every;                  /* retake the means after every means_every-th iteration; 0: never after the start */
+  int use_edge;                     /* 1: rho = mu g with the context's edge plane */
+  int resume;                       /* 1: continue the stored relaxation state */
+} cvh_convex_params;
+int cvh_convex_run(cvh_context *ctx, int max_steps, const cvh_convex_params *params, int *steps_done, double *norm, double *trace, int trace_rows,
+                   int *rows);
+int cvh_convex_run_batch(cvh_context *const *ctxs, int n, int max_steps, const cvh_convex_params *params /* n */, int *steps_done /* n */,
+                         double *norms /* n */, double *const *traces /* n or NULL */, int trace_rows, int *rows /* n */);
+int cvh_get_relaxed(cvh_context *ctx, double *v, double *qx, double *qy);   /* host, h w doubles each; any may be NULL */
+int cvh_get_relaxed_device(cvh_context *ctx, double *d_v, void *stream);
+void cvh_convex_geometry(int h, int w, int *cols, int *strip_rows, int *items);   /* pure host arithmetic; 0 rows / items: not a plane the calls take */
+
 /* Library version string, e.g. "chanvese_hip 0.1 (gfx950)". */
 const char *cvh_version(void);
 
